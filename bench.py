@@ -7,7 +7,9 @@ produced) + for N > 1 the single RCCL all-reduce of the per-GPU counts.  One pro
 nccl == RCCL); the buffer is sharded by contiguous 32 GiB chunk per rank (weak scaling), each rank generates its own shard
 in HBM with the counter-based generator at global offset rank*shard.
 
-    python bench.py                      # N = 1: literal8 + (extra) memchr1 and ac1000, roofline + cpu_baseline
+    python bench.py                      # N = 1: literal8 only: set-up, warm-up, the timed steps, the line (roofline from their events)
+    python bench.py --full               # ... + the in-run correctness gate, cpu_baseline, and (N = 1) the extra workloads
+    python bench.py --dump-outputs DIR   # ... + what the last timed step returned, as DIR/<name>.npy (dump_outputs())
     python bench.py --gpus 8             # spawns the 8 ranks itself (torch.distributed.run on 127.0.0.1) ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 ... bench.py --gpus 8     # ... or is launched as ranks
     python bench.py --gpus 2 --backend gloo   # CPU dry run of the launcher / collective plumbing (no scan, no number)
@@ -404,6 +406,35 @@ def verify_step(name, wl, eng, plan, buf, pos, out, n, text_len, shard_off, worl
                   f"(oracle/_ref) in its emission order; self-consistent beside it: {stored} records == count-only scan, "
                   f"(end, longest-first) order, lengths in the dictionary's range")
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_RECORDS_MAX = 3_500_000  # 56 MB of float64 (start, end) pairs: every record of the default line (literal8, 32 GiB: 3.44 M)
+DUMP_SAMPLE = 2_000_000       # above that, a sample of this many records and their indices: 48 MB
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, out, pos, reduced, rank, world):
+    """What the timed path handed its caller in its last step, as float64 .npy files (offsets below 2**53 are exact):
+    counts.npy = [count, total_matches, stored] of the scan; records.npy = its (start, end) records in the order returned, all of
+    them up to DUMP_RECORDS_MAX, else a fixed seeded sample of DUMP_SAMPLE whose indices are record_index.npy; with N > 1 ranks,
+    counts_allreduced.npy = [count, total_matches] summed over the ranks, and every file name carries _rank<r>."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    stored = int(out.stored)
+    rec = pos[: 2 * stored].view(-1, 2)
+    files = {"counts": np.array([int(out.count), int(out.total_matches), stored], dtype=np.float64)}
+    if stored > DUMP_RECORDS_MAX:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(stored, DUMP_SAMPLE, replace=False))
+        rec = rec[torch.from_numpy(idx).to(rec.device)]
+        files["record_index"] = idx.astype(np.float64)
+    files["records"] = rec.cpu().numpy().astype(np.float64)
+    if reduced is not None:
+        files["counts_allreduced"] = np.array(reduced, dtype=np.float64)
+    for k, v in files.items():
+        np.save(os.path.join(out_dir, f"{k}{sfx}.npy"), v)
+
+
 # ---------------------------------------------------------------------------------------------- one workload on this rank
 def positions_capacity(name, n):
     wl = WORKLOADS[name]
@@ -411,9 +442,10 @@ def positions_capacity(name, n):
     return int(n * density * 1.25) + 4096
 
 
-def run_workload(name, args, eng, buf, pos, dev, rank, world, local, use_dist):
+def run_workload(name, args, eng, buf, pos, dev, rank, world, local, use_dist, verify=False, dump_dir=None):
     """Generates the rank's shard, runs warmup + EXACTLY args.steps timed steps (barrier + synchronize on both sides, MAX over
-    ranks) and returns the measurement dict (rank 0) incl. the roofline object of the dominant kernel."""
+    ranks) and returns the measurement dict (rank 0) incl. the roofline object of the dominant kernel.  After the timed steps:
+    the last step's outputs to `dump_dir` (dump_outputs()), then, with `verify`, the in-run correctness gate (verify_step())."""
     import torch
     import torch.distributed as dist
     from krep_amd import abi
@@ -476,14 +508,19 @@ def run_workload(name, args, eng, buf, pos, dev, rank, world, local, use_dist):
         total_matches = int(out.total_matches)
     assert not out.overflow, "position buffer too small"
     stored = int(out.stored)
-    try:
-        verified, how = verify_step(name, wl, eng, plan, buf, pos, out, n, text_len, shard_off, world)
-    except Exception as e:
-        verified, how = False, f"verification failed to run: {e!r}"
-    if use_dist:
-        v = torch.tensor([1 if verified else 0], dtype=torch.int32, device=dev)
-        dist.all_reduce(v, op=dist.ReduceOp.MIN)  # every rank checks its own shard
-        verified = bool(int(v.item()))
+    if dump_dir:
+        dump_outputs(dump_dir, out, pos, (reduced if use_dist == "c" else counts.tolist()) if use_dist else None, rank, world)
+    checked = {}
+    if verify:
+        try:
+            verified, how = verify_step(name, wl, eng, plan, buf, pos, out, n, text_len, shard_off, world)
+        except Exception as e:
+            verified, how = False, f"verification failed to run: {e!r}"
+        if use_dist:
+            v = torch.tensor([1 if verified else 0], dtype=torch.int32, device=dev)
+            dist.all_reduce(v, op=dist.ReduceOp.MIN)  # every rank checks its own shard
+            verified = bool(int(v.item()))
+        checked = {"verified": verified, "verified_how": how}
     plan.close()
     if rank != 0:
         return None
@@ -492,7 +529,7 @@ def run_workload(name, args, eng, buf, pos, dev, rank, world, local, use_dist):
     k_avg, k_med = sum(k_ms) / len(k_ms), statistics.median(k_ms)
     achieved = n / (k_avg * 1e-3) / 1e9
     return {
-        "wl": wl, "collective": use_dist if use_dist else None, "verified": verified, "verified_how": how,
+        "wl": wl, "collective": use_dist if use_dist else None, **checked,
         "value": round(value, 1), "ms_per_step": round(ms_step, 4), "matches": total_matches,
         "matches_per_s": round(total_matches / (dt / args.steps), 1),
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -569,13 +606,19 @@ def main():
     # the headline.
     ap.add_argument("--placement-tries", type=int, default=1,
                     help="candidate blocks (haystack + record buffer) krep_gpu_alloc_placed() draws from (1 = the first allocation as it comes)")
-    ap.add_argument("--no-extra", action="store_true", help="N = 1: do not measure the other two BASELINE workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="also the in-run correctness gate, cpu_baseline and (N = 1) the extra workloads; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most ~64 MB)")
+    ap.add_argument("--no-extra", action="store_true", help="--full, N = 1: do not measure the other BASELINE workloads")
     ap.add_argument("--cpu-sample-gib", type=float, default=4.0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo = CPU dry run of the plumbing")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and all-reduce even with one rank (self-test)")
     ap.add_argument("--collective", default="c", choices=["c", "torch"],
                     help="who issues the count all-reduce: the C library's own RCCL communicator (default) or torch.distributed")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)
@@ -623,6 +666,7 @@ def main():
     global SCAN_STREAM
     SCAN_STREAM = torch.cuda.Stream(device=dev)
     n = int(args.gib * (1 << 30))
+    # (sized for the extra workloads also without --full: the headline's buffers are allocated exactly as in a --full run)
     names = [args.workload] + ([w for w in ("literal8", "memchr1", "ac1000", "words1000") if w != args.workload]
                                if (world == 1 and not args.no_extra) else [])
     pos_words = 2 * max(positions_capacity(w, n) for w in names)
@@ -652,7 +696,8 @@ def main():
         buf = torch.empty(n + 64, dtype=torch.uint8, device=dev)
         pos = torch.empty(pos_words, dtype=torch.int64, device=dev)
 
-    res = run_workload(args.workload, args, eng, buf, pos, dev, rank, world, local, use_dist)
+    res = run_workload(args.workload, args, eng, buf, pos, dev, rank, world, local, use_dist, verify=args.full,
+                       dump_dir=args.dump_outputs)
     line = None
     if rank == 0:
         wl = res["wl"]
@@ -663,24 +708,25 @@ def main():
             "dtype": "u8", "data": "synthetic",
             "config": config_of(args.workload, wl, args, world, n, res),
             "roofline": res["roofline"],
-            "verified": res["verified"], "verified_how": res["verified_how"],
         }
+        if args.full:
+            line.update(verified=res["verified"], verified_how=res["verified_how"])
         # (top level and short, so that it survives a truncating reader of `config`)
         line["placement"] = placement or {"tries": 1, "policy": "the first allocation of each buffer, as the driver places it"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(wl, min(n, int(args.cpu_sample_gib * (1 << 30))), buf)
             except Exception as e:  # the baseline is reported, never required
                 line["cpu_baseline"] = {"value": None, "unit": "GB/s", "cores": os.cpu_count(), "kind": "port",
                                         "sample": f"failed: {e}"}
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         # the other two single-GPU BASELINE configurations, same protocol, same run (configs[2] and configs[3])
         extra = {}
         for name in ("literal8", "memchr1", "ac1000", "words1000"):
             if name == args.workload:
                 continue
             try:
-                r = run_workload(name, args, eng, buf, pos, dev, rank, world, local, use_dist)
+                r = run_workload(name, args, eng, buf, pos, dev, rank, world, local, use_dist, verify=True)
                 e = {"value": r["value"], "unit": "GB/s", "ms_per_step": r["ms_per_step"],
                      "config": config_of(name, r["wl"], args, world, n, r), "roofline": r["roofline"],
                      "verified": r["verified"], "verified_how": r["verified_how"]}

@@ -5,6 +5,8 @@ TEST INFRASTRUCTURE: imported by tests/, __graft_entry__.smoke() and bench.py's 
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 import sys
@@ -151,10 +153,9 @@ class RefEngine(_Engine):
     init_name, free_name = "match_result_init", "match_result_free"
     ac_build, ac_free = "ac_trie_build", "ac_trie_free"
 
-    def __init__(self, level: int):
-        self.level = level
-        self.name = "ref:" + _REF_FILES[level]
-        self.lib = C.CDLL(os.path.join(REF_DIR, _REF_FILES[level]))
+    @staticmethod
+    def exports(level: int) -> dict:
+        """{algo: function name} of the build of `level`."""
         fn = {abi.RA_BMH: "boyer_moore_search", abi.RA_KMP: "kmp_search",
               abi.RA_MEMCHR: "memchr_search", abi.RA_MEMCHR_SHORT: "memchr_short_search",
               abi.RA_AHO_CORASICK: "aho_corasick_search"}
@@ -166,7 +167,13 @@ class RefEngine(_Engine):
             fn[abi.RA_AVX2] = "simd_avx2_search"
         if level == abi.REF_AVX512:
             fn[abi.RA_AVX512] = "simd_avx512_search"
-        self.fn = fn
+        return fn
+
+    def __init__(self, level: int):
+        self.level = level
+        self.name = "ref:" + _REF_FILES[level]
+        self.lib = C.CDLL(os.path.join(REF_DIR, _REF_FILES[level]))
+        self.fn = self.exports(level)
         self._setup()
         self.lib.select_search_algorithm.restype = C.c_void_p
         self.lib.select_search_algorithm.argtypes = [C.POINTER(abi.SearchParams)]
@@ -270,6 +277,58 @@ def checker() -> Checker:
     if "chk" not in _cache:
         _cache["chk"] = Checker()
     return _cache["chk"]
+
+
+REF_ANSWERS = os.path.join(ROOT, "tests", "golden", "ref_answers.json")
+
+
+def answer_digest(*parts) -> str:
+    """One answer of the compiled reference as tests/golden/ref_answers.json stores it: ints, bytes and record arrays
+    (as uint64), each length-prefixed, under a 16-hex-digit SHA-256."""
+    h = hashlib.sha256()
+    for x in parts:
+        b = (np.ascontiguousarray(x, dtype=np.uint64).tobytes() if isinstance(x, np.ndarray) else
+             x if isinstance(x, bytes) else str(int(x)).encode())
+        h.update(len(b).to_bytes(8, "little") + b)
+    return h.hexdigest()[:16]
+
+
+class RefAnswers:
+    """The compiled reference's answers for one test module, kept in tests/golden/ref_answers.json (section `section`) so
+    that its tests compare with the reference also where oracle/_ref cannot be built: that needs the reference's sources.
+    Where builds are present their answers are used and must equal the stored ones; KREP_RECORD_REF=1 stores them instead
+    (tests/golden/gen_ref_answers.py)."""
+
+    def __init__(self, section: str):
+        self.section = section
+        self.record = os.environ.get("KREP_RECORD_REF") == "1"
+        with open(REF_ANSWERS) as f:
+            self.stored = json.load(f).get(section, {})
+
+    def want(self, key: str, live: list) -> tuple[str, int]:
+        """-> (answer digest, number of builds that gave it) for `key`: from `live`, the digests of the builds asked here
+        (they must agree), or from the store when `live` is empty."""
+        if live:
+            assert len(set(live)) == 1, (self.section, key, live)
+            if self.record:
+                self.stored[key] = [live[0], len(live)]
+            else:
+                assert self.stored.get(key, live[:1])[0] == live[0], f"{REF_ANSWERS} [{self.section}][{key}] is stale"
+            return live[0], len(live)
+        assert key in self.stored, f"no compiled reference here and no stored answer: {REF_ANSWERS} [{self.section}][{key}]"
+        d, k = self.stored[key]
+        return d, k
+
+    def save(self):
+        """With KREP_RECORD_REF=1: write this section back (other sections kept)."""
+        if not self.record:
+            return
+        with open(REF_ANSWERS) as f:
+            data = json.load(f)
+        data[self.section] = dict(sorted(self.stored.items()))
+        with open(REF_ANSWERS, "w") as f:
+            json.dump(data, f, indent=0, sort_keys=True)
+            f.write("\n")
 
 
 def ref_cli() -> str | None:

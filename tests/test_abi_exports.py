@@ -15,6 +15,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def lib():
+    # torch first, as krep_amd.Engine does: a process that binds the library's HIP runtime before torch's own hides the GPU
+    # from torch, and every GPU test after this one in the same run would fail
+    import torch  # noqa: F401
     return C.CDLL(build.build())
 
 

@@ -20,6 +20,9 @@ BLOCK = {abi.RA_AVX2: 32, abi.RA_AVX512: 64, abi.RA_NEON: 16}
 
 @pytest.fixture(scope="module")
 def lib():
+    # torch first, as krep_amd.Engine does: a process that binds the library's HIP runtime before torch's own hides the GPU
+    # from torch, and every GPU test after this one in the same run would fail
+    import torch  # noqa: F401
     L = C.CDLL(build.build())
     L.krep_gpu_debug_replay_host.restype = C.c_uint64
     L.krep_gpu_debug_replay_host.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_uint32, C.c_int, C.c_size_t, C.c_int]

@@ -1,4 +1,4 @@
-"""N fresh processes of the default bench line (no CPU baseline): per process the kernel time and roofline fraction of the three
+"""N fresh processes of the `--full` bench line (no CPU baseline): per process the kernel time and roofline fraction of the three
 BASELINE workloads and what the placement draw saw.  usage: python tools/run_to_run.py [N] [extra bench.py args...]
        python tools/run_to_run.py 6                      -> first allocations
        python tools/run_to_run.py 6 --placement-tries 4  -> through the library's placed allocator (krep_gpu_alloc_placed)"""
@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 extra = sys.argv[2:]
 for i in range(n):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "10", "--warmup", "2"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "10", "--warmup", "2"] + extra,
                        capture_output=True, text=True)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not lines:
