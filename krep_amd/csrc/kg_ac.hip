@@ -1064,14 +1064,6 @@ __global__ void ac_redo_list_kernel(const u64 *__restrict__ info, u64 n_units, u
 // ---------------------------------------------------------------------------------------------- host: launches and the scan driver
 // (the tables: kg_ac_tables.h, built by kg_ac_build.hip)
 
-#define SCHK(x)                                                                                \
-    do                                                                                         \
-    {                                                                                          \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess)                                                                  \
-            return fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 int g_ac_force_stage_cap = 0; // test hook (krep_gpu_debug_force_stage_cap)
 
 bool ac_counts_lines_in_registers(const AcTables *t) { return t && t->tiny.ok && !t->tiny.five; }
@@ -1154,8 +1146,8 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
             if (d_pos && cap && track)
             {
                 const match_position_t z{global_base, global_base};
-                SCHK(hipMemcpyAsync(d_pos, &z, sizeof z, hipMemcpyHostToDevice, st));
-                SCHK(hipStreamSynchronize(st));
+                HIPCHK(hipMemcpyAsync(d_pos, &z, sizeof z, hipMemcpyHostToDevice, st));
+                HIPCHK(hipStreamSynchronize(st));
                 out->stored = 1;
             }
         }
@@ -1213,7 +1205,7 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
     // filters on the anchor grams and verifies the ends they name
     if (t->anch_state == 0 && text_len >= (1u << 20) && own_hi - own_lo >= (1u << 19))
     {
-        SCHK(hipSetDevice(t->device));
+        HIPCHK(hipSetDevice(t->device));
         if (ac_anchor_prepare(t, d_text, text_len, own_lo, own_hi, st) == 2)
             (void)hipGetLastError(); // (the end grams stay; a failed sample is not a failed scan)
     }
@@ -1248,9 +1240,27 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
         a.flags |= F_POS;
     a.positions = (u64 *)d_pos;
     a.pos_cap = want;
+    // a one-pass scan that recorded every match (kg_single.hip, kg_ac_tiny.hip): its time and its result
+    auto one_pass_out = [&]() -> int {
+        if (time_it)
+        {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
+            out->kernel_ms = ms;
+        }
+        out->total_matches = h_ctr->total;
+        out->head_line_hit = out->tail_line_hit = h_ctr->total != 0;
+        out->count = std::min<u64>(h_ctr->total, (u64)max_count);
+        if (track)
+        {
+            out->stored = std::min<u64>(out->count, want);
+            out->overflow = out->count > cap;
+        }
+        return 0;
+    };
     // ---- a dictionary of single bytes, records wanted: memchr_search's one-pass kernel with a needle set (kg_single.hip).  The
     // matches of aho_corasick_search for such a dictionary are one (i, i + 1) per matching position in text order
-    // (aho_corasick.c:383-437) — exactly that kernel's records.  Shapes by counted density as in lit_pass (kg_scan.hip).
+    // (aho_corasick.c:383-437) — exactly that kernel's records.  Its shape rules: kg_single.hip single_fused_run.
     if (t->set_n && want && !ww && !own_by_end && t->set_ok && text_len >= (size_t)16 * kSegBytes && !g_ac_force_stage_cap &&
         !getenv("KREP_GPU_NO_FUSED1") && !getenv("KREP_GPU_AC_NO_TINY"))
     {
@@ -1280,55 +1290,14 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
         la.l0 = la.set_l[0];
         la.k0 = 0xffu;
         const u64 units32 = la.num_tiles * kWavesPerBlk;
-        SCHK(hipSetDevice(t->device));
-        if (time_it) SCHK(hipEventRecord(ev0, st));
-        for (;;)
-        {
-            const int shape = t->set_shape;
-            const u64 n_tk = single_fused_tickets(units32, shape);
-            if (n_tk > post.tk_cap)
-            {
-                if (post.d_tk) (void)hipFree(post.d_tk);
-                post.d_tk = nullptr;
-                post.tk_cap = 0;
-                SCHK(hipMalloc(&post.d_tk, single_fused_scratch_words(n_tk) * sizeof(unsigned long long)));
-                post.tk_cap = n_tk;
-            }
-            SCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
-            SCHK(hipMemsetAsync(post.d_tk, 0, single_fused_scratch_words(n_tk) * sizeof(unsigned long long), st));
-            SCHK(launch_single_fused(la, post.d_tk, post.d_tk + n_tk, n_tk, (u32)num_cu, shape, st));
-            if (time_it) SCHK(hipEventRecord(ev1, st));
-            SCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-            SCHK(hipStreamSynchronize(st));
-            if (!h_ctr->overflow_units)
-            {
-                if (time_it)
-                {
-                    float ms = 0;
-                    SCHK(hipEventElapsedTime(&ms, ev0, ev1));
-                    out->kernel_ms = ms;
-                }
-                const u64 total = h_ctr->total;
-                if (shape > 0 && (double)total / (double)(own_hi - la.anchor) < 0.5 * single_fused_max_density(shape - 1))
-                    t->set_shape = shape - 1; // (re-evaluated by every scan: a sparser text goes back to the larger tickets)
-                out->total_matches = total;
-                out->head_line_hit = out->tail_line_hit = total != 0;
-                out->count = std::min<u64>(total, (u64)max_count);
-                if (track)
-                {
-                    out->stored = std::min<u64>(out->count, want);
-                    out->overflow = out->count > cap;
-                }
-                return 0;
-            }
-            const double density = (double)h_ctr->total / (double)(own_hi - la.anchor);
-            int next = shape + 1;
-            while (next <= kFusedShapeMax && density > single_fused_max_density(next))
-                ++next;
-            if (next > kFusedShapeMax || h_ctr->total == 0)
-                break;
-            t->set_shape = next;
-        }
+        HIPCHK(hipSetDevice(t->device));
+        if (time_it) HIPCHK(hipEventRecord(ev0, st));
+        const int rc = single_fused_run(la, units32, own_hi - la.anchor, post, d_ctr, h_ctr, (u32)num_cu, &t->set_shape, time_it ? ev1 : nullptr,
+                                        st, false); // (not counted as krep_gpu_debug_single_launches)
+        if (rc == 2)
+            return 2;
+        if (rc != kFusedGaveUp)
+            return one_pass_out();
         t->set_ok = false; // denser than the largest rings hold: the register-compare kernel below, for good
     }
     // ---- a tiny dictionary, records wanted: ONE pass (kg_ac_tiny.hip FUSED, round 5) — matches ranked into an LDS ring per
@@ -1358,49 +1327,34 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
         AcArgs f = a;
         f.upt = dense ? t->tiny_dense_upt : (u32)std::min<u64>(kAcUnitsPerTicketMax, std::max<u64>(1, f.num_tiles / ((u64)num_cu * kTinyWaves * 4)));
         const u64 n_tk = (f.num_tiles + f.upt - 1) / f.upt;
-        if (n_tk > post.tk_cap)
-        {
-            if (post.d_tk) (void)hipFree(post.d_tk);
-            post.d_tk = nullptr;
-            post.tk_cap = 0;
-            SCHK(hipMalloc(&post.d_tk, single_fused_scratch_words(n_tk) * sizeof(unsigned long long)));
-            post.tk_cap = n_tk;
-        }
+        const size_t tk_bytes = 2 * n_tk * sizeof(unsigned long long); // counts | prefixes
+        HIPCHK(grow_scratch(post.tk_cap, n_tk, n_tk, {dev_buf(post.d_tk, tk_bytes)}));
         f.tk_agg = post.d_tk;
         f.tk_pref = post.d_tk + n_tk;
         f.n_tk = n_tk;
         f.stage_cap = 0;
-        SCHK(hipSetDevice(t->device));
-        if (time_it) SCHK(hipEventRecord(ev0, st));
-        SCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
-        SCHK(hipMemsetAsync(post.d_tk, 0, single_fused_scratch_words(n_tk) * sizeof(unsigned long long), st));
-        SCHK(ac_tiny_launch_fused(f, t->tiny, n_tk, (u32)num_cu, st, dense));
+        HIPCHK(hipSetDevice(t->device));
+        if (time_it) HIPCHK(hipEventRecord(ev0, st));
+        HIPCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
+        HIPCHK(hipMemsetAsync(post.d_tk, 0, tk_bytes, st));
+        HIPCHK(ac_tiny_launch_fused(f, t->tiny, n_tk, (u32)num_cu, st, dense));
         // (the record list -c is counted on: its line gaps behind the scan on the same stream, skipped by the kernel itself when
         //  a ticket overflowed its ring)
         if (lines_on_list && tail_launch_line_gaps(d_text, text_len, global_base, (const uint64_t *)d_pos, &d_ctr->total, &d_ctr->overflow_units,
                                                    want, &d_ctr->lines, st))
             return 2;
-        if (time_it) SCHK(hipEventRecord(ev1, st));
-        SCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        SCHK(hipStreamSynchronize(st));
+        if (time_it) HIPCHK(hipEventRecord(ev1, st));
+        HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         const double per_unit = (double)h_ctr->total / (double)f.num_tiles;
         if (getenv("KREP_GPU_DEBUG"))
             fprintf(stderr, "krep-gpu: tiny one-pass (%s, %u units per ticket): %llu matches, %.1f per unit, %llu waves overflowed\n",
                     dense ? "dense" : "items", f.upt, (unsigned long long)h_ctr->total, per_unit, (unsigned long long)h_ctr->overflow_units);
         if (!h_ctr->overflow_units)
         {
-            if (time_it)
-            {
-                float ms = 0;
-                SCHK(hipEventElapsedTime(&ms, ev0, ev1));
-                out->kernel_ms = ms;
-            }
+            if (one_pass_out()) // (track: one_pass_ok asks for it)
+                return 2;
             const u64 total = h_ctr->total;
-            out->total_matches = total;
-            out->head_line_hit = out->tail_line_hit = total != 0;
-            out->count = std::min<u64>(total, (u64)max_count);
-            out->stored = std::min<u64>(out->count, want);
-            out->overflow = out->count > cap;
             if (lines_on_list)
                 out->line_count = total <= want ? h_ctr->lines : ~0ull; // ~0: the list did not fit when the gaps were counted
             if (dense)
@@ -1434,7 +1388,7 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
     const u64 n_units = a.num_tiles;
     // 16 staged matches (32-bit words: unit-relative start + length) = one 64-byte slot per 16 KiB unit; BASELINE config 4 puts 5.3
     // matches in a unit.  Units that hold more are re-scanned in emit mode, and a scan in which more than 1 in 64 units did
-    // raises the dictionary's slot to 64 for its next scans.  (Small slots keep the store stream dense: kg_scan.hip, lit_pass.)
+    // raises the dictionary's slot to 64 for its next scans.  (Small slots keep the store stream dense: kg_scan.hip, lit_args.)
     a.stage_cap = want ? (g_ac_force_stage_cap ? (u32)g_ac_force_stage_cap : t->stage_cap) : 0u;
     if (chain)
     {
@@ -1444,7 +1398,7 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
         a.stage = (u64 *)post.d_stage;
         a.offsets = (const u64 *)post.d_offsets;
     }
-    SCHK(hipSetDevice(t->device));
+    HIPCHK(hipSetDevice(t->device));
     // tiny dictionaries run in kg_ac_tiny.hip (same units, staging, info words and post-pass); -w takes the general kernel
     // (4-byte patterns beside a long length — AcTiny::five: only the case-sensitive COUNT runs in the register-compare kernel, every
     //  other mode of such a dictionary measured faster here)
@@ -1464,7 +1418,7 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
     const u64 n_tickets = (a.num_tiles + a.upt - 1) / a.upt;
     const u32 grid = (u32)std::min<u64>((n_tickets + waves - 1) / waves, (u64)num_cu * per_cu);
     auto launch = [&](const AcArgs &args) { return tiny ? ac_tiny_launch(args, t->tiny, n_tickets, (u32)num_cu, st) : ac_launch(args, grid, lds, st); };
-    if (time_it) SCHK(hipEventRecord(ev0, st));
+    if (time_it) HIPCHK(hipEventRecord(ev0, st));
     // KREP_GPU_SYNC_DEBUG=1: synchronise behind every launch of this function and say which one faulted
     const bool dbg_sync = getenv("KREP_GPU_SYNC_DEBUG") != nullptr;
     auto dbg = [&](const char *what) -> int {
@@ -1476,8 +1430,8 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
                                           (unsigned long long)a.own_lo, (unsigned long long)a.own_hi, (unsigned long long)a.end_lo,
                                           (unsigned long long)a.end_hi, (unsigned long long)text_len);
     };
-    SCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
-    SCHK(launch(a));
+    HIPCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
+    HIPCHK(launch(a));
     if (dbg("scan kernel")) return 2;
     if (chain && post_order(post, n_units, a.stage_cap, 0, a.anchor + global_base, unit_bytes, lines, (uint64_t *)d_pos, want, d_ctr, num_cu, st))
         return 2;
@@ -1488,9 +1442,9 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
     if (lines_on_list && want && tail_launch_line_gaps(d_text, text_len, global_base, (const uint64_t *)d_pos, &d_ctr->total, &d_ctr->overflow_units, want, &d_ctr->lines, st))
         return 2;
     if (dbg("line-gap kernel")) return 2;
-    if (time_it) SCHK(hipEventRecord(ev1, st));
-    SCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-    SCHK(hipStreamSynchronize(st));
+    if (time_it) HIPCHK(hipEventRecord(ev1, st));
+    HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     // The anchor decision follows the TEXT, and a dictionary meets more than one: the kernel counts the positions its filter passed, and a
     // scan whose measured rate is both one that matters (the decision's own 0.8 % bar) and more than twice what the decision estimated for
     // the filter it chose re-opens the decision, so that the next scan samples the text it is given (an i.i.d. text first, a word-like
@@ -1531,8 +1485,7 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
         if (tiny && !t->tiny.five && t->tiny_dense_ok && !t->tiny_dense_upt && h_ctr->total >= n_units * 48)
             t->tiny_dense_upt = dense_upt((double)h_ctr->total / (double)n_units);
         // a byte-set dictionary that proved too dense for the one-pass rings gets them back on a text half as dense as they hold
-        if (t->set_n && !t->set_ok && own_hi > a.anchor &&
-            (double)h_ctr->total / (double)(own_hi - a.anchor) < 0.5 * single_fused_max_density(kFusedShapeMax))
+        if (t->set_n && !t->set_ok && own_hi > a.anchor && single_fused_reopens(h_ctr->total, own_hi - a.anchor))
             t->set_ok = true;
     }
     const bool list_lines_valid = lines_on_list && want && !h_ctr->overflow_units && h_ctr->total <= want;
@@ -1541,38 +1494,31 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
     {
         AcArgs e = a;
         e.emit_mode = 1;
-        SCHK(hipMemsetAsync(&d_ctr->ticket, 0, sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(&d_ctr->ticket, 0, sizeof(unsigned long long), st));
         if (!tiny && !getenv("KREP_GPU_AC_NO_REDO_LIST"))
         {
             // the overflowed units as a list (their number is known: the scan counted them), one ticket each
             const u64 n_over = h_ctr->overflow_units;
-            if (n_over > t->redo_cap)
-            {
-                if (t->d_redo) (void)hipFree(t->d_redo);
-                t->d_redo = nullptr;
-                t->redo_cap = 0;
-                if (hipMalloc(&t->d_redo, (n_over + n_over / 4 + 64) * sizeof(u32)) == hipSuccess)
-                    t->redo_cap = n_over + n_over / 4 + 64;
-                else
-                    (void)hipGetLastError();
-            }
+            const u64 redo_cap = n_over + n_over / 4 + 64;
+            if (grow_scratch(t->redo_cap, n_over, redo_cap, {dev_buf(t->d_redo, redo_cap * sizeof(u32))}) != hipSuccess)
+                (void)hipGetLastError(); // (no list: the emit pass walks every unit)
             if (t->d_redo && n_over <= 0xffffffffull)
             {
-                SCHK(hipMemsetAsync(&d_ctr->pad[3], 0, sizeof(unsigned long long), st));
+                HIPCHK(hipMemsetAsync(&d_ctr->pad[3], 0, sizeof(unsigned long long), st));
                 hipLaunchKernelGGL(ac_redo_list_kernel, dim3((u32)((n_units + 255) / 256)), dim3(256), 0, st, (const u64 *)a.unitinfo, n_units, a.stage_cap, t->d_redo,
                                    (u32)t->redo_cap, &d_ctr->pad[3]);
                 e.redo_list = t->d_redo;
                 e.n_redo = (u32)n_over;
             }
         }
-        SCHK(launch(e));
-        if (time_it) SCHK(hipEventRecord(ev1, st));
-        SCHK(hipStreamSynchronize(st));
+        HIPCHK(launch(e));
+        if (time_it) HIPCHK(hipEventRecord(ev1, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
     if (time_it)
     {
         float ms = 0;
-        SCHK(hipEventElapsedTime(&ms, ev0, ev1));
+        HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
         out->kernel_ms = ms;
     }
     const u64 total = h_ctr->total, nl = h_ctr->lines;

@@ -132,14 +132,6 @@ const char *rccl_why() { return g_rccl && !g_rccl->why.empty() ? g_rccl->why.c_s
         if (e_ != ncclSuccess)                                                                     \
             return kg::fail("%s failed: %s (%s:%d)", #x, (R)->GetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
-#define HCHK(x)                                                                                   \
-    do                                                                                            \
-    {                                                                                             \
-        hipError_t e_ = (x);                                                                      \
-        if (e_ != hipSuccess)                                                                     \
-            return kg::fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 // ---- one process, several devices ---------------------------------------------------------------------------------
 struct Clique
 {
@@ -195,10 +187,10 @@ int clique_for(Rccl *R, const std::vector<int> &devs, size_t n, Clique **out) //
     {
         for (size_t i = 0; i < devs.size(); ++i)
         {
-            HCHK(hipSetDevice(devs[i]));
+            HIPCHK(hipSetDevice(devs[i]));
             if (c->d_vec[i]) (void)hipFree(c->d_vec[i]);
             c->d_vec[i] = nullptr;
-            HCHK(hipMalloc(&c->d_vec[i], n * sizeof(unsigned long long)));
+            HIPCHK(hipMalloc(&c->d_vec[i], n * sizeof(unsigned long long)));
         }
         c->cap = n;
     }
@@ -236,8 +228,8 @@ int allreduce_across_devices(const std::vector<int> &devs, std::vector<std::vect
     auto body = [&]() -> int {
         for (size_t i = 0; i < devs.size(); ++i)
         {
-            HCHK(hipSetDevice(devs[i]));
-            HCHK(hipMemcpyAsync(c->d_vec[i], vecs[i].data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->streams[i]));
+            HIPCHK(hipSetDevice(devs[i]));
+            HIPCHK(hipMemcpyAsync(c->d_vec[i], vecs[i].data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->streams[i]));
         }
         NCHK(R, R->GroupStart());
         for (size_t i = 0; i < devs.size(); ++i)
@@ -246,13 +238,13 @@ int allreduce_across_devices(const std::vector<int> &devs, std::vector<std::vect
         g_calls.fetch_add(1);
         for (size_t i = 0; i < devs.size(); ++i)
         {
-            HCHK(hipSetDevice(devs[i]));
-            HCHK(hipMemcpyAsync(vecs[i].data(), c->d_vec[i], n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->streams[i]));
+            HIPCHK(hipSetDevice(devs[i]));
+            HIPCHK(hipMemcpyAsync(vecs[i].data(), c->d_vec[i], n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->streams[i]));
         }
         for (size_t i = 0; i < devs.size(); ++i)
         {
-            HCHK(hipSetDevice(devs[i]));
-            HCHK(hipStreamSynchronize(c->streams[i]));
+            HIPCHK(hipSetDevice(devs[i]));
+            HIPCHK(hipStreamSynchronize(c->streams[i]));
         }
         return 0;
     };
@@ -339,7 +331,7 @@ extern "C" int krep_gpu_comm_init_rank(const void *id128, int nranks, int rank, 
                 (void)hipSetDevice(prev);
         }
     } restore;
-    HCHK(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     ncclUniqueId id;
     memcpy(&id, id128, sizeof id);
     {
@@ -397,21 +389,21 @@ extern "C" int krep_gpu_comm_allreduce_u64(uint64_t *values, int n)
         std::lock_guard<std::mutex> lk(g_mu);
         if (!g_rank.comm)
             return kg::fail("comm_allreduce: no rank communicator (krep_gpu_comm_init_rank)");
-        HCHK(hipSetDevice(g_rank.device));
+        HIPCHK(hipSetDevice(g_rank.device));
         if (g_rank.cap < (size_t)n)
         {
             if (g_rank.d_vec) (void)hipFree(g_rank.d_vec);
             g_rank.d_vec = nullptr;
             g_rank.cap = 0;
-            HCHK(hipMalloc(&g_rank.d_vec, (size_t)n * sizeof(unsigned long long)));
+            HIPCHK(hipMalloc(&g_rank.d_vec, (size_t)n * sizeof(unsigned long long)));
             g_rank.cap = (size_t)n;
         }
-        HCHK(hipMemcpyAsync(g_rank.d_vec, values, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, g_rank.stream));
+        HIPCHK(hipMemcpyAsync(g_rank.d_vec, values, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, g_rank.stream));
     }
     if (krep_gpu_comm_allreduce_device_u64(g_rank.d_vec, n, nullptr))
         return 2;
-    HCHK(hipMemcpyAsync(values, g_rank.d_vec, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, g_rank.stream));
-    HCHK(hipStreamSynchronize(g_rank.stream));
+    HIPCHK(hipMemcpyAsync(values, g_rank.d_vec, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, g_rank.stream));
+    HIPCHK(hipStreamSynchronize(g_rank.stream));
     return 0;
 }
 

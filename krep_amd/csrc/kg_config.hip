@@ -39,14 +39,6 @@ int fail(const char *fmt, ...)
 }
 bool have_error() { return !g_err.empty(); }
 } // namespace kg
-#define HIPCHK(x)                                                                             \
-    do                                                                                        \
-    {                                                                                         \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess)                                                                 \
-            return kg::fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 extern "C" const char *krep_gpu_last_error(void) { return g_err.c_str(); }
 extern "C" void krep_gpu_clear_error(void) { g_err.clear(); }
 extern "C" const char *krep_gpu_version(void) { return "krep-gpu 0.3 (gfx950)"; }

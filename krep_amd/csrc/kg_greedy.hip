@@ -445,17 +445,17 @@ __global__ void g_nlwalk(const u64 *__restrict__ occ, u64 n_occ, const u64 *__re
     out[2] = seen; // ... and the line it counted last
 }
 
-#define GCHK(x)                                                                                \
-    do                                                                                         \
-    {                                                                                          \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess)                                                                  \
-            return fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 // occ: n_occ records already in s.d_occ.  Results: *total kept matches; records into d_pos (<= want);
 // with ws.lines the distinct-line count (the survivors are compacted into scratch for that).
 // *resume (may be NULL): start + consume of the last element the walk visited (0 for an empty list).
+// the walks' survivor flags, block counts and compacted survivors for n_occ occurrences (one cap; grow-only)
+static hipError_t keep_reserve(PostScratch &s, u64 n_occ)
+{
+    const u64 nb = (n_occ + kGBlockElems - 1) / kGBlockElems;
+    return grow_scratch(s.keep_cap, n_occ, n_occ,
+                        {dev_buf(s.d_keep, n_occ), dev_buf(s.d_gblk, nb * sizeof(u64)), dev_buf(s.d_surv, n_occ * 2 * sizeof(u64))});
+}
+
 int post_walk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint64_t global_base, const WalkSpec &ws,
               uint64_t n_occ, uint64_t *d_pos, uint64_t want, Counters *d_ctr, Counters *h_ctr, hipStream_t st,
               uint64_t *total, uint64_t *nlines, uint64_t *resume)
@@ -467,36 +467,26 @@ int post_walk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint64_t
     if (n_occ == 0)
         return 0;
     const u64 nb = (n_occ + kGBlockElems - 1) / kGBlockElems;
-    if (n_occ > s.keep_cap)
-    {
-        if (s.d_keep) (void)hipFree(s.d_keep);
-        if (s.d_gblk) (void)hipFree(s.d_gblk);
-        if (s.d_surv) (void)hipFree(s.d_surv);
-        s.d_keep = nullptr; s.d_gblk = nullptr; s.d_surv = nullptr; s.keep_cap = 0;
-        GCHK(hipMalloc(&s.d_keep, n_occ));
-        GCHK(hipMalloc(&s.d_gblk, nb * sizeof(u64)));
-        GCHK(hipMalloc(&s.d_surv, n_occ * 2 * sizeof(u64)));
-        s.keep_cap = n_occ;
-    }
+    HIPCHK(keep_reserve(s, n_occ));
     const u64 *occ = (const u64 *)s.d_occ;
     const u32 g1 = (u32)((n_occ + kGB - 1) / kGB);
     const u32 set_len = ws.mode != kWalkGreedy ? ws.m : 0u;
     const bool chain_only = ws.mode == kWalkShortOLines; // no cluster structure: the parallel form from the list's first element
-    GCHK(hipMemsetAsync(s.d_keep, 0, n_occ, st));
-    GCHK(hipMemsetAsync(&d_ctr->pad[1], 0, sizeof(u64), st));
+    HIPCHK(hipMemsetAsync(s.d_keep, 0, n_occ, st));
+    HIPCHK(hipMemsetAsync(&d_ctr->pad[1], 0, sizeof(u64), st));
     if (!chain_only)
     {
         hipLaunchKernelGGL(g_walk, dim3(g1), dim3(kGB), 0, st, occ, (u64)n_occ, (u64)global_base, d_text, (u64)text_len, ws, s.d_keep,
                            (u32 *)&d_ctr->pad[1]);
-        GCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
     if (chain_only || h_ctr->pad[1] || getenv("KREP_GPU_FORCE_POINTER_JUMPING"))
     {
         // a giant cluster: redo the pass in its parallel form (pointer jumping, ceil(log2 n) rounds)
         u64 *jmp = nullptr;
         uint8_t *flags = nullptr; // visited A | visited B | accept
-        GCHK(hipMalloc(&jmp, 2 * n_occ * sizeof(u64)));
+        HIPCHK(hipMalloc(&jmp, 2 * n_occ * sizeof(u64)));
         if (hipMalloc(&flags, 3 * n_occ) != hipSuccess)
         {
             (void)hipFree(jmp);
@@ -520,7 +510,7 @@ int post_walk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint64_t
         if (e1 != hipSuccess || e2 != hipSuccess)
             return fail("pointer-jumping pass failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     }
-    GCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
+    HIPCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
     if (resume)
         hipLaunchKernelGGL(g_resume, dim3(1), dim3(64), 0, st, occ, (u64)n_occ, (u64)global_base, d_text, (u64)text_len, ws,
                            (const uint8_t *)s.d_keep, (u64 *)&d_ctr->pad[1]);
@@ -532,12 +522,12 @@ int post_walk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint64_t
     {
         hipLaunchKernelGGL(g_scatter, dim3((u32)nb), dim3(kGB), 0, st, occ, (const uint8_t *)s.d_keep, (u64)n_occ,
                            (const u64 *)s.d_gblk, (u64 *)s.d_surv, (u64)n_occ, set_len);
-        GCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         const u64 nsurv = h_ctr->total;
         if (nsurv)
         {
-            GCHK(hipMemsetAsync(&d_ctr->lines, 0, sizeof(u64), st));
+            HIPCHK(hipMemsetAsync(&d_ctr->lines, 0, sizeof(u64), st));
             hipLaunchKernelGGL(g_lines, dim3((u32)((nsurv + kGB - 1) / kGB)), dim3(kGB), 0, st, (const u64 *)s.d_surv, (u64)nsurv,
                                (u64)global_base, d_text, d_ctr);
         }
@@ -545,9 +535,9 @@ int post_walk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint64_t
     else if (d_pos && want)
         hipLaunchKernelGGL(g_scatter, dim3((u32)nb), dim3(kGB), 0, st, occ, (const uint8_t *)s.d_keep, (u64)n_occ,
                            (const u64 *)s.d_gblk, (u64 *)d_pos, (u64)want, set_len);
-    GCHK(hipGetLastError());
-    GCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-    GCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     *total = h_ctr->total;
     *nlines = chain_only ? h_ctr->total : (ws.lines ? h_ctr->lines : 0);
     if (resume)
@@ -566,20 +556,9 @@ int post_nlwalk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint32
     *seen_out = seen_in;
     if (n_occ == 0)
         return 0;
-    if (n_occ > s.keep_cap)
-    {
-        const u64 nb = (n_occ + kGBlockElems - 1) / kGBlockElems;
-        if (s.d_keep) (void)hipFree(s.d_keep);
-        if (s.d_gblk) (void)hipFree(s.d_gblk);
-        if (s.d_surv) (void)hipFree(s.d_surv);
-        s.d_keep = nullptr; s.d_gblk = nullptr; s.d_surv = nullptr; s.keep_cap = 0;
-        GCHK(hipMalloc(&s.d_keep, n_occ));
-        GCHK(hipMalloc(&s.d_gblk, nb * sizeof(u64)));
-        GCHK(hipMalloc(&s.d_surv, n_occ * 2 * sizeof(u64)));
-        s.keep_cap = n_occ;
-    }
+    HIPCHK(keep_reserve(s, n_occ));
     const u64 *occ = (const u64 *)s.d_occ;
-    GCHK(hipMemsetAsync(s.d_keep, kKeep, n_occ, st));
+    HIPCHK(hipMemsetAsync(s.d_keep, kKeep, n_occ, st));
     if (ww)
         hipLaunchKernelGGL(g_ww, dim3((u32)((n_occ + kGB - 1) / kGB)), dim3(kGB), 0, st, occ, (u64)n_occ, (u64)global_base, d_text, (u64)text_len, m,
                            s.d_keep);
@@ -588,9 +567,9 @@ int post_nlwalk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint32
     ws.line_off = line_off; ws.cp_in = cp_in; ws.seen_in = seen_in;
     hipLaunchKernelGGL(g_nlwalk, dim3(1), dim3(64), 0, st, occ, (u64)n_occ, (const u64 *)d_lineno, (const uint8_t *)s.d_keep, ws,
                        (u64 *)&d_ctr->pad[1]);
-    GCHK(hipGetLastError());
-    GCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-    GCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     *count = h_ctr->pad[1];
     *cp_out = h_ctr->pad[2];
     *seen_out = h_ctr->pad[3];

@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/krep_gpu.h"
@@ -15,6 +16,41 @@ namespace kg {
 int fail(const char *fmt, ...); // records krep_gpu_last_error(), prints "krep-gpu: ..." and returns 2
 const char *device_unusable(int device); // NULL: a gfx950 device this code object runs on; else why not
 bool inject(int kind);                   // test hook: is failure `kind` being injected (krep_gpu_debug_inject_failure)
+// a HIP call that fails makes the calling function return fail(...)
+#define HIPCHK(x)                                                                                 \
+    do                                                                                            \
+    {                                                                                             \
+        hipError_t e_ = (x);                                                                      \
+        if (e_ != hipSuccess)                                                                     \
+            return kg::fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+// Grow-only device scratch.  When `need` is beyond `cap`, every buffer of the group is freed first, then each is allocated again
+// with its own byte count (the caller's slack included; 0: left null for a later user) and `cap` becomes `new_cap`.  A failed
+// allocation returns its error with `cap` at 0; what it means (an error, or another road) is the caller's decision.
+struct DevBuf
+{
+    void **p;
+    size_t bytes;
+};
+template <class T> DevBuf dev_buf(T *&p, size_t bytes) { return {reinterpret_cast<void **>(&p), bytes}; }
+inline hipError_t grow_scratch(uint64_t &cap, uint64_t need, uint64_t new_cap, std::initializer_list<DevBuf> bufs)
+{
+    if (need <= cap)
+        return hipSuccess;
+    for (const DevBuf &b : bufs)
+    {
+        if (*b.p) (void)hipFree(*b.p);
+        *b.p = nullptr;
+    }
+    cap = 0;
+    for (const DevBuf &b : bufs)
+        if (b.bytes)
+            if (const hipError_t e = hipMalloc(b.p, b.bytes); e != hipSuccess)
+                return e;
+    cap = new_cap;
+    return hipSuccess;
+}
 
 // kg_literal.hip
 hipError_t launch_literal(const LitArgs &a, uint32_t num_cu, hipStream_t st); // grid = resident blocks of the variant x CUs
@@ -28,12 +64,21 @@ extern std::atomic<uint64_t> g_runs_launches;                                   
 extern std::atomic<uint64_t> g_lit_dma_launches;                                   // launches of lit_scan_dma (test hook)
 
 // kg_single.hip — single byte with records in one pass (counts resolved by one wave, records written a ticket later)
-uint64_t single_fused_tickets(uint64_t n_units, int shape);
-uint64_t single_fused_scratch_words(uint64_t n_tickets);
+struct PostScratch;
 constexpr int kFusedShapeMax = 5;
 double single_fused_max_density(int shape); // hits per byte a shape's rings are sure to hold (shapes 0..5: ~1.2 / 3.7 / 5 / 7.5 / 10 / 20 %)
-hipError_t launch_single_fused(const LitArgs &a, unsigned long long *d_agg, unsigned long long *d_pref, uint64_t n_tickets,
-                               uint32_t num_cu, int shape, hipStream_t st);
+// the smallest shape from `start` on whose rings hold `margin` x `density` hits per byte (kFusedShapeMax when none does)
+int single_fused_shape_for(double density, double margin, int start);
+// a text sparse enough (`total` hits in `span` bytes) to re-open the one-pass road to a plan that overflowed its largest rings
+bool single_fused_reopens(uint64_t total, uint64_t span);
+// One one-pass scan at *shape over the `n_units` units of `a` (`span` bytes from a.anchor), its ticket scratch in post.d_tk.  A ticket
+// that overflowed its ring: the counted density picks a larger shape (*shape follows) and the scan runs again.  Done (0): the
+// counters are in *h_ctr, and a text half as sparse as the next smaller shape holds has stepped *shape down for the next scan.
+// kFusedGaveUp: too dense for the largest rings (or the total is not to be trusted).  2: an error.  ev_end (if any) is recorded
+// behind each launch; count_launch: each launch counts towards krep_gpu_debug_single_launches.
+constexpr int kFusedGaveUp = 1;
+int single_fused_run(const LitArgs &a, uint64_t n_units, uint64_t span, PostScratch &post, Counters *d_ctr, Counters *h_ctr,
+                     uint32_t num_cu, int *shape, hipEvent_t ev_end, hipStream_t st, bool count_launch);
 
 // kg_post.hip — ordering post-pass shared by the literal and Aho-Corasick scans
 struct PostScratch

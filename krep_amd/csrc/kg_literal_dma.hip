@@ -476,9 +476,9 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
         atomicAdd(&a.ctr->candidates, (u64)pf_cells);
 }
 
-// The look before the first launch (kg_scan.hip lit_pass): in how many 1-KiB cells of a sample does the prefilter's byte occur at all?
+// The look before the first launch (kg_scan.hip lit_dma_look): in how many 1-KiB cells of a sample does the prefilter's byte occur at all?
 // A cell that holds it costs lit_scan_dma the full 16-position compare, and at two workgroups per CU that work is not hidden; the register
-// kernel (kg_literal.hip, more waves per SIMD) is the faster one from ~4 cells in 10 on (measured: kg_scan.hip lit_pass).  One wave per cell, 16 B per lane.
+// kernel (kg_literal.hip, more waves per SIMD) is the faster one from ~4 cells in 10 on (measured: kg_scan.hip lit_dma_look).  One wave per cell, 16 B per lane.
 __global__ __launch_bounds__(256) void dma_byte_look(const uint8_t *text, u64 lo, u32 n_cells, u32 b4, u32 fold, unsigned long long *out)
 {
     const u32 lane = d_lane();

@@ -39,14 +39,6 @@
 
 using namespace kg;
 
-#define HIPCHK(x)                                                                             \
-    do                                                                                        \
-    {                                                                                         \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess)                                                                 \
-            return kg::fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 namespace {
 thread_local krep_gpu_shard_info_t tl_shards{1, 1, {0}, 0, 0}; // krep_gpu_last_shard_info()
 // ---------------------------------------------------------------------------------------------- device buffers

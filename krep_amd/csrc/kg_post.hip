@@ -370,35 +370,12 @@ void post_free(PostScratch &s)
     s = PostScratch{};
 }
 
-#define PCHK(x)                                                                                \
-    do                                                                                         \
-    {                                                                                          \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess)                                                                  \
-            return fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 int post_reserve(PostScratch &s, uint64_t n_units, uint64_t stage_words)
 {
-    if (n_units > s.units_cap)
-    {
-        if (s.d_unitinfo) (void)hipFree(s.d_unitinfo);
-        if (s.d_offsets) (void)hipFree(s.d_offsets);
-        if (s.d_blk) (void)hipFree(s.d_blk);
-        s.d_unitinfo = nullptr; s.d_offsets = nullptr; s.d_blk = nullptr; s.units_cap = 0;
-        const uint64_t nb = (n_units + kPostUnitsPerBlock - 1) / kPostUnitsPerBlock;
-        PCHK(hipMalloc(&s.d_unitinfo, n_units * sizeof(u64)));
-        PCHK(hipMalloc(&s.d_offsets, n_units * sizeof(u64)));
-        PCHK(hipMalloc(&s.d_blk, 2 * nb * sizeof(u64)));
-        s.units_cap = n_units;
-    }
-    if (stage_words > s.stage_cap_words)
-    {
-        if (s.d_stage) (void)hipFree(s.d_stage);
-        s.d_stage = nullptr; s.stage_cap_words = 0;
-        PCHK(hipMalloc(&s.d_stage, stage_words * sizeof(u64)));
-        s.stage_cap_words = stage_words;
-    }
+    const uint64_t nb = (n_units + kPostUnitsPerBlock - 1) / kPostUnitsPerBlock;
+    HIPCHK(grow_scratch(s.units_cap, n_units, n_units,
+                        {dev_buf(s.d_unitinfo, n_units * sizeof(u64)), dev_buf(s.d_offsets, n_units * sizeof(u64)), dev_buf(s.d_blk, 2 * nb * sizeof(u64))}));
+    HIPCHK(grow_scratch(s.stage_cap_words, stage_words, stage_words, {dev_buf(s.d_stage, stage_words * sizeof(u64))}));
     if (getenv("KREP_GPU_DEBUG_ALLOC")) // tools/placement_probe.py
         fprintf(stderr, "[krep_gpu] scratch: unitinfo %p offsets %p blk %p stage %p (%llu units, %llu stage words)\n", (void *)s.d_unitinfo,
                 (void *)s.d_offsets, (void *)s.d_blk, (void *)s.d_stage, (unsigned long long)s.units_cap, (unsigned long long)s.stage_cap_words);
@@ -414,7 +391,7 @@ int post_offsets_pass(PostScratch &s, uint64_t n_units, bool want_lines, Counter
     hipLaunchKernelGGL(post_carry, dim3(1), dim3(64), 0, st, (u64)nb, blk_sum, blk_bits, d_ctr);
     hipLaunchKernelGGL(post_offsets, dim3((u32)nb), dim3(kPostBlock), 0, st, (const u64 *)s.d_unitinfo, (u64)n_units,
                        (const u64 *)blk_sum, (const u64 *)blk_bits, (u64 *)s.d_offsets, d_ctr, want_lines ? 1 : 0);
-    PCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -428,7 +405,7 @@ int post_gather_pass(PostScratch &s, uint64_t n_units, uint32_t stage_cap, uint3
     hipLaunchKernelGGL(post_gather, dim3(grid ? grid : 1), dim3(kPostBlock), 0, st, (const u64 *)s.d_unitinfo, (u64)n_units,
                        (const u64 *)s.d_offsets, (const u64 *)s.d_stage, stage_cap, fixed_len, (u64)origin, (u64)unit_bytes,
                        (u64 *)d_pos, (u64)pos_cap);
-    PCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

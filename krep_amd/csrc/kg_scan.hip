@@ -1,7 +1,8 @@
 // kg_scan.hip — krep_gpu_scan_device[_ex|_seq](): the device-resident scan with every reference return-value convention
-// (verdict_for), the single-literal pass and its post-passes (lit_pass), the match-set families (greedy walks, end-of-text
-// replay of the block-structured -c bodies, kg_greedy.hip / kg_tail.hip), how a text may be split (kg::split_mode, the boundary
-// record kg::fold_carry) and the multi-pattern drivers around kg_ac.hip.  Host logic only; kernels live in kg_literal.hip /
+// (verdict_for), the single-literal pass and its post-passes (lit_pass and its steps lit_args .. lit_reopen), one function per
+// match-set family behind scan_literal (lit_nlwalk, lit_replay_piece / _whole, lit_neon_zero, lit_plain, lit_walk; the shared
+// epilogue lit_finish; kg_greedy.hip / kg_tail.hip), how a text may be split (kg::split_mode, the boundary record kg::fold_carry)
+// and the multi-pattern drivers around kg_ac.hip.  Host logic only; kernels live in kg_literal.hip /
 // kg_single.hip / kg_ac.hip / kg_post.hip / kg_greedy.hip / kg_tail.hip / kg_format.hip.
 #include <hip/hip_runtime.h>
 
@@ -25,14 +26,6 @@
 
 using namespace kg;
 
-#define HIPCHK(x)                                                                             \
-    do                                                                                        \
-    {                                                                                         \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess)                                                                 \
-            return kg::fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 // ------------------------------------------------------------------------------------ reference return-value conventions
 // What the reference function returns / stores given the number of emitted matches (`total`, after
 // greedy selection and -w) or distinct lines.  One place for all the max_count corner cases.
@@ -52,7 +45,7 @@ static Verdict verdict_for(int algo, const krep_gpu_plan *pl, uint64_t total, ui
             return v;
         break;
     case KREP_RA_NEON: // :4516 then the pre-increment checks :4582/:4616; count-only with max_count == 0 is resolved by
-                       // the caller (the tail call's BMH convention, scan_literal)
+                       // the caller (the tail call's BMH convention, lit_neon_zero)
         if (maxc == 0)
             return v;
         break;
@@ -78,6 +71,17 @@ static Verdict verdict_for(int algo, const krep_gpu_plan *pl, uint64_t total, ui
             v.store = v.ret + 1; // krep.c:1717-1724 stores the (max_count+1)-th match before breaking
     }
     return v;
+}
+
+// The end of a timed scan: ev1 recorded (unless the scan's last launch did that), the stream waited for, kernel_ms = ev0 -> ev1.
+static int stop_clock(krep_gpu_plan *pl, bool record_ev1, hipStream_t st, krep_gpu_scan_out_t *out)
+{
+    if (record_ev1) HIPCHK(hipEventRecord(pl->ev1, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, pl->ev0, pl->ev1));
+    out->kernel_ms = ms;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------ device scan: single literal
@@ -111,6 +115,18 @@ struct LitResult
     unsigned long long summary = 0;
     uint64_t n_units = 0, unit_bytes = 0, anchor = 0;
 };
+// a window as the literal kernels see it (lit_pass): their arguments and what the steps of one pass share
+struct LitScan
+{
+    LitArgs a{};
+    uint64_t hi_match = 0;  // starts in [a.own_lo, hi_match) are matched
+    uint64_t n_units = 0;   // 32-KiB units of the launch
+    int fsc = 0;            // krep_gpu_debug_force_stage_cap (0: the plan's own slot)
+    bool dma_keep = false;  // KREP_GPU_LIT_DMA_KEEP (measurement aid): no look, no bar
+    uint64_t span() const { return hi_match - a.anchor; }
+    uint64_t unit_bytes() const { return (uint64_t)a.rounds * kSegBytes; }
+    double density(uint64_t hits) const { return (double)hits / (double)span(); }
+};
 } // namespace
 
 // hits per 32-KiB unit from which a 2..8-byte literal with records takes the one-pass kernel (KREP_GPU_FUSEDK_MIN: measurement aid)
@@ -122,20 +138,20 @@ static double fusedk_min_hits_per_unit()
     }();
     return v;
 }
-
-static int lit_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, hipStream_t st, LitResult *res)
+// share of the 1-KiB cells beyond which a text bars the LDS-DMA kernel (KREP_GPU_LIT_DMA_MAX_PASS: measurement aid)
+static double lit_dma_max_pass()
 {
-    *res = LitResult{};
-    const uint32_t m_scan = ps.first_byte ? 1u : pl->m;
-    size_t own_hi = std::min(ps.own_hi, w.text_len);
-    if (ps.first_byte)
-        own_hi = std::min<size_t>(own_hi, w.text_len - pl->m + 1);
-    const uint64_t hi_match = std::min<uint64_t>(own_hi, w.text_len - m_scan + 1);
-    if (hi_match <= ps.own_lo)
-        return 0;
-    PostScratch &post = *ps.post;
+    static const double v = [] { const char *e = getenv("KREP_GPU_LIT_DMA_MAX_PASS"); return e ? atof(e) : 0.35; }();
+    return v;
+}
 
-    LitArgs a{};
+// the kernel arguments of a pass over the window: tiles, pattern words, flags, the LDS-DMA prefilter, the staging slot
+static LitScan lit_args(const krep_gpu_plan *pl, const Window &w, const LitPass &ps, size_t own_hi, uint64_t hi_match)
+{
+    LitScan L;
+    LitArgs &a = L.a;
+    const uint32_t m_scan = ps.first_byte ? 1u : pl->m;
+    L.hi_match = hi_match;
     a.text = w.d_text;
     a.text_len = w.text_len;
     a.own_lo = ps.own_lo;
@@ -185,55 +201,7 @@ static int lit_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, hipSt
             rare = rare && b0 != (uint32_t)*q;
         a.prefilter = (rare && !ps.first_byte && !getenv("KREP_GPU_LIT_NO_PREFILTER")) ? 0x01010101u * b0 : 0u;
     }
-    const bool chain = (a.flags & (F_POS | F_LINES)) != 0;
-    const uint64_t n_units = a.num_tiles * kWavesPerBlk;
-    // Dealing: from ~24 GiB on every wave draws tickets of 8 units (>= 24 tickets per resident wave, ~26 fetch-adds/us on the
-    // ticket word); below that the static interleaved deal (upt = 0) is faster — measured at 8 GiB: 1.38 vs 1.41 ms with
-    // offsets, 1.29 vs 1.37 ms counting; at 16 GiB 2.58 vs 2.63 ms; at 2 GiB 0.37 vs 0.48 ms (the ticket word becomes the limit
-    // of a short scan); at 32 GiB tickets win: 5.20 vs 5.31 ms, and 7.1 vs 7.9 ms on the single-byte workload
-    // (the LDS-DMA kernel, kg_literal_dma.hip, wants tickets — a ticket is what it streams through without a seam — and is ahead with them
-    //  from ~8 GiB on: 8 GiB 1.339 against 1.362 ms for the register kernel's static deal, 16 GiB 2.610 against 2.639; round 6)
-    bool dma_shape = m_scan >= 2 && m_scan <= 8 && !ps.lines && !ps.first_byte && a.prefilter != 0u && !getenv("KREP_GPU_LIT_NO_DMA");
-    auto tickets_for = [&](bool dma) { return (a.rounds == kRoundsBig && n_units / ((uint64_t)pl->num_cu * 16) >= (dma ? 64u : 192u)) ? 8u : 0u; };
-    a.upt = tickets_for(dma_shape);
-    // ... and wants a TEXT in which the prefilter's byte is rare: a 1-KiB cell that holds it pays the full compare, which two workgroups per CU
-    // do not hide.  32 GiB, offsets produced, by the share of cells that hold the byte (profiles/r06_ldsdma_byte_rate.txt): 10 % 5.08 ms,
-    // 27 % 5.08, 46 % 5.23, 68 % 5.75, 96 % 6.49 — against 5.19-5.20 ms of the register kernel throughout.  The static rule above only bars
-    // the letters that running text is made of; what THIS text holds is sampled once (two 2-MiB windows, one wave per cell) before the plan's
-    // first such launch, and counted by every launch of the kernel (Counters::candidates).  A plan barred by one text looks again at the next.
-    static const double kDmaMaxPass = [] { const char *e = getenv("KREP_GPU_LIT_DMA_MAX_PASS"); return e ? atof(e) : 0.35; }();
-    const bool dma_keep = getenv("KREP_GPU_LIT_DMA_KEEP") != nullptr; // measurement aid: no look, no bar
-    if (dma_shape && (a.upt >= 4 || getenv("KREP_GPU_LIT_DMA_ALL")) && a.rounds == kRoundsBig && !dma_keep && hi_match - a.anchor >= (64ull << 20) &&
-        (!pl->dma_look_done || (pl->dma_off && (pl->dma_off_text != (const void *)w.d_text || pl->dma_off_len != w.text_len))))
-    {
-        pl->dma_look_done = true;
-        const uint64_t span = hi_match - a.anchor, win = 2ull << 20;
-        HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-        for (int q = 0; q < 2; ++q)
-            HIPCHK(launch_dma_byte_look(w.d_text, (a.anchor + span / 4 * (2 * q + 1)) & ~(uint64_t)15, (uint32_t)(win / kCellBytes), a.prefilter,
-                                        !pl->cs, &pl->d_ctr->candidates, st));
-        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        pl->dma_pass_rate = (double)pl->h_ctr->candidates / (double)(2 * win / kCellBytes);
-        pl->dma_off = pl->dma_pass_rate > kDmaMaxPass;
-        pl->dma_off_text = w.d_text;
-        pl->dma_off_len = w.text_len;
-        if (getenv("KREP_GPU_DEBUG"))
-            fprintf(stderr, "krep-gpu: literal scan: the prefilter's byte 0x%02x occurs in %.1f %% of the sampled 1-KiB cells -> %s kernel\n", a.prefilter & 0xffu,
-                    100.0 * pl->dma_pass_rate, pl->dma_off ? "register" : "LDS-DMA");
-    }
-    if (pl->dma_off && !dma_keep)
-    {
-        a.prefilter = 0u; // (kg_literal_dma.hip literal_dma_eligible: the register kernel)
-        dma_shape = false;
-        a.upt = tickets_for(false);
-    }
-    if (const char *e = getenv("KREP_GPU_LIT_UPT")) // measurement aid; only the values the kernel's parked-store bookkeeping
-    {                                               // is built for (kPark = 240 must be a multiple; ADVICE r02)
-        const int v = atoi(e);
-        if (v == 0 || v == 1 || v == 2 || v == 4 || v == 8)
-            a.upt = (uint32_t)v;
-    }
+    L.n_units = a.num_tiles * kWavesPerBlk;
     // Staging slot per unit.  Single byte: 512 offsets (1 KiB) per 32 KiB unit, ~1.5x BASELINE's 1 % density.  Sparse kinds:
     // 16 offsets = ONE 32-byte slot per 32 KiB unit (BASELINE's 1e-4/B puts 3.3 hits in a unit); units that hold more take the
     // emit-mode re-scan, and a scan in which more than 1 in 64 units did raises the plan's slot to 64 for its next scans.
@@ -245,246 +213,317 @@ static int lit_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, hipSt
     a.stage_cap = 0;
     if (a.flags & F_POS)
         a.stage_cap = a.rounds == kRoundsBig ? (m_scan == 1 ? 512u : pl->sparse_cap) : (m_scan == 1 ? 256u : 32u);
-    const int fsc = g_force_stage_cap.load(std::memory_order_relaxed);
-    if (fsc && (a.flags & F_POS))
-        a.stage_cap = (uint32_t)fsc;
-    const uint32_t grid = (uint32_t)pl->num_cu; // the launchers size the grid: resident blocks of the chosen variant x CUs
-    const uint64_t unit_bytes = (uint64_t)a.rounds * kSegBytes, origin = a.anchor + w.global_base;
-    res->n_units = n_units;
-    res->unit_bytes = unit_bytes;
-    res->anchor = a.anchor;
-    // ---- single byte with records (memchr_search, BASELINE config 3): ONE pass, the records written by the scanning waves
-    // at their final index (kg_single.hip) — no staging, no info words, no post-pass.  A scan too dense for the rings of its
-    // shape is counted but not recorded: the count picks the shape that holds it (up to ~20 % hits) and the scan runs again in
-    // that shape — the plan keeps it; beyond that the two-pass kernels below take this scan and the plan's later ones.
-    // The same kernel takes a literal of 2..8 bytes (its MULTI instantiations) once a two-pass scan of the plan has counted a
-    // density at which the staging slots of the sparse kinds overflow (`-i sh`: 35 hits per unit; ` a`: 180): pl->fusedk_on.
-    // ---- the FIRST records scan of a plan on a large text: one cheap look before the full launch (round 6).  A plan
-    // used to learn the density of its text from whole scans — the two-pass road first, the one-pass writers and their ring shape
-    // from the third or fourth scan on (`-i Sh`: 4222 / 4886 / 5026 / 5097 GB/s in four consecutive scans), which a CLI process,
-    // making ONE scan, never reached.  Two 2-MiB windows are counted (~0.1 ms next to >= 0.16 ms of scan) and the road, the ring shape
-    // and the staging slot are chosen from that; every later scan re-evaluates them as before.
-    if (ps.sink == LitPass::RECORDS && !pl->first_look_done && a.rounds == kRoundsBig && fsc == 0 && !ps.first_byte && !ps.lines &&
-        ps.excl_lo == ps.excl_hi && hi_match - a.anchor >= (1ull << 30) && !getenv("KREP_GPU_NO_FIRST_LOOK"))
+    L.fsc = g_force_stage_cap.load(std::memory_order_relaxed);
+    if (L.fsc && (a.flags & F_POS))
+        a.stage_cap = (uint32_t)L.fsc;
+    return L;
+}
+
+// The dealing of units to waves, and the LDS-DMA kernel's look at the text and the bar it sets.
+static int lit_dma_look(krep_gpu_plan *pl, const Window &w, const LitPass &ps, LitScan &L, hipStream_t st)
+{
+    LitArgs &a = L.a;
+    const uint32_t m_scan = a.m;
+    // Dealing: from ~24 GiB on every wave draws tickets of 8 units (>= 24 tickets per resident wave, ~26 fetch-adds/us on the
+    // ticket word); below that the static interleaved deal (upt = 0) is faster — measured at 8 GiB: 1.38 vs 1.41 ms with
+    // offsets, 1.29 vs 1.37 ms counting; at 16 GiB 2.58 vs 2.63 ms; at 2 GiB 0.37 vs 0.48 ms (the ticket word becomes the limit
+    // of a short scan); at 32 GiB tickets win: 5.20 vs 5.31 ms, and 7.1 vs 7.9 ms on the single-byte workload
+    // (the LDS-DMA kernel, kg_literal_dma.hip, wants tickets — a ticket is what it streams through without a seam — and is ahead with them
+    //  from ~8 GiB on: 8 GiB 1.339 against 1.362 ms for the register kernel's static deal, 16 GiB 2.610 against 2.639; round 6)
+    const bool dma_shape = m_scan >= 2 && m_scan <= 8 && !ps.lines && !ps.first_byte && a.prefilter != 0u && !getenv("KREP_GPU_LIT_NO_DMA");
+    auto tickets_for = [&](bool dma) { return (a.rounds == kRoundsBig && L.n_units / ((uint64_t)pl->num_cu * 16) >= (dma ? 64u : 192u)) ? 8u : 0u; };
+    a.upt = tickets_for(dma_shape);
+    // ... and wants a TEXT in which the prefilter's byte is rare: a 1-KiB cell that holds it pays the full compare, which two workgroups per CU
+    // do not hide.  32 GiB, offsets produced, by the share of cells that hold the byte (profiles/r06_ldsdma_byte_rate.txt): 10 % 5.08 ms,
+    // 27 % 5.08, 46 % 5.23, 68 % 5.75, 96 % 6.49 — against 5.19-5.20 ms of the register kernel throughout.  The static rule above only bars
+    // the letters that running text is made of; what THIS text holds is sampled once (two 2-MiB windows, one wave per cell) before the plan's
+    // first such launch, and counted by every launch of the kernel (Counters::candidates, lit_dma_rate).  A plan barred by one text looks
+    // again at the next.
+    const double max_pass = lit_dma_max_pass();
+    L.dma_keep = getenv("KREP_GPU_LIT_DMA_KEEP") != nullptr; // measurement aid: no look, no bar
+    if (dma_shape && (a.upt >= 4 || getenv("KREP_GPU_LIT_DMA_ALL")) && a.rounds == kRoundsBig && !L.dma_keep && L.span() >= (64ull << 20) &&
+        (!pl->dma_look_done || (pl->dma_off && (pl->dma_off_text != (const void *)w.d_text || pl->dma_off_len != w.text_len))))
     {
-        pl->first_look_done = true;
-        const uint64_t span = hi_match - a.anchor, win = 2ull << 20, tile_bytes = (uint64_t)kRoundsBig * kSegBytes * kWavesPerBlk;
+        pl->dma_look_done = true;
+        const uint64_t span = L.span(), win = 2ull << 20;
         HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-        uint64_t looked = 0;
         for (int q = 0; q < 2; ++q)
-        {
-            LitArgs sm = a;
-            sm.flags &= ~(uint32_t)(F_POS | F_LINES);
-            sm.stage_cap = 0;
-            sm.upt = 0;
-            sm.emit_mode = 0;
-            sm.own_lo = (a.anchor + span / 4 * (2 * q + 1)) & ~(uint64_t)15;
-            sm.own_hi = std::min<uint64_t>(hi_match, sm.own_lo + win);
-            sm.anchor = sm.own_lo;
-            sm.num_tiles = (sm.own_hi - sm.anchor + tile_bytes - 1) / tile_bytes;
-            looked += sm.own_hi - sm.own_lo;
-            HIPCHK(launch_literal(sm, grid, st));
-        }
+            HIPCHK(launch_dma_byte_look(w.d_text, (a.anchor + span / 4 * (2 * q + 1)) & ~(uint64_t)15, (uint32_t)(win / kCellBytes), a.prefilter,
+                                        !pl->cs, &pl->d_ctr->candidates, st));
         HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        const double density = looked ? (double)pl->h_ctr->total / (double)looked : 0.0, per_unit = density * 32768.0;
-        if (m_scan == 1)
-        {
-            if (density > single_fused_max_density(kFusedShapeMax))
-                pl->fused1_ok = false;
-            else
-            {
-                int shape = 0;
-                while (shape < kFusedShapeMax && 1.05 * density > single_fused_max_density(shape))
-                    ++shape;
-                pl->fused1_shape = shape;
-            }
-        }
-        else if (m_scan <= 8 && !pl->fusedk_never && per_unit >= fusedk_min_hits_per_unit() &&
-                 density <= single_fused_max_density(kFusedShapeMax))
-        {
-            int shape = 0;
-            while (shape < kFusedShapeMax && 1.05 * density > single_fused_max_density(shape))
-                ++shape;
-            pl->fusedk_on = true;
-            pl->fusedk_shape = shape;
-        }
-        else if (per_unit > 6.0) // the staging road with slots that hold what a unit holds (what a whole scan used to find out)
-            pl->sparse_cap = std::max<uint32_t>(pl->sparse_cap, per_unit > 100.0 ? 256u : per_unit > 40.0 ? 128u : 64u);
+        pl->dma_pass_rate = (double)pl->h_ctr->candidates / (double)(2 * win / kCellBytes);
+        pl->dma_off = pl->dma_pass_rate > max_pass;
+        pl->dma_off_text = w.d_text;
+        pl->dma_off_len = w.text_len;
         if (getenv("KREP_GPU_DEBUG"))
-            fprintf(stderr, "krep-gpu: first look: %.2f hits per 32-KiB unit in %llu sampled bytes -> one-pass %d (shape %d / %d), staging slot %u\n", per_unit,
-                    (unsigned long long)looked, (int)(m_scan == 1 ? pl->fused1_ok : pl->fusedk_on), pl->fused1_shape, pl->fusedk_shape, pl->sparse_cap);
-        if ((a.flags & F_POS) && !fsc)
-            a.stage_cap = a.rounds == kRoundsBig ? (m_scan == 1 ? 512u : pl->sparse_cap) : a.stage_cap;
+            fprintf(stderr, "krep-gpu: literal scan: the prefilter's byte 0x%02x occurs in %.1f %% of the sampled 1-KiB cells -> %s kernel\n", a.prefilter & 0xffu,
+                    100.0 * pl->dma_pass_rate, pl->dma_off ? "register" : "LDS-DMA");
     }
-    const bool fusedk = m_scan >= 2 && m_scan <= 8 && pl->fusedk_on;
-    // (-w: the 2..8-byte instantiations test it in registers since round 6; the single-byte ones do not build the window it needs)
-    if ((m_scan == 1 ? pl->fused1_ok : fusedk) && ps.sink == LitPass::RECORDS && !(ps.ww && m_scan == 1) && !ps.lines && !ps.first_byte &&
-        a.rounds == kRoundsBig && fsc == 0 && ps.excl_lo == ps.excl_hi && w.text_len >= 2 * (size_t)kSegBytes &&
-        !getenv("KREP_GPU_NO_FUSED1"))
+    if (pl->dma_off && !L.dma_keep)
     {
-        a.positions = ps.d_out;
-        a.pos_cap = ps.out_cap;
-        int &plan_shape = m_scan == 1 ? pl->fused1_shape : pl->fusedk_shape;
-        for (;;)
-        {
-            const int shape = plan_shape;
-            const uint64_t n_tk = single_fused_tickets(n_units, shape);
-            if (n_tk > post.tk_cap)
-            {
-                if (post.d_tk) (void)hipFree(post.d_tk);
-                post.d_tk = nullptr;
-                post.tk_cap = 0;
-                HIPCHK(hipMalloc(&post.d_tk, single_fused_scratch_words(n_tk) * sizeof(unsigned long long)));
-                post.tk_cap = n_tk;
-            }
-            HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-            HIPCHK(hipMemsetAsync(post.d_tk, 0, single_fused_scratch_words(n_tk) * sizeof(unsigned long long), st));
-            HIPCHK(launch_single_fused(a, post.d_tk, post.d_tk + n_tk, n_tk, grid, shape, st));
-            g_fused1_launches.fetch_add(1);
-            if (ps.ev_end) HIPCHK(hipEventRecord(ps.ev_end, st));
-            HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (!pl->h_ctr->overflow_units)
-            {
-                res->total = pl->h_ctr->total;
-                res->summary = res->total ? (kLnHead | kLnTail) : 0;
-                // the decision is re-evaluated by every scan: a text half as dense as the next smaller shape holds
-                // sends the plan's following scans back to it (larger tickets, more waves per CU)
-                const double density = (double)res->total / (double)(hi_match - a.anchor);
-                if (shape > 0 && density < 0.5 * single_fused_max_density(shape - 1))
-                    plan_shape = shape - 1;
-                if (m_scan != 1 && density * 32768.0 < 0.5 * fusedk_min_hits_per_unit())
-                    pl->fusedk_on = false; // (a sparser text: the staging road is faster there)
-                return 0;
-            }
-            // the scan counted every ticket (the resolver's running sum): the density chooses the shape — unless the spin-limit
-            // safety net fired (then the total is not to be trusted and the two-pass kernels take over)
-            const double density = (double)pl->h_ctr->total / (double)(hi_match - a.anchor);
-            int next = shape + 1;
-            while (next <= kFusedShapeMax && density > single_fused_max_density(next))
-                ++next;
-            if (next > kFusedShapeMax || pl->h_ctr->total == 0)
-                break;
-            plan_shape = next;
-        }
-        if (m_scan == 1)
+        a.prefilter = 0u; // (kg_literal_dma.hip literal_dma_eligible: the register kernel)
+        a.upt = tickets_for(false);
+    }
+    if (const char *e = getenv("KREP_GPU_LIT_UPT")) // measurement aid; only the values the kernel's parked-store bookkeeping
+    {                                               // is built for (kPark = 240 must be a multiple; ADVICE r02)
+        const int v = atoi(e);
+        if (v == 0 || v == 1 || v == 2 || v == 4 || v == 8)
+            a.upt = (uint32_t)v;
+    }
+    return 0;
+}
+// what the LDS-DMA kernel itself counted on this text (behind a scan): its later scans go by it
+static void lit_dma_rate(krep_gpu_plan *pl, const Window &w, const LitScan &L)
+{
+    if (!literal_dma_eligible(L.a) || L.span() < (64ull << 20))
+        return;
+    pl->dma_pass_rate = (double)pl->h_ctr->candidates / ((double)L.span() / kCellBytes);
+    if (pl->dma_pass_rate > lit_dma_max_pass() && !L.dma_keep)
+    {
+        pl->dma_off = true;
+        pl->dma_off_text = w.d_text;
+        pl->dma_off_len = w.text_len;
+        if (getenv("KREP_GPU_DEBUG"))
+            fprintf(stderr, "krep-gpu: literal scan: the prefilter passed %.1f %% of the 1-KiB cells -> the register kernel from the next scan on\n", 100.0 * pl->dma_pass_rate);
+    }
+}
+
+// ---- the FIRST records scan of a plan on a large text: one cheap look before the full launch (round 6).  A plan
+// used to learn the density of its text from whole scans — the two-pass road first, the one-pass writers and their ring shape
+// from the third or fourth scan on (`-i Sh`: 4222 / 4886 / 5026 / 5097 GB/s in four consecutive scans), which a CLI process,
+// making ONE scan, never reached.  Two 2-MiB windows are counted (~0.1 ms next to >= 0.16 ms of scan) and the road, the ring shape
+// and the staging slot are chosen from that; every later scan re-evaluates them as before.
+static int lit_first_look(krep_gpu_plan *pl, const LitPass &ps, LitScan &L, hipStream_t st)
+{
+    LitArgs &a = L.a;
+    const uint32_t m_scan = a.m;
+    if (!(ps.sink == LitPass::RECORDS && !pl->first_look_done && a.rounds == kRoundsBig && L.fsc == 0 && !ps.first_byte && !ps.lines &&
+          ps.excl_lo == ps.excl_hi && L.span() >= (1ull << 30) && !getenv("KREP_GPU_NO_FIRST_LOOK")))
+        return 0;
+    pl->first_look_done = true;
+    const uint64_t span = L.span(), win = 2ull << 20, tile_bytes = (uint64_t)kRoundsBig * kSegBytes * kWavesPerBlk;
+    HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
+    uint64_t looked = 0;
+    for (int q = 0; q < 2; ++q)
+    {
+        LitArgs sm = a;
+        sm.flags &= ~(uint32_t)(F_POS | F_LINES);
+        sm.stage_cap = 0;
+        sm.upt = 0;
+        sm.emit_mode = 0;
+        sm.own_lo = (a.anchor + span / 4 * (2 * q + 1)) & ~(uint64_t)15;
+        sm.own_hi = std::min<uint64_t>(L.hi_match, sm.own_lo + win);
+        sm.anchor = sm.own_lo;
+        sm.num_tiles = (sm.own_hi - sm.anchor + tile_bytes - 1) / tile_bytes;
+        looked += sm.own_hi - sm.own_lo;
+        HIPCHK(launch_literal(sm, (uint32_t)pl->num_cu, st));
+    }
+    HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const double density = looked ? (double)pl->h_ctr->total / (double)looked : 0.0, per_unit = density * 32768.0;
+    if (m_scan == 1)
+    {
+        if (density > single_fused_max_density(kFusedShapeMax))
             pl->fused1_ok = false;
         else
-            pl->fusedk_on = false, pl->fusedk_never = true;
-        g_fused1_failovers.fetch_add(1);
+            pl->fused1_shape = single_fused_shape_for(density, 1.05, 0);
     }
-    if (chain)
+    else if (m_scan <= 8 && !pl->fusedk_never && per_unit >= fusedk_min_hits_per_unit() &&
+             density <= single_fused_max_density(kFusedShapeMax))
     {
-        if (post_reserve(post, n_units, (n_units * a.stage_cap + 3) / 4)) // 16-bit staging entries
-            return 2;
-        a.unitinfo = post.d_unitinfo;
-        a.stage = (uint64_t *)post.d_stage;
-        a.offsets = (const uint64_t *)post.d_offsets;
+        pl->fusedk_on = true;
+        pl->fusedk_shape = single_fused_shape_for(density, 1.05, 0);
     }
-    HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-    if (ps.sink != LitPass::OCC)
+    else if (per_unit > 6.0) // the staging road with slots that hold what a unit holds (what a whole scan used to find out)
+        pl->sparse_cap = std::max<uint32_t>(pl->sparse_cap, per_unit > 100.0 ? 256u : per_unit > 40.0 ? 128u : 64u);
+    if (getenv("KREP_GPU_DEBUG"))
+        fprintf(stderr, "krep-gpu: first look: %.2f hits per 32-KiB unit in %llu sampled bytes -> one-pass %d (shape %d / %d), staging slot %u\n", per_unit,
+                (unsigned long long)looked, (int)(m_scan == 1 ? pl->fused1_ok : pl->fusedk_on), pl->fused1_shape, pl->fusedk_shape, pl->sparse_cap);
+    if ((a.flags & F_POS) && !L.fsc)
+        a.stage_cap = a.rounds == kRoundsBig ? (m_scan == 1 ? 512u : pl->sparse_cap) : a.stage_cap;
+    return 0;
+}
+
+// ---- single byte with records (memchr_search, BASELINE config 3): ONE pass, the records written by the scanning waves
+// at their final index (kg_single.hip) — no staging, no info words, no post-pass.  A scan too dense for the rings of its
+// shape is counted but not recorded: the count picks the shape that holds it (up to ~20 % hits) and the scan runs again in
+// that shape — the plan keeps it; beyond that the two-pass kernels take this scan and the plan's later ones.
+// The same kernel takes a literal of 2..8 bytes (its MULTI instantiations) once a two-pass scan of the plan has counted a
+// density at which the staging slots of the sparse kinds overflow (`-i sh`: 35 hits per unit; ` a`: 180): pl->fusedk_on.
+// *done: the scan is complete (else the two-pass road takes it).
+static int lit_one_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, LitScan &L, hipStream_t st, LitResult *res, bool *done)
+{
+    LitArgs &a = L.a;
+    const uint32_t m_scan = a.m;
+    *done = false;
+    const bool fusedk = m_scan >= 2 && m_scan <= 8 && pl->fusedk_on;
+    // (-w: the 2..8-byte instantiations test it in registers since round 6; the single-byte ones do not build the window it needs)
+    if (!((m_scan == 1 ? pl->fused1_ok : fusedk) && ps.sink == LitPass::RECORDS && !(ps.ww && m_scan == 1) && !ps.lines && !ps.first_byte &&
+          a.rounds == kRoundsBig && L.fsc == 0 && ps.excl_lo == ps.excl_hi && w.text_len >= 2 * (size_t)kSegBytes &&
+          !getenv("KREP_GPU_NO_FUSED1")))
+        return 0;
+    a.positions = ps.d_out;
+    a.pos_cap = ps.out_cap;
+    int &plan_shape = m_scan == 1 ? pl->fused1_shape : pl->fusedk_shape;
+    const int rc = single_fused_run(a, L.n_units, L.span(), *ps.post, pl->d_ctr, pl->h_ctr, (uint32_t)pl->num_cu, &plan_shape, ps.ev_end, st,
+                                    true);
+    if (rc == 2)
+        return 2;
+    if (rc != kFusedGaveUp)
     {
-        a.positions = ps.d_out;
-        a.pos_cap = ps.sink == LitPass::RECORDS ? ps.out_cap : 0;
-        HIPCHK(launch_literal(a, grid, st));
-        if (chain && post_order(post, n_units, a.stage_cap, m_scan, origin, unit_bytes, ps.lines, ps.d_out, a.pos_cap, pl->d_ctr,
-                                pl->num_cu, st))
-            return 2;
+        res->total = pl->h_ctr->total;
+        res->summary = res->total ? (kLnHead | kLnTail) : 0;
+        if (m_scan != 1 && L.density(res->total) * 32768.0 < 0.5 * fusedk_min_hits_per_unit())
+            pl->fusedk_on = false; // (a sparser text: the staging road is faster there)
+        *done = true;
+        return 0;
+    }
+    if (m_scan == 1)
+        pl->fused1_ok = false;
+    else
+        pl->fusedk_on = false, pl->fusedk_never = true;
+    g_fused1_failovers.fetch_add(1);
+    return 0;
+}
+
+// behind a two-pass scan into records or counts: the plan's staging slot and its one-pass road from the counted density
+static void lit_learn_density(krep_gpu_plan *pl, const LitPass &ps, const LitScan &L)
+{
+    const LitArgs &a = L.a;
+    const uint32_t m_scan = a.m;
+    if ((a.flags & F_POS) && m_scan != 1 && a.rounds == kRoundsBig && pl->h_ctr->overflow_units * 64 > L.n_units && !L.fsc)
+    {
+        // a dense input: the next scans of this plan stage 64 hits per unit — and if more than 1 unit in 64 overflows that as
+        // well (`-i sh`: 36 hits per unit on average, clustered), as many as the fullest unit held, up to 256: re-scanning
+        // 5 % of the units cold cost m = 2 -i a fifth of its time
+        uint32_t want = 64;
+        if (pl->sparse_cap >= 64)
+            for (want = 128; want < 256 && want < pl->h_ctr->max_unit_count; want *= 2) {}
+        pl->sparse_cap = std::max(pl->sparse_cap, want);
+    }
+    if ((a.flags & F_POS) && m_scan >= 2 && m_scan <= 8 && a.rounds == kRoundsBig && !L.fsc && !pl->fusedk_never &&
+        ps.sink == LitPass::RECORDS && !ps.lines && L.hi_match > a.anchor)
+    {
+        // dense enough for the one-pass record writer (kg_single.hip, MULTI)?  Its shape from the density just counted.
+        const double density = L.density(pl->h_ctr->total);
+        if (density * 32768.0 >= fusedk_min_hits_per_unit() && density <= single_fused_max_density(kFusedShapeMax))
+        {
+            pl->fusedk_on = true;
+            pl->fusedk_shape = single_fused_shape_for(density, 1.0, 0);
+        }
+    }
+    if (getenv("KREP_GPU_DEBUG") && (a.flags & F_POS))
+        fprintf(stderr, "krep-gpu: literal scan: %llu of %llu units overflowed a %u-entry slot (fullest: %llu); one-pass next: %d (shape %d)\n",
+                pl->h_ctr->overflow_units, (unsigned long long)L.n_units, a.stage_cap, pl->h_ctr->max_unit_count, (int)pl->fusedk_on,
+                pl->fusedk_shape);
+}
+// behind every two-pass scan: a later, sparser text of the same plan takes the one-pass kernel again (the 2..8-byte
+// instantiations as well: one overflowing text no longer bars them for good)
+static void lit_reopen(krep_gpu_plan *pl, const LitScan &L)
+{
+    const uint32_t m_scan = L.a.m;
+    if (!pl->fused1_ok && m_scan == 1 && single_fused_reopens(pl->h_ctr->total, L.span()))
+        pl->fused1_ok = true;
+    if (pl->fusedk_never && m_scan >= 2 && m_scan <= 8 && single_fused_reopens(pl->h_ctr->total, L.span()))
+        pl->fusedk_never = false;
+}
+
+// ---- the two-pass road into records or counts: the scan (kg_literal.hip / kg_literal_dma.hip), the ordering post-pass
+// (kg_post.hip) behind it, and an emit-mode re-scan of the units whose hits overflowed their staging slot
+static int lit_two_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, LitScan &L, bool chain, hipStream_t st)
+{
+    LitArgs &a = L.a;
+    a.positions = ps.d_out;
+    a.pos_cap = ps.sink == LitPass::RECORDS ? ps.out_cap : 0;
+    HIPCHK(launch_literal(a, (uint32_t)pl->num_cu, st));
+    if (chain && post_order(*ps.post, L.n_units, a.stage_cap, a.m, a.anchor + w.global_base, L.unit_bytes(), ps.lines, ps.d_out, a.pos_cap,
+                            pl->d_ctr, pl->num_cu, st))
+        return 2;
+    if (ps.ev_end) HIPCHK(hipEventRecord(ps.ev_end, st));
+    HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    lit_dma_rate(pl, w, L);
+    lit_learn_density(pl, ps, L);
+    if ((a.flags & F_POS) && pl->h_ctr->overflow_units)
+    {
+        // some units held more hits than their staging slot: re-scan exactly those, writing in place
+        LitArgs e = a;
+        e.emit_mode = 1;
+        HIPCHK(hipMemsetAsync(&pl->d_ctr->ticket, 0, sizeof(unsigned long long), st));
+        HIPCHK(launch_literal(e, (uint32_t)pl->num_cu, st));
         if (ps.ev_end) HIPCHK(hipEventRecord(ps.ev_end, st));
-        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (literal_dma_eligible(a) && hi_match - a.anchor >= (64ull << 20))
+    }
+    return 0;
+}
+// ---- the two-pass road into the occurrence list: all owned hits into post.d_occ (sized after the count is known), the input of
+// the sequential-family walks
+static int lit_two_pass_occ(krep_gpu_plan *pl, const Window &w, const LitPass &ps, const LitScan &L, hipStream_t st)
+{
+    const LitArgs &a = L.a;
+    PostScratch &post = *ps.post;
+    HIPCHK(launch_literal(a, (uint32_t)pl->num_cu, st));
+    if (post_offsets_pass(post, L.n_units, false, pl->d_ctr, st))
+        return 2;
+    HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t n_occ = pl->h_ctr->total;
+    HIPCHK(grow_scratch(post.occ_cap, n_occ, n_occ, {dev_buf(post.d_occ, n_occ * 2 * sizeof(uint64_t))}));
+    if (n_occ)
+    {
+        if (post_gather_pass(post, L.n_units, a.stage_cap, a.m, a.anchor + w.global_base, L.unit_bytes(), post.d_occ, n_occ, pl->num_cu, st))
+            return 2;
+        if (pl->h_ctr->overflow_units)
         {
-            // what the LDS-DMA kernel itself counted on this text: its later scans go by it
-            pl->dma_pass_rate = (double)pl->h_ctr->candidates / ((double)(hi_match - a.anchor) / kCellBytes);
-            if (pl->dma_pass_rate > kDmaMaxPass && !dma_keep)
-            {
-                pl->dma_off = true;
-                pl->dma_off_text = w.d_text;
-                pl->dma_off_len = w.text_len;
-                if (getenv("KREP_GPU_DEBUG"))
-                    fprintf(stderr, "krep-gpu: literal scan: the prefilter passed %.1f %% of the 1-KiB cells -> the register kernel from the next scan on\n", 100.0 * pl->dma_pass_rate);
-            }
-        }
-        if ((a.flags & F_POS) && m_scan != 1 && a.rounds == kRoundsBig && pl->h_ctr->overflow_units * 64 > n_units && !fsc)
-        {
-            // a dense input: the next scans of this plan stage 64 hits per unit — and if more than 1 unit in 64 overflows that as
-            // well (`-i sh`: 36 hits per unit on average, clustered), as many as the fullest unit held, up to 256: re-scanning
-            // 5 % of the units cold cost m = 2 -i a fifth of its time
-            uint32_t want = 64;
-            if (pl->sparse_cap >= 64)
-                for (want = 128; want < 256 && want < pl->h_ctr->max_unit_count; want *= 2) {}
-            pl->sparse_cap = std::max(pl->sparse_cap, want);
-        }
-        if ((a.flags & F_POS) && m_scan >= 2 && m_scan <= 8 && a.rounds == kRoundsBig && !fsc && !pl->fusedk_never &&
-            ps.sink == LitPass::RECORDS && !ps.lines && hi_match > a.anchor)
-        {
-            // dense enough for the one-pass record writer (kg_single.hip, MULTI)?  Its shape from the density just counted.
-            const double density = (double)pl->h_ctr->total / (double)(hi_match - a.anchor);
-            if (density * 32768.0 >= fusedk_min_hits_per_unit() && density <= single_fused_max_density(kFusedShapeMax))
-            {
-                int shape = 0;
-                while (shape < kFusedShapeMax && density > single_fused_max_density(shape))
-                    ++shape;
-                pl->fusedk_on = true;
-                pl->fusedk_shape = shape;
-            }
-        }
-        if (getenv("KREP_GPU_DEBUG") && (a.flags & F_POS))
-            fprintf(stderr, "krep-gpu: literal scan: %llu of %llu units overflowed a %u-entry slot (fullest: %llu); one-pass next: %d (shape %d)\n",
-                    pl->h_ctr->overflow_units, (unsigned long long)n_units, a.stage_cap, pl->h_ctr->max_unit_count, (int)pl->fusedk_on,
-                    pl->fusedk_shape);
-        if ((a.flags & F_POS) && pl->h_ctr->overflow_units)
-        {
-            // some units held more hits than their staging slot: re-scan exactly those, writing in place
             LitArgs e = a;
             e.emit_mode = 1;
+            e.positions = post.d_occ;
+            e.pos_cap = n_occ;
             HIPCHK(hipMemsetAsync(&pl->d_ctr->ticket, 0, sizeof(unsigned long long), st));
-            HIPCHK(launch_literal(e, grid, st));
-            if (ps.ev_end) HIPCHK(hipEventRecord(ps.ev_end, st));
+            HIPCHK(launch_literal(e, (uint32_t)pl->num_cu, st));
         }
     }
-    else
+    return 0;
+}
+
+// one pass of the literal kernel family over the window, with its ordering post-pass
+static int lit_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, hipStream_t st, LitResult *res)
+{
+    *res = LitResult{};
+    const uint32_t m_scan = ps.first_byte ? 1u : pl->m;
+    size_t own_hi = std::min(ps.own_hi, w.text_len);
+    if (ps.first_byte)
+        own_hi = std::min<size_t>(own_hi, w.text_len - pl->m + 1);
+    const uint64_t hi_match = std::min<uint64_t>(own_hi, w.text_len - m_scan + 1);
+    if (hi_match <= ps.own_lo)
+        return 0;
+    LitScan L = lit_args(pl, w, ps, own_hi, hi_match);
+    if (lit_dma_look(pl, w, ps, L, st))
+        return 2;
+    res->n_units = L.n_units;
+    res->unit_bytes = L.unit_bytes();
+    res->anchor = L.a.anchor;
+    bool done = false;
+    if (lit_first_look(pl, ps, L, st) || lit_one_pass(pl, w, ps, L, st, res, &done))
+        return 2;
+    if (done)
+        return 0;
+    const bool chain = (L.a.flags & (F_POS | F_LINES)) != 0;
+    if (chain)
     {
-        // all owned hits into post.d_occ (sized after the count is known): input of the sequential-family walks
-        HIPCHK(launch_literal(a, grid, st));
-        if (post_offsets_pass(post, n_units, false, pl->d_ctr, st))
+        PostScratch &post = *ps.post;
+        if (post_reserve(post, L.n_units, (L.n_units * L.a.stage_cap + 3) / 4)) // 16-bit staging entries
             return 2;
-        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const uint64_t n_occ = pl->h_ctr->total;
-        if (n_occ > post.occ_cap)
-        {
-            if (post.d_occ) (void)hipFree(post.d_occ);
-            post.d_occ = nullptr;
-            post.occ_cap = 0;
-            HIPCHK(hipMalloc(&post.d_occ, n_occ * 2 * sizeof(uint64_t)));
-            post.occ_cap = n_occ;
-        }
-        if (n_occ)
-        {
-            if (post_gather_pass(post, n_units, a.stage_cap, m_scan, origin, unit_bytes, post.d_occ, n_occ, pl->num_cu, st))
-                return 2;
-            if (pl->h_ctr->overflow_units)
-            {
-                LitArgs e = a;
-                e.emit_mode = 1;
-                e.positions = post.d_occ;
-                e.pos_cap = n_occ;
-                HIPCHK(hipMemsetAsync(&pl->d_ctr->ticket, 0, sizeof(unsigned long long), st));
-                HIPCHK(launch_literal(e, grid, st));
-            }
-        }
+        L.a.unitinfo = post.d_unitinfo;
+        L.a.stage = (uint64_t *)post.d_stage;
+        L.a.offsets = (const uint64_t *)post.d_offsets;
     }
+    HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
+    if (ps.sink != LitPass::OCC ? lit_two_pass(pl, w, ps, L, chain, st) : lit_two_pass_occ(pl, w, ps, L, st))
+        return 2;
     res->total = pl->h_ctr->total;
     res->lines = pl->h_ctr->lines;
-    if (!pl->fused1_ok && m_scan == 1 && hi_match > a.anchor &&
-        (double)pl->h_ctr->total / (double)(hi_match - a.anchor) < 0.5 * single_fused_max_density(kFusedShapeMax))
-        pl->fused1_ok = true; // (a later, sparser text of the same plan takes the one-pass kernel again)
-    if (pl->fusedk_never && m_scan >= 2 && m_scan <= 8 && hi_match > a.anchor &&
-        (double)pl->h_ctr->total / (double)(hi_match - a.anchor) < 0.5 * single_fused_max_density(kFusedShapeMax))
-        pl->fusedk_never = false; // (the same for the 2..8-byte instantiations: one overflowing text no longer bars them for good)
+    lit_reopen(pl, L);
     res->summary = chain ? pl->h_ctr->summary : (res->total ? (kLnHead | kLnTail) : 0);
     return 0;
 }
@@ -605,6 +644,18 @@ extern "C" void krep_gpu_debug_fold_carry(const krep_gpu_seq_carry_t *in, const 
 extern "C" int krep_gpu_split_mode(const search_params_t *p, size_t text_len)
 {
     return kg::split_mode(p, kg::current_config(), text_len);
+}
+
+// The plan's ordered record list and the line number of every start (d_nl_rec / d_nl_ln: one cap, grow-only).  More than nl_cap
+// records needed: both are freed and the records allocated again for `want`, the line numbers too when `with_ln` — the list road
+// of plain -c sizes only the records, and a later user that needs the line numbers allocates them at the cap the records have.
+static int nl_reserve(krep_gpu_plan *pl, uint64_t need, uint64_t want, bool with_ln)
+{
+    HIPCHK(grow_scratch(pl->nl_cap, need, want,
+                        {dev_buf(pl->d_nl_rec, want * sizeof(match_position_t)), dev_buf(pl->d_nl_ln, with_ln ? want * sizeof(uint64_t) : 0)}));
+    if (with_ln && !pl->d_nl_ln)
+        HIPCHK(hipMalloc(&pl->d_nl_ln, pl->nl_cap * sizeof(uint64_t)));
+    return 0;
 }
 
 // Where the reference's block loop stands when it enters the last kReplayWindow bytes (kg_replay.h): `cur`, and for
@@ -742,6 +793,402 @@ static int replay_entry(krep_gpu_plan *pl, int algo, const Window &w, const LitR
     return 0;
 }
 
+namespace {
+// a single-literal scan as scan_literal hands it to the function of its family
+struct LitJob
+{
+    krep_gpu_plan *pl;
+    int algo;
+    const Window &w;
+    size_t own_hi;            // the ownership window's end, clipped to the buffer
+    bool whole;               // the window is the whole text
+    hipStream_t st;
+    const krep_gpu_seq_carry_t *carry_in;
+    krep_gpu_seq_carry_t *carry_out;
+    match_position_t *d_pos;
+    uint64_t cap, want;       // records room / records the caller can use
+    uint64_t excl_lo = 0, excl_hi = 0, ww_exempt = ~0ull; // the block-structured functions' quirks (buffer-relative)
+};
+// what the plain, walk and replay families leave for the shared epilogue (lit_finish)
+struct LitTotals
+{
+    uint64_t total = 0, lines = 0;
+    unsigned long long summary = 0;
+    bool ev1_recorded = false;
+};
+} // namespace
+
+// -c through simd_sse42_search / kmp_search with a newline inside the pattern: all occurrences, the line number of every
+// start, the -w verdicts — then ONE thread walks the list the way the reference's loop moves (kg_greedy.hip (3)).
+// Pieces (round 5): a piece owns the occurrences that START in it; what couples it to the text in front of it is where
+// the reference's scan stands (resume), the line it counted last and the newlines so far (krep_gpu_seq_carry_t).
+static int lit_nlwalk(const LitJob &j, int time_it, krep_gpu_scan_out_t *out)
+{
+    krep_gpu_plan *pl = j.pl;
+    const Window &w = j.w;
+    const hipStream_t st = j.st;
+    const uint32_t m = pl->m;
+    const krep_gpu_seq_carry_t in = j.carry_in ? *j.carry_in : krep_gpu_seq_carry_t{};
+    krep_gpu_seq_carry_t local{};
+    if (!j.whole && !j.carry_in && w.global_base + w.own_lo != 0)
+        return kg::fail("-c through %s with a newline inside the pattern is a chain over every counted match: scan the whole "
+                        "text in one window, or its pieces in text order through krep_gpu_scan_device_seq()", krep_gpu_algorithm_name(j.algo));
+    if (pl->max_count == 0)
+        return 0; // krep.c:4713, :1634
+    HIPCHK(hipSetDevice(pl->device));
+    if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
+    unsigned long long *d_slot = &pl->d_ctr->pad[0], *h_slot = &pl->h_ctr->pad[0];
+    uint64_t nl_halo = 0, nl_own = 0;
+    if (tail_count_newlines(w.d_text, 0, w.own_lo, d_slot, h_slot, st, &nl_halo) ||
+        tail_count_newlines(w.d_text, w.own_lo, j.own_hi, d_slot, h_slot, st, &nl_own))
+        return 2;
+    local.local_nl = nl_own;
+    LitPass ps;
+    ps.own_lo = w.own_lo; ps.own_hi = j.own_hi; ps.sink = LitPass::OCC; ps.post = &pl->post;
+    LitResult lr0;
+    if (lit_pass(pl, w, ps, st, &lr0))
+        return 2;
+    uint64_t lines_counted = 0, cp_out = in.resume, seen_out = in.last_line ? in.last_line : ~0ull;
+    if (lr0.total)
+    {
+        if (nl_reserve(pl, lr0.total, lr0.total + lr0.total / 4 + 1024, true))
+            return 2;
+        if (krep_gpu_line_numbers_ex(w.d_text, w.text_len, w.global_base, (const match_position_t *)pl->post.d_occ, lr0.total, pl->d_nl_ln, st))
+            return 2;
+        const uint32_t k0 = (uint32_t)((const uint8_t *)memchr(pl->pats[0].data(), '\n', m) - pl->pats[0].data());
+        // buffer-relative line numbers (1 + newlines in [0, start)) -> global ones: + newlines in front of the buffer
+        const uint64_t line_off = in.nl_before - nl_halo;
+        if (post_nlwalk(pl->post, w.d_text, w.text_len, j.algo == KREP_RA_KMP ? kNlWalkKmp : kNlWalkSse42, m, k0, pl->ww,
+                        pl->only_matching, pl->max_count == SIZE_MAX ? ~0ull : (uint64_t)pl->max_count, lr0.total, pl->d_nl_ln,
+                        pl->d_ctr, pl->h_ctr, st, &lines_counted, w.global_base, w.global_len, line_off, in.resume,
+                        in.last_line ? in.last_line : ~0ull, &cp_out, &seen_out))
+            return 2;
+    }
+    if (time_it && stop_clock(pl, true, st, out))
+        return 2;
+    if (j.carry_out)
+    {
+        // (the line counted last, relative to own_lo and biased like the multi-pattern record's, so that fold_carry() re-bases it)
+        if (seen_out != ~0ull && seen_out != (in.last_line ? in.last_line : ~0ull))
+            local.local_last = (1ull << 62) + (seen_out - (in.nl_before + 1ull));
+        krep_gpu_seq_carry_t o = kg::fold_carry(in, local);
+        if (!local.local_last)
+            o.last_line = in.last_line;
+        o.resume = std::max<uint64_t>(in.resume, cp_out);
+        *j.carry_out = o;
+    }
+    out->total_matches = lines_counted;
+    out->line_count = lines_counted;
+    out->has_newline = j.whole ? 0 : 1; // (pieces: krep_gpu_combine_line_counts adds the counts up, the record has settled the cuts)
+    out->head_line_hit = out->tail_line_hit = j.whole ? lines_counted != 0 : 0;
+    out->count = lines_counted; // the walk applies max_count the way the functions do (a break before the increment)
+    return 0;
+}
+
+// -c through a block-structured function, a PIECE of the text (krep_gpu_scan_device_seq): canonical -c over the starts before the
+// last kReplayWindow bytes, then the reference's own walk over the rest.  Only the piece that ends the text runs the replay; what it
+// needs from the text in front of it is the line-skip history {last accepted occurrence q, first '\n' behind it}, which every piece
+// extends (krep_gpu_seq_carry_t) — the piece's own contribution is reported next to the folded state, so that shards scanned out of
+// order can be folded afterwards.
+static int lit_replay_piece(const LitJob &j, LitTotals *t)
+{
+    krep_gpu_plan *pl = j.pl;
+    const Window &w = j.w;
+    const hipStream_t st = j.st;
+    const int algo = j.algo;
+    const uint64_t G = w.global_len, X = G > kReplayWindow ? G - kReplayWindow : 0;
+    const uint64_t base = w.global_base, B = algo == KREP_RA_AVX512 ? 64 : algo == KREP_RA_AVX2 ? 32 : 16;
+    const bool final_piece = base + j.own_hi >= G;
+    if (base + w.own_lo != 0 && !j.carry_in)
+        return kg::fail("-c through %s restarts its block grid at every counted line: scan the whole text in one window, "
+                        "or its pieces in text order through krep_gpu_scan_device_seq()", krep_gpu_algorithm_name(algo));
+    if (final_piece && (base + w.text_len != G || X < base + w.own_lo + B))
+        return kg::fail("-c through %s: the piece that ends the text must hold its last %llu bytes", krep_gpu_algorithm_name(algo),
+                        (unsigned long long)(kReplayWindow + B));
+    const uint64_t lim = final_piece ? X - base : j.own_hi; // the canonical pass covers the starts in [own_lo, lim)
+    const uint64_t nl_end = final_piece ? w.text_len : j.own_hi; // where this piece's newline searches stop
+    unsigned long long *d_slot = &pl->d_ctr->pad[0], *h_slot = &pl->h_ctr->pad[0];
+    LitResult lr;
+    if (lim > w.own_lo)
+    {
+        LitPass ps;
+        ps.ww = pl->ww; ps.lines = true; ps.own_lo = w.own_lo; ps.own_hi = lim; ps.post = &pl->post;
+        if (lit_pass(pl, w, ps, st, &lr))
+            return 2;
+    }
+    const krep_gpu_seq_carry_t in = j.carry_in ? *j.carry_in : krep_gpu_seq_carry_t{};
+    krep_gpu_seq_carry_t pc{}; // this piece's own contribution
+    bool have_q = false;
+    uint64_t q = 0;
+    if (lim > w.own_lo && last_accepted_before(pl, w, lr, w.own_lo, lim, st, &have_q, &q))
+        return 2;
+    {
+        uint64_t nl = nl_end; // first newline of the piece (the record of a piece without an occurrence; neon_search's kind 2)
+        if ((!have_q || algo == KREP_RA_NEON) && tail_find_next_newline(w.d_text, w.own_lo, nl_end, d_slot, h_slot, st, &nl))
+            return 2;
+        pc.local_first_nl1 = nl < nl_end ? base + nl + 1 : 0;
+    }
+    if (have_q)
+    {
+        uint64_t nl = nl_end;
+        if (tail_find_next_newline(w.d_text, q, nl_end, d_slot, h_slot, st, &nl))
+            return 2;
+        pc.local_q1 = base + q + 1;
+        pc.local_nl1 = nl < nl_end ? base + nl + 1 : 0;
+        if (algo == KREP_RA_NEON)
+        {
+            // the grid origin in effect for q's line: (first newline behind the last accepted occurrence on an earlier
+            // line) + 1 — from this piece if that occurrence lies in it, else from the record in front of it
+            uint64_t lsp1 = 0;
+            if (tail_find_prev_newline(w.d_text, q, d_slot, h_slot, st, &lsp1))
+                return 2;
+            if (lsp1 <= w.own_lo) // no newline in [own_lo, q): q's line started in front of this piece
+                pc.local_g0_kind = 3;
+            else
+            {
+                bool have_q2 = false;
+                uint64_t q2 = 0;
+                if (last_accepted_before(pl, w, lr, w.own_lo, lsp1, st, &have_q2, &q2))
+                    return 2;
+                if (!have_q2)
+                    pc.local_g0_kind = 2;
+                else
+                {
+                    uint64_t nl2 = nl_end;
+                    if (tail_find_next_newline(w.d_text, q2, nl_end, d_slot, h_slot, st, &nl2))
+                        return 2;
+                    pc.local_g0_kind = 1;
+                    pc.local_g0 = base + nl2 + 1; // nl2 < lsp1 <= q: it exists
+                }
+            }
+        }
+    }
+    if (final_piece)
+        pc.local_lines = lr.lines + 1; // (what krep_gpu_replay_tail() starts from when the record turns out different)
+    const krep_gpu_seq_carry_t co = kg::fold_carry(in, pc);
+    if (j.carry_out)
+        *j.carry_out = co;
+    t->total = lr.total; t->lines = lr.lines; t->summary = lr.summary;
+    if (final_piece)
+    {
+        uint64_t extra = 0;
+        if (replay_from_record(pl, algo, co, rebased(w.d_text, base), base ? base + 1 : 0, G, st, &extra)) // (global offsets >= cur - 1 >= base: inside the buffer)
+            return 2;
+        // the lines the replay counts are new ones (it starts behind the line of q), and the line open at the piece's
+        // start can only be among them when nothing in front of the piece counted it: the canonical head bit stands
+        t->lines = lr.lines + extra;
+        t->total = t->lines;
+    }
+    return 0;
+}
+
+// -c through a block-structured function over the whole text: canonical -c over the starts before the last kReplayWindow bytes,
+// then the reference's own walk over the rest
+static int lit_replay_whole(const LitJob &j, LitTotals *t)
+{
+    krep_gpu_plan *pl = j.pl;
+    const Window &w = j.w;
+    const uint64_t G = w.global_len, X = G > kReplayWindow ? G - kReplayWindow : 0;
+    LitResult lr;
+    uint64_t cur = 0, extra = 0;
+    int open = 0;
+    if (X)
+    {
+        LitPass ps;
+        ps.ww = pl->ww; ps.lines = true; ps.own_lo = 0; ps.own_hi = X; ps.post = &pl->post;
+        if (lit_pass(pl, w, ps, j.st, &lr))
+            return 2;
+        if (replay_entry(pl, j.algo, w, lr, X, j.st, &cur, &open))
+            return 2;
+    }
+    ReplayIn r{};
+    r.algo = j.algo; r.m = pl->m; r.ww = pl->ww; r.n = G; r.cur = cur; r.open = open;
+    r.text = w.d_text; r.pat = pl->d_pat;
+    if (cur < G && tail_run_replay(r, &pl->d_ctr->pad[0], &pl->h_ctr->pad[0], j.st, &extra))
+        return 2;
+    t->lines = lr.lines + extra;
+    t->total = t->lines; // occurrence totals are not defined by a -c scan
+    t->summary = t->lines ? (kLnHead | kLnTail) : 0;
+    return 0;
+}
+
+// neon_search, count-only with max_count == 0: the first body hit returns 0 (krep.c:4616); with no body hit the tail call's
+// BMH returns 1 on its first hit (krep.c:1355-1367).  (ev1 is recorded, kernel_ms is not set.)
+static int lit_neon_zero(const LitJob &j, int time_it, krep_gpu_scan_out_t *out)
+{
+    krep_gpu_plan *pl = j.pl;
+    const Window &w = j.w;
+    const uint64_t G = w.global_len, T = G - G % 16;
+    if (!j.whole)
+        return kg::fail("neon_search with max_count == 0 needs the whole text in one window");
+    LitPass ps;
+    ps.ww = pl->ww; ps.own_lo = 0; ps.own_hi = T; ps.ww_exempt = j.ww_exempt; ps.post = &pl->post;
+    LitResult lr;
+    if (lit_pass(pl, w, ps, j.st, &lr))
+        return 2;
+    uint64_t ret = 0;
+    if (lr.total == 0 && G - T >= pl->m)
+    {
+        ps.own_lo = T; ps.own_hi = G;
+        if (lit_pass(pl, w, ps, j.st, &lr))
+            return 2;
+        ret = lr.total ? 1 : 0;
+    }
+    if (time_it) HIPCHK(hipEventRecord(pl->ev1, j.st));
+    HIPCHK(hipStreamSynchronize(j.st));
+    out->count = ret;
+    out->total_matches = lr.total;
+    return 0;
+}
+
+// every occurrence the reference reports (memchr / BMH / the block-structured bodies, -c without a replay): one literal pass
+static int lit_plain(const LitJob &j, int time_it, LitTotals *t)
+{
+    krep_gpu_plan *pl = j.pl;
+    LitPass ps;
+    ps.ww = pl->ww; ps.lines = pl->lines; ps.own_lo = j.w.own_lo; ps.own_hi = j.own_hi;
+    ps.excl_lo = j.excl_lo; ps.excl_hi = j.excl_hi; ps.ww_exempt = j.ww_exempt;
+    ps.sink = j.want ? LitPass::RECORDS : LitPass::COUNT;
+    ps.d_out = (uint64_t *)j.d_pos; ps.out_cap = j.want; ps.post = &pl->post;
+    ps.ev_end = time_it ? pl->ev1 : nullptr;
+    LitResult lr;
+    if (lit_pass(pl, j.w, ps, j.st, &lr))
+        return 2;
+    t->ev1_recorded = time_it != 0 && lr.n_units != 0;
+    t->total = lr.total; t->lines = lr.lines; t->summary = lr.summary;
+    return 0;
+}
+
+// sequential families on the ordered list (kg_greedy.hip): greedy non-overlapping selection (SSE4.2 / KMP, and BMH
+// under -o) over all occurrences, or memchr_short's -o walk over the first-byte candidates.  A window inside the text
+// starts where the reference's scan stands (carry_in->resume): starts in front of that point are consumed, the first
+// one at or behind it is looked at afresh — exactly what the reference's loop does after `advance`.
+static int lit_walk(const LitJob &j, const Family &fam, LitTotals *t)
+{
+    krep_gpu_plan *pl = j.pl;
+    const Window &w = j.w;
+    const hipStream_t st = j.st;
+    const uint32_t m = pl->m;
+    const size_t own_hi = j.own_hi;
+    const bool mshort_o = fam.mshort_o;
+    const bool ww_first = pl->ww && j.algo == KREP_RA_BMH; // BMH -o: a -w rejected hit does not consume (krep.c:1323-1329)
+    const uint64_t resume_in = j.carry_in ? j.carry_in->resume : 0;
+    size_t lo_eff = w.own_lo;
+    if (resume_in > w.global_base + w.own_lo)
+        lo_eff = (size_t)std::min<uint64_t>(own_hi, resume_in - w.global_base);
+    uint64_t resume_out = 0;
+    // ---- a pattern of ONE repeated byte (`  `, `--`, `aa`), counted: inside a run of R such bytes the kept matches start at every
+    // m-th byte — no list of all occurrences (kg_runs.hip; round 6: `-c -o '  '` materialised 188 M occurrences at 0.65 TB/s)
+    bool runs_done = false;
+    if (!mshort_o && !pl->ww && !pl->lines && j.want == 0 && m >= 2 && !getenv("KREP_GPU_NO_RUNS"))
+    {
+        bool uniform = true;
+        for (uint32_t i = 1; i < m; ++i)
+            uniform = uniform && pl->pat_folded[i] == pl->pat_folded[0];
+        if (uniform)
+        {
+            uint64_t end_p1 = 0;
+            const int rc = runs_count_greedy(w.d_text, w.text_len, lo_eff, own_hi, m, pl->pat_folded[0], !pl->cs, pl->num_cu, &pl->d_ctr->pad[1],
+                                             &pl->h_ctr->pad[1], st, &t->total, &end_p1);
+            if (rc == 2)
+                return 2;
+            if (rc == 0)
+            {
+                runs_done = true;
+                resume_out = end_p1 ? w.global_base + end_p1 : 0;
+            }
+        }
+    }
+    LitPass ps;
+    ps.own_lo = lo_eff; ps.own_hi = own_hi; ps.sink = LitPass::OCC; ps.post = &pl->post;
+    ps.first_byte = mshort_o;
+    ps.ww = ww_first;
+    LitResult lr;
+    if (!runs_done && lit_pass(pl, w, ps, st, &lr))
+        return 2;
+    WalkSpec ws{};
+    ws.mode = mshort_o ? (pl->lines ? kWalkShortOLines : kWalkShortO) : kWalkGreedy;
+    if (ws.mode == kWalkShortOLines && !j.whole)
+        return kg::fail("-c -o through memchr_short_search jumps to the next line start after every counted line: scan the whole "
+                        "text in one window");
+    ws.m = m;
+    ws.ww = pl->ww && !ww_first;
+    ws.lines = pl->lines;
+    ws.ci = !pl->cs;
+    ws.b1 = m > 1 ? pl->pat_folded[1] : 0;
+    ws.b2 = m > 2 ? pl->pat_folded[2] : 0;
+    if (lr.total)
+    {
+        HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
+        int rc = post_walk(pl->post, w.d_text, w.text_len, w.global_base, ws, lr.total, (uint64_t *)j.d_pos, j.want, pl->d_ctr,
+                           pl->h_ctr, st, &t->total, &t->lines, &resume_out);
+        if (rc)
+            return rc;
+    }
+    if (j.carry_out)
+        j.carry_out->resume = std::max(resume_in, resume_out);
+    t->summary = t->total ? (kLnHead | kLnTail) : 0;
+    if (pl->lines && !j.whole)
+    {
+        // line bits of the owned window for the left-to-right fold over the pieces (krep_gpu_combine_line_counts): is there
+        // a '\n' in [own_lo, own_hi), does a survivor start at or before the first / behind the last one
+        unsigned long long *d_slot = &pl->d_ctr->pad[0], *h_slot = &pl->h_ctr->pad[0];
+        uint64_t first_nl = own_hi, last_p1 = 0;
+        if (tail_find_next_newline(w.d_text, w.own_lo, own_hi, d_slot, h_slot, st, &first_nl))
+            return 2;
+        t->summary = 0;
+        if (first_nl < own_hi)
+        {
+            if (tail_find_prev_newline(w.d_text, own_hi, d_slot, h_slot, st, &last_p1))
+                return 2;
+            t->summary |= kLnNl;
+        }
+        if (t->total)
+        {
+            uint64_t s_first[2], s_last[2]; // the survivors were compacted into post.d_surv for the line count
+            HIPCHK(hipMemcpy(s_first, pl->post.d_surv, sizeof s_first, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(s_last, pl->post.d_surv + 2 * (t->total - 1), sizeof s_last, hipMemcpyDeviceToHost));
+            const uint64_t f = s_first[0] - w.global_base, l = s_last[0] - w.global_base;
+            if (!(t->summary & kLnNl))
+                t->summary |= kLnHead | kLnTail;
+            else
+                t->summary |= (f <= first_nl ? kLnHead : 0) | (l >= last_p1 ? kLnTail : 0);
+        }
+    }
+    return 0;
+}
+
+// the epilogue of the plain, walk and replay families: timing, the stream's end, the reference's return value and what is stored
+static int lit_finish(const LitJob &j, int time_it, const LitTotals &t, krep_gpu_scan_out_t *out)
+{
+    krep_gpu_plan *pl = j.pl;
+    if (time_it)
+    {
+        if (stop_clock(pl, !t.ev1_recorded, j.st, out))
+            return 2;
+    }
+    else
+        HIPCHK(hipStreamSynchronize(j.st));
+    out->total_matches = t.total;
+    out->line_count = t.lines;
+    out->has_newline = (t.summary & kLnNl) != 0;
+    out->head_line_hit = (t.summary & kLnHead) != 0;
+    out->tail_line_hit = (t.summary & kLnTail) != 0;
+    Verdict v = verdict_for(j.algo, pl, t.total, t.lines, j.d_pos != nullptr);
+    out->count = v.ret;
+    if (j.d_pos && j.cap && pl->track && !pl->lines)
+    {
+        // records the reference semantics need (memchr: one more than max_count, the host fixes the order)
+        const uint64_t maxc = pl->max_count;
+        const uint64_t needed = (j.algo == KREP_RA_MEMCHR && maxc != SIZE_MAX && maxc != 0) ? std::min<uint64_t>(t.total, maxc + 1)
+                                                                                             : v.store;
+        out->overflow = needed > j.cap;
+        out->stored = std::min<uint64_t>(needed, std::min<uint64_t>(t.total, j.want));
+    }
+    return 0;
+}
+
+// krep_gpu_scan_device*: one single-literal scan, by the match-set family of the reference function reproduced (Family)
 static int scan_literal(krep_gpu_plan *pl, int algo, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st,
                         int time_it, const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out)
 {
@@ -757,92 +1204,17 @@ static int scan_literal(krep_gpu_plan *pl, int algo, const Window &w, match_posi
 
     const Family fam = family_of(algo, pl->only_matching, pl->lines, pl->ww, pl->track, pl->max_count, pl->has_border, m,
                                  pl->has_newline);
-    const bool mshort_o = fam.mshort_o, need_walk = fam.need_walk, replay = fam.replay;
+    LitJob j{pl, algo, w, own_hi, whole, st, carry_in, carry_out, d_pos, cap, 0};
     if (fam.nlwalk)
-    {
-        // -c through simd_sse42_search / kmp_search with a newline inside the pattern: all occurrences, the line number of every
-        // start, the -w verdicts — then ONE thread walks the list the way the reference's loop moves (kg_greedy.hip (3)).
-        // Pieces (round 5): a piece owns the occurrences that START in it; what couples it to the text in front of it is where
-        // the reference's scan stands (resume), the line it counted last and the newlines so far (krep_gpu_seq_carry_t).
-        const krep_gpu_seq_carry_t in = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
-        krep_gpu_seq_carry_t local{};
-        if (!whole && !carry_in && w.global_base + w.own_lo != 0)
-            return kg::fail("-c through %s with a newline inside the pattern is a chain over every counted match: scan the whole "
-                            "text in one window, or its pieces in text order through krep_gpu_scan_device_seq()", krep_gpu_algorithm_name(algo));
-        if (pl->max_count == 0)
-            return 0; // krep.c:4713, :1634
-        HIPCHK(hipSetDevice(pl->device));
-        if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
-        unsigned long long *d_slot = &pl->d_ctr->pad[0], *h_slot = &pl->h_ctr->pad[0];
-        uint64_t nl_halo = 0, nl_own = 0;
-        if (tail_count_newlines(w.d_text, 0, w.own_lo, d_slot, h_slot, st, &nl_halo) ||
-            tail_count_newlines(w.d_text, w.own_lo, own_hi, d_slot, h_slot, st, &nl_own))
-            return 2;
-        local.local_nl = nl_own;
-        LitPass ps;
-        ps.own_lo = w.own_lo; ps.own_hi = own_hi; ps.sink = LitPass::OCC; ps.post = &pl->post;
-        LitResult lr0;
-        if (lit_pass(pl, w, ps, st, &lr0))
-            return 2;
-        uint64_t lines_counted = 0, cp_out = in.resume, seen_out = in.last_line ? in.last_line : ~0ull;
-        if (lr0.total)
-        {
-            if (lr0.total > pl->nl_cap)
-            {
-                if (pl->d_nl_rec) (void)hipFree(pl->d_nl_rec);
-                if (pl->d_nl_ln) (void)hipFree(pl->d_nl_ln);
-                pl->d_nl_rec = nullptr; pl->d_nl_ln = nullptr; pl->nl_cap = 0;
-                const uint64_t want_n = lr0.total + lr0.total / 4 + 1024;
-                HIPCHK(hipMalloc(&pl->d_nl_rec, want_n * sizeof(match_position_t)));
-                HIPCHK(hipMalloc(&pl->d_nl_ln, want_n * sizeof(uint64_t)));
-                pl->nl_cap = want_n;
-            }
-            if (krep_gpu_line_numbers_ex(w.d_text, w.text_len, w.global_base, (const match_position_t *)pl->post.d_occ, lr0.total, pl->d_nl_ln, st))
-                return 2;
-            const uint32_t k0 = (uint32_t)((const uint8_t *)memchr(pl->pats[0].data(), '\n', m) - pl->pats[0].data());
-            // buffer-relative line numbers (1 + newlines in [0, start)) -> global ones: + newlines in front of the buffer
-            const uint64_t line_off = in.nl_before - nl_halo;
-            if (post_nlwalk(pl->post, w.d_text, w.text_len, algo == KREP_RA_KMP ? kNlWalkKmp : kNlWalkSse42, m, k0, pl->ww,
-                            pl->only_matching, pl->max_count == SIZE_MAX ? ~0ull : (uint64_t)pl->max_count, lr0.total, pl->d_nl_ln,
-                            pl->d_ctr, pl->h_ctr, st, &lines_counted, w.global_base, w.global_len, line_off, in.resume,
-                            in.last_line ? in.last_line : ~0ull, &cp_out, &seen_out))
-                return 2;
-        }
-        if (time_it)
-        {
-            HIPCHK(hipEventRecord(pl->ev1, st));
-            HIPCHK(hipStreamSynchronize(st));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, pl->ev0, pl->ev1));
-            out->kernel_ms = ms;
-        }
-        if (carry_out)
-        {
-            // (the line counted last, relative to own_lo and biased like the multi-pattern record's, so that fold_carry() re-bases it)
-            if (seen_out != ~0ull && seen_out != (in.last_line ? in.last_line : ~0ull))
-                local.local_last = (1ull << 62) + (seen_out - (in.nl_before + 1ull));
-            krep_gpu_seq_carry_t o = kg::fold_carry(in, local);
-            if (!local.local_last)
-                o.last_line = in.last_line;
-            o.resume = std::max<uint64_t>(in.resume, cp_out);
-            *carry_out = o;
-        }
-        out->total_matches = lines_counted;
-        out->line_count = lines_counted;
-        out->has_newline = whole ? 0 : 1; // (pieces: krep_gpu_combine_line_counts adds the counts up, the record has settled the cuts)
-        out->head_line_hit = out->tail_line_hit = whole ? lines_counted != 0 : 0;
-        out->count = lines_counted; // the walk applies max_count the way the functions do (a break before the increment)
-        return 0;
-    }
+        return lit_nlwalk(j, time_it, out);
     // the walks couple neighbouring matches: a window that does not start the text needs the boundary record of the text
     // in front of it (where the reference's scan stands: krep_gpu_seq_carry_t::resume)
-    if (need_walk && !whole && !carry_in && w.global_base + w.own_lo != 0)
+    if (fam.need_walk && !whole && !carry_in && w.global_base + w.own_lo != 0)
         return kg::fail("the greedy / only-matching families couple neighbouring matches: scan the whole text in one window, or "
                         "its pieces in text order through krep_gpu_scan_device_seq() (%s, pattern length %u)",
                         krep_gpu_algorithm_name(algo), m);
 
     // ---- where the block-structured functions put their quirks: positions in the WHOLE text, translated to the buffer
-    uint64_t excl_lo = 0, excl_hi = 0, ww_exempt = ~0ull;
     {
         const uint64_t G = w.global_len, base = w.global_base;
         auto to_local = [&](uint64_t g) -> uint64_t { return g >= base && g - base < w.text_len ? g - base : ~0ull; };
@@ -851,303 +1223,41 @@ static int scan_literal(krep_gpu_plan *pl, int algo, const Window &w, match_posi
             const uint64_t ghi = G - G % 64, glo = ghi - 64;
             if (ghi > base && glo < base + w.text_len)
             {
-                excl_lo = glo > base ? glo - base : 0;
-                excl_hi = std::min<uint64_t>(ghi - base, w.text_len);
+                j.excl_lo = glo > base ? glo - base : 0;
+                j.excl_hi = std::min<uint64_t>(ghi - base, w.text_len);
             }
         }
         if (pl->ww && !pl->lines)
         { // the scalar tail call of the block functions sees the tail as its own text: no left context at its first byte
             const uint64_t B = algo == KREP_RA_AVX2 ? 32 : algo == KREP_RA_AVX512 ? 64 : algo == KREP_RA_NEON ? 16 : 0;
             if (B && (G % B) >= m)
-                ww_exempt = to_local(G - G % B);
+                j.ww_exempt = to_local(G - G % B);
         }
     }
-
-    const uint64_t maxc = pl->max_count;
-    uint64_t want = 0; // records the caller can use
-    if (d_pos && cap && !pl->lines)
+    if (d_pos && cap && !pl->lines) // records the caller can use
     {
-        want = maxc;
+        const uint64_t maxc = pl->max_count;
+        j.want = maxc;
         if ((algo == KREP_RA_KMP || algo == KREP_RA_MEMCHR) && maxc != SIZE_MAX)
-            want = maxc + 1; // KMP stores one more (krep.c:1717); the memchr batch quirk needs the next record too
-        want = std::min<uint64_t>(want, cap);
+            j.want = maxc + 1; // KMP stores one more (krep.c:1717); the memchr batch quirk needs the next record too
+        j.want = std::min<uint64_t>(j.want, cap);
     }
 
     HIPCHK(hipSetDevice(pl->device));
     if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
-    uint64_t total = 0, lines = 0;
-    unsigned long long summary = 0;
-    LitResult lr;
-    bool ev1_recorded = false;
-    if (replay)
-    {
-        // canonical -c over the starts before the last kReplayWindow bytes, then the reference's own walk over the rest
-        const uint64_t G = w.global_len, X = G > kReplayWindow ? G - kReplayWindow : 0;
-        if (!whole)
-        {
-            // ---- a PIECE of the text (krep_gpu_scan_device_seq).  Only the piece that ends the text runs the replay; what it
-            // needs from the text in front of it is the line-skip history {last accepted occurrence q, first '\n' behind it},
-            // which every piece extends (krep_gpu_seq_carry_t) — the piece's own contribution is reported next to the folded
-            // state, so that shards scanned out of order can be folded afterwards.
-            const uint64_t base = w.global_base, B = algo == KREP_RA_AVX512 ? 64 : algo == KREP_RA_AVX2 ? 32 : 16;
-            const bool final_piece = base + own_hi >= G;
-            if (base + w.own_lo != 0 && !carry_in)
-                return kg::fail("-c through %s restarts its block grid at every counted line: scan the whole text in one window, "
-                                "or its pieces in text order through krep_gpu_scan_device_seq()", krep_gpu_algorithm_name(algo));
-            if (final_piece && (base + w.text_len != G || X < base + w.own_lo + B))
-                return kg::fail("-c through %s: the piece that ends the text must hold its last %llu bytes", krep_gpu_algorithm_name(algo),
-                                (unsigned long long)(kReplayWindow + B));
-            const uint64_t lim = final_piece ? X - base : own_hi; // the canonical pass covers the starts in [own_lo, lim)
-            const uint64_t nl_end = final_piece ? w.text_len : own_hi; // where this piece's newline searches stop
-            unsigned long long *d_slot = &pl->d_ctr->pad[0], *h_slot = &pl->h_ctr->pad[0];
-            if (lim > w.own_lo)
-            {
-                LitPass ps;
-                ps.ww = pl->ww; ps.lines = true; ps.own_lo = w.own_lo; ps.own_hi = lim; ps.post = &pl->post;
-                if (lit_pass(pl, w, ps, st, &lr))
-                    return 2;
-            }
-            const krep_gpu_seq_carry_t in = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
-            krep_gpu_seq_carry_t pc{}; // this piece's own contribution
-            bool have_q = false;
-            uint64_t q = 0;
-            if (lim > w.own_lo && last_accepted_before(pl, w, lr, w.own_lo, lim, st, &have_q, &q))
-                return 2;
-            {
-                uint64_t nl = nl_end; // first newline of the piece (the record of a piece without an occurrence; neon_search's kind 2)
-                if ((!have_q || algo == KREP_RA_NEON) && tail_find_next_newline(w.d_text, w.own_lo, nl_end, d_slot, h_slot, st, &nl))
-                    return 2;
-                pc.local_first_nl1 = nl < nl_end ? base + nl + 1 : 0;
-            }
-            if (have_q)
-            {
-                uint64_t nl = nl_end;
-                if (tail_find_next_newline(w.d_text, q, nl_end, d_slot, h_slot, st, &nl))
-                    return 2;
-                pc.local_q1 = base + q + 1;
-                pc.local_nl1 = nl < nl_end ? base + nl + 1 : 0;
-                if (algo == KREP_RA_NEON)
-                {
-                    // the grid origin in effect for q's line: (first newline behind the last accepted occurrence on an earlier
-                    // line) + 1 — from this piece if that occurrence lies in it, else from the record in front of it
-                    uint64_t lsp1 = 0;
-                    if (tail_find_prev_newline(w.d_text, q, d_slot, h_slot, st, &lsp1))
-                        return 2;
-                    if (lsp1 <= w.own_lo) // no newline in [own_lo, q): q's line started in front of this piece
-                        pc.local_g0_kind = 3;
-                    else
-                    {
-                        bool have_q2 = false;
-                        uint64_t q2 = 0;
-                        if (last_accepted_before(pl, w, lr, w.own_lo, lsp1, st, &have_q2, &q2))
-                            return 2;
-                        if (!have_q2)
-                            pc.local_g0_kind = 2;
-                        else
-                        {
-                            uint64_t nl2 = nl_end;
-                            if (tail_find_next_newline(w.d_text, q2, nl_end, d_slot, h_slot, st, &nl2))
-                                return 2;
-                            pc.local_g0_kind = 1;
-                            pc.local_g0 = base + nl2 + 1; // nl2 < lsp1 <= q: it exists
-                        }
-                    }
-                }
-            }
-            if (final_piece)
-                pc.local_lines = lr.lines + 1; // (what krep_gpu_replay_tail() starts from when the record turns out different)
-            const krep_gpu_seq_carry_t co = kg::fold_carry(in, pc);
-            if (carry_out)
-                *carry_out = co;
-            total = lr.total; lines = lr.lines; summary = lr.summary;
-            if (final_piece)
-            {
-                uint64_t extra = 0;
-                if (replay_from_record(pl, algo, co, rebased(w.d_text, base), base ? base + 1 : 0, G, st, &extra)) // (global offsets >= cur - 1 >= base: inside the buffer)
-                    return 2;
-                // the lines the replay counts are new ones (it starts behind the line of q), and the line open at the piece's
-                // start can only be among them when nothing in front of the piece counted it: the canonical head bit stands
-                lines = lr.lines + extra;
-                total = lines;
-            }
-        }
-        else
-        {
-            uint64_t cur = 0, extra = 0;
-            int open = 0;
-            if (X)
-            {
-                LitPass ps;
-                ps.ww = pl->ww; ps.lines = true; ps.own_lo = 0; ps.own_hi = X; ps.post = &pl->post;
-                if (lit_pass(pl, w, ps, st, &lr))
-                    return 2;
-                if (replay_entry(pl, algo, w, lr, X, st, &cur, &open))
-                    return 2;
-            }
-            ReplayIn r{};
-            r.algo = algo; r.m = m; r.ww = pl->ww; r.n = G; r.cur = cur; r.open = open;
-            r.text = w.d_text; r.pat = pl->d_pat;
-            if (cur < G && tail_run_replay(r, &pl->d_ctr->pad[0], &pl->h_ctr->pad[0], st, &extra))
-                return 2;
-            lines = lr.lines + extra;
-            total = lines; // occurrence totals are not defined by a -c scan
-            summary = lines ? (kLnHead | kLnTail) : 0;
-        }
-    }
-    else if (!need_walk)
-    {
-        if (fam.neon_zero)
-        {
-            // count-only with max_count == 0: the first body hit returns 0 (krep.c:4616); with no body hit the tail call's
-            // BMH returns 1 on its first hit (krep.c:1355-1367)
-            const uint64_t G = w.global_len, T = G - G % 16;
-            if (!whole)
-                return kg::fail("neon_search with max_count == 0 needs the whole text in one window");
-            LitPass ps;
-            ps.ww = pl->ww; ps.own_lo = 0; ps.own_hi = T; ps.ww_exempt = ww_exempt; ps.post = &pl->post;
-            if (lit_pass(pl, w, ps, st, &lr))
-                return 2;
-            uint64_t ret = 0;
-            if (lr.total == 0 && G - T >= m)
-            {
-                ps.own_lo = T; ps.own_hi = G;
-                if (lit_pass(pl, w, ps, st, &lr))
-                    return 2;
-                ret = lr.total ? 1 : 0;
-            }
-            if (time_it) HIPCHK(hipEventRecord(pl->ev1, st));
-            HIPCHK(hipStreamSynchronize(st));
-            out->count = ret;
-            out->total_matches = lr.total;
-            return 0;
-        }
-        LitPass ps;
-        ps.ww = pl->ww; ps.lines = pl->lines; ps.own_lo = w.own_lo; ps.own_hi = own_hi;
-        ps.excl_lo = excl_lo; ps.excl_hi = excl_hi; ps.ww_exempt = ww_exempt;
-        ps.sink = want ? LitPass::RECORDS : LitPass::COUNT;
-        ps.d_out = (uint64_t *)d_pos; ps.out_cap = want; ps.post = &pl->post;
-        ps.ev_end = time_it ? pl->ev1 : nullptr;
-        if (lit_pass(pl, w, ps, st, &lr))
-            return 2;
-        ev1_recorded = time_it != 0 && lr.n_units != 0;
-        total = lr.total; lines = lr.lines; summary = lr.summary;
-    }
+    LitTotals t;
+    int rc;
+    if (fam.replay)
+        rc = whole ? lit_replay_whole(j, &t) : lit_replay_piece(j, &t);
+    else if (fam.need_walk)
+        rc = lit_walk(j, fam, &t);
+    else if (fam.neon_zero)
+        return lit_neon_zero(j, time_it, out); // (fills `out` itself)
     else
-    {
-        // sequential families on the ordered list (kg_greedy.hip): greedy non-overlapping selection (SSE4.2 / KMP, and BMH
-        // under -o) over all occurrences, or memchr_short's -o walk over the first-byte candidates.  A window inside the text
-        // starts where the reference's scan stands (carry_in->resume): starts in front of that point are consumed, the first
-        // one at or behind it is looked at afresh — exactly what the reference's loop does after `advance`.
-        const bool ww_first = pl->ww && algo == KREP_RA_BMH; // BMH -o: a -w rejected hit does not consume (krep.c:1323-1329)
-        const uint64_t resume_in = carry_in ? carry_in->resume : 0;
-        size_t lo_eff = w.own_lo;
-        if (resume_in > w.global_base + w.own_lo)
-            lo_eff = (size_t)std::min<uint64_t>(own_hi, resume_in - w.global_base);
-        uint64_t resume_out = 0;
-        // ---- a pattern of ONE repeated byte (`  `, `--`, `aa`), counted: inside a run of R such bytes the kept matches start at every
-        // m-th byte — no list of all occurrences (kg_runs.hip; round 6: `-c -o '  '` materialised 188 M occurrences at 0.65 TB/s)
-        bool runs_done = false;
-        if (!mshort_o && !pl->ww && !pl->lines && want == 0 && m >= 2 && !getenv("KREP_GPU_NO_RUNS"))
-        {
-            bool uniform = true;
-            for (uint32_t i = 1; i < m; ++i)
-                uniform = uniform && pl->pat_folded[i] == pl->pat_folded[0];
-            if (uniform)
-            {
-                uint64_t end_p1 = 0;
-                const int rc = runs_count_greedy(w.d_text, w.text_len, lo_eff, own_hi, m, pl->pat_folded[0], !pl->cs, pl->num_cu, &pl->d_ctr->pad[1],
-                                                 &pl->h_ctr->pad[1], st, &total, &end_p1);
-                if (rc == 2)
-                    return 2;
-                if (rc == 0)
-                {
-                    runs_done = true;
-                    resume_out = end_p1 ? w.global_base + end_p1 : 0;
-                }
-            }
-        }
-        LitPass ps;
-        ps.own_lo = lo_eff; ps.own_hi = own_hi; ps.sink = LitPass::OCC; ps.post = &pl->post;
-        ps.first_byte = mshort_o;
-        ps.ww = ww_first;
-        if (!runs_done && lit_pass(pl, w, ps, st, &lr))
-            return 2;
-        WalkSpec ws{};
-        ws.mode = mshort_o ? (pl->lines ? kWalkShortOLines : kWalkShortO) : kWalkGreedy;
-        if (ws.mode == kWalkShortOLines && !whole)
-            return kg::fail("-c -o through memchr_short_search jumps to the next line start after every counted line: scan the whole "
-                            "text in one window");
-        ws.m = m;
-        ws.ww = pl->ww && !ww_first;
-        ws.lines = pl->lines;
-        ws.ci = !pl->cs;
-        ws.b1 = m > 1 ? pl->pat_folded[1] : 0;
-        ws.b2 = m > 2 ? pl->pat_folded[2] : 0;
-        if (lr.total)
-        {
-            HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-            int rc = post_walk(pl->post, w.d_text, w.text_len, w.global_base, ws, lr.total, (uint64_t *)d_pos, want, pl->d_ctr,
-                               pl->h_ctr, st, &total, &lines, &resume_out);
-            if (rc)
-                return rc;
-        }
-        if (carry_out)
-            carry_out->resume = std::max(resume_in, resume_out);
-        summary = total ? (kLnHead | kLnTail) : 0;
-        if (pl->lines && !whole)
-        {
-            // line bits of the owned window for the left-to-right fold over the pieces (krep_gpu_combine_line_counts): is there
-            // a '\n' in [own_lo, own_hi), does a survivor start at or before the first / behind the last one
-            unsigned long long *d_slot = &pl->d_ctr->pad[0], *h_slot = &pl->h_ctr->pad[0];
-            uint64_t first_nl = own_hi, last_p1 = 0;
-            if (tail_find_next_newline(w.d_text, w.own_lo, own_hi, d_slot, h_slot, st, &first_nl))
-                return 2;
-            summary = 0;
-            if (first_nl < own_hi)
-            {
-                if (tail_find_prev_newline(w.d_text, own_hi, d_slot, h_slot, st, &last_p1))
-                    return 2;
-                summary |= kLnNl;
-            }
-            if (total)
-            {
-                uint64_t s_first[2], s_last[2]; // the survivors were compacted into post.d_surv for the line count
-                HIPCHK(hipMemcpy(s_first, pl->post.d_surv, sizeof s_first, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(s_last, pl->post.d_surv + 2 * (total - 1), sizeof s_last, hipMemcpyDeviceToHost));
-                const uint64_t f = s_first[0] - w.global_base, l = s_last[0] - w.global_base;
-                if (!(summary & kLnNl))
-                    summary |= kLnHead | kLnTail;
-                else
-                    summary |= (f <= first_nl ? kLnHead : 0) | (l >= last_p1 ? kLnTail : 0);
-            }
-        }
-    }
-    if (time_it)
-    {
-        if (!ev1_recorded) HIPCHK(hipEventRecord(pl->ev1, st));
-        HIPCHK(hipStreamSynchronize(st));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, pl->ev0, pl->ev1));
-        out->kernel_ms = ms;
-    }
-    else
-        HIPCHK(hipStreamSynchronize(st));
-    out->total_matches = total;
-    out->line_count = lines;
-    out->has_newline = (summary & kLnNl) != 0;
-    out->head_line_hit = (summary & kLnHead) != 0;
-    out->tail_line_hit = (summary & kLnTail) != 0;
-    Verdict v = verdict_for(algo, pl, total, lines, d_pos != nullptr);
-    out->count = v.ret;
-    if (d_pos && cap && pl->track && !pl->lines)
-    {
-        // records the reference semantics need (memchr: one more than max_count, the host fixes the order)
-        const uint64_t needed = (algo == KREP_RA_MEMCHR && maxc != SIZE_MAX && maxc != 0) ? std::min<uint64_t>(total, maxc + 1)
-                                                                                           : v.store;
-        out->overflow = needed > cap;
-        out->stored = std::min<uint64_t>(needed, std::min<uint64_t>(total, want));
-    }
-    return 0;
+        rc = lit_plain(j, time_it, &t);
+    if (rc)
+        return rc;
+    return lit_finish(j, time_it, t, out);
 }
 
 // aho_corasick_search -c when a pattern contains '\n': matches are visited in emission order (end ascending, longest
@@ -1188,20 +1298,8 @@ static int scan_ac_newline_lines(krep_gpu_plan *pl, const Window &w, hipStream_t
     local.local_nl = nl_own;
     if (total)
     {
-        if (total > pl->nl_cap) // grow-only scratch of the plan (no allocation per call)
-        {
-            if (pl->d_nl_rec) (void)hipFree(pl->d_nl_rec);
-            if (pl->d_nl_ln) (void)hipFree(pl->d_nl_ln);
-            pl->d_nl_rec = nullptr;
-            pl->d_nl_ln = nullptr;
-            pl->nl_cap = 0;
-            const uint64_t want = total + total / 4 + 1024;
-            HIPCHK(hipMalloc(&pl->d_nl_rec, want * sizeof(match_position_t)));
-            HIPCHK(hipMalloc(&pl->d_nl_ln, want * sizeof(uint64_t)));
-            pl->nl_cap = want;
-        }
-        if (!pl->d_nl_ln) // (the list road of plain -c sizes only the records)
-            HIPCHK(hipMalloc(&pl->d_nl_ln, pl->nl_cap * sizeof(uint64_t)));
+        if (nl_reserve(pl, total, total + total / 4 + 1024, true))
+            return 2;
         match_position_t *d_rec = pl->d_nl_rec;
         uint64_t *d_ln = pl->d_nl_ln;
         rc = ac_scan(pl->ac, pl->d_ctr, pl->h_ctr, pl->post, pl->num_cu, w.d_text, w.text_len, w.own_lo, own_hi, w.global_base, d_rec, total,
@@ -1223,14 +1321,8 @@ static int scan_ac_newline_lines(krep_gpu_plan *pl, const Window &w, hipStream_t
             changes -= 1; // the first match of this piece starts on the line of the text's last match so far: not counted again
         local.local_last = last_rel;
     }
-    if (time_it)
-    {
-        HIPCHK(hipEventRecord(pl->ev1, st));
-        HIPCHK(hipStreamSynchronize(st));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, pl->ev0, pl->ev1));
-        out->kernel_ms = ms;
-    }
+    if (time_it && stop_clock(pl, true, st, out))
+        return 2;
     leave();
     out->total_matches = total;
     out->line_count = changes;
@@ -1334,17 +1426,10 @@ static int scan_ac_split(krep_gpu_plan *pl, const uint8_t *d_text, size_t text_l
     if (limited)
     {
         const uint64_t need = 2 * (uint64_t)pl->max_count;
-        if (need > pl->split_cap)
+        if (grow_scratch(pl->split_cap, need, need, {dev_buf(pl->d_split_rec, need * sizeof(match_position_t))}) != hipSuccess)
         {
-            if (pl->d_split_rec) (void)hipFree(pl->d_split_rec);
-            pl->d_split_rec = nullptr;
-            pl->split_cap = 0;
-            if (hipMalloc(&pl->d_split_rec, need * sizeof(match_position_t)) != hipSuccess)
-            {
-                (void)hipGetLastError();
-                return 1; // (no room for the scratch list: one scan of the whole dictionary)
-            }
-            pl->split_cap = need;
+            (void)hipGetLastError();
+            return 1; // (no room for the scratch list: one scan of the whole dictionary)
         }
         dst = pl->d_split_rec;
         room = need;
@@ -1415,12 +1500,8 @@ static int scan_ac_lines_on_list(krep_gpu_plan *pl, const Window &w, hipStream_t
     const uint64_t dense = w.text_len / (ac_counts_lines_in_registers(pl->ac) ? 1000 : 400) + 4096;
     if (pl->lines_list_off)
         return 1;
-    if (pl->nl_cap == 0)
-    {
-        const uint64_t want = std::max<uint64_t>(w.text_len / 1024, 1u << 16);
-        HIPCHK(hipMalloc(&pl->d_nl_rec, want * sizeof(match_position_t)));
-        pl->nl_cap = want;
-    }
+    if (nl_reserve(pl, 1, std::max<uint64_t>(w.text_len / 1024, 1u << 16), false))
+        return 2;
     krep_gpu_scan_out_t o1;
     for (int attempt = 0;; ++attempt)
     {
@@ -1471,14 +1552,9 @@ static int scan_ac_lines_on_list(krep_gpu_plan *pl, const Window &w, hipStream_t
         }
         if (!o1.overflow || attempt == 1)
             break;
-        if (pl->d_nl_rec) (void)hipFree(pl->d_nl_rec);
-        if (pl->d_nl_ln) (void)hipFree(pl->d_nl_ln); // (the other user of the list sizes both)
-        pl->d_nl_rec = nullptr;
-        pl->d_nl_ln = nullptr;
-        pl->nl_cap = 0;
-        const uint64_t want = o1.total_matches + o1.total_matches / 8 + 1024;
-        HIPCHK(hipMalloc(&pl->d_nl_rec, want * sizeof(match_position_t)));
-        pl->nl_cap = want;
+        // (whatever nl_cap says: the list overflowed)
+        if (nl_reserve(pl, pl->nl_cap + 1, o1.total_matches + o1.total_matches / 8 + 1024, false))
+            return 2;
     }
     const uint64_t total = o1.total_matches;
     uint64_t lines = o1.line_count; // counted behind the post-pass on the stream, unless some unit overflowed its staging slot
@@ -1505,13 +1581,8 @@ static int scan_ac_lines_on_list(krep_gpu_plan *pl, const Window &w, hipStream_t
         head = ends[0].start_offset - w.global_base < first_nl;
         tail = ends[1].start_offset - w.global_base >= last_nl1;
     }
-    if (time_it)
-    {
-        HIPCHK(hipStreamSynchronize(st));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, pl->ev0, pl->ev1));
-        out->kernel_ms = ms;
-    }
+    if (time_it && stop_clock(pl, false, st, out)) // (ev1: behind the line count above)
+        return 2;
     out->total_matches = total;
     out->line_count = lines;
     out->has_newline = has_nl;

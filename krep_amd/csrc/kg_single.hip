@@ -35,7 +35,7 @@
 // SIMD; the table is in front of launch_shape below): from 128-KiB tickets / 8 KiB of ring / 16 waves per CU for up to ~1.2 % hits
 // (BASELINE config 3) to 32-KiB tickets / 32 KiB / 4 waves for up to ~20 % (80 tickets per microsecond is what one counter gives:
 // fine while the records, 16 bytes per hit, are most of the traffic).  The host picks the shape from the density the
-// first scan of a plan counted (kg_scan.hip, lit_pass) and falls back to the two-pass kernels beyond that.
+// first scan of a plan counted (single_fused_run, below) and falls back to the two-pass kernels beyond that.
 // SET: up to four needle bytes instead of one — a dictionary of single-byte patterns (`-e e -e t`) is this scan with a set
 // (aho_corasick_search reports such matches in text order, one per position: the records are memchr_search's).
 #include <hip/hip_runtime.h>
@@ -98,7 +98,7 @@ __device__ __noinline__ uint4 s_load16_guarded(const uint8_t *text, u64 text_len
 // lit_scan's (kg_literal.hip: the 16 start positions of a lane compared in registers against the pattern's first word, and its
 // second word where the pattern is longer than four bytes); the 8 bytes behind a lane come from its right neighbour, behind the
 // round from one extra 8-byte load.  For DENSE short literals with records (`-i sh`: 35 hits per 32-KiB unit, ` a`: 180), whose
-// staging slots overflow and whose text the two-pass kernels then read twice: chosen by lit_pass from the density a scan counted.
+// staging slots overflow and whose text the two-pass kernels then read twice: chosen by kg_scan.hip from the density a scan counted.
 // BDRAW (round 5, the shapes with 32-KiB tickets): ONE draw per WORKGROUP — thread 0 fetches kWavesPerBlk consecutive tickets, a
 // barrier hands wave w ticket base + w, the four waves start their tickets together.  The one counter gives ~65 draws per
 // microsecond (same-address atomics serialise in one L2 channel): a million 32-KiB tickets are 15 ms whatever the text holds.
@@ -515,8 +515,8 @@ static hipError_t launch_fused(const LitArgs &a, u64 *agg, u64 *pref, u64 n_tick
 constexpr u32 kRingMid = 6144u;
 static u32 shape_upt(int shape) { return shape == 0 ? kUptStd : (shape <= 2 ? 2u : 1u); }
 static u32 shape_ring(int shape) { return shape == 0 ? kRingStd : (shape == 5 ? kRingDensest : ((shape & 1) ? kRingMid : kRingDense)); }
-uint64_t single_fused_tickets(uint64_t n_units, int shape) { return (n_units + shape_upt(shape) - 1) / shape_upt(shape); }
-uint64_t single_fused_scratch_words(uint64_t n_tickets) { return 2 * n_tickets; } // counts | prefixes
+static uint64_t single_fused_tickets(uint64_t n_units, int shape) { return (n_units + shape_upt(shape) - 1) / shape_upt(shape); }
+static uint64_t single_fused_scratch_words(uint64_t n_tickets) { return 2 * n_tickets; } // counts | prefixes
 // the densest text (hits per byte) a shape's ring is sure to hold
 double single_fused_max_density(int shape)
 {
@@ -560,6 +560,54 @@ hipError_t launch_single_fused(const LitArgs &a, unsigned long long *d_agg, unsi
                   : launch_shape<false, true>(a, d_agg, d_pref, n_tickets, num_cu, shape, st);
     return ci ? launch_shape<true, false>(a, d_agg, d_pref, n_tickets, num_cu, shape, st)
               : launch_shape<false, false>(a, d_agg, d_pref, n_tickets, num_cu, shape, st);
+}
+
+// ---- the shape rules, shared by the literal scan (kg_scan.hip lit_first_look, lit_one_pass, lit_learn_density, lit_reopen) and the
+// byte-set dictionaries (kg_ac.hip ac_scan)
+int single_fused_shape_for(double density, double margin, int start)
+{
+    int shape = start;
+    while (shape < kFusedShapeMax && margin * density > single_fused_max_density(shape))
+        ++shape;
+    return shape;
+}
+bool single_fused_reopens(uint64_t total, uint64_t span)
+{
+    return span && (double)total / (double)span < 0.5 * single_fused_max_density(kFusedShapeMax);
+}
+int single_fused_run(const LitArgs &a, uint64_t n_units, uint64_t span, PostScratch &post, Counters *d_ctr, Counters *h_ctr,
+                     uint32_t num_cu, int *shape_io, hipEvent_t ev_end, hipStream_t st, bool count_launch)
+{
+    for (;;)
+    {
+        const int shape = *shape_io;
+        const uint64_t n_tk = single_fused_tickets(n_units, shape);
+        const size_t tk_bytes = single_fused_scratch_words(n_tk) * sizeof(unsigned long long);
+        HIPCHK(grow_scratch(post.tk_cap, n_tk, n_tk, {dev_buf(post.d_tk, tk_bytes)}));
+        HIPCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
+        HIPCHK(hipMemsetAsync(post.d_tk, 0, tk_bytes, st));
+        HIPCHK(launch_single_fused(a, post.d_tk, post.d_tk + n_tk, n_tk, num_cu, shape, st));
+        if (count_launch)
+            g_fused1_launches.fetch_add(1);
+        if (ev_end) HIPCHK(hipEventRecord(ev_end, st));
+        HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const double density = (double)h_ctr->total / (double)span;
+        if (!h_ctr->overflow_units)
+        {
+            // the decision is re-evaluated by every scan: a text half as dense as the next smaller shape holds
+            // sends the following scans back to it (larger tickets, more waves per CU)
+            if (shape > 0 && density < 0.5 * single_fused_max_density(shape - 1))
+                *shape_io = shape - 1;
+            return 0;
+        }
+        // the scan counted every ticket (the resolver's running sum): the density chooses the shape — unless the spin-limit
+        // safety net fired (then the total is not to be trusted and the two-pass kernels take over)
+        const int next = shape < kFusedShapeMax ? single_fused_shape_for(density, 1.0, shape + 1) : shape;
+        if (next == shape || density > single_fused_max_density(next) || h_ctr->total == 0)
+            return kFusedGaveUp;
+        *shape_io = next;
+    }
 }
 
 } // namespace kg

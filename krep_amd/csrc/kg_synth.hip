@@ -8,14 +8,6 @@
 
 using namespace kg;
 
-#define HIPCHK(x)                                                                             \
-    do                                                                                        \
-    {                                                                                         \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess)                                                                 \
-            return kg::fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 // ------------------------------------------------------------------------------------ generators
 __global__ void synth_kernel(uint8_t *dst, size_t len, size_t goff, int kind, uint64_t seed, const uint8_t *plant,
                              uint64_t plen, uint64_t period)

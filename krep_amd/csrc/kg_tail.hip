@@ -15,14 +15,6 @@ namespace kg {
 using u32 = uint32_t;
 using u64 = unsigned long long;
 
-#define TCHK(x)                                                                                \
-    do                                                                                         \
-    {                                                                                          \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess)                                                                  \
-            return fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 // out[0] = 1 + index of the last unit u < limit whose info word reports a hit (0 = none)
 __global__ __launch_bounds__(256) void tail_last_hit_unit(const u64 *__restrict__ info, u64 limit, u64 *out)
 {
@@ -263,15 +255,15 @@ __global__ void tail_replay(ReplayIn r, u64 *out)
 int tail_last_hit(const unsigned long long *d_unitinfo, uint64_t limit_units, unsigned long long *d_slot,
                   unsigned long long *h_slot, hipStream_t st, uint64_t *unit_plus1)
 {
-    TCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
+    HIPCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
     if (limit_units)
     {
         const u32 grid = (u32)std::min<u64>((limit_units + 255) / 256, 1024);
         hipLaunchKernelGGL(tail_last_hit_unit, dim3(grid), dim3(256), 0, st, (const u64 *)d_unitinfo, (u64)limit_units, (u64 *)d_slot);
-        TCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
-    TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     *unit_plus1 = *h_slot;
     return 0;
 }
@@ -283,21 +275,21 @@ int tail_find_next_newline(const uint8_t *d_text, uint64_t from, uint64_t n, uns
     if (from >= n)
         return 0;
     *h_slot = n; // pinned: the sentinel "no newline"
-    TCHK(hipMemcpyAsync(d_slot, h_slot, sizeof(u64), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_slot, h_slot, sizeof(u64), hipMemcpyHostToDevice, st));
     // one workgroup on the first chunk (a line ends within a few hundred bytes in any text worth counting lines in); the wide
     // sweep only when that chunk holds none
     const u64 chunks = (n - (from & ~15ull) + kNlChunk - 1) / kNlChunk;
     hipLaunchKernelGGL(tail_next_newline, dim3(1), dim3(256), 0, st, d_text, (u64)from, (u64)std::min<u64>(n, (from & ~15ull) + kNlChunk), (u64 *)d_slot);
-    TCHK(hipGetLastError());
-    TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     if (*h_slot == n && chunks > 1)
     {
         hipLaunchKernelGGL(tail_next_newline, dim3((u32)std::min<u64>(chunks - 1, 1024)), dim3(256), 0, st, d_text,
                            (u64)((from & ~15ull) + kNlChunk), (u64)n, (u64 *)d_slot);
-        TCHK(hipGetLastError());
-        TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-        TCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
     *pos = *h_slot;
     return 0;
@@ -309,18 +301,18 @@ int tail_find_prev_newline(const uint8_t *d_text, uint64_t before, unsigned long
     *pos_plus1 = 0;
     if (before == 0)
         return 0;
-    TCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
+    HIPCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
     const u64 chunks = (((before + 15ull) & ~15ull) + kNlChunk - 1) / kNlChunk;
     hipLaunchKernelGGL(tail_prev_newline, dim3(1), dim3(256), 0, st, d_text, (u64)before, (u64)1, (u64 *)d_slot); // (the last chunk first)
-    TCHK(hipGetLastError());
-    TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     if (*h_slot == 0 && chunks > 1)
     {
         hipLaunchKernelGGL(tail_prev_newline, dim3((u32)std::min<u64>(chunks, 1024)), dim3(256), 0, st, d_text, (u64)before, ~0ull, (u64 *)d_slot);
-        TCHK(hipGetLastError());
-        TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-        TCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
     *pos_plus1 = *h_slot;
     return 0;
@@ -329,15 +321,15 @@ int tail_find_prev_newline(const uint8_t *d_text, uint64_t before, unsigned long
 int tail_count_changes(const uint64_t *d_v, uint64_t n, unsigned long long *d_slot, unsigned long long *h_slot, hipStream_t st,
                        uint64_t *changes)
 {
-    TCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
+    HIPCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
     if (n)
     {
         const u32 grid = (u32)std::min<u64>((n + 255) / 256, 2048);
         hipLaunchKernelGGL(tail_changes, dim3(grid), dim3(256), 0, st, (const u64 *)d_v, (u64)n, (u64 *)d_slot);
-        TCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
-    TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     *changes = *h_slot;
     return 0;
 }
@@ -345,16 +337,16 @@ int tail_count_changes(const uint64_t *d_v, uint64_t n, unsigned long long *d_sl
 int tail_count_line_gaps(const uint8_t *d_text, uint64_t text_len, uint64_t global_base, const uint64_t *d_rec, uint64_t n, unsigned long long *d_slot,
                          unsigned long long *h_slot, hipStream_t st, uint64_t *lines)
 {
-    TCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
+    HIPCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
     if (n)
     {
         const u32 grid = (u32)std::min<u64>((n + 255) / 256, 8192);
         hipLaunchKernelGGL(tail_line_gaps, dim3(grid), dim3(256), 0, st, d_text, (u64)text_len, (const u64 *)d_rec, (u64)n, (const u64 *)nullptr,
                            (const u64 *)nullptr, (u64)global_base, (u64 *)d_slot);
-        TCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
-    TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     *lines = *h_slot;
     return 0;
 }
@@ -368,7 +360,7 @@ int tail_launch_line_gaps(const uint8_t *d_text, uint64_t text_len, uint64_t glo
     const u32 grid = (u32)std::min<u64>((cap + 255) / 256, 8192);
     hipLaunchKernelGGL(tail_line_gaps, dim3(grid), dim3(256), 0, st, d_text, (u64)text_len, (const u64 *)d_rec, (u64)cap, (const u64 *)d_n,
                        (const u64 *)d_skip_if, (u64)global_base, (u64 *)d_out);
-    TCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -378,12 +370,12 @@ int tail_count_newlines(const uint8_t *d_text, uint64_t lo, uint64_t hi, unsigne
     *count = 0;
     if (lo >= hi)
         return 0;
-    TCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
+    HIPCHK(hipMemsetAsync(d_slot, 0, sizeof(u64), st));
     const u32 grid = (u32)std::min<u64>(((hi - lo) / 16 + 255) / 256 + 1, 2048);
     hipLaunchKernelGGL(tail_newlines, dim3(grid), dim3(256), 0, st, d_text, (u64)lo, (u64)hi, (u64 *)d_slot);
-    TCHK(hipGetLastError());
-    TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     *count = *h_slot;
     return 0;
 }
@@ -391,9 +383,9 @@ int tail_count_newlines(const uint8_t *d_text, uint64_t lo, uint64_t hi, unsigne
 int tail_run_replay(const ReplayIn &r, unsigned long long *d_slot, unsigned long long *h_slot, hipStream_t st, uint64_t *lines)
 {
     hipLaunchKernelGGL(tail_replay, dim3(1), dim3(64), 0, st, r, (u64 *)d_slot);
-    TCHK(hipGetLastError());
-    TCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_slot, d_slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     *lines = *h_slot;
     return 0;
 }
