@@ -1064,10 +1064,6 @@ __global__ void ac_redo_list_kernel(const u64 *__restrict__ info, u64 n_units, u
 // ---------------------------------------------------------------------------------------------- host: launches and the scan driver
 // (the tables: kg_ac_tables.h, built by kg_ac_build.hip)
 
-int g_ac_force_stage_cap = 0; // test hook (krep_gpu_debug_force_stage_cap)
-
-bool ac_counts_lines_in_registers(const AcTables *t) { return t && t->tiny.ok && !t->tiny.five; }
-
 static u32 ac_lds_bytes(u32 filter_words, bool lines)
 {
     const u32 per_wave = kAcBitmapWords + (lines ? 2u * kAcBitmapWords : 0u);
@@ -1081,23 +1077,9 @@ static hipError_t ac_launch3(const AcArgs &a, u32 grid, u32 lds, hipStream_t st)
     if constexpr (!WW && STRIDE == 2 && !SHORT)
         if (a.flags & F_WW)
             return ac_launch3<CI, LN, SHORT, STRIDE, ANCH, true>(a, grid, lds, st);
-    // more than 64 KiB of dynamic LDS has to be requested explicitly — once per instantiation and device, not on every launch
-    // (the call sits on the latency path of small host buffers), and always for the MOST this kernel can ask for (the whole
-    // 160 KiB of a CU), so that no later, larger request can find a stale grant.  Atomic flags: concurrent scans from several
-    // host threads may launch the same instantiation; devices beyond the table simply set it every time.
-    constexpr int kMaxDev = 64;
-    static std::atomic<bool> granted[kMaxDev];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDev || !granted[dev].load(std::memory_order_acquire))
-    {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ac_scan_kernel<CI, LN, SHORT, STRIDE, ANCH, WW>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAcMaxLds);
-        if (e != hipSuccess)
-            return e;
-        if (dev >= 0 && dev < kMaxDev)
-            granted[dev].store(true, std::memory_order_release);
-    }
+    // (always the MOST this kernel can ask for, the whole 160 KiB of a CU: no later, larger request can find a stale grant)
+    if (const hipError_t e = grant_dynamic_lds<&ac_scan_kernel<CI, LN, SHORT, STRIDE, ANCH, WW>>((int)kAcMaxLds); e != hipSuccess)
+        return e;
     hipLaunchKernelGGL((ac_scan_kernel<CI, LN, SHORT, STRIDE, ANCH, WW>), dim3(grid), dim3(kAcBlock), lds, st, a);
     return hipGetLastError();
 }
@@ -1124,81 +1106,81 @@ static hipError_t ac_launch(const AcArgs &a, u32 grid, u32 lds, hipStream_t st)
     return ac_launch2<false, false>(a, grid, lds, st);
 }
 
-int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, int num_cu, const uint8_t *d_text, size_t text_len,
-            size_t own_lo, size_t own_hi, size_t global_base, match_position_t *d_pos, uint64_t cap, bool ww, bool lines,
-            bool track, size_t max_count, hipStream_t st, int time_it, hipEvent_t ev0, hipEvent_t ev1, krep_gpu_scan_out_t *out,
-            int list_mode)
+// one ac_scan call as its steps see it (kAcNext: a step hands the scan on to the next)
+struct AcRun
 {
-    // list_mode 1: the record list multi-pattern -c is counted on (END-owned, line gaps counted behind the post-pass);
-    // 2: END-owned records only (the emission-order list of -c with a newline inside a pattern: kg_scan.hip)
-    const bool lines_on_list = list_mode == 1, own_by_end = list_mode != 0;
-    memset(out, 0, sizeof *out);
-    if (max_count == 0) // aho_corasick.c:316
+    AcArgs a{};
+    size_t own_hi = 0; // the caller's own range ends here (clipped to the text); a.own_* is the whole buffer for END-owned records
+    u64 want = 0;      // records wanted: min(cap, max_count) (0: counts or -c)
+    bool lines_on_list = false; // AcOwn::LinesOnList
+    int fsc = 0;       // krep_gpu_debug_force_stage_cap (0: the dictionary's own slot)
+    bool tiny = false; // the staged road: the register-compare kernel (kg_ac_tiny.hip), else the general one
+};
+constexpr int kAcNext = -1;
+// max_count 0, the empty text (its one empty match), an empty own range, -c with a newline inside a pattern
+static int ac_early_out(const AcScan &c, size_t own_hi, krep_gpu_scan_out_t *out)
+{
+    if (c.max_count == 0) // aho_corasick.c:316
         return 0;
-    if (own_hi > text_len)
-        own_hi = text_len;
-    if (text_len == 0)
+    if (c.text_len == 0)
     {
         // the empty pattern matches the empty text once (aho_corasick.c:441-463)
-        if (t->has_empty)
-        {
+        if (c.t->has_empty)
             out->count = out->total_matches = 1;
-            if (d_pos && cap && track)
-            {
-                const match_position_t z{global_base, global_base};
-                HIPCHK(hipMemcpyAsync(d_pos, &z, sizeof z, hipMemcpyHostToDevice, st));
-                HIPCHK(hipStreamSynchronize(st));
-                out->stored = 1;
-            }
+        if (c.t->has_empty && c.d_pos && c.cap && c.track)
+        {
+            const match_position_t z{c.global_base, c.global_base};
+            HIPCHK(hipMemcpyAsync(c.d_pos, &z, sizeof z, hipMemcpyHostToDevice, c.st));
+            HIPCHK(hipStreamSynchronize(c.st));
+            out->stored = 1;
         }
         return 0;
     }
-    if (own_lo >= own_hi || t->lmax == 0)
+    if (c.own_lo >= own_hi || c.t->lmax == 0)
         return 0;
-    if (lines && t->has_nl)
+    if (c.lines && c.t->has_nl)
         return fail("-c with a pattern containing a newline is not supported by the multi-pattern scan");
-
-    AcArgs a{};
-    a.text = d_text;
-    a.text_len = text_len;
-    a.own_lo = own_lo;
-    a.own_hi = own_hi;
-    a.global_base = global_base;
+    return kAcNext;
+}
+// the scan kernel's arguments: ownership and the END range, the unit grid, the anchor decision, the exact dictionary, the hooks
+static int ac_args(const AcScan &c, AcRun &r)
+{
+    AcTables *t = c.t;
+    AcArgs &a = r.a;
+    const size_t own_lo = c.own_lo, own_hi = r.own_hi, text_len = c.text_len;
+    const bool own_by_end = c.own != AcOwn::Start;
+    r.lines_on_list = c.own == AcOwn::LinesOnList;
+    r.fsc = g_force_stage_cap.load(std::memory_order_relaxed);
+    a.text = c.d_text; a.text_len = text_len; a.global_base = c.global_base;
+    a.own_lo = own_lo; a.own_hi = own_hi;
     // END indices to examine.  Positions/counts own a match by its START (start-offset ownership), so ends
     // run up to own_hi + Lmax - 2.  -c owns by END index instead (a pattern without '\n' starts and ends
     // on the same line), which keeps the line bookkeeping inside the owned window.
     a.end_lo = own_lo;
-    a.end_hi = (lines || own_by_end) ? own_hi : std::min<u64>(text_len, (u64)own_hi + t->lmax - 1);
+    a.end_hi = (c.lines || own_by_end) ? own_hi : std::min<u64>(text_len, (u64)own_hi + t->lmax - 1);
     if (own_by_end)
     {
-        // the record list -c is counted on (kg_scan.hip scan_ac_lines_on_list) owns by END like the in-kernel -c road does: two
+        // the record list -c is counted on (kg_scan_ac.hip scan_ac_lines_on_list) owns by END like the in-kernel -c road does: two
         // neighbouring pieces / shards may take different roads, and a match across their cut must belong to exactly one of them
         // (ADVICE r04).  No start clip: every start the buffer holds is in.
-        a.own_lo = 0;
-        a.own_hi = text_len;
+        a.own_lo = 0, a.own_hi = text_len;
     }
     // (END-owned records: a unit verifies the ends behind its first byte, so the end AT own_lo belongs to the unit in front —
     //  which has to exist; round 6)
-    a.anchor = ((own_by_end && !lines && own_lo && !getenv("KREP_GPU_AC_R05_ANCHOR")) ? own_lo - 1 : own_lo) & ~(u64)15; // (the hook: the round-5 grid, for the regression test's own check)
-    const u64 unit_bytes = (u64)kAcUnitBytes;
-    a.num_tiles = (a.end_hi - a.anchor + unit_bytes - 1) / unit_bytes;
-    a.flags = (t->ci ? F_CI : 0) | (ww ? F_WW : 0) | (lines ? F_LINES : 0);
-    if (getenv("KREP_GPU_AC_NOVERIFY")) // measurement hook: filter cost only (wrong results by design)
-        a.flags |= 1u << 31;
-    if (getenv("KREP_GPU_AC_NOSTAGE3")) // measurement hook (anchored scan): candidates -> END pairs, no verify; a count-only scan returns the number of marked pairs
-        a.flags |= 1u << 28;
-    if (getenv("KREP_GPU_AC_NODEFER")) // A/B hook (anchored scan): stage 3 at every unit's end, as first built
-        a.flags |= 1u << 27;
-    if (getenv("KREP_GPU_AC_NOPROBE")) // measurement hook: filter + candidate enumeration, no probes: a count-only scan returns the number of candidates
-        a.flags |= 1u << 30;
-    a.lmax = t->lmax;
-    a.has1 = t->has1; a.has2 = t->has2; a.has3 = t->has3; a.has4 = t->has4;
+    a.anchor = ((own_by_end && !c.lines && own_lo && !getenv("KREP_GPU_AC_R05_ANCHOR")) ? own_lo - 1 : own_lo) & ~(u64)15; // (the hook: the round-5 grid, for the regression test's own check)
+    a.num_tiles = (a.end_hi - a.anchor + kAcUnitBytes - 1) / kAcUnitBytes;
+    a.flags = (t->ci ? F_CI : 0) | (c.ww ? F_WW : 0) | (c.lines ? F_LINES : 0);
+    a.flags |= getenv("KREP_GPU_AC_NOVERIFY") ? 1u << 31 : 0u; // measurement hook: filter cost only (wrong results by design)
+    a.flags |= getenv("KREP_GPU_AC_NOSTAGE3") ? 1u << 28 : 0u; // measurement hook (anchored scan): candidates -> END pairs, no verify; a count-only scan returns the number of marked pairs
+    a.flags |= getenv("KREP_GPU_AC_NODEFER") ? 1u << 27 : 0u;  // A/B hook (anchored scan): stage 3 at every unit's end, as first built
+    a.flags |= getenv("KREP_GPU_AC_NOPROBE") ? 1u << 30 : 0u;  // measurement hook: filter + candidate enumeration, no probes: a count-only scan returns the number of candidates
+    a.lmax = t->lmax; a.has1 = t->has1; a.has2 = t->has2; a.has3 = t->has3; a.has4 = t->has4;
     a.stride = 1;
-    a.filter = lines ? t->d_filterx19 : t->d_filterx20;
-    a.filter_words = (1u << (lines ? kXBitsLines : kXBitsBig)) / 32;
+    a.filter = c.lines ? t->d_filterx19 : t->d_filterx20;
+    a.filter_words = (1u << (c.lines ? kXBitsLines : kXBitsBig)) / 32;
     if (t->d_filters20)
     {
-        a.filter = lines ? t->d_filters19 : t->d_filters20;
+        a.filter = c.lines ? t->d_filters19 : t->d_filters20;
         a.stride = 2;
     }
     // anchors (kg_ac_anchor.hip): decided once per dictionary on the first text of >= 1 MiB; every launch without in-kernel -c then
@@ -1206,116 +1188,131 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
     if (t->anch_state == 0 && text_len >= (1u << 20) && own_hi - own_lo >= (1u << 19))
     {
         HIPCHK(hipSetDevice(t->device));
-        if (ac_anchor_prepare(t, d_text, text_len, own_lo, own_hi, st) == 2)
+        if (ac_anchor_prepare(t, c.d_text, text_len, own_lo, own_hi, c.st) == 2)
             (void)hipGetLastError(); // (the end grams stay; a failed sample is not a failed scan)
     }
-    if (t->anch_state == 2 && !lines && a.stride == 2 && !getenv("KREP_GPU_AC_NO_ANCHOR"))
+    if (t->anch_state == 2 && !c.lines && a.stride == 2 && !getenv("KREP_GPU_AC_NO_ANCHOR"))
     {
         a.filter = t->d_filtera20;
-        a.anch = t->d_anch;
-        a.anch_mask = t->anch_mask;
-        a.anch_mul = t->anch_mul;
-        a.anch_five = t->anch_five;
+        a.anch = t->d_anch; a.anch_mask = t->anch_mask; a.anch_mul = t->anch_mul; a.anch_five = t->anch_five;
     }
     if (t->d_xtab && !getenv("KREP_GPU_AC_NO_EXACT")) // the exact dictionary: stage 3 of the anchored scan, the slow path of the others
     {
-        a.xlen = t->d_xlen;
-        a.xtab = t->d_xtab;
-        a.xmask = t->xmask;
-        a.xmul = t->xmul;
+        a.xlen = t->d_xlen; a.xtab = t->d_xtab; a.xmask = t->xmask; a.xmul = t->xmul;
     }
     a.s1 = t->d_s1; a.s2 = t->d_s2; a.s3 = t->d_s3;
     if (t->short_dup)
         a.flags |= F_AC_SHORT_DUP;
-    a.edges = t->d_edges;
-    a.emask = t->emask;
-    a.copies = t->d_copies;
-    a.gram4 = t->d_gram4;
-    a.g4x = t->d_g4x;
-    a.g4mask = t->g4mask;
+    a.edges = t->d_edges; a.emask = t->emask; a.copies = t->d_copies;
+    a.gram4 = t->d_gram4; a.g4x = t->d_g4x; a.g4mask = t->g4mask;
     a.g4x_mode = t->g4x_mode; a.g4x_mask = t->g4x_mask; a.g4x_mul = t->g4x_mul;
-    a.ctr = d_ctr;
-    const u64 want = (d_pos && cap && !lines) ? std::min<u64>(cap, (u64)max_count) : 0;
-    if (want)
+    a.ctr = c.d_ctr;
+    r.want = (c.d_pos && c.cap && !c.lines) ? std::min<u64>(c.cap, (u64)c.max_count) : 0;
+    if (r.want)
         a.flags |= F_POS;
-    a.positions = (u64 *)d_pos;
-    a.pos_cap = want;
-    // a one-pass scan that recorded every match (kg_single.hip, kg_ac_tiny.hip): its time and its result
-    auto one_pass_out = [&]() -> int {
-        if (time_it)
-        {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
-            out->kernel_ms = ms;
-        }
-        out->total_matches = h_ctr->total;
-        out->head_line_hit = out->tail_line_hit = h_ctr->total != 0;
-        out->count = std::min<u64>(h_ctr->total, (u64)max_count);
-        if (track)
-        {
-            out->stored = std::min<u64>(out->count, want);
-            out->overflow = out->count > cap;
-        }
-        return 0;
-    };
-    // ---- a dictionary of single bytes, records wanted: memchr_search's one-pass kernel with a needle set (kg_single.hip).  The
-    // matches of aho_corasick_search for such a dictionary are one (i, i + 1) per matching position in text order
-    // (aho_corasick.c:383-437) — exactly that kernel's records.  Its shape rules: kg_single.hip single_fused_run.
-    if (t->set_n && want && !ww && !own_by_end && t->set_ok && text_len >= (size_t)16 * kSegBytes && !g_ac_force_stage_cap &&
-        !getenv("KREP_GPU_NO_FUSED1") && !getenv("KREP_GPU_AC_NO_TINY"))
+    a.positions = (u64 *)c.d_pos; a.pos_cap = r.want;
+    return 0;
+}
+// from the counters in *c.h_ctr (a one-pass road, !staged, recorded every match and counts no lines; ~0 lines: the list -c is
+// counted on overflowed a staging slot or its cap, and the caller counts again)
+static int ac_result(const AcScan &c, const AcRun &r, bool staged, krep_gpu_scan_out_t *out)
+{
+    const Counters &h = *c.h_ctr;
+    if (c.time_it)
     {
-        LitArgs la{};
-        la.text = d_text;
-        la.text_len = text_len;
-        la.own_lo = own_lo;
-        la.own_hi = own_hi;
-        la.anchor = own_lo & ~(u64)15;
-        la.rounds = kRoundsBig;
-        const u64 tile_bytes = (u64)kRoundsBig * kSegBytes * kWavesPerBlk;
-        la.num_tiles = (own_hi - la.anchor + tile_bytes - 1) / tile_bytes;
-        la.global_base = global_base;
-        la.ww_exempt_left = ~0ull;
-        la.m = 1;
-        la.flags = (t->ci ? F_CI : 0) | F_POS;
-        la.ctr = d_ctr;
-        la.positions = (uint64_t *)d_pos;
-        la.pos_cap = want;
-        la.set_n = t->set_n;
-        for (u32 k = 0; k < t->set_n; ++k)
-        {
-            la.set_p[k] = 0x01010101u * t->set_b[k];
-            la.set_l[k] = (t->ci && t->set_b[k] >= 'a' && t->set_b[k] <= 'z') ? 0x20202020u : 0u;
-        }
-        la.p0 = la.set_p[0];
-        la.l0 = la.set_l[0];
-        la.k0 = 0xffu;
-        const u64 units32 = la.num_tiles * kWavesPerBlk;
-        HIPCHK(hipSetDevice(t->device));
-        if (time_it) HIPCHK(hipEventRecord(ev0, st));
-        const int rc = single_fused_run(la, units32, own_hi - la.anchor, post, d_ctr, h_ctr, (u32)num_cu, &t->set_shape, time_it ? ev1 : nullptr,
-                                        st, false); // (not counted as krep_gpu_debug_single_launches)
-        if (rc == 2)
-            return 2;
-        if (rc != kFusedGaveUp)
-            return one_pass_out();
-        t->set_ok = false; // denser than the largest rings hold: the register-compare kernel below, for good
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        out->kernel_ms = ms;
     }
-    // ---- a tiny dictionary, records wanted: ONE pass (kg_ac_tiny.hip FUSED, round 5) — matches ranked into an LDS ring per
-    // 128-KiB ticket, the tickets' counts resolved into prefixes by one wave, records written at their final index: no masks kept,
-    // no staging, no info words, no post-pass.  A ticket with more matches than its ring holds (~0.6 % of the bytes) is counted,
-    // not recorded; the count gives the density, and the density the ticket size (1..4 units) of the DENSE flavour — 16-bit ring
-    // entries, matches decoded where they are found — which takes the scan again and the dictionary's next ones (up to ~15 % of
-    // the bytes; a long length included, which the item flavour does not take).  Beyond that, and for 4-byte patterns beside a long
-    // length, the staging road below; every decision is re-evaluated by the following scans.
-    const bool one_pass_ok = t->tiny.ok && !t->tiny.five && want && !ww && list_mode != 2 && track && !g_ac_force_stage_cap &&
-                             text_len >= (size_t)64 * kAcUnitBytes && !getenv("KREP_GPU_AC_NO_TINY_FUSED") && !getenv("KREP_GPU_AC_NO_TINY");
-    // tickets of the DENSE flavour for e matches per unit: two consecutive tickets share the ring, a quarter is left for clustering
-    auto dense_upt = [&](const double e) -> u32 {
-        if (e <= 0.0)
-            return 4u;
-        const double u = (double)ac_tiny_dense_ring() / (2.5 * e);
-        return u >= 4.0 ? 4u : (u32)u;
-    };
+    const u64 total = h.total;
+    out->total_matches = total;
+    out->line_count = staged ? h.lines : 0;
+    if (r.lines_on_list)
+        out->line_count = (r.want && !h.overflow_units && total <= r.want) ? h.lines : ~0ull;
+    const u64 summary = (staged && (r.want || c.lines)) ? h.summary : (total ? (kLnHead | kLnTail) : 0);
+    out->has_newline = (summary & kLnNl) != 0;
+    out->head_line_hit = (summary & kLnHead) != 0;
+    out->tail_line_hit = (summary & kLnTail) != 0;
+    out->count = std::min<u64>(c.lines ? h.lines : total, (u64)c.max_count);
+    if (r.want && c.track)
+    {
+        out->stored = std::min<u64>(out->count, r.want);
+        out->overflow = out->count > c.cap;
+    }
+    return 0;
+}
+// ---- a dictionary of single bytes, records wanted: memchr_search's one-pass kernel with a needle set (kg_single.hip).  The
+// matches of aho_corasick_search for such a dictionary are one (i, i + 1) per matching position in text order
+// (aho_corasick.c:383-437) — exactly that kernel's records.  Its shape rules: kg_single.hip single_fused_run.
+static int ac_byte_set(const AcScan &c, AcRun &r, krep_gpu_scan_out_t *out)
+{
+    AcTables *t = c.t;
+    if (!(t->set_n && r.want && !c.ww && c.own == AcOwn::Start && t->set_ok && c.text_len >= (size_t)16 * kSegBytes && !r.fsc &&
+          !getenv("KREP_GPU_NO_FUSED1") && !getenv("KREP_GPU_AC_NO_TINY")))
+        return kAcNext;
+    LitArgs la{};
+    la.text = c.d_text; la.text_len = c.text_len; la.global_base = c.global_base;
+    la.own_lo = c.own_lo; la.own_hi = r.own_hi;
+    la.anchor = c.own_lo & ~(u64)15;
+    la.rounds = kRoundsBig;
+    const u64 tile_bytes = (u64)kRoundsBig * kSegBytes * kWavesPerBlk;
+    la.num_tiles = (r.own_hi - la.anchor + tile_bytes - 1) / tile_bytes;
+    la.ww_exempt_left = ~0ull;
+    la.m = 1;
+    la.flags = (t->ci ? F_CI : 0) | F_POS;
+    la.ctr = c.d_ctr; la.positions = (uint64_t *)c.d_pos; la.pos_cap = r.want;
+    la.set_n = t->set_n;
+    for (u32 k = 0; k < t->set_n; ++k)
+    {
+        la.set_p[k] = 0x01010101u * t->set_b[k];
+        la.set_l[k] = (t->ci && t->set_b[k] >= 'a' && t->set_b[k] <= 'z') ? 0x20202020u : 0u;
+    }
+    la.p0 = la.set_p[0]; la.l0 = la.set_l[0]; la.k0 = 0xffu;
+    HIPCHK(hipSetDevice(t->device));
+    if (c.time_it) HIPCHK(hipEventRecord(c.ev0, c.st));
+    const int rc = single_fused_run(la, la.num_tiles * kWavesPerBlk, r.own_hi - la.anchor, *c.post, c.d_ctr, c.h_ctr, (u32)c.num_cu, &t->set_shape,
+                                    c.time_it ? c.ev1 : nullptr, c.st, false); // (not counted as krep_gpu_debug_single_launches)
+    if (rc == 2)
+        return 2;
+    if (rc != kFusedGaveUp)
+        return ac_result(c, r, false, out);
+    t->set_ok = false; // denser than the largest rings hold: the register-compare kernel below, for good
+    return kAcNext;
+}
+// ---- the tiny dictionary's density rules: its one-pass flavours (ac_tiny_one_pass) and their re-opening behind a staged scan
+// tickets of the DENSE flavour for e matches per unit: two consecutive tickets share the ring, a quarter is left for clustering
+static u32 tiny_dense_upt(double e)
+{
+    if (e <= 0.0)
+        return 4u;
+    const double u = (double)ac_tiny_dense_ring() / (2.5 * e);
+    return u >= 4.0 ? 4u : (u32)u;
+}
+// behind a staged scan of a tiny dictionary that counted `total` matches in `n_units` units
+static void tiny_reopen(AcTables *t, u64 total, u64 n_units)
+{
+    if (!t->tiny_fused_ok && total < n_units * 20) // (a 128-KiB ticket's ring holds ~1000: 125 per unit)
+        t->tiny_fused_ok = true;
+    if (!t->tiny_dense_ok && total < n_units * 20)
+        t->tiny_dense_ok = true;
+    // a dense text through the staging road (a dictionary with a long length starts here: the item flavour of the one-pass
+    // writer does not take it): its next scans take the DENSE flavour, in tickets sized by the density just counted
+    if (!t->tiny.five && t->tiny_dense_ok && !t->tiny_dense_upt && total >= n_units * 48)
+        t->tiny_dense_upt = tiny_dense_upt((double)total / (double)n_units);
+}
+// ---- a tiny dictionary, records wanted: ONE pass (kg_ac_tiny.hip FUSED, round 5) — matches ranked into an LDS ring per
+// 128-KiB ticket, the tickets' counts resolved into prefixes by one wave, records written at their final index: no masks kept,
+// no staging, no info words, no post-pass.  A ticket with more matches than its ring holds (~0.6 % of the bytes) is counted,
+// not recorded; the count gives the density, and the density the ticket size (1..4 units) of the DENSE flavour — 16-bit ring
+// entries, matches decoded where they are found — which takes the scan again and the dictionary's next ones (up to ~15 % of
+// the bytes; a long length included, which the item flavour does not take).  Beyond that, and for 4-byte patterns beside a long
+// length, the staging road; every decision is re-evaluated by the following scans.
+static int ac_tiny_one_pass(const AcScan &c, const AcRun &r, krep_gpu_scan_out_t *out)
+{
+    AcTables *t = c.t;
+    Counters *h_ctr = c.h_ctr;
+    const bool one_pass_ok = t->tiny.ok && !t->tiny.five && r.want && !c.ww && c.own != AcOwn::End && c.track && !r.fsc &&
+                             c.text_len >= (size_t)64 * kAcUnitBytes && !getenv("KREP_GPU_AC_NO_TINY_FUSED") && !getenv("KREP_GPU_AC_NO_TINY");
     const bool dense_first = getenv("KREP_GPU_AC_TINY_DENSE_FIRST") != nullptr; // measurement hook: the DENSE flavour at any density
     if (dense_first && one_pass_ok && !t->tiny_dense_upt && t->tiny_dense_ok)
         t->tiny_dense_upt = 4;
@@ -1324,138 +1321,150 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
         const bool dense = t->tiny_dense_upt != 0 && !getenv("KREP_GPU_AC_NO_TINY_DENSE");
         if (!dense && (!t->tiny_fused_ok || t->tiny.llong))
             break;
-        AcArgs f = a;
-        f.upt = dense ? t->tiny_dense_upt : (u32)std::min<u64>(kAcUnitsPerTicketMax, std::max<u64>(1, f.num_tiles / ((u64)num_cu * kTinyWaves * 4)));
+        AcArgs f = r.a;
+        f.upt = dense ? t->tiny_dense_upt : (u32)std::min<u64>(kAcUnitsPerTicketMax, std::max<u64>(1, f.num_tiles / ((u64)c.num_cu * kTinyWaves * 4)));
         const u64 n_tk = (f.num_tiles + f.upt - 1) / f.upt;
         const size_t tk_bytes = 2 * n_tk * sizeof(unsigned long long); // counts | prefixes
-        HIPCHK(grow_scratch(post.tk_cap, n_tk, n_tk, {dev_buf(post.d_tk, tk_bytes)}));
-        f.tk_agg = post.d_tk;
-        f.tk_pref = post.d_tk + n_tk;
-        f.n_tk = n_tk;
-        f.stage_cap = 0;
+        HIPCHK(grow_scratch(c.post->tk_cap, n_tk, n_tk, {dev_buf(c.post->d_tk, tk_bytes)}));
+        f.tk_agg = c.post->d_tk; f.tk_pref = c.post->d_tk + n_tk; f.n_tk = n_tk; f.stage_cap = 0;
         HIPCHK(hipSetDevice(t->device));
-        if (time_it) HIPCHK(hipEventRecord(ev0, st));
-        HIPCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
-        HIPCHK(hipMemsetAsync(post.d_tk, 0, tk_bytes, st));
-        HIPCHK(ac_tiny_launch_fused(f, t->tiny, n_tk, (u32)num_cu, st, dense));
+        if (c.time_it) HIPCHK(hipEventRecord(c.ev0, c.st));
+        HIPCHK(hipMemsetAsync(c.d_ctr, 0, sizeof(Counters), c.st));
+        HIPCHK(hipMemsetAsync(c.post->d_tk, 0, tk_bytes, c.st));
+        HIPCHK(ac_tiny_launch_fused(f, t->tiny, n_tk, (u32)c.num_cu, c.st, dense));
         // (the record list -c is counted on: its line gaps behind the scan on the same stream, skipped by the kernel itself when
         //  a ticket overflowed its ring)
-        if (lines_on_list && tail_launch_line_gaps(d_text, text_len, global_base, (const uint64_t *)d_pos, &d_ctr->total, &d_ctr->overflow_units,
-                                                   want, &d_ctr->lines, st))
+        if (r.lines_on_list && tail_launch_line_gaps(c.d_text, c.text_len, c.global_base, (const uint64_t *)c.d_pos, &c.d_ctr->total,
+                                                     &c.d_ctr->overflow_units, r.want, &c.d_ctr->lines, c.st))
             return 2;
-        if (time_it) HIPCHK(hipEventRecord(ev1, st));
-        HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        if (c.time_it) HIPCHK(hipEventRecord(c.ev1, c.st));
+        HIPCHK(hipMemcpyAsync(h_ctr, c.d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipStreamSynchronize(c.st));
         const double per_unit = (double)h_ctr->total / (double)f.num_tiles;
         if (getenv("KREP_GPU_DEBUG"))
             fprintf(stderr, "krep-gpu: tiny one-pass (%s, %u units per ticket): %llu matches, %.1f per unit, %llu waves overflowed\n",
                     dense ? "dense" : "items", f.upt, (unsigned long long)h_ctr->total, per_unit, (unsigned long long)h_ctr->overflow_units);
         if (!h_ctr->overflow_units)
         {
-            if (one_pass_out()) // (track: one_pass_ok asks for it)
+            if (ac_result(c, r, false, out)) // (track: one_pass_ok asks for it)
                 return 2;
-            const u64 total = h_ctr->total;
-            if (lines_on_list)
-                out->line_count = total <= want ? h_ctr->lines : ~0ull; // ~0: the list did not fit when the gaps were counted
             if (dense)
             {
                 // re-evaluated by every scan: the ticket size follows the density, and a text with fewer than 24 matches per unit
                 // goes back to the item flavour (or, with a long length, to the staging road)
                 if (per_unit < 24.0 && !dense_first)
-                {
-                    t->tiny_dense_upt = 0;
-                    t->tiny_fused_ok = true;
-                }
+                    t->tiny_dense_upt = 0, t->tiny_fused_ok = true;
                 else
-                    t->tiny_dense_upt = std::max(1u, dense_upt(per_unit));
+                    t->tiny_dense_upt = std::max(1u, tiny_dense_upt(per_unit));
             }
             return 0;
         }
         // counted, not recorded (the resolver's running sum is the total — unless the spin-limit safety net fired: total 0)
-        u32 nu = (t->tiny_dense_ok && h_ctr->total) ? dense_upt(per_unit) : 0u;
+        u32 nu = (t->tiny_dense_ok && h_ctr->total) ? tiny_dense_upt(per_unit) : 0u;
         if (dense && nu >= t->tiny_dense_upt)
             nu = t->tiny_dense_upt - 1u; // (clustered matches: the next smaller ticket)
         if (!dense)
-            t->tiny_fused_ok = false; // (re-opened below by a text sparse enough for the rings)
+            t->tiny_fused_ok = false; // (re-opened by tiny_reopen, by a text sparse enough for the rings)
         t->tiny_dense_upt = nu;
         if (!nu)
         {
-            t->tiny_dense_ok = false; // (re-opened below, like tiny_fused_ok)
+            t->tiny_dense_ok = false; // (re-opened like tiny_fused_ok)
             break;
         }
     }
-    const bool chain = want || lines;
+    return kAcNext;
+}
+// a launch of the staged road (its scan or its emit pass): the register-compare kernel over the tickets, else the general one
+static hipError_t ac_staged_launch(const AcScan &c, const AcRun &r, const AcArgs &a)
+{
+    const u64 n_tickets = (a.num_tiles + a.upt - 1) / a.upt;
+    if (r.tiny)
+        return ac_tiny_launch(a, c.t->tiny, n_tickets, (u32)c.num_cu, c.st);
+    const u32 lds = ac_lds_bytes(a.filter_words, c.lines), per_cu = lds <= 80 * 1024 ? 2u : 1u;
+    return ac_launch(a, (u32)std::min<u64>((n_tickets + kAcWaves - 1) / kAcWaves, (u64)c.num_cu * per_cu), lds, c.st);
+}
+// ---- the staged road: the scan kernel stages every unit's matches, the post-pass orders them into the record list (and counts
+// -c's lines), the line gaps of the record list -c is counted on behind it; the counters are read back
+static int ac_staged(const AcScan &c, AcRun &r)
+{
+    AcArgs &a = r.a;
+    const bool chain = r.want || c.lines;
     const u64 n_units = a.num_tiles;
     // 16 staged matches (32-bit words: unit-relative start + length) = one 64-byte slot per 16 KiB unit; BASELINE config 4 puts 5.3
     // matches in a unit.  Units that hold more are re-scanned in emit mode, and a scan in which more than 1 in 64 units did
     // raises the dictionary's slot to 64 for its next scans.  (Small slots keep the store stream dense: kg_scan.hip, lit_args.)
-    a.stage_cap = want ? (g_ac_force_stage_cap ? (u32)g_ac_force_stage_cap : t->stage_cap) : 0u;
+    a.stage_cap = r.want ? (r.fsc ? (u32)r.fsc : c.t->stage_cap) : 0u;
     if (chain)
     {
-        if (post_reserve(post, n_units, (n_units * a.stage_cap + 1) / 2))
+        if (post_reserve(*c.post, n_units, (n_units * a.stage_cap + 1) / 2))
             return 2;
-        a.unitinfo = post.d_unitinfo;
-        a.stage = (u64 *)post.d_stage;
-        a.offsets = (const u64 *)post.d_offsets;
+        a.unitinfo = c.post->d_unitinfo; a.stage = (u64 *)c.post->d_stage; a.offsets = (const u64 *)c.post->d_offsets;
     }
-    HIPCHK(hipSetDevice(t->device));
+    HIPCHK(hipSetDevice(c.t->device));
     // tiny dictionaries run in kg_ac_tiny.hip (same units, staging, info words and post-pass); -w takes the general kernel
     // (4-byte patterns beside a long length — AcTiny::five: only the case-sensitive COUNT runs in the register-compare kernel, every
     //  other mode of such a dictionary measured faster here)
-    const bool tiny = t->tiny.ok && !ww && (!t->tiny.five || (!want && !lines && !t->ci));
-    const u32 waves = tiny ? (u32)kTinyWaves : (u32)kAcWaves;
-    const u32 lds = ac_lds_bytes(a.filter_words, lines);
-    const u32 per_cu = lds <= 80 * 1024 ? 2u : 1u;
+    r.tiny = c.t->tiny.ok && !c.ww && (!c.t->tiny.five || (!r.want && !c.lines && !c.t->ci));
+    const u32 waves = r.tiny ? (u32)kTinyWaves : (u32)kAcWaves;
     // ticket size by text size: >= ~4 tickets per resident wave before tickets grow (small host buffers keep every
     // CU busy), 8 units (128 KiB) on large texts
-    a.upt = (u32)std::min<u64>(kAcUnitsPerTicketMax, std::max<u64>(1, a.num_tiles / ((u64)num_cu * waves * 4)));
+    a.upt = (u32)std::min<u64>(kAcUnitsPerTicketMax, std::max<u64>(1, a.num_tiles / ((u64)c.num_cu * waves * 4)));
     if (const char *e = getenv("KREP_GPU_AC_UPT")) // test hook: the ticket size large texts get (the anchored scan defers its verify stage over a ticket's units)
     {
         const int v = atoi(e);
         if (v >= 1 && v <= (int)kAcUnitsPerTicketMax)
             a.upt = (u32)v;
     }
-    const u64 n_tickets = (a.num_tiles + a.upt - 1) / a.upt;
-    const u32 grid = (u32)std::min<u64>((n_tickets + waves - 1) / waves, (u64)num_cu * per_cu);
-    auto launch = [&](const AcArgs &args) { return tiny ? ac_tiny_launch(args, t->tiny, n_tickets, (u32)num_cu, st) : ac_launch(args, grid, lds, st); };
-    if (time_it) HIPCHK(hipEventRecord(ev0, st));
+    if (c.time_it) HIPCHK(hipEventRecord(c.ev0, c.st));
     // KREP_GPU_SYNC_DEBUG=1: synchronise behind every launch of this function and say which one faulted
     const bool dbg_sync = getenv("KREP_GPU_SYNC_DEBUG") != nullptr;
     auto dbg = [&](const char *what) -> int {
         if (!dbg_sync)
             return 0;
-        const hipError_t e = hipStreamSynchronize(st);
+        const hipError_t e = hipStreamSynchronize(c.st);
         return e == hipSuccess ? 0 : fail("ac_scan: %s faulted: %s (tiny=%d stride=%u units=%llu stage_cap=%u lines=%d list=%d own=[%llu,%llu) end=[%llu,%llu) n=%llu)", what,
-                                          hipGetErrorString(e), (int)tiny, a.stride, (unsigned long long)n_units, a.stage_cap, (int)lines, (int)lines_on_list,
+                                          hipGetErrorString(e), (int)r.tiny, a.stride, (unsigned long long)n_units, a.stage_cap, (int)c.lines, (int)r.lines_on_list,
                                           (unsigned long long)a.own_lo, (unsigned long long)a.own_hi, (unsigned long long)a.end_lo,
-                                          (unsigned long long)a.end_hi, (unsigned long long)text_len);
+                                          (unsigned long long)a.end_hi, (unsigned long long)c.text_len);
     };
-    HIPCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), st));
-    HIPCHK(launch(a));
+    HIPCHK(hipMemsetAsync(c.d_ctr, 0, sizeof(Counters), c.st));
+    HIPCHK(ac_staged_launch(c, r, a));
     if (dbg("scan kernel")) return 2;
-    if (chain && post_order(post, n_units, a.stage_cap, 0, a.anchor + global_base, unit_bytes, lines, (uint64_t *)d_pos, want, d_ctr, num_cu, st))
+    if (chain && post_order(*c.post, n_units, a.stage_cap, 0, a.anchor + c.global_base, kAcUnitBytes, c.lines, (uint64_t *)c.d_pos, r.want, c.d_ctr,
+                            c.num_cu, c.st))
         return 2;
-    // lines_on_list (kg_scan.hip scan_ac_lines_on_list): the distinct lines of the record list just gathered, counted by the
-    // newline gaps between neighbours, behind the post-pass on the same stream — valid when no unit overflowed its staging
-    // slot and the list fitted (the caller checks both and repeats otherwise)
     if (dbg("post-pass")) return 2;
-    if (lines_on_list && want && tail_launch_line_gaps(d_text, text_len, global_base, (const uint64_t *)d_pos, &d_ctr->total, &d_ctr->overflow_units, want, &d_ctr->lines, st))
+    // lines_on_list (kg_scan_ac.hip scan_ac_lines_on_list): the distinct lines of the record list just gathered, counted by the
+    // newline gaps between neighbours, behind the post-pass on the same stream — valid when no unit overflowed its staging
+    // slot and the list fitted (ac_result checks both; the caller repeats otherwise)
+    if (r.lines_on_list && r.want && tail_launch_line_gaps(c.d_text, c.text_len, c.global_base, (const uint64_t *)c.d_pos, &c.d_ctr->total,
+                                                           &c.d_ctr->overflow_units, r.want, &c.d_ctr->lines, c.st))
         return 2;
     if (dbg("line-gap kernel")) return 2;
-    if (time_it) HIPCHK(hipEventRecord(ev1, st));
-    HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (c.time_it) HIPCHK(hipEventRecord(c.ev1, c.st));
+    HIPCHK(hipMemcpyAsync(c.h_ctr, c.d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipStreamSynchronize(c.st));
+    return 0;
+}
+// behind a staged scan: what its counters teach the dictionary for the next scans
+static void ac_learn(const AcScan &c, const AcRun &r)
+{
+    AcTables *t = c.t;
+    const AcArgs &a = r.a;
+    const Counters &h = *c.h_ctr;
+    const size_t own_lo = c.own_lo, own_hi = r.own_hi;
+    const u64 n_units = a.num_tiles;
     // The anchor decision follows the TEXT, and a dictionary meets more than one: the kernel counts the positions its filter passed, and a
     // scan whose measured rate is both one that matters (the decision's own 0.8 % bar) and more than twice what the decision estimated for
     // the filter it chose re-opens the decision, so that the next scan samples the text it is given (an i.i.d. text first, a word-like
     // one after it: 0.04 of the roofline without this, 0.49 with).  Matches are candidates too, so a text dense with matches can ask as
     // well; the repeats are bounded, and a repeat on the same kind of text decides as before.
-    if (!tiny && !lines && a.stride == 2 && !a.emit_mode && own_hi > own_lo)
+    if (!r.tiny && !c.lines && a.stride == 2 && own_hi > own_lo)
     {
         const double tested = 0.5 * (double)(own_hi - own_lo);
-        t->anch_measured = (double)h_ctr->candidates / tested;
+        t->anch_measured = (double)h.candidates / tested;
         const double est = t->anch_state == 2 ? t->anch_rate : t->anch_rate0;
-        if (t->anch_state != 0 && t->anch_resamples < kAnchResamples && text_len >= (1u << 20) && own_hi - own_lo >= (1u << 19) &&
+        if (t->anch_state != 0 && t->anch_resamples < kAnchResamples && c.text_len >= (1u << 20) && own_hi - own_lo >= (1u << 19) &&
             t->anch_measured > 0.008 && t->anch_measured > 2.0 * est + 0.002 && !getenv("KREP_GPU_AC_ANCHOR") && !getenv("KREP_GPU_AC_NO_RESAMPLE"))
         {
             if (getenv("KREP_GPU_DEBUG"))
@@ -1465,78 +1474,64 @@ int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, in
             ++t->anch_resamples;
         }
     }
-    if (want && !g_ac_force_stage_cap)
+    if (!r.want || r.fsc)
+        return;
+    // a dense dictionary / text: the next scans stage 64 matches per unit — or, when most units of a tiny dictionary hold more
+    // than that and the average is beyond 256 (`-e e -e t`: a thousand per unit), none at all: the first launch only counts (no masks kept, nothing staged)
+    // and the emit-mode launch writes every record
+    if (r.tiny && h.overflow_units * 2 > n_units && h.total > n_units * 256)
+        t->stage_cap = 0;
+    else if (t->stage_cap && h.overflow_units * 64 > n_units)
+        t->stage_cap = 64;
+    else if (!t->stage_cap && h.total < n_units * 32)
+        t->stage_cap = 64; // the dense road (count pass + emit pass) is left again when a text holds < 32 matches per unit
+    if (r.tiny)
+        tiny_reopen(t, h.total, n_units);
+    // a byte-set dictionary that proved too dense for the one-pass rings gets them back on a text half as dense as they hold
+    if (t->set_n && !t->set_ok && own_hi > a.anchor && single_fused_reopens(h.total, own_hi - a.anchor))
+        t->set_ok = true;
+}
+// ---- the units whose matches did not fit their staging slot: scanned again in emit mode, each writing at its own offset
+static int ac_emit(const AcScan &c, const AcRun &r)
+{
+    AcTables *t = c.t;
+    const u64 n_units = r.a.num_tiles;
+    AcArgs e = r.a;
+    e.emit_mode = 1;
+    HIPCHK(hipMemsetAsync(&c.d_ctr->ticket, 0, sizeof(unsigned long long), c.st));
+    if (!r.tiny && !getenv("KREP_GPU_AC_NO_REDO_LIST"))
     {
-        // a dense dictionary / text: the next scans stage 64 matches per unit — or, when most units of a tiny dictionary hold more
-        // than that and the average is beyond 256 (`-e e -e t`: a thousand per unit), none at all: the first launch only counts (no masks kept, nothing staged)
-        // and the emit-mode launch writes every record
-        if (tiny && h_ctr->overflow_units * 2 > n_units && h_ctr->total > n_units * 256)
-            t->stage_cap = 0;
-        else if (t->stage_cap && h_ctr->overflow_units * 64 > n_units)
-            t->stage_cap = 64;
-        else if (!t->stage_cap && h_ctr->total < n_units * 32)
-            t->stage_cap = 64; // the dense road (count pass + emit pass) is left again when a text holds < 32 matches per unit
-        if (tiny && !t->tiny_fused_ok && h_ctr->total < n_units * 20) // (a 128-KiB ticket's ring holds ~1000: 125 per unit)
-            t->tiny_fused_ok = true;
-        if (tiny && !t->tiny_dense_ok && h_ctr->total < n_units * 20)
-            t->tiny_dense_ok = true;
-        // a dense text through the staging road (a dictionary with a long length starts here: the item flavour of the one-pass
-        // writer does not take it): its next scans take the DENSE flavour, in tickets sized by the density just counted
-        if (tiny && !t->tiny.five && t->tiny_dense_ok && !t->tiny_dense_upt && h_ctr->total >= n_units * 48)
-            t->tiny_dense_upt = dense_upt((double)h_ctr->total / (double)n_units);
-        // a byte-set dictionary that proved too dense for the one-pass rings gets them back on a text half as dense as they hold
-        if (t->set_n && !t->set_ok && own_hi > a.anchor && single_fused_reopens(h_ctr->total, own_hi - a.anchor))
-            t->set_ok = true;
-    }
-    const bool list_lines_valid = lines_on_list && want && !h_ctr->overflow_units && h_ctr->total <= want;
-    const u64 list_lines = h_ctr->lines;
-    if (want && h_ctr->overflow_units)
-    {
-        AcArgs e = a;
-        e.emit_mode = 1;
-        HIPCHK(hipMemsetAsync(&d_ctr->ticket, 0, sizeof(unsigned long long), st));
-        if (!tiny && !getenv("KREP_GPU_AC_NO_REDO_LIST"))
+        // the overflowed units as a list (their number is known: the scan counted them), one ticket each
+        const u64 n_over = c.h_ctr->overflow_units;
+        const u64 redo_cap = n_over + n_over / 4 + 64;
+        if (grow_scratch(t->redo_cap, n_over, redo_cap, {dev_buf(t->d_redo, redo_cap * sizeof(u32))}) != hipSuccess)
+            (void)hipGetLastError(); // (no list: the emit pass walks every unit)
+        if (t->d_redo && n_over <= 0xffffffffull)
         {
-            // the overflowed units as a list (their number is known: the scan counted them), one ticket each
-            const u64 n_over = h_ctr->overflow_units;
-            const u64 redo_cap = n_over + n_over / 4 + 64;
-            if (grow_scratch(t->redo_cap, n_over, redo_cap, {dev_buf(t->d_redo, redo_cap * sizeof(u32))}) != hipSuccess)
-                (void)hipGetLastError(); // (no list: the emit pass walks every unit)
-            if (t->d_redo && n_over <= 0xffffffffull)
-            {
-                HIPCHK(hipMemsetAsync(&d_ctr->pad[3], 0, sizeof(unsigned long long), st));
-                hipLaunchKernelGGL(ac_redo_list_kernel, dim3((u32)((n_units + 255) / 256)), dim3(256), 0, st, (const u64 *)a.unitinfo, n_units, a.stage_cap, t->d_redo,
-                                   (u32)t->redo_cap, &d_ctr->pad[3]);
-                e.redo_list = t->d_redo;
-                e.n_redo = (u32)n_over;
-            }
+            HIPCHK(hipMemsetAsync(&c.d_ctr->pad[3], 0, sizeof(unsigned long long), c.st));
+            hipLaunchKernelGGL(ac_redo_list_kernel, dim3((u32)((n_units + 255) / 256)), dim3(256), 0, c.st, (const u64 *)e.unitinfo, n_units, e.stage_cap,
+                               t->d_redo, (u32)t->redo_cap, &c.d_ctr->pad[3]);
+            e.redo_list = t->d_redo, e.n_redo = (u32)n_over;
         }
-        HIPCHK(launch(e));
-        if (time_it) HIPCHK(hipEventRecord(ev1, st));
-        HIPCHK(hipStreamSynchronize(st));
     }
-    if (time_it)
-    {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
-        out->kernel_ms = ms;
-    }
-    const u64 total = h_ctr->total, nl = h_ctr->lines;
-    out->total_matches = total;
-    out->line_count = nl;
-    const u64 summary = chain ? h_ctr->summary : (total ? (kLnHead | kLnTail) : 0);
-    out->has_newline = (summary & kLnNl) != 0;
-    out->head_line_hit = (summary & kLnHead) != 0;
-    out->tail_line_hit = (summary & kLnTail) != 0;
-    if (lines_on_list)
-        out->line_count = list_lines_valid ? list_lines : ~0ull; // ~0: the list was not complete when the gaps were counted
-    out->count = std::min<u64>(lines ? nl : total, (u64)max_count);
-    if (want && track)
-    {
-        out->stored = std::min<u64>(out->count, want);
-        out->overflow = out->count > cap;
-    }
+    HIPCHK(ac_staged_launch(c, r, e));
+    if (c.time_it) HIPCHK(hipEventRecord(c.ev1, c.st));
+    HIPCHK(hipStreamSynchronize(c.st));
     return 0;
+}
+int ac_scan(const AcScan &c, krep_gpu_scan_out_t *out)
+{
+    memset(out, 0, sizeof *out);
+    AcRun r;
+    r.own_hi = std::min(c.own_hi, c.text_len);
+    int rc = ac_early_out(c, r.own_hi, out);
+    if (rc == kAcNext) rc = ac_args(c, r) ? 2 : ac_byte_set(c, r, out);
+    if (rc == kAcNext) rc = ac_tiny_one_pass(c, r, out);
+    if (rc != kAcNext) return rc;
+    if (ac_staged(c, r)) return 2;
+    ac_learn(c, r);
+    if (r.want && c.h_ctr->overflow_units && ac_emit(c, r)) return 2;
+    return ac_result(c, r, true, out);
 }
 
 } // namespace kg

@@ -1052,19 +1052,8 @@ u32 ac_tiny_blocks_per_cu(const AcArgs &a)
 template <bool CI, bool LN, bool KEEP, bool EMIT, bool LONG>
 static hipError_t tiny_launch4(const AcArgs &a, const AcTiny &td, u32 grid, hipStream_t st)
 {
-    constexpr int kMaxDev = 64; // (dynamic LDS beyond 64 KiB is granted once per instantiation and device: see ac_launch3)
-    static std::atomic<bool> granted[kMaxDev];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDev || !granted[dev].load(std::memory_order_acquire))
-    {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ac_tiny_kernel<CI, LN, KEEP, EMIT, LONG>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess)
-            return e;
-        if (dev >= 0 && dev < kMaxDev)
-            granted[dev].store(true, std::memory_order_release);
-    }
+    if (const hipError_t e = grant_dynamic_lds<&ac_tiny_kernel<CI, LN, KEEP, EMIT, LONG>>(160 * 1024); e != hipSuccess) // (the most: see ac_launch3)
+        return e;
     hipLaunchKernelGGL((ac_tiny_kernel<CI, LN, KEEP, EMIT, LONG>), dim3(grid), dim3(kTinyBlock), KEEP ? ac_tiny_lds_bytes(LN, !LN) : 0u, st, a, td);
     return hipGetLastError();
 }

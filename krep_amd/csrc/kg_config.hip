@@ -241,9 +241,8 @@ extern "C" const char *krep_gpu_unavailable_reason(void)
 namespace kg {
 std::atomic<int> g_force_rounds{0};    // test hook: 0 = auto, 1 / 4 = force the tile shape
 std::atomic<int> g_force_stage_cap{0}; // test hook: staging records per unit (0 = auto)
-extern int g_ac_force_stage_cap;
 }
-extern "C" void krep_gpu_debug_force_stage_cap(int c) { g_force_stage_cap.store(c); kg::g_ac_force_stage_cap = c; }
+extern "C" void krep_gpu_debug_force_stage_cap(int c) { g_force_stage_cap.store(c); }
 extern "C" void krep_gpu_debug_force_rounds(int r) { g_force_rounds.store(r); }
 namespace kg {
 extern int g_s1_force_grid;

@@ -52,6 +52,22 @@ inline hipError_t grow_scratch(uint64_t &cap, uint64_t need, uint64_t new_cap, s
     return hipSuccess;
 }
 
+// More than 64 KiB of dynamic LDS is requested once per kernel and device (the call sits on the latency path of small host buffers);
+// atomic flags: several host threads may launch one kernel; devices beyond the table set it every time.
+template <auto Kernel> hipError_t grant_dynamic_lds(int bytes)
+{
+    static std::atomic<bool> granted[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const bool known = dev >= 0 && dev < 64;
+    if (known && granted[dev].load(std::memory_order_acquire))
+        return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && known)
+        granted[dev].store(true, std::memory_order_release);
+    return e;
+}
+
 // kg_literal.hip
 hipError_t launch_literal(const LitArgs &a, uint32_t num_cu, hipStream_t st); // grid = resident blocks of the variant x CUs
 // kg_runs.hip: the greedy families on a pattern of one repeated byte, counted without a list (1: a run too long for its look-back)
@@ -152,11 +168,27 @@ int order_records(match_position_t *d_positions, uint64_t n, size_t max_offset, 
 struct AcTables;
 AcTables *ac_build(const search_params_t &sp, int device);
 void ac_free(AcTables *t);
-bool ac_counts_lines_in_registers(const AcTables *t); // a tiny dictionary: its in-kernel -c road keeps nothing in LDS (kg_ac_tiny.hip)
-int ac_scan(AcTables *t, Counters *d_ctr, Counters *h_ctr, PostScratch &post, int num_cu,
-            const uint8_t *d_text, size_t text_len, size_t own_lo, size_t own_hi, size_t global_base,
-            match_position_t *d_pos, uint64_t cap, bool ww, bool lines, bool track, size_t max_count, hipStream_t st,
-            int time_it, hipEvent_t ev0, hipEvent_t ev1, krep_gpu_scan_out_t *out, int list_mode = 0);
+// One multi-pattern scan: what ac_scan reads and where it writes (the scan side fills the workspace from its plan: kg_scan_ac.hip)
+// AcOwn: Start — a match belongs to the window of its START; LinesOnList — END-owned records, their line gaps counted behind the
+// post-pass (-c on the record list); End — END-owned records only (the emission-order list of -c with a newline inside a pattern)
+enum class AcOwn { Start, LinesOnList, End };
+struct AcScan
+{
+    AcTables *t = nullptr;
+    Counters *d_ctr = nullptr, *h_ctr = nullptr; // workspace
+    PostScratch *post = nullptr;
+    int num_cu = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t st = nullptr;
+    const uint8_t *d_text = nullptr; // window
+    size_t text_len = 0, own_lo = 0, own_hi = 0, global_base = 0;
+    match_position_t *d_pos = nullptr; // record sink
+    uint64_t cap = 0, max_count = SIZE_MAX;
+    bool track = false, ww = false, lines = false;
+    AcOwn own = AcOwn::Start;
+    int time_it = 0;
+};
+int ac_scan(const AcScan &c, krep_gpu_scan_out_t *out);
 
 // kg_config.hip — test hooks shared with the scan drivers
 extern std::atomic<int> g_force_rounds, g_force_stage_cap;   // krep_gpu_debug_force_rounds / _stage_cap

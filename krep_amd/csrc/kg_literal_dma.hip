@@ -514,19 +514,8 @@ template <int KIND, bool MASKED, bool CI>
 static hipError_t dma_launch3(const LitArgs &a, u32 num_cu, hipStream_t st)
 {
     constexpr u32 lds = kWavesPerBlk * kDmaWaveLds; // dynamic part (the rings); the parked stores are static
-    constexpr int kMaxDev = 64;
-    static std::atomic<bool> granted[kMaxDev];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDev || !granted[dev].load(std::memory_order_acquire))
-    {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lit_scan_dma<KIND, MASKED, CI>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return e;
-        if (dev >= 0 && dev < kMaxDev)
-            granted[dev].store(true, std::memory_order_release);
-    }
+    if (const hipError_t e = grant_dynamic_lds<&lit_scan_dma<KIND, MASKED, CI>>((int)lds); e != hipSuccess)
+        return e;
     static const u32 bpc = [] { const char *e = getenv("KREP_GPU_LIT_DMA_BLOCKS_PER_CU"); return e && atoi(e) > 0 ? (u32)atoi(e) : 2u; }();
     const u32 grid = (u32)std::min<u64>(a.num_tiles, (u64)num_cu * bpc);
     hipLaunchKernelGGL((lit_scan_dma<KIND, MASKED, CI>), dim3(grid ? grid : 1), dim3(kBlock), lds, st, a);

@@ -1,4 +1,5 @@
-// kg_plan.h — the plan object behind krep_gpu_plan_t (shared by kg_plan.hip, kg_scan.hip and kg_ops.hip).
+// kg_plan.h — the plan object behind krep_gpu_plan_t (shared by kg_plan.hip, kg_scan.hip, kg_scan_ac.hip and kg_ops.hip) and what
+// the scan drivers share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,7 +34,7 @@ struct krep_gpu_plan
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // multi-pattern
     kg::AcTables *ac = nullptr;
-    // a dictionary with 1..3-byte patterns beside many longer ones, on a text where the longer ones gain from anchors (kg_scan.hip
+    // a dictionary with 1..3-byte patterns beside many longer ones, on a text where the longer ones gain from anchors (kg_scan_ac.hip
     // scan_ac_split, round 6): the two parts as dictionaries of their own, scanned one after the other, their record lists merged
     kg::AcTables *ac_long = nullptr, *ac_short = nullptr;
     int ac_split = 0; // 0: not decided, 1: the whole dictionary in one scan, 2: split
@@ -43,7 +44,6 @@ struct krep_gpu_plan
     kg::PostScratch post; // ordering post-pass / sequential-family scratch of the main pass
     uint32_t sparse_cap = 16; // staging entries per 32 KiB unit of the sparse literal kinds: 16, raised to 64 after a scan whose
                               // units overflowed (see lit_learn_density); one 32-byte slot per unit keeps the store stream dense
-    uint32_t ac_cap = 16;     // the same for the multi-pattern scan (16 KiB units)
     // lit_dma_look, the LDS-DMA literal kernel (kg_literal_dma.hip): chosen by what the TEXT holds — the share of 1-KiB cells its prefilter lets
     // through, sampled before the plan's first eligible launch and counted by every launch of the kernel itself
     bool dma_look_done = false;   // the sample has been taken
@@ -60,9 +60,29 @@ struct krep_gpu_plan
     match_position_t *d_nl_rec = nullptr; // multi-pattern -c with a newline inside a pattern (scan_ac_newline_lines): the
     uint64_t *d_nl_ln = nullptr;          // ordered record list and the line number of every start; grow-only
     uint64_t nl_cap = 0;
-    bool lines_list_off = false; // multi-pattern -c: a scan found the text too dense for the record-list road (kg_scan.hip)
+    bool lines_list_off = false; // multi-pattern -c: a scan found the text too dense for the record-list road (kg_scan_ac.hip)
     kg::PostScratch aux;  // small auxiliary passes that must not disturb `post` (end-of-text replay)
     search_params_t sp{}; // shallow copy with patterns pointing into `pats`
     std::vector<const char *> pat_ptrs;
     std::vector<size_t> pat_lens;
 };
+namespace kg {
+// the device buffer being scanned: a slice [global_base, global_base + text_len) of a text of global_len bytes
+struct Window
+{
+    const uint8_t *d_text;
+    size_t text_len;          // bytes readable in the buffer
+    size_t own_lo, own_hi;    // buffer-relative ownership window
+    size_t global_base;       // offset of buffer byte 0 in the whole text (added to reported offsets)
+    size_t global_len;        // length of the whole text (== global_base + text_len for the buffer that holds its end)
+};
+// kg_scan.hip: the end of a timed scan — ev1 recorded (unless the scan's last launch did that), the stream waited for, kernel_ms = ev0 -> ev1
+int stop_clock(krep_gpu_plan *pl, bool record_ev1, hipStream_t st, krep_gpu_scan_out_t *out);
+// The plan's ordered record list and the line number of every start (d_nl_rec / d_nl_ln: one cap, grow-only).  More than nl_cap
+// records needed: both are freed and the records allocated again for `want`, the line numbers too when `with_ln` — the list road
+// of plain -c sizes only the records, and a later user that needs the line numbers allocates them at the cap the records have.
+int nl_reserve(krep_gpu_plan *pl, uint64_t need, uint64_t want, bool with_ln);
+// kg_scan_ac.hip: the multi-pattern scan of a window (scan_device_impl behind its common checks)
+int scan_ac(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
+            const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out);
+} // namespace kg

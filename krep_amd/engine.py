@@ -446,7 +446,7 @@ class Plan:
         return bool(a.value), bool(b.value), float(r.value)
 
     def split_state(self) -> int:
-        """0 undecided / 1 one dictionary / 2 split into a >= 4-byte part and a 1..3-byte part (kg_scan.hip scan_ac_split)"""
+        """0 undecided / 1 one dictionary / 2 split into a >= 4-byte part and a 1..3-byte part (kg_scan_ac.hip scan_ac_split)"""
         f = self.eng.lib.krep_gpu_debug_split_state
         f.restype = C.c_int
         f.argtypes = [C.c_void_p]

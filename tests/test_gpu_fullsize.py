@@ -399,7 +399,7 @@ def test_one_pass_writers_8gib_properties(gpu):
 def test_word_dictionary_8gib_of_word_text(gpu, short_words):
     """The multi-pattern scan on WORD text at a size where its round-6 machinery is all in play (8 GiB: tickets of 8 units — the verify
     stage deferred over the ticket —, anchors with the five-class index, the exact dictionary; with two short words in the list the
-    two-part scan and its merged record list, kg_scan.hip scan_ac_split):
+    two-part scan and its merged record list, kg_scan_ac.hip scan_ac_split):
       * the whole list is in aho_corasick_search's emission order (/root/reference/aho_corasick.c:383-437: end ascending, longest first);
       * its length equals the SUM of the single-literal all-occurrence counts of every word (an independent code path, at full size);
       * exact (start, end) lists against the compiled reference's aho_corasick_search on 1-MiB windows, one of them above 4 GiB."""

@@ -125,7 +125,7 @@ def test_word_dictionary_device_windows_with_global_base(gpu, oracle_engine, wor
 
 def test_word_dictionary_with_short_words_is_split_and_merged(gpu, oracle_engine, words):
     """A word list that also holds 1..3-byte words (`of`, `the`, a rare three-letter word ...) gets no anchors as one dictionary; on word
-    text the plan scans its >= 4-byte part anchored and its short part on its own and merges the two record lists (kg_scan.hip
+    text the plan scans its >= 4-byte part anchored and its short part on its own and merges the two record lists (kg_scan_ac.hip
     scan_ac_split).  The merged list must be aho_corasick_search's, record for record: END ascending, longest first at one END
     (/root/reference/aho_corasick.c:383-437), under -i, -w and max_count; counting adds the two counts; -c (lines) keeps one scan."""
     import torch
@@ -179,7 +179,7 @@ def test_word_dictionary_with_short_words_is_split_and_merged(gpu, oracle_engine
 
 def test_count_lines_of_a_split_dictionary_on_the_merged_list(gpu, oracle_engine, words):
     """-c (distinct lines) of a word dictionary with short words, on a text large enough for the record-list road (>= 32 MiB): the two
-    parts' END-owned lists are merged and the line gaps counted on the merged list (kg_scan.hip scan_ac_lines_on_list); the same count
+    parts' END-owned lists are merged and the line gaps counted on the merged list (kg_scan_ac.hip scan_ac_lines_on_list); the same count
     as aho_corasick_search's count_lines_mode (/root/reference/aho_corasick.c:353-431), also in two ownership windows whose line counts
     combine (krep_gpu_combine_line_counts)."""
     import torch
