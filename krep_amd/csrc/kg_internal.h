@@ -217,6 +217,10 @@ bool shardable(const search_params_t *p, const krep_gpu_config_t &c, size_t text
 // a piece's own contribution (the local_* fields of `piece`) folded onto the record of the text in front of it
 krep_gpu_seq_carry_t fold_carry(const krep_gpu_seq_carry_t &in, const krep_gpu_seq_carry_t &piece);
 bool result_reserve(match_result_t *r, uint64_t extra);
+inline bool by_start_end(const match_position_t &a, const match_position_t &b) // the formatter's order (krep.c:420-434)
+{
+    return a.start_offset != b.start_offset ? a.start_offset < b.start_offset : a.end_offset < b.end_offset;
+}
 bool have_error();
 
 // kg_format.hip
@@ -231,7 +235,8 @@ int comm_clique_ranks(const std::vector<int> &devs); // ranks of the cached comm
 void cost_note_device_init(double ms);                  // the first device call of the process (availability probe)
 void cost_note_host_path(size_t bytes, double seconds); // a host-buffer operator call that went through the staging ring
 
-// kg_ops.hip — host-buffer side
-void memchr_batch_quirk(match_position_t *recs, uint64_t have, size_t maxc);
+// kg_exec.hip — a host buffer through HBM, whole or in pieces over num_gpus devices, records appended to `result`; 2: failed
+int host_scan(const search_params_t *params, const krep_gpu_config_t &cfg, const char *text, size_t text_len, int num_gpus,
+              match_result_t *result, uint64_t *ret);
 
 } // namespace kg

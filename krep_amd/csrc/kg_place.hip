@@ -4,7 +4,7 @@
 // stream moves by 2-3 %, a scan that also writes GBs of records (the single-byte workload: 1 % of the bytes match) by ~10 % (DESIGN.md 6,
 // profiles/r04_placement.txt, r05_run_to_run.txt).  Nothing inside a kernel can change that, and freeing a block and allocating again hands the
 // same pages back.  What an application CAN do is draw again while it keeps the earlier draws: krep_gpu_alloc_placed() allocates up to `tries`
-// candidate blocks (text area + record area behind it, the layout of the host path's arena, kg_ops.hip), fills each text area with the
+// candidate blocks (text area + record area behind it, the layout of the host path's arena, kg_exec.hip), fills each text area with the
 // generator's 1 %-density text (kind 3), times the single-byte scan on it — counting only, then with its records written into the candidate's
 // record area — keeps the candidate on which the record-writing scan ran fastest (the first one that runs within 1.32x of its own counting scan
 // is taken at once: the fast mode sits at 1.28x, the slow one at 1.41x) and returns the others to the driver.  This is what bench.py's

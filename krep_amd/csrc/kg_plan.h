@@ -1,4 +1,4 @@
-// kg_plan.h — the plan object behind krep_gpu_plan_t (shared by kg_plan.hip, kg_scan.hip, kg_scan_ac.hip and kg_ops.hip) and what
+// kg_plan.h — the plan object behind krep_gpu_plan_t (shared by kg_plan.hip, kg_scan.hip, kg_scan_ac.hip and kg_exec.hip) and what
 // the scan drivers share.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // kg_plan.hip — krep_gpu_plan_t: everything a scan needs that depends only on the parameters (folded pattern words and masks,
-// the multi-pattern tables of kg_ac.hip, counters, events, scratch), built once and reused (kg_ops.hip caches plans per
+// the multi-pattern tables of kg_ac.hip, counters, events, scratch), built once and reused (kg_exec.hip caches plans per
 // device; the CLI calls its operator once per file with the same parameters, krep.c:1950).  Host logic only.
 #include <hip/hip_runtime.h>
 

@@ -29,7 +29,7 @@ static bool ac_counts_lines_in_registers(const AcTables *t) { return t && t->tin
 // Pieces (round 5): a piece owns the matches that END in [own_lo, own_hi) — the pieces' lists, concatenated in text order, ARE
 // the emission order — and what couples it to the text in front of it is two numbers (krep_gpu_seq_carry_t): the newlines so
 // far (its line numbers are global) and the line of the last match's start (its first match counts only on another line).
-// The buffer must hold the longest pattern's length in front of own_lo (every piece of run_pieces does).
+// The buffer must hold the longest pattern's length in front of own_lo (every piece of kg_exec.hip's run_pieces does).
 static int scan_ac_newline_lines(krep_gpu_plan *pl, const Window &w, hipStream_t st, int time_it, const krep_gpu_seq_carry_t *carry_in,
                                  krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out)
 {

@@ -1,4 +1,4 @@
-"""TEST SUPPORT (moved out of the package in round 5: the product shards in C, kg_ops.hip run_pieces): a Python model of the
+"""TEST SUPPORT (moved out of the package in round 5: the product shards in C, kg_exec.hip run_pieces): a Python model of the
 rank-level sharding for the one-process-per-GPU path (torch.distributed; backend "nccl" == RCCL on ROCm,
 "gloo" in the CPU tests).  The haystack is sharded by CONTIGUOUS chunk; a rank reports a match iff its
 START lies in the rank's window (start-offset ownership) and reads `halo` bytes past the
@@ -78,7 +78,7 @@ def allgather_ints(values: Sequence[int], device=None) -> list[list[int]]:
 
 
 def true_resumes(lows: Sequence[int], resume_used: Sequence[int], resume_out: Sequence[int]) -> tuple[list[int], list[bool]]:
-    """The exchange step of the chained families (krep_gpu_seq_carry_t::resume, kg_ops.hip::run_pieces): given, per shard in
+    """The exchange step of the chained families (krep_gpu_seq_carry_t::resume, kg_exec.hip::chain_fixup): given, per shard in
     text order, the record it was scanned with and the record it left, the record each shard SHOULD have been scanned with and
     whether its scan has to be repeated.  A repeated shard's own record is unknown until it has been re-scanned, so the walk
     stops at the first stale shard: call again after re-scanning it (a text that is one cluster re-scans every shard)."""

@@ -75,12 +75,18 @@ def test_search_buffer_shards_hand_back_sorted_records(gpu, oracle_engine):
     alpha = b"abc \n"
     text = cases.rand_text(rng, 200_000, alpha)
     pats = [cases.pick_pattern(rng, text, m, alpha) for m in (2, 4, 6, 11)]
-    want = oracle_engine.call(abi.RA_AHO_CORASICK, abi.Params(pats), text)[1]
-    want = want[np.lexsort((want[:, 1], want[:, 0]))]
+    emitted = oracle_engine.call(abi.RA_AHO_CORASICK, abi.Params(pats), text)[1]
+    want = emitted[np.lexsort((emitted[:, 1], emitted[:, 0]))]
+    maxc = 500
+    first = emitted[:maxc]          # -m: the first max_count records in emission order, then the formatter's order
+    want_first = first[np.lexsort((first[:, 1], first[:, 0]))]
     try:
         gpu.set_result_order(True)
         for shards in (1, 3):
             rc, cnt, got = gpu.search_buffer(abi.Params(pats), text, num_gpus=shards)
             assert rc == 0 and np.array_equal(got, want), shards
+        # 3 shards cut this text into pieces: the piece road's max_count branch merges the lists, then sorts the first max_count
+        rc, cnt, got = gpu.search_buffer(abi.Params(pats, max_count=maxc), text, num_gpus=3)
+        assert rc == 0 and cnt == maxc and np.array_equal(got, want_first)
     finally:
         gpu.set_result_order(False)
