@@ -1,11 +1,31 @@
 // kg_ac_tables.h — the device-resident tables of one dictionary (built on the host by kg_ac_build.hip, read by the scan drivers of
 // kg_ac.hip): class-filter tables for LDS, the chain-compressed 4-gram buckets, exact bitmaps of the 1-3-byte patterns, the
-// reversed trie's edge table, and what the scans have learnt about the dictionary's density.
+// reversed trie's edge table, and what the scans have learnt about the dictionary's density; the host helpers its builders share.
 #pragma once
+#include <functional>
 #include <vector>
 #include "kg_ac_common.h"
 
 namespace kg {
+
+// ---- host helpers of the table builders (kg_ac_build.hip) ----
+// Two-way bucket tables (the chain-compressed 4-gram entries, the exact dictionary, the anchor table): the first bucket count
+// nb = 1024, 2048, ... <= nb_max and multiplier under which no bucket h(i, mul) & (nb - 1) holds more than two of the n items,
+// and slot[i] = 2 * bucket + way of item i, the ways taken in item order.  nb == 0: nothing fits.
+struct TwoWayFit
+{
+    u32 nb = 0, mul = 0;
+    std::vector<u32> slot;
+};
+inline constexpr u32 kBucketMuls[6] = {0x9E3779B1u, 0x85EBCA6Bu, 0xC2B2AE35u, 0x27D4EB2Fu, 0x165667B1u, 0xD3A2646Cu}; // 4-gram, anchor
+inline constexpr u32 kExactMuls[6] = {0x9E3779B1u, 0x7FEB352Du, 0x846CA68Bu, 0x2C1B3C6Du, 0x297A2D39u, 0xB55A4F09u};  // exact dictionary
+TwoWayFit fit_two_way(size_t n, u32 nb_max, const u32 (&muls)[6], const std::function<u32(size_t i, u32 mul)> &hash);
+// Class-gram tables: set the slot of every class gram that ends at p[end - 1] and agrees with the pattern: the last min(end, 4)
+// bytes (Five: 5) fix their classes, the classes in front of the pattern are free.  Plain: x = c0 | c1 << 5 | c2 << 10 | c3 << 15,
+// c3 the class of p[end - 1]; Pair: ac_pair_slot(x); Plain19 / Pair19: the same, cut to the 2^19-bit tables of -c; Five: the class
+// of the byte in front of the gram below x, ac_pair_slot5.
+enum class ClsLayout { Plain, Pair, Plain19, Pair19, Five };
+void set_class_grams(std::vector<u32> &tab, ClsLayout layout, const std::vector<uint8_t> &p, size_t end);
 
 struct AcTables
 {
