@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
     static_assert(!WW || (STRIDE == 2 && !SHORT), "the -w filter of the depth masks: pair filter, no short patterns");
     static_assert(!ANCH || (STRIDE == 2 && !LINES && !SHORT), "anchored scan: pair filter, records / counts only");
     extern __shared__ __attribute__((aligned(16))) u32 s_mem[]; // filter table | per wave: candidate bitmap (+ hit and newline bitmaps for -c)
-    const u32 lane = ac_lane();
+    const u32 lane = lane_id();
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if ((u32)(size_t)((__attribute__((address_space(3))) u32 *)s_mem) != 0u)
         __builtin_trap(); // the table lookups address LDS absolutely (no static __shared__ in this kernel)
@@ -112,10 +112,7 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
     // because of the table) made every wave wait for the slowest verifier of its tile.
     for (;;)
     {
-        u64 tk = 0;
-        if (lane == 0)
-            tk = __hip_atomic_fetch_add(&a.ctr->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tk = ac_rfl64(tk);
+        const u64 tk = wave_fetch_add(&a.ctr->ticket, 1ull, lane);
         // (emit mode with a list: ticket k is the k-th unit that has to be scanned again — the launch no longer walks the info words of all
         //  units, one dependent load each: 0.7 ms per 8 GiB whenever a single unit had overflowed its slot)
         const bool listed = emit_final && a.redo_list != nullptr;
@@ -218,7 +215,7 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
                 //  in the line pass was measured — one more memory round trip per unit cost more than it saved: 10.15 -> 11.3 ms)
 #pragma unroll
                 for (int w = 0; w < 4; ++w)
-                    NL |= ac_movemask4(ac_eq_bytes(W[w + 1], 0x0a0a0a0au)) << (4 * w);
+                    NL |= movemask4(eq_bytes(W[w + 1], 0x0a0a0a0au)) << (4 * w);
             }
             u32 cand = 0;
             if constexpr (PAIR)
@@ -562,11 +559,10 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
             };
             // its eight bytes t - 6 .. t + 1 (without the last one where the text ends: one byte lower, shifted back)
             auto fetch = [&](const u64 t, const bool valid) -> u64 {
-                struct __attribute__((packed)) U64p { u64 v; };
                 if (!valid || t < 16u)
                     return 0ull;
                 const bool hasB = t + 1 < a.text_len;
-                const u64 q8 = reinterpret_cast<const U64p *>(a.text + (t - (hasB ? 6u : 7u)))->v;
+                const u64 q8 = load_unaligned<u64>(a.text + (t - (hasB ? 6u : 7u)));
                 return hasB ? q8 : (q8 >> 8);
             };
             // Two dependent round trips per batch (window, then bucket) and, on a text where most candidates reach their bucket, three
@@ -977,7 +973,7 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
             if (ANCH && n) // (wave-uniform) the END-pair bitmap is the next unit's again
                 *reinterpret_cast<uint4 *>(ebits + lane * 4u) = make_uint4(0u, 0u, 0u, 0u);
         }
-        LS2 wls{0, false, false, false};
+        LineState wls{0, false, false, false};
         if (LINES)
         {
             wls = ac_line_pass(kAcRounds * kCells, [&](int rj, u32 &H, u32 &N) {
@@ -994,8 +990,7 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
         {
             u64 info = (u64)wcnt;
             if (LINES)
-                info |= (wls.nl ? kLnNl : 0) | (wls.head ? kLnHead : 0) | (wls.tail ? kLnTail : 0) |
-                        ((u64)(wls.cnt & kUiLineMask) << kUiLineShift);
+                info |= line_bits(wls) | ((u64)(wls.cnt & kUiLineMask) << kUiLineShift);
             else if (wcnt)
                 info |= kLnHead | kLnTail;
             if (parked)

@@ -26,6 +26,7 @@
 #include "../../include/krep_gpu.h"
 #include "kg_ac_common.h"
 #include "kg_ac_tables.h"
+#include "kg_device.h"
 #include "kg_internal.h"
 
 namespace kg {
@@ -38,9 +39,8 @@ __global__ __launch_bounds__(256) void ac_gram_hist_kernel(const uint8_t *text, 
 {
     const u64 c = blockIdx.x;
     u64 base = lo + (nchunks > 1 ? (span - chunk_bytes) / (nchunks - 1) * c : 0ull);
-    struct __attribute__((packed)) U32p { u32 v; };
     for (u32 p = threadIdx.x; p + 4u <= chunk_bytes; p += blockDim.x)
-        atomicAdd(&hist[ac_cls4(reinterpret_cast<const U32p *>(text + base + p)->v)], 1u);
+        atomicAdd(&hist[ac_cls4(load_unaligned<u32>(text + base + p))], 1u);
 }
 
 // how often do the given five-class grams (sorted keys, c(b0) | c(b1) << 5 | ... | c(b4) << 20) occur in the same sample?
@@ -49,10 +49,9 @@ __global__ __launch_bounds__(256) void ac_gram5_count_kernel(const uint8_t *text
 {
     const u64 c = blockIdx.x;
     const u64 base = lo + (nchunks > 1 ? (span - chunk_bytes) / (nchunks - 1) * c : 0ull);
-    struct __attribute__((packed)) U32p { u32 v; };
     for (u32 p = threadIdx.x; p + 5u <= chunk_bytes; p += blockDim.x)
     {
-        const u32 key = ac_cls4(reinterpret_cast<const U32p *>(text + base + p)->v) | (((u32)text[base + p + 4] & 31u) << 20);
+        const u32 key = ac_cls4(load_unaligned<u32>(text + base + p)) | (((u32)text[base + p + 4] & 31u) << 20);
         u32 a = 0, b = nkeys; // lower bound
         while (a < b)
         {

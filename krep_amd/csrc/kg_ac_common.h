@@ -3,12 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kg_common.h"
+#include "kg_device.h"
 
 namespace kg {
 
-
-using u32 = uint32_t;
-using u64 = unsigned long long;
 
 #ifndef KG_AC_BLOCK
 #define KG_AC_BLOCK 1024
@@ -102,11 +100,6 @@ u32 ac_tiny_dense_ring(); // 16-bit ring entries per wave of its DENSE flavour
 constexpr u32 kTinyRing = 1024; // items (12 bytes: a lane-cell's two length words + its index) per wave of the one-pass kernel's LDS ring:
                                 // the ticket being scanned + the one waiting
 
-__device__ __forceinline__ u32 ac_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ u64 ac_rfl64(u64 v)
-{
-    return ((u64)__builtin_amdgcn_readfirstlane((u32)(v >> 32)) << 32) | __builtin_amdgcn_readfirstlane((u32)v);
-}
 // inclusive prefix sum over the 64 lanes on the DPP network: four row shifts inside the rows of 16, then lane 15 of rows 0 / 2 into rows
 // 1 / 3 and lane 31 into rows 2 and 3 — six v_add with a DPP modifier, no LDS traffic and no per-lane address registers (the shuffle
 // version keeps six of them alive for as long as it is loop-invariant)
@@ -125,15 +118,7 @@ __device__ __forceinline__ u32 ac_fold4(u32 x)
     u32 t = x & 0x7f7f7f7fu;
     return x | (((t + 0x3f3f3f3fu) & ~(t + 0x25252525u) & ~x & 0x80808080u) >> 2);
 }
-__device__ __forceinline__ u32 ac_eq_bytes(u32 x, u32 c4)
-{
-    u32 y = x ^ c4;
-    return ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu);
-}
-__device__ __forceinline__ u32 ac_movemask4(u32 t) { return (((t >> 7) * 0x00204081u) >> 21) & 0xfu; }
-__device__ __forceinline__ bool ac_wordc(u32 c) { return (c - '0' < 10u) || ((c | 0x20u) - 'a' < 26u) || c == '_'; }
 
-struct LS2 { u32 cnt; bool nl, head, tail; };
 // The distinct lines of a unit that hold a match END, from the 16-bit hit / newline masks H, N of its lane-cells (get(rj, H, N),
 // rj = cell of the unit, this lane's 16 bytes): a line is counted at its first match.  Inside a lane that is carry arithmetic on
 // the two masks; across the 64 lanes of a cell "does the line that enters this lane already hold a match" is a carry chain —
@@ -142,7 +127,7 @@ struct LS2 { u32 cnt; bool nl, head, tail; };
 // scheme as kg_literal.hip line_cell.  Round 4 resolved every cell with four ballots, a per-lane search for the nearest newline
 // lane below and a shuffle reduction, and the -c instantiations spilled 8-44 bytes per lane).
 template <typename Get>
-__device__ __forceinline__ LS2 ac_line_pass(int ncells, Get get)
+__device__ __forceinline__ LineState ac_line_pass(int ncells, Get get)
 {
     u32 l_cnt = 0, s_new = 0;
     bool s_open = false, s_seen = false, s_head = false;
@@ -182,12 +167,7 @@ __device__ __forceinline__ LS2 ac_line_pass(int ncells, Get get)
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1)
         l_cnt += __shfl_xor(l_cnt, o);
-    return LS2{l_cnt + s_new, s_seen, s_seen ? s_head : s_open, s_open};
-}
-__device__ __forceinline__ LS2 ls2_combine(const LS2 &a, const LS2 &b)
-{
-    return LS2{a.cnt + b.cnt - ((a.tail && b.head) ? 1u : 0u), a.nl || b.nl, a.nl ? a.head : (a.head || b.head),
-               b.nl ? b.tail : (a.tail || b.tail)};
+    return LineState{l_cnt + s_new, s_seen, s_seen ? s_head : s_open, s_open};
 }
 
 // Walk the reversed trie from end index i.  EMIT == false: returns the number of matches ending at i
@@ -204,8 +184,7 @@ __device__ __forceinline__ u32 ac_walk(const AcArgs &a, u64 i, u32 total, Put pu
     if (JUMP && i >= 3)
     {
         // every pattern has >= 4 bytes: resolve trie levels 1..4 with ONE probe keyed by the exact last 4 bytes
-        struct __attribute__((packed)) U32p { u32 v; };
-        u32 E = reinterpret_cast<const U32p *>(a.text + (i - 3))->v; // one unaligned dword load
+        u32 E = load_unaligned<u32>(a.text + (i - 3)); // one unaligned dword load
         if (CI)
             E = ac_fold4(E);
         for (u32 h = (E * kHashMul) >> 9;; ++h)
@@ -254,9 +233,9 @@ __device__ __forceinline__ u32 ac_walk(const AcArgs &a, u64 i, u32 total, Put pu
             bool ok = lines ? true : (s >= a.own_lo && s < a.own_hi); // -c owns by END index (see ac_scan)
             if (ok && ww)
             {
-                if (s > 0 && ac_wordc(a.text[s - 1]))
+                if (s > 0 && is_wordc(a.text[s - 1]))
                     ok = false;
-                else if (i + 1 < a.text_len && ac_wordc(a.text[i + 1]))
+                else if (i + 1 < a.text_len && is_wordc(a.text[i + 1]))
                     ok = false;
             }
             if (ok)
@@ -289,9 +268,8 @@ __device__ __forceinline__ u32 ac_walk_levels(const AcArgs &a, u64 i, bool own_b
         simple = false;
         return ac_walk<CI, false, true>(a, i, 0u, [](u32, u64, u32) {});
     }
-    struct __attribute__((packed)) U32p { u32 v; };
-    const U32p *q = reinterpret_cast<const U32p *>(a.text + (i - 15));
-    u32 T[4] = {q[0].v, q[1].v, q[2].v, q[3].v};
+    const uint8_t *q = a.text + (i - 15);
+    u32 T[4] = {load_unaligned<u32>(q), load_unaligned<u32>(q + 4), load_unaligned<u32>(q + 8), load_unaligned<u32>(q + 12)};
     if (CI)
     {
 #pragma unroll
@@ -353,9 +331,9 @@ __device__ __forceinline__ u32 ac_walk_levels(const AcArgs &a, u64 i, bool own_b
             bool ok = own_by_end ? true : (s >= a.own_lo && s < a.own_hi);
             if (ok && ww)
             {
-                if (s > 0 && ac_wordc(a.text[s - 1]))
+                if (s > 0 && is_wordc(a.text[s - 1]))
                     ok = false;
-                else if (i + 1 < a.text_len && ac_wordc(a.text[i + 1]))
+                else if (i + 1 < a.text_len && is_wordc(a.text[i + 1]))
                     ok = false;
             }
             if (ok)
@@ -461,9 +439,8 @@ __device__ __forceinline__ u32 ac_walk_fast(const AcArgs &a, u64 i, bool own_by_
     u32 dm = 0;
     if (!slow)
     {
-        struct __attribute__((packed)) U32p { u32 v; };
-        const U32p *q = reinterpret_cast<const U32p *>(a.text + (i - 15));
-        u32 T[4] = {q[0].v, q[1].v, q[2].v, q[3].v};
+        const uint8_t *q = a.text + (i - 15);
+        u32 T[4] = {load_unaligned<u32>(q), load_unaligned<u32>(q + 4), load_unaligned<u32>(q + 8), load_unaligned<u32>(q + 12)};
         if (CI)
         {
 #pragma unroll
@@ -537,13 +514,11 @@ __device__ __forceinline__ void ac_walk_probe2(const AcArgs &a, u64 i, bool live
     // ONE 17-byte window serves both ends: A = its first 16 bytes (the text up to i), B = the same one byte further (up to
     // i + 1) by funnel shifts.  Only the byte text[i + 1] is read behind A, and only when it exists (liveB): nothing is
     // touched past the end of the buffer.
-    struct __attribute__((packed)) U32p { u32 v; };
-    struct __attribute__((packed)) U64p { u64 v; };
     u32 w0 = 0, w1 = 0, w2 = 0, w3 = 0, w4 = 0;
     if constexpr (STAGED)
     {
         // bytes i - 6 .. i + 1 (without the last one where it does not exist: one byte lower, shifted back)
-        const u64 q8 = reinterpret_cast<const U64p *>(a.text + (i - (liveB ? 6u : 7u)))->v;
+        const u64 q8 = load_unaligned<u64>(a.text + (i - (liveB ? 6u : 7u)));
         const u64 Q = liveB ? q8 : (q8 >> 8);
         w3 = (u32)(Q >> 24);                                // bytes i - 3 .. i
         w4 = (u32)(Q >> 56);                                // byte i + 1
@@ -553,14 +528,14 @@ __device__ __forceinline__ void ac_walk_probe2(const AcArgs &a, u64 i, bool live
             liveB = gtest((u32)(Q >> 32));                  // bytes i - 2 .. i + 1
         if (liveA || liveB)
         {
-            const U32p *qa = reinterpret_cast<const U32p *>(a.text + (i - 15));
-            w0 = qa[0].v; w1 = qa[1].v; w2 = qa[2].v;
+            const uint8_t *qa = a.text + (i - 15);
+            w0 = load_unaligned<u32>(qa); w1 = load_unaligned<u32>(qa + 4); w2 = load_unaligned<u32>(qa + 8);
         }
     }
     else
     {
-        const U32p *qa = reinterpret_cast<const U32p *>(a.text + (i - 15));
-        w0 = qa[0].v; w1 = qa[1].v; w2 = qa[2].v; w3 = qa[3].v;
+        const uint8_t *qa = a.text + (i - 15);
+        w0 = load_unaligned<u32>(qa); w1 = load_unaligned<u32>(qa + 4); w2 = load_unaligned<u32>(qa + 8); w3 = load_unaligned<u32>(qa + 12);
         w4 = liveB ? (u32)a.text[i + 1] : 0u;
         if (liveA)
             liveA = gtest(__builtin_amdgcn_alignbyte(w3, w2, 3));
@@ -653,7 +628,7 @@ __device__ __forceinline__ void ac_walk_probe2(const AcArgs &a, u64 i, bool live
         auto wwf = [&](u32 m, const u32 (&T)[4], u64 e) -> u32 {
             if (!m)
                 return 0u;
-            if (e + 1 < a.text_len && ac_wordc(a.text[e + 1]))
+            if (e + 1 < a.text_len && is_wordc(a.text[e + 1]))
                 return 0u;
             u32 r = m;
             for (u32 rest = m; rest;)
@@ -668,7 +643,7 @@ __device__ __forceinline__ void ac_walk_probe2(const AcArgs &a, u64 i, bool live
                 }
                 else if (e >= d)
                     c = a.text[e - d];
-                if (ac_wordc(c))
+                if (is_wordc(c))
                     r &= ~(1u << d);
             }
             return r;
@@ -705,9 +680,8 @@ __host__ __device__ __forceinline__ u32 ac_xlen_slot8(u32 w2, u32 w3)
 template <bool CI>
 __device__ __forceinline__ u32 ac_exact_end(const AcArgs &a, u64 i, bool &multi)
 {
-    struct __attribute__((packed)) U32p { u32 v; };
-    const U32p *q = reinterpret_cast<const U32p *>(a.text + (i - 15));
-    u32 T[4] = {q[0].v, q[1].v, q[2].v, q[3].v};
+    const uint8_t *q = a.text + (i - 15);
+    u32 T[4] = {load_unaligned<u32>(q), load_unaligned<u32>(q + 4), load_unaligned<u32>(q + 8), load_unaligned<u32>(q + 12)};
     if (CI)
     {
 #pragma unroll
@@ -749,10 +723,9 @@ __device__ __forceinline__ u32 ac_exact_end(const AcArgs &a, u64 i, bool &multi)
 template <bool CI, bool WW>
 __device__ __forceinline__ void ac_exact_end2(const AcArgs &a, u64 i, bool liveA, bool liveB, u32 &dmA, u32 &dmB, bool &multiA, bool &multiB)
 {
-    struct __attribute__((packed)) U32p { u32 v; };
     constexpr bool ww = WW; // -w (is_whole_word_match krep.h:312-319): a match needs a non-word byte (or the text's edge) on either side
-    const U32p *q = reinterpret_cast<const U32p *>(a.text + (i - 15));
-    u32 TA[4] = {q[0].v, q[1].v, q[2].v, q[3].v};
+    const uint8_t *q = a.text + (i - 15);
+    u32 TA[4] = {load_unaligned<u32>(q), load_unaligned<u32>(q + 4), load_unaligned<u32>(q + 8), load_unaligned<u32>(q + 12)};
     const u32 nxt = ((liveB || ww) && i + 1 < a.text_len) ? (u32)a.text[i + 1] : 0u; // (a live end i + 1 lies inside the text)
     // -w: the byte behind end i + 1, and the byte in front of a 16-byte pattern that ends at i (the other neighbours are in the window)
     const u32 nxt2 = (ww && liveB && i + 2 < a.text_len) ? (u32)a.text[i + 2] : 0u;
@@ -777,9 +750,9 @@ __device__ __forceinline__ void ac_exact_end2(const AcArgs &a, u64 i, bool liveA
     u32 lmA = liveA ? ((a4 & 0xfu) | (a8 & 0x1ff0u)) : 0u, lmB = liveB ? ((b4 & 0xfu) | (b8 & 0x1ff0u)) : 0u;
     if (ww)
     { // a word character behind the end: no pattern ends here as a whole word
-        if (ac_wordc(nxt))
+        if (is_wordc(nxt))
             lmA = 0u;
-        if (ac_wordc(nxt2))
+        if (is_wordc(nxt2))
             lmB = 0u;
     }
     dmA = dmB = 0;
@@ -797,10 +770,10 @@ __device__ __forceinline__ void ac_exact_end2(const AcArgs &a, u64 i, bool liveA
     // 16 bytes: `far`, the byte in front of the window — 0 where the text starts there)
     auto left_is_word = [](const u32 (&T)[4], u32 len, u32 far) -> bool {
         if (len >= 16u)
-            return ac_wordc(far);
+            return is_wordc(far);
         const u32 at = 15u - len, w = at >> 2;
         const u32 word = w == 0u ? T[0] : w == 1u ? T[1] : w == 2u ? T[2] : T[3];
-        return ac_wordc((word >> (8u * (at & 3u))) & 0xffu);
+        return is_wordc((word >> (8u * (at & 3u))) & 0xffu);
     };
     while (lmA | lmB)
     {

@@ -7,7 +7,7 @@
 // registers, four positions per dword:
 //   X_j = the lane's 16 bytes shifted by j bytes (byte e of X_j is text[e - j]; 3 x 4 v_alignbyte per 1-KiB cell),
 //   a pattern c_0 .. c_{L-1} ends at byte e  <=>  byte e of  V = (X_{L-1} ^ c_0c_0c_0c_0) | ... | (X_0 ^ c_{L-1}...)  is zero,
-//   one exact zero-byte test per pattern and dword (ac_eq_bytes), OR-ed into one flag word per LENGTH and dword.
+//   one exact zero-byte test per pattern and dword (eq_bytes), OR-ed into one flag word per LENGTH and dword.
 // What a cell leaves depends on what the scan is for (template parameters):
 //   * a count (`KEEP = false`): the popcounts of the flag words — no LDS at all, 12 waves per CU;
 //   * records (`KEEP`): per lane-cell the four lengths' 16-bit masks in a scrambled order that costs 4 shifts instead of 4
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
 {
     static_assert(!DENSE || (FUSED && !FIVE), "DENSE is a flavour of the one-pass writer");
     extern __shared__ __attribute__((aligned(16))) u32 s_tiny[];
-    const u32 lane = ac_lane(), wave = threadIdx.x >> 6;
+    const u32 lane = lane_id(), wave = threadIdx.x >> 6;
     static_assert(!FUSED || (!LINES && !KEEP && !EMIT), "the one-pass record writer is its own mode");
     static_assert(!FIVE || (!LINES && !KEEP && !EMIT && !LONG), "a fifth class: counting and one-pass records only");
     if constexpr (FUSED)
@@ -106,12 +106,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
         // the resolver: whichever wave 0 of a block gets here first (a wave that runs, whatever part of the grid is resident)
         bool resolver = false;
         if (__builtin_amdgcn_readfirstlane(wave) == 0u)
-        {
-            u64 r = 1;
-            if (lane == 0)
-                r = __hip_atomic_fetch_add(&a.ctr->pad[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            resolver = ac_rfl64(r) == 0ull;
-        }
+            resolver = wave_fetch_add(&a.ctr->pad[0], 1ull, lane) == 0ull;
         if (resolver)
         {
             tk_resolve(a.tk_agg, a.tk_pref, a.n_tk, a.ctr, lane);
@@ -211,7 +206,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
             u32 excl = 0, tot = 0;
             auto plane = [&](const int b) __attribute__((always_inline)) {
                 const u64 bm = __ballot((c >> b) & 1u);
-                excl += __builtin_amdgcn_mbcnt_hi((u32)(bm >> 32), __builtin_amdgcn_mbcnt_lo((u32)bm, 0u)) << b;
+                excl += mbcnt64(bm) << b;
                 tot += (u32)__popcll(bm) << b;
             };
             plane(0);
@@ -264,10 +259,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
 
     for (;;)
     {
-        u64 tk = 0;
-        if (lane == 0)
-            tk = __hip_atomic_fetch_add(&a.ctr->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tk = ac_rfl64(tk);
+        const u64 tk = wave_fetch_add(&a.ctr->ticket, 1ull, lane);
         // (emit mode draws groups of 64 units and looks at all their info words at once: one load per lane and a ballot instead
         //  of a dependent load per unit)
         const u64 upt = EMIT ? 64ull : (u64)a.upt;
@@ -362,7 +354,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                     {
 #pragma unroll
                         for (int w = 0; w < 4; ++w)
-                            NL |= ac_movemask4(ac_eq_bytes(D[w], 0x0a0a0a0au)) << (4 * w);
+                            NL |= movemask4(eq_bytes(D[w], 0x0a0a0a0au)) << (4 * w);
                     }
                     // ---- the shifted copies of the lane's bytes: byte e of X[s][w] is text[lane base + 4 w + e - s], as far back
                     //      as the longest pattern reaches (a class that uses X[s] exists only when lmax > s: never read undefined)
@@ -459,7 +451,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                                     }
                                 }
                             }
-                            const u32 z = ~(((V & k7f) + k7f) | V | k7f); // 0x80 in every zero byte, exact (ac_eq_bytes)
+                            const u32 z = ~(((V & k7f) + k7f) | V | k7f); // 0x80 in every zero byte, exact (eq_bytes)
                             Z[w] = first ? z : (Z[w] | z);
                         }
                     };
@@ -509,7 +501,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                                 u32 pm = 0;
 #pragma unroll
                                 for (int w = 0; w < 4; ++w)
-                                    pm |= ac_movemask4(Z[w]) << (4 * w);
+                                    pm |= movemask4(Z[w]) << (4 * w);
                                 const u64 lm1 = (L == 4 ? (u64)len4 : (u64)L) - 1ull; // (class 4 may stand for a long length)
                                 pm &= clip(a.end_lo, a.end_hi) & clip(lm1, ~0ull);
                                 if (!LINES)
@@ -567,7 +559,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                                 u32 pm = 0;
 #pragma unroll
                                 for (int w = 0; w < 4; ++w)
-                                    pm |= ac_movemask4(Z[w]) << (4 * w);
+                                    pm |= movemask4(Z[w]) << (4 * w);
                                 const u64 lm1 = (u64)ll - 1ull;
                                 pm &= clip(a.end_lo, a.end_hi) & clip(lm1, ~0ull) & clip(a.own_lo + lm1, a.own_hi + lm1);
                                 F5 = tiny_scramble16(pm);
@@ -602,7 +594,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                             u32 idx = f_items, tot = 0;
                             auto plane = [&](const int b) __attribute__((always_inline)) {
                                 const u64 bm = __ballot((c >> b) & 1u);
-                                idx += __builtin_amdgcn_mbcnt_hi((u32)(bm >> 32), __builtin_amdgcn_mbcnt_lo((u32)bm, 0u)) << b;
+                                idx += mbcnt64(bm) << b;
                                 tot += (u32)__popcll(bm) << b;
                             };
                             plane(0);
@@ -647,7 +639,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                         const u64 bm = __ballot(c != 0u);
                         if (bm)
                         {
-                            const u32 idx = f_items + __builtin_amdgcn_mbcnt_hi((u32)(bm >> 32), __builtin_amdgcn_mbcnt_lo((u32)bm, 0u));
+                            const u32 idx = f_items + mbcnt64(bm);
                             if (c && idx < f_room)
                             {
                                 const u32 slot = (f_at + idx) & (kTinyRing - 1u);
@@ -665,7 +657,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                         {
 #pragma unroll
                             for (int w = 0; w < 4; ++w)
-                                m16 |= ac_movemask4(HA[w]) << (4 * w);
+                                m16 |= movemask4(HA[w]) << (4 * w);
                         }
                         u32 nlm = NL;
                         if (!inter)
@@ -916,13 +908,13 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                     acc_total += mycnt;
             }
 
-            LS2 wls{0, false, false, false};
+            LineState wls{0, false, false, false};
             if constexpr (LINL)
             {
 #pragma unroll
                 for (int o = 32; o >= 1; o >>= 1)
                     l_cnt += __shfl_xor(l_cnt, o);
-                wls = LS2{l_cnt + s_new, s_seen, s_seen ? s_head : s_open, s_open};
+                wls = LineState{l_cnt + s_new, s_seen, s_seen ? s_head : s_open, s_open};
             }
 
             if (chain)
@@ -930,7 +922,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
             if (chain && !emit_final && lane == 0)
             {
                 u64 info = (u64)wcnt;
-                if (LINES)
+                if (LINES) // (written out: through line_bits() the four LINES instantiations compile differently)
                     info |= (wls.nl ? kLnNl : 0) | (wls.head ? kLnHead : 0) | (wls.tail ? kLnTail : 0) |
                             ((u64)(wls.cnt & kUiLineMask) << kUiLineShift);
                 else if (wcnt)

@@ -16,12 +16,10 @@
 #include <mutex>
 
 #include "../../include/krep_gpu.h"
+#include "kg_device.h"
 #include "kg_internal.h"
 
 namespace kg {
-
-using u32 = uint32_t;
-using u64 = unsigned long long;
 
 #define FCHK(x)                                                                                \
     do                                                                                         \
@@ -77,8 +75,7 @@ __global__ __launch_bounds__(256) void fmt_count_newlines(const uint8_t *__restr
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                 {
-                    const u32 y = w[q] ^ 0x0a0a0a0au;
-                    c += (u32)__popc(~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu));
+                    c += (u32)__popc(eq_bytes(w[q], 0x0a0a0a0au));
                 }
             }
             else
@@ -109,10 +106,7 @@ __global__ void fmt_line_numbers(const uint8_t *__restrict__ text, u64 text_len,
     }
     const u64 s = g - base, b = s / kLineBlock;
     u64 ln = 1 + block_prefix[b];
-    auto nl4 = [](u32 w) -> u32 { // newlines among the 4 bytes of w (exact SWAR byte equality)
-        const u32 y = w ^ 0x0a0a0a0au;
-        return (u32)__popc(~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu));
-    };
+    auto nl4 = [](u32 w) -> u32 { return (u32)__popc(eq_bytes(w, 0x0a0a0a0au)); }; // newlines among the 4 bytes of w
     u64 p = b * kLineBlock;
     if ((reinterpret_cast<size_t>(text) & 15u) == 0) // 16 bytes at a time while they lie wholly before `s`
         for (; p + 16 <= s; p += 16)

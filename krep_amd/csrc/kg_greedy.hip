@@ -26,18 +26,14 @@
 #include <algorithm>
 #include <cstdlib>
 #include "kg_common.h"
+#include "kg_device.h"
 #include "kg_internal.h"
 
 namespace kg {
 
-using u32 = uint32_t;
-using u64 = unsigned long long;
-
 constexpr int kGB = 256;            // threads per block
 constexpr int kGPer = 4;            // elements per thread in the compaction kernels
 constexpr int kGBlockElems = kGB * kGPer;
-
-__device__ __forceinline__ bool g_wordc(u32 c) { return (c - '0' < 10u) || ((c | 0x20u) - 'a' < 26u) || c == '_'; }
 
 __device__ __forceinline__ uint8_t g_fold(uint8_t c) { return (c >= 'A' && c <= 'Z') ? (uint8_t)(c + 32) : c; }
 
@@ -62,9 +58,9 @@ __device__ __forceinline__ Visit g_visit(const WalkSpec &ws, u64 sj, u64 base, c
     bool ok = true;
     if (ws.ww)
     {
-        if (p > 0 && g_wordc(text[p - 1]))
+        if (p > 0 && is_wordc(text[p - 1]))
             ok = false;
-        else if (p + m < text_len && g_wordc(text[p + m]))
+        else if (p + m < text_len && is_wordc(text[p + m]))
             ok = false;
     }
     if (ok && ws.mode == kWalkShortOLines)
@@ -74,10 +70,9 @@ __device__ __forceinline__ Visit g_visit(const WalkSpec &ws, u64 sj, u64 base, c
         // (eight bytes per step until a word holds the '\n': every candidate of the list pays this walk in g_next's parallel form,
         //  visited or not, and a text with very long lines made it a byte loop per candidate — ADVICE r05)
         u64 q = p;
-        struct __attribute__((packed)) U64p { u64 v; };
         while (q + 8 <= text_len)
         {
-            const u64 y = reinterpret_cast<const U64p *>(text + q)->v ^ 0x0a0a0a0a0a0a0a0aull;
+            const u64 y = load_unaligned<u64>(text + q) ^ 0x0a0a0a0a0a0a0a0aull;
             if ((y - 0x0101010101010101ull) & ~y & 0x8080808080808080ull)
                 break;
             q += 8;
@@ -216,9 +211,9 @@ __global__ __launch_bounds__(kGB) void g_ww(const u64 *__restrict__ occ, u64 n, 
         return;
     const u64 p = occ[2 * i] - base; // offset inside the device buffer
     bool ok = true;
-    if (p > 0 && g_wordc(text[p - 1]))
+    if (p > 0 && is_wordc(text[p - 1]))
         ok = false;
-    else if (p + m < text_len && g_wordc(text[p + m]))
+    else if (p + m < text_len && is_wordc(text[p + m]))
         ok = false;
     if (!ok)
         keep[i] &= (uint8_t)~kKeep; // still visited: a rejected hit consumed (krep.c:4767, :1684)

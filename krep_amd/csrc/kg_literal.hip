@@ -30,48 +30,9 @@
 #include <cstdlib>
 #include <type_traits>
 #include "kg_common.h"
+#include "kg_device.h"
 
 namespace kg {
-
-using u32 = uint32_t;
-using u64 = unsigned long long;
-
-__device__ __forceinline__ u32 lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-// popcount(mask & lanes_below_me)
-__device__ __forceinline__ u32 mbcnt64(u64 m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
-__device__ __forceinline__ u64 rfl64(u64 v)
-{
-    u32 lo = __builtin_amdgcn_readfirstlane((u32)v), hi = __builtin_amdgcn_readfirstlane((u32)(v >> 32));
-    return ((u64)hi << 32) | lo;
-}
-
-// 0x80 in every byte of x that equals the byte replicated in c4 (exact, no false positives)
-__device__ __forceinline__ u32 eq_bytes(u32 x, u32 c4)
-{
-    u32 y = x ^ c4;
-    u32 t = (y & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    return ~(t | y | 0x7f7f7f7fu);
-}
-// gather the four 0x80 flags of a dword into a 4-bit mask
-__device__ __forceinline__ u32 movemask4(u32 t) { return (((t >> 7) * 0x00204081u) >> 21) & 0xfu; }
-
-__device__ __forceinline__ bool is_wordc(u32 c)
-{
-    return (c - '0' < 10u) || ((c | 0x20u) - 'a' < 26u) || c == '_';
-}
-
-// ---- line bookkeeping monoid: a window summarised as (cnt, has_nl, head, tail) -------------
-struct LS { u32 cnt; bool nl, head, tail; };
-__device__ __forceinline__ LS ls_combine(const LS &a, const LS &b)
-{
-    LS r;
-    r.cnt = a.cnt + b.cnt - ((a.tail && b.head) ? 1u : 0u);
-    r.nl = a.nl || b.nl;
-    r.head = a.nl ? a.head : (a.head || b.head);
-    r.tail = b.nl ? b.tail : (a.tail || b.tail);
-    return r;
-}
-__device__ __forceinline__ u64 ls_bits(const LS &s) { return (s.nl ? kLnNl : 0) | (s.head ? kLnHead : 0) | (s.tail ? kLnTail : 0); }
 
 // wave sum of a small per-lane value (< 32) through ballot bit-planes: SALU only
 // (two planes when no lane exceeds 3 — even the 1 % single-byte workload almost never has 4 hits in 16 bytes)
@@ -94,26 +55,6 @@ __device__ __forceinline__ u32 wave_excl5(u32 v)
     for (int b = 0; b < 5; ++b)
         s += mbcnt64(__ballot((v >> b) & 1u)) << b;
     return s;
-}
-
-// guarded 24-byte window for the (at most two) tiles that touch the end of the buffer
-struct W6 { u32 v[6]; };
-__device__ __noinline__ W6 load_window_guarded(const uint8_t *text, u64 text_len, u64 off)
-{
-    W6 r;
-#pragma unroll
-    for (int w = 0; w < 6; ++w)
-    {
-        u32 v = 0;
-        for (int b = 0; b < 4; ++b)
-        {
-            u64 o = off + (u64)(w * 4 + b);
-            if (o < text_len)
-                v |= (u32)text[o] << (8 * b);
-        }
-        r.v[w] = v;
-    }
-    return r;
 }
 
 // KIND: 1 -> m == 1 (SWAR), 4 -> 2..4 bytes (one word), 8 -> 5..8 bytes (two words), 9 -> m > 8 (filter+verify),
@@ -200,6 +141,8 @@ __global__ __launch_bounds__(kBlock, (KIND == 1 && LINES && R == 4) ? KG_LIT1_LI
         {
             while (!em_mask)
             {
+                // (both draws of this kernel are written out: through wave_fetch_add() the compiler orders the loop's blocks
+                //  differently and assigns other registers in most instantiations)
                 u64 g = 0;
                 if (lane == 0)
                     g = __hip_atomic_fetch_add(&a.ctr->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -244,7 +187,6 @@ __global__ __launch_bounds__(kBlock, (KIND == 1 && LINES && R == 4) ? KG_LIT1_LI
         // candidates — a pattern that overlaps itself within 16 bytes — takes a second iteration), every lane's loads in flight
         // together; the survivors are ranked behind the unit's hits so far and staged (or, in emit mode, written out) in order
         auto verify_parked = [&]() __attribute__((always_inline)) {
-            struct __attribute__((packed)) U64p { unsigned long long v; };
             typedef const __attribute__((address_space(4))) unsigned long long cu64;
             cu64 *pc = (cu64 *)(size_t)a.pat_chunks;
             const u32 last = a.n_chunks - 1u;
@@ -283,7 +225,7 @@ __global__ __launch_bounds__(kBlock, (KIND == 1 && LINES && R == 4) ? KG_LIT1_LI
                             {
                                 const u32 kk = g0 + i < last ? g0 + i : last;
                                 const u32 q = 8u + 8u * kk < a.m - 8u ? 8u + 8u * kk : a.m - 8u;
-                                t[i] = reinterpret_cast<const U64p *>(tp + q)->v;
+                                t[i] = load_unaligned<u64>(tp + q);
                             }
 #pragma unroll
                             for (u32 i = 0; i < W; ++i)
@@ -353,7 +295,7 @@ __global__ __launch_bounds__(kBlock, (KIND == 1 && LINES && R == 4) ? KG_LIT1_LI
             }
             n_cand = 0;
         };
-        LS wls{0, false, false, false};
+        LineState wls{0, false, false, false};
         // ---- -c: the line bookkeeping of a unit (round 5).  A line that holds a match is counted at its FIRST match.  Inside a
         // lane's 16 bytes that is carry arithmetic on the hit / newline masks (l_cnt: first match behind a newline OF THIS LANE,
         // summed over the unit in a vector register, reduced once per unit); the part of a lane in front of its first newline
@@ -698,7 +640,6 @@ __global__ __launch_bounds__(kBlock, (KIND == 1 && LINES && R == 4) ? KG_LIT1_LI
                             // exit: a byte loop paid one dependent global access per byte — 5.6 -> 3.3 TB/s at
                             // m = 9, 1.3 at m = 64); the last partial chunk is re-anchored at m - 8, which is
                             // inside [p, p + m) and therefore inside the text
-                            struct __attribute__((packed)) U64p { unsigned long long v; };
                             const unsigned char *tp = a.text + p;
                             // groups of eight chunks: the eight text loads are issued back to back and waited for ONCE.  Round 1's
                             // counted loop cost one dependent memory round trip per chunk (two register pairs under the 128-VGPR
@@ -719,7 +660,7 @@ __global__ __launch_bounds__(kBlock, (KIND == 1 && LINES && R == 4) ? KG_LIT1_LI
                                 {
                                     const u32 k = g0 + i < last ? g0 + i : last;
                                     const u32 q = 8u + 8u * k < a.m - 8u ? 8u + 8u * k : a.m - 8u;
-                                    t[i] = reinterpret_cast<const U64p *>(tp + q)->v;
+                                    t[i] = load_unaligned<u64>(tp + q);
                                 }
 #pragma unroll
                                 for (u32 i = 0; i < W; ++i)
@@ -864,7 +805,7 @@ __global__ __launch_bounds__(kBlock, (KIND == 1 && LINES && R == 4) ? KG_LIT1_LI
             }
             if (KIND == 1)
                 wcnt += h; // (the flag-word cells count their hits per lane)
-            wls = LS{t + s_new, s_seen, s_seen ? s_head : s_open, s_open};
+            wls = LineState{t + s_new, s_seen, s_seen ? s_head : s_open, s_open};
         }
         acc_total += wcnt;
         if (!chain)
@@ -877,7 +818,7 @@ __global__ __launch_bounds__(kBlock, (KIND == 1 && LINES && R == 4) ? KG_LIT1_LI
             {
                 u64 info = (u64)wcnt;
                 if (LINES)
-                    info |= ls_bits(wls) | ((u64)(wls.cnt & kUiLineMask) << kUiLineShift);
+                    info |= line_bits(wls) | ((u64)(wls.cnt & kUiLineMask) << kUiLineShift);
                 else if (wcnt)
                     info |= kLnHead | kLnTail;
                 if (park)

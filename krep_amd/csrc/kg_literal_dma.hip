@@ -19,12 +19,10 @@
 #include <atomic>
 #include <cstdlib>
 #include "kg_common.h"
+#include "kg_device.h"
 #include "kg_internal.h"
 
 namespace kg {
-
-using u32 = uint32_t;
-using u64 = unsigned long long;
 
 namespace {
 
@@ -32,34 +30,6 @@ constexpr u32 kDmaPark = 80;                 // parked units per wave (info word
 constexpr u32 kDmaRing = 2u * kSegBytes;     // two rounds
 constexpr u32 kDmaTail = 256u;               // the DMA piece behind a ticket (4 B per lane)
 constexpr u32 kDmaWaveLds = kDmaRing + kDmaTail; // dynamic LDS per wave; + 44 B per parked unit in static arrays: 20160 B per wave, two workgroups per CU
-
-__device__ __forceinline__ u32 d_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ u32 d_mbcnt(u64 m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
-__device__ __forceinline__ u64 d_rfl64(u64 v)
-{
-    return ((u64)__builtin_amdgcn_readfirstlane((u32)(v >> 32)) << 32) | __builtin_amdgcn_readfirstlane((u32)v);
-}
-__device__ __forceinline__ bool d_wordc(u32 c) { return (c - '0' < 10u) || ((c | 0x20u) - 'a' < 26u) || c == '_'; }
-
-struct W6d { u32 v[6]; };
-__device__ __noinline__ W6d d_window_guarded(const uint8_t *text, u64 text_len, u64 off)
-{
-    W6d r;
-#pragma unroll
-    for (int w = 0; w < 6; ++w)
-    {
-        u32 v = 0;
-        for (int b = 0; b < 4; ++b)
-        {
-            const u64 o = off + (u64)(w * 4 + b);
-            if (o < text_len)
-                v |= (u32)text[o] << (8 * b);
-        }
-        r.v[w] = v;
-    }
-    return r;
-}
-
 } // namespace
 
 template <int KIND, bool MASKED, bool CI>
@@ -72,7 +42,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
     __shared__ u64 s_info_all[kWavesPerBlk][kDmaPark];
     __shared__ __attribute__((aligned(16))) unsigned short s_slots_all[kWavesPerBlk][kDmaPark * 16u];
     __shared__ u32 s_unit_all[kWavesPerBlk][kDmaPark];
-    const u32 lane = d_lane();
+    const u32 lane = lane_id();
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t *ring = d_smem + wave * kDmaWaveLds;
     uint8_t *tailb = ring + kDmaRing;
@@ -114,10 +84,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
     auto next_ticket = [&]() -> u64 {
         if (a.upt)
         {
-            u64 tk = 0;
-            if (lane == 0)
-                tk = __hip_atomic_fetch_add(&a.ctr->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return d_rfl64(tk) * (u64)a.upt;
+            return wave_fetch_add(&a.ctr->ticket, 1ull, lane) * (u64)a.upt;
         }
         const u64 u = static_next;
         static_next += (u64)gridDim.x * kWavesPerBlk;
@@ -192,9 +159,9 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
     };
     auto owned = [&](u64 p) -> bool { return p >= a.own_lo && p < hi_match && !(p >= a.excl_lo && p < a.excl_hi); };
     auto word_ok = [&](u64 p) -> bool { // -w: is_whole_word_match (krep.h:312-319)
-        if (p > 0 && p != a.ww_exempt_left && d_wordc(a.text[p - 1]))
+        if (p > 0 && p != a.ww_exempt_left && is_wordc(a.text[p - 1]))
             return false;
-        if (p + a.m < a.text_len && d_wordc(a.text[p + a.m]))
+        if (p + a.m < a.text_len && is_wordc(a.text[p + a.m]))
             return false;
         return true;
     };
@@ -220,7 +187,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
         if (bm)
         {
             if (h && want_pos)
-                stage_hit(unit, wcnt + d_mbcnt(bm), r_prev * kSegBytes + (kSegBytes - 8u) + q);
+                stage_hit(unit, wcnt + mbcnt64(bm), r_prev * kSegBytes + (kSegBytes - 8u) + q);
             wcnt += (u32)__popcll(bm);
         }
     };
@@ -299,7 +266,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
 #pragma unroll
                 for (int j = 0; j < kCells; ++j)
                 {
-                    const W6d w = d_window_guarded(a.text, a.text_len, seg + (u64)j * kCellBytes + (u64)lane * 16u);
+                    const W6 w = load_window_guarded(a.text, a.text_len, seg + (u64)j * kCellBytes + (u64)lane * 16u);
                     vv[j] = make_uint4(w.v[0], w.v[1], w.v[2], w.v[3]);
                     nn[j] = make_uint2(w.v[4], w.v[5]);
                 }
@@ -394,7 +361,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
                         if (edge || (lane == 0u && k == 0u))
                             bad = !word_ok(p);
                         else
-                            bad = (p != a.ww_exempt_left && d_wordc(pick(k + 3u))) || d_wordc(pick(k + a.m + 4u));
+                            bad = (p != a.ww_exempt_left && is_wordc(pick(k + 3u))) || is_wordc(pick(k + a.m + 4u));
                         if (bad)
                             m16 &= ~(1u << k);
                     }
@@ -406,7 +373,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
                 u32 idx = wcnt, tot = 0;
                 auto plane = [&](int b) {
                     const u64 bm = __ballot((cnt >> b) & 1u);
-                    idx += d_mbcnt(bm) << b;
+                    idx += mbcnt64(bm) << b;
                     tot += (u32)__popcll(bm) << b;
                 };
                 plane(0);
@@ -453,7 +420,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
                     }
                     else
                     {
-                        const W6d w = d_window_guarded(a.text, a.text_len, seg + kSegBytes);
+                        const W6 w = load_window_guarded(a.text, a.text_len, seg + kSegBytes);
                         n0 = __builtin_amdgcn_readfirstlane(w.v[0]);
                         n1 = __builtin_amdgcn_readfirstlane(w.v[1]);
                     }
@@ -481,7 +448,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
 // kernel (kg_literal.hip, more waves per SIMD) is the faster one from ~4 cells in 10 on (measured: kg_scan.hip lit_dma_look).  One wave per cell, 16 B per lane.
 __global__ __launch_bounds__(256) void dma_byte_look(const uint8_t *text, u64 lo, u32 n_cells, u32 b4, u32 fold, unsigned long long *out)
 {
-    const u32 lane = d_lane();
+    const u32 lane = lane_id();
     const u32 wave = blockIdx.x * 4u + (threadIdx.x >> 6), n_waves = gridDim.x * 4u;
     u32 cnt = 0;
     for (u32 c = wave; c < n_cells; c += n_waves)

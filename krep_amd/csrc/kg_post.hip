@@ -15,12 +15,10 @@
 #include <cstdlib>
 #include <algorithm>
 #include "kg_common.h"
+#include "kg_device.h"
 #include "kg_internal.h"
 
 namespace kg {
-
-using u32 = uint32_t;
-using u64 = unsigned long long;
 
 constexpr int kPostBlock = 256;          // threads
 constexpr int kPostUnitsPerThread = 4;
@@ -34,7 +32,6 @@ __device__ __forceinline__ Bits compose(Bits a, Bits b)
 {
     return Bits{a.nl || b.nl, a.nl ? a.head : (a.head || b.head), b.nl ? b.tail : (a.tail || b.tail)};
 }
-__device__ __forceinline__ u32 plane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // compose the 64 lane summaries of a wave in lane order (lane 0 = earliest)
 __device__ __forceinline__ Bits wave_compose(Bits mine)
@@ -71,7 +68,7 @@ __global__ __launch_bounds__(kPostBlock) void post_reduce(const u64 *__restrict_
 {
     __shared__ u64 s_sum[4];
     __shared__ u64 s_bits[4];
-    const u32 lane = plane_id(), wave = threadIdx.x >> 6;
+    const u32 lane = lane_id(), wave = threadIdx.x >> 6;
     const u64 u0 = (u64)blockIdx.x * kPostUnitsPerBlock + (u64)threadIdx.x * kPostUnitsPerThread;
     u64 sum = 0;
     Bits b{false, false, false};
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(kPostBlock) void post_reduce(const u64 *__restrict_
 // one wave scans the block records 64 at a time (n_blocks = units/1024: 1024 for a 32 GiB shard)
 __global__ __launch_bounds__(64) void post_carry(u64 n_blocks, u64 *__restrict__ blk_sum, u64 *__restrict__ blk_bits, Counters *ctr)
 {
-    const u32 lane = plane_id();
+    const u32 lane = lane_id();
     u64 run = 0;                 // hits in all earlier blocks (uniform)
     Bits c{false, false, false}; // composition of all earlier blocks (uniform)
     for (u64 b0 = 0; b0 < n_blocks; b0 += 64)
@@ -146,7 +143,7 @@ __global__ __launch_bounds__(kPostBlock) void post_offsets(const u64 *__restrict
     __shared__ u32 s_wsum[4];
     __shared__ u64 s_wbits[4];
     __shared__ u64 s_lines[4];
-    const u32 lane = plane_id(), wave = threadIdx.x >> 6;
+    const u32 lane = lane_id(), wave = threadIdx.x >> 6;
     const u64 u0 = (u64)blockIdx.x * kPostUnitsPerBlock + (u64)threadIdx.x * kPostUnitsPerThread;
     u64 w[kPostUnitsPerThread];
     u32 tsum = 0;
@@ -228,7 +225,7 @@ __global__ __launch_bounds__(kPostBlock) void post_gather(const u64 *__restrict_
                                                           u64 *__restrict__ positions, u64 pos_cap)
 {
     const unsigned short *stage16 = reinterpret_cast<const unsigned short *>(stage);
-    const u32 lane = plane_id();
+    const u32 lane = lane_id();
     const u64 n_waves = (u64)gridDim.x * (kPostBlock / 64);
     const u64 wid = (u64)blockIdx.x * (kPostBlock / 64) + (threadIdx.x >> 6);
     const u32 *stage32 = reinterpret_cast<const u32 *>(stage);

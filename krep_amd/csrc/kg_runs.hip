@@ -16,26 +16,20 @@
 #include <cstdlib>
 #include <vector>
 #include "kg_common.h"
+#include "kg_device.h"
 #include "kg_internal.h"
 
 namespace kg {
 
-using u32 = uint32_t;
-using u64 = unsigned long long;
 std::atomic<uint64_t> g_runs_launches{0}; // (test hook: krep_gpu_debug_runs_launches)
 
 namespace {
 constexpr u64 kRunUnit = (u64)kRoundsBig * kSegBytes; // 32 KiB per wave and step
 constexpr u64 kLookBack = 4u * 1024u; // (a run this long in front of a unit: the two-level form)
 
-__device__ __forceinline__ u32 r_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ u32 r_eq16(const uint4 &v, u32 splat, u32 fold)
 { // bit k: byte k of the lane's 16 equals b ((x | fold) == splat: fold = 0x20 per byte for a letter under -i)
-    auto eq = [&](u32 x) -> u32 {
-        const u32 y = (x | fold) ^ splat;
-        const u32 t = ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu);
-        return (((t >> 7) * 0x00204081u) >> 21) & 0xfu;
-    };
+    auto eq = [&](u32 x) -> u32 { return movemask4(eq_bytes(x | fold, splat)); };
     return eq(v.x) | (eq(v.y) << 4) | (eq(v.z) << 8) | (eq(v.w) << 12);
 }
 } // namespace
@@ -45,7 +39,7 @@ __device__ __forceinline__ u32 r_eq16(const uint4 &v, u32 splat, u32 fold)
 __global__ __launch_bounds__(256) void run_count_kernel(const uint8_t *__restrict__ text, u64 text_len, u64 lo, u64 hi, u32 m, u32 splat, u32 fold,
                                                         u64 n_units, unsigned long long *out, const u32 *__restrict__ carries)
 {
-    const u32 lane = r_lane();
+    const u32 lane = lane_id();
     const u64 anchor = lo & ~(u64)15;
     const u64 end_lo = lo + m - 1, end_hi = (hi + m - 1 < text_len) ? hi + m - 1 : text_len; // ENDs of the owned matches
     u64 total = 0, last_end = 0; // (per LANE: summed / maximised over the wave once, when the kernel ends)
@@ -237,7 +231,7 @@ __global__ __launch_bounds__(256) void run_count_kernel(const uint8_t *__restric
 __global__ __launch_bounds__(256) void run_summary_kernel(const uint8_t *__restrict__ text, u64 text_len, u64 lo, u32 splat, u32 fold, u64 n_units,
                                                           uint2 *__restrict__ summ)
 {
-    const u32 lane = r_lane();
+    const u32 lane = lane_id();
     const u64 anchor = lo & ~(u64)15;
     for (u64 unit = (u64)blockIdx.x * kWavesPerBlk + (threadIdx.x >> 6); unit < n_units; unit += (u64)gridDim.x * kWavesPerBlk)
     {

@@ -43,13 +43,11 @@
 #include <atomic>
 #include <cstdlib>
 #include "kg_common.h"
+#include "kg_device.h"
 #include "kg_internal.h"
 #include "kg_tickets.h"
 
 namespace kg {
-
-using u32 = uint32_t;
-using u64 = unsigned long long;
 
 // Ticket size (A/B builds: python -m krep_amd.build --variant x -DKG_S1_UPT=2).  ONE ticket counter: the drawn tickets are
 // always a prefix of the ticket space, which is what the progress argument above needs.  Measured in one process (32 GiB,
@@ -68,21 +66,6 @@ constexpr u32 kRingDense = 8192u;             // ... of the dense shapes (16 KiB
 constexpr u32 kRingDensest = 16384u;          // ... of the densest one (32 KiB per wave: one workgroup per CU)
 constexpr u64 kReady = kTkReady;              // (the resolver itself: kg_tickets.h, shared with kg_ac_tiny.hip)
 constexpr u64 kUnitBytes1 = (u64)kRoundsBig * kSegBytes;
-
-__device__ __forceinline__ u32 s_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ u32 s_mbcnt(u64 m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
-__device__ __forceinline__ u64 s_rfl64(u64 v)
-{
-    const u32 lo = __builtin_amdgcn_readfirstlane((u32)v), hi = __builtin_amdgcn_readfirstlane((u32)(v >> 32));
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u32 s_eq_bytes(u32 x, u32 c4)
-{
-    const u32 y = x ^ c4;
-    const u32 t = (y & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    return ~(t | y | 0x7f7f7f7fu);
-}
-__device__ __forceinline__ u32 s_movemask4(u32 t) { return (((t >> 7) * 0x00204081u) >> 21) & 0xfu; }
 
 // the (at most one) round that touches the end of the buffer: byte-wise, bounds-checked, out of line
 __device__ __noinline__ uint4 s_load16_guarded(const uint8_t *text, u64 text_len, u64 off)
@@ -106,7 +89,6 @@ __device__ __noinline__ uint4 s_load16_guarded(const uint8_t *text, u64 text_len
 // stands; a wave at the barrier holds nothing unpublished.  The resolver's own workgroup cannot use the barrier (its wave 0 never
 // gets there): its other three waves keep drawing one ticket each from the same counter — any mix of draws leaves a prefix — so a
 // device that runs a single workgroup of the grid still makes progress.
-__device__ __forceinline__ bool s_wordc(u32 c) { return (c - '0' < 10u) || ((c | 0x20u) - 'a' < 26u) || c == '_'; }
 
 template <bool CI, u32 kUpt, u32 kRing, int WPE, bool SET, bool MULTI = false, bool BDRAW = false, bool WW = false>
 __global__ __launch_bounds__(kBlock, WPE) void single_fused(const LitArgs a, u64 *__restrict__ agg, u64 *__restrict__ pref,
@@ -121,7 +103,7 @@ __global__ __launch_bounds__(kBlock, WPE) void single_fused(const LitArgs a, u64
         else
             return x >= kRing ? x - kRing : x;
     };
-    const u32 lane = s_lane();
+    const u32 lane = lane_id();
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const u64 n_units = a.num_tiles * kWavesPerBlk;
 
@@ -130,10 +112,10 @@ __global__ __launch_bounds__(kBlock, WPE) void single_fused(const LitArgs a, u64
     bool resolver = false;
     if (wave == 0)
     {
-        u64 r = 1;
+        u64 r = 1; // (written out: wave_fetch_add() starts the other lanes from 0, one different instruction)
         if (lane == 0)
             r = __hip_atomic_fetch_add(&a.ctr->pad[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        resolver = s_rfl64(r) == 0ull;
+        resolver = rfl64(r) == 0ull;
     }
     extern __shared__ __attribute__((aligned(16))) unsigned short s_ring[]; // [kWavesPerBlk][kRing] (dynamic: the densest shape asks for 128 KiB)
     u64 *s_draw = reinterpret_cast<u64 *>(s_ring + (size_t)kWavesPerBlk * kRing); // BDRAW: [0] the workgroup's ticket base, [1] "the resolver's workgroup"
@@ -303,12 +285,12 @@ __global__ __launch_bounds__(kBlock, WPE) void single_fused(const LitArgs a, u64
                         const u32 k = __builtin_ctz(rest);
                         rest &= rest - 1u;
                         const u64 p = lb + k;
-                        bool left = s_wordc(pick(k + 3u));
+                        bool left = is_wordc(pick(k + 3u));
                         if (lane == 0u && k == 0u)
-                            left = p > 0 && s_wordc(a.text[p - 1]);
+                            left = p > 0 && is_wordc(a.text[p - 1]);
                         if (p == a.ww_exempt_left)
                             left = false;
-                        if (left || s_wordc(pick(k + a.m + 4u)))
+                        if (left || is_wordc(pick(k + a.m + 4u)))
                             m16 &= ~(1u << k);
                     }
                 }
@@ -318,18 +300,18 @@ __global__ __launch_bounds__(kBlock, WPE) void single_fused(const LitArgs a, u64
 #pragma unroll
                 for (int w = 0; w < 4; ++w)
                 {
-                    u32 f = s_eq_bytes(CI ? (D[w] | a.set_l[0]) : D[w], a.set_p[0]);
-                    if (a.set_n > 1u) f |= s_eq_bytes(CI ? (D[w] | a.set_l[1]) : D[w], a.set_p[1]);
-                    if (a.set_n > 2u) f |= s_eq_bytes(CI ? (D[w] | a.set_l[2]) : D[w], a.set_p[2]);
-                    if (a.set_n > 3u) f |= s_eq_bytes(CI ? (D[w] | a.set_l[3]) : D[w], a.set_p[3]);
-                    m16 |= s_movemask4(f) << (4 * w);
+                    u32 f = eq_bytes(CI ? (D[w] | a.set_l[0]) : D[w], a.set_p[0]);
+                    if (a.set_n > 1u) f |= eq_bytes(CI ? (D[w] | a.set_l[1]) : D[w], a.set_p[1]);
+                    if (a.set_n > 2u) f |= eq_bytes(CI ? (D[w] | a.set_l[2]) : D[w], a.set_p[2]);
+                    if (a.set_n > 3u) f |= eq_bytes(CI ? (D[w] | a.set_l[3]) : D[w], a.set_p[3]);
+                    m16 |= movemask4(f) << (4 * w);
                 }
             }
             else
             {
 #pragma unroll
                 for (int w = 0; w < 4; ++w)
-                    m16 |= s_movemask4(s_eq_bytes(CI ? (D[w] | a.l0) : D[w], a.p0)) << (4 * w);
+                    m16 |= movemask4(eq_bytes(CI ? (D[w] | a.l0) : D[w], a.p0)) << (4 * w);
             }
             if (!interior)
             {
@@ -345,7 +327,7 @@ __global__ __launch_bounds__(kBlock, WPE) void single_fused(const LitArgs a, u64
                 u32 idx = cnt, tot = 0;
                 auto plane = [&](int b) {
                     const u64 bm = __ballot((c >> b) & 1u);
-                    idx += s_mbcnt(bm) << b;
+                    idx += mbcnt64(bm) << b;
                     tot += (u32)__popcll(bm) << b;
                 };
                 plane(0);
@@ -388,9 +370,7 @@ __global__ __launch_bounds__(kBlock, WPE) void single_fused(const LitArgs a, u64
         }
         else
         {
-            if (lane == 0)
-                tk = __hip_atomic_fetch_add(&a.ctr->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tk = s_rfl64(tk);
+            tk = wave_fetch_add(&a.ctr->ticket, 1ull, lane);
         }
         return tk < n_tickets ? tk : ~0ull;
     };

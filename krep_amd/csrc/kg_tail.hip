@@ -7,13 +7,11 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "kg_common.h"
+#include "kg_device.h"
 #include "kg_internal.h"
 #include "kg_replay.h"
 
 namespace kg {
-
-using u32 = uint32_t;
-using u64 = unsigned long long;
 
 // out[0] = 1 + index of the last unit u < limit whose info word reports a hit (0 = none)
 __global__ __launch_bounds__(256) void tail_last_hit_unit(const u64 *__restrict__ info, u64 limit, u64 *out)
@@ -39,11 +37,7 @@ constexpr u32 kNlChunk = 64 * 1024; // bytes one workgroup inspects per step
 // each read their whole 64 KiB before the first result was visible (0.24 ms per sweep at 32 GiB for a newline 80 bytes away).
 __device__ __forceinline__ u32 nl_mask16(const uint4 v) // bit k: byte k of the 16 is '\n'
 {
-    auto m4 = [](u32 x) -> u32 {
-        const u32 y = x ^ 0x0a0a0a0au;
-        const u32 z = ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu); // 0x80 in every byte equal to '\n'
-        return (((z >> 7) * 0x00204081u) >> 21) & 0xfu;
-    };
+    auto m4 = [](u32 x) -> u32 { return movemask4(eq_bytes(x, 0x0a0a0a0au)); };
     return m4(v.x) | (m4(v.y) << 4) | (m4(v.z) << 8) | (m4(v.w) << 12);
 }
 
@@ -151,7 +145,7 @@ __device__ __forceinline__ bool tail_gap_has_newline(const uint8_t *__restrict__
     // out of the test (reading them is safe: they share an aligned 16-byte granule with a byte of the gap)
     // 0x80 in every '\n' byte, exactly (the borrow-based (y - 0x01..) & ~y & 0x80.. test is exact only for "any zero byte": a real
     // '\n' below a 0x0b byte flags that one too, and the window mask behind this test can cut the real one away — ADVICE r04)
-    auto z = [](u32 x) -> u32 { const u32 y = x ^ 0x0a0a0a0au; return ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu); };
+    auto z = [](u32 x) -> u32 { return eq_bytes(x, 0x0a0a0a0au); };
     const size_t mis = ((size_t)(t + lo)) & 15u;
     const uint8_t *p = t + lo - mis; // aligned
     const u64 total = hi - lo + mis; // bytes from p to hi

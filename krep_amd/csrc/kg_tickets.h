@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kg_common.h"
+#include "kg_device.h"
 
 namespace kg {
 
@@ -23,8 +24,6 @@ constexpr uint32_t kTkResolveChunk = 8;      // tickets per resolver lane and pa
 __device__ __forceinline__ void tk_resolve(unsigned long long *__restrict__ agg, unsigned long long *__restrict__ pref,
                                            const unsigned long long n_tickets, Counters *ctr, const uint32_t lane)
 {
-    typedef unsigned long long u64;
-    typedef uint32_t u32;
     // Window of 64 x kTkResolveChunk tickets from `base`; every pass publishes the prefixes of the leading run of ready
     // tickets and moves the window behind it.  In the steady state the scanners are far ahead and a pass takes the whole
     // window; what matters is that the prefix of ticket p never waits for a ticket BEHIND p.
@@ -101,7 +100,6 @@ __device__ __forceinline__ void tk_resolve(unsigned long long *__restrict__ agg,
 __device__ __forceinline__ unsigned long long tk_wait_prefix(const unsigned long long *__restrict__ pref, const unsigned long long t,
                                                               Counters *ctr, const uint32_t lane)
 {
-    typedef unsigned long long u64;
     u64 p = 0;
     if (lane == 0)
     {
@@ -119,8 +117,7 @@ __device__ __forceinline__ unsigned long long tk_wait_prefix(const unsigned long
             __builtin_amdgcn_s_sleep(4);
         }
     }
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-    return (((u64)hi << 32) | lo) & ~kTkReady;
+    return rfl64(p) & ~kTkReady;
 }
 
 } // namespace kg
