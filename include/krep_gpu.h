@@ -471,6 +471,41 @@ int krep_gpu_line_numbers_ex(const void *d_text, size_t text_len, size_t global_
                              uint64_t n, uint64_t *d_lines, void *stream);
 void krep_gpu_set_result_order(int by_start);
 
+/* ---- the matching lines of a text in HBM: the reference's default output (print_matching_items(), full-line mode without colour,
+ * krep.c:797-1071) ----
+ * Input: the whole text in one buffer and its n records in (start, end) order, relative to d_text[0] (krep_gpu_order_by_start()
+ * on a multi-pattern list; a single literal's list is in that order already).  A record belongs to the line of its START:
+ * line_start = one past the last '\n' in [0, start), line_end = the first '\n' at or after it, else text_len.  Each distinct line
+ * once, ascending, at most max_lines of them (SIZE_MAX: all, 0: none).  Only the first 2048 records of a line take part in its
+ * bytes (MAX_MATCHES_PER_LINE; the reference warns on stderr: capped_lines).  A line's bytes follow the reference's cursor, which
+ * starts at line_start: per record text[cursor, start) if start > cursor, then the match clamped to line_end, and the cursor
+ * moves to the clamped end, also backwards — overlapping or nested records repeat bytes ("xx Sherlock yy" with the records of
+ * Sherlock, er and lock prints "xx Sherlockerlock yy"); then text[cursor, line_end) and '\n'.  A record whose clamped match is
+ * empty (end == start, or a start ON a '\n', where the reference CLI does not terminate) adds nothing of its own.
+ * A list that is not ascending in start, or holds a record with start >= text_len or end < start, is refused (2) before any
+ * byte of the text is read through it.  Colour escapes and shard windows (a line may cross a shard) are the host's business.
+ * Both calls return 0, or 2 with krep_gpu_last_error() set, and synchronise `stream` before they return.  A NULL output pointer
+ * or a capacity of 0 is a size query.  A capacity that is too small sets `overflow` and returns 0: the sizes are valid, the
+ * output buffers hold nothing usable. */
+typedef struct krep_gpu_lines_out
+{
+    uint64_t lines;        /* distinct lines emitted (after max_lines)                                   */
+    uint64_t lines_total;  /* distinct lines that hold a record's start                                  */
+    uint64_t out_bytes;    /* bytes krep_gpu_format_lines wrote, or needs (0 from krep_gpu_matching_lines) */
+    uint64_t capped_lines; /* emitted lines with more than 2048 records                                  */
+    int overflow;          /* a capacity was too small                                                   */
+} krep_gpu_lines_out_t;
+/* d_lines[l] = {line_start, line_end} of the l-th emitted line; d_first_record[l] = index of its first record, and
+ * d_first_record[lines] = index one past the records of the last emitted line (ALL its records, not only the first 2048): it
+ * holds line_capacity + 1 entries. */
+int krep_gpu_matching_lines(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
+                            uint64_t max_lines, match_position_t *d_lines, uint64_t *d_first_record, uint64_t line_capacity,
+                            krep_gpu_lines_out_t *out, void *stream);
+/* the bytes themselves into d_out (device memory, any alignment); prefix = "FILE:" in front of every line, or empty (a host string) */
+int krep_gpu_format_lines(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
+                          uint64_t max_lines, const char *prefix, size_t prefix_len, void *d_out, size_t out_capacity,
+                          krep_gpu_lines_out_t *out, void *stream);
+
 int krep_gpu_device_count(void);
 const char *krep_gpu_last_error(void); /* "" when the last call on this thread succeeded */
 void krep_gpu_clear_error(void);

@@ -55,6 +55,12 @@ class ScanOut(C.Structure):
                 ("has_newline", C.c_uint8), ("overflow", C.c_uint8), ("kernel_ms", C.c_float)]
 
 
+class LinesOut(C.Structure):
+    """krep_gpu_lines_out_t: what krep_gpu_matching_lines / krep_gpu_format_lines report"""
+    _fields_ = [("lines", C.c_uint64), ("lines_total", C.c_uint64), ("out_bytes", C.c_uint64), ("capped_lines", C.c_uint64),
+                ("overflow", C.c_int)]
+
+
 class Config(C.Structure):
     """krep_gpu_config_t: the reference's build level and file-static option globals, explicit."""
     _fields_ = [("reference_simd", C.c_int), ("only_matching", C.c_int), ("force_no_simd", C.c_int),

@@ -119,8 +119,12 @@ __global__ void fmt_line_numbers(const uint8_t *__restrict__ text, u64 text_len,
     lines[i] = ln;
 }
 
-// ---- exclusive prefix sum over the per-block newline counts (hand-written: three tiny kernels, 64-bit sizes) -----------
-constexpr u32 kScanBlock = 256, kScanPer = 8, kScanElems = kScanBlock * kScanPer; // 2048 counts per workgroup
+// ---- exclusive prefix scan of 64-bit words (hand-written: three tiny kernels, 64-bit sizes) — the sum (the per-block newline
+// counts, and the head flags and byte counts of kg_lines.hip) or, with MAX, the running maximum (kg_lines.hip: the last newline
+// in front of a block, the first record of a line) -------------------------------------------------------------------------
+constexpr u32 kScanBlock = 256, kScanPer = 8, kScanElems = kScanBlock * kScanPer; // 2048 words per workgroup
+template <bool MAX> __device__ __forceinline__ u64 scan_op(u64 a, u64 b) { return MAX ? (a > b ? a : b) : a + b; }
+template <bool MAX>
 __global__ __launch_bounds__(kScanBlock) void fmt_scan_local(const u64 *__restrict__ in, u64 n, u64 *__restrict__ out,
                                                             u64 *__restrict__ block_sum)
 {
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(kScanBlock) void fmt_scan_local(const u64 *__restri
     for (u32 k = 0; k < kScanPer; ++k)
     {
         v[k] = i0 + k < n ? in[i0 + k] : 0ull;
-        t += v[k];
+        t = scan_op<MAX>(t, v[k]);
     }
     u64 incl = t;
 #pragma unroll
@@ -140,25 +144,33 @@ __global__ __launch_bounds__(kScanBlock) void fmt_scan_local(const u64 *__restri
     {
         const u64 up = __shfl_up(incl, o);
         if (lane >= (u32)o)
-            incl += up;
+            incl = scan_op<MAX>(incl, up);
     }
     if (lane == 63)
         s_w[wave] = incl;
     __syncthreads();
-    u64 e = incl - t;
+    u64 e;
+    if (MAX)
+    {
+        e = __shfl_up(incl, 1); // the lanes in front of this one (the maximum cannot be taken back out of `incl`)
+        if (lane == 0)
+            e = 0;
+    }
+    else
+        e = incl - t;
     for (u32 w = 0; w < wave; ++w)
-        e += s_w[w];
+        e = scan_op<MAX>(e, s_w[w]);
 #pragma unroll
     for (u32 k = 0; k < kScanPer; ++k)
     {
         if (i0 + k < n)
             out[i0 + k] = e;
-        e += v[k];
+        e = scan_op<MAX>(e, v[k]);
     }
     if (threadIdx.x == kScanBlock - 1)
         block_sum[blockIdx.x] = e;
 }
-__global__ __launch_bounds__(64) void fmt_scan_sums(u64 *__restrict__ block_sum, u64 nb)
+template <bool MAX> __global__ __launch_bounds__(64) void fmt_scan_sums(u64 *__restrict__ block_sum, u64 nb)
 {
     const u32 lane = threadIdx.x;
     u64 run = 0;
@@ -171,13 +183,23 @@ __global__ __launch_bounds__(64) void fmt_scan_sums(u64 *__restrict__ block_sum,
         {
             const u64 up = __shfl_up(incl, o);
             if (lane >= (u32)o)
-                incl += up;
+                incl = scan_op<MAX>(incl, up);
         }
+        u64 excl;
+        if (MAX)
+        {
+            excl = __shfl_up(incl, 1);
+            if (lane == 0)
+                excl = 0;
+        }
+        else
+            excl = incl - v;
         if (b0 + lane < nb)
-            block_sum[b0 + lane] = run + incl - v;
-        run += __shfl(incl, 63);
+            block_sum[b0 + lane] = scan_op<MAX>(run, excl);
+        run = scan_op<MAX>(run, __shfl(incl, 63));
     }
 }
+template <bool MAX>
 __global__ __launch_bounds__(kScanBlock) void fmt_scan_add(u64 *__restrict__ out, u64 n, const u64 *__restrict__ block_off)
 {
     const u64 add = block_off[blockIdx.x];
@@ -185,18 +207,36 @@ __global__ __launch_bounds__(kScanBlock) void fmt_scan_add(u64 *__restrict__ out
 #pragma unroll
     for (u32 k = 0; k < kScanPer; ++k)
         if (i0 + k < n)
-            out[i0 + k] += add;
+            out[i0 + k] = scan_op<MAX>(out[i0 + k], add);
+}
+uint64_t scan_sums_words(uint64_t n) { return (n + kScanElems - 1) / kScanElems; }
+template <bool MAX> static void scan_launch(const u64 *in, u64 n, u64 *out, u64 *sums, hipStream_t st)
+{
+    const u64 nsb = scan_sums_words(n);
+    hipLaunchKernelGGL(fmt_scan_local<MAX>, dim3((u32)nsb), dim3(kScanBlock), 0, st, in, n, out, sums);
+    hipLaunchKernelGGL(fmt_scan_sums<MAX>, dim3(1), dim3(64), 0, st, sums, nsb);
+    hipLaunchKernelGGL(fmt_scan_add<MAX>, dim3((u32)nsb), dim3(kScanBlock), 0, st, out, n, (const u64 *)sums);
+}
+void scan_exclusive(const u64 *in, uint64_t n, u64 *out, u64 *sums, bool take_max, hipStream_t st)
+{
+    if (!n)
+        return;
+    if (take_max)
+        scan_launch<true>(in, n, out, sums, st);
+    else
+        scan_launch<false>(in, n, out, sums, st);
 }
 
 // ---- scratch: one grow-only buffer per device, reused across calls (ADVICE / VERDICT r02: no hipMalloc per call) ------
+std::mutex g_fmt_mu; // held for the whole call: the entry points synchronise before they return
 namespace {
 struct FmtScratch
 {
     void *p = nullptr;
     size_t cap = 0;
 };
-std::mutex g_fmt_mu; // held for the whole call: the entry points synchronise before they return
 FmtScratch g_fmt[64];
+} // namespace
 int fmt_reserve(size_t bytes, void **out)
 {
     int dev = 0;
@@ -219,7 +259,6 @@ int fmt_reserve(size_t bytes, void **out)
     *out = s.p;
     return 0;
 }
-} // namespace
 void format_release()
 {
     std::lock_guard<std::mutex> lk(g_fmt_mu);
@@ -312,9 +351,7 @@ extern "C" int krep_gpu_line_numbers_ex(const void *d_text, size_t text_len, siz
         const u32 grid = (u32)std::min<u64>((nblocks + 3) / 4, 256u * 32u);
         hipLaunchKernelGGL(fmt_count_newlines, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
                            (u64)(nblocks - 1), cnt);
-        hipLaunchKernelGGL(fmt_scan_local, dim3((u32)nsb), dim3(kScanBlock), 0, st, (const u64 *)cnt, (u64)nblocks, pre, sums);
-        hipLaunchKernelGGL(fmt_scan_sums, dim3(1), dim3(64), 0, st, sums, (u64)nsb);
-        hipLaunchKernelGGL(fmt_scan_add, dim3((u32)nsb), dim3(kScanBlock), 0, st, pre, (u64)nblocks, (const u64 *)sums);
+        scan_exclusive(cnt, nblocks, pre, sums, false, st);
         hipLaunchKernelGGL(fmt_line_numbers, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
                            (u64)global_base, (const u64 *)d_positions, (u64)n, (const u64 *)pre, (u64 *)d_lines);
         FCHK(hipGetLastError());

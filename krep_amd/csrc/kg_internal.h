@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cstring>
 #include <initializer_list>
+#include <mutex>
 #include <vector>
 
 #include "../../include/krep_gpu.h"
@@ -223,8 +224,14 @@ inline bool by_start_end(const match_position_t &a, const match_position_t &b) /
 }
 bool have_error();
 
-// kg_format.hip
+// kg_format.hip — what the formatter-side entry points share (kg_lines.hip)
 void format_release(); // frees the formatter scratch of every device
+extern std::mutex g_fmt_mu;                 // held for a whole formatter call: its scratch is one buffer per device
+int fmt_reserve(size_t bytes, void **out);  // that buffer, grown to at least `bytes` (g_fmt_mu held); 2: failed
+uint64_t scan_sums_words(uint64_t n);       // words of scratch (`sums`) a scan of n words needs
+// exclusive prefix scan of in[0, n) into out (a buffer of its own) on `st`: the sum, or with take_max the running maximum (0 in front)
+void scan_exclusive(const unsigned long long *in, uint64_t n, unsigned long long *out, unsigned long long *sums, bool take_max,
+                    hipStream_t st);
 
 // kg_comm.hip — the RCCL all-reduce of the per-shard counters (one process driving several devices)
 int allreduce_across_devices(const std::vector<int> &devs, std::vector<std::vector<unsigned long long>> &vecs);

@@ -1,0 +1,525 @@
+// kg_lines.hip — the reference's DEFAULT output on a text that is resident in HBM: every line that holds the start of a match,
+// once, as print_matching_items() writes it in full-line mode without colour (krep.c:797-1071).
+//
+// Contract (restated from krep.c:838-1061; the record list is in (start, end) order, as search_file() leaves it):
+//   * a record belongs to the line of its START: line_start = one past the last '\n' in [0, start) (find_line_start,
+//     krep.c:363-398), line_end = the first '\n' at or after it, else text_len (find_line_end, :401-415);
+//   * every distinct line once, ascending, at most max_lines of them; only the first 2048 records of a line take part
+//     (MAX_MATCHES_PER_LINE, :496, :893-913);
+//   * a line's bytes follow a cursor that starts at line_start: per record the text between the cursor and the record's start (if
+//     the start lies behind the cursor), then the match clamped to line_end, and the cursor moves to the clamped end — also
+//     BACKWARDS, so overlapping records repeat bytes; a record whose clamped match is empty is passed over (:973-974); behind the
+//     last record the text from the cursor to line_end, then '\n' (:963-1018).
+// In front of a record's match lies either nothing new (its start is behind the cursor) or the text from the cursor on, and
+// behind the last record's match the rest of the line: what a record adds is ONE range of the text, [min(start, cursor),
+// clamped end or line_end), plus the prefix in front of the line's first record and the '\n' behind its last.  So the sizes are a
+// prefix sum and the copy is a segmented gather.  (A record that starts ON a '\n' has an empty clamped match: it belongs to the line
+// that newline ends and adds nothing of its own.  The reference CLI does not terminate on such a list without -m 1.)
+//
+// Steps: (1) one streaming pass over the text leaves per 4 KiB block its first and last newline; a running maximum / minimum over
+// the blocks turns them into "last newline in front of this block" / "first newline behind it"; (2) per record both line bounds,
+// searched in 16-byte steps inside the record's own block only, else taken from the table — no thread walks more than one block per
+// direction, whatever the text; the same kernel refuses a list that is not ascending or points outside the text; (3) line heads,
+// line index and first record of the line (one sum, one running maximum); (4) per record its range and byte count, summed;
+// (5) the gather, dealt by OUTPUT bytes: a lane owns 16 aligned bytes of the output, a wave 1 KiB, the first record of a tile comes
+// from a binary search in the summed offsets.  A call reads the text once in (1), then only around the records and what it copies.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+
+#include "../../include/krep_gpu.h"
+#include "kg_device.h"
+#include "kg_internal.h"
+
+namespace kg {
+
+constexpr u32 kLnBlock = 4096;           // the table keeps the first and the last newline per 4 KiB of text
+constexpr u64 kLnCap = 2048;             // MAX_MATCHES_PER_LINE (krep.c:496)
+constexpr u64 kLnNone = ~0ull;
+constexpr u64 kLnFirst = 1ull << 63, kLnLast = 1ull << 62, kLnSrc = kLnLast - 1; // a record's range word: flags | source offset
+
+// bit q set: byte q of the 16 is a '\n'
+__device__ __forceinline__ u32 nl_mask16(const uint4 v)
+{
+    return movemask4(eq_bytes(v.x, 0x0a0a0a0au)) | (movemask4(eq_bytes(v.y, 0x0a0a0a0au)) << 4) |
+           (movemask4(eq_bytes(v.z, 0x0a0a0a0au)) << 8) | (movemask4(eq_bytes(v.w, 0x0a0a0a0au)) << 12);
+}
+
+// (1) one wave per block.  last1[b]: one past the block's last newline (0: none); first_rev[nb - 1 - b]: the complement of its
+// first newline's offset (0: none) — reversed and complemented, the running MAXIMUM in front of an entry is the first newline
+// BEHIND the block
+__global__ __launch_bounds__(256) void ln_block_table(const uint8_t *__restrict__ text, u64 text_len, u64 nb, u64 *__restrict__ last1,
+                                                      u64 *__restrict__ first_rev)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u64 wid = (u64)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (u64)gridDim.x * (blockDim.x >> 6);
+    for (u64 b = wid; b < nb; b += nw)
+    {
+        const u64 base = b * kLnBlock;
+        u32 lo = ~0u, hi = 0; // offset of the first newline in the block / one past the last
+        for (u32 it = 0; it < kLnBlock / 1024; ++it)
+        {
+            const u32 rel = it * 1024 + lane * 16;
+            const u64 off = base + rel;
+            u32 m = 0;
+            if (off + 16 <= text_len)
+                m = nl_mask16(load_unaligned<uint4>(text + off));
+            else
+                for (u32 q = 0; q < 16; ++q)
+                    if (off + q < text_len && text[off + q] == '\n')
+                        m |= 1u << q;
+            if (m)
+            {
+                lo = min(lo, rel + (u32)__ffs(m) - 1u);
+                hi = rel + 32u - (u32)__clz(m);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1)
+        {
+            lo = min(lo, (u32)__shfl_xor(lo, o));
+            hi = max(hi, (u32)__shfl_xor(hi, o));
+        }
+        if (lane == 0)
+        {
+            last1[b] = hi ? base + hi : 0ull;
+            first_rev[nb - 1 - b] = lo != ~0u ? ~(base + lo) : 0ull;
+        }
+    }
+}
+
+// (2) line bounds of every record; a record that may not be read (outside the text, end before start, start before its
+// predecessor's) raises the flag and touches no text
+__global__ __launch_bounds__(256) void ln_bounds(const uint8_t *__restrict__ text, u64 text_len, const u64 *__restrict__ rec, u64 n,
+                                                 const u64 *__restrict__ prev1, const u64 *__restrict__ next_rev, u64 nb,
+                                                 u64 *__restrict__ ls, u64 *__restrict__ le, u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint4 r = *reinterpret_cast<const uint4 *>(rec + 2 * i);
+    const u64 s = ((u64)r.y << 32) | r.x, e = ((u64)r.w << 32) | r.z;
+    if (s >= text_len || e < s || (i > 0 && rec[2 * (i - 1)] > s))
+    {
+        ctr[0] = 1; // (every writer stores the same value)
+        ls[i] = 0;
+        le[i] = 0;
+        return;
+    }
+    const u64 b = s / kLnBlock, base = b * kLnBlock, lim = min(base + kLnBlock, text_len);
+    u64 p = s, a = kLnNone;
+    while (p >= base + 16)
+    {
+        const u32 m = nl_mask16(load_unaligned<uint4>(text + p - 16));
+        if (m)
+        {
+            a = p - 16 + (32u - (u32)__clz(m));
+            break;
+        }
+        p -= 16;
+    }
+    if (a == kLnNone)
+    {
+        for (; p > base; --p)
+            if (text[p - 1] == '\n')
+                break;
+        a = p > base ? p : prev1[b]; // (a newline in the block's last byte before `base` is the table's)
+    }
+    u64 q = s, z = kLnNone;
+    while (q + 16 <= lim)
+    {
+        const u32 m = nl_mask16(load_unaligned<uint4>(text + q));
+        if (m)
+        {
+            z = q + (u32)__ffs(m) - 1u;
+            break;
+        }
+        q += 16;
+    }
+    if (z == kLnNone)
+    {
+        for (; q < lim; ++q)
+            if (text[q] == '\n')
+                break;
+        if (q < lim)
+            z = q;
+        else
+        {
+            const u64 nx = next_rev[nb - 1 - b];
+            z = nx ? ~nx : text_len;
+        }
+    }
+    ls[i] = a;
+    le[i] = z;
+}
+
+// (3) head[i]: the record opens a line; mark[i]: its index + 1 there, else 0 (their running maximum is the line's first record)
+__global__ __launch_bounds__(256) void ln_heads(const u64 *__restrict__ ls, u64 n, u64 *__restrict__ head, u64 *__restrict__ mark)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n)
+        return;
+    const bool h = i < n && (i == 0 || ls[i] != ls[i - 1]);
+    head[i] = h ? 1ull : 0ull; // (entry n: 0, so that the scanned entry n is the total)
+    mark[i] = h ? i + 1 : 0ull;
+}
+
+struct LnRecord
+{
+    bool head;
+    u64 line, first; // index of its line, index of that line's first record
+};
+__device__ __forceinline__ LnRecord ln_record(const u64 *ls, const u64 *heads_before, const u64 *mark_before, u64 i)
+{
+    LnRecord r;
+    r.head = i == 0 || ls[i] != ls[i - 1];
+    r.line = heads_before[i] + (r.head ? 1u : 0u) - 1u;
+    r.first = r.head ? i : mark_before[i] - 1;
+    return r;
+}
+
+// krep_gpu_matching_lines: the spans and first records of the first `emit` lines (write != 0), and the emitted lines that hold more
+// than 2048 records
+__global__ __launch_bounds__(256) void ln_spans(const u64 *__restrict__ ls, const u64 *__restrict__ le, const u64 *__restrict__ heads_before,
+                                                const u64 *__restrict__ mark_before, u64 n, u64 emit, int write, u64 *__restrict__ lines,
+                                                u64 *__restrict__ first_record, u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const LnRecord r = ln_record(ls, heads_before, mark_before, i);
+    if (r.line < emit && i - r.first == kLnCap)
+        (void)__hip_atomic_fetch_add(ctr + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!write)
+        return;
+    if (r.head && r.line <= emit)
+    {
+        first_record[r.line] = i;
+        if (r.line < emit)
+        {
+            lines[2 * r.line] = ls[i];
+            lines[2 * r.line + 1] = le[i];
+        }
+    }
+    if (i == n - 1 && heads_before[n] == emit)
+        first_record[emit] = n;
+}
+
+// (4) what record i adds to the output: bytes[i], and range[i] = flags | offset of its range in the text
+__global__ __launch_bounds__(256) void ln_sizes(const u64 *__restrict__ rec, const u64 *__restrict__ ls, const u64 *__restrict__ le,
+                                                const u64 *__restrict__ heads_before, const u64 *__restrict__ mark_before, u64 n,
+                                                u64 max_lines, u64 prefix_len, u64 *__restrict__ bytes, u64 *__restrict__ range,
+                                                u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n)
+        return;
+    if (i == n)
+    {
+        bytes[n] = 0;
+        return;
+    }
+    const LnRecord r = ln_record(ls, heads_before, mark_before, i);
+    const u64 emit = min(heads_before[n], max_lines), rank = i - r.first;
+    if (r.line < emit && rank == kLnCap)
+        (void)__hip_atomic_fetch_add(ctr + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (r.line >= emit || rank >= kLnCap)
+    {
+        bytes[i] = 0;
+        range[i] = 0;
+        return;
+    }
+    const u64 a = ls[i], z = le[i], s = rec[2 * i], cend = min(rec[2 * i + 1], z);
+    const bool solid = s < cend; // its clamped match is not empty
+    // the cursor in front of it: the clamped end of the nearest record before it on the line whose match is not empty (the record
+    // just before it, unless that one starts on the newline or is empty: at most 2047 steps, on such lists only)
+    u64 cur = a;
+    for (u64 j = i; j > r.first; --j)
+    {
+        const u64 sj = rec[2 * (j - 1)], ej = min(rec[2 * (j - 1) + 1], z);
+        if (sj < ej)
+        {
+            cur = ej;
+            break;
+        }
+    }
+    const bool last = rank == kLnCap - 1 || i + 1 == n || ls[i + 1] != a;
+    const u64 src = solid ? min(s, cur) : cur;
+    const u64 end = last ? z : (solid ? cend : cur);
+    bytes[i] = (rank == 0 ? prefix_len : 0ull) + (end - src) + (last ? 1ull : 0ull);
+    range[i] = src | (rank == 0 ? kLnFirst : 0ull) | (last ? kLnLast : 0ull);
+}
+
+// the largest r in [lo, hi] with off[r] <= pos (off[lo] <= pos)
+__device__ __forceinline__ u64 ln_find(const u64 *__restrict__ off, u64 lo, u64 hi, u64 pos)
+{
+    while (lo < hi)
+    {
+        const u64 mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= pos)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// where a lane stands in the output: inside record r, with `pre` bytes of the prefix, `txt` bytes of the text and `nl` newline to go
+struct LnCursor
+{
+    u64 r, src, txt;
+    u32 pre, ppos, nl;
+};
+__device__ __forceinline__ LnCursor ln_enter(const u64 *__restrict__ off, const u64 *__restrict__ range, u32 prefix_len, u64 r, u64 skip)
+{
+    LnCursor c;
+    const u64 w = range[r], total = off[r + 1] - off[r];
+    const u32 pl = (w & kLnFirst) ? prefix_len : 0u, nl = (w & kLnLast) ? 1u : 0u;
+    const u64 tl = total - pl - nl;
+    c.r = r;
+    c.src = w & kLnSrc;
+    c.ppos = 0;
+    c.pre = pl;
+    c.txt = tl;
+    c.nl = nl;
+    if (skip)
+    {
+        const u32 sp = (u32)min((u64)pl, skip);
+        c.ppos = sp;
+        c.pre = pl - sp;
+        skip -= sp;
+        const u64 st = min(tl, skip);
+        c.src += st;
+        c.txt = tl - st;
+        skip -= st;
+        if (skip)
+            c.nl = 0;
+    }
+    return c;
+}
+
+// (5) chunk c is the 16 aligned bytes at (out - misalign) + 16 c, i.e. output offsets [16 c - misalign, + 16)
+__global__ __launch_bounds__(256) void ln_gather(const uint8_t *__restrict__ text, const u64 *__restrict__ off, const u64 *__restrict__ range,
+                                                 u64 n, const uint8_t *__restrict__ prefix, u32 prefix_len, uint8_t *__restrict__ out,
+                                                 u64 total, u32 misalign, u64 nchunks)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u64 wid = (u64)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (u64)gridDim.x * (blockDim.x >> 6);
+    for (u64 c0 = wid * 64; c0 < nchunks; c0 += nw * 64)
+    {
+        // the records of the wave's 1 KiB tile
+        const u64 tile_lo = c0 ? c0 * 16 - misalign : 0ull, tile_hi = min((c0 + 64) * 16 - misalign, total) - 1;
+        const u64 r_lo = ln_find(off, 0, n - 1, tile_lo), r_hi = ln_find(off, r_lo, n - 1, tile_hi);
+        const u64 c = c0 + lane;
+        if (c >= nchunks)
+            continue;
+        const u64 o0 = c ? c * 16 - misalign : 0ull, o1 = min((c + 1) * 16 - misalign, total);
+        const bool whole = o1 - o0 == 16;
+        u64 r = ln_find(off, r_lo, r_hi, o0);
+        LnCursor k = ln_enter(off, range, prefix_len, r, o0 - off[r]);
+        if (whole && k.pre == 0 && k.txt >= 16)
+        {
+            *reinterpret_cast<uint4 *>(out + o0) = load_unaligned<uint4>(text + k.src);
+            continue;
+        }
+        u32 w[4] = {0, 0, 0, 0};
+        const u32 shift = (u32)(o0 + misalign - c * 16); // bytes of the chunk in front of the output (chunk 0 only)
+        u64 pos = o0;
+#pragma unroll
+        for (u32 q = 0; q < 16; ++q)
+        {
+            if (q >= shift && pos < o1)
+            {
+                while (k.pre == 0 && k.txt == 0 && k.nl == 0) // the record is used up: the next one that adds bytes
+                {
+                    r = k.r + 1;
+                    if (off[r + 1] == off[r])
+                        r = ln_find(off, r, n - 1, pos);
+                    k = ln_enter(off, range, prefix_len, r, 0);
+                }
+                u32 byte;
+                if (k.pre)
+                {
+                    byte = prefix[k.ppos++];
+                    --k.pre;
+                }
+                else if (k.txt)
+                {
+                    byte = text[k.src++];
+                    --k.txt;
+                }
+                else
+                {
+                    byte = '\n';
+                    k.nl = 0;
+                }
+                w[q >> 2] |= byte << (8 * (q & 3u));
+                ++pos;
+            }
+        }
+        if (whole)
+            *reinterpret_cast<uint4 *>(out + o0) = make_uint4(w[0], w[1], w[2], w[3]);
+        else
+        {
+#pragma unroll
+            for (u32 q = 0; q < 16; ++q)
+                if (q >= shift && o0 + (q - shift) < o1)
+                    out[o0 + (q - shift)] = (uint8_t)(w[q >> 2] >> (8 * (q & 3u)));
+        }
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+struct LnWork
+{
+    u64 *ctr, *last1, *prev1, *first_rev, *next_rev; // counters {refused, capped lines}; the block table and its scans
+    u64 *ls, *le, *a, *heads_before, *mark_before, *range, *sums;
+    uint8_t *prefix;
+    u64 nb;
+};
+
+int ln_check(const char *who, const void *d_text, const void *d_positions, uint64_t n, krep_gpu_lines_out_t *out)
+{
+    if (!out)
+        return fail("%s: out is NULL", who);
+    *out = krep_gpu_lines_out_t{};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return fail("%s: no HIP device available", who);
+    }
+    if (const char *why = device_unusable(dev))
+        return fail("%s: %s", who, why);
+    if (n && (!d_text || !d_positions))
+        return fail("%s: d_text / d_positions is NULL", who);
+    if (n >> 40)
+        return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
+    return 0;
+}
+
+// steps (1)-(3) on `st`; the scratch is laid out here (g_fmt_mu held by the caller)
+int ln_analyse(const uint8_t *d_text, u64 text_len, const u64 *d_rec, u64 n, size_t prefix_len, LnWork &w, hipStream_t st)
+{
+    if (!text_len)
+        return fail("krep_gpu_matching_lines / krep_gpu_format_lines: records on an empty text");
+    const u64 nb = (text_len + kLnBlock - 1) / kLnBlock, n1 = n + 1;
+    const u64 sums = scan_sums_words(std::max(nb, n1));
+    void *base = nullptr;
+    if (fmt_reserve((8 + 4 * nb + 6 * n1 + sums) * sizeof(u64) + prefix_len + 16, &base))
+        return 2;
+    u64 *p = (u64 *)base;
+    auto take = [&](u64 words) { u64 *q = p; p += words; return q; };
+    w.nb = nb;
+    w.ctr = take(8);
+    w.last1 = take(nb), w.prev1 = take(nb), w.first_rev = take(nb), w.next_rev = take(nb);
+    w.ls = take(n1), w.le = take(n1), w.a = take(n1), w.heads_before = take(n1), w.mark_before = take(n1), w.range = take(n1);
+    w.sums = take(sums);
+    w.prefix = (uint8_t *)p;
+    HIPCHK(hipMemsetAsync(w.ctr, 0, 8 * sizeof(u64), st));
+    const u32 grid_t = (u32)std::min<u64>((nb + 3) / 4, 256u * 32u), grid_n = (u32)((n1 + 255) / 256);
+    hipLaunchKernelGGL(ln_block_table, dim3(grid_t), dim3(256), 0, st, d_text, text_len, nb, w.last1, w.first_rev);
+    scan_exclusive(w.last1, nb, w.prev1, w.sums, true, st);
+    scan_exclusive(w.first_rev, nb, w.next_rev, w.sums, true, st);
+    hipLaunchKernelGGL(ln_bounds, dim3(grid_n), dim3(256), 0, st, d_text, text_len, d_rec, n, (const u64 *)w.prev1,
+                       (const u64 *)w.next_rev, nb, w.ls, w.le, w.ctr);
+    hipLaunchKernelGGL(ln_heads, dim3(grid_n), dim3(256), 0, st, (const u64 *)w.ls, n, w.a, w.range);
+    scan_exclusive(w.a, n1, w.heads_before, w.sums, false, st);
+    scan_exclusive(w.range, n1, w.mark_before, w.sums, true, st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+} // namespace kg
+
+using namespace kg;
+
+extern "C" int krep_gpu_matching_lines(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
+                                       uint64_t max_lines, match_position_t *d_lines, uint64_t *d_first_record, uint64_t line_capacity,
+                                       krep_gpu_lines_out_t *out, void *stream)
+{
+    if (ln_check("krep_gpu_matching_lines", d_text, d_positions, n, out))
+        return 2;
+    if (!n)
+        return 0;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(g_fmt_mu);
+    LnWork w;
+    if (ln_analyse((const uint8_t *)d_text, text_len, (const u64 *)d_positions, n, 0, w, st))
+        return 2;
+    u64 h[2] = {0, 0}, total = 0;
+    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h, w.ctr, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[0])
+        return fail("krep_gpu_matching_lines: the record list is not ascending in start, or a record lies outside the text");
+    const u64 emit = std::min<u64>(total, max_lines);
+    const bool query = !d_lines || !d_first_record || !line_capacity;
+    const bool fits = !query && emit <= line_capacity;
+    hipLaunchKernelGGL(ln_spans, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const u64 *)w.ls, (const u64 *)w.le,
+                       (const u64 *)w.heads_before, (const u64 *)w.mark_before, (u64)n, emit, fits ? 1 : 0, (u64 *)d_lines,
+                       (u64 *)d_first_record, w.ctr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, w.ctr, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    out->lines = emit;
+    out->lines_total = total;
+    out->capped_lines = h[1];
+    out->overflow = !query && !fits;
+    return 0;
+}
+
+extern "C" int krep_gpu_format_lines(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
+                                     uint64_t max_lines, const char *prefix, size_t prefix_len, void *d_out, size_t out_capacity,
+                                     krep_gpu_lines_out_t *out, void *stream)
+{
+    if (ln_check("krep_gpu_format_lines", d_text, d_positions, n, out))
+        return 2;
+    if (prefix_len && !prefix)
+        return fail("krep_gpu_format_lines: prefix is NULL");
+    if (prefix_len >> 20)
+        return fail("krep_gpu_format_lines: a prefix of %zu bytes", prefix_len);
+    if (!n)
+        return 0;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(g_fmt_mu);
+    LnWork w;
+    if (ln_analyse((const uint8_t *)d_text, text_len, (const u64 *)d_positions, n, prefix_len, w, st))
+        return 2;
+    if (prefix_len)
+        HIPCHK(hipMemcpyAsync(w.prefix, prefix, prefix_len, hipMemcpyHostToDevice, st));
+    u64 *off = w.ls; // the line starts are not read again behind ln_sizes: their buffer takes the summed byte counts
+    hipLaunchKernelGGL(ln_sizes, dim3((u32)((n + 1 + 255) / 256)), dim3(256), 0, st, (const u64 *)d_positions, (const u64 *)w.ls,
+                       (const u64 *)w.le, (const u64 *)w.heads_before, (const u64 *)w.mark_before, (u64)n, (u64)max_lines, (u64)prefix_len,
+                       w.a, w.range, w.ctr);
+    scan_exclusive(w.a, n + 1, off, w.sums, false, st);
+    HIPCHK(hipGetLastError());
+    u64 h[2] = {0, 0}, total = 0, bytes = 0;
+    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bytes, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h, w.ctr, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[0])
+        return fail("krep_gpu_format_lines: the record list is not ascending in start, or a record lies outside the text");
+    out->lines = std::min<u64>(total, max_lines);
+    out->lines_total = total;
+    out->out_bytes = bytes;
+    out->capped_lines = h[1];
+    const bool query = !d_out || !out_capacity;
+    if (query || !bytes)
+        return 0;
+    if (bytes > out_capacity)
+    {
+        out->overflow = 1;
+        return 0;
+    }
+    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
+    const u64 nchunks = (bytes + misalign + 15) / 16;
+    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
+    hipLaunchKernelGGL(ln_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)off, (const u64 *)w.range, (u64)n,
+                       (const uint8_t *)w.prefix, (u32)prefix_len, (uint8_t *)d_out, bytes, misalign, nchunks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}

@@ -95,6 +95,13 @@ class Engine:
         L.krep_gpu_order_by_start.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.c_void_p]
         L.krep_gpu_line_numbers.restype = C.c_int
         L.krep_gpu_line_numbers.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        if hasattr(L, "krep_gpu_format_lines"):  # (an older build of the library as an A/B partner lacks them)
+            L.krep_gpu_matching_lines.restype = C.c_int
+            L.krep_gpu_matching_lines.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                  C.c_uint64, C.POINTER(abi.LinesOut), C.c_void_p]
+            L.krep_gpu_format_lines.restype = C.c_int
+            L.krep_gpu_format_lines.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t,
+                                                C.c_void_p, C.c_size_t, C.POINTER(abi.LinesOut), C.c_void_p]
         for n in ("krep_gpu_set_reference_simd", "krep_gpu_set_only_matching", "krep_gpu_set_force_no_simd",
                   "krep_gpu_set_algo_override", "krep_gpu_debug_force_rounds", "krep_gpu_debug_force_stage_cap",
                   "krep_gpu_set_result_order", "krep_gpu_set_device", "krep_gpu_set_num_gpus", "krep_gpu_debug_inject_failure"):
@@ -344,6 +351,29 @@ class Engine:
                                           C.c_void_p(stream)):
             raise KrepGpuError("krep_gpu_line_numbers failed: " + self.last_error())
 
+    # ---- the matching lines themselves (print_matching_items(), full-line mode without colour, krep.c:797-1071) ----
+    def matching_lines(self, d_text: int, text_len: int, d_positions: int, n: int, max_lines: int = abi.SIZE_MAX, d_lines: int = 0,
+                       d_first_record: int = 0, line_capacity: int = 0, stream: int = 0) -> "abi.LinesOut":
+        """krep_gpu_matching_lines(): {line_start, line_end} and first record of every distinct line the records (in (start, end)
+        order) start on.  d_lines = 0 asks for the sizes; a capacity that is too small comes back as .overflow."""
+        out = abi.LinesOut()
+        if self.lib.krep_gpu_matching_lines(C.c_void_p(d_text), text_len, C.c_void_p(d_positions), n, max_lines,
+                                            C.c_void_p(d_lines) if d_lines else None,
+                                            C.c_void_p(d_first_record) if d_first_record else None, line_capacity, C.byref(out),
+                                            C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_matching_lines failed: " + self.last_error())
+        return out
+
+    def format_lines(self, d_text: int, text_len: int, d_positions: int, n: int, max_lines: int = abi.SIZE_MAX, prefix: bytes = b"",
+                     d_out: int = 0, out_capacity: int = 0, stream: int = 0) -> "abi.LinesOut":
+        """krep_gpu_format_lines(): the bytes the reference prints for these records, into d_out.  d_out = 0 asks for .out_bytes."""
+        out = abi.LinesOut()
+        if self.lib.krep_gpu_format_lines(C.c_void_p(d_text), text_len, C.c_void_p(d_positions), n, max_lines, prefix, len(prefix),
+                                          C.c_void_p(d_out) if d_out else None, out_capacity, C.byref(out),
+                                          C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_format_lines failed: " + self.last_error())
+        return out
+
     # ---- search_func_t-shaped operators on host buffers ----
     def _ptr(self, text):
         if isinstance(text, np.ndarray):
@@ -430,6 +460,41 @@ class Plan:
         if rc:
             raise KrepGpuError("krep_gpu_scan_device failed: " + self.eng.last_error())
         return out
+
+    def grep_lines(self, d_text: int, n: int, filename=None, max_count=None, stream: int = 0) -> bytes:
+        """What `krep [-m N] PATTERN FILE` prints (colour off) for the n bytes at d_text: the scan with records, the cut to the
+        first max_count records in emission order (search_file()), the (start, end) order for a multi-pattern list, and the
+        lines from krep_gpu_format_lines.  filename: str / bytes in front of every line ("FILE:"), None as for search_string().
+        max_count: None takes the plan's.  Device buffers come from torch (the current device)."""
+        import torch
+        eng = self.eng
+        limit = int(self.params.s.max_count)
+        if max_count is not None:
+            limit = min(limit, int(max_count))
+        if limit == 0 or n == 0:
+            return b""
+        found = self.scan(d_text, n, stream=stream)
+        cap = int(max(found.count, found.total_matches))
+        if cap == 0:
+            return b""
+        pos = torch.empty(2 * (cap + 1), dtype=torch.int64, device="cuda")
+        out = self.scan(d_text, n, d_positions=pos.data_ptr(), capacity=cap + 1, stream=stream)
+        if out.overflow:
+            raise KrepGpuError("grep_lines: the record list outgrew the count of the scan before it")
+        m = min(int(out.stored), limit)
+        if m == 0:
+            return b""
+        if self.params.s.num_patterns > 1:
+            eng.order_by_start(pos.data_ptr(), m, n, stream)
+        prefix = b"" if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode()) + b":"
+        guess = m * (len(prefix) + 256) + 4096  # one call when the lines are short; the sizes it reports serve the second
+        buf = torch.empty(guess, dtype=torch.uint8, device="cuda")
+        res = eng.format_lines(d_text, n, pos.data_ptr(), m, limit, prefix, buf.data_ptr(), guess, stream)
+        if res.overflow:
+            buf = torch.empty(int(res.out_bytes), dtype=torch.uint8, device="cuda")
+            res = eng.format_lines(d_text, n, pos.data_ptr(), m, limit, prefix, buf.data_ptr(), int(res.out_bytes), stream)
+            assert not res.overflow
+        return buf[: int(res.out_bytes)].cpu().numpy().tobytes()
 
     def anchor_info(self):
         """(state 0 undecided / 1 end grams / 2 anchored, patterns moved, est. candidate rate end grams, ... anchors) — multi-pattern plans"""

@@ -1,0 +1,88 @@
+"""The matching lines on the device, timed: krep_gpu_matching_lines and krep_gpu_format_lines beside krep_gpu_line_numbers (the
+in-tree primitive of the same shape) on the same record list and text, alternating, in ONE process with the text resident.
+Events around the calls, warmed up.  Beside them the floor from the bytes moved: the text once + 16 B per record + 2 x out_bytes
+at the measured streaming rate (bench.HBM_MEASURED_GBS).
+usage: python tools/lines_bench.py [--gib 32] [--reps 9] [--warmup 2] [--only literal8|ac1000] [--out profiles/lines_on_device.txt]"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=32.0)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--only", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lines_on_device.txt"))
+    args = ap.parse_args()
+    import torch
+    import bench
+    import krep_amd
+    from krep_amd import abi
+    eng = krep_amd.load()
+    n = int(args.gib * (1 << 30))
+    lines = [f"# tools/lines_bench.py --gib {args.gib:g} --reps {args.reps} --warmup {args.warmup}: one process, text resident, "
+             "events around each call (the calls synchronise), calls alternating",
+             f"# {torch.cuda.get_device_name(0)}; floor = (text + 16 B x records + 2 x out_bytes) / {bench.HBM_MEASURED_GBS:g} GB/s; "
+             "ms as median [min .. max]"]
+    buf = torch.empty(n + 64, dtype=torch.uint8, device="cuda")
+    for name in ("literal8", "ac1000"):
+        if args.only and args.only != name:
+            continue
+        wl = bench.workload(name)
+        pats = wl["patterns"]
+        plant = wl["plant"] if wl["plant"] is not None else bench.pack_dict(pats)
+        eng.generate(buf.data_ptr(), n, 0, wl["kind"], wl.get("seed", bench.SEED), plant, wl["period"])
+        plan = eng.plan(abi.Params(pats))
+        cap = int(plan.scan(buf.data_ptr(), n).total_matches) + 16
+        pos = torch.empty(2 * cap, dtype=torch.int64, device="cuda")
+        out = plan.scan(buf.data_ptr(), n, d_positions=pos.data_ptr(), capacity=cap)
+        assert not out.overflow
+        m = int(out.stored)
+        if len(pats) > 1:
+            eng.order_by_start(pos.data_ptr(), m, n)
+        prefix = b"corpus.txt:"
+        q = eng.format_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, prefix)
+        L, nbytes = int(q.lines), int(q.out_bytes)
+        lineno = torch.empty(m, dtype=torch.int64, device="cuda")
+        spans = torch.empty(2 * L, dtype=torch.int64, device="cuda")
+        first = torch.empty(L + 1, dtype=torch.int64, device="cuda")
+        dst = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda")
+        calls = {
+            "krep_gpu_line_numbers": lambda: eng.line_numbers(buf.data_ptr(), n, pos.data_ptr(), m, lineno.data_ptr()),
+            "krep_gpu_matching_lines": lambda: eng.matching_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, spans.data_ptr(),
+                                                                  first.data_ptr(), L),
+            "krep_gpu_format_lines": lambda: eng.format_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, prefix, dst.data_ptr(),
+                                                              nbytes),
+        }
+        ms = {k: [] for k in calls}
+        for rep in range(args.warmup + args.reps):
+            for k, f in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                f()
+                e1.record()
+                e1.synchronize()
+                if rep >= args.warmup:
+                    ms[k].append(e0.elapsed_time(e1))
+        lines.append(f"{name}: text {n} B, {m} records, {L} lines ({int(q.capped_lines)} capped), out_bytes {nbytes}")
+        for k, v in ms.items():
+            moved = n + 16 * m + (2 * nbytes if k == "krep_gpu_format_lines" else 0)
+            lines.append(f"  {k:26s} {statistics.median(v):9.3f} ms [{min(v):.3f} .. {max(v):.3f}]   floor {moved / bench.HBM_MEASURED_GBS / 1e6:7.3f} ms")
+        plan.close()
+        del pos, lineno, spans, first, dst
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()
