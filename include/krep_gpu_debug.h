@@ -47,6 +47,13 @@ uint64_t krep_gpu_debug_anchored_launches(void);
 /* test hook: launches of the LDS-DMA literal kernel (kg_literal_dma.hip: 2..8-byte patterns on 32-KiB units without -c) since the
  * process started; $KREP_GPU_LIT_NO_DMA=1 keeps such scans on the register-load kernel (kg_literal.hip) */
 uint64_t krep_gpu_debug_literal_dma_launches(void);
+/* ... in its one-pass records mode (the scanning waves write the records at their final index, no ordering post-pass: records of a sparse
+ * literal on a ticketed text), how many of those scans handed over to the two-pass road (a ticket denser than a wave's hit list, or the
+ * spin-limit safety net), and a starved grid for that mode: at most `blocks` workgroups (0 = auto).  $KREP_GPU_LIT_DMA_TWO_PASS=1 keeps
+ * such scans on the two-pass road (A/B inside one library) */
+uint64_t krep_gpu_debug_literal_dma_one_pass_launches(void);
+uint64_t krep_gpu_debug_literal_dma_one_pass_failovers(void);
+void krep_gpu_debug_force_literal_dma_grid(int blocks);
 /* what chose between that kernel and the register kernel for `plan`: has the text been sampled, is the kernel barred for it (the prefilter's
  * byte occurs in more than 35 % of its 1-KiB cells; $KREP_GPU_LIT_DMA_MAX_PASS), the share last measured (sample or launch).
  * $KREP_GPU_LIT_DMA_KEEP=1: no sample, no bar (measurement aid) */

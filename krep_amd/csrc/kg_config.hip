@@ -267,5 +267,8 @@ std::atomic<uint64_t> g_ac_anchored_launches{0}; // launches of the multi-patter
 }
 extern "C" uint64_t krep_gpu_debug_anchored_launches(void) { return kg::g_ac_anchored_launches.load(); }
 extern "C" uint64_t krep_gpu_debug_literal_dma_launches(void) { return kg::g_lit_dma_launches.load(); }
+extern "C" uint64_t krep_gpu_debug_literal_dma_one_pass_launches(void) { return kg::g_lit_dma1p_launches.load(); }
+extern "C" uint64_t krep_gpu_debug_literal_dma_one_pass_failovers(void) { return kg::g_lit_dma1p_failovers.load(); }
+extern "C" void krep_gpu_debug_force_literal_dma_grid(int blocks) { kg::g_lit_dma1p_force_grid = blocks < 0 ? 0 : blocks; }
 extern "C" uint64_t krep_gpu_debug_runs_launches(void) { return kg::g_runs_launches.load(); }
 

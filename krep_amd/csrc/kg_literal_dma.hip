@@ -11,6 +11,9 @@
 //     from LDS, not from a shuffle — and compares all 16 start positions in registers exactly as lit_scan does;
 //   * the up-to-seven start positions whose window crosses the end of a round wait for the next round's first 8 bytes (a ticket's
 //     last round: a 256-byte DMA piece behind the ticket) and are tested by lanes 0..7 then.
+// ONEP, the records sink on a ticketed text (kg_scan.hip lit_dma_one_pass): the same streaming loop, but what is found is not staged for
+// kg_post.hip — the waves write the records at their final index through the ticket -> resolver -> deferred-store scheme of
+// kg_tickets.h (in front of the kernel, below).  One launch per scan, no info words, no staging slots, no ordering post-pass.
 // Why: a bare LDS-DMA reader runs at 7.3 TB/s on this part where the register reader reaches 7.06, and with the literal compare
 // at 6.98 (2 workgroups per CU) where the register version with a rolling prefetch reaches 6.77 and lit_scan 6.5-6.65
 // (tools/ubench/read_ceiling.hip `ldsdma`, profiles/r06_ldsdma_ubench.txt).  No MFMA anywhere: an HBM-bound byte scan.
@@ -21,6 +24,7 @@
 #include "kg_common.h"
 #include "kg_device.h"
 #include "kg_internal.h"
+#include "kg_tickets.h"
 
 namespace kg {
 
@@ -30,20 +34,56 @@ constexpr u32 kDmaPark = 80;                 // parked units per wave (info word
 constexpr u32 kDmaRing = 2u * kSegBytes;     // two rounds
 constexpr u32 kDmaTail = 256u;               // the DMA piece behind a ticket (4 B per lane)
 constexpr u32 kDmaWaveLds = kDmaRing + kDmaTail; // dynamic LDS per wave; + 44 B per parked unit in static arrays: 20160 B per wave, two workgroups per CU
+// ONEP (the records sink without a post-pass): instead of the parked units, per wave
+constexpr u32 kOpHits = 768;                 // ... the hit list: ticket-relative offsets (u32) of the parked tickets, in rank order
+constexpr u32 kOpTk = 32;                    // ... and the table of parked tickets {ticket, hits, first list index}
+static_assert(kOpHits * 4u + kOpTk * 12u <= kDmaPark * 44u, "the one-pass mode's static LDS stays within the staging mode's (two workgroups per CU)");
+static_assert(kOpTk <= 64u, "one lane per parked ticket picks its prefix up");
 } // namespace
+uint32_t lit_dma_one_pass_list() { return kOpHits; }
 
-template <int KIND, bool MASKED, bool CI>
-__global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
+// ONEP: the scanning waves write the records themselves, at their final index, by the ticket -> resolver -> deferred-store scheme of
+// kg_tickets.h (agg / pref: its per-ticket counts and prefixes, zeroed by the host; n_tickets = ceil(units / a.upt), a.upt >= 1):
+//   * the first wave 0 to claim ctr->pad[0] is the resolver and does not scan;
+//   * a hit goes into the wave's LDS hit list as its ticket-relative offset, ranked inside the TICKET (wcnt runs over the ticket);
+//   * at a ticket's end its count is published (one 8-byte store) BEFORE anything is waited for, and {ticket, count, list index} is parked;
+//   * when the list (a ring) is more than half full or the table is full (BASELINE's 27 hits per 256-KiB ticket: every ~14 tickets, ~1 ms), and
+//     at the end, the wave picks up the prefixes of all its parked tickets BUT THE ONE THAT HAS JUST ENDED at once (one lane each: one memory latency, and every count they
+//     depend on was published by a wave that was not waiting) and writes the records: 16-byte non-temporal stores, lanes mapped to record
+//     indices rounded down to 8 as kg_single.hip does.  These sit where flush_parked() sits in the staging mode: between rounds;
+//   * a ticket with more hits than the list has room for is counted, not recorded: ctr->overflow_units, the host takes the two-pass road.
+// No info words, no staging slots.  The streaming loop is the staging mode's, instruction for instruction.
+template <int KIND, bool MASKED, bool CI, bool ONEP>
+__global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *__restrict__ agg, const u64 *__restrict__ pref, const u64 n_tickets)
 {
     // The ring is the ONLY thing in the dynamic LDS block and is read through inline ds_read (below): the compiler orders every LDS
     // access that may alias an LDS-DMA destination behind s_waitcnt vmcnt(0) — which would retire the next round's DMA before this
     // round is looked at (measured: 6.3 ms where the register kernel takes 5.3).  The parked stores live in static arrays of their own.
     extern __shared__ __attribute__((aligned(16))) uint8_t d_smem[];
-    __shared__ u64 s_info_all[kWavesPerBlk][kDmaPark];
-    __shared__ __attribute__((aligned(16))) unsigned short s_slots_all[kWavesPerBlk][kDmaPark * 16u];
-    __shared__ u32 s_unit_all[kWavesPerBlk][kDmaPark];
+    // (ONEP does not use s_info / s_slots / s_unit: one-element dummies, which the compiler drops — 13 824 B against 14 080; the staging mode
+    //  does not use s_hits / s_tk.  s_tk is written by lane 0 and read by every lane of the SAME wave through plain LDS accesses: a wave's LDS
+    //  operations complete in order and the compiler waits lgkmcnt before the values are used, so no barrier is needed; no other wave touches it)
+    __shared__ u64 s_info_all[kWavesPerBlk][ONEP ? 1u : kDmaPark];
+    __shared__ __attribute__((aligned(16))) unsigned short s_slots_all[kWavesPerBlk][ONEP ? 8u : kDmaPark * 16u];
+    __shared__ u32 s_unit_all[kWavesPerBlk][ONEP ? 1u : kDmaPark];
+    __shared__ u32 s_hits_all[kWavesPerBlk][ONEP ? kOpHits : 1u];
+    __shared__ u32 s_tk_all[kWavesPerBlk][ONEP ? 3u * kOpTk : 1u];
     const u32 lane = lane_id();
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (ONEP && wave == 0)
+    {
+        // the resolver (kg_tickets.h): the first wave 0 of any block to get here — a wave that RUNS, whatever part of the grid is resident
+        u64 r = 1;
+        if (lane == 0)
+            r = __hip_atomic_fetch_add(&a.ctr->pad[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (rfl64(r) == 0ull)
+        {
+            tk_resolve(agg, const_cast<u64 *>(pref), n_tickets, a.ctr, lane);
+            return;
+        }
+    }
+    u32 *s_hits = s_hits_all[wave];
+    u32 *s_tk = s_tk_all[wave];
     uint8_t *ring = d_smem + wave * kDmaWaveLds;
     uint8_t *tailb = ring + kDmaRing;
     u64 *s_info = s_info_all[wave];
@@ -110,18 +150,72 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
         return true;
     };
 
+    // ONEP: the parked tickets of this wave (all uniform); the hit list is a ring
+    u32 hp = 0;     // ring index where the hits of the ticket being scanned start
+    u32 used = 0;   // ring entries the parked tickets hold
+    u32 n_tkp = 0;  // parked tickets
+    bool overflowed = false;
+    auto hwrap = [](const u32 x) -> u32 { return x >= kOpHits ? x - kOpHits : x; }; // (x < 2 kOpHits)
+    // the records of the first n_out parked tickets; the rest (at most the one that has just ended) moves to the front of the table
+    auto flush_records = [&](const u32 n_out) __attribute__((always_inline)) {
+        u64 pfx = 0;
+        if (lane < n_out)
+            pfx = tk_wait_prefix_lane(pref, (u64)s_tk[3u * lane], a.ctr);
+        for (u32 i = 0; i < n_out; ++i)
+        {
+            const u32 t = __builtin_amdgcn_readfirstlane(s_tk[3u * i]), cnt = __builtin_amdgcn_readfirstlane(s_tk[3u * i + 1u]),
+                      at = __builtin_amdgcn_readfirstlane(s_tk[3u * i + 2u]);
+            const u64 first = ((u64)(u32)__builtin_amdgcn_readlane((u32)(pfx >> 32), i) << 32) | (u32)__builtin_amdgcn_readlane((u32)pfx, i);
+            const u64 tbase = a.global_base + a.anchor + (u64)t * ((u64)tk_units * kUnitBytes);
+            const u32 pad = (u32)(first & 7ull); // (whole 128-byte lines per store instruction except at the two ends of the ticket's run)
+            for (u32 q = lane; q < cnt + pad; q += 64u)
+            {
+                if (q < pad)
+                    continue;
+                const u32 e = q - pad;
+                const u64 idx = first + e;
+                if (idx < a.pos_cap)
+                {
+                    const u64 st = tbase + s_hits[hwrap(at + e)], en = st + a.m;
+                    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+                    const u32x4 rec = {(u32)st, (u32)(st >> 32), (u32)en, (u32)(en >> 32)};
+                    __builtin_nontemporal_store(rec, reinterpret_cast<u32x4 *>(a.positions + 2 * idx));
+                }
+            }
+            used -= cnt;
+        }
+        if (n_out < n_tkp) // (one ticket stays)
+        {
+            const u32 t = s_tk[3u * n_out], cnt = s_tk[3u * n_out + 1u], at = s_tk[3u * n_out + 2u];
+            if (lane == 0)
+            {
+                s_tk[0] = t;
+                s_tk[1] = cnt;
+                s_tk[2] = at;
+            }
+        }
+        n_tkp -= n_out;
+    };
+
     u64 acc_total = 0;
     u32 pf_cells = 0; // 1-KiB cells the prefilter let through (uniform; Counters::candidates — what the host's choice of kernel follows)
-    u32 wcnt = 0; // hits of the unit being scanned (uniform)
-    // a hit at unit-relative offset `rel` of `unit`, ranked idx: staged (parked or in the unit's slot)
+    u32 wcnt = 0; // hits of the unit being scanned (uniform); ONEP: of the ticket
+    // a hit at unit-relative offset `rel` of `unit`, ranked idx: staged (parked or in the unit's slot); ONEP: `rel` is ticket-relative, into the list
     auto stage_hit = [&](u64 unit, u32 idx, u32 rel) __attribute__((always_inline)) {
-        if (idx < a.stage_cap)
+        if (ONEP)
+        {
+            if (idx < kOpHits - used)
+                s_hits[hwrap(hp + idx)] = rel;
+        }
+        else if (idx < a.stage_cap)
         {
             unsigned short *slot = park ? &s_slots[n_park * a.stage_cap] : reinterpret_cast<unsigned short *>(a.stage) + unit * (u64)a.stage_cap;
             slot[idx] = (unsigned short)rel;
         }
     };
     auto publish = [&](u64 unit) __attribute__((always_inline)) {
+        if (ONEP)
+            return; // (a unit's end is nothing to a ticket's list)
         acc_total += wcnt;
         if (want_pos)
         {
@@ -145,6 +239,33 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
                 flush_parked();
         }
         wcnt = 0;
+    };
+    // ONEP, the end of ticket `t`: its count published before anything is waited for, its hits parked; then the flush, if it is time —
+    // of the tickets parked BEFORE this one: the prefix of a ticket that has just ended still waits for the tickets drawn shortly before
+    // it, which other waves are about to finish (measured: flushing the newest ticket too cost the scan 0.1-0.2 ms of 5.2), while a
+    // ticket that is one ticket period old has its prefix, and nobody waits (kg_single.hip flushes one ticket later for the same reason)
+    auto end_ticket = [&](u32 t) __attribute__((always_inline)) {
+        if (lane == 0)
+            __hip_atomic_store(&agg[t], (u64)wcnt | kTkReady, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        u32 fresh = 0;
+        if (wcnt > kOpHits - used)
+            overflowed = true; // too dense for the list: counted (the resolver's sum is the total), not recorded
+        else if (wcnt)
+        {
+            if (lane == 0)
+            {
+                s_tk[3u * n_tkp] = t;
+                s_tk[3u * n_tkp + 1u] = wcnt;
+                s_tk[3u * n_tkp + 2u] = hp;
+            }
+            ++n_tkp;
+            hp = hwrap(hp + wcnt);
+            used += wcnt;
+            fresh = 1;
+        }
+        wcnt = 0;
+        if ((n_tkp == kOpTk || used > kOpHits / 2u) && n_tkp > fresh)
+            flush_records(n_tkp - fresh);
     };
     // exact compare of the window whose first word is A0 and second word A4 (the -i superset filter's second step included)
     auto exact = [&](u32 A0, u32 A4) -> bool {
@@ -274,7 +395,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
             // ---- the crossing positions of the round in front, now that its next 8 bytes are here
             if (deferred)
             {
-                boundary(seg - kSegBytes, u0 + ((g - 1u) >> 2), (g - 1u) & 3u, c0, c1, __builtin_amdgcn_readfirstlane(vv[0].x),
+                boundary(seg - kSegBytes, u0 + ((g - 1u) >> 2), ONEP ? g - 1u : (g - 1u) & 3u, c0, c1, __builtin_amdgcn_readfirstlane(vv[0].x),
                          __builtin_amdgcn_readfirstlane(vv[0].y));
                 deferred = false;
                 if (r == 0u)
@@ -387,7 +508,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
                 wcnt += tot;
                 if (want_pos)
                 {
-                    const u32 rel0 = (r * (u32)kCells + (u32)j) * kCellBytes + lane * 16u;
+                    const u32 rel0 = ((ONEP ? g : r) * (u32)kCells + (u32)j) * kCellBytes + lane * 16u;
                     u32 rest = m16;
                     while (rest)
                     {
@@ -424,10 +545,13 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
                         n0 = __builtin_amdgcn_readfirstlane(w.v[0]);
                         n1 = __builtin_amdgcn_readfirstlane(w.v[1]);
                     }
-                    boundary(seg, unit, r, c0, c1, n0, n1);
+                    boundary(seg, unit, ONEP ? g : r, c0, c1, n0, n1);
                     deferred = false;
                 }
-                publish(unit);
+                if (ONEP)
+                    end_ticket((u32)u0 / tk_units);
+                else
+                    publish(unit);
             }
             else if (!deferred && r == 3u)
                 publish(unit); // (a guarded round ended the unit: nothing is pending)
@@ -435,8 +559,12 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a)
         }
         u0 = u_next;
     }
-    if (park && n_park)
+    if (!ONEP && park && n_park)
         flush_parked();
+    if (ONEP && n_tkp)
+        flush_records(n_tkp);
+    if (ONEP && overflowed && lane == 0)
+        atomicAdd(&a.ctr->overflow_units, 1ull);
     if (lane == 0 && acc_total)
         atomicAdd(&a.ctr->total, acc_total);
     if (lane == 0 && pf_cells)
@@ -476,23 +604,42 @@ hipError_t launch_dma_byte_look(const uint8_t *text, uint64_t lo, uint32_t n_cel
 
 // ---- launcher ----------------------------------------------------------------------------------
 std::atomic<uint64_t> g_lit_dma_launches{0};
+std::atomic<uint64_t> g_lit_dma1p_launches{0}; // ... of them in the one-pass records mode (ONEP)
+std::atomic<uint64_t> g_lit_dma1p_failovers{0}; // ... whose scan was handed over to the two-pass road (kg_scan.hip lit_dma_one_pass)
+int g_lit_dma1p_force_grid = 0;                // test hook: at most this many workgroups for that mode (0 = auto)
 
-template <int KIND, bool MASKED, bool CI>
-static hipError_t dma_launch3(const LitArgs &a, u32 num_cu, hipStream_t st)
+template <int KIND, bool MASKED, bool CI, bool ONEP>
+static hipError_t dma_launch4(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st)
 {
     constexpr u32 lds = kWavesPerBlk * kDmaWaveLds; // dynamic part (the rings); the parked stores are static
-    if (const hipError_t e = grant_dynamic_lds<&lit_scan_dma<KIND, MASKED, CI>>((int)lds); e != hipSuccess)
+    if (const hipError_t e = grant_dynamic_lds<&lit_scan_dma<KIND, MASKED, CI, ONEP>>((int)lds); e != hipSuccess)
         return e;
     static const u32 bpc = [] { const char *e = getenv("KREP_GPU_LIT_DMA_BLOCKS_PER_CU"); return e && atoi(e) > 0 ? (u32)atoi(e) : 2u; }();
-    const u32 grid = (u32)std::min<u64>(a.num_tiles, (u64)num_cu * bpc);
-    hipLaunchKernelGGL((lit_scan_dma<KIND, MASKED, CI>), dim3(grid ? grid : 1), dim3(kBlock), lds, st, a);
+    u32 grid = (u32)std::min<u64>(a.num_tiles, (u64)num_cu * bpc);
+    if (ONEP && g_lit_dma1p_force_grid > 0) // test hook: a starved grid — the progress argument of kg_tickets.h
+        grid = std::min<u32>(grid, (u32)g_lit_dma1p_force_grid);
+    hipLaunchKernelGGL((lit_scan_dma<KIND, MASKED, CI, ONEP>), dim3(grid ? grid : 1), dim3(kBlock), lds, st, a, agg, pref, n_tickets);
     g_lit_dma_launches.fetch_add(1, std::memory_order_relaxed);
+    if (ONEP)
+        g_lit_dma1p_launches.fetch_add(1, std::memory_order_relaxed);
     return hipGetLastError();
 }
-template <int KIND, bool MASKED>
-static hipError_t dma_launch2(const LitArgs &a, u32 num_cu, hipStream_t st)
+template <int KIND, bool MASKED, bool ONEP>
+static hipError_t dma_launch2(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st)
 {
-    return (a.flags & F_CI) ? dma_launch3<KIND, MASKED, true>(a, num_cu, st) : dma_launch3<KIND, MASKED, false>(a, num_cu, st);
+    return (a.flags & F_CI) ? dma_launch4<KIND, MASKED, true, ONEP>(a, agg, pref, n_tickets, num_cu, st)
+                            : dma_launch4<KIND, MASKED, false, ONEP>(a, agg, pref, n_tickets, num_cu, st);
+}
+template <bool ONEP>
+static hipError_t dma_launch1(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st)
+{
+    if (a.m < 4)
+        return dma_launch2<4, true, ONEP>(a, agg, pref, n_tickets, num_cu, st);
+    if (a.m == 4)
+        return dma_launch2<4, false, ONEP>(a, agg, pref, n_tickets, num_cu, st);
+    if (a.m < 8)
+        return dma_launch2<8, true, ONEP>(a, agg, pref, n_tickets, num_cu, st);
+    return dma_launch2<8, false, ONEP>(a, agg, pref, n_tickets, num_cu, st);
 }
 
 // does this launch take the LDS-DMA kernel?  2..8-byte patterns, 32-KiB units, no -c, not the emit-mode re-scan
@@ -507,13 +654,16 @@ bool literal_dma_eligible(const LitArgs &a)
 }
 hipError_t launch_literal_dma(const LitArgs &a, u32 num_cu, hipStream_t st)
 {
-    if (a.m < 4)
-        return dma_launch2<4, true>(a, num_cu, st);
-    if (a.m == 4)
-        return dma_launch2<4, false>(a, num_cu, st);
-    if (a.m < 8)
-        return dma_launch2<8, true>(a, num_cu, st);
-    return dma_launch2<8, false>(a, num_cu, st);
+    return dma_launch1<false>(a, nullptr, nullptr, 0, num_cu, st);
+}
+// the one-pass records mode: d_agg / d_pref = n_tickets words each, zeroed on the stream in front of the launch, like a.ctr
+hipError_t launch_literal_dma_one_pass(const LitArgs &a, unsigned long long *d_agg, unsigned long long *d_pref, uint64_t n_tickets, u32 num_cu,
+                                       hipStream_t st)
+{
+    const u64 n_units = a.num_tiles * kWavesPerBlk;
+    if (!(a.flags & F_POS) || !a.upt || n_units >= (1ull << 32) || n_tickets != (n_units + a.upt - 1) / a.upt || (u64)a.upt * kRoundsBig * kSegBytes > (1ull << 31))
+        return hipErrorInvalidValue;
+    return dma_launch1<true>(a, d_agg, d_pref, n_tickets, num_cu, st);
 }
 
 } // namespace kg

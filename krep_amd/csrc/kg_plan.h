@@ -51,6 +51,11 @@ struct krep_gpu_plan
     const void *dma_off_text = nullptr; // ... the text that said so
     size_t dma_off_len = 0;
     double dma_pass_rate = 0;     // last share measured (sample or launch)
+    // lit_dma_one_pass, that kernel writing the records itself (its ONEP mode): while the text's tickets fit its hit list
+    bool dma1p_off = false;       // a ticket of this text overflowed the list (or the safety net fired): the two-pass road for this text
+    const void *dma1p_off_text = nullptr;
+    size_t dma1p_off_len = 0;
+    double lit_density = -1.0;    // hits per byte the plan knows of its text (first look / last scan); < 0: nothing known yet
     bool first_look_done = false; // lit_first_look: the density of the plan's first large text has been sampled (road / ring shape / slot from it)
     bool fused1_ok = true;    // single byte with records: the one-pass kernel (kg_single.hip) until a scan proves too dense for it
     bool fusedk_on = false;   // a 2..8-byte literal with records: the same kernel's MULTI instantiations, switched on by a two-pass scan that

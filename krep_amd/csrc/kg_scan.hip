@@ -306,6 +306,7 @@ static int lit_first_look(krep_gpu_plan *pl, const LitPass &ps, LitScan &L, hipS
     HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const double density = looked ? (double)pl->h_ctr->total / (double)looked : 0.0, per_unit = density * 32768.0;
+    pl->lit_density = density;
     if (m_scan == 1)
     {
         if (density > single_fused_max_density(kFusedShapeMax))
@@ -376,6 +377,8 @@ static void lit_learn_density(krep_gpu_plan *pl, const LitPass &ps, const LitSca
 {
     const LitArgs &a = L.a;
     const uint32_t m_scan = a.m;
+    if (L.span() >= 8 * L.unit_bytes() && !ps.first_byte) // (a window shorter than a ticket says nothing about the text)
+        pl->lit_density = L.density(pl->h_ctr->total);
     if ((a.flags & F_POS) && m_scan != 1 && a.rounds == kRoundsBig && pl->h_ctr->overflow_units * 64 > L.n_units && !L.fsc)
     {
         // a dense input: the next scans of this plan stage 64 hits per unit — and if more than 1 unit in 64 overflows that as
@@ -411,6 +414,71 @@ static void lit_reopen(krep_gpu_plan *pl, const LitScan &L)
         pl->fused1_ok = true;
     if (pl->fusedk_never && m_scan >= 2 && m_scan <= 8 && single_fused_reopens(pl->h_ctr->total, L.span()))
         pl->fusedk_never = false;
+}
+
+// ---- records of a SPARSE 2..8-byte literal on a ticketed text (BASELINE config 2: 3.3 hits per 32-KiB unit): the LDS-DMA kernel in its
+// one-pass mode (kg_literal_dma.hip ONEP) — the scanning waves write the records at their final index through the ticket -> resolver ->
+// deferred-store scheme of kg_tickets.h, so there are no info words, no staging slots and no ordering post-pass: on the stream, one
+// memset (the counters and the ticket arrays lie in one block of post.d_tk), the launch, the end event, the read-back of the counters.
+// A ticket with more hits than a wave's list holds (or the spin-limit safety net) raises overflow_units: the two-pass road takes this
+// scan and the plan's later ones on this text.  *done: the scan is complete.
+static int lit_dma_one_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, LitScan &L, hipStream_t st, LitResult *res, bool *done)
+{
+    *done = false;
+    // ($KREP_GPU_LIT_DMA_TWO_PASS is read per launch: the A/B tools flip it inside one process; the two switches below are the tests', flipped
+    //  per test like literal_dma_eligible()'s, and are only looked at on a text below the ticketed range)
+    if (!(ps.sink == LitPass::RECORDS && !ps.lines && !ps.first_byte && ps.excl_lo == ps.excl_hi && L.fsc == 0 && !getenv("KREP_GPU_LIT_DMA_TWO_PASS")))
+        return 0;
+    LitArgs a = L.a;
+    if (!a.upt && getenv("KREP_GPU_LIT_DMA_ALL") && !getenv("KREP_GPU_LIT_UPT"))
+        a.upt = 8; // (the tests' switch on a text below the ticketed range: this mode needs tickets from one counter)
+    if (!a.upt || !literal_dma_eligible(a) || L.n_units >= (1ull << 32))
+        return 0;
+    if (pl->dma1p_off && pl->dma1p_off_text == (const void *)w.d_text && pl->dma1p_off_len == w.text_len)
+        return 0;
+    const uint64_t ticket_bytes = (uint64_t)a.upt * L.unit_bytes();
+    // the gate, in hits per ticket: a quarter of the list, and never above the density from which the one-pass writers of kg_single.hip
+    // take such a literal (fusedk_min_hits_per_unit) — this road does not run lit_learn_density(), so a text at or above the gate has to
+    // reach the two-pass road, which switches them on (the defaults coincide: 768 / 4 = 24 x 8)
+    const double gate = std::min(0.25 * (double)lit_dma_one_pass_list(), fusedk_min_hits_per_unit() * (double)a.upt);
+    if (pl->lit_density >= 0.0 && pl->lit_density * (double)ticket_bytes >= gate)
+        return 0;
+    // [Counters (16 words) | counts | prefixes]: one block, one memset
+    constexpr uint64_t kCtrWords = 16;
+    static_assert(sizeof(Counters) <= kCtrWords * sizeof(unsigned long long), "the counters in front of the ticket arrays");
+    const uint64_t n_tk = (L.n_units + a.upt - 1) / a.upt, cap_tk = n_tk + kCtrWords / 2;
+    PostScratch &post = *ps.post;
+    HIPCHK(grow_scratch(post.tk_cap, cap_tk, cap_tk, {dev_buf(post.d_tk, 2 * cap_tk * sizeof(unsigned long long))}));
+    Counters *d_ctr = reinterpret_cast<Counters *>(post.d_tk);
+    unsigned long long *d_agg = post.d_tk + kCtrWords, *d_pref = d_agg + n_tk;
+    a.ctr = d_ctr;
+    a.positions = ps.d_out;
+    a.pos_cap = ps.out_cap;
+    a.stage_cap = 0;
+    HIPCHK(hipMemsetAsync(post.d_tk, 0, (kCtrWords + 2 * n_tk) * sizeof(unsigned long long), st));
+    HIPCHK(launch_literal_dma_one_pass(a, d_agg, d_pref, n_tk, (uint32_t)pl->num_cu, st));
+    if (ps.ev_end) HIPCHK(hipEventRecord(ps.ev_end, st));
+    HIPCHK(hipMemcpyAsync(pl->h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    LitScan La = L;
+    La.a = a;
+    lit_dma_rate(pl, w, La);
+    if (pl->h_ctr->overflow_units)
+    {
+        pl->dma1p_off = true;
+        pl->dma1p_off_text = w.d_text;
+        pl->dma1p_off_len = w.text_len;
+        g_lit_dma1p_failovers.fetch_add(1);
+        if (getenv("KREP_GPU_DEBUG"))
+            fprintf(stderr, "krep-gpu: literal scan: a ticket overflowed the one-pass hit list -> the two-pass road for this text\n");
+        return 0;
+    }
+    if (L.span() >= ticket_bytes)
+        pl->lit_density = L.density(pl->h_ctr->total);
+    res->total = pl->h_ctr->total;
+    res->summary = res->total ? (kLnHead | kLnTail) : 0;
+    *done = true;
+    return 0;
 }
 
 // ---- the two-pass road into records or counts: the scan (kg_literal.hip / kg_literal_dma.hip), the ordering post-pass
@@ -489,6 +557,10 @@ static int lit_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, hipSt
     res->anchor = L.a.anchor;
     bool done = false;
     if (lit_first_look(pl, ps, L, st) || lit_one_pass(pl, w, ps, L, st, res, &done))
+        return 2;
+    if (done)
+        return 0;
+    if (lit_dma_one_pass(pl, w, ps, L, st, res, &done))
         return 2;
     if (done)
         return 0;

@@ -1,5 +1,6 @@
 // kg_tickets.h — the ticket -> resolver -> deferred-store scheme of the one-pass record writers (kg_single.hip: a single byte or a
-// byte set; kg_ac_tiny.hip FUSED: the register-compare dictionary kernel), device side.
+// byte set; kg_ac_tiny.hip FUSED: the register-compare dictionary kernel; kg_literal_dma.hip ONEP: the sparse 2..8-byte literal, which
+// parks several tickets and picks their prefixes up together), device side.
 //
 // A scanning wave draws tickets from ONE counter (so the drawn tickets are always a prefix of the ticket space), ranks the matches
 // of a ticket into an LDS ring, publishes the ticket's count (`agg[t] = count | kTkReady`) and goes on; ONE resolver wave — the first
@@ -118,6 +119,28 @@ __device__ __forceinline__ unsigned long long tk_wait_prefix(const unsigned long
         }
     }
     return rfl64(p) & ~kTkReady;
+}
+
+// ... of the CALLING LANE's own ticket: every lane that calls spins for itself, so a wave that parked several tickets — all their counts
+// published — picks their prefixes up in one memory latency (kg_literal_dma.hip ONEP: one lane per parked ticket)
+__device__ __forceinline__ unsigned long long tk_wait_prefix_lane(const unsigned long long *__restrict__ pref, const unsigned long long t,
+                                                                   Counters *ctr)
+{
+    u64 p = 0;
+    for (uint32_t spins = 0;; ++spins)
+    {
+        p = __hip_atomic_load(&pref[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p & kTkReady)
+            break;
+        if (spins > 2u * kTkSpinLimit) // safety net, as above
+        {
+            atomicAdd(&ctr->overflow_units, 1ull);
+            p = kTkReady;
+            break;
+        }
+        __builtin_amdgcn_s_sleep(4);
+    }
+    return p & ~kTkReady;
 }
 
 } // namespace kg

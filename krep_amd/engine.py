@@ -134,6 +134,11 @@ class Engine:
             L.krep_gpu_debug_anchor_info.restype = C.c_int
             L.krep_gpu_debug_anchor_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                                                      C.POINTER(C.c_double)]
+        if hasattr(L, "krep_gpu_debug_literal_dma_one_pass_launches"):
+            L.krep_gpu_debug_literal_dma_one_pass_launches.restype = C.c_uint64
+            L.krep_gpu_debug_literal_dma_one_pass_failovers.restype = C.c_uint64
+            L.krep_gpu_debug_force_literal_dma_grid.restype = None
+            L.krep_gpu_debug_force_literal_dma_grid.argtypes = [C.c_int]
         if hasattr(L, "krep_gpu_alloc_placed"):
             L.krep_gpu_alloc_placed.restype = C.c_int
             L.krep_gpu_alloc_placed.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -209,6 +214,16 @@ class Engine:
 
     def literal_dma_launches(self) -> int:
         return int(self.lib.krep_gpu_debug_literal_dma_launches())
+
+    def literal_dma_one_pass_launches(self) -> int:
+        """launches of the LDS-DMA literal kernel in its one-pass records mode (no ordering post-pass)"""
+        return int(self.lib.krep_gpu_debug_literal_dma_one_pass_launches())
+
+    def literal_dma_one_pass_failovers(self) -> int:
+        return int(self.lib.krep_gpu_debug_literal_dma_one_pass_failovers())
+
+    def force_literal_dma_grid(self, blocks: int):
+        self.lib.krep_gpu_debug_force_literal_dma_grid(blocks)
 
     def alloc_placed(self, text_bytes: int, record_bytes: int, tries: int = 3, device: int = 0):
         """krep_gpu_alloc_placed(): (d_text, d_records, abi.Placement) — one block, its placement drawn for; free_placed(d_text)"""

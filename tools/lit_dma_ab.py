@@ -1,5 +1,5 @@
 """A/B of the LDS-DMA literal kernel (kg_literal_dma.hip) against the register-load kernel (kg_literal.hip) IN ONE PROCESS on the
-same HBM buffers: $KREP_GPU_LIT_NO_DMA is read per launch.   usage: python tools/lit_dma_ab.py <gib> [reps]
+same HBM buffers: $KREP_GPU_LIT_NO_DMA and $KREP_GPU_LIT_DMA_TWO_PASS (the records road with the ordering post-pass) are read per launch.   usage: python tools/lit_dma_ab.py <gib> [reps]
        python tools/lit_dma_ab.py <gib> <reps> rate   -> the two kernels against the share of 1-KiB cells that hold the pattern's first byte
                                                          (i.i.d. text with that byte sprinkled in), and what the library's own choice does:
                                                          profiles/r06_ldsdma_byte_rate.txt"""
@@ -54,7 +54,7 @@ if len(sys.argv) > 3 and sys.argv[3] == "rate":
               "   ".join(f"{k} {v:6.3f} ({n / v / 1e6:5.0f})" for k, v in med.items()) +
               f"   auto chose {'regs' if st_auto[1] else 'dma'}   count {cnt['dma']}  same: {len(set(cnt.values())) == 1}", flush=True)
     sys.exit(0)
-print(f"# {gib:g} GiB, median of {reps} launches each, alternating in one process; ms (GB/s)   [dma = kg_literal_dma.hip (where eligible), regs = kg_literal.hip, +pf = with the rare-first-byte prefilter]")
+print(f"# {gib:g} GiB, median of {reps} launches each, alternating in one process; ms (GB/s)   [dma = kg_literal_dma.hip (where eligible; offsets on a ticketed text: its one-pass records mode), dma 2-pass = the same kernel with the ordering post-pass ($KREP_GPU_LIT_DMA_TWO_PASS), regs = kg_literal.hip, +pf = with the rare-first-byte prefilter]")
 for m, kw, label in ((8, {}, "m=8 offsets"), (8, dict(count_lines=True, only_match=True), "m=8 count"), (8, dict(case_sensitive=False), "m=8 -i offsets"),
                      (8, dict(whole_word=True), "m=8 -w offsets"), (5, {}, "m=5 offsets"), (4, {}, "m=4 offsets"), (3, {}, "m=3 offsets"), (2, {}, "m=2 offsets")):
     pat = base[:m]
@@ -62,7 +62,8 @@ for m, kw, label in ((8, {}, "m=8 offsets"), (8, dict(count_lines=True, only_mat
     torch.cuda.synchronize()
     want_pos = "count" not in label
     plan = e.plan(abi.Params([pat], **kw))
-    ENV = {"dma": {}, "regs+pf": {"KREP_GPU_LIT_NO_DMA": "1"}, "regs": {"KREP_GPU_LIT_NO_DMA": "1", "KREP_GPU_LIT_NO_PREFILTER": "1"}}
+    ENV = {"dma": {}, "dma 2-pass": {"KREP_GPU_LIT_DMA_TWO_PASS": "1"}, "regs+pf": {"KREP_GPU_LIT_NO_DMA": "1"},
+           "regs": {"KREP_GPU_LIT_NO_DMA": "1", "KREP_GPU_LIT_NO_PREFILTER": "1"}}
     t = {k: [] for k in ENV}
     cnt = {}
     for rep in range(reps + 1):
