@@ -506,6 +506,46 @@ int krep_gpu_format_lines(const void *d_text, size_t text_len, const match_posit
                           uint64_t max_lines, const char *prefix, size_t prefix_len, void *d_out, size_t out_capacity,
                           krep_gpu_lines_out_t *out, void *stream);
 
+/* ---- the matches of a text in HBM, one per line: the reference's -o output (print_matching_items(), only-matching mode,
+ * krep.c:517-793) ----
+ * Input as above: the whole text and its n records in (start, end) order, n being the reference's result->count (search_file() has
+ * cut the list to its first max_count records in emission order and ordered it).  For record i < min(n, max_items), in list order:
+ *     prefix  before_number  LINE ':'  after_number  MATCH  after_match  '\n'
+ * The four strings are the caller's ("FILE:" and nothing else without colour; the escape codes of krep.h:34-39 with it: the library
+ * knows none).  MATCH is text[start, min(end, text_len)) with every '\n' inside it replaced by a blank (krep.c:736-747).
+ * LINE is the 1-based line of the record's start (a start ON a '\n' belongs to the line that newline ends), with the reference's
+ * exception: once a list holds more than 10 records the reference looks the line up in an index of the text's newlines
+ * (krep.c:531-556, :619-653), and a record that starts behind the text's LAST newline finds no entry there and prints the number of
+ * the search before it: LINE of the nearest earlier record that starts at or before the last newline, or 1 when there is none.  A
+ * list of at most 10 records, or a text without a newline, prints true numbers throughout.
+ * A list that is not ascending in start, or holds a record with start >= text_len or end < start, is refused (2) before any byte of
+ * the text is read through it (the reference passes over such a record; the calls above refuse the list, and so does this one).
+ * A match longer than the reference's 8 MiB batch buffer is outside what its code defines; here it is copied like any other.
+ * Returns 0, or 2 with krep_gpu_last_error() set (a string of more than 2^20 bytes, n >= 2^40, a failing HIP call), and synchronises
+ * `stream` before it returns.  d_out == NULL or out_capacity == 0 is a size query; a capacity that is too small sets `overflow` and
+ * returns 0 with valid sizes and nothing usable in d_out.  d_text and d_out may have any alignment; nothing is written outside
+ * [d_out, d_out + out_bytes).  n == 0 leaves everything 0. */
+typedef struct krep_gpu_match_format /* host strings, each may be NULL with length 0 */
+{
+    const char *prefix;
+    size_t prefix_len;
+    const char *before_number;
+    size_t before_number_len;
+    const char *after_number;
+    size_t after_number_len;
+    const char *after_match;
+    size_t after_match_len;
+} krep_gpu_match_format_t;
+typedef struct krep_gpu_matches_out
+{
+    uint64_t items;     /* records emitted = min(n, max_items) */
+    uint64_t out_bytes; /* bytes written, or needed            */
+    int overflow;       /* out_capacity was too small          */
+} krep_gpu_matches_out_t;
+int krep_gpu_format_matches(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
+                            uint64_t max_items, const krep_gpu_match_format_t *fmt /* NULL: all empty */, void *d_out,
+                            size_t out_capacity, krep_gpu_matches_out_t *out, void *stream);
+
 int krep_gpu_device_count(void);
 const char *krep_gpu_last_error(void); /* "" when the last call on this thread succeeded */
 void krep_gpu_clear_error(void);

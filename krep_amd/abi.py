@@ -61,6 +61,21 @@ class LinesOut(C.Structure):
                 ("overflow", C.c_int)]
 
 
+class MatchFormat(C.Structure):
+    """krep_gpu_match_format_t: the four host strings krep_gpu_format_matches puts around LINE and the match"""
+    _fields_ = [("prefix", C.c_char_p), ("prefix_len", C.c_size_t), ("before_number", C.c_char_p), ("before_number_len", C.c_size_t),
+                ("after_number", C.c_char_p), ("after_number_len", C.c_size_t), ("after_match", C.c_char_p), ("after_match_len", C.c_size_t)]
+
+    def __init__(self, prefix: bytes = b"", before_number: bytes = b"", after_number: bytes = b"", after_match: bytes = b""):
+        super().__init__(prefix, len(prefix), before_number, len(before_number), after_number, len(after_number), after_match,
+                         len(after_match))
+
+
+class MatchesOut(C.Structure):
+    """krep_gpu_matches_out_t: what krep_gpu_format_matches reports"""
+    _fields_ = [("items", C.c_uint64), ("out_bytes", C.c_uint64), ("overflow", C.c_int)]
+
+
 class Config(C.Structure):
     """krep_gpu_config_t: the reference's build level and file-static option globals, explicit."""
     _fields_ = [("reference_simd", C.c_int), ("only_matching", C.c_int), ("force_no_simd", C.c_int),

@@ -53,8 +53,6 @@ __global__ void fmt_merge(const u64 *__restrict__ starts, const u64 *__restrict_
     }
 }
 
-constexpr u32 kLineBlock = 4096; // newline counts are kept per 4 KiB of text
-
 // one wave per 4 KiB block: 4 x (64 lanes x 16 B), SWAR byte-equality + popcount
 __global__ __launch_bounds__(256) void fmt_count_newlines(const uint8_t *__restrict__ text, u64 text_len, u64 nblocks,
                                                           u64 *__restrict__ counts)
@@ -227,6 +225,17 @@ void scan_exclusive(const u64 *in, uint64_t n, u64 *out, u64 *sums, bool take_ma
         scan_launch<false>(in, n, out, sums, st);
 }
 
+// the newline-count pass and its sum (krep_gpu_line_numbers, krep_gpu_format_matches)
+int newlines_before_blocks(const uint8_t *d_text, uint64_t text_len, u64 *counts, u64 *before, u64 *sums, hipStream_t st)
+{
+    const u64 nblocks = line_blocks(text_len); // + 1: a match may start at text_len, and the last entry is the total
+    HIPCHK(hipMemsetAsync(counts, 0, nblocks * sizeof(u64), st));
+    const u32 grid = (u32)std::min<u64>((nblocks + 3) / 4, 256u * 32u);
+    hipLaunchKernelGGL(fmt_count_newlines, dim3(grid), dim3(256), 0, st, d_text, (u64)text_len, (u64)(nblocks - 1), counts);
+    scan_exclusive(counts, nblocks, before, sums, false, st);
+    return 0;
+}
+
 // ---- scratch: one grow-only buffer per device, reused across calls (ADVICE / VERDICT r02: no hipMalloc per call) ------
 std::mutex g_fmt_mu; // held for the whole call: the entry points synchronise before they return
 namespace {
@@ -338,7 +347,7 @@ extern "C" int krep_gpu_line_numbers_ex(const void *d_text, size_t text_len, siz
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(g_fmt_mu);
     int rc = 0;
-    const u64 nblocks = ((u64)text_len + kLineBlock - 1) / kLineBlock + 1; // + 1: a match may start at text_len
+    const u64 nblocks = line_blocks(text_len);
     const u64 nsb = (nblocks + kScanElems - 1) / kScanElems;
     if (nsb > 0x7fffffffull)
         return fail("krep_gpu_line_numbers: text too long"); // > 2^54 bytes
@@ -347,11 +356,8 @@ extern "C" int krep_gpu_line_numbers_ex(const void *d_text, size_t text_len, siz
         if (fmt_reserve((2 * nblocks + nsb) * sizeof(u64), &base))
             return 2;
         u64 *cnt = (u64 *)base, *pre = cnt + nblocks, *sums = pre + nblocks;
-        FCHK(hipMemsetAsync(cnt, 0, nblocks * sizeof(u64), st));
-        const u32 grid = (u32)std::min<u64>((nblocks + 3) / 4, 256u * 32u);
-        hipLaunchKernelGGL(fmt_count_newlines, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
-                           (u64)(nblocks - 1), cnt);
-        scan_exclusive(cnt, nblocks, pre, sums, false, st);
+        if (newlines_before_blocks((const uint8_t *)d_text, text_len, cnt, pre, sums, st))
+            return 2;
         hipLaunchKernelGGL(fmt_line_numbers, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
                            (u64)global_base, (const u64 *)d_positions, (u64)n, (const u64 *)pre, (u64 *)d_lines);
         FCHK(hipGetLastError());

@@ -240,6 +240,13 @@ uint64_t scan_sums_words(uint64_t n);       // words of scratch (`sums`) a scan 
 // exclusive prefix scan of in[0, n) into out (a buffer of its own) on `st`: the sum, or with take_max the running maximum (0 in front)
 void scan_exclusive(const unsigned long long *in, uint64_t n, unsigned long long *out, unsigned long long *sums, bool take_max,
                     hipStream_t st);
+constexpr uint32_t kLineBlock = 4096;       // newline counts are kept per 4 KiB of text
+// entries of the table below: one per block of the text and one more, so that its last entry is the text's total
+inline uint64_t line_blocks(uint64_t text_len) { return (text_len + kLineBlock - 1) / kLineBlock + 1; }
+// one streaming pass over the text on `st`: before[b] = the newlines in front of block b; `counts` (line_blocks words) and `sums`
+// (scan_sums_words(line_blocks)) are scratch.  (krep_gpu_line_numbers, kg_matches.hip)
+int newlines_before_blocks(const uint8_t *d_text, uint64_t text_len, unsigned long long *counts, unsigned long long *before,
+                           unsigned long long *sums, hipStream_t st);
 
 // kg_comm.hip — the RCCL all-reduce of the per-shard counters (one process driving several devices)
 int allreduce_across_devices(const std::vector<int> &devs, std::vector<std::vector<unsigned long long>> &vecs);

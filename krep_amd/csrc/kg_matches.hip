@@ -1,0 +1,340 @@
+// kg_matches.hip — the reference's -o output on a text that is resident in HBM: one `FILE:LINE:match` per record, as
+// print_matching_items() writes it in only-matching mode (krep.c:517-793), with or without its colour strings.
+//
+// Contract (restated from krep.c:597-780; the record list is in (start, end) order and already cut to max_count records, as
+// search_file() leaves it, n = result->count):
+//   * record i < min(n, max_items) prints  prefix before_number LINE ':' after_number MATCH after_match '\n'; the four strings are
+//     the caller's (the escape codes of krep.h:34-39 under --color=always, nothing but "FILE:" without);
+//   * MATCH = text[start, min(end, text_len)) with every '\n' replaced by a blank (:736-747);
+//   * LINE = 1 + the newlines in [0, start) — except that with more than 10 records the reference looks the line up in an index of
+//     the text's N newlines (:531-556, :619-653), and a record that starts behind the last newline finds nothing there and prints
+//     what the search before it left: LINE of the nearest earlier record that starts at or before the last newline, else 1.  On an
+//     ascending list those records are a suffix, and they are the records whose true number is N + 1.
+//
+// Steps: (1) the newline-count pass of kg_format.hip over the text and its sum: N and the newlines in front of every 4 KiB block;
+// (2) per record its true line number, counted from the NEARER end of its own block in 16-byte steps; the same kernel refuses a
+// list that is not ascending or points outside the text, and leaves the largest number <= N in a counter word: the stale value;
+// (3) per record the number it prints and its byte count (the stale value's digits are known only now), summed; (4) the gather,
+// dealt by OUTPUT bytes: a lane owns 16 aligned bytes of the output, a wave 1 KiB, the first record of a tile comes from a binary
+// search in the summed offsets.  A call reads the text once in (1), then only around the records and what it copies.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "../../include/krep_gpu.h"
+#include "kg_device.h"
+#include "kg_internal.h"
+
+namespace kg {
+
+constexpr u64 kOmStaleAfter = 10;          // result->count > 10 builds the newline index (krep.c:531)
+constexpr u64 kOmMaxText = 10000000000000000ull; // a line number has at most 16 digits here (two registers of 8)
+
+// newlines among the 16 bytes
+__device__ __forceinline__ u32 nl_count16(const uint4 v)
+{
+    return (u32)(__popc(eq_bytes(v.x, 0x0a0a0a0au)) + __popc(eq_bytes(v.y, 0x0a0a0a0au)) + __popc(eq_bytes(v.z, 0x0a0a0a0au)) +
+                 __popc(eq_bytes(v.w, 0x0a0a0a0au)));
+}
+// newlines in text[lo, hi) (hi <= text_len), any alignment
+__device__ __forceinline__ u32 nl_count(const uint8_t *__restrict__ text, u64 lo, u64 hi)
+{
+    u32 c = 0;
+    u64 p = lo;
+#pragma unroll 4
+    for (; p + 16 <= hi; p += 16)
+        c += nl_count16(load_unaligned<uint4>(text + p));
+    for (; p < hi; ++p)
+        c += text[p] == '\n';
+    return c;
+}
+__device__ __forceinline__ u32 om_digits(u64 v)
+{
+    u32 d = 1;
+    for (; v >= 10; v /= 10)
+        ++d;
+    return d;
+}
+
+// (2) line[i] = 1 + the newlines in front of record i's start; before[] = newlines in front of every 4 KiB block, one entry more
+// than the text has blocks (its last entry is N).  A record that may not be read raises ctr[0] and touches no text.  ctr[1]: the
+// largest line number <= N (0: none), i.e. that of the last record with a newline at or behind its start
+__global__ __launch_bounds__(256) void om_lines(const uint8_t *__restrict__ text, u64 text_len, const u64 *__restrict__ rec, u64 n,
+                                                const u64 *__restrict__ before, u64 nblocks, u64 *__restrict__ line,
+                                                u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u64 ln = 0;
+    if (i < n)
+    {
+        const uint4 r = *reinterpret_cast<const uint4 *>(rec + 2 * i);
+        const u64 s = ((u64)r.y << 32) | r.x, e = ((u64)r.w << 32) | r.z;
+        if (s >= text_len || e < s || (i > 0 && rec[2 * (i - 1)] > s))
+            ctr[0] = 1; // (every writer stores the same value)
+        else
+        {
+            const u64 b = s / kLineBlock, base = b * kLineBlock, lim = min(base + kLineBlock, text_len);
+            ln = s - base <= lim - s ? 1 + before[b] + nl_count(text, base, s) : 1 + before[b + 1] - nl_count(text, s, lim);
+        }
+        line[i] = ln;
+    }
+    u64 m = ln <= before[nblocks - 1] ? ln : 0ull;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        m = max(m, (u64)__shfl_xor(m, o));
+    if ((threadIdx.x & 63u) == 0 && m)
+        (void)__hip_atomic_fetch_max(ctr + 1, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// (3) the number record i prints (line[i], in place) and what it adds to the output; entry n: 0, so that the summed entry n is the
+// total.  (On a refused list the numbers mean nothing; nothing is read through them, and the host reports the refusal)
+__global__ __launch_bounds__(256) void om_sizes(const u64 *__restrict__ rec, u64 n, u64 text_len, const u64 *__restrict__ total_newlines,
+                                                u64 max_items, u64 fixed, const u64 *__restrict__ ctr, u64 *__restrict__ line,
+                                                u64 *__restrict__ bytes)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n)
+        return;
+    if (i == n || i >= max_items)
+    {
+        bytes[i] = 0;
+        return;
+    }
+    const u64 newlines = *total_newlines;
+    u64 ln = line[i];
+    if (n > kOmStaleAfter && newlines && ln == newlines + 1)
+    {
+        ln = max(ctr[1], 1ull);
+        line[i] = ln;
+    }
+    const u64 s = rec[2 * i], e = min(rec[2 * i + 1], text_len);
+    bytes[i] = fixed + om_digits(ln) + 1 + (e - s) + 1;
+}
+
+// the largest r in [lo, hi] with off[r] <= pos (off[lo] <= pos)
+__device__ __forceinline__ u64 om_find(const u64 *__restrict__ off, u64 lo, u64 hi, u64 pos)
+{
+    while (lo < hi)
+    {
+        const u64 mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= pos)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// the lengths of the three fixed strings, which lie behind one another in `fix`: prefix + before_number | after_number | after_match
+struct OmFixed
+{
+    u32 head, mid, tail;
+};
+// one record's output: where its parts end, counted from its first byte (b6 + 1 = its length)
+struct OmItem
+{
+    u64 src, b4, b5; // the match is text[src, src + b5 - b4)
+    u64 dlo, dhi;    // the digits of LINE as characters, the first one in the lowest byte of dlo
+    u32 b1, b2;      // head [0, b1), digits [b1, b2), ':' at b2, after_number [b2 + 1, b4), after_match [b5, b6), '\n' at b6
+    u64 b6;
+};
+__device__ __forceinline__ OmItem om_item(const u64 *__restrict__ rec, const u64 *__restrict__ line, u64 text_len, const OmFixed f, u64 r)
+{
+    OmItem it;
+    const uint4 w = *reinterpret_cast<const uint4 *>(rec + 2 * r);
+    const u64 s = ((u64)w.y << 32) | w.x, e = min(((u64)w.w << 32) | w.z, text_len);
+    u64 v = line[r], lo = 0, hi = 0;
+    u32 d = 0;
+    do // the least significant digit first: each one pushes the others up by a byte
+    {
+        hi = (hi << 8) | (lo >> 56);
+        lo = (lo << 8) | (u64)('0' + (u32)(v % 10));
+        v /= 10;
+        ++d;
+    } while (v);
+    it.src = s;
+    it.dlo = lo;
+    it.dhi = hi;
+    it.b1 = f.head;
+    it.b2 = f.head + d;
+    it.b4 = (u64)it.b2 + 1 + f.mid;
+    it.b5 = it.b4 + (e - s);
+    it.b6 = it.b5 + f.tail;
+    return it;
+}
+// its byte k (k <= b6)
+__device__ __forceinline__ u32 om_byte(const uint8_t *__restrict__ text, const uint8_t *__restrict__ fix, const OmFixed f, const OmItem &it, u64 k)
+{
+    if (k >= it.b4)
+    {
+        if (k < it.b5)
+        {
+            const u32 c = text[it.src + (k - it.b4)];
+            return c == '\n' ? (u32)' ' : c;
+        }
+        return k < it.b6 ? (u32)fix[f.head + f.mid + (k - it.b5)] : (u32)'\n';
+    }
+    if (k < it.b1)
+        return fix[k];
+    if (k < it.b2)
+    {
+        const u32 j = (u32)k - it.b1;
+        return (u32)((j < 8 ? it.dlo >> (8 * j) : it.dhi >> (8 * (j - 8))) & 0xffu);
+    }
+    return k == it.b2 ? (u32)':' : (u32)fix[f.head + (k - it.b2 - 1)];
+}
+// '\n' -> ' ' in the four bytes of w: the bytes differ in 0x2a
+__device__ __forceinline__ u32 om_blank(u32 w) { return w ^ ((eq_bytes(w, 0x0a0a0a0au) >> 7) * 0x2au); }
+
+// (4) chunk c is the 16 aligned bytes at (out - misalign) + 16 c, i.e. output offsets [16 c - misalign, + 16); `emit` records add bytes
+__global__ __launch_bounds__(256) void om_gather(const uint8_t *__restrict__ text, u64 text_len, const u64 *__restrict__ rec,
+                                                 const u64 *__restrict__ line, const u64 *__restrict__ off, u64 emit,
+                                                 const uint8_t *__restrict__ fix, const OmFixed f, uint8_t *__restrict__ out, u64 total,
+                                                 u32 misalign, u64 nchunks)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u64 wid = (u64)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (u64)gridDim.x * (blockDim.x >> 6);
+    for (u64 c0 = wid * 64; c0 < nchunks; c0 += nw * 64)
+    {
+        // the records of the wave's 1 KiB tile
+        const u64 tile_lo = c0 ? c0 * 16 - misalign : 0ull, tile_hi = min((c0 + 64) * 16 - misalign, total) - 1;
+        const u64 r_lo = om_find(off, 0, emit - 1, tile_lo), r_hi = om_find(off, r_lo, emit - 1, tile_hi);
+        const u64 c = c0 + lane;
+        if (c >= nchunks)
+            continue;
+        const u64 o0 = c ? c * 16 - misalign : 0ull, o1 = min((c + 1) * 16 - misalign, total);
+        const bool whole = o1 - o0 == 16;
+        u64 r = om_find(off, r_lo, r_hi, o0);
+        OmItem it = om_item(rec, line, text_len, f, r);
+        u64 k = o0 - off[r];
+        if (whole && k >= it.b4 && k + 16 <= it.b5) // wholly inside one match
+        {
+            const uint4 v = load_unaligned<uint4>(text + it.src + (k - it.b4));
+            *reinterpret_cast<uint4 *>(out + o0) = make_uint4(om_blank(v.x), om_blank(v.y), om_blank(v.z), om_blank(v.w));
+            continue;
+        }
+        u32 w[4] = {0, 0, 0, 0};
+        const u32 shift = (u32)(o0 + misalign - c * 16); // bytes of the chunk in front of the output (chunk 0 only)
+        const u32 cnt = (u32)(o1 - o0);
+#pragma unroll
+        for (u32 q = 0; q < 16; ++q)
+        {
+            if (q >= shift && q - shift < cnt)
+            {
+                if (k > it.b6) // the record is used up (every emitted record adds bytes)
+                {
+                    it = om_item(rec, line, text_len, f, ++r);
+                    k = 0;
+                }
+                w[q >> 2] |= om_byte(text, fix, f, it, k) << (8 * (q & 3u));
+                ++k;
+            }
+        }
+        if (whole)
+            *reinterpret_cast<uint4 *>(out + o0) = make_uint4(w[0], w[1], w[2], w[3]);
+        else
+        {
+#pragma unroll
+            for (u32 q = 0; q < 16; ++q)
+                if (q >= shift && q - shift < cnt)
+                    out[o0 + (q - shift)] = (uint8_t)(w[q >> 2] >> (8 * (q & 3u)));
+        }
+    }
+}
+
+} // namespace kg
+
+using namespace kg;
+
+extern "C" int krep_gpu_format_matches(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
+                                       uint64_t max_items, const krep_gpu_match_format_t *fmt, void *d_out, size_t out_capacity,
+                                       krep_gpu_matches_out_t *out, void *stream)
+{
+    const char *who = "krep_gpu_format_matches";
+    if (!out)
+        return fail("%s: out is NULL", who);
+    *out = krep_gpu_matches_out_t{};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return fail("%s: no HIP device available", who);
+    }
+    if (const char *why = device_unusable(dev))
+        return fail("%s: %s", who, why);
+    if (n && (!d_text || !d_positions))
+        return fail("%s: d_text / d_positions is NULL", who);
+    if (n >> 40)
+        return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
+    const krep_gpu_match_format_t none{};
+    const krep_gpu_match_format_t &m = fmt ? *fmt : none;
+    const char *str[4] = {m.prefix, m.before_number, m.after_number, m.after_match};
+    const size_t len[4] = {m.prefix_len, m.before_number_len, m.after_number_len, m.after_match_len};
+    for (int k = 0; k < 4; ++k)
+    {
+        if (len[k] && !str[k])
+            return fail("%s: a string of the format is NULL", who);
+        if (len[k] >> 20)
+            return fail("%s: a format string of %zu bytes", who, len[k]);
+    }
+    if (!n)
+        return 0;
+    if (!text_len)
+        return fail("%s: records on an empty text", who);
+    if (text_len >= kOmMaxText)
+        return fail("%s: text too long", who);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(g_fmt_mu);
+    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the fixed strings behind one another, alive until the copy has run
+    h_fix.clear();
+    for (int k = 0; k < 4; ++k)
+        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
+    const OmFixed f{(u32)(len[0] + len[1]), (u32)len[2], (u32)len[3]};
+    const u64 fixed = h_fix.size(), nblocks = line_blocks(text_len), n1 = n + 1;
+    const u64 sums = scan_sums_words(std::max(nblocks, n1));
+    void *base = nullptr;
+    if (fmt_reserve((8 + 2 * nblocks + 3 * n1 + sums) * sizeof(u64) + fixed + 16, &base))
+        return 2;
+    u64 *p = (u64 *)base;
+    auto take = [&](u64 words) { u64 *q = p; p += words; return q; };
+    u64 *ctr = take(8), *counts = take(nblocks), *before = take(nblocks); // ctr: {refused, stale value}
+    u64 *line = take(n1), *bytes = take(n1), *off = take(n1), *sum_words = take(sums);
+    uint8_t *d_fix = (uint8_t *)p;
+    HIPCHK(hipMemsetAsync(ctr, 0, 8 * sizeof(u64), st));
+    if (fixed)
+        HIPCHK(hipMemcpyAsync(d_fix, h_fix.data(), fixed, hipMemcpyHostToDevice, st));
+    if (newlines_before_blocks((const uint8_t *)d_text, text_len, counts, before, sum_words, st))
+        return 2;
+    hipLaunchKernelGGL(om_lines, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
+                       (const u64 *)d_positions, (u64)n, (const u64 *)before, nblocks, line, ctr);
+    hipLaunchKernelGGL(om_sizes, dim3((u32)((n1 + 255) / 256)), dim3(256), 0, st, (const u64 *)d_positions, (u64)n, (u64)text_len,
+                       (const u64 *)(before + nblocks - 1), (u64)max_items, fixed, (const u64 *)ctr, line, bytes);
+    scan_exclusive(bytes, n1, off, sum_words, false, st);
+    HIPCHK(hipGetLastError());
+    u64 refused = 0, total = 0;
+    HIPCHK(hipMemcpyAsync(&refused, ctr, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&total, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (refused)
+        return fail("%s: the record list is not ascending in start, or a record lies outside the text", who);
+    const u64 emit = std::min<u64>(n, max_items);
+    out->items = emit;
+    out->out_bytes = total;
+    if (!d_out || !out_capacity || !total)
+        return 0;
+    if (total > out_capacity)
+    {
+        out->overflow = 1;
+        return 0;
+    }
+    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
+    const u64 nchunks = (total + misalign + 15) / 16;
+    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
+    hipLaunchKernelGGL(om_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len, (const u64 *)d_positions,
+                       (const u64 *)line, (const u64 *)off, emit, (const uint8_t *)d_fix, f, (uint8_t *)d_out, total, misalign, nchunks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}

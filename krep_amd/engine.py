@@ -102,6 +102,10 @@ class Engine:
             L.krep_gpu_format_lines.restype = C.c_int
             L.krep_gpu_format_lines.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t,
                                                 C.c_void_p, C.c_size_t, C.POINTER(abi.LinesOut), C.c_void_p]
+        if hasattr(L, "krep_gpu_format_matches"):
+            L.krep_gpu_format_matches.restype = C.c_int
+            L.krep_gpu_format_matches.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(abi.MatchFormat),
+                                                  C.c_void_p, C.c_size_t, C.POINTER(abi.MatchesOut), C.c_void_p]
         for n in ("krep_gpu_set_reference_simd", "krep_gpu_set_only_matching", "krep_gpu_set_force_no_simd",
                   "krep_gpu_set_algo_override", "krep_gpu_debug_force_rounds", "krep_gpu_debug_force_stage_cap",
                   "krep_gpu_set_result_order", "krep_gpu_set_device", "krep_gpu_set_num_gpus", "krep_gpu_debug_inject_failure"):
@@ -389,6 +393,18 @@ class Engine:
             raise KrepGpuError("krep_gpu_format_lines failed: " + self.last_error())
         return out
 
+    # ---- the matches themselves, one per line (print_matching_items(), only-matching mode, krep.c:517-793) ----
+    def format_matches(self, d_text: int, text_len: int, d_positions: int, n: int, max_items: int = abi.SIZE_MAX,
+                       fmt: "abi.MatchFormat | None" = None, d_out: int = 0, out_capacity: int = 0, stream: int = 0) -> "abi.MatchesOut":
+        """krep_gpu_format_matches(): the bytes the reference prints under -o for these records, into d_out.  fmt: the strings around
+        LINE and the match (None: none).  d_out = 0 asks for .out_bytes; a capacity that is too small comes back as .overflow."""
+        out = abi.MatchesOut()
+        if self.lib.krep_gpu_format_matches(C.c_void_p(d_text), text_len, C.c_void_p(d_positions), n, max_items,
+                                            C.byref(fmt) if fmt is not None else None, C.c_void_p(d_out) if d_out else None,
+                                            out_capacity, C.byref(out), C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_format_matches failed: " + self.last_error())
+        return out
+
     # ---- search_func_t-shaped operators on host buffers ----
     def _ptr(self, text):
         if isinstance(text, np.ndarray):
@@ -440,7 +456,7 @@ class Engine:
         h = self.lib.krep_gpu_plan_create(params.ref, int(only_matching), device)
         if not h:
             raise KrepGpuError("krep_gpu_plan_create failed: " + self.last_error())
-        return Plan(self, h, params)
+        return Plan(self, h, params, bool(only_matching))
 
     def generate(self, d_ptr: int, length: int, global_off: int, kind: int, seed: int, plant: bytes = b"",
                  period: int = 0, stream: int = 0):
@@ -458,8 +474,8 @@ class Engine:
 
 
 class Plan:
-    def __init__(self, eng: Engine, handle, params):
-        self.eng, self.h, self.params = eng, handle, params
+    def __init__(self, eng: Engine, handle, params, only_matching=False):
+        self.eng, self.h, self.params, self.only_matching = eng, handle, params, only_matching
 
     @property
     def ref_algo(self) -> int:
@@ -508,6 +524,46 @@ class Plan:
         if res.overflow:
             buf = torch.empty(int(res.out_bytes), dtype=torch.uint8, device="cuda")
             res = eng.format_lines(d_text, n, pos.data_ptr(), m, limit, prefix, buf.data_ptr(), int(res.out_bytes), stream)
+            assert not res.overflow
+        return buf[: int(res.out_bytes)].cpu().numpy().tobytes()
+
+    def grep_only_matching(self, d_text: int, n: int, filename=None, max_count=None, color=False, stream: int = 0) -> bytes:
+        """What `krep -o [-m N] [--color=always] PATTERN FILE` prints for the n bytes at d_text: one FILE:LINE:match per match.  The
+        scan with records, the cut to the first max_count records in emission order (search_file()), the (start, end) order for a
+        multi-pattern list, and the bytes from krep_gpu_format_matches.  The plan must have been made with only_matching=True: under
+        -o the reference's match set is another one.  filename, max_count: as for grep_lines."""
+        import torch
+        eng = self.eng
+        if not self.only_matching:
+            raise KrepGpuError("grep_only_matching: the plan was not created with only_matching=True (the match set of -o differs)")
+        limit = int(self.params.s.max_count)
+        if max_count is not None:
+            limit = min(limit, int(max_count))
+        if limit == 0 or n == 0:
+            return b""
+        found = self.scan(d_text, n, stream=stream)
+        cap = int(max(found.count, found.total_matches))
+        if cap == 0:
+            return b""
+        pos = torch.empty(2 * (cap + 1), dtype=torch.int64, device="cuda")
+        out = self.scan(d_text, n, d_positions=pos.data_ptr(), capacity=cap + 1, stream=stream)
+        if out.overflow:
+            raise KrepGpuError("grep_only_matching: the record list outgrew the count of the scan before it")
+        m = min(int(out.stored), limit)
+        if m == 0:
+            return b""
+        if self.params.s.num_patterns > 1:
+            eng.order_by_start(pos.data_ptr(), m, n, stream)
+        name = b"" if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
+        fmt = match_format(name if filename is not None else None, color)
+        longest = max(int(x) for x in self.params.s.pattern_lens[: self.params.s.num_patterns])
+        per_item = fmt.prefix_len + fmt.before_number_len + fmt.after_number_len + fmt.after_match_len + 20 + 2 + longest
+        guess = m * per_item + 4096  # enough by construction; the second call serves a list whose records are longer than a pattern
+        buf = torch.empty(guess, dtype=torch.uint8, device="cuda")
+        res = eng.format_matches(d_text, n, pos.data_ptr(), m, limit, fmt, buf.data_ptr(), guess, stream)
+        if res.overflow:
+            buf = torch.empty(int(res.out_bytes), dtype=torch.uint8, device="cuda")
+            res = eng.format_matches(d_text, n, pos.data_ptr(), m, limit, fmt, buf.data_ptr(), int(res.out_bytes), stream)
             assert not res.overflow
         return buf[: int(res.out_bytes)].cpu().numpy().tobytes()
 
@@ -561,6 +617,19 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+# the escape codes of the reference's coloured output (data: krep.h:34-39)
+COLOR_RESET, COLOR_FILENAME, COLOR_SEPARATOR = b"\033[0m", b"\033[1;38;5;81m", b"\033[38;5;244m"
+COLOR_LINE_NUMBER, COLOR_MATCH = b"\033[1;38;5;111m", b"\033[1;38;5;222m"
+
+
+def match_format(filename: "bytes | None" = None, color: bool = False) -> "abi.MatchFormat":
+    """the strings of `krep -o` around LINE and the match (krep.c:565, :719-766): filename None prints no FILE: in front"""
+    if not color:
+        return abi.MatchFormat(b"" if filename is None else filename + b":")
+    prefix = b"" if filename is None else COLOR_FILENAME + filename + COLOR_RESET + COLOR_SEPARATOR + b":"
+    return abi.MatchFormat(prefix, COLOR_LINE_NUMBER, COLOR_RESET + COLOR_MATCH, COLOR_RESET)
 
 
 _engine = None

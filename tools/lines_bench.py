@@ -1,5 +1,6 @@
-"""The matching lines on the device, timed: krep_gpu_matching_lines and krep_gpu_format_lines beside krep_gpu_line_numbers (the
-in-tree primitive of the same shape) on the same record list and text, alternating, in ONE process with the text resident.
+"""The matching lines and the -o output on the device, timed: krep_gpu_matching_lines, krep_gpu_format_lines and
+krep_gpu_format_matches beside krep_gpu_line_numbers (the in-tree primitive of the same shape) on the same record list and text,
+alternating, in ONE process with the text resident.
 Events around the calls, warmed up.  Beside them the floor from the bytes moved: the text once + 16 B per record + 2 x out_bytes
 at the measured streaming rate (bench.HBM_MEASURED_GBS).
 usage: python tools/lines_bench.py [--gib 32] [--reps 9] [--warmup 2] [--only literal8|ac1000] [--out profiles/lines_on_device.txt]"""
@@ -53,13 +54,17 @@ def main():
         lineno = torch.empty(m, dtype=torch.int64, device="cuda")
         spans = torch.empty(2 * L, dtype=torch.int64, device="cuda")
         first = torch.empty(L + 1, dtype=torch.int64, device="cuda")
-        dst = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda")
+        fmt = abi.MatchFormat(prefix)
+        obytes = int(eng.format_matches(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, fmt).out_bytes)
+        dst = torch.empty(max(nbytes, obytes) + 64, dtype=torch.uint8, device="cuda")
         calls = {
             "krep_gpu_line_numbers": lambda: eng.line_numbers(buf.data_ptr(), n, pos.data_ptr(), m, lineno.data_ptr()),
             "krep_gpu_matching_lines": lambda: eng.matching_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, spans.data_ptr(),
                                                                   first.data_ptr(), L),
             "krep_gpu_format_lines": lambda: eng.format_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, prefix, dst.data_ptr(),
                                                               nbytes),
+            "krep_gpu_format_matches": lambda: eng.format_matches(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, fmt, dst.data_ptr(),
+                                                                  obytes),
         }
         ms = {k: [] for k in calls}
         for rep in range(args.warmup + args.reps):
@@ -71,9 +76,9 @@ def main():
                 e1.synchronize()
                 if rep >= args.warmup:
                     ms[k].append(e0.elapsed_time(e1))
-        lines.append(f"{name}: text {n} B, {m} records, {L} lines ({int(q.capped_lines)} capped), out_bytes {nbytes}")
+        lines.append(f"{name}: text {n} B, {m} records, {L} lines ({int(q.capped_lines)} capped), out_bytes {nbytes}, -o out_bytes {obytes}")
         for k, v in ms.items():
-            moved = n + 16 * m + (2 * nbytes if k == "krep_gpu_format_lines" else 0)
+            moved = n + 16 * m + 2 * {"krep_gpu_format_lines": nbytes, "krep_gpu_format_matches": obytes}.get(k, 0)
             lines.append(f"  {k:26s} {statistics.median(v):9.3f} ms [{min(v):.3f} .. {max(v):.3f}]   floor {moved / bench.HBM_MEASURED_GBS / 1e6:7.3f} ms")
         plan.close()
         del pos, lineno, spans, first, dst
