@@ -483,8 +483,9 @@ void krep_gpu_set_result_order(int by_start);
  * Sherlock, er and lock prints "xx Sherlockerlock yy"); then text[cursor, line_end) and '\n'.  A record whose clamped match is
  * empty (end == start, or a start ON a '\n', where the reference CLI does not terminate) adds nothing of its own.
  * A list that is not ascending in start, or holds a record with start >= text_len or end < start, is refused (2) before any
- * byte of the text is read through it.  Colour escapes and shard windows (a line may cross a shard) are the host's business.
- * Both calls return 0, or 2 with krep_gpu_last_error() set, and synchronise `stream` before they return.  A NULL output pointer
+ * byte of the text is read through it.  Shard windows (a line may cross a shard) are the host's business; the strings of a
+ * coloured output go in through krep_gpu_format_lines_ex below.
+ * The calls return 0, or 2 with krep_gpu_last_error() set, and synchronise `stream` before they return.  A NULL output pointer
  * or a capacity of 0 is a size query.  A capacity that is too small sets `overflow` and returns 0: the sizes are valid, the
  * output buffers hold nothing usable. */
 typedef struct krep_gpu_lines_out
@@ -505,6 +506,34 @@ int krep_gpu_matching_lines(const void *d_text, size_t text_len, const match_pos
 int krep_gpu_format_lines(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
                           uint64_t max_lines, const char *prefix, size_t prefix_len, void *d_out, size_t out_capacity,
                           krep_gpu_lines_out_t *out, void *stream);
+/* The same lines with the caller's strings in them: what the reference prints under --color=always (krep.c:797-1071 with
+ * color_output_enabled).  Per emitted line:
+ *     prefix
+ *     per counted record (the first 2048 of the line) whose match, clamped to line_end, is not empty:
+ *         text[cursor, start) if start > cursor,  before_match,  text[start, clamped end),  after_match;  cursor = clamped end
+ *     text[cursor, line_end) if cursor < line_end,  line_close,  '\n'
+ * A record whose clamped match is empty adds nothing, no strings either; overlapping records repeat bytes, each inside its own
+ * pair of strings.  The strings are the caller's, the library knows no escape code: the reference uses prefix = filename colour,
+ * FILE, reset, separator colour, ":", text colour (the text colour alone without a filename), before_match = match colour,
+ * after_match = text colour, line_close = reset (krep.h:34-39).  With only `prefix` set the bytes are those of
+ * krep_gpu_format_lines.  Everything else is as for krep_gpu_format_lines: the record order, the refusal (2) of a list that is
+ * not ascending or out of range before the text is read, the size query, `overflow` with valid sizes, any alignment of d_text
+ * and d_out, nothing written outside [d_out, d_out + out_bytes), `stream` synchronised, n == 0 leaves everything 0.  A string
+ * of more than 2^20 bytes is refused (2). */
+typedef struct krep_gpu_line_format /* host strings, each may be NULL with length 0 */
+{
+    const char *prefix;
+    size_t prefix_len;
+    const char *before_match;
+    size_t before_match_len;
+    const char *after_match;
+    size_t after_match_len;
+    const char *line_close;
+    size_t line_close_len;
+} krep_gpu_line_format_t;
+int krep_gpu_format_lines_ex(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
+                             uint64_t max_lines, const krep_gpu_line_format_t *fmt /* NULL: all empty */, void *d_out,
+                             size_t out_capacity, krep_gpu_lines_out_t *out, void *stream);
 
 /* ---- the matches of a text in HBM, one per line: the reference's -o output (print_matching_items(), only-matching mode,
  * krep.c:517-793) ----

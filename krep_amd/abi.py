@@ -61,6 +61,16 @@ class LinesOut(C.Structure):
                 ("overflow", C.c_int)]
 
 
+class LineFormat(C.Structure):
+    """krep_gpu_line_format_t: the four host strings krep_gpu_format_lines_ex puts around a line and its matches"""
+    _fields_ = [("prefix", C.c_char_p), ("prefix_len", C.c_size_t), ("before_match", C.c_char_p), ("before_match_len", C.c_size_t),
+                ("after_match", C.c_char_p), ("after_match_len", C.c_size_t), ("line_close", C.c_char_p), ("line_close_len", C.c_size_t)]
+
+    def __init__(self, prefix: bytes = b"", before_match: bytes = b"", after_match: bytes = b"", line_close: bytes = b""):
+        super().__init__(prefix, len(prefix), before_match, len(before_match), after_match, len(after_match), line_close,
+                         len(line_close))
+
+
 class MatchFormat(C.Structure):
     """krep_gpu_match_format_t: the four host strings krep_gpu_format_matches puts around LINE and the match"""
     _fields_ = [("prefix", C.c_char_p), ("prefix_len", C.c_size_t), ("before_number", C.c_char_p), ("before_number_len", C.c_size_t),

@@ -23,10 +23,13 @@
 // line index and first record of the line (one sum, one running maximum); (4) per record its range and byte count, summed;
 // (5) the gather, dealt by OUTPUT bytes: a lane owns 16 aligned bytes of the output, a wave 1 KiB, the first record of a tile comes
 // from a binary search in the summed offsets.  A call reads the text once in (1), then only around the records and what it copies.
+// krep_gpu_format_lines_ex (--color=always: the caller's strings around the line and around every match) shares (1)-(3) and has a
+// size pass and a gather of its own, (4') and (5') below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <mutex>
+#include <vector>
 
 #include "../../include/krep_gpu.h"
 #include "kg_device.h"
@@ -206,30 +209,23 @@ __global__ __launch_bounds__(256) void ln_spans(const u64 *__restrict__ ls, cons
         first_record[emit] = n;
 }
 
-// (4) what record i adds to the output: bytes[i], and range[i] = flags | offset of its range in the text
-__global__ __launch_bounds__(256) void ln_sizes(const u64 *__restrict__ rec, const u64 *__restrict__ ls, const u64 *__restrict__ le,
-                                                const u64 *__restrict__ heads_before, const u64 *__restrict__ mark_before, u64 n,
-                                                u64 max_lines, u64 prefix_len, u64 *__restrict__ bytes, u64 *__restrict__ range,
-                                                u64 *__restrict__ ctr)
+// what record i adds to its line: ONE range [src, end) of the text; counted: it is among the first 2048 records of an emitted line
+struct LnExtent
 {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n)
-        return;
-    if (i == n)
-    {
-        bytes[n] = 0;
-        return;
-    }
+    bool counted, first, last, solid; // first / last counted record of its line; solid: its clamped match [start, cend) is not empty
+    u64 src, end;
+};
+__device__ __forceinline__ LnExtent ln_extent(const u64 *__restrict__ rec, const u64 *__restrict__ ls, const u64 *__restrict__ le,
+                                              const u64 *__restrict__ heads_before, const u64 *__restrict__ mark_before, u64 n,
+                                              u64 max_lines, u64 i, u64 *__restrict__ ctr)
+{
+    LnExtent x{};
     const LnRecord r = ln_record(ls, heads_before, mark_before, i);
     const u64 emit = min(heads_before[n], max_lines), rank = i - r.first;
     if (r.line < emit && rank == kLnCap)
         (void)__hip_atomic_fetch_add(ctr + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (r.line >= emit || rank >= kLnCap)
-    {
-        bytes[i] = 0;
-        range[i] = 0;
-        return;
-    }
+        return x;
     const u64 a = ls[i], z = le[i], s = rec[2 * i], cend = min(rec[2 * i + 1], z);
     const bool solid = s < cend; // its clamped match is not empty
     // the cursor in front of it: the clamped end of the nearest record before it on the line whose match is not empty (the record
@@ -244,11 +240,38 @@ __global__ __launch_bounds__(256) void ln_sizes(const u64 *__restrict__ rec, con
             break;
         }
     }
-    const bool last = rank == kLnCap - 1 || i + 1 == n || ls[i + 1] != a;
-    const u64 src = solid ? min(s, cur) : cur;
-    const u64 end = last ? z : (solid ? cend : cur);
-    bytes[i] = (rank == 0 ? prefix_len : 0ull) + (end - src) + (last ? 1ull : 0ull);
-    range[i] = src | (rank == 0 ? kLnFirst : 0ull) | (last ? kLnLast : 0ull);
+    x.counted = true;
+    x.first = rank == 0;
+    x.last = rank == kLnCap - 1 || i + 1 == n || ls[i + 1] != a;
+    x.solid = solid;
+    x.src = solid ? min(s, cur) : cur;
+    x.end = x.last ? z : (solid ? cend : cur);
+    return x;
+}
+
+// (4) what record i adds to the output: bytes[i], and range[i] = flags | offset of its range in the text
+__global__ __launch_bounds__(256) void ln_sizes(const u64 *__restrict__ rec, const u64 *__restrict__ ls, const u64 *__restrict__ le,
+                                                const u64 *__restrict__ heads_before, const u64 *__restrict__ mark_before, u64 n,
+                                                u64 max_lines, u64 prefix_len, u64 *__restrict__ bytes, u64 *__restrict__ range,
+                                                u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n)
+        return;
+    if (i == n)
+    {
+        bytes[n] = 0;
+        return;
+    }
+    const LnExtent x = ln_extent(rec, ls, le, heads_before, mark_before, n, max_lines, i, ctr);
+    if (!x.counted)
+    {
+        bytes[i] = 0;
+        range[i] = 0;
+        return;
+    }
+    bytes[i] = (x.first ? prefix_len : 0ull) + (x.end - x.src) + (x.last ? 1ull : 0ull);
+    range[i] = x.src | (x.first ? kLnFirst : 0ull) | (x.last ? kLnLast : 0ull);
 }
 
 // the largest r in [lo, hi] with off[r] <= pos (off[lo] <= pos)
@@ -365,6 +388,162 @@ __global__ __launch_bounds__(256) void ln_gather(const uint8_t *__restrict__ tex
 #pragma unroll
             for (u32 q = 0; q < 16; ++q)
                 if (q >= shift && o0 + (q - shift) < o1)
+                    out[o0 + (q - shift)] = (uint8_t)(w[q >> 2] >> (8 * (q & 3u)));
+        }
+    }
+}
+
+// ---- the same lines with the caller's strings in them (krep_gpu_format_lines_ex) ---------------------------------------------
+// A record's range of the text stays ONE range [src, end); before_match goes in at start - src and after_match at cend - src, the
+// prefix in front of a line's first record, line_close and '\n' behind its last.  So a record is at most seven pieces besides the
+// newline, and four of them are the strings, which lie behind one another in one small device buffer `fix`.
+constexpr u64 kLcSolid = 1ull << 61, kLcSrc = kLcSolid - 1; // one more flag in the range word
+
+struct LcFixed
+{
+    u32 prefix, before, after, close; // the lengths; in `fix`: prefix | before_match | after_match | line_close
+};
+
+// (4') bytes[i] and range[i] = flags | offset of the record's range in the text
+__global__ __launch_bounds__(256) void lc_sizes(const u64 *__restrict__ rec, const u64 *__restrict__ ls, const u64 *__restrict__ le,
+                                                const u64 *__restrict__ heads_before, const u64 *__restrict__ mark_before, u64 n,
+                                                u64 max_lines, const LcFixed f, u64 *__restrict__ bytes, u64 *__restrict__ range,
+                                                u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n)
+        return;
+    if (i == n)
+    {
+        bytes[n] = 0;
+        return;
+    }
+    const LnExtent x = ln_extent(rec, ls, le, heads_before, mark_before, n, max_lines, i, ctr);
+    if (!x.counted)
+    {
+        bytes[i] = 0;
+        range[i] = 0;
+        return;
+    }
+    bytes[i] = (x.first ? (u64)f.prefix : 0ull) + (x.end - x.src) + (x.solid ? (u64)f.before + f.after : 0ull) +
+               (x.last ? (u64)f.close + 1ull : 0ull);
+    range[i] = x.src | (x.first ? kLnFirst : 0ull) | (x.last ? kLnLast : 0ull) | (x.solid ? kLcSolid : 0ull);
+}
+
+// one record's output, counted from its first byte: prefix [0, e0), text [e0, e1), before_match [e1, e2), the match [e2, e3),
+// after_match [e3, e4), text [e4, e5), line_close [e5, e6), '\n' at e6 if the record closes its line.  Lines of 1 GiB and more are
+// legal: the ends are 64-bit.  The three text pieces are one range: byte k of them is text[src + k - (string bytes in front of k)]
+struct LcItem
+{
+    u64 src, e1, e2, e3, e4, e5, e6, total;
+    u32 e0;
+};
+__device__ __forceinline__ LcItem lc_item(const u64 *__restrict__ rec, const u64 *__restrict__ le, const u64 *__restrict__ off,
+                                          const u64 *__restrict__ range, const LcFixed f, u64 r)
+{
+    LcItem it;
+    const u64 w = range[r];
+    const bool first = w & kLnFirst, last = w & kLnLast, solid = w & kLcSolid;
+    it.total = off[r + 1] - off[r];
+    it.src = w & kLcSrc;
+    u64 t1 = 0, t2 = 0;
+    if (solid)
+    {
+        const uint4 p = *reinterpret_cast<const uint4 *>(rec + 2 * r);
+        const u64 s = ((u64)p.y << 32) | p.x, e = min(((u64)p.w << 32) | p.z, le[r]);
+        t1 = s - it.src;
+        t2 = e - s;
+    }
+    it.e0 = first ? f.prefix : 0u;
+    it.e1 = it.e0 + t1;
+    it.e2 = it.e1 + (solid ? f.before : 0u);
+    it.e3 = it.e2 + t2;
+    it.e4 = it.e3 + (solid ? f.after : 0u);
+    it.e6 = it.total - (last ? 1u : 0u);
+    it.e5 = it.e6 - (last ? f.close : 0u);
+    return it;
+}
+// its byte k (k < total)
+__device__ __forceinline__ u32 lc_byte(const uint8_t *__restrict__ text, const uint8_t *__restrict__ fix, const LcFixed f, const LcItem &it,
+                                       u64 k)
+{
+    if (k < it.e2)
+    {
+        if (k < it.e0)
+            return fix[k];
+        return k < it.e1 ? (u32)text[it.src + (k - it.e0)] : (u32)fix[f.prefix + (k - it.e1)];
+    }
+    if (k < it.e4)
+        return k < it.e3 ? (u32)text[it.src + (k - it.e2) + (it.e1 - it.e0)] : (u32)fix[f.prefix + f.before + (k - it.e3)];
+    if (k < it.e5)
+        return text[it.src + (k - it.e4) + (it.e1 - it.e0) + (it.e3 - it.e2)];
+    return k < it.e6 ? (u32)fix[f.prefix + f.before + f.after + (k - it.e5)] : (u32)'\n';
+}
+
+// (5') as ln_gather: chunk c is the 16 aligned bytes at (out - misalign) + 16 c, i.e. output offsets [16 c - misalign, + 16)
+__global__ __launch_bounds__(256) void lc_gather(const uint8_t *__restrict__ text, const u64 *__restrict__ rec, const u64 *__restrict__ le,
+                                                 const u64 *__restrict__ off, const u64 *__restrict__ range, u64 n,
+                                                 const uint8_t *__restrict__ fix, const LcFixed f, uint8_t *__restrict__ out, u64 total,
+                                                 u32 misalign, u64 nchunks)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u64 wid = (u64)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (u64)gridDim.x * (blockDim.x >> 6);
+    for (u64 c0 = wid * 64; c0 < nchunks; c0 += nw * 64)
+    {
+        // the records of the wave's 1 KiB tile
+        const u64 tile_lo = c0 ? c0 * 16 - misalign : 0ull, tile_hi = min((c0 + 64) * 16 - misalign, total) - 1;
+        const u64 r_lo = ln_find(off, 0, n - 1, tile_lo), r_hi = ln_find(off, r_lo, n - 1, tile_hi);
+        const u64 c = c0 + lane;
+        if (c >= nchunks)
+            continue;
+        const u64 o0 = c ? c * 16 - misalign : 0ull, o1 = min((c + 1) * 16 - misalign, total);
+        const bool whole = o1 - o0 == 16;
+        u64 r = ln_find(off, r_lo, r_hi, o0);
+        LcItem it = lc_item(rec, le, off, range, f, r);
+        u64 k = o0 - off[r];
+        if (whole)
+        {
+            // wholly inside one of the three text pieces: `skip` string bytes lie in front of it
+            u64 skip = kLnNone;
+            if (k >= it.e0 && k + 16 <= it.e1)
+                skip = it.e0;
+            else if (k >= it.e2 && k + 16 <= it.e3)
+                skip = it.e2 - (it.e1 - it.e0);
+            else if (k >= it.e4 && k + 16 <= it.e5)
+                skip = it.e4 - (it.e1 - it.e0) - (it.e3 - it.e2);
+            if (skip != kLnNone)
+            {
+                *reinterpret_cast<uint4 *>(out + o0) = load_unaligned<uint4>(text + it.src + (k - skip));
+                continue;
+            }
+        }
+        u32 w[4] = {0, 0, 0, 0};
+        const u32 shift = (u32)(o0 + misalign - c * 16); // bytes of the chunk in front of the output (chunk 0 only)
+        const u32 cnt = (u32)(o1 - o0);
+#pragma unroll
+        for (u32 q = 0; q < 16; ++q)
+        {
+            if (q >= shift && q - shift < cnt)
+            {
+                if (k >= it.total) // the record is used up: the next one that adds bytes
+                {
+                    ++r;
+                    if (off[r + 1] == off[r])
+                        r = ln_find(off, r, n - 1, o0 + (q - shift));
+                    it = lc_item(rec, le, off, range, f, r);
+                    k = 0;
+                }
+                w[q >> 2] |= lc_byte(text, fix, f, it, k) << (8 * (q & 3u));
+                ++k;
+            }
+        }
+        if (whole)
+            *reinterpret_cast<uint4 *>(out + o0) = make_uint4(w[0], w[1], w[2], w[3]);
+        else
+        {
+#pragma unroll
+            for (u32 q = 0; q < 16; ++q)
+                if (q >= shift && q - shift < cnt)
                     out[o0 + (q - shift)] = (uint8_t)(w[q >> 2] >> (8 * (q & 3u)));
         }
     }
@@ -519,6 +698,73 @@ extern "C" int krep_gpu_format_lines(const void *d_text, size_t text_len, const 
     const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
     hipLaunchKernelGGL(ln_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)off, (const u64 *)w.range, (u64)n,
                        (const uint8_t *)w.prefix, (u32)prefix_len, (uint8_t *)d_out, bytes, misalign, nchunks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int krep_gpu_format_lines_ex(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
+                                        uint64_t max_lines, const krep_gpu_line_format_t *fmt, void *d_out, size_t out_capacity,
+                                        krep_gpu_lines_out_t *out, void *stream)
+{
+    const char *who = "krep_gpu_format_lines_ex";
+    if (ln_check(who, d_text, d_positions, n, out))
+        return 2;
+    const krep_gpu_line_format_t none{};
+    const krep_gpu_line_format_t &m = fmt ? *fmt : none;
+    const char *str[4] = {m.prefix, m.before_match, m.after_match, m.line_close};
+    const size_t len[4] = {m.prefix_len, m.before_match_len, m.after_match_len, m.line_close_len};
+    for (int k = 0; k < 4; ++k)
+    {
+        if (len[k] && !str[k])
+            return fail("%s: a string of the format is NULL", who);
+        if (len[k] >> 20)
+            return fail("%s: a format string of %zu bytes", who, len[k]);
+    }
+    if (!n)
+        return 0;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(g_fmt_mu);
+    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the strings behind one another, alive until the copy has run
+    h_fix.clear();
+    for (int k = 0; k < 4; ++k)
+        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
+    const LcFixed f{(u32)len[0], (u32)len[1], (u32)len[2], (u32)len[3]};
+    LnWork w;
+    if (ln_analyse((const uint8_t *)d_text, text_len, (const u64 *)d_positions, n, h_fix.size(), w, st))
+        return 2;
+    if (!h_fix.empty())
+        HIPCHK(hipMemcpyAsync(w.prefix, h_fix.data(), h_fix.size(), hipMemcpyHostToDevice, st));
+    u64 *off = w.ls; // the line starts are not read again behind lc_sizes: their buffer takes the summed byte counts
+    hipLaunchKernelGGL(lc_sizes, dim3((u32)((n + 1 + 255) / 256)), dim3(256), 0, st, (const u64 *)d_positions, (const u64 *)w.ls,
+                       (const u64 *)w.le, (const u64 *)w.heads_before, (const u64 *)w.mark_before, (u64)n, (u64)max_lines, f, w.a,
+                       w.range, w.ctr);
+    scan_exclusive(w.a, n + 1, off, w.sums, false, st);
+    HIPCHK(hipGetLastError());
+    u64 h[2] = {0, 0}, total = 0, bytes = 0;
+    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bytes, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h, w.ctr, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[0])
+        return fail("%s: the record list is not ascending in start, or a record lies outside the text", who);
+    out->lines = std::min<u64>(total, max_lines);
+    out->lines_total = total;
+    out->out_bytes = bytes;
+    out->capped_lines = h[1];
+    if (!d_out || !out_capacity || !bytes)
+        return 0;
+    if (bytes > out_capacity)
+    {
+        out->overflow = 1;
+        return 0;
+    }
+    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
+    const u64 nchunks = (bytes + misalign + 15) / 16;
+    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
+    hipLaunchKernelGGL(lc_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)d_positions, (const u64 *)w.le,
+                       (const u64 *)off, (const u64 *)w.range, (u64)n, (const uint8_t *)w.prefix, f, (uint8_t *)d_out, bytes, misalign,
+                       nchunks);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     return 0;

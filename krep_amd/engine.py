@@ -102,6 +102,10 @@ class Engine:
             L.krep_gpu_format_lines.restype = C.c_int
             L.krep_gpu_format_lines.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t,
                                                 C.c_void_p, C.c_size_t, C.POINTER(abi.LinesOut), C.c_void_p]
+        if hasattr(L, "krep_gpu_format_lines_ex"):
+            L.krep_gpu_format_lines_ex.restype = C.c_int
+            L.krep_gpu_format_lines_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(abi.LineFormat),
+                                                   C.c_void_p, C.c_size_t, C.POINTER(abi.LinesOut), C.c_void_p]
         if hasattr(L, "krep_gpu_format_matches"):
             L.krep_gpu_format_matches.restype = C.c_int
             L.krep_gpu_format_matches.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(abi.MatchFormat),
@@ -393,6 +397,17 @@ class Engine:
             raise KrepGpuError("krep_gpu_format_lines failed: " + self.last_error())
         return out
 
+    def format_lines_ex(self, d_text: int, text_len: int, d_positions: int, n: int, max_lines: int = abi.SIZE_MAX,
+                        fmt: "abi.LineFormat | None" = None, d_out: int = 0, out_capacity: int = 0, stream: int = 0) -> "abi.LinesOut":
+        """krep_gpu_format_lines_ex(): the same lines with the caller's strings in them (--color=always), into d_out.  fmt: prefix,
+        before_match, after_match, line_close (None: none).  d_out = 0 asks for .out_bytes."""
+        out = abi.LinesOut()
+        if self.lib.krep_gpu_format_lines_ex(C.c_void_p(d_text), text_len, C.c_void_p(d_positions), n, max_lines,
+                                             C.byref(fmt) if fmt is not None else None, C.c_void_p(d_out) if d_out else None,
+                                             out_capacity, C.byref(out), C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_format_lines_ex failed: " + self.last_error())
+        return out
+
     # ---- the matches themselves, one per line (print_matching_items(), only-matching mode, krep.c:517-793) ----
     def format_matches(self, d_text: int, text_len: int, d_positions: int, n: int, max_items: int = abi.SIZE_MAX,
                        fmt: "abi.MatchFormat | None" = None, d_out: int = 0, out_capacity: int = 0, stream: int = 0) -> "abi.MatchesOut":
@@ -492,11 +507,12 @@ class Plan:
             raise KrepGpuError("krep_gpu_scan_device failed: " + self.eng.last_error())
         return out
 
-    def grep_lines(self, d_text: int, n: int, filename=None, max_count=None, stream: int = 0) -> bytes:
+    def grep_lines(self, d_text: int, n: int, filename=None, max_count=None, stream: int = 0, color=False) -> bytes:
         """What `krep [-m N] PATTERN FILE` prints (colour off) for the n bytes at d_text: the scan with records, the cut to the
         first max_count records in emission order (search_file()), the (start, end) order for a multi-pattern list, and the
         lines from krep_gpu_format_lines.  filename: str / bytes in front of every line ("FILE:"), None as for search_string().
-        max_count: None takes the plan's.  Device buffers come from torch (the current device)."""
+        max_count: None takes the plan's.  color=True: what `krep --color=always` prints (`--color=always -s` without a filename),
+        from krep_gpu_format_lines_ex with the strings of line_format().  Device buffers come from torch (the current device)."""
         import torch
         eng = self.eng
         limit = int(self.params.s.max_count)
@@ -517,13 +533,25 @@ class Plan:
             return b""
         if self.params.s.num_patterns > 1:
             eng.order_by_start(pos.data_ptr(), m, n, stream)
-        prefix = b"" if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode()) + b":"
-        guess = m * (len(prefix) + 256) + 4096  # one call when the lines are short; the sizes it reports serve the second
+        name = None if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
+        if color:
+            fmt = line_format(name, True)
+            extra = fmt.prefix_len + fmt.line_close_len + fmt.before_match_len + fmt.after_match_len  # (at most a line per record)
+
+            def call(d_out, capacity):
+                return eng.format_lines_ex(d_text, n, pos.data_ptr(), m, limit, fmt, d_out, capacity, stream)
+        else:
+            prefix = b"" if name is None else name + b":"
+            extra = len(prefix)
+
+            def call(d_out, capacity):
+                return eng.format_lines(d_text, n, pos.data_ptr(), m, limit, prefix, d_out, capacity, stream)
+        guess = m * (extra + 256) + 4096  # one call when the lines are short; the sizes it reports serve the second
         buf = torch.empty(guess, dtype=torch.uint8, device="cuda")
-        res = eng.format_lines(d_text, n, pos.data_ptr(), m, limit, prefix, buf.data_ptr(), guess, stream)
+        res = call(buf.data_ptr(), guess)
         if res.overflow:
             buf = torch.empty(int(res.out_bytes), dtype=torch.uint8, device="cuda")
-            res = eng.format_lines(d_text, n, pos.data_ptr(), m, limit, prefix, buf.data_ptr(), int(res.out_bytes), stream)
+            res = call(buf.data_ptr(), int(res.out_bytes))
             assert not res.overflow
         return buf[: int(res.out_bytes)].cpu().numpy().tobytes()
 
@@ -622,6 +650,7 @@ class Plan:
 # the escape codes of the reference's coloured output (data: krep.h:34-39)
 COLOR_RESET, COLOR_FILENAME, COLOR_SEPARATOR = b"\033[0m", b"\033[1;38;5;81m", b"\033[38;5;244m"
 COLOR_LINE_NUMBER, COLOR_MATCH = b"\033[1;38;5;111m", b"\033[1;38;5;222m"
+COLOR_TEXT = b"\033[38;5;252m"
 
 
 def match_format(filename: "bytes | None" = None, color: bool = False) -> "abi.MatchFormat":
@@ -630,6 +659,14 @@ def match_format(filename: "bytes | None" = None, color: bool = False) -> "abi.M
         return abi.MatchFormat(b"" if filename is None else filename + b":")
     prefix = b"" if filename is None else COLOR_FILENAME + filename + COLOR_RESET + COLOR_SEPARATOR + b":"
     return abi.MatchFormat(prefix, COLOR_LINE_NUMBER, COLOR_RESET + COLOR_MATCH, COLOR_RESET)
+
+
+def line_format(filename: "bytes | None" = None, color: bool = False) -> "abi.LineFormat":
+    """the strings of the default line output around a line and its matches (krep.c:940-1018): filename None prints no FILE: in front"""
+    if not color:
+        return abi.LineFormat(b"" if filename is None else filename + b":")
+    prefix = COLOR_TEXT if filename is None else COLOR_FILENAME + filename + COLOR_RESET + COLOR_SEPARATOR + b":" + COLOR_TEXT
+    return abi.LineFormat(prefix, COLOR_MATCH, COLOR_TEXT, COLOR_RESET)
 
 
 _engine = None

@@ -1,5 +1,5 @@
-"""The matching lines and the -o output on the device, timed: krep_gpu_matching_lines, krep_gpu_format_lines and
-krep_gpu_format_matches beside krep_gpu_line_numbers (the in-tree primitive of the same shape) on the same record list and text,
+"""The matching lines and the -o output on the device, timed: krep_gpu_matching_lines, krep_gpu_format_lines, its coloured
+sibling krep_gpu_format_lines_ex (the reference's --color=always strings) and krep_gpu_format_matches beside krep_gpu_line_numbers (the in-tree primitive of the same shape) on the same record list and text,
 alternating, in ONE process with the text resident.
 Events around the calls, warmed up.  Beside them the floor from the bytes moved: the text once + 16 B per record + 2 x out_bytes
 at the measured streaming rate (bench.HBM_MEASURED_GBS).
@@ -56,13 +56,17 @@ def main():
         first = torch.empty(L + 1, dtype=torch.int64, device="cuda")
         fmt = abi.MatchFormat(prefix)
         obytes = int(eng.format_matches(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, fmt).out_bytes)
-        dst = torch.empty(max(nbytes, obytes) + 64, dtype=torch.uint8, device="cuda")
+        cfmt = krep_amd.engine.line_format(prefix[:-1], True)
+        cbytes = int(eng.format_lines_ex(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, cfmt).out_bytes)
+        dst = torch.empty(max(nbytes, obytes, cbytes) + 64, dtype=torch.uint8, device="cuda")
         calls = {
             "krep_gpu_line_numbers": lambda: eng.line_numbers(buf.data_ptr(), n, pos.data_ptr(), m, lineno.data_ptr()),
             "krep_gpu_matching_lines": lambda: eng.matching_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, spans.data_ptr(),
                                                                   first.data_ptr(), L),
             "krep_gpu_format_lines": lambda: eng.format_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, prefix, dst.data_ptr(),
                                                               nbytes),
+            "krep_gpu_format_lines_ex": lambda: eng.format_lines_ex(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, cfmt,
+                                                                    dst.data_ptr(), cbytes),
             "krep_gpu_format_matches": lambda: eng.format_matches(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, fmt, dst.data_ptr(),
                                                                   obytes),
         }
@@ -76,9 +80,10 @@ def main():
                 e1.synchronize()
                 if rep >= args.warmup:
                     ms[k].append(e0.elapsed_time(e1))
-        lines.append(f"{name}: text {n} B, {m} records, {L} lines ({int(q.capped_lines)} capped), out_bytes {nbytes}, -o out_bytes {obytes}")
+        lines.append(f"{name}: text {n} B, {m} records, {L} lines ({int(q.capped_lines)} capped), out_bytes {nbytes}, "
+                     f"coloured out_bytes {cbytes}, -o out_bytes {obytes}")
         for k, v in ms.items():
-            moved = n + 16 * m + 2 * {"krep_gpu_format_lines": nbytes, "krep_gpu_format_matches": obytes}.get(k, 0)
+            moved = n + 16 * m + 2 * {"krep_gpu_format_lines": nbytes, "krep_gpu_format_lines_ex": cbytes, "krep_gpu_format_matches": obytes}.get(k, 0)
             lines.append(f"  {k:26s} {statistics.median(v):9.3f} ms [{min(v):.3f} .. {max(v):.3f}]   floor {moved / bench.HBM_MEASURED_GBS / 1e6:7.3f} ms")
         plan.close()
         del pos, lineno, spans, first, dst
