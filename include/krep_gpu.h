@@ -483,8 +483,9 @@ void krep_gpu_set_result_order(int by_start);
  * Sherlock, er and lock prints "xx Sherlockerlock yy"); then text[cursor, line_end) and '\n'.  A record whose clamped match is
  * empty (end == start, or a start ON a '\n', where the reference CLI does not terminate) adds nothing of its own.
  * A list that is not ascending in start, or holds a record with start >= text_len or end < start, is refused (2) before any
- * byte of the text is read through it.  Shard windows (a line may cross a shard) are the host's business; the strings of a
- * coloured output go in through krep_gpu_format_lines_ex below.
+ * byte of the text is read through it.  These calls take the WHOLE text; a text in pieces (a shard, a streamed buffer: a line may
+ * cross a cut) goes through krep_gpu_format_lines_window below.  The strings of a coloured output go in through
+ * krep_gpu_format_lines_ex below.
  * The calls return 0, or 2 with krep_gpu_last_error() set, and synchronise `stream` before they return.  A NULL output pointer
  * or a capacity of 0 is a size query.  A capacity that is too small sets `overflow` and returns 0: the sizes are valid, the
  * output buffers hold nothing usable. */
@@ -535,9 +536,61 @@ int krep_gpu_format_lines_ex(const void *d_text, size_t text_len, const match_po
                              uint64_t max_lines, const krep_gpu_line_format_t *fmt /* NULL: all empty */, void *d_out,
                              size_t out_capacity, krep_gpu_lines_out_t *out, void *stream);
 
+/* ---- the same lines for a text in pieces: one call per WINDOW, the outputs concatenate ----
+ * The window contract of the scans (start ownership + halo) for the line output.  `fmt`, the bytes of an emitted line, the cursor
+ * rule, the clamp to line_end, the 2048-records-per-line cap and capped_lines, "an empty clamped match adds nothing" and "at most
+ * max_lines lines" are those of krep_gpu_format_lines_ex.
+ * Buffer: d_text[0 .. text_len) holds text[global_base .. global_base + text_len); it ends the text when global_base + text_len ==
+ *   global_len.
+ * Records: GLOBAL offsets, as krep_gpu_scan_device_ex writes them with a global_base, in (start, end) order.  A list that is not
+ *   ascending in start, or holds a record with start outside [global_base, global_base + text_len) or end < start, is refused (2)
+ *   before any byte of the text is read through it: the rule of the whole-text calls.
+ * Line start: one past the last '\n' in [global_base, start).  With no such newline it is 0 when global_base == 0; otherwise the
+ *   line starts in front of the buffer, is not owned, and the record is passed over silently.
+ * Ownership: the call owns the lines with line_start in [own_lo, own_hi); records of other lines are passed over, they are a
+ *   neighbour's.  So the ONE byte in front of own_lo is all the left context a window needs.  A record that starts ON a '\n'
+ *   belongs to the line that newline ends.
+ * Line end: the first '\n' at or after line_start inside the buffer.  An owned matching line is COMPLETE when that newline exists and
+ *   lies in front of records_hi (the list holds every record with start < records_hi, so all of the line's); or when the buffer ends
+ *   the text and records_hi == global_len: then line_end = global_len serves a last line without a newline.  Otherwise the line is
+ *   incomplete — at most one can be, the last owned one.  It is not emitted and not counted in lines / lines_total.  If it would have
+ *   been emitted (its index among the owned matching lines is < max_lines) it is reported: incomplete_line_start1 = its global
+ *   line_start + 1, incomplete_first_record = the index of its first record.  The caller submits it again as a window of its own
+ *   (own_lo = line_start, own_hi = line_start + 1) with a longer buffer.
+ *   What the call cannot see: an owned line that outruns the buffer and whose FIRST record lies at or behind records_hi (no record
+ *   of it is in the list).  That can only be the line that is open at records_hi; a caller that cuts its halos short looks for it.
+ * Window: global_base <= own_lo <= own_hi <= records_hi <= global_base + text_len <= global_len, and own_lo > global_base unless
+ *   both are 0; anything else is refused (2).
+ * Invariant: cut a text at 0 = c0 < c1 < ... < ck = global_len, give window [ci, ci+1) a buffer from ci - 1 (or 0) far enough to the
+ *   right that nothing is incomplete, state records_hi truthfully and pass max_lines on as what is left: the outputs, concatenated,
+ *   are the bytes of krep_gpu_format_lines_ex on the whole text, and lines, lines_total and capped_lines sum to its values.
+ * -m: cutting the record list to its first max_count records in EMISSION order is a property of the whole list; it stays with the
+ *   caller, as it does for the whole-text calls.
+ * As for krep_gpu_format_lines_ex: d_out == NULL or out_capacity == 0 is a size query, `overflow` comes with valid sizes, d_text and
+ *   d_out may have any alignment, nothing is written outside [d_out, d_out + out_bytes), `stream` is synchronised on return, a
+ *   string of more than 2^20 bytes and n >= 2^40 are refused (2), n == 0 leaves everything 0 (after the window has been checked). */
+typedef struct krep_gpu_lines_window
+{
+    size_t global_base;    /* offset in the text of d_text[0]                                                      */
+    size_t global_len;     /* length of the whole text                                                             */
+    size_t own_lo, own_hi; /* global offsets: the call owns the lines whose line_start is in [own_lo, own_hi)      */
+    size_t records_hi;     /* the record list is complete for every start < records_hi (global)                    */
+} krep_gpu_lines_window_t;
+typedef struct krep_gpu_lines_window_out
+{
+    krep_gpu_lines_out_t lines;       /* lines, lines_total, out_bytes, capped_lines, overflow: of the OWNED, COMPLETE lines */
+    uint64_t incomplete_line_start1;  /* global line_start + 1 of the owned matching line that could not be completed (0: none) */
+    uint64_t incomplete_first_record; /* index of its first record in the list (n when none)                                    */
+} krep_gpu_lines_window_out_t;
+int krep_gpu_format_lines_window(const void *d_text, size_t text_len, const krep_gpu_lines_window_t *win,
+                                 const match_position_t *d_positions, uint64_t n, uint64_t max_lines,
+                                 const krep_gpu_line_format_t *fmt /* NULL: all empty */, void *d_out, size_t out_capacity,
+                                 krep_gpu_lines_window_out_t *out, void *stream);
+
 /* ---- the matches of a text in HBM, one per line: the reference's -o output (print_matching_items(), only-matching mode,
  * krep.c:517-793) ----
- * Input as above: the whole text and its n records in (start, end) order, n being the reference's result->count (search_file() has
+ * Input as for the whole-text line calls: the whole text (shard windows of this form are the host's business) and its n records in
+ * (start, end) order, n being the reference's result->count (search_file() has
  * cut the list to its first max_count records in emission order and ordered it).  For record i < min(n, max_items), in list order:
  *     prefix  before_number  LINE ':'  after_number  MATCH  after_match  '\n'
  * The four strings are the caller's ("FILE:" and nothing else without colour; the escape codes of krep.h:34-39 with it: the library

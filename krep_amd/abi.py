@@ -71,6 +71,17 @@ class LineFormat(C.Structure):
                          len(line_close))
 
 
+class LinesWindow(C.Structure):
+    """krep_gpu_lines_window_t: which part of a text the buffer of krep_gpu_format_lines_window holds and which lines the call owns"""
+    _fields_ = [("global_base", C.c_size_t), ("global_len", C.c_size_t), ("own_lo", C.c_size_t), ("own_hi", C.c_size_t),
+                ("records_hi", C.c_size_t)]
+
+
+class LinesWindowOut(C.Structure):
+    """krep_gpu_lines_window_out_t: LinesOut of the owned, complete lines, and the owned line that could not be completed"""
+    _fields_ = [("lines", LinesOut), ("incomplete_line_start1", C.c_uint64), ("incomplete_first_record", C.c_uint64)]
+
+
 class MatchFormat(C.Structure):
     """krep_gpu_match_format_t: the four host strings krep_gpu_format_matches puts around LINE and the match"""
     _fields_ = [("prefix", C.c_char_p), ("prefix_len", C.c_size_t), ("before_number", C.c_char_p), ("before_number_len", C.c_size_t),

@@ -24,7 +24,9 @@
 // (5) the gather, dealt by OUTPUT bytes: a lane owns 16 aligned bytes of the output, a wave 1 KiB, the first record of a tile comes
 // from a binary search in the summed offsets.  A call reads the text once in (1), then only around the records and what it copies.
 // krep_gpu_format_lines_ex (--color=always: the caller's strings around the line and around every match) shares (1)-(3) and has a
-// size pass and a gather of its own, (4') and (5') below.
+// size pass and a gather of its own, (4') and (5') below.  krep_gpu_format_lines_window (the same lines for a WINDOW of a text: the
+// buffer may begin and end inside a line, the call owns the lines that START in [own_lo, own_hi)) shares (1), the sums and (5') and
+// has (2"), (3") and (4") of its own, further below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -549,6 +551,149 @@ __global__ __launch_bounds__(256) void lc_gather(const uint8_t *__restrict__ tex
     }
 }
 
+// ---- the same lines for a window of a text (krep_gpu_format_lines_window) ------------------------------------------------------
+// The buffer holds text[global_base, global_base + text_len) and may begin and end inside a line; the records carry GLOBAL offsets.
+// A record is KEPT when its line is owned (line_start in [own_lo, own_hi), known from a newline inside the buffer or from
+// global_base == 0) and complete (its newline lies in front of records_hi, or the buffer ends the text and the list with it).
+// Everything behind (2") works on buffer-relative offsets: (2") leaves a relative copy of the list and ls = kLnNone for a record
+// that is passed over, (3") opens lines at kept records only, (4") gives a passed-over record zero bytes — so the sums and
+// lc_gather run as they are, on a list whose passed-over records add nothing, without compaction.
+constexpr u32 kLwFirst = 2, kLwStart1 = 3; // counter block: [2] least index of a record on the owned line that is incomplete (kLnNone:
+                                           // none), [3] that line's global line_start + 1
+
+struct LwWindow
+{
+    u64 base, own_lo, own_hi, records_hi; // global_base; the other three RELATIVE to it
+    u32 ends_text;                        // the buffer ends the text and the list is complete up to there
+};
+
+// (2") line bounds of every record inside the buffer, ownership and completeness; refuses as ln_bounds does
+__global__ __launch_bounds__(256) void lw_bounds(const uint8_t *__restrict__ text, u64 text_len, const u64 *__restrict__ rec, u64 n,
+                                                 const LwWindow w, const u64 *__restrict__ prev1, const u64 *__restrict__ next_rev, u64 nb,
+                                                 u64 *__restrict__ loc, u64 *__restrict__ ls, u64 *__restrict__ le, u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u64 open = kLnNone, open_start1 = 0; // i, if record i lies on the owned line that is incomplete
+    if (i < n)
+    {
+        const uint4 r = *reinterpret_cast<const uint4 *>(rec + 2 * i);
+        const u64 sg = ((u64)r.y << 32) | r.x, eg = ((u64)r.w << 32) | r.z;
+        u64 a = kLnNone, z = 0, s = 0, e = 0;
+        if (sg < w.base || sg - w.base >= text_len || eg < sg || (i > 0 && rec[2 * (i - 1)] > sg))
+            ctr[0] = 1; // (every writer stores the same value)
+        else
+        {
+            s = sg - w.base;
+            e = eg - w.base;
+            const u64 b = s / kLnBlock, base = b * kLnBlock, lim = min(base + kLnBlock, text_len);
+            u64 p = s;
+            while (p >= base + 16)
+            {
+                const u32 m = nl_mask16(load_unaligned<uint4>(text + p - 16));
+                if (m)
+                {
+                    a = p - 16 + (32u - (u32)__clz(m));
+                    break;
+                }
+                p -= 16;
+            }
+            if (a == kLnNone)
+            {
+                for (; p > base; --p)
+                    if (text[p - 1] == '\n')
+                        break;
+                a = p > base ? p : prev1[b];
+                if (a == 0 && w.base != 0)
+                    a = kLnNone; // no newline in front of it inside the buffer: the line starts in front of the buffer
+            }
+            u64 q = s;
+            z = kLnNone;
+            while (q + 16 <= lim)
+            {
+                const u32 m = nl_mask16(load_unaligned<uint4>(text + q));
+                if (m)
+                {
+                    z = q + (u32)__ffs(m) - 1u;
+                    break;
+                }
+                q += 16;
+            }
+            if (z == kLnNone)
+            {
+                for (; q < lim; ++q)
+                    if (text[q] == '\n')
+                        break;
+                if (q < lim)
+                    z = q;
+                else
+                {
+                    const u64 nx = next_rev[nb - 1 - b];
+                    z = nx ? ~nx : text_len; // text_len: no newline up to the buffer's end
+                }
+            }
+            if (a == kLnNone || a < w.own_lo || a >= w.own_hi)
+                a = kLnNone; // a neighbour's line
+            else if (z < text_len ? z >= w.records_hi : !w.ends_text)
+            {
+                open = i;
+                open_start1 = w.base + a + 1;
+                a = kLnNone;
+            }
+        }
+        ls[i] = a;
+        le[i] = z;
+        *reinterpret_cast<uint4 *>(loc + 2 * i) = make_uint4((u32)s, (u32)(s >> 32), (u32)e, (u32)(e >> 32));
+    }
+    u64 m = open;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        m = min(m, (u64)__shfl_xor((unsigned long long)m, o));
+    if (m != kLnNone && open == m)
+    {
+        (void)__hip_atomic_fetch_min(ctr + kLwFirst, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ctr[kLwStart1] = open_start1; // (at most one line is incomplete: every writer stores the same value)
+    }
+}
+
+// (3") as ln_heads, but only a kept record opens a line
+__global__ __launch_bounds__(256) void lw_heads(const u64 *__restrict__ ls, u64 n, u64 *__restrict__ head, u64 *__restrict__ mark)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n)
+        return;
+    const bool h = i < n && ls[i] != kLnNone && (i == 0 || ls[i] != ls[i - 1]);
+    head[i] = h ? 1ull : 0ull;
+    mark[i] = h ? i + 1 : 0ull;
+}
+
+// (4") as lc_sizes on the relative list; a record that is passed over adds nothing
+__global__ __launch_bounds__(256) void lw_sizes(const u64 *__restrict__ loc, const u64 *__restrict__ ls, const u64 *__restrict__ le,
+                                                const u64 *__restrict__ heads_before, const u64 *__restrict__ mark_before, u64 n,
+                                                u64 max_lines, const LcFixed f, u64 *__restrict__ bytes, u64 *__restrict__ range,
+                                                u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n)
+        return;
+    if (i == n)
+    {
+        bytes[n] = 0;
+        return;
+    }
+    LnExtent x{};
+    if (ls[i] != kLnNone)
+        x = ln_extent(loc, ls, le, heads_before, mark_before, n, max_lines, i, ctr);
+    if (!x.counted)
+    {
+        bytes[i] = 0;
+        range[i] = 0;
+        return;
+    }
+    bytes[i] = (x.first ? (u64)f.prefix : 0ull) + (x.end - x.src) + (x.solid ? (u64)f.before + f.after : 0ull) +
+               (x.last ? (u64)f.close + 1ull : 0ull);
+    range[i] = x.src | (x.first ? kLnFirst : 0ull) | (x.last ? kLnLast : 0ull) | (x.solid ? kLcSolid : 0ull);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------
 struct LnWork
 {
@@ -763,6 +908,122 @@ extern "C" int krep_gpu_format_lines_ex(const void *d_text, size_t text_len, con
     const u64 nchunks = (bytes + misalign + 15) / 16;
     const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
     hipLaunchKernelGGL(lc_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)d_positions, (const u64 *)w.le,
+                       (const u64 *)off, (const u64 *)w.range, (u64)n, (const uint8_t *)w.prefix, f, (uint8_t *)d_out, bytes, misalign,
+                       nchunks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int krep_gpu_format_lines_window(const void *d_text, size_t text_len, const krep_gpu_lines_window_t *win,
+                                            const match_position_t *d_positions, uint64_t n, uint64_t max_lines,
+                                            const krep_gpu_line_format_t *fmt, void *d_out, size_t out_capacity,
+                                            krep_gpu_lines_window_out_t *out, void *stream)
+{
+    const char *who = "krep_gpu_format_lines_window";
+    if (!out)
+        return fail("%s: out is NULL", who);
+    *out = krep_gpu_lines_window_out_t{};
+    if (ln_check(who, d_text, d_positions, n, &out->lines))
+        return 2;
+    const krep_gpu_line_format_t none{};
+    const krep_gpu_line_format_t &m = fmt ? *fmt : none;
+    const char *str[4] = {m.prefix, m.before_match, m.after_match, m.line_close};
+    const size_t len[4] = {m.prefix_len, m.before_match_len, m.after_match_len, m.line_close_len};
+    for (int k = 0; k < 4; ++k)
+    {
+        if (len[k] && !str[k])
+            return fail("%s: a string of the format is NULL", who);
+        if (len[k] >> 20)
+            return fail("%s: a format string of %zu bytes", who, len[k]);
+    }
+    if (!win)
+        return fail("%s: win is NULL", who);
+    const u64 gb = win->global_base, glen = win->global_len;
+    if (gb > glen || text_len > glen - gb)
+        return fail("%s: the buffer [%zu, +%zu) does not lie inside a text of %zu bytes", who, win->global_base, text_len, win->global_len);
+    if (!(gb <= win->own_lo && win->own_lo <= win->own_hi && win->own_hi <= win->records_hi && win->records_hi <= gb + text_len))
+        return fail("%s: the window wants global_base <= own_lo <= own_hi <= records_hi <= global_base + text_len", who);
+    if (win->own_lo == gb && gb != 0)
+        return fail("%s: own_lo == global_base > 0: the byte in front of own_lo must be in the buffer", who);
+    out->incomplete_first_record = n;
+    if (!n)
+        return 0;
+    if (!text_len)
+        return fail("%s: records on an empty buffer", who);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(g_fmt_mu);
+    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the strings behind one another, alive until the copy has run
+    h_fix.clear();
+    for (int k = 0; k < 4; ++k)
+        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
+    const LcFixed f{(u32)len[0], (u32)len[1], (u32)len[2], (u32)len[3]};
+    const LwWindow lw{gb, win->own_lo - gb, win->own_hi - gb, win->records_hi - gb,
+                      (gb + text_len == glen && win->records_hi == glen) ? 1u : 0u};
+    // the scratch: as ln_analyse lays it out, and the relative copy of the list (16-byte aligned: it follows the counter block)
+    const u64 nb = (text_len + kLnBlock - 1) / kLnBlock, n1 = n + 1;
+    const u64 sums = scan_sums_words(std::max(nb, n1));
+    void *base = nullptr;
+    if (fmt_reserve((8 + 2 * n1 + 4 * nb + 6 * n1 + sums) * sizeof(u64) + h_fix.size() + 16, &base))
+        return 2;
+    u64 *p = (u64 *)base;
+    auto take = [&](u64 words) { u64 *q = p; p += words; return q; };
+    LnWork w;
+    w.nb = nb;
+    w.ctr = take(8);
+    u64 *loc = take(2 * n1);
+    w.last1 = take(nb), w.prev1 = take(nb), w.first_rev = take(nb), w.next_rev = take(nb);
+    w.ls = take(n1), w.le = take(n1), w.a = take(n1), w.heads_before = take(n1), w.mark_before = take(n1), w.range = take(n1);
+    w.sums = take(sums);
+    w.prefix = (uint8_t *)p;
+    HIPCHK(hipMemsetAsync(w.ctr, 0, 8 * sizeof(u64), st));
+    HIPCHK(hipMemsetAsync(w.ctr + kLwFirst, 0xff, sizeof(u64), st));
+    if (!h_fix.empty())
+        HIPCHK(hipMemcpyAsync(w.prefix, h_fix.data(), h_fix.size(), hipMemcpyHostToDevice, st));
+    const u32 grid_t = (u32)std::min<u64>((nb + 3) / 4, 256u * 32u), grid_n = (u32)((n1 + 255) / 256);
+    hipLaunchKernelGGL(ln_block_table, dim3(grid_t), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len, nb, w.last1, w.first_rev);
+    scan_exclusive(w.last1, nb, w.prev1, w.sums, true, st);
+    scan_exclusive(w.first_rev, nb, w.next_rev, w.sums, true, st);
+    hipLaunchKernelGGL(lw_bounds, dim3(grid_n), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len, (const u64 *)d_positions, (u64)n,
+                       lw, (const u64 *)w.prev1, (const u64 *)w.next_rev, nb, loc, w.ls, w.le, w.ctr);
+    hipLaunchKernelGGL(lw_heads, dim3(grid_n), dim3(256), 0, st, (const u64 *)w.ls, (u64)n, w.a, w.range);
+    scan_exclusive(w.a, n1, w.heads_before, w.sums, false, st);
+    scan_exclusive(w.range, n1, w.mark_before, w.sums, true, st);
+    u64 *off = w.ls; // the line starts are not read again behind lw_sizes: their buffer takes the summed byte counts
+    hipLaunchKernelGGL(lw_sizes, dim3(grid_n), dim3(256), 0, st, (const u64 *)loc, (const u64 *)w.ls, (const u64 *)w.le,
+                       (const u64 *)w.heads_before, (const u64 *)w.mark_before, (u64)n, (u64)max_lines, f, w.a, w.range, w.ctr);
+    scan_exclusive(w.a, n1, off, w.sums, false, st);
+    HIPCHK(hipGetLastError());
+    u64 h[4] = {0, 0, 0, 0}, total = 0, bytes = 0;
+    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bytes, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h, w.ctr, 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[0])
+    {
+        out->incomplete_first_record = 0;
+        return fail("%s: the record list is not ascending in start, or a record lies outside the buffer", who);
+    }
+    out->lines.lines = std::min<u64>(total, max_lines);
+    out->lines.lines_total = total;
+    out->lines.out_bytes = bytes;
+    out->lines.capped_lines = h[1];
+    if (h[kLwFirst] != kLnNone && total < max_lines) // the incomplete line is the last owned one: `total` lines stand in front of it
+    {
+        out->incomplete_line_start1 = h[kLwStart1];
+        out->incomplete_first_record = h[kLwFirst];
+    }
+    if (!d_out || !out_capacity || !bytes)
+        return 0;
+    if (bytes > out_capacity)
+    {
+        out->lines.overflow = 1;
+        return 0;
+    }
+    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
+    const u64 nchunks = (bytes + misalign + 15) / 16;
+    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
+    hipLaunchKernelGGL(lc_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)loc, (const u64 *)w.le,
                        (const u64 *)off, (const u64 *)w.range, (u64)n, (const uint8_t *)w.prefix, f, (uint8_t *)d_out, bytes, misalign,
                        nchunks);
     HIPCHK(hipGetLastError());

@@ -106,6 +106,11 @@ class Engine:
             L.krep_gpu_format_lines_ex.restype = C.c_int
             L.krep_gpu_format_lines_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(abi.LineFormat),
                                                    C.c_void_p, C.c_size_t, C.POINTER(abi.LinesOut), C.c_void_p]
+        if hasattr(L, "krep_gpu_format_lines_window"):
+            L.krep_gpu_format_lines_window.restype = C.c_int
+            L.krep_gpu_format_lines_window.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(abi.LinesWindow), C.c_void_p, C.c_uint64,
+                                                       C.c_uint64, C.POINTER(abi.LineFormat), C.c_void_p, C.c_size_t,
+                                                       C.POINTER(abi.LinesWindowOut), C.c_void_p]
         if hasattr(L, "krep_gpu_format_matches"):
             L.krep_gpu_format_matches.restype = C.c_int
             L.krep_gpu_format_matches.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(abi.MatchFormat),
@@ -408,6 +413,19 @@ class Engine:
             raise KrepGpuError("krep_gpu_format_lines_ex failed: " + self.last_error())
         return out
 
+    def format_lines_window(self, d_text: int, text_len: int, win: "abi.LinesWindow", d_positions: int, n: int,
+                            max_lines: int = abi.SIZE_MAX, fmt: "abi.LineFormat | None" = None, d_out: int = 0, out_capacity: int = 0,
+                            stream: int = 0) -> "abi.LinesWindowOut":
+        """krep_gpu_format_lines_window(): format_lines_ex for a WINDOW of a text.  The text_len bytes at d_text are
+        text[win.global_base:], the records carry global offsets, the call emits the lines that start in [win.own_lo, win.own_hi)
+        and are complete in front of win.records_hi, and reports the one that is not (.incomplete_line_start1)."""
+        out = abi.LinesWindowOut()
+        if self.lib.krep_gpu_format_lines_window(C.c_void_p(d_text), text_len, C.byref(win), C.c_void_p(d_positions), n, max_lines,
+                                                 C.byref(fmt) if fmt is not None else None, C.c_void_p(d_out) if d_out else None,
+                                                 out_capacity, C.byref(out), C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_format_lines_window failed: " + self.last_error())
+        return out
+
     # ---- the matches themselves, one per line (print_matching_items(), only-matching mode, krep.c:517-793) ----
     def format_matches(self, d_text: int, text_len: int, d_positions: int, n: int, max_items: int = abi.SIZE_MAX,
                        fmt: "abi.MatchFormat | None" = None, d_out: int = 0, out_capacity: int = 0, stream: int = 0) -> "abi.MatchesOut":
@@ -554,6 +572,147 @@ class Plan:
             res = call(buf.data_ptr(), int(res.out_bytes))
             assert not res.overflow
         return buf[: int(res.out_bytes)].cpu().numpy().tobytes()
+
+    def grep_lines_pieces(self, text, piece_bytes: int, filename=None, color=False, halo_bytes: int = 4096) -> bytes:
+        """grep_lines for a text on the HOST that never lies on the device as a whole: it is staged piece by piece into ONE device
+        buffer of 1 + piece_bytes + halo bytes (the byte of left context, the piece, the halo), every piece is scanned with start
+        ownership up to records_hi = buffer end - (longest pattern - 1) (the text's end where the buffer ends it), a multi-pattern
+        list is put in (start, end) order, and krep_gpu_format_lines_window formats the lines that START in the piece.  A line the
+        call reports as incomplete (it outruns the halo) is staged again as a window of its own, its reach doubled until it is
+        complete.  A line of the piece that outruns the halo and holds no record in front of records_hi is one the call cannot
+        know of: the driver finds the line that is open at records_hi on the host and stages it whole.  Returns the concatenated
+        bytes: those of grep_lines on the resident text.
+        text: bytes, a numpy uint8 array or a CPU uint8 tensor.  The plan's max_count holds: a single literal's list is in emission
+        order, so it is cut by counting records across the pieces; a multi-pattern plan with a finite max_count is refused (the
+        cut to the first max_count records in emission order is a property of the whole list).  So are the classes whose match
+        set cannot be cut into independent pieces (krep_gpu_split_mode() != PIECES)."""
+        import torch
+        eng, s = self.eng, self.params.s
+        if isinstance(text, torch.Tensor):
+            host = text.contiguous().view(torch.uint8).reshape(-1)
+        else:
+            a = np.ascontiguousarray(text, dtype=np.uint8).reshape(-1) if isinstance(text, np.ndarray) \
+                else np.frombuffer(bytes(text), dtype=np.uint8)
+            host = torch.from_numpy(a if a.flags.writeable else a.copy())  # (torch takes no read-only array; nothing writes to it)
+        total = int(host.numel())
+        piece_bytes = int(piece_bytes)
+        if piece_bytes <= 0:
+            raise KrepGpuError("grep_lines_pieces: piece_bytes must be positive")
+        limit = int(s.max_count)
+        multi = s.num_patterns > 1
+        if multi and limit != abi.SIZE_MAX:
+            raise KrepGpuError("grep_lines_pieces: a multi-pattern plan with max_count: the cut to the first max_count records in "
+                               "emission order needs the whole record list")
+        if limit == 0 or total == 0:
+            return b""
+        if eng.split_mode(self.params, total) != abi.SPLIT_PIECES:
+            raise KrepGpuError("grep_lines_pieces: the match set of this search cannot be cut into independent pieces "
+                               "(krep_gpu_split_mode)")
+        longest = max(int(x) for x in s.pattern_lens[: s.num_patterns]) if s.num_patterns else int(s.pattern_len)
+        halo = max(int(halo_bytes), longest)  # (records_hi >= own_hi)
+        name = None if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
+        fmt = line_format(name, bool(color))
+        extra = fmt.prefix_len + fmt.line_close_len + fmt.before_match_len + fmt.after_match_len
+        state = {"buf": torch.empty(1 + piece_bytes + halo + 64, dtype=torch.uint8, device="cuda")}
+        parts = []
+        view, step = memoryview(host.numpy()), 1 << 20
+
+        def newline_before(pos):
+            """the last newline in front of pos on the host (-1: none): a line's length at the most is looked at"""
+            while pos > 0:
+                lo_ = max(pos - step, 0)
+                k = bytes(view[lo_:pos]).rfind(b"\n")
+                if k >= 0:
+                    return lo_ + k
+                pos = lo_
+            return -1
+
+        def newline_from(pos):
+            """the first newline at or behind pos on the host (total: none)"""
+            while pos < total:
+                k = bytes(view[pos:pos + step]).find(b"\n")
+                if k >= 0:
+                    return pos + k
+                pos += step
+            return total
+
+        def window(own_lo, own_hi, reach, records_left, lines_left):
+            """stage [own_lo - 1, own_hi + reach), scan and format it -> (LinesWindowOut, records the scan stored)"""
+            base, end = max(own_lo - 1, 0), min(own_hi + reach, total)
+            if state["buf"].numel() < end - base + 64:
+                state["buf"] = torch.empty(end - base + 64, dtype=torch.uint8, device="cuda")
+            buf = state["buf"]
+            buf[: end - base].copy_(host[base:end])
+            d_text, blen = buf.data_ptr(), end - base
+            records_hi = total if end == total else end - (longest - 1)
+            lo, hi = own_lo - base, records_hi - base
+            found = self.scan(d_text, blen, lo, hi, base, global_len=total)
+            cap = int(max(found.count, found.total_matches))
+            if cap == 0:
+                return None, 0
+            pos = torch.empty(2 * (cap + 1), dtype=torch.int64, device="cuda")
+            got = self.scan(d_text, blen, lo, hi, base, pos.data_ptr(), cap + 1, global_len=total)
+            if got.overflow:
+                raise KrepGpuError("grep_lines_pieces: the record list outgrew the count of the scan before it")
+            m = min(int(got.stored), records_left)
+            if m == 0:
+                return None, 0
+            if multi:
+                eng.order_by_start(pos.data_ptr(), m, total)
+            win = abi.LinesWindow(base, total, own_lo, own_hi, records_hi)
+            guess = m * (extra + 256) + 4096
+            out = torch.empty(guess, dtype=torch.uint8, device="cuda")
+            res = eng.format_lines_window(d_text, blen, win, pos.data_ptr(), m, lines_left, fmt, out.data_ptr(), guess)
+            if res.lines.overflow:
+                out = torch.empty(int(res.lines.out_bytes), dtype=torch.uint8, device="cuda")
+                res = eng.format_lines_window(d_text, blen, win, pos.data_ptr(), m, lines_left, fmt, out.data_ptr(),
+                                              int(res.lines.out_bytes))
+                assert not res.lines.overflow
+            if res.lines.out_bytes:
+                parts.append(out[: int(res.lines.out_bytes)].cpu().numpy().tobytes())
+            return res, m
+
+        before, lines_left = 0, limit  # records in front of the piece (counted under a finite max_count only); lines still to emit
+        for lo in range(0, total, piece_bytes):
+            hi = min(lo + piece_bytes, total)
+            left = limit - before
+            if left <= 0 or lines_left <= 0:
+                break
+            res, stored = window(lo, hi, halo, left, lines_left)
+            records_hi = total if hi + halo >= total else hi + halo - (longest - 1)
+            if limit != abi.SIZE_MAX and hi < total:  # the records that START in the piece, on the buffer as it still stands
+                base = max(lo - 1, 0)
+                before += int(self.scan(state["buf"].data_ptr(), min(hi + halo, total) - base, lo - base, hi - base, base,
+                                        global_len=total).total_matches)
+            if res is not None and lines_left != abi.SIZE_MAX:
+                lines_left -= int(res.lines.lines)
+            if res is not None and res.incomplete_line_start1:
+                start = int(res.incomplete_line_start1) - 1
+                reach = 2 * (min(hi + halo, total) - (start + 1))  # the line outruns what the piece's buffer held of it: twice that
+                ahead = int(res.incomplete_first_record)  # records of the piece's list in front of the line
+                while True:
+                    again, _ = window(start, start + 1, reach, left - ahead, 1)
+                    if again is None:
+                        raise KrepGpuError("grep_lines_pieces: a line reported incomplete holds no record when staged again")
+                    if not again.incomplete_line_start1:
+                        break
+                    if start + 1 + reach >= total:
+                        raise KrepGpuError("grep_lines_pieces: a line is incomplete in a buffer that ends the text")
+                    reach *= 2
+                assert again.lines.lines == 1
+                if lines_left != abi.SIZE_MAX:
+                    lines_left -= 1
+            elif records_hi < total and lines_left > 0:
+                # A call cannot report an owned line whose FIRST record lies at or behind records_hi: no record of it is in its
+                # list.  That can only be the line that is open at records_hi; where the piece owns it, it is staged whole.
+                start = newline_before(records_hi) + 1
+                if lo <= start < hi:
+                    whole, _ = window(start, start + 1, newline_from(records_hi) + longest - (start + 1), left - stored, 1)
+                    if whole is not None:
+                        assert whole.lines.lines == 1 and not whole.incomplete_line_start1
+                        if lines_left != abi.SIZE_MAX:
+                            lines_left -= 1
+        return b"".join(parts)
 
     def grep_only_matching(self, d_text: int, n: int, filename=None, max_count=None, color=False, stream: int = 0) -> bytes:
         """What `krep -o [-m N] [--color=always] PATTERN FILE` prints for the n bytes at d_text: one FILE:LINE:match per match.  The

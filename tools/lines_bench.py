@@ -3,7 +3,9 @@ sibling krep_gpu_format_lines_ex (the reference's --color=always strings) and kr
 alternating, in ONE process with the text resident.
 Events around the calls, warmed up.  Beside them the floor from the bytes moved: the text once + 16 B per record + 2 x out_bytes
 at the measured streaming rate (bench.HBM_MEASURED_GBS).
-usage: python tools/lines_bench.py [--gib 32] [--reps 9] [--warmup 2] [--only literal8|ac1000] [--out profiles/lines_on_device.txt]"""
+--windows K adds a row: the same text formatted as K windows of text/K bytes through krep_gpu_format_lines_window (each window's buffer a
+slice of the resident text, 4 KiB of left context, a 1 MiB halo, its records a slice of the one list), the K calls of a repetition summed.
+usage: python tools/lines_bench.py [--gib 32] [--reps 9] [--warmup 2] [--only literal8|ac1000] [--windows 8] [--out profiles/lines_on_device.txt]"""
 import argparse
 import os
 import statistics
@@ -20,6 +22,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--windows", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lines_on_device.txt"))
     args = ap.parse_args()
     import torch
@@ -70,6 +73,32 @@ def main():
             "krep_gpu_format_matches": lambda: eng.format_matches(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, fmt, dst.data_ptr(),
                                                                   obytes),
         }
+        if args.windows:
+            # the windows of the resident text: buffer [lo - 4 KiB, hi + 1 MiB), the records with base <= start < records_hi, the
+            # output of window k behind that of window k - 1; checked once against the whole-text call's bytes
+            K, halo = args.windows, 1 << 20
+            starts = pos[: 2 * m].view(-1, 2)[:, 0].contiguous()
+            wins, at = [], 0
+            for k in range(K):
+                lo, hi = n * k // K, n * (k + 1) // K
+                base, end = max(lo - 4096, 0), min(hi + halo, n)
+                i0, i1 = (int(x) for x in torch.searchsorted(starts, torch.tensor([base, end], dtype=torch.int64, device="cuda")))
+                win = abi.LinesWindow(base, n, lo, hi, end)
+                r = eng.format_lines_window(buf.data_ptr() + base, end - base, win, pos.data_ptr() + 16 * i0, i1 - i0, abi.SIZE_MAX, cfmt)
+                assert not r.incomplete_line_start1
+                wins.append((base, end, win, i0, i1, at, int(r.lines.out_bytes)))
+                at += int(r.lines.out_bytes)
+            assert at == cbytes, (at, cbytes)
+            dst2 = torch.empty(cbytes + 64, dtype=torch.uint8, device="cuda")
+
+            def windows():
+                for base, end, win, i0, i1, at, size in wins:
+                    eng.format_lines_window(buf.data_ptr() + base, end - base, win, pos.data_ptr() + 16 * i0, i1 - i0, abi.SIZE_MAX, cfmt,
+                                            dst2.data_ptr() + at, size)
+            calls["krep_gpu_format_lines_ex"]()
+            windows()
+            assert torch.equal(dst[:cbytes], dst2[:cbytes]), "the windows do not concatenate to the whole-text output"
+            calls[f"krep_gpu_format_lines_window x{K}"] = windows
         ms = {k: [] for k in calls}
         for rep in range(args.warmup + args.reps):
             for k, f in calls.items():
@@ -83,10 +112,12 @@ def main():
         lines.append(f"{name}: text {n} B, {m} records, {L} lines ({int(q.capped_lines)} capped), out_bytes {nbytes}, "
                      f"coloured out_bytes {cbytes}, -o out_bytes {obytes}")
         for k, v in ms.items():
-            moved = n + 16 * m + 2 * {"krep_gpu_format_lines": nbytes, "krep_gpu_format_lines_ex": cbytes, "krep_gpu_format_matches": obytes}.get(k, 0)
+            moved = n + 16 * m + 2 * {"krep_gpu_format_lines": nbytes, "krep_gpu_format_lines_ex": cbytes, "krep_gpu_format_matches": obytes}.get(k, cbytes if "window" in k else 0)
             lines.append(f"  {k:26s} {statistics.median(v):9.3f} ms [{min(v):.3f} .. {max(v):.3f}]   floor {moved / bench.HBM_MEASURED_GBS / 1e6:7.3f} ms")
         plan.close()
         del pos, lineno, spans, first, dst
+        if args.windows:
+            del dst2, starts
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
