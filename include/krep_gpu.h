@@ -589,8 +589,8 @@ int krep_gpu_format_lines_window(const void *d_text, size_t text_len, const krep
 
 /* ---- the matches of a text in HBM, one per line: the reference's -o output (print_matching_items(), only-matching mode,
  * krep.c:517-793) ----
- * Input as for the whole-text line calls: the whole text (shard windows of this form are the host's business) and its n records in
- * (start, end) order, n being the reference's result->count (search_file() has
+ * Input as for the whole-text line calls: the whole text (a text in pieces goes through krep_gpu_format_matches_window below) and its n
+ * records in (start, end) order, n being the reference's result->count (search_file() has
  * cut the list to its first max_count records in emission order and ordered it).  For record i < min(n, max_items), in list order:
  *     prefix  before_number  LINE ':'  after_number  MATCH  after_match  '\n'
  * The four strings are the caller's ("FILE:" and nothing else without colour; the escape codes of krep.h:34-39 with it: the library
@@ -627,6 +627,56 @@ typedef struct krep_gpu_matches_out
 int krep_gpu_format_matches(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
                             uint64_t max_items, const krep_gpu_match_format_t *fmt /* NULL: all empty */, void *d_out,
                             size_t out_capacity, krep_gpu_matches_out_t *out, void *stream);
+
+/* ---- the same -o output for a text in pieces: one call per WINDOW, the outputs concatenate ----
+ * `fmt`, the bytes of a record (prefix before_number LINE ':' after_number MATCH after_match '\n', every '\n' inside MATCH a blank, an
+ * empty match an empty MATCH) and "at most max_items records" are those of krep_gpu_format_matches.
+ * Buffer: d_text[0 .. text_len) holds text[global_base .. global_base + text_len); it ends the text when global_base + text_len ==
+ *   global_len.
+ * Records: GLOBAL offsets, as krep_gpu_scan_device_ex / _seq write them with a global_base, in (start, end) order; the list is any
+ *   consecutive run of the whole text's list.  Ownership is the scan's: the call emits every record it is given (a record is one
+ *   item and belongs to whoever scanned it), so there is no own_lo / own_hi.  MATCH is text[start, min(end, global_len)).
+ *   Refused (2) before any byte of the text is read through the list: a list not ascending in start, a record with start outside
+ *   [global_base, global_base + text_len) or end < start, or a match that outruns the buffer (min(end, global_len) > global_base +
+ *   text_len: a match is no longer than the longest pattern, so the caller can always size its halo; nothing is "incomplete").
+ * LINE: the true number is 1 + newlines_before + the newlines in d_text[0, start - global_base); a start ON a '\n' belongs to the line
+ *   that newline ends.  The reference's stale number (above) applies when stale_rule != 0, last_newline1 != 0 and start >=
+ *   last_newline1 — decided by OFFSET, the window does not know the text's newline total.  Such a record prints S: the largest true
+ *   LINE among this list's n records (all n, not only the emitted ones) with start < last_newline1; win->stale_line when the list
+ *   has none; 1 when that is 0 too.
+ * Carries out, valid for n == 0 too (a window without records still advances the line count), on a size query and with overflow:
+ *   out->stale_line = S before the fallback to 1 (the largest such LINE of this list, else win->stale_line);
+ *   out->newlines_before_count_to = newlines_before + the newlines in d_text[0, count_to - global_base).
+ * Also refused (2): global_base + text_len > global_len, count_to outside [global_base, global_base + text_len], last_newline1 >
+ *   global_len, global_len >= 10^16 or a LINE of more than 16 digits, a format string of more than 2^20 bytes, n >= 2^40, NULL win / out.
+ * Invariant: cut the whole list into consecutive sub-lists in order; give each a buffer that holds its records, with non-decreasing
+ *   global_base; set count_to to the next buffer's global_base; chain newlines_before (<- newlines_before_count_to) and stale_line;
+ *   give every call the same truthful last_newline1 and stale_rule; pass max_items on as what is left.  The outputs, concatenated, are
+ *   byte for byte those of krep_gpu_format_matches on the whole text, and `items` sums to its value.
+ * As for krep_gpu_format_matches: d_out == NULL or out_capacity == 0 is a size query, `overflow` comes with valid sizes, d_text and d_out
+ *   may have any alignment, nothing is written outside [d_out, d_out + out_bytes), `stream` is synchronised on return. */
+typedef struct krep_gpu_matches_window
+{
+    size_t global_base;       /* offset in the text of d_text[0]                                                                 */
+    size_t global_len;        /* length of the whole text                                                                        */
+    size_t count_to;          /* global offset in [global_base, global_base + text_len]: see newlines_before_count_to            */
+    uint64_t newlines_before; /* '\n' bytes in text[0, global_base)                                                              */
+    uint64_t last_newline1;   /* global offset of the text's LAST '\n', + 1 (0: the text has none)                               */
+    uint64_t stale_line;      /* LINE of the nearest record IN FRONT of this list that starts at or before the last newline (0:
+                                 none)                                                                                           */
+    int stale_rule;           /* the whole list of the text, after its max_count cut, holds more than 10 records                 */
+    int reserved;             /* (keeps the size free of implicit padding; not read)                                             */
+} krep_gpu_matches_window_t;
+typedef struct krep_gpu_matches_window_out
+{
+    krep_gpu_matches_out_t matches;    /* items, out_bytes, overflow: of the records of this call                                */
+    uint64_t newlines_before_count_to; /* '\n' bytes in text[0, count_to): the next window's newlines_before                     */
+    uint64_t stale_line;               /* the next window's stale_line                                                           */
+} krep_gpu_matches_window_out_t;
+int krep_gpu_format_matches_window(const void *d_text, size_t text_len, const krep_gpu_matches_window_t *win,
+                                   const match_position_t *d_positions, uint64_t n, uint64_t max_items,
+                                   const krep_gpu_match_format_t *fmt /* NULL: all empty */, void *d_out, size_t out_capacity,
+                                   krep_gpu_matches_window_out_t *out, void *stream);
 
 int krep_gpu_device_count(void);
 const char *krep_gpu_last_error(void); /* "" when the last call on this thread succeeded */

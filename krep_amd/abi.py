@@ -97,6 +97,17 @@ class MatchesOut(C.Structure):
     _fields_ = [("items", C.c_uint64), ("out_bytes", C.c_uint64), ("overflow", C.c_int)]
 
 
+class MatchesWindow(C.Structure):
+    """krep_gpu_matches_window_t: which part of a text the buffer of krep_gpu_format_matches_window holds, and the two carries in"""
+    _fields_ = [("global_base", C.c_size_t), ("global_len", C.c_size_t), ("count_to", C.c_size_t), ("newlines_before", C.c_uint64),
+                ("last_newline1", C.c_uint64), ("stale_line", C.c_uint64), ("stale_rule", C.c_int), ("reserved", C.c_int)]
+
+
+class MatchesWindowOut(C.Structure):
+    """krep_gpu_matches_window_out_t: MatchesOut of the call's records, and the two carries out"""
+    _fields_ = [("matches", MatchesOut), ("newlines_before_count_to", C.c_uint64), ("stale_line", C.c_uint64)]
+
+
 class Config(C.Structure):
     """krep_gpu_config_t: the reference's build level and file-static option globals, explicit."""
     _fields_ = [("reference_simd", C.c_int), ("only_matching", C.c_int), ("force_no_simd", C.c_int),

@@ -17,6 +17,13 @@
 // (3) per record the number it prints and its byte count (the stale value's digits are known only now), summed; (4) the gather,
 // dealt by OUTPUT bytes: a lane owns 16 aligned bytes of the output, a wave 1 KiB, the first record of a tile comes from a binary
 // search in the summed offsets.  A call reads the text once in (1), then only around the records and what it copies.
+//
+// krep_gpu_format_matches_window is the same output for a WINDOW of a text (a buffer that holds text[global_base, + text_len), records
+// with offsets in the whole text, any consecutive run of its list).  Two numbers couple a window to the rest of the text, and the caller
+// chains them: the newlines in front of the buffer, and the stale value the records in front of the list leave.  "Behind the last newline"
+// is decided by offset against last_newline1, which the caller states (the window does not know N).  Its kernels (mw_*) mirror the steps:
+// (1) unchanged on the buffer, (2w) mw_lines, (3w) mw_sizes, (4w) om_gather<true> = the gather with the source moved by global_base,
+// (5w) mw_count_to: the newlines in front of count_to, the next window's carry.  The whole-text call keeps its kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -140,7 +147,9 @@ struct OmItem
     u32 b1, b2;      // head [0, b1), digits [b1, b2), ':' at b2, after_number [b2 + 1, b4), after_match [b5, b6), '\n' at b6
     u64 b6;
 };
-__device__ __forceinline__ OmItem om_item(const u64 *__restrict__ rec, const u64 *__restrict__ line, u64 text_len, const OmFixed f, u64 r)
+// (`base`: the text offset of text[0] — 0 for the whole-text call, global_base for a window, whose text_len is the whole text's length)
+__device__ __forceinline__ OmItem om_item(const u64 *__restrict__ rec, const u64 *__restrict__ line, u64 text_len, const OmFixed f, u64 r,
+                                          u64 base = 0)
 {
     OmItem it;
     const uint4 w = *reinterpret_cast<const uint4 *>(rec + 2 * r);
@@ -154,7 +163,7 @@ __device__ __forceinline__ OmItem om_item(const u64 *__restrict__ rec, const u64
         v /= 10;
         ++d;
     } while (v);
-    it.src = s;
+    it.src = s - base;
     it.dlo = lo;
     it.dhi = hi;
     it.b1 = f.head;
@@ -189,11 +198,15 @@ __device__ __forceinline__ u32 om_byte(const uint8_t *__restrict__ text, const u
 __device__ __forceinline__ u32 om_blank(u32 w) { return w ^ ((eq_bytes(w, 0x0a0a0a0au) >> 7) * 0x2au); }
 
 // (4) chunk c is the 16 aligned bytes at (out - misalign) + 16 c, i.e. output offsets [16 c - misalign, + 16); `emit` records add bytes
+// text_len: the length of the WHOLE text, the clamp of a record's end in both instantiations.  WIN: the window call's gather — text[0] is
+// byte `win_base` of the whole text (the whole-text call passes win_base = 0 and does not read it)
+template <bool WIN>
 __global__ __launch_bounds__(256) void om_gather(const uint8_t *__restrict__ text, u64 text_len, const u64 *__restrict__ rec,
                                                  const u64 *__restrict__ line, const u64 *__restrict__ off, u64 emit,
                                                  const uint8_t *__restrict__ fix, const OmFixed f, uint8_t *__restrict__ out, u64 total,
-                                                 u32 misalign, u64 nchunks)
+                                                 u32 misalign, u64 nchunks, u64 win_base)
 {
+    const u64 base = WIN ? win_base : 0ull;
     const u32 lane = threadIdx.x & 63u;
     const u64 wid = (u64)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = (u64)gridDim.x * (blockDim.x >> 6);
     for (u64 c0 = wid * 64; c0 < nchunks; c0 += nw * 64)
@@ -207,7 +220,7 @@ __global__ __launch_bounds__(256) void om_gather(const uint8_t *__restrict__ tex
         const u64 o0 = c ? c * 16 - misalign : 0ull, o1 = min((c + 1) * 16 - misalign, total);
         const bool whole = o1 - o0 == 16;
         u64 r = om_find(off, r_lo, r_hi, o0);
-        OmItem it = om_item(rec, line, text_len, f, r);
+        OmItem it = om_item(rec, line, text_len, f, r, base);
         u64 k = o0 - off[r];
         if (whole && k >= it.b4 && k + 16 <= it.b5) // wholly inside one match
         {
@@ -225,7 +238,7 @@ __global__ __launch_bounds__(256) void om_gather(const uint8_t *__restrict__ tex
             {
                 if (k > it.b6) // the record is used up (every emitted record adds bytes)
                 {
-                    it = om_item(rec, line, text_len, f, ++r);
+                    it = om_item(rec, line, text_len, f, ++r, base);
                     k = 0;
                 }
                 w[q >> 2] |= om_byte(text, fix, f, it, k) << (8 * (q & 3u));
@@ -244,9 +257,110 @@ __global__ __launch_bounds__(256) void om_gather(const uint8_t *__restrict__ tex
     }
 }
 
+// ---- the same output for a WINDOW of a text (krep_gpu_format_matches_window) ----
+// The buffer `text` holds the whole text's bytes [base, base + buf_len); the records carry offsets in the whole text; the 4 KiB blocks
+// of before[] are the BUFFER's.  What the window cannot count itself comes in: nl_before, the newlines in front of `base`.
+struct MwWindow
+{
+    u64 base, buf_len, global_len; // base + buf_len <= global_len
+    u64 nl_before;                 // '\n' bytes in front of base
+    u64 last_nl1;                  // offset of the whole text's last '\n', + 1 (0: none)
+    u64 stale_in;                  // the stale value the lists in front of this one leave (0: none)
+    u32 stale_rule;                // the whole list holds more than 10 records
+};
+
+// (2w) om_lines with the window's bounds: line[i] = 1 + nl_before + the newlines of the buffer in front of record i's start.
+// ctr[0]: refused; ctr[1]: the largest line number among the records that start at or before the last newline (0: none)
+__global__ __launch_bounds__(256) void mw_lines(const uint8_t *__restrict__ text, const MwWindow w, const u64 *__restrict__ rec, u64 n,
+                                                const u64 *__restrict__ before, u64 *__restrict__ line, u64 *__restrict__ ctr)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u64 m = 0;
+    if (i < n)
+    {
+        const uint4 r = *reinterpret_cast<const uint4 *>(rec + 2 * i);
+        const u64 s = ((u64)r.y << 32) | r.x, e = ((u64)r.w << 32) | r.z;
+        u64 ln = 0;
+        if (s < w.base || s - w.base >= w.buf_len || e < s || min(e, w.global_len) - w.base > w.buf_len ||
+            (i > 0 && rec[2 * (i - 1)] > s))
+            ctr[0] = 1; // (every writer stores the same value)
+        else
+        {
+            const u64 o = s - w.base, b = o / kLineBlock, lo = b * kLineBlock, lim = min(lo + kLineBlock, w.buf_len);
+            ln = w.nl_before + (o - lo <= lim - o ? 1 + before[b] + nl_count(text, lo, o) : 1 + before[b + 1] - nl_count(text, o, lim));
+            m = s < w.last_nl1 ? ln : 0ull;
+        }
+        line[i] = ln;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        m = max(m, (u64)__shfl_xor(m, o));
+    if ((threadIdx.x & 63u) == 0 && m)
+        (void)__hip_atomic_fetch_max(ctr + 1, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// (3w) om_sizes with the stale decision by OFFSET: a record that starts behind the whole text's last newline prints the stale value
+__global__ __launch_bounds__(256) void mw_sizes(const u64 *__restrict__ rec, u64 n, const MwWindow w, u64 max_items, u64 fixed,
+                                                const u64 *__restrict__ ctr, u64 *__restrict__ line, u64 *__restrict__ bytes)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n)
+        return;
+    if (i == n || i >= max_items)
+    {
+        bytes[i] = 0;
+        return;
+    }
+    const u64 s = rec[2 * i], e = min(rec[2 * i + 1], w.global_len);
+    u64 ln = line[i];
+    if (w.stale_rule && w.last_nl1 && s >= w.last_nl1)
+    {
+        const u64 mine = ctr[1];
+        ln = mine ? mine : max(w.stale_in, 1ull);
+        line[i] = ln;
+    }
+    bytes[i] = fixed + om_digits(ln) + 1 + (e - s) + 1;
+}
+
+// (5w) one wave: ctr[2] = nl_before + the newlines of the buffer in front of buffer offset `upto` (<= buf_len): a table entry and a
+// partial block; ctr[3] = the newlines of the whole buffer
+__global__ __launch_bounds__(64) void mw_count_to(const uint8_t *__restrict__ text, const MwWindow w, u64 upto, const u64 *__restrict__ before,
+                                                  u64 nblocks, u64 *__restrict__ ctr)
+{
+    const u64 b = upto / kLineBlock, lo = b * kLineBlock + (u64)threadIdx.x * (kLineBlock / 64);
+    u64 c = lo < upto ? (u64)nl_count(text, lo, min(lo + kLineBlock / 64, upto)) : 0ull;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        c += (u64)__shfl_xor(c, o);
+    if (threadIdx.x == 0)
+    {
+        ctr[2] = w.nl_before + before[b] + c;
+        ctr[3] = before[nblocks - 1];
+    }
+}
+
 } // namespace kg
 
 using namespace kg;
+
+// the four strings of a format (NULL: all empty), checked
+static int om_strings(const char *who, const krep_gpu_match_format_t *fmt, const char *str[4], size_t len[4])
+{
+    const krep_gpu_match_format_t none{};
+    const krep_gpu_match_format_t &m = fmt ? *fmt : none;
+    const char *s[4] = {m.prefix, m.before_number, m.after_number, m.after_match};
+    const size_t l[4] = {m.prefix_len, m.before_number_len, m.after_number_len, m.after_match_len};
+    for (int k = 0; k < 4; ++k)
+    {
+        if (l[k] && !s[k])
+            return fail("%s: a string of the format is NULL", who);
+        if (l[k] >> 20)
+            return fail("%s: a format string of %zu bytes", who, l[k]);
+        str[k] = s[k];
+        len[k] = l[k];
+    }
+    return 0;
+}
 
 extern "C" int krep_gpu_format_matches(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
                                        uint64_t max_items, const krep_gpu_match_format_t *fmt, void *d_out, size_t out_capacity,
@@ -268,17 +382,10 @@ extern "C" int krep_gpu_format_matches(const void *d_text, size_t text_len, cons
         return fail("%s: d_text / d_positions is NULL", who);
     if (n >> 40)
         return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
-    const krep_gpu_match_format_t none{};
-    const krep_gpu_match_format_t &m = fmt ? *fmt : none;
-    const char *str[4] = {m.prefix, m.before_number, m.after_number, m.after_match};
-    const size_t len[4] = {m.prefix_len, m.before_number_len, m.after_number_len, m.after_match_len};
-    for (int k = 0; k < 4; ++k)
-    {
-        if (len[k] && !str[k])
-            return fail("%s: a string of the format is NULL", who);
-        if (len[k] >> 20)
-            return fail("%s: a format string of %zu bytes", who, len[k]);
-    }
+    const char *str[4];
+    size_t len[4];
+    if (om_strings(who, fmt, str, len))
+        return 2;
     if (!n)
         return 0;
     if (!text_len)
@@ -332,8 +439,123 @@ extern "C" int krep_gpu_format_matches(const void *d_text, size_t text_len, cons
     const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
     const u64 nchunks = (total + misalign + 15) / 16;
     const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
-    hipLaunchKernelGGL(om_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len, (const u64 *)d_positions,
-                       (const u64 *)line, (const u64 *)off, emit, (const uint8_t *)d_fix, f, (uint8_t *)d_out, total, misalign, nchunks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(om_gather<false>), dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
+                       (const u64 *)d_positions, (const u64 *)line, (const u64 *)off, emit, (const uint8_t *)d_fix, f, (uint8_t *)d_out,
+                       total, misalign, nchunks, (u64)0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int krep_gpu_format_matches_window(const void *d_text, size_t text_len, const krep_gpu_matches_window_t *win,
+                                              const match_position_t *d_positions, uint64_t n, uint64_t max_items,
+                                              const krep_gpu_match_format_t *fmt, void *d_out, size_t out_capacity,
+                                              krep_gpu_matches_window_out_t *out, void *stream)
+{
+    const char *who = "krep_gpu_format_matches_window";
+    if (!out)
+        return fail("%s: out is NULL", who);
+    *out = krep_gpu_matches_window_out_t{};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return fail("%s: no HIP device available", who);
+    }
+    if (const char *why = device_unusable(dev))
+        return fail("%s: %s", who, why);
+    if (!win)
+        return fail("%s: win is NULL", who);
+    if ((text_len && !d_text) || (n && !d_positions))
+        return fail("%s: d_text / d_positions is NULL", who);
+    if (n >> 40)
+        return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
+    const char *str[4];
+    size_t len[4];
+    if (om_strings(who, fmt, str, len))
+        return 2;
+    const u64 gb = win->global_base, glen = win->global_len;
+    if (glen >= kOmMaxText)
+        return fail("%s: text too long", who);
+    if (gb > glen || text_len > glen - gb)
+        return fail("%s: the buffer [%llu, + %zu) is not inside the text of %llu bytes", who, (unsigned long long)gb, text_len,
+                    (unsigned long long)glen);
+    if (win->count_to < gb || win->count_to - gb > text_len)
+        return fail("%s: count_to = %llu lies outside the buffer", who, (unsigned long long)win->count_to);
+    if (win->last_newline1 > glen)
+        return fail("%s: last_newline1 = %llu lies behind the text", who, (unsigned long long)win->last_newline1);
+    if (win->newlines_before >= kOmMaxText || win->stale_line >= kOmMaxText)
+        return fail("%s: a line number of more than 16 digits", who);
+    if (n && !text_len)
+        return fail("%s: records on an empty buffer", who);
+    out->stale_line = win->stale_line;
+    out->newlines_before_count_to = win->newlines_before;
+    if (!text_len)
+        return 0;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(g_fmt_mu);
+    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the fixed strings behind one another, alive until the copy has run
+    h_fix.clear();
+    for (int k = 0; k < 4; ++k)
+        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
+    const OmFixed f{(u32)(len[0] + len[1]), (u32)len[2], (u32)len[3]};
+    const MwWindow w{gb, (u64)text_len, glen, win->newlines_before, win->last_newline1, win->stale_line, win->stale_rule ? 1u : 0u};
+    const u64 fixed = h_fix.size(), nblocks = line_blocks(text_len), n1 = n + 1;
+    const u64 sums = scan_sums_words(std::max(nblocks, n1));
+    void *base = nullptr;
+    if (fmt_reserve((8 + 2 * nblocks + 3 * n1 + sums) * sizeof(u64) + fixed + 16, &base))
+        return 2;
+    u64 *p = (u64 *)base;
+    auto take = [&](u64 words) { u64 *q = p; p += words; return q; };
+    u64 *ctr = take(8), *counts = take(nblocks), *before = take(nblocks); // ctr: {refused, stale value, newlines in front of count_to, newlines of the buffer}
+    u64 *line = take(n1), *bytes = take(n1), *off = take(n1), *sum_words = take(sums);
+    uint8_t *d_fix = (uint8_t *)p;
+    HIPCHK(hipMemsetAsync(ctr, 0, 8 * sizeof(u64), st));
+    if (fixed && n)
+        HIPCHK(hipMemcpyAsync(d_fix, h_fix.data(), fixed, hipMemcpyHostToDevice, st));
+    if (newlines_before_blocks((const uint8_t *)d_text, text_len, counts, before, sum_words, st))
+        return 2;
+    hipLaunchKernelGGL(mw_count_to, dim3(1), dim3(64), 0, st, (const uint8_t *)d_text, w, (u64)(win->count_to - gb), (const u64 *)before,
+                       nblocks, ctr);
+    if (n)
+    {
+        hipLaunchKernelGGL(mw_lines, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_text, w, (const u64 *)d_positions,
+                           (u64)n, (const u64 *)before, line, ctr);
+        hipLaunchKernelGGL(mw_sizes, dim3((u32)((n1 + 255) / 256)), dim3(256), 0, st, (const u64 *)d_positions, (u64)n, w, (u64)max_items,
+                           fixed, (const u64 *)ctr, line, bytes);
+        scan_exclusive(bytes, n1, off, sum_words, false, st);
+    }
+    HIPCHK(hipGetLastError());
+    u64 h_ctr[4] = {0, 0, 0, 0}, total = 0;
+    HIPCHK(hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+    if (n)
+        HIPCHK(hipMemcpyAsync(&total, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h_ctr[0] || win->newlines_before + h_ctr[3] + 1 >= kOmMaxText)
+        *out = krep_gpu_matches_window_out_t{};
+    if (h_ctr[0])
+        return fail("%s: the record list is not ascending in start, or a record lies outside the buffer or outruns it", who);
+    if (win->newlines_before + h_ctr[3] + 1 >= kOmMaxText)
+        return fail("%s: a line number of more than 16 digits", who);
+    if (h_ctr[1])
+        out->stale_line = h_ctr[1];
+    out->newlines_before_count_to = h_ctr[2];
+    const u64 emit = std::min<u64>(n, max_items);
+    out->matches.items = emit;
+    out->matches.out_bytes = total;
+    if (!d_out || !out_capacity || !total)
+        return 0;
+    if (total > out_capacity)
+    {
+        out->matches.overflow = 1;
+        return 0;
+    }
+    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
+    const u64 nchunks = (total + misalign + 15) / 16;
+    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(om_gather<true>), dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, glen,
+                       (const u64 *)d_positions, (const u64 *)line, (const u64 *)off, emit, (const uint8_t *)d_fix, f, (uint8_t *)d_out,
+                       total, misalign, nchunks, gb);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     return 0;

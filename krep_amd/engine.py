@@ -115,6 +115,11 @@ class Engine:
             L.krep_gpu_format_matches.restype = C.c_int
             L.krep_gpu_format_matches.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(abi.MatchFormat),
                                                   C.c_void_p, C.c_size_t, C.POINTER(abi.MatchesOut), C.c_void_p]
+        if hasattr(L, "krep_gpu_format_matches_window"):
+            L.krep_gpu_format_matches_window.restype = C.c_int
+            L.krep_gpu_format_matches_window.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(abi.MatchesWindow), C.c_void_p, C.c_uint64,
+                                                         C.c_uint64, C.POINTER(abi.MatchFormat), C.c_void_p, C.c_size_t,
+                                                         C.POINTER(abi.MatchesWindowOut), C.c_void_p]
         for n in ("krep_gpu_set_reference_simd", "krep_gpu_set_only_matching", "krep_gpu_set_force_no_simd",
                   "krep_gpu_set_algo_override", "krep_gpu_debug_force_rounds", "krep_gpu_debug_force_stage_cap",
                   "krep_gpu_set_result_order", "krep_gpu_set_device", "krep_gpu_set_num_gpus", "krep_gpu_debug_inject_failure"):
@@ -438,6 +443,20 @@ class Engine:
             raise KrepGpuError("krep_gpu_format_matches failed: " + self.last_error())
         return out
 
+    def format_matches_window(self, d_text: int, text_len: int, win: "abi.MatchesWindow", d_positions: int, n: int,
+                              max_items: int = abi.SIZE_MAX, fmt: "abi.MatchFormat | None" = None, d_out: int = 0, capacity: int = 0,
+                              stream: int = 0) -> "abi.MatchesWindowOut":
+        """krep_gpu_format_matches_window(): format_matches for a WINDOW of a text.  The text_len bytes at d_text are
+        text[win.global_base:], the n records (global offsets) are a consecutive run of the text's list; win carries the newlines in
+        front of the buffer and the stale line number in, the result carries them out (.newlines_before_count_to, .stale_line)."""
+        out = abi.MatchesWindowOut()
+        if self.lib.krep_gpu_format_matches_window(C.c_void_p(d_text) if d_text else None, text_len, C.byref(win),
+                                                   C.c_void_p(d_positions) if d_positions else None, n, max_items,
+                                                   C.byref(fmt) if fmt is not None else None, C.c_void_p(d_out) if d_out else None,
+                                                   capacity, C.byref(out), C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_format_matches_window failed: " + self.last_error())
+        return out
+
     # ---- search_func_t-shaped operators on host buffers ----
     def _ptr(self, text):
         if isinstance(text, np.ndarray):
@@ -754,6 +773,134 @@ class Plan:
             assert not res.overflow
         return buf[: int(res.out_bytes)].cpu().numpy().tobytes()
 
+    def grep_only_matching_pieces(self, text, piece_bytes: int, filename=None, color=False) -> bytes:
+        """grep_only_matching for a text on the HOST that never lies on the device as a whole; returns the bytes of
+        grep_only_matching on the resident text.  The text is cut into pieces of piece_bytes; piece [lo, hi) is staged as
+        [max(lo - 1, 0), min(hi + longest pattern, total)) into ONE reused device buffer (the byte of left context for -w, and
+        behind the piece a match that starts on its last byte with the byte -w looks at behind it).  Under -o many single
+        literals couple a match to the one before it (krep_gpu_split_mode() = CHAIN), so the pieces are scanned IN TEXT ORDER
+        through scan_seq, each taking the carry of the one before it (the counting scan and the recording scan of a piece take the
+        same carry); families without that dependency pass the carry through, so one road serves both classes.  A multi-pattern
+        list is put in (start, end) order, and krep_gpu_format_matches_window formats the piece's records with count_to = the
+        next piece's base (hi - 1: its byte of left context), the newline count and the stale line number chained from call to call.
+        last_newline1 is looked up once on the host, backwards from the end of the text.  stale_rule (more than 10 records in the
+        whole list) is false when max_count <= 10 and true as soon as the running count passes 10.  Until then only records that
+        start at or behind last_newline1 depend on it: those are HELD BACK (StaleSchedule: at most 10 (start, end) pairs on the
+        host, nothing emitted behind them) while everything in front of them is formatted at once.  When the rule is decided (the
+        count passes 10, or the text ends) each held record is formatted by a call of its own on a buffer staged from the host
+        text: global_base = its start, newlines_before = the text's newline total (known by then: the chain has passed the last
+        newline), the chained stale_line.  Then the pieces go on normally.
+        text: bytes, a numpy uint8 array or a CPU uint8 tensor.  The plan's max_count holds: a single literal's list is in emission
+        order, so it is cut by counting records across the pieces.  Refused: a plan made without only_matching=True, a
+        multi-pattern plan with a finite max_count (the cut to the first max_count records in emission order needs the whole
+        list), and a search krep_gpu_split_mode() calls WHOLE."""
+        import torch
+        eng, s = self.eng, self.params.s
+        if not self.only_matching:
+            raise KrepGpuError("grep_only_matching_pieces: the plan was not created with only_matching=True (the match set of -o "
+                               "differs)")
+        if isinstance(text, torch.Tensor):
+            host = text.contiguous().view(torch.uint8).reshape(-1)
+        else:
+            a = np.ascontiguousarray(text, dtype=np.uint8).reshape(-1) if isinstance(text, np.ndarray) \
+                else np.frombuffer(bytes(text), dtype=np.uint8)
+            host = torch.from_numpy(a if a.flags.writeable else a.copy())  # (torch takes no read-only array; nothing writes to it)
+        total = int(host.numel())
+        piece_bytes = int(piece_bytes)
+        if piece_bytes <= 0:
+            raise KrepGpuError("grep_only_matching_pieces: piece_bytes must be positive")
+        limit = int(s.max_count)
+        multi = s.num_patterns > 1
+        if multi and limit != abi.SIZE_MAX:
+            raise KrepGpuError("grep_only_matching_pieces: a multi-pattern plan with max_count: the cut to the first max_count "
+                               "records in emission order needs the whole record list")
+        cfg = eng.default_config()  # the class of the search under -o (the plan carries only_matching; the process default may not)
+        cfg.only_matching = 1
+        eng.set_thread_config(cfg)
+        try:
+            mode = eng.split_mode(self.params, total)
+        finally:
+            eng.set_thread_config(None)
+        if mode == abi.SPLIT_WHOLE:
+            raise KrepGpuError("grep_only_matching_pieces: this search takes the whole text in one window (krep_gpu_split_mode)")
+        if limit == 0 or total == 0:
+            return b""
+        longest = max(int(x) for x in s.pattern_lens[: s.num_patterns]) if s.num_patterns else int(s.pattern_len)
+        name = None if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
+        fmt = match_format(name, bool(color))
+        per_item = fmt.prefix_len + fmt.before_number_len + fmt.after_number_len + fmt.after_match_len + 20 + 2 + longest
+        buf = torch.empty(1 + piece_bytes + longest + 64, dtype=torch.uint8, device="cuda")
+        view, step = memoryview(host.numpy()), 1 << 20
+        last_nl1, at = 0, total  # the last newline of the text + 1, looked for backwards from its end
+        while at > 0 and not last_nl1:
+            lo_ = max(at - step, 0)
+            k = bytes(view[lo_:at]).rfind(b"\n")
+            last_nl1 = lo_ + k + 1 if k >= 0 else 0
+            at = lo_
+        sched = StaleSchedule(limit, last_nl1)
+        parts = []
+        chain = {"nl": 0, "stale": 0}  # the two carries of krep_gpu_format_matches_window
+
+        # reused like the text buffer: the output of one call, and the text and the record of a held one
+        dev = {"out": torch.empty(4096, dtype=torch.uint8, device="cuda"), "one": torch.empty(longest + 64, dtype=torch.uint8, device="cuda"),
+               "rec": torch.empty(2, dtype=torch.int64, device="cuda")}
+
+        def grown(key, nbytes):
+            if dev[key].numel() < nbytes:
+                dev[key] = torch.empty(max(nbytes, 2 * dev[key].numel()), dtype=torch.uint8, device="cuda")
+            return dev[key]
+
+        def fmt_call(d_text, blen, base, count_to, d_pos, n, rule):
+            win = abi.MatchesWindow(base, total, count_to, chain["nl"], last_nl1, chain["stale"], int(rule))
+            out = grown("out", n * per_item + 4096)
+            res = eng.format_matches_window(d_text, blen, win, d_pos, n, abi.SIZE_MAX, fmt, out.data_ptr(), out.numel())
+            if res.matches.overflow:  # (a record longer than a pattern)
+                out = grown("out", int(res.matches.out_bytes))
+                res = eng.format_matches_window(d_text, blen, win, d_pos, n, abi.SIZE_MAX, fmt, out.data_ptr(), out.numel())
+                assert not res.matches.overflow
+            if res.matches.out_bytes:
+                parts.append(out[: int(res.matches.out_bytes)].cpu().numpy().tobytes())
+            return res
+
+        def held_calls(records, rule):
+            """every held record in a call of its own: they lie behind the last newline, where chain["nl"] is the text's total"""
+            for start, end in records:
+                stop = max(min(end, total), start + 1)
+                one = grown("one", stop - start + 64)
+                one[: stop - start].copy_(host[start:stop])
+                dev["rec"].copy_(torch.tensor([start, end], dtype=torch.int64))
+                chain["stale"] = int(fmt_call(one.data_ptr(), stop - start, start, start, dev["rec"].data_ptr(), 1, rule).stale_line)
+
+        carry = None
+        for lo in range(0, total, piece_bytes):
+            left = limit - sched.count
+            if left <= 0:
+                break
+            hi = min(lo + piece_bytes, total)
+            base, end = max(lo - 1, 0), min(hi + longest, total)
+            buf[: end - base].copy_(host[base:end])
+            d_text, blen = buf.data_ptr(), end - base
+            found, carry_out = self.scan_seq(d_text, blen, lo - base, hi - base, base, global_len=total, carry_in=carry)
+            cap, m, pos = int(max(found.count, found.total_matches)), 0, None
+            if cap:
+                pos = torch.empty(2 * (cap + 1), dtype=torch.int64, device="cuda")
+                got, carry_out = self.scan_seq(d_text, blen, lo - base, hi - base, base, pos.data_ptr(), cap + 1, global_len=total,
+                                               carry_in=carry)
+                if got.overflow:
+                    raise KrepGpuError("grep_only_matching_pieces: the record list outgrew the count of the scan before it")
+                m = min(int(got.stored), left)
+                if multi and m:
+                    eng.order_by_start(pos.data_ptr(), m, total)
+            carry = carry_out
+            flush, now, rule = sched.add(m, lambda: pos[: 2 * m].view(-1, 2).cpu().tolist())
+            held_calls(flush, rule)
+            # (a piece without records is formatted too: its call carries the newline count on)
+            res = fmt_call(d_text, blen, base, hi - 1 if hi < total else total, pos.data_ptr() if now else 0, now, rule)
+            chain["nl"], chain["stale"] = int(res.newlines_before_count_to), int(res.stale_line)
+        flush, rule = sched.end()
+        held_calls(flush, rule)
+        return b"".join(parts)
+
     def anchor_info(self):
         """(state 0 undecided / 1 end grams / 2 anchored, patterns moved, est. candidate rate end grams, ... anchors) — multi-pattern plans"""
         st, mv, r0, r1 = C.c_int(0), C.c_uint32(0), C.c_double(0), C.c_double(0)
@@ -810,6 +957,7 @@ class Plan:
 COLOR_RESET, COLOR_FILENAME, COLOR_SEPARATOR = b"\033[0m", b"\033[1;38;5;81m", b"\033[38;5;244m"
 COLOR_LINE_NUMBER, COLOR_MATCH = b"\033[1;38;5;111m", b"\033[1;38;5;222m"
 COLOR_TEXT = b"\033[38;5;252m"
+STALE_AFTER = 10  # -o: with more than this many records the reference prints stale line numbers behind the last newline (krep.c:531)
 
 
 def match_format(filename: "bytes | None" = None, color: bool = False) -> "abi.MatchFormat":
@@ -826,6 +974,41 @@ def line_format(filename: "bytes | None" = None, color: bool = False) -> "abi.Li
         return abi.LineFormat(b"" if filename is None else filename + b":")
     prefix = COLOR_TEXT if filename is None else COLOR_FILENAME + filename + COLOR_RESET + COLOR_SEPARATOR + b":" + COLOR_TEXT
     return abi.LineFormat(prefix, COLOR_MATCH, COLOR_TEXT, COLOR_RESET)
+
+
+class StaleSchedule:
+    """When Plan.grep_only_matching_pieces may format the records of a piece.  The reference's stale line number (more than 10
+    records in the whole list, after its max_count cut) touches only the records that start at or behind last_newline1; until the
+    running count has passed 10 or the text has ended nobody knows whether it applies.  So while the rule is undecided those
+    records (at most 10) are HELD on the host, in order, and nothing is emitted behind them; everything in front of them is
+    formatted at once.  Host logic only."""
+
+    def __init__(self, max_count: int, last_newline1: int):
+        self.count, self.held, self.last_newline1 = 0, [], int(last_newline1)
+        # never applies: a list of at most 10 records, or a text without a newline
+        self.rule = False if (max_count <= STALE_AFTER or not last_newline1) else None
+
+    def add(self, m: int, fetch):
+        """the next piece brought m records; fetch() -> their (start, end) pairs, asked for only while undecided (then m <= 10).
+        -> (held records to format first, each in a call of its own; how many of the piece's records to format now;
+        stale_rule for both)"""
+        self.count += int(m)
+        if self.rule is None and self.count > STALE_AFTER:
+            self.rule = True
+        if self.rule is not None:
+            flush, self.held = self.held, []
+            return flush, int(m), self.rule
+        recs = [(int(s), int(e)) for s, e in fetch()] if m else []
+        now = 0 if self.held else sum(1 for s, _ in recs if s < self.last_newline1)  # (ascending: a prefix)
+        self.held += recs[now:]
+        return [], now, False
+
+    def end(self):
+        """the text has ended -> (held records to format, stale_rule): undecided until now means at most 10 records"""
+        if self.rule is None:
+            self.rule = False
+        flush, self.held = self.held, []
+        return flush, self.rule
 
 
 _engine = None

@@ -1,8 +1,8 @@
 """A/B of several builds of libkrep_gpu.so IN ONE PROCESS on the same HBM buffers (development aid).
 Process-to-process variance of a 32 GiB scan is +-4 % on this part (placement), far above most kernel-level differences.
-usage: python tools/ab_bench.py <gib> <kind: 2 literal8 | 3 memchr1 | 4 ac1000> <mode: pos|count|lines|format> <variant.so> [...]
+usage: python tools/ab_bench.py <gib> <kind: 2 literal8 | 3 memchr1 | 4 ac1000> <mode: pos|count|lines|format|matches> <variant.so> [...]
 mode format: not the scan but krep_gpu_format_lines of every build on ONE record list (the first build's scan), calls alternating,
-events around each call; name a build twice to see the spread it shows against itself."""
+events around each call; name a build twice to see the spread it shows against itself.  mode matches: the same for krep_gpu_format_matches."""
 import os, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,7 +28,7 @@ engs[0][1].generate(buf.data_ptr(), n, 0, wl["kind"], 42, wl["plant"], wl["perio
 if os.environ.get("AB_PATTERN"):
     wl["patterns"] = [os.environ["AB_PATTERN"].encode()]
 kw = dict(count_lines=True, only_match=True) if mode == "count" else dict(count_lines=True) if mode == "lines" else {}
-cap = (n // int(os.environ.get("AB_CAP_DIV", "50" if kind == 3 else "1500"))) + 4096 if mode in ("pos", "format") else 0  # (AB_CAP_DIV: denser patterns through AB_PATTERN)
+cap = (n // int(os.environ.get("AB_CAP_DIV", "50" if kind == 3 else "1500"))) + 4096 if mode in ("pos", "format", "matches") else 0  # (AB_CAP_DIV: denser patterns through AB_PATTERN)
 pos = torch.empty(2 * cap, dtype=torch.int64, device="cuda") if cap else None
 plans = []
 for name, e in engs:  # the environment of a variant also holds while its plan (and tables) are built
@@ -38,20 +38,25 @@ for name, e in engs:  # the environment of a variant also holds while its plan (
         os.environ.pop(k, None)
 times = {name: [] for name, _ in plans}
 counts = {}
-if mode == "format":
+if mode in ("format", "matches"):
     out = plans[0][1].scan(buf.data_ptr(), n, 0, n, 0, pos.data_ptr(), cap)
     assert not out.overflow
     m = int(out.stored)
     if len(wl["patterns"]) > 1:
         engs[0][1].order_by_start(pos.data_ptr(), m, n)
     prefix = b"corpus.txt:"
-    nbytes = int(engs[0][1].format_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, prefix).out_bytes)
+    what = "krep_gpu_format_lines" if mode == "format" else "krep_gpu_format_matches"
+    def fmt_call(e, d_out=0, capacity=0):
+        if mode == "format":
+            return e.format_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, prefix, d_out, capacity)
+        return e.format_matches(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, abi.MatchFormat(prefix), d_out, capacity)
+    nbytes = int(fmt_call(engs[0][1]).out_bytes)
     dst = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda")
     for rep in range(int(os.environ.get("AB_REPS", "9")) + 2):
         for name, e in engs:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            r = e.format_lines(buf.data_ptr(), n, pos.data_ptr(), m, abi.SIZE_MAX, prefix, dst.data_ptr(), nbytes)
+            r = fmt_call(e, dst.data_ptr(), nbytes)
             e1.record()
             e1.synchronize()
             assert r.out_bytes == nbytes and not r.overflow
@@ -59,7 +64,7 @@ if mode == "format":
                 times[name].append(e0.elapsed_time(e1))
     for name, _ in engs:
         t = times[name]
-        print(f"{name:40s} krep_gpu_format_lines kind={kind} {m} records, out_bytes {nbytes}: median {statistics.median(t):7.3f} ms "
+        print(f"{name:40s} {what} kind={kind} {m} records, out_bytes {nbytes}: median {statistics.median(t):7.3f} ms "
               f"[{min(t):.3f} .. {max(t):.3f}]")
     sys.exit(0)
 for rep in range(int(os.environ.get("AB_REPS", "9"))):

@@ -4,7 +4,8 @@ alternating, in ONE process with the text resident.
 Events around the calls, warmed up.  Beside them the floor from the bytes moved: the text once + 16 B per record + 2 x out_bytes
 at the measured streaming rate (bench.HBM_MEASURED_GBS).
 --windows K adds a row: the same text formatted as K windows of text/K bytes through krep_gpu_format_lines_window (each window's buffer a
-slice of the resident text, 4 KiB of left context, a 1 MiB halo, its records a slice of the one list), the K calls of a repetition summed.
+slice of the resident text, 4 KiB of left context, a 1 MiB halo, its records a slice of the one list), the K calls of a repetition summed;
+and one for the -o form through krep_gpu_format_matches_window (buffer [lo, hi + 4 KiB), the records that start in [lo, hi), carries chained).
 usage: python tools/lines_bench.py [--gib 32] [--reps 9] [--warmup 2] [--only literal8|ac1000] [--windows 8] [--out profiles/lines_on_device.txt]"""
 import argparse
 import os
@@ -99,6 +100,32 @@ def main():
             windows()
             assert torch.equal(dst[:cbytes], dst2[:cbytes]), "the windows do not concatenate to the whole-text output"
             calls[f"krep_gpu_format_lines_window x{K}"] = windows
+            # the -o form the same way: window k holds the records that start in [lo, hi) in the buffer [lo, hi + 4 KiB), count_to is
+            # the next window's base, the newline count and the stale line number are chained from call to call, live in every repetition
+            last1, at = 0, n
+            while at > 0 and not last1:
+                lo = max(at - (1 << 24), 0)
+                hit = (buf[lo:at] == 10).nonzero()
+                last1 = lo + int(hit[-1]) + 1 if hit.numel() else 0
+                at = lo
+            edges = [n * k // K for k in range(K + 1)]
+            idx = [int(x) for x in torch.searchsorted(starts, torch.tensor(edges, dtype=torch.int64, device="cuda"))]
+            dst3 = torch.empty(obytes + 64, dtype=torch.uint8, device="cuda")
+
+            def matches_windows():
+                nl = stale = at = 0
+                for k in range(K):
+                    lo, hi = edges[k], edges[k + 1]
+                    win = abi.MatchesWindow(lo, n, hi, nl, last1, stale, int(m > 10))
+                    r = eng.format_matches_window(buf.data_ptr() + lo, min(hi + 4096, n) - lo, win, pos.data_ptr() + 16 * idx[k],
+                                                  idx[k + 1] - idx[k], abi.SIZE_MAX, fmt, dst3.data_ptr() + at, obytes - at)
+                    assert not r.matches.overflow
+                    nl, stale, at = int(r.newlines_before_count_to), int(r.stale_line), at + int(r.matches.out_bytes)
+                return at
+            calls["krep_gpu_format_matches"]()
+            assert matches_windows() == obytes
+            assert torch.equal(dst[:obytes], dst3[:obytes]), "the -o windows do not concatenate to the whole-text output"
+            calls[f"krep_gpu_format_matches_window x{K}"] = matches_windows
         ms = {k: [] for k in calls}
         for rep in range(args.warmup + args.reps):
             for k, f in calls.items():
@@ -112,12 +139,12 @@ def main():
         lines.append(f"{name}: text {n} B, {m} records, {L} lines ({int(q.capped_lines)} capped), out_bytes {nbytes}, "
                      f"coloured out_bytes {cbytes}, -o out_bytes {obytes}")
         for k, v in ms.items():
-            moved = n + 16 * m + 2 * {"krep_gpu_format_lines": nbytes, "krep_gpu_format_lines_ex": cbytes, "krep_gpu_format_matches": obytes}.get(k, cbytes if "window" in k else 0)
+            moved = n + 16 * m + 2 * {"krep_gpu_format_lines": nbytes, "krep_gpu_format_lines_ex": cbytes, "krep_gpu_format_matches": obytes}.get(k, obytes if "matches_window" in k else cbytes if "window" in k else 0)
             lines.append(f"  {k:26s} {statistics.median(v):9.3f} ms [{min(v):.3f} .. {max(v):.3f}]   floor {moved / bench.HBM_MEASURED_GBS / 1e6:7.3f} ms")
         plan.close()
         del pos, lineno, spans, first, dst
         if args.windows:
-            del dst2, starts
+            del dst2, dst3, starts
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
