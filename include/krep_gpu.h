@@ -23,7 +23,8 @@
  *     KREP_GPU_FAILED, which the caller must test (the error_flag path of krep.c:2940-2947).
  * search_buffer() returns 0 match / 1 no match / 2 error exactly like search_file()/search_string()
  * (krep.h:159,168).  The library itself contains no CPU implementation of any search: a fallback is
- * always the CALLER's function.
+ * always the CALLER's function.  (krep_gpu_regex_compile() asks libc's regcomp / regexec which bytes each one-byte atom of a
+ * pattern matches — 256 one-byte probes per atom, while the plan is made; that is a table, no search of a text.)
  */
 #ifndef KREP_GPU_H
 #define KREP_GPU_H
@@ -110,7 +111,8 @@ enum krep_ref_algo
     KREP_RA_AVX512 = 7,       /* simd_avx512_search   krep.c:5108 (33..64 B body) */
     KREP_RA_NEON = 8,         /* neon_search          krep.c:4506 */
     KREP_RA_AHO_CORASICK = 9, /* aho_corasick_search  aho_corasick.c:299 */
-    KREP_RA_REGEX = 10        /* regex_search — out of scope, never executed here */
+    KREP_RA_REGEX = 10        /* regex_search         krep.c:1389 — the fixed-length class sequences of
+                                 krep_gpu_regex_compile() below; every other expression stays on the CPU */
 };
 
 /* All of it in one explicit object.  Plans and search_buffer_ex() carry their configuration; the setters below write the
@@ -221,8 +223,12 @@ uint64_t krep_gpu_literal_search(const search_params_t *params, const char *text
                                  size_t text_len, match_result_t *result);
 uint64_t krep_gpu_aho_corasick_search(const search_params_t *params, const char *text_start,
                                       size_t text_len, match_result_t *result);
-/* Drop-in for select_search_algorithm(): returns one of the two functions above, or NULL when the backend does not
- * take the search — no usable device (krep_gpu_available() == 0), regex_search, and the input classes
+/* regex_search (krep.c:1389-1579) for the patterns krep_gpu_regex_compile() accepts; params->compiled_regex is never read here
+ * and goes to the registered CPU function untouched when the attempt fails. */
+uint64_t krep_gpu_regex_search(const search_params_t *params, const char *text_start,
+                               size_t text_len, match_result_t *result);
+/* Drop-in for select_search_algorithm(): returns one of the three functions above, or NULL when the backend does not
+ * take the search — no usable device (krep_gpu_available() == 0), a regex krep_gpu_regex_compile() refuses, and the input classes
  * krep_gpu_can_accelerate() names — so that the caller keeps the CPU function pointer the reference's own
  * select_search_algorithm() gives it.  (-c through simd_sse42_search / kmp_search with a newline inside the pattern, refused
  * until round 3, is reproduced: one device thread walks the ordered occurrence list the way the reference's loop moves.) */
@@ -230,12 +236,55 @@ search_func_t krep_gpu_select_search_algorithm(const search_params_t *params);
 /* 1 when the backend takes the search for `params` under the current configuration, 0 when not:
  *   - no usable gfx950 device (krep_gpu_available() == 0);
  *   - no pattern at all (num_patterns == 0 and pattern == NULL);
- *   - use_regex.
+ *   - use_regex with a pattern krep_gpu_regex_compile() refuses (anything that is not a fixed number of byte classes in a
+ *     row, several patterns, -w).
  * (count_lines_mode together with only_matching through memchr_short_search — a combination krep's main() never produces,
  * krep.c:3811-3814 — was refused until round 5 and is reproduced now: one window, krep_gpu_split_mode() = WHOLE.)
  * An operator called with such params anyway treats it like a run-time failure (see the top of this header): the
  * registered CPU function answers, or status KREP_GPU_FAILED; nothing is silently approximated. */
 int krep_gpu_can_accelerate(const search_params_t *params);
+
+/* ---- krep -E on the device: fixed-length class sequences ----
+ * Most -E patterns are a fixed number of byte classes in a row (Sherl[oO]ck, [0-9]{3}-[0-9]{4}, 0x[0-9a-f]{8}); those are
+ * scanned on the device, every other expression stays with krep's regex_search.  The compiler is a TOKENISER: it cuts
+ * params->pattern (or patterns[0]) into atoms and interprets none of them.
+ * Accepted atoms: an ordinary byte; '\' followed by a punctuation byte; '.'; a bracket expression, whose closing ']' is found
+ *   by POSIX's rules (an optional '^', a ']' directly behind '[' or '[^' is literal, [:name:] [.x.] [=x=] are stepped over).
+ *   Each atom may be followed by {n}, n >= 1, which repeats it.  The atoms in a row are the L byte classes C0..C(L-1), 1 <= L <= 16.
+ * Refused (2, the reason in krep_gpu_last_error()): ( ) * + ? | ^ $ outside brackets; {n,} and {n,m}; '{' not behind an atom;
+ *   '\' followed by a letter or digit (\b, \w, \1, ...); a pattern byte outside 0x01-0x7F; L outside 1..16; num_patterns > 1
+ *   (the CLI turns several -e into an alternation); whole_word — the CLI compiles \bPATTERN\b (krep.c:2122-2135) and still calls
+ *   is_whole_word_match(), a library caller compiles PATTERN alone, the operator sees only params->pattern and never the compiled
+ *   expression, and the two forms disagree on real texts: there is no single behaviour to reproduce.  Also refused: every pattern
+ *   while the process runs in a multibyte locale (MB_CUR_MAX > 1, a caller that called setlocale()): libc's regexec matches
+ *   characters there — '.', a negated or named class and, under REG_ICASE, even a letter take a whole multibyte sequence as one
+ *   atom — so nothing is a fixed number of byte classes.  krep itself never calls setlocale() and runs in the C locale.
+ * Classes: every atom's substring is compiled ALONE with regcomp(REG_EXTENDED | REG_NEWLINE | (case_sensitive ? 0 : REG_ICASE)),
+ *   the flags of krep.c:2148, and all 256 one-byte texts are put to regexec(REG_STARTEND): the class is what matched.  So the
+ *   classes are those of the libc the caller's own regexec uses, wherever the library runs — in glibc's C locale '.' is 0x01-0x7F
+ *   without '\n' (no NUL, no byte >= 0x80), [^a] holds NUL but no byte >= 0x80 and no '\n' and loses 'A' too under REG_ICASE,
+ *   [[:space:]] holds '\n' — and no table written down here can be wrong about them.
+ * What a scan reproduces (regex_search's REG_STARTEND loop, which resumes at the match's end, krep.c:1539-1568): an occurrence
+ *   is a position p with text[p + j] in Cj for all j, p + L <= text_len.  Matches: the greedy leftmost non-overlapping
+ *   occurrences, each (p, p + L).  -c: the distinct lines that hold the START of an occurrence (overlap does not matter: after a
+ *   counted line the reference jumps to the next line start); a start ON a '\n' belongs to the line that newline ends.
+ *   max_count: the return value is min(total, max_count), the records are the first max_count; max_count == 0 returns 0 when
+ *   count_lines_mode or track_positions is set and otherwise 1 as soon as one occurrence exists (krep.c:1395, :1533).
+ *   only_matching and reference_simd change nothing.
+ * Split: a pattern that cannot overlap itself (self_overlap == 0: for no shift d in 1..L-1 do Cj and C(j+d) meet for every j),
+ *   and every pattern under -c, is KREP_GPU_SPLIT_PIECES.  A self-overlapping pattern without -c goes through the greedy pass over
+ *   the occurrence list: KREP_GPU_SPLIT_WHOLE, and a window that is not the whole text is refused (2). */
+typedef struct krep_gpu_regex_info
+{
+    uint32_t L;               /* byte classes in a row, 1..16                                            */
+    uint8_t classes[16][32];  /* class j as a 256-bit set: byte b is in it iff classes[j][b >> 3] >> (b & 7) & 1 */
+    int self_overlap;         /* 1: two occurrences may overlap (the greedy pass decides which are matches)      */
+    uint32_t anchor;          /* index of the class with the fewest bytes (the first such)                */
+    uint8_t anchor_bytes[4];  /* its bytes, ascending, when there are at most 4 of them                   */
+    uint32_t n_anchor;        /* how many of anchor_bytes are set; 0: the class holds more than 4 bytes (or none) */
+} krep_gpu_regex_info_t;
+/* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
+int krep_gpu_regex_compile(const search_params_t *params, krep_gpu_regex_info_t *out);
 
 /* The in-memory twin of search_file()/search_string() that BASELINE.json calls search_buffer():
  * validation as krep.c:2013-2049 (no patterns -> 2; empty pattern among several -> 2; pattern
@@ -395,8 +444,9 @@ int krep_gpu_replay_tail(krep_gpu_plan_t *plan, const void *d_tail, size_t tail_
 /* How a text of text_len bytes may be cut for `params` under the current configuration. */
 enum krep_gpu_split
 {
-    KREP_GPU_SPLIT_WHOLE = 0,  /* one window only: neon_search's max_count == 0 corner, and -c with -o through
-                                  memchr_short_search (never produced by krep's main())                                    */
+    KREP_GPU_SPLIT_WHOLE = 0,  /* one window only: neon_search's max_count == 0 corner, -c with -o through
+                                  memchr_short_search (never produced by krep's main()), and a regex that can overlap
+                                  itself without -c (krep_gpu_regex_compile)                                               */
     KREP_GPU_SPLIT_PIECES = 1, /* independent pieces: start-offset ownership + halo, results concatenate / merge          */
     KREP_GPU_SPLIT_CHAIN = 2   /* pieces in text order through krep_gpu_scan_device_seq() (round 5: also -c with a newline
                                   inside a pattern, multi-pattern and through simd_sse42_search / kmp_search)             */

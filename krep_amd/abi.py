@@ -130,6 +130,16 @@ class Cost(C.Structure):
                 ("cpu_threads", C.c_int), ("cpu_algo", C.c_int), ("device_ready", C.c_int)]
 
 
+class RegexInfo(C.Structure):
+    """krep_gpu_regex_info_t: what krep_gpu_regex_compile() makes of an -E pattern"""
+    _fields_ = [("L", C.c_uint32), ("classes", (C.c_uint8 * 32) * 16), ("self_overlap", C.c_int), ("anchor", C.c_uint32),
+                ("anchor_bytes", C.c_uint8 * 4), ("n_anchor", C.c_uint32)]
+
+    def class_bytes(self, j: int) -> bytes:
+        """the bytes of class j, ascending"""
+        return bytes(b for b in range(256) if (self.classes[j][b >> 3] >> (b & 7)) & 1)
+
+
 class ShardInfo(C.Structure):
     """krep_gpu_shard_info_t: where the calling thread's last sharded host search ran."""
     _fields_ = [("shards", C.c_int), ("devices_used", C.c_int), ("device_ids", C.c_int * 16), ("comm_ranks", C.c_int),
@@ -158,10 +168,12 @@ class Placement(C.Structure):
 
 
 class Params:
-    """Owns the Python-side buffers a search_params_t points into."""
+    """Owns the Python-side buffers a search_params_t points into.  regex=True sets use_regex (krep -E): the library takes such a search
+    only in the C locale — Python enters the environment's locale at start-up, so call locale.setlocale(locale.LC_CTYPE, "C") before
+    Engine.search / Engine.plan / Engine.regex_compile, or every pattern is refused (Engine.regex_compile says why)."""
 
     def __init__(self, patterns: Sequence[bytes], *, case_sensitive=True, count_lines=False,
-                 only_match=False, whole_word=False, max_count=SIZE_MAX, track_positions=None):
+                 only_match=False, whole_word=False, max_count=SIZE_MAX, track_positions=None, regex=False):
         pats = [bytes(p) for p in patterns]
         self._pats = pats
         n = len(pats)
@@ -177,7 +189,7 @@ class Params:
             s.pattern = pats[0]
             s.pattern_len = len(pats[0])
         s.case_sensitive = case_sensitive
-        s.use_regex = False
+        s.use_regex = bool(regex)
         # create_base_params(), test/test_krep.c:225-229
         s.count_lines_mode = bool(count_lines and not only_match)
         s.count_matches_mode = bool(count_lines and only_match)

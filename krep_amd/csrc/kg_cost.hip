@@ -156,6 +156,8 @@ extern "C" int krep_gpu_cost_estimate(const search_params_t *p, size_t text_len,
         q.pattern_len = p->pattern_lens[0];
     }
     const int algo = p->use_regex ? KREP_RA_REGEX : kg::mirror_effective(kg::mirror_top(&q, c), &q, text_len);
+    if (algo == KREP_RA_REGEX)
+        threads = 1; // regex_search: ONE thread at the scalar rate whatever the caller runs — deliberately generous to the CPU side
     double per = r.cpu_scalar_gbps, cap = r.cpu_scalar_cap_gbps;
     switch (algo)
     {

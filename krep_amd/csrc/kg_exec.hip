@@ -730,6 +730,8 @@ std::vector<Piece> piece_layout(const PieceJob &job, size_t chunk, int ndev)
     size_t lmax = 1;
     for (size_t i = 0; i < job.params->num_patterns; ++i)
         lmax = std::max(lmax, job.params->pattern_lens[i]);
+    if (job.params->use_regex)
+        lmax = std::max<size_t>(lmax, 16); // a{16} is five pattern bytes and sixteen text bytes: the halo follows L <= 16
     const size_t ctx = lmax + 1; // pattern_len-1 to complete straddling matches, +1 for -w, +1 slack
     const size_t share = (len + (size_t)job.G - 1) / (size_t)job.G;
     std::vector<Piece> pcs;
@@ -966,7 +968,8 @@ uint64_t piece_verdict(const PieceJob &job, uint64_t total, uint64_t lines)
 {
     const search_params_t *params = job.params;
     if (params->max_count == 0)
-        return (job.algo == KREP_RA_BMH || job.algo == KREP_RA_MEMCHR_SHORT || job.algo == KREP_RA_AVX2 || job.algo == KREP_RA_AVX512) &&
+        return (job.algo == KREP_RA_BMH || job.algo == KREP_RA_MEMCHR_SHORT || job.algo == KREP_RA_AVX2 || job.algo == KREP_RA_AVX512 ||
+                job.algo == KREP_RA_REGEX) &&
                        !params->count_lines_mode && !params->track_positions
                    ? (total > 0 ? 1 : 0) // count-only: the first hit makes 1 >= 0 true (krep.c:1355-1367)
                    : 0;

@@ -124,7 +124,7 @@ static uint64_t run_with_fallback(const search_params_t *params, const char *tex
     }
     const krep_gpu_cpu_select_t sel = g_cpu_select.load();
     search_func_t cpu = (sel && params && allow_fallback) ? sel(params) : nullptr;
-    if (cpu == krep_gpu_literal_search || cpu == krep_gpu_aho_corasick_search)
+    if (cpu == krep_gpu_literal_search || cpu == krep_gpu_aho_corasick_search || cpu == krep_gpu_regex_search)
         cpu = nullptr; // a selector that hands our own operators back would recurse
     if (!cpu)
     {
@@ -156,6 +156,11 @@ extern "C" uint64_t krep_gpu_aho_corasick_search(const search_params_t *params, 
     const krep_gpu_config_t cfg = kg::current_config();
     return run_with_fallback(params, text, len, result, cfg, cfg.num_gpus, nullptr);
 }
+extern "C" uint64_t krep_gpu_regex_search(const search_params_t *params, const char *text, size_t len, match_result_t *result)
+{
+    const krep_gpu_config_t cfg = kg::current_config();
+    return run_with_fallback(params, text, len, result, cfg, cfg.num_gpus, nullptr);
+}
 extern "C" search_func_t krep_gpu_select_search_algorithm(const search_params_t *params)
 {
     if (!params)
@@ -182,6 +187,8 @@ extern "C" search_func_t krep_gpu_select_search_algorithm(const search_params_t 
                 krep_gpu_clear_error();
         }
     }
+    if (params->use_regex)
+        return krep_gpu_regex_search;
     return params->num_patterns > 1 ? krep_gpu_aho_corasick_search : krep_gpu_literal_search;
 }
 
@@ -196,8 +203,6 @@ extern "C" int search_buffer_ex(const search_params_t *params, const char *buf, 
         return kg::fail("Error: No pattern specified.");
     if (!buf && len)
         return kg::fail("Error: NULL text in search_buffer.");
-    if (params->use_regex)
-        return kg::fail("regex search is not accelerated; keep krep's regex_search for it");
     for (size_t i = 0; i < params->num_patterns; ++i)
     {
         if (params->pattern_lens[i] == 0)

@@ -9,6 +9,8 @@
 #include "kg_common.h"
 #include "kg_internal.h"
 
+namespace kg { struct RegexProg; } // kg_regex.hip
+
 struct krep_gpu_plan
 {
     krep_gpu_config_t cfg{};     // the configuration this plan was compiled for (explicit; no global is read after creation)
@@ -34,6 +36,8 @@ struct krep_gpu_plan
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // multi-pattern
     kg::AcTables *ac = nullptr;
+    // regex (KREP_RA_REGEX): the compiled class sequence and its device table (kg_regex.hip)
+    kg::RegexProg *rx = nullptr;
     // a dictionary with 1..3-byte patterns beside many longer ones, on a text where the longer ones gain from anchors (kg_scan_ac.hip
     // scan_ac_split, round 6): the two parts as dictionaries of their own, scanned one after the other, their record lists merged
     kg::AcTables *ac_long = nullptr, *ac_short = nullptr;
@@ -90,4 +94,10 @@ int nl_reserve(krep_gpu_plan *pl, uint64_t need, uint64_t want, bool with_ln);
 // kg_scan_ac.hip: the multi-pattern scan of a window (scan_device_impl behind its common checks)
 int scan_ac(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
             const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out);
+// kg_regex.hip: the program of an accepted -E pattern (NULL: refused or out of memory, the reason in krep_gpu_last_error()), and
+// the regex scan of a window
+RegexProg *regex_prog_create(const search_params_t &sp);
+void regex_prog_free(RegexProg *rx);
+int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
+               const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out);
 } // namespace kg

@@ -87,7 +87,7 @@ extern "C" krep_gpu_plan_t *krep_gpu_plan_create_ex(const search_params_t *p, co
     bool ok = hipMalloc(&pl->d_ctr, sizeof(Counters)) == hipSuccess &&
               hipHostMalloc(&pl->h_ctr, sizeof(Counters)) == hipSuccess &&
               hipEventCreate(&pl->ev0) == hipSuccess && hipEventCreate(&pl->ev1) == hipSuccess;
-    if (ok && pl->sp.num_patterns == 1 && pl->pats[0].size() >= 1)
+    if (ok && pl->sp.num_patterns == 1 && pl->pats[0].size() >= 1 && !pl->sp.use_regex)
     {
         const auto &raw = pl->pats[0];
         pl->m = (uint32_t)raw.size();
@@ -150,6 +150,11 @@ extern "C" krep_gpu_plan_t *krep_gpu_plan_create_ex(const search_params_t *p, co
                  hipMemcpy(pl->d_pat_chunks, ch.data(), ch.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
         }
     }
+    if (ok && pl->ref_algo == KREP_RA_REGEX && !pl->unsupported)
+    {
+        pl->rx = regex_prog_create(pl->sp);
+        ok = pl->rx != nullptr;
+    }
     if (ok && pl->ref_algo == KREP_RA_AHO_CORASICK)
     {
         for (auto &v : pl->pats)
@@ -194,6 +199,7 @@ extern "C" void krep_gpu_plan_destroy(krep_gpu_plan_t *pl)
     if (pl->ev0) DBGFREE(hipEventDestroy(pl->ev0));
     if (pl->ev1) DBGFREE(hipEventDestroy(pl->ev1));
     if (pl->ac) ac_free(pl->ac);
+    regex_prog_free(pl->rx);
     if (pl->ac_long) ac_free(pl->ac_long);
     if (pl->ac_short) ac_free(pl->ac_short);
     if (pl->d_split_rec) DBGFREE(hipFree(pl->d_split_rec));

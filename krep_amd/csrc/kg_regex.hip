@@ -1,0 +1,479 @@
+// kg_regex.hip — krep -E for fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile): the exported pattern
+// compiler (kg_regex_compile.h), the bit-parallel shift-and scan kernel and its driver kg::scan_regex.
+//
+// The kernel.  T[byte] is a 16-bit mask, bit j set when byte is in class Cj.  It sits in LDS once per bank (entry b of copy k at
+// dword b * 32 + k, a lane reads copy lane % 32), so the 64 lookups of a wave instruction never meet in a bank whatever the
+// text holds.  A lane takes 16 bytes and runs S = ((S << 1) | 1) & T[b] over them from the optimistic state 0xFFFF.  Because
+// L <= 16 its EXIT state is exact from its own bytes; one cross-lane move hands it to the next lane as that lane's true entry
+// state E (lane 0: the exit of lane 63 of the cell before, kept in a scalar).  The optimistic walk already knows everything
+// about a match that ends at the lane's byte k except the part in front of the lane: for k >= L - 1 nothing is in front, for
+// k < L - 1 the match is real iff bit L - 2 - k of E is set.  So the hits are H & ((0xFFFF << (L-1)) | reverse(E's low L-1 bits)):
+// one walk, no second pass over the bytes.
+// Coordinates: a match is seen at its END byte e = start + L - 1, so the whole kernel works in end coordinates: start s is at
+// coordinate s + L - 1, and for -c a newline at byte n is put at coordinate n + L - 1 as well (its mask shifted across the lane
+// boundary the same way).  Ownership is by START in [own_lo, hi_match); a unit is 32 KiB of coordinates, units are contiguous
+// and in order, so their info words compose in kg_post.hip like those of every other scan.
+// Anchor fast path (patterns whose smallest class holds 1..4 bytes, no -c): a cell is walked only when it or the cell in front of
+// it holds an anchor byte (a match that ends in the cell has its anchor byte in one of the two); after skipped cells the entry
+// state of lane 0 is rebuilt from the 16 bytes in front of the cell (kept in scalars), once.
+// Reads: no byte outside [0, text_len) — whole 8-KiB rounds inside the text are vector loads, everything else is guarded per byte.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/krep_gpu.h"
+#include "kg_common.h"
+#include "kg_device.h"
+#include "kg_internal.h"
+#include "kg_plan.h"
+#include "kg_regex_compile.h"
+
+namespace kg {
+
+struct RegexProg
+{
+    krep_gpu_regex_info_t info{};
+    u32 *d_table = nullptr; // T[256]
+};
+
+constexpr u32 kRxUnitBytes = kRoundsBig * kSegBytes; // 32 KiB of coordinates per wave unit
+
+struct RxArgs
+{
+    const uint8_t *text;
+    u64 text_len;
+    u64 anchor;          // grid origin: a multiple of 16, <= own_lo
+    u64 own_lo, hi_match; // starts in [own_lo, hi_match) are matches; hi_match + L - 1 <= text_len
+    u64 nl_hi;           // -c: the newlines of bytes [own_lo, nl_hi) take part (nl_hi <= text_len)
+    u64 cov_hi;          // coordinates >= cov_hi hold nothing
+    u64 n_units;
+    u64 global_base;
+    u32 L;
+    u32 n_anchor;
+    u32 ab[4];           // the anchor bytes, each in every byte lane
+    const u32 *table;
+    u64 *unitinfo;       // count mode: per-unit info words (nullptr: only the total is wanted)
+    const u64 *offsets;  // emit mode: exclusive index of each unit's first record
+    u64 *positions;
+    u64 pos_cap;
+    Counters *ctr;
+};
+
+// 16 bytes from `off`, bytes at or past text_len read as 0
+static __device__ __noinline__ uint4 rx_load_guarded(const uint8_t *text, u64 text_len, u64 off)
+{
+    u32 v[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+    {
+        u32 x = 0;
+        for (int b = 0; b < 4; ++b)
+        {
+            const u64 o = off + (u64)(w * 4 + b);
+            if (o < text_len)
+                x |= (u32)text[o] << (8 * b);
+        }
+        v[w] = x;
+    }
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+// bit k set iff lo <= q + k < hi, k = 0..15
+static __device__ __forceinline__ u32 rx_range(u64 q, u64 lo, u64 hi)
+{
+    const u32 lk = lo > q ? (u32)min(lo - q, (u64)16) : 0u, hk = hi > q ? (u32)min(hi - q, (u64)16) : 0u;
+    return ((1u << hk) - 1u) & ~((1u << lk) - 1u);
+}
+// the optimistic walk over a lane's 16 bytes: bit k of the result = bit L-1 of the state behind byte k; X = the exit state
+static __device__ __forceinline__ u32 rx_walk(const u32 *T, const uint4 &d, u32 Lm1, u32 &X)
+{
+    const u32 w[4] = {d.x, d.y, d.z, d.w};
+    u32 S = 0xffffu, H = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+    {
+        const u32 b = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
+        S = ((S << 1) | 1u) & T[b << 5];
+        H = (H >> 1) | ((S >> Lm1) << 31);
+    }
+    X = S;
+    return H >> 16;
+}
+static __device__ __forceinline__ u32 rx_newlines(const uint4 &d)
+{
+    return movemask4(eq_bytes(d.x, 0x0a0a0a0au)) | (movemask4(eq_bytes(d.y, 0x0a0a0a0au)) << 4) |
+           (movemask4(eq_bytes(d.z, 0x0a0a0a0au)) << 8) | (movemask4(eq_bytes(d.w, 0x0a0a0a0au)) << 12);
+}
+
+template <bool ANCH, bool LINES, bool EMIT>
+__global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
+{
+    static_assert(!(ANCH && LINES) && !(LINES && EMIT), "-c walks every cell and writes no records");
+    __shared__ u32 s_T[256 * 32];
+    for (u32 i = threadIdx.x; i < 256u * 32u; i += kBlock)
+        s_T[i] = a.table[i >> 5];
+    __syncthreads();
+    const u32 lane = lane_id(), wave = threadIdx.x >> 6;
+    const u32 *T = s_T + (lane & 31u);
+    const u32 Lm1 = a.L - 1u;
+    const u64 c_lo = a.own_lo + Lm1, c_hi = a.hi_match + Lm1; // the coordinates of the owned starts
+    const u64 n_waves = (u64)gridDim.x * kWavesPerBlk;
+    u64 acc_total = 0;
+
+    for (u64 unit = (u64)blockIdx.x * kWavesPerBlk + wave; unit < a.n_units; unit += n_waves)
+    {
+        const u64 ubase = a.anchor + unit * kRxUnitBytes;
+        // the 16 bytes in front of the unit give lane 0 its entry state (and, for -c, the newlines that shift into the unit)
+        u32 x63 = 0; // exit state | raw newline mask << 16 of the 16 bytes in front of the next cell (uniform)
+        if (ubase != 0)
+        {
+            const uint4 p = rx_load_guarded(a.text, a.text_len, ubase - 16);
+            u32 X;
+            (void)rx_walk(T, p, Lm1, X);
+            x63 = X;
+            if (LINES)
+                x63 |= (rx_newlines(p) & rx_range(ubase - 16, a.own_lo, a.nl_hi)) << 16;
+            x63 = __builtin_amdgcn_readfirstlane(x63);
+        }
+        bool have_state = true, prev_anch = true; // ANCH: x63 is valid | the cell in front holds an anchor byte (unknown: yes)
+        u32 p63[4] = {0, 0, 0, 0};                // ANCH: lane 63's bytes of the last skipped cell
+        u32 l_hits = 0;                           // per lane
+        u64 out_idx = EMIT ? a.offsets[unit] : 0; // uniform
+        // -c: the line state of the unit, as kg_literal.hip keeps it (carry arithmetic over the 64 lanes of a cell)
+        u32 l_cnt = 0, s_new = 0;
+        bool s_open = false, s_seen = false, s_head = false;
+        auto line_cell = [&](u64 B_nl, u64 B_any, u64 B_head, u64 B_tail) __attribute__((always_inline)) {
+            const u64 G = B_tail, P = ~(B_nl | B_any);
+            const unsigned __int128 sum = (unsigned __int128)(G | P) + G + (s_open ? 1u : 0u);
+            const u64 O = (u64)sum ^ P; // bit l: the line entering lane l already holds a match
+            s_new += (u32)__popcll(B_head & ~O);
+            if (!s_seen && B_nl)
+            {
+                const int f = __builtin_ctzll(B_nl);
+                s_head = (((O | B_head) >> f) & 1ull) != 0ull;
+                s_seen = true;
+            }
+            s_open = (u64)(sum >> 64) != 0ull;
+        };
+
+        for (int r = 0; r < kRoundsBig; ++r)
+        {
+            const u64 seg = ubase + (u64)r * kSegBytes;
+            if (seg >= a.cov_hi)
+                break;
+            const bool fast = seg + kSegBytes <= a.text_len;
+            uint4 d[kCells];
+            if (fast)
+            {
+                const uint4 *src = reinterpret_cast<const uint4 *>(a.text + seg) + lane;
+#pragma unroll
+                for (int j = 0; j < kCells; ++j)
+                {
+                    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+                    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + j * kWave));
+                    d[j] = make_uint4(v.x, v.y, v.z, v.w);
+                }
+            }
+            else
+            {
+#pragma unroll
+                for (int j = 0; j < kCells; ++j)
+                {
+                    const u64 cb = seg + (u64)j * kCellBytes;
+                    d[j] = cb < a.cov_hi ? rx_load_guarded(a.text, a.text_len, cb + (u64)lane * 16u) : make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kCells; ++j)
+            {
+                const u64 cbase = seg + (u64)j * kCellBytes;
+                if (cbase >= a.cov_hi)
+                    break;
+                const u64 q = cbase + (u64)lane * 16u;
+                bool anch = true;
+                if (ANCH)
+                {
+                    u32 f = 0;
+                    for (u32 i = 0; i < a.n_anchor; ++i)
+                        f |= eq_bytes(d[j].x, a.ab[i]) | eq_bytes(d[j].y, a.ab[i]) | eq_bytes(d[j].z, a.ab[i]) | eq_bytes(d[j].w, a.ab[i]);
+                    anch = __ballot(f != 0u) != 0ull;
+                    if (!anch && !prev_anch)
+                    {
+                        // no match ends here: keep only what the next walked cell needs for its entry state
+                        have_state = false;
+                        p63[0] = __builtin_amdgcn_readlane(d[j].x, 63);
+                        p63[1] = __builtin_amdgcn_readlane(d[j].y, 63);
+                        p63[2] = __builtin_amdgcn_readlane(d[j].z, 63);
+                        p63[3] = __builtin_amdgcn_readlane(d[j].w, 63);
+                        prev_anch = false;
+                        continue;
+                    }
+                    if (!have_state)
+                    {
+                        u32 X;
+                        (void)rx_walk(T, make_uint4(p63[0], p63[1], p63[2], p63[3]), Lm1, X);
+                        x63 = __builtin_amdgcn_readfirstlane(X);
+                        have_state = true;
+                    }
+                    prev_anch = anch;
+                }
+                u32 X;
+                u32 H = rx_walk(T, d[j], Lm1, X);
+                u32 mine = X;
+                if (LINES)
+                    mine |= (rx_newlines(d[j]) & rx_range(q, a.own_lo, a.nl_hi)) << 16;
+                u32 prev = __shfl_up(mine, 1);
+                if (lane == 0)
+                    prev = x63;
+                x63 = __builtin_amdgcn_readlane(mine, 63);
+                const u32 E = prev & 0xffffu;
+                H &= (0xffffu << Lm1) | (Lm1 ? (__brev(E) >> (32u - Lm1)) : 0u);
+                if (!(cbase >= c_lo && cbase + kCellBytes <= c_hi))
+                    H &= rx_range(q, c_lo, c_hi);
+                l_hits += (u32)__popc(H);
+                if (LINES)
+                {
+                    const u32 N = (((mine >> 16) << Lm1) | ((prev >> 16) >> (16u - Lm1))) & 0xffffu, Hs = H | N;
+                    l_cnt += (u32)__popc(H & ~(Hs - ((N << 1) & 0xffffu)));
+                    // head: the lowest flag is a match (one ON a newline belongs to the line it ends); tail: a match behind the last newline
+                    line_cell(__ballot(N != 0u), __ballot(H != 0u), __ballot((H & (Hs ^ (Hs - 1u))) != 0u),
+                              __ballot((H >> (32 - __clz((int)N))) != 0u));
+                }
+                if (EMIT)
+                {
+                    if (__ballot(H != 0u))
+                    {
+                        const u32 c = (u32)__popc(H);
+                        u32 incl = c;
+#pragma unroll
+                        for (int o = 1; o < 64; o <<= 1)
+                        {
+                            const u32 t = __shfl_up(incl, o);
+                            if (lane >= (u32)o)
+                                incl += t;
+                        }
+                        u64 idx = out_idx + (incl - c);
+                        while (H)
+                        {
+                            const u32 k = (u32)__builtin_ctz(H);
+                            H &= H - 1u;
+                            if (idx < a.pos_cap)
+                            {
+                                const u64 s0 = q + k - Lm1 + a.global_base, e0 = s0 + a.L;
+                                *reinterpret_cast<uint4 *>(a.positions + 2 * idx) = make_uint4((u32)s0, (u32)(s0 >> 32), (u32)e0, (u32)(e0 >> 32));
+                            }
+                            ++idx;
+                        }
+                        out_idx += (u32)__builtin_amdgcn_readlane(incl, 63);
+                    }
+                }
+            }
+        }
+        if (EMIT)
+            continue;
+        u32 h = l_hits, t = l_cnt;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1)
+        {
+            h += __shfl_xor(h, o);
+            if (LINES)
+                t += __shfl_xor(t, o);
+        }
+        acc_total += h;
+        if (a.unitinfo && lane == 0)
+        {
+            u64 info = (u64)h;
+            if (LINES)
+            {
+                const LineState ls{t + s_new, s_seen, s_seen ? s_head : s_open, s_open};
+                info |= line_bits(ls) | ((u64)(ls.cnt & kUiLineMask) << kUiLineShift);
+            }
+            else if (h)
+                info |= kLnHead | kLnTail;
+            a.unitinfo[unit] = info;
+        }
+    }
+    if (!EMIT && lane == 0 && acc_total)
+        atomicAdd(&a.ctr->total, acc_total);
+}
+
+template <bool ANCH, bool LINES, bool EMIT> static hipError_t rx_launch(const RxArgs &a, int num_cu, hipStream_t st)
+{
+    const u64 blocks = (a.n_units + kWavesPerBlk - 1) / kWavesPerBlk;
+    const u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 5)); // 32 KiB of LDS each: five workgroups fit a CU
+    hipLaunchKernelGGL((regex_scan<ANCH, LINES, EMIT>), dim3(grid), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+static hipError_t rx_run(const RxArgs &a, bool lines, bool emit, int num_cu, hipStream_t st)
+{
+    if (lines)
+        return rx_launch<false, true, false>(a, num_cu, st);
+    if (a.n_anchor)
+        return emit ? rx_launch<true, false, true>(a, num_cu, st) : rx_launch<true, false, false>(a, num_cu, st);
+    return emit ? rx_launch<false, false, true>(a, num_cu, st) : rx_launch<false, false, false>(a, num_cu, st);
+}
+
+// ------------------------------------------------------------------------------------------------ plan side
+RegexProg *regex_prog_create(const search_params_t &sp)
+{
+    auto *rx = new RegexProg();
+    if (const char *why = regex_compile_cached(&sp, &rx->info))
+    {
+        fail("%s", why);
+        delete rx;
+        return nullptr;
+    }
+    u32 table[256];
+    for (int b = 0; b < 256; ++b)
+    {
+        u32 m = 0;
+        for (u32 j = 0; j < rx->info.L; ++j)
+            m |= ((rx->info.classes[j][b >> 3] >> (b & 7)) & 1u) << j;
+        table[b] = m;
+    }
+    if (hipMalloc(&rx->d_table, sizeof table) != hipSuccess ||
+        hipMemcpy(rx->d_table, table, sizeof table, hipMemcpyHostToDevice) != hipSuccess)
+    {
+        fail("regex plan: device allocation failed");
+        regex_prog_free(rx);
+        return nullptr;
+    }
+    return rx;
+}
+void regex_prog_free(RegexProg *rx)
+{
+    if (!rx)
+        return;
+    if (rx->d_table) (void)hipFree(rx->d_table);
+    delete rx;
+}
+
+// ------------------------------------------------------------------------------------------------ the scan of a window
+int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
+               const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out)
+{
+    memset(out, 0, sizeof *out);
+    if (carry_out)
+        *carry_out = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
+    if (!pl->rx)
+        return fail("scan_device: the regex plan holds no program");
+    const krep_gpu_regex_info_t &info = pl->rx->info;
+    const u32 L = info.L;
+    if (w.global_len < L || w.text_len < L || w.own_lo >= w.own_hi)
+        return 0; // (text_len == 0 included: L >= 1 matches no empty string)
+    const size_t own_hi = std::min(w.own_hi, w.text_len);
+    const u64 hi_match = std::min<u64>(own_hi, w.text_len - L + 1);
+    const bool lines = pl->lines, greedy = info.self_overlap && !lines;
+    const bool whole = w.global_base == 0 && w.own_lo == 0 && own_hi + L > w.text_len && w.global_len == w.text_len;
+    if (greedy && !whole)
+        return fail("this regex can overlap itself, its matches are the greedy selection over the whole occurrence list: scan the whole "
+                    "text in one window (krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
+    if (own_hi <= w.own_lo || (!lines && hi_match <= w.own_lo))
+        return 0;
+    const size_t maxc = pl->max_count;
+    const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(maxc, cap) : 0;
+
+    RxArgs a{};
+    a.text = w.d_text; a.text_len = w.text_len;
+    a.anchor = w.own_lo & ~(u64)15;
+    a.own_lo = w.own_lo; a.hi_match = std::max<u64>(hi_match, w.own_lo);
+    a.nl_hi = own_hi;
+    a.cov_hi = (lines ? (u64)own_hi : a.hi_match) + (L - 1);
+    a.n_units = (a.cov_hi - a.anchor + kRxUnitBytes - 1) / kRxUnitBytes;
+    a.global_base = w.global_base;
+    a.L = L;
+    a.n_anchor = lines ? 0 : info.n_anchor;
+    for (u32 i = 0; i < 4; ++i)
+        a.ab[i] = 0x01010101u * info.anchor_bytes[i < info.n_anchor ? i : 0];
+    a.table = pl->rx->d_table;
+    a.ctr = pl->d_ctr;
+
+    HIPCHK(hipSetDevice(pl->device));
+    if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
+    const bool chain = lines || want || greedy;
+    PostScratch &post = pl->post;
+    if (chain)
+    {
+        if (post_reserve(post, a.n_units, 0))
+            return 2;
+        a.unitinfo = post.d_unitinfo;
+        a.offsets = (const u64 *)post.d_offsets;
+    }
+    HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
+    HIPCHK(rx_run(a, lines, false, pl->num_cu, st));
+    if (chain && post_offsets_pass(post, a.n_units, lines, pl->d_ctr, st))
+        return 2;
+    uint64_t total = 0, nlines = 0;
+    unsigned long long summary = 0;
+    if (greedy)
+    {
+        // all occurrences into post.d_occ (sized once their number is known), then the greedy pass of kg_greedy.hip, consume = L
+        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t n_occ = pl->h_ctr->total;
+        HIPCHK(grow_scratch(post.occ_cap, n_occ, n_occ, {dev_buf(post.d_occ, n_occ * 2 * sizeof(uint64_t))}));
+        if (n_occ)
+        {
+            a.positions = (u64 *)post.d_occ;
+            a.pos_cap = n_occ;
+            HIPCHK(rx_run(a, false, true, pl->num_cu, st));
+            HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
+            WalkSpec ws{};
+            ws.mode = kWalkGreedy;
+            ws.m = L;
+            if (const int rc = post_walk(post, w.d_text, w.text_len, w.global_base, ws, n_occ, (uint64_t *)d_pos, want, pl->d_ctr, pl->h_ctr,
+                                         st, &total, &nlines, nullptr))
+                return rc;
+        }
+        summary = total ? (kLnHead | kLnTail) : 0;
+    }
+    else
+    {
+        if (want)
+        {
+            a.positions = (u64 *)d_pos;
+            a.pos_cap = want;
+            HIPCHK(rx_run(a, false, true, pl->num_cu, st));
+        }
+        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        total = pl->h_ctr->total;
+        nlines = pl->h_ctr->lines;
+        summary = lines ? pl->h_ctr->summary : (total ? (kLnHead | kLnTail) : 0);
+    }
+    if (time_it && stop_clock(pl, true, st, out))
+        return 2;
+    out->total_matches = total;
+    out->line_count = nlines;
+    out->has_newline = (summary & kLnNl) != 0;
+    out->head_line_hit = (summary & kLnHead) != 0;
+    out->tail_line_hit = (summary & kLnTail) != 0;
+    // regex_search's return value (krep.c:1395, :1533): max_count == 0 answers 0 with -c or positions, else 1 on the first occurrence
+    uint64_t store = 0;
+    if (maxc == 0)
+        out->count = (lines || pl->track) ? 0 : (total ? 1 : 0);
+    else if (lines)
+        out->count = std::min<uint64_t>(nlines, maxc);
+    else
+    {
+        out->count = std::min<uint64_t>(total, maxc);
+        store = (pl->track && d_pos) ? out->count : 0;
+    }
+    if (d_pos && cap && pl->track && !lines)
+    {
+        out->overflow = store > cap;
+        out->stored = std::min<uint64_t>(store, std::min<uint64_t>(total, want));
+    }
+    return 0;
+}
+} // namespace kg
+
+extern "C" int krep_gpu_regex_compile(const search_params_t *params, krep_gpu_regex_info_t *out)
+{
+    krep_gpu_clear_error();
+    if (const char *why = kg::regex_compile(params, out))
+        return kg::fail("%s", why);
+    return 0;
+}

@@ -1,0 +1,219 @@
+// kg_regex_compile.h — the pattern compiler of the -E path (krep_gpu_regex_compile, include/krep_gpu.h): a TOKENISER that cuts an
+// extended regular expression into a fixed number of one-byte atoms, and libc's own regcomp / regexec asked about every atom
+// and every byte.  Host code without any HIP in it, so that a stand-alone program can run it under the sanitizers
+// (tools/regex_compile_san.cpp).  It never sees a text: what it produces is a table, the search is the kernel's (kg_regex.hip).
+#pragma once
+#include <regex.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../include/krep_gpu.h"
+
+namespace kg {
+
+constexpr uint32_t kRegexMaxL = 16;
+
+// one atom of the pattern: bytes [at, at + len) of it, `rep` times in a row
+struct RegexAtom { size_t at, len; uint32_t rep; };
+
+inline bool regex_is_punct(uint8_t c) { return (c >= 0x21 && c <= 0x2f) || (c >= 0x3a && c <= 0x40) || (c >= 0x5b && c <= 0x60) || (c >= 0x7b && c <= 0x7e); }
+
+// the closing ']' of the bracket expression that opens at pat[i] (POSIX 9.3.5): an optional '^', a ']' directly behind that is
+// literal, [:name:] [.x.] [=x=] are stepped over.  Returns its index, or n when the expression is not closed.
+inline size_t regex_bracket_end(const uint8_t *pat, size_t n, size_t i)
+{
+    size_t k = i + 1;
+    if (k < n && pat[k] == '^')
+        ++k;
+    if (k < n && pat[k] == ']')
+        ++k;
+    while (k < n && pat[k] != ']')
+    {
+        if (pat[k] == '[' && k + 1 < n && (pat[k + 1] == ':' || pat[k + 1] == '.' || pat[k + 1] == '='))
+        {
+            const uint8_t close = pat[k + 1];
+            size_t e = k + 2;
+            while (e + 1 < n && !(pat[e] == close && pat[e + 1] == ']'))
+                ++e;
+            if (e + 1 >= n)
+                return n;
+            k = e + 2;
+        }
+        else
+            ++k;
+    }
+    return k;
+}
+
+// The class of one atom: the bytes b for which libc's regexec, with the atom compiled alone under the reference's flags
+// (krep.c:2148), matches the one-byte text b.  false: regcomp refused the atom.
+inline bool regex_probe_atom(const uint8_t *atom, size_t len, bool case_sensitive, uint8_t cls[32])
+{
+    char buf[1032];
+    if (len >= sizeof buf)
+        return false;
+    memcpy(buf, atom, len);
+    buf[len] = 0;
+    regex_t re;
+    if (regcomp(&re, buf, REG_EXTENDED | REG_NEWLINE | (case_sensitive ? 0 : REG_ICASE)) != 0)
+        return false;
+    memset(cls, 0, 32);
+    for (int b = 0; b < 256; ++b)
+    {
+        const char t[2] = {(char)b, 0};
+        regmatch_t m;
+        m.rm_so = 0;
+        m.rm_eo = 1;
+        if (regexec(&re, t, 1, &m, REG_STARTEND) == 0 && m.rm_so == 0 && m.rm_eo == 1)
+            cls[b >> 3] |= (uint8_t)(1u << (b & 7));
+    }
+    regfree(&re);
+    return true;
+}
+
+// NULL: `out` is filled.  Else why the pattern is not taken (a string literal).
+inline const char *regex_compile(const search_params_t *p, krep_gpu_regex_info_t *out)
+{
+    if (!p || !out)
+        return "NULL params";
+    memset(out, 0, sizeof *out);
+    if (!p->use_regex)
+        return "not a regex search (use_regex is not set)";
+    if (p->num_patterns > 1)
+        return "several regex patterns are an alternation (the CLI joins them with '|'): kept on krep's regex_search";
+    if (p->whole_word)
+        return "regex with -w: the CLI compiles \\bPATTERN\\b, a library caller PATTERN, and the operator sees neither compiled "
+               "expression: kept on krep's regex_search";
+    // In a multibyte locale libc's regexec matches CHARACTERS: '.', a negated or named class and, under REG_ICASE, even a letter
+    // take a whole multibyte sequence as one atom, so no pattern is a fixed number of BYTE classes there and one-byte probes cannot
+    // say what an atom matches.  The krep CLI never calls setlocale(): it runs in the C locale, where a character is a byte.
+    if (MB_CUR_MAX > 1)
+        return "regex in a multibyte locale (the process called setlocale): libc matches characters there, not bytes: kept on "
+               "krep's regex_search (krep itself runs in the C locale)";
+    const uint8_t *pat = (const uint8_t *)p->pattern;
+    size_t n = p->pattern_len;
+    if (p->num_patterns == 1 && p->patterns && p->pattern_lens && p->patterns[0])
+    {
+        pat = (const uint8_t *)p->patterns[0];
+        n = p->pattern_lens[0];
+    }
+    if (!pat)
+        return "no pattern";
+    if (n == 0)
+        return "an empty regex matches the empty string: kept on krep's regex_search";
+    if (n > 1024)
+        return "regex pattern longer than 1024 bytes";
+    for (size_t i = 0; i < n; ++i)
+        if (pat[i] < 0x01 || pat[i] > 0x7f)
+            return "regex pattern holds a byte outside 0x01-0x7F";
+    RegexAtom atoms[kRegexMaxL];
+    uint32_t n_atoms = 0, L = 0;
+    bool repeatable = false; // the token in front is an atom that has no repetition yet
+    for (size_t i = 0; i < n;)
+    {
+        const uint8_t c = pat[i];
+        if (c == '{')
+        {
+            if (!repeatable)
+                return "regex: '{' not behind an atom";
+            size_t k = i + 1;
+            uint32_t v = 0;
+            bool digits = false;
+            while (k < n && pat[k] >= '0' && pat[k] <= '9' && v <= 1000)
+            {
+                v = v * 10 + (uint32_t)(pat[k] - '0');
+                digits = true;
+                ++k;
+            }
+            if (!digits || k >= n)
+                return "regex: malformed repetition";
+            if (pat[k] == ',')
+                return "regex: {n,} and {n,m} repeat a varying number of times: kept on krep's regex_search";
+            if (pat[k] != '}')
+                return "regex: malformed repetition";
+            if (v < 1)
+                return "regex: {0} makes an atom optional: kept on krep's regex_search";
+            if (L - 1 + v > kRegexMaxL)
+                return "regex: more than 16 byte classes in a row";
+            L += v - 1;
+            atoms[n_atoms - 1].rep = v;
+            repeatable = false;
+            i = k + 1;
+            continue;
+        }
+        size_t len = 1;
+        if (c == '(' || c == ')' || c == '*' || c == '+' || c == '?' || c == '|' || c == '^' || c == '$')
+            return "regex: ( ) * + ? | ^ $ make a general automaton: kept on krep's regex_search";
+        if (c == '\\')
+        {
+            if (i + 1 >= n)
+                return "regex: trailing backslash";
+            const uint8_t e = pat[i + 1];
+            if ((e >= '0' && e <= '9') || ((e | 0x20) >= 'a' && (e | 0x20) <= 'z'))
+                return "regex: a backslash in front of a letter or digit (\\b, \\w, \\1, ...) is an operator: kept on krep's regex_search";
+            if (!regex_is_punct(e))
+                return "regex: a backslash in front of a byte that is not punctuation";
+            len = 2;
+        }
+        else if (c == '[')
+        {
+            const size_t e = regex_bracket_end(pat, n, i);
+            if (e >= n)
+                return "regex: bracket expression without its ']'";
+            len = e + 1 - i;
+        }
+        if (L + 1 > kRegexMaxL)
+            return "regex: more than 16 byte classes in a row";
+        atoms[n_atoms++] = RegexAtom{i, len, 1};
+        ++L;
+        repeatable = true;
+        i += len;
+    }
+    if (L < 1)
+        return "regex: no atom";
+    uint32_t j = 0;
+    for (uint32_t a = 0; a < n_atoms; ++a)
+    {
+        uint8_t cls[32];
+        if (!regex_probe_atom(pat + atoms[a].at, atoms[a].len, p->case_sensitive, cls))
+            return "regex: regcomp refuses an atom of the pattern";
+        for (uint32_t r = 0; r < atoms[a].rep; ++r)
+            memcpy(out->classes[j++], cls, 32);
+    }
+    out->L = L;
+    auto size_of = [&](uint32_t k) {
+        uint32_t s = 0;
+        for (int b = 0; b < 256; ++b)
+            s += (out->classes[k][b >> 3] >> (b & 7)) & 1u;
+        return s;
+    };
+    uint32_t best = 0, best_n = size_of(0);
+    for (uint32_t k = 1; k < L; ++k)
+        if (const uint32_t s = size_of(k); s < best_n)
+        {
+            best = k;
+            best_n = s;
+        }
+    out->anchor = best;
+    if (best_n >= 1 && best_n <= 4)
+        for (int b = 0; b < 256; ++b)
+            if ((out->classes[best][b >> 3] >> (b & 7)) & 1u)
+                out->anchor_bytes[out->n_anchor++] = (uint8_t)b;
+    // can the pattern overlap itself: a shift d at which every class meets the one d places on
+    for (uint32_t d = 1; d < L && !out->self_overlap; ++d)
+    {
+        bool all = true;
+        for (uint32_t k = 0; k + d < L && all; ++k)
+        {
+            bool meet = false;
+            for (int w = 0; w < 32 && !meet; ++w)
+                meet = (out->classes[k][w] & out->classes[k + d][w]) != 0;
+            all = meet;
+        }
+        out->self_overlap = all ? 1 : 0;
+    }
+    return nullptr;
+}
+
+} // namespace kg

@@ -631,11 +631,18 @@ namespace kg {
 // reference's scan stands; -c through simd_avx512_search / simd_avx2_search -w: the line-skip history the end-of-text replay
 // needs, for neon_search with its grid origin; multi-pattern -c with a '\n' inside a pattern: newlines so far and the line of
 // the last match — krep_gpu_seq_carry_t).  kSplitWhole: one window only — the newline-pattern -c walk of kg_greedy.hip (3),
-// neon_search's max_count == 0 corner.
+// neon_search's max_count == 0 corner, a regex that can overlap itself without -c.
 int split_mode(const search_params_t *p, const krep_gpu_config_t &c, size_t text_len)
 {
-    if (!p || p->use_regex || p->num_patterns == 0)
+    if (!p || (!p->use_regex && p->num_patterns == 0))
         return kSplitWhole;
+    if (p->use_regex)
+    { // a pattern that can overlap itself goes through the greedy pass over the whole occurrence list; -c never does (kg_regex.hip)
+        krep_gpu_regex_info_t info;
+        if (regex_compile_cached(p, &info))
+            return kSplitWhole;
+        return info.self_overlap && !p->count_lines_mode ? kSplitWhole : kSplitPieces;
+    }
     if (p->num_patterns > 1)
     {
         if (!p->count_lines_mode)
@@ -1345,6 +1352,8 @@ static int scan_device_impl(krep_gpu_plan_t *pl, const void *d_text, size_t text
     Window w{(const uint8_t *)d_text, text_len, own_lo, own_hi, global_base, global_len};
     if (pl->ref_algo == KREP_RA_AHO_CORASICK)
         return scan_ac(pl, w, d_positions, position_capacity, st, time_it, carry_in, carry_out, out);
+    if (pl->ref_algo == KREP_RA_REGEX)
+        return scan_regex(pl, w, d_positions, position_capacity, st, time_it, carry_in, carry_out, out);
     if (pl->sp.num_patterns != 1)
         return kg::fail("scan_device: no pattern");
     const int algo = mirror_effective(pl->ref_algo, &pl->sp, global_len);

@@ -35,7 +35,7 @@ class Engine:
                 pass
         L = self.lib = C.CDLL(path)
         sf = [C.POINTER(abi.SearchParams), C.c_void_p, C.c_size_t, C.POINTER(abi.MatchResult)]
-        for n in ("krep_gpu_literal_search", "krep_gpu_aho_corasick_search"):
+        for n in ("krep_gpu_literal_search", "krep_gpu_aho_corasick_search", "krep_gpu_regex_search"):
             getattr(L, n).restype = C.c_uint64
             getattr(L, n).argtypes = sf
         L.krep_gpu_select_search_algorithm.restype = C.c_void_p
@@ -46,6 +46,8 @@ class Engine:
         L.search_buffer_ex.restype = C.c_int
         L.search_buffer_ex.argtypes = [C.POINTER(abi.SearchParams), C.c_void_p, C.c_size_t, C.POINTER(abi.Config), C.c_int,
                                        C.POINTER(abi.MatchResult), C.POINTER(C.c_uint64)]
+        L.krep_gpu_regex_compile.restype = C.c_int
+        L.krep_gpu_regex_compile.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexInfo)]
         L.krep_gpu_can_accelerate.restype = C.c_int
         L.krep_gpu_can_accelerate.argtypes = [C.POINTER(abi.SearchParams)]
         L.krep_gpu_config_default.restype = None
@@ -274,6 +276,15 @@ class Engine:
     def set_stream_chunk(self, nbytes: int):
         self.lib.krep_gpu_set_stream_chunk(nbytes)
 
+    def regex_compile(self, params: abi.Params) -> "abi.RegexInfo":
+        """krep_gpu_regex_compile: the byte classes of an -E pattern (host only); KrepGpuError with the reason when it is refused.
+        Python puts the process into the environment's locale at start-up; in a multibyte one (UTF-8) libc matches characters, not
+        bytes, and every pattern is refused: locale.setlocale(locale.LC_CTYPE, "C") is the locale krep itself runs in."""
+        info = abi.RegexInfo()
+        if self.lib.krep_gpu_regex_compile(params.ref, C.byref(info)):
+            raise KrepGpuError(self.last_error())
+        return info
+
     def can_accelerate(self, params: abi.Params) -> bool:
         return bool(self.lib.krep_gpu_can_accelerate(params.ref))
 
@@ -467,9 +478,11 @@ class Engine:
         return C.cast(cp, C.c_void_p), len(raw), (raw, cp)
 
     def search(self, params: abi.Params, text, want_result=True):
-        """krep_gpu_select_search_algorithm(params)(params, text, len, result) -> (ret, positions)."""
+        """krep_gpu_select_search_algorithm(params)(params, text, len, result) -> (ret, positions).  A regex search (use_regex) is
+        taken in the C locale only: see regex_compile()."""
         ptr, n, keep = self._ptr(text)
-        fn = self.lib.krep_gpu_aho_corasick_search if params.s.num_patterns > 1 else self.lib.krep_gpu_literal_search
+        fn = (self.lib.krep_gpu_regex_search if params.s.use_regex else
+              self.lib.krep_gpu_aho_corasick_search if params.s.num_patterns > 1 else self.lib.krep_gpu_literal_search)
         res = self.lib.krep_gpu_match_result_init(16) if want_result else None
         dummy = C.c_int(0)
         if params.s.num_patterns > 1 and not params.s.ac_trie:

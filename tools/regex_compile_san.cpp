@@ -1,0 +1,91 @@
+// tools/regex_compile_san.cpp — the -E pattern compiler (krep_amd/csrc/kg_regex_compile.h: host code, no HIP) as a stand-alone
+// program for AddressSanitizer / UBSan:  python tools/sanitize.py regex   (or by hand:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer tools/regex_compile_san.cpp -o regex_compile_san).
+// It feeds the tokeniser accepted patterns, every refusal, and 200 000 pattern strings drawn from the bytes the grammar cares
+// about, each copied into a heap block of exactly its length so that a read past the pattern is a report.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../krep_amd/csrc/kg_regex_compile.h"
+
+static int compile(const std::string &pat, bool cs, bool ww, krep_gpu_regex_info_t *info, const char **why)
+{
+    char *heap = (char *)malloc(pat.size() ? pat.size() : 1); // exactly the pattern: no terminator to lean on
+    memcpy(heap, pat.data(), pat.size());
+    const char *one = heap;
+    size_t len = pat.size();
+    search_params_t p;
+    memset(&p, 0, sizeof p);
+    p.pattern = heap;
+    p.pattern_len = len;
+    p.patterns = &one;
+    p.pattern_lens = &len;
+    p.num_patterns = 1;
+    p.case_sensitive = cs;
+    p.use_regex = true;
+    p.whole_word = ww;
+    p.max_count = SIZE_MAX;
+    *why = kg::regex_compile(&p, info);
+    free(heap);
+    return *why ? 2 : 0;
+}
+
+int main()
+{
+    krep_gpu_regex_info_t info;
+    const char *why = nullptr;
+    int bad = 0;
+    const char *ok[] = {"Sherl[oO]ck", "[0-9]{3}-[0-9]{4}", "ERROR [0-9]{3}", "0x[0-9a-f]{8}", ".", "[^a]", "[]a]", "[^]a]", "[a-]",
+                        "[[:alpha:]]", "[[:space:]]", "[[:punct:]]", "\\.", "x{3}", "a{16}", "[[.-.]a]", "[[=a=]]b", "a\\{2\\}"};
+    for (const char *s : ok)
+        for (int cs = 0; cs < 2; ++cs)
+            if (compile(s, cs != 0, false, &info, &why) != 0 || info.L < 1 || info.L > 16)
+            {
+                printf("FAIL: %s refused: %s\n", s, why ? why : "?");
+                ++bad;
+            }
+    const char *no[] = {"a.*b", "(ab)", "a+", "a?", "a|b", "^a", "a$", "a{2,}", "a{2,3}", "{2}a", "a{2}{3}", "\\bword", "\\w", "\\1",
+                        "caf\xe9", "a{17}", "a{16}b", "", "[ab", "a{0}", "a\\", "a{", "a{2", "a{x}", "[[:alpha:", "[[.a", "[a[=", "a{99999999999}"};
+    for (const char *s : no)
+        if (compile(s, true, false, &info, &why) != 2 || !why || !*why)
+        {
+            printf("FAIL: %s accepted\n", s);
+            ++bad;
+        }
+    if (compile("ab", true, true, &info, &why) != 2)
+    {
+        printf("FAIL: -w accepted\n");
+        ++bad;
+    }
+    // pattern strings over the bytes the grammar looks at
+    const char alphabet[] = "ab[]^-:.={},\\0129(|*\n x";
+    unsigned long long s = 88172645463325252ull;
+    unsigned taken = 0, refused = 0;
+    for (int i = 0; i < 200000; ++i)
+    {
+        std::string pat;
+        s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+        const int len = (int)(s % 12);
+        for (int k = 0; k < len; ++k)
+        {
+            s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+            pat.push_back(alphabet[s % (sizeof alphabet - 1)]);
+        }
+        if (compile(pat, (s >> 40) & 1, false, &info, &why) == 0)
+        {
+            ++taken;
+            if (info.L < 1 || info.L > 16 || info.anchor >= info.L || info.n_anchor > 4)
+            {
+                printf("FAIL: inconsistent info for a random pattern\n");
+                ++bad;
+            }
+        }
+        else
+            ++refused;
+    }
+    printf("regex_compile_san: %u random patterns taken, %u refused, %d failures\n", taken, refused, bad);
+    return bad ? 1 : 0;
+}

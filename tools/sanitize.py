@@ -8,6 +8,7 @@ with the sanitizer named.
     python tools/sanitize.py tsan      # libkrep_gpu_tsan.so under the multi-shard failover tests (8 logical shards, injected failures)
     python tools/sanitize.py oracle    # oracle/krep_oracle.c under ASan + UBSan against the golden vectors and the compiled reference
     python tools/sanitize.py reference # the reference's own krep_test built with ASan + UBSan (findings there are the reference's)
+    python tools/sanitize.py regex     # the -E pattern compiler as a stand-alone program (tools/regex_compile_san.cpp) under ASan + UBSan
 
 Each mode prints the sanitizer reports it saw (none expected) and exits non-zero on one; profiles/r06_sanitizers.txt is its log."""
 import glob
@@ -84,6 +85,17 @@ def main():
                 cwd=SAN)
         out = r.stdout + r.stderr
         bad = [l for l in out.splitlines() if "ERROR: AddressSanitizer" in l or "runtime error:" in l]
+        print(out[-1500:])
+        rc = r.returncode
+    elif mode == "regex":
+        exe = os.path.join(SAN, "regex_compile_san")
+        r = run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-o", exe,
+                 os.path.join(ROOT, "tools", "regex_compile_san.cpp")])
+        if r.returncode:
+            return r.returncode
+        r = run([exe], env={"ASAN_OPTIONS": "detect_leaks=1:halt_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}, capture_output=True, text=True)
+        out = r.stdout + r.stderr
+        bad = [l for l in out.splitlines() if "ERROR: AddressSanitizer" in l or "ERROR: LeakSanitizer" in l or "runtime error:" in l]
         print(out[-1500:])
         rc = r.returncode
     else:
