@@ -61,6 +61,9 @@ int krep_gpu_debug_literal_dma_state(const krep_gpu_plan_t *plan, int *looked, i
 /* test hook: launches of the run-length kernel (kg_runs.hip: the greedy families on a pattern of one repeated byte, count-only);
  * $KREP_GPU_NO_RUNS=1 keeps such scans on the list road */
 uint64_t krep_gpu_debug_runs_launches(void);
+/* test hook of the regex scan (kg_regex.hip): at most `blocks` workgroups (0 = auto) — a starved grid, so that a wave takes a
+ * second and third 32-KiB unit on a text of a few hundred KiB (its own grid does that only beyond 5 units per compute unit) */
+void krep_gpu_debug_force_regex_grid(int blocks);
 /* a multi-pattern plan whose dictionary holds 1..3-byte patterns beside >= 8 longer ones: 0 not decided yet, 1 scanned as one dictionary, 2 split
  * (the long part anchored, the short part on its own, the record lists merged: kg_scan_ac.hip scan_ac_split); $KREP_GPU_AC_NO_SPLIT=1: never */
 int krep_gpu_debug_split_state(const krep_gpu_plan_t *plan);

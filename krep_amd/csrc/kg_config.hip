@@ -241,9 +241,11 @@ extern "C" const char *krep_gpu_unavailable_reason(void)
 namespace kg {
 std::atomic<int> g_force_rounds{0};    // test hook: 0 = auto, 1 / 4 = force the tile shape
 std::atomic<int> g_force_stage_cap{0}; // test hook: staging records per unit (0 = auto)
+std::atomic<int> g_rx_force_grid{0};   // test hook: workgroups of the regex scan (0 = auto)
 }
 extern "C" void krep_gpu_debug_force_stage_cap(int c) { g_force_stage_cap.store(c); }
 extern "C" void krep_gpu_debug_force_rounds(int r) { g_force_rounds.store(r); }
+extern "C" void krep_gpu_debug_force_regex_grid(int blocks) { g_rx_force_grid.store(blocks < 0 ? 0 : blocks); }
 namespace kg {
 extern int g_s1_force_grid;
 std::atomic<uint64_t> g_fused1_failovers{0}; // one-pass single-byte scans that handed over to the two-pass kernels

@@ -302,7 +302,9 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
 template <bool ANCH, bool LINES, bool EMIT> static hipError_t rx_launch(const RxArgs &a, int num_cu, hipStream_t st)
 {
     const u64 blocks = (a.n_units + kWavesPerBlk - 1) / kWavesPerBlk;
-    const u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 5)); // 32 KiB of LDS each: five workgroups fit a CU
+    u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 5)); // 32 KiB of LDS each: five workgroups fit a CU
+    if (const int force = g_rx_force_grid.load(); force > 0) // test hook: a starved grid (krep_gpu_debug_force_regex_grid)
+        grid = std::min<u32>(grid, (u32)force);
     hipLaunchKernelGGL((regex_scan<ANCH, LINES, EMIT>), dim3(grid), dim3(kBlock), 0, st, a);
     return hipGetLastError();
 }

@@ -159,6 +159,9 @@ class Engine:
             L.krep_gpu_debug_literal_dma_one_pass_failovers.restype = C.c_uint64
             L.krep_gpu_debug_force_literal_dma_grid.restype = None
             L.krep_gpu_debug_force_literal_dma_grid.argtypes = [C.c_int]
+        if hasattr(L, "krep_gpu_debug_force_regex_grid"):
+            L.krep_gpu_debug_force_regex_grid.restype = None
+            L.krep_gpu_debug_force_regex_grid.argtypes = [C.c_int]
         if hasattr(L, "krep_gpu_alloc_placed"):
             L.krep_gpu_alloc_placed.restype = C.c_int
             L.krep_gpu_alloc_placed.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -244,6 +247,10 @@ class Engine:
 
     def force_literal_dma_grid(self, blocks: int):
         self.lib.krep_gpu_debug_force_literal_dma_grid(blocks)
+
+    def force_regex_grid(self, blocks: int):
+        """at most `blocks` workgroups for the regex scan (0 = auto): every wave then takes several 32-KiB units"""
+        self.lib.krep_gpu_debug_force_regex_grid(blocks)
 
     def alloc_placed(self, text_bytes: int, record_bytes: int, tries: int = 3, device: int = 0):
         """krep_gpu_alloc_placed(): (d_text, d_records, abi.Placement) — one block, its placement drawn for; free_placed(d_text)"""

@@ -8,6 +8,7 @@ import pytest
 import line_model as lm
 import regex_model
 import regex_ref
+import regex_skip_model as sm
 from krep_amd import abi
 from krep_amd.engine import KrepGpuError
 
@@ -31,6 +32,7 @@ def gpu():
     yield e
     e.inject_failure(0)
     e.set_cpu_fallback(None)
+    e.force_regex_grid(0)
 
 
 def expected(pat, text, **kw):
@@ -297,3 +299,226 @@ def test_grep_lines_of_a_regex_plan(gpu):
         finally:
             plan.close()
     del hold
+
+
+# ------------------------------------------------------------------------------------ the entry state behind skipped cells
+@pytest.fixture(scope="module")
+def skip_texts():
+    """regex_skip_model.build_text for each of its patterns, built once (tests/test_regex_skip_model_cpu.py pins what they hold)"""
+    out = []
+    for pat, cs in sm.PATTERNS:
+        cl = regex_model.classes(pat, cs)
+        out.append((pat, dict() if cs else dict(case_sensitive=False), cl) + sm.build_text(cl))
+    return out
+
+
+@pytest.mark.parametrize("case", range(len(sm.PATTERNS)))
+def test_entry_state_behind_skipped_cells(gpu, skip_texts, case):
+    """the anchor sits behind the first class, the background holds no anchor byte: most cells are skipped, and a match that straddles
+    the boundary behind a skipped cell is found only through the entry state rebuilt from that cell's last 16 bytes; the decoys are
+    what a state of 0xFFFF or one left over from the last walked cell reports"""
+    pat, cs, cl, text, plants = skip_texts[case]
+    info = gpu.regex_compile(regex_ref.params(pat, **cs))
+    ai, ab = sm.anchor(cl)
+    assert (info.L, info.anchor, info.n_anchor, bytes(info.anchor_bytes[:info.n_anchor])) == (len(cl), ai, ab.size, ab.tobytes())
+    assert bool(info.self_overlap) == regex_model.self_overlap(cl)
+    g = sm.Geometry(cl, text)
+    assert sm.missing(cl, text) == [] and g.skipped.sum() >= 30 and len(g.dependent()) >= max(ai, 10)
+    for kw in (dict(), dict(track_positions=False), dict(max_count=3)):
+        want = expected(pat, text, **cs, **kw)
+        got = gpu.search(regex_ref.params(pat, **cs, **kw), text)
+        assert gpu.last_status() == abi.STATUS_OK
+        assert got[0] == want[0], (pat, kw, got[0], want[0])
+        assert np.array_equal(got[1], want[1]), (pat, kw, sorted(set(got[1][:, 0].tolist()) ^ set(want[1][:, 0].tolist()))[:8])
+    assert expected(pat, text, **cs)[0] == g.occ.size  # (the plants stand apart: every occurrence is a match)
+
+
+def skip_windows(g, plants, ai):
+    """three windows that start 5, 9 and 13 bytes into a skipped cell (the grid starts at that cell, so other cells start the units), the
+    last of them ending inside the text; then two that start one byte behind the start of a dependent straddler"""
+    n = g.text.size
+    skipped = [c for c in range(2, g.n_cells - 40) if g.skipped[c]]
+    windows = [(skipped[0] * sm.CELL + 5, n), (skipped[len(skipped) // 2] * sm.CELL + 9, n), (skipped[3] * sm.CELL + 13, 100 * sm.CELL + 7)]
+    dependents = [p for p in plants if p.kind == "straddler" and p.k <= ai]
+    cut = [p for p in dependents if p.k % 16 != 1][:2] or dependents[:1]  # (L = 2 has k = 1 only: that own_lo is a cell boundary)
+    return windows + [(p.start + 1, n) for p in cut]
+
+
+@pytest.mark.parametrize("case", [i for i, (pat, cs) in enumerate(sm.PATTERNS) if pat not in (b"[0-9]{3}-[0-9]{4}", b"[a-f]{8}Q[a-f]{7}")])
+def test_entry_state_in_windows_of_an_unaligned_text(gpu, skip_texts, case):
+    """the same texts 3 bytes into their allocation, own_lo no multiple of 16: inside a run of skipped cells (the grid starts at
+    own_lo & ~15, so the units start elsewhere and other cells are rebuilt), and one byte behind the start of a straddler, which is
+    then not owned while its anchor byte is"""
+    pat, cs, cl, text, plants = skip_texts[case]
+    assert not regex_model.self_overlap(cl)
+    n, L, (ai, _) = text.size, len(cl), sm.anchor(cl)
+    g = sm.Geometry(cl, text)
+    windows = skip_windows(g, plants, ai)
+    hold, d_text = to_device(text, 3)
+    plan = gpu.plan(regex_ref.params(pat, **cs))
+    try:
+        for i, (own_lo, own_hi) in enumerate(windows):
+            gw = sm.Geometry(cl, text, own_lo, own_hi)
+            mine = gw.occ
+            if i < 3:
+                assert own_lo % 16 and gw.origin % sm.CELL == 0 and g.skipped[own_lo // sm.CELL] and len(gw.dependent()) >= 3
+            else:
+                assert own_lo - 1 not in mine and own_lo - 1 in g.occ and ai >= 1  # (the straddler is not owned, its anchor byte is)
+            out, rec = scan_records(plan, d_text, n, own_lo, own_hi, global_base=1000, global_len=1000 + n)
+            assert out.count == mine.size and out.total_matches == mine.size, (pat, own_lo, own_hi, out.count, mine.size)
+            assert np.array_equal(rec[:, 0], mine.astype(np.uint64) + 1000) and np.array_equal(rec[:, 1], rec[:, 0] + L)
+            assert plan.scan(d_text, n, own_lo, own_hi).count == mine.size  # count only
+    finally:
+        plan.close()
+    del hold
+
+
+# ------------------------------------------------------------------------------------ -c with newlines inside long matches
+NL_PATTERNS = [b"[a-c\n]{16}", b"x[a-c\n]{14}y", b"[\n]a{8}"]
+
+
+def newline_sites(n):
+    """-> [(kind, B)]: every cell boundary of the text (kind unit / round / cell) and three lane boundaries between two of them"""
+    out = []
+    for B in range(256, n - 256, 256):
+        out.append(("unit" if B % sm.UNIT == 0 else "round" if B % sm.ROUND == 0 else "cell" if B % sm.CELL == 0 else "lane", B))
+    return out
+
+
+def newline_text(cl, n, turn, seed, breakers=True):
+    """A text over abc, x, y and newline in which every site holds one newline at B - 1 - j, j = 0 .. L - 2, that is in the last L - 1
+    bytes in front of a lane, cell, round or unit boundary B, so that its shifted coordinate n + L - 1 lies behind B, and a match that
+    starts in front of it (the newline inside the match where its classes allow that), on it or directly behind it; a second match
+    stands on the other line of the two the newline parts, and two more newlines close those lines.  The background has an x or y
+    in every 7 bytes: no match outside the sites.  `turn` moves every kind of site through the (j, place) pairs: the three unit
+    boundaries of a 100-KiB text see all of them in L - 1 turns.  breakers=False: abc only, and only the newlines are put (every
+    position of a text without x and y starts a match of a class sequence that holds all of a, b, c and newline).
+    -> (text, [(kind, B, j, place, newline)])"""
+    L = len(cl)
+    rng = np.random.RandomState(seed)
+    text = np.frombuffer(b"abc", dtype=np.uint8)[rng.randint(0, 3, size=n)].copy()
+    if breakers:
+        at = np.arange(3, n, 7)
+        text[at] = np.frombuffer(b"xy", dtype=np.uint8)[(at // 7) % 2]
+
+    def match():
+        m = np.zeros(L, dtype=np.uint8)
+        for i, t in enumerate(cl):
+            pick = [b for b in b"abcxy" if t[b]] or [10]
+            m[i] = pick[rng.randint(len(pick))]
+        return m
+
+    combos = [(j, place) for j in range(L - 1) for place in ("front", "on", "behind")]
+    sites = newline_sites(n)
+    per_kind = {k: sum(1 for kind, _ in sites if kind == k) for k in ("unit", "round", "cell", "lane")}
+    seen = dict.fromkeys(per_kind, 0)
+    out = []
+    for kind, B in sites:
+        j, place = combos[(seen[kind] + turn * per_kind[kind]) % len(combos)]
+        seen[kind] += 1
+        p = B - 1 - j
+        if breakers:
+            inside = [d for d in range(1, L) if cl[d][10]]
+            if place == "on" and not cl[0][10]:
+                place = "front"
+            s = p if place == "on" else p + 1 if place == "behind" else p - (inside[rng.randint(len(inside))] if inside else L)
+            other = p - 40 if place == "behind" else p + 24
+            for q in (other, s):
+                text[q - 1], text[q + L] = ord("x"), ord("y")
+                text[q:q + L] = match()
+            text[p - 56] = text[p + 72] = 10
+        text[p] = 10
+        out.append((kind, B, j, place, p))
+    return text, out
+
+
+def window_lines(cl, text, lo, hi):
+    """line_count, has_newline, head_line_hit, tail_line_hit of include/krep_gpu.h for the window [lo, hi): the starts and the newlines
+    the window owns; a start ON a newline belongs to the line that newline ends"""
+    occ = regex_model.occurrences(cl, text)
+    mine = occ[(occ >= lo) & (occ < hi)]
+    nl = np.flatnonzero(text[lo:hi] == 10) + lo
+    lines = np.unique(np.searchsorted(nl, mine, side="left")).size  # the line of a start: the owned newlines in front of it
+    head = bool(mine.size) and (nl.size == 0 or mine[0] <= nl[0])
+    tail = bool(mine.size) and (nl.size == 0 or mine[-1] > nl[-1])
+    return int(lines), bool(nl.size), bool(head), bool(tail)
+
+
+@pytest.mark.parametrize("case", range(len(NL_PATTERNS)))
+def test_count_lines_with_newlines_inside_long_matches(gpu, case):
+    """-c moves every newline to coordinate n + L - 1: one in the last L - 1 bytes of a lane crosses into the next lane, of a cell
+    into the next cell (through x63), of a unit into the next unit (through the guarded load in front of it)"""
+    pat = NL_PATTERNS[case]
+    cl = regex_model.classes(pat)
+    L, n = len(cl), 3 * sm.UNIT + 4321
+    assert gpu.regex_compile(regex_ref.params(pat)).L == L and L >= 9
+    plan = gpu.plan(regex_ref.params(pat, count_lines=True))
+    covered = set()
+    try:
+        turns = [(t, True) for t in range(L - 1)] + ([(0, False), (7, False)] if case == 0 else [])
+        for turn, breakers in turns:
+            text, sites = newline_text(cl, n, turn, 3000 + 100 * case + turn, breakers)
+            covered |= {(kind, j, place) for kind, _, j, place, _ in sites if breakers}
+            want = expected(pat, text, count_lines=True)
+            got = gpu.search(regex_ref.params(pat, count_lines=True), text)
+            assert gpu.last_status() == abi.STATUS_OK and got[0] == want[0] and got[1].size == 0, (pat, turn, breakers, got[0], want[0])
+            assert want[0] == window_lines(cl, text, 0, n)[0] and want[0] > len(sites) // 2
+            hold, d_text = to_device(text)
+            assert plan.scan(d_text, n).line_count == want[0]
+            # three windows: around a unit and a cell boundary, an odd offset, on a planted newline and on the byte behind it
+            first, third = sites[len(sites) // 5][4], sites[4 * len(sites) // 5][4]
+            lows = [sm.UNIT - 1, sm.UNIT, sm.UNIT + 1, 17 * sm.CELL - 1, 17 * sm.CELL + 1, 33333, first, first + 1]
+            highs = [2 * sm.UNIT + 1, 2 * sm.UNIT, 2 * sm.UNIT - 1, 70 * sm.CELL + 1, 70 * sm.CELL - 1, 65537, third + 1, third]
+            for pair in (turn % 8, (turn + 5) % 8):
+                cuts = [0, lows[pair], highs[pair], n]
+                outs = [plan.scan(d_text, n, lo, hi) for lo, hi in zip(cuts[:-1], cuts[1:])]
+                for (lo, hi), o in zip(zip(cuts[:-1], cuts[1:]), outs):
+                    have = (int(o.line_count), bool(o.has_newline), bool(o.head_line_hit), bool(o.tail_line_hit))
+                    assert have == window_lines(cl, text, lo, hi), (pat, turn, breakers, lo, hi)
+                assert gpu.lib.krep_gpu_combine_line_counts((abi.ScanOut * 3)(*outs), 3) == want[0], (pat, turn, cuts)
+            del hold
+    finally:
+        plan.close()
+    # every j at every kind of boundary, with every place the pattern allows
+    places = {"front", "behind"} | ({"on"} if cl[0][10] else set())
+    assert covered >= {(kind, j, place) for kind in ("lane", "cell", "round", "unit") for j in range(L - 1) for place in places}
+
+
+# ------------------------------------------------------------------------------------ a starved grid: several units per wave
+def sprinkled(rng, n, alphabet, plant, step):
+    t = planted(rng, n, alphabet, plant, len(plant))
+    p = np.frombuffer(plant, dtype=np.uint8)
+    for s in range(step, n - len(p), step):
+        t[s:s + len(p)] = p
+    return t
+
+
+def test_starved_grid_a_wave_takes_several_units(gpu):
+    """1 and 2 workgroups on 14 units (krep_gpu_debug_force_regex_grid): a wave resets its state for every unit it takes, reads that
+    unit's record offset, and adds up its counts: every instantiation of the kernel"""
+    n = 13 * sm.UNIT + 100
+    rng = np.random.RandomState(12)
+    words = sprinkled(rng, n, b"abcdefghijklmnopqrstuvwxyz \n", b"Sherlock", 7001)
+    skip_pat = b"[a-f]{7}S"
+    skip_cl = regex_model.classes(skip_pat)
+    skips, _ = sm.build_text(skip_cl, n=n, seed=3)
+    g = sm.Geometry(skip_cl, skips)
+    assert {c // sm.CELLS_PER_UNIT for _, c, _ in g.dependent()} == set(range(13)) and g.skipped.sum() > 13 * 8
+    nl_pat = NL_PATTERNS[1]
+    newlines, _ = newline_text(regex_model.classes(nl_pat), n, 4, 77)
+    ab = background(rng, n, b"ab")
+    jobs = [(b"[A-Z][a-z]{7}", words, dict(track_positions=False)), (b"[A-Z][a-z]{7}", words, dict()),        # the table path
+            (skip_pat, skips, dict(track_positions=False)), (skip_pat, skips, dict()),                          # the anchor path
+            (b"[a-z]{4}", words, dict(count_lines=True)), (nl_pat, newlines, dict(count_lines=True)),           # -c
+            (b"[ab]{3}", ab, dict()), (b"[ab]{3}", ab, dict(track_positions=False))]                            # the greedy road
+    wants = [expected(pat, text, **kw) for pat, text, kw in jobs]
+    assert all(w[0] > 13 for w in wants)
+    try:
+        for blocks in (1, 2):
+            gpu.force_regex_grid(blocks)
+            for (pat, text, kw), want in zip(jobs, wants):
+                got = gpu.search(regex_ref.params(pat, **kw), text)
+                assert gpu.last_status() == abi.STATUS_OK
+                assert got[0] == want[0] and np.array_equal(got[1], want[1]), (blocks, pat, kw, got[0], want[0])
+    finally:
+        gpu.force_regex_grid(0)
