@@ -223,12 +223,12 @@ uint64_t krep_gpu_literal_search(const search_params_t *params, const char *text
                                  size_t text_len, match_result_t *result);
 uint64_t krep_gpu_aho_corasick_search(const search_params_t *params, const char *text_start,
                                       size_t text_len, match_result_t *result);
-/* regex_search (krep.c:1389-1579) for the patterns krep_gpu_regex_compile() accepts; params->compiled_regex is never read here
+/* regex_search (krep.c:1389-1579) for the patterns krep_gpu_regex_compile_anchored() accepts; params->compiled_regex is never read here
  * and goes to the registered CPU function untouched when the attempt fails. */
 uint64_t krep_gpu_regex_search(const search_params_t *params, const char *text_start,
                                size_t text_len, match_result_t *result);
 /* Drop-in for select_search_algorithm(): returns one of the three functions above, or NULL when the backend does not
- * take the search — no usable device (krep_gpu_available() == 0), a regex krep_gpu_regex_compile() refuses, and the input classes
+ * take the search — no usable device (krep_gpu_available() == 0), a regex krep_gpu_regex_compile_anchored() refuses, and the input classes
  * krep_gpu_can_accelerate() names — so that the caller keeps the CPU function pointer the reference's own
  * select_search_algorithm() gives it.  (-c through simd_sse42_search / kmp_search with a newline inside the pattern, refused
  * until round 3, is reproduced: one device thread walks the ordered occurrence list the way the reference's loop moves.) */
@@ -236,8 +236,8 @@ search_func_t krep_gpu_select_search_algorithm(const search_params_t *params);
 /* 1 when the backend takes the search for `params` under the current configuration, 0 when not:
  *   - no usable gfx950 device (krep_gpu_available() == 0);
  *   - no pattern at all (num_patterns == 0 and pattern == NULL);
- *   - use_regex with a pattern krep_gpu_regex_compile() refuses (anything that is not a fixed number of byte classes in a
- *     row, several patterns, -w).
+ *   - use_regex with a pattern krep_gpu_regex_compile_anchored() refuses (anything that is not a fixed number of byte classes
+ *     in a row with an optional ^ in front and $ behind, several patterns, -w).
  * (count_lines_mode together with only_matching through memchr_short_search — a combination krep's main() never produces,
  * krep.c:3811-3814 — was refused until round 5 and is reproduced now: one window, krep_gpu_split_mode() = WHOLE.)
  * An operator called with such params anyway treats it like a run-time failure (see the top of this header): the
@@ -251,7 +251,8 @@ int krep_gpu_can_accelerate(const search_params_t *params);
  * Accepted atoms: an ordinary byte; '\' followed by a punctuation byte; '.'; a bracket expression, whose closing ']' is found
  *   by POSIX's rules (an optional '^', a ']' directly behind '[' or '[^' is literal, [:name:] [.x.] [=x=] are stepped over).
  *   Each atom may be followed by {n}, n >= 1, which repeats it.  The atoms in a row are the L byte classes C0..C(L-1), 1 <= L <= 16.
- * Refused (2, the reason in krep_gpu_last_error()): ( ) * + ? | ^ $ outside brackets; {n,} and {n,m}; '{' not behind an atom;
+ * Refused (2, the reason in krep_gpu_last_error()): ( ) * + ? | outside brackets; ^ and $ outside brackets (as the first / last
+ *   pattern byte they are line anchors: krep_gpu_regex_compile_anchored() below takes those); {n,} and {n,m}; '{' not behind an atom;
  *   '\' followed by a letter or digit (\b, \w, \1, ...); a pattern byte outside 0x01-0x7F; L outside 1..16; num_patterns > 1
  *   (the CLI turns several -e into an alternation); whole_word — the CLI compiles \bPATTERN\b (krep.c:2122-2135) and still calls
  *   is_whole_word_match(), a library caller compiles PATTERN alone, the operator sees only params->pattern and never the compiled
@@ -285,6 +286,38 @@ typedef struct krep_gpu_regex_info
 } krep_gpu_regex_info_t;
 /* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
 int krep_gpu_regex_compile(const search_params_t *params, krep_gpu_regex_info_t *out);
+
+/* ---- line anchors around a class sequence: ^ERROR, ;$, ^#include$, [0-9]{3}$ ----
+ * Grammar: an optional '^' as the first pattern byte, an optional '$' as the last one (when it is not the second byte of a \$
+ *   escape), and between them exactly the grammar above.  \^, \$, [$^] and [^a] stay ordinary atoms.  krep_gpu_regex_compile()
+ *   keeps refusing both anchors (its struct cannot say them); everything that takes a search — krep_gpu_can_accelerate(),
+ *   krep_gpu_select_search_algorithm(), krep_gpu_split_mode(), the plans and the operators — goes through this call.
+ * Refused (2, each with its own reason): '^' or '$' anywhere else outside a bracket (a^b, a$b, ^^a, a$$); {n} directly behind
+ *   '^'; ^$, ^ and $ on their own (L = 0: an empty match); L + bol + eol > 16; and everything krep_gpu_regex_compile() refuses.
+ * What a scan reproduces (regex_search under REG_EXTENDED | REG_NEWLINE, REG_NOTBOL unless the search resumes at the text start
+ *   or behind a '\n', REG_STARTEND with rm_eo = the end of the text): an occurrence is a position p with
+ *     text[p + j] in Cj for all j < L, and p + L <= text_len;
+ *     when bol: p == 0 or text[p - 1] == '\n';
+ *     when eol: text[p + L] == '\n', or p + L == text_len in a case-sensitive search.  (regex_search ORs REG_ICASE into regexec's
+ *       eflags, krep.c:1420, where that bit is REG_NOTEOL: with case_sensitive == false the end of the text ends no line, and
+ *       a$ does not match the text "a".  The scan reproduces that.)
+ *   The anchors consume nothing: the records are (p, p + L), the matches the greedy leftmost non-overlapping occurrences with
+ *   consume = L.  -c counts the distinct lines that hold p; a p ON a '\n' belongs to the line that newline ends.  max_count, its
+ *   0 quirk, only_matching and the empty text are as above.
+ * seq.self_overlap: a shift d in 1..L-1 counts only when Cj and C(j+d) meet for every j AND, with bol, C(d-1) holds '\n' (the byte
+ *   in front of the second occurrence lies inside the first) AND, with eol, C(L-d) holds '\n'.  So ^ab, ab$ and ^[ab]{2} are
+ *   KREP_GPU_SPLIT_PIECES, ^[a\n]{2} is KREP_GPU_SPLIT_WHOLE (without -c).
+ * Windows: a scan needs text[p - 1] and text[p + L] of every start it owns.  Refused (2): bol with own_lo == 0 in a buffer that
+ *   does not begin the text (global_base > 0); eol with an owned start at p + L == text_len in a buffer that does not end the text
+ *   (global_base + text_len < global_len).  The pieces the library cuts itself carry 17 bytes on both sides and never ask that. */
+typedef struct krep_gpu_regex_anchored
+{
+    krep_gpu_regex_info_t seq; /* the L real classes; anchor / anchor_bytes / n_anchor as above, over the real classes */
+    int bol;                   /* the pattern starts with an unescaped ^ */
+    int eol;                   /* the pattern ends with an unescaped $   */
+} krep_gpu_regex_anchored_t;
+/* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
+int krep_gpu_regex_compile_anchored(const search_params_t *params, krep_gpu_regex_anchored_t *out);
 
 /* The in-memory twin of search_file()/search_string() that BASELINE.json calls search_buffer():
  * validation as krep.c:2013-2049 (no patterns -> 2; empty pattern among several -> 2; pattern

@@ -140,6 +140,11 @@ class RegexInfo(C.Structure):
         return bytes(b for b in range(256) if (self.classes[j][b >> 3] >> (b & 7)) & 1)
 
 
+class RegexAnchored(C.Structure):
+    """krep_gpu_regex_anchored_t: what krep_gpu_regex_compile_anchored() makes of an -E pattern with an optional ^ in front and $ behind"""
+    _fields_ = [("seq", RegexInfo), ("bol", C.c_int), ("eol", C.c_int)]
+
+
 class ShardInfo(C.Structure):
     """krep_gpu_shard_info_t: where the calling thread's last sharded host search ran."""
     _fields_ = [("shards", C.c_int), ("devices_used", C.c_int), ("device_ids", C.c_int * 16), ("comm_ranks", C.c_int),

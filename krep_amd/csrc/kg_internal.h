@@ -224,7 +224,7 @@ const char *unsupported_reason(const search_params_t *p, const krep_gpu_config_t
 // kg_regex_compile.h behind a one-entry cache per thread: an operator call asks the selector, the executor, the split rule and (on a
 // cache miss) the plan about the same pattern, and one compile is up to 16 regcomp calls and 4096 regexec probes.  The key is
 // everything the compiler reads (pattern bytes, case, -w, the number of patterns, whether the locale is multibyte).
-const char *regex_compile_cached(const search_params_t *p, krep_gpu_regex_info_t *out); // NULL: taken; else the refusal
+const char *regex_compile_cached(const search_params_t *p, krep_gpu_regex_anchored_t *out); // NULL: taken; else the refusal
 constexpr int kSplitWhole = 0, kSplitPieces = 1, kSplitChain = 2; // enum krep_gpu_split (include/krep_gpu.h)
 int split_mode(const search_params_t *p, const krep_gpu_config_t &c, size_t text_len);
 bool shardable(const search_params_t *p, const krep_gpu_config_t &c, size_t text_len); // split_mode != whole

@@ -151,7 +151,8 @@ extern "C" const char *krep_gpu_algorithm_name(int a)
 }
 
 // ------------------------------------------------------------------------------------ what is accelerated
-// A regular expression (-E) is taken when krep_gpu_regex_compile() accepts it: a fixed number of byte classes in a row, one pattern,
+// A regular expression (-E) is taken when krep_gpu_regex_compile_anchored() accepts it: a fixed number of byte classes in a row
+// (an optional ^ in front, an optional $ behind), one pattern,
 // no -w; every other expression stays with krep's regex_search.  Beyond that ONE input class is not taken; for it krep_gpu_can_accelerate() says 0, krep_gpu_select_search_algorithm() returns NULL (the
 // caller keeps its CPU function pointer, exactly like the regex case) and an operator called with it anyway takes the failure road:
 //  * memchr_short_search in -c mode while the file-static only_matching is set: main() never produces that
@@ -159,19 +160,19 @@ extern "C" const char *krep_gpu_algorithm_name(int a)
 // (Round 3: -c through simd_sse42_search / kmp_search with a '\n' inside the pattern — refused until then — is reproduced by a
 //  walk over the ordered occurrence list, kg_greedy.hip (3).)
 namespace kg {
-const char *regex_compile_cached(const search_params_t *p, krep_gpu_regex_info_t *out)
+const char *regex_compile_cached(const search_params_t *p, krep_gpu_regex_anchored_t *out)
 {
     struct Entry
     {
         bool valid = false, cs = false, ww = false, mb = false;
         size_t np = 0;
         std::string pat;
-        krep_gpu_regex_info_t info{};
+        krep_gpu_regex_anchored_t info{};
         const char *why = nullptr;
     };
     static thread_local Entry e;
     if (!p || !out || !p->use_regex)
-        return regex_compile(p, out);
+        return regex_compile_anchored(p, out);
     const char *pat = p->pattern;
     size_t n = p->pattern_len;
     if (p->num_patterns == 1 && p->patterns && p->pattern_lens && p->patterns[0])
@@ -180,13 +181,13 @@ const char *regex_compile_cached(const search_params_t *p, krep_gpu_regex_info_t
         n = p->pattern_lens[0];
     }
     if (!pat || n > 1024)
-        return regex_compile(p, out);
+        return regex_compile_anchored(p, out);
     const bool mb = MB_CUR_MAX > 1;
     if (!(e.valid && e.cs == p->case_sensitive && e.ww == p->whole_word && e.mb == mb && e.np == p->num_patterns && e.pat.size() == n &&
           memcmp(e.pat.data(), pat, n) == 0))
     {
         e.valid = false;
-        e.why = regex_compile(p, &e.info);
+        e.why = regex_compile_anchored(p, &e.info);
         e.cs = p->case_sensitive; e.ww = p->whole_word; e.mb = mb; e.np = p->num_patterns;
         e.pat.assign(pat, n);
         e.valid = true;
@@ -199,8 +200,9 @@ const char *unsupported_reason(const search_params_t *p, const krep_gpu_config_t
     if (!p)
         return "NULL params";
     if (p->use_regex)
-    { // -E: taken exactly when the pattern is a fixed number of byte classes in a row (kg_regex_compile.h names the refusals)
-        krep_gpu_regex_info_t info;
+    { // -E: taken exactly when the pattern is a fixed number of byte classes in a row, ^ in front and $ behind allowed
+      // (kg_regex_compile.h names the refusals)
+        krep_gpu_regex_anchored_t info;
         return regex_compile_cached(p, &info);
     }
     if (p->num_patterns > 1)

@@ -16,6 +16,16 @@
 // Anchor fast path (patterns whose smallest class holds 1..4 bytes, no -c): a cell is walked only when it or the cell in front of
 // it holds an anchor byte (a match that ends in the cell has its anchor byte in one of the two); after skipped cells the entry
 // state of lane 0 is rebuilt from the 16 bytes in front of the cell (kept in scalars), once.
+// Line anchors (krep_gpu_regex_compile_anchored).  ^ and $ are one more place each in the sequence, the class { '\n' }: the walk runs
+// over the EXTENDED sequence [\n] C0..C(L-1) [\n] of Lx = L + bol + eol <= 16 places, so the 16-bit state, the exact exit state and the
+// entry-state mask hold with Lx in place of L.  Two shifts follow from it: a hit is seen at the extended end, text byte
+// p + L - 1 + eol, so a START p is at coordinate p + sh with sh = L - 1 + eol (not Lx - 1: the ^ place lies in front of p), and that
+// is the shift of the -c newline mask, of the ownership range and of the records.  Two newlines exist in no buffer: the one in front
+// of byte 0 of the text (global_base == 0) is the entry state 1 of unit 0 instead of 0, the one behind the last byte is OR-ed into
+// the lane of a guarded round that holds offset text_len when the buffer ends the text and the search is case-sensitive (so with
+// $ the coordinates reach text_len itself: one more cell, round or unit when text_len is a multiple of one).  Neither is a
+// newline of -c.  The anchor bytes come from the real classes, and the cell behind one that holds them is always walked: the
+// cell that holds nothing but the newline behind the text is reached that way.
 // Reads: no byte outside [0, text_len) — whole 8-KiB rounds inside the text are vector loads, everything else is guarded per byte.
 #include <hip/hip_runtime.h>
 
@@ -35,8 +45,8 @@ namespace kg {
 
 struct RegexProg
 {
-    krep_gpu_regex_info_t info{};
-    u32 *d_table = nullptr; // T[256]
+    krep_gpu_regex_anchored_t info{};
+    u32 *d_table = nullptr; // T[256] over the extended sequence: bit 0 is ^'s newline when bol, bit bol + j class j, bit bol + L $'s newline
 };
 
 constexpr u32 kRxUnitBytes = kRoundsBig * kSegBytes; // 32 KiB of coordinates per wave unit
@@ -51,7 +61,13 @@ struct RxArgs
     u64 cov_hi;          // coordinates >= cov_hi hold nothing
     u64 n_units;
     u64 global_base;
-    u32 L;
+    // One word for the geometry (the kernels run at the limit of their scalar registers: every further uniform value is spilled):
+    //   bits 0-7   L: the real classes, a record is (p, p + L)
+    //   bits 8-15  Lx: places of the walk, L + bol + eol
+    //   bits 16-23 sh: start p is at coordinate p + sh, L - 1 + eol
+    //   bit 24     entry state of the unit at coordinate 0: 1 when ^ and the buffer begins the text, else 0
+    //   bit 25     a guarded round holds '\n' at offset text_len: $ in the buffer that ends the text (not under -i)
+    u32 geom;
     u32 n_anchor;
     u32 ab[4];           // the anchor bytes, each in every byte lane
     const u32 *table;
@@ -117,8 +133,9 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
     __syncthreads();
     const u32 lane = lane_id(), wave = threadIdx.x >> 6;
     const u32 *T = s_T + (lane & 31u);
-    const u32 Lm1 = a.L - 1u;
-    const u64 c_lo = a.own_lo + Lm1, c_hi = a.hi_match + Lm1; // the coordinates of the owned starts
+    const u32 Lm1 = ((a.geom >> 8) & 0xffu) - 1u, sh = (a.geom >> 16) & 0xffu;
+
+    const u64 c_lo = a.own_lo + sh, c_hi = a.hi_match + sh; // the coordinates of the owned starts
     const u64 n_waves = (u64)gridDim.x * kWavesPerBlk;
     u64 acc_total = 0;
 
@@ -126,10 +143,10 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
     {
         const u64 ubase = a.anchor + unit * kRxUnitBytes;
         // the 16 bytes in front of the unit give lane 0 its entry state (and, for -c, the newlines that shift into the unit)
-        u32 x63 = 0; // exit state | raw newline mask << 16 of the 16 bytes in front of the next cell (uniform)
+        u32 x63 = (a.geom >> 24) & 1u; // exit state | raw newline mask << 16 of the 16 bytes in front of the next cell (uniform)
         if (ubase != 0)
         {
-            const uint4 p = rx_load_guarded(a.text, a.text_len, ubase - 16);
+            const uint4 p = rx_load_guarded(a.text, a.text_len, ubase - 16); // (ubase <= text_len: the newline behind the text is not among them)
             u32 X;
             (void)rx_walk(T, p, Lm1, X);
             x63 = X;
@@ -184,6 +201,22 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
                     const u64 cb = seg + (u64)j * kCellBytes;
                     d[j] = cb < a.cov_hi ? rx_load_guarded(a.text, a.text_len, cb + (u64)lane * 16u) : make_uint4(0u, 0u, 0u, 0u);
                 }
+                if ((a.geom >> 25) & 1u)
+                { // $: the newline behind the last byte of the text, put into the one lane whose 16 bytes hold offset text_len
+#pragma unroll
+                    for (int j = 0; j < kCells; ++j)
+                    {
+                        const u64 rel = a.text_len - (seg + (u64)j * kCellBytes + (u64)lane * 16u);
+                        if (rel < 16u)
+                        {
+                            const u32 nl = 0x0au << (8u * ((u32)rel & 3u)), w = (u32)rel >> 2;
+                            d[j].x |= w == 0u ? nl : 0u;
+                            d[j].y |= w == 1u ? nl : 0u;
+                            d[j].z |= w == 2u ? nl : 0u;
+                            d[j].w |= w == 3u ? nl : 0u;
+                        }
+                    }
+                }
             }
 #pragma unroll
             for (int j = 0; j < kCells; ++j)
@@ -235,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
                 l_hits += (u32)__popc(H);
                 if (LINES)
                 {
-                    const u32 N = (((mine >> 16) << Lm1) | ((prev >> 16) >> (16u - Lm1))) & 0xffffu, Hs = H | N;
+                    const u32 N = (((mine >> 16) << sh) | ((prev >> 16) >> (16u - sh))) & 0xffffu, Hs = H | N;
                     l_cnt += (u32)__popc(H & ~(Hs - ((N << 1) & 0xffffu)));
                     // head: the lowest flag is a match (one ON a newline belongs to the line it ends); tail: a match behind the last newline
                     line_cell(__ballot(N != 0u), __ballot(H != 0u), __ballot((H & (Hs ^ (Hs - 1u))) != 0u),
@@ -261,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
                             H &= H - 1u;
                             if (idx < a.pos_cap)
                             {
-                                const u64 s0 = q + k - Lm1 + a.global_base, e0 = s0 + a.L;
+                                const u64 s0 = q + k - sh + a.global_base, e0 = s0 + (a.geom & 0xffu);
                                 *reinterpret_cast<uint4 *>(a.positions + 2 * idx) = make_uint4((u32)s0, (u32)(s0 >> 32), (u32)e0, (u32)(e0 >> 32));
                             }
                             ++idx;
@@ -327,14 +360,17 @@ RegexProg *regex_prog_create(const search_params_t &sp)
         delete rx;
         return nullptr;
     }
+    const krep_gpu_regex_info_t &seq = rx->info.seq;
+    const u32 bol = rx->info.bol ? 1u : 0u, eol = rx->info.eol ? 1u : 0u;
     u32 table[256];
     for (int b = 0; b < 256; ++b)
     {
         u32 m = 0;
-        for (u32 j = 0; j < rx->info.L; ++j)
-            m |= ((rx->info.classes[j][b >> 3] >> (b & 7)) & 1u) << j;
+        for (u32 j = 0; j < seq.L; ++j)
+            m |= ((seq.classes[j][b >> 3] >> (b & 7)) & 1u) << (bol + j);
         table[b] = m;
     }
+    table['\n'] |= bol | (eol << (bol + seq.L));
     if (hipMalloc(&rx->d_table, sizeof table) != hipSuccess ||
         hipMemcpy(rx->d_table, table, sizeof table, hipMemcpyHostToDevice) != hipSuccess)
     {
@@ -361,8 +397,8 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
         *carry_out = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
     if (!pl->rx)
         return fail("scan_device: the regex plan holds no program");
-    const krep_gpu_regex_info_t &info = pl->rx->info;
-    const u32 L = info.L;
+    const krep_gpu_regex_info_t &info = pl->rx->info.seq;
+    const u32 L = info.L, bol = pl->rx->info.bol ? 1u : 0u, eol = pl->rx->info.eol ? 1u : 0u;
     if (w.global_len < L || w.text_len < L || w.own_lo >= w.own_hi)
         return 0; // (text_len == 0 included: L >= 1 matches no empty string)
     const size_t own_hi = std::min(w.own_hi, w.text_len);
@@ -374,6 +410,14 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
                     "text in one window (krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
     if (own_hi <= w.own_lo || (!lines && hi_match <= w.own_lo))
         return 0;
+    // an anchor needs the byte in front of, or behind, every occurrence the window owns
+    const bool ends_text = w.global_base + w.text_len == w.global_len;
+    if (bol && w.own_lo == 0 && w.global_base > 0)
+        return fail("regex with ^: the window owns buffer byte 0, which is not the start of the text (global_base > 0), and the byte in "
+                    "front of it decides a match there: start the buffer at least one byte in front of own_lo");
+    if (eol && !ends_text && w.own_lo + L <= w.text_len && own_hi + L > w.text_len)
+        return fail("regex with $: the window owns a start whose occurrence ends on the last byte of a buffer that does not end the "
+                    "text, and the byte behind it decides the match: end own_hi at least L bytes in front of the buffer's end");
     const size_t maxc = pl->max_count;
     const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(maxc, cap) : 0;
 
@@ -382,10 +426,13 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
     a.anchor = w.own_lo & ~(u64)15;
     a.own_lo = w.own_lo; a.hi_match = std::max<u64>(hi_match, w.own_lo);
     a.nl_hi = own_hi;
-    a.cov_hi = (lines ? (u64)own_hi : a.hi_match) + (L - 1);
+    const u32 sh = L - 1 + eol;
+    a.cov_hi = (lines ? (u64)own_hi : a.hi_match) + sh; // (with $ in the buffer that ends the text this reaches text_len + 1)
     a.n_units = (a.cov_hi - a.anchor + kRxUnitBytes - 1) / kRxUnitBytes;
     a.global_base = w.global_base;
-    a.L = L;
+    // (regex_search ORs REG_ICASE into regexec's eflags, where that bit is REG_NOTEOL: under -i the end of the text ends no line)
+    const u32 entry0 = bol && w.global_base == 0 ? 1u : 0u, vnl = eol && ends_text && pl->sp.case_sensitive ? 1u : 0u;
+    a.geom = L | ((L + bol + eol) << 8) | (sh << 16) | (entry0 << 24) | (vnl << 25);
     a.n_anchor = lines ? 0 : info.n_anchor;
     for (u32 i = 0; i < 4; ++i)
         a.ab[i] = 0x01010101u * info.anchor_bytes[i < info.n_anchor ? i : 0];
@@ -476,6 +523,13 @@ extern "C" int krep_gpu_regex_compile(const search_params_t *params, krep_gpu_re
 {
     krep_gpu_clear_error();
     if (const char *why = kg::regex_compile(params, out))
+        return kg::fail("%s", why);
+    return 0;
+}
+extern "C" int krep_gpu_regex_compile_anchored(const search_params_t *params, krep_gpu_regex_anchored_t *out)
+{
+    krep_gpu_clear_error();
+    if (const char *why = kg::regex_compile_anchored(params, out))
         return kg::fail("%s", why);
     return 0;
 }

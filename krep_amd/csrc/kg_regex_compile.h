@@ -72,12 +72,13 @@ inline bool regex_probe_atom(const uint8_t *atom, size_t len, bool case_sensitiv
     return true;
 }
 
-// NULL: `out` is filled.  Else why the pattern is not taken (a string literal).
-inline const char *regex_compile(const search_params_t *p, krep_gpu_regex_info_t *out)
+// Both entry points.  anchors: a '^' as the first and a '$' as the last pattern byte are line anchors (krep_gpu_regex_compile_anchored);
+// without it they are refused like everywhere else in the pattern (krep_gpu_regex_compile, whose struct cannot say them).
+// NULL: `out`, *bol and *eol are filled.  Else why the pattern is not taken (a string literal).
+inline const char *regex_compile_seq(const search_params_t *p, bool anchors, krep_gpu_regex_info_t *out, int *bol_out, int *eol_out)
 {
-    if (!p || !out)
-        return "NULL params";
     memset(out, 0, sizeof *out);
+    *bol_out = *eol_out = 0;
     if (!p->use_regex)
         return "not a regex search (use_regex is not set)";
     if (p->num_patterns > 1)
@@ -110,11 +111,28 @@ inline const char *regex_compile(const search_params_t *p, krep_gpu_regex_info_t
     RegexAtom atoms[kRegexMaxL];
     uint32_t n_atoms = 0, L = 0;
     bool repeatable = false; // the token in front is an atom that has no repetition yet
+    bool bol = false, eol = false;
     for (size_t i = 0; i < n;)
     {
         const uint8_t c = pat[i];
+        // (the loop steps over escapes and bracket expressions whole: a '^' or '$' it stands on is an unescaped one outside brackets)
+        if ((c == '^' && i == 0) || (c == '$' && i + 1 == n))
+        {
+            if (!anchors)
+                return "regex: a line anchor (^ in front, $ at the end) is not a byte class and krep_gpu_regex_info_t cannot say it: "
+                       "krep_gpu_regex_compile_anchored() takes it";
+            (c == '^' ? bol : eol) = true;
+            repeatable = false;
+            ++i;
+            continue;
+        }
+        if (c == '^' || c == '$')
+            return "regex: ^ that is not the first or $ that is not the last byte of the pattern (a^b, a$b, ^^a, a$$) anchors inside "
+                   "the sequence: kept on krep's regex_search";
         if (c == '{')
         {
+            if (bol && i == 1)
+                return "regex: a repetition directly behind ^ repeats the anchor: kept on krep's regex_search";
             if (!repeatable)
                 return "regex: '{' not behind an atom";
             size_t k = i + 1;
@@ -143,8 +161,8 @@ inline const char *regex_compile(const search_params_t *p, krep_gpu_regex_info_t
             continue;
         }
         size_t len = 1;
-        if (c == '(' || c == ')' || c == '*' || c == '+' || c == '?' || c == '|' || c == '^' || c == '$')
-            return "regex: ( ) * + ? | ^ $ make a general automaton: kept on krep's regex_search";
+        if (c == '(' || c == ')' || c == '*' || c == '+' || c == '?' || c == '|')
+            return "regex: ( ) * + ? | make a general automaton: kept on krep's regex_search";
         if (c == '\\')
         {
             if (i + 1 >= n)
@@ -171,7 +189,9 @@ inline const char *regex_compile(const search_params_t *p, krep_gpu_regex_info_t
         i += len;
     }
     if (L < 1)
-        return "regex: no atom";
+        return (bol || eol) ? "regex: ^, $ and ^$ on their own match the empty string: kept on krep's regex_search" : "regex: no atom";
+    if (L + bol + eol > kRegexMaxL)
+        return "regex: more than 16 places in a row (^ and $ take one each beside the byte classes)";
     uint32_t j = 0;
     for (uint32_t a = 0; a < n_atoms; ++a)
     {
@@ -200,10 +220,12 @@ inline const char *regex_compile(const search_params_t *p, krep_gpu_regex_info_t
         for (int b = 0; b < 256; ++b)
             if ((out->classes[best][b >> 3] >> (b & 7)) & 1u)
                 out->anchor_bytes[out->n_anchor++] = (uint8_t)b;
-    // can the pattern overlap itself: a shift d at which every class meets the one d places on
+    // can the pattern overlap itself: a shift d at which every class meets the one d places on; behind ^ the byte in front of the
+    // second occurrence, which lies inside the first, has to be a newline, and in front of $ the byte behind the first occurrence
+    auto holds_nl = [&](uint32_t k) { return ((out->classes[k]['\n' >> 3] >> ('\n' & 7)) & 1u) != 0; };
     for (uint32_t d = 1; d < L && !out->self_overlap; ++d)
     {
-        bool all = true;
+        bool all = (!bol || holds_nl(d - 1)) && (!eol || holds_nl(L - d));
         for (uint32_t k = 0; k + d < L && all; ++k)
         {
             bool meet = false;
@@ -213,7 +235,25 @@ inline const char *regex_compile(const search_params_t *p, krep_gpu_regex_info_t
         }
         out->self_overlap = all ? 1 : 0;
     }
+    *bol_out = bol;
+    *eol_out = eol;
     return nullptr;
+}
+// krep_gpu_regex_compile: exactly the unanchored grammar
+inline const char *regex_compile(const search_params_t *p, krep_gpu_regex_info_t *out)
+{
+    if (!p || !out)
+        return "NULL params";
+    int bol, eol;
+    return regex_compile_seq(p, false, out, &bol, &eol);
+}
+// krep_gpu_regex_compile_anchored: the same with an optional ^ in front and an optional $ at the end
+inline const char *regex_compile_anchored(const search_params_t *p, krep_gpu_regex_anchored_t *out)
+{
+    if (!p || !out)
+        return "NULL params";
+    out->bol = out->eol = 0;
+    return regex_compile_seq(p, true, &out->seq, &out->bol, &out->eol);
 }
 
 } // namespace kg

@@ -638,10 +638,10 @@ int split_mode(const search_params_t *p, const krep_gpu_config_t &c, size_t text
         return kSplitWhole;
     if (p->use_regex)
     { // a pattern that can overlap itself goes through the greedy pass over the whole occurrence list; -c never does (kg_regex.hip)
-        krep_gpu_regex_info_t info;
+        krep_gpu_regex_anchored_t info;
         if (regex_compile_cached(p, &info))
             return kSplitWhole;
-        return info.self_overlap && !p->count_lines_mode ? kSplitWhole : kSplitPieces;
+        return info.seq.self_overlap && !p->count_lines_mode ? kSplitWhole : kSplitPieces;
     }
     if (p->num_patterns > 1)
     {

@@ -48,6 +48,9 @@ class Engine:
                                        C.POINTER(abi.MatchResult), C.POINTER(C.c_uint64)]
         L.krep_gpu_regex_compile.restype = C.c_int
         L.krep_gpu_regex_compile.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexInfo)]
+        if hasattr(L, "krep_gpu_regex_compile_anchored"):  # (an older build loaded as an A/B partner lacks it: tools/ab_bench.py)
+            L.krep_gpu_regex_compile_anchored.restype = C.c_int
+            L.krep_gpu_regex_compile_anchored.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexAnchored)]
         L.krep_gpu_can_accelerate.restype = C.c_int
         L.krep_gpu_can_accelerate.argtypes = [C.POINTER(abi.SearchParams)]
         L.krep_gpu_config_default.restype = None
@@ -289,6 +292,14 @@ class Engine:
         bytes, and every pattern is refused: locale.setlocale(locale.LC_CTYPE, "C") is the locale krep itself runs in."""
         info = abi.RegexInfo()
         if self.lib.krep_gpu_regex_compile(params.ref, C.byref(info)):
+            raise KrepGpuError(self.last_error())
+        return info
+
+    def regex_compile_anchored(self, params: abi.Params) -> "abi.RegexAnchored":
+        """krep_gpu_regex_compile_anchored: the same with a ^ in front and a $ behind taken as line anchors (bol / eol; seq holds the
+        real classes).  This is the compiler every search goes through; regex_compile() keeps refusing both anchors."""
+        info = abi.RegexAnchored()
+        if self.lib.krep_gpu_regex_compile_anchored(params.ref, C.byref(info)):
             raise KrepGpuError(self.last_error())
         return info
 

@@ -1,6 +1,7 @@
 """A/B of several builds of libkrep_gpu.so IN ONE PROCESS on the same HBM buffers (development aid).
 Process-to-process variance of a 32 GiB scan is +-4 % on this part (placement), far above most kernel-level differences.
-usage: python tools/ab_bench.py <gib> <kind: 2 literal8 | 3 memchr1 | 4 ac1000> <mode: pos|count|lines|format|matches> <variant.so> [...]
+usage: python tools/ab_bench.py <gib> <kind: 2 literal8 | 3 memchr1 | 4 ac1000> <mode: pos|count|total|lines|format|matches> <variant.so> [...]
+mode total: the match count alone (track_positions off).  AB_REGEX=1: AB_PATTERN is a regular expression (krep -E, scanned in the C locale).
 mode format: not the scan but krep_gpu_format_lines of every build on ONE record list (the first build's scan), calls alternating,
 events around each call; name a build twice to see the spread it shows against itself.  mode matches: the same for krep_gpu_format_matches."""
 import os, sys, statistics
@@ -28,6 +29,12 @@ engs[0][1].generate(buf.data_ptr(), n, 0, wl["kind"], 42, wl["plant"], wl["perio
 if os.environ.get("AB_PATTERN"):
     wl["patterns"] = [os.environ["AB_PATTERN"].encode()]
 kw = dict(count_lines=True, only_match=True) if mode == "count" else dict(count_lines=True) if mode == "lines" else {}
+if mode == "total":
+    kw = dict(track_positions=False)
+if os.environ.get("AB_REGEX"):
+    import locale
+    locale.setlocale(locale.LC_CTYPE, "C")  # the locale krep runs in: the -E compiler takes no pattern in a multibyte one
+    kw["regex"] = True
 cap = (n // int(os.environ.get("AB_CAP_DIV", "50" if kind == 3 else "1500"))) + 4096 if mode in ("pos", "format", "matches") else 0  # (AB_CAP_DIV: denser patterns through AB_PATTERN)
 pos = torch.empty(2 * cap, dtype=torch.int64, device="cuda") if cap else None
 plans = []

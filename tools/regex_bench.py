@@ -58,7 +58,13 @@ plan.close()
 literal_matches = out.total_matches
 
 JOBS = [(b"Sherl[oO]ck", "anchor path", ("count", "records")), (b"[A-Z][a-z]{7}", "table path", ("count", "records")),
-        (b"[a-z]{4}", "dense", ("count", "-c")), (b"Sherlock", "a literal as a regex", ("count", "records"))]
+        (b"[a-z]{4}", "dense", ("count", "-c")), (b"Sherlock", "a literal as a regex", ("count", "records")),
+        # line anchors: each row beside its unanchored twin above (few lines of the haystack start with the planted word, most end
+        # behind a run of lower-case letters)
+        (b"^Sherlock", "anchor path, ^", ("count", "records")), (b"[a-z]{4}$", "dense, $", ("count", "-c")),
+        (b"^[A-Z][a-z]{7}$", "table path, ^ and $", ("count", "records"))]
+TWIN = {b"^Sherlock": b"Sherlock", b"[a-z]{4}$": b"[a-z]{4}", b"^[A-Z][a-z]{7}$": b"[A-Z][a-z]{7}"}
+took = {}
 for pat, what, modes in JOBS:
     for mode in modes:
         kw = dict(count_lines=True) if mode == "-c" else dict(track_positions=(mode == "records"))
@@ -66,8 +72,10 @@ for pat, what, modes in JOBS:
         ms, out = median_ms(plan, mode == "records")
         plan.close()
         ref_ms = yard["records" if mode == "records" else "count"]
+        took[pat, mode] = ms
+        twin = f"; {ms / took[TWIN[pat], mode]:4.2f} x the time of {TWIN[pat].decode()}" if pat in TWIN else ""
         say(f"regex    {pat.decode():<16} {mode:<8} {ms:8.3f} ms {n / ms / 1e6:7.0f} GB/s  ratio {ref_ms / ms:4.2f}  "
-            f"{'lines' if mode == '-c' else 'matches'} {out.count}  ({what})")
+            f"{'lines' if mode == '-c' else 'matches'} {out.count}  ({what}{twin})")
         if pat in (b"Sherl[oO]ck", b"Sherlock") and mode != "-c":
             assert out.total_matches == literal_matches, (pat, out.total_matches, literal_matches)
 

@@ -1,8 +1,8 @@
 // tools/regex_compile_san.cpp — the -E pattern compiler (krep_amd/csrc/kg_regex_compile.h: host code, no HIP) as a stand-alone
 // program for AddressSanitizer / UBSan:  python tools/sanitize.py regex   (or by hand:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer tools/regex_compile_san.cpp -o regex_compile_san).
-// It feeds the tokeniser accepted patterns, every refusal, and 200 000 pattern strings drawn from the bytes the grammar cares
-// about, each copied into a heap block of exactly its length so that a read past the pattern is a report.
+// It feeds both entry points' compilers accepted patterns, every refusal, and 200 000 pattern strings drawn from the bytes the
+// grammar cares about (^ and $ among them), each copied into a heap block of exactly its length so that a read past the pattern is a report.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -11,7 +11,8 @@
 
 #include "../krep_amd/csrc/kg_regex_compile.h"
 
-static int compile(const std::string &pat, bool cs, bool ww, krep_gpu_regex_info_t *info, const char **why)
+static int compile(const std::string &pat, bool cs, bool ww, krep_gpu_regex_info_t *info, const char **why,
+                   krep_gpu_regex_anchored_t *anchored = nullptr) // anchored: krep_gpu_regex_compile_anchored's compiler instead
 {
     char *heap = (char *)malloc(pat.size() ? pat.size() : 1); // exactly the pattern: no terminator to lean on
     memcpy(heap, pat.data(), pat.size());
@@ -28,7 +29,7 @@ static int compile(const std::string &pat, bool cs, bool ww, krep_gpu_regex_info
     p.use_regex = true;
     p.whole_word = ww;
     p.max_count = SIZE_MAX;
-    *why = kg::regex_compile(&p, info);
+    *why = anchored ? kg::regex_compile_anchored(&p, anchored) : kg::regex_compile(&p, info);
     free(heap);
     return *why ? 2 : 0;
 }
@@ -60,10 +61,44 @@ int main()
         printf("FAIL: -w accepted\n");
         ++bad;
     }
+    // the anchored entry point: accepted shapes with their anchors and L, every new refusal, and what the old one still refuses
+    krep_gpu_regex_anchored_t an;
+    struct { const char *pat; int bol, eol; unsigned L; int overlap; } aok[] = {
+        {"^a", 1, 0, 1, 0}, {"a$", 0, 1, 1, 0}, {"^a$", 1, 1, 1, 0}, {"^Sherl[oO]ck", 1, 0, 8, 0}, {"[0-9]{3}$", 0, 1, 3, 0},
+        {"^[[:space:]]", 1, 0, 1, 0}, {"\\^a", 0, 0, 2, 0}, {"a\\$", 0, 0, 2, 0}, {"[$^]", 0, 0, 1, 0}, {"^a{15}", 1, 0, 15, 0},
+        {"^a{14}$", 1, 1, 14, 0}, {"^ab", 1, 0, 2, 0}, {"ab$", 0, 1, 2, 0}, {"^[a\n]{2}", 1, 0, 2, 1}, {"^[ab]{2}", 1, 0, 2, 0},
+        {"[a\n]{2}$", 0, 1, 2, 1}, {"\\$$", 0, 1, 1, 0}, {"[\\]$", 0, 1, 1, 0}, {"^[^a]", 1, 0, 1, 0}, {"Sherl[oO]ck", 0, 0, 8, 0}};
+    for (const auto &c : aok)
+        for (int cs = 0; cs < 2; ++cs)
+            if (compile(c.pat, cs != 0, false, &info, &why, &an) != 0 || an.bol != c.bol || an.eol != c.eol || an.seq.L != c.L ||
+                an.seq.self_overlap != c.overlap)
+            {
+                printf("FAIL: anchored %s: %s\n", c.pat, why ? why : "wrong fields");
+                ++bad;
+            }
+    const char *ano[] = {"^a{16}", "^a{15}$", "a^b", "a$b", "^^a", "a$$", "^$", "^", "$", "^{2}a", "^a|b", "^(a)", "^a.*b", "a+$", "^a{2,3}",
+                         "^\\bword", "^[ab", "^a\\", "", "^a{", "^[[:alpha:", "$a", "a{2}^", "^a{0}"};
+    for (const char *s : ano)
+        if (compile(s, true, false, &info, &why, &an) != 2 || !why || !*why)
+        {
+            printf("FAIL: anchored %s accepted\n", s);
+            ++bad;
+        }
+    for (const char *s : {"^a", "a$", "^a$", "^", "$", "^$"})
+        if (compile(s, true, false, &info, &why) != 2 || !why || !*why)
+        {
+            printf("FAIL: krep_gpu_regex_compile's compiler takes %s\n", s);
+            ++bad;
+        }
+    if (compile("^ab", true, true, &info, &why, &an) != 2)
+    {
+        printf("FAIL: anchored -w accepted\n");
+        ++bad;
+    }
     // pattern strings over the bytes the grammar looks at
-    const char alphabet[] = "ab[]^-:.={},\\0129(|*\n x";
+    const char alphabet[] = "ab[]^-:.={},\\0129(|*\n x$";
     unsigned long long s = 88172645463325252ull;
-    unsigned taken = 0, refused = 0;
+    unsigned taken = 0, refused = 0, ataken = 0;
     for (int i = 0; i < 200000; ++i)
     {
         std::string pat;
@@ -85,7 +120,25 @@ int main()
         }
         else
             ++refused;
+        // the same string through the anchored compiler: it takes whatever the old one takes, with the same fields, and more
+        const bool old_ok = why == nullptr;
+        const krep_gpu_regex_info_t old = info;
+        if (compile(pat, (s >> 40) & 1, false, &info, &why, &an) == 0)
+        {
+            ++ataken;
+            if (an.seq.L < 1 || an.seq.L + (an.bol != 0) + (an.eol != 0) > 16 || an.seq.anchor >= an.seq.L || an.seq.n_anchor > 4 ||
+                (an.bol != 0) != (pat[0] == '^') || (an.eol && pat.back() != '$') || (old_ok && (an.bol || an.eol || memcmp(&old, &an.seq, sizeof old))))
+            {
+                printf("FAIL: inconsistent anchored info for a random pattern\n");
+                ++bad;
+            }
+        }
+        else if (old_ok)
+        {
+            printf("FAIL: the anchored compiler refuses what the old one takes\n");
+            ++bad;
+        }
     }
-    printf("regex_compile_san: %u random patterns taken, %u refused, %d failures\n", taken, refused, bad);
+    printf("regex_compile_san: %u random patterns taken, %u refused, %u taken with anchors allowed, %d failures\n", taken, refused, ataken, bad);
     return bad ? 1 : 0;
 }
