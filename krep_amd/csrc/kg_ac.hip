@@ -719,8 +719,12 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
                         };
                         mA = clip(mA, pos);
                         mB = clip(mB, pos + 1u);
-                        slA = muA && mA != 0u; // (a pattern the dictionary holds twice: counted and emitted by the level walk)
-                        slB = muB && mB != 0u;
+                        // a `multi` entry (a pattern the dictionary holds twice, or the 16-byte stand-in of a LONGER pattern, kg_ac_anchor.hip
+                        // exact_table): counted and emitted by the level walk, which owns by the TRUE start.  Decided on the unclipped answer —
+                        // the clip above takes a stand-in for a 16-byte pattern and would drop a longer one that starts in front of own_hi
+                        // and ends 16 bytes or more behind it (muA implies a hit, i.e. a mask that was not empty before the clip).
+                        slA = muA;
+                        slB = muB;
                         exact_done = true;
                     }
                 if (exact_done)
@@ -765,12 +769,12 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
                         if (slA)
                         {
                             const u32 m = clipx(ac_exact_end<CI>(a, pos, mu), pos);
-                            if (!mu || !m) { mA = m; slA = false; }
+                            if (!mu) { mA = m; slA = false; } // (mu: the level walk decides, by the true start — a stand-in's bit 16 is not its length)
                         }
                         if (slB)
                         {
                             const u32 m = clipx(ac_exact_end<CI>(a, pos + 1u, mu), pos + 1u);
-                            if (!mu || !m) { mB = m; slB = false; }
+                            if (!mu) { mB = m; slB = false; }
                         }
                         dmA = mA; dmB = mB;
                         cA = (u32)__popc(mA); cB = (u32)__popc(mB);

@@ -63,7 +63,7 @@ extern "C" int krep_gpu_alloc_placed(int device, size_t text_bytes, size_t recor
         {
             if (rec) krep_gpu_plan_destroy(rec);
             if (cnt) krep_gpu_plan_destroy(cnt);
-            return 2;
+            return kg::fail("krep_gpu_alloc_placed: the probe plans could not be created on device %d (%s)", device, krep_gpu_last_error());
         }
     }
     std::vector<void *> cand;
@@ -97,16 +97,18 @@ extern "C" int krep_gpu_alloc_placed(int device, size_t text_bytes, size_t recor
         }
         float c_ms = 1e30f, r_ms[3] = {0, 0, 0};
         bool ok = krep_gpu_generate(p, probe_len, 0, 3, 0x9e3779b97f4a7c15ull + (uint64_t)i, "#", 1, 0, nullptr) == 0;
-        krep_gpu_scan_out_t out;
+        krep_gpu_scan_out_t out{};
         for (int k = 0; ok && k < 3; ++k)
         {
             ok = krep_gpu_scan_device(cnt, p, probe_len, 0, probe_len, 0, nullptr, 0, nullptr, 1, &out) == 0;
-            c_ms = std::min(c_ms, out.kernel_ms);
+            if (ok)
+                c_ms = std::min(c_ms, out.kernel_ms);
         }
         for (int k = 0; ok && k < 3; ++k)
         {
             ok = krep_gpu_scan_device(rec, p, probe_len, 0, probe_len, 0, (match_position_t *)((uint8_t *)p + text_area), cap, nullptr, 1, &out) == 0;
-            r_ms[k] = out.kernel_ms;
+            if (ok)
+                r_ms[k] = out.kernel_ms;
         }
         if (!ok)
         { // a probe that cannot run is not a reason to fail the allocation: the first candidate, as the driver placed it

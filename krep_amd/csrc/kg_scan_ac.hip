@@ -193,10 +193,11 @@ static int scan_ac_split(krep_gpu_plan *pl, const Window &w, match_position_t *d
 {
     if (ac_split_decide(pl, w, st) != 2)
         return 1;
-    // Under a max_count smaller than the caller's list the result is the first max_count records of the MERGED list: either part may
-    // contribute all of them, so both parts' first max_count records go to a scratch list of the plan, are merged there, and the first
-    // max_count are copied out.  Without such a limit the caller's list holds everything (or overflows, as always).
-    const bool want = d_pos && pl->track, limited = want && (uint64_t)pl->max_count < cap;
+    // Under a max_count that the caller's list can hold (max_count == cap included: the long part alone could fill that list) the
+    // result is the first max_count records of the MERGED list: either part may contribute all of them, so both parts' first max_count
+    // records go to a scratch list of the plan, are merged there, and the first max_count are copied out.  Without such a limit the
+    // caller's list holds everything (or overflows, as always).
+    const bool want = d_pos && pl->track, limited = want && pl->max_count != SIZE_MAX && (uint64_t)pl->max_count <= cap;
     match_position_t *dst = d_pos;
     uint64_t room = cap;
     if (limited)
