@@ -112,7 +112,8 @@ enum krep_ref_algo
     KREP_RA_NEON = 8,         /* neon_search          krep.c:4506 */
     KREP_RA_AHO_CORASICK = 9, /* aho_corasick_search  aho_corasick.c:299 */
     KREP_RA_REGEX = 10        /* regex_search         krep.c:1389 — the fixed-length class sequences of
-                                 krep_gpu_regex_compile() below; every other expression stays on the CPU */
+                                 krep_gpu_regex_compile() below and their alternations
+                                 (krep_gpu_regex_compile_alt()); every other expression stays on the CPU */
 };
 
 /* All of it in one explicit object.  Plans and search_buffer_ex() carry their configuration; the setters below write the
@@ -223,12 +224,12 @@ uint64_t krep_gpu_literal_search(const search_params_t *params, const char *text
                                  size_t text_len, match_result_t *result);
 uint64_t krep_gpu_aho_corasick_search(const search_params_t *params, const char *text_start,
                                       size_t text_len, match_result_t *result);
-/* regex_search (krep.c:1389-1579) for the patterns krep_gpu_regex_compile_anchored() accepts; params->compiled_regex is never read here
+/* regex_search (krep.c:1389-1579) for the patterns krep_gpu_regex_compile_anchored() or krep_gpu_regex_compile_alt() accepts; params->compiled_regex is never read here
  * and goes to the registered CPU function untouched when the attempt fails. */
 uint64_t krep_gpu_regex_search(const search_params_t *params, const char *text_start,
                                size_t text_len, match_result_t *result);
 /* Drop-in for select_search_algorithm(): returns one of the three functions above, or NULL when the backend does not
- * take the search — no usable device (krep_gpu_available() == 0), a regex krep_gpu_regex_compile_anchored() refuses, and the input classes
+ * take the search — no usable device (krep_gpu_available() == 0), a regex both -E compilers refuse, and the input classes
  * krep_gpu_can_accelerate() names — so that the caller keeps the CPU function pointer the reference's own
  * select_search_algorithm() gives it.  (-c through simd_sse42_search / kmp_search with a newline inside the pattern, refused
  * until round 3, is reproduced: one device thread walks the ordered occurrence list the way the reference's loop moves.) */
@@ -236,8 +237,10 @@ search_func_t krep_gpu_select_search_algorithm(const search_params_t *params);
 /* 1 when the backend takes the search for `params` under the current configuration, 0 when not:
  *   - no usable gfx950 device (krep_gpu_available() == 0);
  *   - no pattern at all (num_patterns == 0 and pattern == NULL);
- *   - use_regex with a pattern krep_gpu_regex_compile_anchored() refuses (anything that is not a fixed number of byte classes
- *     in a row with an optional ^ in front and $ behind, several patterns, -w).
+ *   - use_regex with a search both krep_gpu_regex_compile_anchored() and krep_gpu_regex_compile_alt() refuse (anything that is
+ *     neither a fixed number of byte classes in a row with an optional ^ in front and $ behind nor an alternation of such
+ *     sequences without anchors; -w).  The reason reported is the alternation compiler's when the search says an alternation
+ *     (several patterns, or a '|' or '(' outside brackets and not behind a backslash), else the anchored compiler's.
  * (count_lines_mode together with only_matching through memchr_short_search — a combination krep's main() never produces,
  * krep.c:3811-3814 — was refused until round 5 and is reproduced now: one window, krep_gpu_split_mode() = WHOLE.)
  * An operator called with such params anyway treats it like a run-time failure (see the top of this header): the
@@ -318,6 +321,40 @@ typedef struct krep_gpu_regex_anchored
 } krep_gpu_regex_anchored_t;
 /* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
 int krep_gpu_regex_compile_anchored(const search_params_t *params, krep_gpu_regex_anchored_t *out);
+
+/* ---- alternations of class sequences: ERROR|WARN|FATAL, cat|d[oi]g|b.rd, and every -E run with several -e ----
+ * Grammar: every pattern of params (patterns[0..num_patterns), or pattern alone) is B ( '|' B )*, each B either a class sequence
+ *   of the unanchored grammar above or one such sequence inside exactly one pair of parentheses, (Sherl[oO]ck).  The branches of
+ *   all patterns together are the alternation: that is what the CLI's (p1)|(p2) means.  '|', '(' and ')' inside a bracket
+ *   expression or behind a backslash stay ordinary.  Branches whose class tables are identical are merged.
+ * Refused (2, each with its own reason): an empty branch (a|, |a, (), a||b: it matches the empty string); nested or unbalanced
+ *   parentheses; a group that is not a whole branch (x(a|b)y, (ab)c, (ab){2}, (a|b)); ^ or $ in any branch; more than 8 branches
+ *   after merging; a branch of more than 16 classes; total_L > 32; and everything krep_gpu_regex_compile() refuses in a branch.
+ *   krep_gpu_regex_compile() and krep_gpu_regex_compile_anchored() keep refusing '|', '(', ')' and several patterns: everything that
+ *   takes a search asks the anchored compiler first and this one only when that one refuses, so a pattern accepted there runs
+ *   the kernel it always ran.
+ * What a scan reproduces (regex_search, checked against the compiled reference with a brute-force model): branch i with classes
+ *   C[i][0..L_i) occurs at p when text[p + j] is in C[i][j] for all j and p + L_i <= text_len.  The occurrence at p is
+ *   (p, p + len(p)), len(p) the LONGEST L_i among the branches that occur at p (POSIX leftmost-longest: ab|abc on xabcabx gives
+ *   (1,4),(4,6)).  Matches: the greedy leftmost non-overlapping selection over the positions that hold an occurrence, consuming
+ *   len(p) (a|aa on aaaaa gives (0,2),(2,4),(4,5)); records ascend in start.  -c: the distinct lines that hold the start of any
+ *   branch's occurrence (no greedy selection: after a counted line the reference jumps to the next line start); a start ON a
+ *   '\n' belongs to the line that newline ends.  max_count, its 0 quirk, only_matching and reference_simd as above.
+ * cross_overlap: 1 iff there are branches i, j and a shift d, 0 <= d < L_i (d >= 1 when i == j), such that C[i][d + t] meets
+ *   C[j][t] for every t with d + t < L_i and t < L_j: two occurrences can share a byte (d == 0 with i != j is the same start).
+ * Split: -c is always KREP_GPU_SPLIT_PIECES; without -c PIECES when cross_overlap == 0, else KREP_GPU_SPLIT_WHOLE (the greedy
+ *   pass runs over the whole occurrence list, and a window that is not the whole text is refused (2)).  Halo and shards use
+ *   Lmax <= 16 where a single sequence uses L. */
+typedef struct krep_gpu_regex_alt
+{
+    uint32_t n_branches;             /* 1..8, after identical branches have been merged              */
+    uint32_t Lmin, Lmax, total_L;    /* over the branches; every L in 1..16, total_L <= 32            */
+    int cross_overlap;               /* 1: two occurrences (of one branch or of two) can share a byte */
+    uint32_t reserved;
+    krep_gpu_regex_info_t branch[8]; /* each exactly what krep_gpu_regex_compile() makes of the branch alone */
+} krep_gpu_regex_alt_t;
+/* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
+int krep_gpu_regex_compile_alt(const search_params_t *params, krep_gpu_regex_alt_t *out);
 
 /* The in-memory twin of search_file()/search_string() that BASELINE.json calls search_buffer():
  * validation as krep.c:2013-2049 (no patterns -> 2; empty pattern among several -> 2; pattern
@@ -479,7 +516,7 @@ enum krep_gpu_split
 {
     KREP_GPU_SPLIT_WHOLE = 0,  /* one window only: neon_search's max_count == 0 corner, -c with -o through
                                   memchr_short_search (never produced by krep's main()), and a regex that can overlap
-                                  itself without -c (krep_gpu_regex_compile)                                               */
+                                  itself without -c (krep_gpu_regex_compile; an alternation: cross_overlap)                */
     KREP_GPU_SPLIT_PIECES = 1, /* independent pieces: start-offset ownership + halo, results concatenate / merge          */
     KREP_GPU_SPLIT_CHAIN = 2   /* pieces in text order through krep_gpu_scan_device_seq() (round 5: also -c with a newline
                                   inside a pattern, multi-pattern and through simd_sse42_search / kmp_search)             */

@@ -145,6 +145,12 @@ class RegexAnchored(C.Structure):
     _fields_ = [("seq", RegexInfo), ("bol", C.c_int), ("eol", C.c_int)]
 
 
+class RegexAlt(C.Structure):
+    """krep_gpu_regex_alt_t: what krep_gpu_regex_compile_alt() makes of an alternation of class sequences (a|b, several -e patterns)"""
+    _fields_ = [("n_branches", C.c_uint32), ("Lmin", C.c_uint32), ("Lmax", C.c_uint32), ("total_L", C.c_uint32),
+                ("cross_overlap", C.c_int), ("reserved", C.c_uint32), ("branch", RegexInfo * 8)]
+
+
 class ShardInfo(C.Structure):
     """krep_gpu_shard_info_t: where the calling thread's last sharded host search ran."""
     _fields_ = [("shards", C.c_int), ("devices_used", C.c_int), ("device_ids", C.c_int * 16), ("comm_ranks", C.c_int),

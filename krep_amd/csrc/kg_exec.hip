@@ -1016,7 +1016,7 @@ void gather_pieces(std::vector<Piece> &pcs, match_position_t *dst, bool multi)
 // the records of `ret` > 0 matches: the merged piece lists, cut with the reference's -m conventions
 int emit_records(const PieceJob &job, std::vector<Piece> &pcs, uint64_t ret, match_result_t *out)
 {
-    const bool multi = job.params->num_patterns > 1;
+    const bool multi = job.params->num_patterns > 1 && !job.params->use_regex; // (several -E patterns: one alternation, records by start)
     const size_t maxc = job.params->max_count;
     size_t tot = 0;
     for (const Piece &p : pcs)
@@ -1059,7 +1059,7 @@ int run_pieces(const search_params_t *params, const krep_gpu_config_t &cfg, cons
         return kg::fail("no HIP device available");
     const PieceJob job{params, cfg, buf, len, params->track_positions && out != nullptr && !params->count_lines_mode,
                        kg::split_mode(params, cfg, len) == kSplitChain,
-                       params->num_patterns > 1 ? KREP_RA_AHO_CORASICK : mirror_effective(mirror_top(params, cfg), params, len),
+                       params->num_patterns > 1 && !params->use_regex ? KREP_RA_AHO_CORASICK : mirror_effective(mirror_top(params, cfg), params, len),
                        (int)std::min<size_t>((size_t)std::max(1, num_gpus), len / 4096 + 1)};
     std::vector<Piece> pcs = piece_layout(job, chunk, ndev);
     std::vector<DeviceRun> runs;

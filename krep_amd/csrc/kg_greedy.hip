@@ -127,6 +127,68 @@ __global__ __launch_bounds__(kGB) void g_walk(const u64 *__restrict__ occ, u64 n
     }
 }
 
+// kWalkAlt (kg_regex_alt.hip): the list holds every (start, end) a branch of an alternation matches, ordered by start and, within a
+// start, by ascending end.  The reference reports the LONGEST occurrence of a start and resumes at its end: only the last record of
+// a run of equal starts can be visited, and the walk goes on at that record's own end.  Clusters split at gaps >= m = Lmax (no
+// record is longer), and a run of equal starts never spans two clusters (its gaps are 0).
+__global__ __launch_bounds__(kGB) void g_walk_alt(const u64 *__restrict__ occ, u64 n, u32 m, uint8_t *__restrict__ keep, u32 *too_long)
+{
+    const u64 i = (u64)blockIdx.x * kGB + threadIdx.x;
+    if (i >= n)
+        return;
+    const u64 s = occ[2 * i];
+    if (i != 0 && s - occ[2 * (i - 1)] < m)
+        return; // not the head of a cluster
+    u64 cur = s, prev = s;
+    for (u64 j = i; j < n; ++j)
+    {
+        const u64 sj = occ[2 * j];
+        if (j != i && sj - prev >= m)
+            break;
+        if (j - i >= kWalkBound)
+        {
+            *too_long = 1u;
+            return;
+        }
+        prev = sj;
+        if (sj < cur || (j + 1 < n && occ[2 * (j + 1)] == sj))
+        {
+            keep[j] = 0; // consumed by an earlier match, or a longer branch matches at the same start
+            continue;
+        }
+        keep[j] = kKeep | kVisited;
+        cur = occ[2 * j + 1];
+    }
+}
+// ... and its pointer-jumping form: a record that is not the last of its start hands the walk to the next record and is not
+// kept; the last one sends it to the first record that starts at or behind its end (the first of that start's run)
+__global__ __launch_bounds__(kGB) void g_next_alt(const u64 *__restrict__ occ, u64 n, u32 m, u64 *__restrict__ jump,
+                                                  uint8_t *__restrict__ visited, uint8_t *__restrict__ accept)
+{
+    const u64 i = (u64)blockIdx.x * kGB + threadIdx.x;
+    if (i >= n)
+        return;
+    const u64 s = occ[2 * i];
+    const bool last = i + 1 >= n || occ[2 * (i + 1)] != s;
+    accept[i] = last ? 1 : 0;
+    u64 lo = i + 1;
+    if (last)
+    {
+        const u64 target = occ[2 * i + 1];
+        u64 hi = n; // first j > i with start >= target (starts ascend)
+        while (lo < hi)
+        {
+            const u64 mid = lo + (hi - lo) / 2;
+            if (occ[2 * mid] < target)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+    }
+    jump[i] = lo; // n = end of the list
+    visited[i] = (i == 0 || s - occ[2 * (i - 1)] >= m) ? 1 : 0;
+}
+
 // ---- the same walk without a serial chain (giant clusters): pointer jumping ---------------------------------------------------
 // Visiting element i sends the walk to nxt[i] = the first element starting at or behind s_i + consume_i — a function of element
 // i alone.  The visited set is what cluster heads reach through nxt; log2(n) rounds of pointer doubling mark it:
@@ -465,14 +527,17 @@ int post_walk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint64_t
     HIPCHK(keep_reserve(s, n_occ));
     const u64 *occ = (const u64 *)s.d_occ;
     const u32 g1 = (u32)((n_occ + kGB - 1) / kGB);
-    const u32 set_len = ws.mode != kWalkGreedy ? ws.m : 0u;
+    const u32 set_len = (ws.mode != kWalkGreedy && ws.mode != kWalkAlt) ? ws.m : 0u;
     const bool chain_only = ws.mode == kWalkShortOLines; // no cluster structure: the parallel form from the list's first element
     HIPCHK(hipMemsetAsync(s.d_keep, 0, n_occ, st));
     HIPCHK(hipMemsetAsync(&d_ctr->pad[1], 0, sizeof(u64), st));
     if (!chain_only)
     {
-        hipLaunchKernelGGL(g_walk, dim3(g1), dim3(kGB), 0, st, occ, (u64)n_occ, (u64)global_base, d_text, (u64)text_len, ws, s.d_keep,
-                           (u32 *)&d_ctr->pad[1]);
+        if (ws.mode == kWalkAlt)
+            hipLaunchKernelGGL(g_walk_alt, dim3(g1), dim3(kGB), 0, st, occ, (u64)n_occ, ws.m, s.d_keep, (u32 *)&d_ctr->pad[1]);
+        else
+            hipLaunchKernelGGL(g_walk, dim3(g1), dim3(kGB), 0, st, occ, (u64)n_occ, (u64)global_base, d_text, (u64)text_len, ws, s.d_keep,
+                               (u32 *)&d_ctr->pad[1]);
         HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
@@ -489,7 +554,10 @@ int post_walk(PostScratch &s, const uint8_t *d_text, uint64_t text_len, uint64_t
         }
         u64 *ja = jmp, *jb = jmp + n_occ;
         uint8_t *va = flags, *vb = flags + n_occ, *acc = flags + 2 * n_occ;
-        hipLaunchKernelGGL(g_next, dim3(g1), dim3(kGB), 0, st, occ, (u64)n_occ, (u64)global_base, d_text, (u64)text_len, ws, ja, va, acc);
+        if (ws.mode == kWalkAlt)
+            hipLaunchKernelGGL(g_next_alt, dim3(g1), dim3(kGB), 0, st, occ, (u64)n_occ, ws.m, ja, va, acc);
+        else
+            hipLaunchKernelGGL(g_next, dim3(g1), dim3(kGB), 0, st, occ, (u64)n_occ, (u64)global_base, d_text, (u64)text_len, ws, ja, va, acc);
         for (u64 span = 1; span < n_occ; span <<= 1)
         {
             (void)hipMemcpyAsync(vb, va, n_occ, hipMemcpyDeviceToDevice, st);

@@ -137,6 +137,8 @@ constexpr uint32_t kWalkGreedy = 0; // simd_sse42_search / kmp_search (and BMH u
 constexpr uint32_t kWalkShortO = 1; // memchr_short_search under -o: first-byte candidates, m skipped after a failed one too
 constexpr uint32_t kWalkShortOLines = 2; // ... with -c as well (krep.c:4449-4470): an accepted match counts its line and sends the
                                          // walk to the next line start — every visited accepted candidate is one counted line
+constexpr uint32_t kWalkAlt = 3;    // krep -E alternation (kg_regex_alt.hip): records ordered by start, equal starts in ascending length; the
+                                    // longest record of a visited start is kept and consumes its own length; m = Lmax splits the clusters
 struct WalkSpec
 {
     uint32_t mode, m;
@@ -223,8 +225,17 @@ int mirror_effective(int top, const search_params_t *p, size_t text_len);
 const char *unsupported_reason(const search_params_t *p, const krep_gpu_config_t &c); // NULL = accelerated
 // kg_regex_compile.h behind a one-entry cache per thread: an operator call asks the selector, the executor, the split rule and (on a
 // cache miss) the plan about the same pattern, and one compile is up to 16 regcomp calls and 4096 regexec probes.  The key is
-// everything the compiler reads (pattern bytes, case, -w, the number of patterns, whether the locale is multibyte).
-const char *regex_compile_cached(const search_params_t *p, krep_gpu_regex_anchored_t *out); // NULL: taken; else the refusal
+// everything the compilers read (the bytes and the length of every pattern, case, -w, whether the locale is multibyte).
+// The anchored compiler is asked first; only what it refuses goes to the alternation compiler (is_alt: that one took it).  The
+// refusal of a search both refuse is the alternation compiler's when the search says an alternation (several patterns, or a '|'
+// or '(' outside brackets and not behind a backslash), else the anchored compiler's.
+struct RegexCompiled
+{
+    bool is_alt = false;
+    krep_gpu_regex_anchored_t seq{}; // !is_alt
+    krep_gpu_regex_alt_t alt{};      // is_alt
+};
+const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out); // NULL: taken; else the refusal
 constexpr int kSplitWhole = 0, kSplitPieces = 1, kSplitChain = 2; // enum krep_gpu_split (include/krep_gpu.h)
 int split_mode(const search_params_t *p, const krep_gpu_config_t &c, size_t text_len);
 bool shardable(const search_params_t *p, const krep_gpu_config_t &c, size_t text_len); // split_mode != whole

@@ -152,7 +152,8 @@ extern "C" const char *krep_gpu_algorithm_name(int a)
 
 // ------------------------------------------------------------------------------------ what is accelerated
 // A regular expression (-E) is taken when krep_gpu_regex_compile_anchored() accepts it: a fixed number of byte classes in a row
-// (an optional ^ in front, an optional $ behind), one pattern,
+// (an optional ^ in front, an optional $ behind), one pattern, or when krep_gpu_regex_compile_alt() accepts what that one refuses:
+// an alternation of up to 8 such sequences without anchors, in one pattern or several;
 // no -w; every other expression stays with krep's regex_search.  Beyond that ONE input class is not taken; for it krep_gpu_can_accelerate() says 0, krep_gpu_select_search_algorithm() returns NULL (the
 // caller keeps its CPU function pointer, exactly like the regex case) and an operator called with it anyway takes the failure road:
 //  * memchr_short_search in -c mode while the file-static only_matching is set: main() never produces that
@@ -160,39 +161,56 @@ extern "C" const char *krep_gpu_algorithm_name(int a)
 // (Round 3: -c through simd_sse42_search / kmp_search with a '\n' inside the pattern — refused until then — is reproduced by a
 //  walk over the ordered occurrence list, kg_greedy.hip (3).)
 namespace kg {
-const char *regex_compile_cached(const search_params_t *p, krep_gpu_regex_anchored_t *out)
+// both compilers in the order every search asks them (kg_internal.h)
+static const char *regex_compile_both(const search_params_t *p, RegexCompiled *out)
+{
+    out->is_alt = false;
+    const char *why = regex_compile_anchored(p, &out->seq);
+    if (!why)
+        return nullptr;
+    if (!p || !p->use_regex)
+        return why;
+    if (const char *why_alt = regex_compile_alt(p, &out->alt))
+        return regex_has_alt_syntax(p) ? why_alt : why;
+    out->is_alt = true;
+    return nullptr;
+}
+const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out)
 {
     struct Entry
     {
         bool valid = false, cs = false, ww = false, mb = false;
-        size_t np = 0;
-        std::string pat;
-        krep_gpu_regex_anchored_t info{};
+        std::string key; // every pattern: its length, then its bytes
+        RegexCompiled rc;
         const char *why = nullptr;
     };
     static thread_local Entry e;
     if (!p || !out || !p->use_regex)
-        return regex_compile_anchored(p, out);
-    const char *pat = p->pattern;
-    size_t n = p->pattern_len;
-    if (p->num_patterns == 1 && p->patterns && p->pattern_lens && p->patterns[0])
+        return out ? regex_compile_both(p, out) : "NULL params";
+    if (p->num_patterns > 1 && !(p->patterns && p->pattern_lens))
+        return regex_compile_both(p, out);
+    std::string key;
+    const size_t np = regex_pattern_count(p);
+    for (size_t k = 0; k < np; ++k)
     {
-        pat = p->patterns[0];
-        n = p->pattern_lens[0];
+        const uint8_t *pat;
+        size_t n;
+        regex_pattern_at(p, k, &pat, &n);
+        if (!pat || n > 1024)
+            return regex_compile_both(p, out);
+        key.append((const char *)&n, sizeof n);
+        key.append((const char *)pat, n);
     }
-    if (!pat || n > 1024)
-        return regex_compile_anchored(p, out);
     const bool mb = MB_CUR_MAX > 1;
-    if (!(e.valid && e.cs == p->case_sensitive && e.ww == p->whole_word && e.mb == mb && e.np == p->num_patterns && e.pat.size() == n &&
-          memcmp(e.pat.data(), pat, n) == 0))
+    if (!(e.valid && e.cs == p->case_sensitive && e.ww == p->whole_word && e.mb == mb && e.key == key))
     {
         e.valid = false;
-        e.why = regex_compile_anchored(p, &e.info);
-        e.cs = p->case_sensitive; e.ww = p->whole_word; e.mb = mb; e.np = p->num_patterns;
-        e.pat.assign(pat, n);
+        e.why = regex_compile_both(p, &e.rc);
+        e.cs = p->case_sensitive; e.ww = p->whole_word; e.mb = mb;
+        e.key.swap(key);
         e.valid = true;
     }
-    *out = e.info;
+    *out = e.rc;
     return e.why;
 }
 const char *unsupported_reason(const search_params_t *p, const krep_gpu_config_t &c)
@@ -200,10 +218,10 @@ const char *unsupported_reason(const search_params_t *p, const krep_gpu_config_t
     if (!p)
         return "NULL params";
     if (p->use_regex)
-    { // -E: taken exactly when the pattern is a fixed number of byte classes in a row, ^ in front and $ behind allowed
-      // (kg_regex_compile.h names the refusals)
-        krep_gpu_regex_anchored_t info;
-        return regex_compile_cached(p, &info);
+    { // -E: taken exactly when the pattern is a fixed number of byte classes in a row, ^ in front and $ behind allowed, or an
+      // alternation of such sequences without anchors (kg_regex_compile.h names the refusals)
+        RegexCompiled rc;
+        return regex_compile_cached(p, &rc);
     }
     if (p->num_patterns > 1)
         return (p->patterns && p->pattern_lens) ? nullptr : "several patterns announced but patterns / pattern_lens are NULL";

@@ -91,8 +91,8 @@ static int run_host_operator(const search_params_t *raw, const char *text, size_
         return kg::fail("%s", why);
     if (const char *why = kg::device_unusable(cfg.device))
         return kg::fail("%s", why);
-    if (params->num_patterns > 1 && !params->ac_trie)
-        return 0; // aho_corasick.c:306: no trie, no matches
+    if (params->num_patterns > 1 && !params->ac_trie && !params->use_regex)
+        return 0; // aho_corasick.c:306: no trie, no matches (several -E patterns are one alternation: no trie is involved)
     DeviceGuard guard;
     int ndev = 1;
     (void)hipGetDeviceCount(&ndev);
@@ -217,7 +217,7 @@ extern "C" int search_buffer_ex(const search_params_t *params, const char *buf, 
     int st = 2;
     search_params_t local = *params;
     static int dummy_trie;
-    const bool no_trie = local.num_patterns > 1 && !local.ac_trie;
+    const bool no_trie = local.num_patterns > 1 && !local.ac_trie && !local.use_regex;
     if (no_trie)
         local.ac_trie = (ac_trie_t *)&dummy_trie; // search_string builds the trie itself (krep.c:2067-2078)
     // (a CPU function could not use that placeholder: the fallback needs the caller's real trie)

@@ -9,7 +9,7 @@
 #include "kg_common.h"
 #include "kg_internal.h"
 
-namespace kg { struct RegexProg; } // kg_regex.hip
+namespace kg { struct RegexProg; } // kg_regex_dev.h
 
 struct krep_gpu_plan
 {
@@ -36,7 +36,7 @@ struct krep_gpu_plan
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // multi-pattern
     kg::AcTables *ac = nullptr;
-    // regex (KREP_RA_REGEX): the compiled class sequence and its device table (kg_regex.hip)
+    // regex (KREP_RA_REGEX): the compiled class sequence, or alternation of them, and its device table (kg_regex.hip, kg_regex_alt.hip)
     kg::RegexProg *rx = nullptr;
     // a dictionary with 1..3-byte patterns beside many longer ones, on a text where the longer ones gain from anchors (kg_scan_ac.hip
     // scan_ac_split, round 6): the two parts as dictionaries of their own, scanned one after the other, their record lists merged

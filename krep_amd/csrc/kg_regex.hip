@@ -1,5 +1,7 @@
 // kg_regex.hip — krep -E for fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile): the exported pattern
-// compiler (kg_regex_compile.h), the bit-parallel shift-and scan kernel and its driver kg::scan_regex.
+// compilers (kg_regex_compile.h), the bit-parallel shift-and scan kernel and its driver kg::scan_regex.  An alternation of such
+// sequences (krep_gpu_regex_compile_alt) has its own kernel and driver in kg_regex_alt.hip: regex_prog_create builds its table
+// here, scan_regex hands over.
 //
 // The kernel.  T[byte] is a 16-bit mask, bit j set when byte is in class Cj.  It sits in LDS once per bank (entry b of copy k at
 // dword b * 32 + k, a lane reads copy lane % 32), so the 64 lookups of a wave instruction never meet in a bank whatever the
@@ -40,16 +42,9 @@
 #include "kg_internal.h"
 #include "kg_plan.h"
 #include "kg_regex_compile.h"
+#include "kg_regex_dev.h"
 
 namespace kg {
-
-struct RegexProg
-{
-    krep_gpu_regex_anchored_t info{};
-    u32 *d_table = nullptr; // T[256] over the extended sequence: bit 0 is ^'s newline when bol, bit bol + j class j, bit bol + L $'s newline
-};
-
-constexpr u32 kRxUnitBytes = kRoundsBig * kSegBytes; // 32 KiB of coordinates per wave unit
 
 struct RxArgs
 {
@@ -78,30 +73,6 @@ struct RxArgs
     Counters *ctr;
 };
 
-// 16 bytes from `off`, bytes at or past text_len read as 0
-static __device__ __noinline__ uint4 rx_load_guarded(const uint8_t *text, u64 text_len, u64 off)
-{
-    u32 v[4];
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-    {
-        u32 x = 0;
-        for (int b = 0; b < 4; ++b)
-        {
-            const u64 o = off + (u64)(w * 4 + b);
-            if (o < text_len)
-                x |= (u32)text[o] << (8 * b);
-        }
-        v[w] = x;
-    }
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-// bit k set iff lo <= q + k < hi, k = 0..15
-static __device__ __forceinline__ u32 rx_range(u64 q, u64 lo, u64 hi)
-{
-    const u32 lk = lo > q ? (u32)min(lo - q, (u64)16) : 0u, hk = hi > q ? (u32)min(hi - q, (u64)16) : 0u;
-    return ((1u << hk) - 1u) & ~((1u << lk) - 1u);
-}
 // the optimistic walk over a lane's 16 bytes: bit k of the result = bit L-1 of the state behind byte k; X = the exit state
 static __device__ __forceinline__ u32 rx_walk(const u32 *T, const uint4 &d, u32 Lm1, u32 &X)
 {
@@ -117,12 +88,6 @@ static __device__ __forceinline__ u32 rx_walk(const u32 *T, const uint4 &d, u32 
     X = S;
     return H >> 16;
 }
-static __device__ __forceinline__ u32 rx_newlines(const uint4 &d)
-{
-    return movemask4(eq_bytes(d.x, 0x0a0a0a0au)) | (movemask4(eq_bytes(d.y, 0x0a0a0a0au)) << 4) |
-           (movemask4(eq_bytes(d.z, 0x0a0a0a0au)) << 8) | (movemask4(eq_bytes(d.w, 0x0a0a0a0au)) << 12);
-}
-
 template <bool ANCH, bool LINES, bool EMIT>
 __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
 {
@@ -354,23 +319,45 @@ static hipError_t rx_run(const RxArgs &a, bool lines, bool emit, int num_cu, hip
 RegexProg *regex_prog_create(const search_params_t &sp)
 {
     auto *rx = new RegexProg();
-    if (const char *why = regex_compile_cached(&sp, &rx->info))
+    RegexCompiled rc;
+    if (const char *why = regex_compile_cached(&sp, &rc))
     {
         fail("%s", why);
         delete rx;
         return nullptr;
     }
-    const krep_gpu_regex_info_t &seq = rx->info.seq;
-    const u32 bol = rx->info.bol ? 1u : 0u, eol = rx->info.eol ? 1u : 0u;
     u32 table[256];
-    for (int b = 0; b < 256; ++b)
-    {
-        u32 m = 0;
-        for (u32 j = 0; j < seq.L; ++j)
-            m |= ((seq.classes[j][b >> 3] >> (b & 7)) & 1u) << (bol + j);
-        table[b] = m;
+    if (rc.is_alt)
+    { // an alternation: branch i in bits [o_i, o_i + L_i) (kg_regex_alt.hip)
+        rx->is_alt = true;
+        rx->alt = rc.alt;
+        memset(table, 0, sizeof table);
+        u32 o = 0;
+        for (u32 i = 0; i < rc.alt.n_branches; ++i)
+        {
+            const krep_gpu_regex_info_t &br = rc.alt.branch[i];
+            rx->init |= 1u << o;
+            rx->fin |= 1u << (o + br.L - 1);
+            for (int b = 0; b < 256; ++b)
+                for (u32 j = 0; j < br.L; ++j)
+                    table[b] |= ((br.classes[j][b >> 3] >> (b & 7)) & 1u) << (o + j);
+            o += br.L;
+        }
     }
-    table['\n'] |= bol | (eol << (bol + seq.L));
+    else
+    {
+        rx->info = rc.seq;
+        const krep_gpu_regex_info_t &seq = rx->info.seq;
+        const u32 bol = rx->info.bol ? 1u : 0u, eol = rx->info.eol ? 1u : 0u;
+        for (int b = 0; b < 256; ++b)
+        {
+            u32 m = 0;
+            for (u32 j = 0; j < seq.L; ++j)
+                m |= ((seq.classes[j][b >> 3] >> (b & 7)) & 1u) << (bol + j);
+            table[b] = m;
+        }
+        table['\n'] |= bol | (eol << (bol + seq.L));
+    }
     if (hipMalloc(&rx->d_table, sizeof table) != hipSuccess ||
         hipMemcpy(rx->d_table, table, sizeof table, hipMemcpyHostToDevice) != hipSuccess)
     {
@@ -397,6 +384,8 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
         *carry_out = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
     if (!pl->rx)
         return fail("scan_device: the regex plan holds no program");
+    if (pl->rx->is_alt)
+        return scan_regex_alt(pl, w, d_pos, cap, st, time_it, out);
     const krep_gpu_regex_info_t &info = pl->rx->info.seq;
     const u32 L = info.L, bol = pl->rx->info.bol ? 1u : 0u, eol = pl->rx->info.eol ? 1u : 0u;
     if (w.global_len < L || w.text_len < L || w.own_lo >= w.own_hi)
@@ -530,6 +519,13 @@ extern "C" int krep_gpu_regex_compile_anchored(const search_params_t *params, kr
 {
     krep_gpu_clear_error();
     if (const char *why = kg::regex_compile_anchored(params, out))
+        return kg::fail("%s", why);
+    return 0;
+}
+extern "C" int krep_gpu_regex_compile_alt(const search_params_t *params, krep_gpu_regex_alt_t *out)
+{
+    krep_gpu_clear_error();
+    if (const char *why = kg::regex_compile_alt(params, out))
         return kg::fail("%s", why);
     return 0;
 }

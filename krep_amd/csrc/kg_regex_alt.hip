@@ -1,0 +1,443 @@
+// kg_regex_alt.hip — krep -E for an ALTERNATION of fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile_alt):
+// ERROR|WARN|FATAL, cat|d[oi]g|b.rd, every -E run with several -e.  The multi-branch shift-and scan kernel and its driver
+// kg::scan_regex_alt; kg_regex.hip keeps the single sequence and hands over when the plan's program is an alternation.
+//
+// The kernel.  Branch i lives in bits [o_i, o_i + L_i) of a 32-bit state; T[byte] has bit o_i + j set when byte is in C[i][j]
+// (in LDS once per bank, as in kg_regex.hip: 32 KiB, five workgroups per CU); INIT holds every o_i, FIN every o_i + L_i - 1, and
+// one step is S = ((S << 1) | INIT) & T[b].  The bit a branch shifts out of its top lands on the next branch's INIT bit (set
+// anyway) or on a bit T never holds, so the branches do not disturb each other.
+// A lane takes 16 bytes.  (1) It walks its last Lmax - 1 bytes from the all-ones state: with every L_i <= 16 the state behind them
+// is exact in every bit a later step can use, and one cross-lane move hands it to the next lane as that lane's TRUE entry state
+// (lane 0: the exit of lane 63 of the cell before, kept in a scalar; the first cell of a unit: the 16 bytes in front of it).
+// (2) It walks its 16 bytes from the true entry state and keeps the 16-bit mask of the bytes behind which any FIN bit is set.
+// Bytes at or behind text_len are masked out of it before anything else: guarded loads read 0 there and a class may hold NUL.
+// (3) A wave without a hit is done with the cell; in the others the lanes that hold hits walk again and read off, byte by byte,
+// which branches end there: the branch of FIN bit f begins at the highest INIT bit at or below f, which gives its length.
+// A hit of length L behind byte e is the occurrence (e - L + 1, e + 1), owned when its START lies in [own_lo, own_hi).
+//   count / records: one unit per (end, branch) pair, in end order and within an end in branch order.  When no two occurrences
+//     can share a byte (cross_overlap == 0) there is at most one pair per end, end order is start order and every occurrence is a
+//     match; a cell whose ends all lie in [own_lo + Lmax - 1, own_hi) owns whatever ends in it and is counted from the mask alone.
+//     The counting and the emitting launch count a lane with the same function (the two-pass offsets scheme of kg_post.hip).
+//   cross_overlap == 1 without -c: every pair goes to post.d_occ, the device sort orders them by start (it is stable and equal
+//     starts leave the kernel in end order, so the last record of a run of equal starts is the longest) and the greedy pass of
+//     kg_greedy.hip (kWalkAlt) takes the longest record of each visited start and consumes its length.  One window only.
+//   -c: every owned hit moves to the common coordinate start + Lmax - 1, that is up by Lmax - L < 16 places: the low 16 bits of
+//     the shifted mask stay in the lane, the spill goes to the next lane (lane 63's to a scalar for the next cell; a unit rebuilds
+//     it from the 16 bytes in front of it: an occurrence that spills out of them starts inside them).  From there on the newline
+//     mask shifted by Lmax - 1, the line-state arithmetic and the info words are those of kg_regex.hip's -c mode.
+// The anchor-byte fast path of kg_regex.hip is not taken: DESIGN §4.9 measured no gain from it on sparse text.
+// Reads: no byte outside [0, text_len) — whole 8-KiB rounds inside the text are vector loads, everything else is guarded per byte.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/krep_gpu.h"
+#include "kg_common.h"
+#include "kg_device.h"
+#include "kg_internal.h"
+#include "kg_plan.h"
+#include "kg_regex_dev.h"
+
+namespace kg {
+
+struct RaArgs
+{
+    const uint8_t *text;
+    u64 text_len;
+    u64 anchor;         // grid origin: a multiple of 16, <= own_lo
+    u64 own_lo, own_hi; // starts in [own_lo, own_hi) are owned (own_hi <= text_len); -c: so are the newlines of these bytes
+    u64 cov_hi;         // ends (-c: coordinates start + Lmax - 1) >= cov_hi hold nothing
+    u64 n_units;
+    u64 global_base;
+    u32 init, fin;
+    u32 geom;           // bits 0-7 Lmax; bit 8 cross_overlap
+    const u32 *table;
+    u64 *unitinfo;      // count mode: per-unit info words (nullptr: only the total is wanted)
+    const u64 *offsets; // emit mode: exclusive index of each unit's first record
+    u64 *positions;
+    u64 pos_cap;
+    Counters *ctr;
+};
+
+constexpr int kRaCount = 0, kRaEmit = 1, kRaLines = 2;
+
+static __device__ __forceinline__ u32 ra_byte(const uint4 &d, int i)
+{
+    const u32 w = (i >> 2) == 0 ? d.x : (i >> 2) == 1 ? d.y : (i >> 2) == 2 ? d.z : d.w;
+    return (w >> (8 * (i & 3))) & 0xffu;
+}
+// the state behind a lane's 16 bytes, exact in bits 0 .. Lmax - 2 of every branch: bytes `first` = 17 - Lmax .. 15 from all-ones
+static __device__ __forceinline__ u32 ra_exit(const u32 *T, const uint4 &d, u32 init, u32 first)
+{
+    u32 S = 0xffffffffu;
+#pragma unroll
+    for (int i = 1; i < 16; ++i)
+        if ((u32)i >= first)
+            S = ((S << 1) | init) & T[ra_byte(d, i) << 5];
+    return S;
+}
+// the walk from the true entry state E: bit k of the result = some branch ends behind byte k
+static __device__ __forceinline__ u32 ra_walk(const u32 *T, const uint4 &d, u32 init, u32 fin, u32 E)
+{
+    u32 S = E, H = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+    {
+        S = ((S << 1) | init) & T[ra_byte(d, i) << 5];
+        H |= ((S & fin) != 0u ? 1u : 0u) << i;
+    }
+    return H;
+}
+// the same walk again for a lane that holds hits: f(k, L) for every branch that ends behind a byte k of H, L its length
+template <class F> static __device__ __forceinline__ void ra_hits(const u32 *T, const uint4 &d, u32 init, u32 fin, u32 E, u32 H, F &&f)
+{
+    u32 S = E;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+    {
+        if ((H >> i) == 0u)
+            break;
+        S = ((S << 1) | init) & T[ra_byte(d, i) << 5];
+        if ((H >> i) & 1u)
+        {
+            u32 fm = S & fin;
+            while (fm)
+            {
+                const u32 fb = (u32)__builtin_ctz(fm);
+                fm &= fm - 1u;
+                const u32 o = 31u - (u32)__clz((int)(init & ((2u << fb) - 1u))); // the branch's lowest bit
+                f((u32)i, fb - o + 1u);
+            }
+        }
+    }
+}
+// the (end, branch) pairs of a lane whose occurrence starts in [own_lo, own_hi): the unit both launches count
+static __device__ __forceinline__ u32 ra_count_lane(const u32 *T, const uint4 &d, const RaArgs &a, u32 E, u32 H, u64 q, bool all_owned)
+{
+    if (all_owned)
+        return (u32)__popc(H); // (no two occurrences share a byte: one pair per end)
+    u32 c = 0;
+    if (H)
+        ra_hits(T, d, a.init, a.fin, E, H, [&](u32 k, u32 L) {
+            const u64 s = q + k + 1u - L;
+            c += (s >= a.own_lo && s < a.own_hi) ? 1u : 0u;
+        });
+    return c;
+}
+// -c: the owned hits of a lane at coordinate start + Lmax - 1, relative to q (bits 16..30: the spill into the next lane)
+static __device__ __forceinline__ u32 ra_starts(const u32 *T, const uint4 &d, const RaArgs &a, u32 E, u32 H, u64 q, u32 Lmax)
+{
+    u32 M = 0;
+    if (H)
+        ra_hits(T, d, a.init, a.fin, E, H, [&](u32 k, u32 L) {
+            const u64 s = q + k + 1u - L;
+            if (s >= a.own_lo && s < a.own_hi)
+                M |= 1u << (k + Lmax - L);
+        });
+    return M;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
+{
+    constexpr bool LINES = MODE == kRaLines, EMIT = MODE == kRaEmit;
+    __shared__ u32 s_T[256 * 32];
+    for (u32 i = threadIdx.x; i < 256u * 32u; i += kBlock)
+        s_T[i] = a.table[i >> 5];
+    __syncthreads();
+    const u32 lane = lane_id(), wave = threadIdx.x >> 6;
+    const u32 *T = s_T + (lane & 31u);
+    const u32 Lmax = a.geom & 0xffu, sh = Lmax - 1u, first = 17u - Lmax;
+    const bool cross = ((a.geom >> 8) & 1u) != 0u;
+    const u64 in_lo = a.own_lo + sh; // a cell of ends in [in_lo, own_hi) owns every occurrence that ends in it
+    const u64 n_waves = (u64)gridDim.x * kWavesPerBlk;
+    u64 acc_total = 0;
+
+    for (u64 unit = (u64)blockIdx.x * kWavesPerBlk + wave; unit < a.n_units; unit += n_waves)
+    {
+        const u64 ubase = a.anchor + unit * kRxUnitBytes;
+        // the 16 bytes in front of the unit give lane 0 its entry state and, for -c, the spill and the newlines that shift into the unit
+        u32 x63 = 0; // exit state of the 16 bytes in front of the next cell (uniform)
+        u32 y63 = 0; // -c: their spill | their raw newline mask << 16 (uniform)
+        if (ubase != 0)
+        {
+            const u64 pq = ubase - 16u;
+            const uint4 p = rx_load_guarded(a.text, a.text_len, pq);
+            x63 = __builtin_amdgcn_readfirstlane(ra_exit(T, p, a.init, first));
+            if (LINES)
+            {
+                // (an occurrence whose coordinate start + Lmax - 1 lies in the unit and whose end does not starts inside these 16 bytes:
+                //  the entry state of the walk does not reach it)
+                const u32 Hp = ra_walk(T, p, a.init, a.fin, 0u) & rx_range(pq, 0, a.text_len);
+                const u32 M = ra_starts(T, p, a, 0u, Hp, pq, Lmax);
+                y63 = __builtin_amdgcn_readfirstlane((M >> 16) | ((rx_newlines(p) & rx_range(pq, a.own_lo, a.own_hi)) << 16));
+            }
+        }
+        u32 l_hits = 0;                           // per lane
+        u64 out_idx = EMIT ? a.offsets[unit] : 0; // uniform
+        // -c: the line state of the unit, as kg_regex.hip keeps it (carry arithmetic over the 64 lanes of a cell)
+        u32 l_cnt = 0, s_new = 0;
+        bool s_open = false, s_seen = false, s_head = false;
+        auto line_cell = [&](u64 B_nl, u64 B_any, u64 B_head, u64 B_tail) __attribute__((always_inline)) {
+            const u64 G = B_tail, P = ~(B_nl | B_any);
+            const unsigned __int128 sum = (unsigned __int128)(G | P) + G + (s_open ? 1u : 0u);
+            const u64 O = (u64)sum ^ P; // bit l: the line entering lane l already holds a match
+            s_new += (u32)__popcll(B_head & ~O);
+            if (!s_seen && B_nl)
+            {
+                const int f = __builtin_ctzll(B_nl);
+                s_head = (((O | B_head) >> f) & 1ull) != 0ull;
+                s_seen = true;
+            }
+            s_open = (u64)(sum >> 64) != 0ull;
+        };
+
+        for (int r = 0; r < kRoundsBig; ++r)
+        {
+            const u64 seg = ubase + (u64)r * kSegBytes;
+            if (seg >= a.cov_hi)
+                break;
+            const bool fast = seg + kSegBytes <= a.text_len;
+            uint4 d[kCells];
+            if (fast)
+            {
+                const uint4 *src = reinterpret_cast<const uint4 *>(a.text + seg) + lane;
+#pragma unroll
+                for (int j = 0; j < kCells; ++j)
+                {
+                    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+                    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + j * kWave));
+                    d[j] = make_uint4(v.x, v.y, v.z, v.w);
+                }
+            }
+            else
+            {
+#pragma unroll
+                for (int j = 0; j < kCells; ++j)
+                {
+                    const u64 cb = seg + (u64)j * kCellBytes;
+                    d[j] = cb < a.cov_hi ? rx_load_guarded(a.text, a.text_len, cb + (u64)lane * 16u) : make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kCells; ++j)
+            {
+                const u64 cbase = seg + (u64)j * kCellBytes;
+                if (cbase >= a.cov_hi)
+                    break;
+                const u64 q = cbase + (u64)lane * 16u;
+                const u32 X = ra_exit(T, d[j], a.init, first);
+                u32 E = __shfl_up(X, 1);
+                if (lane == 0)
+                    E = x63;
+                x63 = __builtin_amdgcn_readlane(X, 63);
+                u32 H = ra_walk(T, d[j], a.init, a.fin, E);
+                if (!fast)
+                    H &= rx_range(q, 0, a.text_len); // an end is a byte of the text
+                if (LINES)
+                {
+                    const u32 M = ra_starts(T, d[j], a, E, H, q, Lmax);
+                    const u32 mine = (M >> 16) | ((rx_newlines(d[j]) & rx_range(q, a.own_lo, a.own_hi)) << 16);
+                    u32 prev = __shfl_up(mine, 1);
+                    if (lane == 0)
+                        prev = y63;
+                    y63 = __builtin_amdgcn_readlane(mine, 63);
+                    const u32 Hc = (M | prev) & 0xffffu; // the owned starts at coordinates q .. q + 15
+                    l_hits += (u32)__popc(Hc);
+                    const u32 N = (((mine >> 16) << sh) | ((prev >> 16) >> (16u - sh))) & 0xffffu, Hs = Hc | N;
+                    l_cnt += (u32)__popc(Hc & ~(Hs - ((N << 1) & 0xffffu)));
+                    // head: the lowest flag is a match (one ON a newline belongs to the line it ends); tail: a match behind the last newline
+                    line_cell(__ballot(N != 0u), __ballot(Hc != 0u), __ballot((Hc & (Hs ^ (Hs - 1u))) != 0u),
+                              __ballot((Hc >> (32 - __clz((int)N))) != 0u));
+                }
+                else if (__ballot(H != 0u))
+                {
+                    const bool all_owned = !cross && cbase >= in_lo && cbase + kCellBytes <= a.own_hi;
+                    const u32 c = ra_count_lane(T, d[j], a, E, H, q, all_owned);
+                    l_hits += c;
+                    if (EMIT)
+                    {
+                        u32 incl = c;
+#pragma unroll
+                        for (int o = 1; o < 64; o <<= 1)
+                        {
+                            const u32 t = __shfl_up(incl, o);
+                            if (lane >= (u32)o)
+                                incl += t;
+                        }
+                        if (c)
+                        {
+                            u64 idx = out_idx + (incl - c);
+                            ra_hits(T, d[j], a.init, a.fin, E, H, [&](u32 k, u32 L) {
+                                const u64 s = q + k + 1u - L;
+                                if (s >= a.own_lo && s < a.own_hi)
+                                {
+                                    if (idx < a.pos_cap)
+                                    {
+                                        const u64 s0 = s + a.global_base, e0 = s0 + L;
+                                        *reinterpret_cast<uint4 *>(a.positions + 2 * idx) = make_uint4((u32)s0, (u32)(s0 >> 32), (u32)e0, (u32)(e0 >> 32));
+                                    }
+                                    ++idx;
+                                }
+                            });
+                        }
+                        out_idx += (u32)__builtin_amdgcn_readlane(incl, 63);
+                    }
+                }
+            }
+        }
+        if (EMIT)
+            continue;
+        u32 h = l_hits, t = l_cnt;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1)
+        {
+            h += __shfl_xor(h, o);
+            if (LINES)
+                t += __shfl_xor(t, o);
+        }
+        acc_total += h;
+        if (a.unitinfo && lane == 0)
+        {
+            u64 info = (u64)h;
+            if (LINES)
+            {
+                const LineState ls{t + s_new, s_seen, s_seen ? s_head : s_open, s_open};
+                info |= line_bits(ls) | ((u64)(ls.cnt & kUiLineMask) << kUiLineShift);
+            }
+            else if (h)
+                info |= kLnHead | kLnTail;
+            a.unitinfo[unit] = info;
+        }
+    }
+    if (!EMIT && lane == 0 && acc_total)
+        atomicAdd(&a.ctr->total, acc_total);
+}
+
+template <int MODE> static hipError_t ra_launch(const RaArgs &a, int num_cu, hipStream_t st)
+{
+    const u64 blocks = (a.n_units + kWavesPerBlk - 1) / kWavesPerBlk;
+    // (32 KiB of LDS each would let five workgroups into a CU, but the kernel holds 112 to 125 VGPRs: four waves per SIMD, four workgroups)
+    u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 4));
+    if (const int force = g_rx_force_grid.load(); force > 0) // test hook: a starved grid (krep_gpu_debug_force_regex_grid)
+        grid = std::min<u32>(grid, (u32)force);
+    hipLaunchKernelGGL((regex_alt_scan<MODE>), dim3(grid), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ the scan of a window
+int scan_regex_alt(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
+                   krep_gpu_scan_out_t *out)
+{
+    const RegexProg &rx = *pl->rx;
+    const u32 Lmin = rx.alt.Lmin, Lmax = rx.alt.Lmax;
+    if (w.global_len < Lmin || w.text_len < Lmin || w.own_lo >= w.own_hi)
+        return 0; // (text_len == 0 included: no branch matches the empty string)
+    const size_t own_hi = std::min(w.own_hi, w.text_len);
+    const bool lines = pl->lines, greedy = rx.alt.cross_overlap && !lines;
+    const bool whole = w.global_base == 0 && w.own_lo == 0 && own_hi + Lmin > w.text_len && w.global_len == w.text_len;
+    if (greedy && !whole)
+        return fail("two occurrences of this regex alternation can overlap, its matches are the greedy selection over the whole occurrence "
+                    "list: scan the whole text in one window (krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
+    if (own_hi <= w.own_lo)
+        return 0;
+    const size_t maxc = pl->max_count;
+    const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(maxc, cap) : 0;
+
+    RaArgs a{};
+    a.text = w.d_text; a.text_len = w.text_len;
+    a.anchor = w.own_lo & ~(u64)15;
+    a.own_lo = w.own_lo; a.own_hi = own_hi;
+    a.cov_hi = lines ? (u64)own_hi + (Lmax - 1) : std::min<u64>((u64)own_hi + (Lmax - 1), w.text_len);
+    a.n_units = (a.cov_hi - a.anchor + kRxUnitBytes - 1) / kRxUnitBytes;
+    a.global_base = w.global_base;
+    a.init = rx.init; a.fin = rx.fin;
+    a.geom = Lmax | ((rx.alt.cross_overlap ? 1u : 0u) << 8);
+    a.table = rx.d_table;
+    a.ctr = pl->d_ctr;
+
+    HIPCHK(hipSetDevice(pl->device));
+    if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
+    const bool chain = lines || want || greedy;
+    PostScratch &post = pl->post;
+    if (chain)
+    {
+        if (post_reserve(post, a.n_units, 0))
+            return 2;
+        a.unitinfo = post.d_unitinfo;
+        a.offsets = (const u64 *)post.d_offsets;
+    }
+    HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
+    HIPCHK(lines ? ra_launch<kRaLines>(a, pl->num_cu, st) : ra_launch<kRaCount>(a, pl->num_cu, st));
+    if (chain && post_offsets_pass(post, a.n_units, lines, pl->d_ctr, st))
+        return 2;
+    uint64_t total = 0, nlines = 0;
+    unsigned long long summary = 0;
+    if (greedy)
+    {
+        // every (end, branch) pair into post.d_occ (sized once their number is known), ordered by start, then the greedy pass of
+        // kg_greedy.hip: the longest record of a visited start is the match, consume = its own length
+        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t n_occ = pl->h_ctr->total;
+        HIPCHK(grow_scratch(post.occ_cap, n_occ, n_occ, {dev_buf(post.d_occ, n_occ * 2 * sizeof(uint64_t))}));
+        if (n_occ)
+        {
+            a.positions = (u64 *)post.d_occ;
+            a.pos_cap = n_occ;
+            HIPCHK(ra_launch<kRaEmit>(a, pl->num_cu, st));
+            if (order_records((match_position_t *)post.d_occ, n_occ, w.global_base + w.text_len + 1, st, false))
+                return 2;
+            HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
+            WalkSpec ws{};
+            ws.mode = kWalkAlt;
+            ws.m = Lmax;
+            if (const int rc = post_walk(post, w.d_text, w.text_len, w.global_base, ws, n_occ, (uint64_t *)d_pos, want, pl->d_ctr, pl->h_ctr,
+                                         st, &total, &nlines, nullptr))
+                return rc;
+        }
+        summary = total ? (kLnHead | kLnTail) : 0;
+    }
+    else
+    {
+        if (want)
+        {
+            a.positions = (u64 *)d_pos;
+            a.pos_cap = want;
+            HIPCHK(ra_launch<kRaEmit>(a, pl->num_cu, st));
+        }
+        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        total = pl->h_ctr->total;
+        nlines = pl->h_ctr->lines;
+        summary = lines ? pl->h_ctr->summary : (total ? (kLnHead | kLnTail) : 0);
+    }
+    if (time_it && stop_clock(pl, true, st, out))
+        return 2;
+    out->total_matches = total;
+    out->line_count = nlines;
+    out->has_newline = (summary & kLnNl) != 0;
+    out->head_line_hit = (summary & kLnHead) != 0;
+    out->tail_line_hit = (summary & kLnTail) != 0;
+    // regex_search's return value (krep.c:1395, :1533): max_count == 0 answers 0 with -c or positions, else 1 on the first occurrence
+    uint64_t store = 0;
+    if (maxc == 0)
+        out->count = (lines || pl->track) ? 0 : (total ? 1 : 0);
+    else if (lines)
+        out->count = std::min<uint64_t>(nlines, maxc);
+    else
+    {
+        out->count = std::min<uint64_t>(total, maxc);
+        store = (pl->track && d_pos) ? out->count : 0;
+    }
+    if (d_pos && cap && pl->track && !lines)
+    {
+        out->overflow = store > cap;
+        out->stored = std::min<uint64_t>(store, std::min<uint64_t>(total, want));
+    }
+    return 0;
+}
+} // namespace kg

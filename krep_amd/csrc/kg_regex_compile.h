@@ -2,6 +2,8 @@
 // extended regular expression into a fixed number of one-byte atoms, and libc's own regcomp / regexec asked about every atom
 // and every byte.  Host code without any HIP in it, so that a stand-alone program can run it under the sanitizers
 // (tools/regex_compile_san.cpp).  It never sees a text: what it produces is a table, the search is the kernel's (kg_regex.hip).
+// krep_gpu_regex_compile_alt (at the end of this file) cuts an alternation at its top-level '|', takes one pair of parentheses
+// off a branch and hands every branch to the same tokeniser (kg_regex_alt.hip scans what it makes).
 #pragma once
 #include <regex.h>
 #include <stdint.h>
@@ -254,6 +256,213 @@ inline const char *regex_compile_anchored(const search_params_t *p, krep_gpu_reg
         return "NULL params";
     out->bol = out->eol = 0;
     return regex_compile_seq(p, true, &out->seq, &out->bol, &out->eol);
+}
+
+// ---- krep_gpu_regex_compile_alt: an alternation of class sequences ------------------------------------------------------------
+constexpr uint32_t kRegexMaxBranches = 8, kRegexMaxTotalL = 32;
+
+// the patterns a search names: patterns[0..num_patterns) when the arrays are there, else pattern alone
+inline size_t regex_pattern_count(const search_params_t *p) { return (p->num_patterns >= 1 && p->patterns && p->pattern_lens) ? p->num_patterns : 1; }
+inline void regex_pattern_at(const search_params_t *p, size_t k, const uint8_t **pat, size_t *n)
+{
+    if (p->num_patterns >= 1 && p->patterns && p->pattern_lens)
+    {
+        *pat = (const uint8_t *)p->patterns[k];
+        *n = p->pattern_lens[k];
+    }
+    else
+    {
+        *pat = (const uint8_t *)p->pattern;
+        *n = p->pattern_len;
+    }
+}
+// does the search say an alternation: several patterns, or a '|' or '(' outside brackets and not behind a backslash
+inline bool regex_has_alt_syntax(const search_params_t *p)
+{
+    if (!p || !p->use_regex)
+        return false;
+    if (p->num_patterns > 1)
+        return true;
+    const uint8_t *pat;
+    size_t n;
+    regex_pattern_at(p, 0, &pat, &n);
+    if (!pat)
+        return false;
+    for (size_t i = 0; i < n;)
+    {
+        if (pat[i] == '\\')
+            i += 2;
+        else if (pat[i] == '[')
+            i = regex_bracket_end(pat, n, i) + 1;
+        else if (pat[i] == '|' || pat[i] == '(')
+            return true;
+        else
+            ++i;
+    }
+    return false;
+}
+inline bool regex_classes_meet(const uint8_t a[32], const uint8_t b[32])
+{
+    for (int w = 0; w < 32; ++w)
+        if (a[w] & b[w])
+            return true;
+    return false;
+}
+// can an occurrence of branch j start d bytes into an occurrence of branch i (every class pair that lies on one byte meets)
+inline bool regex_branches_overlap(const krep_gpu_regex_info_t &bi, const krep_gpu_regex_info_t &bj, uint32_t d)
+{
+    for (uint32_t t = 0; d + t < bi.L && t < bj.L; ++t)
+        if (!regex_classes_meet(bi.classes[d + t], bj.classes[t]))
+            return false;
+    return true;
+}
+inline const char *regex_compile_alt_branches(const search_params_t *p, krep_gpu_regex_alt_t *out)
+{
+    if (!p->use_regex)
+        return "not a regex search (use_regex is not set)";
+    if (p->whole_word)
+        return "regex with -w: the CLI compiles \\bPATTERN\\b, a library caller PATTERN, and the operator sees neither compiled "
+               "expression: kept on krep's regex_search";
+    if (MB_CUR_MAX > 1)
+        return "regex in a multibyte locale (the process called setlocale): libc matches characters there, not bytes: kept on "
+               "krep's regex_search (krep itself runs in the C locale)";
+    if (p->num_patterns > 1 && !(p->patterns && p->pattern_lens))
+        return "several patterns announced but patterns / pattern_lens are NULL";
+    const size_t n_pat = regex_pattern_count(p);
+    for (size_t k = 0; k < n_pat; ++k)
+    {
+        const uint8_t *pat;
+        size_t n;
+        regex_pattern_at(p, k, &pat, &n);
+        if (!pat)
+            return "no pattern";
+        if (n == 0)
+            return "an empty regex matches the empty string: kept on krep's regex_search";
+        if (n > 1024)
+            return "regex pattern longer than 1024 bytes";
+        for (size_t i = 0; i < n; ++i)
+            if (pat[i] < 0x01 || pat[i] > 0x7f)
+                return "regex pattern holds a byte outside 0x01-0x7F";
+        // cut the pattern at its top-level '|'; a branch is bytes [lo, hi) of it, the parentheses around it taken off
+        size_t bs = 0;            // where the branch under the cursor begins
+        size_t inner = 0;         // ... and where its sequence begins (behind a '(')
+        bool open = false, closed = false; // inside the branch's group | its ')' is behind the cursor
+        for (size_t i = 0; i <= n;)
+        {
+            const uint8_t c = i < n ? pat[i] : (uint8_t)'|'; // the end of the pattern ends a branch like a '|'
+            if (c == '\\' && i < n)
+            {
+                if (closed)
+                    return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general "
+                           "automaton: kept on krep's regex_search";
+                if (i + 1 >= n)
+                    return "regex: trailing backslash";
+                i += 2;
+                continue;
+            }
+            if (c == '[' && i < n)
+            {
+                if (closed)
+                    return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general "
+                           "automaton: kept on krep's regex_search";
+                const size_t e = regex_bracket_end(pat, n, i);
+                if (e >= n)
+                    return "regex: bracket expression without its ']'";
+                i = e + 1;
+                continue;
+            }
+            if (c == '(')
+            {
+                if (open)
+                    return "regex alternation: nested parentheses: kept on krep's regex_search";
+                if (i != bs || closed)
+                    return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general "
+                           "automaton: kept on krep's regex_search";
+                open = true;
+                inner = i + 1;
+                ++i;
+                continue;
+            }
+            if (c == ')')
+            {
+                if (!open)
+                    return "regex alternation: unbalanced parentheses: kept on krep's regex_search";
+                open = false;
+                closed = true;
+                if (i == inner)
+                    return "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
+                ++i;
+                continue;
+            }
+            if (c == '|')
+            {
+                if (open)
+                    return i < n ? "regex alternation: a group that holds an alternation ((a|b)) is not one class sequence: kept on "
+                                   "krep's regex_search"
+                                 : "regex alternation: unbalanced parentheses: kept on krep's regex_search";
+                const size_t lo = closed ? inner : bs, hi = closed ? i - 1 : i;
+                if (hi <= lo)
+                    return "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
+                search_params_t q = *p;
+                q.pattern = (const char *)pat + lo;
+                q.pattern_len = hi - lo;
+                q.patterns = nullptr;
+                q.pattern_lens = nullptr;
+                q.num_patterns = 0;
+                krep_gpu_regex_info_t info;
+                int bol, eol;
+                if (const char *why = regex_compile_seq(&q, false, &info, &bol, &eol))
+                {
+                    return strstr(why, "more than 16") ? "regex alternation: a branch of more than 16 byte classes: kept on krep's regex_search" : why;
+                }
+                bool dup = false;
+                for (uint32_t b = 0; b < out->n_branches && !dup; ++b)
+                    dup = out->branch[b].L == info.L && memcmp(out->branch[b].classes, info.classes, (size_t)info.L * 32) == 0;
+                if (!dup)
+                {
+                    if (out->n_branches >= kRegexMaxBranches)
+                        return "regex alternation: more than 8 branches: kept on krep's regex_search";
+                    out->branch[out->n_branches++] = info;
+                }
+                bs = i + 1;
+                closed = false;
+                ++i;
+                continue;
+            }
+            if (closed)
+                return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general automaton: "
+                       "kept on krep's regex_search";
+            if (c == '^' || c == '$')
+                return "regex alternation: ^ or $ in a branch (anchors inside an alternation): kept on krep's regex_search";
+            ++i;
+        }
+    }
+    out->Lmin = kRegexMaxL;
+    for (uint32_t b = 0; b < out->n_branches; ++b)
+    {
+        const uint32_t L = out->branch[b].L;
+        out->Lmin = L < out->Lmin ? L : out->Lmin;
+        out->Lmax = L > out->Lmax ? L : out->Lmax;
+        out->total_L += L;
+    }
+    if (out->total_L > kRegexMaxTotalL)
+        return "regex alternation: more than 32 byte classes in all branches together: kept on krep's regex_search";
+    for (uint32_t i = 0; i < out->n_branches && !out->cross_overlap; ++i)
+        for (uint32_t j = 0; j < out->n_branches && !out->cross_overlap; ++j)
+            for (uint32_t d = i == j ? 1u : 0u; d < out->branch[i].L && !out->cross_overlap; ++d)
+                out->cross_overlap = regex_branches_overlap(out->branch[i], out->branch[j], d) ? 1 : 0;
+    return nullptr;
+}
+// krep_gpu_regex_compile_alt: NULL and *out filled, or the refusal and *out zeroed
+inline const char *regex_compile_alt(const search_params_t *p, krep_gpu_regex_alt_t *out)
+{
+    if (!p || !out)
+        return "NULL params";
+    memset(out, 0, sizeof *out);
+    const char *why = regex_compile_alt_branches(p, out);
+    if (why)
+        memset(out, 0, sizeof *out);
+    return why;
 }
 
 } // namespace kg

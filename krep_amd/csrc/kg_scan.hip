@@ -637,11 +637,12 @@ int split_mode(const search_params_t *p, const krep_gpu_config_t &c, size_t text
     if (!p || (!p->use_regex && p->num_patterns == 0))
         return kSplitWhole;
     if (p->use_regex)
-    { // a pattern that can overlap itself goes through the greedy pass over the whole occurrence list; -c never does (kg_regex.hip)
-        krep_gpu_regex_anchored_t info;
-        if (regex_compile_cached(p, &info))
+    { // a pattern that can overlap itself (an alternation: two occurrences that can share a byte) goes through the greedy pass over
+      // the whole occurrence list; -c never does (kg_regex.hip, kg_regex_alt.hip)
+        RegexCompiled rc;
+        if (regex_compile_cached(p, &rc))
             return kSplitWhole;
-        return info.seq.self_overlap && !p->count_lines_mode ? kSplitWhole : kSplitPieces;
+        return (rc.is_alt ? rc.alt.cross_overlap : rc.seq.seq.self_overlap) && !p->count_lines_mode ? kSplitWhole : kSplitPieces;
     }
     if (p->num_patterns > 1)
     {

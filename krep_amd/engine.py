@@ -51,6 +51,9 @@ class Engine:
         if hasattr(L, "krep_gpu_regex_compile_anchored"):  # (an older build loaded as an A/B partner lacks it: tools/ab_bench.py)
             L.krep_gpu_regex_compile_anchored.restype = C.c_int
             L.krep_gpu_regex_compile_anchored.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexAnchored)]
+        if hasattr(L, "krep_gpu_regex_compile_alt"):  # (likewise)
+            L.krep_gpu_regex_compile_alt.restype = C.c_int
+            L.krep_gpu_regex_compile_alt.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexAlt)]
         L.krep_gpu_can_accelerate.restype = C.c_int
         L.krep_gpu_can_accelerate.argtypes = [C.POINTER(abi.SearchParams)]
         L.krep_gpu_config_default.restype = None
@@ -300,6 +303,15 @@ class Engine:
         real classes).  This is the compiler every search goes through; regex_compile() keeps refusing both anchors."""
         info = abi.RegexAnchored()
         if self.lib.krep_gpu_regex_compile_anchored(params.ref, C.byref(info)):
+            raise KrepGpuError(self.last_error())
+        return info
+
+    def regex_compile_alt(self, params: abi.Params) -> "abi.RegexAlt":
+        """krep_gpu_regex_compile_alt: an alternation of class sequences (a|b, (a)|(b), several patterns): its merged branches, each
+        what regex_compile() makes of the branch alone, and cross_overlap.  Every search asks regex_compile_anchored() first and this
+        compiler only for what that one refuses."""
+        info = abi.RegexAlt()
+        if self.lib.krep_gpu_regex_compile_alt(params.ref, C.byref(info)):
             raise KrepGpuError(self.last_error())
         return info
 

@@ -1,4 +1,4 @@
-"""krep -E on the device (kg_regex.hip) beside the literal scan and beside the reference's regex_search on the CPU.
+"""krep -E on the device (kg_regex.hip, kg_regex_alt.hip) beside the literal scan and beside the reference's regex_search on the CPU.
 One kind-2 haystack with `Sherlock` planted every 10 000 bytes, resident in HBM; hipEvent times, the median of 10 steady scans
 after 2 warm-up scans.  The yardstick comes first: the literal plan for `Sherlock` on the same buffer.  Then the regex patterns,
 each with its ratio to the yardstick; and regex_search itself (oracle/_ref, one thread) on the first 256 MiB of the host twin.
@@ -53,7 +53,7 @@ plan = e.plan(abi.Params([b"Sherlock"]))
 for mode, want_pos in (("count", False), ("records", True)):
     ms, out = median_ms(plan, want_pos)
     yard[mode] = ms
-    say(f"literal  {'Sherlock':<16} {mode:<8} {ms:8.3f} ms {n / ms / 1e6:7.0f} GB/s  ratio 1.00  matches {out.total_matches}")
+    say(f"literal  {'Sherlock':<22} {mode:<8} {ms:8.3f} ms {n / ms / 1e6:7.0f} GB/s  ratio 1.00  matches {out.total_matches}")
 plan.close()
 literal_matches = out.total_matches
 
@@ -62,8 +62,12 @@ JOBS = [(b"Sherl[oO]ck", "anchor path", ("count", "records")), (b"[A-Z][a-z]{7}"
         # line anchors: each row beside its unanchored twin above (few lines of the haystack start with the planted word, most end
         # behind a run of lower-case letters)
         (b"^Sherlock", "anchor path, ^", ("count", "records")), (b"[a-z]{4}$", "dense, $", ("count", "-c")),
-        (b"^[A-Z][a-z]{7}$", "table path, ^ and $", ("count", "records"))]
-TWIN = {b"^Sherlock": b"Sherlock", b"[a-z]{4}$": b"[a-z]{4}", b"^[A-Z][a-z]{7}$": b"[A-Z][a-z]{7}"}
+        (b"^[A-Z][a-z]{7}$", "table path, ^ and $", ("count", "records")),
+        # alternations (kg_regex_alt.hip): each row beside the table-path row of [A-Z][a-z]{7} on the same buffer (-c beside its count row)
+        (b"Sherlock|Watson|Holmes", "alternation, 3 branches", ("count", "records", "-c")),
+        (b"[A-Z][a-z]{7}|[0-9]{4}", "alternation, [0-9]{4} overlaps itself: greedy pass", ("count", "records", "-c"))]
+TWIN = {b"^Sherlock": b"Sherlock", b"[a-z]{4}$": b"[a-z]{4}", b"^[A-Z][a-z]{7}$": b"[A-Z][a-z]{7}",
+        b"Sherlock|Watson|Holmes": b"[A-Z][a-z]{7}", b"[A-Z][a-z]{7}|[0-9]{4}": b"[A-Z][a-z]{7}"}
 took = {}
 for pat, what, modes in JOBS:
     for mode in modes:
@@ -73,8 +77,9 @@ for pat, what, modes in JOBS:
         plan.close()
         ref_ms = yard["records" if mode == "records" else "count"]
         took[pat, mode] = ms
-        twin = f"; {ms / took[TWIN[pat], mode]:4.2f} x the time of {TWIN[pat].decode()}" if pat in TWIN else ""
-        say(f"regex    {pat.decode():<16} {mode:<8} {ms:8.3f} ms {n / ms / 1e6:7.0f} GB/s  ratio {ref_ms / ms:4.2f}  "
+        twin_mode = mode if pat not in TWIN or (TWIN[pat], mode) in took else "count"
+        twin = f"; {ms / took[TWIN[pat], twin_mode]:4.2f} x the time of {TWIN[pat].decode()}" if pat in TWIN else ""
+        say(f"regex    {pat.decode():<22} {mode:<8} {ms:8.3f} ms {n / ms / 1e6:7.0f} GB/s  ratio {ref_ms / ms:4.2f}  "
             f"{'lines' if mode == '-c' else 'matches'} {out.count}  ({what}{twin})")
         if pat in (b"Sherl[oO]ck", b"Sherlock") and mode != "-c":
             assert out.total_matches == literal_matches, (pat, out.total_matches, literal_matches)
@@ -91,7 +96,7 @@ if regex_ref.available():
             t0 = time.perf_counter()
             ret, _ = regex_ref.call(pat, host, want_result=False, **kw)
             dt = time.perf_counter() - t0
-            say(f"cpu      {pat.decode():<16} {mode:<8} {dt * 1e3:8.0f} ms {m / dt / 1e9:7.3f} GB/s  returned {ret}")
+            say(f"cpu      {pat.decode():<22} {mode:<8} {dt * 1e3:8.0f} ms {m / dt / 1e9:7.3f} GB/s  returned {ret}")
 else:
     say("# no compiled reference (oracle/_ref) on this host: the CPU rows are missing")
 with open(out_path, "w") as f:

@@ -1,8 +1,8 @@
 // tools/regex_compile_san.cpp — the -E pattern compiler (krep_amd/csrc/kg_regex_compile.h: host code, no HIP) as a stand-alone
 // program for AddressSanitizer / UBSan:  python tools/sanitize.py regex   (or by hand:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer tools/regex_compile_san.cpp -o regex_compile_san).
-// It feeds both entry points' compilers accepted patterns, every refusal, and 200 000 pattern strings drawn from the bytes the
-// grammar cares about (^ and $ among them), each copied into a heap block of exactly its length so that a read past the pattern is a report.
+// It feeds the three entry points' compilers (the alternation compiler with one and with two patterns) accepted patterns, every refusal, and 200 000 pattern strings drawn from the bytes the
+// grammar cares about (^ $ | ( ) among them), each copied into a heap block of exactly its length so that a read past the pattern is a report.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +32,53 @@ static int compile(const std::string &pat, bool cs, bool ww, krep_gpu_regex_info
     *why = anchored ? kg::regex_compile_anchored(&p, anchored) : kg::regex_compile(&p, info);
     free(heap);
     return *why ? 2 : 0;
+}
+
+// krep_gpu_regex_compile_alt's compiler over one or several patterns, each in a heap block of exactly its length
+static int compile_alt(const std::vector<std::string> &pats, bool cs, bool ww, krep_gpu_regex_alt_t *alt, const char **why)
+{
+    std::vector<char *> heap;
+    std::vector<const char *> ptrs;
+    std::vector<size_t> lens;
+    for (const std::string &s : pats)
+    {
+        heap.push_back((char *)malloc(s.size() ? s.size() : 1));
+        memcpy(heap.back(), s.data(), s.size());
+        ptrs.push_back(heap.back());
+        lens.push_back(s.size());
+    }
+    search_params_t p;
+    memset(&p, 0, sizeof p);
+    p.pattern = ptrs[0];
+    p.pattern_len = lens[0];
+    p.patterns = ptrs.data();
+    p.pattern_lens = lens.data();
+    p.num_patterns = pats.size();
+    p.case_sensitive = cs;
+    p.use_regex = true;
+    p.whole_word = ww;
+    p.max_count = SIZE_MAX;
+    *why = kg::regex_compile_alt(&p, alt);
+    (void)kg::regex_has_alt_syntax(&p);
+    for (char *h : heap)
+        free(h);
+    return *why ? 2 : 0;
+}
+static bool alt_consistent(const krep_gpu_regex_alt_t &a)
+{
+    if (a.n_branches < 1 || a.n_branches > 8 || a.Lmin < 1 || a.Lmin > a.Lmax || a.Lmax > 16 || a.total_L > 32 || a.reserved)
+        return false;
+    unsigned tot = 0;
+    for (unsigned i = 0; i < a.n_branches; ++i)
+    {
+        const unsigned L = a.branch[i].L;
+        if (L < a.Lmin || L > a.Lmax || a.branch[i].anchor >= L || a.branch[i].n_anchor > 4)
+            return false;
+        if (a.branch[i].self_overlap && !a.cross_overlap)
+            return false;
+        tot += L;
+    }
+    return tot == a.total_L;
 }
 
 int main()
@@ -95,10 +142,40 @@ int main()
         printf("FAIL: anchored -w accepted\n");
         ++bad;
     }
+    // the alternation compiler: accepted shapes with their fields, every refusal, several patterns
+    krep_gpu_regex_alt_t alt;
+    struct { std::vector<std::string> pats; unsigned nb, Lmin, Lmax, total; int overlap; } alt_ok[] = {
+        {{"cat|d[oi]g|b.rd"}, 3, 3, 4, 10, 1}, {{"(ERROR)|(WARN[0-9])"}, 2, 5, 5, 10, 0}, {{"ERROR", "WARN[0-9]"}, 2, 5, 5, 10, 0},
+        {{"(a)|(b)|(a)"}, 2, 1, 1, 2, 0}, {{"a{16}|b{16}"}, 2, 16, 16, 32, 1}, {{"ab|abc"}, 2, 2, 3, 5, 1}, {{"ab|cd"}, 2, 2, 2, 4, 0},
+        {{"a|aa"}, 2, 1, 2, 3, 1}, {{"(Sherl[oO]ck)"}, 1, 8, 8, 8, 0}, {{"a[|]b|c\\|d|[(]x[)]"}, 3, 3, 3, 9, 0}, {{"x|[a-c]{16}"}, 2, 1, 16, 17, 1},
+        {{"a|b|c|d|e|f|g|h|a"}, 8, 1, 1, 8, 0}, {{"ERROR|FATAL", "(WARN[0-9])"}, 3, 5, 5, 15, 0}};
+    for (const auto &c : alt_ok)
+        for (int cs = 0; cs < 2; ++cs)
+            if (compile_alt(c.pats, cs != 0, false, &alt, &why) != 0 || alt.n_branches != c.nb || alt.Lmin != c.Lmin || alt.Lmax != c.Lmax ||
+                alt.total_L != c.total || alt.cross_overlap != c.overlap || !alt_consistent(alt))
+            {
+                printf("FAIL: alt %s: %s\n", c.pats[0].c_str(), why ? why : "wrong fields");
+                ++bad;
+            }
+    const char *alt_no[] = {"a|", "|a", "()", "a||b", "a|()", "((a))", "(a(b))", "(a", "a)", "a|(b", "x(a|b)y", "(ab)c", "(ab){2}", "(a)(b)", "(a|b)",
+                            "^a|b", "a|b$", "(^a)|b", "a|^|b", "a|b|c|d|e|f|g|h|i", "a{17}|b", "a{16}|b{16}|c", "a|b.*", "a+|b", "a|b?", "a{2,3}|b",
+                            "a|\\bw", "a|caf\xe9", "a|[bc", "a|b\\", "a|b{0}", "a|{2}", "", "|", "(", ")", "a|[", "a|(", "a|\\", "(a)|", "[(]|("};
+    for (const char *s : alt_no)
+        if (compile_alt({s}, true, false, &alt, &why) != 2 || !why || !*why || alt.n_branches != 0)
+        {
+            printf("FAIL: alt %s accepted\n", s);
+            ++bad;
+        }
+    if (compile_alt({"a|b"}, true, true, &alt, &why) != 2 || compile_alt({"a", ""}, true, false, &alt, &why) != 2 ||
+        compile_alt({"a", "b*"}, true, false, &alt, &why) != 2 || compile_alt({std::string(1100, 'a') + "|b"}, true, false, &alt, &why) != 2)
+    {
+        printf("FAIL: alt -w, an empty pattern, a refused second pattern or an overlong pattern accepted\n");
+        ++bad;
+    }
     // pattern strings over the bytes the grammar looks at
     const char alphabet[] = "ab[]^-:.={},\\0129(|*\n x$";
     unsigned long long s = 88172645463325252ull;
-    unsigned taken = 0, refused = 0, ataken = 0;
+    unsigned taken = 0, refused = 0, ataken = 0, alt_taken = 0;
     for (int i = 0; i < 200000; ++i)
     {
         std::string pat;
@@ -138,7 +215,30 @@ int main()
             printf("FAIL: the anchored compiler refuses what the old one takes\n");
             ++bad;
         }
+        // the same string, cut in two at a drawn place every other time, through the alternation compiler: it takes whatever the old
+        // one takes as a single branch, and what it takes is consistent
+        std::vector<std::string> pats{pat};
+        if ((s >> 33) & 1)
+        {
+            const size_t cut = pat.empty() ? 0 : (size_t)((s >> 20) % (pat.size() + 1));
+            pats = {pat.substr(0, cut), pat.substr(cut)};
+        }
+        if (compile_alt(pats, (s >> 40) & 1, false, &alt, &why) == 0)
+        {
+            ++alt_taken;
+            if (!alt_consistent(alt) || (old_ok && pats.size() == 1 && (alt.n_branches != 1 || memcmp(&old, &alt.branch[0], sizeof old))))
+            {
+                printf("FAIL: inconsistent alternation info for a random pattern\n");
+                ++bad;
+            }
+        }
+        else if ((old_ok && pats.size() == 1) || alt.n_branches != 0)
+        {
+            printf("FAIL: the alternation compiler refuses a single sequence the old one takes, or leaves a refused struct filled\n");
+            ++bad;
+        }
     }
-    printf("regex_compile_san: %u random patterns taken, %u refused, %u taken with anchors allowed, %d failures\n", taken, refused, ataken, bad);
+    printf("regex_compile_san: %u random patterns taken, %u refused, %u taken with anchors allowed, %u taken as alternations, %d failures\n", taken,
+           refused, ataken, alt_taken, bad);
     return bad ? 1 : 0;
 }
