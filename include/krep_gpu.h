@@ -112,8 +112,8 @@ enum krep_ref_algo
     KREP_RA_NEON = 8,         /* neon_search          krep.c:4506 */
     KREP_RA_AHO_CORASICK = 9, /* aho_corasick_search  aho_corasick.c:299 */
     KREP_RA_REGEX = 10        /* regex_search         krep.c:1389 — the fixed-length class sequences of
-                                 krep_gpu_regex_compile() below and their alternations
-                                 (krep_gpu_regex_compile_alt()); every other expression stays on the CPU */
+                                 krep_gpu_regex_compile() below, their alternations (krep_gpu_regex_compile_alt())
+                                 and what krep_gpu_regex_compile_ext() expands into one; everything else stays on the CPU */
 };
 
 /* All of it in one explicit object.  Plans and search_buffer_ex() carry their configuration; the setters below write the
@@ -224,12 +224,13 @@ uint64_t krep_gpu_literal_search(const search_params_t *params, const char *text
                                  size_t text_len, match_result_t *result);
 uint64_t krep_gpu_aho_corasick_search(const search_params_t *params, const char *text_start,
                                       size_t text_len, match_result_t *result);
-/* regex_search (krep.c:1389-1579) for the patterns krep_gpu_regex_compile_anchored() or krep_gpu_regex_compile_alt() accepts; params->compiled_regex is never read here
+/* regex_search (krep.c:1389-1579) for the patterns krep_gpu_regex_compile_anchored(), krep_gpu_regex_compile_alt() or
+ * krep_gpu_regex_compile_ext() accepts; params->compiled_regex is never read here
  * and goes to the registered CPU function untouched when the attempt fails. */
 uint64_t krep_gpu_regex_search(const search_params_t *params, const char *text_start,
                                size_t text_len, match_result_t *result);
 /* Drop-in for select_search_algorithm(): returns one of the three functions above, or NULL when the backend does not
- * take the search — no usable device (krep_gpu_available() == 0), a regex both -E compilers refuse, and the input classes
+ * take the search — no usable device (krep_gpu_available() == 0), a regex all -E compilers refuse, and the input classes
  * krep_gpu_can_accelerate() names — so that the caller keeps the CPU function pointer the reference's own
  * select_search_algorithm() gives it.  (-c through simd_sse42_search / kmp_search with a newline inside the pattern, refused
  * until round 3, is reproduced: one device thread walks the ordered occurrence list the way the reference's loop moves.) */
@@ -237,10 +238,11 @@ search_func_t krep_gpu_select_search_algorithm(const search_params_t *params);
 /* 1 when the backend takes the search for `params` under the current configuration, 0 when not:
  *   - no usable gfx950 device (krep_gpu_available() == 0);
  *   - no pattern at all (num_patterns == 0 and pattern == NULL);
- *   - use_regex with a search both krep_gpu_regex_compile_anchored() and krep_gpu_regex_compile_alt() refuse (anything that is
- *     neither a fixed number of byte classes in a row with an optional ^ in front and $ behind nor an alternation of such
- *     sequences without anchors; -w).  The reason reported is the alternation compiler's when the search says an alternation
- *     (several patterns, or a '|' or '(' outside brackets and not behind a backslash), else the anchored compiler's.
+ *   - use_regex with a search krep_gpu_regex_compile_anchored(), krep_gpu_regex_compile_alt() and krep_gpu_regex_compile_ext()
+ *     all refuse (anything that is neither a fixed number of byte classes in a row with an optional ^ in front and $ behind nor
+ *     an alternation of such sequences nor an expression of ?, {n,m} and groups that expands into one; -w).  The reason reported
+ *     is the alternation compiler's when the search says an alternation (several patterns, or a '|' or '(' outside brackets and
+ *     not behind a backslash), else the anchored compiler's; krep_gpu_regex_compile_ext()'s when only its own limits refuse.
  * (count_lines_mode together with only_matching through memchr_short_search — a combination krep's main() never produces,
  * krep.c:3811-3814 — was refused until round 5 and is reproduced now: one window, krep_gpu_split_mode() = WHOLE.)
  * An operator called with such params anyway treats it like a run-time failure (see the top of this header): the
@@ -355,6 +357,52 @@ typedef struct krep_gpu_regex_alt
 } krep_gpu_regex_alt_t;
 /* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
 int krep_gpu_regex_compile_alt(const search_params_t *params, krep_gpu_regex_alt_t *out);
+
+/* ---- ?, {n,m}, inner groups and anchored alternations: colou?r, [0-9]{1,3}%, (GET|POST) /api, ^(ERROR|WARN), \.(jpg|png)$ ----
+ * Each of these is a finite set of fixed-length class sequences between one pair of line anchors.  This compiler EXPANDS the
+ * expression into that set; the scan is the alternation's, with ^ and $ as one more place in front of and behind every branch.
+ * Grammar: every pattern of params is B ( '|' B )*, the top-level branches of all patterns together being the alternation.
+ *   B     = ['^'] item+ ['$']
+ *   item  = atom quant? | group quant?
+ *   atom  = what krep_gpu_regex_compile() takes as one: an ordinary byte, '\' + punctuation, '.', a bracket expression
+ *   group = '(' seq ( '|' seq )* ')',  seq = ( atom quant? )+      (no group inside a group, no ^ or $ inside a group)
+ *   quant = '?' | '{n}' | '{n,m}'  with 0 <= n <= m and m >= 1
+ *   A branch expands to the product of its items' alternatives (colou?r: color, colour; (ab){2}: abab; x(a|bc)y: xay, xbcy);
+ *   sequences whose class tables are identical merge.  ^ and $ are anchors only as the first and the last byte of a top-level
+ *   branch, and every branch of every pattern must carry the same pair: ^(a|b), ^a|^b and -e '^GET' -e '^POST' are taken,
+ *   ^a|b and -e a -e '^b' are not.
+ * Refused (2, each with its own reason): * + and {n,}; a quantifier behind a quantifier; an expansion that holds an empty
+ *   sequence (a?, (a|b)?, a{0}, ^$); an empty alternative in a group or an empty branch; nested or unbalanced parentheses; ^ or $
+ *   inside a group or in the middle of a branch; mixed anchors; more than 8 distinct sequences; a sequence with L + bol + eol > 16;
+ *   the sum of L + bol + eol over the sequences > 32; -w; a multibyte locale; a pattern byte outside 0x01-0x7F; an atom the
+ *   tokeniser refuses.
+ * Every search asks krep_gpu_regex_compile_anchored() first, then krep_gpu_regex_compile_alt(), then this call: a search one of
+ *   those takes runs the kernel it always ran.  The reason reported for a search all three refuse is the one reported before
+ *   this compiler existed, unless the search fails only at this compiler's own limits (the number of sequences or places after
+ *   expansion, an empty sequence in the expansion): then it is this compiler's.
+ * What a scan reproduces (regex_search; checked against glibc with a brute-force model): branch i with classes C[i][0..L_i)
+ *   occurs at p when text[p + j] is in C[i][j] for all j < L_i, p + L_i <= text_len;
+ *     when bol: p == 0 or text[p - 1] == '\n';
+ *     when eol: text[p + L_i] == '\n', or p + L_i == text_len in a case-sensitive search (the REG_NOTEOL quirk described above).
+ *   The occurrence at p is (p, p + the longest occurring L_i); the matches are the greedy leftmost non-overlapping selection that
+ *   consumes that length; the anchors consume nothing.  -c counts the distinct lines that hold an occurrence's start.  max_count
+ *   and its 0 quirk as above.
+ * alt: the expanded branches over the REAL classes, each what krep_gpu_regex_compile() makes of that sequence alone; Lmin, Lmax
+ *   and total_L over the real lengths.  alt.cross_overlap is computed over the expanded set: branches i, j and a shift d as above,
+ *   where for d >= 1 an anchor rules the pair out when the newline it needs falls on a class that holds none (under ^ the byte in
+ *   front of the second occurrence, class C[i][d - 1]; under $ the byte behind the occurrence that ends first).  The same start
+ *   on two branches (d == 0) always counts.  Split and windows: as for an alternation and for an anchored sequence — -c is
+ *   KREP_GPU_SPLIT_PIECES, without -c PIECES when cross_overlap == 0 and else WHOLE; bol with own_lo == 0 in a buffer that does not
+ *   begin the text and eol with an owned occurrence that ends on the last byte of a buffer that does not end the text are
+ *   refused (2). */
+typedef struct krep_gpu_regex_ext
+{
+    krep_gpu_regex_alt_t alt; /* the expanded set over the real classes                  */
+    int bol;                  /* every top-level branch starts with an unescaped ^       */
+    int eol;                  /* every top-level branch ends with an unescaped $         */
+} krep_gpu_regex_ext_t;
+/* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
+int krep_gpu_regex_compile_ext(const search_params_t *params, krep_gpu_regex_ext_t *out);
 
 /* The in-memory twin of search_file()/search_string() that BASELINE.json calls search_buffer():
  * validation as krep.c:2013-2049 (no patterns -> 2; empty pattern among several -> 2; pattern

@@ -151,6 +151,12 @@ class RegexAlt(C.Structure):
                 ("cross_overlap", C.c_int), ("reserved", C.c_uint32), ("branch", RegexInfo * 8)]
 
 
+class RegexExt(C.Structure):
+    """krep_gpu_regex_ext_t: what krep_gpu_regex_compile_ext() expands ?, {n,m}, inner groups and anchored alternations into: an
+    alternation over the real classes between the line anchors bol / eol"""
+    _fields_ = [("alt", RegexAlt), ("bol", C.c_int), ("eol", C.c_int)]
+
+
 class ShardInfo(C.Structure):
     """krep_gpu_shard_info_t: where the calling thread's last sharded host search ran."""
     _fields_ = [("shards", C.c_int), ("devices_used", C.c_int), ("device_ids", C.c_int * 16), ("comm_ranks", C.c_int),

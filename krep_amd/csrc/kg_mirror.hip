@@ -153,7 +153,8 @@ extern "C" const char *krep_gpu_algorithm_name(int a)
 // ------------------------------------------------------------------------------------ what is accelerated
 // A regular expression (-E) is taken when krep_gpu_regex_compile_anchored() accepts it: a fixed number of byte classes in a row
 // (an optional ^ in front, an optional $ behind), one pattern, or when krep_gpu_regex_compile_alt() accepts what that one refuses:
-// an alternation of up to 8 such sequences without anchors, in one pattern or several;
+// an alternation of up to 8 such sequences without anchors, in one pattern or several; or when krep_gpu_regex_compile_ext() accepts
+// what both refuse: ?, {n,m} and inner groups that expand into up to 8 such sequences, all between one pair of line anchors;
 // no -w; every other expression stays with krep's regex_search.  Beyond that ONE input class is not taken; for it krep_gpu_can_accelerate() says 0, krep_gpu_select_search_algorithm() returns NULL (the
 // caller keeps its CPU function pointer, exactly like the regex case) and an operator called with it anyway takes the failure road:
 //  * memchr_short_search in -c mode while the file-static only_matching is set: main() never produces that
@@ -161,19 +162,35 @@ extern "C" const char *krep_gpu_algorithm_name(int a)
 // (Round 3: -c through simd_sse42_search / kmp_search with a '\n' inside the pattern — refused until then — is reproduced by a
 //  walk over the ordered occurrence list, kg_greedy.hip (3).)
 namespace kg {
-// both compilers in the order every search asks them (kg_internal.h)
+// the three compilers in the order every search asks them (kg_internal.h)
 static const char *regex_compile_both(const search_params_t *p, RegexCompiled *out)
 {
     out->is_alt = false;
+    out->alt_bol = out->alt_eol = 0;
     const char *why = regex_compile_anchored(p, &out->seq);
     if (!why)
         return nullptr;
     if (!p || !p->use_regex)
         return why;
-    if (const char *why_alt = regex_compile_alt(p, &out->alt))
-        return regex_has_alt_syntax(p) ? why_alt : why;
-    out->is_alt = true;
-    return nullptr;
+    const char *why_alt = regex_compile_alt(p, &out->alt);
+    if (!why_alt)
+    {
+        out->is_alt = true;
+        return nullptr;
+    }
+    krep_gpu_regex_ext_t ext;
+    const char *why_ext = regex_compile_ext(p, &ext);
+    if (!why_ext)
+    {
+        out->is_alt = true;
+        out->alt = ext.alt;
+        out->alt_bol = ext.bol;
+        out->alt_eol = ext.eol;
+        return nullptr;
+    }
+    // the reason of a search all three refuse: what it was before the expanding compiler, unless only that one's own limits are in the way
+    const char *before = regex_has_alt_syntax(p) ? why_alt : why;
+    return regex_ext_own_limit(why_ext) && !strstr(before, "more than") ? why_ext : before;
 }
 const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out)
 {
@@ -218,8 +235,8 @@ const char *unsupported_reason(const search_params_t *p, const krep_gpu_config_t
     if (!p)
         return "NULL params";
     if (p->use_regex)
-    { // -E: taken exactly when the pattern is a fixed number of byte classes in a row, ^ in front and $ behind allowed, or an
-      // alternation of such sequences without anchors (kg_regex_compile.h names the refusals)
+    { // -E: taken exactly when the pattern is a fixed number of byte classes in a row, ^ in front and $ behind allowed, an
+      // alternation of such sequences, or an expression that expands into one (kg_regex_compile.h names the refusals)
         RegexCompiled rc;
         return regex_compile_cached(p, &rc);
     }

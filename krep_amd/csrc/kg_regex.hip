@@ -1,7 +1,7 @@
 // kg_regex.hip — krep -E for fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile): the exported pattern
 // compilers (kg_regex_compile.h), the bit-parallel shift-and scan kernel and its driver kg::scan_regex.  An alternation of such
-// sequences (krep_gpu_regex_compile_alt) has its own kernel and driver in kg_regex_alt.hip: regex_prog_create builds its table
-// here, scan_regex hands over.
+// sequences (krep_gpu_regex_compile_alt, and what krep_gpu_regex_compile_ext expands into one, line anchors included) has its own
+// kernel and driver in kg_regex_alt.hip: regex_prog_create builds its table here, scan_regex hands over.
 //
 // The kernel.  T[byte] is a 16-bit mask, bit j set when byte is in class Cj.  It sits in LDS once per bank (entry b of copy k at
 // dword b * 32 + k, a lane reads copy lane % 32), so the 64 lookups of a wave instruction never meet in a bank whatever the
@@ -328,20 +328,28 @@ RegexProg *regex_prog_create(const search_params_t &sp)
     }
     u32 table[256];
     if (rc.is_alt)
-    { // an alternation: branch i in bits [o_i, o_i + L_i) (kg_regex_alt.hip)
+    { // an alternation: branch i in bits [o_i, o_i + Lx_i), Lx_i = L_i + bol + eol places: the class { '\n' } in front of and / or behind
+      // its classes when the branches stand between line anchors (kg_regex_alt.hip)
         rx->is_alt = true;
         rx->alt = rc.alt;
+        rx->alt_bol = rc.alt_bol ? 1u : 0u;
+        rx->alt_eol = rc.alt_eol ? 1u : 0u;
         memset(table, 0, sizeof table);
         u32 o = 0;
         for (u32 i = 0; i < rc.alt.n_branches; ++i)
         {
             const krep_gpu_regex_info_t &br = rc.alt.branch[i];
+            const u32 Lx = br.L + rx->alt_bol + rx->alt_eol;
             rx->init |= 1u << o;
-            rx->fin |= 1u << (o + br.L - 1);
+            rx->fin |= 1u << (o + Lx - 1);
             for (int b = 0; b < 256; ++b)
                 for (u32 j = 0; j < br.L; ++j)
-                    table[b] |= ((br.classes[j][b >> 3] >> (b & 7)) & 1u) << (o + j);
-            o += br.L;
+                    table[b] |= ((br.classes[j][b >> 3] >> (b & 7)) & 1u) << (o + rx->alt_bol + j);
+            if (rx->alt_bol)
+                table['\n'] |= 1u << o;
+            if (rx->alt_eol)
+                table['\n'] |= 1u << (o + Lx - 1);
+            o += Lx;
         }
     }
     else
@@ -526,6 +534,13 @@ extern "C" int krep_gpu_regex_compile_alt(const search_params_t *params, krep_gp
 {
     krep_gpu_clear_error();
     if (const char *why = kg::regex_compile_alt(params, out))
+        return kg::fail("%s", why);
+    return 0;
+}
+extern "C" int krep_gpu_regex_compile_ext(const search_params_t *params, krep_gpu_regex_ext_t *out)
+{
+    krep_gpu_clear_error();
+    if (const char *why = kg::regex_compile_ext(params, out))
         return kg::fail("%s", why);
     return 0;
 }

@@ -1,5 +1,5 @@
-// kg_regex_alt.hip — krep -E for an ALTERNATION of fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile_alt):
-// ERROR|WARN|FATAL, cat|d[oi]g|b.rd, every -E run with several -e.  The multi-branch shift-and scan kernel and its driver
+// kg_regex_alt.hip — krep -E for an ALTERNATION of fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile_alt and
+// krep_gpu_regex_compile_ext): ERROR|WARN|FATAL, cat|d[oi]g|b.rd, every -E run with several -e, colou?r, ^(ERROR|WARN).  The multi-branch shift-and scan kernel and its driver
 // kg::scan_regex_alt; kg_regex.hip keeps the single sequence and hands over when the plan's program is an alternation.
 //
 // The kernel.  Branch i lives in bits [o_i, o_i + L_i) of a 32-bit state; T[byte] has bit o_i + j set when byte is in C[i][j]
@@ -25,6 +25,14 @@
 //     the shifted mask stay in the lane, the spill goes to the next lane (lane 63's to a scalar for the next cell; a unit rebuilds
 //     it from the 16 bytes in front of it: an occurrence that spills out of them starts inside them).  From there on the newline
 //     mask shifted by Lmax - 1, the line-state arithmetic and the info words are those of kg_regex.hip's -c mode.
+// Line anchors (krep_gpu_regex_compile_ext: ^(ERROR|WARN), (jpg|png)$, and what ?, {n,m} and inner groups expand into): the
+// instantiations with ANCH.  Every branch gets the place { '\n' } in front of (^) and / or behind ($) its classes, so branch i takes
+// Lx_i = L_i + bol + eol bits and everything above holds with the places Lx in the role of the lengths: the lookback is Lxmax - 1
+// <= 15 bytes, a hit of Lx places behind byte e is the occurrence (e + 1 - Lx + bol, e + 1 - eol), the common coordinate of -c is
+// start + Lmax - 1 + eol.  Two newlines stand in no buffer: the one in front of byte 0 of the text is the entry state INIT of the unit
+// at coordinate 0, the one behind the last byte is OR-ed into the one lane of a guarded load that holds offset text_len, in a
+// case-sensitive search only (so with $ the coordinates reach text_len: one more cell or unit when the length is a multiple of
+// one).  Neither is a newline of -c.  Sets without anchors run the instantiations without ANCH: the code they always ran.
 // The anchor-byte fast path of kg_regex.hip is not taken: DESIGN §4.9 measured no gain from it on sparse text.
 // Reads: no byte outside [0, text_len) — whole 8-KiB rounds inside the text are vector loads, everything else is guarded per byte.
 #include <hip/hip_runtime.h>
@@ -53,7 +61,13 @@ struct RaArgs
     u64 n_units;
     u64 global_base;
     u32 init, fin;
-    u32 geom;           // bits 0-7 Lmax; bit 8 cross_overlap
+    // One word for the geometry (every further uniform value costs scalar registers):
+    //   bits 0-7  Lxmax: the places of the longest branch, Lmax + bol + eol (the lookback of the exit state is Lxmax - 1 bytes)
+    //   bit 8     cross_overlap
+    //   bit 9     bol, bit 10 eol: every branch has the place { '\n' } in front of / behind its classes (anchored instantiations only)
+    //   bit 11    the entry state of the unit at coordinate 0 is INIT: ^ and the buffer begins the text
+    //   bit 12    a guarded load holds '\n' at offset text_len: $ in the buffer that ends the text (not under -i)
+    u32 geom;
     const u32 *table;
     u64 *unitinfo;      // count mode: per-unit info words (nullptr: only the total is wanted)
     const u64 *offsets; // emit mode: exclusive index of each unit's first record
@@ -91,7 +105,20 @@ static __device__ __forceinline__ u32 ra_walk(const u32 *T, const uint4 &d, u32 
     }
     return H;
 }
-// the same walk again for a lane that holds hits: f(k, L) for every branch that ends behind a byte k of H, L its length
+// $: the newline behind the last byte of the text, put into the 16 bytes from q when they hold offset text_len
+static __device__ __forceinline__ void ra_put_eot(uint4 &d, u64 q, u64 text_len)
+{
+    const u64 rel = text_len - q;
+    if (rel < 16u)
+    {
+        const u32 nl = 0x0au << (8u * ((u32)rel & 3u)), w = (u32)rel >> 2;
+        d.x |= w == 0u ? nl : 0u;
+        d.y |= w == 1u ? nl : 0u;
+        d.z |= w == 2u ? nl : 0u;
+        d.w |= w == 3u ? nl : 0u;
+    }
+}
+// the same walk again for a lane that holds hits: f(k, L) for every branch that ends behind a byte k of H, L its places
 template <class F> static __device__ __forceinline__ void ra_hits(const u32 *T, const uint4 &d, u32 init, u32 fin, u32 E, u32 H, F &&f)
 {
     u32 S = E;
@@ -114,33 +141,40 @@ template <class F> static __device__ __forceinline__ void ra_hits(const u32 *T, 
         }
     }
 }
-// the (end, branch) pairs of a lane whose occurrence starts in [own_lo, own_hi): the unit both launches count
+// the (end, branch) pairs of a lane whose occurrence starts in [own_lo, own_hi): the unit both launches count.  A hit of Lx places
+// behind byte k starts at q + k + 1 - Lx + bol: the ^ place lies in front of the start.
+template <bool ANCH>
 static __device__ __forceinline__ u32 ra_count_lane(const u32 *T, const uint4 &d, const RaArgs &a, u32 E, u32 H, u64 q, bool all_owned)
 {
     if (all_owned)
         return (u32)__popc(H); // (no two occurrences share a byte: one pair per end)
+    const u32 bol = ANCH ? (a.geom >> 9) & 1u : 0u;
     u32 c = 0;
     if (H)
         ra_hits(T, d, a.init, a.fin, E, H, [&](u32 k, u32 L) {
-            const u64 s = q + k + 1u - L;
+            const u64 s = q + k + 1u + bol - L;
             c += (s >= a.own_lo && s < a.own_hi) ? 1u : 0u;
         });
     return c;
 }
-// -c: the owned hits of a lane at coordinate start + Lmax - 1, relative to q (bits 16..30: the spill into the next lane)
+// -c: the owned hits of a lane at the common coordinate (the end a branch of Lmax places would have), relative to q (bits 16..30: the
+// spill into the next lane)
+template <bool ANCH>
 static __device__ __forceinline__ u32 ra_starts(const u32 *T, const uint4 &d, const RaArgs &a, u32 E, u32 H, u64 q, u32 Lmax)
 {
+    const u32 bol = ANCH ? (a.geom >> 9) & 1u : 0u;
     u32 M = 0;
     if (H)
         ra_hits(T, d, a.init, a.fin, E, H, [&](u32 k, u32 L) {
-            const u64 s = q + k + 1u - L;
+            const u64 s = q + k + 1u + bol - L;
             if (s >= a.own_lo && s < a.own_hi)
                 M |= 1u << (k + Lmax - L);
         });
     return M;
 }
 
-template <int MODE>
+// ANCH: the branches stand between line anchors (krep_gpu_regex_compile_ext); without it the code is the unanchored alternation's
+template <int MODE, bool ANCH>
 __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
 {
     constexpr bool LINES = MODE == kRaLines, EMIT = MODE == kRaEmit;
@@ -150,8 +184,12 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
     __syncthreads();
     const u32 lane = lane_id(), wave = threadIdx.x >> 6;
     const u32 *T = s_T + (lane & 31u);
-    const u32 Lmax = a.geom & 0xffu, sh = Lmax - 1u, first = 17u - Lmax;
+    // Lmax: the places of the longest branch; a start p is seen, or for -c put, at coordinate p + sh = p + Lmax - 1 - bol
+    const u32 bol = ANCH ? (a.geom >> 9) & 1u : 0u, eol = ANCH ? (a.geom >> 10) & 1u : 0u;
+    const u32 Lmax = a.geom & 0xffu, sh = Lmax - 1u - bol, first = 17u - Lmax;
     const bool cross = ((a.geom >> 8) & 1u) != 0u;
+    const bool eot = ANCH && ((a.geom >> 12) & 1u) != 0u;
+    const u64 end_hi = ANCH ? a.text_len + (eot ? 1u : 0u) : a.text_len; // an end is a byte of the text, or the newline behind it
     const u64 in_lo = a.own_lo + sh; // a cell of ends in [in_lo, own_hi) owns every occurrence that ends in it
     const u64 n_waves = (u64)gridDim.x * kWavesPerBlk;
     u64 acc_total = 0;
@@ -162,17 +200,22 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
         // the 16 bytes in front of the unit give lane 0 its entry state and, for -c, the spill and the newlines that shift into the unit
         u32 x63 = 0; // exit state of the 16 bytes in front of the next cell (uniform)
         u32 y63 = 0; // -c: their spill | their raw newline mask << 16 (uniform)
+        if constexpr (ANCH)
+            x63 = ((a.geom >> 11) & 1u) != 0u ? a.init : 0u; // ^: the newline in front of byte 0 of the text
         if (ubase != 0)
         {
             const u64 pq = ubase - 16u;
-            const uint4 p = rx_load_guarded(a.text, a.text_len, pq);
+            uint4 p = rx_load_guarded(a.text, a.text_len, pq);
+            if constexpr (ANCH)
+                if (eot)
+                    ra_put_eot(p, pq, a.text_len);
             x63 = __builtin_amdgcn_readfirstlane(ra_exit(T, p, a.init, first));
             if (LINES)
             {
-                // (an occurrence whose coordinate start + Lmax - 1 lies in the unit and whose end does not starts inside these 16 bytes:
-                //  the entry state of the walk does not reach it)
-                const u32 Hp = ra_walk(T, p, a.init, a.fin, 0u) & rx_range(pq, 0, a.text_len);
-                const u32 M = ra_starts(T, p, a, 0u, Hp, pq, Lmax);
+                // (an occurrence whose coordinate start + sh lies in the unit and whose end does not starts behind the first of these 16
+                //  bytes, its ^ place inside them: the entry state of the walk does not reach it)
+                const u32 Hp = ra_walk(T, p, a.init, a.fin, 0u) & rx_range(pq, 0, end_hi);
+                const u32 M = ra_starts<ANCH>(T, p, a, 0u, Hp, pq, Lmax);
                 y63 = __builtin_amdgcn_readfirstlane((M >> 16) | ((rx_newlines(p) & rx_range(pq, a.own_lo, a.own_hi)) << 16));
             }
         }
@@ -221,6 +264,13 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
                     const u64 cb = seg + (u64)j * kCellBytes;
                     d[j] = cb < a.cov_hi ? rx_load_guarded(a.text, a.text_len, cb + (u64)lane * 16u) : make_uint4(0u, 0u, 0u, 0u);
                 }
+                if constexpr (ANCH)
+                    if (eot)
+                    {
+#pragma unroll
+                        for (int j = 0; j < kCells; ++j)
+                            ra_put_eot(d[j], seg + (u64)j * kCellBytes + (u64)lane * 16u, a.text_len);
+                    }
             }
 #pragma unroll
             for (int j = 0; j < kCells; ++j)
@@ -236,10 +286,10 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
                 x63 = __builtin_amdgcn_readlane(X, 63);
                 u32 H = ra_walk(T, d[j], a.init, a.fin, E);
                 if (!fast)
-                    H &= rx_range(q, 0, a.text_len); // an end is a byte of the text
+                    H &= rx_range(q, 0, end_hi);
                 if (LINES)
                 {
-                    const u32 M = ra_starts(T, d[j], a, E, H, q, Lmax);
+                    const u32 M = ra_starts<ANCH>(T, d[j], a, E, H, q, Lmax);
                     const u32 mine = (M >> 16) | ((rx_newlines(d[j]) & rx_range(q, a.own_lo, a.own_hi)) << 16);
                     u32 prev = __shfl_up(mine, 1);
                     if (lane == 0)
@@ -256,7 +306,7 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
                 else if (__ballot(H != 0u))
                 {
                     const bool all_owned = !cross && cbase >= in_lo && cbase + kCellBytes <= a.own_hi;
-                    const u32 c = ra_count_lane(T, d[j], a, E, H, q, all_owned);
+                    const u32 c = ra_count_lane<ANCH>(T, d[j], a, E, H, q, all_owned);
                     l_hits += c;
                     if (EMIT)
                     {
@@ -272,12 +322,12 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
                         {
                             u64 idx = out_idx + (incl - c);
                             ra_hits(T, d[j], a.init, a.fin, E, H, [&](u32 k, u32 L) {
-                                const u64 s = q + k + 1u - L;
+                                const u64 s = q + k + 1u + bol - L;
                                 if (s >= a.own_lo && s < a.own_hi)
                                 {
                                     if (idx < a.pos_cap)
                                     {
-                                        const u64 s0 = s + a.global_base, e0 = s0 + L;
+                                        const u64 s0 = s + a.global_base, e0 = s0 + (L - bol - eol);
                                         *reinterpret_cast<uint4 *>(a.positions + 2 * idx) = make_uint4((u32)s0, (u32)(s0 >> 32), (u32)e0, (u32)(e0 >> 32));
                                     }
                                     ++idx;
@@ -317,15 +367,19 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
         atomicAdd(&a.ctr->total, acc_total);
 }
 
-template <int MODE> static hipError_t ra_launch(const RaArgs &a, int num_cu, hipStream_t st)
+template <int MODE, bool ANCH> static hipError_t ra_launch_as(const RaArgs &a, int num_cu, hipStream_t st)
 {
     const u64 blocks = (a.n_units + kWavesPerBlk - 1) / kWavesPerBlk;
     // (32 KiB of LDS each would let five workgroups into a CU, but the kernel holds 112 to 125 VGPRs: four waves per SIMD, four workgroups)
     u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 4));
     if (const int force = g_rx_force_grid.load(); force > 0) // test hook: a starved grid (krep_gpu_debug_force_regex_grid)
         grid = std::min<u32>(grid, (u32)force);
-    hipLaunchKernelGGL((regex_alt_scan<MODE>), dim3(grid), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL((regex_alt_scan<MODE, ANCH>), dim3(grid), dim3(kBlock), 0, st, a);
     return hipGetLastError();
+}
+template <int MODE> static hipError_t ra_launch(const RaArgs &a, int num_cu, hipStream_t st)
+{
+    return ((a.geom >> 9) & 3u) ? ra_launch_as<MODE, true>(a, num_cu, st) : ra_launch_as<MODE, false>(a, num_cu, st);
 }
 
 // ------------------------------------------------------------------------------------------------ the scan of a window
@@ -344,6 +398,17 @@ int scan_regex_alt(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, 
                     "list: scan the whole text in one window (krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
     if (own_hi <= w.own_lo)
         return 0;
+    // an anchor needs the byte in front of, or behind, every occurrence the window owns (as in kg_regex.hip)
+    const u32 bol = rx.alt_bol, eol = rx.alt_eol;
+    const bool ends_text = w.global_base + w.text_len == w.global_len;
+    if (bol && w.own_lo == 0 && w.global_base > 0)
+        return fail("regex with ^: the window owns buffer byte 0, which is not the start of the text (global_base > 0), and the byte in "
+                    "front of it decides a match there: start the buffer at least one byte in front of own_lo");
+    if (eol && !ends_text)
+        for (u32 i = 0; i < rx.alt.n_branches; ++i)
+            if (const u32 L = rx.alt.branch[i].L; w.own_lo + L <= w.text_len && own_hi + L > w.text_len)
+                return fail("regex with $: the window owns a start whose occurrence ends on the last byte of a buffer that does not end the "
+                            "text, and the byte behind it decides the match: end own_hi at least L bytes in front of the buffer's end");
     const size_t maxc = pl->max_count;
     const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(maxc, cap) : 0;
 
@@ -351,11 +416,14 @@ int scan_regex_alt(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, 
     a.text = w.d_text; a.text_len = w.text_len;
     a.anchor = w.own_lo & ~(u64)15;
     a.own_lo = w.own_lo; a.own_hi = own_hi;
-    a.cov_hi = lines ? (u64)own_hi + (Lmax - 1) : std::min<u64>((u64)own_hi + (Lmax - 1), w.text_len);
+    // (regex_search ORs REG_ICASE into regexec's eflags, where that bit is REG_NOTEOL: under -i the end of the text ends no line)
+    const u32 entry0 = bol && w.global_base == 0 ? 1u : 0u, eot = eol && ends_text && pl->sp.case_sensitive ? 1u : 0u;
+    const u32 sh = Lmax - 1 + eol; // a start p is seen at p + L_i - 1 + eol and, for -c, put at p + sh
+    a.cov_hi = lines ? (u64)own_hi + sh : std::min<u64>((u64)own_hi + sh, w.text_len + eot); // (with $ this reaches text_len + 1)
     a.n_units = (a.cov_hi - a.anchor + kRxUnitBytes - 1) / kRxUnitBytes;
     a.global_base = w.global_base;
     a.init = rx.init; a.fin = rx.fin;
-    a.geom = Lmax | ((rx.alt.cross_overlap ? 1u : 0u) << 8);
+    a.geom = (Lmax + bol + eol) | ((rx.alt.cross_overlap ? 1u : 0u) << 8) | (bol << 9) | (eol << 10) | (entry0 << 11) | (eot << 12);
     a.table = rx.d_table;
     a.ctr = pl->d_ctr;
 

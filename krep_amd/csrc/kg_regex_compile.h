@@ -4,6 +4,8 @@
 // (tools/regex_compile_san.cpp).  It never sees a text: what it produces is a table, the search is the kernel's (kg_regex.hip).
 // krep_gpu_regex_compile_alt (at the end of this file) cuts an alternation at its top-level '|', takes one pair of parentheses
 // off a branch and hands every branch to the same tokeniser (kg_regex_alt.hip scans what it makes).
+// krep_gpu_regex_compile_ext (behind it) EXPANDS ?, {n,m} and inner groups into such an alternation and takes a ^ in front of and
+// a $ behind every top-level branch, the same pair on all of them.
 #pragma once
 #include <regex.h>
 #include <stdint.h>
@@ -72,6 +74,45 @@ inline bool regex_probe_atom(const uint8_t *atom, size_t len, bool case_sensitiv
     }
     regfree(&re);
     return true;
+}
+
+// The fields behind the classes of a sequence whose L and classes are set: the anchor class with its bytes, and self_overlap
+inline void regex_seq_finish(krep_gpu_regex_info_t *out, bool bol, bool eol)
+{
+    const uint32_t L = out->L;
+    auto size_of = [&](uint32_t k) {
+        uint32_t s = 0;
+        for (int b = 0; b < 256; ++b)
+            s += (out->classes[k][b >> 3] >> (b & 7)) & 1u;
+        return s;
+    };
+    uint32_t best = 0, best_n = size_of(0);
+    for (uint32_t k = 1; k < L; ++k)
+        if (const uint32_t s = size_of(k); s < best_n)
+        {
+            best = k;
+            best_n = s;
+        }
+    out->anchor = best;
+    if (best_n >= 1 && best_n <= 4)
+        for (int b = 0; b < 256; ++b)
+            if ((out->classes[best][b >> 3] >> (b & 7)) & 1u)
+                out->anchor_bytes[out->n_anchor++] = (uint8_t)b;
+    // can the pattern overlap itself: a shift d at which every class meets the one d places on; behind ^ the byte in front of the
+    // second occurrence, which lies inside the first, has to be a newline, and in front of $ the byte behind the first occurrence
+    auto holds_nl = [&](uint32_t k) { return ((out->classes[k]['\n' >> 3] >> ('\n' & 7)) & 1u) != 0; };
+    for (uint32_t d = 1; d < L && !out->self_overlap; ++d)
+    {
+        bool all = (!bol || holds_nl(d - 1)) && (!eol || holds_nl(L - d));
+        for (uint32_t k = 0; k + d < L && all; ++k)
+        {
+            bool meet = false;
+            for (int w = 0; w < 32 && !meet; ++w)
+                meet = (out->classes[k][w] & out->classes[k + d][w]) != 0;
+            all = meet;
+        }
+        out->self_overlap = all ? 1 : 0;
+    }
 }
 
 // Both entry points.  anchors: a '^' as the first and a '$' as the last pattern byte are line anchors (krep_gpu_regex_compile_anchored);
@@ -204,39 +245,7 @@ inline const char *regex_compile_seq(const search_params_t *p, bool anchors, kre
             memcpy(out->classes[j++], cls, 32);
     }
     out->L = L;
-    auto size_of = [&](uint32_t k) {
-        uint32_t s = 0;
-        for (int b = 0; b < 256; ++b)
-            s += (out->classes[k][b >> 3] >> (b & 7)) & 1u;
-        return s;
-    };
-    uint32_t best = 0, best_n = size_of(0);
-    for (uint32_t k = 1; k < L; ++k)
-        if (const uint32_t s = size_of(k); s < best_n)
-        {
-            best = k;
-            best_n = s;
-        }
-    out->anchor = best;
-    if (best_n >= 1 && best_n <= 4)
-        for (int b = 0; b < 256; ++b)
-            if ((out->classes[best][b >> 3] >> (b & 7)) & 1u)
-                out->anchor_bytes[out->n_anchor++] = (uint8_t)b;
-    // can the pattern overlap itself: a shift d at which every class meets the one d places on; behind ^ the byte in front of the
-    // second occurrence, which lies inside the first, has to be a newline, and in front of $ the byte behind the first occurrence
-    auto holds_nl = [&](uint32_t k) { return ((out->classes[k]['\n' >> 3] >> ('\n' & 7)) & 1u) != 0; };
-    for (uint32_t d = 1; d < L && !out->self_overlap; ++d)
-    {
-        bool all = (!bol || holds_nl(d - 1)) && (!eol || holds_nl(L - d));
-        for (uint32_t k = 0; k + d < L && all; ++k)
-        {
-            bool meet = false;
-            for (int w = 0; w < 32 && !meet; ++w)
-                meet = (out->classes[k][w] & out->classes[k + d][w]) != 0;
-            all = meet;
-        }
-        out->self_overlap = all ? 1 : 0;
-    }
+    regex_seq_finish(out, bol, eol);
     *bol_out = bol;
     *eol_out = eol;
     return nullptr;
@@ -460,6 +469,367 @@ inline const char *regex_compile_alt(const search_params_t *p, krep_gpu_regex_al
         return "NULL params";
     memset(out, 0, sizeof *out);
     const char *why = regex_compile_alt_branches(p, out);
+    if (why)
+        memset(out, 0, sizeof *out);
+    return why;
+}
+
+// ---- krep_gpu_regex_compile_ext: ?, {n,m}, inner groups and anchored alternations, expanded into class sequences --------------
+// A partial expansion: at most 8 distinct sequences (only L and classes of each are in use; L == 0 is the empty sequence).  The
+// number of distinct sequences never shrinks when something is put behind all of them, and no sequence gets shorter, so a set
+// that passes 8 sequences or a sequence that passes 16 classes ends the expansion at once.
+struct RegexSeqSet
+{
+    uint32_t n;
+    krep_gpu_regex_info_t s[kRegexMaxBranches];
+};
+constexpr const char *kRegexExtTooMany = "regex expansion: ?, {n,m} and groups multiply out to more than 8 distinct class sequences: kept on krep's regex_search";
+constexpr const char *kRegexExtTooLong = "regex expansion: a sequence of more than 16 places (^ and $ take one each beside the byte classes): kept on krep's "
+                                         "regex_search";
+constexpr const char *kRegexExtTooWide = "regex expansion: more than 32 places in all sequences together (^ and $ take one each in every sequence): kept on "
+                                         "krep's regex_search";
+constexpr const char *kRegexExtEmpty = "regex expansion: one of the sequences holds no byte class (a?, (a|b)?, a{0,1}): it matches the empty string: kept on "
+                                       "krep's regex_search";
+inline bool regex_ext_own_limit(const char *why) { return why == kRegexExtTooMany || why == kRegexExtTooLong || why == kRegexExtTooWide || why == kRegexExtEmpty; }
+
+inline const char *regex_set_add(RegexSeqSet &S, const krep_gpu_regex_info_t &q)
+{
+    for (uint32_t i = 0; i < S.n; ++i)
+        if (S.s[i].L == q.L && memcmp(S.s[i].classes, q.classes, (size_t)q.L * 32) == 0)
+            return nullptr;
+    if (S.n >= kRegexMaxBranches)
+        return kRegexExtTooMany;
+    S.s[S.n++] = q;
+    return nullptr;
+}
+inline const char *regex_set_union(RegexSeqSet &S, const RegexSeqSet &A)
+{
+    for (uint32_t i = 0; i < A.n; ++i)
+        if (const char *why = regex_set_add(S, A.s[i]))
+            return why;
+    return nullptr;
+}
+// C = every sequence of A with every sequence of B behind it
+inline const char *regex_set_cat(const RegexSeqSet &A, const RegexSeqSet &B, RegexSeqSet &C)
+{
+    C.n = 0;
+    for (uint32_t i = 0; i < A.n; ++i)
+        for (uint32_t j = 0; j < B.n; ++j)
+        {
+            if (A.s[i].L + B.s[j].L > kRegexMaxL)
+                return kRegexExtTooLong;
+            krep_gpu_regex_info_t q = A.s[i];
+            for (uint32_t t = 0; t < B.s[j].L; ++t)
+                memcpy(q.classes[q.L++], B.s[j].classes[t], 32);
+            if (const char *why = regex_set_add(C, q))
+                return why;
+        }
+    return nullptr;
+}
+inline void regex_set_empty_seq(RegexSeqSet &S)
+{
+    memset(&S, 0, sizeof S);
+    S.n = 1;
+}
+// A{lo,hi}: lo..hi sequences of A in a row (hi >= 1)
+inline const char *regex_set_repeat(RegexSeqSet &A, uint32_t lo, uint32_t hi)
+{
+    RegexSeqSet P, R, T;
+    regex_set_empty_seq(P);
+    memset(&R, 0, sizeof R);
+    for (uint32_t k = 0;; ++k)
+    {
+        if (k >= lo)
+            if (const char *why = regex_set_union(R, P))
+                return why;
+        if (k == hi)
+            break;
+        if (const char *why = regex_set_cat(P, A, T))
+            return why;
+        P = T;
+    }
+    A = R;
+    return nullptr;
+}
+inline bool regex_is_quant(uint8_t c) { return c == '?' || c == '*' || c == '+' || c == '{'; }
+
+// the cursor over one pattern
+struct RegexExtCursor
+{
+    const uint8_t *pat;
+    size_t n, i;
+    bool case_sensitive;
+};
+// an optional quantifier at the cursor, applied to A
+inline const char *regex_ext_quant(RegexExtCursor &c, RegexSeqSet &A)
+{
+    if (c.i >= c.n || !regex_is_quant(c.pat[c.i]))
+        return nullptr;
+    uint32_t lo = 0, hi = 1;
+    if (c.pat[c.i] == '*' || c.pat[c.i] == '+')
+        return "regex: * and + repeat without a bound, which needs an unbounded state: kept on krep's regex_search";
+    if (c.pat[c.i] == '?')
+        ++c.i;
+    else
+    {
+        size_t k = c.i + 1;
+        auto number = [&](uint32_t &v) {
+            bool digits = false;
+            v = 0;
+            while (k < c.n && c.pat[k] >= '0' && c.pat[k] <= '9' && v <= 1000)
+            {
+                v = v * 10 + (uint32_t)(c.pat[k] - '0');
+                digits = true;
+                ++k;
+            }
+            return digits;
+        };
+        if (!number(lo) || k >= c.n)
+            return "regex: malformed repetition";
+        hi = lo;
+        if (c.pat[k] == ',')
+        {
+            ++k;
+            if (k < c.n && c.pat[k] == '}')
+                return "regex: {n,} repeats without a bound, which needs an unbounded state: kept on krep's regex_search";
+            if (!number(hi) || k >= c.n)
+                return "regex: malformed repetition";
+        }
+        if (c.pat[k] != '}' || lo > hi || hi > 1000)
+            return "regex: malformed repetition";
+        if (hi == 0)
+            return "regex: {0} repeats an atom zero times, a{0} matches the empty string: kept on krep's regex_search";
+        c.i = k + 1;
+    }
+    if (c.i < c.n && regex_is_quant(c.pat[c.i]))
+        return "regex: a quantifier behind a quantifier (a?{2}, a{2}{3}, a?+): kept on krep's regex_search";
+    return regex_set_repeat(A, lo, hi);
+}
+// one atom at the cursor (the tokeniser's rules, regex_compile_seq) with its optional quantifier: its alternatives into A
+inline const char *regex_ext_atom(RegexExtCursor &c, RegexSeqSet &A)
+{
+    const uint8_t ch = c.pat[c.i];
+    size_t len = 1;
+    if (ch == '\\')
+    {
+        if (c.i + 1 >= c.n)
+            return "regex: trailing backslash";
+        const uint8_t e = c.pat[c.i + 1];
+        if ((e >= '0' && e <= '9') || ((e | 0x20) >= 'a' && (e | 0x20) <= 'z'))
+            return "regex: a backslash in front of a letter or digit (\\b, \\w, \\1, ...) is an operator: kept on krep's regex_search";
+        if (!regex_is_punct(e))
+            return "regex: a backslash in front of a byte that is not punctuation";
+        len = 2;
+    }
+    else if (ch == '[')
+    {
+        const size_t e = regex_bracket_end(c.pat, c.n, c.i);
+        if (e >= c.n)
+            return "regex: bracket expression without its ']'";
+        len = e + 1 - c.i;
+    }
+    regex_set_empty_seq(A);
+    if (!regex_probe_atom(c.pat + c.i, len, c.case_sensitive, A.s[0].classes[0]))
+        return "regex: regcomp refuses an atom of the pattern";
+    A.s[0].L = 1;
+    c.i += len;
+    return regex_ext_quant(c, A);
+}
+// a group, the cursor behind its '(': '(' seq ('|' seq)* ')' quant?, seq = (atom quant?)+
+inline const char *regex_ext_group(RegexExtCursor &c, RegexSeqSet &G)
+{
+    RegexSeqSet cur, A, T;
+    memset(&G, 0, sizeof G);
+    regex_set_empty_seq(cur);
+    bool any = false; // the alternative under the cursor holds an atom
+    for (;;)
+    {
+        if (c.i >= c.n)
+            return "regex alternation: unbalanced parentheses: kept on krep's regex_search";
+        const uint8_t ch = c.pat[c.i];
+        if (ch == '(')
+            return "regex alternation: nested parentheses: kept on krep's regex_search";
+        if (ch == '^' || ch == '$')
+            return "regex: ^ or $ inside a group anchors in the middle of the expression: kept on krep's regex_search";
+        if (ch == '|' || ch == ')')
+        {
+            if (!any)
+                return "regex alternation: an empty alternative in a group ((), (a|), (|a)) matches the empty string: kept on krep's "
+                       "regex_search";
+            if (const char *why = regex_set_union(G, cur))
+                return why;
+            regex_set_empty_seq(cur);
+            any = false;
+            ++c.i;
+            if (ch == ')')
+                return regex_ext_quant(c, G);
+            continue;
+        }
+        if (regex_is_quant(ch))
+            return "regex: a quantifier that is not behind an atom or a group";
+        if (const char *why = regex_ext_atom(c, A))
+            return why;
+        if (const char *why = regex_set_cat(cur, A, T))
+            return why;
+        cur = T;
+        any = true;
+    }
+}
+// one top-level branch, up to its '|' or the end of the pattern: ['^'] item+ ['$']
+inline const char *regex_ext_branch(RegexExtCursor &c, RegexSeqSet &S, int *bol, int *eol)
+{
+    RegexSeqSet A, T;
+    regex_set_empty_seq(S);
+    *bol = *eol = 0;
+    bool any = false;
+    if (c.i < c.n && c.pat[c.i] == '^')
+    {
+        *bol = 1;
+        ++c.i;
+    }
+    while (c.i < c.n && c.pat[c.i] != '|')
+    {
+        const uint8_t ch = c.pat[c.i];
+        if (ch == '$' && (c.i + 1 == c.n || c.pat[c.i + 1] == '|'))
+        {
+            *eol = 1;
+            ++c.i;
+            break;
+        }
+        if (ch == '^' || ch == '$')
+            return "regex: ^ that is not the first or $ that is not the last byte of a branch (a^b, a$b, ^^a, a$$) anchors in the middle of "
+                   "the expression: kept on krep's regex_search";
+        if (ch == ')')
+            return "regex alternation: unbalanced parentheses: kept on krep's regex_search";
+        if (regex_is_quant(ch))
+            return (*bol && !any) ? "regex: a repetition directly behind ^ repeats the anchor: kept on krep's regex_search"
+                                  : "regex: a quantifier that is not behind an atom or a group";
+        if (ch == '(')
+        {
+            ++c.i;
+            if (const char *why = regex_ext_group(c, A))
+                return why;
+        }
+        else if (const char *why = regex_ext_atom(c, A))
+            return why;
+        if (const char *why = regex_set_cat(S, A, T))
+            return why;
+        S = T;
+        any = true;
+    }
+    if (!any)
+        return (*bol || *eol) ? "regex: ^, $ and ^$ on their own match the empty string: kept on krep's regex_search"
+                              : "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
+    for (uint32_t k = 0; k < S.n; ++k)
+        if (S.s[k].L == 0)
+            return kRegexExtEmpty;
+    return nullptr;
+}
+inline bool regex_class_holds_nl(const uint8_t cls[32]) { return ((cls['\n' >> 3] >> ('\n' & 7)) & 1u) != 0; }
+// can an occurrence of branch j start d bytes into an occurrence of branch i when every branch stands between the same anchors.
+// d == 0 (the same start) is never ruled out by an anchor.  d >= 1 under ^: the byte in front of j lies inside i.  Under $: the byte
+// behind the occurrence that ends first lies inside the other one.
+inline bool regex_branches_overlap_anchored(const krep_gpu_regex_info_t &bi, const krep_gpu_regex_info_t &bj, uint32_t d, bool bol, bool eol)
+{
+    if (!regex_branches_overlap(bi, bj, d))
+        return false;
+    if (d == 0)
+        return true;
+    if (bol && !regex_class_holds_nl(bi.classes[d - 1]))
+        return false;
+    if (eol && bi.L - d < bj.L && !regex_class_holds_nl(bj.classes[bi.L - d]))
+        return false;
+    if (eol && d + bj.L < bi.L && !regex_class_holds_nl(bi.classes[d + bj.L]))
+        return false;
+    return true;
+}
+inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu_regex_ext_t *out)
+{
+    if (!p->use_regex)
+        return "not a regex search (use_regex is not set)";
+    if (p->whole_word)
+        return "regex with -w: the CLI compiles \\bPATTERN\\b, a library caller PATTERN, and the operator sees neither compiled "
+               "expression: kept on krep's regex_search";
+    if (MB_CUR_MAX > 1)
+        return "regex in a multibyte locale (the process called setlocale): libc matches characters there, not bytes: kept on "
+               "krep's regex_search (krep itself runs in the C locale)";
+    if (p->num_patterns > 1 && !(p->patterns && p->pattern_lens))
+        return "several patterns announced but patterns / pattern_lens are NULL";
+    RegexSeqSet all;
+    memset(&all, 0, sizeof all);
+    const size_t n_pat = regex_pattern_count(p);
+    bool first = true;
+    for (size_t k = 0; k < n_pat; ++k)
+    {
+        RegexExtCursor c{nullptr, 0, 0, p->case_sensitive};
+        regex_pattern_at(p, k, &c.pat, &c.n);
+        if (!c.pat)
+            return "no pattern";
+        if (c.n == 0)
+            return "an empty regex matches the empty string: kept on krep's regex_search";
+        if (c.n > 1024)
+            return "regex pattern longer than 1024 bytes";
+        for (size_t i = 0; i < c.n; ++i)
+            if (c.pat[i] < 0x01 || c.pat[i] > 0x7f)
+                return "regex pattern holds a byte outside 0x01-0x7F";
+        for (;;)
+        {
+            RegexSeqSet S;
+            int bol, eol;
+            if (const char *why = regex_ext_branch(c, S, &bol, &eol))
+                return why;
+            if (first)
+            {
+                out->bol = bol;
+                out->eol = eol;
+                first = false;
+            }
+            else if (bol != out->bol || eol != out->eol)
+                return "regex alternation: ^ or $ in a branch (anchors inside an alternation): kept on krep's regex_search";
+            if (const char *why = regex_set_union(all, S))
+                return why;
+            if (c.i >= c.n)
+                break;
+            ++c.i; // the '|'
+            if (c.i >= c.n)
+                return "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
+        }
+    }
+    const uint32_t extra = (uint32_t)(out->bol + out->eol);
+    krep_gpu_regex_alt_t &alt = out->alt;
+    alt.Lmin = kRegexMaxL;
+    uint32_t places = 0;
+    for (uint32_t b = 0; b < all.n; ++b)
+    {
+        const uint32_t L = all.s[b].L;
+        if (L + extra > kRegexMaxL)
+            return kRegexExtTooLong;
+        alt.Lmin = L < alt.Lmin ? L : alt.Lmin;
+        alt.Lmax = L > alt.Lmax ? L : alt.Lmax;
+        alt.total_L += L;
+        places += L + extra;
+    }
+    if (places > kRegexMaxTotalL)
+        return kRegexExtTooWide;
+    alt.n_branches = all.n;
+    for (uint32_t b = 0; b < all.n; ++b)
+    {
+        alt.branch[b] = all.s[b];
+        regex_seq_finish(&alt.branch[b], false, false); // (each branch what krep_gpu_regex_compile() makes of it alone)
+    }
+    for (uint32_t i = 0; i < alt.n_branches && !alt.cross_overlap; ++i)
+        for (uint32_t j = 0; j < alt.n_branches && !alt.cross_overlap; ++j)
+            for (uint32_t d = i == j ? 1u : 0u; d < alt.branch[i].L && !alt.cross_overlap; ++d)
+                alt.cross_overlap = regex_branches_overlap_anchored(alt.branch[i], alt.branch[j], d, out->bol != 0, out->eol != 0) ? 1 : 0;
+    return nullptr;
+}
+// krep_gpu_regex_compile_ext: NULL and *out filled, or the refusal and *out zeroed
+inline const char *regex_compile_ext(const search_params_t *p, krep_gpu_regex_ext_t *out)
+{
+    if (!p || !out)
+        return "NULL params";
+    memset(out, 0, sizeof *out);
+    const char *why = regex_compile_ext_branches(p, out);
     if (why)
         memset(out, 0, sizeof *out);
     return why;

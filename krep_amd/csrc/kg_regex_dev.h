@@ -17,8 +17,11 @@ struct RegexProg
     u32 *d_table = nullptr; // T[256] over the extended sequence: bit 0 is ^'s newline when bol, bit bol + j class j, bit bol + L $'s newline
     // an alternation (krep_gpu_regex_compile_alt took the search, the anchored compiler did not): branch i in bits [o_i, o_i + L_i) of
     // the state, T[b] bit o_i + j set iff b is in C[i][j]; init = every o_i, fin = every o_i + L_i - 1
+    // alt_bol / alt_eol (krep_gpu_regex_compile_ext): every branch has the place { '\n' } in front of / behind its classes, so branch i
+    // takes L_i + alt_bol + alt_eol bits
     bool is_alt = false;
     krep_gpu_regex_alt_t alt{};
+    u32 alt_bol = 0, alt_eol = 0;
     u32 init = 0, fin = 0;
 };
 

@@ -54,6 +54,9 @@ class Engine:
         if hasattr(L, "krep_gpu_regex_compile_alt"):  # (likewise)
             L.krep_gpu_regex_compile_alt.restype = C.c_int
             L.krep_gpu_regex_compile_alt.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexAlt)]
+        if hasattr(L, "krep_gpu_regex_compile_ext"):  # (likewise)
+            L.krep_gpu_regex_compile_ext.restype = C.c_int
+            L.krep_gpu_regex_compile_ext.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexExt)]
         L.krep_gpu_can_accelerate.restype = C.c_int
         L.krep_gpu_can_accelerate.argtypes = [C.POINTER(abi.SearchParams)]
         L.krep_gpu_config_default.restype = None
@@ -312,6 +315,15 @@ class Engine:
         compiler only for what that one refuses."""
         info = abi.RegexAlt()
         if self.lib.krep_gpu_regex_compile_alt(params.ref, C.byref(info)):
+            raise KrepGpuError(self.last_error())
+        return info
+
+    def regex_compile_ext(self, params: abi.Params) -> "abi.RegexExt":
+        """krep_gpu_regex_compile_ext: ?, {n}, {n,m}, inner groups and a ^ / $ around every top-level branch, expanded into up to 8
+        class sequences (alt, over the real classes) between the line anchors bol / eol.  Every search asks regex_compile_anchored()
+        first, then regex_compile_alt(), then this compiler."""
+        info = abi.RegexExt()
+        if self.lib.krep_gpu_regex_compile_ext(params.ref, C.byref(info)):
             raise KrepGpuError(self.last_error())
         return info
 

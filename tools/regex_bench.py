@@ -1,4 +1,4 @@
-"""krep -E on the device (kg_regex.hip, kg_regex_alt.hip) beside the literal scan and beside the reference's regex_search on the CPU.
+"""krep -E on the device (kg_regex.hip, kg_regex_alt.hip; the last rows: what krep_gpu_regex_compile_ext expands) beside the literal scan and beside the reference's regex_search on the CPU.
 One kind-2 haystack with `Sherlock` planted every 10 000 bytes, resident in HBM; hipEvent times, the median of 10 steady scans
 after 2 warm-up scans.  The yardstick comes first: the literal plan for `Sherlock` on the same buffer.  Then the regex patterns,
 each with its ratio to the yardstick; and regex_search itself (oracle/_ref, one thread) on the first 256 MiB of the host twin.
@@ -65,9 +65,16 @@ JOBS = [(b"Sherl[oO]ck", "anchor path", ("count", "records")), (b"[A-Z][a-z]{7}"
         (b"^[A-Z][a-z]{7}$", "table path, ^ and $", ("count", "records")),
         # alternations (kg_regex_alt.hip): each row beside the table-path row of [A-Z][a-z]{7} on the same buffer (-c beside its count row)
         (b"Sherlock|Watson|Holmes", "alternation, 3 branches", ("count", "records", "-c")),
-        (b"[A-Z][a-z]{7}|[0-9]{4}", "alternation, [0-9]{4} overlaps itself: greedy pass", ("count", "records", "-c"))]
+        (b"[A-Z][a-z]{7}|[0-9]{4}", "alternation, [0-9]{4} overlaps itself: greedy pass", ("count", "records", "-c")),
+        # what krep_gpu_regex_compile_ext expands: each row beside Sherlock|Watson|Holmes above, the unanchored kernel with the same
+        # number of branches (the first row runs that kernel, the other two its anchored instantiations)
+        (b"Sherlo?ck|Watson", "expanded: Sherlck, Sherlock, Watson", ("count", "records", "-c")),
+        (b"^(Sherlock|Watson|Holmes)", "alternation between anchors, ^", ("count", "records", "-c")),
+        (b"(Sherlock|Watson|Holmes)$", "alternation between anchors, $", ("count", "records", "-c"))]
 TWIN = {b"^Sherlock": b"Sherlock", b"[a-z]{4}$": b"[a-z]{4}", b"^[A-Z][a-z]{7}$": b"[A-Z][a-z]{7}",
-        b"Sherlock|Watson|Holmes": b"[A-Z][a-z]{7}", b"[A-Z][a-z]{7}|[0-9]{4}": b"[A-Z][a-z]{7}"}
+        b"Sherlock|Watson|Holmes": b"[A-Z][a-z]{7}", b"[A-Z][a-z]{7}|[0-9]{4}": b"[A-Z][a-z]{7}",
+        b"Sherlo?ck|Watson": b"Sherlock|Watson|Holmes", b"^(Sherlock|Watson|Holmes)": b"Sherlock|Watson|Holmes",
+        b"(Sherlock|Watson|Holmes)$": b"Sherlock|Watson|Holmes"}
 took = {}
 for pat, what, modes in JOBS:
     for mode in modes:

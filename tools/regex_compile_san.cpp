@@ -1,7 +1,7 @@
 // tools/regex_compile_san.cpp — the -E pattern compiler (krep_amd/csrc/kg_regex_compile.h: host code, no HIP) as a stand-alone
 // program for AddressSanitizer / UBSan:  python tools/sanitize.py regex   (or by hand:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer tools/regex_compile_san.cpp -o regex_compile_san).
-// It feeds the three entry points' compilers (the alternation compiler with one and with two patterns) accepted patterns, every refusal, and 200 000 pattern strings drawn from the bytes the
+// It feeds the four entry points' compilers (the alternation compiler with one and with two patterns) accepted patterns, every refusal, and 200 000 pattern strings drawn from the bytes the
 // grammar cares about (^ $ | ( ) among them), each copied into a heap block of exactly its length so that a read past the pattern is a report.
 #include <cstdio>
 #include <cstdlib>
@@ -60,6 +60,35 @@ static int compile_alt(const std::vector<std::string> &pats, bool cs, bool ww, k
     p.max_count = SIZE_MAX;
     *why = kg::regex_compile_alt(&p, alt);
     (void)kg::regex_has_alt_syntax(&p);
+    for (char *h : heap)
+        free(h);
+    return *why ? 2 : 0;
+}
+// krep_gpu_regex_compile_ext's compiler over one or several patterns, each in a heap block of exactly its length
+static int compile_ext(const std::vector<std::string> &pats, bool cs, bool ww, krep_gpu_regex_ext_t *ext, const char **why)
+{
+    std::vector<char *> heap;
+    std::vector<const char *> ptrs;
+    std::vector<size_t> lens;
+    for (const std::string &s : pats)
+    {
+        heap.push_back((char *)malloc(s.size() ? s.size() : 1));
+        memcpy(heap.back(), s.data(), s.size());
+        ptrs.push_back(heap.back());
+        lens.push_back(s.size());
+    }
+    search_params_t p;
+    memset(&p, 0, sizeof p);
+    p.pattern = ptrs[0];
+    p.pattern_len = lens[0];
+    p.patterns = ptrs.data();
+    p.pattern_lens = lens.data();
+    p.num_patterns = pats.size();
+    p.case_sensitive = cs;
+    p.use_regex = true;
+    p.whole_word = ww;
+    p.max_count = SIZE_MAX;
+    *why = kg::regex_compile_ext(&p, ext);
     for (char *h : heap)
         free(h);
     return *why ? 2 : 0;
@@ -240,5 +269,84 @@ int main()
     }
     printf("regex_compile_san: %u random patterns taken, %u refused, %u taken with anchors allowed, %u taken as alternations, %d failures\n", taken,
            refused, ataken, alt_taken, bad);
+    // the expanding compiler: accepted shapes with their fields, every refusal, and random patterns of its grammar
+    krep_gpu_regex_ext_t ext;
+    struct { std::vector<std::string> pats; int bol, eol; unsigned nb, Lmin, Lmax, total; int overlap; } ext_ok[] = {
+        {{"colou?r"}, 0, 0, 2, 5, 6, 11, 0}, {{"https?://"}, 0, 0, 2, 7, 8, 15, 0}, {{"[0-9]{1,3}%"}, 0, 0, 3, 2, 4, 9, 1},
+        {{"x(a|bc)y"}, 0, 0, 2, 3, 4, 7, 0}, {{"(ab){2}"}, 0, 0, 1, 4, 4, 4, 1}, {{"(ab){2}|b{0,2}a"}, 0, 0, 4, 1, 4, 10, 1},
+        {{"^(ERROR|WARN|FATAL)"}, 1, 0, 3, 4, 5, 14, 0}, {{"\\.(jpg|png)$"}, 0, 1, 2, 4, 4, 8, 0}, {{"^GET", "^POST[0-9]"}, 1, 0, 2, 3, 5, 8, 0},
+        {{"^(a{14}|b{14})$"}, 1, 1, 2, 14, 14, 28, 0}, {{"(x|[a-c]{15})$"}, 0, 1, 2, 1, 15, 16, 0}, {{"^[ab]{1,3}$"}, 1, 1, 3, 1, 3, 6, 1},
+        {{"^(a|bc)d?$"}, 1, 1, 4, 1, 3, 8, 1}, {{"(a|b|c|d)(e|f)|ae"}, 0, 0, 8, 2, 2, 16, 0}, {{"ab|cd"}, 0, 0, 2, 2, 2, 4, 0}, {{"^ab$"}, 1, 1, 1, 2, 2, 2, 0}};
+    for (const auto &c : ext_ok)
+        for (int cs = 0; cs < 2; ++cs)
+            if (compile_ext(c.pats, cs != 0, false, &ext, &why) != 0 || ext.bol != c.bol || ext.eol != c.eol || ext.alt.n_branches != c.nb ||
+                ext.alt.Lmin != c.Lmin || ext.alt.Lmax != c.Lmax || ext.alt.total_L != c.total || ext.alt.cross_overlap != c.overlap ||
+                ext.alt.Lmax + ext.bol + ext.eol > 16 || ext.alt.total_L + ext.alt.n_branches * (ext.bol + ext.eol) > 32)
+            {
+                printf("FAIL: ext %s: %s\n", c.pats[0].c_str(), why ? why : "wrong fields");
+                ++bad;
+            }
+    const char *ext_no[] = {"ab*", "a+b", "a{2,}", "(a|b)*c", "a?{2}", "a{2}{3}", "a?\?", "a?", "(a|b)?", "a{0}", "a{0,1}", "^$", "^", "$", "x(a|)y", "x()y", "a|",
+                            "|a", "a||b", "x((a))", "(a(b|c))d", "x(a", "a)b", "(a|b", "x(^a|b)", "(a|b$)x", "(^a)|(^b)", "a^b", "a$b", "^^a", "a$$", "^a|b",
+                            "a|b$", "[ab]{1,9}", "(a|b)(c|d)(e|f)(g|h)", "a{17}", "^a{16}", "^a{15}$", "a{9}(b|c)a{8}", "a{16}|b{16}|c", "^(a{15}|b{15}|c)",
+                            "caf\xe9?", "a\\b?", "[ab?", "ab?\\", "{2}a", "a|?b", "(?a)", "^{2}a", "a{2", "a{x}", "a{3,2}", "", "(", ")", "a{1,", "a{1,2", "a{,2}",
+                            "a{99999999999,3}", "a{1,99999999999}", "(a{1,1000}){1,1000}", "(a?){1,1000}", "((", "a(", "a(|", "a(b|", "a(b\\"};
+    for (const char *s : ext_no)
+        if (compile_ext({s}, true, false, &ext, &why) != 2 || !why || !*why || ext.alt.n_branches != 0 || ext.bol || ext.eol)
+        {
+            printf("FAIL: ext %s accepted\n", s);
+            ++bad;
+        }
+    if (compile_ext({"colou?r"}, true, true, &ext, &why) != 2 || compile_ext({"a?b", ""}, true, false, &ext, &why) != 2 ||
+        compile_ext({"a", "^b"}, true, false, &ext, &why) != 2 || compile_ext({std::string(1100, 'a') + "?b"}, true, false, &ext, &why) != 2)
+    {
+        printf("FAIL: ext -w, an empty pattern, mixed anchors or an overlong pattern accepted\n");
+        ++bad;
+    }
+    const char *pieces[] = {"a", "b", "[ab]", "[^a]", ".", "\\.", "\n", "?", "{2}", "{1,2}", "{0,3}", "{2,}", "(", ")", "|", "^", "$", "*", "+", "{", "}", ",", "1", "[", "]", "\\"};
+    unsigned ext_taken = 0, ext_refused = 0;
+    for (int i = 0; i < 200000; ++i)
+    {
+        std::vector<std::string> pats(1);
+        s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+        const int len = (int)(s % 10);
+        for (int k = 0; k < len; ++k)
+        {
+            s ^= s << 13; s ^= s >> 7; s ^= s << 17;
+            const unsigned r = (unsigned)(s % 40);
+            pats.back() += pieces[r < 14 ? r % 7 : (r - 14) % (sizeof pieces / sizeof *pieces)]; // (atoms more often than the rest)
+            if ((s >> 50) % 23 == 0)
+                pats.emplace_back(); // several patterns every now and then
+        }
+        if (compile_ext(pats, (s >> 40) & 1, false, &ext, &why) == 0)
+        {
+            ++ext_taken;
+            const unsigned extra = (unsigned)(ext.bol + ext.eol);
+            krep_gpu_regex_alt_t plain = ext.alt; // (a branch's self_overlap is that of the sequence alone, cross_overlap knows the anchors)
+            for (unsigned b = 0; extra && b < plain.n_branches; ++b)
+                plain.branch[b].self_overlap = 0;
+            if (!alt_consistent(plain) || ext.alt.Lmax + extra > 16 || ext.alt.total_L + ext.alt.n_branches * extra > 32 || (ext.bol | ext.eol) >> 1)
+            {
+                printf("FAIL: inconsistent expansion for a random pattern\n");
+                ++bad;
+            }
+            // what the alternation compiler takes, this one takes as the same alternation
+            if (compile_alt(pats, (s >> 40) & 1, false, &alt, &why) == 0 && (extra || memcmp(&alt, &ext.alt, sizeof alt)))
+            {
+                printf("FAIL: the expanding compiler differs from the alternation compiler on a pattern both take\n");
+                ++bad;
+            }
+        }
+        else
+        {
+            ++ext_refused;
+            if (ext.alt.n_branches != 0 || compile_alt(pats, (s >> 40) & 1, false, &alt, &why) == 0)
+            {
+                printf("FAIL: the expanding compiler refuses what the alternation compiler takes, or leaves a refused struct filled\n");
+                ++bad;
+            }
+        }
+    }
+    printf("regex_compile_san: expanding compiler: %u random patterns of its grammar taken, %u refused, %d failures in all\n", ext_taken, ext_refused, bad);
     return bad ? 1 : 0;
 }
