@@ -806,7 +806,9 @@ int krep_gpu_format_matches(const void *d_text, size_t text_len, const match_pos
  *   item and belongs to whoever scanned it), so there is no own_lo / own_hi.  MATCH is text[start, min(end, global_len)).
  *   Refused (2) before any byte of the text is read through the list: a list not ascending in start, a record with start outside
  *   [global_base, global_base + text_len) or end < start, or a match that outruns the buffer (min(end, global_len) > global_base +
- *   text_len: a match is no longer than the longest pattern, so the caller can always size its halo; nothing is "incomplete").
+ *   text_len: a match is no longer than the longest match of the search -- the longest pattern of a literal search, L / Lmax of the
+ *   regex compilers under -E, where `a{16}` is five pattern bytes and sixteen text bytes -- so the caller can always size its halo;
+ *   nothing is "incomplete").
  * LINE: the true number is 1 + newlines_before + the newlines in d_text[0, start - global_base); a start ON a '\n' belongs to the line
  *   that newline ends.  The reference's stale number (above) applies when stale_rule != 0, last_newline1 != 0 and start >=
  *   last_newline1 — decided by OFFSET, the window does not know the text's newline total.  Such a record prints S: the largest true

@@ -599,6 +599,27 @@ class Plan:
             raise KrepGpuError("krep_gpu_scan_device failed: " + self.eng.last_error())
         return out
 
+    def longest_match(self) -> int:
+        """The most text bytes that decide one match of the plan: what the output drivers size a halo, a staging length, records_hi
+        and a per-item guess by.  A literal plan: its longest pattern.  A regex plan (krep -E): NOT the length of the pattern string
+        (`q[a-c]{15}` is 10 pattern bytes and 16 text bytes) but L / Lmax of the compiler that takes the search, asked in the order
+        every search asks them (anchored, then alternation, then the expanding one), plus the newline a `$` looks at behind the
+        match: a window must hold that byte too, or the scan refuses it."""
+        s = self.params.s
+        if not s.use_regex:
+            return max(int(x) for x in s.pattern_lens[: s.num_patterns]) if s.num_patterns else int(s.pattern_len)
+        eng = self.eng
+        try:
+            info = eng.regex_compile_anchored(self.params)
+            return int(info.seq.L) + int(bool(info.eol))
+        except KrepGpuError:
+            pass
+        try:
+            return int(eng.regex_compile_alt(self.params).Lmax)
+        except KrepGpuError:
+            info = eng.regex_compile_ext(self.params)
+            return int(info.alt.Lmax) + int(bool(info.eol))
+
     def grep_lines(self, d_text: int, n: int, filename=None, max_count=None, stream: int = 0, color=False) -> bytes:
         """What `krep [-m N] PATTERN FILE` prints (colour off) for the n bytes at d_text: the scan with records, the cut to the
         first max_count records in emission order (search_file()), the (start, end) order for a multi-pattern list, and the
@@ -650,7 +671,7 @@ class Plan:
     def grep_lines_pieces(self, text, piece_bytes: int, filename=None, color=False, halo_bytes: int = 4096) -> bytes:
         """grep_lines for a text on the HOST that never lies on the device as a whole: it is staged piece by piece into ONE device
         buffer of 1 + piece_bytes + halo bytes (the byte of left context, the piece, the halo), every piece is scanned with start
-        ownership up to records_hi = buffer end - (longest pattern - 1) (the text's end where the buffer ends it), a multi-pattern
+        ownership up to records_hi = buffer end - (longest_match() - 1) (the text's end where the buffer ends it), a multi-pattern
         list is put in (start, end) order, and krep_gpu_format_lines_window formats the lines that START in the piece.  A line the
         call reports as incomplete (it outruns the halo) is staged again as a window of its own, its reach doubled until it is
         complete.  A line of the piece that outruns the halo and holds no record in front of records_hi is one the call cannot
@@ -682,7 +703,7 @@ class Plan:
         if eng.split_mode(self.params, total) != abi.SPLIT_PIECES:
             raise KrepGpuError("grep_lines_pieces: the match set of this search cannot be cut into independent pieces "
                                "(krep_gpu_split_mode)")
-        longest = max(int(x) for x in s.pattern_lens[: s.num_patterns]) if s.num_patterns else int(s.pattern_len)
+        longest = self.longest_match()
         halo = max(int(halo_bytes), longest)  # (records_hi >= own_hi)
         name = None if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
         fmt = line_format(name, bool(color))
@@ -817,9 +838,9 @@ class Plan:
             eng.order_by_start(pos.data_ptr(), m, n, stream)
         name = b"" if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
         fmt = match_format(name if filename is not None else None, color)
-        longest = max(int(x) for x in self.params.s.pattern_lens[: self.params.s.num_patterns])
+        longest = self.longest_match()
         per_item = fmt.prefix_len + fmt.before_number_len + fmt.after_number_len + fmt.after_match_len + 20 + 2 + longest
-        guess = m * per_item + 4096  # enough by construction; the second call serves a list whose records are longer than a pattern
+        guess = m * per_item + 4096  # enough by construction (no record is longer than longest_match()); the second call is a backstop
         buf = torch.empty(guess, dtype=torch.uint8, device="cuda")
         res = eng.format_matches(d_text, n, pos.data_ptr(), m, limit, fmt, buf.data_ptr(), guess, stream)
         if res.overflow:
@@ -831,7 +852,7 @@ class Plan:
     def grep_only_matching_pieces(self, text, piece_bytes: int, filename=None, color=False) -> bytes:
         """grep_only_matching for a text on the HOST that never lies on the device as a whole; returns the bytes of
         grep_only_matching on the resident text.  The text is cut into pieces of piece_bytes; piece [lo, hi) is staged as
-        [max(lo - 1, 0), min(hi + longest pattern, total)) into ONE reused device buffer (the byte of left context for -w, and
+        [max(lo - 1, 0), min(hi + longest_match(), total)) into ONE reused device buffer (the byte of left context for -w, and
         behind the piece a match that starts on its last byte with the byte -w looks at behind it).  Under -o many single
         literals couple a match to the one before it (krep_gpu_split_mode() = CHAIN), so the pieces are scanned IN TEXT ORDER
         through scan_seq, each taking the carry of the one before it (the counting scan and the recording scan of a piece take the
@@ -880,7 +901,7 @@ class Plan:
             raise KrepGpuError("grep_only_matching_pieces: this search takes the whole text in one window (krep_gpu_split_mode)")
         if limit == 0 or total == 0:
             return b""
-        longest = max(int(x) for x in s.pattern_lens[: s.num_patterns]) if s.num_patterns else int(s.pattern_len)
+        longest = self.longest_match()
         name = None if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
         fmt = match_format(name, bool(color))
         per_item = fmt.prefix_len + fmt.before_number_len + fmt.after_number_len + fmt.after_match_len + 20 + 2 + longest
@@ -909,7 +930,7 @@ class Plan:
             win = abi.MatchesWindow(base, total, count_to, chain["nl"], last_nl1, chain["stale"], int(rule))
             out = grown("out", n * per_item + 4096)
             res = eng.format_matches_window(d_text, blen, win, d_pos, n, abi.SIZE_MAX, fmt, out.data_ptr(), out.numel())
-            if res.matches.overflow:  # (a record longer than a pattern)
+            if res.matches.overflow:  # (a backstop: per_item holds the longest match)
                 out = grown("out", int(res.matches.out_bytes))
                 res = eng.format_matches_window(d_text, blen, win, d_pos, n, abi.SIZE_MAX, fmt, out.data_ptr(), out.numel())
                 assert not res.matches.overflow

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import line_model as lm
+import only_matching_model as om
 import regex_model
 import regex_ref
 import regex_skip_model as sm
@@ -295,7 +296,10 @@ def test_grep_lines_of_a_regex_plan(gpu):
         plan = gpu.plan(regex_ref.params(pat, **kw), only_matching=True)  # (-o changes nothing for regex_search: the same records)
         try:
             out = plan.grep_only_matching(d_text, text.size)
-            assert out.count(b"\n") == (want[0] if mc is None else min(mc, want[0])), (pat, mc)
+            assert out == om.grep_o_output(text.tobytes(), want[1], None, False, mc), (pat, mc)
+            assert out.count(b"\n") == (want[0] if mc is None else min(mc, want[0])) > 0, (pat, mc)
+            out = plan.grep_only_matching(d_text, text.size, filename=b"f.txt", color=True)
+            assert out == om.grep_o_output(text.tobytes(), want[1], b"f.txt", True, mc), (pat, mc)
         finally:
             plan.close()
     del hold
