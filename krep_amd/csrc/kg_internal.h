@@ -11,6 +11,7 @@
 #include "../../include/krep_gpu.h"
 #include "../../include/krep_gpu_debug.h" // (test hooks, exported by the same library)
 #include "kg_common.h"
+#include "kg_regex_compile.h"
 
 namespace kg {
 
@@ -223,21 +224,10 @@ krep_gpu_config_t current_config(); // the calling thread's override, else the p
 int mirror_top(const search_params_t *p, const krep_gpu_config_t &c);
 int mirror_effective(int top, const search_params_t *p, size_t text_len);
 const char *unsupported_reason(const search_params_t *p, const krep_gpu_config_t &c); // NULL = accelerated
-// kg_regex_compile.h behind a one-entry cache per thread: an operator call asks the selector, the executor, the split rule and (on a
-// cache miss) the plan about the same pattern, and one compile is up to 16 regcomp calls and 4096 regexec probes.  The key is
-// everything the compilers read (the bytes and the length of every pattern, case, -w, whether the locale is multibyte).
-// The anchored compiler is asked first; only what it refuses goes to the alternation compiler (is_alt: that one took it).  The
-// refusal of a search both refuse is the alternation compiler's when the search says an alternation (several patterns, or a '|'
-// or '(' outside brackets and not behind a backslash), else the anchored compiler's.  What both refuse goes to the expanding
-// compiler (krep_gpu_regex_compile_ext: ?, {n,m}, inner groups, anchored alternations), whose result is an alternation too, between
-// the line anchors alt_bol / alt_eol; its refusal is the one reported only when it comes from its own limits.
-struct RegexCompiled
-{
-    bool is_alt = false;
-    krep_gpu_regex_anchored_t seq{}; // !is_alt
-    krep_gpu_regex_alt_t alt{};      // is_alt
-    int alt_bol = 0, alt_eol = 0;    // is_alt: ^ in front of / $ behind every branch (the expanding compiler only)
-};
+// regex_compile_search (kg_regex_compile.h: the -E compilers in the order every search asks them, RegexCompiled their verdict) behind a
+// one-entry cache per thread: an operator call asks the selector, the executor, the split rule and (on a cache miss) the plan about
+// the same pattern, and one compile is up to 16 regcomp calls and 4096 regexec probes.  The key is everything the compilers read
+// (the bytes and the length of every pattern, case, -w, whether the locale is multibyte).
 const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out); // NULL: taken; else the refusal
 constexpr int kSplitWhole = 0, kSplitPieces = 1, kSplitChain = 2; // enum krep_gpu_split (include/krep_gpu.h)
 int split_mode(const search_params_t *p, const krep_gpu_config_t &c, size_t text_len);

@@ -162,36 +162,7 @@ extern "C" const char *krep_gpu_algorithm_name(int a)
 // (Round 3: -c through simd_sse42_search / kmp_search with a '\n' inside the pattern — refused until then — is reproduced by a
 //  walk over the ordered occurrence list, kg_greedy.hip (3).)
 namespace kg {
-// the three compilers in the order every search asks them (kg_internal.h)
-static const char *regex_compile_both(const search_params_t *p, RegexCompiled *out)
-{
-    out->is_alt = false;
-    out->alt_bol = out->alt_eol = 0;
-    const char *why = regex_compile_anchored(p, &out->seq);
-    if (!why)
-        return nullptr;
-    if (!p || !p->use_regex)
-        return why;
-    const char *why_alt = regex_compile_alt(p, &out->alt);
-    if (!why_alt)
-    {
-        out->is_alt = true;
-        return nullptr;
-    }
-    krep_gpu_regex_ext_t ext;
-    const char *why_ext = regex_compile_ext(p, &ext);
-    if (!why_ext)
-    {
-        out->is_alt = true;
-        out->alt = ext.alt;
-        out->alt_bol = ext.bol;
-        out->alt_eol = ext.eol;
-        return nullptr;
-    }
-    // the reason of a search all three refuse: what it was before the expanding compiler, unless only that one's own limits are in the way
-    const char *before = regex_has_alt_syntax(p) ? why_alt : why;
-    return regex_ext_own_limit(why_ext) && !strstr(before, "more than") ? why_ext : before;
-}
+// regex_compile_search (kg_regex_compile.h) behind the calling thread's one-entry cache (kg_internal.h)
 const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out)
 {
     struct Entry
@@ -203,9 +174,9 @@ const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out)
     };
     static thread_local Entry e;
     if (!p || !out || !p->use_regex)
-        return out ? regex_compile_both(p, out) : "NULL params";
+        return out ? regex_compile_search(p, out) : "NULL params";
     if (p->num_patterns > 1 && !(p->patterns && p->pattern_lens))
-        return regex_compile_both(p, out);
+        return regex_compile_search(p, out);
     std::string key;
     const size_t np = regex_pattern_count(p);
     for (size_t k = 0; k < np; ++k)
@@ -214,7 +185,7 @@ const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out)
         size_t n;
         regex_pattern_at(p, k, &pat, &n);
         if (!pat || n > 1024)
-            return regex_compile_both(p, out);
+            return regex_compile_search(p, out);
         key.append((const char *)&n, sizeof n);
         key.append((const char *)pat, n);
     }
@@ -222,7 +193,7 @@ const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out)
     if (!(e.valid && e.cs == p->case_sensitive && e.ww == p->whole_word && e.mb == mb && e.key == key))
     {
         e.valid = false;
-        e.why = regex_compile_both(p, &e.rc);
+        e.why = regex_compile_search(p, &e.rc);
         e.cs = p->case_sensitive; e.ww = p->whole_word; e.mb = mb;
         e.key.swap(key);
         e.valid = true;

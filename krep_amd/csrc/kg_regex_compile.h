@@ -1,11 +1,20 @@
-// kg_regex_compile.h — the pattern compiler of the -E path (krep_gpu_regex_compile, include/krep_gpu.h): a TOKENISER that cuts an
-// extended regular expression into a fixed number of one-byte atoms, and libc's own regcomp / regexec asked about every atom
-// and every byte.  Host code without any HIP in it, so that a stand-alone program can run it under the sanitizers
-// (tools/regex_compile_san.cpp).  It never sees a text: what it produces is a table, the search is the kernel's (kg_regex.hip).
-// krep_gpu_regex_compile_alt (at the end of this file) cuts an alternation at its top-level '|', takes one pair of parentheses
-// off a branch and hands every branch to the same tokeniser (kg_regex_alt.hip scans what it makes).
-// krep_gpu_regex_compile_ext (behind it) EXPANDS ?, {n,m} and inner groups into such an alternation and takes a ^ in front of and
-// a $ behind every top-level branch, the same pair on all of them.
+// kg_regex_compile.h — the pattern compilers of the -E path (include/krep_gpu.h) and the order a search asks them in.  Host code
+// without any HIP in it, so that a stand-alone program can run it under the sanitizers and pin its answers
+// (tools/regex_compile_san.cpp).  It never sees a text: what it produces is a table, the search is the kernels' (kg_regex.hip,
+// kg_regex_alt.hip).  In the order of the file:
+//   the rules every compiler shares, one copy of each: what a search and a pattern must be (regex_check_search, regex_check_pattern),
+//     where an atom ends (regex_atom), a repetition count (regex_count), an atom's class from libc's own regcomp / regexec
+//     (regex_probe_atom), when two sequences overlap (regex_branches_overlap_anchored), identical class tables merging
+//     (regex_branch_add), and the fields behind the classes (regex_seq_finish, regex_alt_finish);
+//   krep_gpu_regex_compile / _anchored: a TOKENISER that cuts an expression into a fixed number of one-byte atoms;
+//   krep_gpu_regex_compile_alt: cuts an alternation at its top-level '|', takes one pair of parentheses off a branch and hands
+//     every branch to that tokeniser;
+//   krep_gpu_regex_compile_ext: EXPANDS ?, {n,m} and inner groups into such an alternation and takes a ^ in front of and a $ behind
+//     every top-level branch, the same pair on all of them;
+//   regex_compile_search: the three of them that take a search, in the order every search asks them, and the reason it reports.
+// Each compiler reports the first fault IT meets, and they meet faults in different orders (the tokeniser probes atoms only after
+// the whole pattern is cut, the expanding compiler as it goes, the alternation compiler walks a branch's parentheses before it
+// tokenises the branch): the refusal strings are public, so the shared rules sit under four control flows.
 #pragma once
 #include <regex.h>
 #include <stdint.h>
@@ -16,10 +25,43 @@
 
 namespace kg {
 
-constexpr uint32_t kRegexMaxL = 16;
+constexpr uint32_t kRegexMaxL = 16, kRegexMaxBranches = 8, kRegexMaxTotalL = 32;
 
-// one atom of the pattern: bytes [at, at + len) of it, `rep` times in a row
-struct RegexAtom { size_t at, len; uint32_t rep; };
+// ---- the shared rules -----------------------------------------------------------------------------------------------------------
+// What every compiler asks of the search.  several_ok: the compiler takes several patterns (the alternation and the expanding one).
+inline const char *regex_check_search(const search_params_t *p, bool several_ok)
+{
+    if (!p->use_regex)
+        return "not a regex search (use_regex is not set)";
+    if (!several_ok && p->num_patterns > 1)
+        return "several regex patterns are an alternation (the CLI joins them with '|'): kept on krep's regex_search";
+    if (p->whole_word)
+        return "regex with -w: the CLI compiles \\bPATTERN\\b, a library caller PATTERN, and the operator sees neither compiled "
+               "expression: kept on krep's regex_search";
+    // In a multibyte locale libc's regexec matches CHARACTERS: '.', a negated or named class and, under REG_ICASE, even a letter
+    // take a whole multibyte sequence as one atom, so no pattern is a fixed number of BYTE classes there and one-byte probes cannot
+    // say what an atom matches.  The krep CLI never calls setlocale(): it runs in the C locale, where a character is a byte.
+    if (MB_CUR_MAX > 1)
+        return "regex in a multibyte locale (the process called setlocale): libc matches characters there, not bytes: kept on "
+               "krep's regex_search (krep itself runs in the C locale)";
+    if (several_ok && p->num_patterns > 1 && !(p->patterns && p->pattern_lens))
+        return "several patterns announced but patterns / pattern_lens are NULL";
+    return nullptr;
+}
+// ... and of every pattern
+inline const char *regex_check_pattern(const uint8_t *pat, size_t n)
+{
+    if (!pat)
+        return "no pattern";
+    if (n == 0)
+        return "an empty regex matches the empty string: kept on krep's regex_search";
+    if (n > 1024)
+        return "regex pattern longer than 1024 bytes";
+    for (size_t i = 0; i < n; ++i)
+        if (pat[i] < 0x01 || pat[i] > 0x7f)
+            return "regex pattern holds a byte outside 0x01-0x7F";
+    return nullptr;
+}
 
 inline bool regex_is_punct(uint8_t c) { return (c >= 0x21 && c <= 0x2f) || (c >= 0x3a && c <= 0x40) || (c >= 0x5b && c <= 0x60) || (c >= 0x7b && c <= 0x7e); }
 
@@ -49,6 +91,48 @@ inline size_t regex_bracket_end(const uint8_t *pat, size_t n, size_t i)
     }
     return k;
 }
+// The atom at pat[i], i < n: an ordinary byte, a backslash with the punctuation byte behind it, a bracket expression up to its ']'.
+// NULL and its length in *len, or why it is none.  A refused escape still spans *len = 2 bytes (who only looks for the operators
+// between the atoms steps over it and leaves the reason to the compiler of the branch); *len = 0: the pattern ends inside the atom.
+inline const char *regex_atom(const uint8_t *pat, size_t n, size_t i, size_t *len)
+{
+    *len = 1;
+    if (pat[i] == '\\')
+    {
+        *len = 0;
+        if (i + 1 >= n)
+            return "regex: trailing backslash";
+        *len = 2;
+        const uint8_t e = pat[i + 1];
+        if ((e >= '0' && e <= '9') || ((e | 0x20) >= 'a' && (e | 0x20) <= 'z'))
+            return "regex: a backslash in front of a letter or digit (\\b, \\w, \\1, ...) is an operator: kept on krep's regex_search";
+        if (!regex_is_punct(e))
+            return "regex: a backslash in front of a byte that is not punctuation";
+    }
+    else if (pat[i] == '[')
+    {
+        const size_t e = regex_bracket_end(pat, n, i);
+        *len = e < n ? e + 1 - i : 0;
+        if (e >= n)
+            return "regex: bracket expression without its ']'";
+    }
+    return nullptr;
+}
+// The count of a repetition, digits from pat[*k] on: its value (read up to the first digit that takes it past 1000) in *v, *k behind
+// it.  false: no digit, or the pattern ends behind the digits — malformed, like whatever the caller does not find behind the count.
+constexpr const char *kRegexMalformed = "regex: malformed repetition";
+inline bool regex_count(const uint8_t *pat, size_t n, size_t *k, uint32_t *v)
+{
+    bool digits = false;
+    *v = 0;
+    while (*k < n && pat[*k] >= '0' && pat[*k] <= '9' && *v <= 1000)
+    {
+        *v = *v * 10 + (uint32_t)(pat[*k] - '0');
+        digits = true;
+        ++*k;
+    }
+    return digits && *k < n;
+}
 
 // The class of one atom: the bytes b for which libc's regexec, with the atom compiled alone under the reference's flags
 // (krep.c:2148), matches the one-byte text b.  false: regcomp refused the atom.
@@ -75,8 +159,48 @@ inline bool regex_probe_atom(const uint8_t *atom, size_t len, bool case_sensitiv
     regfree(&re);
     return true;
 }
+constexpr const char *kRegexAtomRefused = "regex: regcomp refuses an atom of the pattern";
 
-// The fields behind the classes of a sequence whose L and classes are set: the anchor class with its bytes, and self_overlap
+inline bool regex_classes_meet(const uint8_t a[32], const uint8_t b[32])
+{
+    for (int w = 0; w < 32; ++w)
+        if (a[w] & b[w])
+            return true;
+    return false;
+}
+inline bool regex_class_holds_nl(const uint8_t cls[32]) { return ((cls['\n' >> 3] >> ('\n' & 7)) & 1u) != 0; }
+// Can an occurrence of sequence j start d bytes into an occurrence of sequence i (every class pair that lies on one byte meets) when
+// both stand between the same anchors.  d == 0 (the same start) is never ruled out by an anchor.  d >= 1 under ^: the byte in front
+// of j lies inside i.  Under $: the byte behind the occurrence that ends first lies inside the other one.
+inline bool regex_branches_overlap_anchored(const krep_gpu_regex_info_t &bi, const krep_gpu_regex_info_t &bj, uint32_t d, bool bol, bool eol)
+{
+    for (uint32_t t = 0; d + t < bi.L && t < bj.L; ++t)
+        if (!regex_classes_meet(bi.classes[d + t], bj.classes[t]))
+            return false;
+    if (d == 0)
+        return true;
+    if (bol && !regex_class_holds_nl(bi.classes[d - 1]))
+        return false;
+    if (eol && bi.L - d < bj.L && !regex_class_holds_nl(bj.classes[bi.L - d]))
+        return false;
+    if (eol && d + bj.L < bi.L && !regex_class_holds_nl(bi.classes[d + bj.L]))
+        return false;
+    return true;
+}
+// q among the *n distinct sequences of `set` (room for 8; only L and classes are compared): identical class tables merge.
+// false: it would be the ninth.
+inline bool regex_branch_add(krep_gpu_regex_info_t *set, uint32_t *n, const krep_gpu_regex_info_t &q)
+{
+    for (uint32_t i = 0; i < *n; ++i)
+        if (set[i].L == q.L && memcmp(set[i].classes, q.classes, (size_t)q.L * 32) == 0)
+            return true;
+    if (*n >= kRegexMaxBranches)
+        return false;
+    set[(*n)++] = q;
+    return true;
+}
+// The fields behind the classes of a sequence whose L and classes are set: the anchor class with its bytes, and self_overlap (a
+// shift d >= 1 at which the sequence, between its anchors, overlaps itself)
 inline void regex_seq_finish(krep_gpu_regex_info_t *out, bool bol, bool eol)
 {
     const uint32_t L = out->L;
@@ -98,22 +222,33 @@ inline void regex_seq_finish(krep_gpu_regex_info_t *out, bool bol, bool eol)
         for (int b = 0; b < 256; ++b)
             if ((out->classes[best][b >> 3] >> (b & 7)) & 1u)
                 out->anchor_bytes[out->n_anchor++] = (uint8_t)b;
-    // can the pattern overlap itself: a shift d at which every class meets the one d places on; behind ^ the byte in front of the
-    // second occurrence, which lies inside the first, has to be a newline, and in front of $ the byte behind the first occurrence
-    auto holds_nl = [&](uint32_t k) { return ((out->classes[k]['\n' >> 3] >> ('\n' & 7)) & 1u) != 0; };
     for (uint32_t d = 1; d < L && !out->self_overlap; ++d)
-    {
-        bool all = (!bol || holds_nl(d - 1)) && (!eol || holds_nl(L - d));
-        for (uint32_t k = 0; k + d < L && all; ++k)
-        {
-            bool meet = false;
-            for (int w = 0; w < 32 && !meet; ++w)
-                meet = (out->classes[k][w] & out->classes[k + d][w]) != 0;
-            all = meet;
-        }
-        out->self_overlap = all ? 1 : 0;
-    }
+        out->self_overlap = regex_branches_overlap_anchored(*out, *out, d, bol, eol) ? 1 : 0;
 }
+// The fields behind the branches of an alternation whose n_branches and branch[] are set: Lmin, Lmax, total_L and cross_overlap
+// (two occurrences, of one branch at a shift d >= 1 or of two at any shift, can share a byte between the anchors)
+inline void regex_alt_finish(krep_gpu_regex_alt_t *alt, bool bol, bool eol)
+{
+    alt->Lmin = kRegexMaxL;
+    for (uint32_t b = 0; b < alt->n_branches; ++b)
+    {
+        const uint32_t L = alt->branch[b].L;
+        alt->Lmin = L < alt->Lmin ? L : alt->Lmin;
+        alt->Lmax = L > alt->Lmax ? L : alt->Lmax;
+        alt->total_L += L;
+    }
+    for (uint32_t i = 0; i < alt->n_branches && !alt->cross_overlap; ++i)
+        for (uint32_t j = 0; j < alt->n_branches && !alt->cross_overlap; ++j)
+            for (uint32_t d = i == j ? 1u : 0u; d < alt->branch[i].L && !alt->cross_overlap; ++d)
+                alt->cross_overlap = regex_branches_overlap_anchored(alt->branch[i], alt->branch[j], d, bol, eol) ? 1 : 0;
+}
+
+// ---- krep_gpu_regex_compile, krep_gpu_regex_compile_anchored: one sequence of byte classes ----------------------------------------
+// one atom of the pattern: bytes [at, at + len) of it, `rep` times in a row
+struct RegexAtom { size_t at, len; uint32_t rep; };
+
+constexpr const char *kRegexSeqTooManyClasses = "regex: more than 16 byte classes in a row";
+constexpr const char *kRegexSeqTooManyPlaces = "regex: more than 16 places in a row (^ and $ take one each beside the byte classes)";
 
 // Both entry points.  anchors: a '^' as the first and a '$' as the last pattern byte are line anchors (krep_gpu_regex_compile_anchored);
 // without it they are refused like everywhere else in the pattern (krep_gpu_regex_compile, whose struct cannot say them).
@@ -122,19 +257,8 @@ inline const char *regex_compile_seq(const search_params_t *p, bool anchors, kre
 {
     memset(out, 0, sizeof *out);
     *bol_out = *eol_out = 0;
-    if (!p->use_regex)
-        return "not a regex search (use_regex is not set)";
-    if (p->num_patterns > 1)
-        return "several regex patterns are an alternation (the CLI joins them with '|'): kept on krep's regex_search";
-    if (p->whole_word)
-        return "regex with -w: the CLI compiles \\bPATTERN\\b, a library caller PATTERN, and the operator sees neither compiled "
-               "expression: kept on krep's regex_search";
-    // In a multibyte locale libc's regexec matches CHARACTERS: '.', a negated or named class and, under REG_ICASE, even a letter
-    // take a whole multibyte sequence as one atom, so no pattern is a fixed number of BYTE classes there and one-byte probes cannot
-    // say what an atom matches.  The krep CLI never calls setlocale(): it runs in the C locale, where a character is a byte.
-    if (MB_CUR_MAX > 1)
-        return "regex in a multibyte locale (the process called setlocale): libc matches characters there, not bytes: kept on "
-               "krep's regex_search (krep itself runs in the C locale)";
+    if (const char *why = regex_check_search(p, false))
+        return why;
     const uint8_t *pat = (const uint8_t *)p->pattern;
     size_t n = p->pattern_len;
     if (p->num_patterns == 1 && p->patterns && p->pattern_lens && p->patterns[0])
@@ -142,15 +266,8 @@ inline const char *regex_compile_seq(const search_params_t *p, bool anchors, kre
         pat = (const uint8_t *)p->patterns[0];
         n = p->pattern_lens[0];
     }
-    if (!pat)
-        return "no pattern";
-    if (n == 0)
-        return "an empty regex matches the empty string: kept on krep's regex_search";
-    if (n > 1024)
-        return "regex pattern longer than 1024 bytes";
-    for (size_t i = 0; i < n; ++i)
-        if (pat[i] < 0x01 || pat[i] > 0x7f)
-            return "regex pattern holds a byte outside 0x01-0x7F";
+    if (const char *why = regex_check_pattern(pat, n))
+        return why;
     RegexAtom atoms[kRegexMaxL];
     uint32_t n_atoms = 0, L = 0;
     bool repeatable = false; // the token in front is an atom that has no repetition yet
@@ -179,53 +296,30 @@ inline const char *regex_compile_seq(const search_params_t *p, bool anchors, kre
             if (!repeatable)
                 return "regex: '{' not behind an atom";
             size_t k = i + 1;
-            uint32_t v = 0;
-            bool digits = false;
-            while (k < n && pat[k] >= '0' && pat[k] <= '9' && v <= 1000)
-            {
-                v = v * 10 + (uint32_t)(pat[k] - '0');
-                digits = true;
-                ++k;
-            }
-            if (!digits || k >= n)
-                return "regex: malformed repetition";
+            uint32_t v;
+            if (!regex_count(pat, n, &k, &v))
+                return kRegexMalformed;
             if (pat[k] == ',')
                 return "regex: {n,} and {n,m} repeat a varying number of times: kept on krep's regex_search";
             if (pat[k] != '}')
-                return "regex: malformed repetition";
+                return kRegexMalformed;
             if (v < 1)
                 return "regex: {0} makes an atom optional: kept on krep's regex_search";
             if (L - 1 + v > kRegexMaxL)
-                return "regex: more than 16 byte classes in a row";
+                return kRegexSeqTooManyClasses;
             L += v - 1;
             atoms[n_atoms - 1].rep = v;
             repeatable = false;
             i = k + 1;
             continue;
         }
-        size_t len = 1;
         if (c == '(' || c == ')' || c == '*' || c == '+' || c == '?' || c == '|')
             return "regex: ( ) * + ? | make a general automaton: kept on krep's regex_search";
-        if (c == '\\')
-        {
-            if (i + 1 >= n)
-                return "regex: trailing backslash";
-            const uint8_t e = pat[i + 1];
-            if ((e >= '0' && e <= '9') || ((e | 0x20) >= 'a' && (e | 0x20) <= 'z'))
-                return "regex: a backslash in front of a letter or digit (\\b, \\w, \\1, ...) is an operator: kept on krep's regex_search";
-            if (!regex_is_punct(e))
-                return "regex: a backslash in front of a byte that is not punctuation";
-            len = 2;
-        }
-        else if (c == '[')
-        {
-            const size_t e = regex_bracket_end(pat, n, i);
-            if (e >= n)
-                return "regex: bracket expression without its ']'";
-            len = e + 1 - i;
-        }
+        size_t len;
+        if (const char *why = regex_atom(pat, n, i, &len))
+            return why;
         if (L + 1 > kRegexMaxL)
-            return "regex: more than 16 byte classes in a row";
+            return kRegexSeqTooManyClasses;
         atoms[n_atoms++] = RegexAtom{i, len, 1};
         ++L;
         repeatable = true;
@@ -234,13 +328,13 @@ inline const char *regex_compile_seq(const search_params_t *p, bool anchors, kre
     if (L < 1)
         return (bol || eol) ? "regex: ^, $ and ^$ on their own match the empty string: kept on krep's regex_search" : "regex: no atom";
     if (L + bol + eol > kRegexMaxL)
-        return "regex: more than 16 places in a row (^ and $ take one each beside the byte classes)";
+        return kRegexSeqTooManyPlaces;
     uint32_t j = 0;
     for (uint32_t a = 0; a < n_atoms; ++a)
     {
         uint8_t cls[32];
         if (!regex_probe_atom(pat + atoms[a].at, atoms[a].len, p->case_sensitive, cls))
-            return "regex: regcomp refuses an atom of the pattern";
+            return kRegexAtomRefused;
         for (uint32_t r = 0; r < atoms[a].rep; ++r)
             memcpy(out->classes[j++], cls, 32);
     }
@@ -268,8 +362,6 @@ inline const char *regex_compile_anchored(const search_params_t *p, krep_gpu_reg
 }
 
 // ---- krep_gpu_regex_compile_alt: an alternation of class sequences ------------------------------------------------------------
-constexpr uint32_t kRegexMaxBranches = 8, kRegexMaxTotalL = 32;
-
 // the patterns a search names: patterns[0..num_patterns) when the arrays are there, else pattern alone
 inline size_t regex_pattern_count(const search_params_t *p) { return (p->num_patterns >= 1 && p->patterns && p->pattern_lens) ? p->num_patterns : 1; }
 inline void regex_pattern_at(const search_params_t *p, size_t k, const uint8_t **pat, size_t *n)
@@ -297,169 +389,101 @@ inline bool regex_has_alt_syntax(const search_params_t *p)
     regex_pattern_at(p, 0, &pat, &n);
     if (!pat)
         return false;
-    for (size_t i = 0; i < n;)
+    for (size_t i = 0, len; i < n; i += len)
     {
-        if (pat[i] == '\\')
-            i += 2;
-        else if (pat[i] == '[')
-            i = regex_bracket_end(pat, n, i) + 1;
-        else if (pat[i] == '|' || pat[i] == '(')
+        if (pat[i] == '|' || pat[i] == '(')
             return true;
-        else
-            ++i;
+        if (regex_atom(pat, n, i, &len) && !len)
+            break;
     }
     return false;
 }
-inline bool regex_classes_meet(const uint8_t a[32], const uint8_t b[32])
+constexpr const char *kRegexAltEmptyBranch = "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
+constexpr const char *kRegexAltUnbalanced = "regex alternation: unbalanced parentheses: kept on krep's regex_search";
+constexpr const char *kRegexAltNested = "regex alternation: nested parentheses: kept on krep's regex_search";
+constexpr const char *kRegexAltMixedAnchors = "regex alternation: ^ or $ in a branch (anchors inside an alternation): kept on krep's regex_search";
+constexpr const char *kRegexAltBranchTooLong = "regex alternation: a branch of more than 16 byte classes: kept on krep's regex_search";
+constexpr const char *kRegexAltTooManyBranches = "regex alternation: more than 8 branches: kept on krep's regex_search";
+constexpr const char *kRegexAltTooWide = "regex alternation: more than 32 byte classes in all branches together: kept on krep's regex_search";
+
+// The top-level branch of pat that begins at bs: *end its '|' or n, [*lo, *hi) its sequence with the one pair of parentheses around it
+// taken off.  The walk reports what it meets first, a misplaced parenthesis or anchor or an atom the pattern ends in; every other
+// fault of an atom is the tokeniser's, which gets the sequence.
+inline const char *regex_alt_branch(const uint8_t *pat, size_t n, size_t bs, size_t *lo, size_t *hi, size_t *end)
 {
-    for (int w = 0; w < 32; ++w)
-        if (a[w] & b[w])
-            return true;
-    return false;
-}
-// can an occurrence of branch j start d bytes into an occurrence of branch i (every class pair that lies on one byte meets)
-inline bool regex_branches_overlap(const krep_gpu_regex_info_t &bi, const krep_gpu_regex_info_t &bj, uint32_t d)
-{
-    for (uint32_t t = 0; d + t < bi.L && t < bj.L; ++t)
-        if (!regex_classes_meet(bi.classes[d + t], bj.classes[t]))
-            return false;
-    return true;
+    size_t i = bs, inner = bs;         // inner: where the sequence begins, behind a '('
+    bool open = false, closed = false; // inside the branch's group | its ')' is behind the cursor
+    while (i < n && pat[i] != '|')
+    {
+        const uint8_t c = pat[i];
+        if ((closed && c != ')') || (c == '(' && !open && i != bs))
+            return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general automaton: kept on "
+                   "krep's regex_search";
+        size_t len = 1;
+        if (c == '(')
+        {
+            if (open)
+                return kRegexAltNested;
+            open = true;
+            inner = i + 1;
+        }
+        else if (c == ')')
+        {
+            if (!open)
+                return kRegexAltUnbalanced;
+            open = false;
+            closed = true;
+            if (i == inner)
+                return kRegexAltEmptyBranch;
+        }
+        else if (c == '^' || c == '$')
+            return kRegexAltMixedAnchors;
+        else if (const char *why = regex_atom(pat, n, i, &len); why && !len)
+            return why;
+        i += len;
+    }
+    if (open)
+        return i < n ? "regex alternation: a group that holds an alternation ((a|b)) is not one class sequence: kept on krep's regex_search"
+                     : kRegexAltUnbalanced;
+    *lo = closed ? inner : bs;
+    *hi = closed ? i - 1 : i;
+    *end = i;
+    return *hi <= *lo ? kRegexAltEmptyBranch : nullptr;
 }
 inline const char *regex_compile_alt_branches(const search_params_t *p, krep_gpu_regex_alt_t *out)
 {
-    if (!p->use_regex)
-        return "not a regex search (use_regex is not set)";
-    if (p->whole_word)
-        return "regex with -w: the CLI compiles \\bPATTERN\\b, a library caller PATTERN, and the operator sees neither compiled "
-               "expression: kept on krep's regex_search";
-    if (MB_CUR_MAX > 1)
-        return "regex in a multibyte locale (the process called setlocale): libc matches characters there, not bytes: kept on "
-               "krep's regex_search (krep itself runs in the C locale)";
-    if (p->num_patterns > 1 && !(p->patterns && p->pattern_lens))
-        return "several patterns announced but patterns / pattern_lens are NULL";
+    if (const char *why = regex_check_search(p, true))
+        return why;
     const size_t n_pat = regex_pattern_count(p);
     for (size_t k = 0; k < n_pat; ++k)
     {
         const uint8_t *pat;
         size_t n;
         regex_pattern_at(p, k, &pat, &n);
-        if (!pat)
-            return "no pattern";
-        if (n == 0)
-            return "an empty regex matches the empty string: kept on krep's regex_search";
-        if (n > 1024)
-            return "regex pattern longer than 1024 bytes";
-        for (size_t i = 0; i < n; ++i)
-            if (pat[i] < 0x01 || pat[i] > 0x7f)
-                return "regex pattern holds a byte outside 0x01-0x7F";
-        // cut the pattern at its top-level '|'; a branch is bytes [lo, hi) of it, the parentheses around it taken off
-        size_t bs = 0;            // where the branch under the cursor begins
-        size_t inner = 0;         // ... and where its sequence begins (behind a '(')
-        bool open = false, closed = false; // inside the branch's group | its ')' is behind the cursor
-        for (size_t i = 0; i <= n;)
+        if (const char *why = regex_check_pattern(pat, n))
+            return why;
+        for (size_t bs = 0, end; bs <= n; bs = end + 1) // (a '|' at the very end has an empty branch behind it)
         {
-            const uint8_t c = i < n ? pat[i] : (uint8_t)'|'; // the end of the pattern ends a branch like a '|'
-            if (c == '\\' && i < n)
-            {
-                if (closed)
-                    return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general "
-                           "automaton: kept on krep's regex_search";
-                if (i + 1 >= n)
-                    return "regex: trailing backslash";
-                i += 2;
-                continue;
-            }
-            if (c == '[' && i < n)
-            {
-                if (closed)
-                    return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general "
-                           "automaton: kept on krep's regex_search";
-                const size_t e = regex_bracket_end(pat, n, i);
-                if (e >= n)
-                    return "regex: bracket expression without its ']'";
-                i = e + 1;
-                continue;
-            }
-            if (c == '(')
-            {
-                if (open)
-                    return "regex alternation: nested parentheses: kept on krep's regex_search";
-                if (i != bs || closed)
-                    return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general "
-                           "automaton: kept on krep's regex_search";
-                open = true;
-                inner = i + 1;
-                ++i;
-                continue;
-            }
-            if (c == ')')
-            {
-                if (!open)
-                    return "regex alternation: unbalanced parentheses: kept on krep's regex_search";
-                open = false;
-                closed = true;
-                if (i == inner)
-                    return "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
-                ++i;
-                continue;
-            }
-            if (c == '|')
-            {
-                if (open)
-                    return i < n ? "regex alternation: a group that holds an alternation ((a|b)) is not one class sequence: kept on "
-                                   "krep's regex_search"
-                                 : "regex alternation: unbalanced parentheses: kept on krep's regex_search";
-                const size_t lo = closed ? inner : bs, hi = closed ? i - 1 : i;
-                if (hi <= lo)
-                    return "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
-                search_params_t q = *p;
-                q.pattern = (const char *)pat + lo;
-                q.pattern_len = hi - lo;
-                q.patterns = nullptr;
-                q.pattern_lens = nullptr;
-                q.num_patterns = 0;
-                krep_gpu_regex_info_t info;
-                int bol, eol;
-                if (const char *why = regex_compile_seq(&q, false, &info, &bol, &eol))
-                {
-                    return strstr(why, "more than 16") ? "regex alternation: a branch of more than 16 byte classes: kept on krep's regex_search" : why;
-                }
-                bool dup = false;
-                for (uint32_t b = 0; b < out->n_branches && !dup; ++b)
-                    dup = out->branch[b].L == info.L && memcmp(out->branch[b].classes, info.classes, (size_t)info.L * 32) == 0;
-                if (!dup)
-                {
-                    if (out->n_branches >= kRegexMaxBranches)
-                        return "regex alternation: more than 8 branches: kept on krep's regex_search";
-                    out->branch[out->n_branches++] = info;
-                }
-                bs = i + 1;
-                closed = false;
-                ++i;
-                continue;
-            }
-            if (closed)
-                return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general automaton: "
-                       "kept on krep's regex_search";
-            if (c == '^' || c == '$')
-                return "regex alternation: ^ or $ in a branch (anchors inside an alternation): kept on krep's regex_search";
-            ++i;
+            size_t lo, hi;
+            if (const char *why = regex_alt_branch(pat, n, bs, &lo, &hi, &end))
+                return why;
+            search_params_t q = *p;
+            q.pattern = (const char *)pat + lo;
+            q.pattern_len = hi - lo;
+            q.patterns = nullptr;
+            q.pattern_lens = nullptr;
+            q.num_patterns = 0;
+            krep_gpu_regex_info_t info;
+            int bol, eol;
+            if (const char *why = regex_compile_seq(&q, false, &info, &bol, &eol))
+                return why == kRegexSeqTooManyClasses ? kRegexAltBranchTooLong : why;
+            if (!regex_branch_add(out->branch, &out->n_branches, info))
+                return kRegexAltTooManyBranches;
         }
     }
-    out->Lmin = kRegexMaxL;
-    for (uint32_t b = 0; b < out->n_branches; ++b)
-    {
-        const uint32_t L = out->branch[b].L;
-        out->Lmin = L < out->Lmin ? L : out->Lmin;
-        out->Lmax = L > out->Lmax ? L : out->Lmax;
-        out->total_L += L;
-    }
+    regex_alt_finish(out, false, false);
     if (out->total_L > kRegexMaxTotalL)
-        return "regex alternation: more than 32 byte classes in all branches together: kept on krep's regex_search";
-    for (uint32_t i = 0; i < out->n_branches && !out->cross_overlap; ++i)
-        for (uint32_t j = 0; j < out->n_branches && !out->cross_overlap; ++j)
-            for (uint32_t d = i == j ? 1u : 0u; d < out->branch[i].L && !out->cross_overlap; ++d)
-                out->cross_overlap = regex_branches_overlap(out->branch[i], out->branch[j], d) ? 1 : 0;
+        return kRegexAltTooWide;
     return nullptr;
 }
 // krep_gpu_regex_compile_alt: NULL and *out filled, or the refusal and *out zeroed
@@ -492,21 +516,11 @@ constexpr const char *kRegexExtEmpty = "regex expansion: one of the sequences ho
                                        "krep's regex_search";
 inline bool regex_ext_own_limit(const char *why) { return why == kRegexExtTooMany || why == kRegexExtTooLong || why == kRegexExtTooWide || why == kRegexExtEmpty; }
 
-inline const char *regex_set_add(RegexSeqSet &S, const krep_gpu_regex_info_t &q)
-{
-    for (uint32_t i = 0; i < S.n; ++i)
-        if (S.s[i].L == q.L && memcmp(S.s[i].classes, q.classes, (size_t)q.L * 32) == 0)
-            return nullptr;
-    if (S.n >= kRegexMaxBranches)
-        return kRegexExtTooMany;
-    S.s[S.n++] = q;
-    return nullptr;
-}
 inline const char *regex_set_union(RegexSeqSet &S, const RegexSeqSet &A)
 {
     for (uint32_t i = 0; i < A.n; ++i)
-        if (const char *why = regex_set_add(S, A.s[i]))
-            return why;
+        if (!regex_branch_add(S.s, &S.n, A.s[i]))
+            return kRegexExtTooMany;
     return nullptr;
 }
 // C = every sequence of A with every sequence of B behind it
@@ -521,8 +535,8 @@ inline const char *regex_set_cat(const RegexSeqSet &A, const RegexSeqSet &B, Reg
             krep_gpu_regex_info_t q = A.s[i];
             for (uint32_t t = 0; t < B.s[j].L; ++t)
                 memcpy(q.classes[q.L++], B.s[j].classes[t], 32);
-            if (const char *why = regex_set_add(C, q))
-                return why;
+            if (!regex_branch_add(C.s, &C.n, q))
+                return kRegexExtTooMany;
         }
     return nullptr;
 }
@@ -573,30 +587,19 @@ inline const char *regex_ext_quant(RegexExtCursor &c, RegexSeqSet &A)
     else
     {
         size_t k = c.i + 1;
-        auto number = [&](uint32_t &v) {
-            bool digits = false;
-            v = 0;
-            while (k < c.n && c.pat[k] >= '0' && c.pat[k] <= '9' && v <= 1000)
-            {
-                v = v * 10 + (uint32_t)(c.pat[k] - '0');
-                digits = true;
-                ++k;
-            }
-            return digits;
-        };
-        if (!number(lo) || k >= c.n)
-            return "regex: malformed repetition";
+        if (!regex_count(c.pat, c.n, &k, &lo))
+            return kRegexMalformed;
         hi = lo;
         if (c.pat[k] == ',')
         {
             ++k;
             if (k < c.n && c.pat[k] == '}')
                 return "regex: {n,} repeats without a bound, which needs an unbounded state: kept on krep's regex_search";
-            if (!number(hi) || k >= c.n)
-                return "regex: malformed repetition";
+            if (!regex_count(c.pat, c.n, &k, &hi))
+                return kRegexMalformed;
         }
         if (c.pat[k] != '}' || lo > hi || hi > 1000)
-            return "regex: malformed repetition";
+            return kRegexMalformed;
         if (hi == 0)
             return "regex: {0} repeats an atom zero times, a{0} matches the empty string: kept on krep's regex_search";
         c.i = k + 1;
@@ -605,32 +608,15 @@ inline const char *regex_ext_quant(RegexExtCursor &c, RegexSeqSet &A)
         return "regex: a quantifier behind a quantifier (a?{2}, a{2}{3}, a?+): kept on krep's regex_search";
     return regex_set_repeat(A, lo, hi);
 }
-// one atom at the cursor (the tokeniser's rules, regex_compile_seq) with its optional quantifier: its alternatives into A
+// one atom at the cursor with its optional quantifier: its alternatives into A
 inline const char *regex_ext_atom(RegexExtCursor &c, RegexSeqSet &A)
 {
-    const uint8_t ch = c.pat[c.i];
-    size_t len = 1;
-    if (ch == '\\')
-    {
-        if (c.i + 1 >= c.n)
-            return "regex: trailing backslash";
-        const uint8_t e = c.pat[c.i + 1];
-        if ((e >= '0' && e <= '9') || ((e | 0x20) >= 'a' && (e | 0x20) <= 'z'))
-            return "regex: a backslash in front of a letter or digit (\\b, \\w, \\1, ...) is an operator: kept on krep's regex_search";
-        if (!regex_is_punct(e))
-            return "regex: a backslash in front of a byte that is not punctuation";
-        len = 2;
-    }
-    else if (ch == '[')
-    {
-        const size_t e = regex_bracket_end(c.pat, c.n, c.i);
-        if (e >= c.n)
-            return "regex: bracket expression without its ']'";
-        len = e + 1 - c.i;
-    }
+    size_t len;
+    if (const char *why = regex_atom(c.pat, c.n, c.i, &len))
+        return why;
     regex_set_empty_seq(A);
     if (!regex_probe_atom(c.pat + c.i, len, c.case_sensitive, A.s[0].classes[0]))
-        return "regex: regcomp refuses an atom of the pattern";
+        return kRegexAtomRefused;
     A.s[0].L = 1;
     c.i += len;
     return regex_ext_quant(c, A);
@@ -645,10 +631,10 @@ inline const char *regex_ext_group(RegexExtCursor &c, RegexSeqSet &G)
     for (;;)
     {
         if (c.i >= c.n)
-            return "regex alternation: unbalanced parentheses: kept on krep's regex_search";
+            return kRegexAltUnbalanced;
         const uint8_t ch = c.pat[c.i];
         if (ch == '(')
-            return "regex alternation: nested parentheses: kept on krep's regex_search";
+            return kRegexAltNested;
         if (ch == '^' || ch == '$')
             return "regex: ^ or $ inside a group anchors in the middle of the expression: kept on krep's regex_search";
         if (ch == '|' || ch == ')')
@@ -700,7 +686,7 @@ inline const char *regex_ext_branch(RegexExtCursor &c, RegexSeqSet &S, int *bol,
             return "regex: ^ that is not the first or $ that is not the last byte of a branch (a^b, a$b, ^^a, a$$) anchors in the middle of "
                    "the expression: kept on krep's regex_search";
         if (ch == ')')
-            return "regex alternation: unbalanced parentheses: kept on krep's regex_search";
+            return kRegexAltUnbalanced;
         if (regex_is_quant(ch))
             return (*bol && !any) ? "regex: a repetition directly behind ^ repeats the anchor: kept on krep's regex_search"
                                   : "regex: a quantifier that is not behind an atom or a group";
@@ -718,60 +704,25 @@ inline const char *regex_ext_branch(RegexExtCursor &c, RegexSeqSet &S, int *bol,
         any = true;
     }
     if (!any)
-        return (*bol || *eol) ? "regex: ^, $ and ^$ on their own match the empty string: kept on krep's regex_search"
-                              : "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
+        return (*bol || *eol) ? "regex: ^, $ and ^$ on their own match the empty string: kept on krep's regex_search" : kRegexAltEmptyBranch;
     for (uint32_t k = 0; k < S.n; ++k)
         if (S.s[k].L == 0)
             return kRegexExtEmpty;
     return nullptr;
 }
-inline bool regex_class_holds_nl(const uint8_t cls[32]) { return ((cls['\n' >> 3] >> ('\n' & 7)) & 1u) != 0; }
-// can an occurrence of branch j start d bytes into an occurrence of branch i when every branch stands between the same anchors.
-// d == 0 (the same start) is never ruled out by an anchor.  d >= 1 under ^: the byte in front of j lies inside i.  Under $: the byte
-// behind the occurrence that ends first lies inside the other one.
-inline bool regex_branches_overlap_anchored(const krep_gpu_regex_info_t &bi, const krep_gpu_regex_info_t &bj, uint32_t d, bool bol, bool eol)
-{
-    if (!regex_branches_overlap(bi, bj, d))
-        return false;
-    if (d == 0)
-        return true;
-    if (bol && !regex_class_holds_nl(bi.classes[d - 1]))
-        return false;
-    if (eol && bi.L - d < bj.L && !regex_class_holds_nl(bj.classes[bi.L - d]))
-        return false;
-    if (eol && d + bj.L < bi.L && !regex_class_holds_nl(bi.classes[d + bj.L]))
-        return false;
-    return true;
-}
 inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu_regex_ext_t *out)
 {
-    if (!p->use_regex)
-        return "not a regex search (use_regex is not set)";
-    if (p->whole_word)
-        return "regex with -w: the CLI compiles \\bPATTERN\\b, a library caller PATTERN, and the operator sees neither compiled "
-               "expression: kept on krep's regex_search";
-    if (MB_CUR_MAX > 1)
-        return "regex in a multibyte locale (the process called setlocale): libc matches characters there, not bytes: kept on "
-               "krep's regex_search (krep itself runs in the C locale)";
-    if (p->num_patterns > 1 && !(p->patterns && p->pattern_lens))
-        return "several patterns announced but patterns / pattern_lens are NULL";
-    RegexSeqSet all;
-    memset(&all, 0, sizeof all);
+    if (const char *why = regex_check_search(p, true))
+        return why;
+    krep_gpu_regex_alt_t &alt = out->alt;
     const size_t n_pat = regex_pattern_count(p);
     bool first = true;
     for (size_t k = 0; k < n_pat; ++k)
     {
         RegexExtCursor c{nullptr, 0, 0, p->case_sensitive};
         regex_pattern_at(p, k, &c.pat, &c.n);
-        if (!c.pat)
-            return "no pattern";
-        if (c.n == 0)
-            return "an empty regex matches the empty string: kept on krep's regex_search";
-        if (c.n > 1024)
-            return "regex pattern longer than 1024 bytes";
-        for (size_t i = 0; i < c.n; ++i)
-            if (c.pat[i] < 0x01 || c.pat[i] > 0x7f)
-                return "regex pattern holds a byte outside 0x01-0x7F";
+        if (const char *why = regex_check_pattern(c.pat, c.n))
+            return why;
         for (;;)
         {
             RegexSeqSet S;
@@ -785,42 +736,27 @@ inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu
                 first = false;
             }
             else if (bol != out->bol || eol != out->eol)
-                return "regex alternation: ^ or $ in a branch (anchors inside an alternation): kept on krep's regex_search";
-            if (const char *why = regex_set_union(all, S))
-                return why;
+                return kRegexAltMixedAnchors;
+            for (uint32_t b = 0; b < S.n; ++b)
+                if (!regex_branch_add(alt.branch, &alt.n_branches, S.s[b]))
+                    return kRegexExtTooMany;
             if (c.i >= c.n)
                 break;
             ++c.i; // the '|'
             if (c.i >= c.n)
-                return "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
+                return kRegexAltEmptyBranch;
         }
     }
     const uint32_t extra = (uint32_t)(out->bol + out->eol);
-    krep_gpu_regex_alt_t &alt = out->alt;
-    alt.Lmin = kRegexMaxL;
-    uint32_t places = 0;
-    for (uint32_t b = 0; b < all.n; ++b)
+    for (uint32_t b = 0; b < alt.n_branches; ++b)
     {
-        const uint32_t L = all.s[b].L;
-        if (L + extra > kRegexMaxL)
+        if (alt.branch[b].L + extra > kRegexMaxL)
             return kRegexExtTooLong;
-        alt.Lmin = L < alt.Lmin ? L : alt.Lmin;
-        alt.Lmax = L > alt.Lmax ? L : alt.Lmax;
-        alt.total_L += L;
-        places += L + extra;
-    }
-    if (places > kRegexMaxTotalL)
-        return kRegexExtTooWide;
-    alt.n_branches = all.n;
-    for (uint32_t b = 0; b < all.n; ++b)
-    {
-        alt.branch[b] = all.s[b];
         regex_seq_finish(&alt.branch[b], false, false); // (each branch what krep_gpu_regex_compile() makes of it alone)
     }
-    for (uint32_t i = 0; i < alt.n_branches && !alt.cross_overlap; ++i)
-        for (uint32_t j = 0; j < alt.n_branches && !alt.cross_overlap; ++j)
-            for (uint32_t d = i == j ? 1u : 0u; d < alt.branch[i].L && !alt.cross_overlap; ++d)
-                alt.cross_overlap = regex_branches_overlap_anchored(alt.branch[i], alt.branch[j], d, out->bol != 0, out->eol != 0) ? 1 : 0;
+    regex_alt_finish(&alt, out->bol != 0, out->eol != 0);
+    if (alt.total_L + alt.n_branches * extra > kRegexMaxTotalL)
+        return kRegexExtTooWide;
     return nullptr;
 }
 // krep_gpu_regex_compile_ext: NULL and *out filled, or the refusal and *out zeroed
@@ -833,6 +769,54 @@ inline const char *regex_compile_ext(const search_params_t *p, krep_gpu_regex_ex
     if (why)
         memset(out, 0, sizeof *out);
     return why;
+}
+
+// ---- the compilers in the order every search asks them -------------------------------------------------------------------------
+// The anchored compiler is asked first; only what it refuses goes to the alternation compiler, and what both refuse to the expanding
+// compiler, whose result is an alternation too, between the line anchors alt_bol / alt_eol (is_alt: one of the two took it).  So a
+// search an earlier compiler takes runs the kernel it always ran.
+struct RegexCompiled
+{
+    bool is_alt = false;
+    krep_gpu_regex_anchored_t seq{}; // !is_alt
+    krep_gpu_regex_alt_t alt{};      // is_alt
+    int alt_bol = 0, alt_eol = 0;    // is_alt: ^ in front of / $ behind every branch (the expanding compiler only)
+};
+// a refusal of the two older compilers that is a limit of theirs: one the expanding compiler's own limits do not replace
+inline bool regex_older_limit(const char *why)
+{
+    return why == kRegexSeqTooManyClasses || why == kRegexSeqTooManyPlaces || why == kRegexAltBranchTooLong || why == kRegexAltTooManyBranches ||
+           why == kRegexAltTooWide;
+}
+// NULL: taken.  Else the reason of a search all three refuse: what it was before the expanding compiler — the alternation compiler's
+// when the search says an alternation, else the anchored compiler's — unless only the expanding compiler's own limits are in the way.
+inline const char *regex_compile_search(const search_params_t *p, RegexCompiled *out)
+{
+    out->is_alt = false;
+    out->alt_bol = out->alt_eol = 0;
+    const char *why = regex_compile_anchored(p, &out->seq);
+    if (!why)
+        return nullptr;
+    if (!p || !p->use_regex)
+        return why;
+    const char *why_alt = regex_compile_alt(p, &out->alt);
+    if (!why_alt)
+    {
+        out->is_alt = true;
+        return nullptr;
+    }
+    krep_gpu_regex_ext_t ext;
+    const char *why_ext = regex_compile_ext(p, &ext);
+    if (!why_ext)
+    {
+        out->is_alt = true;
+        out->alt = ext.alt;
+        out->alt_bol = ext.bol;
+        out->alt_eol = ext.eol;
+        return nullptr;
+    }
+    const char *before = regex_has_alt_syntax(p) ? why_alt : why;
+    return regex_ext_own_limit(why_ext) && !regex_older_limit(before) ? why_ext : before;
 }
 
 } // namespace kg

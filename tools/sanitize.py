@@ -8,10 +8,12 @@ with the sanitizer named.
     python tools/sanitize.py tsan      # libkrep_gpu_tsan.so under the multi-shard failover tests (8 logical shards, injected failures)
     python tools/sanitize.py oracle    # oracle/krep_oracle.c under ASan + UBSan against the golden vectors and the compiled reference
     python tools/sanitize.py reference # the reference's own krep_test built with ASan + UBSan (findings there are the reference's)
-    python tools/sanitize.py regex     # the -E pattern compiler as a stand-alone program (tools/regex_compile_san.cpp) under ASan + UBSan
+    python tools/sanitize.py regex     # the -E pattern compiler as a stand-alone program (tools/regex_compile_san.cpp) under ASan + UBSan,
+                                       # then its --digest over the whole corpus against tests/golden/regex_compile_digest.json
 
 Each mode prints the sanitizer reports it saw (none expected) and exits non-zero on one; profiles/r06_sanitizers.txt is its log."""
 import glob
+import json
 import os
 import subprocess
 import sys
@@ -98,6 +100,24 @@ def main():
         bad = [l for l in out.splitlines() if "ERROR: AddressSanitizer" in l or "ERROR: LeakSanitizer" in l or "runtime error:" in l]
         print(out[-1500:])
         rc = r.returncode
+        # ... and every answer of the compilers over the whole corpus against the recording (tests/golden/regex_compile_digest.json)
+        r = run([exe, "--digest"], env={"ASAN_OPTIONS": "detect_leaks=1:halt_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}, capture_output=True, text=True)
+        bad += [l for l in r.stderr.splitlines() if "ERROR: AddressSanitizer" in l or "ERROR: LeakSanitizer" in l or "runtime error:" in l]
+        with open(os.path.join(ROOT, "tests", "golden", "regex_compile_digest.json")) as f:
+            want = json.load(f)
+        have = {}
+        for line in r.stdout.splitlines():
+            name, _, h = line.split()
+            have.setdefault(name, []).append(h)
+        if have.get("classes") != want["classes"]:
+            print("regex digest: this libc gives other byte classes than the recording's: the recording does not apply here")
+        else:
+            differ = [f"{name} {k}" for name in ("named", "bytes", "pieces") for k, h in enumerate(want[name])
+                      if have.get(name, [])[k:k + 1] != [h]]
+            print(f"regex digest: {sum(len(want[n]) for n in ('named', 'bytes', 'pieces'))} blocks of the whole corpus, {len(differ)} differ from the "
+                  f"recording {' '.join(differ[:20])}")
+            rc = rc or (1 if differ else 0)
+        rc = rc or r.returncode
     else:
         print(__doc__)
         return 2
