@@ -1,7 +1,10 @@
 // kg_regex.hip — krep -E for fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile): the exported pattern
-// compilers (kg_regex_compile.h), the bit-parallel shift-and scan kernel and its driver kg::scan_regex.  An alternation of such
+// compilers (kg_regex_compile.h), the bit-parallel shift-and scan kernel and its scan kg::scan_regex.  An alternation of such
 // sequences (krep_gpu_regex_compile_alt, and what krep_gpu_regex_compile_ext expands into one, line anchors included) has its own
-// kernel and driver in kg_regex_alt.hip: regex_prog_create builds its table here, scan_regex hands over.
+// kernel and scan in kg_regex_alt.hip: regex_prog_create builds its table here, scan_regex hands over.
+// Both scans go through the one window driver of this file (rx_window: the window checks and refusals; rx_drive: the launches, the
+// greedy pass, the read-back and the krep_gpu_scan_out_t), and both kernels are built around their walk from the device helpers of
+// kg_regex_dev.h (table fill, round loader, -c line state, record store, unit end, grid).
 //
 // The kernel.  T[byte] is a 16-bit mask, bit j set when byte is in class Cj.  It sits in LDS once per bank (entry b of copy k at
 // dword b * 32 + k, a lane reads copy lane % 32), so the 64 lookups of a wave instruction never meet in a bank whatever the
@@ -66,11 +69,7 @@ struct RxArgs
     u32 n_anchor;
     u32 ab[4];           // the anchor bytes, each in every byte lane
     const u32 *table;
-    u64 *unitinfo;       // count mode: per-unit info words (nullptr: only the total is wanted)
-    const u64 *offsets;  // emit mode: exclusive index of each unit's first record
-    u64 *positions;
-    u64 pos_cap;
-    Counters *ctr;
+    RxOut o;             // what the window driver sets (kg_regex_dev.h)
 };
 
 // the optimistic walk over a lane's 16 bytes: bit k of the result = bit L-1 of the state behind byte k; X = the exit state
@@ -93,9 +92,7 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
 {
     static_assert(!(ANCH && LINES) && !(LINES && EMIT), "-c walks every cell and writes no records");
     __shared__ u32 s_T[256 * 32];
-    for (u32 i = threadIdx.x; i < 256u * 32u; i += kBlock)
-        s_T[i] = a.table[i >> 5];
-    __syncthreads();
+    rx_fill_table(s_T, a.table);
     const u32 lane = lane_id(), wave = threadIdx.x >> 6;
     const u32 *T = s_T + (lane & 31u);
     const u32 Lm1 = ((a.geom >> 8) & 0xffu) - 1u, sh = (a.geom >> 16) & 0xffu;
@@ -122,23 +119,8 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
         bool have_state = true, prev_anch = true; // ANCH: x63 is valid | the cell in front holds an anchor byte (unknown: yes)
         u32 p63[4] = {0, 0, 0, 0};                // ANCH: lane 63's bytes of the last skipped cell
         u32 l_hits = 0;                           // per lane
-        u64 out_idx = EMIT ? a.offsets[unit] : 0; // uniform
-        // -c: the line state of the unit, as kg_literal.hip keeps it (carry arithmetic over the 64 lanes of a cell)
-        u32 l_cnt = 0, s_new = 0;
-        bool s_open = false, s_seen = false, s_head = false;
-        auto line_cell = [&](u64 B_nl, u64 B_any, u64 B_head, u64 B_tail) __attribute__((always_inline)) {
-            const u64 G = B_tail, P = ~(B_nl | B_any);
-            const unsigned __int128 sum = (unsigned __int128)(G | P) + G + (s_open ? 1u : 0u);
-            const u64 O = (u64)sum ^ P; // bit l: the line entering lane l already holds a match
-            s_new += (u32)__popcll(B_head & ~O);
-            if (!s_seen && B_nl)
-            {
-                const int f = __builtin_ctzll(B_nl);
-                s_head = (((O | B_head) >> f) & 1ull) != 0ull;
-                s_seen = true;
-            }
-            s_open = (u64)(sum >> 64) != 0ull;
-        };
+        u64 out_idx = EMIT ? a.o.offsets[unit] : 0; // uniform
+        RxLineCarry lc;                           // -c: the line state of the unit
 
         for (int r = 0; r < kRoundsBig; ++r)
         {
@@ -147,42 +129,7 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
                 break;
             const bool fast = seg + kSegBytes <= a.text_len;
             uint4 d[kCells];
-            if (fast)
-            {
-                const uint4 *src = reinterpret_cast<const uint4 *>(a.text + seg) + lane;
-#pragma unroll
-                for (int j = 0; j < kCells; ++j)
-                {
-                    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-                    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + j * kWave));
-                    d[j] = make_uint4(v.x, v.y, v.z, v.w);
-                }
-            }
-            else
-            {
-#pragma unroll
-                for (int j = 0; j < kCells; ++j)
-                {
-                    const u64 cb = seg + (u64)j * kCellBytes;
-                    d[j] = cb < a.cov_hi ? rx_load_guarded(a.text, a.text_len, cb + (u64)lane * 16u) : make_uint4(0u, 0u, 0u, 0u);
-                }
-                if ((a.geom >> 25) & 1u)
-                { // $: the newline behind the last byte of the text, put into the one lane whose 16 bytes hold offset text_len
-#pragma unroll
-                    for (int j = 0; j < kCells; ++j)
-                    {
-                        const u64 rel = a.text_len - (seg + (u64)j * kCellBytes + (u64)lane * 16u);
-                        if (rel < 16u)
-                        {
-                            const u32 nl = 0x0au << (8u * ((u32)rel & 3u)), w = (u32)rel >> 2;
-                            d[j].x |= w == 0u ? nl : 0u;
-                            d[j].y |= w == 1u ? nl : 0u;
-                            d[j].z |= w == 2u ? nl : 0u;
-                            d[j].w |= w == 3u ? nl : 0u;
-                        }
-                    }
-                }
-            }
+            rx_load_round(d, a, seg, lane, fast, ((a.geom >> 25) & 1u) != 0u);
 #pragma unroll
             for (int j = 0; j < kCells; ++j)
             {
@@ -232,35 +179,21 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
                     H &= rx_range(q, c_lo, c_hi);
                 l_hits += (u32)__popc(H);
                 if (LINES)
-                {
-                    const u32 N = (((mine >> 16) << sh) | ((prev >> 16) >> (16u - sh))) & 0xffffu, Hs = H | N;
-                    l_cnt += (u32)__popc(H & ~(Hs - ((N << 1) & 0xffffu)));
-                    // head: the lowest flag is a match (one ON a newline belongs to the line it ends); tail: a match behind the last newline
-                    line_cell(__ballot(N != 0u), __ballot(H != 0u), __ballot((H & (Hs ^ (Hs - 1u))) != 0u),
-                              __ballot((H >> (32 - __clz((int)N))) != 0u));
-                }
+                    lc.lane16(H, mine >> 16, prev >> 16, sh);
                 if (EMIT)
                 {
                     if (__ballot(H != 0u))
                     {
-                        const u32 c = (u32)__popc(H);
-                        u32 incl = c;
-#pragma unroll
-                        for (int o = 1; o < 64; o <<= 1)
-                        {
-                            const u32 t = __shfl_up(incl, o);
-                            if (lane >= (u32)o)
-                                incl += t;
-                        }
+                        const u32 c = (u32)__popc(H), incl = rx_wave_incl(c, lane);
                         u64 idx = out_idx + (incl - c);
                         while (H)
                         {
                             const u32 k = (u32)__builtin_ctz(H);
                             H &= H - 1u;
-                            if (idx < a.pos_cap)
+                            if (idx < a.o.pos_cap)
                             {
-                                const u64 s0 = q + k - sh + a.global_base, e0 = s0 + (a.geom & 0xffu);
-                                *reinterpret_cast<uint4 *>(a.positions + 2 * idx) = make_uint4((u32)s0, (u32)(s0 >> 32), (u32)e0, (u32)(e0 >> 32));
+                                const u64 s0 = q + k - sh + a.global_base;
+                                rx_store_record(a.o.positions, idx, s0, s0 + (a.geom & 0xffu));
                             }
                             ++idx;
                         }
@@ -271,45 +204,21 @@ __global__ __launch_bounds__(kBlock) void regex_scan(const RxArgs a)
         }
         if (EMIT)
             continue;
-        u32 h = l_hits, t = l_cnt;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1)
-        {
-            h += __shfl_xor(h, o);
-            if (LINES)
-                t += __shfl_xor(t, o);
-        }
-        acc_total += h;
-        if (a.unitinfo && lane == 0)
-        {
-            u64 info = (u64)h;
-            if (LINES)
-            {
-                const LineState ls{t + s_new, s_seen, s_seen ? s_head : s_open, s_open};
-                info |= line_bits(ls) | ((u64)(ls.cnt & kUiLineMask) << kUiLineShift);
-            }
-            else if (h)
-                info |= kLnHead | kLnTail;
-            a.unitinfo[unit] = info;
-        }
+        acc_total += rx_unit_end<LINES>(l_hits, lc, a.o.unitinfo, unit, lane);
     }
     if (!EMIT && lane == 0 && acc_total)
-        atomicAdd(&a.ctr->total, acc_total);
+        atomicAdd(&a.o.ctr->total, acc_total);
 }
 
 template <bool ANCH, bool LINES, bool EMIT> static hipError_t rx_launch(const RxArgs &a, int num_cu, hipStream_t st)
 {
-    const u64 blocks = (a.n_units + kWavesPerBlk - 1) / kWavesPerBlk;
-    u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 5)); // 32 KiB of LDS each: five workgroups fit a CU
-    if (const int force = g_rx_force_grid.load(); force > 0) // test hook: a starved grid (krep_gpu_debug_force_regex_grid)
-        grid = std::min<u32>(grid, (u32)force);
-    hipLaunchKernelGGL((regex_scan<ANCH, LINES, EMIT>), dim3(grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
+    return rx_launch_grid(regex_scan<ANCH, LINES, EMIT>, a, a.n_units, num_cu, 5, st); // 32 KiB of LDS each: five workgroups fit a CU
 }
-static hipError_t rx_run(const RxArgs &a, bool lines, bool emit, int num_cu, hipStream_t st)
+static hipError_t rx_run(const RxArgs &a, int mode, int num_cu, hipStream_t st)
 {
-    if (lines)
+    if (mode == kRxLines)
         return rx_launch<false, true, false>(a, num_cu, st);
+    const bool emit = mode == kRxEmit;
     if (a.n_anchor)
         return emit ? rx_launch<true, false, true>(a, num_cu, st) : rx_launch<true, false, false>(a, num_cu, st);
     return emit ? rx_launch<false, false, true>(a, num_cu, st) : rx_launch<false, false, false>(a, num_cu, st);
@@ -383,94 +292,81 @@ void regex_prog_free(RegexProg *rx)
     delete rx;
 }
 
-// ------------------------------------------------------------------------------------------------ the scan of a window
-int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
-               const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out)
+// ------------------------------------------------------------------------------------------------ the window driver of both scans
+int rx_window(const krep_gpu_plan *pl, const Window &w, const match_position_t *d_pos, uint64_t cap, const RxSpec &sp, RxWindow *g)
 {
-    memset(out, 0, sizeof *out);
-    if (carry_out)
-        *carry_out = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
-    if (!pl->rx)
-        return fail("scan_device: the regex plan holds no program");
-    if (pl->rx->is_alt)
-        return scan_regex_alt(pl, w, d_pos, cap, st, time_it, out);
-    const krep_gpu_regex_info_t &info = pl->rx->info.seq;
-    const u32 L = info.L, bol = pl->rx->info.bol ? 1u : 0u, eol = pl->rx->info.eol ? 1u : 0u;
-    if (w.global_len < L || w.text_len < L || w.own_lo >= w.own_hi)
-        return 0; // (text_len == 0 included: L >= 1 matches no empty string)
-    const size_t own_hi = std::min(w.own_hi, w.text_len);
-    const u64 hi_match = std::min<u64>(own_hi, w.text_len - L + 1);
-    const bool lines = pl->lines, greedy = info.self_overlap && !lines;
-    const bool whole = w.global_base == 0 && w.own_lo == 0 && own_hi + L > w.text_len && w.global_len == w.text_len;
-    if (greedy && !whole)
-        return fail("this regex can overlap itself, its matches are the greedy selection over the whole occurrence list: scan the whole "
-                    "text in one window (krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
-    if (own_hi <= w.own_lo || (!lines && hi_match <= w.own_lo))
+    *g = RxWindow{};
+    g->empty = true;
+    if (w.global_len < sp.Lmin || w.text_len < sp.Lmin || w.own_lo >= w.own_hi)
+        return 0; // (text_len == 0 included: no occurrence is empty)
+    g->own_hi = std::min(w.own_hi, w.text_len);
+    g->hi_match = std::min<u64>(g->own_hi, w.text_len - sp.Lmin + 1);
+    g->lines = pl->lines;
+    g->greedy = sp.overlap && !g->lines;
+    const bool whole = w.global_base == 0 && w.own_lo == 0 && g->own_hi + sp.Lmin > w.text_len && w.global_len == w.text_len;
+    if (g->greedy && !whole)
+        return fail("%s", sp.one_window);
+    if (g->own_hi <= w.own_lo || (!g->lines && g->hi_match <= w.own_lo))
         return 0;
     // an anchor needs the byte in front of, or behind, every occurrence the window owns
     const bool ends_text = w.global_base + w.text_len == w.global_len;
-    if (bol && w.own_lo == 0 && w.global_base > 0)
+    if (sp.bol && w.own_lo == 0 && w.global_base > 0)
         return fail("regex with ^: the window owns buffer byte 0, which is not the start of the text (global_base > 0), and the byte in "
                     "front of it decides a match there: start the buffer at least one byte in front of own_lo");
-    if (eol && !ends_text && w.own_lo + L <= w.text_len && own_hi + L > w.text_len)
-        return fail("regex with $: the window owns a start whose occurrence ends on the last byte of a buffer that does not end the "
-                    "text, and the byte behind it decides the match: end own_hi at least L bytes in front of the buffer's end");
-    const size_t maxc = pl->max_count;
-    const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(maxc, cap) : 0;
-
-    RxArgs a{};
-    a.text = w.d_text; a.text_len = w.text_len;
-    a.anchor = w.own_lo & ~(u64)15;
-    a.own_lo = w.own_lo; a.hi_match = std::max<u64>(hi_match, w.own_lo);
-    a.nl_hi = own_hi;
-    const u32 sh = L - 1 + eol;
-    a.cov_hi = (lines ? (u64)own_hi : a.hi_match) + sh; // (with $ in the buffer that ends the text this reaches text_len + 1)
-    a.n_units = (a.cov_hi - a.anchor + kRxUnitBytes - 1) / kRxUnitBytes;
-    a.global_base = w.global_base;
+    if (sp.eol && !ends_text)
+        for (u32 i = 0; i < sp.n_lens; ++i)
+            if (const u32 L = sp.lens[i]; w.own_lo + L <= w.text_len && g->own_hi + L > w.text_len)
+                return fail("regex with $: the window owns a start whose occurrence ends on the last byte of a buffer that does not end the "
+                            "text, and the byte behind it decides the match: end own_hi at least L bytes in front of the buffer's end");
+    g->empty = false;
+    g->entry0 = sp.bol && w.global_base == 0 ? 1u : 0u;
     // (regex_search ORs REG_ICASE into regexec's eflags, where that bit is REG_NOTEOL: under -i the end of the text ends no line)
-    const u32 entry0 = bol && w.global_base == 0 ? 1u : 0u, vnl = eol && ends_text && pl->sp.case_sensitive ? 1u : 0u;
-    a.geom = L | ((L + bol + eol) << 8) | (sh << 16) | (entry0 << 24) | (vnl << 25);
-    a.n_anchor = lines ? 0 : info.n_anchor;
-    for (u32 i = 0; i < 4; ++i)
-        a.ab[i] = 0x01010101u * info.anchor_bytes[i < info.n_anchor ? i : 0];
-    a.table = pl->rx->d_table;
-    a.ctr = pl->d_ctr;
+    g->eot = sp.eol && ends_text && pl->sp.case_sensitive ? 1u : 0u;
+    g->want = (d_pos && cap && !g->lines && pl->track) ? std::min<u64>(pl->max_count, cap) : 0;
+    return 0;
+}
 
+int rx_drive(krep_gpu_plan *pl, const Window &w, const RxSpec &sp, const RxWindow &g, match_position_t *d_pos, uint64_t cap, hipStream_t st,
+             int time_it, RxOut *o, u64 n_units, const std::function<hipError_t(int)> &launch, krep_gpu_scan_out_t *out)
+{
+    const bool lines = g.lines, greedy = g.greedy;
+    const u64 want = g.want;
+    o->ctr = pl->d_ctr;
     HIPCHK(hipSetDevice(pl->device));
     if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
     const bool chain = lines || want || greedy;
     PostScratch &post = pl->post;
     if (chain)
     {
-        if (post_reserve(post, a.n_units, 0))
+        if (post_reserve(post, n_units, 0))
             return 2;
-        a.unitinfo = post.d_unitinfo;
-        a.offsets = (const u64 *)post.d_offsets;
+        o->unitinfo = post.d_unitinfo;
+        o->offsets = (const u64 *)post.d_offsets;
     }
     HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-    HIPCHK(rx_run(a, lines, false, pl->num_cu, st));
-    if (chain && post_offsets_pass(post, a.n_units, lines, pl->d_ctr, st))
+    HIPCHK(launch(lines ? kRxLines : kRxCount));
+    if (chain && post_offsets_pass(post, n_units, lines, pl->d_ctr, st))
         return 2;
     uint64_t total = 0, nlines = 0;
     unsigned long long summary = 0;
     if (greedy)
     {
-        // all occurrences into post.d_occ (sized once their number is known), then the greedy pass of kg_greedy.hip, consume = L
+        // all occurrences into post.d_occ (sized once their number is known; an alternation's in start order), then the greedy pass
+        // of kg_greedy.hip
         HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         const uint64_t n_occ = pl->h_ctr->total;
         HIPCHK(grow_scratch(post.occ_cap, n_occ, n_occ, {dev_buf(post.d_occ, n_occ * 2 * sizeof(uint64_t))}));
         if (n_occ)
         {
-            a.positions = (u64 *)post.d_occ;
-            a.pos_cap = n_occ;
-            HIPCHK(rx_run(a, false, true, pl->num_cu, st));
+            o->positions = (u64 *)post.d_occ;
+            o->pos_cap = n_occ;
+            HIPCHK(launch(kRxEmit));
+            if (sp.sort && order_records((match_position_t *)post.d_occ, n_occ, w.global_base + w.text_len + 1, st, false))
+                return 2;
             HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-            WalkSpec ws{};
-            ws.mode = kWalkGreedy;
-            ws.m = L;
-            if (const int rc = post_walk(post, w.d_text, w.text_len, w.global_base, ws, n_occ, (uint64_t *)d_pos, want, pl->d_ctr, pl->h_ctr,
-                                         st, &total, &nlines, nullptr))
+            if (const int rc = post_walk(post, w.d_text, w.text_len, w.global_base, sp.walk, n_occ, (uint64_t *)d_pos, want, pl->d_ctr,
+                                         pl->h_ctr, st, &total, &nlines, nullptr))
                 return rc;
         }
         summary = total ? (kLnHead | kLnTail) : 0;
@@ -479,9 +375,9 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
     {
         if (want)
         {
-            a.positions = (u64 *)d_pos;
-            a.pos_cap = want;
-            HIPCHK(rx_run(a, false, true, pl->num_cu, st));
+            o->positions = (u64 *)d_pos;
+            o->pos_cap = want;
+            HIPCHK(launch(kRxEmit));
         }
         HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -497,6 +393,7 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
     out->head_line_hit = (summary & kLnHead) != 0;
     out->tail_line_hit = (summary & kLnTail) != 0;
     // regex_search's return value (krep.c:1395, :1533): max_count == 0 answers 0 with -c or positions, else 1 on the first occurrence
+    const size_t maxc = pl->max_count;
     uint64_t store = 0;
     if (maxc == 0)
         out->count = (lines || pl->track) ? 0 : (total ? 1 : 0);
@@ -513,6 +410,48 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
         out->stored = std::min<uint64_t>(store, std::min<uint64_t>(total, want));
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the scan of a window
+int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
+               const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out)
+{
+    memset(out, 0, sizeof *out);
+    if (carry_out)
+        *carry_out = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
+    if (!pl->rx)
+        return fail("scan_device: the regex plan holds no program");
+    if (pl->rx->is_alt)
+        return scan_regex_alt(pl, w, d_pos, cap, st, time_it, out);
+    const krep_gpu_regex_info_t &info = pl->rx->info.seq;
+    const u32 L = info.L, bol = pl->rx->info.bol ? 1u : 0u, eol = pl->rx->info.eol ? 1u : 0u;
+    RxSpec sp{};
+    sp.lens = &L; sp.n_lens = 1; sp.Lmin = L;
+    sp.bol = bol; sp.eol = eol;
+    sp.overlap = info.self_overlap;
+    sp.one_window = "this regex can overlap itself, its matches are the greedy selection over the whole occurrence list: scan the whole "
+                    "text in one window (krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)";
+    sp.walk.mode = kWalkGreedy; sp.walk.m = L; // consume = L
+    RxWindow g;
+    if (const int rc = rx_window(pl, w, d_pos, cap, sp, &g); rc || g.empty)
+        return rc;
+
+    RxArgs a{};
+    a.text = w.d_text; a.text_len = w.text_len;
+    a.anchor = w.own_lo & ~(u64)15;
+    a.own_lo = w.own_lo; a.hi_match = std::max<u64>(g.hi_match, w.own_lo);
+    a.nl_hi = g.own_hi;
+    const u32 sh = L - 1 + eol;
+    a.cov_hi = (g.lines ? g.own_hi : a.hi_match) + sh; // (with $ in the buffer that ends the text this reaches text_len + 1)
+    a.n_units = (a.cov_hi - a.anchor + kRxUnitBytes - 1) / kRxUnitBytes;
+    a.global_base = w.global_base;
+    a.geom = L | ((L + bol + eol) << 8) | (sh << 16) | (g.entry0 << 24) | (g.eot << 25);
+    a.n_anchor = g.lines ? 0 : info.n_anchor;
+    for (u32 i = 0; i < 4; ++i)
+        a.ab[i] = 0x01010101u * info.anchor_bytes[i < info.n_anchor ? i : 0];
+    a.table = pl->rx->d_table;
+    return rx_drive(pl, w, sp, g, d_pos, cap, st, time_it, &a.o, a.n_units,
+                    [&](int mode) { return rx_run(a, mode, pl->num_cu, st); }, out);
 }
 } // namespace kg
 

@@ -1,9 +1,11 @@
 // kg_regex_alt.hip — krep -E for an ALTERNATION of fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile_alt and
-// krep_gpu_regex_compile_ext): ERROR|WARN|FATAL, cat|d[oi]g|b.rd, every -E run with several -e, colou?r, ^(ERROR|WARN).  The multi-branch shift-and scan kernel and its driver
-// kg::scan_regex_alt; kg_regex.hip keeps the single sequence and hands over when the plan's program is an alternation.
+// krep_gpu_regex_compile_ext): ERROR|WARN|FATAL, cat|d[oi]g|b.rd, every -E run with several -e, colou?r, ^(ERROR|WARN).  The multi-branch shift-and scan kernel and its scan
+// kg::scan_regex_alt; kg_regex.hip keeps the single sequence and hands over when the plan's program is an alternation.  The scan
+// names its pattern and fills the kernel's arguments; the window checks, the launches and the result are the window driver's
+// (rx_window / rx_drive, kg_regex.hip).  What the kernel does around its walks comes from kg_regex_dev.h.
 //
 // The kernel.  Branch i lives in bits [o_i, o_i + L_i) of a 32-bit state; T[byte] has bit o_i + j set when byte is in C[i][j]
-// (in LDS once per bank, as in kg_regex.hip: 32 KiB, five workgroups per CU); INIT holds every o_i, FIN every o_i + L_i - 1, and
+// (in LDS once per bank, rx_fill_table: 32 KiB); INIT holds every o_i, FIN every o_i + L_i - 1, and
 // one step is S = ((S << 1) | INIT) & T[b].  The bit a branch shifts out of its top lands on the next branch's INIT bit (set
 // anyway) or on a bit T never holds, so the branches do not disturb each other.
 // A lane takes 16 bytes.  (1) It walks its last Lmax - 1 bytes from the all-ones state: with every L_i <= 16 the state behind them
@@ -24,7 +26,7 @@
 //   -c: every owned hit moves to the common coordinate start + Lmax - 1, that is up by Lmax - L < 16 places: the low 16 bits of
 //     the shifted mask stay in the lane, the spill goes to the next lane (lane 63's to a scalar for the next cell; a unit rebuilds
 //     it from the 16 bytes in front of it: an occurrence that spills out of them starts inside them).  From there on the newline
-//     mask shifted by Lmax - 1, the line-state arithmetic and the info words are those of kg_regex.hip's -c mode.
+//     mask shifted by Lmax - 1, the line-state arithmetic and the info words are the shared ones (RxLineCarry, rx_unit_end).
 // Line anchors (krep_gpu_regex_compile_ext: ^(ERROR|WARN), (jpg|png)$, and what ?, {n,m} and inner groups expand into): the
 // instantiations with ANCH.  Every branch gets the place { '\n' } in front of (^) and / or behind ($) its classes, so branch i takes
 // Lx_i = L_i + bol + eol bits and everything above holds with the places Lx in the role of the lengths: the lookback is Lxmax - 1
@@ -69,14 +71,8 @@ struct RaArgs
     //   bit 12    a guarded load holds '\n' at offset text_len: $ in the buffer that ends the text (not under -i)
     u32 geom;
     const u32 *table;
-    u64 *unitinfo;      // count mode: per-unit info words (nullptr: only the total is wanted)
-    const u64 *offsets; // emit mode: exclusive index of each unit's first record
-    u64 *positions;
-    u64 pos_cap;
-    Counters *ctr;
+    RxOut o;            // what the window driver sets (kg_regex_dev.h)
 };
-
-constexpr int kRaCount = 0, kRaEmit = 1, kRaLines = 2;
 
 static __device__ __forceinline__ u32 ra_byte(const uint4 &d, int i)
 {
@@ -104,19 +100,6 @@ static __device__ __forceinline__ u32 ra_walk(const u32 *T, const uint4 &d, u32 
         H |= ((S & fin) != 0u ? 1u : 0u) << i;
     }
     return H;
-}
-// $: the newline behind the last byte of the text, put into the 16 bytes from q when they hold offset text_len
-static __device__ __forceinline__ void ra_put_eot(uint4 &d, u64 q, u64 text_len)
-{
-    const u64 rel = text_len - q;
-    if (rel < 16u)
-    {
-        const u32 nl = 0x0au << (8u * ((u32)rel & 3u)), w = (u32)rel >> 2;
-        d.x |= w == 0u ? nl : 0u;
-        d.y |= w == 1u ? nl : 0u;
-        d.z |= w == 2u ? nl : 0u;
-        d.w |= w == 3u ? nl : 0u;
-    }
 }
 // the same walk again for a lane that holds hits: f(k, L) for every branch that ends behind a byte k of H, L its places
 template <class F> static __device__ __forceinline__ void ra_hits(const u32 *T, const uint4 &d, u32 init, u32 fin, u32 E, u32 H, F &&f)
@@ -177,11 +160,9 @@ static __device__ __forceinline__ u32 ra_starts(const u32 *T, const uint4 &d, co
 template <int MODE, bool ANCH>
 __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
 {
-    constexpr bool LINES = MODE == kRaLines, EMIT = MODE == kRaEmit;
+    constexpr bool LINES = MODE == kRxLines, EMIT = MODE == kRxEmit;
     __shared__ u32 s_T[256 * 32];
-    for (u32 i = threadIdx.x; i < 256u * 32u; i += kBlock)
-        s_T[i] = a.table[i >> 5];
-    __syncthreads();
+    rx_fill_table(s_T, a.table);
     const u32 lane = lane_id(), wave = threadIdx.x >> 6;
     const u32 *T = s_T + (lane & 31u);
     // Lmax: the places of the longest branch; a start p is seen, or for -c put, at coordinate p + sh = p + Lmax - 1 - bol
@@ -208,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
             uint4 p = rx_load_guarded(a.text, a.text_len, pq);
             if constexpr (ANCH)
                 if (eot)
-                    ra_put_eot(p, pq, a.text_len);
+                    rx_put_eot(p, pq, a.text_len);
             x63 = __builtin_amdgcn_readfirstlane(ra_exit(T, p, a.init, first));
             if (LINES)
             {
@@ -220,23 +201,8 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
             }
         }
         u32 l_hits = 0;                           // per lane
-        u64 out_idx = EMIT ? a.offsets[unit] : 0; // uniform
-        // -c: the line state of the unit, as kg_regex.hip keeps it (carry arithmetic over the 64 lanes of a cell)
-        u32 l_cnt = 0, s_new = 0;
-        bool s_open = false, s_seen = false, s_head = false;
-        auto line_cell = [&](u64 B_nl, u64 B_any, u64 B_head, u64 B_tail) __attribute__((always_inline)) {
-            const u64 G = B_tail, P = ~(B_nl | B_any);
-            const unsigned __int128 sum = (unsigned __int128)(G | P) + G + (s_open ? 1u : 0u);
-            const u64 O = (u64)sum ^ P; // bit l: the line entering lane l already holds a match
-            s_new += (u32)__popcll(B_head & ~O);
-            if (!s_seen && B_nl)
-            {
-                const int f = __builtin_ctzll(B_nl);
-                s_head = (((O | B_head) >> f) & 1ull) != 0ull;
-                s_seen = true;
-            }
-            s_open = (u64)(sum >> 64) != 0ull;
-        };
+        u64 out_idx = EMIT ? a.o.offsets[unit] : 0; // uniform
+        RxLineCarry lc;                           // -c: the line state of the unit
 
         for (int r = 0; r < kRoundsBig; ++r)
         {
@@ -245,33 +211,7 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
                 break;
             const bool fast = seg + kSegBytes <= a.text_len;
             uint4 d[kCells];
-            if (fast)
-            {
-                const uint4 *src = reinterpret_cast<const uint4 *>(a.text + seg) + lane;
-#pragma unroll
-                for (int j = 0; j < kCells; ++j)
-                {
-                    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-                    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + j * kWave));
-                    d[j] = make_uint4(v.x, v.y, v.z, v.w);
-                }
-            }
-            else
-            {
-#pragma unroll
-                for (int j = 0; j < kCells; ++j)
-                {
-                    const u64 cb = seg + (u64)j * kCellBytes;
-                    d[j] = cb < a.cov_hi ? rx_load_guarded(a.text, a.text_len, cb + (u64)lane * 16u) : make_uint4(0u, 0u, 0u, 0u);
-                }
-                if constexpr (ANCH)
-                    if (eot)
-                    {
-#pragma unroll
-                        for (int j = 0; j < kCells; ++j)
-                            ra_put_eot(d[j], seg + (u64)j * kCellBytes + (u64)lane * 16u, a.text_len);
-                    }
-            }
+            rx_load_round(d, a, seg, lane, fast, eot);
 #pragma unroll
             for (int j = 0; j < kCells; ++j)
             {
@@ -297,11 +237,7 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
                     y63 = __builtin_amdgcn_readlane(mine, 63);
                     const u32 Hc = (M | prev) & 0xffffu; // the owned starts at coordinates q .. q + 15
                     l_hits += (u32)__popc(Hc);
-                    const u32 N = (((mine >> 16) << sh) | ((prev >> 16) >> (16u - sh))) & 0xffffu, Hs = Hc | N;
-                    l_cnt += (u32)__popc(Hc & ~(Hs - ((N << 1) & 0xffffu)));
-                    // head: the lowest flag is a match (one ON a newline belongs to the line it ends); tail: a match behind the last newline
-                    line_cell(__ballot(N != 0u), __ballot(Hc != 0u), __ballot((Hc & (Hs ^ (Hs - 1u))) != 0u),
-                              __ballot((Hc >> (32 - __clz((int)N))) != 0u));
+                    lc.lane16(Hc, mine >> 16, prev >> 16, sh);
                 }
                 else if (__ballot(H != 0u))
                 {
@@ -310,14 +246,7 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
                     l_hits += c;
                     if (EMIT)
                     {
-                        u32 incl = c;
-#pragma unroll
-                        for (int o = 1; o < 64; o <<= 1)
-                        {
-                            const u32 t = __shfl_up(incl, o);
-                            if (lane >= (u32)o)
-                                incl += t;
-                        }
+                        const u32 incl = rx_wave_incl(c, lane);
                         if (c)
                         {
                             u64 idx = out_idx + (incl - c);
@@ -325,10 +254,10 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
                                 const u64 s = q + k + 1u + bol - L;
                                 if (s >= a.own_lo && s < a.own_hi)
                                 {
-                                    if (idx < a.pos_cap)
+                                    if (idx < a.o.pos_cap)
                                     {
-                                        const u64 s0 = s + a.global_base, e0 = s0 + (L - bol - eol);
-                                        *reinterpret_cast<uint4 *>(a.positions + 2 * idx) = make_uint4((u32)s0, (u32)(s0 >> 32), (u32)e0, (u32)(e0 >> 32));
+                                        const u64 s0 = s + a.global_base;
+                                        rx_store_record(a.o.positions, idx, s0, s0 + (L - bol - eol));
                                     }
                                     ++idx;
                                 }
@@ -341,45 +270,21 @@ __global__ __launch_bounds__(kBlock) void regex_alt_scan(const RaArgs a)
         }
         if (EMIT)
             continue;
-        u32 h = l_hits, t = l_cnt;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1)
-        {
-            h += __shfl_xor(h, o);
-            if (LINES)
-                t += __shfl_xor(t, o);
-        }
-        acc_total += h;
-        if (a.unitinfo && lane == 0)
-        {
-            u64 info = (u64)h;
-            if (LINES)
-            {
-                const LineState ls{t + s_new, s_seen, s_seen ? s_head : s_open, s_open};
-                info |= line_bits(ls) | ((u64)(ls.cnt & kUiLineMask) << kUiLineShift);
-            }
-            else if (h)
-                info |= kLnHead | kLnTail;
-            a.unitinfo[unit] = info;
-        }
+        acc_total += rx_unit_end<LINES>(l_hits, lc, a.o.unitinfo, unit, lane);
     }
     if (!EMIT && lane == 0 && acc_total)
-        atomicAdd(&a.ctr->total, acc_total);
+        atomicAdd(&a.o.ctr->total, acc_total);
 }
 
-template <int MODE, bool ANCH> static hipError_t ra_launch_as(const RaArgs &a, int num_cu, hipStream_t st)
-{
-    const u64 blocks = (a.n_units + kWavesPerBlk - 1) / kWavesPerBlk;
-    // (32 KiB of LDS each would let five workgroups into a CU, but the kernel holds 112 to 125 VGPRs: four waves per SIMD, four workgroups)
-    u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 4));
-    if (const int force = g_rx_force_grid.load(); force > 0) // test hook: a starved grid (krep_gpu_debug_force_regex_grid)
-        grid = std::min<u32>(grid, (u32)force);
-    hipLaunchKernelGGL((regex_alt_scan<MODE, ANCH>), dim3(grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
-}
 template <int MODE> static hipError_t ra_launch(const RaArgs &a, int num_cu, hipStream_t st)
 {
-    return ((a.geom >> 9) & 3u) ? ra_launch_as<MODE, true>(a, num_cu, st) : ra_launch_as<MODE, false>(a, num_cu, st);
+    // (32 KiB of LDS each would let five workgroups into a CU, but the kernel holds 112 to 126 VGPRs: four waves per SIMD, four workgroups)
+    return ((a.geom >> 9) & 3u) ? rx_launch_grid(regex_alt_scan<MODE, true>, a, a.n_units, num_cu, 4, st)
+                                : rx_launch_grid(regex_alt_scan<MODE, false>, a, a.n_units, num_cu, 4, st);
+}
+static hipError_t ra_run(const RaArgs &a, int mode, int num_cu, hipStream_t st)
+{
+    return mode == kRxLines ? ra_launch<kRxLines>(a, num_cu, st) : mode == kRxEmit ? ra_launch<kRxEmit>(a, num_cu, st) : ra_launch<kRxCount>(a, num_cu, st);
 }
 
 // ------------------------------------------------------------------------------------------------ the scan of a window
@@ -387,125 +292,35 @@ int scan_regex_alt(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, 
                    krep_gpu_scan_out_t *out)
 {
     const RegexProg &rx = *pl->rx;
-    const u32 Lmin = rx.alt.Lmin, Lmax = rx.alt.Lmax;
-    if (w.global_len < Lmin || w.text_len < Lmin || w.own_lo >= w.own_hi)
-        return 0; // (text_len == 0 included: no branch matches the empty string)
-    const size_t own_hi = std::min(w.own_hi, w.text_len);
-    const bool lines = pl->lines, greedy = rx.alt.cross_overlap && !lines;
-    const bool whole = w.global_base == 0 && w.own_lo == 0 && own_hi + Lmin > w.text_len && w.global_len == w.text_len;
-    if (greedy && !whole)
-        return fail("two occurrences of this regex alternation can overlap, its matches are the greedy selection over the whole occurrence "
-                    "list: scan the whole text in one window (krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
-    if (own_hi <= w.own_lo)
-        return 0;
-    // an anchor needs the byte in front of, or behind, every occurrence the window owns (as in kg_regex.hip)
-    const u32 bol = rx.alt_bol, eol = rx.alt_eol;
-    const bool ends_text = w.global_base + w.text_len == w.global_len;
-    if (bol && w.own_lo == 0 && w.global_base > 0)
-        return fail("regex with ^: the window owns buffer byte 0, which is not the start of the text (global_base > 0), and the byte in "
-                    "front of it decides a match there: start the buffer at least one byte in front of own_lo");
-    if (eol && !ends_text)
-        for (u32 i = 0; i < rx.alt.n_branches; ++i)
-            if (const u32 L = rx.alt.branch[i].L; w.own_lo + L <= w.text_len && own_hi + L > w.text_len)
-                return fail("regex with $: the window owns a start whose occurrence ends on the last byte of a buffer that does not end the "
-                            "text, and the byte behind it decides the match: end own_hi at least L bytes in front of the buffer's end");
-    const size_t maxc = pl->max_count;
-    const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(maxc, cap) : 0;
+    const u32 Lmax = rx.alt.Lmax, bol = rx.alt_bol, eol = rx.alt_eol;
+    u32 lens[8]; // (n_branches <= 8, include/krep_gpu.h)
+    for (u32 i = 0; i < rx.alt.n_branches; ++i)
+        lens[i] = rx.alt.branch[i].L;
+    RxSpec sp{};
+    sp.lens = lens; sp.n_lens = rx.alt.n_branches; sp.Lmin = rx.alt.Lmin;
+    sp.bol = bol; sp.eol = eol;
+    sp.overlap = rx.alt.cross_overlap;
+    sp.one_window = "two occurrences of this regex alternation can overlap, its matches are the greedy selection over the whole occurrence "
+                    "list: scan the whole text in one window (krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)";
+    // every (end, branch) pair ordered by start: the longest record of a visited start is the match, consume = its own length
+    sp.walk.mode = kWalkAlt; sp.walk.m = Lmax;
+    sp.sort = true;
+    RxWindow g;
+    if (const int rc = rx_window(pl, w, d_pos, cap, sp, &g); rc || g.empty)
+        return rc;
 
     RaArgs a{};
     a.text = w.d_text; a.text_len = w.text_len;
     a.anchor = w.own_lo & ~(u64)15;
-    a.own_lo = w.own_lo; a.own_hi = own_hi;
-    // (regex_search ORs REG_ICASE into regexec's eflags, where that bit is REG_NOTEOL: under -i the end of the text ends no line)
-    const u32 entry0 = bol && w.global_base == 0 ? 1u : 0u, eot = eol && ends_text && pl->sp.case_sensitive ? 1u : 0u;
+    a.own_lo = w.own_lo; a.own_hi = g.own_hi;
     const u32 sh = Lmax - 1 + eol; // a start p is seen at p + L_i - 1 + eol and, for -c, put at p + sh
-    a.cov_hi = lines ? (u64)own_hi + sh : std::min<u64>((u64)own_hi + sh, w.text_len + eot); // (with $ this reaches text_len + 1)
+    a.cov_hi = g.lines ? g.own_hi + sh : std::min<u64>(g.own_hi + sh, w.text_len + g.eot); // (with $ this reaches text_len + 1)
     a.n_units = (a.cov_hi - a.anchor + kRxUnitBytes - 1) / kRxUnitBytes;
     a.global_base = w.global_base;
     a.init = rx.init; a.fin = rx.fin;
-    a.geom = (Lmax + bol + eol) | ((rx.alt.cross_overlap ? 1u : 0u) << 8) | (bol << 9) | (eol << 10) | (entry0 << 11) | (eot << 12);
+    a.geom = (Lmax + bol + eol) | ((rx.alt.cross_overlap ? 1u : 0u) << 8) | (bol << 9) | (eol << 10) | (g.entry0 << 11) | (g.eot << 12);
     a.table = rx.d_table;
-    a.ctr = pl->d_ctr;
-
-    HIPCHK(hipSetDevice(pl->device));
-    if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
-    const bool chain = lines || want || greedy;
-    PostScratch &post = pl->post;
-    if (chain)
-    {
-        if (post_reserve(post, a.n_units, 0))
-            return 2;
-        a.unitinfo = post.d_unitinfo;
-        a.offsets = (const u64 *)post.d_offsets;
-    }
-    HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-    HIPCHK(lines ? ra_launch<kRaLines>(a, pl->num_cu, st) : ra_launch<kRaCount>(a, pl->num_cu, st));
-    if (chain && post_offsets_pass(post, a.n_units, lines, pl->d_ctr, st))
-        return 2;
-    uint64_t total = 0, nlines = 0;
-    unsigned long long summary = 0;
-    if (greedy)
-    {
-        // every (end, branch) pair into post.d_occ (sized once their number is known), ordered by start, then the greedy pass of
-        // kg_greedy.hip: the longest record of a visited start is the match, consume = its own length
-        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const uint64_t n_occ = pl->h_ctr->total;
-        HIPCHK(grow_scratch(post.occ_cap, n_occ, n_occ, {dev_buf(post.d_occ, n_occ * 2 * sizeof(uint64_t))}));
-        if (n_occ)
-        {
-            a.positions = (u64 *)post.d_occ;
-            a.pos_cap = n_occ;
-            HIPCHK(ra_launch<kRaEmit>(a, pl->num_cu, st));
-            if (order_records((match_position_t *)post.d_occ, n_occ, w.global_base + w.text_len + 1, st, false))
-                return 2;
-            HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-            WalkSpec ws{};
-            ws.mode = kWalkAlt;
-            ws.m = Lmax;
-            if (const int rc = post_walk(post, w.d_text, w.text_len, w.global_base, ws, n_occ, (uint64_t *)d_pos, want, pl->d_ctr, pl->h_ctr,
-                                         st, &total, &nlines, nullptr))
-                return rc;
-        }
-        summary = total ? (kLnHead | kLnTail) : 0;
-    }
-    else
-    {
-        if (want)
-        {
-            a.positions = (u64 *)d_pos;
-            a.pos_cap = want;
-            HIPCHK(ra_launch<kRaEmit>(a, pl->num_cu, st));
-        }
-        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        total = pl->h_ctr->total;
-        nlines = pl->h_ctr->lines;
-        summary = lines ? pl->h_ctr->summary : (total ? (kLnHead | kLnTail) : 0);
-    }
-    if (time_it && stop_clock(pl, true, st, out))
-        return 2;
-    out->total_matches = total;
-    out->line_count = nlines;
-    out->has_newline = (summary & kLnNl) != 0;
-    out->head_line_hit = (summary & kLnHead) != 0;
-    out->tail_line_hit = (summary & kLnTail) != 0;
-    // regex_search's return value (krep.c:1395, :1533): max_count == 0 answers 0 with -c or positions, else 1 on the first occurrence
-    uint64_t store = 0;
-    if (maxc == 0)
-        out->count = (lines || pl->track) ? 0 : (total ? 1 : 0);
-    else if (lines)
-        out->count = std::min<uint64_t>(nlines, maxc);
-    else
-    {
-        out->count = std::min<uint64_t>(total, maxc);
-        store = (pl->track && d_pos) ? out->count : 0;
-    }
-    if (d_pos && cap && pl->track && !lines)
-    {
-        out->overflow = store > cap;
-        out->stored = std::min<uint64_t>(store, std::min<uint64_t>(total, want));
-    }
-    return 0;
+    return rx_drive(pl, w, sp, g, d_pos, cap, st, time_it, &a.o, a.n_units,
+                    [&](int mode) { return ra_run(a, mode, pl->num_cu, st); }, out);
 }
 } // namespace kg

@@ -85,4 +85,4 @@ for rep in range(int(os.environ.get("AB_REPS", "9"))):
             times[name].append(out.kernel_ms)
 for name, _ in plans:
     t = times[name]
-    print(f"{name:40s} {mode:5s} kind={kind} median {statistics.median(t):7.3f} ms  min {min(t):7.3f}  {n / statistics.median(t) / 1e6:7.1f} GB/s   count={counts[name]}")
+    print(f"{name:40s} {mode:5s} kind={kind} median {statistics.median(t):7.3f} ms  min {min(t):7.3f}  max {max(t):7.3f}  {n / statistics.median(t) / 1e6:7.1f} GB/s   count={counts[name]}")
