@@ -848,6 +848,72 @@ int krep_gpu_format_matches_window(const void *d_text, size_t text_len, const kr
                                    const krep_gpu_match_format_t *fmt /* NULL: all empty */, void *d_out, size_t out_capacity,
                                    krep_gpu_matches_window_out_t *out, void *stream);
 
+/* ---- a batch of texts in one scan: krep -r (search_directory_recursive() -> search_file() once per file, krep.c) ----
+ * One operator call costs 50-80 us of launch and synchronisation plus staging, so a tree of ten thousand files of 4-200 KiB never
+ * reaches the device one file at a time (min_text_bytes above).  A batch makes many texts ONE text: the items are packed into one
+ * device buffer with exactly one '\n' between neighbours (none in front of the first, none behind the last), the pack is scanned
+ * once with records, and the record list is cut back into per-item results on the device (krep_amd/csrc/kg_batch.hip).
+ * Contract: for every item i, results[i].count and the records [first_record, first_record + n_records) of `records` are what the
+ *   operator krep_gpu_select_search_algorithm(params) returns produces for (items[i].text, items[i].len) ALONE — the same count, every
+ *   (start, end) relative to the item's own first byte, the reference's emission order inside an item; items appear in `records`
+ *   in item order.  An item of length 0 has count 0.  n_records is 0 when positions are not tracked (track_positions == false,
+ *   or count_lines_mode: the pack is scanned with records and an item's count is the number of distinct lines that hold one of its
+ *   record starts; the records themselves are not returned).
+ * When that is exact: a search is batchable iff its result is newline-separable — for all texts A and B, result(A + '\n' + B) =
+ *   result(A) followed by result(B) shifted by |A| + 1 (under -c: count(A + '\n' + B) = count(A) + count(B)).  That holds when no
+ *   match can contain '\n' (matches neither cross the separator nor couple across it: the greedy and -o selections included), -w
+ *   sees a non-word byte at both item edges ('\n' is one), and the reference function behaves the same wherever a line stands in
+ *   the text.  krep_gpu_batch_can_accelerate() is 1 iff krep_gpu_can_accelerate(params) is 1 and none of these holds (each has its
+ *   own reason in krep_gpu_last_error()):
+ *   - a literal pattern holds '\n';
+ *   - under -E a byte class of the compiled program holds '\n' ([[:space:]], [^a] never does in glibc's C locale: REG_NEWLINE);
+ *     ^ and $ are fine (the separator is a real newline, the first and last item sit at the true text edges) — except $ with
+ *     case_sensitive == false: the REG_NOTEOL quirk (the end of the text ends no line) applies at the end of EVERY item alone and
+ *     in the pack only at the end of the last;
+ *   - the reference function places behaviour by absolute position or by the whole text's length (what krep_gpu_scan_device_ex()
+ *     needs global_len for, and what krep_gpu_split_mode() calls WHOLE): -c through the block loops of simd_avx512_search,
+ *     simd_avx2_search with -w and neon_search (the end-of-text replay); simd_avx512_search without -c (the block it leaves
+ *     unexamined at the text's end); -w through the scalar tail of simd_avx2_search / simd_avx512_search / neon_search (its first
+ *     byte has no left neighbour); neon_search with max_count == 0; -c with -o through memchr_short_search.  A regex plan that is
+ *     WHOLE is NOT refused for that alone: its overlap never crosses a newline and the pack is scanned in one window;
+ *   - memchr_short_search under -o with a 3-byte pattern: its walk skips pattern_len bytes behind a FAILED candidate too
+ *     (krep.c:4495), so a candidate on the last byte of an item steps over the first byte of the next one — alone, the item ends
+ *     the walk there;
+ *   - -o through simd_avx2_search / neon_search with a pattern that can overlap itself: the block body reports every occurrence,
+ *     the scalar tail is boyer_moore_search, which under -o skips a match's length (krep.c:1371), and where that tail begins
+ *     depends on the whole text's length;
+ *   - max_count != SIZE_MAX: the per-function max_count quirks are a property of each item's own list; cutting per item is
+ *     follow-up work.
+ * Failure (a refused search, allocation, copy, launch): nothing is appended to `records`, `results` is not written, the call
+ *   returns 2 and krep_gpu_last_error() names the reason.  The batch call has NO CPU fallback of its own (the selector registered
+ *   with krep_gpu_set_cpu_fallback() is not asked): the caller loops over its files with its CPU function, as it does today.
+ * Size: a batch whose packed size exceeds what one device buffer of the host path takes (two pieces of cfg->stream_chunk_bytes,
+ *   256 MiB by default) is scanned in several packs, cut between items and never inside one; info->scans says how many.
+ * items[i].text are HOST pointers; records == NULL: counts only.  cfg == NULL: the calling thread's current configuration;
+ *   the pack runs on cfg->device alone (sharding a batch over several devices is follow-up work). */
+typedef struct krep_gpu_batch_item
+{
+    const char *text; /* host pointer; may be NULL when len == 0 */
+    size_t len;
+} krep_gpu_batch_item_t;
+typedef struct krep_gpu_batch_result
+{
+    uint64_t count;        /* what the reference function returns for THIS item alone (matches, or lines under count_lines_mode) */
+    uint64_t first_record; /* index into records->positions of the item's first record                                          */
+    uint64_t n_records;    /* its records (0 when positions are not tracked)                                                     */
+} krep_gpu_batch_result_t;
+typedef struct krep_gpu_batch_info
+{
+    uint64_t packed_bytes;  /* bytes staged: the items and the separators between them, over all packs */
+    uint64_t scans;         /* packs scanned                                                           */
+    uint64_t total_records; /* records the scans produced (under count_lines_mode too)                 */
+    float kernel_ms;        /* hipEvent time of the scan kernels, summed over the packs                */
+} krep_gpu_batch_info_t;
+int krep_gpu_batch_can_accelerate(const search_params_t *params); /* 1 / 0, the reason in krep_gpu_last_error() */
+int krep_gpu_search_batch(const search_params_t *params, const krep_gpu_config_t *cfg /* NULL: current */,
+                          const krep_gpu_batch_item_t *items, size_t n_items, krep_gpu_batch_result_t *results /* n_items */,
+                          match_result_t *records /* nullable */, krep_gpu_batch_info_t *info /* nullable */); /* 0, or 2 */
+
 int krep_gpu_device_count(void);
 const char *krep_gpu_last_error(void); /* "" when the last call on this thread succeeded */
 void krep_gpu_clear_error(void);

@@ -73,6 +73,12 @@ int krep_gpu_debug_anchor_info(const krep_gpu_plan_t *plan, int *state, uint32_t
 /* what the last general-kernel scan of `plan` MEASURED (candidates per tested position, counted in the kernel), and how many times a
  * measurement that contradicted the estimate re-opened the decision (at most 3; $KREP_GPU_AC_NO_RESAMPLE=1: never) */
 int krep_gpu_debug_anchor_measured(const krep_gpu_plan_t *plan, double *measured, int *resamples);
+/* test hook of krep_gpu_search_batch(): the packed size at which a batch is cut into a further pack (0 = the default, two pieces of
+ * the configuration's stream_chunk_bytes), so that a batch of a few hundred KiB takes several scans */
+void krep_gpu_debug_batch_pack_limit(size_t bytes);
+/* where the calling thread's last krep_gpu_search_batch() spent its time, in milliseconds of wall clock: gathering the items into
+ * the pinned staging ring and copying them to the device, the scan, the segmentation kernels, the read-back (tools/batch_bench.py) */
+void krep_gpu_debug_batch_times(double *pack_ms, double *scan_ms, double *segment_ms, double *readback_ms);
 
 #ifdef __cplusplus
 }

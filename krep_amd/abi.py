@@ -163,6 +163,21 @@ class ShardInfo(C.Structure):
                 ("reduced_by", C.c_int)]
 
 
+class BatchItem(C.Structure):
+    """krep_gpu_batch_item_t: one text of a batch (a host pointer and its length)"""
+    _fields_ = [("text", C.c_void_p), ("len", C.c_size_t)]
+
+
+class BatchResult(C.Structure):
+    """krep_gpu_batch_result_t: what krep_gpu_search_batch reports per item"""
+    _fields_ = [("count", C.c_uint64), ("first_record", C.c_uint64), ("n_records", C.c_uint64)]
+
+
+class BatchInfo(C.Structure):
+    """krep_gpu_batch_info_t: what a whole krep_gpu_search_batch call took"""
+    _fields_ = [("packed_bytes", C.c_uint64), ("scans", C.c_uint64), ("total_records", C.c_uint64), ("kernel_ms", C.c_float)]
+
+
 STATUS_OK, STATUS_FELL_BACK, STATUS_FAILED = 0, 1, 2
 SPLIT_WHOLE, SPLIT_PIECES, SPLIT_CHAIN = 0, 1, 2
 

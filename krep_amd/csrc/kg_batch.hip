@@ -1,0 +1,332 @@
+// kg_batch.hip — a batch of texts in one scan (krep_gpu_search_batch, include/krep_gpu.h "a batch of texts in one scan"): the reference's
+// -r mode meets many small texts, and one operator call per text costs more than scanning it.  The items of a batch are packed into one
+// device buffer with one '\n' between neighbours (kg_exec.hip host_batch_pack), the pack is scanned once with records, and the record
+// list is cut back into per-item results HERE:
+//   batch_bounds     one thread per item: lower bounds of the item's base offsets over the record starts -> first_record, n_records, count
+//   batch_rebase     one thread per record: its item by binary search over the offset table (in LDS when it fits), start and end made
+//                    relative to the item's first byte
+//   batch_line_flags -c: 1 where a record's line differs from its predecessor's; an exclusive sum over the flags makes an item's
+//                    distinct-line count the difference at its two bounds (no loop per item: one item may hold every record)
+// and the rule that says when all this is exact (kg::batch_unsupported_reason: newline-separable searches only).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstring>
+#include <vector>
+
+#include "../../include/krep_gpu.h"
+#include "kg_device.h"
+#include "kg_internal.h"
+
+using namespace kg;
+
+namespace kg {
+namespace {
+constexpr u32 kBatchLdsItems = 4096; // offset-table entries (items + 1) batch_rebase keeps in LDS: 32 KiB
+constexpr u32 kRebasePerBlock = 2048; // records one workgroup of batch_rebase walks: the table load is paid once per 2048 records
+
+// first index k in [0, n) whose record starts at or behind `key` (n when none): the list is item-contiguous in item order, so
+// "starts in front of an item's base" is a prefix of it whether it ascends in start (single literal, regex) or in end (multi-pattern)
+__device__ __forceinline__ u64 first_record_at(const u64 *__restrict__ rec, u64 n, u64 key)
+{
+    u64 lo = 0, hi = n;
+    while (lo < hi)
+    {
+        const u64 mid = lo + (hi - lo) / 2;
+        if (rec[2 * mid] < key)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// (a) res[i] = {count, first_record, n_records}.  prefix != NULL (-c): count = the flags summed over the item's records.
+__global__ void __launch_bounds__(256) batch_bounds(const u64 *__restrict__ rec, u64 n_rec, const u64 *__restrict__ off, u64 n_items,
+                                                    u64 rec_base, int report, const u64 *__restrict__ prefix,
+                                                    const u64 *__restrict__ flags, u64 *__restrict__ res)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items)
+        return;
+    const u64 lo = first_record_at(rec, n_rec, off[i]), hi = first_record_at(rec, n_rec, off[i + 1]);
+    u64 count = hi - lo;
+    if (prefix && n_rec)
+    {
+        const u64 total = prefix[n_rec - 1] + flags[n_rec - 1];
+        count = (hi < n_rec ? prefix[hi] : total) - (lo < n_rec ? prefix[lo] : total);
+    }
+    res[3 * i] = count;
+    res[3 * i + 1] = report ? rec_base + lo : rec_base;
+    res[3 * i + 2] = report ? hi - lo : 0;
+}
+
+// (b) every record relative to its item's first byte.  LDS: off[0 .. n_items] fits kBatchLdsItems entries.
+template <bool LDS>
+__global__ void __launch_bounds__(256) batch_rebase(u64 *__restrict__ rec, u64 n_rec, const u64 *__restrict__ off, u64 n_items)
+{
+    __shared__ u64 s_off[LDS ? kBatchLdsItems : 1];
+    if (LDS)
+    {
+        for (u32 t = threadIdx.x; t <= (u32)n_items; t += blockDim.x)
+            s_off[t] = off[t];
+        __syncthreads();
+    }
+    const u64 *tab = LDS ? s_off : off;
+    const u64 k0 = (u64)blockIdx.x * kRebasePerBlock, k1 = k0 + kRebasePerBlock < n_rec ? k0 + kRebasePerBlock : n_rec;
+    for (u64 k = k0 + threadIdx.x; k < k1; k += blockDim.x)
+    {
+        uint4 r = *reinterpret_cast<const uint4 *>(rec + 2 * k);
+        const u64 start = ((u64)r.y << 32) | r.x, end = ((u64)r.w << 32) | r.z;
+        u64 lo = 0, hi = n_items; // the last item whose base is at or in front of the start: tab[lo] <= start < tab[hi]
+        while (hi - lo > 1)
+        {
+            const u64 mid = lo + (hi - lo) / 2;
+            if (tab[mid] <= start)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const u64 base = tab[lo], s = start - base, e = end - base;
+        r.x = (u32)s; r.y = (u32)(s >> 32); r.z = (u32)e; r.w = (u32)(e >> 32);
+        *reinterpret_cast<uint4 *>(rec + 2 * k) = r;
+    }
+}
+
+// (c) -c: record k opens a line when its line differs from record k-1's.  The first record of an item always does: the separator
+// in front of the item is a '\n', so its line number is larger than that of every record of the items before it.
+__global__ void __launch_bounds__(256) batch_line_flags(const u64 *__restrict__ lines, u64 n_rec, u64 *__restrict__ flags)
+{
+    const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_rec)
+        flags[k] = (k == 0 || lines[k] != lines[k - 1]) ? 1 : 0;
+}
+
+std::atomic<size_t> g_pack_limit{0};                // krep_gpu_debug_batch_pack_limit
+thread_local double tl_batch_ms[4] = {0, 0, 0, 0}; // krep_gpu_debug_batch_times
+
+bool holds_newline(const uint8_t cls[32]) { return (cls['\n' >> 3] >> ('\n' & 7)) & 1; }
+} // namespace
+
+void batch_scratch_free(BatchScratch &s)
+{
+    for (void *p : {(void *)s.d_off, (void *)s.d_res, (void *)s.d_lines, (void *)s.d_flags, (void *)s.d_prefix, (void *)s.d_sums})
+        if (p)
+            (void)hipFree(p);
+    s = BatchScratch{};
+}
+
+int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const uint64_t *h_off, uint64_t n_items, match_position_t *d_pos,
+                  uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st)
+{
+    if (!n_items)
+        return 0;
+    {
+        const uint64_t want = std::max<uint64_t>(n_items + n_items / 2, 1024);
+        HIPCHK(grow_scratch(s.items_cap, n_items, want,
+                            {dev_buf(s.d_off, (want + 1) * sizeof(u64)), dev_buf(s.d_res, want * sizeof(krep_gpu_batch_result_t))}));
+    }
+    if (lines && n_rec)
+    {
+        const uint64_t want = std::max<uint64_t>(n_rec + n_rec / 2, 1u << 16);
+        HIPCHK(grow_scratch(s.rec_cap, n_rec, want,
+                            {dev_buf(s.d_lines, want * sizeof(uint64_t)), dev_buf(s.d_flags, want * sizeof(u64)),
+                             dev_buf(s.d_prefix, want * sizeof(u64)), dev_buf(s.d_sums, (scan_sums_words(want) + 1) * sizeof(u64))}));
+    }
+    HIPCHK(hipMemcpyAsync(s.d_off, h_off, (n_items + 1) * sizeof(u64), hipMemcpyHostToDevice, st));
+    const u64 *prefix = nullptr, *flags = nullptr;
+    if (lines && n_rec)
+    {
+        // the line of every record's start, in start order (a multi-pattern list comes in end order: two records of one line may
+        // have a record of the next line between them there)
+        if (by_end && krep_gpu_order_by_start(d_pos, n_rec, packed, st))
+            return 2;
+        if (krep_gpu_line_numbers(d_text, packed, d_pos, n_rec, s.d_lines, st))
+            return 2;
+        hipLaunchKernelGGL(batch_line_flags, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, st, (const u64 *)s.d_lines, (u64)n_rec, s.d_flags);
+        scan_exclusive(s.d_flags, n_rec, s.d_prefix, s.d_sums, false, st);
+        prefix = s.d_prefix;
+        flags = s.d_flags;
+    }
+    hipLaunchKernelGGL(batch_bounds, dim3((u32)((n_items + 255) / 256)), dim3(256), 0, st, (const u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off,
+                       (u64)n_items, (u64)rec_base, report ? 1 : 0, prefix, flags, s.d_res);
+    if (report && !lines && n_rec)
+    {
+        const u32 grid = (u32)((n_rec + kRebasePerBlock - 1) / kRebasePerBlock);
+        if (n_items + 1 <= kBatchLdsItems)
+            hipLaunchKernelGGL(batch_rebase<true>, dim3(grid), dim3(256), 0, st, (u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off, (u64)n_items);
+        else
+            hipLaunchKernelGGL(batch_rebase<false>, dim3(grid), dim3(256), 0, st, (u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off, (u64)n_items);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ when packing is exact
+// NULL: result(A + '\n' + B) = result(A), then result(B) shifted by |A| + 1, for all texts A and B (DESIGN.md §9 carries the code line
+// that makes each refused class depend on where a line stands in the text).
+const char *batch_unsupported_reason(const search_params_t *p, const krep_gpu_config_t &c)
+{
+    if (const char *why = unsupported_reason(p, c))
+        return why;
+    if (p->max_count != SIZE_MAX)
+        return "batch: max_count is a property of each item's own record list; cutting per item is follow-up work";
+    if (p->use_regex)
+    {
+        RegexCompiled rc;
+        if (const char *why = regex_compile_cached(p, &rc))
+            return why;
+        bool nl = false;
+        if (rc.is_alt)
+            for (uint32_t b = 0; b < rc.alt.n_branches; ++b)
+                for (uint32_t j = 0; j < rc.alt.branch[b].L; ++j)
+                    nl = nl || holds_newline(rc.alt.branch[b].classes[j]);
+        else
+            for (uint32_t j = 0; j < rc.seq.seq.L; ++j)
+                nl = nl || holds_newline(rc.seq.seq.classes[j]);
+        if (nl)
+            return "batch: a byte class of the expression holds '\\n': a match could take in the separator between two items";
+        if ((rc.is_alt ? rc.alt_eol : rc.seq.eol) && !p->case_sensitive)
+            return "batch: $ in a case-insensitive search: the end of the text ends no line there (REG_NOTEOL, krep.c:1420), which holds "
+                   "at the end of every item alone and in a pack only at the end of the last";
+        return nullptr;
+    }
+    NormParams np(p);
+    if (!np.valid)
+        return "no pattern";
+    const search_params_t *q = &np.sp;
+    for (size_t i = 0; i < q->num_patterns; ++i)
+        if (q->pattern_lens[i] && memchr(q->patterns[i], '\n', q->pattern_lens[i]))
+            return "batch: a pattern holds '\\n': a match could take in the separator between two items";
+    if (q->num_patterns > 1)
+        return nullptr;
+    const size_t m = q->pattern_len;
+    if (m == 0)
+        return nullptr;
+    // the function that does the work on a text that is not shorter than the pattern (a shorter item holds no match under any of them)
+    const int algo = mirror_effective(mirror_top(q, c), q, m);
+    const bool lines = q->count_lines_mode, ww = q->whole_word, om = c.only_matching != 0;
+    if (lines && (algo == KREP_RA_AVX512 || algo == KREP_RA_NEON || (algo == KREP_RA_AVX2 && ww)))
+        return "batch: -c through the block loop of simd_avx512_search / simd_avx2_search -w / neon_search replays the end of the TEXT "
+               "(krep.c:5203-5218, :5000-5013, :4590-4611): an item's count depends on where the item ends";
+    if (algo == KREP_RA_AVX512)
+        return "batch: simd_avx512_search leaves the last full 64-byte block of the TEXT unexamined (krep.c:5171): which block that is "
+               "depends on the length of everything in front of it";
+    if (ww && (algo == KREP_RA_AVX2 || algo == KREP_RA_NEON))
+        return "batch: -w through the scalar tail of simd_avx2_search / neon_search: the first byte of the TEXT's tail has no left "
+               "neighbour (krep.c:5059-5097), and where that tail begins depends on the whole text's length";
+    if (om && !lines && (algo == KREP_RA_AVX2 || algo == KREP_RA_NEON) && pattern_has_border((const uint8_t *)q->pattern, m))
+        return "batch: -o through simd_avx2_search / neon_search with a pattern that can overlap itself: the block body reports every "
+               "occurrence, the scalar tail is boyer_moore_search, which skips a match's length under -o (krep.c:1371), and where that "
+               "tail begins depends on the whole text's length";
+    if (algo == KREP_RA_MEMCHR_SHORT && om && lines)
+        return "batch: -c with -o through memchr_short_search jumps to the next line start after every counted line (krep.c:4449-4470): "
+               "one window over one text only";
+    if (algo == KREP_RA_MEMCHR_SHORT && om && m >= 3)
+        return "batch: memchr_short_search under -o skips pattern_len bytes behind a failed candidate too (krep.c:4495): with a 3-byte "
+               "pattern a candidate on the last byte of an item steps over the first byte of the next one";
+    return nullptr;
+}
+} // namespace kg
+
+extern "C" void krep_gpu_debug_batch_pack_limit(size_t bytes) { g_pack_limit.store(bytes); }
+extern "C" void krep_gpu_debug_batch_times(double *pack_ms, double *scan_ms, double *segment_ms, double *readback_ms)
+{
+    if (pack_ms) *pack_ms = tl_batch_ms[0];
+    if (scan_ms) *scan_ms = tl_batch_ms[1];
+    if (segment_ms) *segment_ms = tl_batch_ms[2];
+    if (readback_ms) *readback_ms = tl_batch_ms[3];
+}
+
+extern "C" int krep_gpu_batch_can_accelerate(const search_params_t *params)
+{
+    krep_gpu_clear_error();
+    const krep_gpu_config_t c = kg::current_config();
+    const char *why = kg::batch_unsupported_reason(params, c);
+    if (!why)
+        why = kg::device_unusable(c.device);
+    if (why)
+        kg::note_error(why);
+    return why ? 0 : 1;
+}
+
+extern "C" int krep_gpu_search_batch(const search_params_t *raw, const krep_gpu_config_t *cfg_in, const krep_gpu_batch_item_t *items,
+                                     size_t n_items, krep_gpu_batch_result_t *results, match_result_t *records,
+                                     krep_gpu_batch_info_t *info)
+{
+    krep_gpu_clear_error();
+    if (info)
+        *info = krep_gpu_batch_info_t{};
+    for (double &t : tl_batch_ms)
+        t = 0;
+    if (!raw || (n_items && (!items || !results)))
+        return kg::fail("search_batch: NULL params / items / results");
+    const krep_gpu_config_t cfg = cfg_in ? *cfg_in : kg::current_config();
+    // every refusal comes before any device work
+    if (const char *why = kg::batch_unsupported_reason(raw, cfg))
+        return kg::fail("%s", why);
+    NormParams np(raw);
+    if (!np.valid)
+        return kg::fail("no pattern");
+    for (size_t i = 0; i < n_items; ++i)
+        if (!items[i].text && items[i].len)
+            return kg::fail("search_batch: item %zu has a NULL text and a length of %zu", i, items[i].len);
+    if (const char *why = kg::device_unusable(cfg.device))
+        return kg::fail("%s", why);
+    if (!n_items)
+        return 0;
+    const search_params_t *params = &np.sp;
+    const bool lines = params->count_lines_mode;
+    const bool report = params->track_positions && records != nullptr && !lines;
+    const uint64_t count0 = records ? records->count : 0;
+    std::vector<krep_gpu_batch_result_t> res(n_items, krep_gpu_batch_result_t{0, count0, 0});
+    if (params->num_patterns > 1 && !params->ac_trie && !params->use_regex)
+    { // aho_corasick.c:306: no trie, no matches (several -E patterns are one alternation: no trie is involved)
+        memcpy(results, res.data(), n_items * sizeof *results);
+        return 0;
+    }
+    // the pack is scanned with RECORDS whatever the caller wants back: the list is what gets cut per item, under -c too
+    search_params_t scan = *params;
+    scan.count_lines_mode = false;
+    scan.track_positions = true;
+    scan.max_count = SIZE_MAX;
+    const size_t chunk = cfg.stream_chunk_bytes ? cfg.stream_chunk_bytes : ((size_t)128 << 20);
+    const size_t limit = g_pack_limit.load() ? g_pack_limit.load() : 2 * chunk;
+    DeviceGuard guard;
+    krep_gpu_batch_info_t bi{};
+    uint64_t appended = 0;
+    std::vector<uint64_t> off;
+    for (size_t i0 = 0; i0 < n_items;)
+    {
+        // the next pack: items [i0, i1), cut between items and never inside one (an item beyond the limit is a pack of its own)
+        off.assign(1, 0);
+        size_t i1 = i0;
+        for (; i1 < n_items; ++i1)
+        {
+            const uint64_t end = off.back() + items[i1].len; // (the separator in front of it is in off.back() already)
+            if (i1 > i0 && end > limit)
+                break;
+            off.push_back(end + 1);
+        }
+        uint64_t n_rec = 0;
+        float kms = 0;
+        if (kg::host_batch_pack(&scan, cfg, items + i0, i1 - i0, off.data(), lines, report, records, appended, res.data() + i0, &n_rec, &kms,
+                                tl_batch_ms))
+            return 2; // (records->count was never moved: nothing is appended)
+        bi.packed_bytes += off.back() - 1;
+        bi.scans += 1;
+        bi.total_records += n_rec;
+        bi.kernel_ms += kms;
+        if (report)
+            appended += n_rec;
+        i0 = i1;
+    }
+    memcpy(results, res.data(), n_items * sizeof *results);
+    if (report)
+        records->count = count0 + appended;
+    if (info)
+        *info = bi;
+    return 0;
+}

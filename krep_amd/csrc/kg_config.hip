@@ -38,6 +38,7 @@ int fail(const char *fmt, ...)
     return 2;
 }
 bool have_error() { return !g_err.empty(); }
+void note_error(const char *why) { g_err = why ? why : ""; }
 } // namespace kg
 extern "C" const char *krep_gpu_last_error(void) { return g_err.c_str(); }
 extern "C" void krep_gpu_clear_error(void) { g_err.clear(); }

@@ -291,6 +291,37 @@ struct Stager
             HIPCHK(hipEventRecord(after, st));
         return 0;
     }
+    // The same ring for bytes that are not contiguous on the host (a batch of texts packed into one, kg_batch.hip): fill(dst, off, n)
+    // writes bytes [off, off + n) of the packed text into the pinned chunk; the CPU fills chunk k+1 while the DMA of chunk k runs.
+    // Returns once the last DMA is done.
+    template <class Fill> int gather(uint8_t *d_dst, size_t len, Fill fill)
+    {
+        if (!ready)
+            return kg::fail("staging ring not initialised");
+        if (kg::inject(2))
+            return kg::fail("injected failure: host->device copy");
+        HIPCHK(hipSetDevice(dev));
+        for (size_t off = 0, n = 0; off < len; off += n, ++seq)
+        {
+            const int b = (int)(seq & 1);
+            n = len - off <= kChunk + kSlack ? len - off : kChunk;
+            if (seq >= 2)
+                HIPCHK(hipEventSynchronize(done[b])); // the DMA that last used this staging buffer
+            const size_t kT = n >= ((size_t)8 << 20) ? 4 : 1, part = (n + kT - 1) / kT; // (a large chunk: four host threads, as copy_async)
+            std::thread th[3];
+            for (size_t q = 1; q < kT; ++q)
+                if (q * part < n)
+                    th[q - 1] = std::thread([=] { fill(pin[b] + q * part, off + q * part, std::min(part, n - q * part)); });
+            fill(pin[b], off, std::min(part, n));
+            for (auto &t : th)
+                if (t.joinable())
+                    t.join();
+            HIPCHK(hipMemcpyAsync(d_dst + off, pin[b], n, hipMemcpyHostToDevice, st));
+            HIPCHK(hipEventRecord(done[b], st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }
     int copy(uint8_t *d_dst, const char *src, size_t len)
     {
         if (!ready)
@@ -357,6 +388,7 @@ struct DeviceCtx
     uint64_t tick = 0;
     Arena mem; // text buffer(s) + record area, one allocation
     Stager stager;
+    BatchScratch batch; // krep_gpu_search_batch: offset table, per-item results, the -c line flags (kg_batch.hip)
 
     krep_gpu_plan_t *plan_for(const search_params_t *p, const krep_gpu_config_t &c)
     {
@@ -392,6 +424,8 @@ struct DeviceCtx
         plans.clear();
         mem.release();
         stager.release();
+        (void)hipSetDevice(device);
+        batch_scratch_free(batch);
     }
 };
 std::mutex g_ctx_mu;
@@ -1085,6 +1119,84 @@ int host_scan(const search_params_t *params, const krep_gpu_config_t &cfg, const
     DeviceCtx *cx = ctx_for(cfg.device);
     std::lock_guard<std::mutex> lk(cx->mu);
     return run_whole(*cx, params, cfg, text, text_len, result, ret);
+}
+
+// ------------------------------------------------------------------------------------------------ a batch of texts as one text
+// One pack of krep_gpu_search_batch (kg_batch.hip): the items gathered through the staging ring into the arena's text buffer with a
+// '\n' between neighbours, ONE scan over the whole pack in one window with records (again at the exact size when the list
+// overflowed, as the operators do), the list cut per item on the device, results and rebased records read back in one copy each.
+int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t &cfg, const krep_gpu_batch_item_t *items, size_t n,
+                    const uint64_t *off, bool lines, bool report, match_result_t *records, uint64_t appended,
+                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms)
+{
+    using clk = std::chrono::steady_clock;
+    const auto since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    *n_rec_out = 0;
+    *kernel_ms = 0;
+    DeviceCtx &cx = *ctx_for(cfg.device);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    krep_gpu_plan_t *pl = cx.plan_for(scan_params, cfg);
+    if (!pl)
+        return 2;
+    const size_t packed = (size_t)off[n] - 1;
+    HIPCHK(hipSetDevice(cx.device));
+    if (cx.mem.ensure(packed + 64, 1, cx.device))
+        return 2;
+    uint8_t *const d_text = cx.mem.text(0);
+    auto t0 = clk::now();
+    if (packed)
+    {
+        // bytes [lo, lo + cnt) of the pack: item k lies at [off[k], off[k] + len), its separator on the byte behind it
+        const auto fill = [=](uint8_t *dst, size_t lo, size_t cnt) {
+            size_t k = (size_t)(std::upper_bound(off, off + n, (uint64_t)lo) - off) - 1;
+            for (size_t pos = lo, end = lo + cnt; pos < end; ++k)
+            {
+                const size_t ib = (size_t)off[k], ie = ib + items[k].len;
+                if (pos < ie)
+                {
+                    const size_t c = std::min(ie, end) - pos;
+                    memcpy(dst + (pos - lo), items[k].text + (pos - ib), c);
+                    pos += c;
+                }
+                if (pos < end && pos == ie)
+                    dst[pos++ - lo] = '\n';
+            }
+        };
+        if (cx.stager.init(cx.device) || cx.stager.gather(d_text, packed, fill))
+            return 2;
+    }
+    ms[0] += since(t0);
+    t0 = clk::now();
+    krep_gpu_scan_out_t so{};
+    match_position_t *d_pos = nullptr;
+    if (packed && sized_scan(cx, std::max<uint64_t>(1u << 16, packed / 64), so, &d_pos, [&](match_position_t *d, uint64_t c) {
+            return krep_gpu_scan_device_ex(pl, d_text, packed, 0, packed, 0, packed, d, c, nullptr, 1, &so);
+        }))
+        return 2;
+    if (so.overflow)
+        return kg::fail("search_batch: the record list outgrew its second, exact-size buffer");
+    ms[1] += since(t0);
+    t0 = clk::now();
+    const uint64_t n_rec = so.stored;
+    *kernel_ms = so.kernel_ms;
+    const uint64_t rec_base = (records ? records->count : 0) + (report ? appended : 0);
+    if (batch_segment(cx.batch, d_text, packed, off, n, d_pos, n_rec, rec_base, pl->ref_algo == KREP_RA_AHO_CORASICK, lines, report, nullptr))
+        return 2;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    ms[2] += since(t0);
+    t0 = clk::now();
+    if (kg::inject(4) || hipMemcpy(res_out, cx.batch.d_res, n * sizeof *res_out, hipMemcpyDeviceToHost) != hipSuccess)
+        return kg::fail("D2H copy of the batch results failed");
+    if (report && n_rec)
+    {
+        if (!result_reserve(records, appended + n_rec))
+            return kg::fail("out of memory growing match_result_t");
+        if (records_to_host(records->positions + records->count + appended, d_pos, n_rec))
+            return 2;
+    }
+    ms[3] += since(t0);
+    *n_rec_out = n_rec;
+    return 0;
 }
 } // namespace kg
 

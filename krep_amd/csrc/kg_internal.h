@@ -270,4 +270,86 @@ void cost_note_host_path(size_t bytes, double seconds); // a host-buffer operato
 int host_scan(const search_params_t *params, const krep_gpu_config_t &cfg, const char *text, size_t text_len, int num_gpus,
               match_result_t *result, uint64_t *ret);
 
+// ---- what the host-buffer entry points share (kg_ops.hip, kg_batch.hip)
+// One view of the caller's params: legacy callers fill only pattern / pattern_len (the reference's own
+// tests, test/test_krep.c:233-235), the CLI fills the arrays as well.  After this, num_patterns >= 1, patterns / pattern_lens
+// are valid and pattern / pattern_len name the first one (run_pieces read pattern_lens[] of the raw struct).
+struct NormParams
+{
+    search_params_t sp{};
+    const char *one_pat = nullptr;
+    size_t one_len = 0;
+    bool valid = false;
+    explicit NormParams(const search_params_t *p)
+    {
+        sp = *p;
+        if (p->num_patterns > 1)
+        {
+            valid = p->patterns && p->pattern_lens;
+            return;
+        }
+        if (p->num_patterns == 1 && p->patterns && p->pattern_lens && p->patterns[0])
+        {
+            one_pat = p->patterns[0];
+            one_len = p->pattern_lens[0];
+        }
+        else if (p->pattern)
+        {
+            one_pat = p->pattern;
+            one_len = p->pattern_len;
+        }
+        else
+            return;
+        sp.pattern = one_pat;
+        sp.pattern_len = one_len;
+        sp.patterns = &one_pat;
+        sp.pattern_lens = &one_len;
+        sp.num_patterns = 1;
+        valid = true;
+    }
+    NormParams(const NormParams &) = delete;
+    NormParams &operator=(const NormParams &) = delete;
+};
+// restores the calling thread's current HIP device: the operators are called on the HOST's threads (krep.c:1950), and a
+// library must not leave their device changed
+struct DeviceGuard
+{
+    int prev = -1;
+    DeviceGuard() { (void)hipGetDevice(&prev); (void)hipGetLastError(); }
+    ~DeviceGuard()
+    {
+        if (prev >= 0)
+            (void)hipSetDevice(prev);
+    }
+};
+void note_error(const char *why); // kg_config.hip: sets krep_gpu_last_error() without printing (a refusal that is an answer, not a failure)
+
+// kg_batch.hip — a batch of texts in one scan (krep_gpu_search_batch): when packing is exact, and the segmentation of a pack's records
+const char *batch_unsupported_reason(const search_params_t *p, const krep_gpu_config_t &c); // NULL: newline-separable, taken
+struct BatchScratch // grow-only, one per device context
+{
+    unsigned long long *d_off = nullptr; // [items + 1] base offset of every item in the pack; the last entry is packed size + 1
+    unsigned long long *d_res = nullptr; // [items] krep_gpu_batch_result_t
+    uint64_t items_cap = 0;
+    uint64_t *d_lines = nullptr;          // -c: [records] line number of every record's start
+    unsigned long long *d_flags = nullptr; // ... 1 where a record opens a line nobody before it counted
+    unsigned long long *d_prefix = nullptr; // ... their exclusive sum
+    unsigned long long *d_sums = nullptr;   // ... scratch of that sum
+    uint64_t rec_cap = 0;
+};
+void batch_scratch_free(BatchScratch &s);
+// The record list of one pack (n_rec records in d_pos, the reference's emission order; by_end: a multi-pattern list) cut into the
+// n_items results of s.d_res on `st` (not synchronised): first_record = rec_base + the item's first index when `report`, else rec_base
+// with n_records = 0; lines: count = the distinct lines of the item's record starts, the list is ordered by start on the way and not
+// rebased; else count = the item's records and, with `report`, every record is rebased to its item's first byte.  h_off: the table above.
+int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const uint64_t *h_off, uint64_t n_items, match_position_t *d_pos,
+                  uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st);
+// kg_exec.hip — one pack through the device context of cfg.device: gathered through the staging ring into the arena, scanned in one
+// window with the records plan `scan_params`, segmented, read back.  res_out[n]: the items' results; with `report` the rebased records go
+// to records->positions behind records->count + appended (the block grows, count is left alone: a later failure appends nothing).
+// ms[4] += wall clock of packing / scan / segmentation / read-back.  2: failed.
+int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t &cfg, const krep_gpu_batch_item_t *items, size_t n,
+                    const uint64_t *off, bool lines, bool report, match_result_t *records, uint64_t appended,
+                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms);
+
 } // namespace kg

@@ -17,58 +17,6 @@ using namespace kg;
 
 // ------------------------------------------------------------------------------------------------ dispatcher
 namespace {
-// One view of the caller's params for everything below: legacy callers fill only pattern / pattern_len (the reference's own
-// tests, test/test_krep.c:233-235), the CLI fills the arrays as well.  After this, num_patterns >= 1, patterns / pattern_lens
-// are valid and pattern / pattern_len name the first one (run_pieces read pattern_lens[] of the raw struct).
-struct NormParams
-{
-    search_params_t sp{};
-    const char *one_pat = nullptr;
-    size_t one_len = 0;
-    bool valid = false;
-    explicit NormParams(const search_params_t *p)
-    {
-        sp = *p;
-        if (p->num_patterns > 1)
-        {
-            valid = p->patterns && p->pattern_lens;
-            return;
-        }
-        if (p->num_patterns == 1 && p->patterns && p->pattern_lens && p->patterns[0])
-        {
-            one_pat = p->patterns[0];
-            one_len = p->pattern_lens[0];
-        }
-        else if (p->pattern)
-        {
-            one_pat = p->pattern;
-            one_len = p->pattern_len;
-        }
-        else
-            return;
-        sp.pattern = one_pat;
-        sp.pattern_len = one_len;
-        sp.patterns = &one_pat;
-        sp.pattern_lens = &one_len;
-        sp.num_patterns = 1;
-        valid = true;
-    }
-    NormParams(const NormParams &) = delete;
-    NormParams &operator=(const NormParams &) = delete;
-};
-
-// restores the calling thread's current HIP device: the operators are called on the HOST's threads (krep.c:1950), and a
-// library must not leave their device changed
-struct DeviceGuard
-{
-    int prev = -1;
-    DeviceGuard() { (void)hipGetDevice(&prev); (void)hipGetLastError(); }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
 thread_local int tl_status = KREP_GPU_OK;
 std::atomic<krep_gpu_cpu_select_t> g_cpu_select{nullptr};
 } // namespace

@@ -171,6 +171,16 @@ class Engine:
         if hasattr(L, "krep_gpu_debug_force_regex_grid"):
             L.krep_gpu_debug_force_regex_grid.restype = None
             L.krep_gpu_debug_force_regex_grid.argtypes = [C.c_int]
+        if hasattr(L, "krep_gpu_search_batch"):  # (an older build loaded as an A/B partner lacks it: tools/ab_bench.py)
+            L.krep_gpu_batch_can_accelerate.restype = C.c_int
+            L.krep_gpu_batch_can_accelerate.argtypes = [C.POINTER(abi.SearchParams)]
+            L.krep_gpu_search_batch.restype = C.c_int
+            L.krep_gpu_search_batch.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.Config), C.POINTER(abi.BatchItem), C.c_size_t,
+                                                C.POINTER(abi.BatchResult), C.POINTER(abi.MatchResult), C.POINTER(abi.BatchInfo)]
+            L.krep_gpu_debug_batch_pack_limit.restype = None
+            L.krep_gpu_debug_batch_pack_limit.argtypes = [C.c_size_t]
+            L.krep_gpu_debug_batch_times.restype = None
+            L.krep_gpu_debug_batch_times.argtypes = [C.POINTER(C.c_double)] * 4
         if hasattr(L, "krep_gpu_alloc_placed"):
             L.krep_gpu_alloc_placed.restype = C.c_int
             L.krep_gpu_alloc_placed.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -541,6 +551,50 @@ class Engine:
             params.s.ac_trie = None
         del keep
         return int(ret), pos
+
+    # ---- a batch of texts in one scan (krep -r) ----
+    def batch_can_accelerate(self, params: abi.Params) -> bool:
+        """krep_gpu_batch_can_accelerate(): is the search newline-separable (and taken at all); last_error() says why not."""
+        return bool(self.lib.krep_gpu_batch_can_accelerate(params.ref))
+
+    def batch_pack_limit(self, nbytes: int):
+        """test hook: the packed size at which a batch is cut into a further pack (0: the default)"""
+        self.lib.krep_gpu_debug_batch_pack_limit(nbytes)
+
+    def batch_times(self):
+        """(pack, scan, segment, read-back) milliseconds of the calling thread's last search_batch"""
+        t = [C.c_double(0) for _ in range(4)]
+        self.lib.krep_gpu_debug_batch_times(*[C.byref(x) for x in t])
+        return tuple(x.value for x in t)
+
+    def search_batch(self, params: abi.Params, items, cfg=None, want_info=False):
+        """krep_gpu_search_batch(params, items): [(count, positions[(n, 2) uint64])] in item order, every position relative to its
+        item's first byte; `items` are bytes or np.uint8 arrays.  Raises KrepGpuError with the library's reason on 2 (a refused
+        search included: there is no CPU fallback).  want_info: -> (that list, abi.BatchInfo)."""
+        n = len(items)
+        arr = (abi.BatchItem * max(n, 1))()
+        keep = []
+        for i, it in enumerate(items):
+            ptr, ln, k = self._ptr(it)
+            keep.append(k)
+            arr[i].text, arr[i].len = (ptr.value if ln else None), ln
+        res = (abi.BatchResult * max(n, 1))()
+        rec = self.lib.krep_gpu_match_result_init(16)
+        info = abi.BatchInfo()
+        dummy = C.c_int(0)
+        if params.s.num_patterns > 1 and not params.s.ac_trie:
+            params.s.ac_trie = C.cast(C.pointer(dummy), C.c_void_p)  # "caller pre-built the trie" (krep.c:2528)
+        try:
+            rc = self.lib.krep_gpu_search_batch(params.ref, C.byref(cfg) if cfg is not None else None, arr, n, res, rec, C.byref(info))
+            if rc:
+                raise KrepGpuError(self.last_error() or "krep_gpu_search_batch failed")
+            pos = abi.result_positions(rec)
+        finally:
+            self.lib.krep_gpu_match_result_free(rec)
+            params.s.ac_trie = None
+        del keep
+        out = [(int(r.count), pos[int(r.first_record):int(r.first_record) + int(r.n_records)]) for r in res[:n]]
+        return (out, info) if want_info else out
 
     def search_buffer(self, params: abi.Params, text, only_matching=False, num_gpus=1, want_result=True, cfg=None):
         ptr, n, keep = self._ptr(text)
