@@ -79,6 +79,13 @@ void krep_gpu_debug_batch_pack_limit(size_t bytes);
 /* where the calling thread's last krep_gpu_search_batch() spent its time, in milliseconds of wall clock: gathering the items into
  * the pinned staging ring and copying them to the device, the scan, the segmentation kernels, the read-back (tools/batch_bench.py) */
 void krep_gpu_debug_batch_times(double *pack_ms, double *scan_ms, double *segment_ms, double *readback_ms);
+/* test hook (host only, no GPU needed): bytes [lo, lo + cnt) of the pack krep_gpu_search_batch() makes of `items` — the items with one
+ * '\n' between neighbours — written to dst by the function its staging ring fills every chunk with (kg::batch_fill), over the offset
+ * table the batch call builds.  Returns 0, or 2 when [lo, lo + cnt) leaves the pack (tests/test_batch_fill_cpu.py) */
+int krep_gpu_debug_batch_fill_host(const krep_gpu_batch_item_t *items, size_t n, size_t lo, size_t cnt, void *dst);
+/* test hook: launches of the batch's record rebase with the items' offset table in LDS (it fits: items + 1 <= 4096 entries) and with the
+ * table in global memory, since the process started: which of the two a batch at the edge took shows in no result */
+void krep_gpu_debug_batch_rebase_launches(uint64_t *lds_table, uint64_t *global_table);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,7 @@ __global__ void __launch_bounds__(256) batch_line_flags(const u64 *__restrict__ 
 
 std::atomic<size_t> g_pack_limit{0};                // krep_gpu_debug_batch_pack_limit
 thread_local double tl_batch_ms[4] = {0, 0, 0, 0}; // krep_gpu_debug_batch_times
+std::atomic<uint64_t> g_rebase_lds{0}, g_rebase_global{0}; // krep_gpu_debug_batch_rebase_launches
 
 bool holds_newline(const uint8_t cls[32]) { return (cls['\n' >> 3] >> ('\n' & 7)) & 1; }
 } // namespace
@@ -155,7 +156,9 @@ int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const
     if (report && !lines && n_rec)
     {
         const u32 grid = (u32)((n_rec + kRebasePerBlock - 1) / kRebasePerBlock);
-        if (n_items + 1 <= kBatchLdsItems)
+        const bool lds = n_items + 1 <= kBatchLdsItems; // off[0 .. n_items] is n_items + 1 entries
+        (lds ? g_rebase_lds : g_rebase_global).fetch_add(1, std::memory_order_relaxed);
+        if (lds)
             hipLaunchKernelGGL(batch_rebase<true>, dim3(grid), dim3(256), 0, st, (u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off, (u64)n_items);
         else
             hipLaunchKernelGGL(batch_rebase<false>, dim3(grid), dim3(256), 0, st, (u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off, (u64)n_items);
@@ -240,6 +243,25 @@ extern "C" void krep_gpu_debug_batch_times(double *pack_ms, double *scan_ms, dou
     if (readback_ms) *readback_ms = tl_batch_ms[3];
 }
 
+extern "C" void krep_gpu_debug_batch_rebase_launches(uint64_t *lds_table, uint64_t *global_table)
+{
+    if (lds_table) *lds_table = g_rebase_lds.load();
+    if (global_table) *global_table = g_rebase_global.load();
+}
+
+extern "C" int krep_gpu_debug_batch_fill_host(const krep_gpu_batch_item_t *items, size_t n, size_t lo, size_t cnt, void *dst)
+{
+    std::vector<uint64_t> off;
+    if (!n || !items || kg::batch_pack_offsets(items, n, UINT64_MAX, off) != n)
+        return 2;
+    const uint64_t packed = off.back() - 1;
+    if (lo > packed || cnt > packed - lo)
+        return 2; // [lo, lo + cnt) leaves the pack
+    if (cnt)
+        kg::batch_fill(items, off.data(), n, (uint8_t *)dst, lo, cnt);
+    return 0;
+}
+
 extern "C" int krep_gpu_batch_can_accelerate(const search_params_t *params)
 {
     krep_gpu_clear_error();
@@ -301,15 +323,7 @@ extern "C" int krep_gpu_search_batch(const search_params_t *raw, const krep_gpu_
     for (size_t i0 = 0; i0 < n_items;)
     {
         // the next pack: items [i0, i1), cut between items and never inside one (an item beyond the limit is a pack of its own)
-        off.assign(1, 0);
-        size_t i1 = i0;
-        for (; i1 < n_items; ++i1)
-        {
-            const uint64_t end = off.back() + items[i1].len; // (the separator in front of it is in off.back() already)
-            if (i1 > i0 && end > limit)
-                break;
-            off.push_back(end + 1);
-        }
+        const size_t i1 = i0 + kg::batch_pack_offsets(items + i0, n_items - i0, limit, off);
         uint64_t n_rec = 0;
         float kms = 0;
         if (kg::host_batch_pack(&scan, cfg, items + i0, i1 - i0, off.data(), lines, report, records, appended, res.data() + i0, &n_rec, &kms,

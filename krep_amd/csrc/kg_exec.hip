@@ -1146,22 +1146,7 @@ int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t 
     auto t0 = clk::now();
     if (packed)
     {
-        // bytes [lo, lo + cnt) of the pack: item k lies at [off[k], off[k] + len), its separator on the byte behind it
-        const auto fill = [=](uint8_t *dst, size_t lo, size_t cnt) {
-            size_t k = (size_t)(std::upper_bound(off, off + n, (uint64_t)lo) - off) - 1;
-            for (size_t pos = lo, end = lo + cnt; pos < end; ++k)
-            {
-                const size_t ib = (size_t)off[k], ie = ib + items[k].len;
-                if (pos < ie)
-                {
-                    const size_t c = std::min(ie, end) - pos;
-                    memcpy(dst + (pos - lo), items[k].text + (pos - ib), c);
-                    pos += c;
-                }
-                if (pos < end && pos == ie)
-                    dst[pos++ - lo] = '\n';
-            }
-        };
+        const auto fill = [=](uint8_t *dst, size_t lo, size_t cnt) { batch_fill(items, off, n, dst, lo, cnt); };
         if (cx.stager.init(cx.device) || cx.stager.gather(d_text, packed, fill))
             return 2;
     }

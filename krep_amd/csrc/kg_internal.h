@@ -10,6 +10,7 @@
 
 #include "../../include/krep_gpu.h"
 #include "../../include/krep_gpu_debug.h" // (test hooks, exported by the same library)
+#include "kg_batch_pack.h"
 #include "kg_common.h"
 #include "kg_regex_compile.h"
 
@@ -344,6 +345,7 @@ void batch_scratch_free(BatchScratch &s);
 // rebased; else count = the item's records and, with `report`, every record is rebased to its item's first byte.  h_off: the table above.
 int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const uint64_t *h_off, uint64_t n_items, match_position_t *d_pos,
                   uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st);
+// (the next pack of a batch on the host — its offset table, the bytes of any slice of it: kg_batch_pack.h, batch_pack_offsets / batch_fill)
 // kg_exec.hip — one pack through the device context of cfg.device: gathered through the staging ring into the arena, scanned in one
 // window with the records plan `scan_params`, segmented, read back.  res_out[n]: the items' results; with `report` the rebased records go
 // to records->positions behind records->count + appended (the block grows, count is left alone: a later failure appends nothing).

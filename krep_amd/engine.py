@@ -181,6 +181,11 @@ class Engine:
             L.krep_gpu_debug_batch_pack_limit.argtypes = [C.c_size_t]
             L.krep_gpu_debug_batch_times.restype = None
             L.krep_gpu_debug_batch_times.argtypes = [C.POINTER(C.c_double)] * 4
+        if hasattr(L, "krep_gpu_debug_batch_fill_host"):  # (likewise)
+            L.krep_gpu_debug_batch_fill_host.restype = C.c_int
+            L.krep_gpu_debug_batch_fill_host.argtypes = [C.POINTER(abi.BatchItem), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
+            L.krep_gpu_debug_batch_rebase_launches.restype = None
+            L.krep_gpu_debug_batch_rebase_launches.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         if hasattr(L, "krep_gpu_alloc_placed"):
             L.krep_gpu_alloc_placed.restype = C.c_int
             L.krep_gpu_alloc_placed.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -595,6 +600,31 @@ class Engine:
         del keep
         out = [(int(r.count), pos[int(r.first_record):int(r.first_record) + int(r.n_records)]) for r in res[:n]]
         return (out, info) if want_info else out
+
+    def batch_rebase_launches(self):
+        """(with the items' offset table in LDS, with the table in global memory): launches of the batch's record rebase so far"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self.lib.krep_gpu_debug_batch_rebase_launches(C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def batch_items(self, items):
+        """(krep_gpu_batch_item_t[n], n, what keeps the texts alive) for `items` (bytes or np.uint8 arrays): for batch_fill_host()"""
+        arr = (abi.BatchItem * max(len(items), 1))()
+        keep = []
+        for i, it in enumerate(items):
+            ptr, ln, k = self._ptr(it)
+            keep.append(k)
+            arr[i].text, arr[i].len = (ptr.value if ln else None), ln
+        return arr, len(items), keep
+
+    def batch_fill_host(self, held, lo: int, cnt: int, guard: int = 0):
+        """test hook (host only, no GPU needed): bytes [lo, lo + cnt) of the pack of `held` (from batch_items()) exactly as the
+        staging ring of search_batch gets them -> np.uint8[guard + cnt + guard], the guard bytes 0xA5 on both sides of the
+        destination; None when the slice leaves the pack."""
+        arr, n, _ = held
+        out = np.full(cnt + 2 * guard, 0xA5, dtype=np.uint8)
+        rc = self.lib.krep_gpu_debug_batch_fill_host(arr, n, lo, cnt, C.c_void_p(out.ctypes.data + guard))
+        return out if rc == 0 else None
 
     def search_buffer(self, params: abi.Params, text, only_matching=False, num_gpus=1, want_result=True, cfg=None):
         ptr, n, keep = self._ptr(text)

@@ -20,11 +20,13 @@ def lib():
 
 
 def test_the_batch_symbols_are_exported(lib):
-    for n in ("krep_gpu_batch_can_accelerate", "krep_gpu_search_batch", "krep_gpu_debug_batch_pack_limit", "krep_gpu_debug_batch_times"):
+    for n in ("krep_gpu_batch_can_accelerate", "krep_gpu_search_batch", "krep_gpu_debug_batch_pack_limit", "krep_gpu_debug_batch_times",
+              "krep_gpu_debug_batch_fill_host", "krep_gpu_debug_batch_rebase_launches"):
         assert hasattr(lib, n), n
     boundary = open(os.path.join(ROOT, "include", "krep_gpu.h")).read()
     assert "krep_gpu_search_batch" in boundary and "krep_gpu_batch_can_accelerate" in boundary
-    assert "krep_gpu_debug_batch_pack_limit" in open(os.path.join(ROOT, "include", "krep_gpu_debug.h")).read()
+    hooks = open(os.path.join(ROOT, "include", "krep_gpu_debug.h")).read()
+    assert "krep_gpu_debug_batch_pack_limit" in hooks and "krep_gpu_debug_batch_fill_host" in hooks
 
 
 def test_struct_layouts_match_a_c11_probe(tmp_path):

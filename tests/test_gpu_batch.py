@@ -40,8 +40,6 @@ CLASSES = [
 ]
 CLASSES = CLASSES + [s.with_lines() for s in CLASSES if not s.name.startswith("-o memchr_short_search")]
 
-EDGE_LENGTHS = [0, 1, 15, 16, 17, 1023, 1024, 1025, 8191, 8192, 8193, 32767, 32768, 32769]
-
 
 @pytest.fixture(autouse=True, scope="module")
 def _c_locale():
@@ -59,60 +57,7 @@ def gpu():
     e.set_thread_config(None)
 
 
-def edge_items(s, seed=11, n_items=48):
-    """48 items of the edge lengths, repeated with other contents: a match planted at the first byte, at the last byte and in the
-    middle of an item; and, for some neighbours, a match-shaped string SPLIT across them — the end of item k and the start of
-    item k + 1 spell the pattern, which must not be found"""
-    rng = np.random.RandomState(seed)
-    plant = np.frombuffer(s.plants[0], dtype=np.uint8)
-    items = []
-    for k in range(n_items):
-        n = EDGE_LENGTHS[k % len(EDGE_LENGTHS)]
-        t = bm.random_item(rng, s, n)
-        if n >= plant.size:
-            if k % 3 != 2:
-                t[:plant.size] = plant
-            if k % 4 != 3:
-                t[n - plant.size:] = plant
-            if n >= 4 * plant.size:
-                t[n // 2:n // 2 + plant.size] = plant
-        items.append(t)
-    if plant.size >= 2:
-        h = plant.size // 2
-        for k in range(2, n_items - 1, 5):
-            a, b = items[k], items[k + 1]
-            if a.size >= h and b.size >= plant.size - h:
-                a[a.size - h:] = plant[:h]
-                b[:plant.size - h] = plant[h:]
-    return items
-
-
-def check_batch(gpu, s, items, single_every=1):
-    """the batch's per-item results == the reference on each item alone == the operator on each item alone -> (results, info)"""
-    s.configure(gpu)
-    try:
-        got, info = gpu.search_batch(s.params(), items, want_info=True)
-    finally:
-        gpu.set_thread_config(None)
-    assert len(got) == len(items)
-    lines = bool(s.kw.get("count_lines"))
-    for i, it in enumerate(items):
-        want = bm.reference(gpu, s, it)
-        assert got[i][0] == want[0], (s, i, it.size, got[i][0], want[0])
-        if lines:
-            assert got[i][1].shape == (0, 2)
-        else:
-            assert np.array_equal(got[i][1], want[1].reshape(-1, 2)), (s, i, it.size)
-        if i % single_every == 0:
-            s.configure(gpu)
-            try:
-                one = gpu.search(s.params(), it)
-            finally:
-                gpu.set_thread_config(None)
-            assert gpu.last_status() == abi.STATUS_OK
-            assert one[0] == got[i][0] and (lines or np.array_equal(one[1], got[i][1])), (s, i, it.size, one[0], got[i][0])
-    assert info.packed_bytes == sum(it.size for it in items) + len(items) - info.scans  # one separator between neighbours of a pack
-    return got, info
+edge_items, check_batch = bm.edge_items, bm.check_batch  # (shared with tests/test_gpu_batch_roads.py)
 
 
 @pytest.mark.parametrize("s", CLASSES, ids=lambda s: s.name)

@@ -10,6 +10,8 @@ with the sanitizer named.
     python tools/sanitize.py reference # the reference's own krep_test built with ASan + UBSan (findings there are the reference's)
     python tools/sanitize.py regex     # the -E pattern compiler as a stand-alone program (tools/regex_compile_san.cpp) under ASan + UBSan,
                                        # then its --digest over the whole corpus against tests/golden/regex_compile_digest.json
+    python tools/sanitize.py batchfill # the host side of a batch's pack (kg_batch_pack.h) as a stand-alone program
+                                       # (tools/batch_fill_san.cpp) under ASan + UBSan: every slice of 3000 small packs
 
 Each mode prints the sanitizer reports it saw (none expected) and exits non-zero on one; profiles/r06_sanitizers.txt is its log."""
 import glob
@@ -118,6 +120,17 @@ def main():
                   f"recording {' '.join(differ[:20])}")
             rc = rc or (1 if differ else 0)
         rc = rc or r.returncode
+    elif mode == "batchfill":
+        exe = os.path.join(SAN, "batch_fill_san")
+        r = run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-o", exe,
+                 os.path.join(ROOT, "tools", "batch_fill_san.cpp")])
+        if r.returncode:
+            return r.returncode
+        r = run([exe], env={"ASAN_OPTIONS": "detect_leaks=1:halt_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}, capture_output=True, text=True)
+        out = r.stdout + r.stderr
+        bad = [l for l in out.splitlines() if "ERROR: AddressSanitizer" in l or "ERROR: LeakSanitizer" in l or "runtime error:" in l]
+        print(out[-1500:])
+        rc = r.returncode
     else:
         print(__doc__)
         return 2
