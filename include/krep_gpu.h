@@ -914,6 +914,80 @@ int krep_gpu_search_batch(const search_params_t *params, const krep_gpu_config_t
                           const krep_gpu_batch_item_t *items, size_t n_items, krep_gpu_batch_result_t *results /* n_items */,
                           match_result_t *records /* nullable */, krep_gpu_batch_info_t *info /* nullable */); /* 0, or 2 */
 
+/* ---- the grep output of a batch: the two formatters over a PACK, and the host call that prints a batch (krep -r) ----
+ * The searches a batch takes are newline-separable, so every line of a pack lies inside one item, the separator is a real newline that
+ * ends an item's last line, and no record touches a separator: the whole pack is formatted in one go while it lies in HBM, and only
+ * the prefix, the line-number base and the stale-number rule are looked up per item (krep_amd/csrc/kg_batch_format.hip).
+ * The pack is laid out as krep_gpu_search_batch() lays it out: the items joined by one '\n', d_item_off[0 .. n_items] ascending with
+ *   d_item_off[n_items] = packed_len + 1, item i = d_pack[d_item_off[i], d_item_off[i + 1] - 1).  The records carry PACK offsets and
+ *   are in (start, end) order (krep_gpu_order_by_start() first on a multi-pattern list).  Item i's prefix is
+ *   d_prefix_bytes[d_prefix_off[i], d_prefix_off[i + 1]); the prefixes are the caller's ("FILE:", with or without escape codes: the
+ *   library knows none).  fmt->prefix must be empty (length 0), else 2.  All four pointers of the view are DEVICE pointers.
+ * Contract: the output is, byte for byte, the concatenation over i = 0 .. n_items - 1 of what krep_gpu_format_lines_ex (respectively
+ *   krep_gpu_format_matches) writes for the text of item i alone, item i's records rebased to the item's first byte, the same strings
+ *   with prefix = prefix i, and max_lines / max_items = all.  d_item_out_off[i] (if not NULL; n_items + 1 entries) is where item i's
+ *   bytes begin, entry n_items is out_bytes; an item without records adds nothing.  Per item this carries over the cursor rule, the
+ *   clamp to line_end, the 2048-records-per-line cap and capped_lines, and the '\n' behind an item's last line whether or not the
+ *   item ends in one; under -o, LINE restarts at 1 in every item and the reference's stale number is applied per item (it prints once
+ *   per file): in an item with more than 10 records and at least one newline, a record that starts behind the item's last newline
+ *   prints the LINE of the nearest earlier record of the SAME item that starts at or before that newline, or 1 when there is none.
+ * Refused (2) before any byte of the pack is read through the list: a list not ascending in start; end < start; a record whose start
+ *   is not inside an item (on a separator, or >= packed_len) or whose end lies behind its item's end; an offset table that is not
+ *   ascending, does not begin at 0 or does not end on packed_len + 1; a prefix table that is not ascending; a string or a prefix of
+ *   more than 2^20 bytes; n >= 2^40.
+ * Everything else as for the single-text formatters: d_out == NULL or out_capacity == 0 is a size query (the item offsets are valid
+ *   then too), a capacity that is too small sets `overflow` with valid sizes, d_pack and d_out may have any alignment, nothing is
+ *   written outside [d_out, d_out + out_bytes), `stream` is synchronised on return, n == 0 leaves the sizes 0 and every item offset 0. */
+typedef struct krep_gpu_pack_view /* all device pointers */
+{
+    const uint64_t *d_item_off;   /* [n_items + 1]                    */
+    uint64_t n_items;
+    const void *d_prefix_bytes;   /* the prefixes behind one another  */
+    const uint64_t *d_prefix_off; /* [n_items + 1]                    */
+} krep_gpu_pack_view_t;
+int krep_gpu_format_lines_items(const void *d_pack, size_t packed_len, const krep_gpu_pack_view_t *v,
+                                const match_position_t *d_positions, uint64_t n, const krep_gpu_line_format_t *fmt /* NULL: all empty */,
+                                void *d_out, size_t out_capacity, uint64_t *d_item_out_off /* n_items + 1, nullable */,
+                                krep_gpu_lines_out_t *out, void *stream);
+int krep_gpu_format_matches_items(const void *d_pack, size_t packed_len, const krep_gpu_pack_view_t *v,
+                                  const match_position_t *d_positions, uint64_t n, const krep_gpu_match_format_t *fmt /* NULL: all empty */,
+                                  void *d_out, size_t out_capacity, uint64_t *d_item_out_off /* nullable */,
+                                  krep_gpu_matches_out_t *out, void *stream);
+/* krep_gpu_grep_batch(): what `krep [-o | -c] PATTERN` prints for every item of a batch, in item order, appended to out->bytes.
+ * Mode: search_file()'s own branch (krep.c:3014-3027) — COUNT when count_lines_mode or count_matches_mode is set: prefix_i COUNT '\n'
+ *   for EVERY item, zero counts and empty items included (the reference prints FILE:0); else ONLY-MATCHING when cfg->only_matching is
+ *   set; else LINES.  track_positions == false outside COUNT is refused (the reference then prints its empty-match line, which no
+ *   batchable search produces).
+ * Taken: exactly what krep_gpu_batch_can_accelerate() takes under the same configuration, with the same reasons; every refusal comes
+ *   before any device work.  -m per file stays refused with it, and the pack runs on cfg->device alone.
+ * Per pack (the packs of krep_gpu_search_batch(): the same limit, cut between items, info->scans): packed through the staging ring,
+ *   scanned once with records, ordered by start when multi-pattern, cut into item bounds, the prefixes uploaded in one copy, the pack
+ *   formatted in HBM, the bytes copied straight behind out->bytes + out->len.  Under COUNT the counts are printed on the host.
+ * per_item[i].count is what krep_gpu_search_batch() reports; out_offset / out_bytes locate the item's bytes relative to out->len AT
+ *   ENTRY.  out->bytes is a malloc-family block (NULL with capacity 0 is fine) that the call grows.
+ * Failure (a refusal, a failed allocation, copy or launch): 2 with a reason, out->len and per_item untouched, nothing partially
+ *   appended across all packs.  No CPU fallback, as for krep_gpu_search_batch(). */
+typedef struct krep_gpu_grep_format /* host strings; the per-item prefixes are the caller's, e.g. "FILE:" */
+{
+    const char *const *prefixes; /* n_items of each */
+    const size_t *prefix_lens;
+    krep_gpu_line_format_t line;   /* before_match, after_match, line_close (prefix must be empty)  */
+    krep_gpu_match_format_t match; /* before_number, after_number, after_match (prefix must be empty) */
+} krep_gpu_grep_format_t;
+typedef struct krep_gpu_grep_item
+{
+    uint64_t count, out_offset, out_bytes;
+} krep_gpu_grep_item_t;
+typedef struct krep_gpu_grep_output /* malloc family; appended to */
+{
+    char *bytes;
+    size_t len, capacity;
+} krep_gpu_grep_output_t;
+int krep_gpu_grep_batch(const search_params_t *params, const krep_gpu_config_t *cfg /* NULL: current */,
+                        const krep_gpu_batch_item_t *items, size_t n_items, const krep_gpu_grep_format_t *fmt,
+                        krep_gpu_grep_item_t *per_item /* n_items */, krep_gpu_grep_output_t *out,
+                        krep_gpu_batch_info_t *info /* nullable */); /* 0, or 2 */
+
 int krep_gpu_device_count(void);
 const char *krep_gpu_last_error(void); /* "" when the last call on this thread succeeded */
 void krep_gpu_clear_error(void);

@@ -86,6 +86,13 @@ int krep_gpu_debug_batch_fill_host(const krep_gpu_batch_item_t *items, size_t n,
 /* test hook: launches of the batch's record rebase with the items' offset table in LDS (it fits: items + 1 <= 4096 entries) and with the
  * table in global memory, since the process started: which of the two a batch at the edge took shows in no result */
 void krep_gpu_debug_batch_rebase_launches(uint64_t *lds_table, uint64_t *global_table);
+/* the sibling of krep_gpu_debug_batch_times() for krep_gpu_grep_batch(): where the calling thread's last call spent its time, in
+ * milliseconds of wall clock — pack, scan and segmentation as above; format: the ordering of a multi-pattern list, the upload of the
+ * prefixes and the formatter over the pack; readback: the copies of the bytes, the item offsets and the counts (tools/batch_grep_bench.py) */
+void krep_gpu_debug_grep_batch_times(double *pack_ms, double *scan_ms, double *segment_ms, double *format_ms, double *readback_ms);
+/* test hook: calls of the pack formatters (krep_gpu_format_lines_items / krep_gpu_format_matches_items) that looked a record's item up
+ * with the offset table in LDS (items + 1 <= 4096 entries) and with the table in global memory, since the process started */
+void krep_gpu_debug_batch_format_launches(uint64_t *lds_table, uint64_t *global_table);
 
 #ifdef __cplusplus
 }

@@ -178,6 +178,26 @@ class BatchInfo(C.Structure):
     _fields_ = [("packed_bytes", C.c_uint64), ("scans", C.c_uint64), ("total_records", C.c_uint64), ("kernel_ms", C.c_float)]
 
 
+class PackView(C.Structure):
+    """krep_gpu_pack_view_t: the offset table and the per-item prefixes of a pack, all device pointers"""
+    _fields_ = [("d_item_off", C.c_void_p), ("n_items", C.c_uint64), ("d_prefix_bytes", C.c_void_p), ("d_prefix_off", C.c_void_p)]
+
+
+class GrepFormat(C.Structure):
+    """krep_gpu_grep_format_t: the per-item prefixes (host strings) and the other strings of both output forms"""
+    _fields_ = [("prefixes", C.POINTER(C.c_char_p)), ("prefix_lens", C.POINTER(C.c_size_t)), ("line", LineFormat), ("match", MatchFormat)]
+
+
+class GrepItem(C.Structure):
+    """krep_gpu_grep_item_t: an item's count and where its bytes lie in the output, relative to out->len at entry"""
+    _fields_ = [("count", C.c_uint64), ("out_offset", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class GrepOutput(C.Structure):
+    """krep_gpu_grep_output_t: a malloc-family block krep_gpu_grep_batch appends to"""
+    _fields_ = [("bytes", C.c_void_p), ("len", C.c_size_t), ("capacity", C.c_size_t)]
+
+
 STATUS_OK, STATUS_FELL_BACK, STATUS_FAILED = 0, 1, 2
 SPLIT_WHOLE, SPLIT_PIECES, SPLIT_CHAIN = 0, 1, 2
 

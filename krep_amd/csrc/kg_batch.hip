@@ -8,6 +8,8 @@
 //   batch_line_flags -c: 1 where a record's line differs from its predecessor's; an exclusive sum over the flags makes an item's
 //                    distinct-line count the difference at its two bounds (no loop per item: one item may hold every record)
 // and the rule that says when all this is exact (kg::batch_unsupported_reason: newline-separable searches only).
+// krep_gpu_grep_batch (at the end of the file) is the same walk over the packs with one step more per pack: the pack is
+// formatted where it lies (kg_batch_format.hip) and the printed bytes are read back instead of the records.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +20,7 @@
 
 #include "../../include/krep_gpu.h"
 #include "kg_device.h"
+#include "kg_format_dev.h"
 #include "kg_internal.h"
 
 using namespace kg;
@@ -26,22 +29,6 @@ namespace kg {
 namespace {
 constexpr u32 kBatchLdsItems = 4096; // offset-table entries (items + 1) batch_rebase keeps in LDS: 32 KiB
 constexpr u32 kRebasePerBlock = 2048; // records one workgroup of batch_rebase walks: the table load is paid once per 2048 records
-
-// first index k in [0, n) whose record starts at or behind `key` (n when none): the list is item-contiguous in item order, so
-// "starts in front of an item's base" is a prefix of it whether it ascends in start (single literal, regex) or in end (multi-pattern)
-__device__ __forceinline__ u64 first_record_at(const u64 *__restrict__ rec, u64 n, u64 key)
-{
-    u64 lo = 0, hi = n;
-    while (lo < hi)
-    {
-        const u64 mid = lo + (hi - lo) / 2;
-        if (rec[2 * mid] < key)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
 
 // (a) res[i] = {count, first_record, n_records}.  prefix != NULL (-c): count = the flags summed over the item's records.
 __global__ void __launch_bounds__(256) batch_bounds(const u64 *__restrict__ rec, u64 n_rec, const u64 *__restrict__ off, u64 n_items,
@@ -106,6 +93,7 @@ __global__ void __launch_bounds__(256) batch_line_flags(const u64 *__restrict__ 
 
 std::atomic<size_t> g_pack_limit{0};                // krep_gpu_debug_batch_pack_limit
 thread_local double tl_batch_ms[4] = {0, 0, 0, 0}; // krep_gpu_debug_batch_times
+thread_local double tl_grep_ms[5] = {0, 0, 0, 0, 0}; // krep_gpu_debug_grep_batch_times: pack, scan, segment, format, read-back
 std::atomic<uint64_t> g_rebase_lds{0}, g_rebase_global{0}; // krep_gpu_debug_batch_rebase_launches
 
 bool holds_newline(const uint8_t cls[32]) { return (cls['\n' >> 3] >> ('\n' & 7)) & 1; }
@@ -113,7 +101,8 @@ bool holds_newline(const uint8_t cls[32]) { return (cls['\n' >> 3] >> ('\n' & 7)
 
 void batch_scratch_free(BatchScratch &s)
 {
-    for (void *p : {(void *)s.d_off, (void *)s.d_res, (void *)s.d_lines, (void *)s.d_flags, (void *)s.d_prefix, (void *)s.d_sums})
+    for (void *p : {(void *)s.d_off, (void *)s.d_res, (void *)s.d_lines, (void *)s.d_flags, (void *)s.d_prefix, (void *)s.d_sums,
+                    (void *)s.d_pfx, (void *)s.d_pfx_off, (void *)s.d_item_out, (void *)s.d_out})
         if (p)
             (void)hipFree(p);
     s = BatchScratch{};
@@ -340,6 +329,208 @@ extern "C" int krep_gpu_search_batch(const search_params_t *raw, const krep_gpu_
     memcpy(results, res.data(), n_items * sizeof *results);
     if (report)
         records->count = count0 + appended;
+    if (info)
+        *info = bi;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the grep output of a batch
+extern "C" void krep_gpu_debug_grep_batch_times(double *pack_ms, double *scan_ms, double *segment_ms, double *format_ms, double *readback_ms)
+{
+    double *const dst[5] = {pack_ms, scan_ms, segment_ms, format_ms, readback_ms};
+    for (int k = 0; k < 5; ++k)
+        if (dst[k]) *dst[k] = tl_grep_ms[k];
+}
+
+extern "C" int krep_gpu_grep_batch(const search_params_t *raw, const krep_gpu_config_t *cfg_in, const krep_gpu_batch_item_t *items,
+                                   size_t n_items, const krep_gpu_grep_format_t *fmt, krep_gpu_grep_item_t *per_item,
+                                   krep_gpu_grep_output_t *out, krep_gpu_batch_info_t *info)
+{
+    using clk = std::chrono::steady_clock;
+    const auto since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    krep_gpu_clear_error();
+    if (info)
+        *info = krep_gpu_batch_info_t{};
+    for (double &t : tl_grep_ms)
+        t = 0;
+    if (!raw || !fmt || !out || (n_items && (!items || !per_item || !fmt->prefixes || !fmt->prefix_lens)))
+        return kg::fail("grep_batch: NULL params / items / fmt / per_item / out");
+    const krep_gpu_config_t cfg = cfg_in ? *cfg_in : kg::current_config();
+    // every refusal comes before any device work
+    if (const char *why = kg::batch_unsupported_reason(raw, cfg))
+        return kg::fail("%s", why);
+    NormParams np(raw);
+    if (!np.valid)
+        return kg::fail("no pattern");
+    // search_file()'s own branch (krep.c:3014-3027)
+    const bool count_mode = raw->count_lines_mode || raw->count_matches_mode, om = !count_mode && cfg.only_matching;
+    if (!count_mode && !raw->track_positions)
+        return kg::fail("grep_batch: track_positions == false outside -c: the reference prints its empty-match line then (krep.c:3029-3038), "
+                        "which no batchable search produces");
+    if (fmt->line.prefix_len || fmt->match.prefix_len)
+        return kg::fail("grep_batch: the prefix of fmt->line / fmt->match must be empty: the prefixes are per item");
+    {
+        const char *str[6] = {fmt->line.before_match, fmt->line.after_match, fmt->line.line_close,
+                              fmt->match.before_number, fmt->match.after_number, fmt->match.after_match};
+        const size_t len[6] = {fmt->line.before_match_len, fmt->line.after_match_len, fmt->line.line_close_len,
+                               fmt->match.before_number_len, fmt->match.after_number_len, fmt->match.after_match_len};
+        for (int k = 0; k < 6; ++k)
+            if ((len[k] && !str[k]) || (len[k] >> 20))
+                return kg::fail("grep_batch: a string of the format is NULL with a length, or longer than 2^20 bytes");
+    }
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        if (!items[i].text && items[i].len)
+            return kg::fail("grep_batch: item %zu has a NULL text and a length of %zu", i, items[i].len);
+        if ((fmt->prefix_lens[i] && !fmt->prefixes[i]) || (fmt->prefix_lens[i] >> 20))
+            return kg::fail("grep_batch: the prefix of item %zu is NULL with a length, or longer than 2^20 bytes", i);
+    }
+    if (out->len > out->capacity || (!out->bytes && out->capacity))
+        return kg::fail("grep_batch: out holds %zu bytes in a block of %zu", out->len, out->capacity);
+    if (const char *why = kg::device_unusable(cfg.device))
+        return kg::fail("%s", why);
+    if (!n_items)
+        return 0;
+    const search_params_t *params = &np.sp;
+    const size_t len0 = out->len;
+    uint64_t appended = 0; // bytes written behind out->bytes + len0 so far (out->len moves at the very end)
+    const auto host_room = [&](uint64_t more) -> bool { // out->bytes holds len0 + appended + more bytes
+        const size_t need = len0 + appended + more;
+        if (need <= out->capacity)
+            return true;
+        const size_t cap = std::max<size_t>({need, 2 * out->capacity, (size_t)4096});
+        char *p = (char *)realloc(out->bytes, cap);
+        if (!p)
+            return false;
+        out->bytes = p;
+        out->capacity = cap;
+        return true;
+    };
+    std::vector<krep_gpu_batch_result_t> res(n_items, krep_gpu_batch_result_t{0, 0, 0});
+    std::vector<krep_gpu_grep_item_t> pi(n_items, krep_gpu_grep_item_t{0, 0, 0});
+    krep_gpu_batch_info_t bi{};
+    // (aho_corasick.c:306: no trie, no matches — every count stays 0, nothing is scanned)
+    const bool no_trie = params->num_patterns > 1 && !params->ac_trie && !params->use_regex;
+    search_params_t scan = *params;
+    scan.count_lines_mode = false;
+    scan.track_positions = true;
+    scan.max_count = SIZE_MAX;
+    const size_t chunk = cfg.stream_chunk_bytes ? cfg.stream_chunk_bytes : ((size_t)128 << 20);
+    const size_t limit = g_pack_limit.load() ? g_pack_limit.load() : 2 * chunk;
+    DeviceGuard guard;
+    std::vector<uint64_t> off, poff, item_out;
+    std::vector<uint8_t> blob;
+    for (size_t i0 = 0; i0 < n_items && !no_trie;)
+    {
+        const size_t i1 = i0 + kg::batch_pack_offsets(items + i0, n_items - i0, limit, off);
+        // between the segmentation and the read-back: the pack formatted where it lies, its bytes copied behind what is there
+        const BatchStep format = [&](const BatchPackOnDevice &p) -> int {
+            auto t0 = clk::now();
+            const size_t n = (size_t)p.n_items;
+            item_out.assign(n + 1, 0);
+            uint64_t bytes = 0;
+            if (p.n_rec)
+            {
+                BatchScratch &s = p.scratch;
+                if (p.by_end && krep_gpu_order_by_start(p.d_pos, p.n_rec, p.packed, nullptr))
+                    return 2;
+                (void)kg::batch_prefix_blob(fmt->prefixes + i0, fmt->prefix_lens + i0, n, (size_t)1 << 20, blob, poff); // (checked above)
+                if (kg::inject(1))
+                    return kg::fail("grep_batch: device allocation failed (injected)");
+                HIPCHK(grow_scratch(s.pfx_cap, blob.size(), blob.size() + blob.size() / 2 + 4096,
+                                    {dev_buf(s.d_pfx, blob.size() + blob.size() / 2 + 4096)}));
+                {
+                    const uint64_t want = std::max<uint64_t>(n + 1 + n / 2, 1024);
+                    HIPCHK(grow_scratch(s.grep_items_cap, n + 1, want,
+                                        {dev_buf(s.d_pfx_off, want * sizeof(u64)), dev_buf(s.d_item_out, want * sizeof(u64))}));
+                }
+                if (kg::inject(2))
+                    return kg::fail("grep_batch: H2D copy of the prefixes failed (injected)");
+                if (!blob.empty())
+                    HIPCHK(hipMemcpyAsync(s.d_pfx, blob.data(), blob.size(), hipMemcpyHostToDevice, nullptr));
+                HIPCHK(hipMemcpyAsync(s.d_pfx_off, poff.data(), (n + 1) * sizeof(u64), hipMemcpyHostToDevice, nullptr));
+                const krep_gpu_pack_view_t view{(const uint64_t *)p.d_off, (uint64_t)n, s.d_pfx, (const uint64_t *)s.d_pfx_off};
+                const FormatOutGrow grow = [&s](size_t want) -> void * { // the rule of the other scratch: grown by half again
+                    if (grow_scratch(s.out_cap, want, want + want / 2, {dev_buf(s.d_out, want + want / 2)}) != hipSuccess)
+                    {
+                        (void)hipGetLastError();
+                        (void)kg::fail("grep_batch: allocation of %zu bytes for the formatted output failed", want + want / 2);
+                        return nullptr;
+                    }
+                    return s.d_out;
+                };
+                if (kg::inject(3))
+                    return kg::fail("grep_batch: launch of the pack formatter failed (injected)");
+                if (om)
+                {
+                    krep_gpu_matches_out_t mo{};
+                    if (kg::format_matches_items(p.d_text, p.packed, &view, p.d_pos, p.n_rec, &fmt->match, nullptr, 0, &grow,
+                                                 (uint64_t *)s.d_item_out, &mo, nullptr))
+                        return 2;
+                    bytes = mo.out_bytes;
+                }
+                else
+                {
+                    krep_gpu_lines_out_t lo{};
+                    if (kg::format_lines_items(p.d_text, p.packed, &view, p.d_pos, p.n_rec, &fmt->line, nullptr, 0, &grow,
+                                               (uint64_t *)s.d_item_out, &lo, nullptr))
+                        return 2;
+                    bytes = lo.out_bytes;
+                }
+                tl_grep_ms[3] += since(t0);
+                t0 = clk::now();
+                if (kg::inject(4))
+                    return kg::fail("D2H copy of the formatted output failed (injected)");
+                if (!host_room(bytes))
+                    return kg::fail("grep_batch: out of memory growing the output to %zu bytes", (size_t)(len0 + appended + bytes));
+                if ((bytes &&hipMemcpy(out->bytes + len0 + appended, s.d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+                    hipMemcpy(item_out.data(), s.d_item_out, (n + 1) * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess)
+                    return kg::fail("D2H copy of the formatted output failed");
+                tl_grep_ms[4] += since(t0);
+            }
+            for (size_t k = 0; k < n; ++k)
+                pi[i0 + k] = krep_gpu_grep_item_t{0, appended + item_out[k], item_out[k + 1] - item_out[k]};
+            appended += bytes;
+            return 0;
+        };
+        uint64_t n_rec = 0;
+        float kms = 0;
+        double ms[4] = {0, 0, 0, 0};
+        if (kg::host_batch_pack(&scan, cfg, items + i0, i1 - i0, off.data(), count_mode && params->count_lines_mode, false, nullptr, 0,
+                                res.data() + i0, &n_rec, &kms, ms, count_mode ? nullptr : &format))
+            return 2; // (out->len was never moved: nothing is appended)
+        tl_grep_ms[0] += ms[0], tl_grep_ms[1] += ms[1], tl_grep_ms[2] += ms[2], tl_grep_ms[4] += ms[3];
+        bi.packed_bytes += off.back() - 1;
+        bi.scans += 1;
+        bi.total_records += n_rec;
+        bi.kernel_ms += kms;
+        i0 = i1;
+    }
+    if (count_mode) // the counts are printed on the host: prefix COUNT '\n' for every item
+    {
+        const auto t0 = clk::now();
+        uint64_t total = 0;
+        for (size_t i = 0; i < n_items; ++i)
+            total += fmt->prefix_lens[i] + 21;
+        if (!host_room(total))
+            return kg::fail("grep_batch: out of memory growing the output by %zu bytes", (size_t)total);
+        for (size_t i = 0; i < n_items; ++i)
+        {
+            char *dst = out->bytes + len0 + appended;
+            if (fmt->prefix_lens[i])
+                memcpy(dst, fmt->prefixes[i], fmt->prefix_lens[i]);
+            char num[24];
+            const int d = snprintf(num, sizeof num, "%llu\n", (unsigned long long)res[i].count);
+            memcpy(dst + fmt->prefix_lens[i], num, (size_t)d);
+            pi[i] = krep_gpu_grep_item_t{0, appended, fmt->prefix_lens[i] + (uint64_t)d};
+            appended += pi[i].out_bytes;
+        }
+        tl_grep_ms[4] += since(t0);
+    }
+    for (size_t i = 0; i < n_items; ++i)
+        pi[i].count = res[i].count;
+    memcpy(per_item, pi.data(), n_items * sizeof *per_item);
+    out->len = len0 + appended;
     if (info)
         *info = bi;
     return 0;

@@ -50,4 +50,27 @@ inline void batch_fill(const krep_gpu_batch_item_t *items, const uint64_t *off, 
     }
 }
 
+// krep_gpu_grep_batch: the prefixes of n items behind one another in `blob`, poff[k] = where prefix k begins, poff[n] = the blob's size:
+// what the device formatters read a prefix through.  -1, or the index of the first prefix that is NULL with a length or longer than
+// max_len bytes (the vectors then hold the prefixes in front of it)
+inline long batch_prefix_blob(const char *const *prefixes, const size_t *lens, size_t n, size_t max_len, std::vector<uint8_t> &blob,
+                              std::vector<uint64_t> &poff)
+{
+    blob.clear();
+    poff.assign(1, 0);
+    size_t total = 0;
+    for (size_t k = 0; k < n; ++k)
+        total += lens[k] <= max_len ? lens[k] : 0;
+    blob.reserve(total);
+    for (size_t k = 0; k < n; ++k)
+    {
+        if (lens[k] > max_len || (lens[k] && !prefixes[k]))
+            return (long)k;
+        if (lens[k])
+            blob.insert(blob.end(), (const uint8_t *)prefixes[k], (const uint8_t *)prefixes[k] + lens[k]);
+        poff.push_back(blob.size());
+    }
+    return -1;
+}
+
 } // namespace kg

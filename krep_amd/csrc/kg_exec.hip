@@ -1127,7 +1127,7 @@ int host_scan(const search_params_t *params, const krep_gpu_config_t &cfg, const
 // overflowed, as the operators do), the list cut per item on the device, results and rebased records read back in one copy each.
 int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t &cfg, const krep_gpu_batch_item_t *items, size_t n,
                     const uint64_t *off, bool lines, bool report, match_result_t *records, uint64_t appended,
-                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms)
+                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms, const BatchStep *step)
 {
     using clk = std::chrono::steady_clock;
     const auto since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
@@ -1169,6 +1169,9 @@ int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t 
         return 2;
     HIPCHK(hipStreamSynchronize(nullptr));
     ms[2] += since(t0);
+    if (step && (*step)(BatchPackOnDevice{cx.batch, d_text, packed, cx.batch.d_off, n, d_pos, n_rec,
+                                          pl->ref_algo == KREP_RA_AHO_CORASICK})) // (its time is its own)
+        return 2;
     t0 = clk::now();
     if (kg::inject(4) || hipMemcpy(res_out, cx.batch.d_res, n * sizeof *res_out, hipMemcpyDeviceToHost) != hipSuccess)
         return kg::fail("D2H copy of the batch results failed");

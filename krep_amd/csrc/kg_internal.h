@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <mutex>
 #include <vector>
@@ -337,6 +338,13 @@ struct BatchScratch // grow-only, one per device context
     unsigned long long *d_prefix = nullptr; // ... their exclusive sum
     unsigned long long *d_sums = nullptr;   // ... scratch of that sum
     uint64_t rec_cap = 0;
+    // krep_gpu_grep_batch: the items' prefixes and their offsets [items + 1], where every item's output begins [items + 1]; the output
+    unsigned char *d_pfx = nullptr;
+    uint64_t pfx_cap = 0;
+    unsigned long long *d_pfx_off = nullptr, *d_item_out = nullptr;
+    uint64_t grep_items_cap = 0;
+    unsigned char *d_out = nullptr;
+    uint64_t out_cap = 0;
 };
 void batch_scratch_free(BatchScratch &s);
 // The record list of one pack (n_rec records in d_pos, the reference's emission order; by_end: a multi-pattern list) cut into the
@@ -350,8 +358,33 @@ int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const
 // window with the records plan `scan_params`, segmented, read back.  res_out[n]: the items' results; with `report` the rebased records go
 // to records->positions behind records->count + appended (the block grows, count is left alone: a later failure appends nothing).
 // ms[4] += wall clock of packing / scan / segmentation / read-back.  2: failed.
+// step (NULL: none, krep_gpu_search_batch): called between the segmentation and the read-back with the pack as it lies on the device
+// (krep_gpu_grep_batch formats it there); a step that returns non-zero fails the pack.
+struct BatchPackOnDevice
+{
+    BatchScratch &scratch;
+    const uint8_t *d_text;
+    uint64_t packed;
+    const unsigned long long *d_off; // [n_items + 1], as BatchScratch::d_off
+    uint64_t n_items;
+    match_position_t *d_pos; // pack-relative, in emission order (by_end: a multi-pattern list, ascending in end)
+    uint64_t n_rec;
+    bool by_end;
+};
+using BatchStep = std::function<int(const BatchPackOnDevice &)>;
 int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t &cfg, const krep_gpu_batch_item_t *items, size_t n,
                     const uint64_t *off, bool lines, bool report, match_result_t *records, uint64_t appended,
-                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms);
+                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms, const BatchStep *step = nullptr);
+
+// kg_batch_format.hip — the formatters over a pack behind krep_gpu_format_lines_items / krep_gpu_format_matches_items.  grow (NULL:
+// none): asked for the output buffer once the size is known (-> a device buffer of at least that many bytes, NULL: it failed and said
+// why), so that krep_gpu_grep_batch analyses a pack once instead of asking for the size first
+using FormatOutGrow = std::function<void *(size_t)>;
+int format_lines_items(const void *d_pack, size_t packed_len, const krep_gpu_pack_view_t *v, const match_position_t *d_positions, uint64_t n,
+                       const krep_gpu_line_format_t *fmt, void *d_out, size_t out_capacity, const FormatOutGrow *grow,
+                       uint64_t *d_item_out_off, krep_gpu_lines_out_t *out, hipStream_t st);
+int format_matches_items(const void *d_pack, size_t packed_len, const krep_gpu_pack_view_t *v, const match_position_t *d_positions,
+                         uint64_t n, const krep_gpu_match_format_t *fmt, void *d_out, size_t out_capacity, const FormatOutGrow *grow,
+                         uint64_t *d_item_out_off, krep_gpu_matches_out_t *out, hipStream_t st);
 
 } // namespace kg

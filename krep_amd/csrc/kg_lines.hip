@@ -35,14 +35,13 @@
 
 #include "../../include/krep_gpu.h"
 #include "kg_device.h"
+#include "kg_format_dev.h"
 #include "kg_internal.h"
 
 namespace kg {
 
-constexpr u32 kLnBlock = 4096;           // the table keeps the first and the last newline per 4 KiB of text
-constexpr u64 kLnCap = 2048;             // MAX_MATCHES_PER_LINE (krep.c:496)
-constexpr u64 kLnNone = ~0ull;
-constexpr u64 kLnFirst = 1ull << 63, kLnLast = 1ull << 62, kLnSrc = kLnLast - 1; // a record's range word: flags | source offset
+// (the constants, LnRecord / ln_record, LnExtent / ln_extent, ln_find, LcFixed, LcItem / lc_item / lc_byte and LnWork live in
+// kg_format_dev.h: kg_batch_format.hip formats a pack of items with the same helpers)
 
 // bit q set: byte q of the 16 is a '\n'
 __device__ __forceinline__ u32 nl_mask16(const uint4 v)
@@ -170,20 +169,6 @@ __global__ __launch_bounds__(256) void ln_heads(const u64 *__restrict__ ls, u64 
     mark[i] = h ? i + 1 : 0ull;
 }
 
-struct LnRecord
-{
-    bool head;
-    u64 line, first; // index of its line, index of that line's first record
-};
-__device__ __forceinline__ LnRecord ln_record(const u64 *ls, const u64 *heads_before, const u64 *mark_before, u64 i)
-{
-    LnRecord r;
-    r.head = i == 0 || ls[i] != ls[i - 1];
-    r.line = heads_before[i] + (r.head ? 1u : 0u) - 1u;
-    r.first = r.head ? i : mark_before[i] - 1;
-    return r;
-}
-
 // krep_gpu_matching_lines: the spans and first records of the first `emit` lines (write != 0), and the emitted lines that hold more
 // than 2048 records
 __global__ __launch_bounds__(256) void ln_spans(const u64 *__restrict__ ls, const u64 *__restrict__ le, const u64 *__restrict__ heads_before,
@@ -211,46 +196,6 @@ __global__ __launch_bounds__(256) void ln_spans(const u64 *__restrict__ ls, cons
         first_record[emit] = n;
 }
 
-// what record i adds to its line: ONE range [src, end) of the text; counted: it is among the first 2048 records of an emitted line
-struct LnExtent
-{
-    bool counted, first, last, solid; // first / last counted record of its line; solid: its clamped match [start, cend) is not empty
-    u64 src, end;
-};
-__device__ __forceinline__ LnExtent ln_extent(const u64 *__restrict__ rec, const u64 *__restrict__ ls, const u64 *__restrict__ le,
-                                              const u64 *__restrict__ heads_before, const u64 *__restrict__ mark_before, u64 n,
-                                              u64 max_lines, u64 i, u64 *__restrict__ ctr)
-{
-    LnExtent x{};
-    const LnRecord r = ln_record(ls, heads_before, mark_before, i);
-    const u64 emit = min(heads_before[n], max_lines), rank = i - r.first;
-    if (r.line < emit && rank == kLnCap)
-        (void)__hip_atomic_fetch_add(ctr + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (r.line >= emit || rank >= kLnCap)
-        return x;
-    const u64 a = ls[i], z = le[i], s = rec[2 * i], cend = min(rec[2 * i + 1], z);
-    const bool solid = s < cend; // its clamped match is not empty
-    // the cursor in front of it: the clamped end of the nearest record before it on the line whose match is not empty (the record
-    // just before it, unless that one starts on the newline or is empty: at most 2047 steps, on such lists only)
-    u64 cur = a;
-    for (u64 j = i; j > r.first; --j)
-    {
-        const u64 sj = rec[2 * (j - 1)], ej = min(rec[2 * (j - 1) + 1], z);
-        if (sj < ej)
-        {
-            cur = ej;
-            break;
-        }
-    }
-    x.counted = true;
-    x.first = rank == 0;
-    x.last = rank == kLnCap - 1 || i + 1 == n || ls[i + 1] != a;
-    x.solid = solid;
-    x.src = solid ? min(s, cur) : cur;
-    x.end = x.last ? z : (solid ? cend : cur);
-    return x;
-}
-
 // (4) what record i adds to the output: bytes[i], and range[i] = flags | offset of its range in the text
 __global__ __launch_bounds__(256) void ln_sizes(const u64 *__restrict__ rec, const u64 *__restrict__ ls, const u64 *__restrict__ le,
                                                 const u64 *__restrict__ heads_before, const u64 *__restrict__ mark_before, u64 n,
@@ -274,20 +219,6 @@ __global__ __launch_bounds__(256) void ln_sizes(const u64 *__restrict__ rec, con
     }
     bytes[i] = (x.first ? prefix_len : 0ull) + (x.end - x.src) + (x.last ? 1ull : 0ull);
     range[i] = x.src | (x.first ? kLnFirst : 0ull) | (x.last ? kLnLast : 0ull);
-}
-
-// the largest r in [lo, hi] with off[r] <= pos (off[lo] <= pos)
-__device__ __forceinline__ u64 ln_find(const u64 *__restrict__ off, u64 lo, u64 hi, u64 pos)
-{
-    while (lo < hi)
-    {
-        const u64 mid = lo + (hi - lo + 1) / 2;
-        if (off[mid] <= pos)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
 }
 
 // where a lane stands in the output: inside record r, with `pre` bytes of the prefix, `txt` bytes of the text and `nl` newline to go
@@ -399,12 +330,6 @@ __global__ __launch_bounds__(256) void ln_gather(const uint8_t *__restrict__ tex
 // A record's range of the text stays ONE range [src, end); before_match goes in at start - src and after_match at cend - src, the
 // prefix in front of a line's first record, line_close and '\n' behind its last.  So a record is at most seven pieces besides the
 // newline, and four of them are the strings, which lie behind one another in one small device buffer `fix`.
-constexpr u64 kLcSolid = 1ull << 61, kLcSrc = kLcSolid - 1; // one more flag in the range word
-
-struct LcFixed
-{
-    u32 prefix, before, after, close; // the lengths; in `fix`: prefix | before_match | after_match | line_close
-};
 
 // (4') bytes[i] and range[i] = flags | offset of the record's range in the text
 __global__ __launch_bounds__(256) void lc_sizes(const u64 *__restrict__ rec, const u64 *__restrict__ ls, const u64 *__restrict__ le,
@@ -430,56 +355,6 @@ __global__ __launch_bounds__(256) void lc_sizes(const u64 *__restrict__ rec, con
     bytes[i] = (x.first ? (u64)f.prefix : 0ull) + (x.end - x.src) + (x.solid ? (u64)f.before + f.after : 0ull) +
                (x.last ? (u64)f.close + 1ull : 0ull);
     range[i] = x.src | (x.first ? kLnFirst : 0ull) | (x.last ? kLnLast : 0ull) | (x.solid ? kLcSolid : 0ull);
-}
-
-// one record's output, counted from its first byte: prefix [0, e0), text [e0, e1), before_match [e1, e2), the match [e2, e3),
-// after_match [e3, e4), text [e4, e5), line_close [e5, e6), '\n' at e6 if the record closes its line.  Lines of 1 GiB and more are
-// legal: the ends are 64-bit.  The three text pieces are one range: byte k of them is text[src + k - (string bytes in front of k)]
-struct LcItem
-{
-    u64 src, e1, e2, e3, e4, e5, e6, total;
-    u32 e0;
-};
-__device__ __forceinline__ LcItem lc_item(const u64 *__restrict__ rec, const u64 *__restrict__ le, const u64 *__restrict__ off,
-                                          const u64 *__restrict__ range, const LcFixed f, u64 r)
-{
-    LcItem it;
-    const u64 w = range[r];
-    const bool first = w & kLnFirst, last = w & kLnLast, solid = w & kLcSolid;
-    it.total = off[r + 1] - off[r];
-    it.src = w & kLcSrc;
-    u64 t1 = 0, t2 = 0;
-    if (solid)
-    {
-        const uint4 p = *reinterpret_cast<const uint4 *>(rec + 2 * r);
-        const u64 s = ((u64)p.y << 32) | p.x, e = min(((u64)p.w << 32) | p.z, le[r]);
-        t1 = s - it.src;
-        t2 = e - s;
-    }
-    it.e0 = first ? f.prefix : 0u;
-    it.e1 = it.e0 + t1;
-    it.e2 = it.e1 + (solid ? f.before : 0u);
-    it.e3 = it.e2 + t2;
-    it.e4 = it.e3 + (solid ? f.after : 0u);
-    it.e6 = it.total - (last ? 1u : 0u);
-    it.e5 = it.e6 - (last ? f.close : 0u);
-    return it;
-}
-// its byte k (k < total)
-__device__ __forceinline__ u32 lc_byte(const uint8_t *__restrict__ text, const uint8_t *__restrict__ fix, const LcFixed f, const LcItem &it,
-                                       u64 k)
-{
-    if (k < it.e2)
-    {
-        if (k < it.e0)
-            return fix[k];
-        return k < it.e1 ? (u32)text[it.src + (k - it.e0)] : (u32)fix[f.prefix + (k - it.e1)];
-    }
-    if (k < it.e4)
-        return k < it.e3 ? (u32)text[it.src + (k - it.e2) + (it.e1 - it.e0)] : (u32)fix[f.prefix + f.before + (k - it.e3)];
-    if (k < it.e5)
-        return text[it.src + (k - it.e4) + (it.e1 - it.e0) + (it.e3 - it.e2)];
-    return k < it.e6 ? (u32)fix[f.prefix + f.before + f.after + (k - it.e5)] : (u32)'\n';
 }
 
 // (5') as ln_gather: chunk c is the 16 aligned bytes at (out - misalign) + 16 c, i.e. output offsets [16 c - misalign, + 16)
@@ -695,13 +570,6 @@ __global__ __launch_bounds__(256) void lw_sizes(const u64 *__restrict__ loc, con
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-struct LnWork
-{
-    u64 *ctr, *last1, *prev1, *first_rev, *next_rev; // counters {refused, capped lines}; the block table and its scans
-    u64 *ls, *le, *a, *heads_before, *mark_before, *range, *sums;
-    uint8_t *prefix;
-    u64 nb;
-};
 
 int ln_check(const char *who, const void *d_text, const void *d_positions, uint64_t n, krep_gpu_lines_out_t *out)
 {

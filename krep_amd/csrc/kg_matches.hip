@@ -32,38 +32,13 @@
 
 #include "../../include/krep_gpu.h"
 #include "kg_device.h"
+#include "kg_format_dev.h"
 #include "kg_internal.h"
 
 namespace kg {
 
-constexpr u64 kOmStaleAfter = 10;          // result->count > 10 builds the newline index (krep.c:531)
-constexpr u64 kOmMaxText = 10000000000000000ull; // a line number has at most 16 digits here (two registers of 8)
-
-// newlines among the 16 bytes
-__device__ __forceinline__ u32 nl_count16(const uint4 v)
-{
-    return (u32)(__popc(eq_bytes(v.x, 0x0a0a0a0au)) + __popc(eq_bytes(v.y, 0x0a0a0a0au)) + __popc(eq_bytes(v.z, 0x0a0a0a0au)) +
-                 __popc(eq_bytes(v.w, 0x0a0a0a0au)));
-}
-// newlines in text[lo, hi) (hi <= text_len), any alignment
-__device__ __forceinline__ u32 nl_count(const uint8_t *__restrict__ text, u64 lo, u64 hi)
-{
-    u32 c = 0;
-    u64 p = lo;
-#pragma unroll 4
-    for (; p + 16 <= hi; p += 16)
-        c += nl_count16(load_unaligned<uint4>(text + p));
-    for (; p < hi; ++p)
-        c += text[p] == '\n';
-    return c;
-}
-__device__ __forceinline__ u32 om_digits(u64 v)
-{
-    u32 d = 1;
-    for (; v >= 10; v /= 10)
-        ++d;
-    return d;
-}
+// (kOmStaleAfter, kOmMaxText, nl_count, om_digits, om_find, OmFixed, OmItem / om_item / om_byte and om_blank live in kg_format_dev.h:
+// kg_batch_format.hip formats a pack of items with the same helpers)
 
 // (2) line[i] = 1 + the newlines in front of record i's start; before[] = newlines in front of every 4 KiB block, one entry more
 // than the text has blocks (its last entry is N).  A record that may not be read raises ctr[0] and touches no text.  ctr[1]: the
@@ -119,83 +94,6 @@ __global__ __launch_bounds__(256) void om_sizes(const u64 *__restrict__ rec, u64
     const u64 s = rec[2 * i], e = min(rec[2 * i + 1], text_len);
     bytes[i] = fixed + om_digits(ln) + 1 + (e - s) + 1;
 }
-
-// the largest r in [lo, hi] with off[r] <= pos (off[lo] <= pos)
-__device__ __forceinline__ u64 om_find(const u64 *__restrict__ off, u64 lo, u64 hi, u64 pos)
-{
-    while (lo < hi)
-    {
-        const u64 mid = lo + (hi - lo + 1) / 2;
-        if (off[mid] <= pos)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
-// the lengths of the three fixed strings, which lie behind one another in `fix`: prefix + before_number | after_number | after_match
-struct OmFixed
-{
-    u32 head, mid, tail;
-};
-// one record's output: where its parts end, counted from its first byte (b6 + 1 = its length)
-struct OmItem
-{
-    u64 src, b4, b5; // the match is text[src, src + b5 - b4)
-    u64 dlo, dhi;    // the digits of LINE as characters, the first one in the lowest byte of dlo
-    u32 b1, b2;      // head [0, b1), digits [b1, b2), ':' at b2, after_number [b2 + 1, b4), after_match [b5, b6), '\n' at b6
-    u64 b6;
-};
-// (`base`: the text offset of text[0] — 0 for the whole-text call, global_base for a window, whose text_len is the whole text's length)
-__device__ __forceinline__ OmItem om_item(const u64 *__restrict__ rec, const u64 *__restrict__ line, u64 text_len, const OmFixed f, u64 r,
-                                          u64 base = 0)
-{
-    OmItem it;
-    const uint4 w = *reinterpret_cast<const uint4 *>(rec + 2 * r);
-    const u64 s = ((u64)w.y << 32) | w.x, e = min(((u64)w.w << 32) | w.z, text_len);
-    u64 v = line[r], lo = 0, hi = 0;
-    u32 d = 0;
-    do // the least significant digit first: each one pushes the others up by a byte
-    {
-        hi = (hi << 8) | (lo >> 56);
-        lo = (lo << 8) | (u64)('0' + (u32)(v % 10));
-        v /= 10;
-        ++d;
-    } while (v);
-    it.src = s - base;
-    it.dlo = lo;
-    it.dhi = hi;
-    it.b1 = f.head;
-    it.b2 = f.head + d;
-    it.b4 = (u64)it.b2 + 1 + f.mid;
-    it.b5 = it.b4 + (e - s);
-    it.b6 = it.b5 + f.tail;
-    return it;
-}
-// its byte k (k <= b6)
-__device__ __forceinline__ u32 om_byte(const uint8_t *__restrict__ text, const uint8_t *__restrict__ fix, const OmFixed f, const OmItem &it, u64 k)
-{
-    if (k >= it.b4)
-    {
-        if (k < it.b5)
-        {
-            const u32 c = text[it.src + (k - it.b4)];
-            return c == '\n' ? (u32)' ' : c;
-        }
-        return k < it.b6 ? (u32)fix[f.head + f.mid + (k - it.b5)] : (u32)'\n';
-    }
-    if (k < it.b1)
-        return fix[k];
-    if (k < it.b2)
-    {
-        const u32 j = (u32)k - it.b1;
-        return (u32)((j < 8 ? it.dlo >> (8 * j) : it.dhi >> (8 * (j - 8))) & 0xffu);
-    }
-    return k == it.b2 ? (u32)':' : (u32)fix[f.head + (k - it.b2 - 1)];
-}
-// '\n' -> ' ' in the four bytes of w: the bytes differ in 0x2a
-__device__ __forceinline__ u32 om_blank(u32 w) { return w ^ ((eq_bytes(w, 0x0a0a0a0au) >> 7) * 0x2au); }
 
 // (4) chunk c is the 16 aligned bytes at (out - misalign) + 16 c, i.e. output offsets [16 c - misalign, + 16); `emit` records add bytes
 // text_len: the length of the WHOLE text, the clamp of a record's end in both instantiations.  WIN: the window call's gather — text[0] is
@@ -337,6 +235,13 @@ __global__ __launch_bounds__(64) void mw_count_to(const uint8_t *__restrict__ te
         ctr[2] = w.nl_before + before[b] + c;
         ctr[3] = before[nblocks - 1];
     }
+}
+
+// step (2) for a caller in another file (kg_batch_format.hip: the line numbers of a pack, before they are made relative per item)
+void om_lines_on(const uint8_t *d_text, u64 text_len, const u64 *d_rec, u64 n, const u64 *before, u64 nblocks, u64 *line, u64 *ctr,
+                 hipStream_t st)
+{
+    hipLaunchKernelGGL(om_lines, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_text, text_len, d_rec, n, before, nblocks, line, ctr);
 }
 
 } // namespace kg

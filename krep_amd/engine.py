@@ -12,6 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libkrep_gpu.so")
 
 
+def _libc_free(ptr: int):
+    """free() of a malloc-family block the library handed out (krep_gpu_grep_output_t.bytes)"""
+    libc = C.CDLL(None)
+    libc.free.restype = None
+    libc.free.argtypes = [C.c_void_p]
+    libc.free(C.c_void_p(ptr))
+
+
 class KrepGpuError(RuntimeError):
     pass
 
@@ -186,6 +194,23 @@ class Engine:
             L.krep_gpu_debug_batch_fill_host.argtypes = [C.POINTER(abi.BatchItem), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
             L.krep_gpu_debug_batch_rebase_launches.restype = None
             L.krep_gpu_debug_batch_rebase_launches.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "krep_gpu_grep_batch"):  # (likewise)
+            L.krep_gpu_format_lines_items.restype = C.c_int
+            L.krep_gpu_format_lines_items.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(abi.PackView), C.c_void_p, C.c_uint64,
+                                                      C.POINTER(abi.LineFormat), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                      C.POINTER(abi.LinesOut), C.c_void_p]
+            L.krep_gpu_format_matches_items.restype = C.c_int
+            L.krep_gpu_format_matches_items.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(abi.PackView), C.c_void_p, C.c_uint64,
+                                                        C.POINTER(abi.MatchFormat), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                        C.POINTER(abi.MatchesOut), C.c_void_p]
+            L.krep_gpu_grep_batch.restype = C.c_int
+            L.krep_gpu_grep_batch.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.Config), C.POINTER(abi.BatchItem), C.c_size_t,
+                                              C.POINTER(abi.GrepFormat), C.POINTER(abi.GrepItem), C.POINTER(abi.GrepOutput),
+                                              C.POINTER(abi.BatchInfo)]
+            L.krep_gpu_debug_grep_batch_times.restype = None
+            L.krep_gpu_debug_grep_batch_times.argtypes = [C.POINTER(C.c_double)] * 5
+            L.krep_gpu_debug_batch_format_launches.restype = None
+            L.krep_gpu_debug_batch_format_launches.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         if hasattr(L, "krep_gpu_alloc_placed"):
             L.krep_gpu_alloc_placed.restype = C.c_int
             L.krep_gpu_alloc_placed.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -606,6 +631,98 @@ class Engine:
         a, b = C.c_uint64(0), C.c_uint64(0)
         self.lib.krep_gpu_debug_batch_rebase_launches(C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
+
+    # ---- the grep output of a batch (krep -r): the formatters over a pack, and the host call ----
+    def format_lines_items(self, d_pack: int, packed_len: int, view: "abi.PackView", d_positions: int, n: int,
+                           fmt: "abi.LineFormat | None" = None, d_out: int = 0, out_capacity: int = 0, d_item_out_off: int = 0,
+                           stream: int = 0) -> "abi.LinesOut":
+        """krep_gpu_format_lines_items(): format_lines_ex over a PACK of items (pack-relative records in (start, end) order), every
+        item with the prefix `view` names for it.  d_out = 0 asks for .out_bytes; d_item_out_off: n_items + 1 device words, or 0."""
+        out = abi.LinesOut()
+        if self.lib.krep_gpu_format_lines_items(C.c_void_p(d_pack) if d_pack else None, packed_len, C.byref(view),
+                                                C.c_void_p(d_positions) if d_positions else None, n,
+                                                C.byref(fmt) if fmt is not None else None, C.c_void_p(d_out) if d_out else None,
+                                                out_capacity, C.c_void_p(d_item_out_off) if d_item_out_off else None, C.byref(out),
+                                                C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_format_lines_items failed: " + self.last_error())
+        return out
+
+    def format_matches_items(self, d_pack: int, packed_len: int, view: "abi.PackView", d_positions: int, n: int,
+                             fmt: "abi.MatchFormat | None" = None, d_out: int = 0, out_capacity: int = 0, d_item_out_off: int = 0,
+                             stream: int = 0) -> "abi.MatchesOut":
+        """krep_gpu_format_matches_items(): format_matches over a PACK of items: LINE restarts at 1 in every item and the stale
+        number is applied per item.  d_out = 0 asks for .out_bytes; d_item_out_off: n_items + 1 device words, or 0."""
+        out = abi.MatchesOut()
+        if self.lib.krep_gpu_format_matches_items(C.c_void_p(d_pack) if d_pack else None, packed_len, C.byref(view),
+                                                  C.c_void_p(d_positions) if d_positions else None, n,
+                                                  C.byref(fmt) if fmt is not None else None, C.c_void_p(d_out) if d_out else None,
+                                                  out_capacity, C.c_void_p(d_item_out_off) if d_item_out_off else None, C.byref(out),
+                                                  C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_format_matches_items failed: " + self.last_error())
+        return out
+
+    def batch_format_launches(self):
+        """(with the items' offset table in LDS, with the table in global memory): calls of the pack formatters so far"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self.lib.krep_gpu_debug_batch_format_launches(C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def grep_batch_times(self):
+        """(pack, scan, segment, format, read-back) milliseconds of the calling thread's last grep_batch"""
+        t = [C.c_double(0) for _ in range(5)]
+        self.lib.krep_gpu_debug_grep_batch_times(*[C.byref(x) for x in t])
+        return tuple(x.value for x in t)
+
+    def grep_format(self, names, mode: str, color: bool = False):
+        """(abi.GrepFormat, what keeps its strings alive) for items called `names` (bytes; None: no FILE: in front): the per-item
+        prefixes from line_format(name, color).prefix (mode "lines"), match_format(name, color).prefix ("matches") or the plain
+        "FILE:" the reference puts in front of a count ("count"), the other strings from the same two helpers"""
+        n = len(names)
+        if mode == "lines":
+            pre = [bytes(line_format(nm, color).prefix or b"") for nm in names]
+        elif mode == "matches":
+            pre = [bytes(match_format(nm, color).prefix or b"") for nm in names]
+        else:
+            pre = [b"" if nm is None else nm + b":" for nm in names]
+        arr = (C.c_char_p * max(n, 1))(*pre)
+        lens = (C.c_size_t * max(n, 1))(*[len(p) for p in pre])
+        lf, mf = line_format(None, color), match_format(None, color)
+        lf.prefix, lf.prefix_len, mf.prefix, mf.prefix_len = None, 0, None, 0
+        g = abi.GrepFormat(C.cast(arr, C.POINTER(C.c_char_p)), C.cast(lens, C.POINTER(C.c_size_t)), lf, mf)
+        return g, (arr, lens, pre, lf, mf)
+
+    def grep_batch(self, params: abi.Params, items, names, color=False, cfg=None, want_info=False):
+        """krep_gpu_grep_batch(params, items): what `krep [-o | -c] PATTERN` prints for every item, the items called `names` (bytes)
+        -> (bytes, [(count, offset, nbytes)]): item i's text is bytes[offset:offset + nbytes].  The mode is the reference's: -c when
+        params count, -o when cfg.only_matching, else matching lines.  cfg None: the process-wide defaults (a thread configuration
+        is passed as cfg).  Raises KrepGpuError with the library's reason on 2.  want_info: one more, the abi.BatchInfo."""
+        if cfg is None:
+            cfg = self.default_config()
+        n = len(items)
+        names = [None if nm is None else (nm if isinstance(nm, bytes) else str(nm).encode()) for nm in names]
+        assert len(names) == n
+        mode = ("count" if params.s.count_lines_mode or params.s.count_matches_mode else
+                "matches" if cfg.only_matching else "lines")
+        fmt, keep_fmt = self.grep_format(names, mode, color)
+        arr, _, keep = self.batch_items(items)
+        per = (abi.GrepItem * max(n, 1))()
+        out = abi.GrepOutput(None, 0, 0)
+        info = abi.BatchInfo()
+        dummy = C.c_int(0)
+        if params.s.num_patterns > 1 and not params.s.ac_trie:
+            params.s.ac_trie = C.cast(C.pointer(dummy), C.c_void_p)  # "caller pre-built the trie" (krep.c:2528)
+        try:
+            rc = self.lib.krep_gpu_grep_batch(params.ref, C.byref(cfg), arr, n, C.byref(fmt), per, C.byref(out), C.byref(info))
+            if rc:
+                raise KrepGpuError(self.last_error() or "krep_gpu_grep_batch failed")
+            data = C.string_at(out.bytes, out.len) if out.len else b""
+        finally:
+            if out.bytes:
+                _libc_free(out.bytes)
+            params.s.ac_trie = None
+        del keep, keep_fmt
+        res = [(int(p.count), int(p.out_offset), int(p.out_bytes)) for p in per[:n]]
+        return (data, res, info) if want_info else (data, res)
 
     def batch_items(self, items):
         """(krep_gpu_batch_item_t[n], n, what keeps the texts alive) for `items` (bytes or np.uint8 arrays): for batch_fill_host()"""

@@ -12,6 +12,8 @@ with the sanitizer named.
                                        # then its --digest over the whole corpus against tests/golden/regex_compile_digest.json
     python tools/sanitize.py batchfill # the host side of a batch's pack (kg_batch_pack.h) as a stand-alone program
                                        # (tools/batch_fill_san.cpp) under ASan + UBSan: every slice of 3000 small packs
+    python tools/sanitize.py batchprefix # the prefix blob of krep_gpu_grep_batch (kg_batch_pack.h batch_prefix_blob) as a stand-alone
+                                       # program (tools/batch_prefix_san.cpp) under ASan + UBSan: 20000 lists of prefixes
 
 Each mode prints the sanitizer reports it saw (none expected) and exits non-zero on one; profiles/r06_sanitizers.txt is its log."""
 import glob
@@ -120,10 +122,11 @@ def main():
                   f"recording {' '.join(differ[:20])}")
             rc = rc or (1 if differ else 0)
         rc = rc or r.returncode
-    elif mode == "batchfill":
-        exe = os.path.join(SAN, "batch_fill_san")
+    elif mode in ("batchfill", "batchprefix"):
+        name = "batch_fill_san" if mode == "batchfill" else "batch_prefix_san"
+        exe = os.path.join(SAN, name)
         r = run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-o", exe,
-                 os.path.join(ROOT, "tools", "batch_fill_san.cpp")])
+                 os.path.join(ROOT, "tools", name + ".cpp")])
         if r.returncode:
             return r.returncode
         r = run([exe], env={"ASAN_OPTIONS": "detect_leaks=1:halt_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}, capture_output=True, text=True)
