@@ -54,6 +54,18 @@ uint64_t krep_gpu_debug_literal_dma_launches(void);
 uint64_t krep_gpu_debug_literal_dma_one_pass_launches(void);
 uint64_t krep_gpu_debug_literal_dma_one_pass_failovers(void);
 void krep_gpu_debug_force_literal_dma_grid(int blocks);
+/* ... and its ticket map forced: the first `n_long` tickets (as many of them as the text holds) take `long_units` units (8, 16 or 32), the
+ * rest 8, whatever the density the plan knows; long_units = 0: the library's choice again.  A text of 2 MiB reaches every kind of seam so.
+ * A plan whose long ticket overflowed a wave's list on a text halves it for that text all the same. */
+void krep_gpu_debug_force_literal_dma_tickets(int long_units, uint64_t n_long);
+/* ... and the map the last launch of that mode ran with: the units of its long tickets and how many there were (n_long = 0: one size) */
+void krep_gpu_debug_literal_dma_last_tickets(uint32_t *long_units, uint64_t *n_long);
+/* test hooks (host only, no GPU needed) of that map (krep_amd/csrc/kg_tickets.h): ticket `ticket`'s first unit and units under the map
+ * {upt_long, upt, n_long} on a text of n_units, and the map's number of tickets; returns 0, or 2 for a map the launcher refuses.  And the
+ * number of long tickets the library gives a text of n_units scanned by `waves` waves (0: none, every ticket short) */
+int krep_gpu_debug_ticket_map(uint32_t upt_long, uint32_t upt, uint64_t n_long, uint64_t n_units, uint64_t ticket, uint64_t *first,
+                              uint32_t *units, uint64_t *n_tickets);
+uint64_t krep_gpu_debug_ticket_map_long_tickets(uint64_t n_units, uint32_t upt_long, uint32_t upt, uint64_t waves);
 /* what chose between that kernel and the register kernel for `plan`: has the text been sampled, is the kernel barred for it (the prefilter's
  * byte occurs in more than 35 % of its 1-KiB cells; $KREP_GPU_LIT_DMA_MAX_PASS), the share last measured (sample or launch).
  * $KREP_GPU_LIT_DMA_KEEP=1: no sample, no bar (measurement aid) */

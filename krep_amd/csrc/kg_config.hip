@@ -20,6 +20,7 @@
 #include "kg_internal.h"
 #include "kg_plan.h"
 #include "kg_replay.h"
+#include "kg_tickets.h"
 
 using namespace kg;
 
@@ -273,5 +274,32 @@ extern "C" uint64_t krep_gpu_debug_literal_dma_launches(void) { return kg::g_lit
 extern "C" uint64_t krep_gpu_debug_literal_dma_one_pass_launches(void) { return kg::g_lit_dma1p_launches.load(); }
 extern "C" uint64_t krep_gpu_debug_literal_dma_one_pass_failovers(void) { return kg::g_lit_dma1p_failovers.load(); }
 extern "C" void krep_gpu_debug_force_literal_dma_grid(int blocks) { kg::g_lit_dma1p_force_grid = blocks < 0 ? 0 : blocks; }
+extern "C" void krep_gpu_debug_force_literal_dma_tickets(int long_units, uint64_t n_long)
+{
+    const bool ok = long_units == 8 || long_units == 16 || long_units == 32;
+    kg::g_lit_dma1p_force_long = ok ? long_units : 0;
+    kg::g_lit_dma1p_force_n_long = ok ? n_long : 0;
+}
+extern "C" void krep_gpu_debug_literal_dma_last_tickets(uint32_t *long_units, uint64_t *n_long)
+{
+    *long_units = kg::g_lit_dma1p_last_long.load();
+    *n_long = kg::g_lit_dma1p_last_n_long.load();
+}
+extern "C" int krep_gpu_debug_ticket_map(uint32_t upt_long, uint32_t upt, uint64_t n_long, uint64_t n_units, uint64_t ticket, uint64_t *first,
+                                         uint32_t *units, uint64_t *n_tickets)
+{
+    if (!upt || (n_long && (!upt_long || n_long > n_units / upt_long)))
+        return 2;
+    const kg::TkMap m = {upt_long, upt, n_long};
+    const kg::TkSpan s = kg::tk_map(m, n_units, ticket);
+    *first = s.first;
+    *units = s.units;
+    *n_tickets = kg::tk_map_tickets(m, n_units);
+    return 0;
+}
+extern "C" uint64_t krep_gpu_debug_ticket_map_long_tickets(uint64_t n_units, uint32_t upt_long, uint32_t upt, uint64_t waves)
+{
+    return kg::tk_map_long_tickets(n_units, upt_long, upt, waves);
+}
 extern "C" uint64_t krep_gpu_debug_runs_launches(void) { return kg::g_runs_launches.load(); }
 

@@ -83,13 +83,20 @@ hipError_t launch_dma_byte_look(const uint8_t *text, uint64_t lo, uint32_t n_cel
 extern std::atomic<uint64_t> g_runs_launches;                                      // launches of run_count_kernel (kg_runs.hip, test hook)
 extern std::atomic<uint64_t> g_lit_dma_launches;                                   // launches of lit_scan_dma (test hook)
 // ... its one-pass records mode: the scanning waves write the records at their final index (kg_tickets.h); d_agg / d_pref: n_tickets =
-// ceil(units / a.upt) words each, zeroed on the stream in front of the launch like a.ctr (whose pad[0] the resolver is claimed through)
-hipError_t launch_literal_dma_one_pass(const LitArgs &a, unsigned long long *d_agg, unsigned long long *d_pref, uint64_t n_tickets,
+// tk_map_tickets(tk, units) words each (kg_tickets.h: tk = the ticket map, long tickets in front, tk.upt = a.upt), zeroed on the stream in
+// front of the launch like a.ctr (whose pad[0] the resolver is claimed through)
+struct TkMap;
+hipError_t launch_literal_dma_one_pass(const LitArgs &a, const TkMap &tk, unsigned long long *d_agg, unsigned long long *d_pref, uint64_t n_tickets,
                                        uint32_t num_cu, hipStream_t st);
 uint32_t lit_dma_one_pass_list();                                                  // entries of a wave's hit list: what a ticket may hold at most
 extern std::atomic<uint64_t> g_lit_dma1p_launches;                                 // launches in that mode (test hook)
 extern std::atomic<uint64_t> g_lit_dma1p_failovers;                                // ... that handed their scan over to the two-pass road
 extern int g_lit_dma1p_force_grid;                                                 // test hook: at most this many workgroups (0 = auto)
+uint32_t lit_dma_one_pass_grid(const LitArgs &a, uint32_t num_cu);                 // workgroups that mode launches (x 4 waves: who draws its tickets)
+extern std::atomic<uint32_t> g_lit_dma1p_last_long;                                // test hook: the last launch's long ticket (units; the short one if none) ...
+extern std::atomic<uint64_t> g_lit_dma1p_last_n_long;                              // ... and how many of its tickets were long
+extern int g_lit_dma1p_force_long;                                                // test hook: units of a long ticket (0 = the host's choice) ...
+extern uint64_t g_lit_dma1p_force_n_long;                                          // ... and how many tickets are long (as far as the text holds them)
 
 // kg_single.hip — single byte with records in one pass (counts resolved by one wave, records written a ticket later)
 struct PostScratch;

@@ -43,18 +43,22 @@ static_assert(kOpTk <= 64u, "one lane per parked ticket picks its prefix up");
 uint32_t lit_dma_one_pass_list() { return kOpHits; }
 
 // ONEP: the scanning waves write the records themselves, at their final index, by the ticket -> resolver -> deferred-store scheme of
-// kg_tickets.h (agg / pref: its per-ticket counts and prefixes, zeroed by the host; n_tickets = ceil(units / a.upt), a.upt >= 1):
+// kg_tickets.h (agg / pref: its per-ticket counts and prefixes, zeroed by the host; n_tickets = tk_map_tickets() of the ticket map
+// tk = {upt_long, a.upt >= 1, n_long}: long tickets — 16 or 32 units, where the text is sparse enough for the list — for the bulk of a large text, so
+// that a wave crosses fewer seams, and a.upt-unit tickets for its end, so that the kernel's tail is no longer than before):
 //   * the first wave 0 to claim ctr->pad[0] is the resolver and does not scan;
 //   * a hit goes into the wave's LDS hit list as its ticket-relative offset, ranked inside the TICKET (wcnt runs over the ticket);
 //   * at a ticket's end its count is published (one 8-byte store) BEFORE anything is waited for, and {ticket, count, list index} is parked;
-//   * when the list (a ring) is more than half full or the table is full (BASELINE's 27 hits per 256-KiB ticket: every ~14 tickets, ~1 ms), and
+//   * when the list (a ring) is more than half full or the table is full (BASELINE's 27 hits per 256-KiB ticket: every ~14 tickets, ~1 ms; its 105 per
+//     1-MiB long ticket: every three to four), and
 //     at the end, the wave picks up the prefixes of all its parked tickets BUT THE ONE THAT HAS JUST ENDED at once (one lane each: one memory latency, and every count they
 //     depend on was published by a wave that was not waiting) and writes the records: 16-byte non-temporal stores, lanes mapped to record
 //     indices rounded down to 8 as kg_single.hip does.  These sit where flush_parked() sits in the staging mode: between rounds;
 //   * a ticket with more hits than the list has room for is counted, not recorded: ctr->overflow_units, the host takes the two-pass road.
 // No info words, no staging slots.  The streaming loop is the staging mode's, instruction for instruction.
 template <int KIND, bool MASKED, bool CI, bool ONEP>
-__global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *__restrict__ agg, const u64 *__restrict__ pref, const u64 n_tickets)
+__global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *__restrict__ agg, const u64 *__restrict__ pref, const u64 n_tickets,
+                                                          const TkMap tk)
 {
     // The ring is the ONLY thing in the dynamic LDS block and is read through inline ds_read (below): the compiler orders every LDS
     // access that may alias an LDS-DMA destination behind s_waitcnt vmcnt(0) — which would retire the next round's DMA before this
@@ -118,13 +122,23 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *
         n_park = 0;
     };
 
-    // tickets of a.upt consecutive units per wave, or (a.upt == 0) the static interleaved deal, one unit at a time
+    // tickets of a.upt consecutive units per wave, or (a.upt == 0) the static interleaved deal, one unit at a time; ONEP: tickets of two
+    // sizes, long ones in front (kg_tickets.h tk_map).  Returns the ticket's first unit; `units`: at most so many (ONEP: exactly, the ragged
+    // end clipped); `tno`: its number (ONEP)
     const u32 tk_units = a.upt ? a.upt : 1u;
+    const TkMap tmap = {tk.upt_long, tk_units, tk.n_long}; // (the staging mode: n_long = 0, not looked at)
     u64 static_next = (u64)blockIdx.x * kWavesPerBlk + wave;
-    auto next_ticket = [&]() -> u64 {
+    auto next_ticket = [&](u32 &units, u64 &tno) -> u64 {
+        units = tk_units;
         if (a.upt)
         {
-            return wave_fetch_add(&a.ctr->ticket, 1ull, lane) * (u64)a.upt;
+            const u64 t = wave_fetch_add(&a.ctr->ticket, 1ull, lane);
+            if (!ONEP)
+                return t * (u64)a.upt;
+            const TkSpan s = tk_map(tmap, n_units, t);
+            tno = t;
+            units = s.units;
+            return s.first;
         }
         const u64 u = static_next;
         static_next += (u64)gridDim.x * kWavesPerBlk;
@@ -166,7 +180,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *
             const u32 t = __builtin_amdgcn_readfirstlane(s_tk[3u * i]), cnt = __builtin_amdgcn_readfirstlane(s_tk[3u * i + 1u]),
                       at = __builtin_amdgcn_readfirstlane(s_tk[3u * i + 2u]);
             const u64 first = ((u64)(u32)__builtin_amdgcn_readlane((u32)(pfx >> 32), i) << 32) | (u32)__builtin_amdgcn_readlane((u32)pfx, i);
-            const u64 tbase = a.global_base + a.anchor + (u64)t * ((u64)tk_units * kUnitBytes);
+            const u64 tbase = a.global_base + a.anchor + tk_map(tmap, n_units, (u64)t).first * kUnitBytes;
             const u32 pad = (u32)(first & 7ull); // (whole 128-byte lines per store instruction except at the two ends of the ticket's run)
             for (u32 q = lane; q < cnt + pad; q += 64u)
             {
@@ -264,6 +278,9 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *
             fresh = 1;
         }
         wcnt = 0;
+        // (what the next ticket finds free: `used` is at most kOpHits / 2 here, or the flush below leaves nothing but the ticket that has
+        //  just ended — so kOpHits - max(kOpHits / 2, that ticket's hits): half the list after every ticket that held no more than half of
+        //  it, whatever the ticket's length; the host sizes long tickets to a quarter of the list on average, kg_scan.hip lit_dma_one_pass)
         if ((n_tkp == kOpTk || used > kOpHits / 2u) && n_tkp > fresh)
             flush_records(n_tkp - fresh);
     };
@@ -313,11 +330,14 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *
         }
     };
 
-    u64 u0 = next_ticket();
+    u32 tku = 0, tku_next = 0; // units of the ticket being scanned, of the one drawn behind it
+    u64 tno = 0, tno_next = 0; // ONEP: their numbers
+    u64 u0 = next_ticket(tku, tno);
     bool dma_cur = u0 < n_units && issue_round(a.anchor + u0 * kUnitBytes, 0u);
     while (u0 < n_units)
     {
-        const u32 nun = (u32)((n_units - u0 < (u64)tk_units) ? (n_units - u0) : (u64)tk_units), nr = nun * (u32)kRoundsBig;
+        const u32 tk_cap = ONEP ? tku : tk_units; // (ONEP: tk_map has clipped the ragged end already)
+        const u32 nun = (u32)((n_units - u0 < (u64)tk_cap) ? (n_units - u0) : (u64)tk_cap), nr = nun * (u32)kRoundsBig;
         const u64 tbase = a.anchor + u0 * kUnitBytes;
         u64 u_next = ~0ull;
         bool tail_ok = false;
@@ -335,7 +355,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *
                 dma_nx = issue_round(seg + kSegBytes, (g + 1u) & 1u);
             else
             {
-                u_next = next_ticket();
+                u_next = next_ticket(tku_next, tno_next);
                 if (u_next < n_units)
                     dma_nx = issue_round(a.anchor + u_next * kUnitBytes, (g + 1u) & 1u);
             }
@@ -549,7 +569,7 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *
                     deferred = false;
                 }
                 if (ONEP)
-                    end_ticket((u32)u0 / tk_units);
+                    end_ticket((u32)tno);
                 else
                     publish(unit);
             }
@@ -558,6 +578,8 @@ __global__ __launch_bounds__(kBlock, 2) void lit_scan_dma(const LitArgs a, u64 *
             dma_cur = dma_nx;
         }
         u0 = u_next;
+        tku = tku_next;
+        tno = tno_next;
     }
     if (!ONEP && park && n_park)
         flush_parked();
@@ -607,39 +629,56 @@ std::atomic<uint64_t> g_lit_dma_launches{0};
 std::atomic<uint64_t> g_lit_dma1p_launches{0}; // ... of them in the one-pass records mode (ONEP)
 std::atomic<uint64_t> g_lit_dma1p_failovers{0}; // ... whose scan was handed over to the two-pass road (kg_scan.hip lit_dma_one_pass)
 int g_lit_dma1p_force_grid = 0;                // test hook: at most this many workgroups for that mode (0 = auto)
+int g_lit_dma1p_force_long = 0;                // test hook: long tickets of this many units (0 = auto) ...
+uint64_t g_lit_dma1p_force_n_long = 0;         // ... and this many of them (kg_scan.hip lit_dma_one_pass)
+
+std::atomic<uint32_t> g_lit_dma1p_last_long{0};   // test hook: the ticket map of the last one-pass launch
+std::atomic<uint64_t> g_lit_dma1p_last_n_long{0};
+
+static u32 dma_grid(const LitArgs &a, u32 num_cu, bool onep)
+{
+    static const u32 bpc = [] { const char *e = getenv("KREP_GPU_LIT_DMA_BLOCKS_PER_CU"); return e && atoi(e) > 0 ? (u32)atoi(e) : 2u; }();
+    u32 grid = (u32)std::min<u64>(a.num_tiles, (u64)num_cu * bpc);
+    if (onep && g_lit_dma1p_force_grid > 0) // test hook: a starved grid — the progress argument of kg_tickets.h
+        grid = std::min<u32>(grid, (u32)g_lit_dma1p_force_grid);
+    return grid ? grid : 1u;
+}
+uint32_t lit_dma_one_pass_grid(const LitArgs &a, uint32_t num_cu) { return dma_grid(a, num_cu, true); }
 
 template <int KIND, bool MASKED, bool CI, bool ONEP>
-static hipError_t dma_launch4(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st)
+static hipError_t dma_launch4(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st, const TkMap &tk = TkMap{0, 0, 0})
 {
     constexpr u32 lds = kWavesPerBlk * kDmaWaveLds; // dynamic part (the rings); the parked stores are static
     if (const hipError_t e = grant_dynamic_lds<&lit_scan_dma<KIND, MASKED, CI, ONEP>>((int)lds); e != hipSuccess)
         return e;
-    static const u32 bpc = [] { const char *e = getenv("KREP_GPU_LIT_DMA_BLOCKS_PER_CU"); return e && atoi(e) > 0 ? (u32)atoi(e) : 2u; }();
-    u32 grid = (u32)std::min<u64>(a.num_tiles, (u64)num_cu * bpc);
-    if (ONEP && g_lit_dma1p_force_grid > 0) // test hook: a starved grid — the progress argument of kg_tickets.h
-        grid = std::min<u32>(grid, (u32)g_lit_dma1p_force_grid);
-    hipLaunchKernelGGL((lit_scan_dma<KIND, MASKED, CI, ONEP>), dim3(grid ? grid : 1), dim3(kBlock), lds, st, a, agg, pref, n_tickets);
+    const u32 grid = dma_grid(a, num_cu, ONEP);
+    if (ONEP)
+    {
+        g_lit_dma1p_last_long.store(tk.n_long ? tk.upt_long : a.upt, std::memory_order_relaxed);
+        g_lit_dma1p_last_n_long.store(tk.n_long, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL((lit_scan_dma<KIND, MASKED, CI, ONEP>), dim3(grid ? grid : 1), dim3(kBlock), lds, st, a, agg, pref, n_tickets, tk);
     g_lit_dma_launches.fetch_add(1, std::memory_order_relaxed);
     if (ONEP)
         g_lit_dma1p_launches.fetch_add(1, std::memory_order_relaxed);
     return hipGetLastError();
 }
 template <int KIND, bool MASKED, bool ONEP>
-static hipError_t dma_launch2(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st)
+static hipError_t dma_launch2(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st, const TkMap &tk = TkMap{0, 0, 0})
 {
-    return (a.flags & F_CI) ? dma_launch4<KIND, MASKED, true, ONEP>(a, agg, pref, n_tickets, num_cu, st)
-                            : dma_launch4<KIND, MASKED, false, ONEP>(a, agg, pref, n_tickets, num_cu, st);
+    return (a.flags & F_CI) ? dma_launch4<KIND, MASKED, true, ONEP>(a, agg, pref, n_tickets, num_cu, st, tk)
+                            : dma_launch4<KIND, MASKED, false, ONEP>(a, agg, pref, n_tickets, num_cu, st, tk);
 }
 template <bool ONEP>
-static hipError_t dma_launch1(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st)
+static hipError_t dma_launch1(const LitArgs &a, u64 *agg, const u64 *pref, u64 n_tickets, u32 num_cu, hipStream_t st, const TkMap &tk = TkMap{0, 0, 0})
 {
     if (a.m < 4)
-        return dma_launch2<4, true, ONEP>(a, agg, pref, n_tickets, num_cu, st);
+        return dma_launch2<4, true, ONEP>(a, agg, pref, n_tickets, num_cu, st, tk);
     if (a.m == 4)
-        return dma_launch2<4, false, ONEP>(a, agg, pref, n_tickets, num_cu, st);
+        return dma_launch2<4, false, ONEP>(a, agg, pref, n_tickets, num_cu, st, tk);
     if (a.m < 8)
-        return dma_launch2<8, true, ONEP>(a, agg, pref, n_tickets, num_cu, st);
-    return dma_launch2<8, false, ONEP>(a, agg, pref, n_tickets, num_cu, st);
+        return dma_launch2<8, true, ONEP>(a, agg, pref, n_tickets, num_cu, st, tk);
+    return dma_launch2<8, false, ONEP>(a, agg, pref, n_tickets, num_cu, st, tk);
 }
 
 // does this launch take the LDS-DMA kernel?  2..8-byte patterns, 32-KiB units, no -c, not the emit-mode re-scan
@@ -657,13 +696,15 @@ hipError_t launch_literal_dma(const LitArgs &a, u32 num_cu, hipStream_t st)
     return dma_launch1<false>(a, nullptr, nullptr, 0, num_cu, st);
 }
 // the one-pass records mode: d_agg / d_pref = n_tickets words each, zeroed on the stream in front of the launch, like a.ctr
-hipError_t launch_literal_dma_one_pass(const LitArgs &a, unsigned long long *d_agg, unsigned long long *d_pref, uint64_t n_tickets, u32 num_cu,
+hipError_t launch_literal_dma_one_pass(const LitArgs &a, const TkMap &tk, unsigned long long *d_agg, unsigned long long *d_pref, uint64_t n_tickets, u32 num_cu,
                                        hipStream_t st)
 {
     const u64 n_units = a.num_tiles * kWavesPerBlk;
-    if (!(a.flags & F_POS) || !a.upt || n_units >= (1ull << 32) || n_tickets != (n_units + a.upt - 1) / a.upt || (u64)a.upt * kRoundsBig * kSegBytes > (1ull << 31))
+    const u64 tk_max = std::max<u64>(a.upt, tk.n_long ? tk.upt_long : 0u); // (ticket-relative offsets are u32)
+    if (!(a.flags & F_POS) || !a.upt || n_units >= (1ull << 32) || tk.upt != a.upt || (tk.n_long && (!tk.upt_long || tk.n_long > n_units / tk.upt_long)) ||
+        n_tickets != tk_map_tickets(tk, n_units) || tk_max * kRoundsBig * kSegBytes > (1ull << 31))
         return hipErrorInvalidValue;
-    return dma_launch1<true>(a, d_agg, d_pref, n_tickets, num_cu, st);
+    return dma_launch1<true>(a, d_agg, d_pref, n_tickets, num_cu, st, tk);
 }
 
 } // namespace kg

@@ -59,6 +59,9 @@ struct krep_gpu_plan
     bool dma1p_off = false;       // a ticket of this text overflowed the list (or the safety net fired): the two-pass road for this text
     const void *dma1p_off_text = nullptr;
     size_t dma1p_off_len = 0;
+    uint32_t dma1p_long_max = 32; // ... a LONG ticket of this text did: long tickets of at most so many units for it (halved each time; 8 = none)
+    const void *dma1p_long_text = nullptr;
+    size_t dma1p_long_len = 0;
     double lit_density = -1.0;    // hits per byte the plan knows of its text (first look / last scan); < 0: nothing known yet
     bool first_look_done = false; // lit_first_look: the density of the plan's first large text has been sampled (road / ring shape / slot from it)
     bool fused1_ok = true;    // single byte with records: the one-pass kernel (kg_single.hip) until a scan proves too dense for it

@@ -17,6 +17,7 @@
 #include "kg_internal.h"
 #include "kg_plan.h"
 #include "kg_replay.h"
+#include "kg_tickets.h"
 
 using namespace kg;
 
@@ -213,7 +214,9 @@ static int lit_dma_look(krep_gpu_plan *pl, const Window &w, const LitPass &ps, L
     // offsets, 1.29 vs 1.37 ms counting; at 16 GiB 2.58 vs 2.63 ms; at 2 GiB 0.37 vs 0.48 ms (the ticket word becomes the limit
     // of a short scan); at 32 GiB tickets win: 5.20 vs 5.31 ms, and 7.1 vs 7.9 ms on the single-byte workload
     // (the LDS-DMA kernel, kg_literal_dma.hip, wants tickets — a ticket is what it streams through without a seam — and is ahead with them
-    //  from ~8 GiB on: 8 GiB 1.339 against 1.362 ms for the register kernel's static deal, 16 GiB 2.610 against 2.639; round 6)
+    //  from ~8 GiB on: 8 GiB 1.339 against 1.362 ms for the register kernel's static deal, 16 GiB 2.610 against 2.639; round 6.  The 8 units
+    //  set here are the SHORT ticket of its one-pass records mode, which sizes a long one for the bulk of the text by the density the plan
+    //  knows: lit_dma_one_pass, kg_tickets.h TkMap; measured ticket sizes: profiles/r08_ticket_size.txt)
     const bool dma_shape = m_scan >= 2 && m_scan <= 8 && !ps.lines && !ps.first_byte && a.prefilter != 0u && !getenv("KREP_GPU_LIT_NO_DMA");
     auto tickets_for = [&](bool dma) { return (a.rounds == kRoundsBig && L.n_units / ((uint64_t)pl->num_cu * 16) >= (dma ? 64u : 192u)) ? 8u : 0u; };
     a.upt = tickets_for(dma_shape);
@@ -421,7 +424,7 @@ static void lit_reopen(krep_gpu_plan *pl, const LitScan &L)
 // deferred-store scheme of kg_tickets.h, so there are no info words, no staging slots and no ordering post-pass: on the stream, one
 // memset (the counters and the ticket arrays lie in one block of post.d_tk), the launch, the end event, the read-back of the counters.
 // A ticket with more hits than a wave's list holds (or the spin-limit safety net) raises overflow_units: the two-pass road takes this
-// scan and the plan's later ones on this text.  *done: the scan is complete.
+// scan and the plan's later ones on this text (with long tickets in the map: shorter ones first).  *done: the scan is complete.
 static int lit_dma_one_pass(krep_gpu_plan *pl, const Window &w, const LitPass &ps, LitScan &L, hipStream_t st, LitResult *res, bool *done)
 {
     *done = false;
@@ -432,6 +435,13 @@ static int lit_dma_one_pass(krep_gpu_plan *pl, const Window &w, const LitPass &p
     LitArgs a = L.a;
     if (!a.upt && getenv("KREP_GPU_LIT_DMA_ALL") && !getenv("KREP_GPU_LIT_UPT"))
         a.upt = 8; // (the tests' switch on a text below the ticketed range: this mode needs tickets from one counter)
+    const char *upt_env = getenv("KREP_GPU_LIT_UPT");
+    if (upt_env) // measurement aid, wider on this road than in lit_dma_look: the one-pass mode parks no units, so EVERY ticket takes 16 or 32
+    {            // units as well (profiles/r08_ticket_size.txt); with the switch set, whatever its value, the map has one size
+        const int v = atoi(upt_env);
+        if (a.upt && (v == 16 || v == 32))
+            a.upt = (uint32_t)v;
+    }
     if (!a.upt || !literal_dma_eligible(a) || L.n_units >= (1ull << 32))
         return 0;
     if (pl->dma1p_off && pl->dma1p_off_text == (const void *)w.d_text && pl->dma1p_off_len == w.text_len)
@@ -443,10 +453,40 @@ static int lit_dma_one_pass(krep_gpu_plan *pl, const Window &w, const LitPass &p
     const double gate = std::min(0.25 * (double)lit_dma_one_pass_list(), fusedk_min_hits_per_unit() * (double)a.upt);
     if (pl->lit_density >= 0.0 && pl->lit_density * (double)ticket_bytes >= gate)
         return 0;
+    // Long tickets for the bulk of the text, today's for its end (kg_tickets.h TkMap): a wave crosses a seam — the ticket draw it has to wait
+    // for, the tail piece, the count, the parked entry — a quarter as often, and the kernel's end stays graded by short tickets.  How long:
+    // the largest of 32, 16 or 8 units at which the density the plan knows keeps a ticket at or under a quarter of the list (BASELINE's 105 hits
+    // per MiB: 32); a plan that knows no density yet scans with 8.  The list's rule under them (kg_literal_dma.hip end_ticket): a flush leaves
+    // at most the ticket that has just ended in the list, so the ticket being scanned has list_size - max(list_size / 2, hits of the one
+    // before it) entries free — half the list unless a ticket held twice the gate, and a ticket denser than that is counted, not recorded.
+    // How many: tk_map_long_tickets().  A long ticket that overflowed halves the plan's long ticket for this text (below).
+    const bool long_text = pl->dma1p_long_text == (const void *)w.d_text && pl->dma1p_long_len == w.text_len;
+    uint32_t upt_long = a.upt;
+    if (!upt_env && a.upt == 8)
+    {
+        if (g_lit_dma1p_force_long) // (test hook)
+            upt_long = (uint32_t)g_lit_dma1p_force_long;
+        else if (pl->lit_density >= 0.0)
+            for (uint32_t v = 32; v > a.upt && upt_long == a.upt; v >>= 1)
+                if (pl->lit_density * (double)v * (double)L.unit_bytes() <= 0.25 * (double)lit_dma_one_pass_list())
+                    upt_long = v;
+        upt_long = std::min(upt_long, long_text ? std::max(pl->dma1p_long_max, a.upt) : 32u);
+    }
+    TkMap tk = {0u, a.upt, 0ull};
+    if (upt_long > a.upt)
+    {
+        const uint64_t waves = (uint64_t)lit_dma_one_pass_grid(a, (uint32_t)pl->num_cu) * kWavesPerBlk;
+        tk.n_long = g_lit_dma1p_force_long ? std::min<uint64_t>(g_lit_dma1p_force_n_long, L.n_units / upt_long)
+                                           : tk_map_long_tickets(L.n_units, upt_long, a.upt, waves);
+    }
+    tk.upt_long = tk.n_long ? upt_long : 0u;
+    if (getenv("KREP_GPU_DEBUG"))
+        fprintf(stderr, "krep-gpu: literal scan, one pass: %llu units in %llu tickets of %u and the rest in tickets of %u\n", (unsigned long long)L.n_units,
+                (unsigned long long)tk.n_long, tk.upt_long, tk.upt);
     // [Counters (16 words) | counts | prefixes]: one block, one memset
     constexpr uint64_t kCtrWords = 16;
     static_assert(sizeof(Counters) <= kCtrWords * sizeof(unsigned long long), "the counters in front of the ticket arrays");
-    const uint64_t n_tk = (L.n_units + a.upt - 1) / a.upt, cap_tk = n_tk + kCtrWords / 2;
+    const uint64_t n_tk = tk_map_tickets(tk, L.n_units), cap_tk = n_tk + kCtrWords / 2;
     PostScratch &post = *ps.post;
     HIPCHK(grow_scratch(post.tk_cap, cap_tk, cap_tk, {dev_buf(post.d_tk, 2 * cap_tk * sizeof(unsigned long long))}));
     Counters *d_ctr = reinterpret_cast<Counters *>(post.d_tk);
@@ -456,7 +496,7 @@ static int lit_dma_one_pass(krep_gpu_plan *pl, const Window &w, const LitPass &p
     a.pos_cap = ps.out_cap;
     a.stage_cap = 0;
     HIPCHK(hipMemsetAsync(post.d_tk, 0, (kCtrWords + 2 * n_tk) * sizeof(unsigned long long), st));
-    HIPCHK(launch_literal_dma_one_pass(a, d_agg, d_pref, n_tk, (uint32_t)pl->num_cu, st));
+    HIPCHK(launch_literal_dma_one_pass(a, tk, d_agg, d_pref, n_tk, (uint32_t)pl->num_cu, st));
     if (ps.ev_end) HIPCHK(hipEventRecord(ps.ev_end, st));
     HIPCHK(hipMemcpyAsync(pl->h_ctr, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -465,12 +505,24 @@ static int lit_dma_one_pass(krep_gpu_plan *pl, const Window &w, const LitPass &p
     lit_dma_rate(pl, w, La);
     if (pl->h_ctr->overflow_units)
     {
-        pl->dma1p_off = true;
-        pl->dma1p_off_text = w.d_text;
-        pl->dma1p_off_len = w.text_len;
+        if (tk.n_long)
+        {
+            // (the kernel does not say which ticket it was: with long tickets in the map the long ones are the first suspects — half as long
+            //  on the plan's next scan of this text, the road itself barred only once an all-short map has overflowed too)
+            pl->dma1p_long_max = tk.upt_long / 2;
+            pl->dma1p_long_text = w.d_text;
+            pl->dma1p_long_len = w.text_len;
+        }
+        else
+        {
+            pl->dma1p_off = true;
+            pl->dma1p_off_text = w.d_text;
+            pl->dma1p_off_len = w.text_len;
+        }
         g_lit_dma1p_failovers.fetch_add(1);
         if (getenv("KREP_GPU_DEBUG"))
-            fprintf(stderr, "krep-gpu: literal scan: a ticket overflowed the one-pass hit list -> the two-pass road for this text\n");
+            fprintf(stderr, "krep-gpu: literal scan: a ticket overflowed the one-pass hit list -> the two-pass road for this %s\n",
+                    tk.n_long ? "scan, shorter long tickets for this text" : "text");
         return 0;
     }
     if (L.span() >= ticket_bytes)

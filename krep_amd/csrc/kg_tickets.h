@@ -16,6 +16,51 @@
 
 namespace kg {
 
+// ---- the ticket map of kg_literal_dma.hip ONEP: which units a ticket number stands for.  Two sizes: the first n_long tickets hold
+// upt_long units each (the bulk of the text: fewer seams per wave), the rest upt units (the end of the text: the kernel's tail stays as
+// short as a short ticket), the last one what is left.  n_long * upt_long <= n_units.  n_long = 0 is the one-size map, t * upt.
+// The kernel and the host use these three functions and nothing else to get from tickets to units.
+struct TkMap
+{
+    uint32_t upt_long; // units of a long ticket
+    uint32_t upt;      // units of a short one (>= 1)
+    uint64_t n_long;   // tickets [0, n_long) are long
+};
+struct TkSpan
+{
+    uint64_t first; // the ticket's first unit
+    uint32_t units; // ... and how many it holds (0, first = n_units: the ticket lies behind the text)
+};
+__host__ __device__ inline TkSpan tk_map(const TkMap m, const uint64_t n_units, const uint64_t t)
+{
+    const uint64_t u = t < m.n_long ? t * m.upt_long : m.n_long * m.upt_long + (t - m.n_long) * m.upt;
+    const uint32_t c = t < m.n_long ? m.upt_long : m.upt;
+    if (u >= n_units)
+        return TkSpan{n_units, 0u};
+    return TkSpan{u, n_units - u < (uint64_t)c ? (uint32_t)(n_units - u) : c};
+}
+__host__ __device__ inline uint64_t tk_map_tickets(const TkMap m, const uint64_t n_units)
+{
+    return m.n_long + (n_units - m.n_long * m.upt_long + m.upt - 1) / m.upt;
+}
+// How many long tickets a text of n_units gets when `waves` waves scan it.  The text ends with a region of short tickets; when the last
+// long ticket is drawn every other wave is somewhere inside a long ticket of its own, and that region is what keeps them busy until the
+// last one ends.  With equal speeds the worst case is a wave that draws the last long ticket just as all the others finish theirs: they
+// need one long-ticket time each, 1.0 x waves x upt_long units (uniformly spread phases would need half of that).  Waves do not run at
+// equal speeds (the scan moves by 2-3 % with placement alone, a wave that flushes records loses a round), so the region is 1.5 x that:
+// a last long ticket up to half a ticket time late still ends inside the short tickets.  A text that has no room for one long ticket per
+// wave in front of the region gets none: the one-size map.
+__host__ __device__ inline uint64_t tk_map_long_tickets(const uint64_t n_units, const uint32_t upt_long, const uint32_t upt, const uint64_t waves)
+{
+    if (upt_long <= upt || !waves)
+        return 0;
+    const uint64_t region = (3 * waves * upt_long + 1) / 2;
+    if (n_units < region)
+        return 0;
+    const uint64_t n_long = (n_units - region) / upt_long;
+    return n_long >= waves ? n_long : 0;
+}
+
 constexpr unsigned long long kTkReady = 1ull << 63;
 constexpr uint32_t kTkSpinLimit = 1u << 24;  // ~0.25 us per spin: seconds — only a logic error gets there (see the safety nets)
 constexpr uint32_t kTkResolveChunk = 8;      // tickets per resolver lane and pass (512 per pass)

@@ -176,6 +176,16 @@ class Engine:
             L.krep_gpu_debug_literal_dma_one_pass_failovers.restype = C.c_uint64
             L.krep_gpu_debug_force_literal_dma_grid.restype = None
             L.krep_gpu_debug_force_literal_dma_grid.argtypes = [C.c_int]
+        if hasattr(L, "krep_gpu_debug_force_literal_dma_tickets"):
+            L.krep_gpu_debug_force_literal_dma_tickets.restype = None
+            L.krep_gpu_debug_force_literal_dma_tickets.argtypes = [C.c_int, C.c_uint64]
+            L.krep_gpu_debug_literal_dma_last_tickets.restype = None
+            L.krep_gpu_debug_literal_dma_last_tickets.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+            L.krep_gpu_debug_ticket_map.restype = C.c_int
+            L.krep_gpu_debug_ticket_map.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+            L.krep_gpu_debug_ticket_map_long_tickets.restype = C.c_uint64
+            L.krep_gpu_debug_ticket_map_long_tickets.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]
         if hasattr(L, "krep_gpu_debug_force_regex_grid"):
             L.krep_gpu_debug_force_regex_grid.restype = None
             L.krep_gpu_debug_force_regex_grid.argtypes = [C.c_int]
@@ -296,6 +306,26 @@ class Engine:
 
     def force_literal_dma_grid(self, blocks: int):
         self.lib.krep_gpu_debug_force_literal_dma_grid(blocks)
+
+    def force_literal_dma_tickets(self, long_units: int, n_long: int = 0):
+        """the one-pass mode's ticket map forced: the first n_long tickets take long_units (8, 16, 32) units, the rest 8; 0 = the library's choice"""
+        self.lib.krep_gpu_debug_force_literal_dma_tickets(long_units, n_long)
+
+    def literal_dma_last_tickets(self):
+        """(units of a long ticket, number of long tickets) of the last one-pass launch; (8, 0): every ticket short"""
+        u, k = C.c_uint32(0), C.c_uint64(0)
+        self.lib.krep_gpu_debug_literal_dma_last_tickets(C.byref(u), C.byref(k))
+        return int(u.value), int(k.value)
+
+    def ticket_map(self, upt_long: int, upt: int, n_long: int, n_units: int, ticket: int):
+        """(first unit, units) of `ticket` and the number of tickets under the map {upt_long, upt, n_long} (kg_tickets.h); None: refused"""
+        f, c, k = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        if self.lib.krep_gpu_debug_ticket_map(upt_long, upt, n_long, n_units, ticket, C.byref(f), C.byref(c), C.byref(k)):
+            return None
+        return int(f.value), int(c.value), int(k.value)
+
+    def ticket_map_long_tickets(self, n_units: int, upt_long: int, upt: int, waves: int) -> int:
+        return int(self.lib.krep_gpu_debug_ticket_map_long_tickets(n_units, upt_long, upt, waves))
 
     def force_regex_grid(self, blocks: int):
         """at most `blocks` workgroups for the regex scan (0 = auto): every wave then takes several 32-KiB units"""
