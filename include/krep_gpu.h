@@ -404,6 +404,56 @@ typedef struct krep_gpu_regex_ext
 /* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
 int krep_gpu_regex_compile_ext(const search_params_t *params, krep_gpu_regex_ext_t *out);
 
+/* ---- *, + and {n,} behind an atom: ERROR.*timeout, [0-9]+\.[0-9]+, [a-z]+@[a-z]+\.com, colou*r, ^#+ ----
+ * Grammar: krep_gpu_regex_compile_ext()'s, with three more quantifiers behind an ATOM (at top level or inside a group's alternative):
+ *   quant = '?' | '{n}' | '{n,m}' | '*' | '+' | '{n,}'
+ *   A PLACE of a sequence is a byte class plus a flag "repeats": C+ is the place C that repeats, C{n,} is C n - 1 times and then C+, C*
+ *   and C{0,} are {nothing, C+}.  Everything else expands as in krep_gpu_regex_compile_ext(); two sequences are the same when their
+ *   classes and their flags are.  The limits are that compiler's: at most 8 sequences, at most 16 places each (^ and $ take one each),
+ *   at most 32 in all.
+ * Refused (2, each with its own reason): an unbounded quantifier behind a group ((ab)+, (a|b)*); any class of the program that holds
+ *   '\n' ([^a]+ does not, [[:space:]]+ does); an expansion that holds an empty sequence (a*, a*b*); an expression without any *, + or
+ *   {n,} (the older compilers keep what is theirs); and everything krep_gpu_regex_compile_ext() refuses for other reasons.
+ * The filter.  For a branch with places p0..p(L-1) a FACTOR is a run pa..pb in which no place strictly between a and b repeats (a
+ *   repeating place may stand at either end: it gives the one byte of its run that touches its neighbour).  Every text the branch
+ *   matches holds every factor as consecutive bytes.  Per branch the factor with the smallest product of |class| / 256 is taken, on
+ *   a tie the longer one, then the leftmost; identical factors merge.  `filter` is that unanchored alternation of at most 8 sequences of
+ *   at most 16 classes, which the fixed-length kernels scan: a+b gives ab, [0-9]+ gives [0-9], ERROR.*timeout expands into ERRORtimeout
+ *   and ERROR.+timeout and gives ERRORtimeout and .timeout.
+ * What a scan reproduces (regex_search under REG_NEWLINE, checked against the compiled reference with a brute-force model), per line.
+ *   The lines are [0, first '\n'), every stretch between two newlines and what stands behind the last newline, if that is not empty.
+ *   In a line [ls, le), with resume = ls:
+ *     a start s >= resume is tried in ascending order; with bol only s = ls;
+ *     a branch matches (s, e) when text[s, e) can be cut into non-empty runs, one per place and in order, each of bytes of its place's
+ *       class, of length 1 unless the place repeats, and e <= le;
+ *     with eol e must be le; when le is the end of the text and not a newline that holds only in a case-sensitive search (the
+ *       REG_NOTEOL quirk described above);
+ *     the match at s is (s, the largest such e over all branches); the first s that has one is emitted and resume moves to its e.
+ *   Records ascend in start.  -c counts the lines that hold a match.  max_count, its 0 corner and the empty text as above;
+ *   only_matching and reference_simd change nothing.
+ * Split: KREP_GPU_SPLIT_WHOLE.  A window that is not the whole text is refused (2).
+ * Long lines: a lane of the device walks one line, and its worst case is quadratic in the line's length (a.*b on a line of a's).  A
+ *   candidate line of more than 4096 bytes is not walked: the scan returns 2 ("a line of more than 4096 bytes") with nothing
+ *   written, and the operator takes the road of every run-time failure (the registered CPU function, or KREP_GPU_FAILED).
+ * The switch.  krep_gpu_regex_compile_loops() always works.  Whether a SEARCH asks it, last, after the three older compilers have
+ *   refused, is decided by krep_gpu_set_regex_loops(): process-wide, off unless $KREP_GPU_REGEX_LOOPS=1 is set when the library is
+ *   loaded.  Off, every call behaves and reports as if this compiler did not exist.  On, krep_gpu_can_accelerate(), the selector, the
+ *   plans, krep_gpu_regex_search, search_buffer and the batch calls take such a search; a search all four refuse reports what it
+ *   reported before, unless that was a "repeat without a bound" reason: then it is this compiler's. */
+typedef struct krep_gpu_regex_loops
+{
+    krep_gpu_regex_alt_t alt;    /* the expanded sequences over their real classes; L, Lmin, Lmax, total_L count PLACES, not bytes;
+                                    cross_overlap / self_overlap are those of the places read as single bytes: no scan uses them */
+    int bol;                     /* every top-level branch starts with an unescaped ^ */
+    int eol;                     /* every top-level branch ends with an unescaped $   */
+    uint16_t repeat[8];          /* bit j of repeat[i]: place j of alt.branch[i] repeats (C+) */
+    krep_gpu_regex_alt_t filter; /* the factors, each branch what krep_gpu_regex_compile() makes of that sequence alone */
+} krep_gpu_regex_loops_t;
+/* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
+int krep_gpu_regex_compile_loops(const search_params_t *params, krep_gpu_regex_loops_t *out);
+void krep_gpu_set_regex_loops(int on); /* process-wide; default 0, or $KREP_GPU_REGEX_LOOPS at load */
+int krep_gpu_get_regex_loops(void);
+
 /* The in-memory twin of search_file()/search_string() that BASELINE.json calls search_buffer():
  * validation as krep.c:2013-2049 (no patterns -> 2; empty pattern among several -> 2; pattern
  * longer than 1024 -> 2), algorithm selection as krep.c:2166, single-chunk semantics, clamp to

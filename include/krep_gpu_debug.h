@@ -76,6 +76,11 @@ uint64_t krep_gpu_debug_runs_launches(void);
 /* test hook of the regex scan (kg_regex.hip): at most `blocks` workgroups (0 = auto) — a starved grid, so that a wave takes a
  * second and third 32-KiB unit on a text of a few hundred KiB (its own grid does that only beyond 5 units per compute unit) */
 void krep_gpu_debug_force_regex_grid(int blocks);
+/* test hooks of the loops scan (kg_regex_loops.hip; its line walk's grid is capped by the hook above too): which road finds the
+ * candidate lines — 0 the scan's choice (the filter's occurrences per text byte), 1 the sparse road (the filter's records), 2 the dense
+ * road (every line, from the newline records); and how many scans took each road since the process started */
+void krep_gpu_debug_force_regex_loops_road(int road);
+void krep_gpu_debug_regex_loops_roads(uint64_t *sparse, uint64_t *dense);
 /* a multi-pattern plan whose dictionary holds 1..3-byte patterns beside >= 8 longer ones: 0 not decided yet, 1 scanned as one dictionary, 2 split
  * (the long part anchored, the short part on its own, the record lists merged: kg_scan_ac.hip scan_ac_split); $KREP_GPU_AC_NO_SPLIT=1: never */
 int krep_gpu_debug_split_state(const krep_gpu_plan_t *plan);

@@ -157,6 +157,12 @@ class RegexExt(C.Structure):
     _fields_ = [("alt", RegexAlt), ("bol", C.c_int), ("eol", C.c_int)]
 
 
+class RegexLoops(C.Structure):
+    """krep_gpu_regex_loops_t: what krep_gpu_regex_compile_loops() makes of an expression with *, + or {n,} behind an atom: the expanded
+    sequences of places (alt; L counts places), the line anchors, per branch the mask of the places that repeat, and the filter"""
+    _fields_ = [("alt", RegexAlt), ("bol", C.c_int), ("eol", C.c_int), ("repeat", C.c_uint16 * 8), ("filter", RegexAlt)]
+
+
 class ShardInfo(C.Structure):
     """krep_gpu_shard_info_t: where the calling thread's last sharded host search ran."""
     _fields_ = [("shards", C.c_int), ("devices_used", C.c_int), ("device_ids", C.c_int * 16), ("comm_ranks", C.c_int),

@@ -171,7 +171,9 @@ const char *batch_unsupported_reason(const search_params_t *p, const krep_gpu_co
         if (const char *why = regex_compile_cached(p, &rc))
             return why;
         bool nl = false;
-        if (rc.is_alt)
+        if (rc.is_loops)
+            ; // (the loops compiler refuses a class that holds '\n', and its one-window rule is no reason against a pack: a pack is one window)
+        else if (rc.is_alt)
             for (uint32_t b = 0; b < rc.alt.n_branches; ++b)
                 for (uint32_t j = 0; j < rc.alt.branch[b].L; ++j)
                     nl = nl || holds_newline(rc.alt.branch[b].classes[j]);
@@ -180,7 +182,7 @@ const char *batch_unsupported_reason(const search_params_t *p, const krep_gpu_co
                 nl = nl || holds_newline(rc.seq.seq.classes[j]);
         if (nl)
             return "batch: a byte class of the expression holds '\\n': a match could take in the separator between two items";
-        if ((rc.is_alt ? rc.alt_eol : rc.seq.eol) && !p->case_sensitive)
+        if ((rc.is_loops ? rc.loops.eol : rc.is_alt ? rc.alt_eol : rc.seq.eol) && !p->case_sensitive)
             return "batch: $ in a case-insensitive search: the end of the text ends no line there (REG_NOTEOL, krep.c:1420), which holds "
                    "at the end of every item alone and in a pack only at the end of the last";
         return nullptr;

@@ -248,6 +248,26 @@ std::atomic<int> g_rx_force_grid{0};   // test hook: workgroups of the regex sca
 extern "C" void krep_gpu_debug_force_stage_cap(int c) { g_force_stage_cap.store(c); }
 extern "C" void krep_gpu_debug_force_rounds(int r) { g_force_rounds.store(r); }
 extern "C" void krep_gpu_debug_force_regex_grid(int blocks) { g_rx_force_grid.store(blocks < 0 ? 0 : blocks); }
+// The loops compiler behind a switch (include/krep_gpu.h, krep_gpu_regex_compile_loops): process-wide like the setters above, but not a
+// field of krep_gpu_config_t — it is off by default and on for a whole process or not at all.
+static int env_regex_loops()
+{
+    const char *e = getenv("KREP_GPU_REGEX_LOOPS");
+    return e && *e && atoi(e) != 0 ? 1 : 0;
+}
+namespace kg {
+std::atomic<int> g_regex_loops{env_regex_loops()}; // (read when the library is loaded)
+std::atomic<int> g_rl_force_road{0};               // test hook: 0 auto, 1 the sparse road, 2 the dense road (kg_regex_loops.hip)
+std::atomic<uint64_t> g_rl_sparse{0}, g_rl_dense{0}; // scans that took each road
+}
+extern "C" void krep_gpu_set_regex_loops(int on) { kg::g_regex_loops.store(on != 0, std::memory_order_relaxed); }
+extern "C" int krep_gpu_get_regex_loops(void) { return kg::g_regex_loops.load(std::memory_order_relaxed); }
+extern "C" void krep_gpu_debug_force_regex_loops_road(int road) { kg::g_rl_force_road.store(road == 1 || road == 2 ? road : 0); }
+extern "C" void krep_gpu_debug_regex_loops_roads(uint64_t *sparse, uint64_t *dense)
+{
+    if (sparse) *sparse = kg::g_rl_sparse.load();
+    if (dense) *dense = kg::g_rl_dense.load();
+}
 namespace kg {
 extern int g_s1_force_grid;
 std::atomic<uint64_t> g_fused1_failovers{0}; // one-pass single-byte scans that handed over to the two-pass kernels

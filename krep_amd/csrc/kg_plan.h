@@ -38,6 +38,7 @@ struct krep_gpu_plan
     kg::AcTables *ac = nullptr;
     // regex (KREP_RA_REGEX): the compiled class sequence, or alternation of them, and its device table (kg_regex.hip, kg_regex_alt.hip)
     kg::RegexProg *rx = nullptr;
+    uint64_t rx_emit_limit = 0; // an inner plan of the loops scan (kg_regex_loops.hip): more occurrences than this get no records (0: no limit)
     // a dictionary with 1..3-byte patterns beside many longer ones, on a text where the longer ones gain from anchors (kg_scan_ac.hip
     // scan_ac_split, round 6): the two parts as dictionaries of their own, scanned one after the other, their record lists merged
     kg::AcTables *ac_long = nullptr, *ac_short = nullptr;
@@ -100,6 +101,7 @@ int scan_ac(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_
 // kg_regex.hip: the program of an accepted -E pattern (NULL: refused or out of memory, the reason in krep_gpu_last_error()), and
 // the regex scan of a window
 RegexProg *regex_prog_create(const search_params_t &sp);
+RegexProg *regex_prog_create_alt(const krep_gpu_regex_alt_t &alt); // ... of an unanchored alternation no search names (a loops program's filter)
 void regex_prog_free(RegexProg *rx);
 int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
                const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out);

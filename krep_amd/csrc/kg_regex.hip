@@ -225,6 +225,49 @@ static hipError_t rx_run(const RxArgs &a, int mode, int num_cu, hipStream_t st)
 }
 
 // ------------------------------------------------------------------------------------------------ plan side
+// The table of an alternation: branch i in bits [o_i, o_i + Lx_i), Lx_i = L_i + bol + eol places: the class { '\n' } in front of and / or
+// behind its classes when the branches stand between line anchors (kg_regex_alt.hip); rx->init and rx->fin with it
+static void rx_alt_table(RegexProg *rx, const krep_gpu_regex_alt_t &alt, u32 bol, u32 eol, u32 table[256])
+{
+    memset(table, 0, 256 * sizeof(u32));
+    u32 o = 0;
+    for (u32 i = 0; i < alt.n_branches; ++i)
+    {
+        const krep_gpu_regex_info_t &br = alt.branch[i];
+        const u32 Lx = br.L + bol + eol;
+        rx->init |= 1u << o;
+        rx->fin |= 1u << (o + Lx - 1);
+        for (int b = 0; b < 256; ++b)
+            for (u32 j = 0; j < br.L; ++j)
+                table[b] |= ((br.classes[j][b >> 3] >> (b & 7)) & 1u) << (o + bol + j);
+        if (bol)
+            table['\n'] |= 1u << o;
+        if (eol)
+            table['\n'] |= 1u << (o + Lx - 1);
+        o += Lx;
+    }
+}
+static RegexProg *rx_upload(RegexProg *rx, const u32 table[256])
+{
+    if (hipMalloc(&rx->d_table, 256 * sizeof(u32)) != hipSuccess ||
+        hipMemcpy(rx->d_table, table, 256 * sizeof(u32), hipMemcpyHostToDevice) != hipSuccess)
+    {
+        fail("regex plan: device allocation failed");
+        regex_prog_free(rx);
+        return nullptr;
+    }
+    return rx;
+}
+// the program of an unanchored alternation that no search names: the filter of a loops program (kg_regex_loops.hip)
+RegexProg *regex_prog_create_alt(const krep_gpu_regex_alt_t &alt)
+{
+    auto *rx = new RegexProg();
+    u32 table[256];
+    rx->is_alt = true;
+    rx->alt = alt;
+    rx_alt_table(rx, alt, 0, 0, table);
+    return rx_upload(rx, table);
+}
 RegexProg *regex_prog_create(const search_params_t &sp)
 {
     auto *rx = new RegexProg();
@@ -236,30 +279,26 @@ RegexProg *regex_prog_create(const search_params_t &sp)
         return nullptr;
     }
     u32 table[256];
-    if (rc.is_alt)
-    { // an alternation: branch i in bits [o_i, o_i + Lx_i), Lx_i = L_i + bol + eol places: the class { '\n' } in front of and / or behind
-      // its classes when the branches stand between line anchors (kg_regex_alt.hip)
+    if (rc.is_loops)
+    { // places that may repeat (kg_regex_loops.hip): the alternation's layout without anchor places — ^ and $ are the line walk's own —
+      // and `plus`, the bits of the places that repeat
+        rx->is_loops = true;
+        rx->loops = rc.loops;
+        rx_alt_table(rx, rc.loops.alt, 0, 0, table);
+        u32 o = 0;
+        for (u32 i = 0; i < rc.loops.alt.n_branches; ++i)
+        {
+            rx->plus |= (u32)rc.loops.repeat[i] << o;
+            o += rc.loops.alt.branch[i].L;
+        }
+    }
+    else if (rc.is_alt)
+    {
         rx->is_alt = true;
         rx->alt = rc.alt;
         rx->alt_bol = rc.alt_bol ? 1u : 0u;
         rx->alt_eol = rc.alt_eol ? 1u : 0u;
-        memset(table, 0, sizeof table);
-        u32 o = 0;
-        for (u32 i = 0; i < rc.alt.n_branches; ++i)
-        {
-            const krep_gpu_regex_info_t &br = rc.alt.branch[i];
-            const u32 Lx = br.L + rx->alt_bol + rx->alt_eol;
-            rx->init |= 1u << o;
-            rx->fin |= 1u << (o + Lx - 1);
-            for (int b = 0; b < 256; ++b)
-                for (u32 j = 0; j < br.L; ++j)
-                    table[b] |= ((br.classes[j][b >> 3] >> (b & 7)) & 1u) << (o + rx->alt_bol + j);
-            if (rx->alt_bol)
-                table['\n'] |= 1u << o;
-            if (rx->alt_eol)
-                table['\n'] |= 1u << (o + Lx - 1);
-            o += Lx;
-        }
+        rx_alt_table(rx, rc.alt, rx->alt_bol, rx->alt_eol, table);
     }
     else
     {
@@ -275,19 +314,13 @@ RegexProg *regex_prog_create(const search_params_t &sp)
         }
         table['\n'] |= bol | (eol << (bol + seq.L));
     }
-    if (hipMalloc(&rx->d_table, sizeof table) != hipSuccess ||
-        hipMemcpy(rx->d_table, table, sizeof table, hipMemcpyHostToDevice) != hipSuccess)
-    {
-        fail("regex plan: device allocation failed");
-        regex_prog_free(rx);
-        return nullptr;
-    }
-    return rx;
+    return rx_upload(rx, table);
 }
 void regex_prog_free(RegexProg *rx)
 {
     if (!rx)
         return;
+    rx_loops_work_free(rx->work);
     if (rx->d_table) (void)hipFree(rx->d_table);
     delete rx;
 }
@@ -345,6 +378,16 @@ int rx_drive(krep_gpu_plan *pl, const Window &w, const RxSpec &sp, const RxWindo
     }
     HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
     HIPCHK(launch(lines ? kRxLines : kRxCount));
+    if (pl->rx_emit_limit)
+    { // an inner scan of kg_regex_loops.hip: a text that holds more occurrences than its caller has room for gets the number alone
+        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (pl->h_ctr->total > pl->rx_emit_limit)
+        {
+            out->total_matches = pl->h_ctr->total;
+            return 0;
+        }
+    }
     if (chain && post_offsets_pass(post, n_units, lines, pl->d_ctr, st))
         return 2;
     uint64_t total = 0, nlines = 0;
@@ -387,6 +430,12 @@ int rx_drive(krep_gpu_plan *pl, const Window &w, const RxSpec &sp, const RxWindo
     }
     if (time_it && stop_clock(pl, true, st, out))
         return 2;
+    rx_fill_out(pl, lines, total, nlines, summary, d_pos, cap, want, out);
+    return 0;
+}
+void rx_fill_out(const krep_gpu_plan *pl, bool lines, uint64_t total, uint64_t nlines, unsigned long long summary, const match_position_t *d_pos,
+                 uint64_t cap, uint64_t want, krep_gpu_scan_out_t *out)
+{
     out->total_matches = total;
     out->line_count = nlines;
     out->has_newline = (summary & kLnNl) != 0;
@@ -409,7 +458,6 @@ int rx_drive(krep_gpu_plan *pl, const Window &w, const RxSpec &sp, const RxWindo
         out->overflow = store > cap;
         out->stored = std::min<uint64_t>(store, std::min<uint64_t>(total, want));
     }
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ the scan of a window
@@ -421,6 +469,8 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
         *carry_out = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
     if (!pl->rx)
         return fail("scan_device: the regex plan holds no program");
+    if (pl->rx->is_loops)
+        return scan_regex_loops(pl, w, d_pos, cap, st, time_it, out);
     if (pl->rx->is_alt)
         return scan_regex_alt(pl, w, d_pos, cap, st, time_it, out);
     const krep_gpu_regex_info_t &info = pl->rx->info.seq;

@@ -11,7 +11,9 @@
 //     every branch to that tokeniser;
 //   krep_gpu_regex_compile_ext: EXPANDS ?, {n,m} and inner groups into such an alternation and takes a ^ in front of and a $ behind
 //     every top-level branch, the same pair on all of them;
-//   regex_compile_search: the three of them that take a search, in the order every search asks them, and the reason it reports.
+//   krep_gpu_regex_compile_loops: the expanding compiler's walk with *, + and {n,} behind an atom taken too: a place of a sequence may
+//     REPEAT (C+).  It also picks the filter, the fixed-length factors the older kernels find the candidate lines with;
+//   regex_compile_search: those that take a search, in the order every search asks them, and the reason it reports.
 // Each compiler reports the first fault IT meets, and they meet faults in different orders (the tokeniser probes atoms only after
 // the whole pattern is cut, the expanding compiler as it goes, the alternation compiler walks a branch's parentheses before it
 // tokenises the branch): the refusal strings are public, so the shared rules sit under four control flows.
@@ -187,12 +189,16 @@ inline bool regex_branches_overlap_anchored(const krep_gpu_regex_info_t &bi, con
         return false;
     return true;
 }
-// q among the *n distinct sequences of `set` (room for 8; only L and classes are compared): identical class tables merge.
+// While a compiler expands an expression, a sequence keeps the 16-bit mask of its places that REPEAT (C+, the loops compiler) in its
+// `anchor` field, which means nothing until regex_seq_finish() sets it: 0 in every sequence of the older compilers.
+inline uint32_t &regex_seq_plus(krep_gpu_regex_info_t &q) { return q.anchor; }
+inline uint32_t regex_seq_plus(const krep_gpu_regex_info_t &q) { return q.anchor; }
+// q among the *n distinct sequences of `set` (room for 8; L, the classes and the repeat mask are compared): identical ones merge.
 // false: it would be the ninth.
 inline bool regex_branch_add(krep_gpu_regex_info_t *set, uint32_t *n, const krep_gpu_regex_info_t &q)
 {
     for (uint32_t i = 0; i < *n; ++i)
-        if (set[i].L == q.L && memcmp(set[i].classes, q.classes, (size_t)q.L * 32) == 0)
+        if (set[i].L == q.L && regex_seq_plus(set[i]) == regex_seq_plus(q) && memcmp(set[i].classes, q.classes, (size_t)q.L * 32) == 0)
             return true;
     if (*n >= kRegexMaxBranches)
         return false;
@@ -533,6 +539,7 @@ inline const char *regex_set_cat(const RegexSeqSet &A, const RegexSeqSet &B, Reg
             if (A.s[i].L + B.s[j].L > kRegexMaxL)
                 return kRegexExtTooLong;
             krep_gpu_regex_info_t q = A.s[i];
+            regex_seq_plus(q) |= regex_seq_plus(B.s[j]) << A.s[i].L;
             for (uint32_t t = 0; t < B.s[j].L; ++t)
                 memcpy(q.classes[q.L++], B.s[j].classes[t], 32);
             if (!regex_branch_add(C.s, &C.n, q))
@@ -573,16 +580,29 @@ struct RegexExtCursor
     const uint8_t *pat;
     size_t n, i;
     bool case_sensitive;
+    bool loops = false;     // the loops compiler: *, + and {n,} behind an atom are taken
+    bool unbounded = false; // ... and one of them has been met
 };
-// an optional quantifier at the cursor, applied to A
-inline const char *regex_ext_quant(RegexExtCursor &c, RegexSeqSet &A)
+constexpr const char *kRegexStarPlus = "regex: * and + repeat without a bound, which needs an unbounded state: kept on krep's regex_search";
+constexpr const char *kRegexOpenCount = "regex: {n,} repeats without a bound, which needs an unbounded state: kept on krep's regex_search";
+constexpr const char *kRegexLoopsGroup = "regex loops: *, + or {n,} behind a group ((ab)+, (a|b)*) loops over a sub-sequence, not over one byte class: kept on "
+                                         "krep's regex_search";
+// an optional quantifier at the cursor, applied to A (atom: A is one atom's single place, else a group's alternatives)
+inline const char *regex_ext_quant(RegexExtCursor &c, RegexSeqSet &A, bool atom)
 {
     if (c.i >= c.n || !regex_is_quant(c.pat[c.i]))
         return nullptr;
     uint32_t lo = 0, hi = 1;
+    bool unbounded = false;
     if (c.pat[c.i] == '*' || c.pat[c.i] == '+')
-        return "regex: * and + repeat without a bound, which needs an unbounded state: kept on krep's regex_search";
-    if (c.pat[c.i] == '?')
+    {
+        if (!c.loops)
+            return kRegexStarPlus;
+        lo = c.pat[c.i] == '+' ? 1u : 0u;
+        unbounded = true;
+        ++c.i;
+    }
+    else if (c.pat[c.i] == '?')
         ++c.i;
     else
     {
@@ -594,8 +614,13 @@ inline const char *regex_ext_quant(RegexExtCursor &c, RegexSeqSet &A)
         {
             ++k;
             if (k < c.n && c.pat[k] == '}')
-                return "regex: {n,} repeats without a bound, which needs an unbounded state: kept on krep's regex_search";
-            if (!regex_count(c.pat, c.n, &k, &hi))
+            {
+                if (!c.loops)
+                    return kRegexOpenCount;
+                unbounded = true;
+                hi = lo > 1 ? lo : 1;
+            }
+            else if (!regex_count(c.pat, c.n, &k, &hi))
                 return kRegexMalformed;
         }
         if (c.pat[k] != '}' || lo > hi || hi > 1000)
@@ -606,7 +631,25 @@ inline const char *regex_ext_quant(RegexExtCursor &c, RegexSeqSet &A)
     }
     if (c.i < c.n && regex_is_quant(c.pat[c.i]))
         return "regex: a quantifier behind a quantifier (a?{2}, a{2}{3}, a?+): kept on krep's regex_search";
-    return regex_set_repeat(A, lo, hi);
+    if (!unbounded)
+        return regex_set_repeat(A, lo, hi);
+    // C+ is the place C that repeats; C{n,} is C n - 1 times and then C+; C* and C{0,} are nothing, or C+
+    if (!atom)
+        return kRegexLoopsGroup;
+    c.unbounded = true;
+    RegexSeqSet plus = A, T;
+    regex_seq_plus(plus.s[0]) = 1u;
+    if (lo == 0)
+    {
+        regex_set_empty_seq(A);
+        return regex_set_union(A, plus);
+    }
+    if (const char *why = regex_set_repeat(A, lo - 1, lo - 1))
+        return why;
+    if (const char *why = regex_set_cat(A, plus, T))
+        return why;
+    A = T;
+    return nullptr;
 }
 // one atom at the cursor with its optional quantifier: its alternatives into A
 inline const char *regex_ext_atom(RegexExtCursor &c, RegexSeqSet &A)
@@ -619,7 +662,7 @@ inline const char *regex_ext_atom(RegexExtCursor &c, RegexSeqSet &A)
         return kRegexAtomRefused;
     A.s[0].L = 1;
     c.i += len;
-    return regex_ext_quant(c, A);
+    return regex_ext_quant(c, A, true);
 }
 // a group, the cursor behind its '(': '(' seq ('|' seq)* ')' quant?, seq = (atom quant?)+
 inline const char *regex_ext_group(RegexExtCursor &c, RegexSeqSet &G)
@@ -648,7 +691,7 @@ inline const char *regex_ext_group(RegexExtCursor &c, RegexSeqSet &G)
             any = false;
             ++c.i;
             if (ch == ')')
-                return regex_ext_quant(c, G);
+                return regex_ext_quant(c, G, false);
             continue;
         }
         if (regex_is_quant(ch))
@@ -710,7 +753,9 @@ inline const char *regex_ext_branch(RegexExtCursor &c, RegexSeqSet &S, int *bol,
             return kRegexExtEmpty;
     return nullptr;
 }
-inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu_regex_ext_t *out)
+// loops: *, + and {n,} behind an atom are taken too (the loops compiler); plus[b]: the repeat mask of branch b, *unbounded: one was met
+inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu_regex_ext_t *out, bool loops = false, uint32_t *plus = nullptr,
+                                              bool *unbounded = nullptr)
 {
     if (const char *why = regex_check_search(p, true))
         return why;
@@ -719,7 +764,7 @@ inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu
     bool first = true;
     for (size_t k = 0; k < n_pat; ++k)
     {
-        RegexExtCursor c{nullptr, 0, 0, p->case_sensitive};
+        RegexExtCursor c{nullptr, 0, 0, p->case_sensitive, loops};
         regex_pattern_at(p, k, &c.pat, &c.n);
         if (const char *why = regex_check_pattern(c.pat, c.n))
             return why;
@@ -746,12 +791,17 @@ inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu
             if (c.i >= c.n)
                 return kRegexAltEmptyBranch;
         }
+        if (unbounded)
+            *unbounded = *unbounded || c.unbounded;
     }
     const uint32_t extra = (uint32_t)(out->bol + out->eol);
     for (uint32_t b = 0; b < alt.n_branches; ++b)
     {
         if (alt.branch[b].L + extra > kRegexMaxL)
             return kRegexExtTooLong;
+        if (plus)
+            plus[b] = regex_seq_plus(alt.branch[b]);
+        regex_seq_plus(alt.branch[b]) = 0;
         regex_seq_finish(&alt.branch[b], false, false); // (each branch what krep_gpu_regex_compile() makes of it alone)
     }
     regex_alt_finish(&alt, out->bol != 0, out->eol != 0);
@@ -771,16 +821,99 @@ inline const char *regex_compile_ext(const search_params_t *p, krep_gpu_regex_ex
     return why;
 }
 
+// ---- krep_gpu_regex_compile_loops: *, + and {n,} behind an atom, expanded into sequences of places that may repeat ------------------
+constexpr const char *kRegexLoopsEmpty = "regex loops: one of the expanded sequences holds no place (a*, a*b*, (a|b*)): it matches the empty string: kept on "
+                                         "krep's regex_search";
+constexpr const char *kRegexLoopsNewline = "regex loops: a byte class of the expression holds '\\n', so a match can cross a line end and the lines of the text "
+                                           "are no longer independent: kept on krep's regex_search";
+constexpr const char *kRegexLoopsNone = "regex loops: the expression holds no *, + or {n,}: it is the older compilers' (krep_gpu_regex_compile_anchored, _alt, "
+                                        "_ext)";
+// the bytes of a class
+inline uint32_t regex_class_size(const uint8_t cls[32])
+{
+    uint32_t s = 0;
+    for (int w = 0; w < 32; ++w)
+        s += (uint32_t)__builtin_popcount(cls[w]);
+    return s;
+}
+// The filter of a compiled program: per branch the factor (a run of places none of which, strictly inside it, repeats) whose classes
+// have the smallest product of |class| / 256; on a tie the longer, then the leftmost; identical factors merge.
+inline void regex_loops_filter(krep_gpu_regex_loops_t *out)
+{
+    for (uint32_t i = 0; i < out->alt.n_branches; ++i)
+    {
+        const krep_gpu_regex_info_t &br = out->alt.branch[i];
+        const uint32_t plus = out->repeat[i];
+        uint32_t best_a = 0, best_len = 0;
+        unsigned __int128 best = 0;
+        for (uint32_t a = 0; a < br.L; ++a)
+        {
+            unsigned __int128 prod = 1;
+            for (uint32_t b = a; b < br.L; ++b)
+            {
+                // (no class holds '\n': every |class| <= 255, so the product of len of them stays below 256^len <= 2^128)
+                prod *= regex_class_size(br.classes[b]);
+                const uint32_t len = b - a + 1;
+                const unsigned __int128 v = prod << (8u * (kRegexMaxL - len)); // the product over 256^len, times 256^16
+                if (!best_len || v < best || (v == best && len > best_len))
+                {
+                    best = v;
+                    best_a = a;
+                    best_len = len;
+                }
+                if (b > a && ((plus >> b) & 1u))
+                    break; // a repeating place ends the run: it may stand at an end of a factor, never inside
+            }
+        }
+        krep_gpu_regex_info_t q{};
+        q.L = best_len;
+        memcpy(q.classes, br.classes[best_a], (size_t)best_len * 32);
+        (void)regex_branch_add(out->filter.branch, &out->filter.n_branches, q); // (at most one per branch: never a ninth)
+    }
+    for (uint32_t b = 0; b < out->filter.n_branches; ++b)
+        regex_seq_finish(&out->filter.branch[b], false, false);
+    regex_alt_finish(&out->filter, false, false);
+}
+// krep_gpu_regex_compile_loops: NULL and *out filled, or the refusal and *out zeroed
+inline const char *regex_compile_loops(const search_params_t *p, krep_gpu_regex_loops_t *out)
+{
+    if (!p || !out)
+        return "NULL params";
+    memset(out, 0, sizeof *out);
+    krep_gpu_regex_ext_t ext;
+    memset(&ext, 0, sizeof ext);
+    uint32_t plus[kRegexMaxBranches] = {0};
+    bool unbounded = false;
+    if (const char *why = regex_compile_ext_branches(p, &ext, true, plus, &unbounded))
+        return why == kRegexExtEmpty ? kRegexLoopsEmpty : why;
+    if (!unbounded)
+        return kRegexLoopsNone;
+    for (uint32_t b = 0; b < ext.alt.n_branches; ++b)
+        for (uint32_t j = 0; j < ext.alt.branch[b].L; ++j)
+            if (regex_class_holds_nl(ext.alt.branch[b].classes[j]))
+                return kRegexLoopsNewline;
+    out->alt = ext.alt;
+    out->bol = ext.bol;
+    out->eol = ext.eol;
+    for (uint32_t b = 0; b < ext.alt.n_branches; ++b)
+        out->repeat[b] = (uint16_t)plus[b];
+    regex_loops_filter(out);
+    return nullptr;
+}
+
 // ---- the compilers in the order every search asks them -------------------------------------------------------------------------
 // The anchored compiler is asked first; only what it refuses goes to the alternation compiler, and what both refuse to the expanding
 // compiler, whose result is an alternation too, between the line anchors alt_bol / alt_eol (is_alt: one of the two took it).  So a
-// search an earlier compiler takes runs the kernel it always ran.
+// search an earlier compiler takes runs the kernel it always ran.  What all three refuse goes to the loops compiler when the caller
+// says so (krep_gpu_set_regex_loops): is_loops, the program in `loops`.
 struct RegexCompiled
 {
     bool is_alt = false;
     krep_gpu_regex_anchored_t seq{}; // !is_alt
     krep_gpu_regex_alt_t alt{};      // is_alt
     int alt_bol = 0, alt_eol = 0;    // is_alt: ^ in front of / $ behind every branch (the expanding compiler only)
+    bool is_loops = false;           // the loops compiler took it (then !is_alt, and seq holds nothing)
+    krep_gpu_regex_loops_t loops{};
 };
 // a refusal of the two older compilers that is a limit of theirs: one the expanding compiler's own limits do not replace
 inline bool regex_older_limit(const char *why)
@@ -790,9 +923,11 @@ inline bool regex_older_limit(const char *why)
 }
 // NULL: taken.  Else the reason of a search all three refuse: what it was before the expanding compiler — the alternation compiler's
 // when the search says an alternation, else the anchored compiler's — unless only the expanding compiler's own limits are in the way.
-inline const char *regex_compile_search(const search_params_t *p, RegexCompiled *out)
+// loops: the loops compiler is asked last.  Its own reason replaces the earlier one only where that one says "without a bound".
+inline const char *regex_compile_search(const search_params_t *p, RegexCompiled *out, bool loops = false)
 {
     out->is_alt = false;
+    out->is_loops = false;
     out->alt_bol = out->alt_eol = 0;
     const char *why = regex_compile_anchored(p, &out->seq);
     if (!why)
@@ -816,7 +951,16 @@ inline const char *regex_compile_search(const search_params_t *p, RegexCompiled 
         return nullptr;
     }
     const char *before = regex_has_alt_syntax(p) ? why_alt : why;
-    return regex_ext_own_limit(why_ext) && !regex_older_limit(before) ? why_ext : before;
+    const char *today = regex_ext_own_limit(why_ext) && !regex_older_limit(before) ? why_ext : before;
+    if (!loops)
+        return today;
+    const char *why_loops = regex_compile_loops(p, &out->loops);
+    if (!why_loops)
+    {
+        out->is_loops = true;
+        return nullptr;
+    }
+    return today == kRegexStarPlus || today == kRegexOpenCount ? why_loops : today;
 }
 
 } // namespace kg

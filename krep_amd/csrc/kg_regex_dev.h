@@ -30,7 +30,15 @@ struct RegexProg
     krep_gpu_regex_alt_t alt{};
     u32 alt_bol = 0, alt_eol = 0;
     u32 init = 0, fin = 0;
+    // places that may repeat (krep_gpu_regex_compile_loops took the search, kg_regex_loops.hip): the state is laid out like an
+    // alternation's over the places of loops.alt, without anchor places (^ and $ are the line walk's own); plus = the bits of the places
+    // that repeat.  work: the inner plans and the scratch of the scan, made by the plan's first scan
+    bool is_loops = false;
+    krep_gpu_regex_loops_t loops{};
+    u32 plus = 0;
+    struct RxLoopsWork *work = nullptr;
 };
+void rx_loops_work_free(RxLoopsWork *w); // kg_regex_loops.hip
 
 constexpr u32 kRxUnitBytes = kRoundsBig * kSegBytes; // 32 KiB of coordinates per wave unit
 
@@ -255,8 +263,15 @@ int rx_window(const krep_gpu_plan *pl, const Window &w, const match_position_t *
 // launch(mode): one of kRxCount / kRxEmit / kRxLines over n_units units, with what *o holds at that moment
 int rx_drive(krep_gpu_plan *pl, const Window &w, const RxSpec &sp, const RxWindow &g, match_position_t *d_pos, uint64_t cap, hipStream_t st,
              int time_it, RxOut *o, u64 n_units, const std::function<hipError_t(int)> &launch, krep_gpu_scan_out_t *out);
+// the result of one window from its totals, as every -E scan reports it: the line bits of `summary`, count under max_count and its 0
+// corner, stored / overflow for a caller that takes `want` of the records
+void rx_fill_out(const krep_gpu_plan *pl, bool lines, uint64_t total, uint64_t nlines, unsigned long long summary, const match_position_t *d_pos,
+                 uint64_t cap, uint64_t want, krep_gpu_scan_out_t *out);
 
 // kg_regex_alt.hip: the scan of a window for an alternation (scan_regex hands over when the program is one)
 int scan_regex_alt(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
                    krep_gpu_scan_out_t *out);
+// kg_regex_loops.hip: the scan of the whole text for places that may repeat (scan_regex hands over when the program is of that kind)
+int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
+                     krep_gpu_scan_out_t *out);
 } // namespace kg

@@ -1,0 +1,400 @@
+// kg_regex_loops.hip — krep -E with *, + and {n,} behind an atom (include/krep_gpu.h, krep_gpu_regex_compile_loops): ERROR.*timeout,
+// [0-9]+\.[0-9]+, colou*r, ^#+ .  The line walk kernel kg::rx_line_walk and the scan kg::scan_regex_loops; kg_regex.hip builds the
+// program's table and hands over when the plan's program is of this kind.
+//
+// Two properties carry the scan.  No class of such a program holds '\n', so under the reference's REG_NEWLINE a match lies inside one
+// line: the lines are independent, and the leftmost-longest walk of one line is a small sequential job.  And every match holds a
+// fixed-length factor of its branch as consecutive bytes (the program's FILTER), which the fixed-length kernels find at their rate.
+// Stage 1, the candidate lines, by one of two roads:
+//   sparse: the filter alternation is scanned over the text with records by scan_regex_alt / rx_drive (an inner plan); the line
+//     analysis of krep_gpu_matching_lines() turns the records into the distinct line spans that hold one.  The filter's classes hold no
+//     '\n' either, so every line with an occurrence holds the start of a record, whatever the greedy selection kept.
+//   dense: a filter like [a-z] would write 16 bytes of record per text byte.  When the filter's counting launch reports more than one
+//     occurrence per 64 text bytes its emitting launch is skipped (krep_gpu_plan::rx_emit_limit) and EVERY line is a candidate: the
+//     record list of an inner single-byte plan for '\n' (kg_single.hip) says where they are.
+// Stage 2, kg::rx_line_walk<LINES, EMIT>: one lane per candidate line, grid-stride.  Branch i lives in bits [o_i, o_i + L_i) of a 32-bit
+// state, T[byte] has bit o_i + j set when byte is in place j of branch i (in LDS once per bank, rx_fill_table), INIT holds every o_i,
+// FIN every o_i + L_i - 1, PLUS the places that repeat.  An attempt from s starts with S = INIT & T[text[s]] and steps
+// S = (((S << 1) & ~INIT) | (S & PLUS)) & T[b]: a place hands over to the next one, a repeating place also stays.  The last position
+// behind which S & FIN was non-zero is the longest match at s (with $ only the line's end counts; the end of the text ends a line in a
+// case-sensitive search only).  The attempt ends when S is 0 or at the line's end; a start whose byte is in no first place costs one
+// lookup.  The first start with a match is emitted and the walk resumes at its end (with ^ only the line's first byte is tried).
+// Passes: a counting launch writes every candidate line's match count (under -c one per line that holds a match, summed in the
+// kernel with the line bits), the offsets pass of kg_post.hip turns the counts into record indices, the emitting launch walks
+// again and writes each record at its final index, the first max_count only.
+// Bounded work: a lane's worst case is quadratic in its line's length (a.*b on a line of a's).  The counting launch does not walk a
+// candidate line of more than 4096 bytes and raises Counters::overflow_units; the host reads that first and refuses the scan (2)
+// with nothing written.
+// Reads: no byte outside [0, text_len), one byte at a time at any alignment: the walk of a lane per line is not coalesced, which is
+// the price of the dense road.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/krep_gpu.h"
+#include "kg_common.h"
+#include "kg_device.h"
+#include "kg_internal.h"
+#include "kg_plan.h"
+#include "kg_regex_dev.h"
+
+namespace kg {
+
+constexpr u32 kRlMaxLine = 4096; // bytes of the longest candidate line a lane walks
+
+struct RlArgs
+{
+    const uint8_t *text;
+    u64 text_len;
+    // the candidate lines.  from_nl == 0: line l is [spans[2l], spans[2l + 1]).  from_nl == 1: spans holds the n_lines - 1 newline
+    // records of the text in order, line l starts behind newline l - 1 (line 0 at 0) and ends on newline l (the last at text_len)
+    const u64 *spans;
+    u64 n_lines;
+    u64 global_base;
+    u32 from_nl;
+    u32 init, fin, plus;
+    u32 flags; // bit 0 ^, bit 1 $, bit 2: the end of the text ends a line ($ in a case-sensitive search)
+    const u32 *table;
+    RxOut o;   // unitinfo: the count of every candidate line; offsets: the index of its first record (kg_regex_dev.h)
+};
+
+// LINES: -c, a line is done with its first match and nothing is written per line; EMIT: the records at offsets[line]
+template <bool LINES, bool EMIT>
+__global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
+{
+    static_assert(!(LINES && EMIT), "-c writes no records");
+    __shared__ u32 s_T[256 * 32];
+    rx_fill_table(s_T, a.table);
+    const u32 *T = s_T + (lane_id() & 31u);
+    const bool bol = (a.flags & 1u) != 0u, eol = (a.flags & 2u) != 0u, eot_ends = (a.flags & 4u) != 0u;
+    const u64 n_threads = (u64)gridDim.x * kBlock;
+    u64 mine = 0;                 // matches (LINES: lines that hold one) of this lane's lines
+    unsigned long long bits = 0;  // LINES: kLnNl | kLnHead | kLnTail as far as this lane's lines say them
+    bool too_long = false;
+
+    for (u64 line = (u64)blockIdx.x * kBlock + threadIdx.x; line < a.n_lines; line += n_threads)
+    {
+        u64 ls, le;
+        if (a.from_nl)
+        {
+            ls = line ? a.spans[2 * (line - 1)] + 1u : 0u;
+            le = line + 1 < a.n_lines ? a.spans[2 * line] : a.text_len;
+        }
+        else
+        {
+            ls = a.spans[2 * line];
+            le = a.spans[2 * line + 1];
+        }
+        le = min(le, a.text_len); // (whatever a span says, no byte outside the text is read)
+        ls = min(ls, le);
+        u32 cnt = 0;
+        if (le - ls > kRlMaxLine)
+            too_long = true;
+        else if (!eol || le < a.text_len || eot_ends)
+        {
+            u64 idx = EMIT ? a.o.offsets[line] : 0;
+            u64 s = ls;
+            while (s < le)
+            {
+                u32 S = T[(u32)a.text[s] << 5] & a.init;
+                u64 best = 0; // the longest match at s ends here (0: none; a match is never empty)
+                if (S)
+                {
+                    u64 p = s + 1; // S: the state behind byte p - 1
+                    for (;;)
+                    {
+                        if ((S & a.fin) != 0u && (!eol || p == le))
+                            best = p;
+                        if (p >= le)
+                            break;
+                        S = (((S << 1) & ~a.init) | (S & a.plus)) & T[(u32)a.text[p] << 5];
+                        if (!S)
+                            break;
+                        ++p;
+                    }
+                }
+                if (best)
+                {
+                    if (EMIT)
+                    {
+                        if (idx < a.o.pos_cap)
+                            rx_store_record(a.o.positions, idx, s + a.global_base, best + a.global_base);
+                        ++idx;
+                    }
+                    ++cnt;
+                    if (LINES || bol)
+                        break;
+                    s = best;
+                }
+                else
+                {
+                    if (bol)
+                        break;
+                    ++s;
+                }
+            }
+        }
+        if (EMIT)
+            continue;
+        mine += cnt;
+        if (LINES)
+        {
+            if (ls > 0 || le < a.text_len)
+                bits |= kLnNl;
+            if (cnt)
+                bits |= (ls == 0 ? kLnHead : 0ull) | (le == a.text_len ? kLnTail : 0ull);
+        }
+        else
+            a.o.unitinfo[line] = cnt;
+    }
+    if (EMIT)
+        return;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        mine += __shfl_xor(mine, o);
+    if (lane_id() == 0 && mine)
+    {
+        atomicAdd(&a.o.ctr->total, (unsigned long long)mine);
+        if (LINES)
+            atomicAdd(&a.o.ctr->lines, (unsigned long long)mine);
+    }
+    if (LINES && bits)
+        atomicOr(&a.o.ctr->summary, bits);
+    if (too_long)
+        atomicOr(&a.o.ctr->overflow_units, 1ull);
+}
+
+static hipError_t rl_launch(const RlArgs &a, int mode, int num_cu, hipStream_t st)
+{
+    // one lane per line; 32 KiB of LDS each: five workgroups fit a CU
+    const u64 blocks = (a.n_lines + kBlock - 1) / kBlock;
+    u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 5u));
+    if (const int force = g_rx_force_grid.load(); force > 0) // test hook: a starved grid (krep_gpu_debug_force_regex_grid)
+        grid = std::min<u32>(grid, (u32)force);
+    if (mode == kRxLines)
+        hipLaunchKernelGGL((rx_line_walk<true, false>), dim3(grid), dim3(kBlock), 0, st, a);
+    else if (mode == kRxEmit)
+        hipLaunchKernelGGL((rx_line_walk<false, true>), dim3(grid), dim3(kBlock), 0, st, a);
+    else
+        hipLaunchKernelGGL((rx_line_walk<false, false>), dim3(grid), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ what a plan keeps between scans
+struct RxLoopsWork
+{
+    krep_gpu_plan *filter = nullptr;   // a plan whose program is the filter alternation (records, no -c, no max_count)
+    krep_gpu_plan *newlines = nullptr; // the single-byte plan for '\n' with records
+    match_position_t *d_rec = nullptr; // the filter's records, or the newline records
+    uint64_t rec_cap = 0;
+    match_position_t *d_spans = nullptr; // sparse road: the candidate lines and (krep_gpu_matching_lines wants it) their first records
+    uint64_t *d_first = nullptr;
+    uint64_t span_cap = 0;
+};
+void rx_loops_work_free(RxLoopsWork *w)
+{
+    if (!w)
+        return;
+    if (w->filter) krep_gpu_plan_destroy(w->filter);
+    if (w->newlines) krep_gpu_plan_destroy(w->newlines);
+    if (w->d_rec) (void)hipFree(w->d_rec);
+    if (w->d_spans) (void)hipFree(w->d_spans);
+    if (w->d_first) (void)hipFree(w->d_first);
+    delete w;
+}
+// the inner plans, on the outer plan's device and with its configuration
+static int rl_work_create(krep_gpu_plan *pl)
+{
+    auto *wk = new RxLoopsWork();
+    pl->rx->work = wk; // (freed with the program, whatever fails below)
+    auto *f = new krep_gpu_plan();
+    wk->filter = f;
+    f->cfg = pl->cfg;
+    f->device = pl->device;
+    f->cs = pl->cs;
+    f->track = true;
+    f->sp = search_params_t{};
+    f->sp.case_sensitive = pl->sp.case_sensitive;
+    f->sp.use_regex = true;
+    f->sp.track_positions = true;
+    f->sp.max_count = SIZE_MAX;
+    f->ref_algo = KREP_RA_REGEX;
+    f->num_cu = pl->num_cu;
+    HIPCHK(hipMalloc(&f->d_ctr, sizeof(Counters)));
+    HIPCHK(hipHostMalloc(&f->h_ctr, sizeof(Counters)));
+    HIPCHK(hipEventCreate(&f->ev0));
+    HIPCHK(hipEventCreate(&f->ev1));
+    f->rx = regex_prog_create_alt(pl->rx->loops.filter);
+    if (!f->rx)
+        return 2;
+    search_params_t nl{};
+    nl.pattern = "\n";
+    nl.pattern_len = 1;
+    nl.case_sensitive = true;
+    nl.track_positions = true;
+    nl.max_count = SIZE_MAX;
+    nl.num_patterns = 1;
+    wk->newlines = krep_gpu_plan_create_ex(&nl, &pl->cfg);
+    return wk->newlines ? 0 : 2;
+}
+static int rl_reserve_records(RxLoopsWork &wk, u64 need)
+{
+    HIPCHK(grow_scratch(wk.rec_cap, need, need, {dev_buf(wk.d_rec, need * sizeof(match_position_t))}));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the scan of the whole text
+int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
+                     krep_gpu_scan_out_t *out)
+{
+    RegexProg &rx = *pl->rx;
+    if (w.text_len == 0 || w.global_len == 0 || w.own_lo >= w.own_hi)
+        return 0; // (no match is empty: the zeroed *out is the answer)
+    if (!(w.global_base == 0 && w.own_lo == 0 && w.own_hi >= w.text_len && w.global_len == w.text_len))
+        return fail("a regex with *, + or {n,} is walked line by line from each line's first byte: scan the whole text in one window "
+                    "(krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
+    if (!rx.work && rl_work_create(pl))
+        return 2;
+    RxLoopsWork &wk = *rx.work;
+    const bool lines = pl->lines;
+    const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(pl->max_count, cap) : 0;
+    HIPCHK(hipSetDevice(pl->device));
+    if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
+
+    RlArgs a{};
+    a.text = w.d_text; a.text_len = w.text_len;
+    a.global_base = w.global_base;
+    a.init = rx.init; a.fin = rx.fin; a.plus = rx.plus;
+    a.flags = (rx.loops.bol ? 1u : 0u) | (rx.loops.eol ? 2u : 0u) | (pl->sp.case_sensitive ? 4u : 0u);
+    a.table = rx.d_table;
+    a.o.ctr = pl->d_ctr;
+
+    // ---- stage 1: the candidate lines
+    const int force = g_rl_force_road.load();
+    bool dense = force == 2;
+    bool has_newline = false, know_newline = false;
+    if (!dense)
+    {
+        // more than one occurrence per 64 text bytes (a first value, the bench tool runs both roads): the dense road
+        const u64 limit = force == 1 ? UINT64_MAX : w.text_len / 64;
+        for (;;)
+        {
+            if (rl_reserve_records(wk, std::max<u64>(wk.rec_cap, std::min<u64>(limit, w.text_len / 64) + 1)))
+                return 2;
+            krep_gpu_scan_out_t fo;
+            memset(&fo, 0, sizeof fo);
+            wk.filter->rx_emit_limit = std::min<u64>(limit, wk.rec_cap);
+            if (const int rc = scan_regex_alt(wk.filter, w, wk.d_rec, wk.rec_cap, st, 0, &fo))
+                return rc;
+            if (fo.total_matches <= wk.filter->rx_emit_limit)
+            {
+                a.n_lines = fo.stored;
+                break;
+            }
+            if (fo.total_matches > limit)
+            {
+                dense = true;
+                break;
+            }
+            if (rl_reserve_records(wk, fo.total_matches)) // (the forced sparse road on a text denser than the buffer was sized for)
+                return 2;
+        }
+    }
+    if (!dense)
+    {
+        g_rl_sparse.fetch_add(1, std::memory_order_relaxed);
+        if (a.n_lines)
+        {
+            const u64 n_rec = a.n_lines;
+            HIPCHK(grow_scratch(wk.span_cap, n_rec, n_rec,
+                                {dev_buf(wk.d_spans, n_rec * sizeof(match_position_t)), dev_buf(wk.d_first, (n_rec + 1) * sizeof(uint64_t))}));
+            krep_gpu_lines_out_t lo;
+            if (krep_gpu_matching_lines(w.d_text, w.text_len, wk.d_rec, n_rec, UINT64_MAX, wk.d_spans, wk.d_first, n_rec, &lo, st))
+                return 2;
+            a.n_lines = lo.lines;
+            a.spans = (const u64 *)wk.d_spans;
+        }
+    }
+    else
+    {
+        g_rl_dense.fetch_add(1, std::memory_order_relaxed);
+        krep_gpu_scan_out_t no;
+        for (;;)
+        {
+            if (krep_gpu_scan_device_ex(wk.newlines, w.d_text, w.text_len, 0, w.text_len, 0, w.text_len, wk.d_rec, wk.rec_cap, st, 0, &no))
+                return 2;
+            if (no.total_matches <= wk.rec_cap)
+                break;
+            if (rl_reserve_records(wk, no.total_matches))
+                return 2;
+        }
+        a.from_nl = 1;
+        a.spans = (const u64 *)wk.d_rec;
+        a.n_lines = no.total_matches + 1;
+        has_newline = no.total_matches != 0;
+        know_newline = true;
+    }
+
+    // ---- stage 2: the walk of the candidate lines
+    uint64_t total = 0, nlines = 0;
+    unsigned long long summary = 0;
+    if (a.n_lines)
+    {
+        if (!lines)
+        {
+            if (post_reserve(pl->post, a.n_lines, 0))
+                return 2;
+            a.o.unitinfo = pl->post.d_unitinfo;
+            a.o.offsets = (const u64 *)pl->post.d_offsets;
+        }
+        HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
+        HIPCHK(rl_launch(a, lines ? kRxLines : kRxCount, pl->num_cu, st));
+        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (pl->h_ctr->overflow_units)
+            return fail("regex with *, + or {n,}: a line of more than %u bytes: kept on krep's regex_search (a lane walks one line, and its "
+                        "worst case is quadratic in the line's length)", kRlMaxLine);
+        total = pl->h_ctr->total;
+        nlines = pl->h_ctr->lines;
+        summary = pl->h_ctr->summary;
+        if (want && total)
+        {
+            if (post_offsets_pass(pl->post, a.n_lines, false, pl->d_ctr, st))
+                return 2;
+            a.o.positions = (u64 *)d_pos;
+            a.o.pos_cap = want;
+            HIPCHK(rl_launch(a, kRxEmit, pl->num_cu, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
+    if (lines)
+    {
+        // has_newline as a scan of the whole window reports it: the candidate lines may not say (none, or one that is the whole text)
+        if (!know_newline && !(summary & kLnNl))
+        {
+            uint64_t pos = w.text_len;
+            if (tail_find_next_newline(w.d_text, 0, w.text_len, &pl->d_ctr->pad[0], &pl->h_ctr->pad[0], st, &pos))
+                return 2;
+            has_newline = pos < w.text_len;
+        }
+        summary = (summary & ~kLnNl) | ((has_newline || (summary & kLnNl)) ? kLnNl : 0ull);
+    }
+    else
+        summary = total ? (kLnHead | kLnTail) : 0;
+    if (time_it && stop_clock(pl, true, st, out))
+        return 2;
+    rx_fill_out(pl, lines, total, nlines, summary, d_pos, cap, want, out);
+    return 0;
+}
+} // namespace kg
+
+extern "C" int krep_gpu_regex_compile_loops(const search_params_t *params, krep_gpu_regex_loops_t *out)
+{
+    krep_gpu_clear_error();
+    if (const char *why = kg::regex_compile_loops(params, out))
+        return kg::fail("%s", why);
+    return 0;
+}

@@ -186,6 +186,17 @@ class Engine:
                                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
             L.krep_gpu_debug_ticket_map_long_tickets.restype = C.c_uint64
             L.krep_gpu_debug_ticket_map_long_tickets.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]
+        if hasattr(L, "krep_gpu_regex_compile_loops"):  # (likewise)
+            L.krep_gpu_regex_compile_loops.restype = C.c_int
+            L.krep_gpu_regex_compile_loops.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexLoops)]
+            L.krep_gpu_set_regex_loops.restype = None
+            L.krep_gpu_set_regex_loops.argtypes = [C.c_int]
+            L.krep_gpu_get_regex_loops.restype = C.c_int
+            L.krep_gpu_get_regex_loops.argtypes = []
+            L.krep_gpu_debug_force_regex_loops_road.restype = None
+            L.krep_gpu_debug_force_regex_loops_road.argtypes = [C.c_int]
+            L.krep_gpu_debug_regex_loops_roads.restype = None
+            L.krep_gpu_debug_regex_loops_roads.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         if hasattr(L, "krep_gpu_debug_force_regex_grid"):
             L.krep_gpu_debug_force_regex_grid.restype = None
             L.krep_gpu_debug_force_regex_grid.argtypes = [C.c_int]
@@ -396,6 +407,33 @@ class Engine:
         if self.lib.krep_gpu_regex_compile_ext(params.ref, C.byref(info)):
             raise KrepGpuError(self.last_error())
         return info
+
+    def regex_compile_loops(self, params: abi.Params) -> "abi.RegexLoops":
+        """krep_gpu_regex_compile_loops: the expanding compiler's grammar with *, + and {n,} behind an atom: sequences of places of which
+        some repeat (alt, repeat[i] the mask of branch i), the line anchors, and the filter (the fixed-length factors the candidate
+        lines are found with).  It always works; a search asks it, last, only after set_regex_loops(True)."""
+        info = abi.RegexLoops()
+        if self.lib.krep_gpu_regex_compile_loops(params.ref, C.byref(info)):
+            raise KrepGpuError(self.last_error())
+        return info
+
+    def set_regex_loops(self, on: bool):
+        """krep_gpu_set_regex_loops: whether a search asks the loops compiler after the three older ones have refused (process-wide,
+        off by default, $KREP_GPU_REGEX_LOOPS=1 at load)"""
+        self.lib.krep_gpu_set_regex_loops(1 if on else 0)
+
+    def get_regex_loops(self) -> bool:
+        return bool(self.lib.krep_gpu_get_regex_loops())
+
+    def force_regex_loops_road(self, road: int):
+        """which road the loops scan finds its candidate lines by: 0 its own choice, 1 sparse (the filter's records), 2 dense (all lines)"""
+        self.lib.krep_gpu_debug_force_regex_loops_road(int(road))
+
+    def regex_loops_roads(self):
+        """(sparse, dense): loops scans that took each road since the process started"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self.lib.krep_gpu_debug_regex_loops_roads(C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
 
     def can_accelerate(self, params: abi.Params) -> bool:
         return bool(self.lib.krep_gpu_can_accelerate(params.ref))
@@ -835,7 +873,8 @@ class Plan:
         and a per-item guess by.  A literal plan: its longest pattern.  A regex plan (krep -E): NOT the length of the pattern string
         (`q[a-c]{15}` is 10 pattern bytes and 16 text bytes) but L / Lmax of the compiler that takes the search, asked in the order
         every search asks them (anchored, then alternation, then the expanding one), plus the newline a `$` looks at behind the
-        match: a window must hold that byte too, or the scan refuses it."""
+        match: a window must hold that byte too, or the scan refuses it.  With set_regex_loops(True) a search the loops compiler takes
+        says 4097: a match lies inside one line, and no line of more than 4096 bytes is walked."""
         s = self.params.s
         if not s.use_regex:
             return max(int(x) for x in s.pattern_lens[: s.num_patterns]) if s.num_patterns else int(s.pattern_len)
@@ -848,8 +887,15 @@ class Plan:
         try:
             return int(eng.regex_compile_alt(self.params).Lmax)
         except KrepGpuError:
+            pass
+        try:
             info = eng.regex_compile_ext(self.params)
             return int(info.alt.Lmax) + int(bool(info.eol))
+        except KrepGpuError:
+            if not eng.get_regex_loops():  # (no search asks the loops compiler: no plan exists either)
+                raise
+            eng.regex_compile_loops(self.params)  # (raises the refusal when no compiler takes the search)
+            return 4096 + 1  # a match of a loops program lies inside one line, and no line of more than 4096 bytes is walked
 
     def grep_lines(self, d_text: int, n: int, filename=None, max_count=None, stream: int = 0, color=False) -> bytes:
         """What `krep [-m N] PATTERN FILE` prints (colour off) for the n bytes at d_text: the scan with records, the cut to the

@@ -1,0 +1,111 @@
+"""krep -E with *, + and {n,} on the device (kg_regex_loops.hip: the filter scan that names the candidate lines, the line walk) beside the
+literal scan and beside the reference's regex_search on the CPU.  Two texts resident in HBM, one after the other: a kind-2 haystack with
+`Sherlock` planted every 10 000 bytes and a kind-5 word text.  hipEvent times of whole scans, the median of 10 steady scans after 2
+warm-ups (3 after 1 when a scan takes more than half a second).  The yardstick comes first: the literal plan for `Sherlock` on the same
+buffer.  Then every pattern with -c and with records, each road forced in turn (krep_gpu_debug_force_regex_loops_road) and the scan's
+own choice; and regex_search itself (oracle/_ref, one thread) on the first 256 MiB of the host twin.  There is no pass bar on these
+numbers: the switch krep_gpu_set_regex_loops stays off whatever they say.
+  usage: python tools/regex_loops_bench.py [GiB = 8] [CPU MiB = 256] [output = profiles/regex_loops_scan.txt]"""
+import locale
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch  # noqa: E402
+import krep_amd  # noqa: E402
+from krep_amd import abi  # noqa: E402
+from krep_amd.engine import KrepGpuError  # noqa: E402
+import regex_ref  # noqa: E402
+import wordlist  # noqa: E402
+
+locale.setlocale(locale.LC_CTYPE, "C")  # the locale krep runs in; the -E compilers take no pattern in a multibyte one
+gib = float(sys.argv[1]) if len(sys.argv) > 1 else 8.0
+cpu_mib = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "regex_loops_scan.txt")
+n = int(gib * (1 << 30))
+SEED, PERIOD = 42, 10000
+WORDS = wordlist.pack(wordlist.word_list())
+TEXTS = [("kind-2 haystack, `Sherlock` every 10 000 bytes", 2, SEED, b"Sherlock", PERIOD), ("kind-5 word text", 5, 20260930, WORDS, 80)]
+PATTERNS = [(b"Sherlo+ck", "filter Sherlo: rare"), (b"Sherlock.*[a-z]", "filter Sherlock.: rare, the match runs to the line's end"),
+            (b"[a-z]+ck", "filter [a-z]ck")]
+ROADS = [(0, "auto"), (1, "sparse"), (2, "dense")]
+e = krep_amd.load()
+e.set_regex_loops(True)
+buf = torch.empty(n + 64, dtype=torch.uint8, device="cuda")
+cap = n // 64
+pos = torch.empty(2 * cap, dtype=torch.int64, device="cuda")
+rows = []
+
+
+def say(line):
+    print(line, flush=True)
+    rows.append(line)
+
+
+def median_ms(plan, want_pos):
+    def scan():
+        return plan.scan(buf.data_ptr(), n, 0, n, 0, pos.data_ptr() if want_pos else 0, cap if want_pos else 0, time_it=True)
+    out = scan()  # (builds the inner plans and sizes the scratch)
+    warm, steady = (1, 3) if out.kernel_ms > 500 else (2, 10)
+    ms = []
+    for i in range(warm + steady):
+        out = scan()
+        if i >= warm:
+            ms.append(out.kernel_ms)
+    return statistics.median(ms), out
+
+
+say(f"# tools/regex_loops_bench.py: {gib:g} GiB texts, hipEvent time of a whole scan (filter scan, line analysis, line walk), median of 10")
+say("# steady scans after 2 warm-ups (3 after 1 beyond 0.5 s); GB/s = text bytes / time; ratio = to the literal plan for `Sherlock` in the")
+say("# same mode on the same buffer; road: forced, or auto with the road it took")
+for name, kind, seed, needle, period in TEXTS:
+    e.generate(buf.data_ptr(), n, 0, kind, seed, needle, period)
+    torch.cuda.synchronize()
+    say(f"## {name} (seed {seed})")
+    yard = {}
+    plan = e.plan(abi.Params([b"Sherlock"]))
+    for mode, want_pos in (("count", False), ("records", True)):
+        ms, out = median_ms(plan, want_pos)
+        yard[mode] = ms
+        say(f"literal  {'Sherlock':<18} {mode:<8} {'-':<7} {ms:9.3f} ms {n / ms / 1e6:7.0f} GB/s  ratio 1.00  matches {out.total_matches}")
+    plan.close()
+    for pat, what in PATTERNS:
+        for mode in ("-c", "records"):
+            kw = dict(count_lines=True) if mode == "-c" else dict()
+            for road, road_name in ROADS:
+                e.force_regex_loops_road(road)
+                plan = e.plan(abi.Params([pat], regex=True, **kw))
+                try:
+                    before = e.regex_loops_roads()
+                    ms, out = median_ms(plan, mode == "records")
+                    after = e.regex_loops_roads()
+                    took = "sparse" if after[0] > before[0] else "dense"
+                    ref_ms = yard["records" if mode == "records" else "count"]
+                    say(f"regex    {pat.decode():<18} {mode:<8} {road_name + ('>' + took if road == 0 else ''):<12} {ms:9.3f} ms {n / ms / 1e6:7.1f} GB/s  "
+                        f"ratio {ref_ms / ms:5.3f}  {'lines' if mode == '-c' else 'matches'} {out.count}  ({what})")
+                except KrepGpuError as err:
+                    say(f"regex    {pat.decode():<18} {mode:<8} {road_name:<12} refused: {err}")
+                finally:
+                    plan.close()
+                    e.force_regex_loops_road(0)
+    if regex_ref.available():
+        m = min(n, cpu_mib << 20)
+        host = e.generate_host(m, 0, kind, seed, needle, period)
+        say(f"# the reference's regex_search (compiled reference, glibc regexec, ONE thread) on the first {m >> 20} MiB of the same text")
+        for pat, _ in PATTERNS:
+            for mode in ("count", "-c"):
+                kw = dict(count_lines=True) if mode == "-c" else dict(track_positions=False)
+                t0 = time.perf_counter()
+                ret, _ = regex_ref.call(pat, host, want_result=False, **kw)
+                dt = time.perf_counter() - t0
+                say(f"cpu      {pat.decode():<18} {mode:<8} {dt * 1e3:9.0f} ms {m / dt / 1e9:7.3f} GB/s  returned {ret}")
+    else:
+        say("# no compiled reference (oracle/_ref) on this host: the CPU rows are missing")
+e.set_regex_loops(False)
+os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+with open(out_path, "w") as f:
+    f.write("\n".join(rows) + "\n")
