@@ -21,16 +21,22 @@
 //   item output offsets: the summed per-record sizes read at each item's first record (bf_item_offsets).
 // "Behind the item's last newline" is decided as kg_matches.hip decides it for a text: the record's true LINE is the item's newline
 // count + 1.  No kernel loops per item over its records or per record over a line.
+//
+// Host side of both calls (the shared pieces are kg_format_host.h's): out, bf_enter = fmt_enter with the pack view in front of the
+// pointers, the pack's own rule about fmt->prefix, FormatStrings::refuse on the three other strings, n == 0; under g_fmt_mu
+// bf_refuse = (0), the scratch (ln_analyse's for the lines form, with the item words and the strings behind it; a FmtCursor for
+// -o), the strings' upload, the kernels, the read-back (ln_read_back for the lines form) and fmt_gather with bf_gather<P> as its
+// launch, which also asks `grow` for the buffer.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <mutex>
-#include <vector>
 
 #include "../../include/krep_gpu.h"
 #include "kg_device.h"
 #include "kg_format_dev.h"
+#include "kg_format_host.h"
 #include "kg_internal.h"
 
 namespace kg {
@@ -388,34 +394,18 @@ __global__ __launch_bounds__(256) void bf_item_offsets(const u64 *__restrict__ r
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 // what both calls check before they touch the device; *done: nothing is left to do (n == 0: the sizes stay 0, the item offsets are 0)
 int bf_enter(const char *who, const void *d_pack, const krep_gpu_pack_view_t *v, const match_position_t *d_positions, uint64_t n,
-             const size_t prefix_len, const char *const str[3], const size_t len[3], uint64_t *d_item_out_off, hipStream_t st, bool *done)
+             const size_t prefix_len, const FormatStrings &fs, uint64_t *d_item_out_off, hipStream_t st, bool *done)
 {
     *done = false;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return fail("%s: no HIP device available", who);
-    }
-    if (const char *why = device_unusable(dev))
-        return fail("%s: %s", who, why);
-    if (!v)
-        return fail("%s: the pack view is NULL", who);
-    if (v->n_items && (!v->d_item_off || !v->d_prefix_off))
-        return fail("%s: d_item_off / d_prefix_off is NULL", who);
-    if (n && (!d_pack || !d_positions))
-        return fail("%s: d_pack / d_positions is NULL", who);
-    if (n >> 40)
-        return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
+    const char *view = !v                                                            ? "the pack view is NULL"
+                       : (v->n_items && (!v->d_item_off || !v->d_prefix_off)) ? "d_item_off / d_prefix_off is NULL"
+                                                                              : nullptr; // (looked at in front of the pointers)
+    if (fmt_enter(who, view, n && (!d_pack || !d_positions), "d_pack / d_positions", n))
+        return 2;
     if (prefix_len)
         return fail("%s: fmt->prefix must be empty: the prefixes of a pack are per item (krep_gpu_pack_view_t)", who);
-    for (int k = 0; k < 3; ++k)
-    {
-        if (len[k] && !str[k])
-            return fail("%s: a string of the format is NULL", who);
-        if (len[k] >> 20)
-            return fail("%s: a format string of %zu bytes", who, len[k]);
-    }
+    if (fs.refuse(who))
+        return 2;
     if (n && !v->n_items)
         return fail("%s: records on a pack without items", who);
     if (!n)
@@ -457,17 +447,6 @@ int bf_refuse(const char *who, const krep_gpu_pack_view_t &v, u64 packed_len, co
     return 0;
 }
 
-template <class P>
-int bf_launch_gather(const P &p, const u64 *off, u64 n, void *d_out, u64 bytes, hipStream_t st)
-{
-    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
-    const u64 nchunks = (bytes + misalign + 15) / 16;
-    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(bf_gather<P>), dim3(grid), dim3(256), 0, st, p, off, n, (uint8_t *)d_out, bytes, misalign, nchunks);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
-}
 } // namespace
 
 int format_lines_items(const void *d_pack, size_t packed_len, const krep_gpu_pack_view_t *v, const match_position_t *d_positions, uint64_t n,
@@ -480,19 +459,14 @@ int format_lines_items(const void *d_pack, size_t packed_len, const krep_gpu_pac
     *out = krep_gpu_lines_out_t{};
     const krep_gpu_line_format_t none{};
     const krep_gpu_line_format_t &m = fmt ? *fmt : none;
-    const char *str[3] = {m.before_match, m.after_match, m.line_close};
-    const size_t len[3] = {m.before_match_len, m.after_match_len, m.line_close_len};
+    const FormatStrings fs{{m.before_match, m.before_match_len}, {m.after_match, m.after_match_len}, {m.line_close, m.line_close_len}};
     bool done = false;
-    if (bf_enter(who, d_pack, v, d_positions, n, m.prefix_len, str, len, d_item_out_off, st, &done))
+    if (bf_enter(who, d_pack, v, d_positions, n, m.prefix_len, fs, d_item_out_off, st, &done))
         return 2;
     if (done)
         return 0;
     std::lock_guard<std::mutex> lk(g_fmt_mu);
-    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the strings behind one another, alive until the copy has run
-    h_fix.clear();
-    for (int k = 0; k < 3; ++k)
-        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
-    const LcFixed f{0u, (u32)len[0], (u32)len[1], (u32)len[2]};
+    const LcFixed f{0u, (u32)fs.len(0), (u32)fs.len(1), (u32)fs.len(2)};
     const u64 *rec = (const u64 *)d_positions;
     {
         void *base = nullptr;
@@ -502,12 +476,12 @@ int format_lines_items(const void *d_pack, size_t packed_len, const krep_gpu_pac
     // (1)-(3) on the whole pack; behind its words: item[n + 1], then the strings
     const u64 n1 = n + 1;
     LnWork w;
-    if (ln_analyse((const uint8_t *)d_pack, packed_len, rec, n, n1 * sizeof(u64) + h_fix.size(), w, st))
+    if (ln_analyse((const uint8_t *)d_pack, packed_len, rec, n, n1 * sizeof(u64) + fs.bytes(), w, st))
         return 2;
     u64 *item = (u64 *)w.prefix;
     uint8_t *d_fix = (uint8_t *)(item + n1);
-    if (!h_fix.empty())
-        HIPCHK(hipMemcpyAsync(d_fix, h_fix.data(), h_fix.size(), hipMemcpyHostToDevice, st));
+    if (fs.upload(d_fix, st))
+        return 2;
     u64 *off = w.ls; // the line starts are not read again behind the size pass: their buffer takes the summed byte counts
     const u32 grid_s = (u32)((n1 + kBfPerBlock - 1) / kBfPerBlock);
     if (v->n_items + 1 <= kBfLdsItems)
@@ -523,34 +497,16 @@ int format_lines_items(const void *d_pack, size_t packed_len, const krep_gpu_pac
         hipLaunchKernelGGL(bf_item_offsets, dim3((u32)((v->n_items + 1 + 255) / 256)), dim3(256), 0, st, rec, (u64)n,
                            (const u64 *)v->d_item_off, (u64)v->n_items, (const u64 *)off, (u64 *)d_item_out_off);
     HIPCHK(hipGetLastError());
-    u64 h[2] = {0, 0}, total = 0, bytes = 0;
-    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&bytes, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h, w.ctr, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h[0])
-        return fail("%s: the record list is not ascending in start, or a record lies outside the pack", who);
-    out->lines = total;
-    out->lines_total = total;
-    out->out_bytes = bytes;
-    out->capped_lines = h[1];
-    if (grow && bytes)
-    {
-        d_out = (*grow)(bytes);
-        out_capacity = bytes;
-        if (!d_out)
-            return 2;
-    }
-    if (!d_out || !out_capacity || !bytes)
-        return 0;
-    if (bytes > out_capacity)
-    {
-        out->overflow = 1;
-        return 0;
-    }
+    u64 h[2] = {0, 0};
+    if (ln_read_back(who, "pack", w, off, n, ~0ull, h, 2, out, st)) // (no limit: every line of the pack is emitted)
+        return 2;
+    const u64 bytes = out->out_bytes;
     const BfLines p{(const uint8_t *)d_pack, rec, w.le, off, w.range, item, d_fix, f, (const uint8_t *)v->d_prefix_bytes,
                     (const u64 *)v->d_prefix_off};
-    return bf_launch_gather(p, off, n, d_out, bytes, st);
+    return fmt_gather(bytes, d_out, out_capacity, grow, &out->overflow, st, [&](uint8_t *o, u32 misalign, u64 nchunks, u32 grid) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(bf_gather<BfLines>), dim3(grid), dim3(256), 0, st, p, (const u64 *)off, (u64)n, o, bytes, misalign,
+                           nchunks);
+    });
 }
 
 int format_matches_items(const void *d_pack, size_t packed_len, const krep_gpu_pack_view_t *v, const match_position_t *d_positions,
@@ -563,38 +519,31 @@ int format_matches_items(const void *d_pack, size_t packed_len, const krep_gpu_p
     *out = krep_gpu_matches_out_t{};
     const krep_gpu_match_format_t none{};
     const krep_gpu_match_format_t &m = fmt ? *fmt : none;
-    const char *str[3] = {m.before_number, m.after_number, m.after_match};
-    const size_t len[3] = {m.before_number_len, m.after_number_len, m.after_match_len};
+    const FormatStrings fs{{m.before_number, m.before_number_len}, {m.after_number, m.after_number_len}, {m.after_match, m.after_match_len}};
     bool done = false;
-    if (bf_enter(who, d_pack, v, d_positions, n, m.prefix_len, str, len, d_item_out_off, st, &done))
+    if (bf_enter(who, d_pack, v, d_positions, n, m.prefix_len, fs, d_item_out_off, st, &done))
         return 2;
     if (done)
         return 0;
     if (packed_len >= kOmMaxText)
         return fail("%s: pack too long", who);
     std::lock_guard<std::mutex> lk(g_fmt_mu);
-    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the strings behind one another, alive until the copy has run
-    h_fix.clear();
-    for (int k = 0; k < 3; ++k)
-        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
-    const OmFixed f{(u32)len[0], (u32)len[1], (u32)len[2]};
+    const OmFixed f{(u32)fs.len(0), (u32)fs.len(1), (u32)fs.len(2)};
     const u64 *rec = (const u64 *)d_positions;
-    const u64 fixed = h_fix.size(), nblocks = line_blocks(packed_len), n1 = n + 1, ni = v->n_items;
+    const u64 fixed = fs.bytes(), nblocks = line_blocks(packed_len), n1 = n + 1, ni = v->n_items;
     const u64 sums = scan_sums_words(std::max(nblocks, n1));
-    void *base = nullptr;
-    if (fmt_reserve((8 + 2 * nblocks + 4 * n1 + 3 * ni + sums) * sizeof(u64) + fixed + 16, &base))
+    FmtCursor c;
+    if (c.reserve(8 + 2 * nblocks + 4 * n1 + 3 * ni + sums, fixed))
         return 2;
-    u64 *q = (u64 *)base;
-    auto take = [&](u64 words) { u64 *r = q; q += words; return r; };
-    u64 *ctr = take(8), *counts = take(nblocks), *before = take(nblocks); // ctr: {refused, (om_lines' stale word, not used here)}
-    u64 *line = take(n1), *bytes = take(n1), *off = take(n1), *item = take(n1);
-    u64 *nl_base = take(ni), *nl_inside = take(ni), *stale = take(ni), *sum_words = take(sums);
-    uint8_t *d_fix = (uint8_t *)q;
+    u64 *ctr = c.take(8), *counts = c.take(nblocks), *before = c.take(nblocks); // ctr: {refused, (om_lines' stale word, not used here)}
+    u64 *line = c.take(n1), *bytes = c.take(n1), *off = c.take(n1), *item = c.take(n1);
+    u64 *nl_base = c.take(ni), *nl_inside = c.take(ni), *stale = c.take(ni), *sum_words = c.take(sums);
+    uint8_t *d_fix = c.tail();
     if (bf_refuse(who, *v, packed_len, rec, n, ctr, item, st))
         return 2;
     HIPCHK(hipMemsetAsync(ctr, 0, 8 * sizeof(u64), st));
-    if (fixed)
-        HIPCHK(hipMemcpyAsync(d_fix, h_fix.data(), fixed, hipMemcpyHostToDevice, st));
+    if (fs.upload(d_fix, st))
+        return 2;
     if (newlines_before_blocks((const uint8_t *)d_pack, packed_len, counts, before, sum_words, st))
         return 2;
     om_lines_on((const uint8_t *)d_pack, packed_len, rec, n, before, nblocks, line, ctr, st);
@@ -615,23 +564,12 @@ int format_matches_items(const void *d_pack, size_t packed_len, const krep_gpu_p
         return fail("%s: the record list is not ascending in start, or a record lies outside the pack", who);
     out->items = n;
     out->out_bytes = total;
-    if (grow && total)
-    {
-        d_out = (*grow)(total);
-        out_capacity = total;
-        if (!d_out)
-            return 2;
-    }
-    if (!d_out || !out_capacity || !total)
-        return 0;
-    if (total > out_capacity)
-    {
-        out->overflow = 1;
-        return 0;
-    }
     const BfMatches p{(const uint8_t *)d_pack, (u64)packed_len, rec, line, item, d_fix, f, (const uint8_t *)v->d_prefix_bytes,
                       (const u64 *)v->d_prefix_off};
-    return bf_launch_gather(p, off, n, d_out, total, st);
+    return fmt_gather(total, d_out, out_capacity, grow, &out->overflow, st, [&](uint8_t *o, u32 misalign, u64 nchunks, u32 grid) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(bf_gather<BfMatches>), dim3(grid), dim3(256), 0, st, p, (const u64 *)off, (u64)n, o, total, misalign,
+                           nchunks);
+    });
 }
 
 } // namespace kg

@@ -9,14 +9,21 @@
 // (start, end) order.  The sort itself is the vendor's device radix sort (hipCUB, header-only in ROCm; it counts items in an
 // int, hence the documented 2^31-1 record limit of krep_gpu_order_by_start) — a bandwidth-bound primitive off the hot path;
 // the split/merge kernels, the prefix sum and the line-number kernels are ours.  Scratch is one grow-only buffer per device.
+//
+// The file is also the home of what the grep-output drivers (kg_lines.hip, kg_matches.hip, kg_batch_format.hip) share on the host,
+// declared in kg_format_host.h: the entry checks (fmt_enter), the strings of a format (FormatStrings: their check and the one
+// staging vector they are joined in), the scratch and the cursor that carves it (fmt_reserve, FmtCursor), the prefix scan, and the
+// output tail (fmt_gather).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <mutex>
+#include <vector>
 
 #include "../../include/krep_gpu.h"
 #include "kg_device.h"
+#include "kg_format_host.h"
 #include "kg_internal.h"
 
 namespace kg {
@@ -282,6 +289,49 @@ void format_release()
         }
     if (prev >= 0)
         (void)hipSetDevice(prev);
+}
+
+// ---- the host steps of the grep-output drivers (kg_format_host.h) ---------------------------------------------------------------
+int fmt_enter(const char *who, const char *refuse_first, bool null_pointer, const char *pointers, uint64_t n)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return fail("%s: no HIP device available", who);
+    }
+    if (const char *why = device_unusable(dev))
+        return fail("%s: %s", who, why);
+    if (refuse_first)
+        return fail("%s: %s", who, refuse_first);
+    if (null_pointer)
+        return fail("%s: %s is NULL", who, pointers);
+    if (n >> 40)
+        return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
+    return 0;
+}
+
+int FormatStrings::refuse(const char *who) const
+{
+    for (int i = 0; i < k; ++i)
+    {
+        if (s[i].len && !s[i].ptr)
+            return fail("%s: a string of the format is NULL", who);
+        if (s[i].len >> 20)
+            return fail("%s: a format string of %zu bytes", who, s[i].len);
+    }
+    return 0;
+}
+
+int FormatStrings::upload(uint8_t *d, hipStream_t st) const
+{
+    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the strings behind one another, alive until the copy has run
+    h_fix.clear();
+    for (int i = 0; i < k; ++i)
+        h_fix.insert(h_fix.end(), (const uint8_t *)s[i].ptr, (const uint8_t *)s[i].ptr + s[i].len);
+    if (!h_fix.empty())
+        HIPCHK(hipMemcpyAsync(d, h_fix.data(), h_fix.size(), hipMemcpyHostToDevice, st));
+    return 0;
 }
 
 } // namespace kg

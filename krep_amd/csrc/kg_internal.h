@@ -253,7 +253,8 @@ inline bool by_start_end(const match_position_t &a, const match_position_t &b) /
 }
 bool have_error();
 
-// kg_format.hip — what the formatter-side entry points share (kg_lines.hip)
+// kg_format.hip — what the formatter-side entry points share: the scratch, the scan and the newline table below; the host steps of
+// the grep-output drivers (entry checks, format strings, the cursor over the scratch, the output tail) are declared in kg_format_host.h
 void format_release(); // frees the formatter scratch of every device
 extern std::mutex g_fmt_mu;                 // held for a whole formatter call: its scratch is one buffer per device
 int fmt_reserve(size_t bytes, void **out);  // that buffer, grown to at least `bytes` (g_fmt_mu held); 2: failed

@@ -27,15 +27,22 @@
 // size pass and a gather of its own, (4') and (5') below.  krep_gpu_format_lines_window (the same lines for a WINDOW of a text: the
 // buffer may begin and end inside a line, the call owns the lines that START in [own_lo, own_hi)) shares (1), the sums and (5') and
 // has (2"), (3") and (4") of its own, further below.
+//
+// Host side, the same for the three formatting calls (the shared pieces are kg_format_host.h's): ln_check (out, fmt_enter), the
+// format's strings (FormatStrings::refuse), the call's own checks; under g_fmt_mu the scratch from ln_layout, the strings' upload,
+// ln_table = (1), ln_records = (2)-(3) with ln_bounds / ln_heads or the window's lw_bounds / lw_heads — ln_analyse is the layout
+// and these steps for a whole text; then the call's size pass and sum, ln_read_back (one wait: the totals and the counter words,
+// the refusal of a bad list, *out) and fmt_gather with the call's gather as its launch.  krep_gpu_matching_lines has no gather and
+// reads other words back: it shares ln_check and ln_analyse only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <mutex>
-#include <vector>
 
 #include "../../include/krep_gpu.h"
 #include "kg_device.h"
 #include "kg_format_dev.h"
+#include "kg_format_host.h"
 #include "kg_internal.h"
 
 namespace kg {
@@ -576,50 +583,88 @@ int ln_check(const char *who, const void *d_text, const void *d_positions, uint6
     if (!out)
         return fail("%s: out is NULL", who);
     *out = krep_gpu_lines_out_t{};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return fail("%s: no HIP device available", who);
-    }
-    if (const char *why = device_unusable(dev))
-        return fail("%s: %s", who, why);
-    if (n && (!d_text || !d_positions))
-        return fail("%s: d_text / d_positions is NULL", who);
-    if (n >> 40)
-        return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
+    return fmt_enter(who, nullptr, n && (!d_text || !d_positions), "d_text / d_positions", n);
+}
+
+// The scratch of a line analysis (g_fmt_mu held): the 8 counter words, `own_words` words of the caller's (16-byte aligned: they follow
+// the counters), the block table and its scans, six words per record and one more, the sums, then `own_bytes` bytes at w.prefix
+static int ln_layout(u64 text_len, u64 n, u64 own_words, size_t own_bytes, LnWork &w, u64 *&own)
+{
+    const u64 nb = (text_len + kLnBlock - 1) / kLnBlock, n1 = n + 1;
+    const u64 sums = scan_sums_words(std::max(nb, n1));
+    FmtCursor c;
+    if (c.reserve(8 + own_words + 4 * nb + 6 * n1 + sums, own_bytes))
+        return 2;
+    w.nb = nb;
+    w.ctr = c.take(8);
+    own = c.take(own_words);
+    w.last1 = c.take(nb), w.prev1 = c.take(nb), w.first_rev = c.take(nb), w.next_rev = c.take(nb);
+    w.ls = c.take(n1), w.le = c.take(n1), w.a = c.take(n1), w.heads_before = c.take(n1), w.mark_before = c.take(n1), w.range = c.take(n1);
+    w.sums = c.take(sums);
+    w.prefix = c.tail();
     return 0;
 }
 
-// steps (1)-(3) on `st`; the scratch is laid out here (g_fmt_mu held by the caller)
+// step (1) on `st`: the block table and its two running maxima
+static void ln_table(const uint8_t *d_text, u64 text_len, const LnWork &w, hipStream_t st)
+{
+    const u32 grid_t = (u32)std::min<u64>((w.nb + 3) / 4, 256u * 32u);
+    hipLaunchKernelGGL(ln_block_table, dim3(grid_t), dim3(256), 0, st, d_text, text_len, w.nb, w.last1, w.first_rev);
+    scan_exclusive(w.last1, w.nb, w.prev1, w.sums, true, st);
+    scan_exclusive(w.first_rev, w.nb, w.next_rev, w.sums, true, st);
+}
+
+// steps (2)-(3) on `st`; win != NULL: the window's (2") and (3"), which leave the relative copy of the list in `loc`
+static void ln_records(const uint8_t *d_text, u64 text_len, const u64 *d_rec, u64 n, const LnWork &w, hipStream_t st,
+                       const LwWindow *win = nullptr, u64 *loc = nullptr)
+{
+    const u64 n1 = n + 1;
+    const u32 grid_n = (u32)((n1 + 255) / 256);
+    if (win)
+    {
+        hipLaunchKernelGGL(lw_bounds, dim3(grid_n), dim3(256), 0, st, d_text, text_len, d_rec, n, *win, (const u64 *)w.prev1,
+                           (const u64 *)w.next_rev, w.nb, loc, w.ls, w.le, w.ctr);
+        hipLaunchKernelGGL(lw_heads, dim3(grid_n), dim3(256), 0, st, (const u64 *)w.ls, n, w.a, w.range);
+    }
+    else
+    {
+        hipLaunchKernelGGL(ln_bounds, dim3(grid_n), dim3(256), 0, st, d_text, text_len, d_rec, n, (const u64 *)w.prev1,
+                           (const u64 *)w.next_rev, w.nb, w.ls, w.le, w.ctr);
+        hipLaunchKernelGGL(ln_heads, dim3(grid_n), dim3(256), 0, st, (const u64 *)w.ls, n, w.a, w.range);
+    }
+    scan_exclusive(w.a, n1, w.heads_before, w.sums, false, st);
+    scan_exclusive(w.range, n1, w.mark_before, w.sums, true, st);
+}
+
+// the layout and steps (1)-(3) on `st` (g_fmt_mu held by the caller)
 int ln_analyse(const uint8_t *d_text, u64 text_len, const u64 *d_rec, u64 n, size_t prefix_len, LnWork &w, hipStream_t st)
 {
     if (!text_len)
         return fail("krep_gpu_matching_lines / krep_gpu_format_lines: records on an empty text");
-    const u64 nb = (text_len + kLnBlock - 1) / kLnBlock, n1 = n + 1;
-    const u64 sums = scan_sums_words(std::max(nb, n1));
-    void *base = nullptr;
-    if (fmt_reserve((8 + 4 * nb + 6 * n1 + sums) * sizeof(u64) + prefix_len + 16, &base))
+    u64 *none = nullptr;
+    if (ln_layout(text_len, n, 0, prefix_len, w, none))
         return 2;
-    u64 *p = (u64 *)base;
-    auto take = [&](u64 words) { u64 *q = p; p += words; return q; };
-    w.nb = nb;
-    w.ctr = take(8);
-    w.last1 = take(nb), w.prev1 = take(nb), w.first_rev = take(nb), w.next_rev = take(nb);
-    w.ls = take(n1), w.le = take(n1), w.a = take(n1), w.heads_before = take(n1), w.mark_before = take(n1), w.range = take(n1);
-    w.sums = take(sums);
-    w.prefix = (uint8_t *)p;
     HIPCHK(hipMemsetAsync(w.ctr, 0, 8 * sizeof(u64), st));
-    const u32 grid_t = (u32)std::min<u64>((nb + 3) / 4, 256u * 32u), grid_n = (u32)((n1 + 255) / 256);
-    hipLaunchKernelGGL(ln_block_table, dim3(grid_t), dim3(256), 0, st, d_text, text_len, nb, w.last1, w.first_rev);
-    scan_exclusive(w.last1, nb, w.prev1, w.sums, true, st);
-    scan_exclusive(w.first_rev, nb, w.next_rev, w.sums, true, st);
-    hipLaunchKernelGGL(ln_bounds, dim3(grid_n), dim3(256), 0, st, d_text, text_len, d_rec, n, (const u64 *)w.prev1,
-                       (const u64 *)w.next_rev, nb, w.ls, w.le, w.ctr);
-    hipLaunchKernelGGL(ln_heads, dim3(grid_n), dim3(256), 0, st, (const u64 *)w.ls, n, w.a, w.range);
-    scan_exclusive(w.a, n1, w.heads_before, w.sums, false, st);
-    scan_exclusive(w.range, n1, w.mark_before, w.sums, true, st);
+    ln_table(d_text, text_len, w, st);
+    ln_records(d_text, text_len, d_rec, n, w, st);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int ln_read_back(const char *who, const char *what, const LnWork &w, const u64 *off, u64 n, u64 max_lines, u64 *h, int k,
+                 krep_gpu_lines_out_t *out, hipStream_t st)
+{
+    u64 total = 0, bytes = 0;
+    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bytes, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h, w.ctr, k * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[0])
+        return fail("%s: the record list is not ascending in start, or a record lies outside the %s", who, what);
+    out->lines = std::min<u64>(total, max_lines);
+    out->lines_total = total;
+    out->out_bytes = bytes;
+    out->capped_lines = h[1];
     return 0;
 }
 
@@ -687,33 +732,13 @@ extern "C" int krep_gpu_format_lines(const void *d_text, size_t text_len, const 
                        w.a, w.range, w.ctr);
     scan_exclusive(w.a, n + 1, off, w.sums, false, st);
     HIPCHK(hipGetLastError());
-    u64 h[2] = {0, 0}, total = 0, bytes = 0;
-    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&bytes, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h, w.ctr, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h[0])
-        return fail("krep_gpu_format_lines: the record list is not ascending in start, or a record lies outside the text");
-    out->lines = std::min<u64>(total, max_lines);
-    out->lines_total = total;
-    out->out_bytes = bytes;
-    out->capped_lines = h[1];
-    const bool query = !d_out || !out_capacity;
-    if (query || !bytes)
-        return 0;
-    if (bytes > out_capacity)
-    {
-        out->overflow = 1;
-        return 0;
-    }
-    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
-    const u64 nchunks = (bytes + misalign + 15) / 16;
-    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
-    hipLaunchKernelGGL(ln_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)off, (const u64 *)w.range, (u64)n,
-                       (const uint8_t *)w.prefix, (u32)prefix_len, (uint8_t *)d_out, bytes, misalign, nchunks);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    u64 h[2] = {0, 0};
+    if (ln_read_back("krep_gpu_format_lines", "text", w, off, n, max_lines, h, 2, out, st))
+        return 2;
+    return fmt_gather(out->out_bytes, d_out, out_capacity, nullptr, &out->overflow, st, [&](uint8_t *o, u32 misalign, u64 nchunks, u32 grid) {
+        hipLaunchKernelGGL(ln_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)off, (const u64 *)w.range, (u64)n,
+                           (const uint8_t *)w.prefix, (u32)prefix_len, o, (u64)out->out_bytes, misalign, nchunks);
+    });
 }
 
 extern "C" int krep_gpu_format_lines_ex(const void *d_text, size_t text_len, const match_position_t *d_positions, uint64_t n,
@@ -725,62 +750,32 @@ extern "C" int krep_gpu_format_lines_ex(const void *d_text, size_t text_len, con
         return 2;
     const krep_gpu_line_format_t none{};
     const krep_gpu_line_format_t &m = fmt ? *fmt : none;
-    const char *str[4] = {m.prefix, m.before_match, m.after_match, m.line_close};
-    const size_t len[4] = {m.prefix_len, m.before_match_len, m.after_match_len, m.line_close_len};
-    for (int k = 0; k < 4; ++k)
-    {
-        if (len[k] && !str[k])
-            return fail("%s: a string of the format is NULL", who);
-        if (len[k] >> 20)
-            return fail("%s: a format string of %zu bytes", who, len[k]);
-    }
+    const FormatStrings fs{{m.prefix, m.prefix_len}, {m.before_match, m.before_match_len}, {m.after_match, m.after_match_len},
+                           {m.line_close, m.line_close_len}};
+    if (fs.refuse(who))
+        return 2;
     if (!n)
         return 0;
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(g_fmt_mu);
-    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the strings behind one another, alive until the copy has run
-    h_fix.clear();
-    for (int k = 0; k < 4; ++k)
-        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
-    const LcFixed f{(u32)len[0], (u32)len[1], (u32)len[2], (u32)len[3]};
+    const LcFixed f{(u32)fs.len(0), (u32)fs.len(1), (u32)fs.len(2), (u32)fs.len(3)};
     LnWork w;
-    if (ln_analyse((const uint8_t *)d_text, text_len, (const u64 *)d_positions, n, h_fix.size(), w, st))
+    if (ln_analyse((const uint8_t *)d_text, text_len, (const u64 *)d_positions, n, fs.bytes(), w, st) || fs.upload(w.prefix, st))
         return 2;
-    if (!h_fix.empty())
-        HIPCHK(hipMemcpyAsync(w.prefix, h_fix.data(), h_fix.size(), hipMemcpyHostToDevice, st));
     u64 *off = w.ls; // the line starts are not read again behind lc_sizes: their buffer takes the summed byte counts
     hipLaunchKernelGGL(lc_sizes, dim3((u32)((n + 1 + 255) / 256)), dim3(256), 0, st, (const u64 *)d_positions, (const u64 *)w.ls,
                        (const u64 *)w.le, (const u64 *)w.heads_before, (const u64 *)w.mark_before, (u64)n, (u64)max_lines, f, w.a,
                        w.range, w.ctr);
     scan_exclusive(w.a, n + 1, off, w.sums, false, st);
     HIPCHK(hipGetLastError());
-    u64 h[2] = {0, 0}, total = 0, bytes = 0;
-    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&bytes, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h, w.ctr, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h[0])
-        return fail("%s: the record list is not ascending in start, or a record lies outside the text", who);
-    out->lines = std::min<u64>(total, max_lines);
-    out->lines_total = total;
-    out->out_bytes = bytes;
-    out->capped_lines = h[1];
-    if (!d_out || !out_capacity || !bytes)
-        return 0;
-    if (bytes > out_capacity)
-    {
-        out->overflow = 1;
-        return 0;
-    }
-    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
-    const u64 nchunks = (bytes + misalign + 15) / 16;
-    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
-    hipLaunchKernelGGL(lc_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)d_positions, (const u64 *)w.le,
-                       (const u64 *)off, (const u64 *)w.range, (u64)n, (const uint8_t *)w.prefix, f, (uint8_t *)d_out, bytes, misalign,
-                       nchunks);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    u64 h[2] = {0, 0};
+    if (ln_read_back(who, "text", w, off, n, max_lines, h, 2, out, st))
+        return 2;
+    return fmt_gather(out->out_bytes, d_out, out_capacity, nullptr, &out->overflow, st, [&](uint8_t *o, u32 misalign, u64 nchunks, u32 grid) {
+        hipLaunchKernelGGL(lc_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)d_positions, (const u64 *)w.le,
+                           (const u64 *)off, (const u64 *)w.range, (u64)n, (const uint8_t *)w.prefix, f, o, (u64)out->out_bytes, misalign,
+                           nchunks);
+    });
 }
 
 extern "C" int krep_gpu_format_lines_window(const void *d_text, size_t text_len, const krep_gpu_lines_window_t *win,
@@ -796,15 +791,10 @@ extern "C" int krep_gpu_format_lines_window(const void *d_text, size_t text_len,
         return 2;
     const krep_gpu_line_format_t none{};
     const krep_gpu_line_format_t &m = fmt ? *fmt : none;
-    const char *str[4] = {m.prefix, m.before_match, m.after_match, m.line_close};
-    const size_t len[4] = {m.prefix_len, m.before_match_len, m.after_match_len, m.line_close_len};
-    for (int k = 0; k < 4; ++k)
-    {
-        if (len[k] && !str[k])
-            return fail("%s: a string of the format is NULL", who);
-        if (len[k] >> 20)
-            return fail("%s: a format string of %zu bytes", who, len[k]);
-    }
+    const FormatStrings fs{{m.prefix, m.prefix_len}, {m.before_match, m.before_match_len}, {m.after_match, m.after_match_len},
+                           {m.line_close, m.line_close_len}};
+    if (fs.refuse(who))
+        return 2;
     if (!win)
         return fail("%s: win is NULL", who);
     const u64 gb = win->global_base, glen = win->global_len;
@@ -821,80 +811,42 @@ extern "C" int krep_gpu_format_lines_window(const void *d_text, size_t text_len,
         return fail("%s: records on an empty buffer", who);
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(g_fmt_mu);
-    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the strings behind one another, alive until the copy has run
-    h_fix.clear();
-    for (int k = 0; k < 4; ++k)
-        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
-    const LcFixed f{(u32)len[0], (u32)len[1], (u32)len[2], (u32)len[3]};
+    const LcFixed f{(u32)fs.len(0), (u32)fs.len(1), (u32)fs.len(2), (u32)fs.len(3)};
     const LwWindow lw{gb, win->own_lo - gb, win->own_hi - gb, win->records_hi - gb,
                       (gb + text_len == glen && win->records_hi == glen) ? 1u : 0u};
-    // the scratch: as ln_analyse lays it out, and the relative copy of the list (16-byte aligned: it follows the counter block)
-    const u64 nb = (text_len + kLnBlock - 1) / kLnBlock, n1 = n + 1;
-    const u64 sums = scan_sums_words(std::max(nb, n1));
-    void *base = nullptr;
-    if (fmt_reserve((8 + 2 * n1 + 4 * nb + 6 * n1 + sums) * sizeof(u64) + h_fix.size() + 16, &base))
-        return 2;
-    u64 *p = (u64 *)base;
-    auto take = [&](u64 words) { u64 *q = p; p += words; return q; };
+    // ln_analyse's steps with the window's kernels in (2)-(3); the relative copy of the list lies behind the counter words
     LnWork w;
-    w.nb = nb;
-    w.ctr = take(8);
-    u64 *loc = take(2 * n1);
-    w.last1 = take(nb), w.prev1 = take(nb), w.first_rev = take(nb), w.next_rev = take(nb);
-    w.ls = take(n1), w.le = take(n1), w.a = take(n1), w.heads_before = take(n1), w.mark_before = take(n1), w.range = take(n1);
-    w.sums = take(sums);
-    w.prefix = (uint8_t *)p;
+    u64 *loc = nullptr;
+    if (ln_layout(text_len, n, 2 * (n + 1), fs.bytes(), w, loc))
+        return 2;
     HIPCHK(hipMemsetAsync(w.ctr, 0, 8 * sizeof(u64), st));
     HIPCHK(hipMemsetAsync(w.ctr + kLwFirst, 0xff, sizeof(u64), st));
-    if (!h_fix.empty())
-        HIPCHK(hipMemcpyAsync(w.prefix, h_fix.data(), h_fix.size(), hipMemcpyHostToDevice, st));
-    const u32 grid_t = (u32)std::min<u64>((nb + 3) / 4, 256u * 32u), grid_n = (u32)((n1 + 255) / 256);
-    hipLaunchKernelGGL(ln_block_table, dim3(grid_t), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len, nb, w.last1, w.first_rev);
-    scan_exclusive(w.last1, nb, w.prev1, w.sums, true, st);
-    scan_exclusive(w.first_rev, nb, w.next_rev, w.sums, true, st);
-    hipLaunchKernelGGL(lw_bounds, dim3(grid_n), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len, (const u64 *)d_positions, (u64)n,
-                       lw, (const u64 *)w.prev1, (const u64 *)w.next_rev, nb, loc, w.ls, w.le, w.ctr);
-    hipLaunchKernelGGL(lw_heads, dim3(grid_n), dim3(256), 0, st, (const u64 *)w.ls, (u64)n, w.a, w.range);
-    scan_exclusive(w.a, n1, w.heads_before, w.sums, false, st);
-    scan_exclusive(w.range, n1, w.mark_before, w.sums, true, st);
+    if (fs.upload(w.prefix, st))
+        return 2;
+    ln_table((const uint8_t *)d_text, text_len, w, st);
+    ln_records((const uint8_t *)d_text, text_len, (const u64 *)d_positions, n, w, st, &lw, loc);
     u64 *off = w.ls; // the line starts are not read again behind lw_sizes: their buffer takes the summed byte counts
-    hipLaunchKernelGGL(lw_sizes, dim3(grid_n), dim3(256), 0, st, (const u64 *)loc, (const u64 *)w.ls, (const u64 *)w.le,
+    hipLaunchKernelGGL(lw_sizes, dim3((u32)((n + 1 + 255) / 256)), dim3(256), 0, st, (const u64 *)loc, (const u64 *)w.ls, (const u64 *)w.le,
                        (const u64 *)w.heads_before, (const u64 *)w.mark_before, (u64)n, (u64)max_lines, f, w.a, w.range, w.ctr);
-    scan_exclusive(w.a, n1, off, w.sums, false, st);
+    scan_exclusive(w.a, n + 1, off, w.sums, false, st);
     HIPCHK(hipGetLastError());
-    u64 h[4] = {0, 0, 0, 0}, total = 0, bytes = 0;
-    HIPCHK(hipMemcpyAsync(&total, w.heads_before + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&bytes, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h, w.ctr, 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h[0])
+    u64 h[4] = {0, 0, 0, 0};
+    if (ln_read_back(who, "buffer", w, off, n, max_lines, h, 4, &out->lines, st))
     {
-        out->incomplete_first_record = 0;
-        return fail("%s: the record list is not ascending in start, or a record lies outside the buffer", who);
+        if (h[0])
+            out->incomplete_first_record = 0;
+        return 2;
     }
-    out->lines.lines = std::min<u64>(total, max_lines);
-    out->lines.lines_total = total;
-    out->lines.out_bytes = bytes;
-    out->lines.capped_lines = h[1];
-    if (h[kLwFirst] != kLnNone && total < max_lines) // the incomplete line is the last owned one: `total` lines stand in front of it
+    // the incomplete line is the last owned one: lines_total lines stand in front of it
+    if (h[kLwFirst] != kLnNone && out->lines.lines_total < max_lines)
     {
         out->incomplete_line_start1 = h[kLwStart1];
         out->incomplete_first_record = h[kLwFirst];
     }
-    if (!d_out || !out_capacity || !bytes)
-        return 0;
-    if (bytes > out_capacity)
-    {
-        out->lines.overflow = 1;
-        return 0;
-    }
-    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
-    const u64 nchunks = (bytes + misalign + 15) / 16;
-    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
-    hipLaunchKernelGGL(lc_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)loc, (const u64 *)w.le,
-                       (const u64 *)off, (const u64 *)w.range, (u64)n, (const uint8_t *)w.prefix, f, (uint8_t *)d_out, bytes, misalign,
-                       nchunks);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    return fmt_gather(out->lines.out_bytes, d_out, out_capacity, nullptr, &out->lines.overflow, st,
+                      [&](uint8_t *o, u32 misalign, u64 nchunks, u32 grid) {
+                          hipLaunchKernelGGL(lc_gather, dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (const u64 *)loc,
+                                             (const u64 *)w.le, (const u64 *)off, (const u64 *)w.range, (u64)n, (const uint8_t *)w.prefix, f, o,
+                                             (u64)out->lines.out_bytes, misalign, nchunks);
+                      });
 }

@@ -24,15 +24,20 @@
 // is decided by offset against last_newline1, which the caller states (the window does not know N).  Its kernels (mw_*) mirror the steps:
 // (1) unchanged on the buffer, (2w) mw_lines, (3w) mw_sizes, (4w) om_gather<true> = the gather with the source moved by global_base,
 // (5w) mw_count_to: the newlines in front of count_to, the next window's carry.  The whole-text call keeps its kernels.
+//
+// Host side of both calls (the shared pieces are kg_format_host.h's): out, fmt_enter — the window call with its own pointer test and
+// `win` in front of it — the strings of om_strings (FormatStrings::refuse), the call's own checks; under g_fmt_mu the scratch from
+// om_layout (one layout for both), the strings' upload, the kernels above, the read-back of the counter words and the total (each
+// call's own: the window reads four words and takes *out back on a refusal), fmt_gather with om_gather<WIN> as its launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <mutex>
-#include <vector>
 
 #include "../../include/krep_gpu.h"
 #include "kg_device.h"
 #include "kg_format_dev.h"
+#include "kg_format_host.h"
 #include "kg_internal.h"
 
 namespace kg {
@@ -248,22 +253,33 @@ void om_lines_on(const uint8_t *d_text, u64 text_len, const u64 *d_rec, u64 n, c
 
 using namespace kg;
 
-// the four strings of a format (NULL: all empty), checked
-static int om_strings(const char *who, const krep_gpu_match_format_t *fmt, const char *str[4], size_t len[4])
+// the four strings of a format (NULL: all empty)
+static FormatStrings om_strings(const krep_gpu_match_format_t *fmt)
 {
     const krep_gpu_match_format_t none{};
     const krep_gpu_match_format_t &m = fmt ? *fmt : none;
-    const char *s[4] = {m.prefix, m.before_number, m.after_number, m.after_match};
-    const size_t l[4] = {m.prefix_len, m.before_number_len, m.after_number_len, m.after_match_len};
-    for (int k = 0; k < 4; ++k)
-    {
-        if (l[k] && !s[k])
-            return fail("%s: a string of the format is NULL", who);
-        if (l[k] >> 20)
-            return fail("%s: a format string of %zu bytes", who, l[k]);
-        str[k] = s[k];
-        len[k] = l[k];
-    }
+    return {{m.prefix, m.prefix_len}, {m.before_number, m.before_number_len}, {m.after_number, m.after_number_len},
+            {m.after_match, m.after_match_len}};
+}
+
+// the scratch of both calls (g_fmt_mu held)
+struct OmWork
+{
+    u64 *ctr, *counts, *before, *line, *bytes, *off, *sum_words; // ctr: {refused, stale value, (window) the two newline counts}
+    uint8_t *d_fix;
+    u64 nblocks;
+};
+static int om_layout(u64 text_len, u64 n, size_t fixed, OmWork &w)
+{
+    const u64 nblocks = line_blocks(text_len), n1 = n + 1;
+    const u64 sums = scan_sums_words(std::max(nblocks, n1));
+    FmtCursor c;
+    if (c.reserve(8 + 2 * nblocks + 3 * n1 + sums, fixed))
+        return 2;
+    w.nblocks = nblocks;
+    w.ctr = c.take(8), w.counts = c.take(nblocks), w.before = c.take(nblocks);
+    w.line = c.take(n1), w.bytes = c.take(n1), w.off = c.take(n1), w.sum_words = c.take(sums);
+    w.d_fix = c.tail();
     return 0;
 }
 
@@ -275,21 +291,8 @@ extern "C" int krep_gpu_format_matches(const void *d_text, size_t text_len, cons
     if (!out)
         return fail("%s: out is NULL", who);
     *out = krep_gpu_matches_out_t{};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return fail("%s: no HIP device available", who);
-    }
-    if (const char *why = device_unusable(dev))
-        return fail("%s: %s", who, why);
-    if (n && (!d_text || !d_positions))
-        return fail("%s: d_text / d_positions is NULL", who);
-    if (n >> 40)
-        return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
-    const char *str[4];
-    size_t len[4];
-    if (om_strings(who, fmt, str, len))
+    const FormatStrings fs = om_strings(fmt);
+    if (fmt_enter(who, nullptr, n && (!d_text || !d_positions), "d_text / d_positions", n) || fs.refuse(who))
         return 2;
     if (!n)
         return 0;
@@ -299,57 +302,36 @@ extern "C" int krep_gpu_format_matches(const void *d_text, size_t text_len, cons
         return fail("%s: text too long", who);
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(g_fmt_mu);
-    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the fixed strings behind one another, alive until the copy has run
-    h_fix.clear();
-    for (int k = 0; k < 4; ++k)
-        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
-    const OmFixed f{(u32)(len[0] + len[1]), (u32)len[2], (u32)len[3]};
-    const u64 fixed = h_fix.size(), nblocks = line_blocks(text_len), n1 = n + 1;
-    const u64 sums = scan_sums_words(std::max(nblocks, n1));
-    void *base = nullptr;
-    if (fmt_reserve((8 + 2 * nblocks + 3 * n1 + sums) * sizeof(u64) + fixed + 16, &base))
+    const OmFixed f{(u32)(fs.len(0) + fs.len(1)), (u32)fs.len(2), (u32)fs.len(3)};
+    const u64 fixed = fs.bytes(), n1 = n + 1;
+    OmWork w;
+    if (om_layout(text_len, n, fixed, w))
         return 2;
-    u64 *p = (u64 *)base;
-    auto take = [&](u64 words) { u64 *q = p; p += words; return q; };
-    u64 *ctr = take(8), *counts = take(nblocks), *before = take(nblocks); // ctr: {refused, stale value}
-    u64 *line = take(n1), *bytes = take(n1), *off = take(n1), *sum_words = take(sums);
-    uint8_t *d_fix = (uint8_t *)p;
-    HIPCHK(hipMemsetAsync(ctr, 0, 8 * sizeof(u64), st));
-    if (fixed)
-        HIPCHK(hipMemcpyAsync(d_fix, h_fix.data(), fixed, hipMemcpyHostToDevice, st));
-    if (newlines_before_blocks((const uint8_t *)d_text, text_len, counts, before, sum_words, st))
+    HIPCHK(hipMemsetAsync(w.ctr, 0, 8 * sizeof(u64), st));
+    if (fs.upload(w.d_fix, st))
+        return 2;
+    if (newlines_before_blocks((const uint8_t *)d_text, text_len, w.counts, w.before, w.sum_words, st))
         return 2;
     hipLaunchKernelGGL(om_lines, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
-                       (const u64 *)d_positions, (u64)n, (const u64 *)before, nblocks, line, ctr);
+                       (const u64 *)d_positions, (u64)n, (const u64 *)w.before, w.nblocks, w.line, w.ctr);
     hipLaunchKernelGGL(om_sizes, dim3((u32)((n1 + 255) / 256)), dim3(256), 0, st, (const u64 *)d_positions, (u64)n, (u64)text_len,
-                       (const u64 *)(before + nblocks - 1), (u64)max_items, fixed, (const u64 *)ctr, line, bytes);
-    scan_exclusive(bytes, n1, off, sum_words, false, st);
+                       (const u64 *)(w.before + w.nblocks - 1), (u64)max_items, fixed, (const u64 *)w.ctr, w.line, w.bytes);
+    scan_exclusive(w.bytes, n1, w.off, w.sum_words, false, st);
     HIPCHK(hipGetLastError());
     u64 refused = 0, total = 0;
-    HIPCHK(hipMemcpyAsync(&refused, ctr, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&total, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&refused, w.ctr, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&total, w.off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (refused)
         return fail("%s: the record list is not ascending in start, or a record lies outside the text", who);
     const u64 emit = std::min<u64>(n, max_items);
     out->items = emit;
     out->out_bytes = total;
-    if (!d_out || !out_capacity || !total)
-        return 0;
-    if (total > out_capacity)
-    {
-        out->overflow = 1;
-        return 0;
-    }
-    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
-    const u64 nchunks = (total + misalign + 15) / 16;
-    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(om_gather<false>), dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
-                       (const u64 *)d_positions, (const u64 *)line, (const u64 *)off, emit, (const uint8_t *)d_fix, f, (uint8_t *)d_out,
-                       total, misalign, nchunks, (u64)0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    return fmt_gather(total, d_out, out_capacity, nullptr, &out->overflow, st, [&](uint8_t *o, u32 misalign, u64 nchunks, u32 grid) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(om_gather<false>), dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, (u64)text_len,
+                           (const u64 *)d_positions, (const u64 *)w.line, (const u64 *)w.off, emit, (const uint8_t *)w.d_fix, f, o, total,
+                           misalign, nchunks, (u64)0);
+    });
 }
 
 extern "C" int krep_gpu_format_matches_window(const void *d_text, size_t text_len, const krep_gpu_matches_window_t *win,
@@ -361,23 +343,10 @@ extern "C" int krep_gpu_format_matches_window(const void *d_text, size_t text_le
     if (!out)
         return fail("%s: out is NULL", who);
     *out = krep_gpu_matches_window_out_t{};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return fail("%s: no HIP device available", who);
-    }
-    if (const char *why = device_unusable(dev))
-        return fail("%s: %s", who, why);
-    if (!win)
-        return fail("%s: win is NULL", who);
-    if ((text_len && !d_text) || (n && !d_positions))
-        return fail("%s: d_text / d_positions is NULL", who);
-    if (n >> 40)
-        return fail("%s: %llu records are more than one call takes", who, (unsigned long long)n);
-    const char *str[4];
-    size_t len[4];
-    if (om_strings(who, fmt, str, len))
+    const FormatStrings fs = om_strings(fmt);
+    // (this call also runs without records, on the text alone: its pointer test is its own, and `win` is looked at in front of it)
+    if (fmt_enter(who, win ? nullptr : "win is NULL", (text_len && !d_text) || (n && !d_positions), "d_text / d_positions", n) ||
+        fs.refuse(who))
         return 2;
     const u64 gb = win->global_base, glen = win->global_len;
     if (glen >= kOmMaxText)
@@ -399,42 +368,32 @@ extern "C" int krep_gpu_format_matches_window(const void *d_text, size_t text_le
         return 0;
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(g_fmt_mu);
-    static std::vector<uint8_t> h_fix; // (under g_fmt_mu) the fixed strings behind one another, alive until the copy has run
-    h_fix.clear();
-    for (int k = 0; k < 4; ++k)
-        h_fix.insert(h_fix.end(), (const uint8_t *)str[k], (const uint8_t *)str[k] + len[k]);
-    const OmFixed f{(u32)(len[0] + len[1]), (u32)len[2], (u32)len[3]};
-    const MwWindow w{gb, (u64)text_len, glen, win->newlines_before, win->last_newline1, win->stale_line, win->stale_rule ? 1u : 0u};
-    const u64 fixed = h_fix.size(), nblocks = line_blocks(text_len), n1 = n + 1;
-    const u64 sums = scan_sums_words(std::max(nblocks, n1));
-    void *base = nullptr;
-    if (fmt_reserve((8 + 2 * nblocks + 3 * n1 + sums) * sizeof(u64) + fixed + 16, &base))
+    const OmFixed f{(u32)(fs.len(0) + fs.len(1)), (u32)fs.len(2), (u32)fs.len(3)};
+    const MwWindow mw{gb, (u64)text_len, glen, win->newlines_before, win->last_newline1, win->stale_line, win->stale_rule ? 1u : 0u};
+    const u64 fixed = fs.bytes(), n1 = n + 1;
+    OmWork w; // ctr: {refused, stale value, newlines in front of count_to, newlines of the buffer}
+    if (om_layout(text_len, n, fixed, w))
         return 2;
-    u64 *p = (u64 *)base;
-    auto take = [&](u64 words) { u64 *q = p; p += words; return q; };
-    u64 *ctr = take(8), *counts = take(nblocks), *before = take(nblocks); // ctr: {refused, stale value, newlines in front of count_to, newlines of the buffer}
-    u64 *line = take(n1), *bytes = take(n1), *off = take(n1), *sum_words = take(sums);
-    uint8_t *d_fix = (uint8_t *)p;
-    HIPCHK(hipMemsetAsync(ctr, 0, 8 * sizeof(u64), st));
-    if (fixed && n)
-        HIPCHK(hipMemcpyAsync(d_fix, h_fix.data(), fixed, hipMemcpyHostToDevice, st));
-    if (newlines_before_blocks((const uint8_t *)d_text, text_len, counts, before, sum_words, st))
+    HIPCHK(hipMemsetAsync(w.ctr, 0, 8 * sizeof(u64), st));
+    if (n && fs.upload(w.d_fix, st))
         return 2;
-    hipLaunchKernelGGL(mw_count_to, dim3(1), dim3(64), 0, st, (const uint8_t *)d_text, w, (u64)(win->count_to - gb), (const u64 *)before,
-                       nblocks, ctr);
+    if (newlines_before_blocks((const uint8_t *)d_text, text_len, w.counts, w.before, w.sum_words, st))
+        return 2;
+    hipLaunchKernelGGL(mw_count_to, dim3(1), dim3(64), 0, st, (const uint8_t *)d_text, mw, (u64)(win->count_to - gb), (const u64 *)w.before,
+                       w.nblocks, w.ctr);
     if (n)
     {
-        hipLaunchKernelGGL(mw_lines, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_text, w, (const u64 *)d_positions,
-                           (u64)n, (const u64 *)before, line, ctr);
-        hipLaunchKernelGGL(mw_sizes, dim3((u32)((n1 + 255) / 256)), dim3(256), 0, st, (const u64 *)d_positions, (u64)n, w, (u64)max_items,
-                           fixed, (const u64 *)ctr, line, bytes);
-        scan_exclusive(bytes, n1, off, sum_words, false, st);
+        hipLaunchKernelGGL(mw_lines, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_text, mw, (const u64 *)d_positions,
+                           (u64)n, (const u64 *)w.before, w.line, w.ctr);
+        hipLaunchKernelGGL(mw_sizes, dim3((u32)((n1 + 255) / 256)), dim3(256), 0, st, (const u64 *)d_positions, (u64)n, mw, (u64)max_items,
+                           fixed, (const u64 *)w.ctr, w.line, w.bytes);
+        scan_exclusive(w.bytes, n1, w.off, w.sum_words, false, st);
     }
     HIPCHK(hipGetLastError());
     u64 h_ctr[4] = {0, 0, 0, 0}, total = 0;
-    HIPCHK(hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_ctr, w.ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
     if (n)
-        HIPCHK(hipMemcpyAsync(&total, off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&total, w.off + n, sizeof(u64), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (h_ctr[0] || win->newlines_before + h_ctr[3] + 1 >= kOmMaxText)
         *out = krep_gpu_matches_window_out_t{};
@@ -448,20 +407,9 @@ extern "C" int krep_gpu_format_matches_window(const void *d_text, size_t text_le
     const u64 emit = std::min<u64>(n, max_items);
     out->matches.items = emit;
     out->matches.out_bytes = total;
-    if (!d_out || !out_capacity || !total)
-        return 0;
-    if (total > out_capacity)
-    {
-        out->matches.overflow = 1;
-        return 0;
-    }
-    const u32 misalign = (u32)(reinterpret_cast<size_t>(d_out) & 15u);
-    const u64 nchunks = (total + misalign + 15) / 16;
-    const u32 grid = (u32)std::min<u64>((nchunks + 255) / 256, 256u * 64u);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(om_gather<true>), dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, glen,
-                       (const u64 *)d_positions, (const u64 *)line, (const u64 *)off, emit, (const uint8_t *)d_fix, f, (uint8_t *)d_out,
-                       total, misalign, nchunks, gb);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    return fmt_gather(total, d_out, out_capacity, nullptr, &out->matches.overflow, st, [&](uint8_t *o, u32 misalign, u64 nchunks, u32 grid) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(om_gather<true>), dim3(grid), dim3(256), 0, st, (const uint8_t *)d_text, glen,
+                           (const u64 *)d_positions, (const u64 *)w.line, (const u64 *)w.off, emit, (const uint8_t *)w.d_fix, f, o, total,
+                           misalign, nchunks, gb);
+    });
 }
