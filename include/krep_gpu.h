@@ -933,7 +933,27 @@ int krep_gpu_format_matches_window(const void *d_text, size_t text_len, const kr
  *     the scalar tail is boyer_moore_search, which under -o skips a match's length (krep.c:1371), and where that tail begins
  *     depends on the whole text's length;
  *   - max_count != SIZE_MAX: the per-function max_count quirks are a property of each item's own list; cutting per item is
- *     follow-up work.
+ *     follow-up work.  (That is the answer while the switch below is off, which it is by default.)
+ * max_count behind a switch.  krep_gpu_set_batch_max_count(1) — process-wide, off unless $KREP_GPU_BATCH_MAX_COUNT=1 is set when the
+ *   library is loaded — makes a finite max_count no reason to refuse: krep_gpu_batch_can_accelerate(), krep_gpu_search_batch() and
+ *   krep_gpu_grep_batch() then take it, and every other refusal above stands with its own text.  Two max_count == 0 corners are placed
+ *   by the position in the text and stay refused, each with a reason of its own: neon_search (above), and a count-only search
+ *   through simd_avx2_search (a hit in the block body answers 1, a hit in the scalar tail is capped back to 0, krep.c:5036, :5066-5093).  Off, all three behave and report as if the switch did not exist.  The pack is still scanned
+ *   without a limit; each item's list is cut on the device, and the contract above holds with params as given: per item, what the
+ *   operator produces for the item ALONE under that max_count.  With T the item's records in the unlimited list R (emission order),
+ *   Ln its distinct lines and M = max_count:
+ *   - count = min(Ln, M) under count_lines_mode, else min(T, M).  M == 0 gives 0, except that a count-only search (neither
+ *     track_positions nor count_lines_mode) through boyer_moore_search, memchr_short_search or a regex gives T > 0 ? 1 : 0
+ *     (krep.c:1355-1367);
+ *   - records (where the batch returns records at all): the first min(T, M) of R; through kmp_search one more when T > M
+ *     (krep.c:1717-1724); through memchr_search, when T > M, M > 0 and M % 4096 == 0, the flush displacement (krep.c:3976-3991):
+ *     R[0 .. M-4096), R[M], R[M-4096 .. M-1) — M records, R[M-1] dropped; M == 0 keeps nothing; a multi-pattern list is cut in
+ *     emission order (end ascending), not in start order;
+ *   - krep_gpu_grep_batch() repeats search_file() behind the function (krep.c:2954-2981, :3018-3026): the item's list is cut to its
+ *     first M records of the above (kmp_search's extra record goes), put in (start, end) order and formatted; the -o stale-number rule
+ *     ("more than 10 records") sees the cut count; COUNT prints min(count, M), which is per_item[i].count too (0 in the count-only
+ *     M == 0 corner, where search_file caps).
+ *   info->total_records stays the number of records the scans produced — the UNCUT number; the sum of n_records is what came back.
  * Failure (a refused search, allocation, copy, launch): nothing is appended to `records`, `results` is not written, the call
  *   returns 2 and krep_gpu_last_error() names the reason.  The batch call has NO CPU fallback of its own (the selector registered
  *   with krep_gpu_set_cpu_fallback() is not asked): the caller loops over its files with its CPU function, as it does today.
@@ -956,10 +976,12 @@ typedef struct krep_gpu_batch_info
 {
     uint64_t packed_bytes;  /* bytes staged: the items and the separators between them, over all packs */
     uint64_t scans;         /* packs scanned                                                           */
-    uint64_t total_records; /* records the scans produced (under count_lines_mode too)                 */
+    uint64_t total_records; /* records the scans produced (under count_lines_mode too; under max_count: before the cut) */
     float kernel_ms;        /* hipEvent time of the scan kernels, summed over the packs                */
 } krep_gpu_batch_info_t;
 int krep_gpu_batch_can_accelerate(const search_params_t *params); /* 1 / 0, the reason in krep_gpu_last_error() */
+void krep_gpu_set_batch_max_count(int on); /* process-wide; default 0, or $KREP_GPU_BATCH_MAX_COUNT at load */
+int krep_gpu_get_batch_max_count(void);
 int krep_gpu_search_batch(const search_params_t *params, const krep_gpu_config_t *cfg /* NULL: current */,
                           const krep_gpu_batch_item_t *items, size_t n_items, krep_gpu_batch_result_t *results /* n_items */,
                           match_result_t *records /* nullable */, krep_gpu_batch_info_t *info /* nullable */); /* 0, or 2 */
@@ -1009,7 +1031,8 @@ int krep_gpu_format_matches_items(const void *d_pack, size_t packed_len, const k
  *   set; else LINES.  track_positions == false outside COUNT is refused (the reference then prints its empty-match line, which no
  *   batchable search produces).
  * Taken: exactly what krep_gpu_batch_can_accelerate() takes under the same configuration, with the same reasons; every refusal comes
- *   before any device work.  -m per file stays refused with it, and the pack runs on cfg->device alone.
+ *   before any device work.  -m per file stays refused with it unless krep_gpu_set_batch_max_count(1) (above: the cut, then the
+ *   (start, end) order, then the formatters on the kept list), and the pack runs on cfg->device alone.
  * Per pack (the packs of krep_gpu_search_batch(): the same limit, cut between items, info->scans): packed through the staging ring,
  *   scanned once with records, ordered by start when multi-pattern, cut into item bounds, the prefixes uploaded in one copy, the pack
  *   formatted in HBM, the bytes copied straight behind out->bytes + out->len.  Under COUNT the counts are printed on the host.

@@ -103,6 +103,10 @@ int krep_gpu_debug_batch_fill_host(const krep_gpu_batch_item_t *items, size_t n,
 /* test hook: launches of the batch's record rebase with the items' offset table in LDS (it fits: items + 1 <= 4096 entries) and with the
  * table in global memory, since the process started: which of the two a batch at the edge took shows in no result */
 void krep_gpu_debug_batch_rebase_launches(uint64_t *lds_table, uint64_t *global_table);
+/* test hook: launches of the batch's per-item max_count cut (batch_cut, krep_gpu_set_batch_max_count) with the summed kept-record table
+ * in LDS (items + 1 <= 4096 entries) and with the table in global memory, since the process started.  A batch without max_count, one that
+ * returns no records (-c, count-only) and one with max_count == 0 launch none. */
+void krep_gpu_debug_batch_cut_launches(uint64_t *lds_table, uint64_t *global_table);
 /* the sibling of krep_gpu_debug_batch_times() for krep_gpu_grep_batch(): where the calling thread's last call spent its time, in
  * milliseconds of wall clock — pack, scan and segmentation as above; format: the ordering of a multi-pattern list, the upload of the
  * prefixes and the formatter over the pack; readback: the copies of the bytes, the item offsets and the counts (tools/batch_grep_bench.py) */

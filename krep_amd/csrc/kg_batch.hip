@@ -7,6 +7,12 @@
 //                    relative to the item's first byte
 //   batch_line_flags -c: 1 where a record's line differs from its predecessor's; an exclusive sum over the flags makes an item's
 //                    distinct-line count the difference at its two bounds (no loop per item: one item may hold every record)
+// under a max_count (krep_gpu_set_batch_max_count; the rule: batch_cut_rule) the same bounds, then the cut, then the order:
+//   batch_bounds_cut one thread per item: count and the records KEPT from the rule; an exclusive sum over the kept numbers
+//   batch_first      one thread per item: first_record from that sum
+//   batch_cut        one thread per KEPT record: its item by binary search over the summed kept numbers (in LDS when they fit), its
+//                    source through the inverse of memchr_search's flush map, 16 B in and 16 B out into a second list — rebased
+//                    (krep_gpu_search_batch) or pack-relative (krep_gpu_grep_batch)
 // and the rule that says when all this is exact (kg::batch_unsupported_reason: newline-separable searches only).
 // krep_gpu_grep_batch (at the end of the file) is the same walk over the packs with one step more per pack: the pack is
 // formatted where it lies (kg_batch_format.hip) and the printed bytes are read back instead of the records.
@@ -91,10 +97,114 @@ __global__ void __launch_bounds__(256) batch_line_flags(const u64 *__restrict__ 
         flags[k] = (k == 0 || lines[k] != lines[k - 1]) ? 1 : 0;
 }
 
+// ---- under a max_count: the rule per item, then the kept records into a second list
+// (a') batch_bounds with the cut: res[i] = {count, (first_record: batch_first), kept}; keep[i] = kept, lo[i] = the item's first record in
+// the uncut list.  Thread n_items writes the closing entries (keep 0, lo n_rec), so that sum[n_items] is the kept total.
+__global__ void __launch_bounds__(256) batch_bounds_cut(const u64 *__restrict__ rec, u64 n_rec, const u64 *__restrict__ off, u64 n_items,
+                                                        int records, const u64 *__restrict__ prefix, const u64 *__restrict__ flags,
+                                                        const BatchCut cut, u64 *__restrict__ res, u64 *__restrict__ keep,
+                                                        u64 *__restrict__ lo_out)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_items)
+        return;
+    if (i == n_items)
+    {
+        keep[i] = 0;
+        lo_out[i] = n_rec;
+        return;
+    }
+    const u64 lo = first_record_at(rec, n_rec, off[i]), hi = first_record_at(rec, n_rec, off[i + 1]);
+    const u64 T = hi - lo;
+    u64 have = T;
+    if (prefix && n_rec)
+    {
+        const u64 total = prefix[n_rec - 1] + flags[n_rec - 1];
+        have = (hi < n_rec ? prefix[hi] : total) - (lo < n_rec ? prefix[lo] : total);
+    }
+    u64 count = min(have, cut.m), kept = 0;
+    if (cut.m == 0)
+        count = (cut.zero_one && T > 0) ? 1 : 0;
+    else if (records)
+        kept = min(T, cut.m) + (T > cut.m ? (u64)cut.extra : 0ull);
+    res[3 * i] = count;
+    res[3 * i + 2] = kept;
+    keep[i] = kept;
+    lo_out[i] = lo;
+}
+
+// (a'') first_record = rec_base + the kept records of the items in front
+__global__ void __launch_bounds__(256) batch_first(const u64 *__restrict__ new_first, u64 n_items, u64 rec_base, int report,
+                                                   u64 *__restrict__ res)
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_items)
+        res[3 * i + 1] = report ? rec_base + new_first[i] : rec_base;
+}
+
+// (b') kept record d of the pack: its item is the last i with new_first[i] <= d (an item that keeps nothing shares its entry with
+// its successor and is never the last), its place in the item j = d - new_first[i], its source lo[i] + the inverse of the flush map.
+// LDS: new_first[0 .. n_items] fits kBatchLdsItems entries.  REBASE: relative to the item's first byte (what batch_rebase does), in
+// the search's order; else pack-relative with the displaced record where its start puts it (the item's last place).
+template <bool LDS, bool REBASE>
+__global__ void __launch_bounds__(256) batch_cut(const u64 *__restrict__ rec, u64 n_rec, u64 *__restrict__ dst, u64 room,
+                                                 const u64 *__restrict__ new_first, const u64 *__restrict__ lo_tab,
+                                                 const u64 *__restrict__ off, u64 n_items, const BatchCut cut)
+{
+    __shared__ u64 s_first[LDS ? kBatchLdsItems : 1];
+    // the grid covers `room` (the host's bound, what dst holds); a workgroup behind the kept total leaves before it stages anything
+    const u64 n_kept = min(new_first[n_items], room);
+    if ((u64)blockIdx.x * kRebasePerBlock >= n_kept)
+        return;
+    if (LDS)
+    {
+        for (u32 t = threadIdx.x; t <= (u32)n_items; t += blockDim.x)
+            s_first[t] = new_first[t];
+        __syncthreads();
+    }
+    const u64 *tab = LDS ? s_first : new_first;
+    const u64 k0 = (u64)blockIdx.x * kRebasePerBlock, k1 = k0 + kRebasePerBlock < n_kept ? k0 + kRebasePerBlock : n_kept;
+    for (u64 d = k0 + threadIdx.x; d < k1; d += blockDim.x)
+    {
+        u64 lo = 0, hi = n_items; // tab[lo] <= d < tab[hi] (tab[0] = 0, tab[n_items] = n_kept > d)
+        while (hi - lo > 1)
+        {
+            const u64 mid = lo + (hi - lo) / 2;
+            if (tab[mid] <= d)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const u64 j = d - tab[lo], first = lo_tab[lo], T = lo_tab[lo + 1] - first;
+        u64 src = j;
+        if (cut.displace && T > cut.m)
+        {
+            if (REBASE)
+            { // R[0 .. m-4096), R[m], R[m-4096 .. m-1)
+                const u64 f = cut.m - 4096;
+                src = j < f ? j : j == f ? cut.m : j - 1;
+            }
+            else // R[0 .. m-1), R[m]
+                src = j + 1 == cut.m ? cut.m : j;
+        }
+        src += first;
+        if (src >= n_rec) // (cannot happen: src - first < T by the rule)
+            continue;
+        uint4 r = *reinterpret_cast<const uint4 *>(rec + 2 * src);
+        if (REBASE)
+        {
+            const u64 base = off[lo], st = (((u64)r.y << 32) | r.x) - base, e = (((u64)r.w << 32) | r.z) - base;
+            r.x = (u32)st; r.y = (u32)(st >> 32); r.z = (u32)e; r.w = (u32)(e >> 32);
+        }
+        *reinterpret_cast<uint4 *>(dst + 2 * d) = r;
+    }
+}
+
 std::atomic<size_t> g_pack_limit{0};                // krep_gpu_debug_batch_pack_limit
 thread_local double tl_batch_ms[4] = {0, 0, 0, 0}; // krep_gpu_debug_batch_times
 thread_local double tl_grep_ms[5] = {0, 0, 0, 0, 0}; // krep_gpu_debug_grep_batch_times: pack, scan, segment, format, read-back
 std::atomic<uint64_t> g_rebase_lds{0}, g_rebase_global{0}; // krep_gpu_debug_batch_rebase_launches
+std::atomic<uint64_t> g_cut_lds{0}, g_cut_global{0};       // krep_gpu_debug_batch_cut_launches
 
 bool holds_newline(const uint8_t cls[32]) { return (cls['\n' >> 3] >> ('\n' & 7)) & 1; }
 } // namespace
@@ -102,14 +212,26 @@ bool holds_newline(const uint8_t cls[32]) { return (cls['\n' >> 3] >> ('\n' & 7)
 void batch_scratch_free(BatchScratch &s)
 {
     for (void *p : {(void *)s.d_off, (void *)s.d_res, (void *)s.d_lines, (void *)s.d_flags, (void *)s.d_prefix, (void *)s.d_sums,
-                    (void *)s.d_pfx, (void *)s.d_pfx_off, (void *)s.d_item_out, (void *)s.d_out})
+                    (void *)s.d_pfx, (void *)s.d_pfx_off, (void *)s.d_item_out, (void *)s.d_out, (void *)s.d_keep, (void *)s.d_new_first,
+                    (void *)s.d_lo, (void *)s.d_cut_sums, (void *)s.d_cut})
         if (p)
             (void)hipFree(p);
     s = BatchScratch{};
 }
 
+int batch_kept_total(const BatchScratch &s, uint64_t n_items, uint64_t n_rec, uint64_t *n_kept)
+{
+    u64 kept = 0;
+    HIPCHK(hipMemcpy(&kept, s.d_new_first + n_items, sizeof kept, hipMemcpyDeviceToHost));
+    if (kept > n_rec)
+        return fail("batch: the cut keeps %llu of %llu records", (unsigned long long)kept, (unsigned long long)n_rec);
+    *n_kept = kept;
+    return 0;
+}
+
 int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const uint64_t *h_off, uint64_t n_items, match_position_t *d_pos,
-                  uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st)
+                  uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st, const BatchCut *cut,
+                  BatchCutOut form)
 {
     if (!n_items)
         return 0;
@@ -140,6 +262,43 @@ int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const
         prefix = s.d_prefix;
         flags = s.d_flags;
     }
+    if (cut)
+    { // bounds in emission order, then the cut, then (the caller's) order
+        const bool records = form != BatchCutOut::None && !lines;
+        const uint64_t want = std::max<uint64_t>(n_items + n_items / 2, 1024);
+        HIPCHK(grow_scratch(s.cut_items_cap, n_items, want,
+                            {dev_buf(s.d_keep, (want + 2) * sizeof(u64)), dev_buf(s.d_new_first, (want + 2) * sizeof(u64)),
+                             dev_buf(s.d_lo, (want + 2) * sizeof(u64)), dev_buf(s.d_cut_sums, (scan_sums_words(want + 2) + 1) * sizeof(u64))}));
+        const u32 grid_i = (u32)((n_items + 1 + 255) / 256);
+        hipLaunchKernelGGL(batch_bounds_cut, dim3(grid_i), dim3(256), 0, st, (const u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off, (u64)n_items,
+                           records ? 1 : 0, prefix, flags, *cut, s.d_res, s.d_keep, s.d_lo);
+        scan_exclusive(s.d_keep, n_items + 1, s.d_new_first, s.d_cut_sums, false, st);
+        hipLaunchKernelGGL(batch_first, dim3(grid_i), dim3(256), 0, st, (const u64 *)s.d_new_first, (u64)n_items, (u64)rec_base,
+                           report ? 1 : 0, s.d_res);
+        HIPCHK(hipGetLastError());
+        // the kept records are at most `room`: the buffer and the grid are sized by that bound, the kernel reads the kept total itself
+        // (no wait between the sum and the cut; the host reads the total behind the segmentation, batch_kept_total)
+        const u64 per_item = cut->m + cut->extra, room = (per_item && n_items > n_rec / per_item) ? n_rec : n_items * per_item;
+        if (!records || !n_rec || !room)
+            return 0;
+        {
+            const uint64_t cap = std::max<uint64_t>(room + room / 2, 1u << 12);
+            HIPCHK(grow_scratch(s.cut_cap, room, cap, {dev_buf(s.d_cut, cap * sizeof(match_position_t))}));
+        }
+        const u32 grid = (u32)((room + kRebasePerBlock - 1) / kRebasePerBlock);
+        const bool lds = n_items + 1 <= kBatchLdsItems, rebase = form == BatchCutOut::Rebased;
+        (lds ? g_cut_lds : g_cut_global).fetch_add(1, std::memory_order_relaxed);
+#define KG_BATCH_CUT(L, R)                                                                                                              \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(batch_cut<L, R>), dim3(grid), dim3(256), 0, st, (const u64 *)d_pos, (u64)n_rec, (u64 *)s.d_cut, (u64)room, \
+                       (const u64 *)s.d_new_first, (const u64 *)s.d_lo, (const u64 *)s.d_off, (u64)n_items, *cut)
+        if (lds && rebase) KG_BATCH_CUT(true, true);
+        else if (lds) KG_BATCH_CUT(true, false);
+        else if (rebase) KG_BATCH_CUT(false, true);
+        else KG_BATCH_CUT(false, false);
+#undef KG_BATCH_CUT
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     hipLaunchKernelGGL(batch_bounds, dim3((u32)((n_items + 255) / 256)), dim3(256), 0, st, (const u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off,
                        (u64)n_items, (u64)rec_base, report ? 1 : 0, prefix, flags, s.d_res);
     if (report && !lines && n_rec)
@@ -163,7 +322,8 @@ const char *batch_unsupported_reason(const search_params_t *p, const krep_gpu_co
 {
     if (const char *why = unsupported_reason(p, c))
         return why;
-    if (p->max_count != SIZE_MAX)
+    const bool cutting = p->max_count != SIZE_MAX;
+    if (cutting && !g_batch_max_count.load(std::memory_order_relaxed))
         return "batch: max_count is a property of each item's own record list; cutting per item is follow-up work";
     if (p->use_regex)
     {
@@ -221,7 +381,33 @@ const char *batch_unsupported_reason(const search_params_t *p, const krep_gpu_co
     if (algo == KREP_RA_MEMCHR_SHORT && om && m >= 3)
         return "batch: memchr_short_search under -o skips pattern_len bytes behind a failed candidate too (krep.c:4495): with a 3-byte "
                "pattern a candidate on the last byte of an item steps over the first byte of the next one";
+    if (cutting && q->max_count == 0 && algo == KREP_RA_NEON)
+        return "batch: max_count == 0 through neon_search: a count-only search hands the TEXT's last length % 16 bytes to "
+               "boyer_moore_search, whose first hit answers 1 (krep.c:4516, :1355-1367): an item's answer depends on where the item ends";
+    if (cutting && q->max_count == 0 && algo == KREP_RA_AVX2 && !lines && !q->track_positions)
+        return "batch: max_count == 0, count-only, through simd_avx2_search: a hit in the block body answers 1, a hit in the scalar tail "
+               "is capped back to 0 (krep.c:5036, :5066-5093), and where that tail begins depends on the whole text's length";
     return nullptr;
+}
+
+// The cut of one item's list as a function of (params, cfg): the reference function is taken as batch_unsupported_reason takes it, and
+// every field is read off the scans' own verdict (verdict_rule) and memchr_batch_quirk's predicate — probes, not a second table.
+// search_file_cap: krep_gpu_grep_batch repeats search_file() behind the function (krep.c:2954-2981, :3018-3026): the list and the
+// count are capped at max_count there, so kmp_search's extra record and the count-only 1 at max_count == 0 go.
+BatchCut batch_cut_rule(const search_params_t *p, const krep_gpu_config_t &c, bool search_file_cap)
+{
+    const int algo = mirror_effective(mirror_top(p, c), p, p->pattern_len);
+    const size_t m = p->max_count;
+    BatchCut k{};
+    k.m = m;
+    if (!search_file_cap)
+    {
+        k.zero_one = (uint32_t)verdict_rule(algo, 0, p->count_lines_mode, p->track_positions, 1, 1, true).ret;
+        const Verdict over = verdict_rule(algo, 1, false, true, 2, 2, true); // one record beyond max_count
+        k.extra = (uint32_t)(over.store - over.ret);
+    }
+    k.displace = algo == KREP_RA_MEMCHR && memchr_flush_displaces((uint64_t)m + 1, m) ? 1 : 0;
+    return k;
 }
 } // namespace kg
 
@@ -238,6 +424,12 @@ extern "C" void krep_gpu_debug_batch_rebase_launches(uint64_t *lds_table, uint64
 {
     if (lds_table) *lds_table = g_rebase_lds.load();
     if (global_table) *global_table = g_rebase_global.load();
+}
+
+extern "C" void krep_gpu_debug_batch_cut_launches(uint64_t *lds_table, uint64_t *global_table)
+{
+    if (lds_table) *lds_table = g_cut_lds.load();
+    if (global_table) *global_table = g_cut_global.load();
 }
 
 extern "C" int krep_gpu_debug_batch_fill_host(const krep_gpu_batch_item_t *items, size_t n, size_t lo, size_t cnt, void *dst)
@@ -305,6 +497,9 @@ extern "C" int krep_gpu_search_batch(const search_params_t *raw, const krep_gpu_
     scan.count_lines_mode = false;
     scan.track_positions = true;
     scan.max_count = SIZE_MAX;
+    // a finite max_count (the switch is on: the refusal above): the unlimited list is cut per item behind the scan
+    const bool cutting = params->max_count != SIZE_MAX;
+    const BatchCut cut = cutting ? kg::batch_cut_rule(params, cfg, false) : BatchCut{};
     const size_t chunk = cfg.stream_chunk_bytes ? cfg.stream_chunk_bytes : ((size_t)128 << 20);
     const size_t limit = g_pack_limit.load() ? g_pack_limit.load() : 2 * chunk;
     DeviceGuard guard;
@@ -315,17 +510,17 @@ extern "C" int krep_gpu_search_batch(const search_params_t *raw, const krep_gpu_
     {
         // the next pack: items [i0, i1), cut between items and never inside one (an item beyond the limit is a pack of its own)
         const size_t i1 = i0 + kg::batch_pack_offsets(items + i0, n_items - i0, limit, off);
-        uint64_t n_rec = 0;
+        uint64_t n_rec = 0, n_kept = 0;
         float kms = 0;
         if (kg::host_batch_pack(&scan, cfg, items + i0, i1 - i0, off.data(), lines, report, records, appended, res.data() + i0, &n_rec, &kms,
-                                tl_batch_ms))
+                                tl_batch_ms, nullptr, cutting ? &cut : nullptr, report ? BatchCutOut::Rebased : BatchCutOut::None, &n_kept))
             return 2; // (records->count was never moved: nothing is appended)
         bi.packed_bytes += off.back() - 1;
         bi.scans += 1;
         bi.total_records += n_rec;
         bi.kernel_ms += kms;
         if (report)
-            appended += n_rec;
+            appended += cutting ? n_kept : n_rec;
         i0 = i1;
     }
     memcpy(results, res.data(), n_items * sizeof *results);
@@ -417,6 +612,9 @@ extern "C" int krep_gpu_grep_batch(const search_params_t *raw, const krep_gpu_co
     scan.count_lines_mode = false;
     scan.track_positions = true;
     scan.max_count = SIZE_MAX;
+    // a finite max_count (the switch is on): search_file()'s cut per item; the formatters below see the kept list only
+    const bool cutting = params->max_count != SIZE_MAX;
+    const BatchCut cut = cutting ? kg::batch_cut_rule(params, cfg, true) : BatchCut{};
     const size_t chunk = cfg.stream_chunk_bytes ? cfg.stream_chunk_bytes : ((size_t)128 << 20);
     const size_t limit = g_pack_limit.load() ? g_pack_limit.load() : 2 * chunk;
     DeviceGuard guard;
@@ -499,7 +697,8 @@ extern "C" int krep_gpu_grep_batch(const search_params_t *raw, const krep_gpu_co
         float kms = 0;
         double ms[4] = {0, 0, 0, 0};
         if (kg::host_batch_pack(&scan, cfg, items + i0, i1 - i0, off.data(), count_mode && params->count_lines_mode, false, nullptr, 0,
-                                res.data() + i0, &n_rec, &kms, ms, count_mode ? nullptr : &format))
+                                res.data() + i0, &n_rec, &kms, ms, count_mode ? nullptr : &format, cutting ? &cut : nullptr,
+                                count_mode ? BatchCutOut::None : BatchCutOut::PackSorted))
             return 2; // (out->len was never moved: nothing is appended)
         tl_grep_ms[0] += ms[0], tl_grep_ms[1] += ms[1], tl_grep_ms[2] += ms[2], tl_grep_ms[4] += ms[3];
         bi.packed_bytes += off.back() - 1;

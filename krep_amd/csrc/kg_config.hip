@@ -268,6 +268,17 @@ extern "C" void krep_gpu_debug_regex_loops_roads(uint64_t *sparse, uint64_t *den
     if (sparse) *sparse = kg::g_rl_sparse.load();
     if (dense) *dense = kg::g_rl_dense.load();
 }
+// The batch's per-item max_count cut behind a switch of the same kind (include/krep_gpu.h, krep_gpu_set_batch_max_count)
+static int env_batch_max_count()
+{
+    const char *e = getenv("KREP_GPU_BATCH_MAX_COUNT");
+    return e && *e && atoi(e) != 0 ? 1 : 0;
+}
+namespace kg {
+std::atomic<int> g_batch_max_count{env_batch_max_count()}; // (read when the library is loaded)
+}
+extern "C" void krep_gpu_set_batch_max_count(int on) { kg::g_batch_max_count.store(on != 0, std::memory_order_relaxed); }
+extern "C" int krep_gpu_get_batch_max_count(void) { return kg::g_batch_max_count.load(std::memory_order_relaxed); }
 namespace kg {
 extern int g_s1_force_grid;
 std::atomic<uint64_t> g_fused1_failovers{0}; // one-pass single-byte scans that handed over to the two-pass kernels

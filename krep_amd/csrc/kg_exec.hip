@@ -449,7 +449,7 @@ DeviceCtx *ctx_for(int device)
 // matches exist, the (max_count+1)-th record is stored FIRST (in front of the last batch) and the max_count-th is dropped.
 void memchr_batch_quirk(match_position_t *recs, uint64_t have, size_t maxc)
 {
-    if (maxc == SIZE_MAX || maxc == 0 || have <= maxc || (maxc % 4096) != 0)
+    if (!memchr_flush_displaces(have, maxc))
         return;
     const uint64_t f = maxc - 4096;
     match_position_t extra = recs[maxc];
@@ -1127,7 +1127,8 @@ int host_scan(const search_params_t *params, const krep_gpu_config_t &cfg, const
 // overflowed, as the operators do), the list cut per item on the device, results and rebased records read back in one copy each.
 int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t &cfg, const krep_gpu_batch_item_t *items, size_t n,
                     const uint64_t *off, bool lines, bool report, match_result_t *records, uint64_t appended,
-                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms, const BatchStep *step)
+                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms, const BatchStep *step,
+                    const BatchCut *cut, BatchCutOut form, uint64_t *n_kept_out)
 {
     using clk = std::chrono::steady_clock;
     const auto since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
@@ -1165,21 +1166,29 @@ int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t 
     const uint64_t n_rec = so.stored;
     *kernel_ms = so.kernel_ms;
     const uint64_t rec_base = (records ? records->count : 0) + (report ? appended : 0);
-    if (batch_segment(cx.batch, d_text, packed, off, n, d_pos, n_rec, rec_base, pl->ref_algo == KREP_RA_AHO_CORASICK, lines, report, nullptr))
+    uint64_t n_kept = 0; // under a cut: the records of cx.batch.d_cut, the list every later step works on
+    if (batch_segment(cx.batch, d_text, packed, off, n, d_pos, n_rec, rec_base, pl->ref_algo == KREP_RA_AHO_CORASICK, lines, report, nullptr,
+                      cut, form))
         return 2;
     HIPCHK(hipStreamSynchronize(nullptr));
+    if (cut && form != BatchCutOut::None && !lines && n_rec && cut->m && batch_kept_total(cx.batch, n, n_rec, &n_kept))
+        return 2;
     ms[2] += since(t0);
-    if (step && (*step)(BatchPackOnDevice{cx.batch, d_text, packed, cx.batch.d_off, n, d_pos, n_rec,
+    match_position_t *const d_list = cut ? cx.batch.d_cut : d_pos;
+    const uint64_t n_list = cut ? n_kept : n_rec;
+    if (n_kept_out)
+        *n_kept_out = n_kept;
+    if (step && (*step)(BatchPackOnDevice{cx.batch, d_text, packed, cx.batch.d_off, n, d_list, n_list,
                                           pl->ref_algo == KREP_RA_AHO_CORASICK})) // (its time is its own)
         return 2;
     t0 = clk::now();
     if (kg::inject(4) || hipMemcpy(res_out, cx.batch.d_res, n * sizeof *res_out, hipMemcpyDeviceToHost) != hipSuccess)
         return kg::fail("D2H copy of the batch results failed");
-    if (report && n_rec)
+    if (report && n_list)
     {
-        if (!result_reserve(records, appended + n_rec))
+        if (!result_reserve(records, appended + n_list))
             return kg::fail("out of memory growing match_result_t");
-        if (records_to_host(records->positions + records->count + appended, d_pos, n_rec))
+        if (records_to_host(records->positions + records->count + appended, d_list, n_list))
             return 2;
     }
     ms[3] += since(t0);

@@ -215,6 +215,7 @@ int ac_scan(const AcScan &c, krep_gpu_scan_out_t *out);
 extern std::atomic<int> g_force_rounds, g_force_stage_cap;   // krep_gpu_debug_force_rounds / _stage_cap
 extern std::atomic<int> g_rx_force_grid;                     // krep_gpu_debug_force_regex_grid: at most this many workgroups (0 = auto)
 extern std::atomic<int> g_regex_loops;                       // krep_gpu_set_regex_loops: a search asks the loops compiler too
+extern std::atomic<int> g_batch_max_count;                   // krep_gpu_set_batch_max_count: the batch takes a finite max_count
 extern std::atomic<int> g_rl_force_road;                     // krep_gpu_debug_force_regex_loops_road: 0 auto, 1 sparse, 2 dense
 extern std::atomic<uint64_t> g_rl_sparse, g_rl_dense;        // scans of kg_regex_loops.hip that took each road
 extern std::atomic<uint64_t> g_tiny_launches;                // launches of ac_tiny_kernel (kg_ac_tiny.hip)
@@ -252,6 +253,58 @@ inline bool by_start_end(const match_position_t &a, const match_position_t &b) /
     return a.start_offset != b.start_offset ? a.start_offset < b.start_offset : a.end_offset < b.end_offset;
 }
 bool have_error();
+
+// What the reference function returns / stores given the number of emitted matches (`total`, after greedy selection and -w) or
+// distinct lines.  One place for all the max_count corner cases: the scans ask it with their plan (kg_scan.hip verdict_for), the
+// batch derives its per-item cut from it (kg_batch.hip batch_cut_rule).
+struct Verdict { uint64_t ret, store; };
+inline Verdict verdict_rule(int algo, size_t maxc, bool lines, bool track, uint64_t total, uint64_t nlines, bool have_result)
+{
+    const bool store = track && have_result;
+    Verdict v{0, 0};
+    switch (algo)
+    {
+    case KREP_RA_MEMCHR: // krep.c:3897, :3955, :3976
+    case KREP_RA_KMP:    // krep.c:1634, :1696, :1717
+    case KREP_RA_AHO_CORASICK: // aho_corasick.c:316
+    case KREP_RA_SSE42: // :4713 then the pre-increment checks :4778/:4804
+        if (maxc == 0)
+            return v;
+        break;
+    case KREP_RA_NEON: // :4516 then the pre-increment checks :4582/:4616; count-only with max_count == 0 is resolved by
+                       // the caller (the tail call's BMH convention, lit_neon_zero)
+        if (maxc == 0)
+            return v;
+        break;
+    default: // BMH :1266, memchr_short :4376, AVX2 :4887, AVX-512 :5119
+        if (maxc == 0)
+        {
+            if (lines || track)
+                return v;
+            v.ret = total > 0 ? 1 : 0; // count-only: the first hit makes 1 >= 0 true (krep.c:1355-1367)
+            return v;
+        }
+    }
+    if (lines)
+    {
+        v.ret = nlines < maxc ? nlines : maxc;
+        return v;
+    }
+    v.ret = total < maxc ? total : maxc;
+    if (store)
+    {
+        v.store = v.ret;
+        if (algo == KREP_RA_KMP && maxc != SIZE_MAX && total > maxc)
+            v.store = v.ret + 1; // krep.c:1717-1724 stores the (max_count+1)-th match before breaking
+    }
+    return v;
+}
+// memchr_search's final flush (krep.c:3976-3991 + :4026-4038) displaces a record of a list of `have` under max_count `maxc`
+// (kg_exec.hip memchr_batch_quirk moves it; the batch's cut reads through the same map)
+inline bool memchr_flush_displaces(uint64_t have, size_t maxc)
+{
+    return !(maxc == SIZE_MAX || maxc == 0 || have <= maxc || (maxc % 4096) != 0);
+}
 
 // kg_format.hip — what the formatter-side entry points share: the scratch, the scan and the newline table below; the host steps of
 // the grep-output drivers (entry checks, format strings, the cursor over the scratch, the output tail) are declared in kg_format_host.h
@@ -356,14 +409,36 @@ struct BatchScratch // grow-only, one per device context
     uint64_t grep_items_cap = 0;
     unsigned char *d_out = nullptr;
     uint64_t out_cap = 0;
+    // a batch under max_count (BatchCut): per item [items + 2] the records kept, their exclusive sum (entry `items`: the kept total)
+    // and the item's first record in the uncut list (entry `items`: n_rec); the scratch of that sum; the kept records
+    unsigned long long *d_keep = nullptr, *d_new_first = nullptr, *d_lo = nullptr, *d_cut_sums = nullptr;
+    uint64_t cut_items_cap = 0;
+    match_position_t *d_cut = nullptr;
+    uint64_t cut_cap = 0;
 };
 void batch_scratch_free(BatchScratch &s);
+// The per-item cut of a pack's record list under max_count (krep_gpu_set_batch_max_count), as the kernels take it.
+// For item i: T its records in the uncut list, Ln its distinct lines.  count = min(Ln, m) under -c, else min(T, m), and with m == 0:
+// zero_one && T > 0.  Kept: min(T, m) records, `extra` more when T > m (kmp_search), none when m == 0; `displace`: memchr_search's
+// flush map applies when T > m.  batch_cut_rule derives every field from verdict_rule / memchr_flush_displaces.
+struct BatchCut
+{
+    unsigned long long m;
+    uint32_t zero_one, extra, displace;
+};
+enum class BatchCutOut { None, Rebased, PackSorted }; // no records; the search's list per item; the grep list (start order within an item's single-pattern list)
+BatchCut batch_cut_rule(const search_params_t *p, const krep_gpu_config_t &c, bool search_file_cap);
 // The record list of one pack (n_rec records in d_pos, the reference's emission order; by_end: a multi-pattern list) cut into the
 // n_items results of s.d_res on `st` (not synchronised): first_record = rec_base + the item's first index when `report`, else rec_base
 // with n_records = 0; lines: count = the distinct lines of the item's record starts, the list is ordered by start on the way and not
 // rebased; else count = the item's records and, with `report`, every record is rebased to its item's first byte.  h_off: the table above.
+// cut (NULL: none, and nothing below is touched): the rule above applied per item; `form` says whether the kept records are written to
+// s.d_cut (Rebased: as `report` rebases them; PackSorted: pack-relative, the displaced memchr record at its place by start).
+// first_record / n_records then describe the kept list; batch_kept_total reads its length once the stream has been waited for.
 int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const uint64_t *h_off, uint64_t n_items, match_position_t *d_pos,
-                  uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st);
+                  uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st, const BatchCut *cut = nullptr,
+                  BatchCutOut form = BatchCutOut::None);
+int batch_kept_total(const BatchScratch &s, uint64_t n_items, uint64_t n_rec, uint64_t *n_kept); // (a cut with records, n_rec > 0)
 // (the next pack of a batch on the host — its offset table, the bytes of any slice of it: kg_batch_pack.h, batch_pack_offsets / batch_fill)
 // kg_exec.hip — one pack through the device context of cfg.device: gathered through the staging ring into the arena, scanned in one
 // window with the records plan `scan_params`, segmented, read back.  res_out[n]: the items' results; with `report` the rebased records go
@@ -378,14 +453,15 @@ struct BatchPackOnDevice
     uint64_t packed;
     const unsigned long long *d_off; // [n_items + 1], as BatchScratch::d_off
     uint64_t n_items;
-    match_position_t *d_pos; // pack-relative, in emission order (by_end: a multi-pattern list, ascending in end)
+    match_position_t *d_pos; // pack-relative, in emission order (by_end: a multi-pattern list, ascending in end); under a cut: the kept list
     uint64_t n_rec;
     bool by_end;
 };
 using BatchStep = std::function<int(const BatchPackOnDevice &)>;
 int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t &cfg, const krep_gpu_batch_item_t *items, size_t n,
                     const uint64_t *off, bool lines, bool report, match_result_t *records, uint64_t appended,
-                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms, const BatchStep *step = nullptr);
+                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms, const BatchStep *step = nullptr,
+                    const BatchCut *cut = nullptr, BatchCutOut form = BatchCutOut::None, uint64_t *n_kept_out = nullptr);
 
 // kg_batch_format.hip — the formatters over a pack behind krep_gpu_format_lines_items / krep_gpu_format_matches_items.  grow (NULL:
 // none): asked for the output buffer once the size is known (-> a device buffer of at least that many bytes, NULL: it failed and said

@@ -24,48 +24,10 @@ using namespace kg;
 // ------------------------------------------------------------------------------------ reference return-value conventions
 // What the reference function returns / stores given the number of emitted matches (`total`, after
 // greedy selection and -w) or distinct lines.  One place for all the max_count corner cases.
-struct Verdict { uint64_t ret, store; };
+// (the rule itself is kg::verdict_rule, kg_internal.h: the batch's per-item cut is derived from the same function)
 static Verdict verdict_for(int algo, const krep_gpu_plan *pl, uint64_t total, uint64_t lines, bool have_result)
 {
-    const size_t maxc = pl->max_count;
-    const bool store = pl->track && have_result;
-    Verdict v{0, 0};
-    switch (algo)
-    {
-    case KREP_RA_MEMCHR: // krep.c:3897, :3955, :3976
-    case KREP_RA_KMP:    // krep.c:1634, :1696, :1717
-    case KREP_RA_AHO_CORASICK: // aho_corasick.c:316
-    case KREP_RA_SSE42: // :4713 then the pre-increment checks :4778/:4804
-        if (maxc == 0)
-            return v;
-        break;
-    case KREP_RA_NEON: // :4516 then the pre-increment checks :4582/:4616; count-only with max_count == 0 is resolved by
-                       // the caller (the tail call's BMH convention, lit_neon_zero)
-        if (maxc == 0)
-            return v;
-        break;
-    default: // BMH :1266, memchr_short :4376, AVX2 :4887, AVX-512 :5119
-        if (maxc == 0)
-        {
-            if (pl->lines || pl->track)
-                return v;
-            v.ret = total > 0 ? 1 : 0; // count-only: the first hit makes 1 >= 0 true (krep.c:1355-1367)
-            return v;
-        }
-    }
-    if (pl->lines)
-    {
-        v.ret = std::min<uint64_t>(lines, maxc);
-        return v;
-    }
-    v.ret = std::min<uint64_t>(total, maxc);
-    if (store)
-    {
-        v.store = v.ret;
-        if (algo == KREP_RA_KMP && maxc != SIZE_MAX && total > maxc)
-            v.store = v.ret + 1; // krep.c:1717-1724 stores the (max_count+1)-th match before breaking
-    }
-    return v;
+    return verdict_rule(algo, pl->max_count, pl->lines, pl->track, total, lines, have_result);
 }
 
 int kg::stop_clock(krep_gpu_plan *pl, bool record_ev1, hipStream_t st, krep_gpu_scan_out_t *out)

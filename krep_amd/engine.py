@@ -215,6 +215,13 @@ class Engine:
             L.krep_gpu_debug_batch_fill_host.argtypes = [C.POINTER(abi.BatchItem), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
             L.krep_gpu_debug_batch_rebase_launches.restype = None
             L.krep_gpu_debug_batch_rebase_launches.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "krep_gpu_set_batch_max_count"):  # (likewise)
+            L.krep_gpu_set_batch_max_count.restype = None
+            L.krep_gpu_set_batch_max_count.argtypes = [C.c_int]
+            L.krep_gpu_get_batch_max_count.restype = C.c_int
+            L.krep_gpu_get_batch_max_count.argtypes = []
+            L.krep_gpu_debug_batch_cut_launches.restype = None
+            L.krep_gpu_debug_batch_cut_launches.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         if hasattr(L, "krep_gpu_grep_batch"):  # (likewise)
             L.krep_gpu_format_lines_items.restype = C.c_int
             L.krep_gpu_format_lines_items.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(abi.PackView), C.c_void_p, C.c_uint64,
@@ -654,6 +661,20 @@ class Engine:
     def batch_can_accelerate(self, params: abi.Params) -> bool:
         """krep_gpu_batch_can_accelerate(): is the search newline-separable (and taken at all); last_error() says why not."""
         return bool(self.lib.krep_gpu_batch_can_accelerate(params.ref))
+
+    def set_batch_max_count(self, on: bool):
+        """krep_gpu_set_batch_max_count: whether the batch calls take a finite params.max_count and cut every item's record list on
+        the device (process-wide, off by default: a batch with max_count is refused then)"""
+        self.lib.krep_gpu_set_batch_max_count(1 if on else 0)
+
+    def get_batch_max_count(self) -> bool:
+        return bool(self.lib.krep_gpu_get_batch_max_count())
+
+    def batch_cut_launches(self):
+        """(with the summed kept-record table in LDS, with the table in global memory): launches of the batch's max_count cut so far"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self.lib.krep_gpu_debug_batch_cut_launches(C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
 
     def batch_pack_limit(self, nbytes: int):
         """test hook: the packed size at which a batch is cut into a further pack (0: the default)"""
