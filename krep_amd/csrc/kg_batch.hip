@@ -13,15 +13,19 @@
 //   batch_cut        one thread per KEPT record: its item by binary search over the summed kept numbers (in LDS when they fit), its
 //                    source through the inverse of memchr_search's flush map, 16 B in and 16 B out into a second list — rebased
 //                    (krep_gpu_search_batch) or pack-relative (krep_gpu_grep_batch)
-// and the rule that says when all this is exact (kg::batch_unsupported_reason: newline-separable searches only).
-// krep_gpu_grep_batch (at the end of the file) is the same walk over the packs with one step more per pack: the pack is
-// formatted where it lies (kg_batch_format.hip) and the printed bytes are read back instead of the records.
+// launched by batch_segment in steps (segment_reserve, segment_line_prefix, then segment_cut or segment_plain to its end), and the rule
+// that says when all this is exact (kg::batch_unsupported_reason: newline-separable searches only).
+// Both calls are one walk (BatchWalk): enter — the refusals both share, in one order — the call's own checks, the
+// device, then per pack next() and pack() (kg_exec.hip host_batch_pack), then the call's commit of its results at the very end.
+// krep_gpu_grep_batch gives every pack one step more: the pack is formatted where it lies (grep_format_pack over
+// kg_batch_format.hip) and the printed bytes are read back instead of the records; under -c grep_print_counts prints on the host.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 #include "../../include/krep_gpu.h"
@@ -200,13 +204,107 @@ __global__ void __launch_bounds__(256) batch_cut(const u64 *__restrict__ rec, u6
     }
 }
 
-std::atomic<size_t> g_pack_limit{0};                // krep_gpu_debug_batch_pack_limit
-thread_local double tl_batch_ms[4] = {0, 0, 0, 0}; // krep_gpu_debug_batch_times
-thread_local double tl_grep_ms[5] = {0, 0, 0, 0, 0}; // krep_gpu_debug_grep_batch_times: pack, scan, segment, format, read-back
+std::atomic<size_t> g_pack_limit{0};                       // krep_gpu_debug_batch_pack_limit
+thread_local BatchTimes tl_search_times, tl_grep_times;    // krep_gpu_debug_batch_times, krep_gpu_debug_grep_batch_times
 std::atomic<uint64_t> g_rebase_lds{0}, g_rebase_global{0}; // krep_gpu_debug_batch_rebase_launches
 std::atomic<uint64_t> g_cut_lds{0}, g_cut_global{0};       // krep_gpu_debug_batch_cut_launches
 
 bool holds_newline(const uint8_t cls[32]) { return (cls['\n' >> 3] >> ('\n' & 7)) & 1; }
+
+// ---- the segmentation of one pack in steps (batch_segment below)
+// the scratch's growth rule: half again what is needed, `floor` at the least
+uint64_t grown(uint64_t need, uint64_t floor = 0) { return std::max<uint64_t>(need + need / 2, floor); }
+bool counts_lines(const BatchSegment &g) { return g.lines && g.n_rec; } // -c with records: the line prefix step runs
+bool cut_keeps_records(const BatchSegment &g) { return g.form != BatchCutOut::None && !g.lines; }
+// under a cut the kept records are at most this many (0: none is kept, batch_cut does not run): d_cut and the grid of batch_cut are
+// sized by that bound, the kernel reads the kept total itself (no wait between the sum and the cut; the host reads the total behind
+// the segmentation, batch_kept_total)
+u64 cut_room(const BatchSegment &g)
+{
+    const u64 per_item = g.cut->m + g.cut->extra;
+    if (!cut_keeps_records(g) || !g.n_rec)
+        return 0;
+    return (per_item && g.n_items > g.n_rec / per_item) ? g.n_rec : g.n_items * per_item;
+}
+
+int segment_reserve(BatchScratch &s, const BatchSegment &g)
+{
+    const uint64_t items = grown(g.n_items, 1024);
+    HIPCHK(grow_scratch(s.items_cap, g.n_items, items,
+                        {dev_buf(s.d_off, (items + 1) * sizeof(u64)), dev_buf(s.d_res, items * sizeof(krep_gpu_batch_result_t))}));
+    if (counts_lines(g))
+    {
+        const uint64_t recs = grown(g.n_rec, 1u << 16);
+        HIPCHK(grow_scratch(s.rec_cap, g.n_rec, recs,
+                            {dev_buf(s.d_lines, recs * sizeof(uint64_t)), dev_buf(s.d_flags, recs * sizeof(u64)),
+                             dev_buf(s.d_prefix, recs * sizeof(u64)), dev_buf(s.d_sums, (scan_sums_words(recs) + 1) * sizeof(u64))}));
+    }
+    if (!g.cut)
+        return 0;
+    HIPCHK(grow_scratch(s.cut_items_cap, g.n_items, items,
+                        {dev_buf(s.d_keep, (items + 2) * sizeof(u64)), dev_buf(s.d_new_first, (items + 2) * sizeof(u64)),
+                         dev_buf(s.d_lo, (items + 2) * sizeof(u64)), dev_buf(s.d_cut_sums, (scan_sums_words(items + 2) + 1) * sizeof(u64))}));
+    if (const u64 room = cut_room(g))
+        HIPCHK(grow_scratch(s.cut_cap, room, grown(room, 1u << 12), {dev_buf(s.d_cut, grown(room, 1u << 12) * sizeof(match_position_t))}));
+    return 0;
+}
+
+// -c: s.d_prefix[k] = the lines opened by the records in front of record k, s.d_flags[k] = whether record k opens one
+int segment_line_prefix(BatchScratch &s, const BatchSegment &g, hipStream_t st)
+{
+    // the line of every record's start, in start order (a multi-pattern list comes in end order: two records of one line may
+    // have a record of the next line between them there)
+    if (g.by_end && krep_gpu_order_by_start(g.d_pos, g.n_rec, g.packed, st))
+        return 2;
+    if (krep_gpu_line_numbers(g.d_text, g.packed, g.d_pos, g.n_rec, s.d_lines, st))
+        return 2;
+    hipLaunchKernelGGL(batch_line_flags, dim3((u32)((g.n_rec + 255) / 256)), dim3(256), 0, st, (const u64 *)s.d_lines, (u64)g.n_rec, s.d_flags);
+    scan_exclusive(s.d_flags, g.n_rec, s.d_prefix, s.d_sums, false, st);
+    return 0;
+}
+
+// the road under a max_count: bounds in emission order, then the cut, then (the caller's) order
+int segment_cut(BatchScratch &s, const BatchSegment &g, hipStream_t st)
+{
+    const u64 *prefix = counts_lines(g) ? s.d_prefix : nullptr, *flags = counts_lines(g) ? s.d_flags : nullptr;
+    const u32 grid_i = (u32)((g.n_items + 1 + 255) / 256);
+    hipLaunchKernelGGL(batch_bounds_cut, dim3(grid_i), dim3(256), 0, st, (const u64 *)g.d_pos, (u64)g.n_rec, (const u64 *)s.d_off,
+                       (u64)g.n_items, cut_keeps_records(g) ? 1 : 0, prefix, flags, *g.cut, s.d_res, s.d_keep, s.d_lo);
+    scan_exclusive(s.d_keep, g.n_items + 1, s.d_new_first, s.d_cut_sums, false, st);
+    hipLaunchKernelGGL(batch_first, dim3(grid_i), dim3(256), 0, st, (const u64 *)s.d_new_first, (u64)g.n_items, (u64)g.rec_base,
+                       g.report ? 1 : 0, s.d_res);
+    HIPCHK(hipGetLastError());
+    if (const u64 room = cut_room(g))
+    {
+        const bool lds = g.n_items + 1 <= kBatchLdsItems, rebase = g.form == BatchCutOut::Rebased;
+        (lds ? g_cut_lds : g_cut_global).fetch_add(1, std::memory_order_relaxed);
+        const auto kernel = lds ? (rebase ? batch_cut<true, true> : batch_cut<true, false>)
+                                : (rebase ? batch_cut<false, true> : batch_cut<false, false>);
+        hipLaunchKernelGGL(kernel, dim3((u32)((room + kRebasePerBlock - 1) / kRebasePerBlock)), dim3(256), 0, st, (const u64 *)g.d_pos,
+                           (u64)g.n_rec, (u64 *)s.d_cut, (u64)room, (const u64 *)s.d_new_first, (const u64 *)s.d_lo, (const u64 *)s.d_off,
+                           (u64)g.n_items, *g.cut);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+// the plain road: the bounds, then every record relative to its item
+int segment_plain(BatchScratch &s, const BatchSegment &g, hipStream_t st)
+{
+    const u64 *prefix = counts_lines(g) ? s.d_prefix : nullptr, *flags = counts_lines(g) ? s.d_flags : nullptr;
+    hipLaunchKernelGGL(batch_bounds, dim3((u32)((g.n_items + 255) / 256)), dim3(256), 0, st, (const u64 *)g.d_pos, (u64)g.n_rec,
+                       (const u64 *)s.d_off, (u64)g.n_items, (u64)g.rec_base, g.report ? 1 : 0, prefix, flags, s.d_res);
+    if (g.report && !g.lines && g.n_rec)
+    {
+        const u32 grid = (u32)((g.n_rec + kRebasePerBlock - 1) / kRebasePerBlock);
+        const bool lds = g.n_items + 1 <= kBatchLdsItems; // off[0 .. n_items] is n_items + 1 entries
+        (lds ? g_rebase_lds : g_rebase_global).fetch_add(1, std::memory_order_relaxed);
+        hipLaunchKernelGGL(lds ? batch_rebase<true> : batch_rebase<false>, dim3(grid), dim3(256), 0, st, (u64 *)g.d_pos, (u64)g.n_rec,
+                           (const u64 *)s.d_off, (u64)g.n_items);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 } // namespace
 
 void batch_scratch_free(BatchScratch &s)
@@ -229,90 +327,16 @@ int batch_kept_total(const BatchScratch &s, uint64_t n_items, uint64_t n_rec, ui
     return 0;
 }
 
-int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const uint64_t *h_off, uint64_t n_items, match_position_t *d_pos,
-                  uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st, const BatchCut *cut,
-                  BatchCutOut form)
+int batch_segment(BatchScratch &s, const BatchSegment &g, hipStream_t st)
 {
-    if (!n_items)
+    if (!g.n_items)
         return 0;
-    {
-        const uint64_t want = std::max<uint64_t>(n_items + n_items / 2, 1024);
-        HIPCHK(grow_scratch(s.items_cap, n_items, want,
-                            {dev_buf(s.d_off, (want + 1) * sizeof(u64)), dev_buf(s.d_res, want * sizeof(krep_gpu_batch_result_t))}));
-    }
-    if (lines && n_rec)
-    {
-        const uint64_t want = std::max<uint64_t>(n_rec + n_rec / 2, 1u << 16);
-        HIPCHK(grow_scratch(s.rec_cap, n_rec, want,
-                            {dev_buf(s.d_lines, want * sizeof(uint64_t)), dev_buf(s.d_flags, want * sizeof(u64)),
-                             dev_buf(s.d_prefix, want * sizeof(u64)), dev_buf(s.d_sums, (scan_sums_words(want) + 1) * sizeof(u64))}));
-    }
-    HIPCHK(hipMemcpyAsync(s.d_off, h_off, (n_items + 1) * sizeof(u64), hipMemcpyHostToDevice, st));
-    const u64 *prefix = nullptr, *flags = nullptr;
-    if (lines && n_rec)
-    {
-        // the line of every record's start, in start order (a multi-pattern list comes in end order: two records of one line may
-        // have a record of the next line between them there)
-        if (by_end && krep_gpu_order_by_start(d_pos, n_rec, packed, st))
-            return 2;
-        if (krep_gpu_line_numbers(d_text, packed, d_pos, n_rec, s.d_lines, st))
-            return 2;
-        hipLaunchKernelGGL(batch_line_flags, dim3((u32)((n_rec + 255) / 256)), dim3(256), 0, st, (const u64 *)s.d_lines, (u64)n_rec, s.d_flags);
-        scan_exclusive(s.d_flags, n_rec, s.d_prefix, s.d_sums, false, st);
-        prefix = s.d_prefix;
-        flags = s.d_flags;
-    }
-    if (cut)
-    { // bounds in emission order, then the cut, then (the caller's) order
-        const bool records = form != BatchCutOut::None && !lines;
-        const uint64_t want = std::max<uint64_t>(n_items + n_items / 2, 1024);
-        HIPCHK(grow_scratch(s.cut_items_cap, n_items, want,
-                            {dev_buf(s.d_keep, (want + 2) * sizeof(u64)), dev_buf(s.d_new_first, (want + 2) * sizeof(u64)),
-                             dev_buf(s.d_lo, (want + 2) * sizeof(u64)), dev_buf(s.d_cut_sums, (scan_sums_words(want + 2) + 1) * sizeof(u64))}));
-        const u32 grid_i = (u32)((n_items + 1 + 255) / 256);
-        hipLaunchKernelGGL(batch_bounds_cut, dim3(grid_i), dim3(256), 0, st, (const u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off, (u64)n_items,
-                           records ? 1 : 0, prefix, flags, *cut, s.d_res, s.d_keep, s.d_lo);
-        scan_exclusive(s.d_keep, n_items + 1, s.d_new_first, s.d_cut_sums, false, st);
-        hipLaunchKernelGGL(batch_first, dim3(grid_i), dim3(256), 0, st, (const u64 *)s.d_new_first, (u64)n_items, (u64)rec_base,
-                           report ? 1 : 0, s.d_res);
-        HIPCHK(hipGetLastError());
-        // the kept records are at most `room`: the buffer and the grid are sized by that bound, the kernel reads the kept total itself
-        // (no wait between the sum and the cut; the host reads the total behind the segmentation, batch_kept_total)
-        const u64 per_item = cut->m + cut->extra, room = (per_item && n_items > n_rec / per_item) ? n_rec : n_items * per_item;
-        if (!records || !n_rec || !room)
-            return 0;
-        {
-            const uint64_t cap = std::max<uint64_t>(room + room / 2, 1u << 12);
-            HIPCHK(grow_scratch(s.cut_cap, room, cap, {dev_buf(s.d_cut, cap * sizeof(match_position_t))}));
-        }
-        const u32 grid = (u32)((room + kRebasePerBlock - 1) / kRebasePerBlock);
-        const bool lds = n_items + 1 <= kBatchLdsItems, rebase = form == BatchCutOut::Rebased;
-        (lds ? g_cut_lds : g_cut_global).fetch_add(1, std::memory_order_relaxed);
-#define KG_BATCH_CUT(L, R)                                                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(batch_cut<L, R>), dim3(grid), dim3(256), 0, st, (const u64 *)d_pos, (u64)n_rec, (u64 *)s.d_cut, (u64)room, \
-                       (const u64 *)s.d_new_first, (const u64 *)s.d_lo, (const u64 *)s.d_off, (u64)n_items, *cut)
-        if (lds && rebase) KG_BATCH_CUT(true, true);
-        else if (lds) KG_BATCH_CUT(true, false);
-        else if (rebase) KG_BATCH_CUT(false, true);
-        else KG_BATCH_CUT(false, false);
-#undef KG_BATCH_CUT
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    hipLaunchKernelGGL(batch_bounds, dim3((u32)((n_items + 255) / 256)), dim3(256), 0, st, (const u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off,
-                       (u64)n_items, (u64)rec_base, report ? 1 : 0, prefix, flags, s.d_res);
-    if (report && !lines && n_rec)
-    {
-        const u32 grid = (u32)((n_rec + kRebasePerBlock - 1) / kRebasePerBlock);
-        const bool lds = n_items + 1 <= kBatchLdsItems; // off[0 .. n_items] is n_items + 1 entries
-        (lds ? g_rebase_lds : g_rebase_global).fetch_add(1, std::memory_order_relaxed);
-        if (lds)
-            hipLaunchKernelGGL(batch_rebase<true>, dim3(grid), dim3(256), 0, st, (u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off, (u64)n_items);
-        else
-            hipLaunchKernelGGL(batch_rebase<false>, dim3(grid), dim3(256), 0, st, (u64 *)d_pos, (u64)n_rec, (const u64 *)s.d_off, (u64)n_items);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (segment_reserve(s, g))
+        return 2;
+    HIPCHK(hipMemcpyAsync(s.d_off, g.h_off, (g.n_items + 1) * sizeof(u64), hipMemcpyHostToDevice, st));
+    if (counts_lines(g) && segment_line_prefix(s, g, st))
+        return 2;
+    return g.cut ? segment_cut(s, g, st) : segment_plain(s, g, st);
 }
 
 // ------------------------------------------------------------------------------------------------ when packing is exact
@@ -409,15 +433,262 @@ BatchCut batch_cut_rule(const search_params_t *p, const krep_gpu_config_t &c, bo
     k.displace = algo == KREP_RA_MEMCHR && memchr_flush_displaces((uint64_t)m + 1, m) ? 1 : 0;
     return k;
 }
+
+namespace {
+// ------------------------------------------------------------------------------------------------ what both calls share
+// A call is: BatchWalk::enter (nothing on the device yet), its own checks, device_ready, an empty batch answered, start, then per pack
+// next() and pack() with the call's own fields of the job, then the call's commit of its results — at the very end only, so that a
+// failure leaves the caller's memory as it was.
+using clk = std::chrono::steady_clock;
+double ms_since(clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); }
+
+struct BatchWalk
+{
+    BatchTimes &times; // the calling thread's instance for this call
+    krep_gpu_config_t cfg{};
+    std::optional<NormParams> np;
+    const search_params_t *params = nullptr; // the caller's, normalised
+    search_params_t scan{}; // the pack is scanned with RECORDS whatever the caller wants back: the list is what gets cut per item, under -c too
+    BatchCut cut{};         // a finite max_count (the switch is on: the batch rule): the unlimited list is cut per item behind the scan
+    bool no_trie = false;   // aho_corasick.c:306: no trie, no matches — every count stays 0, nothing is scanned
+    size_t limit = 0;       // the packed size at which a further pack begins
+    std::optional<DeviceGuard> guard; // taken with the first pack
+    size_t n_items = 0, i0 = 0, i1 = 0; // the pack in hand: items [i0, i1)
+    std::vector<uint64_t> off;          // ... its offset table
+    BatchPackJob job{}; // ... and its job: items and cut from here; the call sets lines / report / records / appended / step / form
+    krep_gpu_batch_info_t bi{};
+    explicit BatchWalk(BatchTimes &t) : times(t) {}
+
+    // What both calls do first, in this order: the error cleared, *info and the times zeroed, `null_pointer` (the call's own test)
+    // with its message, the configuration, the batch rule, "no pattern".  -> 2 and the message
+    int enter(const char *null_msg, bool null_pointer, const search_params_t *raw, const krep_gpu_config_t *cfg_in, krep_gpu_batch_info_t *info)
+    {
+        krep_gpu_clear_error();
+        if (info)
+            *info = krep_gpu_batch_info_t{};
+        times = BatchTimes{};
+        if (null_pointer)
+            return fail("%s", null_msg);
+        cfg = cfg_in ? *cfg_in : current_config();
+        if (const char *why = batch_unsupported_reason(raw, cfg))
+            return fail("%s", why);
+        np.emplace(raw);
+        params = &np->sp;
+        return np->valid ? 0 : fail("no pattern");
+    }
+    int device_ready() const // the last refusal, behind the call's own: every refusal comes before any device work
+    {
+        const char *why = device_unusable(cfg.device);
+        return why ? fail("%s", why) : 0;
+    }
+    void start(const krep_gpu_batch_item_t *items, size_t n, bool search_file_cap /* see batch_cut_rule */)
+    {
+        n_items = n;
+        scan = *params;
+        scan.count_lines_mode = false;
+        scan.track_positions = true;
+        scan.max_count = SIZE_MAX;
+        if (params->max_count != SIZE_MAX)
+            cut = batch_cut_rule(params, cfg, search_file_cap);
+        job = BatchPackJob{}; // (the call's own fields: none, no records, no step)
+        job.scan = &scan, job.cfg = &cfg, job.items = items;
+        job.cut = params->max_count != SIZE_MAX ? &cut : nullptr;
+        job.form = BatchCutOut::None;
+        no_trie = params->num_patterns > 1 && !params->ac_trie && !params->use_regex; // (several -E patterns are one alternation)
+        const size_t chunk = cfg.stream_chunk_bytes ? cfg.stream_chunk_bytes : ((size_t)128 << 20);
+        limit = g_pack_limit.load() ? g_pack_limit.load() : 2 * chunk;
+    }
+    // the next pack, cut between items and never inside one (an item beyond the limit is a pack of its own); false: none is left
+    bool next()
+    {
+        job.items += i1 - i0;
+        i0 = i1;
+        if (no_trie || i0 >= n_items)
+            return false;
+        if (!guard)
+            guard.emplace(); // (behind the no-trie answer: that one needs no device)
+        job.n = batch_pack_offsets(job.items, n_items - i0, limit, off);
+        job.off = off.data();
+        i1 = i0 + job.n;
+        return true;
+    }
+    int pack(krep_gpu_batch_result_t *res /* [n_items] */, BatchPackDone *done)
+    {
+        const int rc = host_batch_pack(job, res + i0, done);
+        times += done->ms;
+        if (rc)
+            return 2;
+        bi.packed_bytes += off.back() - 1;
+        bi.scans += 1;
+        bi.total_records += done->n_rec;
+        bi.kernel_ms += done->kernel_ms;
+        return 0;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ the grep output of a batch
+// krep_gpu_grep_batch's own refusals, between the entry and the device: search_file()'s own branch (krep.c:3014-3027), the format,
+// per item its text and then its prefix, the output block
+int grep_batch_refuse(const search_params_t *raw, const krep_gpu_batch_item_t *items, size_t n_items, const krep_gpu_grep_format_t *fmt,
+                      const krep_gpu_grep_output_t *out)
+{
+    if (!(raw->count_lines_mode || raw->count_matches_mode) && !raw->track_positions)
+        return fail("grep_batch: track_positions == false outside -c: the reference prints its empty-match line then (krep.c:3029-3038), "
+                    "which no batchable search produces");
+    if (fmt->line.prefix_len || fmt->match.prefix_len)
+        return fail("grep_batch: the prefix of fmt->line / fmt->match must be empty: the prefixes are per item");
+    const char *str[6] = {fmt->line.before_match, fmt->line.after_match, fmt->line.line_close,
+                          fmt->match.before_number, fmt->match.after_number, fmt->match.after_match};
+    const size_t len[6] = {fmt->line.before_match_len, fmt->line.after_match_len, fmt->line.line_close_len,
+                           fmt->match.before_number_len, fmt->match.after_number_len, fmt->match.after_match_len};
+    for (int k = 0; k < 6; ++k)
+        if ((len[k] && !str[k]) || (len[k] >> 20))
+            return fail("grep_batch: a string of the format is NULL with a length, or longer than 2^20 bytes");
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        if (!items[i].text && items[i].len)
+            return fail("grep_batch: item %zu has a NULL text and a length of %zu", i, items[i].len);
+        if ((fmt->prefix_lens[i] && !fmt->prefixes[i]) || (fmt->prefix_lens[i] >> 20))
+            return fail("grep_batch: the prefix of item %zu is NULL with a length, or longer than 2^20 bytes", i);
+    }
+    if (out->len > out->capacity || (!out->bytes && out->capacity))
+        return fail("grep_batch: out holds %zu bytes in a block of %zu", out->len, out->capacity);
+    return 0;
+}
+
+// The caller's block while a call appends to it: the bytes go behind len0 + appended, out->len moves at the very end only
+struct GrepOut
+{
+    krep_gpu_grep_output_t *out;
+    size_t len0;
+    uint64_t appended = 0;
+    char *end() const { return out->bytes + len0 + appended; }
+    bool host_room(uint64_t more) // out->bytes holds len0 + appended + more bytes
+    {
+        const size_t need = len0 + appended + more;
+        if (need <= out->capacity)
+            return true;
+        const size_t cap = std::max<size_t>({need, 2 * out->capacity, (size_t)4096});
+        char *p = (char *)realloc(out->bytes, cap);
+        if (!p)
+            return false;
+        out->bytes = p;
+        out->capacity = cap;
+        return true;
+    }
+};
+struct GrepCall // what the steps below need of one krep_gpu_grep_batch call
+{
+    const krep_gpu_grep_format_t *fmt;
+    bool om;
+    GrepOut out;
+    std::vector<krep_gpu_grep_item_t> pi; // per_item until the commit
+    const BatchWalk &walk; // (i0: the first item of the pack in hand; times: the call's stage clocks)
+    std::vector<uint64_t> poff, item_out;
+    std::vector<uint8_t> blob;
+};
+
+// The BatchStep of a pack, between its segmentation and its read-back: the items' prefixes onto the device, the pack formatted where it
+// lies, its bytes copied behind what the block holds, the items' places noted
+int grep_format_pack(GrepCall &g, const BatchPackOnDevice &p)
+{
+    auto t0 = clk::now();
+    BatchScratch &s = p.scratch;
+    const size_t n = (size_t)p.n_items;
+    g.item_out.assign(n + 1, 0);
+    uint64_t bytes = 0;
+    if (p.n_rec)
+    {
+        if (p.by_end && krep_gpu_order_by_start(p.d_pos, p.n_rec, p.packed, nullptr))
+            return 2;
+        (void)batch_prefix_blob(g.fmt->prefixes + g.walk.i0, g.fmt->prefix_lens + g.walk.i0, n, (size_t)1 << 20, g.blob, g.poff); // (checked at entry)
+        if (inject(1))
+            return fail("grep_batch: device allocation failed (injected)");
+        HIPCHK(grow_scratch(s.pfx_cap, g.blob.size(), grown(g.blob.size()) + 4096, {dev_buf(s.d_pfx, grown(g.blob.size()) + 4096)}));
+        const uint64_t want = std::max<uint64_t>(n + 1 + n / 2, 1024);
+        HIPCHK(grow_scratch(s.grep_items_cap, n + 1, want, {dev_buf(s.d_pfx_off, want * sizeof(u64)), dev_buf(s.d_item_out, want * sizeof(u64))}));
+        if (inject(2))
+            return fail("grep_batch: H2D copy of the prefixes failed (injected)");
+        if (!g.blob.empty())
+            HIPCHK(hipMemcpyAsync(s.d_pfx, g.blob.data(), g.blob.size(), hipMemcpyHostToDevice, nullptr));
+        HIPCHK(hipMemcpyAsync(s.d_pfx_off, g.poff.data(), (n + 1) * sizeof(u64), hipMemcpyHostToDevice, nullptr));
+        const krep_gpu_pack_view_t view{(const uint64_t *)p.d_off, (uint64_t)n, s.d_pfx, (const uint64_t *)s.d_pfx_off};
+        const FormatOutGrow grow = [&s](size_t want) -> void * { // the rule of the other scratch: grown by half again
+            if (grow_scratch(s.out_cap, want, grown(want), {dev_buf(s.d_out, grown(want))}) == hipSuccess)
+                return s.d_out;
+            (void)hipGetLastError();
+            (void)fail("grep_batch: allocation of %zu bytes for the formatted output failed", (size_t)grown(want));
+            return nullptr;
+        };
+        if (inject(3))
+            return fail("grep_batch: launch of the pack formatter failed (injected)");
+        krep_gpu_matches_out_t mo{};
+        krep_gpu_lines_out_t lo{};
+        if (g.om ? format_matches_items(p.d_text, p.packed, &view, p.d_pos, p.n_rec, &g.fmt->match, nullptr, 0, &grow, (uint64_t *)s.d_item_out, &mo, nullptr)
+                 : format_lines_items(p.d_text, p.packed, &view, p.d_pos, p.n_rec, &g.fmt->line, nullptr, 0, &grow, (uint64_t *)s.d_item_out, &lo, nullptr))
+            return 2;
+        bytes = g.om ? mo.out_bytes : lo.out_bytes;
+        g.walk.times.format += ms_since(t0);
+        t0 = clk::now();
+        if (inject(4))
+            return fail("D2H copy of the formatted output failed (injected)");
+        if (!g.out.host_room(bytes))
+            return fail("grep_batch: out of memory growing the output to %zu bytes", (size_t)(g.out.len0 + g.out.appended + bytes));
+        if ((bytes && hipMemcpy(g.out.end(), s.d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+            hipMemcpy(g.item_out.data(), s.d_item_out, (n + 1) * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail("D2H copy of the formatted output failed");
+        g.walk.times.read_back += ms_since(t0);
+    }
+    for (size_t k = 0; k < n; ++k)
+        g.pi[g.walk.i0 + k] = krep_gpu_grep_item_t{0, g.out.appended + g.item_out[k], g.item_out[k + 1] - g.item_out[k]};
+    g.out.appended += bytes;
+    return 0;
+}
+
+// -c: the counts are printed on the host, prefix COUNT '\n' for every item
+int grep_print_counts(GrepCall &g, const krep_gpu_batch_result_t *res, size_t n_items)
+{
+    const auto t0 = clk::now();
+    const krep_gpu_grep_format_t *fmt = g.fmt;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_items; ++i)
+        total += fmt->prefix_lens[i] + 21;
+    if (!g.out.host_room(total))
+        return fail("grep_batch: out of memory growing the output by %zu bytes", (size_t)total);
+    for (size_t i = 0; i < n_items; ++i)
+    {
+        char *dst = g.out.end();
+        if (fmt->prefix_lens[i])
+            memcpy(dst, fmt->prefixes[i], fmt->prefix_lens[i]);
+        char num[24];
+        const int d = snprintf(num, sizeof num, "%llu\n", (unsigned long long)res[i].count);
+        memcpy(dst + fmt->prefix_lens[i], num, (size_t)d);
+        g.pi[i] = krep_gpu_grep_item_t{0, g.out.appended, fmt->prefix_lens[i] + (uint64_t)d};
+        g.out.appended += g.pi[i].out_bytes;
+    }
+    g.walk.times.read_back += ms_since(t0);
+    return 0;
+}
+} // namespace
 } // namespace kg
 
 extern "C" void krep_gpu_debug_batch_pack_limit(size_t bytes) { g_pack_limit.store(bytes); }
 extern "C" void krep_gpu_debug_batch_times(double *pack_ms, double *scan_ms, double *segment_ms, double *readback_ms)
 {
-    if (pack_ms) *pack_ms = tl_batch_ms[0];
-    if (scan_ms) *scan_ms = tl_batch_ms[1];
-    if (segment_ms) *segment_ms = tl_batch_ms[2];
-    if (readback_ms) *readback_ms = tl_batch_ms[3];
+    const BatchTimes &t = tl_search_times;
+    if (pack_ms) *pack_ms = t.pack;
+    if (scan_ms) *scan_ms = t.scan;
+    if (segment_ms) *segment_ms = t.segment;
+    if (readback_ms) *readback_ms = t.read_back;
+}
+extern "C" void krep_gpu_debug_grep_batch_times(double *pack_ms, double *scan_ms, double *segment_ms, double *format_ms, double *readback_ms)
+{
+    const BatchTimes &t = tl_grep_times;
+    if (pack_ms) *pack_ms = t.pack;
+    if (scan_ms) *scan_ms = t.scan;
+    if (segment_ms) *segment_ms = t.segment;
+    if (format_ms) *format_ms = t.format;
+    if (readback_ms) *readback_ms = t.read_back;
 }
 
 extern "C" void krep_gpu_debug_batch_rebase_launches(uint64_t *lds_table, uint64_t *global_table)
@@ -461,278 +732,68 @@ extern "C" int krep_gpu_search_batch(const search_params_t *raw, const krep_gpu_
                                      size_t n_items, krep_gpu_batch_result_t *results, match_result_t *records,
                                      krep_gpu_batch_info_t *info)
 {
-    krep_gpu_clear_error();
-    if (info)
-        *info = krep_gpu_batch_info_t{};
-    for (double &t : tl_batch_ms)
-        t = 0;
-    if (!raw || (n_items && (!items || !results)))
-        return kg::fail("search_batch: NULL params / items / results");
-    const krep_gpu_config_t cfg = cfg_in ? *cfg_in : kg::current_config();
-    // every refusal comes before any device work
-    if (const char *why = kg::batch_unsupported_reason(raw, cfg))
-        return kg::fail("%s", why);
-    NormParams np(raw);
-    if (!np.valid)
-        return kg::fail("no pattern");
+    BatchWalk w(tl_search_times);
+    if (w.enter("search_batch: NULL params / items / results", !raw || (n_items && (!items || !results)), raw, cfg_in, info))
+        return 2;
     for (size_t i = 0; i < n_items; ++i)
         if (!items[i].text && items[i].len)
             return kg::fail("search_batch: item %zu has a NULL text and a length of %zu", i, items[i].len);
-    if (const char *why = kg::device_unusable(cfg.device))
-        return kg::fail("%s", why);
+    if (w.device_ready())
+        return 2;
     if (!n_items)
         return 0;
-    const search_params_t *params = &np.sp;
-    const bool lines = params->count_lines_mode;
-    const bool report = params->track_positions && records != nullptr && !lines;
+    const bool lines = w.params->count_lines_mode;
+    const bool report = w.params->track_positions && records != nullptr && !lines;
     const uint64_t count0 = records ? records->count : 0;
-    std::vector<krep_gpu_batch_result_t> res(n_items, krep_gpu_batch_result_t{0, count0, 0});
-    if (params->num_patterns > 1 && !params->ac_trie && !params->use_regex)
-    { // aho_corasick.c:306: no trie, no matches (several -E patterns are one alternation: no trie is involved)
-        memcpy(results, res.data(), n_items * sizeof *results);
-        return 0;
-    }
-    // the pack is scanned with RECORDS whatever the caller wants back: the list is what gets cut per item, under -c too
-    search_params_t scan = *params;
-    scan.count_lines_mode = false;
-    scan.track_positions = true;
-    scan.max_count = SIZE_MAX;
-    // a finite max_count (the switch is on: the refusal above): the unlimited list is cut per item behind the scan
-    const bool cutting = params->max_count != SIZE_MAX;
-    const BatchCut cut = cutting ? kg::batch_cut_rule(params, cfg, false) : BatchCut{};
-    const size_t chunk = cfg.stream_chunk_bytes ? cfg.stream_chunk_bytes : ((size_t)128 << 20);
-    const size_t limit = g_pack_limit.load() ? g_pack_limit.load() : 2 * chunk;
-    DeviceGuard guard;
-    krep_gpu_batch_info_t bi{};
-    uint64_t appended = 0;
-    std::vector<uint64_t> off;
-    for (size_t i0 = 0; i0 < n_items;)
+    std::vector<krep_gpu_batch_result_t> res(n_items, krep_gpu_batch_result_t{0, count0, 0}); // (what no trie answers)
+    w.start(items, n_items, false);
+    w.job.lines = lines, w.job.report = report, w.job.records = records;
+    w.job.form = report ? BatchCutOut::Rebased : BatchCutOut::None;
+    for (BatchPackDone done; w.next();)
     {
-        // the next pack: items [i0, i1), cut between items and never inside one (an item beyond the limit is a pack of its own)
-        const size_t i1 = i0 + kg::batch_pack_offsets(items + i0, n_items - i0, limit, off);
-        uint64_t n_rec = 0, n_kept = 0;
-        float kms = 0;
-        if (kg::host_batch_pack(&scan, cfg, items + i0, i1 - i0, off.data(), lines, report, records, appended, res.data() + i0, &n_rec, &kms,
-                                tl_batch_ms, nullptr, cutting ? &cut : nullptr, report ? BatchCutOut::Rebased : BatchCutOut::None, &n_kept))
+        if (w.pack(res.data(), &done))
             return 2; // (records->count was never moved: nothing is appended)
-        bi.packed_bytes += off.back() - 1;
-        bi.scans += 1;
-        bi.total_records += n_rec;
-        bi.kernel_ms += kms;
         if (report)
-            appended += cutting ? n_kept : n_rec;
-        i0 = i1;
+            w.job.appended += w.job.cut ? done.n_kept : done.n_rec;
     }
     memcpy(results, res.data(), n_items * sizeof *results);
     if (report)
-        records->count = count0 + appended;
+        records->count = count0 + w.job.appended;
     if (info)
-        *info = bi;
+        *info = w.bi;
     return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ the grep output of a batch
-extern "C" void krep_gpu_debug_grep_batch_times(double *pack_ms, double *scan_ms, double *segment_ms, double *format_ms, double *readback_ms)
-{
-    double *const dst[5] = {pack_ms, scan_ms, segment_ms, format_ms, readback_ms};
-    for (int k = 0; k < 5; ++k)
-        if (dst[k]) *dst[k] = tl_grep_ms[k];
 }
 
 extern "C" int krep_gpu_grep_batch(const search_params_t *raw, const krep_gpu_config_t *cfg_in, const krep_gpu_batch_item_t *items,
                                    size_t n_items, const krep_gpu_grep_format_t *fmt, krep_gpu_grep_item_t *per_item,
                                    krep_gpu_grep_output_t *out, krep_gpu_batch_info_t *info)
 {
-    using clk = std::chrono::steady_clock;
-    const auto since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-    krep_gpu_clear_error();
-    if (info)
-        *info = krep_gpu_batch_info_t{};
-    for (double &t : tl_grep_ms)
-        t = 0;
-    if (!raw || !fmt || !out || (n_items && (!items || !per_item || !fmt->prefixes || !fmt->prefix_lens)))
-        return kg::fail("grep_batch: NULL params / items / fmt / per_item / out");
-    const krep_gpu_config_t cfg = cfg_in ? *cfg_in : kg::current_config();
-    // every refusal comes before any device work
-    if (const char *why = kg::batch_unsupported_reason(raw, cfg))
-        return kg::fail("%s", why);
-    NormParams np(raw);
-    if (!np.valid)
-        return kg::fail("no pattern");
-    // search_file()'s own branch (krep.c:3014-3027)
-    const bool count_mode = raw->count_lines_mode || raw->count_matches_mode, om = !count_mode && cfg.only_matching;
-    if (!count_mode && !raw->track_positions)
-        return kg::fail("grep_batch: track_positions == false outside -c: the reference prints its empty-match line then (krep.c:3029-3038), "
-                        "which no batchable search produces");
-    if (fmt->line.prefix_len || fmt->match.prefix_len)
-        return kg::fail("grep_batch: the prefix of fmt->line / fmt->match must be empty: the prefixes are per item");
-    {
-        const char *str[6] = {fmt->line.before_match, fmt->line.after_match, fmt->line.line_close,
-                              fmt->match.before_number, fmt->match.after_number, fmt->match.after_match};
-        const size_t len[6] = {fmt->line.before_match_len, fmt->line.after_match_len, fmt->line.line_close_len,
-                               fmt->match.before_number_len, fmt->match.after_number_len, fmt->match.after_match_len};
-        for (int k = 0; k < 6; ++k)
-            if ((len[k] && !str[k]) || (len[k] >> 20))
-                return kg::fail("grep_batch: a string of the format is NULL with a length, or longer than 2^20 bytes");
-    }
-    for (size_t i = 0; i < n_items; ++i)
-    {
-        if (!items[i].text && items[i].len)
-            return kg::fail("grep_batch: item %zu has a NULL text and a length of %zu", i, items[i].len);
-        if ((fmt->prefix_lens[i] && !fmt->prefixes[i]) || (fmt->prefix_lens[i] >> 20))
-            return kg::fail("grep_batch: the prefix of item %zu is NULL with a length, or longer than 2^20 bytes", i);
-    }
-    if (out->len > out->capacity || (!out->bytes && out->capacity))
-        return kg::fail("grep_batch: out holds %zu bytes in a block of %zu", out->len, out->capacity);
-    if (const char *why = kg::device_unusable(cfg.device))
-        return kg::fail("%s", why);
+    BatchWalk w(tl_grep_times);
+    if (w.enter("grep_batch: NULL params / items / fmt / per_item / out",
+                !raw || !fmt || !out || (n_items && (!items || !per_item || !fmt->prefixes || !fmt->prefix_lens)), raw, cfg_in, info))
+        return 2;
+    if (grep_batch_refuse(raw, items, n_items, fmt, out) || w.device_ready())
+        return 2;
     if (!n_items)
         return 0;
-    const search_params_t *params = &np.sp;
-    const size_t len0 = out->len;
-    uint64_t appended = 0; // bytes written behind out->bytes + len0 so far (out->len moves at the very end)
-    const auto host_room = [&](uint64_t more) -> bool { // out->bytes holds len0 + appended + more bytes
-        const size_t need = len0 + appended + more;
-        if (need <= out->capacity)
-            return true;
-        const size_t cap = std::max<size_t>({need, 2 * out->capacity, (size_t)4096});
-        char *p = (char *)realloc(out->bytes, cap);
-        if (!p)
-            return false;
-        out->bytes = p;
-        out->capacity = cap;
-        return true;
-    };
+    const bool count_mode = raw->count_lines_mode || raw->count_matches_mode;
+    GrepCall g{fmt, !count_mode && w.cfg.only_matching, GrepOut{out, out->len}, std::vector<krep_gpu_grep_item_t>(n_items), w};
     std::vector<krep_gpu_batch_result_t> res(n_items, krep_gpu_batch_result_t{0, 0, 0});
-    std::vector<krep_gpu_grep_item_t> pi(n_items, krep_gpu_grep_item_t{0, 0, 0});
-    krep_gpu_batch_info_t bi{};
-    // (aho_corasick.c:306: no trie, no matches — every count stays 0, nothing is scanned)
-    const bool no_trie = params->num_patterns > 1 && !params->ac_trie && !params->use_regex;
-    search_params_t scan = *params;
-    scan.count_lines_mode = false;
-    scan.track_positions = true;
-    scan.max_count = SIZE_MAX;
-    // a finite max_count (the switch is on): search_file()'s cut per item; the formatters below see the kept list only
-    const bool cutting = params->max_count != SIZE_MAX;
-    const BatchCut cut = cutting ? kg::batch_cut_rule(params, cfg, true) : BatchCut{};
-    const size_t chunk = cfg.stream_chunk_bytes ? cfg.stream_chunk_bytes : ((size_t)128 << 20);
-    const size_t limit = g_pack_limit.load() ? g_pack_limit.load() : 2 * chunk;
-    DeviceGuard guard;
-    std::vector<uint64_t> off, poff, item_out;
-    std::vector<uint8_t> blob;
-    for (size_t i0 = 0; i0 < n_items && !no_trie;)
-    {
-        const size_t i1 = i0 + kg::batch_pack_offsets(items + i0, n_items - i0, limit, off);
-        // between the segmentation and the read-back: the pack formatted where it lies, its bytes copied behind what is there
-        const BatchStep format = [&](const BatchPackOnDevice &p) -> int {
-            auto t0 = clk::now();
-            const size_t n = (size_t)p.n_items;
-            item_out.assign(n + 1, 0);
-            uint64_t bytes = 0;
-            if (p.n_rec)
-            {
-                BatchScratch &s = p.scratch;
-                if (p.by_end && krep_gpu_order_by_start(p.d_pos, p.n_rec, p.packed, nullptr))
-                    return 2;
-                (void)kg::batch_prefix_blob(fmt->prefixes + i0, fmt->prefix_lens + i0, n, (size_t)1 << 20, blob, poff); // (checked above)
-                if (kg::inject(1))
-                    return kg::fail("grep_batch: device allocation failed (injected)");
-                HIPCHK(grow_scratch(s.pfx_cap, blob.size(), blob.size() + blob.size() / 2 + 4096,
-                                    {dev_buf(s.d_pfx, blob.size() + blob.size() / 2 + 4096)}));
-                {
-                    const uint64_t want = std::max<uint64_t>(n + 1 + n / 2, 1024);
-                    HIPCHK(grow_scratch(s.grep_items_cap, n + 1, want,
-                                        {dev_buf(s.d_pfx_off, want * sizeof(u64)), dev_buf(s.d_item_out, want * sizeof(u64))}));
-                }
-                if (kg::inject(2))
-                    return kg::fail("grep_batch: H2D copy of the prefixes failed (injected)");
-                if (!blob.empty())
-                    HIPCHK(hipMemcpyAsync(s.d_pfx, blob.data(), blob.size(), hipMemcpyHostToDevice, nullptr));
-                HIPCHK(hipMemcpyAsync(s.d_pfx_off, poff.data(), (n + 1) * sizeof(u64), hipMemcpyHostToDevice, nullptr));
-                const krep_gpu_pack_view_t view{(const uint64_t *)p.d_off, (uint64_t)n, s.d_pfx, (const uint64_t *)s.d_pfx_off};
-                const FormatOutGrow grow = [&s](size_t want) -> void * { // the rule of the other scratch: grown by half again
-                    if (grow_scratch(s.out_cap, want, want + want / 2, {dev_buf(s.d_out, want + want / 2)}) != hipSuccess)
-                    {
-                        (void)hipGetLastError();
-                        (void)kg::fail("grep_batch: allocation of %zu bytes for the formatted output failed", want + want / 2);
-                        return nullptr;
-                    }
-                    return s.d_out;
-                };
-                if (kg::inject(3))
-                    return kg::fail("grep_batch: launch of the pack formatter failed (injected)");
-                if (om)
-                {
-                    krep_gpu_matches_out_t mo{};
-                    if (kg::format_matches_items(p.d_text, p.packed, &view, p.d_pos, p.n_rec, &fmt->match, nullptr, 0, &grow,
-                                                 (uint64_t *)s.d_item_out, &mo, nullptr))
-                        return 2;
-                    bytes = mo.out_bytes;
-                }
-                else
-                {
-                    krep_gpu_lines_out_t lo{};
-                    if (kg::format_lines_items(p.d_text, p.packed, &view, p.d_pos, p.n_rec, &fmt->line, nullptr, 0, &grow,
-                                               (uint64_t *)s.d_item_out, &lo, nullptr))
-                        return 2;
-                    bytes = lo.out_bytes;
-                }
-                tl_grep_ms[3] += since(t0);
-                t0 = clk::now();
-                if (kg::inject(4))
-                    return kg::fail("D2H copy of the formatted output failed (injected)");
-                if (!host_room(bytes))
-                    return kg::fail("grep_batch: out of memory growing the output to %zu bytes", (size_t)(len0 + appended + bytes));
-                if ((bytes &&hipMemcpy(out->bytes + len0 + appended, s.d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
-                    hipMemcpy(item_out.data(), s.d_item_out, (n + 1) * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess)
-                    return kg::fail("D2H copy of the formatted output failed");
-                tl_grep_ms[4] += since(t0);
-            }
-            for (size_t k = 0; k < n; ++k)
-                pi[i0 + k] = krep_gpu_grep_item_t{0, appended + item_out[k], item_out[k + 1] - item_out[k]};
-            appended += bytes;
-            return 0;
-        };
-        uint64_t n_rec = 0;
-        float kms = 0;
-        double ms[4] = {0, 0, 0, 0};
-        if (kg::host_batch_pack(&scan, cfg, items + i0, i1 - i0, off.data(), count_mode && params->count_lines_mode, false, nullptr, 0,
-                                res.data() + i0, &n_rec, &kms, ms, count_mode ? nullptr : &format, cutting ? &cut : nullptr,
-                                count_mode ? BatchCutOut::None : BatchCutOut::PackSorted))
+    const BatchStep format = [&g](const BatchPackOnDevice &p) { return grep_format_pack(g, p); };
+    w.start(items, n_items, true); // (a finite max_count: search_file()'s cut per item; the formatter sees the kept list only)
+    w.job.lines = count_mode && raw->count_lines_mode;
+    w.job.step = count_mode ? nullptr : &format;
+    w.job.form = count_mode ? BatchCutOut::None : BatchCutOut::PackSorted;
+    for (BatchPackDone done; w.next();)
+        if (w.pack(res.data(), &done))
             return 2; // (out->len was never moved: nothing is appended)
-        tl_grep_ms[0] += ms[0], tl_grep_ms[1] += ms[1], tl_grep_ms[2] += ms[2], tl_grep_ms[4] += ms[3];
-        bi.packed_bytes += off.back() - 1;
-        bi.scans += 1;
-        bi.total_records += n_rec;
-        bi.kernel_ms += kms;
-        i0 = i1;
-    }
-    if (count_mode) // the counts are printed on the host: prefix COUNT '\n' for every item
-    {
-        const auto t0 = clk::now();
-        uint64_t total = 0;
-        for (size_t i = 0; i < n_items; ++i)
-            total += fmt->prefix_lens[i] + 21;
-        if (!host_room(total))
-            return kg::fail("grep_batch: out of memory growing the output by %zu bytes", (size_t)total);
-        for (size_t i = 0; i < n_items; ++i)
-        {
-            char *dst = out->bytes + len0 + appended;
-            if (fmt->prefix_lens[i])
-                memcpy(dst, fmt->prefixes[i], fmt->prefix_lens[i]);
-            char num[24];
-            const int d = snprintf(num, sizeof num, "%llu\n", (unsigned long long)res[i].count);
-            memcpy(dst + fmt->prefix_lens[i], num, (size_t)d);
-            pi[i] = krep_gpu_grep_item_t{0, appended, fmt->prefix_lens[i] + (uint64_t)d};
-            appended += pi[i].out_bytes;
-        }
-        tl_grep_ms[4] += since(t0);
-    }
+    if (count_mode && grep_print_counts(g, res.data(), n_items))
+        return 2;
     for (size_t i = 0; i < n_items; ++i)
-        pi[i].count = res[i].count;
-    memcpy(per_item, pi.data(), n_items * sizeof *per_item);
-    out->len = len0 + appended;
+        g.pi[i].count = res[i].count;
+    memcpy(per_item, g.pi.data(), n_items * sizeof *per_item);
+    out->len = g.out.len0 + g.out.appended;
     if (info)
-        *info = bi;
+        *info = w.bi;
     return 0;
 }

@@ -1121,81 +1121,100 @@ int host_scan(const search_params_t *params, const krep_gpu_config_t &cfg, const
     return run_whole(*cx, params, cfg, text, text_len, result, ret);
 }
 
+} // namespace kg
+
 // ------------------------------------------------------------------------------------------------ a batch of texts as one text
-// One pack of krep_gpu_search_batch (kg_batch.hip): the items gathered through the staging ring into the arena's text buffer with a
-// '\n' between neighbours, ONE scan over the whole pack in one window with records (again at the exact size when the list
-// overflowed, as the operators do), the list cut per item on the device, results and rebased records read back in one copy each.
-int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t &cfg, const krep_gpu_batch_item_t *items, size_t n,
-                    const uint64_t *off, bool lines, bool report, match_result_t *records, uint64_t appended,
-                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms, const BatchStep *step,
-                    const BatchCut *cut, BatchCutOut form, uint64_t *n_kept_out)
+// One pack of krep_gpu_search_batch / krep_gpu_grep_batch (kg_batch.hip): the items gathered through the staging ring into the arena's
+// text buffer with a '\n' between neighbours, ONE scan over the whole pack in one window with records (again at the exact size when
+// the list overflowed, as the operators do), the list cut per item on the device, the caller's step on the pack where it lies,
+// results and rebased records read back in one copy each.  The steps in that order, cx.mu held:
+namespace {
+struct PackRun
+{
+    DeviceCtx &cx;
+    const BatchPackJob &job;
+    krep_gpu_plan_t *pl;
+    size_t packed;
+    uint8_t *d_text = nullptr;
+    match_position_t *d_pos = nullptr; // the scan's list
+    uint64_t n_rec = 0;
+    match_position_t *d_list = nullptr; // the list every step behind the segmentation works on: under a cut cx.batch.d_cut
+    uint64_t n_list = 0;
+    bool by_end() const { return pl->ref_algo == KREP_RA_AHO_CORASICK; }
+
+    int gather()
+    {
+        const auto fill = [items = job.items, off = job.off, n = job.n](uint8_t *dst, size_t lo, size_t cnt) {
+            batch_fill(items, off, n, dst, lo, cnt);
+        };
+        return packed && (cx.stager.init(cx.device) || cx.stager.gather(d_text, packed, fill)) ? 2 : 0;
+    }
+    int scan(BatchPackDone *done)
+    {
+        krep_gpu_scan_out_t so{};
+        if (packed && sized_scan(cx, std::max<uint64_t>(1u << 16, packed / 64), so, &d_pos, [&](match_position_t *d, uint64_t c) {
+                return krep_gpu_scan_device_ex(pl, d_text, packed, 0, packed, 0, packed, d, c, nullptr, 1, &so);
+            }))
+            return 2;
+        if (so.overflow)
+            return kg::fail("search_batch: the record list outgrew its second, exact-size buffer");
+        n_rec = done->n_rec = so.stored;
+        done->kernel_ms = so.kernel_ms;
+        return 0;
+    }
+    int segment(BatchPackDone *done) // the segmentation, the wait for it, and under a cut that keeps records their number
+    {
+        const uint64_t rec_base = (job.records ? job.records->count : 0) + (job.report ? job.appended : 0);
+        if (batch_segment(cx.batch, BatchSegment{d_text, packed, job.off, job.n, d_pos, n_rec, rec_base, by_end(), job.lines, job.report,
+                                                 job.cut, job.form}, nullptr))
+            return 2;
+        HIPCHK(hipStreamSynchronize(nullptr));
+        if (job.cut && job.form != BatchCutOut::None && !job.lines && n_rec && job.cut->m && batch_kept_total(cx.batch, job.n, n_rec, &done->n_kept))
+            return 2;
+        d_list = job.cut ? cx.batch.d_cut : d_pos;
+        n_list = job.cut ? done->n_kept : n_rec;
+        return 0;
+    }
+    int read_back(krep_gpu_batch_result_t *res_out)
+    {
+        if (kg::inject(4) || hipMemcpy(res_out, cx.batch.d_res, job.n * sizeof *res_out, hipMemcpyDeviceToHost) != hipSuccess)
+            return kg::fail("D2H copy of the batch results failed");
+        if (!job.report || !n_list)
+            return 0;
+        if (!result_reserve(job.records, job.appended + n_list))
+            return kg::fail("out of memory growing match_result_t");
+        return records_to_host(job.records->positions + job.records->count + job.appended, d_list, n_list);
+    }
+};
+} // namespace
+
+int kg::host_batch_pack(const BatchPackJob &job, krep_gpu_batch_result_t *res_out, BatchPackDone *done)
 {
     using clk = std::chrono::steady_clock;
-    const auto since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-    *n_rec_out = 0;
-    *kernel_ms = 0;
-    DeviceCtx &cx = *ctx_for(cfg.device);
+    *done = BatchPackDone{};
+    DeviceCtx &cx = *ctx_for(job.cfg->device);
     std::lock_guard<std::mutex> lk(cx.mu);
-    krep_gpu_plan_t *pl = cx.plan_for(scan_params, cfg);
+    krep_gpu_plan_t *pl = cx.plan_for(job.scan, *job.cfg);
     if (!pl)
         return 2;
-    const size_t packed = (size_t)off[n] - 1;
+    PackRun r{cx, job, pl, (size_t)job.off[job.n] - 1};
     HIPCHK(hipSetDevice(cx.device));
-    if (cx.mem.ensure(packed + 64, 1, cx.device))
+    if (cx.mem.ensure(r.packed + 64, 1, cx.device))
         return 2;
-    uint8_t *const d_text = cx.mem.text(0);
+    r.d_text = cx.mem.text(0);
     auto t0 = clk::now();
-    if (packed)
-    {
-        const auto fill = [=](uint8_t *dst, size_t lo, size_t cnt) { batch_fill(items, off, n, dst, lo, cnt); };
-        if (cx.stager.init(cx.device) || cx.stager.gather(d_text, packed, fill))
-            return 2;
-    }
-    ms[0] += since(t0);
+    const auto timed = [&t0](double &stage, int rc) { // the wall clock since the stage before ended
+        stage = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+        t0 = clk::now();
+        return rc;
+    };
+    if (timed(done->ms.pack, r.gather()) || timed(done->ms.scan, r.scan(done)) || timed(done->ms.segment, r.segment(done)))
+        return 2;
+    if (job.step && (*job.step)(BatchPackOnDevice{cx.batch, r.d_text, r.packed, cx.batch.d_off, job.n, r.d_list, r.n_list, r.by_end()}))
+        return 2; // (its time is its own)
     t0 = clk::now();
-    krep_gpu_scan_out_t so{};
-    match_position_t *d_pos = nullptr;
-    if (packed && sized_scan(cx, std::max<uint64_t>(1u << 16, packed / 64), so, &d_pos, [&](match_position_t *d, uint64_t c) {
-            return krep_gpu_scan_device_ex(pl, d_text, packed, 0, packed, 0, packed, d, c, nullptr, 1, &so);
-        }))
-        return 2;
-    if (so.overflow)
-        return kg::fail("search_batch: the record list outgrew its second, exact-size buffer");
-    ms[1] += since(t0);
-    t0 = clk::now();
-    const uint64_t n_rec = so.stored;
-    *kernel_ms = so.kernel_ms;
-    const uint64_t rec_base = (records ? records->count : 0) + (report ? appended : 0);
-    uint64_t n_kept = 0; // under a cut: the records of cx.batch.d_cut, the list every later step works on
-    if (batch_segment(cx.batch, d_text, packed, off, n, d_pos, n_rec, rec_base, pl->ref_algo == KREP_RA_AHO_CORASICK, lines, report, nullptr,
-                      cut, form))
-        return 2;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    if (cut && form != BatchCutOut::None && !lines && n_rec && cut->m && batch_kept_total(cx.batch, n, n_rec, &n_kept))
-        return 2;
-    ms[2] += since(t0);
-    match_position_t *const d_list = cut ? cx.batch.d_cut : d_pos;
-    const uint64_t n_list = cut ? n_kept : n_rec;
-    if (n_kept_out)
-        *n_kept_out = n_kept;
-    if (step && (*step)(BatchPackOnDevice{cx.batch, d_text, packed, cx.batch.d_off, n, d_list, n_list,
-                                          pl->ref_algo == KREP_RA_AHO_CORASICK})) // (its time is its own)
-        return 2;
-    t0 = clk::now();
-    if (kg::inject(4) || hipMemcpy(res_out, cx.batch.d_res, n * sizeof *res_out, hipMemcpyDeviceToHost) != hipSuccess)
-        return kg::fail("D2H copy of the batch results failed");
-    if (report && n_list)
-    {
-        if (!result_reserve(records, appended + n_list))
-            return kg::fail("out of memory growing match_result_t");
-        if (records_to_host(records->positions + records->count + appended, d_list, n_list))
-            return 2;
-    }
-    ms[3] += since(t0);
-    *n_rec_out = n_rec;
-    return 0;
+    return timed(done->ms.read_back, r.read_back(res_out));
 }
-} // namespace kg
 
 extern "C" void krep_gpu_last_shard_info(krep_gpu_shard_info_t *out) { if (out) *out = tl_shards; }
 

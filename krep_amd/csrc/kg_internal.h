@@ -428,25 +428,32 @@ struct BatchCut
 };
 enum class BatchCutOut { None, Rebased, PackSorted }; // no records; the search's list per item; the grep list (start order within an item's single-pattern list)
 BatchCut batch_cut_rule(const search_params_t *p, const krep_gpu_config_t &c, bool search_file_cap);
-// The record list of one pack (n_rec records in d_pos, the reference's emission order; by_end: a multi-pattern list) cut into the
-// n_items results of s.d_res on `st` (not synchronised): first_record = rec_base + the item's first index when `report`, else rec_base
-// with n_records = 0; lines: count = the distinct lines of the item's record starts, the list is ordered by start on the way and not
-// rebased; else count = the item's records and, with `report`, every record is rebased to its item's first byte.  h_off: the table above.
-// cut (NULL: none, and nothing below is touched): the rule above applied per item; `form` says whether the kept records are written to
-// s.d_cut (Rebased: as `report` rebases them; PackSorted: pack-relative, the displaced memchr record at its place by start).
-// first_record / n_records then describe the kept list; batch_kept_total reads its length once the stream has been waited for.
-int batch_segment(BatchScratch &s, const uint8_t *d_text, uint64_t packed, const uint64_t *h_off, uint64_t n_items, match_position_t *d_pos,
-                  uint64_t n_rec, uint64_t rec_base, bool by_end, bool lines, bool report, hipStream_t st, const BatchCut *cut = nullptr,
-                  BatchCutOut form = BatchCutOut::None);
+// The record list of one pack and how to cut it into the n_items results of BatchScratch::d_res: n_rec records in d_pos, pack-relative,
+// in the reference's emission order (by_end: a multi-pattern list, ascending in end).  first_record = rec_base + the item's first
+// index when `report`, else rec_base with n_records = 0; lines: count = the distinct lines of the item's record starts, the list is
+// ordered by start on the way and not rebased; else count = the item's records and, with `report`, every record is rebased to its
+// item's first byte.  h_off: the table of BatchScratch::d_off on the host.  cut (NULL: none, and no buffer of the cut is touched): the
+// rule above applied per item; `form` says whether the kept records are written to BatchScratch::d_cut (Rebased: as `report` rebases
+// them; PackSorted: pack-relative, the displaced memchr record at its place by start); first_record / n_records then describe the
+// kept list, and batch_kept_total reads its length once the stream has been waited for.
+struct BatchSegment
+{
+    const uint8_t *d_text;
+    uint64_t packed;
+    const uint64_t *h_off;
+    uint64_t n_items;
+    match_position_t *d_pos;
+    uint64_t n_rec, rec_base;
+    bool by_end, lines, report;
+    const BatchCut *cut;
+    BatchCutOut form;
+};
+int batch_segment(BatchScratch &s, const BatchSegment &g, hipStream_t st); // (queued on `st`, not synchronised)
 int batch_kept_total(const BatchScratch &s, uint64_t n_items, uint64_t n_rec, uint64_t *n_kept); // (a cut with records, n_rec > 0)
 // (the next pack of a batch on the host — its offset table, the bytes of any slice of it: kg_batch_pack.h, batch_pack_offsets / batch_fill)
-// kg_exec.hip — one pack through the device context of cfg.device: gathered through the staging ring into the arena, scanned in one
-// window with the records plan `scan_params`, segmented, read back.  res_out[n]: the items' results; with `report` the rebased records go
-// to records->positions behind records->count + appended (the block grows, count is left alone: a later failure appends nothing).
-// ms[4] += wall clock of packing / scan / segmentation / read-back.  2: failed.
-// step (NULL: none, krep_gpu_search_batch): called between the segmentation and the read-back with the pack as it lies on the device
-// (krep_gpu_grep_batch formats it there); a step that returns non-zero fails the pack.
-struct BatchPackOnDevice
+// kg_exec.hip — one pack through the device context of cfg->device (host_batch_pack): gathered through the staging ring into the arena,
+// scanned in one window with the records plan `scan`, segmented, read back.
+struct BatchPackOnDevice // the pack as it lies on the device behind the segmentation
 {
     BatchScratch &scratch;
     const uint8_t *d_text;
@@ -458,10 +465,36 @@ struct BatchPackOnDevice
     bool by_end;
 };
 using BatchStep = std::function<int(const BatchPackOnDevice &)>;
-int host_batch_pack(const search_params_t *scan_params, const krep_gpu_config_t &cfg, const krep_gpu_batch_item_t *items, size_t n,
-                    const uint64_t *off, bool lines, bool report, match_result_t *records, uint64_t appended,
-                    krep_gpu_batch_result_t *res_out, uint64_t *n_rec_out, float *kernel_ms, double *ms, const BatchStep *step = nullptr,
-                    const BatchCut *cut = nullptr, BatchCutOut form = BatchCutOut::None, uint64_t *n_kept_out = nullptr);
+struct BatchTimes // wall clock of a call's stages, ms (krep_gpu_debug_batch_times, krep_gpu_debug_grep_batch_times)
+{
+    double pack = 0, scan = 0, segment = 0, format = 0, read_back = 0;
+    void operator+=(const BatchTimes &t) { pack += t.pack, scan += t.scan, segment += t.segment, format += t.format, read_back += t.read_back; }
+};
+struct BatchPackJob
+{
+    const search_params_t *scan; // the records plan's params
+    const krep_gpu_config_t *cfg;
+    const krep_gpu_batch_item_t *items; // [n], and off[n + 1]: batch_pack_offsets
+    size_t n;
+    const uint64_t *off;
+    bool lines, report; // as BatchSegment
+    // with `report` the rebased records go to records->positions behind records->count + appended (the block grows, count is left
+    // alone: a later failure appends nothing)
+    match_result_t *records;
+    uint64_t appended;
+    // (NULL: none, krep_gpu_search_batch) called between the segmentation and the read-back with the pack as it lies on the device
+    // (krep_gpu_grep_batch formats it there); a step that returns non-zero fails the pack, and its time is its own
+    const BatchStep *step;
+    const BatchCut *cut; // as BatchSegment
+    BatchCutOut form;
+};
+struct BatchPackDone
+{
+    uint64_t n_rec = 0, n_kept = 0; // the records of the scan; under a cut with records: those kept
+    float kernel_ms = 0;
+    BatchTimes ms; // pack, scan, segment, read_back of this pack (of one that failed: as far as it got)
+};
+int host_batch_pack(const BatchPackJob &job, krep_gpu_batch_result_t *res_out /* [job.n] */, BatchPackDone *done); // 2: failed
 
 // kg_batch_format.hip — the formatters over a pack behind krep_gpu_format_lines_items / krep_gpu_format_matches_items.  grow (NULL:
 // none): asked for the output buffer once the size is known (-> a device buffer of at least that many bytes, NULL: it failed and said

@@ -1,6 +1,7 @@
 """ctypes binding of include/krep_gpu.h.  Plumbing only — every search runs in libkrep_gpu.so."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -22,6 +23,19 @@ def _libc_free(ptr: int):
 
 class KrepGpuError(RuntimeError):
     pass
+
+
+@contextlib.contextmanager
+def _borrowed_trie(params: "abi.Params"):
+    """"caller pre-built the trie" (krep.c:2528) for the calls inside: a multi-pattern search without ac_trie is answered with no
+    match (aho_corasick.c:306), so params.s.ac_trie points at a dummy meanwhile and is NULL again afterwards"""
+    dummy = C.c_int(0)
+    if params.s.num_patterns > 1 and not params.s.ac_trie:
+        params.s.ac_trie = C.cast(C.pointer(dummy), C.c_void_p)
+    try:
+        yield
+    finally:
+        params.s.ac_trie = None
 
 
 class Engine:
@@ -641,19 +655,16 @@ class Engine:
         fn = (self.lib.krep_gpu_regex_search if params.s.use_regex else
               self.lib.krep_gpu_aho_corasick_search if params.s.num_patterns > 1 else self.lib.krep_gpu_literal_search)
         res = self.lib.krep_gpu_match_result_init(16) if want_result else None
-        dummy = C.c_int(0)
-        if params.s.num_patterns > 1 and not params.s.ac_trie:
-            params.s.ac_trie = C.cast(C.pointer(dummy), C.c_void_p)  # "caller pre-built the trie" (krep.c:2528)
         try:
-            self.lib.krep_gpu_clear_error()
-            ret = fn(params.ref, ptr, n, res)
+            with _borrowed_trie(params):
+                self.lib.krep_gpu_clear_error()
+                ret = fn(params.ref, ptr, n, res)
             if self.last_status() == abi.STATUS_FAILED:
                 raise KrepGpuError(self.last_error() or "krep-gpu operator failed")
             pos = abi.result_positions(res) if res else None
         finally:
             if res:
                 self.lib.krep_gpu_match_result_free(res)
-            params.s.ac_trie = None
         del keep
         return int(ret), pos
 
@@ -690,27 +701,18 @@ class Engine:
         """krep_gpu_search_batch(params, items): [(count, positions[(n, 2) uint64])] in item order, every position relative to its
         item's first byte; `items` are bytes or np.uint8 arrays.  Raises KrepGpuError with the library's reason on 2 (a refused
         search included: there is no CPU fallback).  want_info: -> (that list, abi.BatchInfo)."""
-        n = len(items)
-        arr = (abi.BatchItem * max(n, 1))()
-        keep = []
-        for i, it in enumerate(items):
-            ptr, ln, k = self._ptr(it)
-            keep.append(k)
-            arr[i].text, arr[i].len = (ptr.value if ln else None), ln
+        arr, n, keep = self.batch_items(items)
         res = (abi.BatchResult * max(n, 1))()
         rec = self.lib.krep_gpu_match_result_init(16)
         info = abi.BatchInfo()
-        dummy = C.c_int(0)
-        if params.s.num_patterns > 1 and not params.s.ac_trie:
-            params.s.ac_trie = C.cast(C.pointer(dummy), C.c_void_p)  # "caller pre-built the trie" (krep.c:2528)
         try:
-            rc = self.lib.krep_gpu_search_batch(params.ref, C.byref(cfg) if cfg is not None else None, arr, n, res, rec, C.byref(info))
+            with _borrowed_trie(params):
+                rc = self.lib.krep_gpu_search_batch(params.ref, C.byref(cfg) if cfg is not None else None, arr, n, res, rec, C.byref(info))
             if rc:
                 raise KrepGpuError(self.last_error() or "krep_gpu_search_batch failed")
             pos = abi.result_positions(rec)
         finally:
             self.lib.krep_gpu_match_result_free(rec)
-            params.s.ac_trie = None
         del keep
         out = [(int(r.count), pos[int(r.first_record):int(r.first_record) + int(r.n_records)]) for r in res[:n]]
         return (out, info) if want_info else out
@@ -797,18 +799,15 @@ class Engine:
         per = (abi.GrepItem * max(n, 1))()
         out = abi.GrepOutput(None, 0, 0)
         info = abi.BatchInfo()
-        dummy = C.c_int(0)
-        if params.s.num_patterns > 1 and not params.s.ac_trie:
-            params.s.ac_trie = C.cast(C.pointer(dummy), C.c_void_p)  # "caller pre-built the trie" (krep.c:2528)
         try:
-            rc = self.lib.krep_gpu_grep_batch(params.ref, C.byref(cfg), arr, n, C.byref(fmt), per, C.byref(out), C.byref(info))
+            with _borrowed_trie(params):
+                rc = self.lib.krep_gpu_grep_batch(params.ref, C.byref(cfg), arr, n, C.byref(fmt), per, C.byref(out), C.byref(info))
             if rc:
                 raise KrepGpuError(self.last_error() or "krep_gpu_grep_batch failed")
             data = C.string_at(out.bytes, out.len) if out.len else b""
         finally:
             if out.bytes:
                 _libc_free(out.bytes)
-            params.s.ac_trie = None
         del keep, keep_fmt
         res = [(int(p.count), int(p.out_offset), int(p.out_bytes)) for p in per[:n]]
         return (data, res, info) if want_info else (data, res)
