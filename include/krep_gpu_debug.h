@@ -114,6 +114,12 @@ void krep_gpu_debug_grep_batch_times(double *pack_ms, double *scan_ms, double *s
 /* test hook: calls of the pack formatters (krep_gpu_format_lines_items / krep_gpu_format_matches_items) that looked a record's item up
  * with the offset table in LDS (items + 1 <= 4096 entries) and with the table in global memory, since the process started */
 void krep_gpu_debug_batch_format_launches(uint64_t *lds_table, uint64_t *global_table);
+/* test hook: the prefix scan every formatter, the batch segmentation and the line analysis share (kg_format.hip scan_exclusive), alone:
+ * d_out[i] = d_in[0] + .. + d_in[i - 1] mod 2^64, or with take_max the largest of them (0 in front of the first), for n 64-bit words on the
+ * device; synchronises `stream` before it returns.  d_out must be a buffer of its own: the scan's kernels take both pointers as
+ * __restrict__ and no caller in the library scans in place, so d_out == d_in is not supported and is refused.  Nothing behind
+ * d_out[n - 1] is written.  Returns 0, or 2 (tests/test_gpu_scan_exclusive.py) */
+int krep_gpu_debug_scan_exclusive(const uint64_t *d_in, uint64_t n, uint64_t *d_out, int take_max, void *stream);
 
 #ifdef __cplusplus
 }

@@ -416,3 +416,27 @@ extern "C" int krep_gpu_line_numbers_ex(const void *d_text, size_t text_len, siz
 done:
     return rc;
 }
+
+// test hook (krep_gpu_debug.h): kg::scan_exclusive alone, its `sums` words from the formatter scratch
+extern "C" int krep_gpu_debug_scan_exclusive(const uint64_t *d_in, uint64_t n, uint64_t *d_out, int take_max, void *stream)
+{
+    if (!n)
+        return 0;
+    if (!d_in || !d_out || d_in == d_out)
+        return fail("krep_gpu_debug_scan_exclusive: d_in / d_out is NULL, or they are one buffer");
+    if (scan_sums_words(n) > 0x7fffffffull)
+        return fail("krep_gpu_debug_scan_exclusive: %llu words are more than one call takes", (unsigned long long)n);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(g_fmt_mu);
+    int rc = 0;
+    {
+        void *base = nullptr;
+        if (fmt_reserve(scan_sums_words(n) * sizeof(u64), &base))
+            return 2;
+        scan_exclusive((const u64 *)d_in, n, (u64 *)d_out, (u64 *)base, take_max != 0, st);
+        FCHK(hipGetLastError());
+        FCHK(hipStreamSynchronize(st));
+    }
+done:
+    return rc;
+}

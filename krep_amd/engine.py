@@ -128,6 +128,11 @@ class Engine:
         L.krep_gpu_order_by_start.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.c_void_p]
         L.krep_gpu_line_numbers.restype = C.c_int
         L.krep_gpu_line_numbers.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.krep_gpu_line_numbers_ex.restype = C.c_int
+        L.krep_gpu_line_numbers_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        if hasattr(L, "krep_gpu_debug_scan_exclusive"):  # (an older build of the library as an A/B partner lacks it)
+            L.krep_gpu_debug_scan_exclusive.restype = C.c_int
+            L.krep_gpu_debug_scan_exclusive.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]
         if hasattr(L, "krep_gpu_format_lines"):  # (an older build of the library as an A/B partner lacks them)
             L.krep_gpu_matching_lines.restype = C.c_int
             L.krep_gpu_matching_lines.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -561,10 +566,19 @@ class Engine:
         if self.lib.krep_gpu_order_by_start(C.c_void_p(d_positions), n, text_len, C.c_void_p(stream)):
             raise KrepGpuError("krep_gpu_order_by_start failed: " + self.last_error())
 
-    def line_numbers(self, d_text: int, text_len: int, d_positions: int, n: int, d_lines: int, stream: int = 0):
-        if self.lib.krep_gpu_line_numbers(C.c_void_p(d_text), text_len, C.c_void_p(d_positions), n, C.c_void_p(d_lines),
-                                          C.c_void_p(stream)):
-            raise KrepGpuError("krep_gpu_line_numbers failed: " + self.last_error())
+    def line_numbers(self, d_text: int, text_len: int, d_positions: int, n: int, d_lines: int, stream: int = 0, global_base: int = 0):
+        """krep_gpu_line_numbers_ex(): the text_len bytes at d_text are text[global_base:], the records carry global offsets; the line
+        numbers count from the buffer's first byte, and a record that starts outside the buffer gets 0"""
+        if self.lib.krep_gpu_line_numbers_ex(C.c_void_p(d_text), text_len, global_base, C.c_void_p(d_positions), n, C.c_void_p(d_lines),
+                                             C.c_void_p(stream)):
+            raise KrepGpuError("krep_gpu_line_numbers_ex failed: " + self.last_error())
+
+    def scan_exclusive(self, d_in: int, n: int, d_out: int, take_max: bool = False, stream: int = 0):
+        """test hook: the formatters' exclusive prefix scan of n 64-bit device words (the sum mod 2^64, or the running maximum), d_in
+        into d_out, a buffer of its own"""
+        if self.lib.krep_gpu_debug_scan_exclusive(C.c_void_p(d_in) if d_in else None, n, C.c_void_p(d_out) if d_out else None,
+                                                  int(bool(take_max)), C.c_void_p(stream) if stream else None):
+            raise KrepGpuError("krep_gpu_debug_scan_exclusive failed: " + self.last_error())
 
     # ---- the matching lines themselves (print_matching_items(), full-line mode without colour, krep.c:797-1071) ----
     def matching_lines(self, d_text: int, text_len: int, d_positions: int, n: int, max_lines: int = abi.SIZE_MAX, d_lines: int = 0,

@@ -42,6 +42,16 @@ JOBS = [
 ]
 
 
+# (level, pattern bytes, params kwargs) of test_block_loop_count_lines_in_pieces (also tests/high_offset_cases.py)
+BLOCK_JOBS = [(abi.REF_AVX512, 40, dict(count_lines=True)), (abi.REF_AVX512, 64, dict(count_lines=True, whole_word=True)),
+              (abi.REF_AVX2, 20, dict(count_lines=True, whole_word=True)), (abi.REF_AVX2, 32, dict(count_lines=True, whole_word=True)),
+              (abi.REF_AVX512, 33, dict(count_lines=True)),
+              # neon_search (arm64 builds): no restart on an unterminated line — the grid origin of the previous counted line
+              # rides on the record as well
+              (abi.REF_NEON, 3, dict(count_lines=True)), (abi.REF_NEON, 9, dict(count_lines=True, whole_word=True)),
+              (abi.REF_NEON, 16, dict(count_lines=True))]
+
+
 def _text(rng, n, cuts):
     text = cases.rand_text(rng, n, b"aab _\n")
     text[: n // 3] = cases.rand_text(rng, n // 3, b"ab")  # a third of it is one dense field of overlapping occurrences
@@ -161,13 +171,7 @@ def test_block_loop_count_lines_in_pieces(gpu, oracle_engine, shards):
     record.  Sharded and streamed, against the compiled reference."""
     rng = np.random.RandomState(900 + shards)
     fix0 = gpu.chain_fixups()
-    jobs = [(abi.REF_AVX512, 40, dict(count_lines=True)), (abi.REF_AVX512, 64, dict(count_lines=True, whole_word=True)),
-            (abi.REF_AVX2, 20, dict(count_lines=True, whole_word=True)), (abi.REF_AVX2, 32, dict(count_lines=True, whole_word=True)),
-            (abi.REF_AVX512, 33, dict(count_lines=True)),
-            # neon_search (arm64 builds): no restart on an unterminated line — the grid origin of the previous counted line
-            # rides on the record as well
-            (abi.REF_NEON, 3, dict(count_lines=True)), (abi.REF_NEON, 9, dict(count_lines=True, whole_word=True)),
-            (abi.REF_NEON, 16, dict(count_lines=True))]
+    jobs = BLOCK_JOBS
     for n in (150_003, 64 * 2500 + 17, 3 * (1 << 20) + 99):
         share = (n + shards - 1) // shards
         for variant in range(4):

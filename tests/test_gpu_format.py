@@ -18,6 +18,9 @@ def gpu():
     return e
 
 
+EDGE_TEXT = b"\n\nab\nabab\n" + b"x" * 5000 + b"\nab"  # (also tests/test_gpu_high_offset_records.py)
+
+
 def test_order_by_start_and_line_numbers_on_the_device(gpu):
     import torch
     import bench
@@ -45,7 +48,7 @@ def test_order_by_start_and_line_numbers_on_the_device(gpu):
 
 def test_line_numbers_edge_cases(gpu):
     import torch
-    text = np.frombuffer(b"\n\nab\nabab\n" + b"x" * 5000 + b"\nab", dtype=np.uint8).copy()
+    text = np.frombuffer(EDGE_TEXT, dtype=np.uint8).copy()
     buf = torch.from_numpy(text).cuda()
     ret, pos = gpu.search(abi.Params([b"ab"]), text)
     d_pos = torch.from_numpy(pos.astype(np.int64)).cuda().contiguous()
