@@ -90,6 +90,31 @@ int krep_gpu_debug_anchor_info(const krep_gpu_plan_t *plan, int *state, uint32_t
 /* what the last general-kernel scan of `plan` MEASURED (candidates per tested position, counted in the kernel), and how many times a
  * measurement that contradicted the estimate re-opened the decision (at most 3; $KREP_GPU_AC_NO_RESAMPLE=1: never) */
 int krep_gpu_debug_anchor_measured(const krep_gpu_plan_t *plan, double *measured, int *resamples);
+/* which kernel answered the last multi-pattern scan of one dictionary of `plan`, and with what (kg_ac.hip ac_scan; host values only) */
+typedef struct krep_gpu_debug_ac_scan
+{
+    uint32_t road;      /* 0 early-out (nothing launched), 1 byte-set one-pass (kg_single.hip), 2 tiny one-pass (items), 3 tiny one-pass (dense),
+                           4 tiny staged (kg_ac_tiny.hip), 5 the general kernel ac_scan_kernel<CI, LINES, SHORT, STRIDE, ANCH, WW> */
+    uint32_t ci, lines; /* -i, in-kernel -c */
+    uint32_t shorts;    /* the dictionary holds a 1..3-byte pattern (SHORT) */
+    uint32_t stride;    /* 1 or 2 (0: the scan left before its arguments were made) */
+    uint32_t anch;      /* 0 end grams, 1 anchored on four classes, 2 on five */
+    uint32_t ww_filter; /* the WW instantiation was launched (-w, stride 2, no short pattern) */
+    uint32_t exact;     /* the exact dictionary (xtab) was passed */
+    uint32_t g4x_mode;
+    uint32_t stage_cap; /* staged matches per unit as launched (0: no records wanted, or a one-pass road) */
+    uint32_t upt;       /* units per ticket */
+    uint64_t n_units;
+    uint64_t overflow_units; /* units with more matches than stage_cap */
+    uint32_t emit;      /* the emit pass: 0 none, 1 over the redo list, 2 a walk over every unit */
+    uint32_t next_stage_cap; /* what the scan left for the dictionary's following scan */
+    uint32_t short_lens;     /* bit k - 1: the dictionary holds a pattern of k bytes, k = 1..3 */
+    uint64_t scans;     /* scans this dictionary has reported so far: a report is the last call's iff this moved by one */
+} krep_gpu_debug_ac_scan_t;
+/* part 0: the plan's dictionary, or the long part of a split plan (krep_gpu_debug_split_state() == 2); part 1: the short part of a split
+ * plan.  Returns 0, or 2 for a single-literal plan and for a part that does not exist.  A dictionary that has not scanned yet reports
+ * scans == 0 and zeroes. */
+int krep_gpu_debug_ac_last_scan(const krep_gpu_plan_t *plan, int part, krep_gpu_debug_ac_scan_t *out);
 /* test hook of krep_gpu_search_batch(): the packed size at which a batch is cut into a further pack (0 = the default, two pieces of
  * the configuration's stream_chunk_bytes), so that a batch of a few hundred KiB takes several scans */
 void krep_gpu_debug_batch_pack_limit(size_t bytes);

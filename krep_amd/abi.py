@@ -216,6 +216,17 @@ class SeqCarry(C.Structure):
                 ("local_last", C.c_uint64), ("local_lines", C.c_uint64)]
 
 
+class AcScan(C.Structure):
+    """krep_gpu_debug_ac_scan_t (include/krep_gpu_debug.h): which multi-pattern kernel answered a dictionary's last scan"""
+    _fields_ = [("road", C.c_uint32), ("ci", C.c_uint32), ("lines", C.c_uint32), ("shorts", C.c_uint32), ("stride", C.c_uint32),
+                ("anch", C.c_uint32), ("ww_filter", C.c_uint32), ("exact", C.c_uint32), ("g4x_mode", C.c_uint32),
+                ("stage_cap", C.c_uint32), ("upt", C.c_uint32), ("n_units", C.c_uint64), ("overflow_units", C.c_uint64),
+                ("emit", C.c_uint32), ("next_stage_cap", C.c_uint32), ("short_lens", C.c_uint32), ("scans", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 SEARCH_FUNC = C.CFUNCTYPE(C.c_uint64, C.POINTER(SearchParams), C.c_char_p, C.c_size_t,
                           C.POINTER(MatchResult))
 

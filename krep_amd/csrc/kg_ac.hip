@@ -1114,6 +1114,8 @@ struct AcRun
     bool lines_on_list = false; // AcOwn::LinesOnList
     int fsc = 0;       // krep_gpu_debug_force_stage_cap (0: the dictionary's own slot)
     bool tiny = false; // the staged road: the register-compare kernel (kg_ac_tiny.hip), else the general one
+    // for krep_gpu_debug_ac_last_scan (ac_report): the road as krep_gpu_debug_ac_scan_t numbers it, a one-pass road's ticket, the emit pass
+    u32 road = 0, one_pass_upt = 0, emit = 0;
 };
 constexpr int kAcNext = -1;
 // max_count 0, the empty text (its one empty match), an empty own range, -c with a newline inside a pattern
@@ -1306,7 +1308,7 @@ static void tiny_reopen(AcTables *t, u64 total, u64 n_units)
 // entries, matches decoded where they are found — which takes the scan again and the dictionary's next ones (up to ~15 % of
 // the bytes; a long length included, which the item flavour does not take).  Beyond that, and for 4-byte patterns beside a long
 // length, the staging road; every decision is re-evaluated by the following scans.
-static int ac_tiny_one_pass(const AcScan &c, const AcRun &r, krep_gpu_scan_out_t *out)
+static int ac_tiny_one_pass(const AcScan &c, AcRun &r, krep_gpu_scan_out_t *out)
 {
     AcTables *t = c.t;
     Counters *h_ctr = c.h_ctr;
@@ -1345,6 +1347,8 @@ static int ac_tiny_one_pass(const AcScan &c, const AcRun &r, krep_gpu_scan_out_t
                     dense ? "dense" : "items", f.upt, (unsigned long long)h_ctr->total, per_unit, (unsigned long long)h_ctr->overflow_units);
         if (!h_ctr->overflow_units)
         {
+            r.road = dense ? 3u : 2u;
+            r.one_pass_upt = f.upt;
             if (ac_result(c, r, false, out)) // (track: one_pass_ok asks for it)
                 return 2;
             if (dense)
@@ -1491,7 +1495,7 @@ static void ac_learn(const AcScan &c, const AcRun &r)
         t->set_ok = true;
 }
 // ---- the units whose matches did not fit their staging slot: scanned again in emit mode, each writing at its own offset
-static int ac_emit(const AcScan &c, const AcRun &r)
+static int ac_emit(const AcScan &c, AcRun &r)
 {
     AcTables *t = c.t;
     const u64 n_units = r.a.num_tiles;
@@ -1513,10 +1517,42 @@ static int ac_emit(const AcScan &c, const AcRun &r)
             e.redo_list = t->d_redo, e.n_redo = (u32)n_over;
         }
     }
+    r.emit = e.redo_list ? 1u : 2u;
     HIPCHK(ac_staged_launch(c, r, e));
     if (c.time_it) HIPCHK(hipEventRecord(c.ev1, c.st));
     HIPCHK(hipStreamSynchronize(c.st));
     return 0;
+}
+// test hook (krep_gpu_debug_ac_last_scan): what the scan that just ended ran with, as the launch rules above decided it
+static void ac_report(const AcScan &c, const AcRun &r)
+{
+    const AcArgs &a = r.a;
+    krep_gpu_debug_ac_scan_t &o = c.t->last;
+    const uint64_t scans = o.scans + 1;
+    o = krep_gpu_debug_ac_scan_t{};
+    o.scans = scans;
+    o.road = r.road;
+    o.next_stage_cap = c.t->stage_cap;
+    o.short_lens = (c.t->has1 ? 1u : 0u) | (c.t->has2 ? 2u : 0u) | (c.t->has3 ? 4u : 0u);
+    o.shorts = o.short_lens != 0;
+    o.ci = c.t->ci;
+    if (r.road == 0)
+        return;
+    const bool general = r.road == 5;
+    o.lines = c.lines;
+    o.stride = a.stride;
+    // (ac_launch2 / ac_launch3: the anchored and the WW instantiations)
+    const bool anchored = general && !c.lines && a.anch && a.stride == 2 && !o.shorts;
+    o.anch = anchored ? (a.anch_five ? 2u : 1u) : 0u;
+    o.ww_filter = general && a.stride == 2 && !o.shorts && (a.flags & F_WW) != 0;
+    o.exact = a.xtab != nullptr;
+    o.g4x_mode = a.g4x_mode;
+    o.n_units = a.num_tiles;
+    const bool staged = r.road >= 4;
+    o.stage_cap = staged ? a.stage_cap : 0u;
+    o.upt = staged ? a.upt : r.one_pass_upt;
+    o.overflow_units = (staged && r.want) ? c.h_ctr->overflow_units : 0;
+    o.emit = r.emit;
 }
 int ac_scan(const AcScan &c, krep_gpu_scan_out_t *out)
 {
@@ -1524,12 +1560,22 @@ int ac_scan(const AcScan &c, krep_gpu_scan_out_t *out)
     AcRun r;
     r.own_hi = std::min(c.own_hi, c.text_len);
     int rc = ac_early_out(c, r.own_hi, out);
-    if (rc == kAcNext) rc = ac_args(c, r) ? 2 : ac_byte_set(c, r, out);
+    if (rc == kAcNext)
+    {
+        r.road = 1; // (the byte set's when it answers; the tiny one-pass road names its flavour)
+        rc = ac_args(c, r) ? 2 : ac_byte_set(c, r, out);
+    }
     if (rc == kAcNext) rc = ac_tiny_one_pass(c, r, out);
-    if (rc != kAcNext) return rc;
+    if (rc != kAcNext)
+    {
+        if (!rc) ac_report(c, r);
+        return rc;
+    }
     if (ac_staged(c, r)) return 2;
+    r.road = r.tiny ? 4u : 5u;
     ac_learn(c, r);
     if (r.want && c.h_ctr->overflow_units && ac_emit(c, r)) return 2;
+    ac_report(c, r);
     return ac_result(c, r, true, out);
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include <functional>
 #include <vector>
+#include "../../include/krep_gpu_debug.h" // (krep_gpu_debug_ac_scan_t)
 #include "kg_ac_common.h"
 
 namespace kg {
@@ -73,6 +74,7 @@ struct AcTables
     double anch_measured = 0;                 // candidates per tested position the last general-kernel scan counted (Counters::candidates)
     double anch_rate0 = 0, anch_rate = 0;     // estimated candidates per tested position: end grams / anchor grams (diagnostic)
     u32 anch_moved = 0;                       // patterns whose anchor is not their end
+    krep_gpu_debug_ac_scan_t last{};          // test hook: what the dictionary's last scan ran with (kg_ac.hip ac_report)
 };
 // kg_ac_anchor.hip
 constexpr int kAnchResamples = 3; // (a session that alternates kinds of text settles on the last decision after three repeats)

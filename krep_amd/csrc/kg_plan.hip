@@ -228,6 +228,16 @@ extern "C" int krep_gpu_debug_anchor_measured(const krep_gpu_plan_t *pl, double 
     if (resamples) *resamples = pl->ac->anch_resamples;
     return 0;
 }
+extern "C" int krep_gpu_debug_ac_last_scan(const krep_gpu_plan_t *pl, int part, krep_gpu_debug_ac_scan_t *out)
+{
+    if (!pl || !pl->ac || !out || part < 0 || part > 1)
+        return 2;
+    const bool split = pl->ac_split == 2 && pl->ac_long && pl->ac_short;
+    if (part == 1 && !split)
+        return 2;
+    *out = (part == 1 ? pl->ac_short : split ? pl->ac_long : pl->ac)->last;
+    return 0;
+}
 extern "C" int krep_gpu_debug_anchor_info(const krep_gpu_plan_t *pl, int *state, uint32_t *moved, double *rate_end_grams, double *rate_anchors)
 {
     if (!pl || !pl->ac)

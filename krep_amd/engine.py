@@ -270,6 +270,9 @@ class Engine:
         if hasattr(L, "krep_gpu_debug_anchor_measured"):
             L.krep_gpu_debug_anchor_measured.restype = C.c_int
             L.krep_gpu_debug_anchor_measured.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        if hasattr(L, "krep_gpu_debug_ac_last_scan"):
+            L.krep_gpu_debug_ac_last_scan.restype = C.c_int
+            L.krep_gpu_debug_ac_last_scan.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.AcScan)]
         L.krep_gpu_last_shard_info.restype = None
         L.krep_gpu_last_shard_info.argtypes = [C.POINTER(abi.ShardInfo)]
         L.krep_gpu_available.restype = C.c_int
@@ -1315,6 +1318,15 @@ class Plan:
         if self.eng.lib.krep_gpu_debug_anchor_measured(self.h, C.byref(m), C.byref(r)):
             return None
         return float(m.value), int(r.value)
+
+    def ac_last_scan(self, part: int = 0):
+        """krep_gpu_debug_ac_last_scan(): the report of the last multi-pattern scan as a dict (road, ci, lines, shorts, stride, anch,
+        ww_filter, exact, g4x_mode, stage_cap, upt, n_units, overflow_units, emit, next_stage_cap, short_lens, scans); part 1: the short
+        part of a split plan.  None: a single-literal plan, or no such part."""
+        rep = abi.AcScan()
+        if self.eng.lib.krep_gpu_debug_ac_last_scan(self.h, int(part), C.byref(rep)):
+            return None
+        return rep.as_dict()
 
     def scan_seq(self, d_text: int, text_len: int, own_lo, own_hi, global_base=0, d_positions: int = 0, capacity: int = 0,
                  global_len=0, carry_in: "abi.SeqCarry | None" = None):
