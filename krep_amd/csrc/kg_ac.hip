@@ -22,6 +22,18 @@
 // -w, -c (line counting), max_count and start-offset ownership are applied exactly as in the literal
 // kernel.  A dense DFA in LDS is impossible for the benchmark set (8605 states x 256 x 2 B = 4.4 MB
 // against 160 KiB), which is why the LDS holds the filter, not the automaton.
+// The kernel below is the set-up, the ticket, unit and round loops, and calls; its stages are in kg_ac_scan_dev.h (AcWave: what a wave's
+// stages share).  stage: in -> out [instantiations]
+//   ac_round_before: text, have, carry -> the 4 bytes in front of the round, scalar [all]
+//   ac_pair_round (ac_pair_issue, ac_pair_finish): the round in d[] -> cbits, 8 bits per lane-cell; the next round into d[] [stride 2 without -c]
+//   ac_cell_round -> ac_filter_cell: the round in d[], windows -> cbits, 16 bits per lane-cell; nlmap [stride 1, -c]
+//   ac_ragged_round -> ac_filter_cell: text bytes, bounds-checked -> cbits, nlmap [all: the round at the text's end]
+//   ac_anchor_stage2 (ac_anchor_locate, _fetch, _gram, _pick, _mark): cbits, text windows, anchor buckets -> ebits [ANCH 1, 2]
+//   ac_verify_ends: one END pair per lane -> counts, depth masks or the level walk's verdict [all]
+//   ac_rank_and_emit (ac_emit_write): a verified batch -> staged words or final records, the -c hit bitmap, wcnt [all]
+//   ac_pend_unit (ac_pend_flush, ac_pend_recount, ac_pend_pos): ebits, pend, npend, ucnt -> verify batches of 64 over the ticket's units [ANCH 1, 2]
+//   ac_verify_count, ac_verify_batch: cbits -> the unit's candidate ranks; one verify batch of the kernel's loop [ANCH 0]
+//   ac_unit_lines [-c]; ac_unit_info | ac_ticket_info | ac_ticket_unpark: bitmap, nlmap -> LineState; wcnt | ucnt | park_* -> info words, overflow report, parked stores
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +45,7 @@
 
 #include "../../include/krep_gpu.h"
 #include "kg_ac_common.h"
+#include "kg_ac_scan_dev.h"
 #include "kg_ac_tables.h"
 #include "kg_internal.h"
 
@@ -43,9 +56,6 @@ namespace kg {
 // pattern's final 4-gram (a match ends at the tested position t), the 4-gram one byte earlier (the match ends at t + 1;
 // for a 4-byte pattern that gram has an unknown first byte: all 32 classes are set).  Half the LDS lookups — the
 // bank-conflict wall of 4.2 — and half the lookup VALU; a candidate verifies both ends, with both probes in flight.
-#ifndef KG_AC_LINES_ROLL_CELLS
-#define KG_AC_LINES_ROLL_CELLS 4 // cells (1 KiB each) of the next round a -c scan prefetches (A/B: krep_amd/build.py --variant x -DKG_AC_LINES_ROLL_CELLS=8)
-#endif
 // ANCH (round 6, kg_ac_anchor.hip; only with STRIDE == 2, no short patterns, no -c): the table holds rarity-chosen ANCHOR grams.
 // A candidate's exact anchor gram names the offsets k at which patterns END behind it; those ends are marked in a second bitmap
 // of the unit — same layout as the candidate bitmap: bit b <-> the END pair (2b + 1, 2b + 2), in the KiB that otherwise parks a
@@ -71,34 +81,25 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
         s_mem[w] = a.filter[w];
     const u32 fw = (a.filter_words + 3u) & ~3u;
     constexpr u32 kPerWave = kAcBitmapWords + (LINES ? 2u * kAcBitmapWords : 0u); // candidate | hit | newline bitmaps
-    constexpr u32 XB = LINES ? kXBitsLines : kXBitsBig; // index bits of the exact-class table
-    constexpr u32 kTabMask = XB == 20 ? 0x1fffcu : 0xfffcu; // byte address of a pair-layout slot
-    constexpr bool PAIR = STRIDE == 2;                  // pair-layout table, odd positions tested (see cell_body)
-    constexpr bool PIPE = PAIR && !LINES;               // ... with the table reads software-pipelined over the cells of a round
-    // -c owns a match by its END and records it in the unit's hit bitmap, so the end j + 2 of the unit's last candidate bit
-    // (= the first byte of the next unit) cannot be reported from here: every unit instead verifies one EXTRA candidate, the
-    // tested position in front of its first byte, for its second end only
-    constexpr bool XCAND = PAIR && LINES;
-    // candidate bitmap of the unit: one bit per end position, written as the lane's 16-bit filter result per cell —
-    // entry (r * 8 + j) * 64 + lane, so that index order is position order
-    u32 *cbits = s_mem + fw + wave * kPerWave;
-    unsigned short *cbits16 = reinterpret_cast<unsigned short *>(cbits);
+    constexpr bool PIPE = STRIDE == 2 && !LINES; // pair-layout table with the table reads software-pipelined over the cells of a round
+    constexpr bool kPend = ac_pends(LINES, SHORT, STRIDE, ANCH);
+    constexpr int kRoll = ac_roll_cells(LINES, STRIDE, ANCH);
     // PIPE: the pair filter only ever sets the even bits of a lane's 16-bit result, so it stores EIGHT bits per lane and cell
     // (bit q <-> tested position 2q + 1): the bitmap is 1 KiB, lane L owns 4 dwords, and the other KiB of the wave's bitmap
     // area parks the info words and staging slots of a ticket's units until the ticket's end (store
     // placement: the waves store nothing while they stream)
-    constexpr u32 kWPL = PIPE ? 4u : 8u; // bitmap dwords per enumerating lane (256 positions)
-    uint8_t *cbits8 = reinterpret_cast<uint8_t *>(cbits);
-    u32 *park_slots = cbits + 256;       // [kAcUnitsPerTicketMax][16] staged words
-    u64 *park_info = reinterpret_cast<u64 *>(cbits + 256 + kAcUnitsPerTicketMax * 16); // [kAcUnitsPerTicketMax]
-    u32 *bitmap = cbits + kAcBitmapWords;
-    unsigned short *nlmap = reinterpret_cast<unsigned short *>(bitmap + kAcBitmapWords); // 16 bits per lane and cell
+    AcWave wv;
+    wv.cbits = s_mem + fw + wave * kPerWave;
+    wv.park_slots = wv.cbits + 256;
+    wv.park_info = reinterpret_cast<u64 *>(wv.cbits + 256 + kAcUnitsPerTicketMax * 16);
+    wv.bitmap = wv.cbits + kAcBitmapWords;
+    wv.nlmap = reinterpret_cast<unsigned short *>(wv.bitmap + kAcBitmapWords);
+    wv.ebits = wv.cbits + 256;
     if (LINES)
         for (u32 w = lane; w < kAcBitmapWords; w += 64)
-            bitmap[w] = 0u;
-    u32 *ebits = cbits + 256; // ANCH: the unit's END-pair bitmap (1 KiB, the park area: an anchored scan parks nothing)
+            wv.bitmap[w] = 0u;
     if (ANCH)
-        *reinterpret_cast<uint4 *>(ebits + lane * 4u) = make_uint4(0u, 0u, 0u, 0u);
+        *reinterpret_cast<uint4 *>(wv.ebits + lane * 4u) = make_uint4(0u, 0u, 0u, 0u);
     const bool want_pos = (a.flags & F_POS) != 0;
     const bool chain = want_pos || LINES;
     const bool emit_final = a.emit_mode != 0;
@@ -122,925 +123,89 @@ __global__ __launch_bounds__(kAcBlock) void ac_scan_kernel(const AcArgs a)
         if (u_begin >= a.num_tiles)
             break;
         const u64 u_end = listed ? u_begin + 1 : ((u_begin + a.upt < a.num_tiles) ? u_begin + a.upt : a.num_tiles);
-      // Rolling prefetch: as soon as cell j of a round has been copied out of d[j], the same registers receive cell j
-      // of the NEXT round (the rounds of a ticket are contiguous), so a wave always has 8 KiB in flight while it
-      // filters and verifies — no second buffer (1024-thread blocks cap a wave at 128 VGPRs).
-      uint4 d[kCells];
-      bool have = false; // d[] holds (or is receiving) the round about to be processed (uniform)
-      u32 carry = 0;     // the 4 bytes in front of that round (valid when have)
-      // ANCH, stage 3 DEFERRED over the ticket (round 6): a unit of word text marks ~6 END pairs — a verify batch of 6 lanes that waits
-      // for three dependent round trips (window, length masks, bucket) like a full one.  The marked pairs of the ticket's units are
-      // collected instead — one per lane in `pend` (unit of the ticket << 14 | pair), verified when 64 are there or the ticket ends —
-      // and the units' match counts wait in lanes 0..7 of `ucnt` until the ticket's info words are written.  Ranking and emission
-      // stay per unit, in END order: the pairs arrive unit by unit, ascending.
-      // (The end-gram kernel with the pipelined pair filter can do the same with its CANDIDATES — -DKG_AC_DEFER_GENERIC — and is slower with
-      //  it: BASELINE config 4 holds ~40 candidates per unit, its batches are two thirds full already, and a batch that spans two units
-      //  ranks and emits twice: 6.45-6.54 ms against 6.32-6.40 in alternating runs on one box.  Off.)
-#ifdef KG_AC_DEFER_GENERIC
-      constexpr bool kPend = ANCH != 0 || (PIPE && !SHORT);
-#else
-      constexpr bool kPend = ANCH != 0;
-#endif
-      const bool defer = kPend && !emit_final && !(a.flags & ((1u << 27) | (1u << 28) | (1u << 30) | (1u << 31))) && a.upt <= kAcUnitsPerTicketMax &&
-                         (ANCH == 0 || a.xtab != nullptr);
-      u32 pend = 0, npend = 0, ucnt = 0;
-      for (u64 unit = u_begin; unit < u_end; ++unit)
-      {
-        const u64 useg = a.anchor + unit * (u64)kAcUnitBytes; // the unit = kAcRounds load rounds of 8 KiB
-        if (emit_final && (u32)(a.unitinfo[unit] & kUiCountMask) <= a.stage_cap)
-            continue;
-
-        const bool parked = PIPE && !ANCH && !emit_final && chain && a.stage_cap == 16u && a.upt <= kAcUnitsPerTicketMax;
-        u32 *slot = parked ? park_slots + (u32)(unit - u_begin) * 16u
-                           : reinterpret_cast<u32 *>(a.stage) + unit * (u64)a.stage_cap; // 32-bit staged words, see write() below
-        const bool do_final = emit_final && want_pos;
-        const bool do_stage = !emit_final && want_pos;
-        const u64 fbase = do_final ? a.offsets[unit] : 0ull;
-        u32 wcnt = 0; // matches of the unit so far == rank of the next one (uniform)
-
-#pragma unroll
-        for (int r = 0; r < kAcRounds; ++r)
+        // Rolling prefetch: as soon as cell j of a round has been copied out of d[j], the same registers receive cell j
+        // of the NEXT round (the rounds of a ticket are contiguous), so a wave always has 8 KiB in flight while it
+        // filters and verifies — no second buffer (1024-thread blocks cap a wave at 128 VGPRs).
+        uint4 d[kCells];
+        bool have = false; // d[] holds (or is receiving) the round about to be processed (uniform)
+        u32 carry = 0;     // the 4 bytes in front of that round (valid when have)
+        // the deferred verify of the ticket (ac_pend_unit): pending pairs, their number, the units' counts
+        const bool defer = kPend && !emit_final && !(a.flags & ((1u << 27) | (1u << 28) | (1u << 30) | (1u << 31))) && a.upt <= kAcUnitsPerTicketMax &&
+                           (ANCH == 0 || a.xtab != nullptr);
+        u32 pend = 0, npend = 0, ucnt = 0;
+        for (u64 unit = u_begin; unit < u_end; ++unit)
         {
-        const u64 seg = useg + (u64)r * kSegBytes;
-        const bool fast_now = seg + kSegBytes <= a.text_len;
-        const bool interior = seg >= a.end_lo && seg + kSegBytes <= a.end_hi;
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.text + seg) + lane;
-        // `before` (the 4 bytes in front of the round) is settled BEFORE the round's loads are issued and kept SCALAR: as a
-        // vector register filled on a cold path it made the compiler wait vmcnt(0) where the paths join — at the start of
-        // EVERY round, draining the rolling prefetch the filter never needed to wait for
-        u32 before = 0;
-        if (have)
-            before = carry;
-        else
-        {
-            u32 bb = 0;
-            if (seg >= 4 && seg <= a.text_len)
-                bb = *reinterpret_cast<const u32 *>(a.text + seg - 4);
-            else
-                for (u32 b = 0; b < 4; ++b)
-                    if (seg + b >= 4 && seg + b - 4 < a.text_len)
-                        bb |= (u32)a.text[seg + b - 4] << (8 * b);
-            before = __builtin_amdgcn_readfirstlane(bb);
-        }
-        // -c prefetches only the first kRoll cells of the next round with the stride-1 filter and none with the pair filter (every
-        // -c instantiation then fits the 128 VGPRs of a 1024-thread block without scratch; with the full prefetch they spilled 8-44
-        // bytes per lane.  Measured at 32 GiB on the 1000-pattern dictionary, in-kernel -c road: 9.90 ms without the prefetch,
-        // 9.61 ms with it and 20 bytes of scratch, profiles/r05_line_counting.txt; texts of 32 MiB and more count their lines on the
-        // record list, kg_scan.hip, at 6.8 ms); the rest of a prefetched round is requested here, at its start
-        // (the anchored instantiations roll six of the eight cells: the last two are requested at the round's start and consumed last —
-        //  their eight registers are free while the two verify stages run, which otherwise spilled 12-20 bytes per lane)
-        constexpr int kRoll = LINES ? (STRIDE == 2 ? 0 : KG_AC_LINES_ROLL_CELLS) : (ANCH != 0 ? kCells - 2 : kCells);
-        if (fast_now)
-        {
+            const u64 useg = a.anchor + unit * (u64)kAcUnitBytes; // the unit = kAcRounds load rounds of 8 KiB
+            if (emit_final && (u32)(a.unitinfo[unit] & kUiCountMask) <= a.stage_cap)
+                continue;
+            // (parks: the ticket's info words and slots wait in LDS.  Per unit: formed at the kernel's start these flags cost config 4 6.44 -> 6.46 ms)
+            const bool parks = PIPE && !ANCH && !emit_final && chain && a.stage_cap == 16u && a.upt <= kAcUnitsPerTicketMax;
+            wv.do_final = emit_final && want_pos;
+            wv.do_stage = !emit_final && want_pos;
+            wv.e_useg = useg;
+            wv.e_fbase = wv.do_final ? a.offsets[unit] : 0ull;
+            wv.e_slot = parks ? wv.park_slots + (u32)(unit - u_begin) * 16u
+                              : reinterpret_cast<u32 *>(a.stage) + unit * (u64)a.stage_cap; // 32-bit staged words, see ac_emit_write
+            wv.wcnt = 0;
 #pragma unroll
-            for (int j = 0; j < kCells; ++j)
-                if (!have || j >= kRoll)
-                    d[j] = src[j * kWave]; // (temporal on purpose: non-temporal stream loads measured 7.45 vs 6.87 ms, the verifier's text windows hit in cache)
-        }
-        // the next round of this ticket, if it is a full one, streams in behind this one
-        constexpr bool ROLL = kRoll > 0;
-        const bool pf_next = ROLL && fast_now && !emit_final && seg + 2 * (u64)kSegBytes <= a.text_len &&
-                             (r + 1 < kAcRounds || unit + 1 < u_end);
-        // always issued in the fast path (a uniform address select, not a branch: the s_waitcnt counts stay static);
-        // without a next round every lane re-reads the first bytes of this one (one cached line per load, dropped)
-        const uint4 *nsrc = pf_next ? src + kSegBytes / 16 : reinterpret_cast<const uint4 *>(a.text + seg);
-        // W[0] = the 4 bytes before the lane, W[1..4] = the lane's 16 bytes of cell j
-        // have_c: the caller already holds the classes of W[0] and W[4] (fast path: it shuffles the 20-bit class word
-        // of the neighbour lane instead of its raw bytes, which saves one compress per cell)
-        auto cell_body = [&](const int j, u32 (&W)[5], const bool have_c, const u32 pc0, const u32 pc4) __attribute__((always_inline)) {
-            u32 NL = 0;
-            if (LINES)
+            for (int r = 0; r < kAcRounds; ++r)
             {
-                // (exact 16-bit mask in every cell, ~40 VALU: storing only a has-newline flag and fetching the hit lanes' bytes
-                //  in the line pass was measured — one more memory round trip per unit cost more than it saved: 10.15 -> 11.3 ms)
-#pragma unroll
-                for (int w = 0; w < 4; ++w)
-                    NL |= movemask4(eq_bytes(W[w + 1], 0x0a0a0a0au)) << (4 * w);
-            }
-            u32 cand = 0;
-            if constexpr (PAIR)
-            {
-                // ---- filter, pair layout (stride 2 without -c): the ODD positions are tested, so the gram of position k is two
-                //      16-bit-aligned byte pairs.  A dword becomes two 10-bit pair classes in its halves (3 VALU); the gram of
-                //      k = 3 (mod 4) is that register as it is, the gram of k = 1 (mod 4) one v_alignbit over two of them.  The
-                //      table slot is chosen for this register (ac_pair_slot): bit = the earliest class (the shifter reads the low
-                //      5 bits itself), byte address = ((u >> 3) ^ (u >> 13)) & 0x1fffc — two shifts and one v_bitop3, and the
-                //      LDS bank is the XOR of two classes (one class alone sends the 16 % blanks of a text to ONE bank: 10.6
-                //      instead of 7.2 cycles per 64-lane read).  Per tested position: 0.5 + 3 + 2 VALU and 1.5 for the
-                //      classes — 58 per 1-KiB cell where the 100-bit class stream took ~95 ----
-                u32 t[5];
-#pragma unroll
-                for (int w = 1; w < 4; ++w)
-                    t[w] = ac_pair(W[w]);
-                t[0] = have_c ? pc0 : ac_pair(W[0]);
-                t[4] = have_c ? pc4 : ac_pair(W[4]);
-                u32 xs[8], dws[8];
-                typedef __attribute__((address_space(3))) const u32 lds_u32;
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
+                const u64 seg = useg + (u64)r * kSegBytes;
+                const bool fast_now = seg + kSegBytes <= a.text_len;
+                const bool interior = seg >= a.end_lo && seg + kSegBytes <= a.end_hi;
+                const uint4 *src = reinterpret_cast<const uint4 *>(a.text + seg) + lane;
+                u32 before = ac_round_before(a, seg, have, carry);
+                if (fast_now) // what the round before did not prefetch (ac_roll_cells)
                 {
-                    const int w = q / 2 + 1;
-                    xs[q] = (q & 1) ? t[w] : __builtin_amdgcn_alignbit(t[w], t[w - 1], 16u);
-                    if constexpr (ANCH == 2)
-                        xs[q] = ac_mix5(xs[q], __builtin_amdgcn_ubfe(t[(2 * q + 1) / 4], ((2 * q + 1) % 4 == 1) ? 5u : 21u, 5u));
-                    // (-c: a 2^19-bit table, address bit 16 = bit 3 of the class c2 dropped)
-                    dws[q] = *(lds_u32 *)(size_t)(((xs[q] >> 3) ^ (xs[q] >> 13)) & kTabMask);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                u32 acc = 0;
 #pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    acc = __builtin_amdgcn_alignbit(dws[q] >> (xs[q] & 31u), acc, 2u);
-                cand = (acc >> 16) & 0x5555u; // bit 2q <-> tested position 2q + 1 (the verify stage adds the 1)
-            }
-            else
-            {
-                // ---- filter, exact-class table: the lane's 20 bytes as a 100-bit stream of 5-bit classes; the
-                //      index of end position k is the 20-bit window at bit 5(k+1): one v_alignbit, no hash ----
-                u32 c[5];
-#pragma unroll
-                for (int w = 1; w < 4; ++w)
-                    c[w] = ac_cls4(W[w]);
-                c[0] = have_c ? pc0 : ac_cls4(W[0]);
-                c[4] = have_c ? pc4 : ac_cls4(W[4]);
-                u32 R[5];
-                R[0] = c[0] | (c[1] << 20);
-                R[1] = (c[1] >> 12) | (c[2] << 8) | (c[3] << 28);
-                R[2] = (c[3] >> 4) | (c[4] << 16);
-                R[3] = c[4] >> 16;
-                R[4] = 0;
-                // per position 5 VALU: window, dword address, ds_read_b32, shift by the low 5 index bits (the shifter
-                // masks them itself), and a funnel shift that pushes the hit bit into the accumulator from the top
-                // all table reads of the cell are issued before the first one is consumed (the scheduler otherwise
-                // serialises read -> wait -> shift through the accumulator chain: 8-16 LDS latencies per cell)
-                constexpr int NK = 16 / STRIDE;
-                // (stride 1 with the rolling prefetch: in two batches of 8 — 32 index / data registers at once spilled 12-20 bytes
-                //  per lane under the 128-VGPR cap)
-#ifndef KG_AC_S1_ONE_BATCH // (A/B switch)
-                constexpr int NB = (NK == 16 && !LINES) ? 8 : NK;
-#else
-                constexpr int NB = NK;
-#endif
-                typedef __attribute__((address_space(3))) const u32 lds_u32;
-                u32 acc = 0;
-#pragma unroll
-                for (int q0 = 0; q0 < NK; q0 += NB)
-                {
-                    u32 xs[NB], dws[NB];
-#pragma unroll
-                    for (int q = 0; q < NB; ++q)
-                    {
-                        const int o = 5 * ((q0 + q) * STRIDE + 1);
-                        xs[q] = (o & 31) ? __builtin_amdgcn_alignbit(R[(o >> 5) + 1], R[o >> 5], (u32)(o & 31)) : R[o >> 5];
-                        // the table sits at LDS address 0 (checked at kernel entry): an absolute LDS pointer saves the
-                        // v_add of the (link-time) base of s_mem on every lookup
-                        dws[q] = *(lds_u32 *)(size_t)((xs[q] >> 3) & ((1u << (XB - 3)) - 4u));
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int q = 0; q < NB; ++q)
-                        acc = __builtin_amdgcn_alignbit(dws[q] >> (xs[q] & 31u), acc, (u32)STRIDE);
-                    if (q0 + NB < NK)
-                        __builtin_amdgcn_sched_barrier(0);
+                    for (int j = 0; j < kCells; ++j)
+                        if (!have || j >= kRoll)
+                            d[j] = src[j * kWave]; // (temporal on purpose: non-temporal stream loads measured 7.45 vs 6.87 ms, the verifier's text windows hit in cache)
                 }
-                cand = STRIDE == 2 ? (acc >> 16) & 0x5555u : acc >> 16;
-            }
-            u32 nlm = NL;
-            if (!interior)
-            {
-                // window bounds relative to the round (uniform, clamped to [0, 8 KiB]) against the lane's 32-bit offset
-                const u32 lrel = (u32)j * kCellBytes + lane * 16u;
-                auto clip = [&](u64 lo, u64 hi) -> u32 {
-                    const u32 rlo = lo > seg ? (u32)((lo - seg) < kSegBytes ? (lo - seg) : kSegBytes) : 0u;
-                    const u32 rhi = hi > seg ? (u32)((hi - seg) < kSegBytes ? (hi - seg) : kSegBytes) : 0u;
-                    const u32 klo = rlo > lrel ? ((rlo - lrel) < 16u ? (rlo - lrel) : 16u) : 0u;
-                    const u32 khi = rhi > lrel ? ((rhi - lrel) < 16u ? (rhi - lrel) : 16u) : 0u;
-                    return khi > klo ? (((1u << khi) - 1u) & ~((1u << klo) - 1u)) : 0u;
-                };
-                const u32 endm = clip(a.end_lo, a.end_hi);
-                if (!PAIR) // (pair layout: a bit stands for the ends k + 1 and k + 2, the second possibly in the next lane; the
-                           //  verify stage applies the exact window)
-                    cand &= STRIDE == 2 ? (endm | (endm >> 1)) : endm; // stride 2: t or t + 1 is an end of this launch
-                if (LINES)
-                    nlm &= clip(a.own_lo, a.own_hi);
-            }
-            if (LINES) // kept in LDS, not in 16 registers, across the verify stage
-                nlmap[(u32)r * (kSegBytes / 16) + (u32)j * kWave + lane] = (unsigned short)nlm;
-
-            // ---- the lane's candidates go into the unit's bitmap; they are enumerated once per unit (below) instead
-            //      of ranked per cell (ballots + a divergent store loop: ~15 VALU per cell), and nothing overflows ----
-            if (PIPE)
-            {
-                u32 x = cand & 0x5555u; // even bits -> 8 contiguous bits
-                x = (x | (x >> 1)) & 0x3333u;
-                x = (x | (x >> 2)) & 0x0f0fu;
-                x = (x | (x >> 4)) & 0x00ffu;
-                cbits8[(u32)r * (kSegBytes / 16) + (u32)j * kWave + lane] = (uint8_t)x;
-            }
-            else
-                cbits16[(u32)r * (kSegBytes / 16) + (u32)j * kWave + lane] = (unsigned short)cand;
-        };
-        if (PIPE && fast_now)
-        {
-            // Pair layout, software-pipelined over the cells of the round: the table reads of cell j + 1 are issued before the
-            // results of cell j are consumed, so a wave waits for LDS once per round instead of once per cell (the LDS pipe
-            // is ~50 % busy with 4 waves per SIMD: the exposed read latency, not its throughput, was the limit).
-            u32 xs[2][8], dw[2][8];
-            typedef __attribute__((address_space(3))) const u32 lds_u32;
-            auto issue = [&](const int j, u32 (&x)[8], u32 (&v)[8]) __attribute__((always_inline)) {
-                u32 t[5];
-                t[1] = ac_pair(d[j].x); t[2] = ac_pair(d[j].y); t[3] = ac_pair(d[j].z); t[4] = ac_pair(d[j].w);
-                const u32 last = d[j].w;
-                if (j < kRoll)
-                    d[j] = nsrc[j * kWave];
-                t[0] = (u32)__builtin_amdgcn_update_dpp((int)ac_pair(before), (int)t[4], 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-                before = __builtin_amdgcn_readlane(last, 63);
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                {
-                    const int w = q / 2 + 1;
-                    x[q] = (q & 1) ? t[w] : __builtin_amdgcn_alignbit(t[w], t[w - 1], 16u);
-                    if constexpr (ANCH == 2) // the class of the byte in front of the gram (byte 2q - 3 of the lane), mixed into the class fields
-                        x[q] = ac_mix5(x[q], __builtin_amdgcn_ubfe(t[(2 * q + 1) / 4], ((2 * q + 1) % 4 == 1) ? 5u : 21u, 5u));
-                    v[q] = *(lds_u32 *)(size_t)(((x[q] >> 3) ^ (x[q] >> 13)) & kTabMask);
-                }
-            };
-            auto finish = [&](const int j, const u32 (&x)[8], const u32 (&v)[8]) __attribute__((always_inline)) {
-                u32 acc = 0;
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    acc = __builtin_amdgcn_alignbit(v[q] >> (x[q] & 31u), acc, 1u);
-                cbits8[(u32)r * (kSegBytes / 16) + (u32)j * kWave + lane] = (uint8_t)(acc >> 24); // bit q <-> tested position 2q + 1
-            };
-            issue(0, xs[0], dw[0]);
-#pragma unroll
-            for (int j = 0; j < kCells; ++j)
-            {
-                if (j + 1 < kCells)
-                    issue(j + 1, xs[(j + 1) & 1], dw[(j + 1) & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-                finish(j, xs[j & 1], dw[j & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        else if (fast_now)
-        { // straight-line: no branch between a prefetch and the next cell's read of d[]
-#pragma unroll
-            for (int j = 0; j < kCells; ++j)
-            {
-                u32 W[5];
-                W[1] = d[j].x; W[2] = d[j].y; W[3] = d[j].z; W[4] = d[j].w;
-                if (j < kRoll)
-                    d[j] = nsrc[j * kWave];
-                {
-                    // the class word of the 4 bytes in front of the lane = the left neighbour's last one: a DPP wave shift
-                    // (lane 0 keeps `old` = the classes of `before`, uniform: scalar ALU) — no LDS permute, no branch
-                    const u32 c4 = PAIR ? ac_pair(W[4]) : ac_cls4(W[4]);
-                    const u32 cb = PAIR ? ac_pair(before) : ac_cls4(before);
-                    const u32 c0 = (u32)__builtin_amdgcn_update_dpp((int)cb, (int)c4, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-                    W[0] = 0;
-                    before = __builtin_amdgcn_readlane(W[4], 63); // the next cell's (and round's) left neighbour
-                    cell_body(j, W, true, c0, c4);
-                }
-            }
-        }
-        else
-        { // the ragged end of the text: bytewise, bounds-checked
-#pragma unroll
-            for (int j = 0; j < kCells; ++j)
-            {
-                const u64 lbase = seg + (u64)j * kCellBytes + (u64)lane * 16u;
-                u32 W[5];
-#pragma unroll
-                for (int w = 0; w < 5; ++w)
-                {
-                    u32 v = 0;
-                    for (int b = 0; b < 4; ++b)
-                    {
-                        const u64 o = lbase + (u64)(w * 4 + b);
-                        if (o >= 4 && o - 4 < a.text_len)
-                            v |= (u32)a.text[o - 4] << (8 * b);
-                    }
-                    W[w] = v;
-                }
-                cell_body(j, W, false, 0u, 0u);
-            }
-        }
-
-        have = pf_next;
-        carry = before;
-        } // rounds
-
-        // ---- verify (and stage/emit) the candidates, 64 at a time, one per lane.  Lane L owns the 256 positions
-        //      [256 L, 256 L + 256) of the bitmap (8 dwords); a wave scan of the popcounts gives every lane its rank
-        //      range, and the lane verifying rank q finds its candidate by a binary search over those sums and a
-        //      select of the t-th set bit in the owner's block ------------------------------------------------
-        // the matches of one batch (one END pair per lane: cA at pos, cB at pos + 1, depth masks or the level walk's verdict):
-        // unit-local ranks by a wave prefix, then staging slots / final records / the -c hit bitmap, longest first at one end
-        // (what an emission refers to: this unit — or, for the deferred stage 3 of the anchored scan, the unit a pending pair belongs to)
-        u64 e_useg = useg, e_fbase = fbase;
-        u32 *e_slot = slot;
-        auto rank_and_emit = [&](const u64 pos, const u32 cA, const u32 cB, const u64 dmA, const u64 dmB, const bool simA, const bool simB)
-            __attribute__((always_inline)) {
-            const u32 c = cA + cB;
-            u32 incl = c;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1)
-            {
-                const u32 t = __shfl_up(incl, o);
-                if (lane >= (u32)o)
-                    incl += t;
-            }
-            const u32 rank0 = wcnt + incl - c;
-            wcnt += __shfl(incl, 63);
-#pragma unroll 1
-            for (int e = 0; e < (STRIDE == 2 ? 2 : 1); ++e)
-            {
-                const u32 ce = e ? cB : cA;
-                if (!ce)
-                    continue;
-                const u64 pe = pos + (u64)e, dme = e ? dmB : dmA;
-                const u32 re = rank0 + (e ? cA : 0u), rele = (u32)(pe - e_useg); // the END's bit in the unit's hit bitmap
-                const bool sime = e ? simB : simA;
-                if (LINES)
-                    atomicOr(&bitmap[rele >> 5], 1u << (rele & 31u));
-                if (do_stage || do_final)
-                {
-                    auto write = [&](u32 at, u64 s0, u32 len) {
-                        if (do_stage)
-                        {
-                            if (at < a.stage_cap)
-                                e_slot[at] = ((u32)(s0 + 1024u - e_useg) << 11) | len; // start relative to the unit (>= -1023), length <= 1024
-                        }
-                        else
-                        {
-                            const u64 g = e_fbase + at;
-                            if (g < a.pos_cap)
-                            {
-                                const u64 st = s0 + a.global_base, en = st + len;
-                                *reinterpret_cast<uint4 *>(a.positions + 2 * g) =
-                                    make_uint4((u32)st, (u32)(st >> 32), (u32)en, (u32)(en >> 32));
-                            }
-                        }
-                    };
-                    if (sime)
-                    {
-                        u32 at = re;
-                        for (u64 rest = dme; rest;) // longest first
-                        {
-                            const u32 d = 63u - (u32)__builtin_clzll(rest);
-                            rest &= ~(1ull << d);
-                            write(at++, pe + 1 - (u64)d, d);
-                        }
-                    }
-                    else
-                        ac_walk<CI, true, !SHORT>(a, pe, ce, [&](u32 r, u64 s2, u32 len) { write(re + r, s2, len); });
-                }
-            }
-        };
-        if constexpr (ANCH)
-        {
-            // ================= anchored, stage 2: candidates -> END-pair bitmap =================
-            // the unit verifies the ends useg + 1 .. useg + 16384 (bit b <-> the pair 2b + 1, 2b + 2), as the end-gram kernel does
-            auto mark = [&](u64 e) {
-                if (e > useg && e <= useg + kAcUnitBytes)
-                {
-                    const u32 b = (u32)(e - useg - 1u) >> 1;
-                    atomicOr(&ebits[b >> 5], 1u << (b & 31u));
-                }
-            };
-            u32 mycnt = 0;
-            {
-                const uint4 lo = *reinterpret_cast<const uint4 *>(cbits + lane * kWPL);
-                mycnt = (u32)(__popc(lo.x) + __popc(lo.y) + __popc(lo.z) + __popc(lo.w));
-            }
-            const u32 incl = ac_wave_scan_incl(mycnt); // (on the DPP network: the shuffle version's six address registers spilled in the -i -w instantiations)
-            const bool off = (a.flags & (1u << 31)) != 0u; // (ablation hook KREP_GPU_AC_NOVERIFY: filter cost only)
-            const u32 n = off ? 0u : __shfl(incl, 63);
-            acc_cand += (u32)__builtin_amdgcn_readfirstlane((int)n);
-            // an END lies up to 13 bytes behind the tested position that names it: the six tested positions in front of the unit
-            // whose ends can fall into it are looked at again here (their own unit drops the ends beyond its last pair)
-            const u32 n_x = (!off && useg >= 16u) ? 6u : 0u;
-            const u32 n_tot = n + n_x;
-            // the candidates of a batch: lane -> tested position (binary search over the owners' prefix sums, then the t-th set bit)
-            auto locate = [&](const u32 b0, u64 &t, bool &live, bool &valid) {
-                const u32 qi = b0 + lane;
-                live = qi < n;
-                const bool isx = qi >= n && qi < n_tot;
-                u32 rel = 0, own = 0;
-#pragma unroll
-                for (u32 step = 32; step; step >>= 1)
-                {
-                    const u32 x = __shfl(incl, (own + step - 1u) & 63u);
-                    if (x <= qi)
-                        own += step;
-                }
-                own &= 63u;
-                const u32 oincl = __shfl(incl, own), ocnt = __shfl(mycnt, own);
-                if (live)
-                {
-                    u32 x = qi - (oincl - ocnt);
-                    const u32 *blk = cbits + own * kWPL;
-                    u32 w = 0, word = blk[0];
-                    for (;;)
-                    {
-                        const u32 c = (u32)__popc(word);
-                        if (x < c)
-                            break;
-                        x -= c;
-                        word = blk[++w];
-                    }
-                    for (; x; --x)
-                        word &= word - 1u;
-                    rel = 2u * (own * 128u + w * 32u + (u32)__builtin_ctz(word)); // (bit b <-> tested position 2b + 1)
-                }
-                t = isx ? useg - 11u + 2u * (u64)(qi - n) : useg + rel + 1u; // the tested position (odd)
-                valid = (live || isx) && t < a.text_len;
-            };
-            // its eight bytes t - 6 .. t + 1 (without the last one where the text ends: one byte lower, shifted back)
-            auto fetch = [&](const u64 t, const bool valid) -> u64 {
-                if (!valid || t < 16u)
-                    return 0ull;
-                const bool hasB = t + 1 < a.text_len;
-                const u64 q8 = load_unaligned<u64>(a.text + (t - (hasB ? 6u : 7u)));
-                return hasB ? q8 : (q8 >> 8);
-            };
-            // Two dependent round trips per batch (window, then bucket) and, on a text where most candidates reach their bucket, three
-            // or four batches per unit: the NEXT batch's windows are requested before this batch's buckets, so a batch waits once
-            u64 tN = 0, QN = 0;
-            bool liveN = false, validN = false;
-            if (n_tot)
-            {
-                locate(0u, tN, liveN, validN);
-                QN = fetch(tN, validN);
-            }
-            for (u32 b0 = 0; b0 < n_tot; b0 += 64)
-            {
-                const u64 t = tN, Q = QN;
-                const bool live = liveN, valid = validN;
-                if (b0 + 64u < n_tot)
-                {
-                    locate(b0 + 64u, tN, liveN, validN);
-                    QN = fetch(tN, validN);
-                }
-                if (a.flags & (1u << 30))
-                { // (ablation hook KREP_GPU_AC_NOPROBE: the count that comes back is the number of filter candidates)
-                    wcnt += (u32)__popcll(__ballot(live));
-                    continue;
-                }
-                if (valid)
-                {
-                    if (t < 16u)
-                    { // (the first bytes of the text: no window in front — every end the position could name)
-                        for (u32 k = 0; k <= kAnchMaxK + 1u; ++k)
-                            mark(t + k);
-                    }
-                    else
-                    {
-                        const bool hasB = t + 1 < a.text_len;
-                        typedef __attribute__((address_space(3))) const u32 lds_u32;
-                        // the table's answer for the gram whose LAST byte is byte `last` of the window (ANCH == 2: with the class of the
-                        // byte in front of the gram, byte last - 4)
-                        auto gtest = [&](const int last) -> bool {
-                            u32 u = ac_pair((u32)(Q >> (8 * (last - 3))));
-                            if constexpr (ANCH == 2)
-                                u = ac_mix5(u, (u32)(Q >> (8 * (last - 4))) & 31u);
-                            return ((*(lds_u32 *)(size_t)(((u >> 3) ^ (u >> 13)) & kTabMask) >> (u & 31u)) & 1u) != 0u;
-                        };
-                        // the position's own gram again for the six in front of the unit; then, as in the end-gram kernel: an anchor
-                        // gram ENDS at t where the window's other gram sits at t - 1, at t + 1 where this one is that other gram
-                        // (window bytes 0..7 = text bytes t - 6 .. t + 1)
-                        const bool own_ok = live || gtest(6);
-                        const bool liveA = own_ok && gtest(5);
-                        const bool liveB = own_ok && hasB && gtest(7);
-                        u32 kA = (u32)(Q >> 24), kB = (u32)(Q >> 32); // the exact anchor gram: bytes t - 3 .. t | t - 2 .. t + 1
-                        if (CI)
-                        {
-                            kA = ac_fold4(kA);
-                            kB = ac_fold4(kB);
-                        }
-                        // buckets of two 16-byte entries {exact anchor gram, 1 << 31 | offset mask, the three bytes in front of the
-                        // 5-byte window, their byte mask}: seven exact bytes decide, all of them in the window already fetched
-                        u32 cxA = (u32)Q & 0xffffffu, cxB = (u32)(Q >> 8) & 0xffffffu; // bytes a - 6 .. a - 4 of either parity
-                        if (CI)
-                        {
-                            cxA = ac_fold4(cxA);
-                            cxB = ac_fold4(cxB);
-                        }
-                        uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0, b0_ = a0, b1_ = a0;
-                        if (liveA)
-                        {
-                            const uint4 *bk = a.anch + 2u * (size_t)(((kA * a.anch_mul) >> 9) & a.anch_mask);
-                            a0 = bk[0];
-                            a1 = bk[1];
-                        }
-                        if (liveB)
-                        {
-                            const uint4 *bk = a.anch + 2u * (size_t)(((kB * a.anch_mul) >> 9) & a.anch_mask);
-                            b0_ = bk[0];
-                            b1_ = bk[1];
-                        }
-                        auto pick = [](const uint4 &e0, const uint4 &e1, u32 key, u32 cx) -> u32 {
-                            const uint4 &e = (e0.x == key && (e0.y >> 31)) ? e0 : e1;
-                            return (e.x == key && (e.y >> 31) && ((cx ^ e.z) & e.w) == 0u) ? (e.y & 0x7fffffffu) : 0u;
-                        };
-                        u32 mA = liveA ? pick(a0, a1, kA, cxA) : 0u;
-                        u32 mB = liveB ? pick(b0_, b1_, kB, cxB) : 0u;
-                        while (mA)
-                        {
-                            mark(t + (u32)__builtin_ctz(mA));
-                            mA &= mA - 1u;
-                        }
-                        while (mB)
-                        {
-                            mark(t + 1u + (u32)__builtin_ctz(mB));
-                            mB &= mB - 1u;
-                        }
-                    }
-                }
-            }
-        }
-        // the verification of ONE END pair per lane (ends pos and pos + 1): the number of matches at either end, their depth masks (or the
-        // level walk's verdict) — everything of a verify batch except its ranking and emission
-        auto verify_ends = [&](const u64 pos, const bool live, const bool isx, const u64 vuseg, u32 &cA, u32 &cB, u64 &dmA, u64 &dmB, bool &simA,
-                               bool &simB) __attribute__((always_inline)) {
-            bool liveA = live, liveB = false;
-            if (STRIDE == 2)
-                liveA = live && pos >= a.end_lo && pos < a.end_hi;
-            if (STRIDE == 2) // a candidate stands for the ends t and t + 1
-                liveB = (live || isx) && pos + 1 >= a.end_lo && pos + 1 < a.end_hi &&
-                        (!XCAND || pos + 1 < vuseg + kAcUnitBytes); // (-c: that end belongs to the next unit's extra candidate)
-            cA = cB = 0;
-            dmA = dmB = 0;
-            simA = simB = false;
-            if (STRIDE == 2)
-            {
-                bool slA = false, slB = false;
-                u32 mA = 0, mB = 0;
-#ifndef KG_AC_NO_BTEST // (A/B switches of krep_amd/build.py --variant)
-                constexpr bool kGram = PAIR && XB == 20 && !ANCH; // the probe asks the class table about both ends (kg_ac_common.h; ANCH: the table holds anchor grams, not end grams)
-#else
-                constexpr bool kGram = false;
-#endif
-#ifndef KG_AC_NO_STAGE
-                constexpr bool kStaged = kGram;
-#else
-                constexpr bool kStaged = false;
-#endif
-                bool exact_done = false;
-                if constexpr (ANCH != 0)
-#ifndef KG_AC_EXACT_SERIAL
-                    if (a.xtab && pos >= 15u && (WW || !(a.flags & F_WW))) // (-w: tested inside ac_exact_end2<.., WW>, on the window's own bytes)
-#else
-                    if (a.xtab && !(a.flags & F_WW) && pos >= 15u)
-#endif
-                    {
-                        // stage 3 through the length-keyed exact dictionary (kg_ac_common.h ac_exact_end): no trie, no chain
-                        bool muA = false, muB = false;
-#ifndef KG_AC_EXACT_SERIAL // (A/B switch of krep_amd/build.py --variant: the two ends one behind the other, as first built)
-                        if (liveA || liveB)
-                            ac_exact_end2<CI, WW>(a, pos, liveA, liveB, mA, mB, muA, muB);
-#else
-                        if (liveA)
-                            mA = ac_exact_end<CI>(a, pos, muA);
-                        if (liveB)
-                            mB = ac_exact_end<CI>(a, pos + 1u, muB);
-#endif
-                        // start ownership (the same clip as ac_eval_entry's)
-                        auto clip = [&](u32 m, u64 end) -> u32 {
-                            const u64 e = end + 1;
-                            if (e <= a.own_lo)
-                                return 0u;
-                            if (e - a.own_lo < 32)
-                                m &= (2u << (u32)(e - a.own_lo)) - 1u;
-                            if (e > a.own_hi)
-                                m = (e - a.own_hi < 32) ? (m & ~((2u << (u32)(e - a.own_hi)) - 1u)) : 0u;
-                            return m;
-                        };
-                        mA = clip(mA, pos);
-                        mB = clip(mB, pos + 1u);
-                        // a `multi` entry (a pattern the dictionary holds twice, or the 16-byte stand-in of a LONGER pattern, kg_ac_anchor.hip
-                        // exact_table): counted and emitted by the level walk, which owns by the TRUE start.  Decided on the unclipped answer —
-                        // the clip above takes a stand-in for a 16-byte pattern and would drop a longer one that starts in front of own_hi
-                        // and ends 16 bytes or more behind it (muA implies a hit, i.e. a mask that was not empty before the clip).
-                        slA = muA;
-                        slB = muB;
-                        exact_done = true;
-                    }
-                if (exact_done)
-                {
-                }
-                else if (!(a.flags & (1u << 30))) // (ablation hook KREP_GPU_AC_NOPROBE: candidate enumeration without the probes)
-                    ac_walk_probe2<CI, SHORT, kStaged, WW>(a, pos, liveA, liveB, LINES, mA, slA, mB, slB, [&](u32 E) -> bool {
-                        if constexpr (kGram)
-                        {
-                            // the filter's own lookup for a gram that lies in one dword (cell_body, k = 3 mod 4)
-                            typedef __attribute__((address_space(3))) const u32 lds_u32;
-                            const u32 u = ac_pair(E);
-                            return ((*(lds_u32 *)(size_t)(((u >> 3) ^ (u >> 13)) & kTabMask) >> (u & 31u)) & 1u) != 0u;
-                        }
-                        else
-                            return true;
-                    });
+                // the next round of this ticket, if it is a full one, streams in behind this one
+                const bool pf_next = kRoll > 0 && fast_now && !emit_final && seg + 2 * (u64)kSegBytes <= a.text_len &&
+                                     (r + 1 < kAcRounds || unit + 1 < u_end);
+                // always issued in the fast path (a uniform address select, not a branch: the s_waitcnt counts stay static);
+                // without a next round every lane re-reads the first bytes of this one (one cached line per load, dropped)
+                const uint4 *nsrc = pf_next ? src + kSegBytes / 16 : reinterpret_cast<const uint4 *>(a.text + seg);
+                if (PIPE && fast_now)
+                    ac_pair_round<ANCH>(wv.cbits, lane, r, d, nsrc, before);
+                else if (fast_now) // (ANCH implies PIPE: see the static_assert at the kernel's head)
+                    ac_cell_round<LINES, STRIDE>(a, wv, lane, r, seg, interior, d, nsrc, before);
                 else
-                    mA = liveA ? 1u : 0u; // ... and the count that comes back is the number of candidates
-                dmA = mA; dmB = mB;
-                cA = (u32)__popc(mA); cB = (u32)__popc(mB);
-                simA = simB = true;
-#ifndef KG_AC_NO_EXACT_SLOW // (A/B switch of krep_amd/build.py --variant)
-                if constexpr (!SHORT && ANCH == 0 && !CI) // (-i: eight bytes of scratch per lane in the BASELINE-shaped kernel for a path the anchored instantiations cover)
-                    if (a.xtab && !(a.flags & F_WW) && pos >= 15u && (slA || slB))
-                    {
-                        // an end the chain-compressed entry cannot answer (the trie branches behind its final gram): the exact dictionary
-                        // instead of the level walk, where there is one (a word-like text, patterns of 4..16 bytes)
-                        auto clipx = [&](u32 m, u64 end) -> u32 {
-                            if (LINES)
-                                return m; // (-c owns by END)
-                            const u64 e = end + 1;
-                            if (e <= a.own_lo)
-                                return 0u;
-                            if (e - a.own_lo < 32)
-                                m &= (2u << (u32)(e - a.own_lo)) - 1u;
-                            if (e > a.own_hi)
-                                m = (e - a.own_hi < 32) ? (m & ~((2u << (u32)(e - a.own_hi)) - 1u)) : 0u;
-                            return m;
-                        };
-                        bool mu = false;
-                        if (slA)
-                        {
-                            const u32 m = clipx(ac_exact_end<CI>(a, pos, mu), pos);
-                            if (!mu) { mA = m; slA = false; } // (mu: the level walk decides, by the true start — a stand-in's bit 16 is not its length)
-                        }
-                        if (slB)
-                        {
-                            const u32 m = clipx(ac_exact_end<CI>(a, pos + 1u, mu), pos + 1u);
-                            if (!mu) { mB = m; slB = false; }
-                        }
-                        dmA = mA; dmB = mB;
-                        cA = (u32)__popc(mA); cB = (u32)__popc(mB);
-                    }
-#endif
-#pragma unroll 1
-                for (int e = 0; e < 2; ++e) // the one call site of the level walk
-                    if (e ? slB : slA)
-                    {
-                        u64 dm;
-                        bool sim;
-                        const u32 c = ac_walk_slow<CI, SHORT>(a, pos + (u64)e, LINES, dm, sim);
-                        if (e) { cB = c; dmB = dm; simB = sim; }
-                        else { cA = c; dmA = dm; simA = sim; }
-                    }
+                    ac_ragged_round<LINES, STRIDE, ANCH>(a, wv, lane, r, seg, interior);
+                have = pf_next;
+                carry = before;
             }
-            else if (liveA)
-                cA = ac_walk_fast<CI, SHORT>(a, pos, LINES, dmA, simA);
-        };
-        // (ANCH: what follows is stage 3 — the same verify, over the END-pair bitmap instead of the candidate bitmap)
-        const u32 *vbits = ANCH ? ebits : cbits;
-        if constexpr (kPend)
-        {
-          if (ANCH != 0 && (a.flags & (1u << 28))) // (ablation hook KREP_GPU_AC_NOSTAGE3: the anchor stage alone; the count is the number of marked END pairs)
-          {
-            const uint4 m = *reinterpret_cast<const uint4 *>(ebits + lane * 4u);
-            const u32 c = (u32)(__popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w));
-            wcnt += (u32)__builtin_amdgcn_readlane((int)ac_wave_scan_incl(c), 63);
-            *reinterpret_cast<uint4 *>(ebits + lane * 4u) = make_uint4(0u, 0u, 0u, 0u);
-          }
-          else if (ANCH == 0 || !(a.flags & (1u << 30)))
-          {
-            // ---- the unit's marked pairs (end-gram kernel: its candidates) join the pending ones; 64 pending pairs are a verify batch.  Deferred: what is left waits for the
-            //      ticket's next unit; otherwise (emit mode, -w, no exact dictionary) it is verified here, at the unit's end ----
-            // (registers: nothing of the collection below lives across a batch, and a pair's position is re-derived from its `pend` word —
-            //  kept live they cost the anchored instantiations 20-28 B/lane of scratch, whose reloads drain the text prefetch)
-            auto pos_of = [&]() -> u64 { // (bit b of a unit's END bitmap <-> the pair 2b + 1, 2b + 2)
-                return a.anchor + (u_begin + (u64)(pend >> 14)) * (u64)kAcUnitBytes + ((pend & 0x3fffu) << 1) + 1u;
-            };
-            auto flush = [&](const u32 cnt) __attribute__((always_inline)) {
-                const bool live = lane < cnt;
-                u32 cA, cB;
-                u64 dmA, dmB;
-                bool simA, simB;
-                verify_ends(pos_of(), live, false, 0ull, cA, cB, dmA, dmB, simA, simB);
-                const u32 cc = cA | (cB << 8);
-                const u32 v0 = (u32)__builtin_amdgcn_readfirstlane((int)(pend >> 14)), v1 = (u32)__builtin_amdgcn_readlane((int)(pend >> 14), (int)(cnt - 1u));
-                for (u32 v = v0; v <= v1; ++v) // (uniform: the units the batch spans, ascending; not deferred: this unit)
-                {
-                    const bool in = live && (pend >> 14) == v;
-                    if (!__ballot(in))
-                        continue;
-                    if (defer)
-                    {
-                        e_useg = a.anchor + (u_begin + (u64)v) * (u64)kAcUnitBytes;
-                        e_slot = parked ? park_slots + v * 16u : reinterpret_cast<u32 *>(a.stage) + (u_begin + (u64)v) * (u64)a.stage_cap;
-                        wcnt = (u32)__builtin_amdgcn_readlane((int)ucnt, (int)v);
-                    }
-                    rank_and_emit(pos_of(), in ? (cc & 0xffu) : 0u, in ? (cc >> 8) : 0u, dmA, dmB, simA, simB);
-                    if (defer && lane == v)
-                        ucnt = wcnt;
-                }
-                if (defer)
-                    wcnt = 0;
-            };
-            const u32 uv = (u32)(unit - u_begin);
-            u32 n = 0, mycnt = 0, incl = 0;
-            auto recount = [&]() { // the marked pairs per lane (four dwords of the bitmap each) and their inclusive prefix
-                const uint4 lo = *reinterpret_cast<const uint4 *>(vbits + lane * 4u);
-                mycnt = (u32)(__popc(lo.x) + __popc(lo.y) + __popc(lo.z) + __popc(lo.w));
-                incl = ac_wave_scan_incl(mycnt);
-                n = (a.flags & (1u << 31)) ? 0u : (u32)__builtin_amdgcn_readlane((int)incl, 63); // (ablation hook KREP_GPU_AC_NOVERIFY: filter cost only)
-            };
-            recount();
-            if (ANCH == 0)
-                acc_cand += n;
-            u32 taken = 0;
-            do // (ONE call site of the verify batch: it is inlined, and two copies cost the anchored instantiations 12-20 B/lane of scratch)
-            {
-                const u32 room = 64u - npend, take = room < n - taken ? room : n - taken;
-                const bool mine = lane >= npend && lane < npend + take;
-                const u32 qi = mine ? taken + (lane - npend) : 0u;
-                u32 own = 0;
-#pragma unroll
-                for (u32 step = 32; step; step >>= 1)
-                {
-                    const u32 t = __shfl(incl, (own + step - 1u) & 63u);
-                    if (t <= qi)
-                        own += step;
-                }
-                own &= 63u;
-                const u32 oincl = __shfl(incl, own), ocnt = __shfl(mycnt, own);
-                if (mine)
-                {
-                    u32 t = qi - (oincl - ocnt); // the t-th set bit of the owner's four dwords
-                    const u32 *blk = vbits + own * 4u;
-                    u32 w = 0, word = blk[0];
-                    for (;;)
-                    {
-                        const u32 c = (u32)__popc(word);
-                        if (t < c)
-                            break;
-                        t -= c;
-                        word = blk[++w];
-                    }
-                    for (; t; --t)
-                        word &= word - 1u;
-                    pend = (uv << 14) | (own * 128u + w * 32u + (u32)__builtin_ctz(word));
-                }
-                npend += take;
-                taken += take;
-                if (npend == 64u || (taken >= n && npend && (!defer || unit + 1 == u_end)))
-                {
-                    flush(npend);
-                    npend = 0;
-                    if (taken < n)
-                        recount(); // (see flush)
-                }
-            } while (taken < n);
-            if (ANCH != 0 && n) // (wave-uniform) the END-pair bitmap is the next unit's again
-            {
-                // (the zeros are made HERE: as a loop-invariant uint4 they were kept in four registers from the kernel's start, spilled,
-                //  and reloaded in front of this store — a scratch load whose wait drained the text prefetch once per unit)
-                u32 z;
-                asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-                *reinterpret_cast<uint4 *>(ebits + lane * 4u) = make_uint4(z, z, z, z);
-            }
-          }
-        }
-        else
-        {
-            u32 mycnt = 0;
-            {
-                const uint4 lo = *reinterpret_cast<const uint4 *>(vbits + lane * kWPL);
-                mycnt = (u32)(__popc(lo.x) + __popc(lo.y) + __popc(lo.z) + __popc(lo.w));
-                if (!PIPE)
-                {
-                    const uint4 hi = *reinterpret_cast<const uint4 *>(vbits + lane * kWPL + 4u);
-                    mycnt += (u32)(__popc(hi.x) + __popc(hi.y) + __popc(hi.z) + __popc(hi.w));
-                }
-            }
-            u32 incl = mycnt; // inclusive prefix of the candidate counts over lanes
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1)
-            {
-                const u32 t = __shfl_up(incl, o);
-                if (lane >= (u32)o)
-                    incl += t;
-            }
-            const u32 n = (a.flags & (1u << 31)) ? 0u : __shfl(incl, 63); // (ablation hook KREP_GPU_AC_NOVERIFY: filter cost only)
-            if (!ANCH)
-                acc_cand += (u32)__builtin_amdgcn_readfirstlane((int)n);
-            constexpr bool pair = STRIDE == 2; // a candidate stands for the ends t and t + 1
-            const u32 n_tot = n + ((XCAND && !(a.flags & (1u << 31)) && useg >= 1u) ? 1u : 0u); // rank n: the extra candidate
-            for (u32 b0 = 0; b0 < n_tot; b0 += 64)
-            {
-                const u32 qi = b0 + lane;
-                const bool live = qi < n;
-                const bool isx = XCAND && qi == n && qi < n_tot;
-                u32 rel = 0;
-                {
-                    // owner = first lane whose inclusive sum exceeds my rank
-                    u32 own = 0;
-#pragma unroll
-                    for (u32 step = 32; step; step >>= 1)
-                    {
-                        const u32 t = __shfl(incl, (own + step - 1u) & 63u);
-                        if (t <= qi)
-                            own += step;
-                    }
-                    own &= 63u;
-                    const u32 oincl = __shfl(incl, own), ocnt = __shfl(mycnt, own);
-                    if (live)
-                    {
-                        u32 t = qi - (oincl - ocnt); // my candidate is the t-th set bit of the owner's block
-                        const u32 *blk = vbits + own * kWPL;
-                        u32 w = 0, word = blk[0];
-                        for (;;)
-                        {
-                            const u32 c = (u32)__popc(word);
-                            if (t < c)
-                                break;
-                            t -= c;
-                            word = blk[++w];
-                        }
-                        for (; t; --t)
-                            word &= word - 1u;
-                        rel = PIPE ? 2u * (own * 128u + w * 32u + (u32)__builtin_ctz(word)) // (bit b <-> tested position 2b + 1)
-                                   : own * 256u + w * 32u + (u32)__builtin_ctz(word);
-                    }
-                }
-                // pair layout: bit j of the bitmap is tested position j + 1
-                const u64 pos = isx ? useg - 1u : useg + rel + (PAIR ? 1u : 0u);
-                u32 cA, cB;
-                u64 dmA, dmB;
-                bool simA, simB;
-                verify_ends(pos, live, isx, useg, cA, cB, dmA, dmB, simA, simB);
-                rank_and_emit(pos, cA, cB, dmA, dmB, simA, simB);
-            }
-            if (ANCH && n) // (wave-uniform) the END-pair bitmap is the next unit's again
-                *reinterpret_cast<uint4 *>(ebits + lane * 4u) = make_uint4(0u, 0u, 0u, 0u);
-        }
-        LineState wls{0, false, false, false};
-        if (LINES)
-        {
-            wls = ac_line_pass(kAcRounds * kCells, [&](int rj, u32 &H, u32 &N) {
-                const u32 bitoff = (u32)rj * kCellBytes + lane * 16u;
-                H = (bitmap[bitoff >> 5] >> (bitoff & 31u)) & 0xffffu;
-                N = nlmap[bitoff >> 4];
-            });
-            for (u32 w = lane; w < kAcBitmapWords; w += 64)
-                bitmap[w] = 0u;
-        }
 
-        acc_total += wcnt; // (deferred stage 3: zero here — the ticket's counts are added below)
-        if (chain && !emit_final && lane == 0 && !(kPend && defer))
-        {
-            u64 info = (u64)wcnt;
+            if constexpr (ANCH != 0)
+                ac_anchor_stage2<CI, ANCH>(a, wv, lane, useg, acc_cand);
+            // (ANCH: what follows is stage 3 — the same verify, over the END-pair bitmap instead of the candidate bitmap)
+            const u32 *vbits = ANCH ? wv.ebits : wv.cbits;
+            if constexpr (kPend)
+                ac_pend_unit<CI, LINES, SHORT, STRIDE, ANCH, WW>(a, wv, lane, vbits, unit, u_begin, u_end, defer, parks, pend, npend, ucnt, acc_cand);
+            else
+            { // the plain verify loop of a unit
+                static_assert(ANCH == 0, "the anchored instantiations pend");
+                u32 mycnt, incl, n, n_tot;
+                ac_verify_count<LINES, STRIDE>(a, vbits, lane, useg, mycnt, incl, n, n_tot);
+                acc_cand += (u32)__builtin_amdgcn_readfirstlane((int)n);
+                for (u32 b0 = 0; b0 < n_tot; b0 += 64)
+                    ac_verify_batch<CI, LINES, SHORT, STRIDE, WW>(a, wv, lane, vbits, useg, mycnt, incl, n, n_tot, b0);
+            }
+            LineState wls{0, false, false, false};
             if (LINES)
-                info |= line_bits(wls) | ((u64)(wls.cnt & kUiLineMask) << kUiLineShift);
-            else if (wcnt)
-                info |= kLnHead | kLnTail;
-            if (parked)
-                park_info[(u32)(unit - u_begin)] = info;
-            else
-                a.unitinfo[unit] = info;
-            if (want_pos && wcnt > a.stage_cap)
-            {
-                atomicAdd(&a.ctr->overflow_units, 1ull);
-                atomicMax(&a.ctr->max_unit_count, (u64)wcnt);
-            }
+                wls = ac_unit_lines(wv, lane);
+
+            acc_total += wv.wcnt; // (deferred stage 3: zero here — the ticket's counts are added below)
+            if (chain && !emit_final && lane == 0 && !(kPend && defer))
+                ac_unit_info<LINES>(a, wv, unit, u_begin, parks, want_pos, wls);
         }
-      }
-      if (kPend && defer)
-      {
-        // the ticket's units: their counts from `ucnt`, their info words in one store
         const u32 nun = (u32)(u_end - u_begin);
-        const u32 c = lane < nun ? ucnt : 0u;
-        acc_total += (u32)__builtin_amdgcn_readlane((int)ac_wave_scan_incl(c), 63); // (lanes 0..7 hold the counts; on the DPP network: no address registers)
-        if (chain && lane < nun)
-        {
-            u32 l2 = lane;
-            asm volatile("" : "+v"(l2)); // (the address is formed here, not kept — and spilled — from the kernel's start)
-            const u64 info = (u64)c | (c ? (kLnHead | kLnTail) : 0ull);
-            if (PIPE && !ANCH && a.stage_cap == 16u) // (parked: written with the ticket's slots below)
-                park_info[l2] = info;
-            else
-                a.unitinfo[u_begin + l2] = info;
-            if (want_pos && c > a.stage_cap)
-            {
-                atomicAdd(&a.ctr->overflow_units, 1ull);
-                atomicMax(&a.ctr->max_unit_count, (u64)c);
-            }
-        }
-      }
-      if (PIPE && !ANCH && !emit_final && chain && a.stage_cap == 16u && a.upt <= kAcUnitsPerTicketMax)
-      {
-        // the ticket's parked info words and slots (consecutive units: one contiguous 64-byte-per-unit region), two stores
-        const u32 nun = (u32)(u_end - u_begin);
-        u32 l3 = lane;
-        asm volatile("" : "+v"(l3)); // (the two addresses are formed here, not kept — and spilled — from the kernel's start)
-        if (l3 < nun)
-            a.unitinfo[u_begin + l3] = park_info[l3];
-        if (want_pos && l3 < nun * 4u)
-            reinterpret_cast<uint4 *>(reinterpret_cast<u32 *>(a.stage) + u_begin * 16u)[l3] = reinterpret_cast<const uint4 *>(park_slots)[l3];
-      }
+        if (kPend && defer)
+            acc_total += ac_ticket_info<PIPE && !ANCH>(a, wv, lane, u_begin, nun, ucnt, chain, want_pos);
+        if (PIPE && !ANCH && !emit_final && chain && a.stage_cap == 16u && a.upt <= kAcUnitsPerTicketMax)
+            ac_ticket_unpark(a, wv, lane, u_begin, nun, want_pos);
     }
     if (lane == 0 && acc_total && !a.emit_mode)
         atomicAdd(&a.ctr->total, acc_total);

@@ -113,6 +113,80 @@ __device__ __forceinline__ u32 ac_wave_scan_incl(u32 x)
     x += (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x143 /* row_bcast:31 */, 0xc, 0xf, false);
     return x;
 }
+// the same sum on the shuffle network (six ds_bpermute with per-lane addresses): see the call sites for which network a stage uses
+__device__ __forceinline__ u32 ac_shfl_scan_incl(u32 x, const u32 lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+        const u32 t = __shfl_up(x, o);
+        if (lane >= (u32)o)
+            x += t;
+    }
+    return x;
+}
+// set bits in a lane's block of a wave bitmap: WPL (4 or 8) dwords at bits + lane * WPL
+template <u32 WPL>
+__device__ __forceinline__ u32 ac_block_popc(const u32 *bits, const u32 lane)
+{
+    static_assert(WPL == 4u || WPL == 8u, "a lane owns 4 or 8 dwords of the unit's bitmap");
+    const uint4 lo = *reinterpret_cast<const uint4 *>(bits + lane * WPL);
+    u32 c = (u32)(__popc(lo.x) + __popc(lo.y) + __popc(lo.z) + __popc(lo.w));
+    if (WPL == 8u)
+    {
+        const uint4 hi = *reinterpret_cast<const uint4 *>(bits + lane * WPL + 4u);
+        c += (u32)(__popc(hi.x) + __popc(hi.y) + __popc(hi.z) + __popc(hi.w));
+    }
+    return c;
+}
+// index of the q-th set bit (q from 0) of a wave bitmap of 64 blocks of WPL dwords, given every lane's count `mycnt` of its block and
+// their inclusive prefix `incl`: owner = first lane whose inclusive sum exceeds q (a binary search over the sums, every lane takes
+// part in its shuffles), then the t-th set bit of the owner's block.  Only a lane with `live` walks the block (q < the bitmap's total).
+template <u32 WPL>
+__device__ __forceinline__ u32 ac_nth_set_bit(const u32 *bits, const u32 incl, const u32 mycnt, const u32 q, const bool live)
+{
+    u32 own = 0;
+#pragma unroll
+    for (u32 step = 32; step; step >>= 1)
+    {
+        const u32 t = __shfl(incl, (own + step - 1u) & 63u);
+        if (t <= q)
+            own += step;
+    }
+    own &= 63u;
+    const u32 oincl = __shfl(incl, own), ocnt = __shfl(mycnt, own);
+    u32 at = 0;
+    if (live)
+    {
+        u32 t = q - (oincl - ocnt);
+        const u32 *blk = bits + own * WPL;
+        u32 w = 0, word = blk[0];
+        for (;;)
+        {
+            const u32 c = (u32)__popc(word);
+            if (t < c)
+                break;
+            t -= c;
+            word = blk[++w];
+        }
+        for (; t; --t)
+            word &= word - 1u;
+        at = own * (32u * WPL) + w * 32u + (u32)__builtin_ctz(word);
+    }
+    return at;
+}
+// start ownership of a depth mask (bit d: a pattern of length d ends at `end`): the match start s = end + 1 - d has to lie in [own_lo, own_hi)
+__device__ __forceinline__ u32 ac_own_clip(u32 m, const u64 end, const u64 own_lo, const u64 own_hi)
+{
+    const u64 e = end + 1;
+    if (e <= own_lo)
+        return 0u;
+    if (e - own_lo < 32)
+        m &= (2u << (u32)(e - own_lo)) - 1u; // d <= e - own_lo
+    if (e > own_hi)
+        m = (e - own_hi < 32) ? (m & ~((2u << (u32)(e - own_hi)) - 1u)) : 0u; // d > e - own_hi
+    return m;
+}
 __device__ __forceinline__ u32 ac_fold4(u32 x)
 {
     u32 t = x & 0x7f7f7f7fu;
@@ -403,20 +477,7 @@ __device__ __forceinline__ void ac_eval_entry(const AcArgs &a, bool found, const
         slow = !(info & kG4Simple) || (L == clen && (info & kG4Cont));
         m |= ((e0.y >> 31) << 4) | ((e0.w & ((1u << L) - 1u)) << 5); // bit d: a pattern of length d ends here
     }
-    if (!own_by_end)
-    { // the match start s = end + 1 - d has to lie in [own_lo, own_hi)
-        const u64 e = end + 1;
-        if (e <= a.own_lo)
-            m = 0;
-        else
-        {
-            if (e - a.own_lo < 32)
-                m &= (2u << (u32)(e - a.own_lo)) - 1u; // d <= e - own_lo
-            if (e > a.own_hi)
-                m = (e - a.own_hi < 32) ? (m & ~((2u << (u32)(e - a.own_hi)) - 1u)) : 0u; // d > e - own_hi
-        }
-    }
-    dm = m;
+    dm = own_by_end ? m : ac_own_clip(m, end, a.own_lo, a.own_hi);
 }
 
 // the level-by-level walk behind the fast verifiers: count, and (dictionaries without short patterns) the depth mask

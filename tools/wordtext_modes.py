@@ -21,4 +21,4 @@ for kind in ("rare", "uniform"):
             out = plan.scan(buf.data_ptr(), n, 0, n, 0, pos.data_ptr(), cap, time_it=True)
             ts.append(out.kernel_ms)
         plan.close()
-        print(f"{kind:8s} {str(kw):50s} {out.count:10d} matches  first {ts[0]:8.2f}  median of the rest {statistics.median(ts[1:]):8.2f} ms = {n / statistics.median(ts[1:]) / 1e6:6.0f} GB/s", flush=True)
+        print(f"{kind:8s} {str(kw):50s} {out.count:10d} matches  first {ts[0]:8.3f}  median of the rest {statistics.median(ts[1:]):8.3f} ms = {n / statistics.median(ts[1:]) / 1e6:6.0f} GB/s", flush=True)
