@@ -86,8 +86,10 @@ __device__ __forceinline__ u32 tiny_scramble16(u32 m) // position-ordered 16 bit
 // scratch reload waits in the same in-order vmcnt queue as the prefetched text: the pipeline drained once per unit)
 // LONG: the dictionary holds a long length (AcTiny::llong) — its own instantiations, so that the others carry none of its code
 // FIVE: 4-byte patterns AND a long length (AcTiny::five): the long patterns are a fifth class.  Shipped for case-sensitive
-// COUNTING only (168 VGPRs, 3 waves per SIMD: `if else while` 3.4 -> 4.2 TB/s); its one-pass and -i instantiations compile but
-// measured slower than the general kernel at the 2 waves per SIMD they need, and are not dispatched
+// COUNTING only (168 VGPRs, 3 waves per SIMD: `if else while` 3.4 -> 4.2 TB/s).  Its one-pass and -i instantiations were built and
+// measured slower than the general kernel at the 2 waves per SIMD they need (one pass: 211-217 VGPRs, `if else while` 2.8 against
+// 3.3 TB/s with offsets; -i: 173 VGPRs, 3.0 against 3.4 TB/s — DESIGN.md 4.2b): they are not dispatched, and the kernel holds no code
+// for them (static_assert below)
 // DENSE (with FUSED): the one-pass writer for texts on which most lane-cells hold a match (`-e a -e Sherlock`: 3.5 % of the bytes,
 // 577 matches per 16-KiB unit — 440 twelve-byte items, three units and the ring is full).  The matches are decoded WHERE THEY ARE
 // FOUND — at that density a third of the lanes walk, not one in sixty — into 16-bit ring entries, the END's offset in the unit and a
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
     extern __shared__ __attribute__((aligned(16))) u32 s_tiny[];
     const u32 lane = lane_id(), wave = threadIdx.x >> 6;
     static_assert(!FUSED || (!LINES && !KEEP && !EMIT), "the one-pass record writer is its own mode");
-    static_assert(!FIVE || (!LINES && !KEEP && !EMIT && !LONG), "a fifth class: counting and one-pass records only");
+    static_assert(!FIVE || (!CI && !LINES && !KEEP && !EMIT && !LONG && !FUSED), "a fifth class: the case-sensitive count only");
     if constexpr (FUSED)
     {
         // the resolver: whichever wave 0 of a block gets here first (a wave that runs, whatever part of the grid is resident)
@@ -166,9 +168,9 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
     };
     // the matches of one lane-cell from its two length words, in the reference's order — END ascending, longest first
     // (aho_corasick.c:383-437): put(position e of the END inside the lane's 16 bytes, length)
-    auto walk_lane_cell = [&](const u32 cx, const u32 cy, const u32 cz, const u32 l4, const u32 l5, auto put) __attribute__((always_inline)) {
+    auto walk_lane_cell = [&](const u32 cx, const u32 cy, const u32 l4, auto put) __attribute__((always_inline)) {
         // ENDs of the lane-cell in position order: bit 8 b + w of the any-length word is position 4 w + b
-        const u32 hs = (cx | (cx >> 4) | cy | (cy >> 4) | cz) & 0x0f0f0f0fu;
+        const u32 hs = (cx | (cx >> 4) | cy | (cy >> 4)) & 0x0f0f0f0fu;
         u32 h = 0;
 #pragma unroll
         for (int b = 0; b < 4; ++b)
@@ -181,14 +183,13 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
             const u32 e = (u32)__builtin_ctz(h);
             h &= h - 1u;
             const u32 bit = 8u * (e & 3u) + (e >> 2);
-            if (FIVE && ((cz >> bit) & 1u)) put(e, l5);
             if ((cy >> (bit + 4u)) & 1u) put(e, l4);
             if ((cy >> bit) & 1u) put(e, 3u);
             if ((cx >> (bit + 4u)) & 1u) put(e, 2u);
             if ((cx >> bit) & 1u) put(e, 1u);
         }
     };
-    auto flush = [&](const u32 l4, const u32 l5) __attribute__((always_inline)) {
+    auto flush = [&](const u32 l4) __attribute__((always_inline)) {
         const u64 first = tk_wait_prefix(a.tk_pref, pend_t, a.ctr, lane);
         const u64 tbase = a.anchor + pend_t * (u64)a.upt * kAcUnitBytes + a.global_base;
         u64 run = first; // record index of the batch's first match (uniform)
@@ -197,11 +198,8 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
             const bool live = b0 + lane < pend_items;
             const u32 slot = (pend_at + b0 + lane) & (kTinyRing - 1u);
             const uint2 m = live ? ring_m[slot] : make_uint2(0u, 0u);
-            const u32 w3 = live ? ring_id[slot] : 0u;
-            // (FIVE: the third word holds the fifth class's length word in the low nibbles and the index in the high ones)
-            const u32 cz = FIVE ? (w3 & 0x0f0f0f0fu) : 0u;
-            const u32 id = FIVE ? (((w3 >> 4) & 0xfu) | ((w3 >> 8) & 0xf0u) | ((w3 >> 12) & 0xf00u) | ((w3 >> 16) & 0xf000u)) : w3;
-            const u32 c = (u32)(__popc(m.x) + __popc(m.y) + __popc(cz));
+            const u32 id = live ? ring_id[slot] : 0u;
+            const u32 c = (u32)(__popc(m.x) + __popc(m.y));
             // exclusive lane prefix of the match counts from ballot bit-planes (an item holds 1-3 matches: two planes as a rule)
             u32 excl = 0, tot = 0;
             auto plane = [&](const int b) __attribute__((always_inline)) {
@@ -227,7 +225,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
             if (c)
             {
                 const u64 end0 = tbase + (u64)id * 16u + 1u; // one past the END at position 0 of the lane-cell
-                walk_lane_cell(m.x, m.y, cz, l4, l5, [&](const u32 e, const u32 len) {
+                walk_lane_cell(m.x, m.y, l4, [&](const u32 e, const u32 len) {
                     if (idx < a.pos_cap)
                     {
                         const u64 en = end0 + e, st = en - len;
@@ -402,7 +400,6 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                     // ---- per length: 0x80 in every byte at which a pattern of that length ENDS.  One pattern = one scalar
                     //      register (its bytes, last one lowest) + under -i one of letter flags; splats on the scalar unit.
                     u32 HA[4] = {0u, 0u, 0u, 0u}, F[4] = {0u, 0u, 0u, 0u}; // any length, per dword | scrambled mask per length
-                    u32 F5 = 0u;                                           // ... of the fifth class (FIVE)
                     // DENSE: the lane-cell's matches as ONE 64-bit word in emission order — bit 4 e + (4 - class) for a match of that
                     // class ending at position e: END ascending, longest class first.  Interior rounds build it per dword (Y[w]: a
                     // nibble per position at bit 8 b, compressed below), boundary rounds from the clipped 16-bit masks.
@@ -545,14 +542,9 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                             }
                             if (inter)
                             {
-                                if (!FUSED)
-                                {
 #pragma unroll
-                                    for (int w = 0; w < 4; ++w)
-                                        asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(mycnt) : "v"(Z[w]));
-                                }
-                                else
-                                    F5 = (Z[0] >> 7) | (Z[1] >> 6) | (Z[2] >> 5) | (Z[3] >> 4);
+                                for (int w = 0; w < 4; ++w)
+                                    asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(mycnt) : "v"(Z[w]));
                             }
                             else
                             {
@@ -562,8 +554,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                                     pm |= movemask4(Z[w]) << (4 * w);
                                 const u64 lm1 = (u64)ll - 1ull;
                                 pm &= clip(a.end_lo, a.end_hi) & clip(lm1, ~0ull) & clip(a.own_lo + lm1, a.own_hi + lm1);
-                                F5 = tiny_scramble16(pm);
-                                mycnt += FUSED ? 0u : (u32)__popc(pm);
+                                mycnt += (u32)__popc(pm);
                             }
                         }
                     }
@@ -634,7 +625,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                     else if constexpr (FUSED)
                     {
                         const u32 cx = F[0] | (F[1] << 4), cy = F[2] | (F[3] << 4);
-                        const u32 c = (u32)(__popc(cx) + __popc(cy) + __popc(F5)); // this lane's matches in the cell
+                        const u32 c = (u32)(__popc(cx) + __popc(cy)); // this lane's matches in the cell
                         lane_cnt += c;
                         const u64 bm = __ballot(c != 0u);
                         if (bm)
@@ -644,9 +635,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
                             {
                                 const u32 slot = (f_at + idx) & (kTinyRing - 1u);
                                 ring_m[slot] = make_uint2(cx, cy);
-                                const u32 id = (u32)(unit - u_begin) * kTinyEntries + (u32)r * (kSegBytes / 16) + (u32)j * kWave + lane;
-                                // (FIVE: the fifth length word sits in the low nibbles, the 13-bit index goes into the high ones)
-                                ring_id[slot] = FIVE ? (F5 | ((id & 0xfu) << 4) | ((id & 0xf0u) << 8) | ((id & 0xf00u) << 12) | ((id & 0xf000u) << 16)) : id;
+                                ring_id[slot] = (u32)(unit - u_begin) * kTinyEntries + (u32)r * (kSegBytes / 16) + (u32)j * kWave + lane;
                             }
                             f_items += (u32)__popcll(bm);
                         }
@@ -972,7 +961,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
             if (lane == 0)
                 __hip_atomic_store(&a.tk_agg[tk], (u64)tcnt | kTkReady, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (pend)
-                flush(len4, llong);
+                flush(len4);
             if (f_items && f_items <= f_room)
             {
                 pend = true;
@@ -1001,7 +990,7 @@ __global__ __launch_bounds__(kTinyBlock, KG_TINY_KEEP_WAVES_ARG) void ac_tiny_ke
             if constexpr (DENSE)
                 flush_dense(len4);
             else
-                flush(len4, llong);
+                flush(len4);
         }
         if (overflowed && lane == 0)
             atomicAdd(&a.ctr->overflow_units, 1ull);
