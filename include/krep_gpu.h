@@ -431,7 +431,27 @@ int krep_gpu_regex_compile_ext(const search_params_t *params, krep_gpu_regex_ext
  *     the match at s is (s, the largest such e over all branches); the first s that has one is emitted and resume moves to its e.
  *   Records ascend in start.  -c counts the lines that hold a match.  max_count, its 0 corner and the empty text as above;
  *   only_matching and reference_simd change nothing.
- * Split: KREP_GPU_SPLIT_WHOLE.  A window that is not the whole text is refused (2).
+ * Split: KREP_GPU_SPLIT_WHOLE.  A window that is not the whole text is refused (2).  That is the default; with
+ *   krep_gpu_set_regex_loops_windows(1) it is KREP_GPU_SPLIT_PIECES:
+ *   Ownership.  A window reports the matches of the whole text whose START lies in its owned range, global_base + [own_lo, own_hi);
+ *     the lists of adjacent windows concatenate to the whole-text list.  A line's walk still starts at the line's first byte — the
+ *     matches in front of own_lo decide where the first owned attempt stands — so the buffer must hold every line that meets the
+ *     owned range, whole.  A finite max_count gives each window its own first max_count records.  -c counts the lines that hold an
+ *     owned start; head_line_hit / tail_line_hit / has_newline mean what every other scan's mean (a counted line that began at or in
+ *     front of own_lo, one that ends at or behind own_hi, a '\n' inside the owned range), and krep_gpu_combine_line_counts() folds the
+ *     windows.  krep_gpu_scan_device_seq() passes its boundary record through: the family has no sequential dependency.
+ *   Context.  No line of more than 4096 bytes is ever walked, so 4096 bytes of the text on each side of the owned range (fewer where
+ *     the text begins or ends) hold every such line.  Two refusals (2, nothing written): a line that meets the owned range and is
+ *     longer than 4096 bytes as far as the buffer shows it ("a line of more than 4096 bytes"), and a line that meets the owned range,
+ *     is at most that long, and touches an end of the buffer that is not an end of the text ("the window does not hold the whole of a
+ *     line that meets its owned range").  A cut line in the context that does not meet the owned range is not looked at.  The line
+ *     the buffer's END cuts is held to this rule whether or not the buffer shows a filter occurrence in it: the occurrence of a match
+ *     that starts in the owned range may lie behind that end.
+ *   The road is chosen per buffer.  The filter scan, its 1/64 density rule and the line analysis run over the buffer, not over the
+ *     owned range, so whether a long line that holds no filter occurrence is met at all depends on the road each buffer takes: a
+ *     scan in pieces may refuse a text for a line of more than 4096 bytes where the one-window scan took the sparse road and never
+ *     looked at that line.  The host operators answer identically either way: the registered CPU function takes over.
+ *   The host executor stages each piece with 4097 bytes on both sides, shards such a search over num_gpus and streams it.
  * Long lines: a lane of the device walks one line, and its worst case is quadratic in the line's length (a.*b on a line of a's).  A
  *   candidate line of more than 4096 bytes is not walked: the scan returns 2 ("a line of more than 4096 bytes") with nothing
  *   written, and the operator takes the road of every run-time failure (the registered CPU function, or KREP_GPU_FAILED).
@@ -453,6 +473,10 @@ typedef struct krep_gpu_regex_loops
 int krep_gpu_regex_compile_loops(const search_params_t *params, krep_gpu_regex_loops_t *out);
 void krep_gpu_set_regex_loops(int on); /* process-wide; default 0, or $KREP_GPU_REGEX_LOOPS at load */
 int krep_gpu_get_regex_loops(void);
+/* Windows of such a search ("Split" above): process-wide; default 0, or $KREP_GPU_REGEX_LOOPS_WINDOWS at load.  Off, or with
+ * krep_gpu_set_regex_loops() off, every call answers as if this switch did not exist. */
+void krep_gpu_set_regex_loops_windows(int on);
+int krep_gpu_get_regex_loops_windows(void);
 
 /* The in-memory twin of search_file()/search_string() that BASELINE.json calls search_buffer():
  * validation as krep.c:2013-2049 (no patterns -> 2; empty pattern among several -> 2; pattern

@@ -255,13 +255,22 @@ static int env_regex_loops()
     const char *e = getenv("KREP_GPU_REGEX_LOOPS");
     return e && *e && atoi(e) != 0 ? 1 : 0;
 }
+// ... and whether such a search may be cut into windows (include/krep_gpu.h, "Windows"): a switch of its own, off by default
+static int env_regex_loops_windows()
+{
+    const char *e = getenv("KREP_GPU_REGEX_LOOPS_WINDOWS");
+    return e && *e && atoi(e) != 0 ? 1 : 0;
+}
 namespace kg {
 std::atomic<int> g_regex_loops{env_regex_loops()}; // (read when the library is loaded)
+std::atomic<int> g_regex_loops_windows{env_regex_loops_windows()};
 std::atomic<int> g_rl_force_road{0};               // test hook: 0 auto, 1 the sparse road, 2 the dense road (kg_regex_loops.hip)
 std::atomic<uint64_t> g_rl_sparse{0}, g_rl_dense{0}; // scans that took each road
 }
 extern "C" void krep_gpu_set_regex_loops(int on) { kg::g_regex_loops.store(on != 0, std::memory_order_relaxed); }
 extern "C" int krep_gpu_get_regex_loops(void) { return kg::g_regex_loops.load(std::memory_order_relaxed); }
+extern "C" void krep_gpu_set_regex_loops_windows(int on) { kg::g_regex_loops_windows.store(on != 0, std::memory_order_relaxed); }
+extern "C" int krep_gpu_get_regex_loops_windows(void) { return kg::g_regex_loops_windows.load(std::memory_order_relaxed); }
 extern "C" void krep_gpu_debug_force_regex_loops_road(int road) { kg::g_rl_force_road.store(road == 1 || road == 2 ? road : 0); }
 extern "C" void krep_gpu_debug_regex_loops_roads(uint64_t *sparse, uint64_t *dense)
 {

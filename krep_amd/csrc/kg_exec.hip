@@ -765,7 +765,12 @@ std::vector<Piece> piece_layout(const PieceJob &job, size_t chunk, int ndev)
     for (size_t i = 0; i < job.params->num_patterns; ++i)
         lmax = std::max(lmax, job.params->pattern_lens[i]);
     if (job.params->use_regex)
+    {
         lmax = std::max<size_t>(lmax, 16); // a{16} is five pattern bytes and sixteen text bytes: the halo follows L <= 16
+        RegexCompiled rc;
+        if (!regex_compile_cached(job.params, &rc) && rc.is_loops)
+            lmax = 4096; // *, + and {n,}: a piece holds every line that meets its owned range, whole (kg_regex_loops.hip)
+    }
     const size_t ctx = lmax + 1; // pattern_len-1 to complete straddling matches, +1 for -w, +1 slack
     const size_t share = (len + (size_t)job.G - 1) / (size_t)job.G;
     std::vector<Piece> pcs;

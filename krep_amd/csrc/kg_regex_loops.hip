@@ -12,7 +12,7 @@
 //   dense: a filter like [a-z] would write 16 bytes of record per text byte.  When the filter's counting launch reports more than one
 //     occurrence per 64 text bytes its emitting launch is skipped (krep_gpu_plan::rx_emit_limit) and EVERY line is a candidate: the
 //     record list of an inner single-byte plan for '\n' (kg_single.hip) says where they are.
-// Stage 2, kg::rx_line_walk<LINES, EMIT>: one lane per candidate line, grid-stride.  Branch i lives in bits [o_i, o_i + L_i) of a 32-bit
+// Stage 2, kg::rx_line_walk<LINES, EMIT, WIN>: one lane per candidate line, grid-stride.  Branch i lives in bits [o_i, o_i + L_i) of a 32-bit
 // state, T[byte] has bit o_i + j set when byte is in place j of branch i (in LDS once per bank, rx_fill_table), INIT holds every o_i,
 // FIN every o_i + L_i - 1, PLUS the places that repeat.  An attempt from s starts with S = INIT & T[text[s]] and steps
 // S = (((S << 1) & ~INIT) | (S & PLUS)) & T[b]: a place hands over to the next one, a repeating place also stays.  The last position
@@ -25,6 +25,19 @@
 // Bounded work: a lane's worst case is quadratic in its line's length (a.*b on a line of a's).  The counting launch does not walk a
 // candidate line of more than 4096 bytes and raises Counters::overflow_units; the host reads that first and refuses the scan (2)
 // with nothing written.
+// Windows (krep_gpu_set_regex_loops_windows; off: any window but the whole text is refused).  The kernel owns STARTS, not lines: a
+// line is looked at when it meets [own_lo, own_hi) (ls < own_hi && le > own_lo), its walk starts at the line's first byte — the
+// matches in front of own_lo say where the first owned attempt stands —, a match is counted or emitted when own_lo <= s < own_hi, and
+// the walk ends with the owned starts (under -c with the first OWNED match).  -c reports what every other scan reports for its owned
+// window: kLnHead for a counted line with ls <= own_lo, kLnTail for one with le >= own_hi, kLnNl for a '\n' inside the owned range
+// (the host looks for one itself when no line that meets the range says so).  A line that meets the owned range and touches an end
+// of the buffer that is not an end of the text is CUT: the buffer does not show where it starts, or ends.  Longer than 4096 bytes
+// as far as it shows, it raises overflow_units bit 0 like any long line; else bit 1, and the host refuses the scan (2) with a reason
+// of its own.  Since no line of more than 4096 bytes is walked, 4096 bytes of context on each side of the owned range hold every line
+// the window needs.  Stage 1 runs over the BUFFER, the inner plans see it as a whole text with base 0; the road is chosen per buffer.
+// On the sparse road the line the buffer's end cuts is looked at by the host as well: its filter occurrence may lie behind that end.
+// The whole-text scan is the case own_lo = 0, own_hi = text_len in a buffer that begins and ends the text; it runs the instantiations
+// without WIN, in which these are constants and the ownership tests fold away (rl_launch picks them).
 // Reads: no byte outside [0, text_len), one byte at a time at any alignment: the walk of a lane per line is not coalesced, which is
 // the price of the dense road.
 #include <hip/hip_runtime.h>
@@ -54,15 +67,45 @@ struct RlArgs
     const u64 *spans;
     u64 n_lines;
     u64 global_base;
+    u64 own_lo, own_hi; // the starts this scan owns (offsets in the buffer, own_hi <= text_len): a match is counted or emitted when
+                        // own_lo <= s < own_hi, a line is looked at when it meets that range
     u32 from_nl;
     u32 init, fin, plus;
-    u32 flags; // bit 0 ^, bit 1 $, bit 2: the end of the text ends a line ($ in a case-sensitive search)
+    // bit 0 ^, bit 1 $, bit 2: the end of the text ends a line ($ in a case-sensitive search, in the buffer that ends the text),
+    // bit 3: the buffer begins the text, bit 4: it ends the text
+    u32 flags;
     const u32 *table;
     RxOut o;   // unitinfo: the count of every candidate line; offsets: the index of its first record (kg_regex_dev.h)
 };
 
-// LINES: -c, a line is done with its first match and nothing is written per line; EMIT: the records at offsets[line]
-template <bool LINES, bool EMIT>
+// the longest match that starts at s in a line that ends at le: its end, 0 when there is none (a match is never empty)
+__device__ __forceinline__ u64 rl_attempt(const uint8_t *text, const u32 *T, u32 init, u32 fin, u32 plus, u64 s, u64 le, bool eol)
+{
+    u32 S = T[(u32)text[s] << 5] & init;
+    u64 best = 0;
+    if (S)
+    {
+        u64 p = s + 1; // S: the state behind byte p - 1
+        for (;;)
+        {
+            if ((S & fin) != 0u && (!eol || p == le))
+                best = p;
+            if (p >= le)
+                break;
+            S = (((S << 1) & ~init) | (S & plus)) & T[(u32)text[p] << 5];
+            if (!S)
+                break;
+            ++p;
+        }
+    }
+    return best;
+}
+
+// LINES: -c, a line is done with its first match and nothing is written per line; EMIT: the records at offsets[line]; WIN: the owned
+// range and the two ends of the buffer are what RlArgs says — without it they are the constants of a scan of the whole text
+// ([0, text_len) in a buffer that begins and ends the text) and the compiler folds the ownership tests away: measured, the same tests
+// on run-time values moved rows of profiles/regex_loops_scan.txt by 3-7 % in both directions (profiles/regex_loops_windows.txt)
+template <bool LINES, bool EMIT, bool WIN>
 __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
 {
     static_assert(!(LINES && EMIT), "-c writes no records");
@@ -70,10 +113,12 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
     rx_fill_table(s_T, a.table);
     const u32 *T = s_T + (lane_id() & 31u);
     const bool bol = (a.flags & 1u) != 0u, eol = (a.flags & 2u) != 0u, eot_ends = (a.flags & 4u) != 0u;
+    const bool begins = !WIN || (a.flags & 8u) != 0u, ends = !WIN || (a.flags & 16u) != 0u;
+    const u64 own_lo = WIN ? a.own_lo : 0, own_hi = WIN ? a.own_hi : a.text_len;
     const u64 n_threads = (u64)gridDim.x * kBlock;
-    u64 mine = 0;                 // matches (LINES: lines that hold one) of this lane's lines
+    u64 mine = 0;                 // owned matches (LINES: lines that hold one) of this lane's lines
     unsigned long long bits = 0;  // LINES: kLnNl | kLnHead | kLnTail as far as this lane's lines say them
-    bool too_long = false;
+    bool too_long = false, cut_line = false;
 
     for (u64 line = (u64)blockIdx.x * kBlock + threadIdx.x; line < a.n_lines; line += n_threads)
     {
@@ -91,31 +136,32 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
         le = min(le, a.text_len); // (whatever a span says, no byte outside the text is read)
         ls = min(ls, le);
         u32 cnt = 0;
-        if (le - ls > kRlMaxLine)
+        // a line that does not meet the owned range holds no owned start: not walked, not measured, count 0 and no bit
+        const bool relevant = ls < own_hi && le > own_lo;
+        if (!relevant)
+            ;
+        else if (le - ls > kRlMaxLine)
             too_long = true;
+        else if ((ls == 0 && !begins) || (le == a.text_len && !ends))
+            cut_line = true; // the buffer does not show where the line really starts, or ends
         else if (!eol || le < a.text_len || eot_ends)
         {
             u64 idx = EMIT ? a.o.offsets[line] : 0;
+            const u64 stop = min(le, own_hi); // the walk ends with the owned starts
             u64 s = ls;
-            while (s < le)
+            // The walk starts at the line's first byte, as the greedy rule wants it: the matches in front of own_lo say where the
+            // first owned attempt stands, and are not counted.  (With ^ the line's first byte is its only start.)  Only a line that
+            // straddles own_lo comes through here; the loop behind it is the walk of a whole line.
+            if (bol && ls < own_lo)
+                s = stop;
+            while (s < own_lo)
             {
-                u32 S = T[(u32)a.text[s] << 5] & a.init;
-                u64 best = 0; // the longest match at s ends here (0: none; a match is never empty)
-                if (S)
-                {
-                    u64 p = s + 1; // S: the state behind byte p - 1
-                    for (;;)
-                    {
-                        if ((S & a.fin) != 0u && (!eol || p == le))
-                            best = p;
-                        if (p >= le)
-                            break;
-                        S = (((S << 1) & ~a.init) | (S & a.plus)) & T[(u32)a.text[p] << 5];
-                        if (!S)
-                            break;
-                        ++p;
-                    }
-                }
+                const u64 best = rl_attempt(a.text, T, a.init, a.fin, a.plus, s, le, eol);
+                s = best ? best : s + 1;
+            }
+            while (s < stop)
+            {
+                const u64 best = rl_attempt(a.text, T, a.init, a.fin, a.plus, s, le, eol);
                 if (best)
                 {
                     if (EMIT)
@@ -126,7 +172,7 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
                     }
                     ++cnt;
                     if (LINES || bol)
-                        break;
+                        break; // (-c: the line's first OWNED match settles it)
                     s = best;
                 }
                 else
@@ -142,10 +188,12 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
         mine += cnt;
         if (LINES)
         {
-            if (ls > 0 || le < a.text_len)
+            // the bits every other scan reports for its owned window (krep_gpu_combine_line_counts): a '\n' inside it — the one that
+            // ends this line or the one in front of it —, a counted line that began at or before own_lo, one that ends behind own_hi
+            if (relevant && ((le < a.text_len && le < own_hi) || (ls > 0 && ls - 1 >= own_lo)))
                 bits |= kLnNl;
             if (cnt)
-                bits |= (ls == 0 ? kLnHead : 0ull) | (le == a.text_len ? kLnTail : 0ull);
+                bits |= (ls <= own_lo ? kLnHead : 0ull) | (le >= own_hi ? kLnTail : 0ull);
         }
         else
             a.o.unitinfo[line] = cnt;
@@ -163,8 +211,8 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
     }
     if (LINES && bits)
         atomicOr(&a.o.ctr->summary, bits);
-    if (too_long)
-        atomicOr(&a.o.ctr->overflow_units, 1ull);
+    if (too_long || cut_line)
+        atomicOr(&a.o.ctr->overflow_units, (too_long ? 1ull : 0ull) | (cut_line ? 2ull : 0ull));
 }
 
 static hipError_t rl_launch(const RlArgs &a, int mode, int num_cu, hipStream_t st)
@@ -174,12 +222,23 @@ static hipError_t rl_launch(const RlArgs &a, int mode, int num_cu, hipStream_t s
     u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 5u));
     if (const int force = g_rx_force_grid.load(); force > 0) // test hook: a starved grid (krep_gpu_debug_force_regex_grid)
         grid = std::min<u32>(grid, (u32)force);
+    // (the scan of a whole text: the instantiations without WIN)
+    const bool win = !(a.own_lo == 0 && a.own_hi == a.text_len && (a.flags & 24u) == 24u);
     if (mode == kRxLines)
-        hipLaunchKernelGGL((rx_line_walk<true, false>), dim3(grid), dim3(kBlock), 0, st, a);
+    {
+        if (win) hipLaunchKernelGGL((rx_line_walk<true, false, true>), dim3(grid), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((rx_line_walk<true, false, false>), dim3(grid), dim3(kBlock), 0, st, a);
+    }
     else if (mode == kRxEmit)
-        hipLaunchKernelGGL((rx_line_walk<false, true>), dim3(grid), dim3(kBlock), 0, st, a);
+    {
+        if (win) hipLaunchKernelGGL((rx_line_walk<false, true, true>), dim3(grid), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((rx_line_walk<false, true, false>), dim3(grid), dim3(kBlock), 0, st, a);
+    }
     else
-        hipLaunchKernelGGL((rx_line_walk<false, false>), dim3(grid), dim3(kBlock), 0, st, a);
+    {
+        if (win) hipLaunchKernelGGL((rx_line_walk<false, false, true>), dim3(grid), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((rx_line_walk<false, false, false>), dim3(grid), dim3(kBlock), 0, st, a);
+    }
     return hipGetLastError();
 }
 
@@ -246,16 +305,32 @@ static int rl_reserve_records(RxLoopsWork &wk, u64 need)
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ the scan of the whole text
+// the two refusals of a scan (Counters::overflow_units bit 0 and bit 1): nothing was written
+static int rl_refuse_long()
+{
+    return fail("regex with *, + or {n,}: a line of more than %u bytes: kept on krep's regex_search (a lane walks one line, and its "
+                "worst case is quadratic in the line's length)", kRlMaxLine);
+}
+static int rl_refuse_cut()
+{
+    return fail("regex with *, + or {n,}: the window does not hold the whole of a line that meets its owned range (the buffer begins or "
+                "ends inside it): stage %u bytes of the text on both sides of the owned range", kRlMaxLine);
+}
+
+// ------------------------------------------------------------------------------------------------ the scan of a window
 int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
                      krep_gpu_scan_out_t *out)
 {
     RegexProg &rx = *pl->rx;
     if (w.text_len == 0 || w.global_len == 0 || w.own_lo >= w.own_hi)
         return 0; // (no match is empty: the zeroed *out is the answer)
-    if (!(w.global_base == 0 && w.own_lo == 0 && w.own_hi >= w.text_len && w.global_len == w.text_len))
+    const bool whole = w.global_base == 0 && w.own_lo == 0 && w.own_hi >= w.text_len && w.global_len == w.text_len;
+    if (!whole && !g_regex_loops_windows.load(std::memory_order_relaxed))
         return fail("a regex with *, + or {n,} is walked line by line from each line's first byte: scan the whole text in one window "
                     "(krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
+    const u64 own_hi = std::min<u64>(w.own_hi, w.text_len);
+    if (w.own_lo >= own_hi)
+        return 0;
     if (!rx.work && rl_work_create(pl))
         return 2;
     RxLoopsWork &wk = *rx.work;
@@ -267,15 +342,34 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
     RlArgs a{};
     a.text = w.d_text; a.text_len = w.text_len;
     a.global_base = w.global_base;
+    a.own_lo = w.own_lo; a.own_hi = own_hi;
     a.init = rx.init; a.fin = rx.fin; a.plus = rx.plus;
-    a.flags = (rx.loops.bol ? 1u : 0u) | (rx.loops.eol ? 2u : 0u) | (pl->sp.case_sensitive ? 4u : 0u);
+    const bool begins = w.global_base == 0, ends = w.global_base + w.text_len == w.global_len;
+    a.flags = (rx.loops.bol ? 1u : 0u) | (rx.loops.eol ? 2u : 0u) | (pl->sp.case_sensitive && ends ? 4u : 0u) | (begins ? 8u : 0u) |
+              (ends ? 16u : 0u);
     a.table = rx.d_table;
     a.o.ctr = pl->d_ctr;
+    // stage 1 looks at the BUFFER, not at the owned range: a match that starts in front of own_hi may hold its filter factor behind it,
+    // and the inner plans refuse windows of their own (a filter alternation that can overlap itself).  To them the buffer is a whole
+    // text with base 0, so their records are buffer-relative, as krep_gpu_matching_lines() wants them.
+    const Window wb{w.d_text, w.text_len, 0, w.text_len, 0, w.text_len};
 
     // ---- stage 1: the candidate lines
     const int force = g_rl_force_road.load();
     bool dense = force == 2;
     bool has_newline = false, know_newline = false;
+    if (!dense && !ends)
+    {
+        // The sparse road looks at the lines that hold a filter occurrence IN THE BUFFER.  The line the buffer's end cuts may hold its
+        // occurrence behind that end and a match that starts in the owned range all the same, so that one line is looked at here: it
+        // meets the owned range when no newline stands between the last owned byte and the buffer's end.  (A line the buffer's START
+        // cuts needs no such look: an owned match lies in the part the buffer holds, with its occurrence.)
+        uint64_t pos = w.text_len;
+        if (tail_find_next_newline(w.d_text, own_hi - 1, w.text_len, &pl->d_ctr->pad[0], &pl->h_ctr->pad[0], st, &pos))
+            return 2;
+        if (pos >= w.text_len)
+            return w.text_len - (own_hi - 1) > kRlMaxLine ? rl_refuse_long() : rl_refuse_cut();
+    }
     if (!dense)
     {
         // more than one occurrence per 64 text bytes (a first value, the bench tool runs both roads): the dense road
@@ -287,7 +381,7 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
             krep_gpu_scan_out_t fo;
             memset(&fo, 0, sizeof fo);
             wk.filter->rx_emit_limit = std::min<u64>(limit, wk.rec_cap);
-            if (const int rc = scan_regex_alt(wk.filter, w, wk.d_rec, wk.rec_cap, st, 0, &fo))
+            if (const int rc = scan_regex_alt(wk.filter, wb, wk.d_rec, wk.rec_cap, st, 0, &fo))
                 return rc;
             if (fo.total_matches <= wk.filter->rx_emit_limit)
             {
@@ -334,8 +428,11 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
         a.from_nl = 1;
         a.spans = (const u64 *)wk.d_rec;
         a.n_lines = no.total_matches + 1;
-        has_newline = no.total_matches != 0;
-        know_newline = true;
+        if (w.own_lo == 0 && own_hi == w.text_len)
+        { // (the owned range is the buffer: its newline count says it)
+            has_newline = no.total_matches != 0;
+            know_newline = true;
+        }
     }
 
     // ---- stage 2: the walk of the candidate lines
@@ -354,9 +451,10 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
         HIPCHK(rl_launch(a, lines ? kRxLines : kRxCount, pl->num_cu, st));
         HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (pl->h_ctr->overflow_units & 1ull)
+            return rl_refuse_long();
         if (pl->h_ctr->overflow_units)
-            return fail("regex with *, + or {n,}: a line of more than %u bytes: kept on krep's regex_search (a lane walks one line, and its "
-                        "worst case is quadratic in the line's length)", kRlMaxLine);
+            return rl_refuse_cut();
         total = pl->h_ctr->total;
         nlines = pl->h_ctr->lines;
         summary = pl->h_ctr->summary;
@@ -372,13 +470,14 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
     }
     if (lines)
     {
-        // has_newline as a scan of the whole window reports it: the candidate lines may not say (none, or one that is the whole text)
+        // has_newline as a scan of the owned window reports it: the candidate lines may not say (none that meets it, or one that
+        // covers it)
         if (!know_newline && !(summary & kLnNl))
         {
-            uint64_t pos = w.text_len;
-            if (tail_find_next_newline(w.d_text, 0, w.text_len, &pl->d_ctr->pad[0], &pl->h_ctr->pad[0], st, &pos))
+            uint64_t pos = own_hi;
+            if (tail_find_next_newline(w.d_text, w.own_lo, own_hi, &pl->d_ctr->pad[0], &pl->h_ctr->pad[0], st, &pos))
                 return 2;
-            has_newline = pos < w.text_len;
+            has_newline = pos < own_hi;
         }
         summary = (summary & ~kLnNl) | ((has_newline || (summary & kLnNl)) ? kLnNl : 0ull);
     }

@@ -216,6 +216,11 @@ class Engine:
             L.krep_gpu_debug_force_regex_loops_road.argtypes = [C.c_int]
             L.krep_gpu_debug_regex_loops_roads.restype = None
             L.krep_gpu_debug_regex_loops_roads.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "krep_gpu_set_regex_loops_windows"):  # (likewise)
+            L.krep_gpu_set_regex_loops_windows.restype = None
+            L.krep_gpu_set_regex_loops_windows.argtypes = [C.c_int]
+            L.krep_gpu_get_regex_loops_windows.restype = C.c_int
+            L.krep_gpu_get_regex_loops_windows.argtypes = []
         if hasattr(L, "krep_gpu_debug_force_regex_grid"):
             L.krep_gpu_debug_force_regex_grid.restype = None
             L.krep_gpu_debug_force_regex_grid.argtypes = [C.c_int]
@@ -453,6 +458,15 @@ class Engine:
 
     def get_regex_loops(self) -> bool:
         return bool(self.lib.krep_gpu_get_regex_loops())
+
+    def set_regex_loops_windows(self, on: bool):
+        """krep_gpu_set_regex_loops_windows: whether a search the loops compiler took may be cut into windows (split_mode() PIECES,
+        4096 bytes of context on both sides of what a window owns) instead of taking the whole text in one (process-wide, off by
+        default, $KREP_GPU_REGEX_LOOPS_WINDOWS=1 at load)"""
+        self.lib.krep_gpu_set_regex_loops_windows(1 if on else 0)
+
+    def get_regex_loops_windows(self) -> bool:
+        return bool(self.lib.krep_gpu_get_regex_loops_windows())
 
     def force_regex_loops_road(self, road: int):
         """which road the loops scan finds its candidate lines by: 0 its own choice, 1 sparse (the filter's records), 2 dense (all lines)"""
@@ -934,6 +948,30 @@ class Plan:
             eng.regex_compile_loops(self.params)  # (raises the refusal when no compiler takes the search)
             return 4096 + 1  # a match of a loops program lies inside one line, and no line of more than 4096 bytes is walked
 
+    def is_loops(self) -> bool:
+        """whether the loops compiler took the plan's search (-E with *, + or {n,} behind an atom): the older compilers refuse it, the
+        switch is on and that compiler takes it"""
+        s, eng = self.params.s, self.eng
+        if not s.use_regex or not eng.get_regex_loops():
+            return False
+        for older in (eng.regex_compile_anchored, eng.regex_compile_alt, eng.regex_compile_ext):
+            try:
+                older(self.params)
+                return False
+            except KrepGpuError:
+                pass
+        try:
+            eng.regex_compile_loops(self.params)
+            return True
+        except KrepGpuError:
+            return False
+
+    def left_context(self, own_lo: int) -> int:
+        """The bytes of the text the pieces drivers stage in front of what a window owns: one (the byte -w and ^ look at), for a
+        loops plan min(own_lo, longest_match() - 1) = up to 4096: the line walk starts at the first byte of every line that meets the
+        owned range, and the scan refuses a buffer that begins inside such a line."""
+        return min(int(own_lo), self.longest_match() - 1 if self.is_loops() else 1)
+
     def grep_lines(self, d_text: int, n: int, filename=None, max_count=None, stream: int = 0, color=False) -> bytes:
         """What `krep [-m N] PATTERN FILE` prints (colour off) for the n bytes at d_text: the scan with records, the cut to the
         first max_count records in emission order (search_file()), the (start, end) order for a multi-pattern list, and the
@@ -984,7 +1022,8 @@ class Plan:
 
     def grep_lines_pieces(self, text, piece_bytes: int, filename=None, color=False, halo_bytes: int = 4096) -> bytes:
         """grep_lines for a text on the HOST that never lies on the device as a whole: it is staged piece by piece into ONE device
-        buffer of 1 + piece_bytes + halo bytes (the byte of left context, the piece, the halo), every piece is scanned with start
+        buffer of 1 + piece_bytes + halo bytes (the byte of left context — left_context(): up to 4096 for a loops plan —, the piece,
+        the halo), every piece is scanned with start
         ownership up to records_hi = buffer end - (longest_match() - 1) (the text's end where the buffer ends it), a multi-pattern
         list is put in (start, end) order, and krep_gpu_format_lines_window formats the lines that START in the piece.  A line the
         call reports as incomplete (it outruns the halo) is staged again as a window of its own, its reach doubled until it is
@@ -1019,10 +1058,11 @@ class Plan:
                                "(krep_gpu_split_mode)")
         longest = self.longest_match()
         halo = max(int(halo_bytes), longest)  # (records_hi >= own_hi)
+        lctx = self.left_context(total)  # one byte; a loops plan: 4096 (a window holds the lines that meet its owned range, whole)
         name = None if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
         fmt = line_format(name, bool(color))
         extra = fmt.prefix_len + fmt.line_close_len + fmt.before_match_len + fmt.after_match_len
-        state = {"buf": torch.empty(1 + piece_bytes + halo + 64, dtype=torch.uint8, device="cuda")}
+        state = {"buf": torch.empty(lctx + piece_bytes + halo + 64, dtype=torch.uint8, device="cuda")}
         parts = []
         view, step = memoryview(host.numpy()), 1 << 20
 
@@ -1046,8 +1086,8 @@ class Plan:
             return total
 
         def window(own_lo, own_hi, reach, records_left, lines_left):
-            """stage [own_lo - 1, own_hi + reach), scan and format it -> (LinesWindowOut, records the scan stored)"""
-            base, end = max(own_lo - 1, 0), min(own_hi + reach, total)
+            """stage [own_lo - lctx, own_hi + reach), scan and format it -> (LinesWindowOut, records the scan stored)"""
+            base, end = max(own_lo - lctx, 0), min(own_hi + reach, total)
             if state["buf"].numel() < end - base + 64:
                 state["buf"] = torch.empty(end - base + 64, dtype=torch.uint8, device="cuda")
             buf = state["buf"]
@@ -1090,7 +1130,7 @@ class Plan:
             res, stored = window(lo, hi, halo, left, lines_left)
             records_hi = total if hi + halo >= total else hi + halo - (longest - 1)
             if limit != abi.SIZE_MAX and hi < total:  # the records that START in the piece, on the buffer as it still stands
-                base = max(lo - 1, 0)
+                base = max(lo - lctx, 0)
                 before += int(self.scan(state["buf"].data_ptr(), min(hi + halo, total) - base, lo - base, hi - base, base,
                                         global_len=total).total_matches)
             if res is not None and lines_left != abi.SIZE_MAX:
@@ -1166,13 +1206,14 @@ class Plan:
     def grep_only_matching_pieces(self, text, piece_bytes: int, filename=None, color=False) -> bytes:
         """grep_only_matching for a text on the HOST that never lies on the device as a whole; returns the bytes of
         grep_only_matching on the resident text.  The text is cut into pieces of piece_bytes; piece [lo, hi) is staged as
-        [max(lo - 1, 0), min(hi + longest_match(), total)) into ONE reused device buffer (the byte of left context for -w, and
+        [max(lo - left_context(), 0), min(hi + longest_match(), total)) into ONE reused device buffer (the byte of left context for -w
+        — up to 4096 for a loops plan, whose line walks start at each line's first byte —, and
         behind the piece a match that starts on its last byte with the byte -w looks at behind it).  Under -o many single
         literals couple a match to the one before it (krep_gpu_split_mode() = CHAIN), so the pieces are scanned IN TEXT ORDER
         through scan_seq, each taking the carry of the one before it (the counting scan and the recording scan of a piece take the
         same carry); families without that dependency pass the carry through, so one road serves both classes.  A multi-pattern
         list is put in (start, end) order, and krep_gpu_format_matches_window formats the piece's records with count_to = the
-        next piece's base (hi - 1: its byte of left context), the newline count and the stale line number chained from call to call.
+        next piece's base (hi - 1: its byte of left context; hi - 4096 for a loops plan), the newline count and the stale line number chained from call to call.
         last_newline1 is looked up once on the host, backwards from the end of the text.  stale_rule (more than 10 records in the
         whole list) is false when max_count <= 10 and true as soon as the running count passes 10.  Until then only records that
         start at or behind last_newline1 depend on it: those are HELD BACK (StaleSchedule: at most 10 (start, end) pairs on the
@@ -1216,10 +1257,11 @@ class Plan:
         if limit == 0 or total == 0:
             return b""
         longest = self.longest_match()
+        lctx = self.left_context(total)  # one byte; a loops plan: 4096 (a window holds the lines that meet its owned range, whole)
         name = None if filename is None else (filename if isinstance(filename, bytes) else str(filename).encode())
         fmt = match_format(name, bool(color))
         per_item = fmt.prefix_len + fmt.before_number_len + fmt.after_number_len + fmt.after_match_len + 20 + 2 + longest
-        buf = torch.empty(1 + piece_bytes + longest + 64, dtype=torch.uint8, device="cuda")
+        buf = torch.empty(lctx + piece_bytes + longest + 64, dtype=torch.uint8, device="cuda")
         view, step = memoryview(host.numpy()), 1 << 20
         last_nl1, at = 0, total  # the last newline of the text + 1, looked for backwards from its end
         while at > 0 and not last_nl1:
@@ -1267,7 +1309,7 @@ class Plan:
             if left <= 0:
                 break
             hi = min(lo + piece_bytes, total)
-            base, end = max(lo - 1, 0), min(hi + longest, total)
+            base, end = max(lo - lctx, 0), min(hi + longest, total)
             buf[: end - base].copy_(host[base:end])
             d_text, blen = buf.data_ptr(), end - base
             found, carry_out = self.scan_seq(d_text, blen, lo - base, hi - base, base, global_len=total, carry_in=carry)
@@ -1285,7 +1327,7 @@ class Plan:
             flush, now, rule = sched.add(m, lambda: pos[: 2 * m].view(-1, 2).cpu().tolist())
             held_calls(flush, rule)
             # (a piece without records is formatted too: its call carries the newline count on)
-            res = fmt_call(d_text, blen, base, hi - 1 if hi < total else total, pos.data_ptr() if now else 0, now, rule)
+            res = fmt_call(d_text, blen, base, max(hi - lctx, 0) if hi < total else total, pos.data_ptr() if now else 0, now, rule)
             chain["nl"], chain["stale"] = int(res.newlines_before_count_to), int(res.stale_line)
         flush, rule = sched.end()
         held_calls(flush, rule)

@@ -5,7 +5,11 @@ warm-ups (3 after 1 when a scan takes more than half a second).  The yardstick c
 buffer.  Then every pattern with -c and with records, each road forced in turn (krep_gpu_debug_force_regex_loops_road) and the scan's
 own choice; and regex_search itself (oracle/_ref, one thread) on the first 256 MiB of the host twin.  There is no pass bar on these
 numbers: the switch krep_gpu_set_regex_loops stays off whatever they say.
-  usage: python tools/regex_loops_bench.py [GiB = 8] [CPU MiB = 256] [output = profiles/regex_loops_scan.txt]"""
+--windows N (with krep_gpu_set_regex_loops_windows on): every regex scan is N scans of the same resident text, window k owning the
+k-th share of it in a buffer that holds 4096 bytes more on each side, as the host executor stages its pieces; the time of a scan is the
+sum of the N hipEvent times, the count the sum of the windows' counts (under -c the lines that hold an owned start, not folded).
+--haystack: the first text only.
+  usage: python tools/regex_loops_bench.py [--windows N] [--haystack] [GiB = 8] [CPU MiB = 256] [output = profiles/regex_loops_scan.txt]"""
 import locale
 import os
 import statistics
@@ -23,6 +27,14 @@ import regex_ref  # noqa: E402
 import wordlist  # noqa: E402
 
 locale.setlocale(locale.LC_CTYPE, "C")  # the locale krep runs in; the -E compilers take no pattern in a multibyte one
+windows = 1
+if "--windows" in sys.argv:
+    i = sys.argv.index("--windows")
+    windows = max(1, int(sys.argv[i + 1]))
+    del sys.argv[i:i + 2]
+haystack_only = "--haystack" in sys.argv
+if haystack_only:
+    sys.argv.remove("--haystack")
 gib = float(sys.argv[1]) if len(sys.argv) > 1 else 8.0
 cpu_mib = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "regex_loops_scan.txt")
@@ -35,6 +47,9 @@ PATTERNS = [(b"Sherlo+ck", "filter Sherlo: rare"), (b"Sherlock.*[a-z]", "filter 
 ROADS = [(0, "auto"), (1, "sparse"), (2, "dense")]
 e = krep_amd.load()
 e.set_regex_loops(True)
+if windows > 1:
+    e.set_regex_loops_windows(True)
+CONTEXT = 4096  # bytes of the text a window's buffer holds on each side of what it owns (include/krep_gpu.h)
 buf = torch.empty(n + 64, dtype=torch.uint8, device="cuda")
 cap = n // 64
 pos = torch.empty(2 * cap, dtype=torch.int64, device="cuda")
@@ -46,9 +61,20 @@ def say(line):
     rows.append(line)
 
 
-def median_ms(plan, want_pos):
+def median_ms(plan, want_pos, parts=1):
     def scan():
-        return plan.scan(buf.data_ptr(), n, 0, n, 0, pos.data_ptr() if want_pos else 0, cap if want_pos else 0, time_it=True)
+        if parts == 1:
+            return plan.scan(buf.data_ptr(), n, 0, n, 0, pos.data_ptr() if want_pos else 0, cap if want_pos else 0, time_it=True)
+        total = abi.ScanOut()
+        for k in range(parts):
+            lo, hi = n * k // parts, n * (k + 1) // parts
+            b0, b1 = max(lo - CONTEXT, 0), min(hi + CONTEXT, n)
+            out = plan.scan(buf.data_ptr() + b0, b1 - b0, lo - b0, hi - b0, b0, pos.data_ptr() if want_pos else 0, cap if want_pos else 0,
+                            time_it=True, global_len=n)
+            total.kernel_ms += out.kernel_ms
+            total.count += out.count
+            total.total_matches += out.total_matches
+        return total
     out = scan()  # (builds the inner plans and sizes the scratch)
     warm, steady = (1, 3) if out.kernel_ms > 500 else (2, 10)
     ms = []
@@ -62,7 +88,10 @@ def median_ms(plan, want_pos):
 say(f"# tools/regex_loops_bench.py: {gib:g} GiB texts, hipEvent time of a whole scan (filter scan, line analysis, line walk), median of 10")
 say("# steady scans after 2 warm-ups (3 after 1 beyond 0.5 s); GB/s = text bytes / time; ratio = to the literal plan for `Sherlock` in the")
 say("# same mode on the same buffer; road: forced, or auto with the road it took")
-for name, kind, seed, needle, period in TEXTS:
+if windows > 1:
+    say(f"# --windows {windows}: every regex scan is {windows} scans, window k owning the k-th share of the text with {CONTEXT} bytes of context on each")
+    say("# side; the time is the sum of their hipEvent times, the count the sum of their counts (-c: not folded across the cuts)")
+for name, kind, seed, needle, period in TEXTS[:1] if haystack_only else TEXTS:
     e.generate(buf.data_ptr(), n, 0, kind, seed, needle, period)
     torch.cuda.synchronize()
     say(f"## {name} (seed {seed})")
@@ -81,7 +110,7 @@ for name, kind, seed, needle, period in TEXTS:
                 plan = e.plan(abi.Params([pat], regex=True, **kw))
                 try:
                     before = e.regex_loops_roads()
-                    ms, out = median_ms(plan, mode == "records")
+                    ms, out = median_ms(plan, mode == "records", windows)
                     after = e.regex_loops_roads()
                     took = "sparse" if after[0] > before[0] else "dense"
                     ref_ms = yard["records" if mode == "records" else "count"]
@@ -106,6 +135,8 @@ for name, kind, seed, needle, period in TEXTS:
     else:
         say("# no compiled reference (oracle/_ref) on this host: the CPU rows are missing")
 e.set_regex_loops(False)
+if windows > 1:
+    e.set_regex_loops_windows(False)
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as f:
     f.write("\n".join(rows) + "\n")
