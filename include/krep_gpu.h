@@ -243,6 +243,9 @@ search_func_t krep_gpu_select_search_algorithm(const search_params_t *params);
  *     an alternation of such sequences nor an expression of ?, {n,m} and groups that expands into one; -w).  The reason reported
  *     is the alternation compiler's when the search says an alternation (several patterns, or a '|' or '(' outside brackets and
  *     not behind a backslash), else the anchored compiler's; krep_gpu_regex_compile_ext()'s when only its own limits refuse.
+ *     With krep_gpu_set_regex_loops(1) krep_gpu_regex_compile_loops() is asked fourth, with krep_gpu_set_regex_groups(1)
+ *     krep_gpu_regex_compile_groups() fifth (both off by default): a search one of them takes is taken, and their own reason
+ *     replaces the earlier one only where their contracts below say so;
  * (count_lines_mode together with only_matching through memchr_short_search — a combination krep's main() never produces,
  * krep.c:3811-3814 — was refused until round 5 and is reproduced now: one window, krep_gpu_split_mode() = WHOLE.)
  * An operator called with such params anyway treats it like a run-time failure (see the top of this header): the
@@ -376,7 +379,8 @@ int krep_gpu_regex_compile_alt(const search_params_t *params, krep_gpu_regex_alt
  *   inside a group or in the middle of a branch; mixed anchors; more than 8 distinct sequences; a sequence with L + bol + eol > 16;
  *   the sum of L + bol + eol over the sequences > 32; -w; a multibyte locale; a pattern byte outside 0x01-0x7F; an atom the
  *   tokeniser refuses.
- * Every search asks krep_gpu_regex_compile_anchored() first, then krep_gpu_regex_compile_alt(), then this call: a search one of
+ * Every search asks krep_gpu_regex_compile_anchored() first, then krep_gpu_regex_compile_alt(), then this call (and, behind their
+ *   switches, krep_gpu_regex_compile_loops() and krep_gpu_regex_compile_groups() below): a search one of
  *   those takes runs the kernel it always ran.  The reason reported for a search all three refuse is the one reported before
  *   this compiler existed, unless the search fails only at this compiler's own limits (the number of sequences or places after
  *   expansion, an empty sequence in the expansion): then it is this compiler's.
@@ -477,6 +481,61 @@ int krep_gpu_get_regex_loops(void);
  * krep_gpu_set_regex_loops() off, every call answers as if this switch did not exist. */
 void krep_gpu_set_regex_loops_windows(int on);
 int krep_gpu_get_regex_loops_windows(void);
+
+/* ---- repeated and nested groups: (ab)+, (foo|bar)+;, ([a-z]+\.)+com, ((GET|POST) |HEAD )/api, [0-9]{1,3}\.[0-9]{1,3}\.… ----
+ * The four compilers above expand an expression into at most 8 flat sequences.  This one does not expand: it holds the expression
+ *   as its POSITION (Glushkov) automaton, one bit per atom occurrence.
+ * Grammar: krep_gpu_regex_compile_loops()'s with groups made recursive:
+ *   item = atom quant? | '(' alt ')' quant?      alt = seq ('|' seq)*      seq = item+
+ *   quant = '?' | '*' | '+' | '{n}' | '{n,}' | '{n,m}', behind atoms and behind groups; parentheses nest to depth 8.
+ *   Atoms are the tokeniser's, their classes probed from libc.  ^ and $ are taken only as the first and the last byte of a top-level
+ *   branch, the same pair on every top-level branch of every pattern; they take no position (the line walk owns them).
+ * Positions.  A counted quantifier copies its operand: X{2,} is X X+, X{1,3} is X X? X?, X{0,} is X*.  The positions are the atom
+ *   occurrences after that copying, numbered left to right, at most 32.  classes[i] is the class of position i; first / last are
+ *   the positions a match can start / end on; follow[i] the positions that can stand directly behind position i.
+ * Refused (2, each with its own reason): a class that holds '\n'; an expression that matches the empty string (a nullable
+ *   sub-expression inside a whole that is not — x(ab)*y, (a*b)+ — is taken); an empty alternative or an empty group; a quantifier
+ *   behind a quantifier or behind nothing; {0} and {0,0}; ^ or $ anywhere else; top-level branches with different anchors; more than 32
+ *   positions; nesting deeper than 8; a follow relation of more than 12 jump pairs (below); an expression without a filter (below);
+ *   -w; a multibyte locale; a pattern byte outside 0x01-0x7F; an atom the tokeniser refuses; and an expression one of the four older
+ *   compilers takes: they keep what is theirs.
+ * Jump pairs.  The line walk steps follow(S) = ((S & CHAIN) << 1) | (S & SELF) | the targets of every pair whose sources meet S:
+ *   CHAIN the positions i with i + 1 in follow[i] (never position 31), SELF those with i in follow[i]; what is left of a follow set
+ *   is a jump (source mask, target mask), and positions with the same remainder share a pair.  At most 12 pairs.
+ * The filter: at most 8 class sequences of at most 16 classes, 32 classes in all, with ONE binding property: every match of the
+ *   expression holds an occurrence of one of them as consecutive bytes.  It is derived from a set of positions that every match
+ *   passes (an atom: itself; a concatenation: the best of its parts that are not nullable; an alternation: the union over its
+ *   alternatives; X+ and X{n>=1,..}: that of X; a nullable part: none).  Each position's factor is its class lengthened along
+ *   forced edges: forward while no position reached so far is in `last` and all positions that can follow have one and the same
+ *   class, backward likewise with `first` and the predecessors.  Best is the smallest sum over the distinct factors of the product of
+ *   |class| / 256; on a tie the set whose shortest factor is longer, then the leftmost.  The IP expression gives [0-9]\.[0-9].
+ * What a scan reproduces: regex_search under REG_NEWLINE, per line, as krep_gpu_regex_compile_loops() states it ("What a scan
+ *   reproduces" above), with "a branch matches (s, e)" read as: text[s, e) is accepted by the automaton — text[s] is in the class of a
+ *   position of `first`, every next byte in the class of a position that follows the one before, the last one in `last`.  The match at
+ *   s is (s, the largest such e): leftmost start, longest end over ALL paths, which is what glibc's regexec reports for these
+ *   expressions (checked against the compiled reference with a brute-force model).
+ * Windows, context, long lines and split are the loops compiler's, word for word: "Split", "Ownership", "Context", "Long lines" above,
+ *   under the same switch krep_gpu_set_regex_loops_windows().
+ * The switch.  krep_gpu_regex_compile_groups() always works.  A SEARCH asks it fifth, after the loops compiler, only when
+ *   krep_gpu_set_regex_groups(1) is on: process-wide, off unless $KREP_GPU_REGEX_GROUPS=1 is set when the library is loaded, and
+ *   independent of krep_gpu_set_regex_loops().  Off, every call behaves and reports as if this compiler did not exist.  On, a search
+ *   all five refuse reports what it reported before, unless that was a reason about a group, about nesting or about what an
+ *   expansion multiplies out to (a group that is not a whole branch, a group that holds an alternation, nested parentheses, a
+ *   quantifier behind a group, more than 8 sequences, 16 places or 32 places after expansion): then it is this compiler's. */
+typedef struct krep_gpu_regex_groups
+{
+    uint32_t n_pos;              /* positions, 1..32 */
+    uint8_t classes[32][32];     /* classes[i]: the 256-bit class of position i */
+    uint32_t first, last;        /* bit i: a match can start / end on position i */
+    uint32_t follow[32];         /* follow[i] bit j: position j can stand directly behind position i */
+    int bol;                     /* every top-level branch starts with an unescaped ^ */
+    int eol;                     /* every top-level branch ends with an unescaped $   */
+    krep_gpu_regex_alt_t filter; /* the factors, each branch what krep_gpu_regex_compile() makes of that sequence alone */
+} krep_gpu_regex_groups_t;
+/* Host only, needs no device.  Returns 0 and fills *out, or 2 with the reason in krep_gpu_last_error(). */
+int krep_gpu_regex_compile_groups(const search_params_t *params, krep_gpu_regex_groups_t *out);
+void krep_gpu_set_regex_groups(int on); /* process-wide; default 0, or $KREP_GPU_REGEX_GROUPS at load */
+int krep_gpu_get_regex_groups(void);
 
 /* The in-memory twin of search_file()/search_string() that BASELINE.json calls search_buffer():
  * validation as krep.c:2013-2049 (no patterns -> 2; empty pattern among several -> 2; pattern

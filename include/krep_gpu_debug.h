@@ -80,6 +80,14 @@ void krep_gpu_debug_force_regex_grid(int blocks);
  * candidate lines — 0 the scan's choice (the filter's occurrences per text byte), 1 the sparse road (the filter's records), 2 the dense
  * road (every line, from the newline records); and how many scans took each road since the process started */
 void krep_gpu_debug_force_regex_loops_road(int road);
+/* test hook of the line walk's general step (kg_regex_loops.hip): with both krep_gpu_set_regex_loops() and krep_gpu_set_regex_groups()
+ * on, a plan made while this is on walks an expression the LOOPS compiler took by the step of the groups compiler's automaton (its
+ * places read as positions: a place hands over along CHAIN, a repeating place is in SELF, no jump pairs) — for the measurement of what
+ * the general step costs and the test that the two steps agree.  Off, or with either switch off, nothing changes. */
+void krep_gpu_debug_force_regex_general(int on);
+/* launches of the line walk's general step since the process started (counting and emitting launches alike): what tells a scan by
+ * the general step from one by the old step */
+uint64_t krep_gpu_debug_regex_general_walks(void);
 void krep_gpu_debug_regex_loops_roads(uint64_t *sparse, uint64_t *dense);
 /* a multi-pattern plan whose dictionary holds 1..3-byte patterns beside >= 8 longer ones: 0 not decided yet, 1 scanned as one dictionary, 2 split
  * (the long part anchored, the short part on its own, the record lists merged: kg_scan_ac.hip scan_ac_split); $KREP_GPU_AC_NO_SPLIT=1: never */

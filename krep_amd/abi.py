@@ -163,6 +163,17 @@ class RegexLoops(C.Structure):
     _fields_ = [("alt", RegexAlt), ("bol", C.c_int), ("eol", C.c_int), ("repeat", C.c_uint16 * 8), ("filter", RegexAlt)]
 
 
+class RegexGroups(C.Structure):
+    """krep_gpu_regex_groups_t: what krep_gpu_regex_compile_groups() makes of an expression with repeated or nested groups: its
+    position automaton (one position per atom occurrence: classes, first, last, follow), the line anchors and the filter"""
+    _fields_ = [("n_pos", C.c_uint32), ("classes", (C.c_uint8 * 32) * 32), ("first", C.c_uint32), ("last", C.c_uint32),
+                ("follow", C.c_uint32 * 32), ("bol", C.c_int), ("eol", C.c_int), ("filter", RegexAlt)]
+
+    def class_bytes(self, i: int) -> bytes:
+        """the bytes of position i's class, ascending"""
+        return bytes(b for b in range(256) if (self.classes[i][b >> 3] >> (b & 7)) & 1)
+
+
 class ShardInfo(C.Structure):
     """krep_gpu_shard_info_t: where the calling thread's last sharded host search ran."""
     _fields_ = [("shards", C.c_int), ("devices_used", C.c_int), ("device_ids", C.c_int * 16), ("comm_ranks", C.c_int),

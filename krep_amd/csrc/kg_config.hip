@@ -261,7 +261,16 @@ static int env_regex_loops_windows()
     const char *e = getenv("KREP_GPU_REGEX_LOOPS_WINDOWS");
     return e && *e && atoi(e) != 0 ? 1 : 0;
 }
+// ... and the groups compiler behind a switch of its own (include/krep_gpu.h, krep_gpu_regex_compile_groups), independent of the two above
+static int env_regex_groups()
+{
+    const char *e = getenv("KREP_GPU_REGEX_GROUPS");
+    return e && *e && atoi(e) != 0 ? 1 : 0;
+}
 namespace kg {
+std::atomic<int> g_regex_groups{env_regex_groups()};
+std::atomic<int> g_rl_force_general{0}; // test hook: a loops program is walked by the general step (kg_regex.hip, regex_prog_create)
+std::atomic<uint64_t> g_rl_general{0};  // launches of the line walk's general step (kg_regex_loops.hip)
 std::atomic<int> g_regex_loops{env_regex_loops()}; // (read when the library is loaded)
 std::atomic<int> g_regex_loops_windows{env_regex_loops_windows()};
 std::atomic<int> g_rl_force_road{0};               // test hook: 0 auto, 1 the sparse road, 2 the dense road (kg_regex_loops.hip)
@@ -271,6 +280,10 @@ extern "C" void krep_gpu_set_regex_loops(int on) { kg::g_regex_loops.store(on !=
 extern "C" int krep_gpu_get_regex_loops(void) { return kg::g_regex_loops.load(std::memory_order_relaxed); }
 extern "C" void krep_gpu_set_regex_loops_windows(int on) { kg::g_regex_loops_windows.store(on != 0, std::memory_order_relaxed); }
 extern "C" int krep_gpu_get_regex_loops_windows(void) { return kg::g_regex_loops_windows.load(std::memory_order_relaxed); }
+extern "C" void krep_gpu_set_regex_groups(int on) { kg::g_regex_groups.store(on != 0, std::memory_order_relaxed); }
+extern "C" int krep_gpu_get_regex_groups(void) { return kg::g_regex_groups.load(std::memory_order_relaxed); }
+extern "C" void krep_gpu_debug_force_regex_general(int on) { kg::g_rl_force_general.store(on != 0); }
+extern "C" uint64_t krep_gpu_debug_regex_general_walks(void) { return kg::g_rl_general.load(); }
 extern "C" void krep_gpu_debug_force_regex_loops_road(int road) { kg::g_rl_force_road.store(road == 1 || road == 2 ? road : 0); }
 extern "C" void krep_gpu_debug_regex_loops_roads(uint64_t *sparse, uint64_t *dense)
 {

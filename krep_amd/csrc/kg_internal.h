@@ -215,6 +215,9 @@ int ac_scan(const AcScan &c, krep_gpu_scan_out_t *out);
 extern std::atomic<int> g_force_rounds, g_force_stage_cap;   // krep_gpu_debug_force_rounds / _stage_cap
 extern std::atomic<int> g_rx_force_grid;                     // krep_gpu_debug_force_regex_grid: at most this many workgroups (0 = auto)
 extern std::atomic<int> g_regex_loops;                       // krep_gpu_set_regex_loops: a search asks the loops compiler too
+extern std::atomic<int> g_regex_groups;                      // krep_gpu_set_regex_groups: a search asks the groups compiler too, fifth
+extern std::atomic<uint64_t> g_rl_general;                   // krep_gpu_debug_regex_general_walks: launches of the line walk's general step
+extern std::atomic<int> g_rl_force_general;                  // krep_gpu_debug_force_regex_general: loops programs through the general step
 extern std::atomic<int> g_regex_loops_windows;               // krep_gpu_set_regex_loops_windows: a loops search is scanned in windows
 extern std::atomic<int> g_batch_max_count;                   // krep_gpu_set_batch_max_count: the batch takes a finite max_count
 extern std::atomic<int> g_rl_force_road;                     // krep_gpu_debug_force_regex_loops_road: 0 auto, 1 sparse, 2 dense

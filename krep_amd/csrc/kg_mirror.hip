@@ -167,17 +167,18 @@ const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out)
 {
     struct Entry
     {
-        bool valid = false, cs = false, ww = false, mb = false, loops = false;
+        bool valid = false, cs = false, ww = false, mb = false, loops = false, groups = false;
         std::string key; // every pattern: its length, then its bytes
         RegexCompiled rc;
         const char *why = nullptr;
     };
     static thread_local Entry e;
     const bool loops = g_regex_loops.load(std::memory_order_relaxed) != 0; // (the switch is part of the key: krep_gpu_set_regex_loops)
+    const bool groups = g_regex_groups.load(std::memory_order_relaxed) != 0; // (and so is krep_gpu_set_regex_groups)
     if (!p || !out || !p->use_regex)
-        return out ? regex_compile_search(p, out, loops) : "NULL params";
+        return out ? regex_compile_search(p, out, loops, groups) : "NULL params";
     if (p->num_patterns > 1 && !(p->patterns && p->pattern_lens))
-        return regex_compile_search(p, out, loops);
+        return regex_compile_search(p, out, loops, groups);
     std::string key;
     const size_t np = regex_pattern_count(p);
     for (size_t k = 0; k < np; ++k)
@@ -186,16 +187,16 @@ const char *regex_compile_cached(const search_params_t *p, RegexCompiled *out)
         size_t n;
         regex_pattern_at(p, k, &pat, &n);
         if (!pat || n > 1024)
-            return regex_compile_search(p, out, loops);
+            return regex_compile_search(p, out, loops, groups);
         key.append((const char *)&n, sizeof n);
         key.append((const char *)pat, n);
     }
     const bool mb = MB_CUR_MAX > 1;
-    if (!(e.valid && e.cs == p->case_sensitive && e.ww == p->whole_word && e.mb == mb && e.loops == loops && e.key == key))
+    if (!(e.valid && e.cs == p->case_sensitive && e.ww == p->whole_word && e.mb == mb && e.loops == loops && e.groups == groups && e.key == key))
     {
         e.valid = false;
-        e.why = regex_compile_search(p, &e.rc, loops);
-        e.cs = p->case_sensitive; e.ww = p->whole_word; e.mb = mb; e.loops = loops;
+        e.why = regex_compile_search(p, &e.rc, loops, groups);
+        e.cs = p->case_sensitive; e.ww = p->whole_word; e.mb = mb; e.loops = loops; e.groups = groups;
         e.key.swap(key);
         e.valid = true;
     }

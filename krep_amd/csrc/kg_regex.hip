@@ -279,7 +279,23 @@ RegexProg *regex_prog_create(const search_params_t &sp)
         return nullptr;
     }
     u32 table[256];
-    if (rc.is_loops)
+    if (rc.is_groups)
+    { // a position automaton (kg_regex_loops.hip, the general step): one bit per position, the follow relation cut into chain, self and
+      // jump pairs; everything around the walk reads it as a loops program
+        rx->is_loops = rx->general = true;
+        rx->loops = rc.loops;
+        for (int b = 0; b < 256; ++b)
+        {
+            u32 m = 0;
+            for (u32 i = 0; i < rc.groups.n_pos; ++i)
+                m |= ((rc.groups.classes[i][b >> 3] >> (b & 7)) & 1u) << i;
+            table[b] = m;
+        }
+        rx->init = rc.groups.first;
+        rx->fin = rc.groups.last;
+        rx->n_jumps = regex_groups_jumps(rc.groups, &rx->chain, &rx->plus, rx->jump_src, rx->jump_dst, kRegexGroupsMaxJumps);
+    }
+    else if (rc.is_loops)
     { // places that may repeat (kg_regex_loops.hip): the alternation's layout without anchor places — ^ and $ are the line walk's own —
       // and `plus`, the bits of the places that repeat
         rx->is_loops = true;
@@ -290,6 +306,13 @@ RegexProg *regex_prog_create(const search_params_t &sp)
         {
             rx->plus |= (u32)rc.loops.repeat[i] << o;
             o += rc.loops.alt.branch[i].L;
+        }
+        // test hook (krep_gpu_debug_force_regex_general): the same program through the general step — a place hands over along CHAIN
+        // (every place but a branch's last), a repeating place is in SELF, no jump pairs
+        if (g_rl_force_general.load() && g_regex_loops.load(std::memory_order_relaxed) && g_regex_groups.load(std::memory_order_relaxed))
+        {
+            rx->general = true;
+            rx->chain = (o >= 32u ? ~0u : (1u << o) - 1u) & ~rx->fin;
         }
     }
     else if (rc.is_alt)

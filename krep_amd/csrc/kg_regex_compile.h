@@ -13,6 +13,9 @@
 //     every top-level branch, the same pair on all of them;
 //   krep_gpu_regex_compile_loops: the expanding compiler's walk with *, + and {n,} behind an atom taken too: a place of a sequence may
 //     REPEAT (C+).  It also picks the filter, the fixed-length factors the older kernels find the candidate lines with;
+//   krep_gpu_regex_compile_groups: a recursive parser of its own for repeated and nested groups; it does not expand but builds the
+//     position (Glushkov) automaton of the expression, cuts its follow relation into what the line walk steps (regex_groups_jumps)
+//     and derives a filter from the positions every match passes;
 //   regex_compile_search: those that take a search, in the order every search asks them, and the reason it reports.
 // Each compiler reports the first fault IT meets, and they meet faults in different orders (the tokeniser probes atoms only after
 // the whole pattern is cut, the expanding compiler as it goes, the alternation compiler walks a branch's parentheses before it
@@ -22,6 +25,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <vector>
 
 #include "../../include/krep_gpu.h"
 
@@ -407,6 +412,9 @@ inline bool regex_has_alt_syntax(const search_params_t *p)
 constexpr const char *kRegexAltEmptyBranch = "regex alternation: an empty branch (a|, |a, (), a||b) matches the empty string: kept on krep's regex_search";
 constexpr const char *kRegexAltUnbalanced = "regex alternation: unbalanced parentheses: kept on krep's regex_search";
 constexpr const char *kRegexAltNested = "regex alternation: nested parentheses: kept on krep's regex_search";
+constexpr const char *kRegexAltGroupNotBranch = "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general automaton: kept on "
+                                                "krep's regex_search";
+constexpr const char *kRegexAltGroupHoldsAlt = "regex alternation: a group that holds an alternation ((a|b)) is not one class sequence: kept on krep's regex_search";
 constexpr const char *kRegexAltMixedAnchors = "regex alternation: ^ or $ in a branch (anchors inside an alternation): kept on krep's regex_search";
 constexpr const char *kRegexAltBranchTooLong = "regex alternation: a branch of more than 16 byte classes: kept on krep's regex_search";
 constexpr const char *kRegexAltTooManyBranches = "regex alternation: more than 8 branches: kept on krep's regex_search";
@@ -423,8 +431,7 @@ inline const char *regex_alt_branch(const uint8_t *pat, size_t n, size_t bs, siz
     {
         const uint8_t c = pat[i];
         if ((closed && c != ')') || (c == '(' && !open && i != bs))
-            return "regex alternation: a group that is not a whole branch ((ab)c, (ab){2}, x(a|b)y) is a general automaton: kept on "
-                   "krep's regex_search";
+            return kRegexAltGroupNotBranch;
         size_t len = 1;
         if (c == '(')
         {
@@ -449,8 +456,7 @@ inline const char *regex_alt_branch(const uint8_t *pat, size_t n, size_t bs, siz
         i += len;
     }
     if (open)
-        return i < n ? "regex alternation: a group that holds an alternation ((a|b)) is not one class sequence: kept on krep's regex_search"
-                     : kRegexAltUnbalanced;
+        return i < n ? kRegexAltGroupHoldsAlt : kRegexAltUnbalanced;
     *lo = closed ? inner : bs;
     *hi = closed ? i - 1 : i;
     *end = i;
@@ -901,19 +907,504 @@ inline const char *regex_compile_loops(const search_params_t *p, krep_gpu_regex_
     return nullptr;
 }
 
+// ---- krep_gpu_regex_compile_groups: repeated and nested groups, held unexpanded as a position (Glushkov) automaton -------------------
+// The expression is parsed into a small tree (counted quantifiers copy their operand by parsing it again: X{2,} is X X+, X{1,3} is
+// X X? X?), the atom occurrences of the tree are the POSITIONS, numbered left to right, and first / last / follow come from the
+// usual recursion over the tree.  Nothing is multiplied out, so [0-9]{1,3}\.[0-9]{1,3}\.[0-9]{1,3}\.[0-9]{1,3} is 15 positions.
+constexpr uint32_t kRegexGroupsMaxPos = 32, kRegexGroupsMaxDepth = 8, kRegexGroupsMaxJumps = 12;
+constexpr const char *kRegexGroupsOlder = "regex groups: an older compiler takes the expression (krep_gpu_regex_compile_anchored, _alt, _ext, _loops): it "
+                                          "stays theirs";
+constexpr const char *kRegexGroupsNewline = "regex groups: a byte class of the expression holds '\\n', so a match can cross a line end and the lines of the text "
+                                            "are no longer independent: kept on krep's regex_search";
+constexpr const char *kRegexGroupsNullable = "regex groups: the expression matches the empty string ((ab)*, (a|b*)+, a?(b)*): kept on krep's regex_search";
+constexpr const char *kRegexGroupsEmptyAlt = "regex groups: an empty alternative or an empty group (a|, |a, (), (a|), a||b) matches the empty string: kept on "
+                                             "krep's regex_search";
+constexpr const char *kRegexGroupsQuantQuant = "regex groups: a quantifier behind a quantifier ((ab)+?, a{2}{3}, (a)*+): kept on krep's regex_search";
+constexpr const char *kRegexGroupsQuantNothing = "regex groups: a quantifier that is not behind an atom or a group";
+constexpr const char *kRegexGroupsZero = "regex groups: {0} and {0,0} repeat their operand zero times: kept on krep's regex_search";
+constexpr const char *kRegexGroupsAnchor = "regex groups: ^ that is not the first or $ that is not the last byte of a top-level branch ((^a)+, a(b$), a^b) "
+                                           "anchors inside the expression: kept on krep's regex_search";
+constexpr const char *kRegexGroupsMixedAnchors = "regex groups: the top-level branches do not all carry the same ^ and $: kept on krep's regex_search";
+constexpr const char *kRegexGroupsTooManyPos = "regex groups: more than 32 positions (atom occurrences after {n,m} has copied its operand): kept on krep's "
+                                               "regex_search";
+constexpr const char *kRegexGroupsTooDeep = "regex groups: parentheses nested deeper than 8: kept on krep's regex_search";
+constexpr const char *kRegexGroupsTooManyJumps = "regex groups: the follow relation needs more than 12 jump pairs beside its chain and self edges: kept on krep's "
+                                                 "regex_search";
+constexpr const char *kRegexGroupsNoFilter = "regex groups: no set of at most 8 fixed-length factors, 32 classes in all, lies on every match: kept on krep's "
+                                             "regex_search";
+
+struct RegexGNode
+{
+    enum Kind : uint8_t { kAtom, kCat, kAlt, kPlus, kStar, kOpt } kind;
+    int a, b; // kAtom: a = the position; kCat / kAlt: both children; the quantifiers: a = the operand
+};
+struct RegexGParser
+{
+    const uint8_t *pat = nullptr;
+    size_t n = 0, i = 0;
+    bool case_sensitive = true;
+    krep_gpu_regex_groups_t *out = nullptr;
+    std::vector<RegexGNode> nodes;
+    int add(RegexGNode::Kind k, int a, int b = -1)
+    {
+        nodes.push_back(RegexGNode{k, a, b});
+        return (int)nodes.size() - 1;
+    }
+};
+inline const char *regex_g_alt(RegexGParser &c, uint32_t depth, int *node);
+// an atom or a group at the cursor, without its quantifier
+inline const char *regex_g_operand(RegexGParser &c, uint32_t depth, int *node)
+{
+    const uint8_t ch = c.pat[c.i];
+    if (ch == '(')
+    {
+        if (depth >= kRegexGroupsMaxDepth)
+            return kRegexGroupsTooDeep;
+        ++c.i;
+        if (const char *why = regex_g_alt(c, depth + 1, node))
+            return why;
+        if (c.i >= c.n || c.pat[c.i] != ')')
+            return kRegexAltUnbalanced;
+        ++c.i;
+        return nullptr;
+    }
+    if (ch == '^' || ch == '$')
+        return kRegexGroupsAnchor;
+    size_t len;
+    if (const char *why = regex_atom(c.pat, c.n, c.i, &len))
+        return why;
+    if (c.out->n_pos >= kRegexGroupsMaxPos)
+        return kRegexGroupsTooManyPos;
+    uint8_t *cls = c.out->classes[c.out->n_pos];
+    if (!regex_probe_atom(c.pat + c.i, len, c.case_sensitive, cls))
+        return kRegexAtomRefused;
+    if (regex_class_holds_nl(cls))
+        return kRegexGroupsNewline;
+    *node = c.add(RegexGNode::kAtom, (int)c.out->n_pos++);
+    c.i += len;
+    return nullptr;
+}
+// item = operand quant?
+inline const char *regex_g_item(RegexGParser &c, uint32_t depth, int *node)
+{
+    const size_t start = c.i;
+    if (const char *why = regex_g_operand(c, depth, node))
+        return why;
+    if (c.i >= c.n || !regex_is_quant(c.pat[c.i]))
+        return nullptr;
+    uint32_t lo = 0, hi = 1;
+    bool unbounded = false;
+    if (c.pat[c.i] == '*' || c.pat[c.i] == '+')
+    {
+        lo = c.pat[c.i] == '+' ? 1u : 0u;
+        unbounded = true;
+        ++c.i;
+    }
+    else if (c.pat[c.i] == '?')
+        ++c.i;
+    else
+    {
+        size_t k = c.i + 1;
+        if (!regex_count(c.pat, c.n, &k, &lo))
+            return kRegexMalformed;
+        hi = lo;
+        if (c.pat[k] == ',')
+        {
+            ++k;
+            if (k < c.n && c.pat[k] == '}')
+                unbounded = true;
+            else if (!regex_count(c.pat, c.n, &k, &hi))
+                return kRegexMalformed;
+        }
+        if (c.pat[k] != '}' || (!unbounded && lo > hi) || lo > 1000 || hi > 1000)
+            return kRegexMalformed;
+        if (!unbounded && hi == 0)
+            return kRegexGroupsZero;
+        c.i = k + 1;
+    }
+    if (c.i < c.n && regex_is_quant(c.pat[c.i]))
+        return kRegexGroupsQuantQuant;
+    const size_t behind = c.i;
+    // X{lo,hi}: lo copies in a row, then hi - lo optional ones; X{lo,}: lo - 1 copies and X+ (lo == 0: X*).  *node is the first copy;
+    // every further one is the operand parsed again, which gives it positions of its own (the 33rd position ends a large count)
+    const uint32_t plain = unbounded ? (lo ? lo - 1 : 0) : lo, opt = unbounded ? 0 : hi - lo;
+    int acc = -1, copy = *node;
+    bool have = true; // `copy` is a copy that no place of the result uses yet
+    auto next_copy = [&]() -> const char * {
+        if (have)
+        {
+            have = false;
+            return nullptr;
+        }
+        c.i = start;
+        return regex_g_operand(c, depth, &copy);
+    };
+    auto put = [&](int nd) { acc = acc < 0 ? nd : c.add(RegexGNode::kCat, acc, nd); };
+    for (uint32_t k = 0; k < plain; ++k)
+    {
+        if (const char *why = next_copy())
+            return why;
+        put(copy);
+    }
+    if (unbounded)
+    {
+        if (const char *why = next_copy())
+            return why;
+        put(c.add(lo ? RegexGNode::kPlus : RegexGNode::kStar, copy));
+    }
+    for (uint32_t k = 0; k < opt; ++k)
+    {
+        if (const char *why = next_copy())
+            return why;
+        put(c.add(RegexGNode::kOpt, copy));
+    }
+    c.i = behind;
+    *node = acc;
+    return nullptr;
+}
+// seq = item+, up to a '|', a ')' or the end; top: a '$' in front of one of those ends the branch and is the line anchor
+inline const char *regex_g_seq(RegexGParser &c, uint32_t depth, bool top, int *node, int *eol)
+{
+    int acc = -1;
+    while (c.i < c.n && c.pat[c.i] != '|' && c.pat[c.i] != ')')
+    {
+        if (top && c.pat[c.i] == '$' && (c.i + 1 == c.n || c.pat[c.i + 1] == '|'))
+        {
+            *eol = 1;
+            ++c.i;
+            break;
+        }
+        if (regex_is_quant(c.pat[c.i]))
+            return kRegexGroupsQuantNothing;
+        int item;
+        if (const char *why = regex_g_item(c, depth, &item))
+            return why;
+        acc = acc < 0 ? item : c.add(RegexGNode::kCat, acc, item);
+    }
+    if (acc < 0)
+        return kRegexGroupsEmptyAlt;
+    *node = acc;
+    return nullptr;
+}
+// alt = seq ('|' seq)*; depth 0 is the top level of a pattern, where every branch may stand between ^ and $: anchors[0] / [1] are
+// -1 before the first branch of the search and then what every branch must carry
+struct RegexGAnchors { int bol = -1, eol = -1; };
+inline const char *regex_g_alt_top(RegexGParser &c, RegexGAnchors &an, int *node)
+{
+    int acc = -1;
+    for (;;)
+    {
+        int bol = 0, eol = 0, seq;
+        if (c.i < c.n && c.pat[c.i] == '^')
+        {
+            bol = 1;
+            ++c.i;
+        }
+        if (const char *why = regex_g_seq(c, 0, true, &seq, &eol))
+            return why;
+        if (an.bol < 0)
+        {
+            an.bol = bol;
+            an.eol = eol;
+        }
+        else if (an.bol != bol || an.eol != eol)
+            return kRegexGroupsMixedAnchors;
+        acc = acc < 0 ? seq : c.add(RegexGNode::kAlt, acc, seq);
+        if (c.i >= c.n)
+            break;
+        if (c.pat[c.i] == ')')
+            return kRegexAltUnbalanced;
+        ++c.i; // the '|'
+    }
+    *node = acc;
+    return nullptr;
+}
+inline const char *regex_g_alt(RegexGParser &c, uint32_t depth, int *node)
+{
+    int acc = -1;
+    for (;;)
+    {
+        int seq, eol = 0;
+        if (const char *why = regex_g_seq(c, depth, false, &seq, &eol))
+            return why;
+        acc = acc < 0 ? seq : c.add(RegexGNode::kAlt, acc, seq);
+        if (c.i >= c.n)
+            return kRegexAltUnbalanced;
+        if (c.pat[c.i] == ')')
+            break;
+        ++c.i; // the '|'
+    }
+    *node = acc;
+    return nullptr;
+}
+// nullable / first / last of a node; the follow edges of everything below it go into out->follow
+struct RegexGSets { bool nullable; uint32_t first, last; };
+inline RegexGSets regex_g_sets(const RegexGParser &c, int nd, krep_gpu_regex_groups_t *out)
+{
+    const RegexGNode &x = c.nodes[(size_t)nd];
+    auto link = [&](uint32_t from, uint32_t to) {
+        for (uint32_t i = 0; i < kRegexGroupsMaxPos; ++i)
+            if ((from >> i) & 1u)
+                out->follow[i] |= to;
+    };
+    if (x.kind == RegexGNode::kAtom)
+        return RegexGSets{false, 1u << x.a, 1u << x.a};
+    const RegexGSets A = regex_g_sets(c, x.a, out);
+    if (x.kind == RegexGNode::kCat)
+    {
+        const RegexGSets B = regex_g_sets(c, x.b, out);
+        link(A.last, B.first);
+        return RegexGSets{A.nullable && B.nullable, A.first | (A.nullable ? B.first : 0u), B.last | (B.nullable ? A.last : 0u)};
+    }
+    if (x.kind == RegexGNode::kAlt)
+    {
+        const RegexGSets B = regex_g_sets(c, x.b, out);
+        return RegexGSets{A.nullable || B.nullable, A.first | B.first, A.last | B.last};
+    }
+    if (x.kind != RegexGNode::kOpt)
+        link(A.last, A.first);
+    return RegexGSets{A.nullable || x.kind != RegexGNode::kPlus, A.first, A.last};
+}
+
+// The follow relation as the line walk holds it (kg_regex_loops.hip): follow(S) = ((S & chain) << 1) | (S & self) | the dst of every
+// pair whose src meets S.  chain: the positions i whose follow set holds i + 1 (never bit 31: nothing shifts out), self: those that
+// hold i; what is left of a follow set is a jump, and positions that share a remainder share a pair.  Returns the number of pairs,
+// which may pass `room`: then only the first `room` are written.
+inline uint32_t regex_groups_jumps(const krep_gpu_regex_groups_t &g, uint32_t *chain, uint32_t *self, uint32_t *src, uint32_t *dst, uint32_t room)
+{
+    uint32_t n = 0;
+    *chain = *self = 0;
+    for (uint32_t i = 0; i < g.n_pos; ++i)
+    {
+        uint32_t rest = g.follow[i];
+        if (i + 1 < kRegexGroupsMaxPos && ((rest >> (i + 1)) & 1u))
+        {
+            *chain |= 1u << i;
+            rest &= ~(1u << (i + 1));
+        }
+        if ((rest >> i) & 1u)
+        {
+            *self |= 1u << i;
+            rest &= ~(1u << i);
+        }
+        if (!rest)
+            continue;
+        uint32_t k = 0;
+        while (k < n && k < room && dst[k] != rest)
+            ++k;
+        if (k < n && k < room)
+            src[k] |= 1u << i;
+        else
+        {
+            if (n < room)
+            {
+                src[n] = 1u << i;
+                dst[n] = rest;
+            }
+            ++n;
+        }
+    }
+    return n;
+}
+
+// The filter.  The FACTOR of a position: its class, lengthened along forced edges.  Forward: while no position of the frontier is in
+// `last` and everything that can follow the frontier has ONE class, that class is the next byte of every match that passes the
+// frontier (a single follow is the plain case; the three digits in front of a '.' of the IP expression are the other).  Backward
+// the same with `first` and the predecessors.  A set of positions that every match passes (an atom: itself; a concatenation: the best
+// of its children that are not nullable; an alternation: the union; X+: that of X; X?, X*: none) gives a filter: its factors.
+struct RegexGFactor { uint32_t L; uint8_t classes[kRegexMaxL][32]; double weight; };
+inline void regex_g_factor(const krep_gpu_regex_groups_t &g, uint32_t p, uint32_t cap, RegexGFactor *f)
+{
+    uint32_t pred[kRegexGroupsMaxPos] = {0};
+    for (uint32_t i = 0; i < g.n_pos; ++i)
+        for (uint32_t j = 0; j < g.n_pos; ++j)
+            if ((g.follow[i] >> j) & 1u)
+                pred[j] |= 1u << i;
+    // one class for all of `set`: its lowest position, or -1
+    auto one_class = [&](uint32_t set) -> int {
+        if (!set)
+            return -1;
+        const int lead = __builtin_ctz(set);
+        for (uint32_t i = 0; i < g.n_pos; ++i)
+            if (((set >> i) & 1u) && memcmp(g.classes[i], g.classes[lead], 32) != 0)
+                return -1;
+        return lead;
+    };
+    auto around = [&](uint32_t set, const uint32_t *rel) {
+        uint32_t r = 0;
+        for (uint32_t i = 0; i < g.n_pos; ++i)
+            if ((set >> i) & 1u)
+                r |= rel[i];
+        return r;
+    };
+    int fwd[kRegexMaxL], bwd[kRegexMaxL];
+    uint32_t nf = 0, nb = 0;
+    for (uint32_t F = 1u << p; 1 + nf < cap && !(F & g.last);)
+    {
+        F = around(F, g.follow);
+        const int cl = one_class(F);
+        if (cl < 0)
+            break;
+        fwd[nf++] = cl;
+    }
+    for (uint32_t B = 1u << p; 1 + nf + nb < cap && !(B & g.first);)
+    {
+        B = around(B, pred);
+        const int cl = one_class(B);
+        if (cl < 0)
+            break;
+        bwd[nb++] = cl;
+    }
+    f->L = 0;
+    f->weight = 1.0;
+    auto put = [&](int pos) {
+        memcpy(f->classes[f->L++], g.classes[pos], 32);
+        f->weight *= (double)regex_class_size(g.classes[pos]) / 256.0;
+    };
+    for (uint32_t k = nb; k-- > 0;)
+        put(bwd[k]);
+    put((int)p);
+    for (uint32_t k = 0; k < nf; ++k)
+        put(fwd[k]);
+}
+// a set of positions every match passes, as a filter: ok (at most 8 distinct factors, 32 classes in all), its weight, its shortest factor
+struct RegexGReq { bool ok; uint32_t set; double weight; uint32_t shortest; };
+inline RegexGReq regex_g_req_of(uint32_t set, const RegexGFactor *fac, krep_gpu_regex_alt_t *filter = nullptr)
+{
+    krep_gpu_regex_alt_t tmp;
+    krep_gpu_regex_alt_t &alt = filter ? *filter : tmp;
+    memset(&alt, 0, sizeof alt);
+    RegexGReq r{set != 0, set, 0.0, kRegexMaxL};
+    uint32_t total = 0;
+    for (uint32_t p = 0; p < kRegexGroupsMaxPos && r.ok; ++p)
+    {
+        if (!((set >> p) & 1u))
+            continue;
+        krep_gpu_regex_info_t q{};
+        q.L = fac[p].L;
+        memcpy(q.classes, fac[p].classes, (size_t)q.L * 32);
+        const uint32_t before = alt.n_branches;
+        r.ok = regex_branch_add(alt.branch, &alt.n_branches, q);
+        if (alt.n_branches != before)
+        {
+            r.weight += fac[p].weight;
+            total += q.L;
+            r.shortest = q.L < r.shortest ? q.L : r.shortest;
+        }
+    }
+    r.ok = r.ok && total <= kRegexMaxTotalL;
+    return r;
+}
+inline RegexGReq regex_g_req(const RegexGParser &c, int nd, const RegexGFactor *fac)
+{
+    const RegexGNode &x = c.nodes[(size_t)nd];
+    const RegexGReq none{false, 0, 0.0, 0};
+    switch (x.kind)
+    {
+    case RegexGNode::kAtom: return regex_g_req_of(1u << x.a, fac);
+    case RegexGNode::kPlus: return regex_g_req(c, x.a, fac);
+    case RegexGNode::kStar:
+    case RegexGNode::kOpt: return none;
+    case RegexGNode::kAlt:
+    {
+        const RegexGReq A = regex_g_req(c, x.a, fac), B = regex_g_req(c, x.b, fac);
+        return A.ok && B.ok ? regex_g_req_of(A.set | B.set, fac) : none;
+    }
+    default:
+    { // a concatenation: the smaller weight; on a tie the one whose shortest factor is longer, then the left one
+        const RegexGReq A = regex_g_req(c, x.a, fac), B = regex_g_req(c, x.b, fac);
+        if (!A.ok || !B.ok)
+            return A.ok ? A : B;
+        return (B.weight < A.weight || (B.weight == A.weight && B.shortest > A.shortest)) ? B : A;
+    }
+    }
+}
+
+inline const char *regex_compile_groups_parse(const search_params_t *p, krep_gpu_regex_groups_t *out)
+{
+    if (const char *why = regex_check_search(p, true))
+        return why;
+    RegexGParser c;
+    c.case_sensitive = p->case_sensitive;
+    c.out = out;
+    RegexGAnchors an;
+    int root = -1;
+    const size_t n_pat = regex_pattern_count(p);
+    for (size_t k = 0; k < n_pat; ++k)
+    {
+        regex_pattern_at(p, k, &c.pat, &c.n);
+        c.i = 0;
+        if (const char *why = regex_check_pattern(c.pat, c.n))
+            return why;
+        int nd;
+        if (const char *why = regex_g_alt_top(c, an, &nd))
+            return why;
+        root = root < 0 ? nd : c.add(RegexGNode::kAlt, root, nd);
+    }
+    const RegexGSets S = regex_g_sets(c, root, out);
+    if (S.nullable)
+        return kRegexGroupsNullable;
+    out->first = S.first;
+    out->last = S.last;
+    out->bol = an.bol > 0;
+    out->eol = an.eol > 0;
+    {   // the older compilers keep what is theirs
+        krep_gpu_regex_anchored_t a;
+        krep_gpu_regex_alt_t b;
+        krep_gpu_regex_ext_t e;
+        krep_gpu_regex_loops_t l;
+        if (!regex_compile_anchored(p, &a) || !regex_compile_alt(p, &b) || !regex_compile_ext(p, &e) || !regex_compile_loops(p, &l))
+            return kRegexGroupsOlder;
+    }
+    uint32_t chain, self, src[kRegexGroupsMaxJumps], dst[kRegexGroupsMaxJumps];
+    if (regex_groups_jumps(*out, &chain, &self, src, dst, kRegexGroupsMaxJumps) > kRegexGroupsMaxJumps)
+        return kRegexGroupsTooManyJumps;
+    // factors of up to 16 classes first; 8 such factors pass the 32 classes of an alternation, so shorter ones are tried behind them
+    for (uint32_t cap = kRegexMaxL; cap >= 4; cap /= 2)
+    {
+        RegexGFactor fac[kRegexGroupsMaxPos];
+        for (uint32_t q = 0; q < out->n_pos; ++q)
+            regex_g_factor(*out, q, cap, &fac[q]);
+        const RegexGReq R = regex_g_req(c, root, fac);
+        if (!R.ok)
+            continue;
+        (void)regex_g_req_of(R.set, fac, &out->filter);
+        for (uint32_t b = 0; b < out->filter.n_branches; ++b)
+            regex_seq_finish(&out->filter.branch[b], false, false);
+        regex_alt_finish(&out->filter, false, false);
+        return nullptr;
+    }
+    return kRegexGroupsNoFilter;
+}
+// krep_gpu_regex_compile_groups: NULL and *out filled, or the refusal and *out zeroed
+inline const char *regex_compile_groups(const search_params_t *p, krep_gpu_regex_groups_t *out)
+{
+    if (!p || !out)
+        return "NULL params";
+    memset(out, 0, sizeof *out);
+    const char *why = regex_compile_groups_parse(p, out);
+    if (why)
+        memset(out, 0, sizeof *out);
+    return why;
+}
+
 // ---- the compilers in the order every search asks them -------------------------------------------------------------------------
 // The anchored compiler is asked first; only what it refuses goes to the alternation compiler, and what both refuse to the expanding
 // compiler, whose result is an alternation too, between the line anchors alt_bol / alt_eol (is_alt: one of the two took it).  So a
 // search an earlier compiler takes runs the kernel it always ran.  What all three refuse goes to the loops compiler when the caller
-// says so (krep_gpu_set_regex_loops): is_loops, the program in `loops`.
+// says so (krep_gpu_set_regex_loops): is_loops, the program in `loops`.  What is still refused goes to the groups compiler when the
+// caller says so (krep_gpu_set_regex_groups): is_loops AND is_groups, the automaton in `groups`; of `loops` only bol, eol and filter
+// are set then — what everything around the line walk reads of a loops program.
 struct RegexCompiled
 {
     bool is_alt = false;
     krep_gpu_regex_anchored_t seq{}; // !is_alt
     krep_gpu_regex_alt_t alt{};      // is_alt
     int alt_bol = 0, alt_eol = 0;    // is_alt: ^ in front of / $ behind every branch (the expanding compiler only)
-    bool is_loops = false;           // the loops compiler took it (then !is_alt, and seq holds nothing)
+    bool is_loops = false;           // the loops or the groups compiler took it (then !is_alt, and seq holds nothing)
     krep_gpu_regex_loops_t loops{};
+    bool is_groups = false;          // the groups compiler took it
+    krep_gpu_regex_groups_t groups{};
 };
 // a refusal of the two older compilers that is a limit of theirs: one the expanding compiler's own limits do not replace
 inline bool regex_older_limit(const char *why)
@@ -921,14 +1412,18 @@ inline bool regex_older_limit(const char *why)
     return why == kRegexSeqTooManyClasses || why == kRegexSeqTooManyPlaces || why == kRegexAltBranchTooLong || why == kRegexAltTooManyBranches ||
            why == kRegexAltTooWide;
 }
+// a refusal that says a group, nesting or what an expansion multiplies out to: the groups compiler's own reason replaces it
+inline bool regex_group_reason(const char *why)
+{
+    return why == kRegexLoopsGroup || why == kRegexAltNested || why == kRegexAltGroupNotBranch || why == kRegexAltGroupHoldsAlt ||
+           why == kRegexExtTooMany || why == kRegexExtTooLong || why == kRegexExtTooWide;
+}
 // NULL: taken.  Else the reason of a search all three refuse: what it was before the expanding compiler — the alternation compiler's
 // when the search says an alternation, else the anchored compiler's — unless only the expanding compiler's own limits are in the way.
-// loops: the loops compiler is asked last.  Its own reason replaces the earlier one only where that one says "without a bound".
-inline const char *regex_compile_search(const search_params_t *p, RegexCompiled *out, bool loops = false)
+// loops: the loops compiler is asked fourth.  Its own reason replaces the earlier one only where that one says "without a bound".
+// groups: the groups compiler is asked fifth.  Its own reason replaces the earlier one only where that one is a group reason.
+inline const char *regex_compile_search_older(const search_params_t *p, RegexCompiled *out, bool loops)
 {
-    out->is_alt = false;
-    out->is_loops = false;
-    out->alt_bol = out->alt_eol = 0;
     const char *why = regex_compile_anchored(p, &out->seq);
     if (!why)
         return nullptr;
@@ -961,6 +1456,27 @@ inline const char *regex_compile_search(const search_params_t *p, RegexCompiled 
         return nullptr;
     }
     return today == kRegexStarPlus || today == kRegexOpenCount ? why_loops : today;
+}
+inline const char *regex_compile_search(const search_params_t *p, RegexCompiled *out, bool loops = false, bool groups = false)
+{
+    out->is_alt = false;
+    out->is_loops = false;
+    out->is_groups = false;
+    out->alt_bol = out->alt_eol = 0;
+    const char *today = regex_compile_search_older(p, out, loops);
+    if (!today || !groups || !p || !p->use_regex)
+        return today;
+    const char *why_groups = regex_compile_groups(p, &out->groups);
+    if (!why_groups)
+    {
+        out->is_loops = out->is_groups = true;
+        memset(&out->loops, 0, sizeof out->loops);
+        out->loops.bol = out->groups.bol;
+        out->loops.eol = out->groups.eol;
+        out->loops.filter = out->groups.filter;
+        return nullptr;
+    }
+    return regex_group_reason(today) ? why_groups : today;
 }
 
 } // namespace kg

@@ -37,6 +37,12 @@ struct RegexProg
     krep_gpu_regex_loops_t loops{};
     u32 plus = 0;
     struct RxLoopsWork *work = nullptr;
+    // a position automaton (krep_gpu_regex_compile_groups took the search; is_loops is set too, and of `loops` only bol, eol and filter):
+    // the line walk takes its general step.  T[b] bit i set iff b is in the class of position i; init = first, fin = last, plus = SELF,
+    // chain and the jump pairs as regex_groups_jumps() (kg_regex_compile.h) cuts the follow relation
+    bool general = false;
+    u32 chain = 0, n_jumps = 0;
+    u32 jump_src[kRegexGroupsMaxJumps] = {0}, jump_dst[kRegexGroupsMaxJumps] = {0};
 };
 void rx_loops_work_free(RxLoopsWork *w); // kg_regex_loops.hip
 

@@ -38,6 +38,12 @@
 // On the sparse road the line the buffer's end cuts is looked at by the host as well: its filter occurrence may lie behind that end.
 // The whole-text scan is the case own_lo = 0, own_hi = text_len in a buffer that begins and ends the text; it runs the instantiations
 // without WIN, in which these are constants and the ownership tests fold away (rl_launch picks them).
+// The GENERAL step (rx_line_walk<..., GEN>; krep_gpu_regex_compile_groups took the search, or the test hook
+// krep_gpu_debug_force_regex_general sends a loops program through it): the state is a set of POSITIONS of the expression's Glushkov
+// automaton, one bit per atom occurrence, T[byte] has bit i set when byte is in position i's class, INIT is the first set, FIN the
+// last set, and a step is S = follow(S) & T[b] with follow(S) = ((S & CHAIN) << 1) | (S & SELF) | the targets of every jump pair whose
+// sources meet S (rl_follow; RlJumps rides in the kernel arguments: the 32 KiB of T leave no LDS at five workgroups per CU).
+// Everything else — the roads, the line loop, ownership, the passes, the 4096-byte rule — is the one copy described above.
 // Reads: no byte outside [0, text_len), one byte at a time at any alignment: the walk of a lane per line is not coalesced, which is
 // the price of the dense road.
 #include <hip/hip_runtime.h>
@@ -58,6 +64,13 @@ namespace kg {
 
 constexpr u32 kRlMaxLine = 4096; // bytes of the longest candidate line a lane walks
 
+// follow(S) of the general step beside SELF: the positions that hand over to their right neighbour, and n pairs (sources, targets) for
+// every other edge; the unused pairs are 0
+struct RlJumps
+{
+    u32 chain, n;
+    u32 src[kRegexGroupsMaxJumps], dst[kRegexGroupsMaxJumps];
+};
 struct RlArgs
 {
     const uint8_t *text;
@@ -76,10 +89,39 @@ struct RlArgs
     u32 flags;
     const u32 *table;
     RxOut o;   // unitinfo: the count of every candidate line; offsets: the index of its first record (kg_regex_dev.h)
+    // the general step (GEN, a position automaton: init = first, fin = last, plus = SELF): the rest of the follow relation.  Wave-uniform
+    // kernel arguments, not a table in LDS: the 32 KiB of T leave no LDS for a sixth array at five workgroups per CU.  Behind
+    // everything the old step reads, so that its instantiations load their arguments from the offsets they always had
+    RlJumps j;
 };
 
-// the longest match that starts at s in a line that ends at le: its end, 0 when there is none (a match is never empty)
-__device__ __forceinline__ u64 rl_attempt(const uint8_t *text, const u32 *T, u32 init, u32 fin, u32 plus, u64 s, u64 le, bool eol)
+// the positions that can stand behind one of S: chain never holds bit 31, so the shift loses nothing.  The pairs in groups of four,
+// each group behind a wave-uniform branch: an automaton of few jumps pays for four
+__device__ __forceinline__ u32 rl_follow(u32 S, u32 self, const RlJumps &j)
+{
+    u32 N = ((S & j.chain) << 1) | (S & self);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        N |= (S & j.src[k]) ? j.dst[k] : 0u;
+    if (j.n > 4u)
+    {
+#pragma unroll
+        for (int k = 4; k < 8; ++k)
+            N |= (S & j.src[k]) ? j.dst[k] : 0u;
+    }
+    if (j.n > 8u)
+    {
+#pragma unroll
+        for (int k = 8; k < (int)kRegexGroupsMaxJumps; ++k)
+            N |= (S & j.src[k]) ? j.dst[k] : 0u;
+    }
+    return N;
+}
+// the longest match that starts at s in a line that ends at le: its end, 0 when there is none (a match is never empty).  GEN: the
+// state is a set of positions of an automaton (init = first, fin = last, plus = SELF) and a step is rl_follow; else of places of
+// flat sequences, and a step is the shift
+template <bool GEN>
+__device__ __forceinline__ u64 rl_attempt(const uint8_t *text, const u32 *T, u32 init, u32 fin, u32 plus, const RlJumps &j, u64 s, u64 le, bool eol)
 {
     u32 S = T[(u32)text[s] << 5] & init;
     u64 best = 0;
@@ -92,7 +134,7 @@ __device__ __forceinline__ u64 rl_attempt(const uint8_t *text, const u32 *T, u32
                 best = p;
             if (p >= le)
                 break;
-            S = (((S << 1) & ~init) | (S & plus)) & T[(u32)text[p] << 5];
+            S = (GEN ? rl_follow(S, plus, j) : (((S << 1) & ~init) | (S & plus))) & T[(u32)text[p] << 5];
             if (!S)
                 break;
             ++p;
@@ -105,16 +147,18 @@ __device__ __forceinline__ u64 rl_attempt(const uint8_t *text, const u32 *T, u32
 // range and the two ends of the buffer are what RlArgs says — without it they are the constants of a scan of the whole text
 // ([0, text_len) in a buffer that begins and ends the text) and the compiler folds the ownership tests away: measured, the same tests
 // on run-time values moved rows of profiles/regex_loops_scan.txt by 3-7 % in both directions (profiles/regex_loops_windows.txt)
-template <bool LINES, bool EMIT, bool WIN>
+// GEN: the attempt steps a position automaton (rl_follow); the line loop is this one copy either way
+template <bool LINES, bool EMIT, bool WIN, bool GEN>
 __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
 {
     static_assert(!(LINES && EMIT), "-c writes no records");
     __shared__ u32 s_T[256 * 32];
     rx_fill_table(s_T, a.table);
     const u32 *T = s_T + (lane_id() & 31u);
+    const u64 text_len = a.text_len; // (a value of its own: min() takes references, and the address of a kernel argument is a stack slot)
     const bool bol = (a.flags & 1u) != 0u, eol = (a.flags & 2u) != 0u, eot_ends = (a.flags & 4u) != 0u;
     const bool begins = !WIN || (a.flags & 8u) != 0u, ends = !WIN || (a.flags & 16u) != 0u;
-    const u64 own_lo = WIN ? a.own_lo : 0, own_hi = WIN ? a.own_hi : a.text_len;
+    const u64 own_lo = WIN ? a.own_lo : 0, own_hi = WIN ? a.own_hi : text_len;
     const u64 n_threads = (u64)gridDim.x * kBlock;
     u64 mine = 0;                 // owned matches (LINES: lines that hold one) of this lane's lines
     unsigned long long bits = 0;  // LINES: kLnNl | kLnHead | kLnTail as far as this lane's lines say them
@@ -126,14 +170,14 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
         if (a.from_nl)
         {
             ls = line ? a.spans[2 * (line - 1)] + 1u : 0u;
-            le = line + 1 < a.n_lines ? a.spans[2 * line] : a.text_len;
+            le = line + 1 < a.n_lines ? a.spans[2 * line] : text_len;
         }
         else
         {
             ls = a.spans[2 * line];
             le = a.spans[2 * line + 1];
         }
-        le = min(le, a.text_len); // (whatever a span says, no byte outside the text is read)
+        le = min(le, text_len); // (whatever a span says, no byte outside the text is read)
         ls = min(ls, le);
         u32 cnt = 0;
         // a line that does not meet the owned range holds no owned start: not walked, not measured, count 0 and no bit
@@ -142,9 +186,9 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
             ;
         else if (le - ls > kRlMaxLine)
             too_long = true;
-        else if ((ls == 0 && !begins) || (le == a.text_len && !ends))
+        else if ((ls == 0 && !begins) || (le == text_len && !ends))
             cut_line = true; // the buffer does not show where the line really starts, or ends
-        else if (!eol || le < a.text_len || eot_ends)
+        else if (!eol || le < text_len || eot_ends)
         {
             u64 idx = EMIT ? a.o.offsets[line] : 0;
             const u64 stop = min(le, own_hi); // the walk ends with the owned starts
@@ -156,12 +200,12 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
                 s = stop;
             while (s < own_lo)
             {
-                const u64 best = rl_attempt(a.text, T, a.init, a.fin, a.plus, s, le, eol);
+                const u64 best = rl_attempt<GEN>(a.text, T, a.init, a.fin, a.plus, a.j, s, le, eol);
                 s = best ? best : s + 1;
             }
             while (s < stop)
             {
-                const u64 best = rl_attempt(a.text, T, a.init, a.fin, a.plus, s, le, eol);
+                const u64 best = rl_attempt<GEN>(a.text, T, a.init, a.fin, a.plus, a.j, s, le, eol);
                 if (best)
                 {
                     if (EMIT)
@@ -190,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
         {
             // the bits every other scan reports for its owned window (krep_gpu_combine_line_counts): a '\n' inside it — the one that
             // ends this line or the one in front of it —, a counted line that began at or before own_lo, one that ends behind own_hi
-            if (relevant && ((le < a.text_len && le < own_hi) || (ls > 0 && ls - 1 >= own_lo)))
+            if (relevant && ((le < text_len && le < own_hi) || (ls > 0 && ls - 1 >= own_lo)))
                 bits |= kLnNl;
             if (cnt)
                 bits |= (ls <= own_lo ? kLnHead : 0ull) | (le >= own_hi ? kLnTail : 0ull);
@@ -215,29 +259,31 @@ __global__ __launch_bounds__(kBlock) void rx_line_walk(const RlArgs a)
         atomicOr(&a.o.ctr->overflow_units, (too_long ? 1ull : 0ull) | (cut_line ? 2ull : 0ull));
 }
 
-static hipError_t rl_launch(const RlArgs &a, int mode, int num_cu, hipStream_t st)
+template <bool GEN> static hipError_t rl_launch(const RlArgs &a, int mode, int num_cu, hipStream_t st)
 {
     // one lane per line; 32 KiB of LDS each: five workgroups fit a CU
     const u64 blocks = (a.n_lines + kBlock - 1) / kBlock;
     u32 grid = (u32)std::max<u64>(1, std::min<u64>(blocks, (u64)num_cu * 5u));
     if (const int force = g_rx_force_grid.load(); force > 0) // test hook: a starved grid (krep_gpu_debug_force_regex_grid)
         grid = std::min<u32>(grid, (u32)force);
+    if (GEN)
+        g_rl_general.fetch_add(1, std::memory_order_relaxed); // (krep_gpu_debug_regex_general_walks)
     // (the scan of a whole text: the instantiations without WIN)
     const bool win = !(a.own_lo == 0 && a.own_hi == a.text_len && (a.flags & 24u) == 24u);
     if (mode == kRxLines)
     {
-        if (win) hipLaunchKernelGGL((rx_line_walk<true, false, true>), dim3(grid), dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((rx_line_walk<true, false, false>), dim3(grid), dim3(kBlock), 0, st, a);
+        if (win) hipLaunchKernelGGL((rx_line_walk<true, false, true, GEN>), dim3(grid), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((rx_line_walk<true, false, false, GEN>), dim3(grid), dim3(kBlock), 0, st, a);
     }
     else if (mode == kRxEmit)
     {
-        if (win) hipLaunchKernelGGL((rx_line_walk<false, true, true>), dim3(grid), dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((rx_line_walk<false, true, false>), dim3(grid), dim3(kBlock), 0, st, a);
+        if (win) hipLaunchKernelGGL((rx_line_walk<false, true, true, GEN>), dim3(grid), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((rx_line_walk<false, true, false, GEN>), dim3(grid), dim3(kBlock), 0, st, a);
     }
     else
     {
-        if (win) hipLaunchKernelGGL((rx_line_walk<false, false, true>), dim3(grid), dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((rx_line_walk<false, false, false>), dim3(grid), dim3(kBlock), 0, st, a);
+        if (win) hipLaunchKernelGGL((rx_line_walk<false, false, true, GEN>), dim3(grid), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((rx_line_walk<false, false, false, GEN>), dim3(grid), dim3(kBlock), 0, st, a);
     }
     return hipGetLastError();
 }
@@ -348,6 +394,14 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
     a.flags = (rx.loops.bol ? 1u : 0u) | (rx.loops.eol ? 2u : 0u) | (pl->sp.case_sensitive && ends ? 4u : 0u) | (begins ? 8u : 0u) |
               (ends ? 16u : 0u);
     a.table = rx.d_table;
+    if (rx.general)
+    {
+        a.j.chain = rx.chain;
+        a.j.n = rx.n_jumps;
+        memcpy(a.j.src, rx.jump_src, sizeof a.j.src);
+        memcpy(a.j.dst, rx.jump_dst, sizeof a.j.dst);
+    }
+    const auto launch = !rx.general ? rl_launch<false> : rl_launch<true>; // (the old step first: its kernels keep their place in the code object)
     a.o.ctr = pl->d_ctr;
     // stage 1 looks at the BUFFER, not at the owned range: a match that starts in front of own_hi may hold its filter factor behind it,
     // and the inner plans refuse windows of their own (a filter alternation that can overlap itself).  To them the buffer is a whole
@@ -448,7 +502,7 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
             a.o.offsets = (const u64 *)pl->post.d_offsets;
         }
         HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-        HIPCHK(rl_launch(a, lines ? kRxLines : kRxCount, pl->num_cu, st));
+        HIPCHK(launch(a, lines ? kRxLines : kRxCount, pl->num_cu, st));
         HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (pl->h_ctr->overflow_units & 1ull)
@@ -464,7 +518,7 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
                 return 2;
             a.o.positions = (u64 *)d_pos;
             a.o.pos_cap = want;
-            HIPCHK(rl_launch(a, kRxEmit, pl->num_cu, st));
+            HIPCHK(launch(a, kRxEmit, pl->num_cu, st));
             HIPCHK(hipStreamSynchronize(st));
         }
     }
@@ -490,6 +544,13 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
 }
 } // namespace kg
 
+extern "C" int krep_gpu_regex_compile_groups(const search_params_t *params, krep_gpu_regex_groups_t *out)
+{
+    krep_gpu_clear_error();
+    if (const char *why = kg::regex_compile_groups(params, out))
+        return kg::fail("%s", why);
+    return 0;
+}
 extern "C" int krep_gpu_regex_compile_loops(const search_params_t *params, krep_gpu_regex_loops_t *out)
 {
     krep_gpu_clear_error();

@@ -216,6 +216,17 @@ class Engine:
             L.krep_gpu_debug_force_regex_loops_road.argtypes = [C.c_int]
             L.krep_gpu_debug_regex_loops_roads.restype = None
             L.krep_gpu_debug_regex_loops_roads.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "krep_gpu_regex_compile_groups"):  # (likewise)
+            L.krep_gpu_regex_compile_groups.restype = C.c_int
+            L.krep_gpu_regex_compile_groups.argtypes = [C.POINTER(abi.SearchParams), C.POINTER(abi.RegexGroups)]
+            L.krep_gpu_set_regex_groups.restype = None
+            L.krep_gpu_set_regex_groups.argtypes = [C.c_int]
+            L.krep_gpu_get_regex_groups.restype = C.c_int
+            L.krep_gpu_get_regex_groups.argtypes = []
+            L.krep_gpu_debug_force_regex_general.restype = None
+            L.krep_gpu_debug_force_regex_general.argtypes = [C.c_int]
+            L.krep_gpu_debug_regex_general_walks.restype = C.c_uint64
+            L.krep_gpu_debug_regex_general_walks.argtypes = []
         if hasattr(L, "krep_gpu_set_regex_loops_windows"):  # (likewise)
             L.krep_gpu_set_regex_loops_windows.restype = None
             L.krep_gpu_set_regex_loops_windows.argtypes = [C.c_int]
@@ -450,6 +461,38 @@ class Engine:
         if self.lib.krep_gpu_regex_compile_loops(params.ref, C.byref(info)):
             raise KrepGpuError(self.last_error())
         return info
+
+    def regex_compile_groups(self, params: abi.Params) -> dict:
+        """krep_gpu_regex_compile_groups: repeated and nested groups ((ab)+, ((GET|POST) |HEAD )/api, [0-9]{1,3}\\.[0-9]{1,3}...) held
+        unexpanded as a position automaton.  Returned as Python values: n_pos; classes (a list of bytes objects, one per position);
+        first and last (sets of positions); follow (a list of sets); bol, eol; filter (a list of class sequences, each a list of bytes
+        objects: every match holds an occurrence of one of them as consecutive bytes); and raw, the abi.RegexGroups itself.  It always
+        works; a search asks it, fifth, only after set_regex_groups(True)."""
+        info = abi.RegexGroups()
+        if self.lib.krep_gpu_regex_compile_groups(params.ref, C.byref(info)):
+            raise KrepGpuError(self.last_error())
+        n = int(info.n_pos)
+        bits = lambda m: {i for i in range(32) if (int(m) >> i) & 1}  # noqa: E731
+        return {"n_pos": n, "classes": [info.class_bytes(i) for i in range(n)], "first": bits(info.first), "last": bits(info.last),
+                "follow": [bits(info.follow[i]) for i in range(n)], "bol": bool(info.bol), "eol": bool(info.eol),
+                "filter": [[br.class_bytes(j) for j in range(int(br.L))] for br in info.filter.branch[: int(info.filter.n_branches)]],
+                "raw": info}
+
+    def set_regex_groups(self, on: bool):
+        """krep_gpu_set_regex_groups: whether a search asks the groups compiler after the four older ones have refused (process-wide,
+        off by default, $KREP_GPU_REGEX_GROUPS=1 at load; independent of set_regex_loops)"""
+        self.lib.krep_gpu_set_regex_groups(1 if on else 0)
+
+    def get_regex_groups(self) -> bool:
+        return bool(self.lib.krep_gpu_get_regex_groups())
+
+    def force_regex_general(self, on: bool):
+        """test hook: with both switches on, a plan made while this is on walks a loops-compiler expression by the general step"""
+        self.lib.krep_gpu_debug_force_regex_general(1 if on else 0)
+
+    def regex_general_walks(self) -> int:
+        """launches of the line walk's general step since the process started"""
+        return int(self.lib.krep_gpu_debug_regex_general_walks())
 
     def set_regex_loops(self, on: bool):
         """krep_gpu_set_regex_loops: whether a search asks the loops compiler after the three older ones have refused (process-wide,
@@ -943,16 +986,18 @@ class Plan:
             info = eng.regex_compile_ext(self.params)
             return int(info.alt.Lmax) + int(bool(info.eol))
         except KrepGpuError:
-            if not eng.get_regex_loops():  # (no search asks the loops compiler: no plan exists either)
+            if not (eng.get_regex_loops() or eng.get_regex_groups()):  # (no search asks those compilers: no plan exists either)
                 raise
-            eng.regex_compile_loops(self.params)  # (raises the refusal when no compiler takes the search)
+            if not self.is_loops():
+                (eng.regex_compile_groups if eng.get_regex_groups() else eng.regex_compile_loops)(self.params)  # (raises the refusal)
             return 4096 + 1  # a match of a loops program lies inside one line, and no line of more than 4096 bytes is walked
 
     def is_loops(self) -> bool:
-        """whether the loops compiler took the plan's search (-E with *, + or {n,} behind an atom): the older compilers refuse it, the
-        switch is on and that compiler takes it"""
+        """whether the plan's search is walked line by line (kg_regex_loops.hip): the three older compilers refuse it, and the loops
+        compiler (-E with *, + or {n,} behind an atom) or the groups compiler (repeated and nested groups) takes it, each asked only
+        when its own switch is on"""
         s, eng = self.params.s, self.eng
-        if not s.use_regex or not eng.get_regex_loops():
+        if not s.use_regex or not (eng.get_regex_loops() or eng.get_regex_groups()):
             return False
         for older in (eng.regex_compile_anchored, eng.regex_compile_alt, eng.regex_compile_ext):
             try:
@@ -960,11 +1005,14 @@ class Plan:
                 return False
             except KrepGpuError:
                 pass
-        try:
-            eng.regex_compile_loops(self.params)
-            return True
-        except KrepGpuError:
-            return False
+        for newer, on in ((eng.regex_compile_loops, eng.get_regex_loops()), (eng.regex_compile_groups, eng.get_regex_groups())):
+            try:
+                if on:
+                    newer(self.params)
+                    return True
+            except KrepGpuError:
+                pass
+        return False
 
     def left_context(self, own_lo: int) -> int:
         """The bytes of the text the pieces drivers stage in front of what a window owns: one (the byte -w and ^ look at), for a

@@ -9,7 +9,11 @@ numbers: the switch krep_gpu_set_regex_loops stays off whatever they say.
 k-th share of it in a buffer that holds 4096 bytes more on each side, as the host executor stages its pieces; the time of a scan is the
 sum of the N hipEvent times, the count the sum of the windows' counts (under -c the lines that hold an owned start, not folded).
 --haystack: the first text only.
-  usage: python tools/regex_loops_bench.py [--windows N] [--haystack] [GiB = 8] [CPU MiB = 256] [output = profiles/regex_loops_scan.txt]"""
+--groups (with krep_gpu_set_regex_groups on): the rows of the groups compiler instead.  On the haystack `Sherlo+ck` and
+`[a-z]+ck` by the old step and, tagged "general", by the general step (krep_gpu_debug_force_regex_general), and `(Sherlock|Watson)+`; on
+the word text `([a-z]+ )+ck`; on a third text, the same haystack generator with `192.168.10.254` planted every 10 000 bytes instead of
+`Sherlock`, the IP expression.  The output goes to profiles/regex_groups_scan.txt unless one is named.
+  usage: python tools/regex_loops_bench.py [--windows N] [--haystack] [--groups] [GiB = 8] [CPU MiB = 256] [output = profiles/regex_loops_scan.txt]"""
 import locale
 import os
 import statistics
@@ -35,9 +39,12 @@ if "--windows" in sys.argv:
 haystack_only = "--haystack" in sys.argv
 if haystack_only:
     sys.argv.remove("--haystack")
+groups = "--groups" in sys.argv
+if groups:
+    sys.argv.remove("--groups")
 gib = float(sys.argv[1]) if len(sys.argv) > 1 else 8.0
 cpu_mib = int(sys.argv[2]) if len(sys.argv) > 2 else 256
-out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "regex_loops_scan.txt")
+out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "regex_groups_scan.txt" if groups else "regex_loops_scan.txt")
 n = int(gib * (1 << 30))
 SEED, PERIOD = 42, 10000
 WORDS = wordlist.pack(wordlist.word_list())
@@ -45,8 +52,18 @@ TEXTS = [("kind-2 haystack, `Sherlock` every 10 000 bytes", 2, SEED, b"Sherlock"
 PATTERNS = [(b"Sherlo+ck", "filter Sherlo: rare"), (b"Sherlock.*[a-z]", "filter Sherlock.: rare, the match runs to the line's end"),
             (b"[a-z]+ck", "filter [a-z]ck")]
 ROADS = [(0, "auto"), (1, "sparse"), (2, "dense")]
+BY_TEXT = [PATTERNS] * len(TEXTS)  # (pattern, what it shows[, True: through the general step]) per text
+if groups:
+    IP = rb"[0-9]{1,3}\.[0-9]{1,3}\.[0-9]{1,3}\.[0-9]{1,3}"
+    TEXTS.append(("kind-2 haystack, `192.168.10.254` every 10 000 bytes", 2, SEED, b"192.168.10.254", PERIOD))
+    BY_TEXT = [[(b"Sherlo+ck", "old step"), (b"Sherlo+ck", "general step", True), (b"[a-z]+ck", "old step"), (b"[a-z]+ck", "general step", True),
+                (b"(Sherlock|Watson)+", "filter Sherlock, Watson: 14 positions")],
+               [(b"([a-z]+ )+ck", "filter [a-z] ck: 4 positions")],
+               [(IP, "filter [0-9]\\.[0-9]: 15 positions")]]
 e = krep_amd.load()
 e.set_regex_loops(True)
+if groups:
+    e.set_regex_groups(True)
 if windows > 1:
     e.set_regex_loops_windows(True)
 CONTEXT = 4096  # bytes of the text a window's buffer holds on each side of what it owns (include/krep_gpu.h)
@@ -91,7 +108,7 @@ say("# same mode on the same buffer; road: forced, or auto with the road it took
 if windows > 1:
     say(f"# --windows {windows}: every regex scan is {windows} scans, window k owning the k-th share of the text with {CONTEXT} bytes of context on each")
     say("# side; the time is the sum of their hipEvent times, the count the sum of their counts (-c: not folded across the cuts)")
-for name, kind, seed, needle, period in TEXTS[:1] if haystack_only else TEXTS:
+for (name, kind, seed, needle, period), patterns in list(zip(TEXTS, BY_TEXT))[:1 if haystack_only else None]:
     e.generate(buf.data_ptr(), n, 0, kind, seed, needle, period)
     torch.cuda.synchronize()
     say(f"## {name} (seed {seed})")
@@ -102,12 +119,18 @@ for name, kind, seed, needle, period in TEXTS[:1] if haystack_only else TEXTS:
         yard[mode] = ms
         say(f"literal  {'Sherlock':<18} {mode:<8} {'-':<7} {ms:9.3f} ms {n / ms / 1e6:7.0f} GB/s  ratio 1.00  matches {out.total_matches}")
     plan.close()
-    for pat, what in PATTERNS:
+    for pat, what, *general in patterns:
         for mode in ("-c", "records"):
             kw = dict(count_lines=True) if mode == "-c" else dict()
             for road, road_name in ROADS:
                 e.force_regex_loops_road(road)
-                plan = e.plan(abi.Params([pat], regex=True, **kw))
+                if general:
+                    e.force_regex_general(True)  # (read when the plan is made)
+                try:
+                    plan = e.plan(abi.Params([pat], regex=True, **kw))
+                finally:
+                    if general:
+                        e.force_regex_general(False)
                 try:
                     before = e.regex_loops_roads()
                     ms, out = median_ms(plan, mode == "records", windows)
@@ -125,7 +148,7 @@ for name, kind, seed, needle, period in TEXTS[:1] if haystack_only else TEXTS:
         m = min(n, cpu_mib << 20)
         host = e.generate_host(m, 0, kind, seed, needle, period)
         say(f"# the reference's regex_search (compiled reference, glibc regexec, ONE thread) on the first {m >> 20} MiB of the same text")
-        for pat, _ in PATTERNS:
+        for pat in dict.fromkeys(p[0] for p in patterns):
             for mode in ("count", "-c"):
                 kw = dict(count_lines=True) if mode == "-c" else dict(track_positions=False)
                 t0 = time.perf_counter()
@@ -135,6 +158,8 @@ for name, kind, seed, needle, period in TEXTS[:1] if haystack_only else TEXTS:
     else:
         say("# no compiled reference (oracle/_ref) on this host: the CPU rows are missing")
 e.set_regex_loops(False)
+if groups:
+    e.set_regex_groups(False)
 if windows > 1:
     e.set_regex_loops_windows(False)
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
