@@ -209,8 +209,6 @@ thread_local BatchTimes tl_search_times, tl_grep_times;    // krep_gpu_debug_bat
 std::atomic<uint64_t> g_rebase_lds{0}, g_rebase_global{0}; // krep_gpu_debug_batch_rebase_launches
 std::atomic<uint64_t> g_cut_lds{0}, g_cut_global{0};       // krep_gpu_debug_batch_cut_launches
 
-bool holds_newline(const uint8_t cls[32]) { return (cls['\n' >> 3] >> ('\n' & 7)) & 1; }
-
 // ---- the segmentation of one pack in steps (batch_segment below)
 // the scratch's growth rule: half again what is needed, `floor` at the least
 uint64_t grown(uint64_t need, uint64_t floor = 0) { return std::max<uint64_t>(need + need / 2, floor); }
@@ -354,19 +352,10 @@ const char *batch_unsupported_reason(const search_params_t *p, const krep_gpu_co
         RegexCompiled rc;
         if (const char *why = regex_compile_cached(p, &rc))
             return why;
-        bool nl = false;
-        if (rc.is_loops)
-            ; // (the loops compiler refuses a class that holds '\n', and its one-window rule is no reason against a pack: a pack is one window)
-        else if (rc.is_alt)
-            for (uint32_t b = 0; b < rc.alt.n_branches; ++b)
-                for (uint32_t j = 0; j < rc.alt.branch[b].L; ++j)
-                    nl = nl || holds_newline(rc.alt.branch[b].classes[j]);
-        else
-            for (uint32_t j = 0; j < rc.seq.seq.L; ++j)
-                nl = nl || holds_newline(rc.seq.seq.classes[j]);
-        if (nl)
+        // (a line walk's classes never hold '\n', and its one-window rule is no reason against a pack: a pack is one window)
+        if (rc.holds_newline())
             return "batch: a byte class of the expression holds '\\n': a match could take in the separator between two items";
-        if ((rc.is_loops ? rc.loops.eol : rc.is_alt ? rc.alt_eol : rc.seq.eol) && !p->case_sensitive)
+        if (rc.has_eol() && !p->case_sensitive)
             return "batch: $ in a case-insensitive search: the end of the text ends no line there (REG_NOTEOL, krep.c:1420), which holds "
                    "at the end of every item alone and in a pack only at the end of the last";
         return nullptr;

@@ -768,7 +768,7 @@ std::vector<Piece> piece_layout(const PieceJob &job, size_t chunk, int ndev)
     {
         lmax = std::max<size_t>(lmax, 16); // a{16} is five pattern bytes and sixteen text bytes: the halo follows L <= 16
         RegexCompiled rc;
-        if (!regex_compile_cached(job.params, &rc) && rc.is_loops)
+        if (!regex_compile_cached(job.params, &rc) && rc.line_walked())
             lmax = 4096; // *, + and {n,}: a piece holds every line that meets its owned range, whole (kg_regex_loops.hip)
     }
     const size_t ctx = lmax + 1; // pattern_len-1 to complete straddling matches, +1 for -w, +1 slack

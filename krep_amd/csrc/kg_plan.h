@@ -101,7 +101,7 @@ int scan_ac(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_
 // kg_regex.hip: the program of an accepted -E pattern (NULL: refused or out of memory, the reason in krep_gpu_last_error()), and
 // the regex scan of a window
 RegexProg *regex_prog_create(const search_params_t &sp);
-RegexProg *regex_prog_create_alt(const krep_gpu_regex_alt_t &alt); // ... of an unanchored alternation no search names (a loops program's filter)
+RegexProg *regex_prog_create_alt(const krep_gpu_regex_alt_t &alt, uint32_t bol = 0, uint32_t eol = 0); // ... of an alternation alone (a line walk's filter)
 void regex_prog_free(RegexProg *rx);
 int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
                const krep_gpu_seq_carry_t *carry_in, krep_gpu_seq_carry_t *carry_out, krep_gpu_scan_out_t *out);

@@ -1,7 +1,8 @@
-// kg_regex.hip — krep -E for fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile): the exported pattern
-// compilers (kg_regex_compile.h), the bit-parallel shift-and scan kernel and its scan kg::scan_regex.  An alternation of such
+// kg_regex.hip — krep -E for fixed-length class sequences (include/krep_gpu.h, krep_gpu_regex_compile): the six exported pattern
+// compilers (kg_regex_compile.h, one body), the bit-parallel shift-and scan kernel and its scan kg::scan_regex.  An alternation of such
 // sequences (krep_gpu_regex_compile_alt, and what krep_gpu_regex_compile_ext expands into one, line anchors included) has its own
-// kernel and scan in kg_regex_alt.hip: regex_prog_create builds its table here, scan_regex hands over.
+// kernel and scan in kg_regex_alt.hip, a line walk (krep_gpu_regex_compile_loops, _groups) in kg_regex_loops.hip: regex_prog_create
+// makes the program of each of the three kinds here (the tables are kg_regex_compile.h's), scan_regex hands over.
 // Both scans go through the one window driver of this file (rx_window: the window checks and refusals; rx_drive: the launches, the
 // greedy pass, the read-back and the krep_gpu_scan_out_t), and both kernels are built around their walk from the device helpers of
 // kg_regex_dev.h (table fill, round loader, -c line state, record store, unit end, grid).
@@ -225,28 +226,7 @@ static hipError_t rx_run(const RxArgs &a, int mode, int num_cu, hipStream_t st)
 }
 
 // ------------------------------------------------------------------------------------------------ plan side
-// The table of an alternation: branch i in bits [o_i, o_i + Lx_i), Lx_i = L_i + bol + eol places: the class { '\n' } in front of and / or
-// behind its classes when the branches stand between line anchors (kg_regex_alt.hip); rx->init and rx->fin with it
-static void rx_alt_table(RegexProg *rx, const krep_gpu_regex_alt_t &alt, u32 bol, u32 eol, u32 table[256])
-{
-    memset(table, 0, 256 * sizeof(u32));
-    u32 o = 0;
-    for (u32 i = 0; i < alt.n_branches; ++i)
-    {
-        const krep_gpu_regex_info_t &br = alt.branch[i];
-        const u32 Lx = br.L + bol + eol;
-        rx->init |= 1u << o;
-        rx->fin |= 1u << (o + Lx - 1);
-        for (int b = 0; b < 256; ++b)
-            for (u32 j = 0; j < br.L; ++j)
-                table[b] |= ((br.classes[j][b >> 3] >> (b & 7)) & 1u) << (o + bol + j);
-        if (bol)
-            table['\n'] |= 1u << o;
-        if (eol)
-            table['\n'] |= 1u << (o + Lx - 1);
-        o += Lx;
-    }
-}
+// The program of a plan: what the compilers said (kg_regex_compile.h, which also builds the tables) and its table on the device
 static RegexProg *rx_upload(RegexProg *rx, const u32 table[256])
 {
     if (hipMalloc(&rx->d_table, 256 * sizeof(u32)) != hipSuccess ||
@@ -258,85 +238,40 @@ static RegexProg *rx_upload(RegexProg *rx, const u32 table[256])
     }
     return rx;
 }
-// the program of an unanchored alternation that no search names: the filter of a loops program (kg_regex_loops.hip)
-RegexProg *regex_prog_create_alt(const krep_gpu_regex_alt_t &alt)
+// the program of an alternation between line anchors: a search's, or with neither anchor the filter of a line walk (kg_regex_loops.hip)
+RegexProg *regex_prog_create_alt(const krep_gpu_regex_alt_t &alt, u32 bol, u32 eol)
 {
     auto *rx = new RegexProg();
     u32 table[256];
-    rx->is_alt = true;
+    rx->kind = RegexCompiled::kAlt;
     rx->alt = alt;
-    rx_alt_table(rx, alt, 0, 0, table);
+    rx->alt_bol = bol;
+    rx->alt_eol = eol;
+    rx_alt_table(alt, bol, eol, table, &rx->init, &rx->fin);
     return rx_upload(rx, table);
 }
 RegexProg *regex_prog_create(const search_params_t &sp)
 {
-    auto *rx = new RegexProg();
     RegexCompiled rc;
     if (const char *why = regex_compile_cached(&sp, &rc))
     {
         fail("%s", why);
-        delete rx;
         return nullptr;
     }
+    if (rc.kind == RegexCompiled::kAlt)
+        return regex_prog_create_alt(rc.alt, rc.alt_bol ? 1u : 0u, rc.alt_eol ? 1u : 0u);
+    auto *rx = new RegexProg();
+    rx->kind = rc.kind;
+    if (rc.kind == RegexCompiled::kWalk)
+    { // test hook (krep_gpu_debug_force_regex_general, with both switches on): a loops program through the general step
+        const bool force = !rc.walk.general && g_rl_force_general.load() && g_regex_loops.load(std::memory_order_relaxed) &&
+                           g_regex_groups.load(std::memory_order_relaxed);
+        rx->walk = force ? regex_walk_as_general(rc.walk) : rc.walk;
+        return rx_upload(rx, rx->walk.table);
+    }
     u32 table[256];
-    if (rc.is_groups)
-    { // a position automaton (kg_regex_loops.hip, the general step): one bit per position, the follow relation cut into chain, self and
-      // jump pairs; everything around the walk reads it as a loops program
-        rx->is_loops = rx->general = true;
-        rx->loops = rc.loops;
-        for (int b = 0; b < 256; ++b)
-        {
-            u32 m = 0;
-            for (u32 i = 0; i < rc.groups.n_pos; ++i)
-                m |= ((rc.groups.classes[i][b >> 3] >> (b & 7)) & 1u) << i;
-            table[b] = m;
-        }
-        rx->init = rc.groups.first;
-        rx->fin = rc.groups.last;
-        rx->n_jumps = regex_groups_jumps(rc.groups, &rx->chain, &rx->plus, rx->jump_src, rx->jump_dst, kRegexGroupsMaxJumps);
-    }
-    else if (rc.is_loops)
-    { // places that may repeat (kg_regex_loops.hip): the alternation's layout without anchor places — ^ and $ are the line walk's own —
-      // and `plus`, the bits of the places that repeat
-        rx->is_loops = true;
-        rx->loops = rc.loops;
-        rx_alt_table(rx, rc.loops.alt, 0, 0, table);
-        u32 o = 0;
-        for (u32 i = 0; i < rc.loops.alt.n_branches; ++i)
-        {
-            rx->plus |= (u32)rc.loops.repeat[i] << o;
-            o += rc.loops.alt.branch[i].L;
-        }
-        // test hook (krep_gpu_debug_force_regex_general): the same program through the general step — a place hands over along CHAIN
-        // (every place but a branch's last), a repeating place is in SELF, no jump pairs
-        if (g_rl_force_general.load() && g_regex_loops.load(std::memory_order_relaxed) && g_regex_groups.load(std::memory_order_relaxed))
-        {
-            rx->general = true;
-            rx->chain = (o >= 32u ? ~0u : (1u << o) - 1u) & ~rx->fin;
-        }
-    }
-    else if (rc.is_alt)
-    {
-        rx->is_alt = true;
-        rx->alt = rc.alt;
-        rx->alt_bol = rc.alt_bol ? 1u : 0u;
-        rx->alt_eol = rc.alt_eol ? 1u : 0u;
-        rx_alt_table(rx, rc.alt, rx->alt_bol, rx->alt_eol, table);
-    }
-    else
-    {
-        rx->info = rc.seq;
-        const krep_gpu_regex_info_t &seq = rx->info.seq;
-        const u32 bol = rx->info.bol ? 1u : 0u, eol = rx->info.eol ? 1u : 0u;
-        for (int b = 0; b < 256; ++b)
-        {
-            u32 m = 0;
-            for (u32 j = 0; j < seq.L; ++j)
-                m |= ((seq.classes[j][b >> 3] >> (b & 7)) & 1u) << (bol + j);
-            table[b] = m;
-        }
-        table['\n'] |= bol | (eol << (bol + seq.L));
-    }
+    rx->info = rc.seq;
+    rx_seq_table(rc.seq, table);
     return rx_upload(rx, table);
 }
 void regex_prog_free(RegexProg *rx)
@@ -492,9 +427,9 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
         *carry_out = carry_in ? *carry_in : krep_gpu_seq_carry_t{};
     if (!pl->rx)
         return fail("scan_device: the regex plan holds no program");
-    if (pl->rx->is_loops)
+    if (pl->rx->kind == RegexCompiled::kWalk)
         return scan_regex_loops(pl, w, d_pos, cap, st, time_it, out);
-    if (pl->rx->is_alt)
+    if (pl->rx->kind == RegexCompiled::kAlt)
         return scan_regex_alt(pl, w, d_pos, cap, st, time_it, out);
     const krep_gpu_regex_info_t &info = pl->rx->info.seq;
     const u32 L = info.L, bol = pl->rx->info.bol ? 1u : 0u, eol = pl->rx->info.eol ? 1u : 0u;
@@ -526,33 +461,19 @@ int scan_regex(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint
     return rx_drive(pl, w, sp, g, d_pos, cap, st, time_it, &a.o, a.n_units,
                     [&](int mode) { return rx_run(a, mode, pl->num_cu, st); }, out);
 }
+// the body of every exported compiler: the compiler's reason is the error
+template <class Out> static int rx_export(const char *(*compile)(const search_params_t *, Out *), const search_params_t *params, Out *out)
+{
+    krep_gpu_clear_error();
+    if (const char *why = compile(params, out))
+        return fail("%s", why);
+    return 0;
+}
 } // namespace kg
 
-extern "C" int krep_gpu_regex_compile(const search_params_t *params, krep_gpu_regex_info_t *out)
-{
-    krep_gpu_clear_error();
-    if (const char *why = kg::regex_compile(params, out))
-        return kg::fail("%s", why);
-    return 0;
-}
-extern "C" int krep_gpu_regex_compile_anchored(const search_params_t *params, krep_gpu_regex_anchored_t *out)
-{
-    krep_gpu_clear_error();
-    if (const char *why = kg::regex_compile_anchored(params, out))
-        return kg::fail("%s", why);
-    return 0;
-}
-extern "C" int krep_gpu_regex_compile_alt(const search_params_t *params, krep_gpu_regex_alt_t *out)
-{
-    krep_gpu_clear_error();
-    if (const char *why = kg::regex_compile_alt(params, out))
-        return kg::fail("%s", why);
-    return 0;
-}
-extern "C" int krep_gpu_regex_compile_ext(const search_params_t *params, krep_gpu_regex_ext_t *out)
-{
-    krep_gpu_clear_error();
-    if (const char *why = kg::regex_compile_ext(params, out))
-        return kg::fail("%s", why);
-    return 0;
-}
+extern "C" int krep_gpu_regex_compile(const search_params_t *p, krep_gpu_regex_info_t *out) { return kg::rx_export(kg::regex_compile, p, out); }
+extern "C" int krep_gpu_regex_compile_anchored(const search_params_t *p, krep_gpu_regex_anchored_t *out) { return kg::rx_export(kg::regex_compile_anchored, p, out); }
+extern "C" int krep_gpu_regex_compile_alt(const search_params_t *p, krep_gpu_regex_alt_t *out) { return kg::rx_export(kg::regex_compile_alt, p, out); }
+extern "C" int krep_gpu_regex_compile_ext(const search_params_t *p, krep_gpu_regex_ext_t *out) { return kg::rx_export(kg::regex_compile_ext, p, out); }
+extern "C" int krep_gpu_regex_compile_loops(const search_params_t *p, krep_gpu_regex_loops_t *out) { return kg::rx_export(kg::regex_compile_loops, p, out); }
+extern "C" int krep_gpu_regex_compile_groups(const search_params_t *p, krep_gpu_regex_groups_t *out) { return kg::rx_export(kg::regex_compile_groups, p, out); }

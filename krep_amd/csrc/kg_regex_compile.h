@@ -3,9 +3,11 @@
 // (tools/regex_compile_san.cpp).  It never sees a text: what it produces is a table, the search is the kernels' (kg_regex.hip,
 // kg_regex_alt.hip).  In the order of the file:
 //   the rules every compiler shares, one copy of each: what a search and a pattern must be (regex_check_search, regex_check_pattern),
-//     where an atom ends (regex_atom), a repetition count (regex_count), an atom's class from libc's own regcomp / regexec
-//     (regex_probe_atom), when two sequences overlap (regex_branches_overlap_anchored), identical class tables merging
-//     (regex_branch_add), and the fields behind the classes (regex_seq_finish, regex_alt_finish);
+//     where an atom ends (regex_atom), a repetition count (regex_count), the quantifier behind an operand (regex_quant), an atom's
+//     class from libc's own regcomp / regexec (regex_probe_atom), the walk over a search's patterns and the frame of an entry point
+//     that zeroes a refused struct (regex_each_pattern, regex_compile_zeroing), when two sequences overlap
+//     (regex_branches_overlap_anchored), identical class tables merging (regex_branch_add), and the fields behind the classes
+//     (regex_seq_finish, regex_alt_finish);
 //   krep_gpu_regex_compile / _anchored: a TOKENISER that cuts an expression into a fixed number of one-byte atoms;
 //   krep_gpu_regex_compile_alt: cuts an alternation at its top-level '|', takes one pair of parentheses off a branch and hands
 //     every branch to that tokeniser;
@@ -16,10 +18,15 @@
 //   krep_gpu_regex_compile_groups: a recursive parser of its own for repeated and nested groups; it does not expand but builds the
 //     position (Glushkov) automaton of the expression, cuts its follow relation into what the line walk steps (regex_groups_jumps)
 //     and derives a filter from the positions every match passes;
-//   regex_compile_search: those that take a search, in the order every search asks them, and the reason it reports.
+//   the tables the kernels look a byte up in (rx_seq_table, rx_alt_table) and RegexWalk, the one program of the line walk
+//     (kg_regex_loops.hip), built from a loops program, from a position automaton, or from the first rewritten as the second
+//     (regex_walk_of_loops, regex_walk_of_groups, regex_walk_as_general);
+//   regex_compile_search: those that take a search, in the order every search asks them, the reason it reports, and its verdict
+//     RegexCompiled: which kind of program (kSeq, kAlt, kWalk), that kind's payload, and what the code around the scans asks of it.
 // Each compiler reports the first fault IT meets, and they meet faults in different orders (the tokeniser probes atoms only after
 // the whole pattern is cut, the expanding compiler as it goes, the alternation compiler walks a branch's parentheses before it
-// tokenises the branch): the refusal strings are public, so the shared rules sit under four control flows.
+// tokenises the branch, the groups compiler has no "without a bound" stage): the refusal strings are public, so the shared rules sit
+// under their control flows.
 #pragma once
 #include <regex.h>
 #include <stdint.h>
@@ -167,6 +174,90 @@ inline bool regex_probe_atom(const uint8_t *atom, size_t len, bool case_sensitiv
     return true;
 }
 constexpr const char *kRegexAtomRefused = "regex: regcomp refuses an atom of the pattern";
+
+// The quantifier behind an operand, pat[*i] one of ? * + {: ? is {0,1}, * is {0,}, + is {1,}, {n} {n,} {n,m} with counts up to 1000.
+// kNone: *q says it (hi == lo when unbounded) and *i stands behind it.  Else the first fault in the order every caller reports them:
+// without unbounded_ok a * or + (kStarPlus) and a {n,} (kOpenCount) where it is met, before the range is judged; a malformed or
+// reversed range or a count past 1000; a range that ends at 0; a second quantifier behind this one.  The strings are the callers'.
+struct RegexQuant { uint32_t lo, hi; bool unbounded; };
+enum class RegexQuantFault { kNone, kStarPlus, kOpenCount, kMalformed, kZero, kBehindQuant };
+inline bool regex_is_quant(uint8_t c) { return c == '?' || c == '*' || c == '+' || c == '{'; }
+inline RegexQuantFault regex_quant(const uint8_t *pat, size_t n, size_t *i, bool unbounded_ok, RegexQuant *q)
+{
+    *q = RegexQuant{0, 1, false};
+    if (pat[*i] == '*' || pat[*i] == '+')
+    {
+        if (!unbounded_ok)
+            return RegexQuantFault::kStarPlus;
+        *q = RegexQuant{pat[*i] == '+' ? 1u : 0u, pat[*i] == '+' ? 1u : 0u, true};
+        ++*i;
+    }
+    else if (pat[*i] == '?')
+        ++*i;
+    else
+    {
+        size_t k = *i + 1;
+        if (!regex_count(pat, n, &k, &q->lo))
+            return RegexQuantFault::kMalformed;
+        q->hi = q->lo;
+        if (pat[k] == ',')
+        {
+            ++k;
+            if (k < n && pat[k] == '}')
+            {
+                if (!unbounded_ok)
+                    return RegexQuantFault::kOpenCount;
+                q->unbounded = true;
+            }
+            else if (!regex_count(pat, n, &k, &q->hi))
+                return RegexQuantFault::kMalformed;
+        }
+        if (pat[k] != '}' || q->lo > q->hi || q->hi > 1000)
+            return RegexQuantFault::kMalformed;
+        if (!q->unbounded && q->hi == 0)
+            return RegexQuantFault::kZero;
+        *i = k + 1;
+    }
+    return *i < n && regex_is_quant(pat[*i]) ? RegexQuantFault::kBehindQuant : RegexQuantFault::kNone;
+}
+
+// What the entry points that take several patterns share.  The frame: NULL params, *out zeroed, the compiler, *out zeroed again when
+// it refuses.  The walk: what the search must be, then every pattern fetched, checked and handed to each(pat, n).
+// the patterns a search names: patterns[0..num_patterns) when the arrays are there, else pattern alone
+inline size_t regex_pattern_count(const search_params_t *p) { return (p->num_patterns >= 1 && p->patterns && p->pattern_lens) ? p->num_patterns : 1; }
+inline void regex_pattern_at(const search_params_t *p, size_t k, const uint8_t **pat, size_t *n)
+{
+    const bool arrays = p->num_patterns >= 1 && p->patterns && p->pattern_lens;
+    *pat = (const uint8_t *)(arrays ? p->patterns[k] : p->pattern);
+    *n = arrays ? p->pattern_lens[k] : p->pattern_len;
+}
+template <class Out, class Compile> inline const char *regex_compile_zeroing(const search_params_t *p, Out *out, Compile compile)
+{
+    if (!p || !out)
+        return "NULL params";
+    memset(out, 0, sizeof *out);
+    const char *why = compile(p, out);
+    if (why)
+        memset(out, 0, sizeof *out);
+    return why;
+}
+template <class Each> inline const char *regex_each_pattern(const search_params_t *p, Each each)
+{
+    if (const char *why = regex_check_search(p, true))
+        return why;
+    const size_t n_pat = regex_pattern_count(p);
+    for (size_t k = 0; k < n_pat; ++k)
+    {
+        const uint8_t *pat;
+        size_t n;
+        regex_pattern_at(p, k, &pat, &n);
+        if (const char *why = regex_check_pattern(pat, n))
+            return why;
+        if (const char *why = each(pat, n))
+            return why;
+    }
+    return nullptr;
+}
 
 inline bool regex_classes_meet(const uint8_t a[32], const uint8_t b[32])
 {
@@ -373,21 +464,6 @@ inline const char *regex_compile_anchored(const search_params_t *p, krep_gpu_reg
 }
 
 // ---- krep_gpu_regex_compile_alt: an alternation of class sequences ------------------------------------------------------------
-// the patterns a search names: patterns[0..num_patterns) when the arrays are there, else pattern alone
-inline size_t regex_pattern_count(const search_params_t *p) { return (p->num_patterns >= 1 && p->patterns && p->pattern_lens) ? p->num_patterns : 1; }
-inline void regex_pattern_at(const search_params_t *p, size_t k, const uint8_t **pat, size_t *n)
-{
-    if (p->num_patterns >= 1 && p->patterns && p->pattern_lens)
-    {
-        *pat = (const uint8_t *)p->patterns[k];
-        *n = p->pattern_lens[k];
-    }
-    else
-    {
-        *pat = (const uint8_t *)p->pattern;
-        *n = p->pattern_len;
-    }
-}
 // does the search say an alternation: several patterns, or a '|' or '(' outside brackets and not behind a backslash
 inline bool regex_has_alt_syntax(const search_params_t *p)
 {
@@ -464,16 +540,7 @@ inline const char *regex_alt_branch(const uint8_t *pat, size_t n, size_t bs, siz
 }
 inline const char *regex_compile_alt_branches(const search_params_t *p, krep_gpu_regex_alt_t *out)
 {
-    if (const char *why = regex_check_search(p, true))
-        return why;
-    const size_t n_pat = regex_pattern_count(p);
-    for (size_t k = 0; k < n_pat; ++k)
-    {
-        const uint8_t *pat;
-        size_t n;
-        regex_pattern_at(p, k, &pat, &n);
-        if (const char *why = regex_check_pattern(pat, n))
-            return why;
+    const char *why = regex_each_pattern(p, [&](const uint8_t *pat, size_t n) -> const char * {
         for (size_t bs = 0, end; bs <= n; bs = end + 1) // (a '|' at the very end has an empty branch behind it)
         {
             size_t lo, hi;
@@ -492,23 +559,15 @@ inline const char *regex_compile_alt_branches(const search_params_t *p, krep_gpu
             if (!regex_branch_add(out->branch, &out->n_branches, info))
                 return kRegexAltTooManyBranches;
         }
-    }
+        return nullptr;
+    });
+    if (why)
+        return why;
     regex_alt_finish(out, false, false);
-    if (out->total_L > kRegexMaxTotalL)
-        return kRegexAltTooWide;
-    return nullptr;
+    return out->total_L > kRegexMaxTotalL ? kRegexAltTooWide : nullptr;
 }
 // krep_gpu_regex_compile_alt: NULL and *out filled, or the refusal and *out zeroed
-inline const char *regex_compile_alt(const search_params_t *p, krep_gpu_regex_alt_t *out)
-{
-    if (!p || !out)
-        return "NULL params";
-    memset(out, 0, sizeof *out);
-    const char *why = regex_compile_alt_branches(p, out);
-    if (why)
-        memset(out, 0, sizeof *out);
-    return why;
-}
+inline const char *regex_compile_alt(const search_params_t *p, krep_gpu_regex_alt_t *out) { return regex_compile_zeroing(p, out, regex_compile_alt_branches); }
 
 // ---- krep_gpu_regex_compile_ext: ?, {n,m}, inner groups and anchored alternations, expanded into class sequences --------------
 // A partial expansion: at most 8 distinct sequences (only L and classes of each are in use; L == 0 is the empty sequence).  The
@@ -578,7 +637,6 @@ inline const char *regex_set_repeat(RegexSeqSet &A, uint32_t lo, uint32_t hi)
     A = R;
     return nullptr;
 }
-inline bool regex_is_quant(uint8_t c) { return c == '?' || c == '*' || c == '+' || c == '{'; }
 
 // the cursor over one pattern
 struct RegexExtCursor
@@ -598,59 +656,30 @@ inline const char *regex_ext_quant(RegexExtCursor &c, RegexSeqSet &A, bool atom)
 {
     if (c.i >= c.n || !regex_is_quant(c.pat[c.i]))
         return nullptr;
-    uint32_t lo = 0, hi = 1;
-    bool unbounded = false;
-    if (c.pat[c.i] == '*' || c.pat[c.i] == '+')
+    RegexQuant q;
+    switch (regex_quant(c.pat, c.n, &c.i, c.loops, &q))
     {
-        if (!c.loops)
-            return kRegexStarPlus;
-        lo = c.pat[c.i] == '+' ? 1u : 0u;
-        unbounded = true;
-        ++c.i;
+    case RegexQuantFault::kNone: break;
+    case RegexQuantFault::kStarPlus: return kRegexStarPlus;
+    case RegexQuantFault::kOpenCount: return kRegexOpenCount;
+    case RegexQuantFault::kMalformed: return kRegexMalformed;
+    case RegexQuantFault::kZero: return "regex: {0} repeats an atom zero times, a{0} matches the empty string: kept on krep's regex_search";
+    case RegexQuantFault::kBehindQuant: return "regex: a quantifier behind a quantifier (a?{2}, a{2}{3}, a?+): kept on krep's regex_search";
     }
-    else if (c.pat[c.i] == '?')
-        ++c.i;
-    else
-    {
-        size_t k = c.i + 1;
-        if (!regex_count(c.pat, c.n, &k, &lo))
-            return kRegexMalformed;
-        hi = lo;
-        if (c.pat[k] == ',')
-        {
-            ++k;
-            if (k < c.n && c.pat[k] == '}')
-            {
-                if (!c.loops)
-                    return kRegexOpenCount;
-                unbounded = true;
-                hi = lo > 1 ? lo : 1;
-            }
-            else if (!regex_count(c.pat, c.n, &k, &hi))
-                return kRegexMalformed;
-        }
-        if (c.pat[k] != '}' || lo > hi || hi > 1000)
-            return kRegexMalformed;
-        if (hi == 0)
-            return "regex: {0} repeats an atom zero times, a{0} matches the empty string: kept on krep's regex_search";
-        c.i = k + 1;
-    }
-    if (c.i < c.n && regex_is_quant(c.pat[c.i]))
-        return "regex: a quantifier behind a quantifier (a?{2}, a{2}{3}, a?+): kept on krep's regex_search";
-    if (!unbounded)
-        return regex_set_repeat(A, lo, hi);
+    if (!q.unbounded)
+        return regex_set_repeat(A, q.lo, q.hi);
     // C+ is the place C that repeats; C{n,} is C n - 1 times and then C+; C* and C{0,} are nothing, or C+
     if (!atom)
         return kRegexLoopsGroup;
     c.unbounded = true;
     RegexSeqSet plus = A, T;
     regex_seq_plus(plus.s[0]) = 1u;
-    if (lo == 0)
+    if (q.lo == 0)
     {
         regex_set_empty_seq(A);
         return regex_set_union(A, plus);
     }
-    if (const char *why = regex_set_repeat(A, lo - 1, lo - 1))
+    if (const char *why = regex_set_repeat(A, q.lo - 1, q.lo - 1))
         return why;
     if (const char *why = regex_set_cat(A, plus, T))
         return why;
@@ -763,17 +792,10 @@ inline const char *regex_ext_branch(RegexExtCursor &c, RegexSeqSet &S, int *bol,
 inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu_regex_ext_t *out, bool loops = false, uint32_t *plus = nullptr,
                                               bool *unbounded = nullptr)
 {
-    if (const char *why = regex_check_search(p, true))
-        return why;
     krep_gpu_regex_alt_t &alt = out->alt;
-    const size_t n_pat = regex_pattern_count(p);
     bool first = true;
-    for (size_t k = 0; k < n_pat; ++k)
-    {
-        RegexExtCursor c{nullptr, 0, 0, p->case_sensitive, loops};
-        regex_pattern_at(p, k, &c.pat, &c.n);
-        if (const char *why = regex_check_pattern(c.pat, c.n))
-            return why;
+    const char *why = regex_each_pattern(p, [&](const uint8_t *pat, size_t n) -> const char * {
+        RegexExtCursor c{pat, n, 0, p->case_sensitive, loops};
         for (;;)
         {
             RegexSeqSet S;
@@ -799,7 +821,10 @@ inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu
         }
         if (unbounded)
             *unbounded = *unbounded || c.unbounded;
-    }
+        return nullptr;
+    });
+    if (why)
+        return why;
     const uint32_t extra = (uint32_t)(out->bol + out->eol);
     for (uint32_t b = 0; b < alt.n_branches; ++b)
     {
@@ -818,13 +843,7 @@ inline const char *regex_compile_ext_branches(const search_params_t *p, krep_gpu
 // krep_gpu_regex_compile_ext: NULL and *out filled, or the refusal and *out zeroed
 inline const char *regex_compile_ext(const search_params_t *p, krep_gpu_regex_ext_t *out)
 {
-    if (!p || !out)
-        return "NULL params";
-    memset(out, 0, sizeof *out);
-    const char *why = regex_compile_ext_branches(p, out);
-    if (why)
-        memset(out, 0, sizeof *out);
-    return why;
+    return regex_compile_zeroing(p, out, [](const search_params_t *q, krep_gpu_regex_ext_t *o) { return regex_compile_ext_branches(q, o); });
 }
 
 // ---- krep_gpu_regex_compile_loops: *, + and {n,} behind an atom, expanded into sequences of places that may repeat ------------------
@@ -880,14 +899,9 @@ inline void regex_loops_filter(krep_gpu_regex_loops_t *out)
         regex_seq_finish(&out->filter.branch[b], false, false);
     regex_alt_finish(&out->filter, false, false);
 }
-// krep_gpu_regex_compile_loops: NULL and *out filled, or the refusal and *out zeroed
-inline const char *regex_compile_loops(const search_params_t *p, krep_gpu_regex_loops_t *out)
+inline const char *regex_compile_loops_expand(const search_params_t *p, krep_gpu_regex_loops_t *out)
 {
-    if (!p || !out)
-        return "NULL params";
-    memset(out, 0, sizeof *out);
-    krep_gpu_regex_ext_t ext;
-    memset(&ext, 0, sizeof ext);
+    krep_gpu_regex_ext_t ext{};
     uint32_t plus[kRegexMaxBranches] = {0};
     bool unbounded = false;
     if (const char *why = regex_compile_ext_branches(p, &ext, true, plus, &unbounded))
@@ -906,6 +920,8 @@ inline const char *regex_compile_loops(const search_params_t *p, krep_gpu_regex_
     regex_loops_filter(out);
     return nullptr;
 }
+// krep_gpu_regex_compile_loops: NULL and *out filled, or the refusal and *out zeroed
+inline const char *regex_compile_loops(const search_params_t *p, krep_gpu_regex_loops_t *out) { return regex_compile_zeroing(p, out, regex_compile_loops_expand); }
 
 // ---- krep_gpu_regex_compile_groups: repeated and nested groups, held unexpanded as a position (Glushkov) automaton -------------------
 // The expression is parsed into a small tree (counted quantifiers copy their operand by parsing it again: X{2,} is X X+, X{1,3} is
@@ -944,6 +960,7 @@ struct RegexGParser
     size_t n = 0, i = 0;
     bool case_sensitive = true;
     krep_gpu_regex_groups_t *out = nullptr;
+    int bol = -1, eol = -1; // the ^ and $ every top-level branch of the search must carry: -1 before the first branch, then what it had
     std::vector<RegexGNode> nodes;
     int add(RegexGNode::Kind k, int a, int b = -1)
     {
@@ -992,42 +1009,18 @@ inline const char *regex_g_item(RegexGParser &c, uint32_t depth, int *node)
         return why;
     if (c.i >= c.n || !regex_is_quant(c.pat[c.i]))
         return nullptr;
-    uint32_t lo = 0, hi = 1;
-    bool unbounded = false;
-    if (c.pat[c.i] == '*' || c.pat[c.i] == '+')
+    RegexQuant q;
+    switch (regex_quant(c.pat, c.n, &c.i, true, &q))
     {
-        lo = c.pat[c.i] == '+' ? 1u : 0u;
-        unbounded = true;
-        ++c.i;
+    case RegexQuantFault::kZero: return kRegexGroupsZero;
+    case RegexQuantFault::kBehindQuant: return kRegexGroupsQuantQuant;
+    case RegexQuantFault::kNone: break;
+    default: return kRegexMalformed;
     }
-    else if (c.pat[c.i] == '?')
-        ++c.i;
-    else
-    {
-        size_t k = c.i + 1;
-        if (!regex_count(c.pat, c.n, &k, &lo))
-            return kRegexMalformed;
-        hi = lo;
-        if (c.pat[k] == ',')
-        {
-            ++k;
-            if (k < c.n && c.pat[k] == '}')
-                unbounded = true;
-            else if (!regex_count(c.pat, c.n, &k, &hi))
-                return kRegexMalformed;
-        }
-        if (c.pat[k] != '}' || (!unbounded && lo > hi) || lo > 1000 || hi > 1000)
-            return kRegexMalformed;
-        if (!unbounded && hi == 0)
-            return kRegexGroupsZero;
-        c.i = k + 1;
-    }
-    if (c.i < c.n && regex_is_quant(c.pat[c.i]))
-        return kRegexGroupsQuantQuant;
     const size_t behind = c.i;
     // X{lo,hi}: lo copies in a row, then hi - lo optional ones; X{lo,}: lo - 1 copies and X+ (lo == 0: X*).  *node is the first copy;
     // every further one is the operand parsed again, which gives it positions of its own (the 33rd position ends a large count)
-    const uint32_t plain = unbounded ? (lo ? lo - 1 : 0) : lo, opt = unbounded ? 0 : hi - lo;
+    const uint32_t plain = q.unbounded ? (q.lo ? q.lo - 1 : 0) : q.lo, opt = q.unbounded ? 0 : q.hi - q.lo;
     int acc = -1, copy = *node;
     bool have = true; // `copy` is a copy that no place of the result uses yet
     auto next_copy = [&]() -> const char * {
@@ -1046,11 +1039,11 @@ inline const char *regex_g_item(RegexGParser &c, uint32_t depth, int *node)
             return why;
         put(copy);
     }
-    if (unbounded)
+    if (q.unbounded)
     {
         if (const char *why = next_copy())
             return why;
-        put(c.add(lo ? RegexGNode::kPlus : RegexGNode::kStar, copy));
+        put(c.add(q.lo ? RegexGNode::kPlus : RegexGNode::kStar, copy));
     }
     for (uint32_t k = 0; k < opt; ++k)
     {
@@ -1086,52 +1079,36 @@ inline const char *regex_g_seq(RegexGParser &c, uint32_t depth, bool top, int *n
     *node = acc;
     return nullptr;
 }
-// alt = seq ('|' seq)*; depth 0 is the top level of a pattern, where every branch may stand between ^ and $: anchors[0] / [1] are
-// -1 before the first branch of the search and then what every branch must carry
-struct RegexGAnchors { int bol = -1, eol = -1; };
-inline const char *regex_g_alt_top(RegexGParser &c, RegexGAnchors &an, int *node)
+// alt = seq ('|' seq)*.  Depth 0 is the top level of a pattern: it ends with the pattern, not with a ')', every branch may stand
+// between ^ and $, and all top-level branches of the search carry the same pair (c.bol / c.eol)
+inline const char *regex_g_alt(RegexGParser &c, uint32_t depth, int *node)
 {
+    const bool top = depth == 0;
     int acc = -1;
     for (;;)
     {
         int bol = 0, eol = 0, seq;
-        if (c.i < c.n && c.pat[c.i] == '^')
+        if (top && c.i < c.n && c.pat[c.i] == '^')
         {
             bol = 1;
             ++c.i;
         }
-        if (const char *why = regex_g_seq(c, 0, true, &seq, &eol))
+        if (const char *why = regex_g_seq(c, depth, top, &seq, &eol))
             return why;
-        if (an.bol < 0)
+        if (top && c.bol < 0)
         {
-            an.bol = bol;
-            an.eol = eol;
+            c.bol = bol;
+            c.eol = eol;
         }
-        else if (an.bol != bol || an.eol != eol)
+        else if (top && (c.bol != bol || c.eol != eol))
             return kRegexGroupsMixedAnchors;
         acc = acc < 0 ? seq : c.add(RegexGNode::kAlt, acc, seq);
-        if (c.i >= c.n)
+        if (c.i >= c.n || c.pat[c.i] == ')')
+        {
+            if ((c.i >= c.n) != top) // a ')' nobody opened, or a group the pattern ends in
+                return kRegexAltUnbalanced;
             break;
-        if (c.pat[c.i] == ')')
-            return kRegexAltUnbalanced;
-        ++c.i; // the '|'
-    }
-    *node = acc;
-    return nullptr;
-}
-inline const char *regex_g_alt(RegexGParser &c, uint32_t depth, int *node)
-{
-    int acc = -1;
-    for (;;)
-    {
-        int seq, eol = 0;
-        if (const char *why = regex_g_seq(c, depth, false, &seq, &eol))
-            return why;
-        acc = acc < 0 ? seq : c.add(RegexGNode::kAlt, acc, seq);
-        if (c.i >= c.n)
-            return kRegexAltUnbalanced;
-        if (c.pat[c.i] == ')')
-            break;
+        }
         ++c.i; // the '|'
     }
     *node = acc;
@@ -1322,32 +1299,29 @@ inline RegexGReq regex_g_req(const RegexGParser &c, int nd, const RegexGFactor *
 
 inline const char *regex_compile_groups_parse(const search_params_t *p, krep_gpu_regex_groups_t *out)
 {
-    if (const char *why = regex_check_search(p, true))
-        return why;
     RegexGParser c;
     c.case_sensitive = p->case_sensitive;
     c.out = out;
-    RegexGAnchors an;
     int root = -1;
-    const size_t n_pat = regex_pattern_count(p);
-    for (size_t k = 0; k < n_pat; ++k)
-    {
-        regex_pattern_at(p, k, &c.pat, &c.n);
+    const char *why = regex_each_pattern(p, [&](const uint8_t *pat, size_t n) -> const char * {
+        c.pat = pat;
+        c.n = n;
         c.i = 0;
-        if (const char *why = regex_check_pattern(c.pat, c.n))
-            return why;
         int nd;
-        if (const char *why = regex_g_alt_top(c, an, &nd))
+        if (const char *why = regex_g_alt(c, 0, &nd))
             return why;
         root = root < 0 ? nd : c.add(RegexGNode::kAlt, root, nd);
-    }
+        return nullptr;
+    });
+    if (why)
+        return why;
     const RegexGSets S = regex_g_sets(c, root, out);
     if (S.nullable)
         return kRegexGroupsNullable;
     out->first = S.first;
     out->last = S.last;
-    out->bol = an.bol > 0;
-    out->eol = an.eol > 0;
+    out->bol = c.bol > 0;
+    out->eol = c.eol > 0;
     {   // the older compilers keep what is theirs
         krep_gpu_regex_anchored_t a;
         krep_gpu_regex_alt_t b;
@@ -1377,34 +1351,125 @@ inline const char *regex_compile_groups_parse(const search_params_t *p, krep_gpu
     return kRegexGroupsNoFilter;
 }
 // krep_gpu_regex_compile_groups: NULL and *out filled, or the refusal and *out zeroed
-inline const char *regex_compile_groups(const search_params_t *p, krep_gpu_regex_groups_t *out)
+inline const char *regex_compile_groups(const search_params_t *p, krep_gpu_regex_groups_t *out) { return regex_compile_zeroing(p, out, regex_compile_groups_parse); }
+
+// ---- the tables the kernels look a text byte up in ---------------------------------------------------------------------------------
+// One sequence between its anchors (kg_regex.hip): bit 0 is ^'s newline when bol, bit bol + j class j, bit bol + L $'s newline
+inline void rx_seq_table(const krep_gpu_regex_anchored_t &a, uint32_t table[256])
 {
-    if (!p || !out)
-        return "NULL params";
-    memset(out, 0, sizeof *out);
-    const char *why = regex_compile_groups_parse(p, out);
-    if (why)
-        memset(out, 0, sizeof *out);
-    return why;
+    const uint32_t bol = a.bol ? 1u : 0u, eol = a.eol ? 1u : 0u;
+    memset(table, 0, 256 * sizeof(uint32_t));
+    for (int b = 0; b < 256; ++b)
+        for (uint32_t j = 0; j < a.seq.L; ++j)
+            table[b] |= ((a.seq.classes[j][b >> 3] >> (b & 7)) & 1u) << (bol + j);
+    table['\n'] |= bol | (eol << (bol + a.seq.L));
+}
+// An alternation (kg_regex_alt.hip; the places of a loops program): branch i in bits [o_i, o_i + Lx_i), Lx_i = L_i + bol + eol places: the
+// class { '\n' } in front of and / or behind its classes when the branches stand between line anchors; *init every o_i, *fin every
+// o_i + Lx_i - 1
+inline void rx_alt_table(const krep_gpu_regex_alt_t &alt, uint32_t bol, uint32_t eol, uint32_t table[256], uint32_t *init, uint32_t *fin)
+{
+    memset(table, 0, 256 * sizeof(uint32_t));
+    *init = *fin = 0;
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < alt.n_branches; ++i)
+    {
+        const krep_gpu_regex_info_t &br = alt.branch[i];
+        const uint32_t Lx = br.L + bol + eol;
+        *init |= 1u << o;
+        *fin |= 1u << (o + Lx - 1);
+        for (int b = 0; b < 256; ++b)
+            for (uint32_t j = 0; j < br.L; ++j)
+                table[b] |= ((br.classes[j][b >> 3] >> (b & 7)) & 1u) << (o + bol + j);
+        table['\n'] |= (bol << o) | (eol << (o + Lx - 1)); // (bol, eol: 0 or 1)
+        o += Lx;
+    }
+}
+
+// ---- the program of the line walk (kg_regex_loops.hip) ------------------------------------------------------------------------------
+// What kg::rx_line_walk runs, whichever compiler took the search.  The state is 32 bits; an attempt starts with init & table[byte],
+// a match ends where the state meets fin.  !general: the bits are the PLACES of flat sequences laid out like an alternation's, and a
+// step is the shift: a place hands over to the next one, a place of `self` also stays.  general: the bits are the POSITIONS of an
+// automaton, and a step is follow(S) = ((S & chain) << 1) | (S & self) | the jump_dst of every pair whose jump_src meets S.  ^ and $
+// are the walk's own (no anchor places), and `filter` is the alternation whose occurrences name the candidate lines.
+struct RegexWalk
+{
+    uint32_t table[256];      // bit i of table[b]: byte b is in place / position i
+    uint32_t init, fin, self; // first, last, the places or positions that stay
+    bool general;
+    uint32_t chain, n_jumps, jump_src[kRegexGroupsMaxJumps], jump_dst[kRegexGroupsMaxJumps]; // general only; the unused pairs are 0
+    int bol, eol;
+    krep_gpu_regex_alt_t filter;
+};
+// a loops program: the alternation's layout without anchor places, `self` the places that repeat
+inline RegexWalk regex_walk_of_loops(const krep_gpu_regex_loops_t &l)
+{
+    RegexWalk w{};
+    rx_alt_table(l.alt, 0, 0, w.table, &w.init, &w.fin);
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < l.alt.n_branches; ++i)
+    {
+        w.self |= (uint32_t)l.repeat[i] << o;
+        o += l.alt.branch[i].L;
+    }
+    w.bol = l.bol, w.eol = l.eol;
+    w.filter = l.filter;
+    return w;
+}
+// a position automaton: init = first, fin = last, the follow relation as regex_groups_jumps() cuts it
+inline RegexWalk regex_walk_of_groups(const krep_gpu_regex_groups_t &g)
+{
+    RegexWalk w{};
+    w.general = true;
+    for (int b = 0; b < 256; ++b)
+        for (uint32_t i = 0; i < g.n_pos; ++i)
+            w.table[b] |= ((g.classes[i][b >> 3] >> (b & 7)) & 1u) << i;
+    w.init = g.first;
+    w.fin = g.last;
+    w.n_jumps = regex_groups_jumps(g, &w.chain, &w.self, w.jump_src, w.jump_dst, kRegexGroupsMaxJumps);
+    w.bol = g.bol, w.eol = g.eol;
+    w.filter = g.filter;
+    return w;
+}
+// The shift of a loops program written as a follow relation (the test hook krep_gpu_debug_force_regex_general): every place but a
+// branch's last hands over along chain, a repeating place is in self already, no jump pairs.  (The last branch's last place is the
+// highest bit of fin.)
+inline RegexWalk regex_walk_as_general(RegexWalk w)
+{
+    const uint32_t places = 32u - (uint32_t)__builtin_clz(w.fin);
+    w.general = true;
+    w.chain = (places >= 32u ? ~0u : (1u << places) - 1u) & ~w.fin;
+    return w;
 }
 
 // ---- the compilers in the order every search asks them -------------------------------------------------------------------------
-// The anchored compiler is asked first; only what it refuses goes to the alternation compiler, and what both refuse to the expanding
-// compiler, whose result is an alternation too, between the line anchors alt_bol / alt_eol (is_alt: one of the two took it).  So a
-// search an earlier compiler takes runs the kernel it always ran.  What all three refuse goes to the loops compiler when the caller
-// says so (krep_gpu_set_regex_loops): is_loops, the program in `loops`.  What is still refused goes to the groups compiler when the
-// caller says so (krep_gpu_set_regex_groups): is_loops AND is_groups, the automaton in `groups`; of `loops` only bol, eol and filter
-// are set then — what everything around the line walk reads of a loops program.
+// The anchored compiler is asked first (kSeq); only what it refuses goes to the alternation compiler, and what both refuse to the
+// expanding compiler, whose result is an alternation too, between the line anchors alt_bol / alt_eol (kAlt: one of the two took it).
+// So a search an earlier compiler takes runs the kernel it always ran.  What all three refuse goes to the loops compiler when the
+// caller says so (krep_gpu_set_regex_loops), and what is still refused to the groups compiler when the caller says so
+// (krep_gpu_set_regex_groups): kWalk either way, the line walk's program.
 struct RegexCompiled
 {
-    bool is_alt = false;
-    krep_gpu_regex_anchored_t seq{}; // !is_alt
-    krep_gpu_regex_alt_t alt{};      // is_alt
-    int alt_bol = 0, alt_eol = 0;    // is_alt: ^ in front of / $ behind every branch (the expanding compiler only)
-    bool is_loops = false;           // the loops or the groups compiler took it (then !is_alt, and seq holds nothing)
-    krep_gpu_regex_loops_t loops{};
-    bool is_groups = false;          // the groups compiler took it
-    krep_gpu_regex_groups_t groups{};
+    enum Kind : uint8_t { kSeq, kAlt, kWalk } kind = kSeq;
+    krep_gpu_regex_anchored_t seq{}; // kSeq
+    krep_gpu_regex_alt_t alt{};      // kAlt
+    int alt_bol = 0, alt_eol = 0;    // kAlt: ^ in front of / $ behind every branch (the expanding compiler only)
+    RegexWalk walk{};                // kWalk
+    // what the code around the scans asks
+    bool line_walked() const { return kind == kWalk; }
+    bool has_eol() const { return (kind == kWalk ? walk.eol : kind == kAlt ? alt_eol : seq.eol) != 0; }
+    // two occurrences can share a byte (never asked of a line walk, whose matches are chosen line by line)
+    bool overlaps() const { return (kind == kAlt ? alt.cross_overlap : seq.seq.self_overlap) != 0; }
+    // a byte class holds '\n' (the loops and the groups compiler refuse such an expression)
+    bool holds_newline() const
+    {
+        const krep_gpu_regex_info_t *br = kind == kAlt ? alt.branch : &seq.seq;
+        bool nl = false;
+        for (uint32_t b = 0; kind != kWalk && b < (kind == kAlt ? alt.n_branches : 1u); ++b)
+            for (uint32_t j = 0; j < br[b].L; ++j)
+                nl = nl || regex_class_holds_nl(br[b].classes[j]);
+        return nl;
+    }
 };
 // a refusal of the two older compilers that is a limit of theirs: one the expanding compiler's own limits do not replace
 inline bool regex_older_limit(const char *why)
@@ -1432,14 +1497,14 @@ inline const char *regex_compile_search_older(const search_params_t *p, RegexCom
     const char *why_alt = regex_compile_alt(p, &out->alt);
     if (!why_alt)
     {
-        out->is_alt = true;
+        out->kind = RegexCompiled::kAlt;
         return nullptr;
     }
     krep_gpu_regex_ext_t ext;
     const char *why_ext = regex_compile_ext(p, &ext);
     if (!why_ext)
     {
-        out->is_alt = true;
+        out->kind = RegexCompiled::kAlt;
         out->alt = ext.alt;
         out->alt_bol = ext.bol;
         out->alt_eol = ext.eol;
@@ -1449,31 +1514,29 @@ inline const char *regex_compile_search_older(const search_params_t *p, RegexCom
     const char *today = regex_ext_own_limit(why_ext) && !regex_older_limit(before) ? why_ext : before;
     if (!loops)
         return today;
-    const char *why_loops = regex_compile_loops(p, &out->loops);
+    krep_gpu_regex_loops_t l;
+    const char *why_loops = regex_compile_loops(p, &l);
     if (!why_loops)
     {
-        out->is_loops = true;
+        out->kind = RegexCompiled::kWalk;
+        out->walk = regex_walk_of_loops(l);
         return nullptr;
     }
     return today == kRegexStarPlus || today == kRegexOpenCount ? why_loops : today;
 }
 inline const char *regex_compile_search(const search_params_t *p, RegexCompiled *out, bool loops = false, bool groups = false)
 {
-    out->is_alt = false;
-    out->is_loops = false;
-    out->is_groups = false;
+    out->kind = RegexCompiled::kSeq;
     out->alt_bol = out->alt_eol = 0;
     const char *today = regex_compile_search_older(p, out, loops);
     if (!today || !groups || !p || !p->use_regex)
         return today;
-    const char *why_groups = regex_compile_groups(p, &out->groups);
+    krep_gpu_regex_groups_t g;
+    const char *why_groups = regex_compile_groups(p, &g);
     if (!why_groups)
     {
-        out->is_loops = out->is_groups = true;
-        memset(&out->loops, 0, sizeof out->loops);
-        out->loops.bol = out->groups.bol;
-        out->loops.eol = out->groups.eol;
-        out->loops.filter = out->groups.filter;
+        out->kind = RegexCompiled::kWalk;
+        out->walk = regex_walk_of_groups(g);
         return nullptr;
     }
     return regex_group_reason(today) ? why_groups : today;

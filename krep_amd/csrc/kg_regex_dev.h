@@ -1,6 +1,7 @@
 // kg_regex_dev.h — what the two -E scans share (kg_regex.hip: one class sequence; kg_regex_alt.hip: an alternation of them).  Each
 // file keeps its walk over a lane's 16 bytes and what it reads off the walk; everything around the walk stands here, once:
-//   the program a plan holds, the unit size, the launch modes and RxOut, the tail of both kernels' argument structs;
+//   the program a plan holds (RegexProg: the kind the compilers said, that kind's payload — for a line walk the RegexWalk of
+//     kg_regex_compile.h as it stands — and the table on the device), the unit size, the launch modes and RxOut, the tail of both kernels' argument structs;
 //   device: the LDS table fill, the loader of a round (with the newline behind the text), a lane's range and newline masks, the -c
 //     line state of a unit (RxLineCarry), the wave prefix sum and the record store of the emitting launch, the end of a unit;
 //   host: the grid of a launch, and the declarations of the window driver (rx_window, rx_drive: defined in kg_regex.hip).
@@ -20,29 +21,18 @@ namespace kg {
 
 struct RegexProg
 {
-    krep_gpu_regex_anchored_t info{};
-    u32 *d_table = nullptr; // T[256] over the extended sequence: bit 0 is ^'s newline when bol, bit bol + j class j, bit bol + L $'s newline
-    // an alternation (krep_gpu_regex_compile_alt took the search, the anchored compiler did not): branch i in bits [o_i, o_i + L_i) of
-    // the state, T[b] bit o_i + j set iff b is in C[i][j]; init = every o_i, fin = every o_i + L_i - 1
-    // alt_bol / alt_eol (krep_gpu_regex_compile_ext): every branch has the place { '\n' } in front of / behind its classes, so branch i
-    // takes L_i + alt_bol + alt_eol bits
-    bool is_alt = false;
+    RegexCompiled::Kind kind = RegexCompiled::kSeq; // which scan runs it: kg_regex.hip | kg_regex_alt.hip | kg_regex_loops.hip
+    u32 *d_table = nullptr;                         // the kind's table (rx_seq_table, rx_alt_table, RegexWalk::table) on the device
+    krep_gpu_regex_anchored_t info{};               // kSeq
+    // kAlt (the alternation or the expanding compiler took the search; the filter of a line walk): alt_bol / alt_eol say the place
+    // { '\n' } in front of / behind every branch's classes; init and fin as rx_alt_table() gives them
     krep_gpu_regex_alt_t alt{};
     u32 alt_bol = 0, alt_eol = 0;
     u32 init = 0, fin = 0;
-    // places that may repeat (krep_gpu_regex_compile_loops took the search, kg_regex_loops.hip): the state is laid out like an
-    // alternation's over the places of loops.alt, without anchor places (^ and $ are the line walk's own); plus = the bits of the places
-    // that repeat.  work: the inner plans and the scratch of the scan, made by the plan's first scan
-    bool is_loops = false;
-    krep_gpu_regex_loops_t loops{};
-    u32 plus = 0;
+    // kWalk (the loops or the groups compiler took the search): the line walk's program, and the inner plans and the scratch of its
+    // scan, made by the plan's first scan
+    RegexWalk walk{};
     struct RxLoopsWork *work = nullptr;
-    // a position automaton (krep_gpu_regex_compile_groups took the search; is_loops is set too, and of `loops` only bol, eol and filter):
-    // the line walk takes its general step.  T[b] bit i set iff b is in the class of position i; init = first, fin = last, plus = SELF,
-    // chain and the jump pairs as regex_groups_jumps() (kg_regex_compile.h) cuts the follow relation
-    bool general = false;
-    u32 chain = 0, n_jumps = 0;
-    u32 jump_src[kRegexGroupsMaxJumps] = {0}, jump_dst[kRegexGroupsMaxJumps] = {0};
 };
 void rx_loops_work_free(RxLoopsWork *w); // kg_regex_loops.hip
 

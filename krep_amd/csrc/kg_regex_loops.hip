@@ -1,6 +1,8 @@
 // kg_regex_loops.hip — krep -E with *, + and {n,} behind an atom (include/krep_gpu.h, krep_gpu_regex_compile_loops): ERROR.*timeout,
-// [0-9]+\.[0-9]+, colou*r, ^#+ .  The line walk kernel kg::rx_line_walk and the scan kg::scan_regex_loops; kg_regex.hip builds the
-// program's table and hands over when the plan's program is of this kind.
+// [0-9]+\.[0-9]+, colou*r, ^#+ .  The line walk kernel kg::rx_line_walk and the scan kg::scan_regex_loops, a sequence of the steps
+// in front of it (rl_window, rl_args, rl_cut_line_look, rl_sparse_road, rl_dense_road, rl_walk_passes, rl_newline_summary).  The
+// program is a RegexWalk (kg_regex_compile.h: table, init, fin, self — PLUS and SELF below —, chain and jump pairs, bol, eol, filter);
+// kg_regex.hip puts it on the device and hands over when the plan's program is of this kind.
 //
 // Two properties carry the scan.  No class of such a program holds '\n', so under the reference's REG_NEWLINE a match lies inside one
 // line: the lines are independent, and the leftmost-longest walk of one line is a small sequential job.  And every match holds a
@@ -332,7 +334,7 @@ static int rl_work_create(krep_gpu_plan *pl)
     HIPCHK(hipHostMalloc(&f->h_ctr, sizeof(Counters)));
     HIPCHK(hipEventCreate(&f->ev0));
     HIPCHK(hipEventCreate(&f->ev1));
-    f->rx = regex_prog_create_alt(pl->rx->loops.filter);
+    f->rx = regex_prog_create_alt(pl->rx->walk.filter);
     if (!f->rx)
         return 2;
     search_params_t nl{};
@@ -363,198 +365,230 @@ static int rl_refuse_cut()
                 "ends inside it): stage %u bytes of the text on both sides of the owned range", kRlMaxLine);
 }
 
-// ------------------------------------------------------------------------------------------------ the scan of a window
-int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
-                     krep_gpu_scan_out_t *out)
+// ------------------------------------------------------------------------------------------------ the scan of a window, in steps
+// what the steps of one scan share
+struct RlScan
 {
-    RegexProg &rx = *pl->rx;
+    krep_gpu_plan *pl;
+    const Window &w;
+    hipStream_t st;
+    u64 own_hi; // min(w.own_hi, text_len)
+    bool ends;  // the buffer ends the text
+    RlArgs a;   // the walk's arguments; stage 1 fills in the candidate lines (spans, n_lines, from_nl)
+    bool has_newline = false, know_newline = false; // -c: what stage 1 learnt about a '\n' in the owned range
+};
+struct RlTotals { uint64_t total = 0, nlines = 0; unsigned long long summary = 0; };
+
+// The window rule.  *go: there is something to walk — without it the zeroed *out is the answer (no match is empty).  2: a window
+// that is not the whole text while krep_gpu_set_regex_loops_windows is off.
+static int rl_window(const Window &w, u64 *own_hi, bool *go)
+{
+    *go = false;
     if (w.text_len == 0 || w.global_len == 0 || w.own_lo >= w.own_hi)
-        return 0; // (no match is empty: the zeroed *out is the answer)
+        return 0;
     const bool whole = w.global_base == 0 && w.own_lo == 0 && w.own_hi >= w.text_len && w.global_len == w.text_len;
     if (!whole && !g_regex_loops_windows.load(std::memory_order_relaxed))
         return fail("a regex with *, + or {n,} is walked line by line from each line's first byte: scan the whole text in one window "
                     "(krep_gpu_split_mode() == KREP_GPU_SPLIT_WHOLE)");
-    const u64 own_hi = std::min<u64>(w.own_hi, w.text_len);
-    if (w.own_lo >= own_hi)
-        return 0;
-    if (!rx.work && rl_work_create(pl))
-        return 2;
-    RxLoopsWork &wk = *rx.work;
-    const bool lines = pl->lines;
-    const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(pl->max_count, cap) : 0;
-    HIPCHK(hipSetDevice(pl->device));
-    if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
-
+    *own_hi = std::min<u64>(w.own_hi, w.text_len);
+    *go = w.own_lo < *own_hi;
+    return 0;
+}
+// the walk's arguments from the window and the plan's program (of a program that steps by the shift, chain and the jump pairs are 0)
+static RlArgs rl_args(const krep_gpu_plan *pl, const Window &w, u64 own_hi)
+{
+    const RegexWalk &p = pl->rx->walk;
     RlArgs a{};
     a.text = w.d_text; a.text_len = w.text_len;
     a.global_base = w.global_base;
     a.own_lo = w.own_lo; a.own_hi = own_hi;
-    a.init = rx.init; a.fin = rx.fin; a.plus = rx.plus;
+    a.init = p.init; a.fin = p.fin; a.plus = p.self;
     const bool begins = w.global_base == 0, ends = w.global_base + w.text_len == w.global_len;
-    a.flags = (rx.loops.bol ? 1u : 0u) | (rx.loops.eol ? 2u : 0u) | (pl->sp.case_sensitive && ends ? 4u : 0u) | (begins ? 8u : 0u) |
-              (ends ? 16u : 0u);
-    a.table = rx.d_table;
-    if (rx.general)
-    {
-        a.j.chain = rx.chain;
-        a.j.n = rx.n_jumps;
-        memcpy(a.j.src, rx.jump_src, sizeof a.j.src);
-        memcpy(a.j.dst, rx.jump_dst, sizeof a.j.dst);
-    }
-    const auto launch = !rx.general ? rl_launch<false> : rl_launch<true>; // (the old step first: its kernels keep their place in the code object)
+    a.flags = (p.bol ? 1u : 0u) | (p.eol ? 2u : 0u) | (pl->sp.case_sensitive && ends ? 4u : 0u) | (begins ? 8u : 0u) | (ends ? 16u : 0u);
+    a.table = pl->rx->d_table;
+    a.j.chain = p.chain; a.j.n = p.n_jumps;
+    memcpy(a.j.src, p.jump_src, sizeof a.j.src);
+    memcpy(a.j.dst, p.jump_dst, sizeof a.j.dst);
     a.o.ctr = pl->d_ctr;
-    // stage 1 looks at the BUFFER, not at the owned range: a match that starts in front of own_hi may hold its filter factor behind it,
+    return a;
+}
+// The sparse road in a buffer that does not end the text: the road looks at the lines that hold a filter occurrence IN THE BUFFER.
+// The line the buffer's end cuts may hold its occurrence behind that end and a match that starts in the owned range all the same, so
+// that one line is looked at here: it meets the owned range when no newline stands between the last owned byte and the buffer's end.
+// (A line the buffer's START cuts needs no such look: an owned match lies in the part the buffer holds, with its occurrence.)
+static int rl_cut_line_look(const RlScan &s)
+{
+    uint64_t pos = s.w.text_len;
+    if (tail_find_next_newline(s.w.d_text, s.own_hi - 1, s.w.text_len, &s.pl->d_ctr->pad[0], &s.pl->h_ctr->pad[0], s.st, &pos))
+        return 2;
+    if (pos >= s.w.text_len)
+        return s.w.text_len - (s.own_hi - 1) > kRlMaxLine ? rl_refuse_long() : rl_refuse_cut();
+    return 0;
+}
+// The sparse road: the filter's records (its emitting launch skipped, and the scan repeated with more room, when there are more than
+// the buffer holds), then the lines that hold one.  *dense: more than one occurrence per 64 text bytes (a first value, the
+// bench tool runs both roads; force == 1: never) — nothing is set, the dense road names the lines.
+static int rl_sparse_road(RlScan &s, int force, bool *dense)
+{
+    RxLoopsWork &wk = *s.pl->rx->work;
+    const Window &w = s.w;
+    // Stage 1 looks at the BUFFER, not at the owned range: a match that starts in front of own_hi may hold its filter factor behind it,
     // and the inner plans refuse windows of their own (a filter alternation that can overlap itself).  To them the buffer is a whole
     // text with base 0, so their records are buffer-relative, as krep_gpu_matching_lines() wants them.
     const Window wb{w.d_text, w.text_len, 0, w.text_len, 0, w.text_len};
+    const u64 limit = force == 1 ? UINT64_MAX : w.text_len / 64;
+    for (;;)
+    {
+        if (rl_reserve_records(wk, std::max<u64>(wk.rec_cap, std::min<u64>(limit, w.text_len / 64) + 1)))
+            return 2;
+        krep_gpu_scan_out_t fo;
+        memset(&fo, 0, sizeof fo);
+        wk.filter->rx_emit_limit = std::min<u64>(limit, wk.rec_cap);
+        if (const int rc = scan_regex_alt(wk.filter, wb, wk.d_rec, wk.rec_cap, s.st, 0, &fo))
+            return rc;
+        if (fo.total_matches <= wk.filter->rx_emit_limit)
+        {
+            s.a.n_lines = fo.stored;
+            break;
+        }
+        if (fo.total_matches > limit)
+        {
+            *dense = true;
+            return 0;
+        }
+        if (rl_reserve_records(wk, fo.total_matches)) // (the forced sparse road on a text denser than the buffer was sized for)
+            return 2;
+    }
+    g_rl_sparse.fetch_add(1, std::memory_order_relaxed);
+    if (!s.a.n_lines)
+        return 0;
+    const u64 n_rec = s.a.n_lines;
+    HIPCHK(grow_scratch(wk.span_cap, n_rec, n_rec,
+                        {dev_buf(wk.d_spans, n_rec * sizeof(match_position_t)), dev_buf(wk.d_first, (n_rec + 1) * sizeof(uint64_t))}));
+    krep_gpu_lines_out_t lo;
+    if (krep_gpu_matching_lines(w.d_text, w.text_len, wk.d_rec, n_rec, UINT64_MAX, wk.d_spans, wk.d_first, n_rec, &lo, s.st))
+        return 2;
+    s.a.n_lines = lo.lines;
+    s.a.spans = (const u64 *)wk.d_spans;
+    return 0;
+}
+// The dense road: every line of the buffer is a candidate, the newline records of the inner single-byte plan say where they are (the
+// scan repeated with more room when there are more than the buffer holds)
+static int rl_dense_road(RlScan &s)
+{
+    RxLoopsWork &wk = *s.pl->rx->work;
+    const Window &w = s.w;
+    g_rl_dense.fetch_add(1, std::memory_order_relaxed);
+    krep_gpu_scan_out_t no;
+    for (;;)
+    {
+        if (krep_gpu_scan_device_ex(wk.newlines, w.d_text, w.text_len, 0, w.text_len, 0, w.text_len, wk.d_rec, wk.rec_cap, s.st, 0, &no))
+            return 2;
+        if (no.total_matches <= wk.rec_cap)
+            break;
+        if (rl_reserve_records(wk, no.total_matches))
+            return 2;
+    }
+    s.a.from_nl = 1;
+    s.a.spans = (const u64 *)wk.d_rec;
+    s.a.n_lines = no.total_matches + 1;
+    if (w.own_lo == 0 && s.own_hi == w.text_len)
+    { // (the owned range is the buffer: its newline count says it)
+        s.has_newline = no.total_matches != 0;
+        s.know_newline = true;
+    }
+    return 0;
+}
+// Stage 2, the walk of the candidate lines: the counting launch (under -c the only one), the two refusals it can raise, and for a
+// caller that takes records the offsets pass and the emitting launch
+static int rl_walk_passes(RlScan &s, bool lines, u64 want, match_position_t *d_pos, RlTotals *t)
+{
+    krep_gpu_plan *pl = s.pl;
+    RlArgs &a = s.a;
+    const auto launch = !pl->rx->walk.general ? rl_launch<false> : rl_launch<true>; // (the old step first: its kernels keep their place in the code object)
+    if (!lines)
+    {
+        if (post_reserve(pl->post, a.n_lines, 0))
+            return 2;
+        a.o.unitinfo = pl->post.d_unitinfo;
+        a.o.offsets = (const u64 *)pl->post.d_offsets;
+    }
+    HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), s.st));
+    HIPCHK(launch(a, lines ? kRxLines : kRxCount, pl->num_cu, s.st));
+    HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s.st));
+    HIPCHK(hipStreamSynchronize(s.st));
+    if (pl->h_ctr->overflow_units & 1ull)
+        return rl_refuse_long();
+    if (pl->h_ctr->overflow_units)
+        return rl_refuse_cut();
+    t->total = pl->h_ctr->total;
+    t->nlines = pl->h_ctr->lines;
+    t->summary = pl->h_ctr->summary;
+    if (want && t->total)
+    {
+        if (post_offsets_pass(pl->post, a.n_lines, false, pl->d_ctr, s.st))
+            return 2;
+        a.o.positions = (u64 *)d_pos;
+        a.o.pos_cap = want;
+        HIPCHK(launch(a, kRxEmit, pl->num_cu, s.st));
+        HIPCHK(hipStreamSynchronize(s.st));
+    }
+    return 0;
+}
+// -c: has_newline as a scan of the owned window reports it.  The candidate lines may not say (none that meets the range, or one that
+// covers it): then the host looks for a '\n' in the range itself
+static int rl_newline_summary(RlScan &s, unsigned long long *summary)
+{
+    if (!s.know_newline && !(*summary & kLnNl))
+    {
+        uint64_t pos = s.own_hi;
+        if (tail_find_next_newline(s.w.d_text, s.w.own_lo, s.own_hi, &s.pl->d_ctr->pad[0], &s.pl->h_ctr->pad[0], s.st, &pos))
+            return 2;
+        s.has_newline = pos < s.own_hi;
+    }
+    *summary = (*summary & ~kLnNl) | ((s.has_newline || (*summary & kLnNl)) ? kLnNl : 0ull);
+    return 0;
+}
 
-    // ---- stage 1: the candidate lines
+int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos, uint64_t cap, hipStream_t st, int time_it,
+                     krep_gpu_scan_out_t *out)
+{
+    u64 own_hi = 0;
+    bool go = false;
+    if (const int rc = rl_window(w, &own_hi, &go); rc || !go)
+        return rc;
+    if (!pl->rx->work && rl_work_create(pl))
+        return 2;
+    const bool lines = pl->lines;
+    const u64 want = (d_pos && cap && !lines && pl->track) ? std::min<u64>(pl->max_count, cap) : 0;
+    HIPCHK(hipSetDevice(pl->device));
+    if (time_it) HIPCHK(hipEventRecord(pl->ev0, st));
+    RlScan s{pl, w, st, own_hi, w.global_base + w.text_len == w.global_len, rl_args(pl, w, own_hi)};
+
+    // ---- stage 1: the candidate lines, by the sparse road unless the filter is dense (or a test forces a road)
     const int force = g_rl_force_road.load();
     bool dense = force == 2;
-    bool has_newline = false, know_newline = false;
-    if (!dense && !ends)
-    {
-        // The sparse road looks at the lines that hold a filter occurrence IN THE BUFFER.  The line the buffer's end cuts may hold its
-        // occurrence behind that end and a match that starts in the owned range all the same, so that one line is looked at here: it
-        // meets the owned range when no newline stands between the last owned byte and the buffer's end.  (A line the buffer's START
-        // cuts needs no such look: an owned match lies in the part the buffer holds, with its occurrence.)
-        uint64_t pos = w.text_len;
-        if (tail_find_next_newline(w.d_text, own_hi - 1, w.text_len, &pl->d_ctr->pad[0], &pl->h_ctr->pad[0], st, &pos))
-            return 2;
-        if (pos >= w.text_len)
-            return w.text_len - (own_hi - 1) > kRlMaxLine ? rl_refuse_long() : rl_refuse_cut();
-    }
+    if (!dense && !s.ends)
+        if (const int rc = rl_cut_line_look(s))
+            return rc;
     if (!dense)
-    {
-        // more than one occurrence per 64 text bytes (a first value, the bench tool runs both roads): the dense road
-        const u64 limit = force == 1 ? UINT64_MAX : w.text_len / 64;
-        for (;;)
-        {
-            if (rl_reserve_records(wk, std::max<u64>(wk.rec_cap, std::min<u64>(limit, w.text_len / 64) + 1)))
-                return 2;
-            krep_gpu_scan_out_t fo;
-            memset(&fo, 0, sizeof fo);
-            wk.filter->rx_emit_limit = std::min<u64>(limit, wk.rec_cap);
-            if (const int rc = scan_regex_alt(wk.filter, wb, wk.d_rec, wk.rec_cap, st, 0, &fo))
-                return rc;
-            if (fo.total_matches <= wk.filter->rx_emit_limit)
-            {
-                a.n_lines = fo.stored;
-                break;
-            }
-            if (fo.total_matches > limit)
-            {
-                dense = true;
-                break;
-            }
-            if (rl_reserve_records(wk, fo.total_matches)) // (the forced sparse road on a text denser than the buffer was sized for)
-                return 2;
-        }
-    }
-    if (!dense)
-    {
-        g_rl_sparse.fetch_add(1, std::memory_order_relaxed);
-        if (a.n_lines)
-        {
-            const u64 n_rec = a.n_lines;
-            HIPCHK(grow_scratch(wk.span_cap, n_rec, n_rec,
-                                {dev_buf(wk.d_spans, n_rec * sizeof(match_position_t)), dev_buf(wk.d_first, (n_rec + 1) * sizeof(uint64_t))}));
-            krep_gpu_lines_out_t lo;
-            if (krep_gpu_matching_lines(w.d_text, w.text_len, wk.d_rec, n_rec, UINT64_MAX, wk.d_spans, wk.d_first, n_rec, &lo, st))
-                return 2;
-            a.n_lines = lo.lines;
-            a.spans = (const u64 *)wk.d_spans;
-        }
-    }
-    else
-    {
-        g_rl_dense.fetch_add(1, std::memory_order_relaxed);
-        krep_gpu_scan_out_t no;
-        for (;;)
-        {
-            if (krep_gpu_scan_device_ex(wk.newlines, w.d_text, w.text_len, 0, w.text_len, 0, w.text_len, wk.d_rec, wk.rec_cap, st, 0, &no))
-                return 2;
-            if (no.total_matches <= wk.rec_cap)
-                break;
-            if (rl_reserve_records(wk, no.total_matches))
-                return 2;
-        }
-        a.from_nl = 1;
-        a.spans = (const u64 *)wk.d_rec;
-        a.n_lines = no.total_matches + 1;
-        if (w.own_lo == 0 && own_hi == w.text_len)
-        { // (the owned range is the buffer: its newline count says it)
-            has_newline = no.total_matches != 0;
-            know_newline = true;
-        }
-    }
+        if (const int rc = rl_sparse_road(s, force, &dense))
+            return rc;
+    if (dense && rl_dense_road(s))
+        return 2;
 
     // ---- stage 2: the walk of the candidate lines
-    uint64_t total = 0, nlines = 0;
-    unsigned long long summary = 0;
-    if (a.n_lines)
-    {
-        if (!lines)
-        {
-            if (post_reserve(pl->post, a.n_lines, 0))
-                return 2;
-            a.o.unitinfo = pl->post.d_unitinfo;
-            a.o.offsets = (const u64 *)pl->post.d_offsets;
-        }
-        HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), st));
-        HIPCHK(launch(a, lines ? kRxLines : kRxCount, pl->num_cu, st));
-        HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (pl->h_ctr->overflow_units & 1ull)
-            return rl_refuse_long();
-        if (pl->h_ctr->overflow_units)
-            return rl_refuse_cut();
-        total = pl->h_ctr->total;
-        nlines = pl->h_ctr->lines;
-        summary = pl->h_ctr->summary;
-        if (want && total)
-        {
-            if (post_offsets_pass(pl->post, a.n_lines, false, pl->d_ctr, st))
-                return 2;
-            a.o.positions = (u64 *)d_pos;
-            a.o.pos_cap = want;
-            HIPCHK(launch(a, kRxEmit, pl->num_cu, st));
-            HIPCHK(hipStreamSynchronize(st));
-        }
-    }
-    if (lines)
-    {
-        // has_newline as a scan of the owned window reports it: the candidate lines may not say (none that meets it, or one that
-        // covers it)
-        if (!know_newline && !(summary & kLnNl))
-        {
-            uint64_t pos = own_hi;
-            if (tail_find_next_newline(w.d_text, w.own_lo, own_hi, &pl->d_ctr->pad[0], &pl->h_ctr->pad[0], st, &pos))
-                return 2;
-            has_newline = pos < own_hi;
-        }
-        summary = (summary & ~kLnNl) | ((has_newline || (summary & kLnNl)) ? kLnNl : 0ull);
-    }
-    else
-        summary = total ? (kLnHead | kLnTail) : 0;
+    RlTotals t;
+    if (s.a.n_lines)
+        if (const int rc = rl_walk_passes(s, lines, want, d_pos, &t))
+            return rc;
+    if (!lines)
+        t.summary = t.total ? (kLnHead | kLnTail) : 0;
+    else if (rl_newline_summary(s, &t.summary))
+        return 2;
     if (time_it && stop_clock(pl, true, st, out))
         return 2;
-    rx_fill_out(pl, lines, total, nlines, summary, d_pos, cap, want, out);
+    rx_fill_out(pl, lines, t.total, t.nlines, t.summary, d_pos, cap, want, out);
     return 0;
 }
 } // namespace kg
-
-extern "C" int krep_gpu_regex_compile_groups(const search_params_t *params, krep_gpu_regex_groups_t *out)
-{
-    krep_gpu_clear_error();
-    if (const char *why = kg::regex_compile_groups(params, out))
-        return kg::fail("%s", why);
-    return 0;
-}
-extern "C" int krep_gpu_regex_compile_loops(const search_params_t *params, krep_gpu_regex_loops_t *out)
-{
-    krep_gpu_clear_error();
-    if (const char *why = kg::regex_compile_loops(params, out))
-        return kg::fail("%s", why);
-    return 0;
-}

@@ -656,10 +656,10 @@ int split_mode(const search_params_t *p, const krep_gpu_config_t &c, size_t text
         RegexCompiled rc;
         if (regex_compile_cached(p, &rc))
             return kSplitWhole;
-        if (rc.is_loops) // a match lies inside one line of at most 4096 bytes: pieces with that much context on both sides, once
+        if (rc.line_walked()) // a match lies inside one line of at most 4096 bytes: pieces with that much context on both sides, once
                          // krep_gpu_set_regex_loops_windows() says so; else one window over the whole text (kg_regex_loops.hip)
             return g_regex_loops_windows.load(std::memory_order_relaxed) ? kSplitPieces : kSplitWhole;
-        return (rc.is_alt ? rc.alt.cross_overlap : rc.seq.seq.self_overlap) && !p->count_lines_mode ? kSplitWhole : kSplitPieces;
+        return rc.overlaps() && !p->count_lines_mode ? kSplitWhole : kSplitPieces;
     }
     if (p->num_patterns > 1)
     {

@@ -1,8 +1,10 @@
 """The -E compilers answer as they did before their rules were folded into one copy each (host only): tools/regex_compile_san.cpp
---digest asks the four compilers and regex_compile_search about a fixed corpus and prints one FNV-1a digest per 1000 entries of
+--digest asks the compilers and regex_compile_search about a fixed corpus and prints one FNV-1a digest per 1000 entries of
 their answers (taken or refused, every byte of a taken struct, the reason of a refusal); tests/golden/regex_compile_digest.json is
-what the compilers of the commit before said (the tool's head names the command that reproduces it).  Here: every named table and
-the first 20 blocks of each random corpus; `python tools/sanitize.py regex` compares the whole corpus."""
+what the compilers of the commit before said (the tool's head names the command that reproduces it).  The rows without a dot are the
+four older compilers'; loops.*, groups.*, search10.*, search01.*, search11.* and walk.* are the loops and the groups compiler, the
+search order with their switches on, and the line walk program of everything they take.  Here: every named table and the first 20
+blocks of each random corpus; `python tools/sanitize.py regex` compares the whole corpus."""
 import json
 import os
 import subprocess
@@ -11,6 +13,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BLOCKS = 20
+NEW_ROWS = ("loops", "groups", "search10", "search01", "search11", "walk")
 
 
 def parse(out):
@@ -49,3 +52,17 @@ def test_the_first_blocks_of_a_random_corpus(have, golden, corpus):
     assert len(have[corpus]) == BLOCKS
     for k, (h, want) in enumerate(zip(have[corpus], golden[corpus])):
         assert h == want, "block %d of the random corpus '%s' (draws %d..%d)" % (k, corpus, 1000 * k, 1000 * k + 999)
+
+
+@pytest.mark.parametrize("row", NEW_ROWS)
+def test_the_named_tables_through_the_loops_and_the_groups_compiler(have, golden, row):
+    assert len(golden[row + ".named"]) == 1 and have[row + ".named"] == golden[row + ".named"]
+
+
+@pytest.mark.parametrize("corpus", ["bytes", "pieces", "quants"])
+@pytest.mark.parametrize("row", NEW_ROWS)
+def test_the_first_blocks_of_a_random_corpus_through_the_loops_and_the_groups_compiler(have, golden, row, corpus):
+    name = row + "." + corpus
+    assert len(have[name]) == BLOCKS and len(golden[name]) >= BLOCKS
+    for k, (h, want) in enumerate(zip(have[name], golden[name])):
+        assert h == want, "block %d of the random corpus '%s', row '%s' (draws %d..%d)" % (k, corpus, row, 1000 * k, 1000 * k + 999)

@@ -5,16 +5,26 @@
 // grammar cares about (^ $ | ( ) among them), each copied into a heap block of exactly its length so that a read past the pattern is a report.
 //
 //   regex_compile_san --digest [--blocks N]
-// instead walks a fixed corpus (every table below and both random generators), asks the four compilers and regex_compile_search about
+// instead walks a fixed corpus (every table below and the random generators), asks the compilers and regex_compile_search about
 // every entry and prints 64-bit FNV-1a digests of their answers, one per 1000 entries: tests/golden/regex_compile_digest.json holds
-// what the compilers said before their rules were folded into one copy each (tests/test_regex_compile_digest_cpu.py).  That recording
-// is reproduced from the commit before (a9eb3ca, whose kg_mirror.hip held regex_compile_search as regex_compile_both) with
-//   git show a9eb3ca:krep_amd/csrc/kg_regex_compile.h > krep_amd/csrc/kg_regex_compile_parent.h
+// what the compilers said before their rules were folded into one copy each (tests/test_regex_compile_digest_cpu.py).  The rows:
+//   classes, named, bytes, pieces: the four older compilers and regex_compile_search with both switches off;
+//   loops.*, groups.*: krep_gpu_regex_compile_loops' and _groups' compilers (every byte of a taken struct, the reason of a refusal);
+//   search10.*, search01.*, search11.*: regex_compile_search with the loops switch, the groups switch and both on (who took it, ^, $,
+//     the reason), read through verdict_of(), the one place here that knows how RegexCompiled is laid out;
+//   walk.*: for every entry the loops or the groups compiler takes, the program the line walk kernel receives (kg::RegexWalk), and for
+//     a loops program also what krep_gpu_debug_force_regex_general makes of it;
+// each over .named (the tables), .bytes, .pieces and .quants (the three generators).  --digest exits non-zero when the corpus does not
+// reach every refusal of the loops and the groups compiler, 1000 taken entries of each, a walk program of more than 8 jump pairs and
+// one of none.  The recording is reproduced from commit e0710b6, the last one whose line walk program had no type of its own (its
+// kg_regex.hip assembled the fields in regex_prog_create; KG_REGEX_PARENT holds that code), with
+//   git show e0710b6:krep_amd/csrc/kg_regex_compile.h > krep_amd/csrc/kg_regex_compile_parent.h
 //   g++ -std=c++17 -O2 -DKG_REGEX_PARENT -DKG_REGEX_HEADER='"../krep_amd/csrc/kg_regex_compile_parent.h"' tools/regex_compile_san.cpp -o digest_parent
 //   ./digest_parent --digest
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -23,44 +33,90 @@
 #endif
 #include KG_REGEX_HEADER
 
-#ifdef KG_REGEX_PARENT // that commit's header ends with the four compilers: the order every search asks them in, as its kg_mirror.hip had it
-namespace kg {
-struct RegexCompiled
+// what regex_compile_search said about a taken search: who took it (0 the anchored compiler, 1 the alternation or the expanding one,
+// 2 the loops compiler, 3 the groups compiler), the line anchors, and the struct of the two older kinds
+struct Verdict
 {
-    bool is_alt = false;
-    krep_gpu_regex_anchored_t seq{};
-    krep_gpu_regex_alt_t alt{};
-    int alt_bol = 0, alt_eol = 0;
+    int took, bol, eol;
+    const krep_gpu_regex_anchored_t *seq;
+    const krep_gpu_regex_alt_t *alt;
 };
-static const char *regex_compile_search(const search_params_t *p, RegexCompiled *out)
+#ifdef KG_REGEX_PARENT // that commit: RegexCompiled is four flags beside every compiler's struct, and the walk program is RegexProg's fields
+static Verdict verdict_of(const kg::RegexCompiled &rc)
 {
-    out->is_alt = false;
-    out->alt_bol = out->alt_eol = 0;
-    const char *why = regex_compile_anchored(p, &out->seq);
-    if (!why)
-        return nullptr;
-    if (!p || !p->use_regex)
-        return why;
-    const char *why_alt = regex_compile_alt(p, &out->alt);
-    if (!why_alt)
-    {
-        out->is_alt = true;
-        return nullptr;
-    }
-    krep_gpu_regex_ext_t ext;
-    const char *why_ext = regex_compile_ext(p, &ext);
-    if (!why_ext)
-    {
-        out->is_alt = true;
-        out->alt = ext.alt;
-        out->alt_bol = ext.bol;
-        out->alt_eol = ext.eol;
-        return nullptr;
-    }
-    const char *before = regex_has_alt_syntax(p) ? why_alt : why;
-    return regex_ext_own_limit(why_ext) && !strstr(before, "more than") ? why_ext : before;
+    if (rc.is_loops)
+        return Verdict{rc.is_groups ? 3 : 2, rc.loops.bol, rc.loops.eol, nullptr, nullptr};
+    if (rc.is_alt)
+        return Verdict{1, rc.alt_bol, rc.alt_eol, nullptr, &rc.alt};
+    return Verdict{0, rc.seq.bol, rc.seq.eol, &rc.seq, nullptr};
 }
-} // namespace kg
+struct Walk
+{
+    uint32_t table[256];
+    uint32_t init, fin, self;
+    bool general;
+    uint32_t chain, n_jumps, jump_src[12], jump_dst[12];
+    int bol, eol;
+    krep_gpu_regex_alt_t filter;
+};
+static Walk walk_of_loops(const krep_gpu_regex_loops_t &l)
+{
+    Walk w;
+    memset(&w, 0, sizeof w);
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < l.alt.n_branches; ++i)
+    {
+        const krep_gpu_regex_info_t &br = l.alt.branch[i];
+        w.init |= 1u << o;
+        w.fin |= 1u << (o + br.L - 1);
+        for (int b = 0; b < 256; ++b)
+            for (uint32_t j = 0; j < br.L; ++j)
+                w.table[b] |= ((br.classes[j][b >> 3] >> (b & 7)) & 1u) << (o + j);
+        w.self |= (uint32_t)l.repeat[i] << o;
+        o += br.L;
+    }
+    w.bol = l.bol;
+    w.eol = l.eol;
+    w.filter = l.filter;
+    return w;
+}
+static Walk walk_forced_general(const krep_gpu_regex_loops_t &l)
+{
+    Walk w = walk_of_loops(l);
+    const uint32_t o = l.alt.total_L;
+    w.general = true;
+    w.chain = (o >= 32u ? ~0u : (1u << o) - 1u) & ~w.fin;
+    return w;
+}
+static Walk walk_of_groups(const krep_gpu_regex_groups_t &g)
+{
+    Walk w;
+    memset(&w, 0, sizeof w);
+    w.general = true;
+    for (int b = 0; b < 256; ++b)
+        for (uint32_t i = 0; i < g.n_pos; ++i)
+            w.table[b] |= ((g.classes[i][b >> 3] >> (b & 7)) & 1u) << i;
+    w.init = g.first;
+    w.fin = g.last;
+    w.n_jumps = kg::regex_groups_jumps(g, &w.chain, &w.self, w.jump_src, w.jump_dst, kg::kRegexGroupsMaxJumps);
+    w.bol = g.bol;
+    w.eol = g.eol;
+    w.filter = g.filter;
+    return w;
+}
+#else
+static Verdict verdict_of(const kg::RegexCompiled &rc)
+{
+    if (rc.kind == kg::RegexCompiled::kWalk)
+        return Verdict{rc.walk.general ? 3 : 2, rc.walk.bol, rc.walk.eol, nullptr, nullptr};
+    if (rc.kind == kg::RegexCompiled::kAlt)
+        return Verdict{1, rc.alt_bol, rc.alt_eol, nullptr, &rc.alt};
+    return Verdict{0, rc.seq.bol, rc.seq.eol, &rc.seq, nullptr};
+}
+typedef kg::RegexWalk Walk;
+static Walk walk_of_loops(const krep_gpu_regex_loops_t &l) { return kg::regex_walk_of_loops(l); }
+static Walk walk_of_groups(const krep_gpu_regex_groups_t &g) { return kg::regex_walk_of_groups(g); }
+static Walk walk_forced_general(const krep_gpu_regex_loops_t &l) { return kg::regex_walk_as_general(kg::regex_walk_of_loops(l)); }
 #endif
 
 // a search over `pats`, each in a heap block of exactly its length: no terminator to lean on
@@ -185,6 +241,30 @@ static const std::vector<std::string> py_cases[] = {
     {"^(a{15}|b{15}|c)"},
     // and what the default run asks beside its tables
     {"a", ""}, {"a", "b*"}, {std::string(1100, 'a') + "|b"}, {"a?b", ""}, {std::string(1100, 'a') + "?b"}};
+// the rows of the loops and the groups compiler alone (loops.*, groups.*, search??.*, walk.*): ACCEPTED and REFUSALS of
+// tests/test_regex_loops_compile_cpu.py with what its other tests name ...
+static const std::vector<std::string> loops_cases[] = {
+    {"ERROR.*timeout"}, {"a+b"}, {"[0-9]+"}, {"ab+c"}, {"ab+cd"}, {"a{2,}b"}, {"a{1,}b"}, {"a{3,}"}, {"a*b"}, {"a{0,}b"}, {"colou*r"}, {"^#+ "}, {"b+$"},
+    {"^a+$"}, {"x(a+|b)y"}, {"[a-z]+@[a-z]+\\.com"}, {"[0-9]+\\.[0-9]+"}, {"a+", "b+c"}, {"a+b|ab"}, {"(a+b){2}"}, {"[ab]+c?"}, {"^(GET|POST) .+"},
+    {"(ab)+"}, {"(a|b)*c"}, {"x(ab){2,}"}, {"(a+)+"}, {"[[:space:]]+x"}, {"a\n+"}, {"a+[b\n]"}, {"a+[[:cntrl:]]"}, {"a*"}, {"a*b*"}, {"x|a*"}, {"^a*$"},
+    {"(a|b*)"}, {"colou?r"}, {"ab"}, {"^(ERROR|WARN)"}, {"a{2,3}"}, {"a+*"}, {"a*?"}, {"a+{2}"}, {"a{2,}?"}, {"x((a+))"}, {"x(a+"}, {"a+)b"}, {"(a+|)b"},
+    {"a+|"}, {"x(^a+|b)"}, {"a+^b"}, {"^a+|b"}, {"+a"}, {"a|*b"}, {"^+a"}, {"^*"}, {"a{17,}"}, {"^a{16,}"}, {"a{9}b+a{7}"}, {"[ab]{1,9}c+"}, {"a*b*c*d*e"},
+    {"a{16}|b{16,}|c"}, {"a{2,"}, {"a{,2}"}, {"a{1001,}"}, {"caf\xe9+"}, {"a\\b+"}, {"[ab+"}, {"ab+\\"}, {"a+", "^b"}, {"a.*b"}, {"a(b|c)+"}};
+// ... the named expressions, REFUSALS and the limits of tests/test_regex_groups_compile_cpu.py ...
+static const std::string kAz = "abcdefghijklmnopqrstuvwxyz", kIp = "[0-9]{1,3}\\.[0-9]{1,3}\\.[0-9]{1,3}\\.[0-9]{1,3}";
+static const std::vector<std::string> groups_cases[] = {
+    {"(ab)+"}, {"(a|b)*c"}, {"(a|bc)+d"}, {"((ab)+c)+d"}, {"(a|ab)(c|bcd)"}, {"(a|ab|abc)+c"}, {"x(ab|a)*bc"}, {"(a+|b)+c"}, {"((a|b)c|d)+e"}, {"(ab){2,}"},
+    {"(foo|bar){2,3};"}, {"([a-z]+\\.)+com"}, {"^(ab)+"}, {"(ab)+$"}, {"^((GET|POST) |HEAD )/api"}, {"(a|b)(c|d)(e|f)(g|h)"}, {kIp}, {"(ab)+", "c(d|e)*f"},
+    {"(ab)+[[:space:]]"}, {"(a\n)+"}, {"(ab)*"}, {"(a|b*)+"}, {"(ab)+|c*"}, {"(ab|)+"}, {"()+a"}, {"(ab)+|"}, {"(ab)+?"}, {"(ab){2}{3}"}, {"(+ab)+"}, {"*(ab)+"},
+    {"(ab){0}c"}, {"(ab)+c{0,0}"}, {"(^ab)+"}, {"(ab$)+"}, {"(ab)+^c"}, {"(ab)+$c"}, {"^(ab)+|c"}, {"(ab)+$|(cd)+"}, {"(abcdefghijkabcdefghijkabcdefghijk)+"},
+    {"(ab){17}"}, {"(ab){1000,}"}, {"(((((((((a)))))))))+"}, {"(a|b)(c|d)(e|f)(g|h)(i|j)(k|l)(m|n)(o|p)"}, {"(ab)+(c"}, {"(ab)+)"}, {"((ab)+"}, {"(ab){2,"},
+    {"(ab){,2}"}, {"(ab){3,2}"}, {"(caf\xe9)+"}, {"(a\\b)+"}, {"([ab)+"}, {"(ab)+\\"}, {"(ab)+", "^(cd)+"}, {"^ab[0-9]$"}, {"ab|cd"}, {"ab", "cd"}, {"colou?r"},
+    {"a+b"}, {"x(a+|b)y"}, {"ERROR.*timeout"}, {"(" + kAz + kAz.substr(0, 6) + ")+"}, {"(" + kAz + kAz.substr(0, 7) + ")+"},
+    {kAz.substr(0, 12) + "(" + kAz.substr(0, 20) + ")+"}, {"((((((((ab))))))))+"}, {"(((((((((ab)))))))))+"}, {"(a|b)(c|d)(e|f)(g|h)(i|j)(k|l)(m|n)"},
+    {"(ab){1,2}(c)+"}, {"(a|b|c|d|e|f|g|h|i)(xy)*"}, {"(a|b|c|d|e|f|g|h)(xy)*"}, {"((ab)+c)+d"}, {"a*"}, {"a.*b"}};
+// ... and the quantifier traps: the expanding compiler says "without a bound" before it judges a range, the groups compiler has no such stage
+static const char *quant_traps[] = {"a*{2}", "a{2000,}", "a{2,}{3}", "a{,}", "a{2,", "a{0}", "a{0,0}", "a{0,}", "a{3,2}", "a{1001}", "(ab){2000,}", "(ab)+?", "^*a"};
+
 
 // ---- the two random corpora: pattern strings over the bytes the grammar looks at, and strings of the expanding compiler's grammar
 struct Rng
@@ -221,6 +301,45 @@ static void draw_pieces(Rng &r, std::vector<std::string> &pats)
     }
 }
 constexpr int kDraws = 200000;
+// the third random corpus (new rows only): expressions around the quantifiers and the groups, of the bytes * + { } , ( ) | most of all
+static void draw_quants(Rng &r, std::vector<std::string> &pats)
+{
+    static const char *atoms[] = {"a", "b", "c", "[ab]", ".", "\\.", "[0-9]"};
+    static const char *quants[] = {"", "", "", "*", "+", "?", "{2}", "{2,}", "{1,3}", "{0,}", "{0}", "{,2}", "{3,2}", "{1001}", "{2", "+?", "*{2}", "{2,}{3}"};
+    static const char *noise[] = {"(", ")", "|", "^", "$", "{", "}", ",", "*", "+", "\n", "()"};
+    const auto pick = [&](const char *const *v, size_t n) { return std::string(v[r.next() % n]); };
+    pats.assign(1, std::string());
+    const int items = 1 + (int)(r.next() % 5);
+    for (int k = 0; k < items; ++k)
+    {
+        std::string &s = pats.back();
+        const unsigned what = (unsigned)(r.next() % 16);
+        if (what < 7)
+            s += pick(atoms, 7) + pick(quants, 18);
+        else if (what < 13)
+        { // a group of one to three alternatives of one to three atoms, one level of nesting now and then
+            std::string g;
+            const int alts = 1 + (int)(r.next() % 3);
+            for (int a = 0; a < alts; ++a)
+            {
+                g += a ? "|" : "";
+                const int len = 1 + (int)(r.next() % 3);
+                for (int t = 0; t < len; ++t)
+                    g += r.next() % 7 == 0 ? "(" + pick(atoms, 7) + pick(atoms, 7) + ")" + pick(quants, 18) : pick(atoms, 7) + pick(quants, 8);
+            }
+            s += "(" + g + ")" + pick(quants, 18);
+        }
+        else if (what < 14)
+            s += pick(noise, 12);
+        else if (what < 15)
+            s += k ? "|" : "^";
+        else
+            pats.emplace_back(); // several patterns every now and then
+    }
+    if (pats.back().empty() && pats.size() > 1)
+        pats.pop_back();
+}
+constexpr int kQuantDraws = 50000;
 
 // ---- --digest
 struct Fnv
@@ -243,6 +362,36 @@ struct Fnv
             bytes(taken, n);
     }
 };
+// the new rows of one block, and what the corpus has reached so far
+static const char *const kRowNames[6] = {"loops", "groups", "search10", "search01", "search11", "walk"};
+struct Rows
+{
+    Fnv f[6];
+    void print(const char *corpus, int k) const
+    {
+        for (int i = 0; i < 6; ++i)
+            printf("%s.%s %d %016llx\n", kRowNames[i], corpus, k, (unsigned long long)f[i].h);
+    }
+};
+static struct
+{
+    unsigned loops_taken = 0, groups_taken = 0, many_jumps = 0, no_jumps = 0;
+    std::set<const char *> reasons;
+} g_reached;
+static void digest_walk(Fnv &f, const Walk &w)
+{
+    const uint8_t general = w.general ? 1 : 0;
+    const int32_t anchors[2] = {w.bol, w.eol};
+    f.bytes(w.table, sizeof w.table);
+    f.bytes(&w.init, 4), f.bytes(&w.fin, 4), f.bytes(&w.self, 4);
+    f.byte(general);
+    f.bytes(&w.chain, 4), f.bytes(&w.n_jumps, 4);
+    f.bytes(w.jump_src, sizeof w.jump_src), f.bytes(w.jump_dst, sizeof w.jump_dst);
+    f.bytes(anchors, sizeof anchors);
+    f.bytes(&w.filter, sizeof w.filter);
+    g_reached.many_jumps += w.n_jumps > 8;
+    g_reached.no_jumps += w.n_jumps == 0;
+}
 // the four compilers and the combined decision about one search
 static void digest_search(Fnv &f, const search_params_t *p)
 {
@@ -256,19 +405,81 @@ static void digest_search(Fnv &f, const search_params_t *p)
     f.answer(3, kg::regex_compile_alt(p, &alt), &alt, sizeof alt);
     f.answer(4, kg::regex_compile_ext(p, &ext), &ext, sizeof ext);
     const char *why = kg::regex_compile_search(p, &rc);
-    const int32_t head[3] = {rc.is_alt, rc.alt_bol, rc.alt_eol};
+    const Verdict v = why ? Verdict{} : verdict_of(rc);
+    const int32_t head[3] = {v.took == 1, v.took == 1 ? v.bol : 0, v.took == 1 ? v.eol : 0};
     f.answer(5, why, head, sizeof head);
     if (!why)
-        rc.is_alt ? f.bytes(&rc.alt, sizeof rc.alt) : f.bytes(&rc.seq, sizeof rc.seq);
+        v.took == 1 ? f.bytes(v.alt, sizeof *v.alt) : f.bytes(v.seq, sizeof *v.seq);
 }
-static void digest_entry(Fnv &f, const std::vector<std::string> &pats, bool cs, bool ww = false)
+// the loops and the groups compiler, the combined decision with their switches on, and the walk program of what they take
+static void digest_search_new(Rows &R, const search_params_t *p)
+{
+    krep_gpu_regex_loops_t loops;
+    krep_gpu_regex_groups_t groups;
+    const char *why_loops = kg::regex_compile_loops(p, &loops), *why_groups = kg::regex_compile_groups(p, &groups);
+    R.f[0].answer(6, why_loops, &loops, sizeof loops);
+    R.f[1].answer(7, why_groups, &groups, sizeof groups);
+    g_reached.reasons.insert(why_loops);
+    g_reached.reasons.insert(why_groups);
+    for (int k = 0; k < 3; ++k)
+    {
+        kg::RegexCompiled rc;
+        const char *why = kg::regex_compile_search(p, &rc, k != 1, k != 0);
+        const Verdict v = why ? Verdict{} : verdict_of(rc);
+        const int32_t head[3] = {v.took, v.bol, v.eol};
+        R.f[2 + k].answer((uint8_t)(8 + k), why, head, sizeof head);
+    }
+    if (!why_loops)
+    {
+        ++g_reached.loops_taken;
+        digest_walk(R.f[5], walk_of_loops(loops));
+        digest_walk(R.f[5], walk_forced_general(loops));
+    }
+    if (!why_groups)
+    {
+        ++g_reached.groups_taken;
+        digest_walk(R.f[5], walk_of_groups(groups));
+    }
+}
+struct Digest
+{
+    Fnv f;  // the rows of the four older compilers
+    Rows r;
+};
+static void digest_entry(Digest &d, const std::vector<std::string> &pats, bool cs, bool ww = false, bool old_rows = true)
 {
     Search s(pats, cs, ww);
-    digest_search(f, &s.p);
+    if (old_rows)
+        digest_search(d.f, &s.p);
+    digest_search_new(d.r, &s.p);
+}
+// did the whole corpus reach what the new rows are there to pin
+static int check_reached()
+{
+    const char *const reasons[] = {kg::kRegexLoopsGroup, kg::kRegexLoopsEmpty, kg::kRegexLoopsNewline, kg::kRegexLoopsNone, kg::kRegexGroupsOlder,
+                                   kg::kRegexGroupsNewline, kg::kRegexGroupsNullable, kg::kRegexGroupsEmptyAlt, kg::kRegexGroupsQuantQuant,
+                                   kg::kRegexGroupsQuantNothing, kg::kRegexGroupsZero, kg::kRegexGroupsAnchor, kg::kRegexGroupsMixedAnchors,
+                                   kg::kRegexGroupsTooManyPos, kg::kRegexGroupsTooDeep, kg::kRegexGroupsTooManyJumps, kg::kRegexGroupsNoFilter};
+    int bad = 0;
+    for (const char *why : reasons)
+        if (!g_reached.reasons.count(why))
+        {
+            fprintf(stderr, "regex_compile_san --digest: the corpus never reaches the refusal \"%s\"\n", why);
+            ++bad;
+        }
+    if (g_reached.loops_taken < 1000 || g_reached.groups_taken < 1000 || !g_reached.many_jumps || !g_reached.no_jumps)
+    {
+        fprintf(stderr, "regex_compile_san --digest: the loops compiler takes %u entries, the groups compiler %u (1000 each are wanted); %u walk "
+                        "programs of more than 8 jump pairs, %u of none\n",
+                g_reached.loops_taken, g_reached.groups_taken, g_reached.many_jumps, g_reached.no_jumps);
+        ++bad;
+    }
+    return bad ? 1 : 0;
 }
 static int run_digest(int blocks)
 {
-    Fnv f;
+    Digest d;
+    Fnv &f = d.f;
     const char *probe[] = {".", "[^a]", "[[:space:]]", "[[:alpha:]]", "[[:punct:]]", "a", "\\.", "[a-]"};
     for (const char *a : probe)
         for (int cs = 1; cs >= 0; --cs)
@@ -282,37 +493,39 @@ static int run_digest(int blocks)
     f = Fnv();
     for (const char *s : ok)
         for (int cs = 0; cs < 2; ++cs)
-            digest_entry(f, {s}, cs != 0);
+            digest_entry(d, {s}, cs != 0);
     for (const char *s : no)
-        digest_entry(f, {s}, true);
+        digest_entry(d, {s}, true);
     for (const auto &c : aok)
         for (int cs = 0; cs < 2; ++cs)
-            digest_entry(f, {c.pat}, cs != 0);
+            digest_entry(d, {c.pat}, cs != 0);
     for (const char *s : ano)
-        digest_entry(f, {s}, true);
+        digest_entry(d, {s}, true);
     for (const auto &c : alt_ok)
         for (int cs = 0; cs < 2; ++cs)
-            digest_entry(f, c.pats, cs != 0);
+            digest_entry(d, c.pats, cs != 0);
     for (const char *s : alt_no)
-        digest_entry(f, {s}, true);
+        digest_entry(d, {s}, true);
     for (const auto &c : ext_ok)
         for (int cs = 0; cs < 2; ++cs)
-            digest_entry(f, c.pats, cs != 0);
+            digest_entry(d, c.pats, cs != 0);
     for (const char *s : ext_no)
-        digest_entry(f, {s}, true);
+        digest_entry(d, {s}, true);
     for (const auto &pats : py_cases)
-        digest_entry(f, pats, true);
-    digest_entry(f, {"ab"}, true, true); // -w
+        digest_entry(d, pats, true);
+    digest_entry(d, {"ab"}, true, true); // -w
     {
         Search s({"ab"}, true, false); // not a regex search
         s.p.use_regex = false;
         digest_search(f, &s.p);
+        digest_search_new(d.r, &s.p);
     }
     {
         Search s({"a", "b"}, true, false); // several patterns announced, the arrays NULL
         s.p.patterns = nullptr;
         s.p.pattern_lens = nullptr;
         digest_search(f, &s.p);
+        digest_search_new(d.r, &s.p);
     }
     {
         Search s({"a"}, true, false); // no pattern at all
@@ -321,39 +534,70 @@ static int run_digest(int blocks)
         s.p.pattern_lens = nullptr;
         s.p.num_patterns = 0;
         digest_search(f, &s.p);
+        digest_search_new(d.r, &s.p);
     }
     printf("named 0 %016llx\n", (unsigned long long)f.h);
-    // the random corpora: the generator always runs through (the second corpus continues the first one's state), the compilers are asked
-    // in the first `blocks` blocks of each
+    // the tables of the new rows alone, in both case modes (the traps: every compiler, whichever switch is on)
+    for (int cs = 1; cs >= 0; --cs)
+    {
+        for (const auto &pats : loops_cases)
+            digest_entry(d, pats, cs != 0, false, false);
+        for (const auto &pats : groups_cases)
+            digest_entry(d, pats, cs != 0, false, false);
+        for (const char *s : quant_traps)
+            digest_entry(d, {s}, cs != 0, false, false);
+    }
+    digest_entry(d, {"a+b"}, true, true, false);   // -w
+    digest_entry(d, {"(ab)+"}, true, true, false);
+    d.r.print("named", 0);
+    // the random corpora: the generator always runs through (each corpus continues the state of the one before), the compilers are
+    // asked in the first `blocks` blocks of each
     Rng r;
     std::string pat;
     std::vector<std::string> pats;
     for (int i = 0; i < kDraws; ++i)
     {
         if (i % 1000 == 0)
-            f = Fnv();
+            d = Digest();
         draw_bytes(r, pat, pats);
         if (i / 1000 >= blocks)
             continue;
         const bool cs = (r.s >> 40) & 1;
-        digest_entry(f, {pat}, cs);
+        digest_entry(d, {pat}, cs);
         if (pats.size() > 1)
-            digest_entry(f, pats, cs);
+            digest_entry(d, pats, cs);
         if (i % 1000 == 999)
+        {
             printf("bytes %d %016llx\n", i / 1000, (unsigned long long)f.h);
+            d.r.print("bytes", i / 1000);
+        }
     }
     for (int i = 0; i < kDraws; ++i)
     {
         if (i % 1000 == 0)
-            f = Fnv();
+            d = Digest();
         draw_pieces(r, pats);
         if (i / 1000 >= blocks)
             continue;
-        digest_entry(f, pats, (r.s >> 40) & 1);
+        digest_entry(d, pats, (r.s >> 40) & 1);
         if (i % 1000 == 999)
+        {
             printf("pieces %d %016llx\n", i / 1000, (unsigned long long)f.h);
+            d.r.print("pieces", i / 1000);
+        }
     }
-    return 0;
+    for (int i = 0; i < kQuantDraws; ++i)
+    {
+        if (i % 1000 == 0)
+            d = Digest();
+        draw_quants(r, pats);
+        if (i / 1000 >= blocks)
+            continue;
+        digest_entry(d, pats, (r.s >> 40) & 1, false, false);
+        if (i % 1000 == 999)
+            d.r.print("quants", i / 1000);
+    }
+    return blocks >= kDraws / 1000 ? check_reached() : 0; // (a part of the corpus need not reach everything)
 }
 
 int main(int argc, char **argv)
