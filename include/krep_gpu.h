@@ -459,6 +459,17 @@ int krep_gpu_regex_compile_ext(const search_params_t *params, krep_gpu_regex_ext
  * Long lines: a lane of the device walks one line, and its worst case is quadratic in the line's length (a.*b on a line of a's).  A
  *   candidate line of more than 4096 bytes is not walked: the scan returns 2 ("a line of more than 4096 bytes") with nothing
  *   written, and the operator takes the road of every run-time failure (the registered CPU function, or KREP_GPU_FAILED).
+ *   krep_gpu_set_regex_long_lines(1) (process-wide, off unless $KREP_GPU_REGEX_LONG_LINES=1 is set when the library is loaded; it
+ *   matters only to a search this compiler or the groups compiler took) lifts that rule for the scan of the WHOLE text in one
+ *   window, batch packs included: a candidate line of more than 4096 bytes is walked by one lane in two linear passes, a backward
+ *   pass that marks in one 32-bit word per line byte the places that still reach a match's end from there and the forward
+ *   leftmost-longest walk pruned by those words — about three steps per byte whatever the expression, the same records and counts.
+ *   The words live in device scratch the plan keeps, at most 256 MiB of them (64 Mi line bytes) plus one line; when a text's long
+ *   candidate lines need more they are walked in rounds.  The rule that stays: one line of more than 1 MiB (min(1 MiB, budget / 4))
+ *   returns 2 with the same sentence and that number in it.  Any other window keeps the 4096-byte rule and its two refusals whatever
+ *   krep_gpu_set_regex_loops_windows() says — the 4096 bytes of context rest on it —, so the sharded and the streaming executor
+ *   and the pieces drivers do too.  The switch changes nothing in krep_gpu_can_accelerate(), krep_gpu_split_mode() or the plan's
+ *   longest match (4097 for such a search).  Off, every call answers and reports as if it did not exist.
  * The switch.  krep_gpu_regex_compile_loops() always works.  Whether a SEARCH asks it, last, after the three older compilers have
  *   refused, is decided by krep_gpu_set_regex_loops(): process-wide, off unless $KREP_GPU_REGEX_LOOPS=1 is set when the library is
  *   loaded.  Off, every call behaves and reports as if this compiler did not exist.  On, krep_gpu_can_accelerate(), the selector, the
@@ -481,6 +492,9 @@ int krep_gpu_get_regex_loops(void);
  * krep_gpu_set_regex_loops() off, every call answers as if this switch did not exist. */
 void krep_gpu_set_regex_loops_windows(int on);
 int krep_gpu_get_regex_loops_windows(void);
+/* Lines of more than 4096 bytes of such a search ("Long lines" above): process-wide; default 0, or $KREP_GPU_REGEX_LONG_LINES at load */
+void krep_gpu_set_regex_long_lines(int on);
+int krep_gpu_get_regex_long_lines(void);
 
 /* ---- repeated and nested groups: (ab)+, (foo|bar)+;, ([a-z]+\.)+com, ((GET|POST) |HEAD )/api, [0-9]{1,3}\.[0-9]{1,3}\.… ----
  * The four compilers above expand an expression into at most 8 flat sequences.  This one does not expand: it holds the expression

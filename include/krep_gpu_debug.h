@@ -89,6 +89,11 @@ void krep_gpu_debug_force_regex_general(int on);
  * the general step from one by the old step */
 uint64_t krep_gpu_debug_regex_general_walks(void);
 void krep_gpu_debug_regex_loops_roads(uint64_t *sparse, uint64_t *dense);
+/* test hooks of the long-line walk (kg_regex_loops.hip, krep_gpu_set_regex_long_lines): the bytes of scratch words one round of long
+ * lines may hold (0: the default, 256 MiB), so that a text of a few hundred KiB takes several rounds and a line of a few KiB meets the
+ * cap min(1 MiB, bytes / 4); and the launches of that walk since the process started (counting, -c and emitting rounds alike) */
+void krep_gpu_debug_set_regex_long_budget(uint64_t bytes);
+uint64_t krep_gpu_debug_regex_long_walks(void);
 /* a multi-pattern plan whose dictionary holds 1..3-byte patterns beside >= 8 longer ones: 0 not decided yet, 1 scanned as one dictionary, 2 split
  * (the long part anchored, the short part on its own, the record lists merged: kg_scan_ac.hip scan_ac_split); $KREP_GPU_AC_NO_SPLIT=1: never */
 int krep_gpu_debug_split_state(const krep_gpu_plan_t *plan);

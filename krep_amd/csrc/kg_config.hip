@@ -267,12 +267,21 @@ static int env_regex_groups()
     const char *e = getenv("KREP_GPU_REGEX_GROUPS");
     return e && *e && atoi(e) != 0 ? 1 : 0;
 }
+// ... and the linear walk of lines over 4096 bytes in a loops or groups search (include/krep_gpu.h, "Long lines"), likewise
+static int env_regex_long_lines()
+{
+    const char *e = getenv("KREP_GPU_REGEX_LONG_LINES");
+    return e && *e && atoi(e) != 0 ? 1 : 0;
+}
 namespace kg {
 std::atomic<int> g_regex_groups{env_regex_groups()};
 std::atomic<int> g_rl_force_general{0}; // test hook: a loops program is walked by the general step (kg_regex.hip, regex_prog_create)
 std::atomic<uint64_t> g_rl_general{0};  // launches of the line walk's general step (kg_regex_loops.hip)
 std::atomic<int> g_regex_loops{env_regex_loops()}; // (read when the library is loaded)
 std::atomic<int> g_regex_loops_windows{env_regex_loops_windows()};
+std::atomic<int> g_regex_long_lines{env_regex_long_lines()};
+std::atomic<uint64_t> g_rl_long_budget{0};         // test hook: bytes of C words a round of long lines may hold (0: the default)
+std::atomic<uint64_t> g_rl_long{0};                // launches of the long-line walk (kg_regex_loops.hip)
 std::atomic<int> g_rl_force_road{0};               // test hook: 0 auto, 1 the sparse road, 2 the dense road (kg_regex_loops.hip)
 std::atomic<uint64_t> g_rl_sparse{0}, g_rl_dense{0}; // scans that took each road
 }
@@ -282,6 +291,10 @@ extern "C" void krep_gpu_set_regex_loops_windows(int on) { kg::g_regex_loops_win
 extern "C" int krep_gpu_get_regex_loops_windows(void) { return kg::g_regex_loops_windows.load(std::memory_order_relaxed); }
 extern "C" void krep_gpu_set_regex_groups(int on) { kg::g_regex_groups.store(on != 0, std::memory_order_relaxed); }
 extern "C" int krep_gpu_get_regex_groups(void) { return kg::g_regex_groups.load(std::memory_order_relaxed); }
+extern "C" void krep_gpu_set_regex_long_lines(int on) { kg::g_regex_long_lines.store(on != 0, std::memory_order_relaxed); }
+extern "C" int krep_gpu_get_regex_long_lines(void) { return kg::g_regex_long_lines.load(std::memory_order_relaxed); }
+extern "C" void krep_gpu_debug_set_regex_long_budget(uint64_t bytes) { kg::g_rl_long_budget.store(bytes, std::memory_order_relaxed); }
+extern "C" uint64_t krep_gpu_debug_regex_long_walks(void) { return kg::g_rl_long.load(); }
 extern "C" void krep_gpu_debug_force_regex_general(int on) { kg::g_rl_force_general.store(on != 0); }
 extern "C" uint64_t krep_gpu_debug_regex_general_walks(void) { return kg::g_rl_general.load(); }
 extern "C" void krep_gpu_debug_force_regex_loops_road(int road) { kg::g_rl_force_road.store(road == 1 || road == 2 ? road : 0); }

@@ -219,6 +219,9 @@ extern std::atomic<int> g_regex_groups;                      // krep_gpu_set_reg
 extern std::atomic<uint64_t> g_rl_general;                   // krep_gpu_debug_regex_general_walks: launches of the line walk's general step
 extern std::atomic<int> g_rl_force_general;                  // krep_gpu_debug_force_regex_general: loops programs through the general step
 extern std::atomic<int> g_regex_loops_windows;               // krep_gpu_set_regex_loops_windows: a loops search is scanned in windows
+extern std::atomic<int> g_regex_long_lines;                  // krep_gpu_set_regex_long_lines: lines over 4096 bytes of a loops search are walked
+extern std::atomic<uint64_t> g_rl_long_budget;               // krep_gpu_debug_set_regex_long_budget: bytes of C words a round holds (0: default)
+extern std::atomic<uint64_t> g_rl_long;                      // krep_gpu_debug_regex_long_walks: launches of the long-line walk
 extern std::atomic<int> g_batch_max_count;                   // krep_gpu_set_batch_max_count: the batch takes a finite max_count
 extern std::atomic<int> g_rl_force_road;                     // krep_gpu_debug_force_regex_loops_road: 0 auto, 1 sparse, 2 dense
 extern std::atomic<uint64_t> g_rl_sparse, g_rl_dense;        // scans of kg_regex_loops.hip that took each road

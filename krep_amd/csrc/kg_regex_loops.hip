@@ -26,7 +26,9 @@
 // again and writes each record at its final index, the first max_count only.
 // Bounded work: a lane's worst case is quadratic in its line's length (a.*b on a line of a's).  The counting launch does not walk a
 // candidate line of more than 4096 bytes and raises Counters::overflow_units; the host reads that first and refuses the scan (2)
-// with nothing written.
+// with nothing written.  With krep_gpu_set_regex_long_lines on, the scan of the whole text lists those lines instead (rx_long_list) and
+// walks them in linear time by a backward and a forward pass (rx_long_walk, "long lines" below); the refusal stays for any other
+// window and for a line beyond min(1 MiB, budget / 4).
 // Windows (krep_gpu_set_regex_loops_windows; off: any window but the whole text is refused).  The kernel owns STARTS, not lines: a
 // line is looked at when it meets [own_lo, own_hi) (ls < own_hi && le > own_lo), its walk starts at the line's first byte — the
 // matches in front of own_lo say where the first owned attempt stands —, a match is counted or emitted when own_lo <= s < own_hi, and
@@ -290,6 +292,223 @@ template <bool GEN> static hipError_t rl_launch(const RlArgs &a, int mode, int n
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ long lines (krep_gpu_set_regex_long_lines)
+// What rx_line_walk leaves out, a candidate line of more than kRlMaxLine bytes in a scan of the whole text, walked in linear time
+// by two passes over the line [ls, le):
+//   backward: C[p] = T[text[p]] & (F(p) | pred(C[p + 1])), C[le] = 0, F(p) = fin where a match may end behind byte p (without $
+//     everywhere, with $ behind the line's last byte only), pred the reverse of the step.  By induction from the line's end C[p] holds
+//     exactly the places that take byte p and from there still reach an allowed end: C is EXACT, not an over-estimate.
+//   forward: an attempt at s starts with S = init & C[s] and steps S = follow(S) & C[p] (C[p] lies inside T[text[p]], so the text is
+//     not read again).  Every place of S reaches an end, so S is 0 directly behind the longest match's end and not before: an
+//     attempt costs its match's length plus one step, a start without a match one load.  n backward and at most about 2n forward
+//     steps, whatever the expression.
+// C is one u32 per line byte in global scratch (RxLoopsWork::d_C), a line's words at the offset the lister drew for it.  -c keeps
+// only the running word: a line holds a match iff some C[s] meets init (with ^: C[ls]).
+struct RlLong
+{
+    u64 *list;           // pairs (candidate line, its first C word counted over all listed lines), appended by rx_long_list
+    u64 list_cap, n;     // entries the list holds | entries it has
+    u32 *C;
+    u64 budget, round;   // a launch walks the entries whose first word lies in [round * budget, (round + 1) * budget)
+    u32 kept;            // EMIT: the counting launch's C words still stand (the one round of the scan), no backward pass
+};
+// line `line` of the candidate lines as rx_line_walk reads it
+struct RlSpan { u64 ls, le; };
+__device__ __forceinline__ RlSpan rl_line_span(const u64 *spans, u32 from_nl, u64 n_lines, u64 text_len, u64 line)
+{
+    u64 ls, le;
+    if (from_nl)
+    {
+        ls = line ? spans[2 * (line - 1)] + 1u : 0u;
+        le = line + 1 < n_lines ? spans[2 * line] : text_len;
+    }
+    else
+    {
+        ls = spans[2 * line];
+        le = spans[2 * line + 1];
+    }
+    le = le < text_len ? le : text_len; // (whatever a span says, no byte outside the text is read)
+    return RlSpan{ls < le ? ls : le, le};
+}
+// the lister: every candidate line rx_line_walk refused, and where its C words go (Counters::pad[1]: lines, pad[2]: the byte cursor,
+// max_unit_count: the longest of them).  Launched behind the counting launch, in front of the copy of the counters.  (A template
+// like the kernels around it, so that it stands behind rx_line_walk's instantiations in the code object.)
+template <class = void> __global__ __launch_bounds__(kBlock) void rx_long_list(const RlArgs a, const RlLong g)
+{
+    const u64 n_threads = (u64)gridDim.x * kBlock;
+    for (u64 line = (u64)blockIdx.x * kBlock + threadIdx.x; line < a.n_lines; line += n_threads)
+    {
+        const RlSpan sp = rl_line_span(a.spans, a.from_nl, a.n_lines, a.text_len, line);
+        const u64 len = sp.le - sp.ls;
+        if (len <= kRlMaxLine)
+            continue;
+        const u64 k = atomicAdd(&a.o.ctr->pad[1], 1ull), off = atomicAdd(&a.o.ctr->pad[2], (unsigned long long)len);
+        atomicMax(&a.o.ctr->max_unit_count, (unsigned long long)len);
+        if (k < g.list_cap)
+        {
+            g.list[2 * k] = line;
+            g.list[2 * k + 1] = off;
+        }
+    }
+}
+// the places that can stand in front of one of S: the reverse of the shift, or of rl_follow (the pairs in its groups of four)
+template <bool GEN> __device__ __forceinline__ u32 rl_pred(u32 S, u32 init, u32 self, const RlJumps &j)
+{
+    if (!GEN)
+        return ((S & ~init) >> 1) | (S & self);
+    u32 N = ((S >> 1) & j.chain) | (S & self);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        N |= (S & j.dst[k]) ? j.src[k] : 0u;
+    if (j.n > 4u)
+    {
+#pragma unroll
+        for (int k = 4; k < 8; ++k)
+            N |= (S & j.dst[k]) ? j.src[k] : 0u;
+    }
+    if (j.n > 8u)
+    {
+#pragma unroll
+        for (int k = 8; k < (int)kRegexGroupsMaxJumps; ++k)
+            N |= (S & j.dst[k]) ? j.src[k] : 0u;
+    }
+    return N;
+}
+// the backward pass over [ls, le): C[p - ls] written when C is not null; returns C[ls], and in *any whether some C[s] meets init
+template <bool GEN>
+__device__ __forceinline__ u32 rl_back(const RlArgs &a, const u32 *T, u32 *C, u64 ls, u64 le, bool eol, bool *any)
+{
+    u32 c = 0, seen = 0;
+    for (u64 p = le; p-- > ls;)
+    {
+        const u32 F = (!eol || p + 1 == le) ? a.fin : 0u;
+        c = T[(u32)a.text[p] << 5] & (F | rl_pred<GEN>(c, a.init, a.plus, a.j));
+        seen |= c;
+        if (C)
+            C[p - ls] = c;
+    }
+    *any = (seen & a.init) != 0u;
+    return c;
+}
+// One lane per listed line of this round, grid-stride over the list.  LINES, EMIT, GEN as in rx_line_walk; the window is the whole
+// text.  Counting: the line's count replaces the 0 rx_line_walk left in unitinfo[line] and joins ctr->total.
+template <bool LINES, bool EMIT, bool GEN>
+__global__ __launch_bounds__(kBlock) void rx_long_walk(const RlArgs a, const RlLong g)
+{
+    static_assert(!(LINES && EMIT), "-c writes no records");
+    __shared__ u32 s_T[256 * 32];
+    rx_fill_table(s_T, a.table);
+    const u32 *T = s_T + (lane_id() & 31u);
+    const u64 text_len = a.text_len;
+    const bool bol = (a.flags & 1u) != 0u, eol = (a.flags & 2u) != 0u, eot_ends = (a.flags & 4u) != 0u;
+    const u64 n_threads = (u64)gridDim.x * kBlock;
+    u64 mine = 0;
+    unsigned long long bits = 0;
+
+    for (u64 k = (u64)blockIdx.x * kBlock + threadIdx.x; k < g.n; k += n_threads)
+    {
+        const u64 line = g.list[2 * k], off = g.list[2 * k + 1];
+        if (off / g.budget != g.round)
+            continue;
+        const RlSpan sp = rl_line_span(a.spans, a.from_nl, a.n_lines, a.text_len, line);
+        const u64 ls = sp.ls, le = sp.le;
+        u32 *C = LINES ? nullptr : g.C + (off - g.round * g.budget); // (-c: no scratch, one round)
+        u32 cnt = 0;
+        if (!eol || le < text_len || eot_ends)
+        {
+            bool any = false;
+            if (LINES)
+            {
+                const u32 c0 = rl_back<GEN>(a, T, nullptr, ls, le, eol, &any);
+                cnt = (bol ? (c0 & a.init) != 0u : any) ? 1u : 0u;
+            }
+            else
+            {
+                if (!EMIT || !g.kept)
+                    (void)rl_back<GEN>(a, T, C, ls, le, eol, &any);
+                u64 idx = EMIT ? a.o.offsets[line] : 0;
+                u64 s = ls;
+                while (s < le)
+                {
+                    u32 S = C[s - ls] & a.init;
+                    u64 best = 0;
+                    if (S)
+                    {
+                        u64 p = s + 1; // S: the state behind byte p - 1
+                        for (;;)
+                        {
+                            if ((S & a.fin) != 0u && (!eol || p == le))
+                                best = p;
+                            if (p >= le)
+                                break;
+                            S = (GEN ? rl_follow(S, a.plus, a.j) : (((S << 1) & ~a.init) | (S & a.plus))) & C[p - ls];
+                            if (!S)
+                                break;
+                            ++p;
+                        }
+                    }
+                    if (best)
+                    {
+                        if (EMIT)
+                        {
+                            if (idx < a.o.pos_cap)
+                                rx_store_record(a.o.positions, idx, s + a.global_base, best + a.global_base);
+                            ++idx;
+                        }
+                        ++cnt;
+                    }
+                    if (bol)
+                        break;
+                    s = best ? best : s + 1;
+                }
+            }
+        }
+        if (EMIT)
+            continue;
+        mine += cnt;
+        if (LINES)
+        {
+            if (le < text_len || ls > 0)
+                bits |= kLnNl;
+            if (cnt)
+                bits |= (ls == 0 ? kLnHead : 0ull) | (le >= text_len ? kLnTail : 0ull);
+        }
+        else
+            a.o.unitinfo[line] = cnt;
+    }
+    if (EMIT)
+        return;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        mine += __shfl_xor(mine, o);
+    if (lane_id() == 0 && mine)
+    {
+        atomicAdd(&a.o.ctr->total, (unsigned long long)mine);
+        if (LINES)
+            atomicAdd(&a.o.ctr->lines, (unsigned long long)mine);
+    }
+    if (LINES && bits)
+        atomicOr(&a.o.ctr->summary, bits);
+}
+static u32 rl_long_grid(u64 n, int num_cu, u32 wg_per_cu)
+{
+    u32 grid = (u32)std::max<u64>(1, std::min<u64>((n + kBlock - 1) / kBlock, (u64)num_cu * wg_per_cu));
+    if (const int force = g_rx_force_grid.load(); force > 0)
+        grid = std::min<u32>(grid, (u32)force);
+    return grid;
+}
+static hipError_t rl_long_list_launch(const RlArgs &a, const RlLong &g, int num_cu, hipStream_t st); // (at the end of the file)
+// one round of the listed lines; 32 KiB of LDS a workgroup, like rx_line_walk
+template <bool GEN> static hipError_t rl_long_launch(const RlArgs &a, const RlLong &g, int mode, int num_cu, hipStream_t st)
+{
+    const dim3 grid(rl_long_grid(g.n, num_cu, 5)), block(kBlock);
+    g_rl_long.fetch_add(1, std::memory_order_relaxed); // (krep_gpu_debug_regex_long_walks)
+    if (mode == kRxLines) hipLaunchKernelGGL((rx_long_walk<true, false, GEN>), grid, block, 0, st, a, g);
+    else if (mode == kRxEmit) hipLaunchKernelGGL((rx_long_walk<false, true, GEN>), grid, block, 0, st, a, g);
+    else hipLaunchKernelGGL((rx_long_walk<false, false, GEN>), grid, block, 0, st, a, g);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ what a plan keeps between scans
 struct RxLoopsWork
 {
@@ -300,6 +519,10 @@ struct RxLoopsWork
     match_position_t *d_spans = nullptr; // sparse road: the candidate lines and (krep_gpu_matching_lines wants it) their first records
     uint64_t *d_first = nullptr;
     uint64_t span_cap = 0;
+    uint64_t *d_long = nullptr; // long lines: the lister's pairs
+    uint64_t long_cap = 0;      // in entries
+    uint32_t *d_C = nullptr;    // ... and the C words of a round
+    uint64_t c_cap = 0;         // in words
 };
 void rx_loops_work_free(RxLoopsWork *w)
 {
@@ -310,6 +533,8 @@ void rx_loops_work_free(RxLoopsWork *w)
     if (w->d_rec) (void)hipFree(w->d_rec);
     if (w->d_spans) (void)hipFree(w->d_spans);
     if (w->d_first) (void)hipFree(w->d_first);
+    if (w->d_long) (void)hipFree(w->d_long);
+    if (w->d_C) (void)hipFree(w->d_C);
     delete w;
 }
 // the inner plans, on the outer plan's device and with its configuration
@@ -354,10 +579,10 @@ static int rl_reserve_records(RxLoopsWork &wk, u64 need)
 }
 
 // the two refusals of a scan (Counters::overflow_units bit 0 and bit 1): nothing was written
-static int rl_refuse_long()
+static int rl_refuse_long(u32 max_line = kRlMaxLine)
 {
     return fail("regex with *, + or {n,}: a line of more than %u bytes: kept on krep's regex_search (a lane walks one line, and its "
-                "worst case is quadratic in the line's length)", kRlMaxLine);
+                "worst case is quadratic in the line's length)", max_line);
 }
 static int rl_refuse_cut()
 {
@@ -499,13 +724,77 @@ static int rl_dense_road(RlScan &s)
     }
     return 0;
 }
+// ---- long lines (krep_gpu_set_regex_long_lines): the steps rl_walk_passes adds with the switch on
+constexpr u64 kRlLongBudget = 256ull << 20; // bytes of C words a round may hold (krep_gpu_debug_set_regex_long_budget: another value)
+constexpr u64 kRlLongMaxLine = 1ull << 20;  // bytes of the longest line admitted: 4 MiB of C words in one lane's hands
+// Only the scan of the whole text takes long lines (the instantiations without WIN of rl_launch): the 4096 bytes of context a
+// window stages rest on the 4096-byte line rule
+static bool rl_long_on(const RlScan &s)
+{
+    return g_regex_long_lines.load(std::memory_order_relaxed) && s.a.own_lo == 0 && s.a.own_hi == s.a.text_len && (s.a.flags & 24u) == 24u;
+}
+static int rl_read_counters(RlScan &s)
+{
+    HIPCHK(hipMemcpyAsync(s.pl->h_ctr, s.pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s.st));
+    HIPCHK(hipStreamSynchronize(s.st));
+    return 0;
+}
+// room for the lister's pairs: a text holds at most text_len / (kRlMaxLine + 1) + 1 long lines
+static int rl_long_reserve_list(RlScan &s, RlLong *g)
+{
+    RxLoopsWork &wk = *s.pl->rx->work;
+    const u64 need = std::min<u64>(s.a.n_lines, s.a.text_len / (kRlMaxLine + 1) + 1);
+    HIPCHK(grow_scratch(wk.long_cap, need, need, {dev_buf(wk.d_long, need * 2 * sizeof(uint64_t))}));
+    g->list = (u64 *)wk.d_long;
+    g->list_cap = wk.long_cap;
+    return 0;
+}
+// What the lister counted (in the counters just read).  The refusal that stays: a line of more than min(1 MiB, budget / 4) bytes —
+// its C words alone would overrun a round.  Else the C scratch, never beyond the budget and the longest line, so that no line
+// straddles its end: a line's round is its first word / budget.
+static int rl_long_admit(RlScan &s, RlLong *g, u64 *rounds)
+{
+    RxLoopsWork &wk = *s.pl->rx->work;
+    const Counters &h = *s.pl->h_ctr;
+    const u64 set = g_rl_long_budget.load(std::memory_order_relaxed);
+    g->budget = std::max<u64>(1, (set ? set : kRlLongBudget) / sizeof(u32));
+    const u64 max_line = std::min<u64>(kRlLongMaxLine, g->budget);
+    if (h.max_unit_count > max_line)
+        return rl_refuse_long((u32)max_line);
+    g->n = std::min<u64>(h.pad[1], g->list_cap);
+    *rounds = (h.pad[2] - 1) / g->budget + 1;
+    const u64 need = std::min<u64>(h.pad[2], g->budget + h.max_unit_count);
+    HIPCHK(grow_scratch(wk.c_cap, need, need, {dev_buf(wk.d_C, need * sizeof(u32))}));
+    g->C = wk.d_C;
+    return 0;
+}
+// the listed lines round by round in one mode (-c keeps no C words: one launch takes them all)
+using RlLongLaunch = hipError_t (*)(const RlArgs &, const RlLong &, int, int, hipStream_t);
+static int rl_long_rounds(RlScan &s, RlLongLaunch launch, RlLong g, u64 rounds, int mode)
+{
+    if (mode == kRxLines)
+    {
+        g.budget = UINT64_MAX;
+        rounds = 1;
+    }
+    g.kept = mode == kRxEmit && rounds == 1;
+    for (g.round = 0; g.round < rounds; ++g.round)
+        HIPCHK(launch(s.a, g, mode, s.pl->num_cu, s.st));
+    return 0;
+}
 // Stage 2, the walk of the candidate lines: the counting launch (under -c the only one), the two refusals it can raise, and for a
-// caller that takes records the offsets pass and the emitting launch
+// caller that takes records the offsets pass and the emitting launch.  With long lines taken (rl_long_on) the lister runs behind
+// the counting launch, overflow_units bit 0 is a refusal only for a line beyond the cap, and the listed lines' rounds follow the
+// counting and the emitting launch on the same stream.
 static int rl_walk_passes(RlScan &s, bool lines, u64 want, match_position_t *d_pos, RlTotals *t)
 {
     krep_gpu_plan *pl = s.pl;
     RlArgs &a = s.a;
     const auto launch = !pl->rx->walk.general ? rl_launch<false> : rl_launch<true>; // (the old step first: its kernels keep their place in the code object)
+    const RlLongLaunch launch_long = !pl->rx->walk.general ? rl_long_launch<false> : rl_long_launch<true>; // (... and behind them these)
+    const bool take_long = rl_long_on(s);
+    RlLong g{};
+    u64 rounds = 0;
     if (!lines)
     {
         if (post_reserve(pl->post, a.n_lines, 0))
@@ -513,14 +802,25 @@ static int rl_walk_passes(RlScan &s, bool lines, u64 want, match_position_t *d_p
         a.o.unitinfo = pl->post.d_unitinfo;
         a.o.offsets = (const u64 *)pl->post.d_offsets;
     }
+    if (take_long && rl_long_reserve_list(s, &g))
+        return 2;
     HIPCHK(hipMemsetAsync(pl->d_ctr, 0, sizeof(Counters), s.st));
     HIPCHK(launch(a, lines ? kRxLines : kRxCount, pl->num_cu, s.st));
-    HIPCHK(hipMemcpyAsync(pl->h_ctr, pl->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, s.st));
-    HIPCHK(hipStreamSynchronize(s.st));
-    if (pl->h_ctr->overflow_units & 1ull)
+    if (take_long)
+        HIPCHK(rl_long_list_launch(a, g, pl->num_cu, s.st));
+    if (rl_read_counters(s))
+        return 2;
+    if ((pl->h_ctr->overflow_units & 1ull) && !take_long)
         return rl_refuse_long();
-    if (pl->h_ctr->overflow_units)
+    if (pl->h_ctr->overflow_units & ~1ull)
         return rl_refuse_cut();
+    if (pl->h_ctr->overflow_units)
+    {
+        if (const int rc = rl_long_admit(s, &g, &rounds))
+            return rc;
+        if (rl_long_rounds(s, launch_long, g, rounds, lines ? kRxLines : kRxCount) || rl_read_counters(s))
+            return 2;
+    }
     t->total = pl->h_ctr->total;
     t->nlines = pl->h_ctr->lines;
     t->summary = pl->h_ctr->summary;
@@ -531,6 +831,8 @@ static int rl_walk_passes(RlScan &s, bool lines, u64 want, match_position_t *d_p
         a.o.positions = (u64 *)d_pos;
         a.o.pos_cap = want;
         HIPCHK(launch(a, kRxEmit, pl->num_cu, s.st));
+        if (rounds && rl_long_rounds(s, launch_long, g, rounds, kRxEmit))
+            return 2;
         HIPCHK(hipStreamSynchronize(s.st));
     }
     return 0;
@@ -590,5 +892,11 @@ int scan_regex_loops(krep_gpu_plan *pl, const Window &w, match_position_t *d_pos
         return 2;
     rx_fill_out(pl, lines, t.total, t.nlines, t.summary, d_pos, cap, want, out);
     return 0;
+}
+// (here, so that the lister is the last kernel the file asks for: the older kernels keep their place in the code object)
+static hipError_t rl_long_list_launch(const RlArgs &a, const RlLong &g, int num_cu, hipStream_t st)
+{
+    hipLaunchKernelGGL(rx_long_list<>, dim3(rl_long_grid(a.n_lines, num_cu, 8)), dim3(kBlock), 0, st, a, g);
+    return hipGetLastError();
 }
 } // namespace kg

@@ -232,6 +232,15 @@ class Engine:
             L.krep_gpu_set_regex_loops_windows.argtypes = [C.c_int]
             L.krep_gpu_get_regex_loops_windows.restype = C.c_int
             L.krep_gpu_get_regex_loops_windows.argtypes = []
+        if hasattr(L, "krep_gpu_set_regex_long_lines"):  # (likewise)
+            L.krep_gpu_set_regex_long_lines.restype = None
+            L.krep_gpu_set_regex_long_lines.argtypes = [C.c_int]
+            L.krep_gpu_get_regex_long_lines.restype = C.c_int
+            L.krep_gpu_get_regex_long_lines.argtypes = []
+            L.krep_gpu_debug_set_regex_long_budget.restype = None
+            L.krep_gpu_debug_set_regex_long_budget.argtypes = [C.c_uint64]
+            L.krep_gpu_debug_regex_long_walks.restype = C.c_uint64
+            L.krep_gpu_debug_regex_long_walks.argtypes = []
         if hasattr(L, "krep_gpu_debug_force_regex_grid"):
             L.krep_gpu_debug_force_regex_grid.restype = None
             L.krep_gpu_debug_force_regex_grid.argtypes = [C.c_int]
@@ -510,6 +519,24 @@ class Engine:
 
     def get_regex_loops_windows(self) -> bool:
         return bool(self.lib.krep_gpu_get_regex_loops_windows())
+
+    def set_regex_long_lines(self, on: bool):
+        """krep_gpu_set_regex_long_lines: whether the one-window scan of a search the loops or the groups compiler took walks a
+        candidate line of more than 4096 bytes (two linear passes, kg_regex_loops.hip) instead of refusing the text (process-wide, off
+        by default, $KREP_GPU_REGEX_LONG_LINES=1 at load)"""
+        self.lib.krep_gpu_set_regex_long_lines(1 if on else 0)
+
+    def get_regex_long_lines(self) -> bool:
+        return bool(self.lib.krep_gpu_get_regex_long_lines())
+
+    def set_regex_long_budget(self, nbytes: int):
+        """test hook: the bytes of scratch words a round of long lines may hold (0: the default); the cap of one line is
+        min(1 MiB, nbytes / 4)"""
+        self.lib.krep_gpu_debug_set_regex_long_budget(int(nbytes))
+
+    def regex_long_walks(self) -> int:
+        """launches of the long-line walk since the process started"""
+        return int(self.lib.krep_gpu_debug_regex_long_walks())
 
     def force_regex_loops_road(self, road: int):
         """which road the loops scan finds its candidate lines by: 0 its own choice, 1 sparse (the filter's records), 2 dense (all lines)"""

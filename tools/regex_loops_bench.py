@@ -13,7 +13,13 @@ sum of the N hipEvent times, the count the sum of the windows' counts (under -c 
 `[a-z]+ck` by the old step and, tagged "general", by the general step (krep_gpu_debug_force_regex_general), and `(Sherlock|Watson)+`; on
 the word text `([a-z]+ )+ck`; on a third text, the same haystack generator with `192.168.10.254` planted every 10 000 bytes instead of
 `Sherlock`, the IP expression.  The output goes to profiles/regex_groups_scan.txt unless one is named.
-  usage: python tools/regex_loops_bench.py [--windows N] [--haystack] [--groups] [GiB = 8] [CPU MiB = 256] [output = profiles/regex_loops_scan.txt]"""
+--long-lines (with krep_gpu_set_regex_groups and krep_gpu_set_regex_long_lines on): the rows of the long-line walk instead (DESIGN
+§4.9, "Long lines").  (a) a JSONL-like text, every line 6 - 10 KiB of lower-case words, numbers and JSON punctuation with `ERROR`,
+`timeout` and `www.example.com` planted: `ERROR.*timeout` (the loops compiler's) and `([a-z]+\.)+com` (the groups compiler's), -c and
+records, both roads, and regex_search on the first CPU MiB of the same text — what such a text gets with the switch off.  (b) the
+kind-2 haystack as it is and with the newlines of 1 MiB - 8 KiB in its middle blanked, one line close to the longest admitted: `Sherlo+ck`,
+-c and records, both roads.  The output goes to profiles/regex_long_lines.txt unless one is named.
+  usage: python tools/regex_loops_bench.py [--windows N] [--haystack] [--groups] [--long-lines] [GiB = 8] [CPU MiB = 256] [output = profiles/regex_loops_scan.txt]"""
 import locale
 import os
 import statistics
@@ -42,9 +48,13 @@ if haystack_only:
 groups = "--groups" in sys.argv
 if groups:
     sys.argv.remove("--groups")
+long_lines = "--long-lines" in sys.argv
+if long_lines:
+    sys.argv.remove("--long-lines")
 gib = float(sys.argv[1]) if len(sys.argv) > 1 else 8.0
 cpu_mib = int(sys.argv[2]) if len(sys.argv) > 2 else 256
-out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "regex_groups_scan.txt" if groups else "regex_loops_scan.txt")
+default_out = "regex_long_lines.txt" if long_lines else "regex_groups_scan.txt" if groups else "regex_loops_scan.txt"
+out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", default_out)
 n = int(gib * (1 << 30))
 SEED, PERIOD = 42, 10000
 WORDS = wordlist.pack(wordlist.word_list())
@@ -99,9 +109,85 @@ def median_ms(plan, want_pos, parts=1):
         out = scan()
         if i >= warm:
             ms.append(out.kernel_ms)
+    median_ms.scans = 1 + warm + steady
     return statistics.median(ms), out
 
 
+def jsonl_text():
+    """the text of row (a) into buf, made on the device: lines of 6 - 10 KiB over lower-case letters, digits, blanks and JSON
+    punctuation, the three plants every 20 011 / 30 011 / 50 021 bytes (over whatever stands there, a newline included)"""
+    g = torch.Generator(device="cuda").manual_seed(20261021)
+    alphabet = torch.tensor(list(b'abcdefghijklmnopqrstuvwxyz0123456789    "":,.{}'), dtype=torch.uint8, device="cuda")
+    step = 1 << 28
+    for lo in range(0, n, step):
+        m = min(step, n - lo)
+        buf[lo:lo + m] = alphabet[torch.randint(0, alphabet.numel(), (m,), generator=g, device="cuda")]
+    ends = torch.cumsum(torch.randint(6144, 10241, (n // 6144 + 2,), generator=g, device="cuda"), 0)
+    buf[ends[ends < n]] = 10
+    for plant, period in ((b"ERROR", 20011), (b"timeout", 30011), (b"www.example.com", 50021)):
+        at = torch.arange(period, n - len(plant), period, device="cuda")
+        for k, c in enumerate(plant):
+            buf[at + k] = c
+    torch.cuda.synchronize()
+    return int((ends < n).sum().item())
+
+
+def long_rows(patterns, cpu_rows):
+    for pat, what in patterns:
+        for mode in ("-c", "records"):
+            kw = dict(count_lines=True) if mode == "-c" else dict()
+            for road, road_name in ROADS[1:]:
+                e.force_regex_loops_road(road)
+                plan = e.plan(abi.Params([pat], regex=True, **kw))
+                try:
+                    before = e.regex_long_walks()
+                    ms, out = median_ms(plan, mode == "records")
+                    say(f"regex    {pat.decode():<18} {mode:<8} {road_name:<8} {ms:10.3f} ms {n / ms / 1e6:8.2f} GB/s  "
+                        f"{'lines' if mode == '-c' else 'matches'} {out.count}  long-walk launches a scan {(e.regex_long_walks() - before) // median_ms.scans}  ({what})")
+                except KrepGpuError as err:
+                    say(f"regex    {pat.decode():<18} {mode:<8} {road_name:<8} refused: {err}")
+                finally:
+                    plan.close()
+                    e.force_regex_loops_road(0)
+    if cpu_rows and regex_ref.available():
+        m = min(n, cpu_mib << 20)
+        host = buf[:m].cpu().numpy()
+        say(f"# the reference's regex_search (compiled reference, glibc regexec, ONE thread) on the first {m >> 20} MiB of the same text")
+        for pat, _ in patterns:
+            for mode in ("count", "-c"):
+                kw = dict(count_lines=True) if mode == "-c" else dict(track_positions=False)
+                t0 = time.perf_counter()
+                ret, _ = regex_ref.call(pat, host, want_result=False, **kw)
+                dt = time.perf_counter() - t0
+                plan = e.plan(abi.Params([pat], regex=True, **kw))
+                got = plan.scan(buf.data_ptr(), m).count  # (the same slice as a text of its own on the device)
+                plan.close()
+                say(f"cpu      {pat.decode():<18} {mode:<8} {dt * 1e3:10.0f} ms {m / dt / 1e9:8.3f} GB/s  returned {ret}  "
+                    f"(the device on the same slice: {got}{'' if got == ret else ' DIFFERS'})")
+
+
+if long_lines:
+    e.set_regex_groups(True)
+    e.set_regex_long_lines(True)
+    say(f"# tools/regex_loops_bench.py --long-lines: {gib:g} GiB texts, hipEvent time of a whole scan, median of 10 steady scans after 2")
+    say("# warm-ups (3 after 1 beyond 0.5 s); GB/s = text bytes / time; krep_gpu_set_regex_long_lines on")
+    say(f"## (a) JSONL-like text, {jsonl_text()} lines of 6 - 10 KiB")
+    long_rows([(b"ERROR.*timeout", "loops"), (b"([a-z]+\\.)+com", "groups")], True)
+    for blank in (False, True):
+        e.generate(buf.data_ptr(), n, 0, 2, SEED, b"Sherlock", PERIOD)
+        if blank:
+            seg = buf[n // 2:n // 2 + (1 << 20) - 8192]
+            seg[seg == 10] = 32
+        torch.cuda.synchronize()
+        say(f"## (b) kind-2 haystack, `Sherlock` every 10 000 bytes" + (", the newlines of 1 MiB - 8 KiB in its middle blanked" if blank else ", as it is"))
+        long_rows([(b"Sherlo+ck", "loops")], False)
+    e.set_regex_long_lines(False)
+    e.set_regex_groups(False)
+    e.set_regex_loops(False)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(rows) + "\n")
+    sys.exit(0)
 say(f"# tools/regex_loops_bench.py: {gib:g} GiB texts, hipEvent time of a whole scan (filter scan, line analysis, line walk), median of 10")
 say("# steady scans after 2 warm-ups (3 after 1 beyond 0.5 s); GB/s = text bytes / time; ratio = to the literal plan for `Sherlock` in the")
 say("# same mode on the same buffer; road: forced, or auto with the road it took")
